@@ -16,11 +16,21 @@ into the N tiles (BASELINE config 4 = --gpus 4 --scaling strong: the 10 M-point 
 Each rank builds the graph of its core on its GPU; the tile-boundary edges are then stitched with two
 all-gather-v exchanges over RCCL (trg_planner/tiled.py; rule and parity oracle: DESIGN.md section 7).
 
-Beside the metric the line carries (rank 0): `ms_per_step_incl_upload` (the cloud handed over in pageable
-host memory, as TRG::setGlobalMap gets it), `updates` (--updates K: K setLocalMap + updateGraph steps of
-BASELINE config 5's stream on the built tile, with the CPU oracle's update beside it on the bounded tile),
-and `cpu_baseline` (the oracle on a bounded tile, 3 repetitions, AND on the full workload, one repetition
-in a child process on a core of its own while the GPU part runs).
+A plain run sets up, warms up, times the --steps builds, writes --dump-outputs and prints the result
+line (rank 0): the metric, `ms_per_step`, the workload's configuration and the per-step counters and
+roofline figures that the timed builds themselves record.
+
+--full adds, after the timed builds (rank 0's figures are reported): `ms_per_step_incl_upload` (the cloud
+handed over in pageable host memory, as TRG::setGlobalMap gets it), `updates` (--updates K: K setLocalMap +
+updateGraph steps of BASELINE config 5's stream on the built tile, with the CPU oracle's update beside it on
+the bounded tile), and `cpu_baseline` (the oracle on a bounded tile, 3 repetitions, AND on the full
+workload, one repetition in a child process on a core of its own while the GPU part runs).
+
+--dump-outputs DIR: the graph the last timed step built, as the caller of that step receives it
+(Engine.graph: node xyz / state / creation id, CSR rowptr / col, per-edge weight / dist) plus its sizes,
+one DIR/<name>.npy each (rank r of N > 1: DIR/rank<r>_<name>.npy), float32 as built, integers exactly in
+float64.  An array of more than DUMP_ROWS rows (DUMP_ROWS / N for N ranks) is written as the fixed, seeded
+sample of rows `dump_rows(n, DUMP_ROWS)`, so that everything stays under 64 MB.
 """
 import argparse
 import json
@@ -49,6 +59,68 @@ BOUNDED_N = 1200  # side of the bounded CPU-baseline tile (lattice points)
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable)
 MOUNTAIN = dict(expand_dist=0.6, robot_size=0.3, height_threshold=0.16, collision_threshold=0.1,
                 update_collision_threshold=0.5, safety_factor=3.0, goal_tolerance=0.8)
+DUMP_ROWS = 1 << 20  # --dump-outputs: longer arrays are written as a seeded sample of this many rows
+DUMP_SEED = 20250418
+DUMP_BYTES = 64 << 20
+
+
+def terrain_tile(ix0, ix1, iy0, iy1, seed):
+    """synth.mountain_tile(ix0, ix1, iy0, iy1, seed=seed), bit for bit, in a fraction of its time.
+
+    Every point is a function of its global lattice index, so bands of lattice rows are generated
+    on host threads (numpy lets go of the GIL inside its loops) straight into their place in row
+    order; mountain_tile's seeded shuffle then follows as one gather through Generator.permutation,
+    which draws the same swaps as Generator.shuffle (tests/test_bench_outputs.py holds the two equal)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from trg_planner import synth
+    nx = ix1 - ix0
+    out = np.empty((nx * (iy1 - iy0), 3), dtype=np.float32)
+    try:
+        ncpu = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        ncpu = os.cpu_count() or 1
+    nthreads = max(1, min(16, ncpu))
+    bands = np.linspace(iy0, iy1, 4 * nthreads + 1).round().astype(np.int64)
+
+    def band(j0, j1):
+        out[(j0 - iy0) * nx:(j1 - iy0) * nx] = synth.mountain_tile(ix0, ix1, j0, j1, seed=seed, shuffle=False)
+
+    with ThreadPoolExecutor(nthreads) as ex:
+        list(ex.map(band, bands[:-1].tolist(), bands[1:].tolist()))
+    rng = np.random.Generator(np.random.PCG64([seed & 0xFFFFFFFF, ix0 & 0xFFFFFFFF, iy0 & 0xFFFFFFFF]))
+    return out[rng.permutation(out.shape[0])]
+
+
+def dump_rows(n, max_rows):
+    """The rows of an n-row array that --dump-outputs writes: all of them, or a fixed, seeded,
+    sorted sample of max_rows when n is larger (the same rows for every array of n rows)."""
+    if n <= max_rows:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, max_rows, replace=False))
+
+
+def write_outputs(out_dir, arrays, max_rows=DUMP_ROWS, prefix=""):
+    """arrays: name -> array.  Written as out_dir/<prefix><name>.npy: float32 stays float32, every
+    other type goes to float64 (exact for the integers here); rows sampled by dump_rows.
+    Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+        rows = dump_rows(a.shape[0], max_rows) if a.ndim else None
+        if rows is not None:
+            a = a[rows]
+        a = np.ascontiguousarray(a)
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+        total += a.nbytes
+    return total
+
+
+def graph_outputs(g):
+    """What Engine.graph() hands its caller, by name."""
+    return {"sizes": np.array([g.V, g.E], np.float64), "xyz": g.xyz, "state": g.state, "cid": g.cid,
+            "rowptr": g.rowptr, "col": g.col, "w": g.w, "dist": g.dist}
 
 
 def kernel_source_sha():
@@ -205,13 +277,18 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed builds also measure the pageable-upload step, the update stream "
+                         "(--updates) and the CPU oracle baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the graph of the last timed step as DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baselines")
     ap.add_argument("--no-full-cpu-baseline", action="store_true",
-                    help="skip the one repetition of the CPU oracle on the full workload (a child process)")
+                    help="--full: skip the one repetition of the CPU oracle on the full workload (a child process)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1: weak = every rank a workload-sized tile; strong = the one cloud cut into N tiles")
     ap.add_argument("--updates", type=int, default=20,
-                    help="K setLocalMap + updateGraph steps after the timed builds (BASELINE config 5's stream)")
+                    help="--full: K setLocalMap + updateGraph steps after the timed builds (BASELINE config 5's stream)")
     ap.add_argument("--seed", type=int, default=20250418)
     ap.add_argument("--oracle-full-child", nargs=4, metavar=("NX", "NY", "S", "OUT"), help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -219,10 +296,12 @@ def main():
         nxc, nyc, Sc, outp = args.oracle_full_child
         oracle_full_child(int(nxc), int(nyc), int(Sc), args.seed, outp)
         return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     rank0_env = int(os.environ.get("RANK", "0")) == 0
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     full_child, full_out = None, None
-    if (rank0_env and world_env == 1 and not args.no_cpu_baseline and not args.no_full_cpu_baseline
+    if (args.full and rank0_env and world_env == 1 and not args.no_cpu_baseline and not args.no_full_cpu_baseline
             and args.workload != "c1"):
         # started before this process touches the GPU; runs on a core of its own while the GPU part runs
         import subprocess
@@ -290,7 +369,7 @@ def main():
         core = np.array([0.0, 0.0, 40.0, 30.0], np.float32)
         lattice_hi = (400, 300)
     else:
-        cloud = synth.mountain_tile(*win, seed=args.seed)
+        cloud = terrain_tile(*win, seed=args.seed)
     d_cloud = torch.from_numpy(cloud).to(dev)  # inputs resident in HBM before the timed region
     n_pts = cloud.shape[0]
     start = [0.5 * float(core[0] + core[2]), 0.5 * float(core[1] + core[3]), 0.0]
@@ -342,6 +421,11 @@ def main():
     fence()
     dt = time.perf_counter() - t0
 
+    if args.dump_outputs:  # the graph of the last timed step, before anything else runs on the engine
+        nbytes = write_outputs(args.dump_outputs, graph_outputs(eng.graph("global" if world == 1 else "stitched")),
+                               max_rows=DUMP_ROWS // world, prefix=f"rank{rank}_" if world > 1 else "")
+        assert nbytes * world <= DUMP_BYTES, nbytes
+
     # ---- the same step with the cloud handed over in pageable host memory (setGlobalMap's real input) --------
     def step_upload():
         eng.set_global_map(h_cloud)
@@ -349,7 +433,7 @@ def main():
         eng.init_graph(start)
         return ms_up
 
-    fast = bool(os.environ.get("TRG_BENCH_FAST"))  # (A/B scripts: the metric only)
+    fast = not args.full or bool(os.environ.get("TRG_BENCH_FAST"))  # (A/B scripts: the metric only)
     ms_incl_upload, ms_upload_only = None, [0.0]
     if not fast:
         step_upload()
@@ -436,12 +520,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * dt / max(1, args.steps), "higher_is_better": True,
             "scaling": args.scaling if world > 1 else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "ms_per_step_incl_upload": ms_incl_upload,
-            "upload": {"ms_per_step": ms_incl_upload, "ms_upload_median": float(np.median(ms_upload_only)),
-                       "bytes": int(n_pts) * 12,
-                       "note": "the cloud in pageable host memory (numpy), staged through pinned chunks by 4 host "
-                               "threads + hipMemcpyAsync; `value` / `ms_per_step` keep the cloud resident in HBM"},
-            "updates": upd_info,
+            "full": args.full,
             "config": {
                 "workload": label, "points_per_gpu": n_pts, "V_prime": V, "E_prime": E,
                 "voxel_filter": voxel_info,
@@ -488,7 +567,15 @@ def main():
                 "fallback_reason": eng.fallback_reason,
             },
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            out["ms_per_step_incl_upload"] = ms_incl_upload
+            out["upload"] = {"ms_per_step": ms_incl_upload, "ms_upload_median": float(np.median(ms_upload_only)),
+                             "bytes": int(n_pts) * 12,
+                             "note": "the cloud in pageable host memory (numpy), staged through pinned chunks by 4 "
+                                     "host threads + hipMemcpyAsync; `value` / `ms_per_step` keep the cloud resident "
+                                     "in HBM"}
+            out["updates"] = upd_info
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb = cpu_baseline(S, updates=min(args.updates, 10), seed=args.seed,
                               given=(h_cloud, dict(PRM, sample_num=S), start) if args.workload == "c1" else None)
             cb["bounded_sample_value"] = cb["value"]

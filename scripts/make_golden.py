@@ -8,6 +8,8 @@
   trg_golden.npz   -- oracle outputs (isCollision / nearest-z / edge risk probes and full
                       initGraph dumps for mountain-like and indoor-like parameters) with every
                       spatial query routed through the reference kdtree.c.
+  pybind_surface.json -- (--pybind-surface <reference tree>) the names the reference's Python
+                      binding defines, per class / enum.
 These are data (inputs + expected outputs); no reference source text is stored.
 """
 import ctypes as C
@@ -165,7 +167,23 @@ def make_trg_golden():
           "status hist", np.bincount(st, minlength=5))
 
 
+def make_pybind_surface(ref_tree):
+    """pybind_surface.json -- the class / enum names of the reference's Python binding
+    (python/trg_planner/pybind/trg_planner_pybind.cpp) with the names each one defines, in order."""
+    import json
+    import re
+    src = open(os.path.join(ref_tree, "python", "trg_planner", "pybind", "trg_planner_pybind.cpp")).read()
+    found = {}
+    for b in re.split(r"py::(?:class_|enum_)<", src)[1:]:
+        found[re.search(r'\(m,\s*"(\w+)"\)', b).group(1)] = re.findall(r'\.(?:def|def_readwrite|value)\("(\w+)"', b)
+    json.dump(found, open(os.path.join(GOLD, "pybind_surface.json"), "w"), indent=1)
+    print("pybind_surface.json", {k: len(v) for k, v in found.items()})
+
+
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
+    if len(sys.argv) == 3 and sys.argv[1] == "--pybind-surface":  # the reference tree's root
+        make_pybind_surface(sys.argv[2])
+        sys.exit(0)
     make_kd_golden()
     make_trg_golden()

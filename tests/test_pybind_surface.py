@@ -1,15 +1,16 @@
 """CPU: the compiled pybind11 module exposes the reference's Python surface for the graph engine
 (python/trg_planner/pybind/trg_planner_pybind.cpp:19-43), and the C++ shim under it
 (include/trg_shim.hpp) compiles, links and refuses to run without a GPU."""
+import json
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_PYBIND = "/root/reference/python/trg_planner/pybind/trg_planner_pybind.cpp"
+# the reference's binding surface, read out of its trg_planner_pybind.cpp by scripts/make_golden.py --pybind-surface
+REF_SURFACE = os.path.join(ROOT, "tests", "golden", "pybind_surface.json")
 
 # the surface of trg_planner_pybind.cpp, by line of that file
 EXPECTED = {
@@ -35,14 +36,9 @@ def test_module_is_compiled_and_has_the_reference_surface():
         c = getattr(trg_planner, cls)
         for n in names:
             assert hasattr(c, n), (cls, n)
-    if os.path.exists(REF_PYBIND):  # the list above IS the reference's (checked where it is present)
-        src = open(REF_PYBIND).read()
-        blocks = re.split(r"py::(?:class_|enum_)<", src)[1:]
-        found = {}
-        for b in blocks:
-            name = re.search(r'\(m,\s*"(\w+)"\)', b).group(1)
-            found[name] = re.findall(r'\.(?:def|def_readwrite|value)\("(\w+)"', b)
-        assert found == EXPECTED, found
+    with open(REF_SURFACE) as f:  # the list above IS the reference's
+        found = json.load(f)
+    assert found == EXPECTED, found
 
 
 def test_edge_node_semantics():
