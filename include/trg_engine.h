@@ -314,6 +314,30 @@ TrgStatus trg_engine_stitch_exchange(TrgEngine *e, const float core_xyxy[4], int
 /* why the last build fell back from the device path to the host replay ("" if it did not) */
 const char *trg_engine_fallback_reason(const TrgEngine *e);
 
+/* ---- cost field (an extension, DESIGN.md section 2 "Cost field"; the reference has no such call) ------
+ * The least risk cost from one node to EVERY node of the global graph, on the device.  An edge u->v costs
+ * (safety_factor * weight + 1) * dist, each operation rounded to fp32 (the A* step of trg.cpp:674); a walk's
+ * cost is the left fold g' = g + c in fp32; walks never enter an Invalid node (trg.cpp:670).  A node's key
+ * is (cost, hops), compared lexicographically; the result equals a host Dijkstra on that key bit for bit.
+ *   cost[v]    least cost, +inf if unreachable
+ *   hops[v]    hop count of that key, -1 if unreachable
+ *   parent[v]  smallest u with an edge u->v whose extension of u's key is v's key; -1 for the source and
+ *              for unreachable nodes
+ * Source: source_id >= 0, or, with source_id == -1, the node planSafePath starts from for source_xy.
+ * The output arrays are host memory of num_nodes entries; any of them may be NULL.
+ * TRG_ERR_NO_GRAPH on an empty graph; TRG_ERR_INVALID_ARG for a source out of range or when an edge cost
+ * is negative or not finite; TRG_ERR_DEVICE if the relaxation does not converge. */
+typedef struct TrgFieldInfo {
+  int32_t source;     /* the resolved source node */
+  int32_t reached;    /* nodes with a finite key */
+  int32_t rounds;     /* relaxation rounds that did work */
+  int32_t host_syncs; /* times the host waited for the device */
+  double ms_device;   /* hipEvent time of the solve */
+  double ms_total;    /* host wall time, upload of a stale CSR and downloads included */
+} TrgFieldInfo;
+TrgStatus trg_engine_cost_field(TrgEngine *e, int32_t source_id, const float source_xy[2],
+                                float *cost, int32_t *hops, int32_t *parent, TrgFieldInfo *info);
+
 /* ---- instrumentation ------------------------------------------------------------------------- */
 TrgStatus trg_engine_get_stats(const TrgEngine *e, TrgStats *out);
 /* the direction table the engine uses (2^table_bits entries each) */

@@ -1,0 +1,138 @@
+"""CPU: the host Dijkstra of the cost field (tests/cpp/field_reference.cpp, the GPU tests' yardstick) against a
+tiny pure-Python restatement of the definition -- a Bellman-Ford on the cost, then a BFS over the tight edges,
+every operation in numpy float32 -- on random small graphs with zero-cost and sub-ulp-cost edges, directed-only
+and duplicate edges, Invalid nodes and disconnected parts.  cost (as bits), hops and parent must be equal."""
+import numpy as np
+import pytest
+
+import field_ref
+
+F32 = np.float32
+INVALID = -1
+
+
+def _py_field(V, rowptr, col, w, dist, state, sf, src):
+    """The definition, restated apart from any Dijkstra: cost = the least fp32 fold over all walks (a
+    Bellman-Ford on the cost alone: fl(a + c) is monotone in a); hops = the BFS depth of the tight subgraph
+    (edges with fl(cost[u] + c) == cost[v]); parent = the smallest tight u with hops[u] + 1 == hops[v]."""
+    sf = F32(sf)
+    ec = [(sf * F32(w[k]) + F32(1.0)) * F32(dist[k]) for k in range(len(col))]
+    edges = [(u, int(col[k]), ec[k]) for u in range(V) for k in range(rowptr[u], rowptr[u + 1])
+             if state[int(col[k])] != INVALID]
+    cost = [None] * V
+    cost[src] = F32(0.0)
+    changed = True
+    while changed:
+        changed = False
+        for u, v, c in edges:
+            if cost[u] is not None and (cost[v] is None or F32(cost[u] + c) < cost[v]):
+                cost[v] = F32(cost[u] + c)
+                changed = True
+    tight = [(u, v) for u, v, c in edges if cost[u] is not None and F32(cost[u] + c) == cost[v]]
+    hops = [-1] * V
+    hops[src] = 0
+    level = [src]
+    while level:
+        nxt = sorted({v for u, v in tight if u in level and hops[v] < 0})
+        for v in nxt:
+            hops[v] = hops[level[0]] + 1
+        level = nxt
+    parent = [-1] * V
+    for u, v in tight:
+        if v != src and hops[u] + 1 == hops[v] and (parent[v] < 0 or u < parent[v]):
+            parent[v] = u
+    cost = np.array([np.inf if c is None else c for c in cost], np.float32)
+    return cost, np.array(hops, np.int32), np.array(parent, np.int32)
+
+
+def _random_graph(rng, V):
+    """Edges: a symmetric core, directed-only extras, duplicates with other weights, zero-dist edges and
+    sub-ulp costs; two components (ids >= V // 2 + 3 only link among themselves); a few Invalid nodes."""
+    edges = []
+    half = V // 2 + 3
+    for _ in range(3 * V):
+        a = int(rng.integers(0, half))
+        b = int(rng.integers(0, half))
+        if a == b:
+            continue
+        w = F32(rng.choice([0.0, rng.uniform(0.1, 1.0)]))
+        d = F32(rng.choice([0.0, 1e-9, rng.uniform(0.3, 0.6), rng.uniform(100.0, 200.0)], p=[0.1, 0.1, 0.6, 0.2]))
+        edges.append((a, b, w, d))
+        r = rng.uniform()
+        if r < 0.6:
+            edges.append((b, a, w, d))  # symmetric
+        elif r < 0.8:
+            edges.append((a, b, F32(rng.uniform(0.1, 1.0)), d))  # duplicate, another weight
+    for _ in range(V):
+        a = int(rng.integers(half, V))
+        b = int(rng.integers(half, V))
+        if a != b:
+            edges.append((a, b, F32(rng.uniform(0.1, 1.0)), F32(rng.uniform(0.3, 0.6))))
+    state = np.zeros(V, np.int32)
+    state[rng.choice(V, size=max(1, V // 8), replace=False)] = INVALID
+    state[rng.choice(V, size=max(1, V // 8), replace=False)] = 1  # Frontier: an ordinary node here
+    order = sorted(range(len(edges)), key=lambda i: edges[i][0])  # rows in push order
+    rowptr = np.zeros(V + 1, np.int32)
+    for i in order:
+        rowptr[edges[i][0] + 1] += 1
+    rowptr = np.cumsum(rowptr).astype(np.int32)
+    col = np.array([edges[i][1] for i in order], np.int32)
+    w = np.array([edges[i][2] for i in order], np.float32)
+    d = np.array([edges[i][3] for i in order], np.float32)
+    return rowptr, col, w, d, state
+
+
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    return field_ref.compile_reference(tmp_path_factory.mktemp("field_ref"))
+
+
+@pytest.mark.parametrize("seed", range(12))
+def test_reference_matches_python(ref, seed):
+    rng = np.random.default_rng(seed)
+    V = int(rng.integers(8, 48))
+    rowptr, col, w, d, state = _random_graph(rng, V)
+    sf = [3.0, 0.5, 1.0][seed % 3]
+    for src in (0, int(rng.integers(0, V)), V - 1):
+        st, cost, hops, parent = field_ref.field(ref, rowptr, col, w, d, state, sf, src)
+        assert st == 0
+        pc, ph, pp = _py_field(V, rowptr, col, w, d, state, sf, src)
+        assert np.array_equal(cost.view(np.uint32), pc.view(np.uint32)), (seed, src)
+        assert np.array_equal(hops, ph), (seed, src)
+        assert np.array_equal(parent, pp), (seed, src)
+        assert parent[src] == -1 and hops[src] == 0 and cost[src] == 0
+        # along the parents: a walk whose fold is the cost, bit for bit, with hops + 1 nodes
+        for v in np.flatnonzero(hops > 0):
+            chain = [int(v)]
+            while parent[chain[-1]] >= 0:
+                chain.append(int(parent[chain[-1]]))
+            assert chain[-1] == src and len(chain) == hops[v] + 1
+        # the second component is out of reach from the first
+        if src < V // 2 + 3:
+            assert np.all(hops[V // 2 + 3:] == -1) and np.all(np.isinf(cost[V // 2 + 3:]))
+
+
+def test_reference_sub_ulp_and_zero_cost():
+    """A chain whose big first edge swallows a sub-ulp step (cost stays equal, hops grow) and a zero-cost
+    shortcut: the hop word decides, the parent is the smallest id among equal extensions."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as td:
+        lib = field_ref.compile_reference(td)
+        # 0 -> 1 (cost 1e6), 1 -> 2 (1e-9: fl(1e6 + 1e-9) == 1e6), 0 -> 3 (1e6), 3 -> 2 (0), 2 -> 4 (1)
+        rows = {0: [(1, 0.0, 1e6), (3, 0.0, 1e6)], 1: [(2, 0.0, 1e-9)], 2: [(4, 0.0, 1.0)], 3: [(2, 0.0, 0.0)], 4: []}
+        rowptr, col, w, d = [0], [], [], []
+        for u in range(5):
+            for v, ww, dd in rows[u]:
+                col.append(v)
+                w.append(ww)
+                d.append(dd)
+            rowptr.append(len(col))
+        st, cost, hops, parent = field_ref.field(lib, rowptr, col, w, d, np.zeros(5, np.int32), 3.0, 0)
+        assert st == 0
+        assert cost[2] == F32(1e6) and hops[2] == 2 and parent[2] == 1  # ties of (cost, hops): smallest id
+        assert cost[4] == F32(1e6) + F32(1.0) and hops[4] == 3
+        # a negative cost is rejected, so is a bad source
+        st, *_ = field_ref.field(lib, rowptr, col, [-1.0] * len(w), d, np.zeros(5, np.int32), 3.0, 0)
+        assert st == field_ref.NO_EDGE
+        st, *_ = field_ref.field(lib, rowptr, col, w, d, np.zeros(5, np.int32), 3.0, 5)
+        assert st == field_ref.BAD_SOURCE

@@ -9,12 +9,13 @@ FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx9
 mkdir -p "$HERE/_obj"
 # (the kernels at -O2: measured 0.15-0.2 ms per C3 build faster than -O3, whose extra unrolling only adds register pressure)
 "$HIPCC" $FLAGS -O2 -c "$HERE/trg_kernels.hip" -o "$HERE/_obj/trg_kernels.o" "$@"
+"$HIPCC" $FLAGS -O2 -c "$HERE/trg_field.hip" -o "$HERE/_obj/trg_field.o"
 "$HIPCC" $FLAGS -c "$HERE/trg_engine.cpp" -o "$HERE/_obj/trg_engine.o"
 # the voxel filter pulls in rocPRIM's radix sort (slow to compile): rebuilt only when it changed
 if [ ! -f "$HERE/_obj/trg_voxel.o" ] || [ "$HERE/trg_voxel.hip" -nt "$HERE/_obj/trg_voxel.o" ] || [ "$HERE/trg_kernels.h" -nt "$HERE/_obj/trg_voxel.o" ]; then
   "$HIPCC" $FLAGS -c "$HERE/trg_voxel.hip" -o "$HERE/_obj/trg_voxel.o"
 fi
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$HERE/_obj/trg_kernels.o" "$HERE/_obj/trg_engine.o" "$HERE/_obj/trg_voxel.o" -o "$HERE/libtrg_engine.so"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$HERE/_obj/trg_kernels.o" "$HERE/_obj/trg_field.o" "$HERE/_obj/trg_engine.o" "$HERE/_obj/trg_voxel.o" -o "$HERE/libtrg_engine.so"
 echo "built $HERE/libtrg_engine.so"
 # pybind11 module trg_planner._trg_pybind: the reference's Python surface (TRG, Edge, NodeState, Node)
 # over include/trg_shim.hpp, i.e. over the C ABI of the library above

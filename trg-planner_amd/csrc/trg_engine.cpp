@@ -345,6 +345,7 @@ struct BfsBuffers;  // device-resident BFS state (trg_engine_bfs.inc)
 struct StitchBufs;  // scratch of the tile-boundary stitch (trg_engine_stitch.inc)
 struct Uploader;    // host cloud -> HBM staging (upload_and_build)
 struct ExchangeState;  // RCCL communicator + buffers of the native stitch exchange (trg_engine_exchange.inc)
+struct FieldBufs;      // device buffers of the cost field (trg_engine_field.ipp)
 
 }  // namespace
 
@@ -352,6 +353,7 @@ struct TrgEngine;
 namespace {
 TrgStatus stitch_fetch(TrgEngine *e);  // trg_engine_stitch.inc
 void exchange_release(TrgEngine *e);   // trg_engine_exchange.inc
+void field_release(TrgEngine *e);      // trg_engine_field.ipp
 }
 // Scratch of one A* search over the CSR.  open_check / close_list of the reference (trg.cpp:619-620,
 // unordered_maps keyed by node id) are flat arrays whose entries count only when their stamp equals the
@@ -475,6 +477,8 @@ struct TrgEngine {
   PlanScratch *plan_scratch = nullptr;
   Uploader *uploader = nullptr;
   ExchangeState *exchange = nullptr;  // host cloud -> HBM staging (upload_and_build)
+  FieldBufs *field = nullptr;    // cost field: work arrays, edge costs and uploaded CSR (cached per graph_version)
+  double field_delta_scale = 4.0;  // cost field: bucket width in mean edge costs (a measurement knob, see set_option)
   bool pool_valid = true;        // e->edges mirrors csr_global
   bool host_grid_valid = true;   // e->grid holds the current node set
   bool kd_order_dirty = false;   // kd_insert_order must be re-derived from order_map
@@ -893,6 +897,7 @@ void trg_engine_destroy(TrgEngine *e) {
       delete e->bfs;
     }
     exchange_release(e);
+    field_release(e);
     if (e->stitch) {
       e->stitch->release();
       delete e->stitch;
@@ -984,6 +989,7 @@ TrgStatus trg_engine_reset_graph(TrgEngine *e, TrgKind kind) {
     ensure_real_map(e);
     reset_graph_global(e);
     e->csr_global.clear();
+    field_release(e);
   }
   return TRG_OK;
 }
@@ -1155,6 +1161,12 @@ TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value
   }
   if (k == "keep_preclean") {
     e->keep_preclean = v != "0";
+    return TRG_OK;
+  }
+  if (k == "field_delta_scale") {  // measurement knob: cost-field bucket width in mean edge costs ("inf": Bellman-Ford)
+    const double d = strtod(v.c_str(), nullptr);
+    if (!(d > 0.0)) return e->fail(TRG_ERR_INVALID_ARG, "field_delta_scale must be > 0");
+    e->field_delta_scale = d;
     return TRG_OK;
   }
   return e->fail(TRG_ERR_INVALID_ARG, "unknown option " + k);
@@ -1395,6 +1407,7 @@ TrgStatus trg_engine_load_json(TrgEngine *e, const char *path) {
 }  // extern "C"
 
 #include "trg_engine_plan.ipp"
+#include "trg_engine_field.ipp"
 
 extern "C" {
 

@@ -1,0 +1,222 @@
+// Part of trg_engine.cpp (included at file scope): the cost field of the global graph -- the least (cost, hops)
+// key from one node to every node, on the device (kernels: trg_field.hip; an extension, the reference has no
+// such call) -- and its C ABI entry.
+
+namespace {
+
+// rounds enqueued between two looks at the pinned "work left" word
+constexpr int FIELD_BATCH = 32;
+
+// device buffers of the cost field, owned by the engine
+struct FieldBufs {
+  DevArr ec, stats, key, q0, q1, far0, far1, stamp_near, stamp_far, parent, cost, hops, ctrl;
+  DevArr up_rowptr, up_col, up_w, up_dist, up_state;  // csr_global + nstate when the device build's CSR is stale
+  uint64_t up_version = 0;   // graph_version of the upload (0: none)
+  uint64_t ec_version = 0;   // graph_version of the edge costs (0: none)
+  const void *ec_col = nullptr;  // ... and the column array they were computed from
+  float ec_sf = 0.0f;
+  double mean_cost = 0.0;    // over relaxable edges
+  bool bad_cost = false;
+  FieldState *h_state = nullptr;      // pinned
+  FieldEdgeStats *h_stats = nullptr;  // pinned
+  int *h_reached = nullptr;           // pinned
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  void release() {
+    for (DevArr *a : {&ec, &stats, &key, &q0, &q1, &far0, &far1, &stamp_near, &stamp_far, &parent, &cost, &hops,
+                      &ctrl, &up_rowptr, &up_col, &up_w, &up_dist, &up_state}) {
+      if (a->p) (void)hipFree(a->p);
+      a->p = nullptr;
+      a->bytes = 0;
+    }
+    if (h_state) (void)hipHostFree(h_state);
+    if (h_stats) (void)hipHostFree(h_stats);
+    if (h_reached) (void)hipHostFree(h_reached);
+    if (t0) (void)hipEventDestroy(t0);
+    if (t1) (void)hipEventDestroy(t1);
+    h_state = nullptr;
+    h_stats = nullptr;
+    h_reached = nullptr;
+    t0 = t1 = nullptr;
+    up_version = ec_version = 0;
+    ec_col = nullptr;
+  }
+};
+
+void field_release(TrgEngine *e) {
+  if (!e->field) return;
+  if (e->device_ok) {
+    (void)hipSetDevice(e->device);
+    (void)hipStreamSynchronize(e->s_main);
+  }
+  e->field->release();
+  delete e->field;
+  e->field = nullptr;
+}
+
+TrgStatus field_solve(TrgEngine *e, int32_t source_id, const float *source_xy, float *cost, int32_t *hops,
+                      int32_t *parent, TrgFieldInfo *info) {
+  const auto t_total = Clock::now();
+  TrgStatus st = plan_prepare(e);  // graph present, CSR rows and node grid current
+  if (st != TRG_OK) return st;
+  const int V = (int)e->nx.size();
+  int src = source_id;
+  if (source_id == -1) {
+    if (!source_xy) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no source");
+    src = plan_nearest_node(e, source_xy[0], source_xy[1], e->plan_scratch->tied);  // planSafePath's start node
+  }
+  if (src < 0 || src >= V) return e->fail(TRG_ERR_INVALID_ARG, "cost field: source out of range");
+  if (!e->field) e->field = new FieldBufs();
+  FieldBufs &fb = *e->field;
+  if (!fb.h_state) {
+    HIPCHK(e, hipHostMalloc((void **)&fb.h_state, sizeof(FieldState), hipHostMallocDefault));
+    HIPCHK(e, hipHostMalloc((void **)&fb.h_stats, sizeof(FieldEdgeStats), hipHostMallocDefault));
+    HIPCHK(e, hipHostMalloc((void **)&fb.h_reached, sizeof(int), hipHostMallocDefault));
+    HIPCHK(e, hipEventCreate(&fb.t0));
+    HIPCHK(e, hipEventCreate(&fb.t1));
+  }
+  hipStream_t s = e->s_main;
+  int syncs = 0;
+
+  // the graph on the device: the device build's CSR in place, else csr_global uploaded once per version
+  const Csr &G = e->csr_global;
+  const int E = G.rowptr.empty() ? 0 : G.rowptr[V];
+  const int *d_rowptr, *d_col, *d_state;
+  const float *d_w, *d_dist;
+  if (e->dev_csr_valid && e->bfs && e->bfs->d_rowptr_new) {
+    const BfsBuffers &bb = *e->bfs;
+    d_rowptr = bb.d_rowptr_new;
+    d_col = bb.d_col2;
+    d_w = bb.d_w2;
+    d_dist = bb.d_dist2;
+    d_state = bb.d_state2;
+  } else {
+    if (fb.up_version != e->graph_version) {
+      fb.up_version = 0;
+      if ((st = ensure_bytes(e, fb.up_rowptr, ((size_t)V + 1) * sizeof(int))) != TRG_OK) return st;
+      if ((st = ensure_bytes(e, fb.up_state, (size_t)V * sizeof(int))) != TRG_OK) return st;
+      if ((st = ensure_bytes(e, fb.up_col, (size_t)E * sizeof(int) + 16)) != TRG_OK) return st;
+      if ((st = ensure_bytes(e, fb.up_w, (size_t)E * sizeof(float) + 16)) != TRG_OK) return st;
+      if ((st = ensure_bytes(e, fb.up_dist, (size_t)E * sizeof(float) + 16)) != TRG_OK) return st;
+      HIPCHK(e, hipMemcpyAsync(fb.up_rowptr.p, G.rowptr.data(), ((size_t)V + 1) * sizeof(int),
+                               hipMemcpyHostToDevice, s));
+      HIPCHK(e, hipMemcpyAsync(fb.up_state.p, e->nstate.data(), (size_t)V * sizeof(int), hipMemcpyHostToDevice, s));
+      if (E) {
+        HIPCHK(e, hipMemcpyAsync(fb.up_col.p, G.col.data(), (size_t)E * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(fb.up_w.p, G.w.data(), (size_t)E * sizeof(float), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(fb.up_dist.p, G.dist.data(), (size_t)E * sizeof(float), hipMemcpyHostToDevice, s));
+      }
+      fb.up_version = e->graph_version;
+    }
+    d_rowptr = (const int *)fb.up_rowptr.p;
+    d_col = (const int *)fb.up_col.p;
+    d_w = (const float *)fb.up_w.p;
+    d_dist = (const float *)fb.up_dist.p;
+    d_state = (const int *)fb.up_state.p;
+  }
+  HIPCHK(e, hipEventRecord(fb.t0, s));
+
+  // edge costs and the bad-cost flag, once per graph version and safety factor
+  const float sf = e->prm.safety_factor;
+  if (fb.ec_version != e->graph_version || fb.ec_col != (const void *)d_col || fb.ec_sf != sf) {
+    fb.ec_version = 0;
+    if ((st = ensure_bytes(e, fb.ec, (size_t)E * sizeof(float) + 16)) != TRG_OK) return st;
+    if ((st = ensure_bytes(e, fb.stats, sizeof(FieldEdgeStats))) != TRG_OK) return st;
+    launch_field_edge_cost(d_col, d_w, d_dist, d_state, V, E, sf, (float *)fb.ec.p, (FieldEdgeStats *)fb.stats.p, s);
+    HIPCHK(e, hipMemcpyAsync(fb.h_stats, fb.stats.p, sizeof(FieldEdgeStats), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    syncs++;
+    fb.bad_cost = fb.h_stats->bad != 0;
+    fb.mean_cost = fb.h_stats->count ? fb.h_stats->sum / fb.h_stats->count : 0.0;
+    fb.ec_version = e->graph_version;
+    fb.ec_col = d_col;
+    fb.ec_sf = sf;
+  }
+  if (fb.bad_cost) return e->fail(TRG_ERR_INVALID_ARG, "cost field: an edge cost is negative or not finite");
+
+  // work arrays
+  const size_t nV = (size_t)V + 4;
+  if ((st = ensure_bytes(e, fb.key, nV * sizeof(unsigned long long))) != TRG_OK) return st;
+  for (DevArr *a : {&fb.q0, &fb.q1, &fb.far0, &fb.far1, &fb.stamp_near, &fb.stamp_far, &fb.parent, &fb.cost,
+                    &fb.hops})
+    if ((st = ensure_bytes(e, *a, nV * sizeof(int))) != TRG_OK) return st;
+  if ((st = ensure_bytes(e, fb.ctrl, sizeof(FieldCtrl))) != TRG_OK) return st;
+  FieldDev F{};
+  F.rowptr = d_rowptr;
+  F.col = d_col;
+  F.ec = (const float *)fb.ec.p;
+  F.V = V;
+  F.key = (unsigned long long *)fb.key.p;
+  F.q[0] = (int *)fb.q0.p;
+  F.q[1] = (int *)fb.q1.p;
+  F.far[0] = (int *)fb.far0.p;
+  F.far[1] = (int *)fb.far1.p;
+  F.stamp_near = (int *)fb.stamp_near.p;
+  F.stamp_far = (unsigned *)fb.stamp_far.p;
+  F.parent = (int *)fb.parent.p;
+  F.ctrl = (FieldCtrl *)fb.ctrl.p;
+
+  // near-far rounds, enqueued in batches; the bucket width is a fixed multiple of the mean edge cost.
+  // Pass 1 finds the least costs, pass 2 the hops over the tight edges (trg_field.hip).
+  const float delta = fb.mean_cost > 0.0 ? (float)(e->field_delta_scale * fb.mean_cost) : 0.0f;
+  const long long cap = 4LL * V + 64;
+  int rounds = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    F.tight = pass ? (const unsigned *)fb.cost.p : nullptr;
+    launch_field_init(F, src, delta, s);
+    for (int round = 0;;) {
+      for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s);
+      HIPCHK(e, hipGetLastError());
+      HIPCHK(e, hipMemcpyAsync(fb.h_state, &F.ctrl->s, sizeof(FieldState), hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipStreamSynchronize(s));
+      syncs++;
+      if (fb.h_state->overflow) return e->fail(TRG_ERR_DEVICE, "cost field: queue overflow");
+      if (fb.h_state->work == 0) break;
+      if (fb.h_state->rounds >= cap) return e->fail(TRG_ERR_DEVICE, "cost field did not converge");
+    }
+    rounds += fb.h_state->rounds;
+    if (pass == 0) launch_field_cost_bits(F, (unsigned *)fb.cost.p, s);
+  }
+  launch_field_finish(F, (float *)fb.cost.p, (int *)fb.hops.p, s);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipEventRecord(fb.t1, s));
+  HIPCHK(e, hipMemcpyAsync(fb.h_reached, &F.ctrl->c.reached, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (cost) HIPCHK(e, hipMemcpyAsync(cost, fb.cost.p, (size_t)V * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (hops) HIPCHK(e, hipMemcpyAsync(hops, fb.hops.p, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (parent) HIPCHK(e, hipMemcpyAsync(parent, fb.parent.p, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  syncs++;
+  float ms_dev = 0.0f;
+  HIPCHK(e, hipEventElapsedTime(&ms_dev, fb.t0, fb.t1));
+  info->source = src;
+  info->reached = *fb.h_reached;
+  info->rounds = rounds;
+  info->host_syncs = syncs;
+  info->ms_device = ms_dev;
+  info->ms_total = ms_since(t_total);
+  return TRG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+TrgStatus trg_engine_cost_field(TrgEngine *e, int32_t source_id, const float source_xy[2], float *cost,
+                                int32_t *hops, int32_t *parent, TrgFieldInfo *info) {
+  REQUIRE_DEVICE(e);
+  TrgFieldInfo local{};
+  if (!info) info = &local;
+  *info = TrgFieldInfo{};
+  info->source = -1;
+  if (source_id < -1) return e->fail(TRG_ERR_INVALID_ARG, "cost field: source out of range");
+  try {
+    return field_solve(e, source_id, source_xy, cost, hops, parent, info);
+  } catch (const std::bad_alloc &) {
+    return e->fail(TRG_ERR_CAPACITY, "cost field: out of host memory");
+  } catch (const std::exception &x) {
+    return e->fail(TRG_ERR_DEVICE, std::string("cost field: ") + x.what());
+  } catch (...) {
+    return e->fail(TRG_ERR_DEVICE, "cost field: unknown exception");
+  }
+}
+
+}  // extern "C"

@@ -1,0 +1,355 @@
+// trg_field.hip -- gfx950 kernels of the cost field: the least (cost, hops) key from one node to every node of
+// the global graph (an extension; the reference answers only single-pair queries, planSafePath trg.cpp:603-690).
+//
+// Semantics ("Cost field"): an edge costs (safety_factor * w + 1) * dist, every operation
+// rounded to fp32 (the A* step of trg.cpp:674 on OptimizeNode's float g_); a walk's cost is the left fold
+// g' = g + c in fp32; walks never enter an Invalid node (trg.cpp:670).  fl(a + c) is monotone in a and never
+// below a, so the least fold over all walks is one least fixed point that every relaxation order reaches.
+// The hop word is NOT monotone under rounding (a < a' can give fl(a + c) == fl(a' + c) with more hops on the
+// cheaper side), so a single label-correcting pass on (cost, hops) could keep the hops of a stale, dearer
+// prefix.  Hence two passes of the same relaxation:
+//   pass 1  keys (cost, hops) over all edges: the cost words are the least folds;
+//   pass 2  keys again, over "tight" edges only (fl(cost[u] + c) == cost[v]): every key now has its final cost,
+//           the hop extension h -> h + 1 is monotone, and the hops are the BFS depths of the tight subgraph --
+//           which is exactly what a host Dijkstra on the (cost, hops) key computes.
+//
+// Relaxation: near-far, label-correcting.  A round expands the near queue with one 16-lane group per node
+// (rows longer than 16 loop); an improved target goes to the next near queue when its cost is below the
+// bucket's threshold, else to the far pile.  A round that pushes nothing near opens the next bucket
+// [least live far cost, + delta) from the far pile.  Pushes are deduplicated by per-round / per-bucket
+// stamps and reserved with one atomicAdd per wave (ballot + prefix).  No launch waits for another
+// workgroup: sizes are read from device memory, the host enqueues rounds in batches.
+//
+// Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
+#include "trg_kernels.h"
+
+#include <limits.h>
+
+#include <algorithm>
+
+namespace trg {
+
+namespace {
+
+constexpr int WAVE = 64;
+constexpr int GROUP = 16;    // lanes per queued node
+constexpr int THREADS = 256;
+constexpr int MAX_BLOCKS = 512;
+
+__device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
+
+__device__ __forceinline__ unsigned long long ballot(bool pred) { return __builtin_amdgcn_ballot_w64(pred); }
+
+// the key of a walk extended by an edge of cost c: (fl(cost + c), hops + 1)
+__device__ __forceinline__ unsigned long long key_extend(unsigned long long k, float c) {
+  const float g = __uint_as_float((unsigned)(k >> 32)) + c;
+  return ((unsigned long long)__float_as_uint(g) << 32) | (unsigned)((unsigned)k + 1u);
+}
+
+__device__ __forceinline__ float key_cost(unsigned long long k) { return __uint_as_float((unsigned)(k >> 32)); }
+
+// The slot of this lane in a queue whose tail is *tail: one atomicAdd per wave for all its pushing lanes.
+// Called by every lane of the wave (convergent); the result is meaningful where pred.
+__device__ __forceinline__ int wave_reserve(bool pred, int *tail) {
+  const unsigned long long m = ballot(pred);
+  if (m == 0) return 0;
+  const int leader = __ffsll((unsigned long long)m) - 1;
+  int base = 0;
+  if (lane_id() == leader) base = atomicAdd(tail, __popcll(m));
+  base = __shfl(base, leader);
+  return base + __popcll(m & ((1ull << lane_id()) - 1ull));
+}
+
+// the next bucket's threshold above the least live far cost (strictly above it, whatever delta is)
+__device__ __forceinline__ float next_threshold(float fmin, float delta) {
+  const float t = fmin + delta;
+  return t > fmin ? t : __uint_as_float(__float_as_uint(fmin) + 1u);
+}
+
+__global__ __launch_bounds__(THREADS) void k_field_edge_cost(const int *__restrict__ col, const float *__restrict__ w,
+                                                             const float *__restrict__ dist,
+                                                             const int *__restrict__ state, int V, int E, float sf,
+                                                             float *__restrict__ ec, FieldEdgeStats *st) {
+  double sum = 0.0;
+  int cnt = 0, bad = 0;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < E; k += gridDim.x * blockDim.x) {
+    const float c = (sf * w[k] + 1.0f) * dist[k];
+    if (!(c >= 0.0f) || c == __builtin_huge_valf()) bad = 1;
+    const int v = col[k];
+    bool skip = v < 0 || v >= V;
+    if (!skip) skip = state[v] == FIELD_NODE_INVALID;
+    ec[k] = skip ? __uint_as_float(FIELD_EDGE_SKIP) : c;
+    if (!skip) {
+      sum += (double)c;
+      cnt++;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    sum += __shfl_xor(sum, m);
+    cnt += __shfl_xor(cnt, m);
+    bad |= __shfl_xor(bad, m);
+  }
+  if (lane_id() == 0) {
+    if (cnt) {
+      atomicAdd(&st->sum, sum);
+      atomicAdd(&st->count, cnt);
+    }
+    if (bad) atomicOr(&st->bad, 1);
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, int src, float delta) {
+  const int V = F.V;
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
+    F.key[v] = v == src ? 0ull : FIELD_KEY_NONE;
+    F.parent[v] = INT_MAX;
+    F.stamp_near[v] = 0;
+    F.stamp_far[v] = 0u;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    F.q[0][0] = src;
+    FieldCounters &c = F.ctrl->c;
+    c.n[0] = 1;
+    c.n[1] = 0;
+    c.nfar[0] = c.nfar[1] = 0;
+    c.fmin = ~0u;
+    c.overflow = 0;
+    c.reached = 0;
+    FieldState &s = F.ctrl->s;
+    s.work = 1;
+    s.rounds = 0;
+    s.overflow = 0;
+    s.thr = delta;
+    s.delta = delta;
+    s.phase = 1;
+    s.far_sel = 0;
+  }
+}
+
+// Expand the near queue of this round: one 16-lane group per queued node, four per wave.
+__global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, int stamp) {
+  const int n = min(F.ctrl->c.n[par], F.V);  // (past V only after an overflow, which the host then reports)
+  if (n == 0) return;
+  const float thr = F.ctrl->s.thr;
+  const unsigned phase = F.ctrl->s.phase;
+  const int fs = F.ctrl->s.far_sel;
+  const int V = F.V;
+  const int *__restrict__ q_cur = F.q[par];
+  int *q_next = F.q[par ^ 1];
+  int *far = F.far[fs];
+  int *next_tail = &F.ctrl->c.n[par ^ 1];
+  int *far_tail = &F.ctrl->c.nfar[fs];
+  const int sub = threadIdx.x & (GROUP - 1);
+  const int gw = lane_id() / GROUP;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  const int nwaves = gridDim.x * blockDim.x / WAVE;
+  constexpr int PER_WAVE = WAVE / GROUP;
+  for (int base = wave * PER_WAVE; base < n; base += nwaves * PER_WAVE) {  // (wave-uniform)
+    const int item = base + gw;
+    unsigned long long ku = 0;
+    int k = 0, kend = 0;
+    if (item < n) {
+      const int u = q_cur[item];
+      ku = F.key[u];
+      k = F.rowptr[u] + sub;
+      kend = F.rowptr[u + 1];
+    }
+    for (;; k += GROUP) {
+      const bool act = k < kend;
+      if (ballot(act) == 0) break;  // (wave-uniform: the longest row of the wave's four)
+      bool to_near = false, to_far = false;
+      int v = 0;
+      if (act) {
+        const float c = F.ec[k];
+        if (__float_as_uint(c) != FIELD_EDGE_SKIP) {
+          v = F.col[k];
+          const unsigned long long nk = key_extend(ku, c);
+          const bool tight = !F.tight || (unsigned)(nk >> 32) == F.tight[v];  // (pass 2: tight edges only)
+          if (tight && nk < F.key[v]) {  // plain load first: the atomic only on an improvement
+            const unsigned long long old = atomicMin(&F.key[v], nk);
+            if (nk < old) {
+              if (key_cost(nk) < thr)
+                to_near = atomicExch(&F.stamp_near[v], stamp) != stamp;
+              else
+                to_far = atomicExch(&F.stamp_far[v], phase) != phase;
+            }
+          }
+        }
+      }
+      const int sn = wave_reserve(to_near, next_tail);
+      if (to_near) {
+        if (sn < V) q_next[sn] = v;
+        else atomicOr(&F.ctrl->c.overflow, 1);
+      }
+      const int sf = wave_reserve(to_far, far_tail);
+      if (to_far) {
+        if (sf < V) far[sf] = v;
+        else atomicOr(&F.ctrl->c.overflow, 1);
+      }
+    }
+  }
+}
+
+// The least live cost of the far pile (live: not below the threshold; an entry below it was pushed near
+// and expanded since) -- only when this round's relaxation pushed nothing near.
+__global__ __launch_bounds__(THREADS) void k_field_far_min(FieldDev F, int par) {
+  if (F.ctrl->c.n[par ^ 1] != 0) return;
+  const int fs = F.ctrl->s.far_sel;
+  const int nf = min(F.ctrl->c.nfar[fs], F.V);
+  const float thr = F.ctrl->s.thr;
+  const int *__restrict__ far = F.far[fs];
+  unsigned best = ~0u;
+  const int n_iter = (nf + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
+    if (i < nf) {
+      const float c = key_cost(F.key[far[i]]);
+      if (c >= thr) best = min(best, __float_as_uint(c));  // (costs are >= +0: their bits order as they do)
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, m));
+  if (lane_id() == 0 && best != ~0u) atomicMin(&F.ctrl->c.fmin, best);
+}
+
+// Open the next bucket: live far entries below the new threshold go to the (empty) next near queue, the
+// rest to the other far pile, stamped with the next phase.
+// (Whether to split is told by fmin, which only k_field_far_min sets: the near-queue size changes here.)
+__global__ __launch_bounds__(THREADS) void k_field_far_split(FieldDev F, int par) {
+  const unsigned fminb = F.ctrl->c.fmin;
+  if (fminb == ~0u) return;
+  const int fs = F.ctrl->s.far_sel;
+  const int nf = min(F.ctrl->c.nfar[fs], F.V);
+  const float thr = F.ctrl->s.thr;
+  const float fmin = __uint_as_float(fminb);
+  const float thr_new = next_threshold(fmin, F.ctrl->s.delta);
+  const unsigned phase_new = F.ctrl->s.phase + 1u;
+  const int V = F.V;
+  const int *__restrict__ far = F.far[fs];
+  int *far_new = F.far[fs ^ 1];
+  int *q_next = F.q[par ^ 1];
+  const int n_iter = (nf + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
+    bool to_near = false, to_far = false;
+    int v = 0;
+    if (i < nf) {
+      v = far[i];
+      const float c = key_cost(F.key[v]);
+      if (c >= thr) {
+        to_near = c < thr_new || c == fmin;  // (c == fmin: a least cost of +inf still makes progress)
+        to_far = !to_near;
+      }
+    }
+    const int sn = wave_reserve(to_near, &F.ctrl->c.n[par ^ 1]);
+    if (to_near) {
+      if (sn < V) q_next[sn] = v;
+      else atomicOr(&F.ctrl->c.overflow, 1);
+    }
+    const int sf = wave_reserve(to_far, &F.ctrl->c.nfar[fs ^ 1]);
+    if (to_far) {
+      F.stamp_far[v] = phase_new;
+      if (sf < V) far_new[sf] = v;
+      else atomicOr(&F.ctrl->c.overflow, 1);
+    }
+  }
+}
+
+// One thread: the next near queue becomes the current one; a split switches the far pile and the bucket.
+__global__ void k_field_round_end(FieldDev F, int par) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  FieldCounters &c = F.ctrl->c;
+  FieldState &s = F.ctrl->s;
+  const bool worked = c.n[par] != 0;
+  c.n[par] = 0;
+  if (c.fmin != ~0u) {  // the bucket was opened from the far pile
+    c.nfar[s.far_sel] = 0;
+    s.far_sel ^= 1;
+    s.phase += 1u;
+    s.thr = next_threshold(__uint_as_float(c.fmin), s.delta);
+    c.fmin = ~0u;
+  } else if (c.n[par ^ 1] == 0) {
+    c.nfar[s.far_sel] = 0;  // converged: what is left in the far pile is stale
+  }
+  if (worked) s.rounds++;
+  s.work = c.n[par ^ 1];
+  s.overflow = c.overflow;
+}
+
+// Parents: the smallest u with an edge u -> v whose extension of key[u] is key[v].
+__global__ __launch_bounds__(THREADS) void k_field_parent(FieldDev F) {
+  const int sub = threadIdx.x & (GROUP - 1);
+  const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
+  const int ng = gridDim.x * blockDim.x / GROUP;
+  for (int u = g0; u < F.V; u += ng) {
+    const unsigned long long ku = F.key[u];
+    if (ku == FIELD_KEY_NONE) continue;
+    for (int k = F.rowptr[u] + sub, kend = F.rowptr[u + 1]; k < kend; k += GROUP) {
+      const float c = F.ec[k];
+      if (__float_as_uint(c) == FIELD_EDGE_SKIP) continue;
+      const int v = F.col[k];
+      if (key_extend(ku, c) == F.key[v]) atomicMin(&F.parent[v], u);
+    }
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void k_field_output(FieldDev F, float *cost, int *hops) {
+  const int V = F.V;
+  const int n_iter = (V + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, v = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, v += gridDim.x * blockDim.x) {
+    bool reached = false;
+    if (v < V) {
+      const unsigned long long k = F.key[v];
+      reached = k != FIELD_KEY_NONE;
+      cost[v] = reached ? key_cost(k) : __builtin_huge_valf();
+      hops[v] = reached ? (int)(unsigned)k : -1;
+      if (F.parent[v] == INT_MAX) F.parent[v] = -1;
+    }
+    const unsigned long long m = ballot(reached);
+    if (lane_id() == 0 && m) atomicAdd(&F.ctrl->c.reached, __popcll(m));
+  }
+}
+
+// pass 1 -> pass 2: the least costs as bits (unreached: ~0)
+__global__ __launch_bounds__(THREADS) void k_field_cost_bits(FieldDev F, unsigned *bits) {
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < F.V; v += gridDim.x * blockDim.x)
+    bits[v] = (unsigned)(F.key[v] >> 32);
+}
+
+int field_blocks(long long items, int per_block) {
+  const long long b = (items + per_block - 1) / per_block;
+  return (int)std::max(1ll, std::min<long long>(b, MAX_BLOCKS));
+}
+
+}  // namespace
+
+void launch_field_edge_cost(const int *col, const float *w, const float *dist, const int *state, int V, int E,
+                            float safety_factor, float *ec, FieldEdgeStats *st, hipStream_t s) {
+  (void)hipMemsetAsync(st, 0, sizeof(FieldEdgeStats), s);
+  if (E == 0) return;
+  hipLaunchKernelGGL(k_field_edge_cost, dim3(field_blocks(E, THREADS * 8)), dim3(THREADS), 0, s, col, w, dist,
+                     state, V, E, safety_factor, ec, st);
+}
+
+void launch_field_init(const FieldDev &F, int source, float delta, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS)), dim3(THREADS), 0, s, F, source, delta);
+}
+
+void launch_field_round(const FieldDev &F, int round, hipStream_t s) {
+  const int par = round & 1;
+  hipLaunchKernelGGL(k_field_relax, dim3(field_blocks((long long)F.V * GROUP, THREADS)), dim3(THREADS), 0, s, F,
+                     par, round + 1);
+  hipLaunchKernelGGL(k_field_far_min, dim3(field_blocks(F.V, THREADS)), dim3(THREADS), 0, s, F, par);
+  hipLaunchKernelGGL(k_field_far_split, dim3(field_blocks(F.V, THREADS)), dim3(THREADS), 0, s, F, par);
+  hipLaunchKernelGGL(k_field_round_end, dim3(1), dim3(64), 0, s, F, par);
+}
+
+void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_cost_bits, dim3(field_blocks(F.V, THREADS)), dim3(THREADS), 0, s, F, bits);
+}
+
+void launch_field_finish(const FieldDev &F, float *cost, int *hops, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS)), dim3(THREADS), 0, s, F);
+  hipLaunchKernelGGL(k_field_output, dim3(field_blocks(F.V, THREADS)), dim3(THREADS), 0, s, F, cost, hops);
+}
+
+}  // namespace trg

@@ -55,6 +55,11 @@ class TrgPathInfo(C.Structure):
                 ("num_points", C.c_int32)]
 
 
+class TrgFieldInfo(C.Structure):
+    _fields_ = [("source", C.c_int32), ("reached", C.c_int32), ("rounds", C.c_int32),
+                ("host_syncs", C.c_int32), ("ms_device", C.c_double), ("ms_total", C.c_double)]
+
+
 class TrgStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "map_points", "expanded_nodes", "trials", "samples", "created_nodes", "invalid_nodes",
@@ -91,7 +96,7 @@ EXPORTS = [
     "trg_engine_stitch_boundary", "trg_engine_stitch_cross", "trg_engine_stitch_assemble",
     "trg_engine_graph_sizes",
     "trg_engine_comm_unique_id", "trg_engine_comm_init", "trg_engine_comm_adopt", "trg_engine_comm_destroy",
-    "trg_engine_stitch_exchange",
+    "trg_engine_stitch_exchange", "trg_engine_cost_field",
 ]
 
 
@@ -172,6 +177,7 @@ def load_library():
     L.trg_engine_comm_destroy.argtypes = [vp]
     L.trg_engine_stitch_exchange.argtypes = [vp, fp, C.c_int32, C.c_int32, ip, ip]
     L.trg_engine_set_option.argtypes = [vp, C.c_char_p, C.c_char_p]
+    L.trg_engine_cost_field.argtypes = [vp, C.c_int32, fp, fp, ip, ip, C.POINTER(TrgFieldInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
     L.trg_engine_fallback_reason.restype = C.c_char_p
     _lib = L
@@ -387,6 +393,53 @@ class Engine:
         self._chk(self.L.trg_engine_plan_batch(self.h, _f(s), _f(g), m, _f(path), path_cap,
                                                off.ctypes.data_as(C.POINTER(C.c_int32)), infos))
         return [(path[off[k]:off[k + 1]].copy(), infos[k]) for k in range(m)]
+
+    def cost_field(self, source_xy=None, source_id=-1):
+        """Least risk cost from one node to every node of the global graph, on the GPU (DESIGN.md
+        section 2, "Cost field").  The source is node `source_id`, or, with source_id == -1, the node
+        planSafePath starts from for `source_xy`.  -> (cost float32 (+inf: unreachable), hops int32 (-1),
+        parent int32 (-1 for the source and unreachable nodes), TrgFieldInfo)."""
+        if source_id == -1 and source_xy is None:
+            raise ValueError("cost_field needs source_xy or source_id")
+        xy = None if source_xy is None else np.ascontiguousarray(source_xy, dtype=np.float32).reshape(2)
+        V, _ = self.graph_sizes("global")
+        cost = np.empty(V, np.float32)
+        hops = np.empty(V, np.int32)
+        parent = np.empty(V, np.int32)
+        info = TrgFieldInfo()
+        self._chk(self.L.trg_engine_cost_field(self.h, int(source_id), None if xy is None else _f(xy), _f(cost),
+                                               _i(hops), _i(parent), C.byref(info)))
+        self._field_source = int(info.source)
+        return cost, hops, parent, info
+
+    def field_path(self, parent, node, source=None):
+        """Node ids from the field's source to `node` along `parent` (of cost_field; `source` defaults to the
+        source of this engine's last cost_field).  Raises ValueError if `node` is unreachable."""
+        if source is None:
+            source = getattr(self, "_field_source", -1)
+        node = int(node)
+        path = [node]
+        while path[-1] != source:
+            p = int(parent[path[-1]])
+            if p < 0 or len(path) > len(parent):
+                raise ValueError(f"node {node} is not reachable from the field's source {source}")
+            path.append(p)
+        return path[::-1]
+
+    def cheapest_frontier(self, source_xy):
+        """The Frontier node that is cheapest to reach from `source_xy`: the least (cost, hops, id) among
+        Frontier nodes with a finite cost -> (node, cost, path ids) or None."""
+        cost, hops, parent, info = self.cost_field(source_xy=source_xy)
+        v = TrgCsrView()
+        self._chk(self.L.trg_engine_export_csr(self.h, KIND_GLOBAL, C.byref(v)))
+        if v.num_nodes == 0:
+            return None
+        state = np.ctypeslib.as_array(v.node_state, shape=(v.num_nodes,))
+        ids = np.flatnonzero((state == 1) & np.isfinite(cost) & (hops >= 0))
+        if ids.size == 0:
+            return None
+        best = int(ids[np.lexsort((ids, hops[ids], cost[ids]))[0]])
+        return best, float(cost[best]), self.field_path(parent, best, int(info.source))
 
     def check_reached(self, pos2d):
         p = np.ascontiguousarray(pos2d, dtype=np.float32)
