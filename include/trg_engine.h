@@ -162,8 +162,8 @@ typedef struct TrgStats {
                                   after a bounded inter-workgroup wait ran out */
   uint64_t bfs_multipass_rows; /* device path: sample slots whose blockers did not fit one row (taken in passes) */
   double ms_upload;            /* host cloud -> HBM of the last setGlobalMap / setLocalMap from a host pointer */
-  uint64_t presampled_nodes;   /* device path: expanded nodes whose samples were already there when their level's
-                                  sampling kernel started (drawn inside the previous level's resolve launch) */
+  uint64_t presampled_nodes;   /* always 0: the variant that drew samples inside the previous level's resolve
+                                  launch was removed; the field keeps the struct's layout */
 } TrgStats;
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
@@ -254,11 +254,10 @@ TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size
                                   float *out_xyz, size_t *n_out, int32_t *passthrough);
 
 /* ---- options ----------------------------------------------------------------------------------- */
-/* "replay" = "device" (default: BFS, dedupe and CSR on the GPU when expandGraph's step 3 is off,
- * trg.cpp:429) | "host" (sequential replay on the host, the only mode for step-3 configs);
- * "keep_preclean" = "0" | "1" (keep the TRG_KIND_PRECLEAN snapshot); "defer_overlap" = "1" | "0" | "2"
+/* "replay" = "device" (default: BFS, dedupe and CSR on the GPU) | "host" (sequential replay on the host);
+ * "keep_preclean" = "0" | "1" (keep the TRG_KIND_PRECLEAN snapshot); "defer_overlap" = "1" | "0"
  * (device BFS: deferred wireEdge evaluations pipelined behind the level loop on a second stream, one
- * batch per level -- default; 0: after the loop; 2: only pair-table inserts and selection beside the loop);
+ * batch per level -- default; 0: after the loop);
  * "tie_inplace" = "1" | "0" (device BFS: a nearest-node distance tie is settled for the affected slot alone on
  * the committed level -- off: the whole level is replayed on the host).  All modes give identical
  * graphs; the env var TRG_REPLAY=host sets the default.  Test hooks (never change results):
@@ -268,7 +267,9 @@ TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size
  * launches), "debug_fallback_level" = n (the device BFS declines at level n -> whole-build host
  * replay), "debug_stall_level" = n (k_level_resolve leaves one candidate of level n undecided ->
  * BFS_ERR_STALL -> the level is taken back and replayed on the host), "debug_lookback_level" = n (one
- * workgroup's commit look-back gives up at level n -> BFS_ERR_LOOKBACK -> whole-build host replay). */
+ * workgroup's commit look-back gives up at level n -> BFS_ERR_LOOKBACK -> whole-build host replay),
+ * "resolve_tickets" = "1" (every resolve launch takes its workgroup indices from start tickets -- by
+ * default only the repeat of a launch whose bounded wait ran out). */
 TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value);
 /* Tiled builds (multi-GPU; an extension, not a reference interface): restrict
  * node creation to the core region [x0,x1) x [y0,y1) -- a sample outside it counts as a rejected

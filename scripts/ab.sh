@@ -11,7 +11,7 @@ d = json.load(sys.stdin)
 b = d["breakdown_last_step"]
 print(sys.argv[1], round(d["ms_per_step"], 2), round(b["ms_bfs_loop"], 2), round(b["ms_deferred"], 2),
       round(b["ms_finalize_host"], 2), round(b["ms_set_map_total"], 2), round(b["ms_index_build_gpu"], 2),
-      b.get("presampled_nodes", ""), b.get("bfs_levels", ""))
+      b.get("bfs_levels", ""))
 PY
 specs=("$@")
 if [ ${#specs[@]} -eq 0 ]; then

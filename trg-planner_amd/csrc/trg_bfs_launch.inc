@@ -20,10 +20,7 @@ void launch_level_expand(const MapView &m, QueryParams p, const float *cos_t, co
   const int spec_slots = (count - node_base) * p.sample_num;
   if (which & 1) {
     // a level whose workgroups are all resident at once anyway takes 8-wave workgroups (twice the draws per round)
-    static const int wide_max = [] {
-      const char *v = getenv("TRG_SAMPLE_WIDE_MAX");
-      return v ? atoi(v) : 512;
-    }();
+    constexpr int wide_max = 512;
     if (count - node_base <= wide_max && 8 <= SW)
       hipLaunchKernelGGL(k_level_sample<8>, dim3(count - node_base), dim3(8 * WAVE), 0, s, m, p, cos_t, sin_t,
                          table_bits, seed, epoch, B, count, count_dev, node_base, parity, tag, pub_stamp, ctr);
@@ -39,45 +36,22 @@ void launch_level_expand(const MapView &m, QueryParams p, const float *cos_t, co
                        B.resc);
 }
 
-void launch_level_resolve_commit(const MapView &m, const BfsDev &B, QueryParams p, int count, int new_state,
+void launch_level_resolve_commit(const BfsDev &B, QueryParams p, int count, int new_state,
                                  long long call_base, int V0, int tag, int epoch, hipStream_t s,
-                                 int stall_test, bool ticketed, unsigned *ticket_base, const LevelNext &next) {
+                                 int stall_test, bool ticketed, unsigned *ticket_base) {
   if (count <= 0) return;
   const int slots = count * p.sample_num;
   // one 16-lane row per sample slot; a workgroup waits for lower-numbered slots / workgroups only
   const unsigned nR = (unsigned)((slots + RW - 1) / RW);
-  PNext pn{};
   const int max_spin = stall_test ? (1 << 10) : (1 << 16);
-  unsigned nP = 0;
-  if (next.count > 0 && next.tag != 0 && !ticketed) {
-    pn.node_rec = (NodeRec *)next.node_rec;
-    pn.slot_rec = (SlotRec *)next.slot_rec;
-    pn.parity = next.parity;
-    pn.tag = next.tag;
-    pn.max_polls = stall_test ? 256 : (1 << 13);
-    pn.cos_t = next.cos_t;
-    pn.sin_t = next.sin_t;
-    pn.table_bits = next.table_bits;
-    pn.seed = next.seed;
-    pn.epoch = next.epoch;
-    pn.ctr = next.ctr;
-    nP = (unsigned)next.count;
-  }
   const unsigned nC = (nR + CRW - 1) / CRW;  // commit workgroups: one thread per slot
   // sample_num > 32: a slot can have more blockers than its row holds at once (multi-pass variant)
   const bool multi = p.sample_num > 32;
-  const dim3 grid(ticketed ? nR + nC : nR + nC + nP), block(RWV * WAVE);
+  const dim3 grid(nR + nC), block(RWV * WAVE);
 #define TRG_LAUNCH_RESOLVE(T, M, S3)                                                                          \
-  do {                                                                                                        \
-    if (nP > 0)                                                                                               \
-      hipLaunchKernelGGL((k_level_resolve<T, M, S3, true>), grid, block, 0, s, B, count, p.sample_num,         \
-                         p.expand_dist, p.robot_size, tag, call_base, stall_test, max_spin, V0, new_state,     \
-                         epoch, (int)nR, (int)nC, ticketed ? *ticket_base : 0u, m, p, pn);                     \
-    else                                                                                                      \
-      hipLaunchKernelGGL((k_level_resolve<T, M, S3, false>), grid, block, 0, s, B, count, p.sample_num,        \
-                         p.expand_dist, p.robot_size, tag, call_base, stall_test, max_spin, V0, new_state,     \
-                         epoch, (int)nR, (int)nC, ticketed ? *ticket_base : 0u, m, p, pn);                     \
-  } while (0)
+  hipLaunchKernelGGL((k_level_resolve<T, M, S3>), grid, block, 0, s, B, count, p.sample_num, p.expand_dist,   \
+                     p.robot_size, tag, call_base, stall_test, max_spin, V0, new_state, epoch, (int)nR,       \
+                     (int)nC, ticketed ? *ticket_base : 0u)
   const bool s3 = B.resc != nullptr;  // expandGraph's step 3 is on
   const int variant = (ticketed ? 4 : 0) | (multi ? 2 : 0) | (s3 ? 1 : 0);
   switch (variant) {

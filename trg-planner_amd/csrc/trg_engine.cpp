@@ -464,10 +464,8 @@ struct TrgEngine {
   bool dev_csr_valid = false;    // the cleaned global CSR of the last device build is still in HBM
   StitchBufs *stitch = nullptr;
   bool keep_preclean = false;    // instrumentation: snapshot the graph before cleanGraph
-  bool use_device_bfs = true;    // device-resident BFS when expandGraph's step 3 is disabled
-  int defer_overlap = 1;         // 1: deferred edge evaluations pipelined behind the level loop on a 2nd stream;
-                                 // 2: only the pair-table inserts + first-of-pair selection run beside the loop
-                                 // (measured: the loop loses more than the pipeline gains; kept as an option)
+  bool use_device_bfs = true;    // device-resident BFS (off: host replay)
+  bool defer_overlap = true;     // deferred edge evaluations pipelined behind the level loop on a 2nd stream
   uint64_t graph_version = 1;    // bumped by everything that changes the global graph (queries cache per version)
   // planner state (A* runs straight on csr_global, see plan_on_csr): positions in the node tree's insertion
   // order for the rare order questions (nearest-node ties, several goal hits), and the search scratch
@@ -490,9 +488,6 @@ struct TrgEngine {
   int debug_stall_level = -1;    // test hook: k_level_resolve leaves one candidate of this level undecided
   bool debug_wait_rerun = false; // test hook: the ticketed repeat of that launch runs into the same hook
   bool debug_call_stride = false; // test hook: the sparse call log of step-3 builds on any configuration
-  bool step3_device = true;      // configurations with expandGraph's step 3 on the device-resident path too (off: host replay)
-  bool presample = false;        // pure part of the next level's expansion inside the resolve launch (p_role workgroups):
-                                 // measured +3 ms per C3 build (the 8-wave workgroups hold the places the resolve workgroups free)
   int resolve_tickets = 0;       // 1: every resolve launch takes its workgroup indices from start tickets (default: only
                                  // the repeat of a launch whose bounded wait ran out)
   float gate_margin = 1e-4f;     // band in which the slope gate is left to the host's libm
@@ -811,29 +806,11 @@ TrgStatus trg_engine_create(const TrgParams *params, int device, TrgEngine **out
   if (e->arch.rfind("gfx950", 0) != 0) {
     return e->fail(TRG_ERR_DEVICE, "kernels are built for gfx950 only, device is " + e->arch);
   }
-  {
-    int pr_least = 0, pr_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest);
-    if (getenv("TRG_MAIN_PRIO") && atoi(getenv("TRG_MAIN_PRIO")) != 0)  // (measurements) the level loop at the highest priority
-      HIPCHK(e, hipStreamCreateWithPriority(&e->s_main, hipStreamNonBlocking, pr_greatest));
-    else
-      HIPCHK(e, hipStreamCreateWithFlags(&e->s_main, hipStreamNonBlocking));
-    // TRG_EDGE_CU_MASK=n: the second stream is confined to n compute units (experiment)
-    const char *cm = getenv("TRG_EDGE_CU_MASK");
-    int ncu_edge = cm ? atoi(cm) : 0;
-    if (ncu_edge > 0) {
-      uint32_t mask[8] = {0};
-      const int stride = 256 / std::max(1, std::min(ncu_edge, 256));
-      for (int k = 0; k < ncu_edge && k * stride < 256; ++k) mask[(k * stride) / 32] |= 1u << ((k * stride) % 32);
-      HIPCHK(e, hipExtStreamCreateWithCUMask(&e->s_edge, 8, mask));
-    } else {
-      // the priority of the main stream (default; lowest leaves a longer tail after the loop: measured
-      // 0.5 ms slower); TRG_EDGE_PRIO=1 (measurements): lowest
-      const bool low = getenv("TRG_EDGE_PRIO") && atoi(getenv("TRG_EDGE_PRIO")) != 0;
-      HIPCHK(e, hipStreamCreateWithPriority(&e->s_edge, hipStreamNonBlocking, low ? pr_least : 0));
-    }
-    HIPCHK(e, hipStreamCreateWithFlags(&e->s_aux, hipStreamNonBlocking));
-  }
+  HIPCHK(e, hipStreamCreateWithFlags(&e->s_main, hipStreamNonBlocking));
+  // the deferred stream at the main stream's priority (the lowest leaves a longer tail after the loop:
+  // measured 0.5 ms slower)
+  HIPCHK(e, hipStreamCreateWithPriority(&e->s_edge, hipStreamNonBlocking, 0));
+  HIPCHK(e, hipStreamCreateWithFlags(&e->s_aux, hipStreamNonBlocking));
   HIPCHK(e, hipMalloc((void **)&e->d_ctr, COUNTER_SHARDS * sizeof(DeviceCounters)));
   HIPCHK(e, hipMemset(e->d_ctr, 0, COUNTER_SHARDS * sizeof(DeviceCounters)));
   HIPCHK(e, hipMalloc((void **)&e->d_bounds, 4 * sizeof(unsigned)));
@@ -844,8 +821,6 @@ TrgStatus trg_engine_create(const TrgParams *params, int device, TrgEngine **out
   e->stitch = new StitchBufs();
   e->uploader = new Uploader();
   if (const char *env = getenv("TRG_REPLAY")) e->use_device_bfs = std::string(env) != "host";
-  if (const char *env = getenv("TRG_PRESAMPLE")) e->presample = atoi(env) != 0;            // (A/B measurements)
-  if (const char *env = getenv("TRG_RESOLVE_TICKETS")) e->resolve_tickets = atoi(env);
   reset_graph_global(e);
   return TRG_OK;
 }
@@ -1013,10 +988,9 @@ TrgStatus trg_engine_init_graph(TrgEngine *e, const float start_xyz[3], const Tr
   // (in the main stream: it is non-blocking, a plain memset would not be ordered with the kernels)
   HIPCHK(e, hipMemsetAsync(e->d_ctr, 0, COUNTER_SHARDS * sizeof(DeviceCounters), e->s_main));
   e->lv_hits_sample = e->lv_hits_spec = 0;
-  const bool want_device = e->use_device_bfs && (!e->step3 || e->step3_device);
-  if (!want_device) ensure_real_map(e);
+  if (!e->use_device_bfs) ensure_real_map(e);
   MapOrderSim sim_before;  // container history as of before this build (for the fallback)
-  if (want_device) {
+  if (e->use_device_bfs) {
     if (!e->real_map_stale) e->nodes_sim.adopt_bucket_state(e->order_map);
     sim_before = e->nodes_sim;
   }
@@ -1054,7 +1028,7 @@ TrgStatus trg_engine_init_graph(TrgEngine *e, const float start_xyz[3], const Tr
     cnt++;
   }
 
-  if (want_device) {
+  if (e->use_device_bfs) {
     st = build_graph_device(e, rx, ry, rz);
     if (st == TRG_OK) {
       read_counters(e);
@@ -1120,7 +1094,9 @@ TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value
     return TRG_OK;
   }
   if (k == "defer_overlap") {
-    e->defer_overlap = atoi(v.c_str());
+    if (v == "1") e->defer_overlap = true;
+    else if (v == "0") e->defer_overlap = false;
+    else return e->fail(TRG_ERR_INVALID_ARG, "defer_overlap must be 0 or 1");
     return TRG_OK;
   }
   if (k == "debug_stall_level") {
@@ -1131,20 +1107,12 @@ TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value
     e->debug_lookback_level = atoi(v.c_str());
     return TRG_OK;
   }
-  if (k == "step3_device") {
-    e->step3_device = v != "0";
-    return TRG_OK;
-  }
   if (k == "debug_call_stride") {
     e->debug_call_stride = v != "0";
     return TRG_OK;
   }
   if (k == "debug_wait_rerun") {
     e->debug_wait_rerun = v != "0";
-    return TRG_OK;
-  }
-  if (k == "presample") {
-    e->presample = v != "0";
     return TRG_OK;
   }
   if (k == "resolve_tickets") {

@@ -94,7 +94,7 @@ struct BfsBuffers {
   FinDev F{};
   LevelSet lv[2];
   DevArr newid_of_call;
-  DevArr gcell, ncov, wg_state, nexp, nhits, fxy0, fxy1, def_counts, front_ready, tl, c_cell, s3_scratch;
+  DevArr gcell, ncov, wg_state, nexp, nhits, fxy0, fxy1, def_counts, tl, c_cell, s3_scratch;
   size_t cap_nx = 0, cap_ny = 0, cap_nz = 0, cap_nstate = 0;
   size_t cap_front0 = 0, cap_front1 = 0;
   size_t cap_mid = 0;
@@ -133,7 +133,7 @@ struct BfsBuffers {
                     B.call_status, B.call_w, B.call_dist, B.ctrs, B.stats64, flag, sel_flag, sel_off,
                     sel_list, sel_tmp, scan_tmp, F.ht_key, F.ht_seq, F.ok_seq, F.call_slot, F.deg, F.fill,
                     F.rowptr, F.col, F.seq, F.w, F.dist, d_new2old, d_old2new, d_deg_new,
-                    d_rowptr_new, d_col2, d_state2, d_w2, d_dist2, d_xyz2, newid_of_call.p, wg_state.p, nexp.p, nhits.p, fxy0.p, fxy1.p, def_counts.p, front_ready.p, tl.p, c_cell.p, s3_scratch.p,
+                    d_rowptr_new, d_col2, d_state2, d_w2, d_dist2, d_xyz2, newid_of_call.p, wg_state.p, nexp.p, nhits.p, fxy0.p, fxy1.p, def_counts.p, tl.p, c_cell.p, s3_scratch.p,
                     d_map_order, d_keep_flag, d_keep_pos};
     for (void *p : ptrs)
       if (p) (void)hipFree(p);
@@ -469,12 +469,6 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   ENSB(bb.c_cell, slots * sizeof(unsigned long long));
   B.c_cell = (unsigned long long *)bb.c_cell.p;
   HIPCHK(e, hipMemsetAsync(B.c_cell, 0, slots * sizeof(unsigned long long), s));  // (launch epochs start at 1 in every build)
-  ENSB(bb.front_ready, (fcap + 1) * sizeof(unsigned long long));
-  B.front_ready = (unsigned long long *)bb.front_ready.p;
-  HIPCHK(e, hipMemsetAsync(B.front_ready, 0, (fcap + 1) * sizeof(unsigned long long), s));  // (no tag is 0)
-  // a node record's stamp marks samples a p_role workgroup left for exactly this level attempt: tags
-  // start over in every build, so records of earlier builds must not carry any
-  for (LevelSet &l : bb.lv) HIPCHK(e, hipMemsetAsync(l.node_rec.p, 0, fcap * sizeof(NodeRec), s));
   ENSB(bb.nexp, vcap * sizeof(int4));
   B.nexp = (int4 *)bb.nexp.p;
   ENSB(bb.nhits, vcap * sizeof(int));
@@ -525,7 +519,7 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   // the next level's k_level_sample writes them into pinned host memory with the level's stamp; the host polls
   // the stamp.
   int &stamp_serial = bb.stamp_serial;  // monotonic over the engine's life: a stale block never matches
-  static const long poll_query_mask = getenv("TRG_POLL_QUERY_BITS") ? ((1L << atoi(getenv("TRG_POLL_QUERY_BITS"))) - 1) : 0xFFFFFL;
+  constexpr long poll_query_mask = 0xFFFFFL;
   auto wait_stamp = [&](int stamp) -> TrgStatus {
     auto t0 = Clock::now();
     volatile int *hv = bb.h_ctrs;
@@ -612,17 +606,15 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   F.ht_size = fht;
   // calls per batch (at least): about one batch per BFS level -- many small batches disturb the level
   // kernels least (measured: 3.2 M -> 54.6 ms per C3 build, 100 k -> 53.2, 6 k -> 51.6; no overlap 54.5)
-  static const long long DEF_BATCH_MIN =
-      getenv("TRG_DEF_BATCH") ? atoll(getenv("TRG_DEF_BATCH")) : 6000;
+  constexpr long long DEF_BATCH_MIN = 6000;
   const size_t sel_cap = (size_t)CALL_EVAL_BATCH + 2;
   ENS(bb.sel_flag, cap_selflag, sel_cap);
   ENS(bb.sel_off, cap_seloff, sel_cap + 1);
   ENS(bb.sel_tmp, cap_seltmp, sel_cap / 2048 + 16);
-  if (getenv("TRG_DEFER_OVERLAP")) e->defer_overlap = atoi(getenv("TRG_DEFER_OVERLAP"));  // (measurements)
   // With step 3 the neighbour calls of a node sit BEFORE later calls in the log but are only known after the
   // loop (trg_step3.inc): "first call of its pair" is not final level by level, so nothing is evaluated beside
   // the loop.
-  const int overlap = e->step3 ? 0 : e->defer_overlap;
+  const bool overlap = !e->step3 && e->defer_overlap;
   if (overlap) {  // (otherwise the table is cleared after the loop, right before its first use)
     HIPCHK(e, hipMemsetAsync(F.ht_key, 0xFF, (size_t)fht * sizeof(unsigned long long), s));
     HIPCHK(e, hipMemsetAsync(F.ht_seq, 0x7F, (size_t)fht * sizeof(int), s));
@@ -634,14 +626,7 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   constexpr int TIMED_BATCH_EVERY = 8;
   size_t n_eval_batches = 0;
   unsigned long long *d_def_total = B.stats64 + 5;  // calls the selections kept (device counter)
-  // defer_overlap == 2: only the pair-table inserts and the first-of-pair selection of finished levels
-  // run beside the level loop (light, atomics-bound kernels); the evaluations themselves follow after it
-  struct SelBatch {
-    long long lo, n;
-    int count_at;
-  };
-  std::vector<SelBatch> sel_batches;
-  ENSB(bb.def_counts, 1024 * sizeof(int));
+  ENSB(bb.def_counts, sizeof(int));  // round 2's count of selected calls
   auto eval_batch = [&](long long lo, long long n, const int *count_dev, hipStream_t st_) -> TrgStatus {
     hipEvent_t a = nullptr, b = nullptr;
     // (timed like the level kernels: every 8th batch, scaled up afterwards -- an event pair per batch was
@@ -662,23 +647,15 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   };
   // calls [def_lo, c1) of finished levels -> pair table, first-of-pair selection, evaluation
   auto launch_deferred = [&](long long c1, bool in_loop) -> TrgStatus {
-    const bool select_only = in_loop && overlap == 2;
     while (def_lo < c1) {
       const long long c_hi = std::min<long long>(c1, def_lo + CALL_EVAL_BATCH);
       const long long n = c_hi - def_lo;
       hipStream_t st_ = in_loop ? s_def : s;
       launch_first_insert(F, B, def_lo, c_hi, st_);
-      if (select_only && sel_batches.size() < 1024) {
-        int *cnt = (int *)bb.def_counts.p + sel_batches.size();
-        launch_calls_select(F, B, def_lo, c_hi, 1, bb.sel_flag, bb.sel_off, bb.sel_tmp, bb.sel_list + def_lo,
-                            d_def_total, st_, cnt);
-        sel_batches.push_back({def_lo, n, (int)sel_batches.size()});
-      } else {
-        launch_calls_select(F, B, def_lo, c_hi, 1, bb.sel_flag, bb.sel_off, bb.sel_tmp, bb.sel_list + def_lo,
-                            d_def_total, st_);
-        TrgStatus r = eval_batch(def_lo, n, bb.sel_off + n, st_);
-        if (r != TRG_OK) return r;
-      }
+      launch_calls_select(F, B, def_lo, c_hi, 1, bb.sel_flag, bb.sel_off, bb.sel_tmp, bb.sel_list + def_lo,
+                          d_def_total, st_);
+      TrgStatus r = eval_batch(def_lo, n, bb.sel_off + n, st_);
+      if (r != TRG_OK) return r;
       def_lo = c_hi;
     }
     return TRG_OK;
@@ -758,8 +735,7 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
     const int V0 = v_now;
     // The next level's record set, hash size and tag: its expansion is launched right behind this
     // level's resolve, before the host has seen this level's counters (the frontier size is read from
-    // the device, the grid is an upper bound); and the PURE part of that expansion already runs inside
-    // the resolve launch, node by node as the commit numbers them (p_role workgroups).
+    // the device, the grid is an upper bound).
     BfsDev Bn = B;
     std::swap(Bn.front_cur, Bn.front_next);
     std::swap(Bn.fxy_cur, Bn.fxy_next);
@@ -773,23 +749,9 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
     if (e->debug_spec_bound > 0) spec_bound = std::min(spec_bound, e->debug_spec_bound);
     const bool next_timed = timed_level(levels + 1);
     int next_tag = ++tag_serial;
-    LevelNext nx{};
-    if (e->presample) {
-      nx.node_rec = Bn.node_rec;
-      nx.slot_rec = Bn.slot_rec;
-      nx.count = spec_bound;
-      nx.parity = parity ^ 1;
-      nx.tag = next_tag;
-      nx.cos_t = e->d_cos;
-      nx.sin_t = e->d_sin;
-      nx.table_bits = e->sampler.table_bits;
-      nx.seed = e->sampler.seed;
-      nx.epoch = e->epoch;
-      nx.ctr = e->d_ctr;
-    }
     const int stall_hook = levels == e->debug_stall_level ? 1 : (levels == e->debug_lookback_level ? 2 : 0);
-    launch_level_resolve_commit(m.view, B, qp, mcur, TRG_NODE_VALID, call_base, V0, cur_tag, ++res_epoch, s,
-                                stall_hook, e->resolve_tickets != 0, &ticket_base, nx);
+    launch_level_resolve_commit(B, qp, mcur, TRG_NODE_VALID, call_base, V0, cur_tag, ++res_epoch, s, stall_hook,
+                                e->resolve_tickets != 0, &ticket_base);
     const int stamp = ++stamp_serial;  // published by the next level's expansion, launched right below
     if (next_timed) HIPCHK(e, hipEventRecord(evn0, s));
     launch_level_expand(m.view, qp, e->d_cos, e->d_sin, e->sampler.table_bits, e->sampler.seed,
@@ -836,8 +798,8 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
       return TRG_OK;
     };
     auto rerun_second_half = [&](bool ticketed = false, int hook = 0) -> TrgStatus {
-      launch_level_resolve_commit(m.view, B, qp, mcur, TRG_NODE_VALID, call_base, V0, cur_tag, ++res_epoch, s, hook,
-                                  ticketed || e->resolve_tickets != 0, &ticket_base, LevelNext{});
+      launch_level_resolve_commit(B, qp, mcur, TRG_NODE_VALID, call_base, V0, cur_tag, ++res_epoch, s, hook,
+                                  ticketed || e->resolve_tickets != 0, &ticket_base);
       TrgStatus r = read_ctrs();  // (rare path: a plain copy)
       if (r != TRG_OK) return r;
       // (what k_level_sample reported about the level stays true: that kernel does not run again)
@@ -1169,8 +1131,6 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
     HIPCHK(e, hipEventRecord(ev_order, e->s_edge));
     HIPCHK(e, hipStreamWaitEvent(s, ev_order, 0));
   }
-  for (const SelBatch &sbt : sel_batches)  // selected beside the loop, evaluated now
-    if ((st = eval_batch(sbt.lo, sbt.n, (const int *)bb.def_counts.p + sbt.count_at, s)) != TRG_OK) return st;
   if ((st = launch_deferred(ncalls, false)) != TRG_OK) return st;  // round 1 of the calls not yet handed over
   // while the GPU evaluates: the reference's graph.nodes[node_id] = node for ids 0..V-1 in creation
   // order (trg.cpp:248); cleanGraph iterates this container below
@@ -1198,7 +1158,7 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   // round 2: every remaining call of the (few) pairs whose first call failed or was left to the host
   uint64_t round2_evals = 0;
   {
-    int *d_n2 = (int *)bb.def_counts.p + 1023;
+    int *d_n2 = (int *)bb.def_counts.p;
     int *h_n2 = bb.h_ctrs + 34;  // pinned
     HIPCHK(e, hipMemsetAsync(d_n2, 0, sizeof(int), s));
     launch_calls_select2_append(F, B, ncalls, bb.sel_list, d_n2, d_def_total, s);
@@ -1420,14 +1380,13 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   bb.host_stats[6] = s64[11];
   bb.host_stats[4] = s64[12];
   bb.host_stats[7] = s64[13];
-  e->stats.presampled_nodes = s64[14];
   if (B.tl) {  // -DLV_TIMELINE=<tag> builds: wall-clock marks of the level kernels (100 MHz), six level attempts
     constexpr int UNITS = 1 << 16, KINDS = 12, TAGS = 6;
     std::vector<unsigned long long> tl((size_t)UNITS * KINDS * TAGS);
     HIPCHK(e, hipMemcpy(tl.data(), B.tl, tl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     static const char *names[KINDS] = {"sample start", "sample end", "spec start", "spec end", "resolve start",
                                        "resolve collected", "resolve decided(w0)", "resolve published",
-                                       "p_role go", "p_role done", "commit start", "commit sums known"};
+                                       "(unused)", "(unused)", "commit start", "commit sums known"};
     for (int t = 0; t < TAGS; ++t) {
       const unsigned long long *base = &tl[(size_t)t * UNITS * KINDS];
       unsigned long long t0 = ~0ull;

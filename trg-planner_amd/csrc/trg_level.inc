@@ -108,8 +108,7 @@ constexpr size_t TL_STRIDE = (size_t)TL_UNITS * TL_KINDS;
 #endif
 // kinds: 0 sample start, 1 sample end (per node); 2 spec start, 3 spec end (per slot); 4 resolve start,
 // 5 blockers collected, 6 first wave decided, 7 counts published (per resolve workgroup, filed under the NEXT
-// level's tag); 8 p_role go, 9 p_role done (per frontier entry, next level's tag); 10 commit start, 11 commit
-// sums known (per commit workgroup, next level's tag)
+// level's tag); 8, 9 unused; 10 commit start, 11 commit sums known (per commit workgroup, next level's tag)
 struct LevelLds {
   float nd_x[LV_NODE_CAP], nd_y[LV_NODE_CAP];
   int nd_id[LV_NODE_CAP];
@@ -302,17 +301,13 @@ __device__ Disc2 sample_tile_disc2(const MapView &m, const SampleLds &L, float *
 // ---- the PURE part of a node's expansion -----------------------------------------------------------------
 // Rejection sampling (trg.cpp:384-403) and the elevation of every accepted sample (addNode, :244-247) are
 // a function of (node position, node id, map) alone: nothing another node of the level does can change
-// them.  sample_pure runs them with a workgroup of NW waves; k_level_sample calls it inline, and the
-// trailing workgroups of the k_level_resolve launch of the PREVIOUS level run it for every node the
-// moment that node is numbered (p_role), so that by the time k_level_sample starts the samples are
-// usually there and only the state-dependent part is left.
+// them.  sample_pure runs them with a workgroup of NW waves; k_level_sample calls it inline.
 template <int NW>
 struct PureLds {
   float sx[LV_SMAX], sy[LV_SMAX], sz[LV_SMAX];
   int r_col[2][2 * NW];
   unsigned long long r_hits[NW];
   int r_ties[NW];
-  int go, id, cslot;  // p_role: what the polling thread found
 };
 
 // all threads of the workgroup: the tile of map points every draw of the node can reach (barriers inside)
@@ -444,16 +439,6 @@ __device__ __forceinline__ void sample_pure_draws(const MapView &m, const QueryP
   draws_out = draws;
 }
 
-// order-independent handshake word between the commit (look-back wave of k_level_resolve) and the
-// p_role workgroups of the same launch: level tag (13 bits, never 0) | creating slot | node id
-__device__ __forceinline__ unsigned long long ready_pack(int tag, int cslot, int id) {
-  return ((unsigned long long)((unsigned)tag % 8191u + 1u) << 51) | ((unsigned long long)(unsigned)cslot << 29) |
-         (unsigned long long)(unsigned)id;
-}
-__device__ __forceinline__ bool ready_is(unsigned long long v, int tag) {
-  return (unsigned)(v >> 51) == (unsigned)tag % 8191u + 1u;
-}
-
 // What the sampling workgroup's lanes share (one node per workgroup)
 template <int NW>
 struct SampleSide {
@@ -490,12 +475,8 @@ __device__ __forceinline__ void sample_body(SampleSide<NW> &SS, const MapView &m
   if (tid == 0) TL_MARK(tag, 0, node);
   const int gid = B.front_cur[node];
   const float2 pxy = B.fxy_cur[node];  // (= nx[gid], ny[gid]: no second round trip before the tile)
-  // what a p_role workgroup of the previous launch may have left for this node (stamp = this level's tag)
-  const int4 pre0 = ((const int4 *)&B.node_rec[node])[0];  // n_acc draws hits_sample -
-  const int4 pre1 = ((const int4 *)&B.node_rec[node])[1];  // - - stamp id
   const float px = pxy.x, py = pxy.y, pz = B.nz[gid];
   const uint32_t id = (uint32_t)gid;
-  const bool presampled = pre1.z == tag && pre1.w == gid && tag != 0;
   if (tid == 0) {
     V.nd_n = 0;
   }
@@ -530,22 +511,8 @@ __device__ __forceinline__ void sample_body(SampleSide<NW> &SS, const MapView &m
   int n_acc = 0, draws = 0;
   unsigned long long hits_node = 0;
   int ties_node = 0;
-  bool use_tile = false;
-  if (presampled) {
-    __syncthreads();  // V.nd_n is zero for everybody (the other path has the tile staging's barriers)
-    n_acc = pre0.x;
-    draws = pre0.y;
-    hits_node = (unsigned long long)(unsigned)pre0.z;
-    if (tid < n_acc) {
-      const float4 r0 = ((const float4 *)&B.slot_rec[node * S + tid])[0];
-      P.sx[tid] = r0.x;
-      P.sy[tid] = r0.y;
-      P.sz[tid] = r0.z;
-    }
-  } else {
-    use_tile = sample_pure_stage<NW>(m, p, px, py, L, P);
-    if (!use_tile) __syncthreads();  // (a box that does not fit the tile is staged without barriers)
-  }
+  const bool use_tile = sample_pure_stage<NW>(m, p, px, py, L, P);
+  if (!use_tile) __syncthreads();  // (a box that does not fit the tile is staged without barriers)
   LV_PHASE(0)
   {
     const int cnt = min(gc0.x, GRID_SLOTS);
@@ -564,17 +531,13 @@ __device__ __forceinline__ void sample_body(SampleSide<NW> &SS, const MapView &m
     }
   }
   LV_PHASE(1)
-  if (!presampled) {
-    sample_pure_draws<NW>(m, p, cos_t, sin_t, table_bits, seed, epoch, B, parity, node * S, ctr, id, px, py, use_tile,
-                           L, P, n_acc, draws);
-    if (tid == 0)
-      for (int i = 0; i < NW; ++i) {
-        hits_node += P.r_hits[i];
-        ties_node += P.r_ties[i];
-      }
-  } else {
-    __syncthreads();  // node list and the presampled positions complete
-  }
+  sample_pure_draws<NW>(m, p, cos_t, sin_t, table_bits, seed, epoch, B, parity, node * S, ctr, id, px, py, use_tile,
+                         L, P, n_acc, draws);
+  if (tid == 0)
+    for (int i = 0; i < NW; ++i) {
+      hits_node += P.r_hits[i];
+      ties_node += P.r_ties[i];
+    }
   if (tid == 0 && V.nd_n > LV_NODE_CAP) atomicOr(&B.ctrs[BFS_CTR_ERR], BFS_ERR_GRID_OVERFLOW);
   const int hh = lane >> 5;
   LV_PHASE(2)
@@ -648,7 +611,7 @@ __device__ __forceinline__ void sample_body(SampleSide<NW> &SS, const MapView &m
   if (tid == 0) {
     int4 *nr = (int4 *)&B.node_rec[node];
     nr[0] = make_int4(n_acc, draws, (int)hits_node, 0);
-    nr[1] = make_int4((int)(unsigned)cand_mask, (int)(unsigned)(cand_mask >> 32), 0, presampled ? 1 : 0);  // (the stamp is spent)
+    nr[1] = make_int4((int)(unsigned)cand_mask, (int)(unsigned)(cand_mask >> 32), 0, 0);
     ((float4 *)nr)[2] = make_float4(px, py, pz, 0.0f);
     if (ties_node && ctr) atomicAdd(&ctr[wg % COUNTER_SHARDS].nn_ties, (unsigned long long)ties_node);
     TL_MARK(tag, 1, node);
@@ -877,83 +840,6 @@ __device__ __forceinline__ void report_tie(const BfsDev &B, int slot) {
   const int k = atomicAdd(&B.ctrs[BFS_CTR_NTIE], 1);
   if (k < BFS_TIE_CAP) B.tie_list[k] = slot;
 }
-// What the p_role workgroups (the trailing workgroups of a k_level_resolve launch) need of the NEXT
-// level: they run the pure part of the expansion of every node this launch creates, as soon as the
-// commit has numbered it (front_ready), into the next level's record set.
-#ifndef TRG_P_SLEEP
-#define TRG_P_SLEEP 8  // s_sleep argument between two polls of a p_role workgroup (64 cycles each)
-#endif
-#ifndef TRG_P_TOTAL_EVERY
-#define TRG_P_TOTAL_EVERY 1
-#endif
-struct PNext {
-  NodeRec *node_rec;
-  SlotRec *slot_rec;
-  int parity;     // of the next level (map-tie records)
-  int tag;        // of the next level's expansion (0: no p_role workgroups); stamp of what they leave
-  int max_polls;  // bound of a p_role workgroup's wait for its node
-  const float *cos_t, *sin_t;
-  int table_bits;
-  uint32_t seed, epoch;
-  DeviceCounters *ctr;
-};
-
-// One p_role workgroup: frontier entry b of the next level.  It never holds anything a resolve
-// workgroup waits for, and its own wait is bounded: if the entry does not arrive (or the launch is
-// later taken back) nothing is lost -- k_level_sample samples a node itself unless it finds the stamp
-// of its own level attempt and the node's id in the record.
-__device__ __forceinline__ void p_role(const MapView &m, const QueryParams &p, const BfsDev &B, const PNext &pn,
-                                       int b, SampleLds &L, PureLds<RWV> &P) {
-  const int tid = threadIdx.x;
-  if (tid == 0) {
-    int go = 0, id = 0, cslot = 0;
-    // one word per entry (the pollers spread over the memory channels); the frontier's length is one
-    // word for everybody and is looked at only every TRG_P_TOTAL_EVERY-th time
-    for (int polls = 0; polls < pn.max_polls; ++polls) {
-      const unsigned long long v = __hip_atomic_load(&B.front_ready[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (ready_is(v, pn.tag)) {
-        go = 1;
-        id = (int)(v & 0x1FFFFFFFull);
-        cslot = (int)((v >> 29) & 0x3FFFFFull);
-        break;
-      }
-      if ((polls + b) % TRG_P_TOTAL_EVERY == 0) {
-        const unsigned long long t =
-            __hip_atomic_load(&B.front_ready[B.fcap], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (ready_is(t, pn.tag) && b >= (int)(t & 0x1FFFFFFFull)) break;  // the level's frontier ends before b
-      }
-      __builtin_amdgcn_s_sleep(TRG_P_SLEEP);
-    }
-    P.go = go;
-    P.id = id;
-    P.cslot = cslot;
-  }
-  __syncthreads();
-  if (!P.go) return;
-  if (tid == 0) TL_MARK(pn.tag, 8, b);
-  const int gid = P.id;
-  const float4 r0 = ((const float4 *)&B.slot_rec[P.cslot])[0];  // the creating sample: the node's position
-  const int S = p.sample_num;
-  int n_acc = 0, draws = 0;
-  const bool use_tile = sample_pure_stage<RWV>(m, p, r0.x, r0.y, L, P);
-  sample_pure_draws<RWV>(m, p, pn.cos_t, pn.sin_t, pn.table_bits, pn.seed, pn.epoch, B, pn.parity, b * S, pn.ctr,
-                         (uint32_t)gid, r0.x, r0.y, use_tile, L, P, n_acc, draws);
-  if (tid < n_acc) ((float4 *)&pn.slot_rec[b * S + tid])[0] = make_float4(P.sx[tid], P.sy[tid], P.sz[tid], 0.0f);
-  if (tid == 0) {
-    unsigned long long th = 0;
-    int tt = 0;
-    for (int i = 0; i < RWV; ++i) {
-      th += P.r_hits[i];
-      tt += P.r_ties[i];
-    }
-    int4 *nr = (int4 *)&pn.node_rec[b];
-    nr[0] = make_int4(n_acc, draws, (int)th, 0);
-    nr[1] = make_int4(0, 0, pn.tag, gid);
-    TL_MARK(pn.tag, 9, b);
-    if (tt && pn.ctr) atomicAdd(&pn.ctr[blockIdx.x % COUNTER_SHARDS].nn_ties, (unsigned long long)tt);
-  }
-}
-
 // the packed state of a blocker in resolve_body (see there)
 constexpr int BL_OPEN = 1, BL_BAD = 2, BL_OC_SHIFT = 2;
 // distance key of a blocker once it is decided as a created node (d2 >= 0: the bit pattern orders like the value)
@@ -967,7 +853,7 @@ __device__ __forceinline__ unsigned bl_key(int st, float dd) {
 template <bool MULTI, bool STEP3>
 __device__ __forceinline__ void resolve_body(ResolveLds &R, const BfsDev &B, int m, int S, float d, float r, int tag,
                                              long long call_base, int stall_test, int max_spin, int V0,
-                                             int new_state, int epoch, int bid, int nwg, int tag_next) {
+                                             int new_state, int epoch, int bid, int nwg) {
   RV_PHASE_BEGIN
   volatile int *vso = R.so;
   const int w = threadIdx.x >> 6, lane = lane_id();
@@ -1342,7 +1228,7 @@ __device__ __forceinline__ void resolve_body(ResolveLds &R, const BfsDev &B, int
       const int4 nr = *(const int4 *)&B.node_rec[slot / S];  // n_acc draws hits_sample hits_spec
       const NodeRec &full = B.node_rec[slot / S];
       const int ncand = __popc(full.cand_lo) + __popc(full.cand_hi);
-      *(int4 *)&B.nexp[u] = make_int4(nr.x | (ncand << 8) | (full.id ? (1 << 30) : 0), nr.y, nr.z, nr.w);
+      *(int4 *)&B.nexp[u] = make_int4(nr.x | (ncand << 8), nr.y, nr.z, nr.w);
     }
     if (created) {
       const int cell = bfs_cell_y(B, qy) * B.GW + bfs_cell_x(B, qx);
@@ -1388,8 +1274,8 @@ __device__ __forceinline__ void resolve_body(ResolveLds &R, const BfsDev &B, int
 
 // Commit workgroup c of a resolve launch: numbers the nodes created by the slots of the resolve workgroups
 // [c * CRW, (c + 1) * CRW) -- a new node's id is V0 + the nodes created by lower slots (creation order) --
-// and appends them to the node store, the node grid (the reserved place gets its id), the next frontier,
-// and tells the p_role workgroups.  Every thread sums the published counts of a share of ALL lower
+// and appends them to the node store, the node grid (the reserved place gets its id) and the next
+// frontier.  Every thread sums the published counts of a share of ALL lower
 // resolve workgroups (a few loads each; they are published long before, when those workgroups left), so
 // no commit workgroup waits for another one.  The last one writes the level's totals.
 constexpr int CRW = RWV * WAVE / RW;  // resolve workgroups per commit workgroup (one thread per slot)
@@ -1400,7 +1286,7 @@ struct CommitLds {
 };
 __device__ __forceinline__ void commit_role(CommitLds &C, const BfsDev &B, int m, int S, long long call_base,
                                             int stall_test, int max_spin, int V0, int new_state, int epoch, int c,
-                                            int nR, int nC, int tag_next, int tl_tag) {
+                                            int nR, int nC, int tl_tag) {
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int slots = m * S;
   if (tid == 0) TL_MARK(tl_tag, 10, c);
@@ -1488,9 +1374,6 @@ __device__ __forceinline__ void commit_role(CommitLds &C, const BfsDev &B, int m
     if (c == nC - 1) {  // the level's totals
       B.ctrs[BFS_CTR_V] = V0 + C.pre_c[last - first];
       B.ctrs[BFS_CTR_MNEXT] = C.pre_v[last - first];
-      if (tag_next)  // p_role workgroups past the end of the next frontier stop waiting
-        __hip_atomic_store(&B.front_ready[B.fcap], ready_pack(tag_next, 0, C.pre_v[last - first]), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
     }
   }
   __syncthreads();
@@ -1526,48 +1409,26 @@ __device__ __forceinline__ void commit_role(CommitLds &C, const BfsDev &B, int m
     if (before_v < B.fcap) {
       B.front_next[before_v] = id;
       B.fxy_next[before_v] = make_float2(r0.x, r0.y);
-      if (tag_next)  // the node is numbered: its p_role workgroup (same launch) may start
-        __hip_atomic_store(&B.front_ready[before_v], ready_pack(tag_next, slot, id), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
     } else {
       atomicOr(&B.ctrs[BFS_CTR_ERR], BFS_ERR_LEVEL_TOO_BIG);
     }
   }
 }
 
-// The launch: nR resolve workgroups, then nC commit workgroups, then the p_role workgroups of the next
-// level's frontier entries [0, gridDim.x - nR - nC).  TICKET = false: a workgroup's logical index is blockIdx.x -- the waits (for
+// The launch: nR resolve workgroups, then nC commit workgroups.  TICKET = false: a workgroup's logical index is blockIdx.x -- the waits (for
 // lower indices only) then rely on the hardware starting workgroups in index order, which it does but
 // does not promise; all waits are bounded, and a launch whose wait ran out is repeated with TICKET = true:
 // the logical index is a ticket drawn at the start, so a lower index belongs to a workgroup that is
 // already running by construction (always-on tickets cost 1.5 ms per C3 build: one contended atomic
 // per workgroup at the head of every launch's dependency chain).
-// PROLE: the launch carries p_role workgroups (option presample).  The default launch is compiled without
-// them: their sampling code would set the register and LDS budget of every resolve workgroup.
-template <bool PROLE>
-struct ResolveShared {
-  union {
-    ResolveLds R;
-    CommitLds C;
-  } U;
-};
-struct PSide {
-  SampleLds L;
-  PureLds<RWV> P;
-};
-template <>
-struct ResolveShared<true> {
-  union {
-    ResolveLds R;
-    CommitLds C;
-    PSide s;
-  } U;
-};
-template <bool TICKET, bool MULTI, bool STEP3, bool PROLE>
-__global__ __launch_bounds__(RWV *WAVE, (MULTI || STEP3 || PROLE) ? RESOLVE_WAVES_PER_SIMD : RESOLVE_WAVES_PER_SIMD_PLAIN) void k_level_resolve(
+template <bool TICKET, bool MULTI, bool STEP3>
+__global__ __launch_bounds__(RWV *WAVE, (MULTI || STEP3) ? RESOLVE_WAVES_PER_SIMD : RESOLVE_WAVES_PER_SIMD_PLAIN) void k_level_resolve(
     BfsDev B, int m, int S, float d, float r, int tag, long long call_base, int stall_test, int max_spin, int V0,
-    int new_state, int epoch, int nR, int nC, unsigned ticket_base, MapView mv, QueryParams qp, PNext pn) {
-  __shared__ ResolveShared<PROLE> sh;
+    int new_state, int epoch, int nR, int nC, unsigned ticket_base) {
+  __shared__ union {
+    ResolveLds R;
+    CommitLds C;
+  } sh;
   __shared__ int wg_ticket;
   int bid = (int)blockIdx.x;
   if (TICKET) {
@@ -1575,25 +1436,21 @@ __global__ __launch_bounds__(RWV *WAVE, (MULTI || STEP3 || PROLE) ? RESOLVE_WAVE
     __syncthreads();
     bid = wg_ticket;
   }
-  const int tag_next = PROLE ? pn.tag : 0;
-  if (bid >= nR + nC) {
-    if constexpr (PROLE) {
-      if (pn.tag) p_role(mv, qp, B, pn, bid - nR - nC, sh.U.s.L, sh.U.s.P);
-    }
-  } else if (bid >= nR) {
-    commit_role(sh.U.C, B, m, S, call_base, stall_test, max_spin, V0, new_state, epoch, bid - nR, nR, nC, tag_next, tag + 1);
+  if (bid >= nR + nC) return;
+  if (bid >= nR) {
+    commit_role(sh.C, B, m, S, call_base, stall_test, max_spin, V0, new_state, epoch, bid - nR, nR, nC, tag + 1);
   } else {
-    resolve_body<MULTI, STEP3>(sh.U.R, B, m, S, d, r, tag, call_base, stall_test, max_spin, V0, new_state, epoch, bid, nR, tag_next);
+    resolve_body<MULTI, STEP3>(sh.R, B, m, S, d, r, tag, call_base, stall_test, max_spin, V0, new_state, epoch, bid, nR);
   }
 }
 
 // Statistics of the whole expansion, once after the level loop: every valid node was expanded exactly
 // once and left its draw / sample / hit counts in nexp; every created node the map points its parent
 // edge touched.  out[0..5] = draws, samples, hits of sampling discs, hits of speculative edges,
-// candidates, hits of the created nodes' parent edges, presampled nodes.
+// candidates, hits of the created nodes' parent edges.
 __global__ __launch_bounds__(256) void k_bfs_stats(BfsDev B, int V, unsigned long long *out) {
-  __shared__ unsigned long long red[7][4];
-  unsigned long long a[7] = {0, 0, 0, 0, 0, 0, 0};
+  __shared__ unsigned long long red[6][4];
+  unsigned long long a[6] = {0, 0, 0, 0, 0, 0};
   for (int id = blockIdx.x * 256 + threadIdx.x; id < V; id += gridDim.x * 256) {
     if (B.nstate[id] != -1) {
       const int4 n = *(const int4 *)&B.nexp[id];
@@ -1602,18 +1459,17 @@ __global__ __launch_bounds__(256) void k_bfs_stats(BfsDev B, int V, unsigned lon
       a[2] += (unsigned long long)n.z;
       a[3] += (unsigned long long)n.w;
       a[4] += (unsigned long long)((n.x >> 8) & 0x3FFFFF);
-      a[6] += (unsigned long long)((n.x >> 30) & 1);  // its samples came from a p_role workgroup
     }
     if (id > 0) a[5] += (unsigned long long)B.nhits[id];
   }
 #pragma unroll
-  for (int q = 0; q < 7; ++q) {
+  for (int q = 0; q < 6; ++q) {
 #pragma unroll
     for (int msk = 32; msk >= 1; msk >>= 1) a[q] += __shfl_xor(a[q], msk);
     if (lane_id() == 0) red[q][threadIdx.x >> 6] = a[q];
   }
   __syncthreads();
-  if (threadIdx.x < 7) {
+  if (threadIdx.x < 6) {
     const unsigned long long t = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
     if (t) atomicAdd(&out[threadIdx.x], t);
   }
