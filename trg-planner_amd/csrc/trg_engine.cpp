@@ -867,16 +867,10 @@ void trg_engine_destroy(TrgEngine *e) {
       e->uploader->release();
       delete e->uploader;
     }
-    if (e->bfs) {
-      e->bfs->release();
-      delete e->bfs;
-    }
+    delete e->bfs;
     exchange_release(e);
     field_release(e);
-    if (e->stitch) {
-      e->stitch->release();
-      delete e->stitch;
-    }
+    delete e->stitch;
     free_pinned(e->sy_in);
     free_pinned(e->sy_in2);
     free_pinned(e->sy_f0);

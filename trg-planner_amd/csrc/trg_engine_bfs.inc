@@ -9,29 +9,18 @@
 
 namespace {
 
-template <typename T>
-TrgStatus dev_ensure(TrgEngine *e, T *&p, size_t &cap, size_t need, bool keep = false) {
-  if (cap >= need && p) return TRG_OK;
-  size_t ncap = std::max(need, cap + cap / 2);
-  T *np = nullptr;
-  HIPCHK(e, hipMalloc((void **)&np, ncap * sizeof(T)));
-  if (keep && p && cap) {
-    hipError_t he = hipMemcpy(np, p, cap * sizeof(T), hipMemcpyDeviceToDevice);
-    if (he != hipSuccess) {
-      (void)hipFree(np);
-      return e->fail(TRG_ERR_DEVICE, std::string("grow copy: ") + hipGetErrorString(he));
-    }
-  }
-  if (p) (void)hipFree(p);
-  p = np;
-  cap = ncap;
-  return TRG_OK;
-}
-
-// a device array with its capacity in bytes
+// a device array with its capacity in bytes; it owns its memory (an empty one makes no HIP call)
 struct DevArr {
   void *p = nullptr;
   size_t bytes = 0;
+  DevArr() = default;
+  DevArr(DevArr &&o) noexcept { *this = std::move(o); }
+  DevArr &operator=(DevArr &&o) noexcept {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+    return *this;
+  }
+  ~DevArr() { if (p) (void)hipFree(p); }
 };
 TrgStatus ensure_bytes(TrgEngine *e, DevArr &a, size_t need, bool keep = false) {
   if (a.p && a.bytes >= need) return TRG_OK;
@@ -50,6 +39,25 @@ TrgStatus ensure_bytes(TrgEngine *e, DevArr &a, size_t need, bool keep = false) 
   a.bytes = nb;
   return TRG_OK;
 }
+TrgStatus ensure_all(TrgEngine *e, std::initializer_list<std::pair<DevArr *, size_t>> need) {
+  for (const auto &n : need) {
+    const TrgStatus st = ensure_bytes(e, *n.first, n.second);
+    if (st != TRG_OK) return st;
+  }
+  return TRG_OK;
+}
+
+// a HIP event of the driver, destroyed on every exit
+struct Event {
+  hipEvent_t ev = nullptr;
+  Event() = default;
+  Event(Event &&o) noexcept { std::swap(ev, o.ev); }
+  Event &operator=(Event &&o) noexcept {
+    std::swap(ev, o.ev);
+    return *this;
+  }
+  ~Event() { if (ev) (void)hipEventDestroy(ev); }
+};
 
 // scratch of the tile-boundary stitch (trg_engine_stitch.inc)
 struct StitchBufs {
@@ -57,16 +65,6 @@ struct StitchBufs {
   DevArr extra, deg, rowptr_new, fill, col_new, w_new, dist_new;
   DevArr up_xyz, up_rowptr, up_col, up_w, up_dist;  // uploads when the device copy of the graph is stale
   DevArr scan_tmp;
-  std::array<DevArr *, 26> all() {
-    return {&flag, &off, &cnt, &pair_a, &pair_b, &p1, &p2, &mid, &status, &npts, &weight, &dist, &n_unc,
-            &extra, &deg, &rowptr_new, &fill, &col_new, &w_new, &dist_new, &up_xyz, &up_rowptr, &up_col,
-            &up_w, &up_dist, &scan_tmp};
-  }
-  void release() {
-    for (DevArr *a : all())
-      if (a->p) (void)hipFree(a->p);
-    *this = StitchBufs();
-  }
 };
 
 // Everything the expansion (k_level_sample + k_level_spec) writes exists twice (level parity): the next level is expanded while the
@@ -78,7 +76,6 @@ struct LevelSet {
   DevArr c_outcome;  // int per sample slot
   DevArr lv_hash;    // HashEnt table
   DevArr resc;       // RescueRec per sample slot (builds with expandGraph's step 3 only)
-  std::array<DevArr *, 5> all() { return {&node_rec, &slot_rec, &c_outcome, &lv_hash, &resc}; }
   void apply(BfsDev &B) const {
     B.node_rec = (NodeRec *)node_rec.p;
     B.slot_rec = (SlotRec *)slot_rec.p;
@@ -89,61 +86,478 @@ struct LevelSet {
   bool use_resc = false;
 };
 
+// pinned words of h_ctrs behind the level counters (BFS_CTR_*) in the same 64-int block
+constexpr int H_CLEAN_TOTALS = 32;  // 2 words: nodes and edges that survive cleanGraph
+constexpr int H_ROUND2_CALLS = 34;  // calls round 2 of the deferred evaluations selected
+constexpr int H_STEP3_LEFT = 40;    // step 3's device node tree: nodes not yet placed
+constexpr int H_CTRS_WORDS = 64;
+static_assert(BFS_CTR_COUNT <= H_CLEAN_TOTALS && H_CLEAN_TOTALS + 2 <= H_ROUND2_CALLS &&
+                  H_ROUND2_CALLS < H_STEP3_LEFT && H_STEP3_LEFT < H_CTRS_WORDS,
+              "pinned words overlap");
+
+// words of B.stats64 the host reads: calls the deferred selections kept, longest resolve wait, rows that went
+// multi-pass; then launch_bfs_stats's draws, samples, map points inside sampling discs and inside
+// speculative-edge queries, speculative parent edges (candidates) and the map points of the parent edges of
+// created nodes; from S64_PHASES 1024 shards x 8 phases of cycles (profiling builds)
+enum : int {
+  S64_DEF_KEPT = 5, S64_MAX_SPIN, S64_MULTIPASS, S64_DRAWS, S64_SAMPLES, S64_DISC_HITS, S64_SPEC_HITS,
+  S64_CANDIDATES, S64_PARENT_HITS, S64_PHASES = 16, S64_WORDS = 16 + 1024 * 8
+};
+
 struct BfsBuffers {
   BfsDev B{};
   FinDev F{};
   LevelSet lv[2];
-  DevArr newid_of_call;
-  DevArr gcell, ncov, wg_state, nexp, nhits, fxy0, fxy1, def_counts, tl, c_cell, s3_scratch;
-  size_t cap_nx = 0, cap_ny = 0, cap_nz = 0, cap_nstate = 0;
-  size_t cap_front0 = 0, cap_front1 = 0;
-  size_t cap_mid = 0;
-  size_t cap_unclist = 0, cap_uncrec = 0, cap_mtrec = 0;
-  size_t cap_c1 = 0, cap_c2 = 0, cap_cs = 0, cap_cw = 0, cap_cd = 0;
-  size_t cap_ctrs = 0, cap_stats = 0;
-  int *flag = nullptr, *scan_tmp = nullptr;
-  size_t cap_flag = 0, cap_scantmp = 0;
-  // selection of the deferred calls that need evaluating (flags, their scan, the index list)
-  int *sel_flag = nullptr, *sel_off = nullptr, *sel_list = nullptr, *sel_tmp = nullptr;
-  size_t cap_selflag = 0, cap_seloff = 0, cap_sellist = 0, cap_seltmp = 0;
-  // finalize
-  size_t cap_fkey = 0, cap_fseq = 0, cap_fslot = 0, cap_fdeg = 0, cap_ffill = 0, cap_frow = 0,
-         cap_fok = 0, cap_fcol = 0, cap_fseqe = 0, cap_fw = 0, cap_fdist = 0;
-  int *d_new2old = nullptr, *d_old2new = nullptr, *d_deg_new = nullptr, *d_rowptr_new = nullptr,
-      *d_col2 = nullptr, *d_state2 = nullptr, *d_map_order = nullptr, *d_keep_flag = nullptr,
-      *d_keep_pos = nullptr;
-  size_t cap_maporder = 0, cap_keepf = 0, cap_keepp = 0;
-  float *d_w2 = nullptr, *d_dist2 = nullptr, *d_xyz2 = nullptr;
-  size_t cap_n2o = 0, cap_o2n = 0, cap_degn = 0, cap_rown = 0, cap_col2 = 0, cap_state2 = 0,
-         cap_w2 = 0, cap_dist2 = 0, cap_xyz2 = 0;
+  // the arrays behind B's views (the frontier pair swaps its views level by level)
+  DevArr nx, ny, nz, nstate, gcell, ncov, nexp, nhits, front0, front1, fxy0, fxy1;
+  DevArr mid, unc_list, unc_rec, mt_rec, ctrs, stats64, wg_state, c_cell, tl, scan_tmp, s3_scratch;
+  DevArr call_n1, call_n2, call_status, call_w, call_dist, newid_of_call, call_slot;  // the call log
+  // selection of the deferred calls that need evaluating (flags, their scan, the index list), round 2's count
+  DevArr sel_flag, sel_off, sel_list, sel_tmp, def_counts;
+  // finalize: pair table, CSR in creation order, cleanGraph's renumbering and the cleaned graph
+  DevArr ht_key, ht_seq, ok_seq, deg, fill, rowptr, col, seq, w, dist;
+  DevArr map_order, keep_flag, keep_pos, new2old, old2new, deg_new, rowptr_new, col2, w2, dist2, xyz2, state2;
   int *h_ctrs = nullptr;  // pinned, device-visible: the counters of a level, its stamp in words 5 and 15
   int stamp_serial = 0;
-  // host mirror of the node states, filled only when a BFS level has to be replayed on the host
+  // host mirror of the nodes [0, hm_state.size()): states and positions, fetched from the device when a
+  // rare event needs them; it only holds nodes of levels that are final or being examined
   std::vector<int> hm_state;
-  int hm_upto = 0;
-  std::vector<float> hm_x, hm_y;  // host mirror of the node positions, extended when a tie has to be broken
-  std::vector<int> rp_stamp, rp_head;  // replay_level_on_host: cell -> newest node this replay created
+  std::vector<float> hm_x, hm_y;
+  std::vector<int> rp_stamp, rp_head;  // replay_level: cell -> newest node this replay created
   int rp_serial = 0;
-  // statistics of the levels that became final: draws, samples, created, invalid, speculative edges,
-  // map points inside sampling discs, map points inside speculative-edge queries
-  unsigned long long host_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // [7]: of [6], parent edges of created nodes
-  void release() {
-    void *ptrs[] = {gcell.p, ncov.p, B.nx, B.ny, B.nz, B.nstate, B.front_cur,
-                    B.front_next, B.mid, B.unc_list, B.unc_rec, B.mt_rec, B.call_n1, B.call_n2,
-                    B.call_status, B.call_w, B.call_dist, B.ctrs, B.stats64, flag, sel_flag, sel_off,
-                    sel_list, sel_tmp, scan_tmp, F.ht_key, F.ht_seq, F.ok_seq, F.call_slot, F.deg, F.fill,
-                    F.rowptr, F.col, F.seq, F.w, F.dist, d_new2old, d_old2new, d_deg_new,
-                    d_rowptr_new, d_col2, d_state2, d_w2, d_dist2, d_xyz2, newid_of_call.p, wg_state.p, nexp.p, nhits.p, fxy0.p, fxy1.p, def_counts.p, tl.p, c_cell.p, s3_scratch.p,
-                    d_map_order, d_keep_flag, d_keep_pos};
-    for (void *p : ptrs)
-      if (p) (void)hipFree(p);
-    for (LevelSet &l : lv)
-      for (DevArr *a : l.all())
-        if (a->p) (void)hipFree(a->p);
-    if (h_ctrs) (void)hipHostFree(h_ctrs);
-    *this = BfsBuffers();
+  unsigned long long nodes_created = 0, nodes_invalid = 0;  // by the levels that became final
+  ~BfsBuffers() { if (h_ctrs) (void)hipHostFree(h_ctrs); }
+};
+
+// the host mirror grown to the nodes [0, n)
+TrgStatus mirror_nodes(TrgEngine *e, BfsBuffers &bb, int n) {
+  const size_t at = bb.hm_state.size();
+  if ((size_t)n <= at) return TRG_OK;
+  const size_t k = (size_t)n - at;
+  bb.hm_state.resize(n);
+  bb.hm_x.resize(n);
+  bb.hm_y.resize(n);
+  HIPCHK(e, hipMemcpy(bb.hm_state.data() + at, bb.B.nstate + at, k * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(bb.hm_x.data() + at, bb.B.nx + at, k * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(bb.hm_y.data() + at, bb.B.ny + at, k * sizeof(float), hipMemcpyDeviceToHost));
+  return TRG_OK;
+}
+
+// squared distance in the reference's accumulation order (kdtree.c:339-342)
+inline float ref_d2(float x, float y, float qx, float qy) {
+  float acc = 0;
+  acc += (x - qx) * (x - qx);
+  acc += (y - qy) * (y - qy);
+  return acc;
+}
+
+// The host's nearest node to a slot's sample as the reference finds it: the pre-level node
+// k_level_sample found (all pre-level nodes that far when it carries SLOT_TIE), then the nodes the level
+// created before the slot's turn, offered one by one.  Exact ties go to the kd-tree's visiting order
+// (kd_tie_winner, host_index.h).  Positions come from the host mirror.
+struct Nearest {
+  int nn = -1;
+  float best = INFINITY;
+  std::vector<int> tied;
+  void start(const BfsBuffers &bb, const SlotRec &sr, int V0) {
+    nn = sr.nn0;
+    best = nn >= 0 ? sr.d0sq : INFINITY;
+    tied.clear();
+    if (nn >= 0 && (sr.cls & SLOT_TIE)) {
+      for (int i = 0; i < V0; ++i)
+        if (ref_d2(bb.hm_x[i], bb.hm_y[i], sr.x, sr.y) == best) tied.push_back(i);
+    } else if (nn >= 0) {
+      tied.push_back(nn);
+    }
+  }
+  void offer(const BfsBuffers &bb, int id, float qx, float qy) {
+    const float dd = ref_d2(bb.hm_x[id], bb.hm_y[id], qx, qy);
+    if (dd < best) {
+      best = dd;
+      nn = id;
+      tied.assign(1, id);
+    } else if (dd == best) {
+      tied.push_back(id);
+    }
+  }
+  bool tie() const { return tied.size() > 1; }
+  // the reference's answer among the nodes [0, V_at)
+  int winner(const BfsBuffers &bb, int V_at, float qx, float qy) {
+    if (!tie()) return nn;
+    std::sort(tied.begin(), tied.end());
+    return kd_tie_winner(bb.hm_x.data(), bb.hm_y.data(), V_at, qx, qy, tied);
   }
 };
+
+constexpr int BFS_FCAP = 1 << 16;       // nodes per BFS level the device path accepts
+constexpr int CALL_EVAL_BATCH = 1 << 22;  // calls per selection / evaluation chunk (sizes the edge scratch)
+// repaired by replaying ONE level on the host (or, for a tie among pre-level nodes only, by handing
+// k_level_resolve the reference's winner)
+constexpr int BFS_ERR_SOFT = BFS_ERR_TIE | BFS_ERR_STALL | BFS_ERR_TIE_CLS;
+// calls per batch (at least): about one batch per BFS level -- many small batches disturb the level
+// kernels least (measured: 3.2 M -> 54.6 ms per C3 build, 100 k -> 53.2, 6 k -> 51.6; no overlap 54.5)
+constexpr long long DEF_BATCH_MIN = 6000;
+
+std::string err_text(int code) {
+  std::string t;
+  if (code & BFS_ERR_GRID_OVERFLOW) t += "grid-cell overflow;";
+  if (code & BFS_ERR_NB_OVERFLOW) t += "neighbour list overflow;";
+  if (code & BFS_ERR_VCAP) t += "node capacity;";
+  if (code & BFS_ERR_TIE) t += "exact fp32 distance tie (kd-tree order decides);";
+  if (code & BFS_ERR_TIE_CLS) t += "exact fp32 distance tie among pre-level nodes;";
+  if (code & BFS_ERR_HASH) t += "hash table full;";
+  if (code & BFS_ERR_LEVEL_TOO_BIG) t += "BFS level too large;";
+  if (code & BFS_ERR_CLEAN) t += "clean remap;";
+  if (code & BFS_ERR_STALL) t += "resolve stalled;";
+  if (code & BFS_ERR_LOOKBACK) t += "commit look-back ran out (another process on the GPU?);";
+  if (code & BFS_ERR_STEP3) t += "step 3: neighbour list / call stride overflow or an uncertain slope gate;";
+  return t;
+}
+
+// test hook: pretend a tie was seen so that the undo + host-level replay are exercised on data that has
+// no real tie
+bool debug_tie_level(const TrgEngine *e, int level) {
+  return e->debug_tie_every > 0 && level > 0 && level % e->debug_tie_every == 0;
+}
+
+int hash_size(size_t nodes, int S) {
+  int ht = 1024;
+  while ((size_t)ht < 2 * nodes * (size_t)S) ht <<= 1;
+  return ht;
+}
+
+// one BFS level as the host sees it
+struct Level {
+  int index, parity, mcur, V0;
+  size_t slots;
+  long long call_base;
+  int tag, unc_ctr;  // the hash tag of the level's expansion, the counter of this parity's uncertain gates
+  // from the counters
+  int err = 0, err_from_sample = 0, mnext = 0, v_after = 0, n_unc = 0, n_mt = 0;
+  bool reexpand = false;  // the level's commit was redone: the next level's expansion is void
+  bool undone = false;    // the commit is taken back and not yet redone
+  bool replayed = false;  // replayed on the host (which counted its own nodes)
+};
+
+// One device build: what its phases share, the phases and the steps of a level.
+struct Build {
+  TrgEngine *e;
+  BfsBuffers &bb;
+  BfsDev &B;
+  FinDev &F;
+  DevMap &m;
+  const QueryParams qp;
+  const hipStream_t s;
+  const int S;
+  // call-log entries per sample slot: with expandGraph's step 3 on, every slot's own call is followed by room
+  // for the neighbour calls of the node it creates (debug_call_stride: the sparse log on any configuration)
+  const int CS;
+  size_t calls_bound = 0;
+  unsigned fht = 0;       // pair-table size
+  bool overlap = false;   // deferred evaluations beside the level loop, on s_def
+  hipStream_t s_def = nullptr;
+  unsigned ticket_base = 0;  // the host's count of the resolve start tickets drawn so far
+  bool unc_changed = false;  // resolve_uncertain: a provisional "not gated" turned out to be gated
+  int res_epoch = 0;         // one per k_level_resolve launch: the look-back words of other launches do not count
+  int levels = 0, V = 1;  // results of the level loop
+  long long ncalls = 0;
+  // deferred wireEdge evaluations
+  long long def_lo = 0;  // first call not yet handed to the deferred pipeline
+  size_t n_eval_batches = 0;
+  std::vector<std::pair<Event, Event>> def_events;
+  Event ev0, ev1, evn0, evn1, ev_order, ev_nodes;
+  Clock::time_point t_fin;  // finalize: its start, TRG_TIMING set
+  bool trace_fin = false;
+
+  explicit Build(TrgEngine *e_)
+      : e(e_), bb(*e_->bfs), B(bb.B), F(bb.F), m(e_->gmap), qp(qparams(e_)), s(e_->s_main),
+        S(e_->prm.sample_num), CS((e_->step3 || e_->debug_call_stride) ? LEVEL_STEP3_STRIDE : 1) {}
+  TrgStatus fallback(const std::string &why) {
+    e->bfs_fallback_reason = why;
+    return TRG_ERR_CAPACITY;
+  }
+  void lap(const char *what) {
+    if (!trace_fin) return;
+    (void)hipStreamSynchronize(s);
+    fprintf(stderr, "[trg finalize] %-28s %8.3f ms\n", what, ms_since(t_fin));
+  }
+  void mark(const char *what) {  // host time only: the stream keeps running
+    if (trace_fin) fprintf(stderr, "[trg finalize]   (host) %-20s %8.3f ms\n", what, ms_since(t_fin));
+  }
+  // phases
+  TrgStatus allocate();
+  TrgStatus seed_root(float root_x, float root_y, float root_z);
+  TrgStatus level_loop();
+  TrgStatus finish_deferred();
+  TrgStatus assemble_csr();
+  TrgStatus clean_and_fetch();
+  TrgStatus report_stats();
+  // steps of a level and of the deferred pipeline
+  TrgStatus read_ctrs();
+  TrgStatus wait_stamp(int stamp);
+  void read_level(Level &lv, bool first);
+  TrgStatus repair_level(Level &lv);
+  TrgStatus undo_level(Level &lv);
+  TrgStatus redo_commit(Level &lv, bool decide_gates = false, bool ticketed = false, int hook = 0);
+  TrgStatus fix_map_ties(Level &lv);
+  TrgStatus fix_pre_level_ties(Level &lv);
+  TrgStatus settle_ties_in_place(Level &lv);
+  TrgStatus replay_level(Level &lv);
+  TrgStatus resolve_uncertain(int n_unc, void *status_base, size_t stride, int list_parity, int ctr_index);
+  TrgStatus grow_call_log(size_t need);
+  TrgStatus launch_deferred(long long c1, bool in_loop);
+};
+
+TrgStatus Build::read_ctrs() {
+  HIPCHK(e, hipMemcpyAsync(bb.h_ctrs, B.ctrs, BFS_CTR_COUNT * sizeof(int), hipMemcpyDeviceToHost, s));
+  auto t0 = Clock::now();
+  HIPCHK(e, hipStreamSynchronize(s));
+  e->stats.ms_wait_gpu += ms_since(t0);
+  return TRG_OK;
+}
+
+// The level's counters reach the host without a copy in the stream: the last workgroup of the next
+// level's k_level_sample writes them into pinned host memory with the level's stamp; the host polls the
+// stamp.
+TrgStatus Build::wait_stamp(int stamp) {
+  constexpr long poll_query_mask = 0xFFFFFL;
+  auto t0 = Clock::now();
+  volatile int *hv = bb.h_ctrs;
+  long spins = 0;
+  while (hv[BFS_CTR_DONE] != stamp || hv[BFS_CTR_COUNT - 1] != stamp) {
+    if ((++spins & poll_query_mask) == 0) {
+      // the kernels may have failed to launch or the queue may be gone: do not spin forever.  (Rarely:
+      // a stream query makes the runtime put a marker behind the last kernel, and the next level's
+      // first kernel then starts ~6 us late.)
+      const hipError_t q = hipStreamQuery(s);
+      if (q != hipErrorNotReady && q != hipSuccess)
+        return e->fail(TRG_ERR_DEVICE, std::string("level kernels: ") + hipGetErrorString(q));
+      if (q == hipSuccess && hv[BFS_CTR_DONE] != stamp && spins > (1L << 24))
+        return e->fail(TRG_ERR_DEVICE, "level counters were not published");
+    }
+    __builtin_ia32_pause();
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  e->stats.ms_wait_gpu += ms_since(t0);
+  return TRG_OK;
+}
+
+// The level's result from the counter block, on the first read after wait_stamp and after every rerun of
+// resolve + commit.  What k_level_sample reported stays true (that kernel does not run again); so do the
+// expansion's counts of uncertain gates and map-point ties, which an undo clears.
+void Build::read_level(Level &lv, bool first) {
+  const int *h = bb.h_ctrs;
+  lv.err = h[BFS_CTR_ERR] | lv.err_from_sample;
+  if (debug_tie_level(e, lv.index)) lv.err |= BFS_ERR_TIE;
+  lv.mnext = h[BFS_CTR_MNEXT];
+  lv.v_after = h[BFS_CTR_V];
+  if (!first) return;
+  lv.err_from_sample = lv.err & BFS_ERR_TIE_CLS;
+  lv.n_unc = h[lv.unc_ctr];
+  lv.n_mt = h[BFS_CTR_NMAPTIE + lv.parity];
+}
+
+// host decision of the slope gates the device could not call (reference libm, trg.cpp:269-274);
+// list: the parity's half of unc_list / unc_rec, entries index status_array
+TrgStatus Build::resolve_uncertain(int n_unc, void *status_base, size_t stride, int list_parity, int ctr_index) {
+  unc_changed = false;
+  if (n_unc > BFS_UNC_CAP) return fallback("too many uncertain slope gates in one batch");
+  std::vector<int> unc_idx(n_unc);
+  std::vector<float> unc_rec(3 * (size_t)n_unc);
+  HIPCHK(e, hipMemcpy(unc_idx.data(), B.unc_list + (size_t)list_parity * BFS_UNC_CAP, n_unc * sizeof(int),
+                      hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(unc_rec.data(), B.unc_rec + (size_t)list_parity * 3 * BFS_UNC_CAP,
+                      3 * (size_t)n_unc * sizeof(float), hipMemcpyDeviceToHost));
+  for (int k = 0; k < n_unc; ++k) {
+    int stt = 0;
+    char *addr = (char *)status_base + (size_t)unc_idx[k] * stride;
+    HIPCHK(e, hipMemcpy(&stt, addr, sizeof(int), hipMemcpyDeviceToHost));
+    e->stats.gate_uncertain++;
+    if (host_slope_gate(e, unc_rec[3 * k], unc_rec[3 * k + 1], unc_rec[3 * k + 2])) {
+      stt = EDGE_GATE;
+      unc_changed = true;
+    } else {
+      stt &= ~EDGE_GATE_UNCERTAIN;
+    }
+    HIPCHK(e, hipMemcpy(addr, &stt, sizeof(int), hipMemcpyHostToDevice));
+  }
+  const int zero = 0;
+  HIPCHK(e, hipMemcpy(B.ctrs + ctr_index, &zero, sizeof(int), hipMemcpyHostToDevice));
+  return TRG_OK;
+}
+
+// the level's commit taken back: its nodes leave the grid, its outcomes are undecided again
+TrgStatus Build::undo_level(Level &lv) {
+  lv.reexpand = true;
+  lv.undone = true;
+  HIPCHK(e, hipStreamSynchronize(s));  // the next level's expansion (now void) must be out of the way
+  launch_bfs_undo_slots(B, (int)lv.slots, s);
+  // k_level_resolve polls outcomes: a rerun must find them undecided again
+  HIPCHK(e, hipMemsetAsync(B.c_outcome, 0, lv.slots * sizeof(int), s));
+  int ctr_host[BFS_CTR_COUNT] = {0};
+  ctr_host[BFS_CTR_V] = lv.V0;
+  HIPCHK(e, hipMemcpy(B.ctrs, ctr_host, BFS_CTR_NUNC2 * sizeof(int), hipMemcpyHostToDevice));  // (the deferred pipeline owns NUNC2)
+  if ((int)bb.hm_state.size() > lv.V0) {  // the host mirror keeps the nodes of earlier levels only
+    bb.hm_state.resize(lv.V0);
+    bb.hm_x.resize(lv.V0);
+    bb.hm_y.resize(lv.V0);
+  }
+  return TRG_OK;
+}
+
+// Undo, resolve + commit again, fall back on a hard error.  decide_gates: the level's uncertain gates are
+// decided in between; ticketed: the resolve workgroups take start tickets (hook: the repeat's test hook).
+TrgStatus Build::redo_commit(Level &lv, bool decide_gates, bool ticketed, int hook) {
+  TrgStatus st;
+  if ((st = undo_level(lv)) != TRG_OK) return st;  // (also clears the tie / gate counters)
+  if (decide_gates && lv.n_unc > 0) {
+    void *status = (char *)B.slot_rec + offsetof(SlotRec, status);
+    if ((st = resolve_uncertain(std::min(lv.n_unc, BFS_UNC_CAP), status, sizeof(SlotRec), lv.parity,
+                                lv.unc_ctr)) != TRG_OK)
+      return st;
+    lv.n_unc = 0;
+  }
+  launch_level_resolve_commit(B, qp, lv.mcur, TRG_NODE_VALID, lv.call_base, lv.V0, lv.tag, ++res_epoch,
+                              s, hook, ticketed || e->resolve_tickets != 0, &ticket_base);
+  if ((st = read_ctrs()) != TRG_OK) return st;  // (rare path: a plain copy)
+  read_level(lv, false);
+  lv.undone = false;
+  if (lv.err & ~BFS_ERR_SOFT) return fallback(err_text(lv.err));
+  return TRG_OK;
+}
+
+// accepted samples whose elevation hung on a nearest-map-point tie: the device took the lowest cloud
+// index; fetch the reference's choice and, if a z changed, re-evaluate that sample's speculative edge and
+// redo resolve + commit (sample positions and classes do not depend on z)
+TrgStatus Build::fix_map_ties(Level &lv) {
+  TrgStatus st;
+  std::vector<MapTieRec> recs((size_t)std::min(lv.n_mt, MAPTIE_CAP));
+  HIPCHK(e, hipMemcpy(recs.data(), B.mt_rec + lv.parity * MAPTIE_CAP, recs.size() * sizeof(MapTieRec),
+                      hipMemcpyDeviceToHost));
+  if (lv.n_mt > MAPTIE_CAP) e->stats.map_nn_unresolved += (uint64_t)(lv.n_mt - MAPTIE_CAP);
+  bool z_changed = false;
+  for (const MapTieRec &r : recs) {
+    float z_exact = 0;
+    bool found = false;
+    if ((st = map_nn_exact(e, m, r.qx, r.qy, &z_exact, &found)) != TRG_OK) return st;
+    SlotRec sr;
+    HIPCHK(e, hipMemcpy(&sr, B.slot_rec + r.slot, sizeof(SlotRec), hipMemcpyDeviceToHost));
+    if (!found || z_exact == sr.z) continue;
+    sr.z = z_exact;
+    z_changed = true;
+    if ((sr.cls & SLOT_CLS_MASK) == 2) {
+      // the candidate's parent edge with the corrected elevation (position-only part of wireEdge)
+      int parent = 0;
+      float p1[3], p2[3] = {r.qx, r.qy, z_exact}, wgt = 0, dd = 0;
+      HIPCHK(e, hipMemcpy(&parent, B.front_cur + r.slot / S, sizeof(int), hipMemcpyDeviceToHost));
+      HIPCHK(e, hipMemcpy(&p1[0], B.nx + parent, sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHK(e, hipMemcpy(&p1[1], B.ny + parent, sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHK(e, hipMemcpy(&p1[2], B.nz + parent, sizeof(float), hipMemcpyDeviceToHost));
+      int32_t raw = 0;
+      if ((st = edges_sync(e, e->gmap, p1, p2, 1, &raw, nullptr, &wgt, &dd, false)) != TRG_OK) return st;
+      if (raw & EDGE_GATE_UNCERTAIN) {
+        e->stats.gate_uncertain++;
+        raw = host_slope_gate(e, p1[2], p2[2], dd) ? EDGE_GATE : (raw & ~EDGE_GATE_UNCERTAIN);
+      }
+      if ((raw & EDGE_STATUS_MASK) != EDGE_OK) wgt = 0.0f;
+      sr.status = raw;
+      sr.dist = dd;
+      sr.cov[0] = wgt;  // the weight itself (already clamped): k_node_weights takes it as given
+      sr.w_given = 1;
+    }
+    HIPCHK(e, hipMemcpy(B.slot_rec + r.slot, &sr, sizeof(SlotRec), hipMemcpyHostToDevice));
+  }
+  if (z_changed)
+    // the level's uncertain gates are decided before the second half runs again (the entry of a
+    // re-evaluated slot is stale but harmless: its status no longer carries the flag)
+    return redo_commit(lv, true);
+  const int zero = 0;
+  HIPCHK(e, hipMemcpy(B.ctrs + BFS_CTR_NMAPTIE + lv.parity, &zero, sizeof(int), hipMemcpyHostToDevice));
+  return TRG_OK;
+}
+
+// Only ties among nodes that existed before the level: nothing else of the level is in doubt.  The
+// reference's winner (kd-tree visiting order, host_index.h) replaces the device's pick in the slot records
+// and resolve + commit run again -- no host replay of the whole level.
+TrgStatus Build::fix_pre_level_ties(Level &lv) {
+  TrgStatus st;
+  std::vector<SlotRec> srec(lv.slots);
+  HIPCHK(e, hipMemcpy(srec.data(), B.slot_rec, lv.slots * sizeof(SlotRec), hipMemcpyDeviceToHost));
+  Nearest near;
+  for (size_t sl = 0; sl < lv.slots; ++sl) {
+    SlotRec &sr = srec[sl];
+    if (!(sr.cls & SLOT_TIE) || (sr.cls & SLOT_CLS_MASK) == 0 || sr.nn0 < 0) continue;
+    if ((st = mirror_nodes(e, bb, lv.V0)) != TRG_OK) return st;
+    near.start(bb, sr, lv.V0);
+    e->stats.nn_ties++;
+    sr.nn0 = near.winner(bb, lv.V0, sr.x, sr.y);
+    sr.cls &= ~SLOT_TIE;
+    HIPCHK(e, hipMemcpy(B.slot_rec + sl, &sr, sizeof(SlotRec), hipMemcpyHostToDevice));
+  }
+  lv.err_from_sample = 0;  // settled
+  if ((st = redo_commit(lv)) != TRG_OK) return st;
+  e->stats.bfs_tie_fixups++;
+  return TRG_OK;
+}
+
+// A tie between two nearest-node candidates touches only the slots that met it: whichever of the tied
+// nodes wins, the distance -- hence "creates a node or not" -- is the same unless their states differ, and
+// nobody waits for a sample that does not create.  The committed level stands; the host decides the
+// listed slots as the reference would and rewrites their call records.  (States differ and one outcome
+// creates: the tie stays in lv.err and the level is replayed.)
+TrgStatus Build::settle_ties_in_place(Level &lv) {
+  TrgStatus st;
+  int ntie = 0;
+  HIPCHK(e, hipMemcpy(&ntie, B.ctrs + BFS_CTR_NTIE, sizeof(int), hipMemcpyDeviceToHost));
+  if (ntie <= 0 || ntie > BFS_TIE_CAP) return TRG_OK;
+  std::vector<int> tslots(ntie);
+  HIPCHK(e, hipMemcpy(tslots.data(), B.tie_list, (size_t)ntie * sizeof(int), hipMemcpyDeviceToHost));
+  std::sort(tslots.begin(), tslots.end());
+  tslots.erase(std::unique(tslots.begin(), tslots.end()), tslots.end());
+  if (tslots.front() < 0 || (size_t)tslots.back() >= lv.slots) return TRG_OK;
+  // which slots created a node (outcomes 3 / 4): the nodes that existed at a slot's turn are
+  // V0 + the creations of the slots before it
+  std::vector<int> oc((size_t)tslots.back() + 1);
+  HIPCHK(e, hipMemcpy(oc.data(), B.c_outcome, oc.size() * sizeof(int), hipMemcpyDeviceToHost));
+  if ((st = mirror_nodes(e, bb, lv.v_after)) != TRG_OK) return st;  // (the level's nodes included)
+  struct Patch {
+    size_t at;
+    int n2, st;
+  };
+  std::vector<Patch> patches;
+  Nearest near;
+  size_t scanned = 0;
+  int created_before = 0;
+  for (int sl : tslots) {
+    for (; scanned < (size_t)sl; ++scanned) created_before += (oc[scanned] == 3 || oc[scanned] == 4);
+    const int V_at = lv.V0 + created_before;
+    SlotRec sr;
+    int u = -1;
+    HIPCHK(e, hipMemcpy(&sr, B.slot_rec + sl, sizeof(SlotRec), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(&u, B.front_cur + sl / S, sizeof(int), hipMemcpyDeviceToHost));
+    if ((sr.cls & SLOT_CLS_MASK) == 0) continue;
+    near.start(bb, sr, lv.V0);
+    for (int i = lv.V0; i < V_at; ++i) near.offer(bb, i, sr.x, sr.y);
+    if (near.nn < 0) return TRG_OK;
+    if (near.tie()) e->stats.nn_ties++;
+    const int nn = near.winner(bb, V_at, sr.x, sr.y);
+    const int kind =
+        bb.hm_state[nn] == TRG_NODE_INVALID ? 1 : (std::sqrt(near.best) < e->prm.robot_size ? 2 : 3);
+    const bool dev_creates = oc[sl] == 3 || oc[sl] == 4;
+    if ((kind == 3) != dev_creates) return TRG_OK;  // the level's node set is in doubt: replay it
+    if (kind == 3) continue;                          // creates either way: its record stands
+    patches.push_back({(size_t)lv.call_base + (size_t)sl, kind == 2 ? nn : -1,
+                       (kind == 2 && nn != u) ? CALL_PENDING : CALL_NONE});
+  }
+  for (const Patch &pt : patches) {
+    HIPCHK(e, hipMemcpy(B.call_n2 + pt.at, &pt.n2, sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(B.call_status + pt.at, &pt.st, sizeof(int), hipMemcpyHostToDevice));
+  }
+  launch_bfs_clear_tie(B, s);
+  lv.err &= ~BFS_ERR_TIE;
+  e->stats.bfs_tie_fixups++;
+  return TRG_OK;
+}
 
 // One BFS level replayed sequentially on the host (exactly the reference's loop, trg.cpp:406-452),
 // consuming what the device already computed for the level: the samples, every sample's nearest
@@ -151,51 +565,24 @@ struct BfsBuffers {
 // SLOT_TIE) and the speculative parent edges.  Used when the device met an exact fp32 distance tie
 // between two nearest-node candidates -- the reference's answer then depends on its kd-tree's
 // traversal order, which kd_tie_winner() (host_index.h) reproduces without building the tree -- or
-// when a resolve wait ran out.  Only the nodes this level creates are indexed here (a small cell
-// map); the positions of all earlier nodes are fetched only if a tie really has to be broken.
-// Afterwards the device BFS continues.
-TrgStatus replay_level_on_host(TrgEngine *e, BfsBuffers &bb, int mcur, int V0, long long call_base,
-                               int *v_out, int *mnext_out) {
-  BfsDev &B = bb.B;
-  const int S = e->prm.sample_num;
-  const size_t slots = (size_t)mcur * S;
-  const float r = e->prm.robot_size;
-  hipStream_t s = e->s_main;
-  // states of the nodes that exist before this level (kept across replays)
-  if (bb.hm_upto < V0) {
-    const size_t n = (size_t)(V0 - bb.hm_upto), at = (size_t)bb.hm_upto;
-    bb.hm_state.resize(V0);
-    HIPCHK(e, hipMemcpy(bb.hm_state.data() + at, B.nstate + at, n * sizeof(int), hipMemcpyDeviceToHost));
-    bb.hm_upto = V0;
-  }
-  bb.hm_state.resize(V0);  // (nodes of a level replayed earlier and then taken back)
+// when a resolve wait ran out.  The nodes this level creates are indexed in a small cell map and
+// appended to the host mirror.  Afterwards the device BFS continues.
+TrgStatus Build::replay_level(Level &lv) {
+  const int V0 = lv.V0;
+  const size_t slots = lv.slots;
+  TrgStatus st;
+  // states and positions of the nodes that exist before this level (kept across replays)
+  if ((st = mirror_nodes(e, bb, V0)) != TRG_OK) return st;  // (the undo before the replay cut it back to V0)
   // level inputs: the records k_level_sample / k_level_spec left (candidates are indexed by slot)
-  std::vector<int> front(mcur);
-  std::vector<NodeRec> nrec(mcur);
+  std::vector<int> front(lv.mcur);
+  std::vector<NodeRec> nrec(lv.mcur);
   std::vector<SlotRec> srec(slots);
-  HIPCHK(e, hipMemcpy(front.data(), B.front_cur, (size_t)mcur * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(e, hipMemcpy(nrec.data(), B.node_rec, (size_t)mcur * sizeof(NodeRec), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(front.data(), B.front_cur, (size_t)lv.mcur * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(nrec.data(), B.node_rec, (size_t)lv.mcur * sizeof(NodeRec), hipMemcpyDeviceToHost));
   HIPCHK(e, hipMemcpy(srec.data(), B.slot_rec, slots * sizeof(SlotRec), hipMemcpyDeviceToHost));
-  unsigned long long C = 0;
-  for (size_t i = 0; i < slots; ++i) C += (srec[i].cls & SLOT_CLS_MASK) == 2;
   std::vector<NodeCov> new_cov;  // of the nodes created here, in creation order
-  std::vector<float> new_x, new_y, new_z;
-  std::vector<int> new_state, new_hits;
-  // positions of ALL nodes [0, Vcur), fetched lazily for kd_tie_winner
-  std::vector<float> all_x, all_y;
-  auto ensure_all_positions = [&](int Vcur) -> TrgStatus {
-    if (all_x.empty()) {
-      all_x.resize(V0);
-      all_y.resize(V0);
-      HIPCHK(e, hipMemcpy(all_x.data(), B.nx, (size_t)V0 * sizeof(float), hipMemcpyDeviceToHost));
-      HIPCHK(e, hipMemcpy(all_y.data(), B.ny, (size_t)V0 * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    for (size_t k = all_x.size() - (size_t)V0; (int)(V0 + k) < Vcur; ++k) {
-      all_x.push_back(new_x[k]);
-      all_y.push_back(new_y[k]);
-    }
-    return TRG_OK;
-  };
+  std::vector<float> new_z;
+  std::vector<int> new_hits;
   // the nodes this level has created so far, by cell of the node grid (cell = robot_size): flat
   // head / next chains; a cell's head is valid only if its stamp is this replay's serial number, so
   // the arrays are never cleared
@@ -212,19 +599,13 @@ TrgStatus replay_level_on_host(TrgEngine *e, BfsBuffers &bb, int mcur, int V0, l
     t = std::min(std::max(t, 0.0f), (float)(n - 1));
     return (int)t;
   };
-  auto d2_of = [](float nx_, float ny_, float qx, float qy) {
-    float acc = 0;  // the reference's accumulation order (kdtree.c:339-342)
-    acc += (nx_ - qx) * (nx_ - qx);
-    acc += (ny_ - qy) * (ny_ - qy);
-    return acc;
-  };
   // sequential replay
-  std::vector<int> call_n1(slots), call_n2(slots, -1), call_st(slots, CALL_NONE), next_front, tied;
+  std::vector<int> call_n1(slots), call_n2(slots, -1), call_st(slots, CALL_NONE), next_front;
   std::vector<float> call_w(slots, 0.0f), call_d(slots, 0.0f);
+  Nearest near;
   int Vcur = V0;
   unsigned long long invalid = 0;
-  TrgStatus st;
-  for (int qpos = 0; qpos < mcur; ++qpos) {
+  for (int qpos = 0; qpos < lv.mcur; ++qpos) {
     const int u = front[qpos];
     for (int j = 0; j < S; ++j) {
       const size_t slot = (size_t)qpos * S + j;
@@ -232,56 +613,25 @@ TrgStatus replay_level_on_host(TrgEngine *e, BfsBuffers &bb, int mcur, int V0, l
       if (j >= nrec[qpos].n_acc) continue;
       const SlotRec &sr = srec[slot];
       const float qx = sr.x, qy = sr.y;
-      // nearest node: the pre-level one the device found ...
-      int nn = sr.nn0;
-      float best = nn >= 0 ? sr.d0sq : INFINITY;
-      tied.clear();
-      bool tie = false;
-      if (nn >= 0 && (sr.cls & SLOT_TIE)) {  // ... which was not unique: all pre-level nodes that far
-        if ((st = ensure_all_positions(Vcur)) != TRG_OK) return st;
-        for (int i = 0; i < V0; ++i)
-          if (d2_of(all_x[i], all_y[i], qx, qy) == best) tied.push_back(i);
-        tie = tied.size() > 1;
-      } else if (nn >= 0) {
-        tied.push_back(nn);
-      }
-      // ... against the nodes created earlier in this level
+      // nearest node: the pre-level one(s) the device found, against the nodes created earlier in this level
+      near.start(bb, sr, V0);
       {
-        const float rad = (nn >= 0 ? std::sqrt(best) : e->prm.expand_dist * 1.01f) * 1.001f + 1e-6f;
+        const float rad = (near.nn >= 0 ? std::sqrt(near.best) : e->prm.expand_dist * 1.01f) * 1.001f + 1e-6f;
         const int cx0 = cell_xy(qx - rad, B.gx0, B.GW), cx1 = cell_xy(qx + rad, B.gx0, B.GW);
         const int cy0 = cell_xy(qy - rad, B.gy0, B.GH), cy1 = cell_xy(qy + rad, B.gy0, B.GH);
         for (int cy = cy0; cy <= cy1; ++cy)
           for (int cx = cx0; cx <= cx1; ++cx) {
             const size_t cell = (size_t)cy * B.GW + cx;
             if (bb.rp_stamp[cell] != serial) continue;
-            for (int id = bb.rp_head[cell]; id >= 0; id = rp_next[id - V0]) {
-              const float dd = d2_of(new_x[id - V0], new_y[id - V0], qx, qy);
-              if (dd < best) {
-                best = dd;
-                nn = id;
-                tied.assign(1, id);
-                tie = false;
-              } else if (dd == best) {
-                tied.push_back(id);
-                tie = true;
-              }
-            }
+            for (int id = bb.rp_head[cell]; id >= 0; id = rp_next[id - V0]) near.offer(bb, id, qx, qy);
           }
       }
-      if (nn < 0) return e->fail(TRG_ERR_DEVICE, "host level replay: a sample without a nearest node");
-      if (tie) {
-        e->stats.nn_ties++;
-        if ((st = ensure_all_positions(Vcur)) != TRG_OK) return st;
-        std::sort(tied.begin(), tied.end());
-        nn = kd_tie_winner(all_x.data(), all_y.data(), Vcur, qx, qy, tied);
-      }
-      const int nn_state = nn < V0 ? bb.hm_state[nn] : new_state[nn - V0];
-      const float nnx = nn < V0 ? 0.0f : new_x[nn - V0], nny = nn < V0 ? 0.0f : new_y[nn - V0];
-      if (nn_state == TRG_NODE_INVALID) continue;                                // trg.cpp:411-413
+      if (near.nn < 0) return e->fail(TRG_ERR_DEVICE, "host level replay: a sample without a nearest node");
+      if (near.tie()) e->stats.nn_ties++;
+      const int nn = near.winner(bb, Vcur, qx, qy);
+      if (bb.hm_state[nn] == TRG_NODE_INVALID) continue;                         // trg.cpp:411-413
       // (existing - sample).norm() < robot_size: the distance is `best` whichever node it is
-      (void)nnx;
-      (void)nny;
-      if (std::sqrt(best) < r) {                                                   // trg.cpp:414-417
+      if (std::sqrt(near.best) < e->prm.robot_size) {                                              // trg.cpp:414-417
         if (nn != u) {
           call_n2[slot] = nn;
           call_st[slot] = CALL_PENDING;
@@ -293,10 +643,10 @@ TrgStatus replay_level_on_host(TrgEngine *e, BfsBuffers &bb, int mcur, int V0, l
       const bool ok = (sr.status & EDGE_STATUS_MASK) == EDGE_OK;
       const int id = Vcur++;
       new_hits.push_back(sr.hits);  // map points of the parent edge the reference evaluates (trg.cpp:425)
-      new_x.push_back(qx);
-      new_y.push_back(qy);
+      bb.hm_x.push_back(qx);
+      bb.hm_y.push_back(qy);
+      bb.hm_state.push_back(ok ? TRG_NODE_VALID : TRG_NODE_INVALID);
       new_z.push_back(sr.z);
-      new_state.push_back(ok ? TRG_NODE_VALID : TRG_NODE_INVALID);
       {
         const size_t cell = (size_t)cell_xy(qy, B.gy0, B.GH) * B.GW + cell_xy(qx, B.gx0, B.GW);
         rp_next.push_back(bb.rp_stamp[cell] == serial ? bb.rp_head[cell] : -1);
@@ -311,7 +661,7 @@ TrgStatus replay_level_on_host(TrgEngine *e, BfsBuffers &bb, int mcur, int V0, l
         next_front.push_back(id);
         for (int q = 0; q < 6; ++q) nc.cov[q] = sr.cov[q];
         nc.w_given = sr.w_given;
-        nc.call = (int)(call_base + (long long)slot);
+        nc.call = (int)(lv.call_base + (long long)slot);
       } else {
         invalid++;
       }
@@ -319,20 +669,18 @@ TrgStatus replay_level_on_host(TrgEngine *e, BfsBuffers &bb, int mcur, int V0, l
     }
   }
   const int created = Vcur - V0;
-  bb.hm_state.insert(bb.hm_state.end(), new_state.begin(), new_state.end());
-  bb.hm_upto = Vcur;
-  bb.host_stats[2] += (unsigned long long)created;
-  bb.host_stats[3] += invalid;
-  (void)C;  // (draws / samples / candidates / hit counts: per-node records, summed after the loop)
+  bb.nodes_created += (unsigned long long)created;
+  bb.nodes_invalid += invalid;
+  // (draws / samples / candidates / hit counts: per-node records, summed after the loop)
   if (Vcur > B.vcap || (int)next_front.size() > B.fcap)
     return e->fail(TRG_ERR_CAPACITY, "host level replay: capacity");
   // hand the level's results to the device
   if (created > 0) {
     const size_t at = (size_t)V0, n = (size_t)created;
-    HIPCHK(e, hipMemcpy(B.nx + at, new_x.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(B.ny + at, new_y.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(B.nx + at, bb.hm_x.data() + at, n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(B.ny + at, bb.hm_y.data() + at, n * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(B.nz + at, new_z.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(B.nstate + at, new_state.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(B.nstate + at, bb.hm_state.data() + at, n * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(B.ncov + at, new_cov.data(), n * sizeof(NodeCov), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(B.nhits + at, new_hits.data(), n * sizeof(int), hipMemcpyHostToDevice));
     launch_bfs_insert_nodes(B, V0, created, s);
@@ -342,12 +690,12 @@ TrgStatus replay_level_on_host(TrgEngine *e, BfsBuffers &bb, int mcur, int V0, l
                         hipMemcpyHostToDevice));
     std::vector<float> fxy(2 * next_front.size());
     for (size_t k = 0; k < next_front.size(); ++k) {
-      fxy[2 * k] = new_x[next_front[k] - V0];
-      fxy[2 * k + 1] = new_y[next_front[k] - V0];
+      fxy[2 * k] = bb.hm_x[next_front[k]];
+      fxy[2 * k + 1] = bb.hm_y[next_front[k]];
     }
     HIPCHK(e, hipMemcpy(B.fxy_next, fxy.data(), fxy.size() * sizeof(float), hipMemcpyHostToDevice));
   }
-  const size_t cb = (size_t)call_base;
+  const size_t cb = (size_t)lv.call_base;
   HIPCHK(e, hipMemcpy(B.call_n1 + cb, call_n1.data(), slots * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(B.call_n2 + cb, call_n2.data(), slots * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(B.call_status + cb, call_st.data(), slots * sizeof(int), hipMemcpyHostToDevice));
@@ -358,39 +706,80 @@ TrgStatus replay_level_on_host(TrgEngine *e, BfsBuffers &bb, int mcur, int V0, l
   ctr_host[BFS_CTR_MNEXT] = (int)next_front.size();
   HIPCHK(e, hipMemcpy(B.ctrs, ctr_host, BFS_CTR_NUNC2 * sizeof(int), hipMemcpyHostToDevice));  // (the deferred pipeline owns NUNC2)
   HIPCHK(e, hipStreamSynchronize(s));
-  *v_out = Vcur;
-  *mnext_out = (int)next_front.size();
+  lv.v_after = Vcur;
+  lv.mnext = (int)next_front.size();
+  lv.replayed = true;
   e->stats.bfs_host_levels++;
   return TRG_OK;
 }
 
-constexpr int BFS_FCAP = 1 << 16;       // nodes per BFS level the device path accepts
-constexpr int CALL_EVAL_BATCH = 1 << 22;  // calls per selection / evaluation chunk (sizes the edge scratch)
-// repaired by replaying ONE level on the host (or, for a tie among pre-level nodes only, by handing
-// k_level_resolve the reference's winner)
-constexpr int BFS_ERR_SOFT = BFS_ERR_TIE | BFS_ERR_STALL | BFS_ERR_TIE_CLS;
+// The rare events of a level, repaired in this order.  The device treats a slope gate it could not call
+// as "not gated" and a nearest-node tie as "lowest id"; when either happened the level's commit is taken
+// back, the host supplies the exact answer, and resolve + commit run again / the level is replayed on the
+// host.
+TrgStatus Build::repair_level(Level &lv) {
+  TrgStatus st;
+  // 1. step-3 guards
+  if (e->step3 && lv.n_unc > 0)
+    // (the rescue search of k_level_spec3 ran on the provisional verdict of that gate)
+    return fallback("a slope gate left to the host's libm in a build with expandGraph's step 3");
+  if (CS > 1 && ((lv.err & BFS_ERR_SOFT & ~BFS_ERR_STALL) || lv.n_mt > 0))
+    // (the host repairs of nearest-node ties and map-point ties are written for the dense call log and
+    // know nothing of step 3: such a build goes to the host replay as a whole)
+    return fallback("exact fp32 distance tie in a build with expandGraph's step 3");
+  const auto t_rare = Clock::now();
+  const bool any_rare = lv.n_mt > 0 || lv.n_unc > 0 || (lv.err & (BFS_ERR_SOFT | BFS_ERR_LOOKBACK));
+  // 2. ticketed repeat: a bounded wait of the resolve launch ran out, the hardware did not start its
+  // workgroups in index order (another process's kernels on the card).  The launch is repeated with start
+  // tickets as logical indices: every wait is then for a workgroup that is already running, whatever the
+  // dispatch order.  (Test hook debug_wait_rerun: the repeat fails as well.)
+  constexpr int ERR_WAIT = BFS_ERR_STALL | BFS_ERR_LOOKBACK;
+  if ((lv.err & ERR_WAIT) && !(lv.err & ~(BFS_ERR_SOFT | ERR_WAIT))) {
+    const int hook = e->debug_wait_rerun ? ((lv.err & BFS_ERR_LOOKBACK) ? 2 : 1) : 0;
+    e->stats.bfs_ticket_reruns++;
+    st = redo_commit(lv, false, true, hook);
+    if (st == TRG_ERR_CAPACITY) e->stats.ms_rare_events += ms_since(t_rare);  // (a hard error, as below)
+    if (st != TRG_OK) return st;
+  }
+  // 3. hard errors
+  if (lv.err & ~BFS_ERR_SOFT) {
+    if (any_rare) e->stats.ms_rare_events += ms_since(t_rare);
+    return fallback(err_text(lv.err));
+  }
+  // 4. map-point ties (the level's gates are decided before their rerun)
+  if (lv.n_mt > 0 && (st = fix_map_ties(lv)) != TRG_OK) return st;
+  // 5. uncertain gates: a speculative edge the level relied on that is in fact gated redoes the second half
+  if (lv.n_unc > 0) {
+    void *status = (char *)B.slot_rec + offsetof(SlotRec, status);
+    if ((st = resolve_uncertain(lv.n_unc, status, sizeof(SlotRec), lv.parity, lv.unc_ctr)) != TRG_OK) return st;
+    if (unc_changed && (st = (lv.err & BFS_ERR_SOFT) ? undo_level(lv) : redo_commit(lv)) != TRG_OK) return st;
+  }
+  // 6. ties among pre-level nodes only
+  if ((lv.err & BFS_ERR_SOFT) == BFS_ERR_TIE_CLS && !lv.undone && (st = fix_pre_level_ties(lv)) != TRG_OK)
+    return st;
+  // 7. ties with the level's own nodes, settled on the committed level
+  if ((lv.err & BFS_ERR_SOFT) == BFS_ERR_TIE && !lv.undone && e->tie_inplace && !debug_tie_level(e, lv.index)) {
+    if ((st = settle_ties_in_place(lv)) != TRG_OK) return st;
+  }
+  // 8. exact fp32 distance tie (or a resolve whose bounded wait ran out): this one level is replayed on the
+  // host, then the device goes on
+  if (lv.err & BFS_ERR_SOFT) {
+    if (CS > 1) return fallback("a level of a build with expandGraph's step 3 needs the host replay");
+    if (!lv.undone && (st = undo_level(lv)) != TRG_OK) return st;
+    if ((st = replay_level(lv)) != TRG_OK) return st;
+  }
+  if (any_rare) {
+    e->stats.ms_rare_events += ms_since(t_rare);
+    if (getenv("TRG_TRACE_LEVELS"))
+      fprintf(stderr, "[trg bfs] level %d: rare events (map ties %d, uncertain gates %d, err %d%s) took %.3f ms\n",
+              lv.index, lv.n_mt, lv.n_unc, lv.err, lv.replayed ? ", host replay" : "",
+              ms_since(t_rare));
+  }
+  return TRG_OK;
+}
 
-// returns TRG_OK, a hard error, or TRG_ERR_CAPACITY with e->bfs_fallback_reason set when the
-// caller should redo the build with the host replay
-TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float root_z) {
-  BfsBuffers &bb = *e->bfs;
-  BfsDev &B = bb.B;
-  FinDev &F = bb.F;
-  const int S = e->prm.sample_num;
-  // call-log entries per sample slot: with expandGraph's step 3 on, every slot's own call is followed by room
-  // for the neighbour calls of the node it creates (debug_call_stride: the sparse log on any configuration)
-  const int CS = (e->step3 || e->debug_call_stride) ? LEVEL_STEP3_STRIDE : 1;
-  B.cstride = CS;
-  const QueryParams qp = qparams(e);
-  hipStream_t s = e->s_main;
-  e->bfs_fallback_reason.clear();
-  auto fallback = [&](const std::string &why) {
-    e->bfs_fallback_reason = why;
-    return TRG_ERR_CAPACITY;
-  };
-
-  // ---- geometry of the node grid and capacities ------------------------------------------------
-  DevMap &m = e->gmap;
+// ---- phase 1: geometry of the node grid, capacities, device buffers -----------------------------------
+TrgStatus Build::allocate() {
   const float pad = e->prm.expand_dist * 2 + e->prm.robot_size;
   float cell = e->prm.robot_size;
   if (!(cell > 0)) return fallback("robot_size <= 0");
@@ -414,69 +803,69 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   if (!level_kernels_support(qp, cell))
     return fallback("sample_num or expand_dist / robot_size outside the level kernels' range");
   TrgStatus st;
-#define ENS(ptr, capf, need) \
-  if ((st = dev_ensure(e, ptr, bb.capf, (size_t)(need))) != TRG_OK) return st
-#define ENSB(arr, bytes) \
-  if ((st = ensure_bytes(e, arr, (size_t)(bytes))) != TRG_OK) return st
-  ENS(B.nx, cap_nx, vcap);
-  ENS(B.ny, cap_ny, vcap);
-  ENS(B.nz, cap_nz, vcap);
-  ENS(B.nstate, cap_nstate, vcap);
+  const size_t wg_words = slots / 16 + 64 + 8;  // (>= one word per resolve workgroup, then the start tickets)
+  const size_t I = sizeof(int), FL = sizeof(float);
+  if ((st = ensure_all(e, {{&bb.nx, vcap * FL}, {&bb.ny, vcap * FL}, {&bb.nz, vcap * FL}, {&bb.nstate, vcap * I},
+                           {&bb.gcell, ncell * sizeof(GridCell)}, {&bb.ncov, vcap * sizeof(NodeCov)},
+                           {&bb.front0, fcap * I}, {&bb.front1, fcap * I}, {&bb.fxy0, fcap * sizeof(float2)},
+                           {&bb.fxy1, fcap * sizeof(float2)}})) != TRG_OK)
+    return st;
+  B.nx = (float *)bb.nx.p;
+  B.ny = (float *)bb.ny.p;
+  B.nz = (float *)bb.nz.p;
+  B.nstate = (int *)bb.nstate.p;
   B.vcap = (int)std::min<size_t>(vcap, 0x7FFFFFF0);
-  ENSB(bb.gcell, ncell * sizeof(GridCell));
   B.gcell = (GridCell *)bb.gcell.p;
-  ENSB(bb.ncov, vcap * sizeof(NodeCov));
   B.ncov = (NodeCov *)bb.ncov.p;
-  ENS(B.front_cur, cap_front0, fcap);
-  ENS(B.front_next, cap_front1, fcap);
-  ENSB(bb.fxy0, fcap * sizeof(float2));
-  ENSB(bb.fxy1, fcap * sizeof(float2));
+  B.front_cur = (int *)bb.front0.p;
+  B.front_next = (int *)bb.front1.p;
   B.fxy_cur = (float2 *)bb.fxy0.p;
   B.fxy_next = (float2 *)bb.fxy1.p;
   B.fcap = (int)fcap;
-  size_t ht_need = 1024;
-  while (ht_need < 2 * slots) ht_need <<= 1;
+  const size_t ht_need = hash_size(fcap, std::max(S, 1));
   for (LevelSet &l : bb.lv) {
-    ENSB(l.node_rec, fcap * sizeof(NodeRec));
-    ENSB(l.slot_rec, slots * sizeof(SlotRec));
-    ENSB(l.c_outcome, slots * sizeof(int));
-    ENSB(l.lv_hash, ht_need * sizeof(HashEnt));
+    if ((st = ensure_all(e, {{&l.node_rec, fcap * sizeof(NodeRec)}, {&l.slot_rec, slots * sizeof(SlotRec)},
+                             {&l.c_outcome, slots * I}, {&l.lv_hash, ht_need * sizeof(HashEnt)}})) != TRG_OK)
+      return st;
     l.use_resc = e->step3;
-    if (e->step3) ENSB(l.resc, slots * sizeof(RescueRec));
+    if (e->step3 && (st = ensure_bytes(e, l.resc, slots * sizeof(RescueRec))) != TRG_OK) return st;
     // tags start at 1 in every build: entries of earlier builds must not look current
     HIPCHK(e, hipMemsetAsync(l.lv_hash.p, 0, ht_need * sizeof(HashEnt), s));
   }
-  ENS(B.mid, cap_mid, edge_mid_floats(CALL_EVAL_BATCH));
-  ENS(B.unc_list, cap_unclist, 3 * BFS_UNC_CAP + BFS_TIE_CAP);  // even levels, odd levels, deferred evaluations; tied slots
+  // unc_list: even levels, odd levels, deferred evaluations; tied slots
+  if ((st = ensure_all(e, {{&bb.mid, edge_mid_floats(CALL_EVAL_BATCH) * FL},
+                           {&bb.unc_list, (3 * BFS_UNC_CAP + BFS_TIE_CAP) * I},
+                           {&bb.unc_rec, 3 * 3 * BFS_UNC_CAP * FL}, {&bb.mt_rec, 2 * MAPTIE_CAP * sizeof(MapTieRec)},
+                           {&bb.ctrs, BFS_CTR_COUNT * I}, {&bb.stats64, S64_WORDS * sizeof(unsigned long long)},
+                           {&bb.wg_state, wg_words * sizeof(unsigned long long)},
+                           {&bb.c_cell, slots * sizeof(unsigned long long)}, {&bb.nexp, vcap * sizeof(int4)},
+                           {&bb.nhits, vcap * I}, {&bb.scan_tmp, (std::max(slots, vcap) / 2048 + 8) * I}})) != TRG_OK)
+    return st;
+  B.mid = (float *)bb.mid.p;
+  B.unc_list = (int *)bb.unc_list.p;
   B.tie_list = B.unc_list + 3 * BFS_UNC_CAP;
-  ENS(B.unc_rec, cap_uncrec, 3 * 3 * BFS_UNC_CAP);
-  ENS(B.mt_rec, cap_mtrec, 2 * MAPTIE_CAP);
-  ENS(B.ctrs, cap_ctrs, BFS_CTR_COUNT);
-  ENS(B.stats64, cap_stats, 16 + 1024 * 8);
-  ENS(bb.flag, cap_flag, slots + 1);
-  ENSB(bb.wg_state, (slots / 16 + 64 + 8) * sizeof(unsigned long long));  // (>= one word per resolve workgroup)
+  B.unc_rec = (float *)bb.unc_rec.p;
+  B.mt_rec = (MapTieRec *)bb.mt_rec.p;
+  B.ctrs = (int *)bb.ctrs.p;
+  B.stats64 = (unsigned long long *)bb.stats64.p;
   B.wg_state = (unsigned long long *)bb.wg_state.p;
-  HIPCHK(e, hipMemsetAsync(B.wg_state, 0, (slots / 16 + 64 + 8) * sizeof(unsigned long long), s));  // epochs start at 1
+  HIPCHK(e, hipMemsetAsync(B.wg_state, 0, wg_words * sizeof(unsigned long long), s));  // epochs start at 1
   B.ticket = (unsigned *)(B.wg_state + (slots / 16 + 64));  // start tickets of the resolve workgroups: zero, like
-  unsigned ticket_base = 0;                                   // the host's count of the tickets drawn so far
+  ticket_base = 0;                                          // the host's count of the tickets drawn so far
   B.tl = nullptr;
   if (getenv("TRG_TIMELINE")) {
     const size_t tl_bytes = (size_t)(1 << 16) * 12 * 6 * sizeof(unsigned long long);
-    ENSB(bb.tl, tl_bytes);
+    if ((st = ensure_bytes(e, bb.tl, tl_bytes)) != TRG_OK) return st;
     B.tl = (unsigned long long *)bb.tl.p;
     HIPCHK(e, hipMemsetAsync(B.tl, 0, tl_bytes, s));
   }
-  ENSB(bb.c_cell, slots * sizeof(unsigned long long));
   B.c_cell = (unsigned long long *)bb.c_cell.p;
   HIPCHK(e, hipMemsetAsync(B.c_cell, 0, slots * sizeof(unsigned long long), s));  // (launch epochs start at 1 in every build)
-  ENSB(bb.nexp, vcap * sizeof(int4));
   B.nexp = (int4 *)bb.nexp.p;
-  ENSB(bb.nhits, vcap * sizeof(int));
   B.nhits = (int *)bb.nhits.p;
-  ENS(bb.scan_tmp, cap_scantmp, std::max(slots, vcap) / 2048 + 8);
   if (!bb.h_ctrs) {
-    HIPCHK(e, hipHostMalloc((void **)&bb.h_ctrs, 64 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(bb.h_ctrs, 0, 64 * sizeof(int));
+    HIPCHK(e, hipHostMalloc((void **)&bb.h_ctrs, H_CTRS_WORDS * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    memset(bb.h_ctrs, 0, H_CTRS_WORDS * sizeof(int));
   }
   {
     void *dp = nullptr;
@@ -485,232 +874,138 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   }
 
   bb.hm_state.clear();
-  bb.hm_upto = 0;
   bb.hm_x.clear();
   bb.hm_y.clear();
-  for (auto &v : bb.host_stats) v = 0;
+  bb.nodes_created = bb.nodes_invalid = 0;
   HIPCHK(e, hipMemsetAsync(B.gcell, 0, ncell * sizeof(GridCell), s));
   HIPCHK(e, hipMemsetAsync(B.ctrs, 0, BFS_CTR_COUNT * sizeof(int), s));
-  HIPCHK(e, hipMemsetAsync(B.stats64, 0, (16 + 1024 * 8) * sizeof(unsigned long long), s));
+  HIPCHK(e, hipMemsetAsync(B.stats64, 0, S64_WORDS * sizeof(unsigned long long), s));
 
-  // ---- root node ---------------------------------------------------------------------------------
-  {
-    const int one = 1, zero = 0, valid = TRG_NODE_VALID;
-    HIPCHK(e, hipMemcpyAsync(B.nx, &root_x, 4, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(B.ny, &root_y, 4, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(B.nz, &root_z, 4, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(B.nstate, &valid, 4, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(B.ctrs + BFS_CTR_V, &one, 4, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(B.front_cur, &zero, 4, hipMemcpyHostToDevice, s));
-    const float root_xy[2] = {root_x, root_y};
-    HIPCHK(e, hipMemcpyAsync(B.fxy_cur, root_xy, sizeof(root_xy), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipStreamSynchronize(s));  // the sources above are stack variables
-    launch_bfs_insert_nodes(B, 0, 1, s);
-  }
-
-  auto read_ctrs = [&]() -> TrgStatus {
-    HIPCHK(e, hipMemcpyAsync(bb.h_ctrs, B.ctrs, BFS_CTR_COUNT * sizeof(int), hipMemcpyDeviceToHost, s));
-    auto t0 = Clock::now();
-    HIPCHK(e, hipStreamSynchronize(s));
-    e->stats.ms_wait_gpu += ms_since(t0);
-    return TRG_OK;
-  };
-  // The level's counters reach the host without a copy in the stream: the last workgroup of
-  // the next level's k_level_sample writes them into pinned host memory with the level's stamp; the host polls
-  // the stamp.
-  int &stamp_serial = bb.stamp_serial;  // monotonic over the engine's life: a stale block never matches
-  constexpr long poll_query_mask = 0xFFFFFL;
-  auto wait_stamp = [&](int stamp) -> TrgStatus {
-    auto t0 = Clock::now();
-    volatile int *hv = bb.h_ctrs;
-    long spins = 0;
-    while (hv[BFS_CTR_DONE] != stamp || hv[BFS_CTR_COUNT - 1] != stamp) {
-      if ((++spins & poll_query_mask) == 0) {
-        // the kernels may have failed to launch or the queue may be gone: do not spin forever.  (Rarely:
-        // a stream query makes the runtime put a marker behind the last kernel, and the next level's
-        // first kernel then starts ~6 us late.)
-        const hipError_t q = hipStreamQuery(s);
-        if (q != hipErrorNotReady && q != hipSuccess)
-          return e->fail(TRG_ERR_DEVICE, std::string("level kernels: ") + hipGetErrorString(q));
-        if (q == hipSuccess && hv[BFS_CTR_DONE] != stamp && spins > (1L << 24))
-          return e->fail(TRG_ERR_DEVICE, "level counters were not published");
-      }
-      __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    e->stats.ms_wait_gpu += ms_since(t0);
-    return TRG_OK;
-  };
-  auto err_text = [](int code) {
-    std::string t;
-    if (code & BFS_ERR_GRID_OVERFLOW) t += "grid-cell overflow;";
-    if (code & BFS_ERR_NB_OVERFLOW) t += "neighbour list overflow;";
-    if (code & BFS_ERR_VCAP) t += "node capacity;";
-    if (code & BFS_ERR_TIE) t += "exact fp32 distance tie (kd-tree order decides);";
-    if (code & BFS_ERR_TIE_CLS) t += "exact fp32 distance tie among pre-level nodes;";
-    if (code & BFS_ERR_HASH) t += "hash table full;";
-    if (code & BFS_ERR_LEVEL_TOO_BIG) t += "BFS level too large;";
-    if (code & BFS_ERR_CLEAN) t += "clean remap;";
-    if (code & BFS_ERR_STALL) t += "resolve stalled;";
-    if (code & BFS_ERR_LOOKBACK) t += "commit look-back ran out (another process on the GPU?);";
-    if (code & BFS_ERR_STEP3) t += "step 3: neighbour list / call stride overflow or an uncertain slope gate;";
-    return t;
-  };
-  // host decision of the slope gates the device could not call (reference libm, trg.cpp:269-274);
-  // list: the parity's half of unc_list / unc_rec, entries index status_array
-  std::vector<int> unc_idx;
-  std::vector<float> unc_rec;
-  bool unc_changed = false;  // set when a provisional "not gated" turned out to be gated
-  auto resolve_uncertain = [&](int n_unc, void *status_base, size_t stride, int list_parity,
-                               int ctr_index) -> TrgStatus {
-    unc_changed = false;
-    if (n_unc > BFS_UNC_CAP) return fallback("too many uncertain slope gates in one batch");
-    unc_idx.resize(n_unc);
-    unc_rec.resize(3 * (size_t)n_unc);
-    HIPCHK(e, hipMemcpy(unc_idx.data(), B.unc_list + (size_t)list_parity * BFS_UNC_CAP,
-                        n_unc * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(unc_rec.data(), B.unc_rec + (size_t)list_parity * 3 * BFS_UNC_CAP,
-                        3 * (size_t)n_unc * sizeof(float), hipMemcpyDeviceToHost));
-    for (int k = 0; k < n_unc; ++k) {
-      int stt = 0;
-      char *addr = (char *)status_base + (size_t)unc_idx[k] * stride;
-      HIPCHK(e, hipMemcpy(&stt, addr, sizeof(int), hipMemcpyDeviceToHost));
-      e->stats.gate_uncertain++;
-      if (host_slope_gate(e, unc_rec[3 * k], unc_rec[3 * k + 1], unc_rec[3 * k + 2])) {
-        stt = EDGE_GATE;
-        unc_changed = true;
-      } else {
-        stt &= ~EDGE_GATE_UNCERTAIN;
-      }
-      HIPCHK(e, hipMemcpy(addr, &stt, sizeof(int), hipMemcpyHostToDevice));
-    }
-    const int zero = 0;
-    HIPCHK(e, hipMemcpy(B.ctrs + ctr_index, &zero, sizeof(int), hipMemcpyHostToDevice));
-    return TRG_OK;
-  };
-  auto slot_status = [&]() { return (void *)((char *)B.slot_rec + offsetof(SlotRec, status)); };
-
-  // ---- deferred wireEdge evaluations (node -> existing node), pipelined behind the level loop -------
-  // wireEdge returns at once when a pair is already wired (trg.cpp:255-267), so per unordered pair
-  // only its FIRST call is evaluated, then (after the loop) the remaining calls of the few pairs
-  // whose first call did not succeed.  "First call of its pair" is final as soon as the call's
-  // level is: the calls of finished levels are therefore handed over in batches to a second, low
-  // priority stream, where they fill the issue slots the latency-bound level kernels leave idle.
-  // The pair table is sized from the node capacity bound (every node is expanded at most once).
-  const size_t calls_bound = std::min<size_t>(vcap * (size_t)std::max(S, 1) * (size_t)CS, 0x7FFFFFF0u);
-  unsigned fht = 1024;
+  // Deferred wireEdge evaluations (node -> existing node), pipelined behind the level loop.  wireEdge
+  // returns at once when a pair is already wired (trg.cpp:255-267), so per unordered pair only its FIRST
+  // call is evaluated, then (after the loop) the remaining calls of the few pairs whose first call did not
+  // succeed.  "First call of its pair" is final as soon as the call's level is: the calls of finished levels
+  // are therefore handed over in batches to a second, low priority stream, where they fill the issue slots
+  // the latency-bound level kernels leave idle.  The pair table is sized from the node capacity bound
+  // (every node is expanded at most once).
+  calls_bound = std::min<size_t>(vcap * (size_t)std::max(S, 1) * (size_t)CS, 0x7FFFFFF0u);
+  fht = 1024;
   while ((unsigned long long)fht < (unsigned long long)calls_bound && fht < (1u << 31)) fht <<= 1;
-  ENS(F.ht_key, cap_fkey, fht);
-  ENS(F.ht_seq, cap_fseq, fht);
-  ENS(F.ok_seq, cap_fok, fht);
-  F.ht_size = fht;
-  // calls per batch (at least): about one batch per BFS level -- many small batches disturb the level
-  // kernels least (measured: 3.2 M -> 54.6 ms per C3 build, 100 k -> 53.2, 6 k -> 51.6; no overlap 54.5)
-  constexpr long long DEF_BATCH_MIN = 6000;
   const size_t sel_cap = (size_t)CALL_EVAL_BATCH + 2;
-  ENS(bb.sel_flag, cap_selflag, sel_cap);
-  ENS(bb.sel_off, cap_seloff, sel_cap + 1);
-  ENS(bb.sel_tmp, cap_seltmp, sel_cap / 2048 + 16);
+  if ((st = ensure_all(e, {{&bb.ht_key, fht * sizeof(unsigned long long)}, {&bb.ht_seq, fht * I},
+                           {&bb.ok_seq, fht * I}, {&bb.sel_flag, sel_cap * I}, {&bb.sel_off, (sel_cap + 1) * I},
+                           {&bb.sel_tmp, (sel_cap / 2048 + 16) * I}, {&bb.def_counts, I}})) != TRG_OK)
+    return st;
+  F.ht_key = (unsigned long long *)bb.ht_key.p;
+  F.ht_seq = (int *)bb.ht_seq.p;
+  F.ok_seq = (int *)bb.ok_seq.p;
+  F.ht_size = fht;
   // With step 3 the neighbour calls of a node sit BEFORE later calls in the log but are only known after the
   // loop (trg_step3.inc): "first call of its pair" is not final level by level, so nothing is evaluated beside
   // the loop.
-  const bool overlap = !e->step3 && e->defer_overlap;
+  overlap = !e->step3 && e->defer_overlap;
   if (overlap) {  // (otherwise the table is cleared after the loop, right before its first use)
     HIPCHK(e, hipMemsetAsync(F.ht_key, 0xFF, (size_t)fht * sizeof(unsigned long long), s));
     HIPCHK(e, hipMemsetAsync(F.ht_seq, 0x7F, (size_t)fht * sizeof(int), s));
   }
   HIPCHK(e, hipMemsetAsync(F.ok_seq, 0x7F, (size_t)fht * sizeof(int), s));  // (first used after the loop)
-  hipStream_t s_def = overlap ? e->s_edge : s;
-  long long def_lo = 0;  // first call not yet handed to the deferred pipeline
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> def_events;
-  constexpr int TIMED_BATCH_EVERY = 8;
-  size_t n_eval_batches = 0;
-  unsigned long long *d_def_total = B.stats64 + 5;  // calls the selections kept (device counter)
-  ENSB(bb.def_counts, sizeof(int));  // round 2's count of selected calls
-  auto eval_batch = [&](long long lo, long long n, const int *count_dev, hipStream_t st_) -> TrgStatus {
-    hipEvent_t a = nullptr, b = nullptr;
-    // (timed like the level kernels: every 8th batch, scaled up afterwards -- an event pair per batch was
-    // a fifth of the host's launch work per level)
-    if ((n_eval_batches++ % TIMED_BATCH_EVERY) == 0 && def_events.size() < 8192) {
-      HIPCHK(e, hipEventCreate(&a));
-      HIPCHK(e, hipEventCreate(&b));
-      HIPCHK(e, hipEventRecord(a, st_));
+  s_def = overlap ? e->s_edge : s;
+  return TRG_OK;
+}
+
+// ---- phase 2: the root node ------------------------------------------------------------------------
+TrgStatus Build::seed_root(float root_x, float root_y, float root_z) {
+  const int one = 1, zero = 0, valid = TRG_NODE_VALID;
+  HIPCHK(e, hipMemcpyAsync(B.nx, &root_x, 4, hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipMemcpyAsync(B.ny, &root_y, 4, hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipMemcpyAsync(B.nz, &root_z, 4, hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipMemcpyAsync(B.nstate, &valid, 4, hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipMemcpyAsync(B.ctrs + BFS_CTR_V, &one, 4, hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipMemcpyAsync(B.front_cur, &zero, 4, hipMemcpyHostToDevice, s));
+  const float root_xy[2] = {root_x, root_y};
+  HIPCHK(e, hipMemcpyAsync(B.fxy_cur, root_xy, sizeof(root_xy), hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipStreamSynchronize(s));  // the sources above are stack variables
+  launch_bfs_insert_nodes(B, 0, 1, s);
+  return TRG_OK;
+}
+
+// ---- deferred wireEdge evaluations -------------------------------------------------------------------------
+// calls [def_lo, c1) of finished levels -> pair table, first-of-pair selection, evaluation
+TrgStatus Build::launch_deferred(long long c1, bool in_loop) {
+  while (def_lo < c1) {
+    const long long c_hi = std::min<long long>(c1, def_lo + CALL_EVAL_BATCH);
+    const long long n = c_hi - def_lo;
+    hipStream_t st_ = in_loop ? s_def : s;
+    launch_first_insert(F, B, def_lo, c_hi, st_);
+    launch_calls_select(F, B, def_lo, c_hi, 1, (int *)bb.sel_flag.p, (int *)bb.sel_off.p, (int *)bb.sel_tmp.p,
+                        (int *)bb.sel_list.p + def_lo, B.stats64 + S64_DEF_KEPT, st_);
+    // the evaluations, timed like the level kernels: every 8th batch, scaled up afterwards (an event pair per
+    // batch was a fifth of the host's launch work per level)
+    Event t0, t1;
+    if ((n_eval_batches++ % 8) == 0 && def_events.size() < 8192) {
+      HIPCHK(e, hipEventCreate(&t0.ev));
+      HIPCHK(e, hipEventCreate(&t1.ev));
+      HIPCHK(e, hipEventRecord(t0.ev, st_));
     }
     // the number of selected calls lives on the device: the grid is an upper bound
-    launch_calls_eval(m.view, qp, B, bb.sel_list + lo, (int)n, count_dev, e->d_ctr, st_);
+    launch_calls_eval(m.view, qp, B, (int *)bb.sel_list.p + def_lo, (int)n, (int *)bb.sel_off.p + n, e->d_ctr, st_);
     e->stats.launches_edge_kernel++;
-    if (a) {
-      HIPCHK(e, hipEventRecord(b, st_));
-      def_events.emplace_back(a, b);
+    if (t0.ev) {
+      HIPCHK(e, hipEventRecord(t1.ev, st_));
+      def_events.emplace_back(std::move(t0), std::move(t1));
     }
-    return TRG_OK;
-  };
-  // calls [def_lo, c1) of finished levels -> pair table, first-of-pair selection, evaluation
-  auto launch_deferred = [&](long long c1, bool in_loop) -> TrgStatus {
-    while (def_lo < c1) {
-      const long long c_hi = std::min<long long>(c1, def_lo + CALL_EVAL_BATCH);
-      const long long n = c_hi - def_lo;
-      hipStream_t st_ = in_loop ? s_def : s;
-      launch_first_insert(F, B, def_lo, c_hi, st_);
-      launch_calls_select(F, B, def_lo, c_hi, 1, bb.sel_flag, bb.sel_off, bb.sel_tmp, bb.sel_list + def_lo,
-                          d_def_total, st_);
-      TrgStatus r = eval_batch(def_lo, n, bb.sel_off + n, st_);
-      if (r != TRG_OK) return r;
-      def_lo = c_hi;
-    }
-    return TRG_OK;
-  };
+    def_lo = c_hi;
+  }
+  return TRG_OK;
+}
 
-  // ---- level loop ----------------------------------------------------------------------------------
-  hipEvent_t ev0, ev1, evn0, evn1, ev_order, ev_nodes;
-  HIPCHK(e, hipEventCreate(&ev0));
-  HIPCHK(e, hipEventCreate(&ev1));
-  HIPCHK(e, hipEventCreate(&evn0));
-  HIPCHK(e, hipEventCreate(&evn1));
-  HIPCHK(e, hipEventCreateWithFlags(&ev_order, hipEventDisableTiming));
-  HIPCHK(e, hipEventCreateWithFlags(&ev_nodes, hipEventDisableTiming));
+// the call log grown to `need` calls, its contents kept
+TrgStatus Build::grow_call_log(size_t need) {
+  const size_t I = sizeof(int);
+  const size_t want = std::max(need, std::max<size_t>(bb.call_n1.bytes / I * 2, (size_t)4 << 20));
+  // the grow copies run on the NULL stream, which does not wait for the (non-blocking) level and
+  // deferred streams: everything that still writes the call log must have finished first
+  HIPCHK(e, hipStreamSynchronize(s));
+  if (s_def != s) HIPCHK(e, hipStreamSynchronize(s_def));
+  TrgStatus st;
+  for (DevArr *a : {&bb.call_n1, &bb.call_n2, &bb.call_status, &bb.call_w, &bb.call_dist, &bb.newid_of_call,
+                    &bb.call_slot})
+    if ((st = ensure_bytes(e, *a, want * I, true)) != TRG_OK) return st;
+  if ((st = ensure_bytes(e, bb.sel_list, (want + 1) * I, true)) != TRG_OK) return st;
+  B.call_n1 = (int *)bb.call_n1.p;
+  B.call_n2 = (int *)bb.call_n2.p;
+  B.call_status = (int *)bb.call_status.p;
+  B.call_w = (float *)bb.call_w.p;
+  B.call_dist = (float *)bb.call_dist.p;
+  B.newid_of_call = (int *)bb.newid_of_call.p;
+  F.call_slot = (int *)bb.call_slot.p;
+  return TRG_OK;
+}
+
+// ---- phase 3: the level loop ---------------------------------------------------------------------------
+TrgStatus Build::level_loop() {
+  TrgStatus st;
+  for (Event *ev : {&ev0, &ev1, &evn0, &evn1}) HIPCHK(e, hipEventCreate(&ev->ev));
+  for (Event *ev : {&ev_order, &ev_nodes}) HIPCHK(e, hipEventCreateWithFlags(&ev->ev, hipEventDisableTiming));
   bool have_expand = false;  // this level's expansion was issued by the previous iteration
   // Kernel timing inside the level loop is SAMPLED: an event pair around a kernel costs ~12 us of
   // stream time.  Every TIMED_EVERY-th level is timed and the totals are scaled by
   // launches / timed launches at the end (levels change slowly, so the subsample is unbiased).
   constexpr int TIMED_EVERY = 8;
-  auto timed_level = [&](int level) { return level % TIMED_EVERY == 0; };
   double ms_expand_timed = 0;
   uint64_t n_expand_timed = 0, n_expand_all = 0;
   bool expand_events_valid = false;  // ev0/ev1 bracket the expand launch of the current level
   int mcur = 1;
   int v_now = 1;  // nodes that exist before the current level (the root)
   long long call_base = 0;
-  int levels = 0;
-  int tag_serial = 0;        // one hash tag per level attempt
+  int tag_serial = 0;  // one hash tag per level attempt
   int cur_tag = 0;
-  int cur_ht = 0;            // hash size the current level's expand used
-  auto ht_for = [&](size_t nodes) {
-    int ht = 1024;
-    while ((size_t)ht < 2 * nodes * (size_t)S) ht <<= 1;
-    return ht;
-  };
-  int res_epoch = 0;  // one per k_level_resolve launch: the look-back words of other launches do not count
+  int cur_ht = 0;  // hash size the current level's expand used
   auto t_loop = Clock::now();
   while (mcur > 0) {
     const size_t level_slots = (size_t)mcur * S;
     const size_t need_calls = (size_t)call_base + level_slots * (size_t)CS;
-    if (bb.cap_c1 < need_calls) {
-      const size_t want = std::max(need_calls, std::max<size_t>(bb.cap_c1 * 2, (size_t)4 << 20));
-      // the grow copies run on the NULL stream, which does not wait for the (non-blocking) level and
-      // deferred streams: everything that still writes the call log must have finished first
-      HIPCHK(e, hipStreamSynchronize(s));
-      if (s_def != s) HIPCHK(e, hipStreamSynchronize(s_def));
-      if ((st = dev_ensure(e, B.call_n1, bb.cap_c1, want, true)) != TRG_OK) return st;
-      if ((st = dev_ensure(e, B.call_n2, bb.cap_c2, want, true)) != TRG_OK) return st;
-      if ((st = dev_ensure(e, B.call_status, bb.cap_cs, want, true)) != TRG_OK) return st;
-      if ((st = dev_ensure(e, B.call_w, bb.cap_cw, want, true)) != TRG_OK) return st;
-      if ((st = dev_ensure(e, B.call_dist, bb.cap_cd, want, true)) != TRG_OK) return st;
-      if ((st = ensure_bytes(e, bb.newid_of_call, want * sizeof(int), true)) != TRG_OK) return st;
-      B.newid_of_call = (int *)bb.newid_of_call.p;
-      if ((st = dev_ensure(e, F.call_slot, bb.cap_fslot, want, true)) != TRG_OK) return st;
-      if ((st = dev_ensure(e, bb.sel_list, bb.cap_sellist, want + 1, true)) != TRG_OK) return st;
-    }
+    if (bb.call_n1.bytes < need_calls * sizeof(int) && (st = grow_call_log(need_calls)) != TRG_OK) return st;
     const int parity = levels & 1;
     bb.lv[parity].apply(B);
     if (levels == e->debug_fallback_level) {
@@ -719,20 +1014,18 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
     }
     if (!have_expand) {
       cur_tag = ++tag_serial;
-      cur_ht = ht_for((size_t)mcur);
+      cur_ht = hash_size((size_t)mcur, S);
       B.ht_size = cur_ht;
-      HIPCHK(e, hipEventRecord(ev0, s));
+      HIPCHK(e, hipEventRecord(ev0.ev, s));
       launch_level_expand(m.view, qp, e->d_cos, e->d_sin, e->sampler.table_bits, e->sampler.seed,
                           e->epoch, B, mcur, nullptr, 0, parity, cur_tag, 0, e->d_ctr, s);
-      HIPCHK(e, hipEventRecord(ev1, s));
+      HIPCHK(e, hipEventRecord(ev1.ev, s));
       expand_events_valid = true;
     }
     B.ht_size = cur_ht;
     // The rest of the level is launched at once and the host looks at the counters once, at the end.
-    // The device treats a slope gate it could not call as "not gated" and a nearest-node tie as
-    // "lowest id"; when either happened (rare) the level's commit is taken back, the host supplies
-    // the exact answer, and resolve + commit run again / the level is replayed on the host.
-    const int V0 = v_now;
+    Level lv{levels, parity, mcur, v_now, level_slots, call_base, cur_tag,
+             parity ? BFS_CTR_NUNC1 : BFS_CTR_NUNC};
     // The next level's record set, hash size and tag: its expansion is launched right behind this
     // level's resolve, before the host has seen this level's counters (the frontier size is read from
     // the device, the grid is an upper bound).
@@ -742,334 +1035,47 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
     bb.lv[parity ^ 1].apply(Bn);
     const size_t next_cap_nodes =
         std::min<size_t>((size_t)B.fcap, std::max<size_t>(2 * (size_t)mcur, (size_t)mcur + 1024));
-    const int next_ht = ht_for(next_cap_nodes);
+    const int next_ht = hash_size(next_cap_nodes, S);
     Bn.ht_size = next_ht;
     int spec_bound = (int)std::min<size_t>(
         (size_t)B.fcap, std::min<size_t>(level_slots, (size_t)(mcur + std::max(128, mcur / 4))));
     if (e->debug_spec_bound > 0) spec_bound = std::min(spec_bound, e->debug_spec_bound);
-    const bool next_timed = timed_level(levels + 1);
+    const bool next_timed = (levels + 1) % TIMED_EVERY == 0;
     int next_tag = ++tag_serial;
     const int stall_hook = levels == e->debug_stall_level ? 1 : (levels == e->debug_lookback_level ? 2 : 0);
-    launch_level_resolve_commit(B, qp, mcur, TRG_NODE_VALID, call_base, V0, cur_tag, ++res_epoch, s, stall_hook,
-                                e->resolve_tickets != 0, &ticket_base);
-    const int stamp = ++stamp_serial;  // published by the next level's expansion, launched right below
-    if (next_timed) HIPCHK(e, hipEventRecord(evn0, s));
+    launch_level_resolve_commit(B, qp, mcur, TRG_NODE_VALID, call_base, lv.V0, cur_tag, ++res_epoch, s,
+                                stall_hook, e->resolve_tickets != 0, &ticket_base);
+    const int stamp = ++bb.stamp_serial;  // published by the next level's expansion, launched right below
+    if (next_timed) HIPCHK(e, hipEventRecord(evn0.ev, s));
     launch_level_expand(m.view, qp, e->d_cos, e->d_sin, e->sampler.table_bits, e->sampler.seed,
                         e->epoch, Bn, spec_bound, B.ctrs + BFS_CTR_MNEXT, 0, parity ^ 1, next_tag, stamp,
                         e->d_ctr, s);
-    if (next_timed) HIPCHK(e, hipEventRecord(evn1, s));
+    if (next_timed) HIPCHK(e, hipEventRecord(evn1.ev, s));
     bool next_events_valid = next_timed;
-    bool reexpand = false;  // set when the level's commit was redone: the frontier may differ
     if ((st = wait_stamp(stamp)) != TRG_OK) return st;
     {
       float ms = 0;
-      if (expand_events_valid && hipEventQuery(ev1) == hipSuccess &&
-          hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) {
+      if (expand_events_valid && hipEventQuery(ev1.ev) == hipSuccess &&
+          hipEventElapsedTime(&ms, ev0.ev, ev1.ev) == hipSuccess) {
         ms_expand_timed += ms;
         n_expand_timed++;
       }
       n_expand_all++;
     }
-    int err = bb.h_ctrs[BFS_CTR_ERR];
-    // test hook: pretend a tie was seen so that the undo + host-level replay are exercised on
-    // data that has no real tie
-    if (e->debug_tie_every > 0 && levels > 0 && levels % e->debug_tie_every == 0) err |= BFS_ERR_TIE;
-    if (err && getenv("TRG_TRACE_LEVELS"))
-      fprintf(stderr, "[trg bfs] level %d: err=%d (%s) mcur=%d v=%d mnext=%d\n", levels, err,
-              err_text(err).c_str(), mcur, bb.h_ctrs[BFS_CTR_V], bb.h_ctrs[BFS_CTR_MNEXT]);
-    int mnext = bb.h_ctrs[BFS_CTR_MNEXT];
-    int v_after = bb.h_ctrs[BFS_CTR_V];
-    const int unc_ctr = parity ? BFS_CTR_NUNC1 : BFS_CTR_NUNC;
-    int n_unc = bb.h_ctrs[unc_ctr];
-    const int n_mt = bb.h_ctrs[BFS_CTR_NMAPTIE + parity];
-    // nodes this level created / created Invalid (a level replayed on the host counts its own)
-    unsigned long long lvl_stats[2] = {(unsigned long long)(v_after - V0),
-                                       (unsigned long long)(v_after - V0 - mnext)};
-    int err_from_sample = err & BFS_ERR_TIE_CLS;
-    auto undo_level = [&]() -> TrgStatus {
-      reexpand = true;
-      HIPCHK(e, hipStreamSynchronize(s));  // the next level's expansion (now void) must be out of the way
-      launch_bfs_undo_slots(B, (int)level_slots, s);
-      // k_level_resolve polls outcomes: a rerun must find them undecided again
-      HIPCHK(e, hipMemsetAsync(B.c_outcome, 0, level_slots * sizeof(int), s));
-      int ctr_host[BFS_CTR_COUNT] = {0};
-      ctr_host[BFS_CTR_V] = V0;
-      HIPCHK(e, hipMemcpy(B.ctrs, ctr_host, BFS_CTR_NUNC2 * sizeof(int), hipMemcpyHostToDevice));  // (the deferred pipeline owns NUNC2)
-      return TRG_OK;
-    };
-    auto rerun_second_half = [&](bool ticketed = false, int hook = 0) -> TrgStatus {
-      launch_level_resolve_commit(B, qp, mcur, TRG_NODE_VALID, call_base, V0, cur_tag, ++res_epoch, s, hook,
-                                  ticketed || e->resolve_tickets != 0, &ticket_base);
-      TrgStatus r = read_ctrs();  // (rare path: a plain copy)
-      if (r != TRG_OK) return r;
-      // (what k_level_sample reported about the level stays true: that kernel does not run again)
-      err = bb.h_ctrs[BFS_CTR_ERR] | err_from_sample;
-      if (e->debug_tie_every > 0 && levels > 0 && levels % e->debug_tie_every == 0) err |= BFS_ERR_TIE;
-      mnext = bb.h_ctrs[BFS_CTR_MNEXT];
-      v_after = bb.h_ctrs[BFS_CTR_V];
-      lvl_stats[0] = (unsigned long long)(v_after - V0);
-      lvl_stats[1] = (unsigned long long)(v_after - V0 - mnext);
-      return TRG_OK;
-    };
-    auto settle_ties_in_place = [&](bool *settled) -> TrgStatus {
-      *settled = false;
-      int ntie = 0;
-      HIPCHK(e, hipMemcpy(&ntie, B.ctrs + BFS_CTR_NTIE, sizeof(int), hipMemcpyDeviceToHost));
-      if (ntie <= 0 || ntie > BFS_TIE_CAP) return TRG_OK;
-      std::vector<int> tslots(ntie);
-      HIPCHK(e, hipMemcpy(tslots.data(), B.tie_list, (size_t)ntie * sizeof(int), hipMemcpyDeviceToHost));
-      std::sort(tslots.begin(), tslots.end());
-      tslots.erase(std::unique(tslots.begin(), tslots.end()), tslots.end());
-      if (tslots.front() < 0 || (size_t)tslots.back() >= level_slots) return TRG_OK;
-      // which slots created a node (outcomes 3 / 4): the nodes that existed at a slot's turn are
-      // V0 + the creations of the slots before it
-      std::vector<int> oc((size_t)tslots.back() + 1);
-      HIPCHK(e, hipMemcpy(oc.data(), B.c_outcome, oc.size() * sizeof(int), hipMemcpyDeviceToHost));
-      if ((int)bb.hm_x.size() < v_after) {  // positions: kd_tie_winner walks them in insertion order
-        const size_t at = bb.hm_x.size(), n = (size_t)v_after - at;
-        bb.hm_x.resize(v_after);
-        bb.hm_y.resize(v_after);
-        HIPCHK(e, hipMemcpy(bb.hm_x.data() + at, B.nx + at, n * sizeof(float), hipMemcpyDeviceToHost));
-        HIPCHK(e, hipMemcpy(bb.hm_y.data() + at, B.ny + at, n * sizeof(float), hipMemcpyDeviceToHost));
-      }
-      const float *ax = bb.hm_x.data(), *ay = bb.hm_y.data();
-      auto d2_of = [](float nx_, float ny_, float qx, float qy) {
-        float acc = 0;  // the reference's accumulation order (kdtree.c:339-342)
-        acc += (nx_ - qx) * (nx_ - qx);
-        acc += (ny_ - qy) * (ny_ - qy);
-        return acc;
-      };
-      struct Patch {
-        size_t at;
-        int n2, st;
-      };
-      std::vector<Patch> patches;
-      std::vector<int> tied;
-      size_t scanned = 0;
-      int created_before = 0;
-      for (int sl : tslots) {
-        for (; scanned < (size_t)sl; ++scanned) created_before += (oc[scanned] == 3 || oc[scanned] == 4);
-        const int V_at = V0 + created_before;
-        SlotRec sr;
-        int u = -1;
-        HIPCHK(e, hipMemcpy(&sr, B.slot_rec + sl, sizeof(SlotRec), hipMemcpyDeviceToHost));
-        HIPCHK(e, hipMemcpy(&u, B.front_cur + sl / S, sizeof(int), hipMemcpyDeviceToHost));
-        if ((sr.cls & SLOT_CLS_MASK) == 0) continue;
-        // nearest node: the pre-level one the device found (all of them if that was not unique) ...
-        float best = sr.nn0 >= 0 ? sr.d0sq : INFINITY;
-        tied.clear();
-        if (sr.nn0 >= 0 && (sr.cls & SLOT_TIE)) {
-          for (int i = 0; i < V0; ++i)
-            if (d2_of(ax[i], ay[i], sr.x, sr.y) == best) tied.push_back(i);
-        } else if (sr.nn0 >= 0) {
-          tied.push_back(sr.nn0);
-        }
-        // ... against the nodes this level created before the slot's turn
-        for (int i = V0; i < V_at; ++i) {
-          const float dd = d2_of(ax[i], ay[i], sr.x, sr.y);
-          if (dd < best) {
-            best = dd;
-            tied.assign(1, i);
-          } else if (dd == best) {
-            tied.push_back(i);
-          }
-        }
-        if (tied.empty()) return TRG_OK;
-        int nn = tied[0];
-        if (tied.size() > 1) {
-          e->stats.nn_ties++;
-          std::sort(tied.begin(), tied.end());
-          nn = kd_tie_winner(ax, ay, V_at, sr.x, sr.y, tied);
-        }
-        int nn_state = 0;
-        HIPCHK(e, hipMemcpy(&nn_state, B.nstate + nn, sizeof(int), hipMemcpyDeviceToHost));
-        const int kind = nn_state == TRG_NODE_INVALID ? 1 : (std::sqrt(best) < e->prm.robot_size ? 2 : 3);
-        const bool dev_creates = oc[sl] == 3 || oc[sl] == 4;
-        if ((kind == 3) != dev_creates) return TRG_OK;  // the level's node set is in doubt: replay it
-        if (kind == 3) continue;                          // creates either way: its record stands
-        patches.push_back({(size_t)call_base + (size_t)sl, kind == 2 ? nn : -1,
-                           (kind == 2 && nn != u) ? CALL_PENDING : CALL_NONE});
-      }
-      for (const Patch &pt : patches) {
-        HIPCHK(e, hipMemcpy(B.call_n2 + pt.at, &pt.n2, sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(e, hipMemcpy(B.call_status + pt.at, &pt.st, sizeof(int), hipMemcpyHostToDevice));
-      }
-      launch_bfs_clear_tie(B, s);
-      *settled = true;
-      return TRG_OK;
-    };
-    if (e->step3 && n_unc > 0)
-      // (the rescue search of k_level_spec3 ran on the provisional verdict of that gate)
-      return fallback("a slope gate left to the host's libm in a build with expandGraph's step 3");
-    if (CS > 1 && ((err & BFS_ERR_SOFT & ~BFS_ERR_STALL) || n_mt > 0))
-      // (the host repairs of nearest-node ties and map-point ties are written for the dense call log and
-      // know nothing of step 3: such a build goes to the host replay as a whole)
-      return fallback("exact fp32 distance tie in a build with expandGraph's step 3");
-    bool undone = false;
-    const auto t_rare = Clock::now();
-    const bool any_rare = n_mt > 0 || n_unc > 0 || (err & (BFS_ERR_SOFT | BFS_ERR_LOOKBACK));
-    constexpr int ERR_WAIT = BFS_ERR_STALL | BFS_ERR_LOOKBACK;
-    if ((err & ERR_WAIT) && !(err & ~(BFS_ERR_SOFT | ERR_WAIT))) {
-      // A bounded wait of the resolve launch ran out: the hardware did not start its workgroups in index
-      // order (another process's kernels on the card).  The level is taken back and the launch repeated
-      // with start tickets as logical indices: every wait is then for a workgroup that is already
-      // running, whatever the dispatch order.  (Test hook debug_wait_rerun: the repeat fails as well.)
-      if ((st = undo_level()) != TRG_OK) return st;
-      const int hook = e->debug_wait_rerun ? ((err & BFS_ERR_LOOKBACK) ? 2 : 1) : 0;
-      if ((st = rerun_second_half(true, hook)) != TRG_OK) return st;
-      e->stats.bfs_ticket_reruns++;
-    }
-    if (err & ~BFS_ERR_SOFT) {
-      if (any_rare) e->stats.ms_rare_events += ms_since(t_rare);
-      return fallback(err_text(err));
-    }
-    if (n_mt > 0) {
-      // accepted samples whose elevation hung on a nearest-map-point tie: the device took the lowest
-      // cloud index; fetch the reference's choice and, if a z changed, re-evaluate that sample's
-      // speculative edge and redo resolve + commit (sample positions and classes do not depend on z)
-      std::vector<MapTieRec> recs((size_t)std::min(n_mt, MAPTIE_CAP));
-      HIPCHK(e, hipMemcpy(recs.data(), B.mt_rec + parity * MAPTIE_CAP, recs.size() * sizeof(MapTieRec),
-                          hipMemcpyDeviceToHost));
-      if (n_mt > MAPTIE_CAP) e->stats.map_nn_unresolved += (uint64_t)(n_mt - MAPTIE_CAP);
-      bool z_changed = false;
-      for (const MapTieRec &r : recs) {
-        float z_exact = 0, z_dev = 0;
-        bool found = false;
-        if ((st = map_nn_exact(e, m, r.qx, r.qy, &z_exact, &found)) != TRG_OK) return st;
-        SlotRec sr;
-        HIPCHK(e, hipMemcpy(&sr, B.slot_rec + r.slot, sizeof(SlotRec), hipMemcpyDeviceToHost));
-        z_dev = sr.z;
-        if (!found || z_exact == z_dev) continue;
-        sr.z = z_exact;
-        z_changed = true;
-        if ((sr.cls & SLOT_CLS_MASK) == 2) {
-          // the candidate's parent edge with the corrected elevation (position-only part of wireEdge)
-          int parent = 0;
-          float p1[3], p2[3] = {r.qx, r.qy, z_exact}, wgt = 0, dd = 0;
-          HIPCHK(e, hipMemcpy(&parent, B.front_cur + r.slot / S, sizeof(int), hipMemcpyDeviceToHost));
-          HIPCHK(e, hipMemcpy(&p1[0], B.nx + parent, sizeof(float), hipMemcpyDeviceToHost));
-          HIPCHK(e, hipMemcpy(&p1[1], B.ny + parent, sizeof(float), hipMemcpyDeviceToHost));
-          HIPCHK(e, hipMemcpy(&p1[2], B.nz + parent, sizeof(float), hipMemcpyDeviceToHost));
-          int32_t raw = 0;
-          if ((st = edges_sync(e, e->gmap, p1, p2, 1, &raw, nullptr, &wgt, &dd, false)) != TRG_OK) return st;
-          if (raw & EDGE_GATE_UNCERTAIN) {
-            e->stats.gate_uncertain++;
-            raw = host_slope_gate(e, p1[2], p2[2], dd) ? EDGE_GATE : (raw & ~EDGE_GATE_UNCERTAIN);
-          }
-          if ((raw & EDGE_STATUS_MASK) != EDGE_OK) wgt = 0.0f;
-          sr.status = raw;
-          sr.dist = dd;
-          sr.cov[0] = wgt;  // the weight itself (already clamped): k_node_weights takes it as given
-          sr.w_given = 1;
-        }
-        HIPCHK(e, hipMemcpy(B.slot_rec + r.slot, &sr, sizeof(SlotRec), hipMemcpyHostToDevice));
-      }
-      if (z_changed) {
-        if ((st = undo_level()) != TRG_OK) return st;  // also clears the tie / gate counters
-        if (n_unc > 0) {
-          // the level's uncertain gates are decided before the second half runs again (the entry of
-          // a re-evaluated slot is stale but harmless: its status no longer carries the flag)
-          if ((st = resolve_uncertain(std::min(n_unc, BFS_UNC_CAP), slot_status(), sizeof(SlotRec), parity,
-                                      unc_ctr)) != TRG_OK)
-            return st;
-          n_unc = 0;
-        }
-        if ((st = rerun_second_half()) != TRG_OK) return st;
-        if (err & ~BFS_ERR_SOFT) return fallback(err_text(err));
-      } else {
-        const int zero = 0;
-        HIPCHK(e, hipMemcpy(B.ctrs + BFS_CTR_NMAPTIE + parity, &zero, sizeof(int), hipMemcpyHostToDevice));
-      }
-    }
-    if (n_unc > 0) {
-      if ((st = resolve_uncertain(n_unc, slot_status(), sizeof(SlotRec), parity, unc_ctr)) != TRG_OK) return st;
-      if (unc_changed) {
-        // a speculative edge the level relied on is in fact gated: redo the second half
-        if ((st = undo_level()) != TRG_OK) return st;
-        undone = true;
-        if (!(err & BFS_ERR_SOFT)) {
-          if ((st = rerun_second_half()) != TRG_OK) return st;
-          if (err & ~BFS_ERR_SOFT) return fallback(err_text(err));
-          undone = false;
-        }
-      }
-    }
-    if ((err & BFS_ERR_SOFT) == BFS_ERR_TIE_CLS && !undone) {
-      // Only ties among nodes that existed before the level: nothing else of the level is in doubt.
-      // The reference's winner (kd-tree visiting order, host_index.h) replaces the device's pick in the
-      // slot records and resolve + commit run again -- no host replay of the whole level.
-      std::vector<SlotRec> srec(level_slots);
-      HIPCHK(e, hipMemcpy(srec.data(), B.slot_rec, level_slots * sizeof(SlotRec), hipMemcpyDeviceToHost));
-      std::vector<float> all_x, all_y;
-      std::vector<int> tied;
-      for (size_t sl = 0; sl < level_slots; ++sl) {
-        SlotRec &sr = srec[sl];
-        if (!(sr.cls & SLOT_TIE) || (sr.cls & SLOT_CLS_MASK) == 0 || sr.nn0 < 0) continue;
-        if (all_x.empty()) {
-          all_x.resize(V0);
-          all_y.resize(V0);
-          HIPCHK(e, hipMemcpy(all_x.data(), B.nx, (size_t)V0 * sizeof(float), hipMemcpyDeviceToHost));
-          HIPCHK(e, hipMemcpy(all_y.data(), B.ny, (size_t)V0 * sizeof(float), hipMemcpyDeviceToHost));
-        }
-        tied.clear();
-        for (int i = 0; i < V0; ++i) {
-          float acc = 0;  // the reference's accumulation order (kdtree.c:339-342)
-          acc += (all_x[i] - sr.x) * (all_x[i] - sr.x);
-          acc += (all_y[i] - sr.y) * (all_y[i] - sr.y);
-          if (acc == sr.d0sq) tied.push_back(i);
-        }
-        e->stats.nn_ties++;
-        if (tied.size() > 1) sr.nn0 = kd_tie_winner(all_x.data(), all_y.data(), V0, sr.x, sr.y, tied);
-        sr.cls &= ~SLOT_TIE;
-        HIPCHK(e, hipMemcpy(B.slot_rec + sl, &sr, sizeof(SlotRec), hipMemcpyHostToDevice));
-      }
-      err_from_sample = 0;  // settled
-      if ((st = undo_level()) != TRG_OK) return st;
-      if ((st = rerun_second_half()) != TRG_OK) return st;
-      if (err & ~BFS_ERR_SOFT) return fallback(err_text(err));
-      e->stats.bfs_tie_fixups++;
-    }
-    if ((err & BFS_ERR_SOFT) == BFS_ERR_TIE && !undone && e->tie_inplace &&
-        !(e->debug_tie_every > 0 && levels > 0 && levels % e->debug_tie_every == 0)) {
-      // A tie between two nearest-node candidates touches only the slots that met it: whichever of
-      // the tied nodes wins, the distance -- hence "creates a node or not" -- is the same unless their
-      // states differ, and nobody waits for a sample that does not create.  The committed level
-      // stands; the host decides the listed slots as the reference would (kd-tree visiting order,
-      // host_index.h) and rewrites their call records.  (States differ and one outcome creates: the
-      // level is replayed below.)
-      bool settled = false;
-      if ((st = settle_ties_in_place(&settled)) != TRG_OK) return st;
-      if (settled) {
-        err &= ~BFS_ERR_TIE;
-        e->stats.bfs_tie_fixups++;
-      }
-    }
-    bool replayed = false;
-    if (err & BFS_ERR_SOFT) {
-      // exact fp32 distance tie (or a resolve whose bounded wait ran out): this one level is replayed
-      // on the host, then the device goes on
-      if (CS > 1) return fallback("a level of a build with expandGraph's step 3 needs the host replay");
-      if (!undone && (st = undo_level()) != TRG_OK) return st;
-      int vnew = V0;
-      if ((st = replay_level_on_host(e, bb, mcur, V0, call_base, &vnew, &mnext)) != TRG_OK) return st;
-      v_after = vnew;
-      replayed = true;
-    }
-    if (any_rare) {
-      e->stats.ms_rare_events += ms_since(t_rare);
-      if (getenv("TRG_TRACE_LEVELS"))
-        fprintf(stderr, "[trg bfs] level %d: rare events (map ties %d, uncertain gates %d, err %d%s) took %.3f ms\n",
-                levels, n_mt, n_unc, err, replayed ? ", host replay" : "", ms_since(t_rare));
-    }
-    // the level is final: its statistics (a replayed level counted draws / samples / nodes itself)
-    if (!replayed) {
-      bb.host_stats[2] += lvl_stats[0];
-      bb.host_stats[3] += lvl_stats[1];
+    read_level(lv, true);
+    if (lv.err && getenv("TRG_TRACE_LEVELS"))
+      fprintf(stderr, "[trg bfs] level %d: err=%d (%s) mcur=%d v=%d mnext=%d\n", levels, lv.err,
+              err_text(lv.err).c_str(), mcur, lv.v_after, lv.mnext);
+    if ((st = repair_level(lv)) != TRG_OK) return st;
+    // the level is final: its statistics (a replayed level counted its nodes itself)
+    if (!lv.replayed) {
+      bb.nodes_created += (unsigned long long)(lv.v_after - lv.V0);
+      bb.nodes_invalid += (unsigned long long)(lv.v_after - lv.V0 - lv.mnext);
     }
     // the next level's expansion: redo it after a redone commit or when its hash was sized too
     // small, top it up past the launch bound
-    if (reexpand || (size_t)mnext > next_cap_nodes) {
-      if (!reexpand) HIPCHK(e, hipStreamSynchronize(s));
+    if (lv.reexpand || (size_t)lv.mnext > next_cap_nodes) {
+      if (!lv.reexpand) HIPCHK(e, hipStreamSynchronize(s));
       int ctr_fix[3] = {0, 0, 0};
       HIPCHK(e, hipMemcpy(B.ctrs + BFS_CTR_NMAPTIE, ctr_fix, 2 * sizeof(int), hipMemcpyHostToDevice));
       HIPCHK(e, hipMemcpy(B.ctrs + ((parity ^ 1) ? BFS_CTR_NUNC1 : BFS_CTR_NUNC), ctr_fix, sizeof(int),
@@ -1077,9 +1083,9 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
       have_expand = false;  // issued at the top of the next iteration with a fresh tag
       next_events_valid = false;
     } else {
-      if (mnext > spec_bound)
+      if (lv.mnext > spec_bound)
         launch_level_expand(m.view, qp, e->d_cos, e->d_sin, e->sampler.table_bits, e->sampler.seed,
-                            e->epoch, Bn, mnext, nullptr, spec_bound, parity ^ 1, next_tag, 0, e->d_ctr, s);
+                            e->epoch, Bn, lv.mnext, nullptr, spec_bound, parity ^ 1, next_tag, 0, e->d_ctr, s);
       have_expand = true;
       cur_tag = next_tag;
       cur_ht = next_ht;
@@ -1087,12 +1093,11 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
     std::swap(ev0, evn0);
     std::swap(ev1, evn1);
     expand_events_valid = next_events_valid;
-    v_now = v_after;
+    v_now = lv.v_after;
     std::swap(B.front_cur, B.front_next);
     std::swap(B.fxy_cur, B.fxy_next);
-    std::swap(bb.cap_front0, bb.cap_front1);
     call_base += (long long)level_slots * CS;
-    mcur = mnext;
+    mcur = lv.mnext;
     levels++;
     // the calls of the levels that are final by now: into the deferred pipeline, a batch at a time
     if (overlap && call_base - def_lo >= DEF_BATCH_MIN && call_base < 0x7FFFFFF0LL)
@@ -1105,12 +1110,16 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   if (n_expand_timed)
     e->stats.ms_sample_kernel += ms_expand_timed * (double)n_expand_all / (double)n_expand_timed;
   e->stats.launches_sample_kernel += n_expand_all;
-  auto t_def = Clock::now();
-  const int V = v_now;
-  const long long ncalls = call_base;
+  V = v_now;
+  ncalls = call_base;
   e->stats.sync_batches += (uint64_t)levels;
+  return TRG_OK;
+}
 
-  // ---- rest of the deferred wireEdge evaluations ------------------------------------------------------
+// ---- phase 4: the rest of the deferred wireEdge evaluations (round 1), then round 2 ----------------------
+TrgStatus Build::finish_deferred() {
+  TrgStatus st;
+  auto t_def = Clock::now();
   if (ncalls >= 0x7FFFFFF0LL) return fallback("call log too long");
   if ((size_t)ncalls > calls_bound) return fallback("more wireEdge calls than the node capacity bound allows");
   if (!overlap) {
@@ -1122,14 +1131,14 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   if (e->step3) {
     // step 3 (trg.cpp:429-444): the node tree rebuilt on the device, every valid node's neighbour calls into
     // the entries behind its creating call; the deferred pipeline below takes them like all other calls
-    ENSB(bb.s3_scratch, (6 * (size_t)V + 8) * sizeof(int));
-    if (launch_step3_calls(B, V, e->prm.expand_dist, (int *)bb.s3_scratch.p, bb.h_ctrs + 40, s) != 0)
+    if ((st = ensure_bytes(e, bb.s3_scratch, (6 * (size_t)V + 8) * sizeof(int))) != TRG_OK) return st;
+    if (launch_step3_calls(B, V, e->prm.expand_dist, (int *)bb.s3_scratch.p, bb.h_ctrs + H_STEP3_LEFT, s) != 0)
       return e->fail(TRG_ERR_DEVICE, "step-3 call generation failed");
     HIPCHK(e, hipGetLastError());
   }
   if (overlap) {  // what ran beside the loop must be complete before the main stream goes on with it
-    HIPCHK(e, hipEventRecord(ev_order, e->s_edge));
-    HIPCHK(e, hipStreamWaitEvent(s, ev_order, 0));
+    HIPCHK(e, hipEventRecord(ev_order.ev, e->s_edge));
+    HIPCHK(e, hipStreamWaitEvent(s, ev_order.ev, 0));
   }
   if ((st = launch_deferred(ncalls, false)) != TRG_OK) return st;  // round 1 of the calls not yet handed over
   // while the GPU evaluates: the reference's graph.nodes[node_id] = node for ids 0..V-1 in creation
@@ -1139,137 +1148,125 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   std::vector<int> map_order;
   e->nodes_sim.iteration_order(map_order);
   // ... and goes to the device on the (idle) second stream, for the renumbering kernels of cleanGraph
-  ENS(bb.d_map_order, cap_maporder, (size_t)V + 1);
+  if ((st = ensure_bytes(e, bb.map_order, ((size_t)V + 1) * sizeof(int))) != TRG_OK) return st;
   if (V > 0)
-    HIPCHK(e, hipMemcpyAsync(bb.d_map_order, map_order.data(), (size_t)V * sizeof(int), hipMemcpyHostToDevice,
+    HIPCHK(e, hipMemcpyAsync(bb.map_order.p, map_order.data(), (size_t)V * sizeof(int), hipMemcpyHostToDevice,
                              e->s_edge));
-  HIPCHK(e, hipEventRecord(ev_order, e->s_edge));
+  HIPCHK(e, hipEventRecord(ev_order.ev, e->s_edge));
   HIPCHK(e, hipStreamSynchronize(s_def));
   if (s_def != s) HIPCHK(e, hipStreamSynchronize(s));  // (the evaluations after the loop run in the main stream)
   double ms_edges = 0;
   for (auto &ev : def_events) {
     float ms = 0;
-    if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) ms_edges += ms;
-    (void)hipEventDestroy(ev.first);
-    (void)hipEventDestroy(ev.second);
+    if (hipEventElapsedTime(&ms, ev.first.ev, ev.second.ev) == hipSuccess) ms_edges += ms;
   }
   if (!def_events.empty()) ms_edges *= (double)n_eval_batches / (double)def_events.size();
   def_events.clear();
   // round 2: every remaining call of the (few) pairs whose first call failed or was left to the host
-  uint64_t round2_evals = 0;
-  {
-    int *d_n2 = (int *)bb.def_counts.p;
-    int *h_n2 = bb.h_ctrs + 34;  // pinned
-    HIPCHK(e, hipMemsetAsync(d_n2, 0, sizeof(int), s));
-    launch_calls_select2_append(F, B, ncalls, bb.sel_list, d_n2, d_def_total, s);
-    HIPCHK(e, hipMemcpyAsync(h_n2, d_n2, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    const int nsel = *h_n2;
-    // (a batch of evaluations shares the edge scratch: at most CALL_EVAL_BATCH at a time)
-    for (long long q0 = 0; q0 < nsel; q0 += CALL_EVAL_BATCH) {
-      const int nq = (int)std::min<long long>(CALL_EVAL_BATCH, nsel - q0);
-      HIPCHK(e, hipEventRecord(ev0, s));
-      launch_calls_eval(m.view, qp, B, bb.sel_list + q0, nq, nullptr, e->d_ctr, s);
-      e->stats.launches_edge_kernel++;
-      HIPCHK(e, hipEventRecord(ev1, s));
-      HIPCHK(e, hipEventSynchronize(ev1));
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) ms_edges += ms;
-      round2_evals += (uint64_t)nq;
-    }
+  int *d_n2 = (int *)bb.def_counts.p;
+  int *h_n2 = bb.h_ctrs + H_ROUND2_CALLS;
+  HIPCHK(e, hipMemsetAsync(d_n2, 0, sizeof(int), s));
+  launch_calls_select2_append(F, B, ncalls, (int *)bb.sel_list.p, d_n2, B.stats64 + S64_DEF_KEPT, s);
+  HIPCHK(e, hipMemcpyAsync(h_n2, d_n2, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  const int nsel = *h_n2;
+  // (a batch of evaluations shares the edge scratch: at most CALL_EVAL_BATCH at a time)
+  for (long long q0 = 0; q0 < nsel; q0 += CALL_EVAL_BATCH) {
+    const int nq = (int)std::min<long long>(CALL_EVAL_BATCH, nsel - q0);
+    HIPCHK(e, hipEventRecord(ev0.ev, s));
+    launch_calls_eval(m.view, qp, B, (int *)bb.sel_list.p + q0, nq, nullptr, e->d_ctr, s);
+    e->stats.launches_edge_kernel++;
+    HIPCHK(e, hipEventRecord(ev1.ev, s));
+    HIPCHK(e, hipEventSynchronize(ev1.ev));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev0.ev, ev1.ev) == hipSuccess) ms_edges += ms;
   }
   e->stats.ms_edge_kernel += ms_edges;
   if ((st = read_ctrs()) != TRG_OK) return st;
   if (bb.h_ctrs[BFS_CTR_ERR]) return fallback(err_text(bb.h_ctrs[BFS_CTR_ERR]));
-  if (bb.h_ctrs[BFS_CTR_NUNC2] > 0) {
-    if ((st = resolve_uncertain(bb.h_ctrs[BFS_CTR_NUNC2], B.call_status, sizeof(int), 2, BFS_CTR_NUNC2)) != TRG_OK)
-      return st;
-  }
-  (void)round2_evals;
-
+  const int n_unc2 = bb.h_ctrs[BFS_CTR_NUNC2];
+  if (n_unc2 > 0 && (st = resolve_uncertain(n_unc2, B.call_status, sizeof(int), 2, BFS_CTR_NUNC2)) != TRG_OK)
+    return st;
   e->stats.ms_deferred = ms_since(t_def);
-  // ---- dedupe + CSR in creation order --------------------------------------------------------------
-  auto t_fin = Clock::now();
-  const bool trace_fin = getenv("TRG_TIMING") != nullptr;
-  auto lap = [&](const char *what) {
-    if (!trace_fin) return;
-    (void)hipStreamSynchronize(s);
-    fprintf(stderr, "[trg finalize] %-28s %8.3f ms\n", what, ms_since(t_fin));
-  };
-  auto mark = [&](const char *what) {  // host time only: the stream keeps running
-    if (trace_fin) fprintf(stderr, "[trg finalize]   (host) %-20s %8.3f ms\n", what, ms_since(t_fin));
-  };
-  ENS(F.deg, cap_fdeg, (size_t)V + 1);
-  ENS(F.fill, cap_ffill, (size_t)V + 1);
-  ENS(F.rowptr, cap_frow, (size_t)V + 2);
+  return TRG_OK;
+}
+
+// ---- phase 5: dedupe + CSR in creation order (and the graph before cleanGraph, on request) ----------
+TrgStatus Build::assemble_csr() {
+  TrgStatus st;
+  t_fin = Clock::now();
+  trace_fin = getenv("TRG_TIMING") != nullptr;
   // the edge count is not known to the host before the scatter runs: the arrays are sized by the
   // bound (every call wires at most one pair, two directed entries)
-  const size_t e_bound = 2 * (size_t)ncalls;
-  ENS(F.col, cap_fcol, e_bound + 1);
-  ENS(F.seq, cap_fseqe, e_bound + 1);
-  ENS(F.w, cap_fw, e_bound + 1);
-  ENS(F.dist, cap_fdist, e_bound + 1);
-  ENS(bb.d_new2old, cap_n2o, (size_t)V + 1);
-  ENS(bb.d_old2new, cap_o2n, (size_t)V + 1);
-  ENS(bb.d_deg_new, cap_degn, (size_t)V + 1);
-  ENS(bb.d_rowptr_new, cap_rown, (size_t)V + 2);
-  ENS(bb.d_keep_flag, cap_keepf, (size_t)V + 1);
-  ENS(bb.d_keep_pos, cap_keepp, (size_t)V + 2);
-  ENS(bb.d_col2, cap_col2, e_bound + 1);
-  ENS(bb.d_w2, cap_w2, e_bound + 1);
-  ENS(bb.d_dist2, cap_dist2, e_bound + 1);
-  ENS(bb.d_xyz2, cap_xyz2, 3 * (size_t)V + 3);
-  ENS(bb.d_state2, cap_state2, (size_t)V + 1);
-  HIPCHK(e, hipMemsetAsync(F.deg, 0, ((size_t)V + 1) * sizeof(int), s));
-  HIPCHK(e, hipMemsetAsync(F.fill, 0, ((size_t)V + 1) * sizeof(int), s));
+  const size_t e_bound = 2 * (size_t)ncalls, I = sizeof(int), FL = sizeof(float), v1 = (size_t)V + 1;
+  if ((st = ensure_all(e, {{&bb.deg, v1 * I}, {&bb.fill, v1 * I}, {&bb.rowptr, (v1 + 1) * I},
+                           {&bb.col, (e_bound + 1) * I}, {&bb.seq, (e_bound + 1) * I}, {&bb.w, (e_bound + 1) * FL},
+                           {&bb.dist, (e_bound + 1) * FL}, {&bb.new2old, v1 * I}, {&bb.old2new, v1 * I},
+                           {&bb.deg_new, v1 * I}, {&bb.rowptr_new, (v1 + 1) * I}, {&bb.keep_flag, v1 * I},
+                           {&bb.keep_pos, (v1 + 1) * I}, {&bb.col2, (e_bound + 1) * I}, {&bb.w2, (e_bound + 1) * FL},
+                           {&bb.dist2, (e_bound + 1) * FL}, {&bb.xyz2, 3 * v1 * FL}, {&bb.state2, v1 * I}})) != TRG_OK)
+    return st;
+  F.deg = (int *)bb.deg.p;
+  F.fill = (int *)bb.fill.p;
+  F.rowptr = (int *)bb.rowptr.p;
+  F.col = (int *)bb.col.p;
+  F.seq = (int *)bb.seq.p;
+  F.w = (float *)bb.w.p;
+  F.dist = (float *)bb.dist.p;
+  HIPCHK(e, hipMemsetAsync(F.deg, 0, v1 * sizeof(int), s));
+  HIPCHK(e, hipMemsetAsync(F.fill, 0, v1 * sizeof(int), s));
   launch_fin_insert_count(F, B, ncalls, s);
-  launch_exclusive_scan(F.deg, F.rowptr, V, bb.scan_tmp, s);
+  launch_exclusive_scan(F.deg, F.rowptr, V, (int *)bb.scan_tmp.p, s);
   launch_fin_scatter(F, B, ncalls, s);
   lap("insert+count+scan+scatter");
-
-  if (e->keep_preclean) {
-    // the graph before cleanGraph, edges in push order (tests compare it with the oracle's)
-    launch_fin_rowsort(F, V, s);
-    if ((st = read_ctrs()) != TRG_OK) return st;
-    if (bb.h_ctrs[BFS_CTR_ERR]) return fallback(err_text(bb.h_ctrs[BFS_CTR_ERR]));
-    int E = 0;
-    HIPCHK(e, hipMemcpy(&E, F.rowptr + V, sizeof(int), hipMemcpyDeviceToHost));
-    std::vector<float> h_x(V), h_y(V), h_z(V);
-    Csr &c = e->csr_pre;
-    c.clear();
-    c.xyz.resize(3 * (size_t)V);
-    c.state.resize(V);
-    c.rowptr.resize((size_t)V + 1);
-    c.cid.resize(V);
-    c.col.resize(E);
-    c.w.resize(E);
-    c.dist.resize(E);
-    HIPCHK(e, hipMemcpy(c.state.data(), B.nstate, (size_t)V * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(c.rowptr.data(), F.rowptr, ((size_t)V + 1) * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(h_x.data(), B.nx, (size_t)V * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(h_y.data(), B.ny, (size_t)V * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(h_z.data(), B.nz, (size_t)V * sizeof(float), hipMemcpyDeviceToHost));
-    for (int i = 0; i < V; ++i) {
-      c.xyz[3 * (size_t)i] = h_x[i];
-      c.xyz[3 * (size_t)i + 1] = h_y[i];
-      c.xyz[3 * (size_t)i + 2] = h_z[i];
-      c.cid[i] = i;
-    }
-    if (E) {
-      HIPCHK(e, hipMemcpy(c.col.data(), F.col, (size_t)E * sizeof(int), hipMemcpyDeviceToHost));
-      HIPCHK(e, hipMemcpy(c.w.data(), F.w, (size_t)E * sizeof(float), hipMemcpyDeviceToHost));
-      HIPCHK(e, hipMemcpy(c.dist.data(), F.dist, (size_t)E * sizeof(float), hipMemcpyDeviceToHost));
-    }
+  if (!e->keep_preclean) return TRG_OK;
+  // the graph before cleanGraph, edges in push order (tests compare it with the oracle's)
+  launch_fin_rowsort(F, V, s);
+  if ((st = read_ctrs()) != TRG_OK) return st;
+  if (bb.h_ctrs[BFS_CTR_ERR]) return fallback(err_text(bb.h_ctrs[BFS_CTR_ERR]));
+  int E = 0;
+  HIPCHK(e, hipMemcpy(&E, F.rowptr + V, sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<float> h_x(V), h_y(V), h_z(V);
+  Csr &c = e->csr_pre;
+  c.clear();
+  c.xyz.resize(3 * (size_t)V);
+  c.state.resize(V);
+  c.rowptr.resize((size_t)V + 1);
+  c.cid.resize(V);
+  c.col.resize(E);
+  c.w.resize(E);
+  c.dist.resize(E);
+  HIPCHK(e, hipMemcpy(c.state.data(), B.nstate, (size_t)V * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(c.rowptr.data(), F.rowptr, ((size_t)V + 1) * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(h_x.data(), B.nx, (size_t)V * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(h_y.data(), B.ny, (size_t)V * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(h_z.data(), B.nz, (size_t)V * sizeof(float), hipMemcpyDeviceToHost));
+  for (int i = 0; i < V; ++i) {
+    c.xyz[3 * (size_t)i] = h_x[i];
+    c.xyz[3 * (size_t)i + 1] = h_y[i];
+    c.xyz[3 * (size_t)i + 2] = h_z[i];
+    c.cid[i] = i;
   }
+  if (E) {
+    HIPCHK(e, hipMemcpy(c.col.data(), F.col, (size_t)E * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(c.w.data(), F.w, (size_t)E * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(c.dist.data(), F.dist, (size_t)E * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return TRG_OK;
+}
 
-  // ---- cleanGraph (trg.cpp:491-535): renumbering in the reference container's iteration order ----
+// ---- phase 6: cleanGraph (trg.cpp:491-535), renumbering in the reference container's iteration order, and
+// the cleaned graph to the host ----
+TrgStatus Build::clean_and_fetch() {
+  TrgStatus st;
   // (the order went to the device while the deferred evaluations ran)
-  HIPCHK(e, hipStreamWaitEvent(s, ev_order, 0));
-  launch_fin_clean(F, B, bb.d_map_order, V, bb.d_keep_flag, bb.d_keep_pos, bb.d_new2old, bb.d_old2new,
-                   bb.d_deg_new, bb.d_rowptr_new, bb.scan_tmp, bb.d_col2, bb.d_w2, bb.d_dist2, bb.d_xyz2,
-                   bb.d_state2, s);
-  int *h_tot = bb.h_ctrs + 32;  // pinned: surviving nodes, edges
-  HIPCHK(e, hipMemcpyAsync(h_tot, bb.d_keep_pos + V, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamWaitEvent(s, ev_order.ev, 0));
+  launch_fin_clean(F, B, (int *)bb.map_order.p, V, (int *)bb.keep_flag.p, (int *)bb.keep_pos.p,
+                   (int *)bb.new2old.p, (int *)bb.old2new.p, (int *)bb.deg_new.p, (int *)bb.rowptr_new.p,
+                   (int *)bb.scan_tmp.p, (int *)bb.col2.p, (float *)bb.w2.p, (float *)bb.dist2.p,
+                   (float *)bb.xyz2.p, (int *)bb.state2.p, s);
+  int *h_tot = bb.h_ctrs + H_CLEAN_TOTALS;
+  HIPCHK(e, hipMemcpyAsync(h_tot, (int *)bb.keep_pos.p + V, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipMemcpyAsync(h_tot + 1, F.rowptr + V, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   const int Vn = h_tot[0], E = h_tot[1];
@@ -1287,19 +1284,15 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
     g.col.resize(En);
     g.w.resize(En);
     g.dist.resize(En);
-    HIPCHK(e, hipMemcpyAsync(g.xyz.data(), bb.d_xyz2, 3 * (size_t)Vn * sizeof(float),
-                             hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipMemcpyAsync(g.state.data(), bb.d_state2, (size_t)Vn * sizeof(int),
-                             hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipMemcpyAsync(g.cid.data(), bb.d_new2old, (size_t)Vn * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipEventRecord(ev_nodes, s));
-    HIPCHK(e, hipMemcpyAsync(g.rowptr.data(), bb.d_rowptr_new, ((size_t)Vn + 1) * sizeof(int),
-                             hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(g.xyz.data(), bb.xyz2.p, 3 * (size_t)Vn * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(g.state.data(), bb.state2.p, (size_t)Vn * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(g.cid.data(), bb.new2old.p, (size_t)Vn * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipEventRecord(ev_nodes.ev, s));
+    HIPCHK(e, hipMemcpyAsync(g.rowptr.data(), bb.rowptr_new.p, ((size_t)Vn + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
     if (En) {
-      HIPCHK(e, hipMemcpyAsync(g.col.data(), bb.d_col2, (size_t)En * sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(e, hipMemcpyAsync(g.w.data(), bb.d_w2, (size_t)En * sizeof(float), hipMemcpyDeviceToHost, s));
-      HIPCHK(e, hipMemcpyAsync(g.dist.data(), bb.d_dist2, (size_t)En * sizeof(float),
-                               hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipMemcpyAsync(g.col.data(), bb.col2.p, (size_t)En * sizeof(int), hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipMemcpyAsync(g.w.data(), bb.w2.p, (size_t)En * sizeof(float), hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipMemcpyAsync(g.dist.data(), bb.dist2.p, (size_t)En * sizeof(float), hipMemcpyDeviceToHost, s));
     }
     mark("copies enqueued");
     // while the copies run: global_graph.nodes = new_nodes (trg.cpp:526) -- the copy takes over the
@@ -1312,7 +1305,7 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
     }
     mark("container replica");
     // ... and the host-side graph state (slot == id) as soon as the node arrays are here
-    HIPCHK(e, hipEventSynchronize(ev_nodes));
+    HIPCHK(e, hipEventSynchronize(ev_nodes.ev));
     mark("node arrays here");
     e->nx.resize(Vn);
     e->ny.resize(Vn);
@@ -1343,7 +1336,7 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   lap("clean kernels + CSR to host");
   e->node_id = Vn;
   lap("host graph state");
-  e->dev_csr_valid = Vn > 0;  // d_xyz2 / d_rowptr_new / d_col2 / d_w2 / d_dist2 hold the cleaned graph
+  e->dev_csr_valid = Vn > 0;  // xyz2 / rowptr_new / col2 / w2 / dist2 / state2 hold the cleaned graph
   e->real_map_stale = true;  // the real std::unordered_map is rebuilt only if a host path needs it
   e->kd_order_dirty = true;  // node-tree refill order (trg.cpp:528-530) derived on demand
   e->kd_valid = false;
@@ -1353,10 +1346,13 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   e->csr_stitched.clear();
   e->pool_valid = false;      // the host edge pool / node grid are rebuilt from the CSR on demand
   e->host_grid_valid = false;
+  return TRG_OK;
+}
 
-  // ---- statistics ------------------------------------------------------------------------------------
+// ---- phase 7: statistics and instrumentation reports -------------------------------------------------
+TrgStatus Build::report_stats() {
   unsigned long long s64[16] = {0};
-  launch_bfs_stats(B, V, B.stats64 + 8, s);  // draws, samples, disc hits, speculative-edge hits, candidates, parent-edge hits
+  launch_bfs_stats(B, V, B.stats64 + S64_DRAWS, s);  // draws, samples, disc hits, speculative-edge hits, candidates, parent-edge hits
   HIPCHK(e, hipStreamSynchronize(s));  // (s does not synchronise with the plain copy below)
   HIPCHK(e, hipMemcpy(s64, B.stats64, sizeof(s64), hipMemcpyDeviceToHost));
   if (getenv("TRG_DEBUG_STATS")) {  // the reduction against a host sum of the same arrays
@@ -1372,14 +1368,8 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
         zero += hx[4 * (size_t)i + 1] == 0;
       }
     fprintf(stderr, "[trg stats] device draws %llu samples %llu | host sum draws %llu samples %llu | valid nodes with 0 draws %zu\n",
-            s64[8], s64[9], d, a, zero);
+            s64[S64_DRAWS], s64[S64_SAMPLES], d, a, zero);
   }
-  bb.host_stats[0] = s64[8];
-  bb.host_stats[1] = s64[9];
-  bb.host_stats[5] = s64[10];
-  bb.host_stats[6] = s64[11];
-  bb.host_stats[4] = s64[12];
-  bb.host_stats[7] = s64[13];
   if (B.tl) {  // -DLV_TIMELINE=<tag> builds: wall-clock marks of the level kernels (100 MHz), six level attempts
     constexpr int UNITS = 1 << 16, KINDS = 12, TAGS = 6;
     std::vector<unsigned long long> tl((size_t)UNITS * KINDS * TAGS);
@@ -1408,7 +1398,7 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
   }
   if (getenv("TRG_PHASE_TIMING") && ncalls > 0) {
     std::vector<unsigned long long> ph(1024 * 8);
-    HIPCHK(e, hipMemcpy(ph.data(), B.stats64 + 16, ph.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(ph.data(), B.stats64 + S64_PHASES, ph.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     double t[8] = {0};
     for (size_t i = 0; i < ph.size(); ++i) t[i & 7] += (double)ph[i];
     const double nodes = (double)(ncalls / std::max(S * CS, 1));
@@ -1420,27 +1410,36 @@ TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float roo
             t[0] / nodes, t[1] / nodes, t[2] / nodes, t[3] / nodes, t[4] / nodes, t[5] / nodes, t[6] / nodes, t[7] / nodes);
   }
   e->stats.expanded_nodes = (uint64_t)(ncalls / std::max(S * CS, 1));
-  e->stats.trials = bb.host_stats[0];
-  e->stats.samples = bb.host_stats[1];
-  e->stats.created_nodes = bb.host_stats[2] + 1;  // + root
-  e->stats.invalid_nodes = bb.host_stats[3];
-  e->stats.edge_calls = bb.host_stats[1];
-  e->stats.edge_evals_gpu = bb.host_stats[4] + s64[5];  // speculative parent edges + deferred
-  e->lv_hits_sample = bb.host_stats[5];
-  e->lv_hits_spec = bb.host_stats[6];
-  e->stats.bytes_spec_created = 12ull * bb.host_stats[7];
+  e->stats.trials = s64[S64_DRAWS];
+  e->stats.samples = s64[S64_SAMPLES];
+  e->stats.created_nodes = bb.nodes_created + 1;  // + root
+  e->stats.invalid_nodes = bb.nodes_invalid;
+  e->stats.edge_calls = s64[S64_SAMPLES];
+  e->stats.edge_evals_gpu = s64[S64_CANDIDATES] + s64[S64_DEF_KEPT];  // speculative parent edges + deferred
+  e->lv_hits_sample = s64[S64_DISC_HITS];
+  e->lv_hits_spec = s64[S64_SPEC_HITS];
+  e->stats.bytes_spec_created = 12ull * s64[S64_PARENT_HITS];
   e->stats.ms_finalize_host = ms_since(t_fin);
   e->stats.bfs_levels = (uint64_t)levels;
-  e->stats.bfs_max_spin = s64[6];
-  e->stats.bfs_multipass_rows = s64[7];
-  (void)hipEventDestroy(ev0);
-  (void)hipEventDestroy(ev1);
-  (void)hipEventDestroy(evn0);
-  (void)hipEventDestroy(evn1);
-  (void)hipEventDestroy(ev_order);
-  (void)hipEventDestroy(ev_nodes);
-#undef ENS
+  e->stats.bfs_max_spin = s64[S64_MAX_SPIN];
+  e->stats.bfs_multipass_rows = s64[S64_MULTIPASS];
   return TRG_OK;
+}
+
+// returns TRG_OK, a hard error, or TRG_ERR_CAPACITY with e->bfs_fallback_reason set when the
+// caller should redo the build with the host replay
+TrgStatus build_graph_device(TrgEngine *e, float root_x, float root_y, float root_z) {
+  e->bfs_fallback_reason.clear();
+  Build b(e);
+  b.B.cstride = b.CS;
+  TrgStatus st;
+  if ((st = b.allocate()) != TRG_OK) return st;
+  if ((st = b.seed_root(root_x, root_y, root_z)) != TRG_OK) return st;
+  if ((st = b.level_loop()) != TRG_OK) return st;
+  if ((st = b.finish_deferred()) != TRG_OK) return st;
+  if ((st = b.assemble_csr()) != TRG_OK) return st;
+  if ((st = b.clean_and_fetch()) != TRG_OK) return st;
+  return b.report_stats();  // (the events of the build are destroyed with it)
 }
 
 }  // namespace

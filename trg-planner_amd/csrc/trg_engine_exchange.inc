@@ -61,12 +61,9 @@ struct ExchangeState {
   int nranks = 0, rank = 0;
   DevArr rec, edges, send, recv, all, cnt;
   long long *h_cnt = nullptr;  // pinned, nranks + 1 words
-  void release() {
-    for (DevArr *a : {&rec, &edges, &send, &recv, &all, &cnt})
-      if (a->p) (void)hipFree(a->p);
+  ~ExchangeState() {  // (the DevArrs free themselves)
     if (h_cnt) (void)hipHostFree(h_cnt);
     if (comm && owned && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(comm);
-    *this = ExchangeState();
   }
 };
 
@@ -118,7 +115,6 @@ TrgStatus exchange_allgatherv(TrgEngine *e, ExchangeState &x, const void *d_mine
 
 void exchange_release(TrgEngine *e) {
   if (!e->exchange) return;
-  e->exchange->release();
   delete e->exchange;
   e->exchange = nullptr;
 }

@@ -21,24 +21,12 @@ struct FieldBufs {
   FieldEdgeStats *h_stats = nullptr;  // pinned
   int *h_reached = nullptr;           // pinned
   hipEvent_t t0 = nullptr, t1 = nullptr;
-  void release() {
-    for (DevArr *a : {&ec, &stats, &key, &q0, &q1, &far0, &far1, &stamp_near, &stamp_far, &parent, &cost, &hops,
-                      &ctrl, &up_rowptr, &up_col, &up_w, &up_dist, &up_state}) {
-      if (a->p) (void)hipFree(a->p);
-      a->p = nullptr;
-      a->bytes = 0;
-    }
+  ~FieldBufs() {
     if (h_state) (void)hipHostFree(h_state);
     if (h_stats) (void)hipHostFree(h_stats);
     if (h_reached) (void)hipHostFree(h_reached);
     if (t0) (void)hipEventDestroy(t0);
     if (t1) (void)hipEventDestroy(t1);
-    h_state = nullptr;
-    h_stats = nullptr;
-    h_reached = nullptr;
-    t0 = t1 = nullptr;
-    up_version = ec_version = 0;
-    ec_col = nullptr;
   }
 };
 
@@ -48,7 +36,6 @@ void field_release(TrgEngine *e) {
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->s_main);
   }
-  e->field->release();
   delete e->field;
   e->field = nullptr;
 }
@@ -82,13 +69,13 @@ TrgStatus field_solve(TrgEngine *e, int32_t source_id, const float *source_xy, f
   const int E = G.rowptr.empty() ? 0 : G.rowptr[V];
   const int *d_rowptr, *d_col, *d_state;
   const float *d_w, *d_dist;
-  if (e->dev_csr_valid && e->bfs && e->bfs->d_rowptr_new) {
+  if (e->dev_csr_valid && e->bfs && e->bfs->rowptr_new.p) {
     const BfsBuffers &bb = *e->bfs;
-    d_rowptr = bb.d_rowptr_new;
-    d_col = bb.d_col2;
-    d_w = bb.d_w2;
-    d_dist = bb.d_dist2;
-    d_state = bb.d_state2;
+    d_rowptr = (const int *)bb.rowptr_new.p;
+    d_col = (const int *)bb.col2.p;
+    d_w = (const float *)bb.w2.p;
+    d_dist = (const float *)bb.dist2.p;
+    d_state = (const int *)bb.state2.p;
   } else {
     if (fb.up_version != e->graph_version) {
       fb.up_version = 0;

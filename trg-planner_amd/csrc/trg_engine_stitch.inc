@@ -20,12 +20,12 @@ TrgStatus stitch_dev_graph(TrgEngine *e, bool need_edges, DevGraph *g) {
   g->V = (int)c.state.size();
   g->E = (int)c.col.size();
   BfsBuffers &bb = *e->bfs;
-  if (e->dev_csr_valid && bb.d_xyz2 && bb.d_rowptr_new) {
-    g->xyz = bb.d_xyz2;
-    g->rowptr = bb.d_rowptr_new;
-    g->col = bb.d_col2;
-    g->w = bb.d_w2;
-    g->dist = bb.d_dist2;
+  if (e->dev_csr_valid && bb.xyz2.p && bb.rowptr_new.p) {
+    g->xyz = (const float *)bb.xyz2.p;
+    g->rowptr = (const int *)bb.rowptr_new.p;
+    g->col = (const int *)bb.col2.p;
+    g->w = (const float *)bb.w2.p;
+    g->dist = (const float *)bb.dist2.p;
     return TRG_OK;
   }
   TrgStatus st;
