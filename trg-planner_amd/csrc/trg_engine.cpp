@@ -26,6 +26,7 @@
 #include <deque>
 #include <fstream>
 #include <functional>
+#include <memory>
 #include <queue>
 #include <sstream>
 #include <string>
@@ -64,19 +65,140 @@ void parallel_ranges(size_t n, F fn) {
   for (auto &th : thr) th.join();
 }
 
+// ---- owners of GPU resources ---------------------------------------------------------------------
+// Whatever this translation unit holds on the device, in pinned host memory or as a HIP handle lives in one of
+// these: move-only, released by the destructor, and the capacity sits inside the owner and changes only with
+// the block itself.  An empty owner makes no HIP call, so an engine that never saw a device is destroyed
+// without one.  The owners of an engine are released with its device current (trg_engine_destroy).
+
+// device memory with its capacity in bytes
+struct DevArr {
+  void *p = nullptr;
+  size_t bytes = 0;
+  DevArr() = default;
+  DevArr(DevArr &&o) noexcept { *this = std::move(o); }
+  DevArr &operator=(DevArr &&o) noexcept {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+    return *this;
+  }
+  ~DevArr() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  // at least `need` bytes, at exactly that size when it has to grow; the contents are not kept, and the old
+  // block goes first (the arrays of a 10 M-point map are too large to hold twice or to give head-room).
+  // ensure_bytes below is the growth with head-room for arrays that creep up.
+  hipError_t reserve(size_t need) {
+    if (p && bytes >= need) return hipSuccess;
+    release();
+    const hipError_t err = hipMalloc(&p, need);
+    if (err != hipSuccess) p = nullptr;
+    else bytes = need;
+    return err;
+  }
+  template <typename T>
+  T *as() const {
+    return (T *)p;
+  }
+};
+
+// a DevArr of T, sized in elements: it goes into a launch as the T* it holds
+template <typename T>
+struct DevBuf : DevArr {
+  hipError_t ensure(size_t n) { return reserve(n * sizeof(T)); }
+  operator T *() const { return (T *)p; }
+};
+
+// pinned host memory of T, the same way (h_ctrs of the device BFS is Mapped | Coherent: the flags are a parameter)
+template <typename T>
+struct Pinned {
+  T *p = nullptr;
+  size_t count = 0;
+  Pinned() = default;
+  Pinned(Pinned &&o) noexcept { *this = std::move(o); }
+  Pinned &operator=(Pinned &&o) noexcept {
+    std::swap(p, o.p);
+    std::swap(count, o.count);
+    return *this;
+  }
+  ~Pinned() { release(); }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    count = 0;
+  }
+  hipError_t ensure(size_t n, unsigned flags = hipHostMallocDefault) {
+    if (p && count >= n) return hipSuccess;
+    release();
+    const hipError_t err = hipHostMalloc((void **)&p, n * sizeof(T), flags);
+    if (err != hipSuccess) p = nullptr;
+    else count = n;
+    return err;
+  }
+  operator T *() const { return p; }
+  T *operator->() const { return p; }
+  template <typename U>
+  U *as() const {
+    return (U *)p;
+  }
+};
+
+// `cap` elements in pinned host memory and as many on the device: the two ends of a staged copy
+template <typename T>
+struct PinnedBuf {
+  Pinned<T> h;
+  DevBuf<T> d;
+  hipError_t ensure(size_t cap) {
+    const hipError_t err = h.ensure(cap);
+    return err != hipSuccess ? err : d.ensure(cap);
+  }
+};
+
+struct Event {
+  hipEvent_t ev = nullptr;
+  Event() = default;
+  Event(Event &&o) noexcept { std::swap(ev, o.ev); }
+  Event &operator=(Event &&o) noexcept {
+    std::swap(ev, o.ev);
+    return *this;
+  }
+  ~Event() { if (ev) (void)hipEventDestroy(ev); }
+  hipError_t create(bool timing = true) {  // (one that exists is kept)
+    return ev ? hipSuccess : hipEventCreateWithFlags(&ev, timing ? hipEventDefault : hipEventDisableTiming);
+  }
+  operator hipEvent_t() const { return ev; }
+};
+
+struct Stream {  // non-blocking
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(Stream &&o) noexcept { std::swap(s, o.s); }
+  Stream &operator=(Stream &&o) noexcept {
+    std::swap(s, o.s);
+    return *this;
+  }
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  hipError_t create() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  hipError_t create_with_priority(int priority) {
+    return s ? hipSuccess : hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority);
+  }
+  operator hipStream_t() const { return s; }
+};
+
 struct IndexScratch {  // temporaries of build_index, grown on demand
-  int *cell_of = nullptr, *rank = nullptr, *counts = nullptr, *tmp = nullptr;  // the direct path (huge grids only)
-  int *hist = nullptr, *base = nullptr, *bin_tmp = nullptr;                    // the path through bins
-  void *aos = nullptr;
-  size_t cap_pts = 0, cap_cells = 0, cap_direct = 0, cap_bins = 0;
+  DevBuf<int> cell_of, rank, counts, tmp;  // the direct path (huge grids only)
+  DevBuf<int> hist, base, bin_tmp;         // the path through bins
+  DevBuf<float4> aos;
 };
 
 struct DevMap {
   size_t n = 0;
-  float *x = nullptr, *y = nullptr, *z = nullptr;
-  int *perm = nullptr, *cell_start = nullptr;
-  float4 *pt = nullptr;  // the sorted points as 16-byte records (MapView::pt)
-  size_t cap_pts = 0, cap_cells = 0;
+  DevBuf<float> x, y, z;
+  DevBuf<int> perm, cell_start;
+  DevBuf<float4> pt;  // the sorted points as 16-byte records (MapView::pt)
   MapView view{};
   float g = 0;
   float bounds[4] = {0, 0, 0, 0};
@@ -88,17 +210,12 @@ struct DevMap {
   std::vector<int> top_left, top_right;
   // For the global map the top is prepared beside the build (start_map_top): its points are fetched on the aux
   // stream and a helper thread inserts them; whoever needs the top (or replaces / frees the map) joins it first.
+  // (The helper reads the map's arrays and the engine's top_xy_h / top_ev: those outlive it, see TrgEngine.)
   std::thread top_thread;
   void top_wait() {
     if (top_thread.joinable()) top_thread.join();
   }
-};
-
-template <typename T>
-struct PinnedBuf {
-  T *h = nullptr;
-  T *d = nullptr;
-  size_t cap = 0;
+  ~DevMap() { top_wait(); }
 };
 
 // results of one speculative / deferred edge evaluation as the replay consumes them
@@ -298,12 +415,11 @@ struct View {  // host / device views into a chunk's packed blobs
 struct Chunk {
   int first = 0, count = 0;  // queue positions [first, first+count)
   bool in_flight = false;
-  hipEvent_t done = nullptr;
-  hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;  // sample start / sample end / edges end
+  Event done;
+  Event t0, t1, t2;  // sample start / sample end / edges end
   // one packed input blob (H2D) and one packed output blob (D2H) per chunk: a single copy each way
   PinnedBuf<uint32_t> in_blob, out_blob;
-  float *d_mid = nullptr;  // phase-1 edge records (device only)
-  size_t mid_cap = 0;
+  DevBuf<float> mid;  // phase-1 edge records (device only)
   View<float> node_xy, node_xyz, sx, sy, sz, weight, dist;
   View<int> node_id, n_acc, n_draws, status;
   // nearest-map-point ties of accepted samples: [0] = count, records from word 4 (MapTieRec)
@@ -311,14 +427,14 @@ struct Chunk {
   size_t in_words = 0, out_words = 0;
   void carve(int cnt, int S) {
     const size_t c = (size_t)cnt, cs = c * (size_t)S;
-    auto iv = [&](size_t off) { return View<int>{(int *)in_blob.h + off, (int *)in_blob.d + off}; };
-    auto fv = [&](size_t off) { return View<float>{(float *)in_blob.h + off, (float *)in_blob.d + off}; };
+    auto iv = [&](size_t off) { return View<int>{in_blob.h.as<int>() + off, in_blob.d.as<int>() + off}; };
+    auto fv = [&](size_t off) { return View<float>{in_blob.h.as<float>() + off, in_blob.d.as<float>() + off}; };
     node_xy = fv(0);
     node_xyz = fv(2 * c);
     node_id = iv(5 * c);
     in_words = 6 * c;
-    auto io = [&](size_t off) { return View<int>{(int *)out_blob.h + off, (int *)out_blob.d + off}; };
-    auto fo = [&](size_t off) { return View<float>{(float *)out_blob.h + off, (float *)out_blob.d + off}; };
+    auto io = [&](size_t off) { return View<int>{out_blob.h.as<int>() + off, out_blob.d.as<int>() + off}; };
+    auto fo = [&](size_t off) { return View<float>{out_blob.h.as<float>() + off, out_blob.d.as<float>() + off}; };
     n_acc = io(0);
     n_draws = io(c);
     sx = fo(2 * c);
@@ -334,16 +450,16 @@ struct Chunk {
 struct EdgeBatch {
   bool in_flight = false;
   int count = 0;
-  hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;
+  Event done, t0, t1;
   std::vector<int> call_idx;  // which CallRec each row fills
   PinnedBuf<float> p1, p2, weight, dist;
   PinnedBuf<int> status;
-  float *d_mid = nullptr;
+  DevBuf<float> mid;
 };
 
 struct BfsBuffers;  // device-resident BFS state (trg_engine_bfs.inc)
 struct StitchBufs;  // scratch of the tile-boundary stitch (trg_engine_stitch.inc)
-struct Uploader;    // host cloud -> HBM staging (upload_and_build)
+struct Uploader;    // host cloud -> HBM staging (trg_engine_map.ipp)
 struct ExchangeState;  // RCCL communicator + buffers of the native stitch exchange (trg_engine_exchange.inc)
 struct FieldBufs;      // device buffers of the cost field (trg_engine_field.ipp)
 
@@ -352,7 +468,6 @@ struct FieldBufs;      // device buffers of the cost field (trg_engine_field.ipp
 struct TrgEngine;
 namespace {
 TrgStatus stitch_fetch(TrgEngine *e);  // trg_engine_stitch.inc
-void exchange_release(TrgEngine *e);   // trg_engine_exchange.inc
 void field_release(TrgEngine *e);      // trg_engine_field.ipp
 }
 // Scratch of one A* search over the CSR.  open_check / close_list of the reference (trg.cpp:619-620,
@@ -387,26 +502,34 @@ struct PlanScratch {
   }
 };
 
+// Members are destroyed last to first, and the order below is the order of teardown that matters: the three
+// streams come first, so they go after everything that may hold work in them, after the uploader's own streams
+// and after the RCCL communicator (ExchangeState); top_xy_h / top_ev stand before the maps, whose destructor
+// joins the helper thread that reads them (and the map's arrays).  trg_engine_destroy makes the engine's
+// device current and synchronises it before any of this runs.
 struct TrgEngine {
+  TrgEngine();   // (both defined at the end of this file, where the types behind the unique_ptrs are complete)
+  ~TrgEngine();
   TrgParams prm{};
   int device = 0;
   std::string err;
   std::string arch;
-  bool device_ok = false;
+  bool device_ok = false;  // create went through: the entry points run (REQUIRE_DEVICE)
 
-  hipStream_t s_main = nullptr, s_edge = nullptr;
-  hipStream_t s_aux = nullptr;  // rare-event work (nearest-point tie walks) beside whatever the main stream holds
+  Stream s_main, s_edge;
+  Stream s_aux;  // rare-event work (nearest-point tie walks) beside whatever the main stream holds
+  DevBuf<float> top_xy_d;  // staging of start_map_top: device,
+  Pinned<float> top_xy_h;  // pinned host,
+  Event top_ev;            // and "fetched"
   DevMap gmap, lmap;
   IndexScratch idx_scratch;
-  float *top_xy_d = nullptr, *top_xy_h = nullptr;  // staging of start_map_top (device / pinned host)
-  hipEvent_t top_ev = nullptr;
-  DeviceCounters *d_ctr = nullptr;
-  unsigned *d_bounds = nullptr;
+  DevBuf<DeviceCounters> d_ctr;
+  DevBuf<unsigned> d_bounds;
 
   // sampler
   TrgSampler sampler{1, 16};
   std::vector<float> cos_t, sin_t;
-  float *d_cos = nullptr, *d_sin = nullptr;
+  DevBuf<float> d_cos, d_sin;
   int table_bits_dev = 0;
   uint32_t epoch = 0;
   uint32_t epoch_base = 0;  // tiled builds: sampler epoch of this tile
@@ -446,23 +569,21 @@ struct TrgEngine {
   static constexpr int EBATCH_MAX = 1 << 16;
   EdgeBatch ebatches[NEBATCH];
   std::vector<int> pending_calls;
-  int chunk_S = 0;
 
   // small synchronous scratch
   PinnedBuf<float> sy_in, sy_in2, sy_f0, sy_f1;
   PinnedBuf<int> sy_i0, sy_i1, sy_i2;
-  float *sy_mid = nullptr;
-  size_t sy_cap = 0;
+  DevBuf<float> sy_mid;
   // exact nearest-map-point tie-break scratch (map_nn_exact)
-  MapTieSet *mt_set_d = nullptr, *mt_set_h = nullptr;
-  MapTieWalk *mt_walk_d = nullptr, *mt_walk_h = nullptr;
+  PinnedBuf<MapTieSet> mt_set;
+  PinnedBuf<MapTieWalk> mt_walk;
 
   Csr csr_global, csr_pre, csr_local;
   Csr csr_stitched;              // tiled builds: this tile's rows of the stitched global graph
   bool stitched_on_device = false;  // ... their edge arrays are still in HBM only (fetched on export)
   int stitched_edges = 0;
   bool dev_csr_valid = false;    // the cleaned global CSR of the last device build is still in HBM
-  StitchBufs *stitch = nullptr;
+  std::unique_ptr<StitchBufs> stitch;
   bool keep_preclean = false;    // instrumentation: snapshot the graph before cleanGraph
   bool use_device_bfs = true;    // device-resident BFS (off: host replay)
   bool defer_overlap = true;     // deferred edge evaluations pipelined behind the level loop on a 2nd stream
@@ -472,10 +593,12 @@ struct TrgEngine {
   std::vector<float> kdo_x, kdo_y;
   std::vector<int> kdo_index;    // node id -> position in the insertion order
   uint64_t kdo_version = 0;
-  PlanScratch *plan_scratch = nullptr;
-  Uploader *uploader = nullptr;
-  ExchangeState *exchange = nullptr;  // host cloud -> HBM staging (upload_and_build)
-  FieldBufs *field = nullptr;    // cost field: work arrays, edge costs and uploaded CSR (cached per graph_version)
+  PlanScratch plan_scratch;
+  std::unique_ptr<Uploader> uploader;  // host cloud -> HBM staging (upload_and_build): pinned slots, streams and events
+                                       // of its copy threads, made on the first cloud that needs them
+  std::unique_ptr<ExchangeState> exchange;  // tiled builds: RCCL communicator and buffers of the native stitch
+                                            // exchange, made by trg_engine_comm_init / comm_adopt
+  std::unique_ptr<FieldBufs> field;  // cost field: work arrays, edge costs and uploaded CSR (cached per graph_version)
   double field_delta_scale = 4.0;  // cost field: bucket width in mean edge costs (a measurement knob, see set_option)
   bool pool_valid = true;        // e->edges mirrors csr_global
   bool host_grid_valid = true;   // e->grid holds the current node set
@@ -491,7 +614,7 @@ struct TrgEngine {
   int resolve_tickets = 0;       // 1: every resolve launch takes its workgroup indices from start tickets (default: only
                                  // the repeat of a launch whose bounded wait ran out)
   float gate_margin = 1e-4f;     // band in which the slope gate is left to the host's libm
-  BfsBuffers *bfs = nullptr;
+  std::unique_ptr<BfsBuffers> bfs;
   std::string bfs_fallback_reason;
   // map points inside the queries of the level kernels of the last device build (instrumentation;
   // counted per committed level, so discarded launches count nothing)
@@ -519,28 +642,24 @@ namespace {
     }                                                                                     \
   } while (0)
 
-template <typename T>
-hipError_t alloc_pinned(PinnedBuf<T> &b, size_t cap) {
-  if (b.cap >= cap) return hipSuccess;
-  if (b.h) (void)hipHostFree(b.h);
-  if (b.d) (void)hipFree(b.d);
-  b.h = nullptr;
-  b.d = nullptr;
-  b.cap = 0;
-  hipError_t e = hipHostMalloc((void **)&b.h, cap * sizeof(T), hipHostMallocDefault);
-  if (e != hipSuccess) return e;
-  e = hipMalloc((void **)&b.d, cap * sizeof(T));
-  if (e != hipSuccess) return e;
-  b.cap = cap;
-  return hipSuccess;
+// growth with head-room for arrays that creep up from build to build (keep: the contents move along)
+TrgStatus ensure_bytes(TrgEngine *e, DevArr &a, size_t need, bool keep = false) {
+  if (a.p && a.bytes >= need) return TRG_OK;
+  DevArr grown;
+  HIPCHK(e, grown.reserve(std::max(need, a.bytes + a.bytes / 2)));
+  if (keep && a.p && a.bytes) {
+    hipError_t he = hipMemcpy(grown.p, a.p, a.bytes, hipMemcpyDeviceToDevice);
+    if (he != hipSuccess) return e->fail(TRG_ERR_DEVICE, std::string("grow copy: ") + hipGetErrorString(he));
+  }
+  std::swap(a, grown);  // (the old block goes with `grown`)
+  return TRG_OK;
 }
-template <typename T>
-void free_pinned(PinnedBuf<T> &b) {
-  if (b.h) (void)hipHostFree(b.h);
-  if (b.d) (void)hipFree(b.d);
-  b.h = nullptr;
-  b.d = nullptr;
-  b.cap = 0;
+TrgStatus ensure_all(TrgEngine *e, std::initializer_list<std::pair<DevArr *, size_t>> need) {
+  for (const auto &n : need) {
+    const TrgStatus st = ensure_bytes(e, *n.first, n.second);
+    if (st != TRG_OK) return st;
+  }
+  return TRG_OK;
 }
 
 QueryParams qparams(const TrgEngine *e) {
@@ -556,17 +675,6 @@ QueryParams qparams(const TrgEngine *e) {
   q.core_y1 = e->core[3];
   q.gate_margin = e->gate_margin;
   return q;
-}
-
-void free_map(DevMap &m) {
-  if (m.x) (void)hipFree(m.x);
-  if (m.y) (void)hipFree(m.y);
-  if (m.z) (void)hipFree(m.z);
-  if (m.perm) (void)hipFree(m.perm);
-  if (m.pt) (void)hipFree(m.pt);
-  if (m.cell_start) (void)hipFree(m.cell_start);
-  m.top_wait();
-  m = DevMap();
 }
 
 inline float key_to_float(unsigned k) {
@@ -594,11 +702,11 @@ TrgStatus ensure_sampler(TrgEngine *e, const TrgSampler *smp) {
     e->cos_t[k] = cos(angle);
     e->sin_t[k] = sin(angle);
   }
-  if (e->d_cos) (void)hipFree(e->d_cos);
-  if (e->d_sin) (void)hipFree(e->d_sin);
-  e->d_cos = e->d_sin = nullptr;
-  HIPCHK(e, hipMalloc((void **)&e->d_cos, n * sizeof(float)));
-  HIPCHK(e, hipMalloc((void **)&e->d_sin, n * sizeof(float)));
+  e->table_bits_dev = 0;
+  e->d_cos.release();  // (a table of another size is allocated afresh, a smaller one too)
+  e->d_sin.release();
+  HIPCHK(e, e->d_cos.ensure(n));
+  HIPCHK(e, e->d_sin.ensure(n));
   HIPCHK(e, hipMemcpy(e->d_cos, e->cos_t.data(), n * sizeof(float), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(e->d_sin, e->sin_t.data(), n * sizeof(float), hipMemcpyHostToDevice));
   e->table_bits_dev = want.table_bits;
@@ -806,20 +914,21 @@ TrgStatus trg_engine_create(const TrgParams *params, int device, TrgEngine **out
   if (e->arch.rfind("gfx950", 0) != 0) {
     return e->fail(TRG_ERR_DEVICE, "kernels are built for gfx950 only, device is " + e->arch);
   }
-  HIPCHK(e, hipStreamCreateWithFlags(&e->s_main, hipStreamNonBlocking));
+  // (whatever exists when one of these fails is released by trg_engine_destroy)
+  HIPCHK(e, e->s_main.create());
   // the deferred stream at the main stream's priority (the lowest leaves a longer tail after the loop:
   // measured 0.5 ms slower)
-  HIPCHK(e, hipStreamCreateWithPriority(&e->s_edge, hipStreamNonBlocking, 0));
-  HIPCHK(e, hipStreamCreateWithFlags(&e->s_aux, hipStreamNonBlocking));
-  HIPCHK(e, hipMalloc((void **)&e->d_ctr, COUNTER_SHARDS * sizeof(DeviceCounters)));
+  HIPCHK(e, e->s_edge.create_with_priority(0));
+  HIPCHK(e, e->s_aux.create());
+  HIPCHK(e, e->d_ctr.ensure(COUNTER_SHARDS));
   HIPCHK(e, hipMemset(e->d_ctr, 0, COUNTER_SHARDS * sizeof(DeviceCounters)));
-  HIPCHK(e, hipMalloc((void **)&e->d_bounds, 4 * sizeof(unsigned)));
+  HIPCHK(e, e->d_bounds.ensure(4));
   // step 3 of expandGraph is compiled in or out by this fp comparison (trg.cpp:429)
   e->step3 = (e->prm.expand_dist - e->prm.robot_size) < 0.25 * e->prm.expand_dist;
+  e->bfs.reset(new BfsBuffers());
+  e->stitch.reset(new StitchBufs());
+  e->uploader.reset(new Uploader());
   e->device_ok = true;
-  e->bfs = new BfsBuffers();
-  e->stitch = new StitchBufs();
-  e->uploader = new Uploader();
   if (const char *env = getenv("TRG_REPLAY")) e->use_device_bfs = std::string(env) != "host";
   reset_graph_global(e);
   return TRG_OK;
@@ -827,73 +936,13 @@ TrgStatus trg_engine_create(const TrgParams *params, int device, TrgEngine **out
 
 void trg_engine_destroy(TrgEngine *e) {
   if (!e) return;
-  if (e->device_ok) {
+  // the main stream is the first thing create makes on the device: without it every owner is empty, and
+  // nothing below needs a device (there may be none)
+  if (e->s_main) {
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
-    free_map(e->gmap);
-    free_map(e->lmap);
-    Chunk *all_chunks[TrgEngine::NCHUNK + 1];
-    for (int i = 0; i < TrgEngine::NCHUNK; ++i) all_chunks[i] = &e->chunks[i];
-    all_chunks[TrgEngine::NCHUNK] = &e->root_chunk;
-    for (Chunk *cp : all_chunks) {
-      Chunk &c = *cp;
-      if (c.done) (void)hipEventDestroy(c.done);
-      if (c.t0) (void)hipEventDestroy(c.t0);
-      if (c.t1) (void)hipEventDestroy(c.t1);
-      if (c.t2) (void)hipEventDestroy(c.t2);
-      free_pinned(c.in_blob);
-      free_pinned(c.out_blob);
-      free_pinned(c.mt);
-      if (c.d_mid) (void)hipFree(c.d_mid);
-    }
-    for (EdgeBatch &b : e->ebatches) {
-      if (b.done) (void)hipEventDestroy(b.done);
-      if (b.t0) (void)hipEventDestroy(b.t0);
-      if (b.t1) (void)hipEventDestroy(b.t1);
-      free_pinned(b.p1);
-      free_pinned(b.p2);
-      free_pinned(b.weight);
-      free_pinned(b.dist);
-      free_pinned(b.status);
-      if (b.d_mid) (void)hipFree(b.d_mid);
-    }
-    if (e->sy_mid) (void)hipFree(e->sy_mid);
-    if (e->mt_set_d) (void)hipFree(e->mt_set_d);
-    if (e->mt_walk_d) (void)hipFree(e->mt_walk_d);
-    if (e->mt_set_h) (void)hipHostFree(e->mt_set_h);
-    if (e->mt_walk_h) (void)hipHostFree(e->mt_walk_h);
-    delete e->plan_scratch;
-    if (e->uploader) {
-      e->uploader->release();
-      delete e->uploader;
-    }
-    delete e->bfs;
-    exchange_release(e);
-    field_release(e);
-    delete e->stitch;
-    free_pinned(e->sy_in);
-    free_pinned(e->sy_in2);
-    free_pinned(e->sy_f0);
-    free_pinned(e->sy_f1);
-    free_pinned(e->sy_i0);
-    free_pinned(e->sy_i1);
-    free_pinned(e->sy_i2);
-    if (e->d_cos) (void)hipFree(e->d_cos);
-    if (e->d_sin) (void)hipFree(e->d_sin);
-    if (e->d_ctr) (void)hipFree(e->d_ctr);
-    if (e->d_bounds) (void)hipFree(e->d_bounds);
-    if (e->top_xy_d) (void)hipFree(e->top_xy_d);
-    if (e->top_xy_h) (void)hipHostFree(e->top_xy_h);
-    if (e->top_ev) (void)hipEventDestroy(e->top_ev);
-    for (void *p : {(void *)e->idx_scratch.cell_of, (void *)e->idx_scratch.rank, (void *)e->idx_scratch.counts,
-                    (void *)e->idx_scratch.tmp, e->idx_scratch.aos, (void *)e->idx_scratch.hist,
-                    (void *)e->idx_scratch.base, (void *)e->idx_scratch.bin_tmp})
-      if (p) (void)hipFree(p);
-    if (e->s_main) (void)hipStreamDestroy(e->s_main);
-    if (e->s_edge) (void)hipStreamDestroy(e->s_edge);
-    if (e->s_aux) (void)hipStreamDestroy(e->s_aux);
   }
-  delete e;
+  delete e;  // the order of release is the members' order, see TrgEngine
 }
 
 const char *trg_engine_last_error(const TrgEngine *e) { return e ? e->err.c_str() : "null engine"; }
@@ -1068,67 +1117,63 @@ TrgStatus trg_engine_init_graph(TrgEngine *e, const float start_xyz[3], const Tr
 
 TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value) {
   if (!e || !key || !value) return TRG_ERR_INVALID_ARG;
+  enum Kind {
+    INT,             // atoi
+    BOOL,            // anything but "0" is true
+    ZERO_OR_ONE,     // -> bool, nothing else accepted
+    HOST_OR_DEVICE,  // -> bool "device", nothing else accepted
+    FLOAT,           // atof
+    POSITIVE_DOUBLE  // strtod, > 0 ("inf" included)
+  };
+  const struct {
+    const char *name;
+    Kind kind;
+    void *target;
+  } options[] = {
+      {"replay", HOST_OR_DEVICE, &e->use_device_bfs},
+      {"defer_overlap", ZERO_OR_ONE, &e->defer_overlap},
+      {"tie_inplace", BOOL, &e->tie_inplace},
+      {"keep_preclean", BOOL, &e->keep_preclean},
+      {"resolve_tickets", INT, &e->resolve_tickets},
+      // measurement knob: cost-field bucket width in mean edge costs ("inf": Bellman-Ford)
+      {"field_delta_scale", POSITIVE_DOUBLE, &e->field_delta_scale},
+      {"debug_gate_margin", FLOAT, &e->gate_margin},
+      {"debug_tie_every", INT, &e->debug_tie_every},
+      {"debug_spec_bound", INT, &e->debug_spec_bound},
+      {"debug_stall_level", INT, &e->debug_stall_level},
+      {"debug_lookback_level", INT, &e->debug_lookback_level},
+      {"debug_fallback_level", INT, &e->debug_fallback_level},
+      {"debug_call_stride", BOOL, &e->debug_call_stride},
+      {"debug_wait_rerun", BOOL, &e->debug_wait_rerun},
+  };
   const std::string k(key), v(value);
-  if (k == "replay") {
-    if (v == "host") e->use_device_bfs = false;
-    else if (v == "device") e->use_device_bfs = true;
-    else return e->fail(TRG_ERR_INVALID_ARG, "replay must be host or device");
-    return TRG_OK;
-  }
-  if (k == "debug_gate_margin") {
-    e->gate_margin = (float)atof(v.c_str());
-    return TRG_OK;
-  }
-  if (k == "debug_tie_every") {
-    e->debug_tie_every = atoi(v.c_str());
-    return TRG_OK;
-  }
-  if (k == "debug_spec_bound") {
-    e->debug_spec_bound = atoi(v.c_str());
-    return TRG_OK;
-  }
-  if (k == "defer_overlap") {
-    if (v == "1") e->defer_overlap = true;
-    else if (v == "0") e->defer_overlap = false;
-    else return e->fail(TRG_ERR_INVALID_ARG, "defer_overlap must be 0 or 1");
-    return TRG_OK;
-  }
-  if (k == "debug_stall_level") {
-    e->debug_stall_level = atoi(v.c_str());
-    return TRG_OK;
-  }
-  if (k == "debug_lookback_level") {
-    e->debug_lookback_level = atoi(v.c_str());
-    return TRG_OK;
-  }
-  if (k == "debug_call_stride") {
-    e->debug_call_stride = v != "0";
-    return TRG_OK;
-  }
-  if (k == "debug_wait_rerun") {
-    e->debug_wait_rerun = v != "0";
-    return TRG_OK;
-  }
-  if (k == "resolve_tickets") {
-    e->resolve_tickets = atoi(v.c_str());
-    return TRG_OK;
-  }
-  if (k == "tie_inplace") {
-    e->tie_inplace = v != "0";
-    return TRG_OK;
-  }
-  if (k == "debug_fallback_level") {
-    e->debug_fallback_level = atoi(v.c_str());
-    return TRG_OK;
-  }
-  if (k == "keep_preclean") {
-    e->keep_preclean = v != "0";
-    return TRG_OK;
-  }
-  if (k == "field_delta_scale") {  // measurement knob: cost-field bucket width in mean edge costs ("inf": Bellman-Ford)
-    const double d = strtod(v.c_str(), nullptr);
-    if (!(d > 0.0)) return e->fail(TRG_ERR_INVALID_ARG, "field_delta_scale must be > 0");
-    e->field_delta_scale = d;
+  for (const auto &o : options) {
+    if (k != o.name) continue;
+    switch (o.kind) {
+      case INT:
+        *(int *)o.target = atoi(value);
+        break;
+      case BOOL:
+        *(bool *)o.target = v != "0";
+        break;
+      case ZERO_OR_ONE:
+        if (v != "0" && v != "1") return e->fail(TRG_ERR_INVALID_ARG, k + " must be 0 or 1");
+        *(bool *)o.target = v == "1";
+        break;
+      case HOST_OR_DEVICE:
+        if (v != "host" && v != "device") return e->fail(TRG_ERR_INVALID_ARG, k + " must be host or device");
+        *(bool *)o.target = v == "device";
+        break;
+      case FLOAT:
+        *(float *)o.target = (float)atof(value);
+        break;
+      case POSITIVE_DOUBLE: {
+        const double d = strtod(value, nullptr);
+        if (!(d > 0.0)) return e->fail(TRG_ERR_INVALID_ARG, k + " must be > 0");
+        *(double *)o.target = d;
+        break;
+      }
+    }
     return TRG_OK;
   }
   return e->fail(TRG_ERR_INVALID_ARG, "unknown option " + k);
@@ -1404,9 +1449,9 @@ TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size
   *n_out = 0;
   if (passthrough) *passthrough = 0;
   if (n == 0) return TRG_OK;
-  float *d_in = nullptr, *d_out = nullptr;
-  HIPCHK(e, hipMalloc((void **)&d_in, n * stride * sizeof(float)));
-  hipError_t he = hipMalloc((void **)&d_out, n * 3 * sizeof(float));
+  DevBuf<float> d_in, d_out;  // (freed on every way out)
+  HIPCHK(e, d_in.ensure(n * stride));
+  hipError_t he = d_out.ensure(n * 3);
   if (he == hipSuccess)
     he = hipMemcpyAsync(d_in, xyz, n * stride * sizeof(float), hipMemcpyHostToDevice, e->s_main);
   int status = 0;
@@ -1414,8 +1459,6 @@ TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size
   if (he == hipSuccess) he = voxel_grid_filter(d_in, n, stride, leaf, d_out, &m, &status, e->s_main);
   if (he == hipSuccess && m)
     he = hipMemcpy(out_xyz, d_out, m * 3 * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
   if (he != hipSuccess)
     return e->fail(TRG_ERR_DEVICE, std::string("voxel filter: ") + hipGetErrorString(he));
   *n_out = m;
@@ -1504,3 +1547,7 @@ TrgStatus trg_engine_debug_map_index(TrgEngine *e, TrgKind map, float *x, float 
 
 #include "trg_engine_stitch.inc"
 #include "trg_engine_exchange.inc"
+
+// (here BfsBuffers, StitchBufs, Uploader, ExchangeState and FieldBufs are complete types)
+TrgEngine::TrgEngine() = default;
+TrgEngine::~TrgEngine() = default;

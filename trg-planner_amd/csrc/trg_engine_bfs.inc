@@ -9,56 +9,6 @@
 
 namespace {
 
-// a device array with its capacity in bytes; it owns its memory (an empty one makes no HIP call)
-struct DevArr {
-  void *p = nullptr;
-  size_t bytes = 0;
-  DevArr() = default;
-  DevArr(DevArr &&o) noexcept { *this = std::move(o); }
-  DevArr &operator=(DevArr &&o) noexcept {
-    std::swap(p, o.p);
-    std::swap(bytes, o.bytes);
-    return *this;
-  }
-  ~DevArr() { if (p) (void)hipFree(p); }
-};
-TrgStatus ensure_bytes(TrgEngine *e, DevArr &a, size_t need, bool keep = false) {
-  if (a.p && a.bytes >= need) return TRG_OK;
-  const size_t nb = std::max(need, a.bytes + a.bytes / 2);
-  void *np = nullptr;
-  HIPCHK(e, hipMalloc(&np, nb));
-  if (keep && a.p && a.bytes) {
-    hipError_t he = hipMemcpy(np, a.p, a.bytes, hipMemcpyDeviceToDevice);
-    if (he != hipSuccess) {
-      (void)hipFree(np);
-      return e->fail(TRG_ERR_DEVICE, std::string("grow copy: ") + hipGetErrorString(he));
-    }
-  }
-  if (a.p) (void)hipFree(a.p);
-  a.p = np;
-  a.bytes = nb;
-  return TRG_OK;
-}
-TrgStatus ensure_all(TrgEngine *e, std::initializer_list<std::pair<DevArr *, size_t>> need) {
-  for (const auto &n : need) {
-    const TrgStatus st = ensure_bytes(e, *n.first, n.second);
-    if (st != TRG_OK) return st;
-  }
-  return TRG_OK;
-}
-
-// a HIP event of the driver, destroyed on every exit
-struct Event {
-  hipEvent_t ev = nullptr;
-  Event() = default;
-  Event(Event &&o) noexcept { std::swap(ev, o.ev); }
-  Event &operator=(Event &&o) noexcept {
-    std::swap(ev, o.ev);
-    return *this;
-  }
-  ~Event() { if (ev) (void)hipEventDestroy(ev); }
-};
-
 // scratch of the tile-boundary stitch (trg_engine_stitch.inc)
 struct StitchBufs {
   DevArr flag, off, cnt, pair_a, pair_b, p1, p2, mid, status, npts, weight, dist, n_unc;
@@ -117,7 +67,7 @@ struct BfsBuffers {
   // finalize: pair table, CSR in creation order, cleanGraph's renumbering and the cleaned graph
   DevArr ht_key, ht_seq, ok_seq, deg, fill, rowptr, col, seq, w, dist;
   DevArr map_order, keep_flag, keep_pos, new2old, old2new, deg_new, rowptr_new, col2, w2, dist2, xyz2, state2;
-  int *h_ctrs = nullptr;  // pinned, device-visible: the counters of a level, its stamp in words 5 and 15
+  Pinned<int> h_ctrs;  // pinned, device-visible: the counters of a level, its stamp in words 5 and 15
   int stamp_serial = 0;
   // host mirror of the nodes [0, hm_state.size()): states and positions, fetched from the device when a
   // rare event needs them; it only holds nodes of levels that are final or being examined
@@ -126,7 +76,6 @@ struct BfsBuffers {
   std::vector<int> rp_stamp, rp_head;  // replay_level: cell -> newest node this replay created
   int rp_serial = 0;
   unsigned long long nodes_created = 0, nodes_invalid = 0;  // by the levels that became final
-  ~BfsBuffers() { if (h_ctrs) (void)hipHostFree(h_ctrs); }
 };
 
 // the host mirror grown to the nodes [0, n)
@@ -864,7 +813,7 @@ TrgStatus Build::allocate() {
   B.nexp = (int4 *)bb.nexp.p;
   B.nhits = (int *)bb.nhits.p;
   if (!bb.h_ctrs) {
-    HIPCHK(e, hipHostMalloc((void **)&bb.h_ctrs, H_CTRS_WORDS * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(e, bb.h_ctrs.ensure(H_CTRS_WORDS, hipHostMallocMapped | hipHostMallocCoherent));
     memset(bb.h_ctrs, 0, H_CTRS_WORDS * sizeof(int));
   }
   {
@@ -943,8 +892,8 @@ TrgStatus Build::launch_deferred(long long c1, bool in_loop) {
     // batch was a fifth of the host's launch work per level)
     Event t0, t1;
     if ((n_eval_batches++ % 8) == 0 && def_events.size() < 8192) {
-      HIPCHK(e, hipEventCreate(&t0.ev));
-      HIPCHK(e, hipEventCreate(&t1.ev));
+      HIPCHK(e, t0.create());
+      HIPCHK(e, t1.create());
       HIPCHK(e, hipEventRecord(t0.ev, st_));
     }
     // the number of selected calls lives on the device: the grid is an upper bound
@@ -985,8 +934,8 @@ TrgStatus Build::grow_call_log(size_t need) {
 // ---- phase 3: the level loop ---------------------------------------------------------------------------
 TrgStatus Build::level_loop() {
   TrgStatus st;
-  for (Event *ev : {&ev0, &ev1, &evn0, &evn1}) HIPCHK(e, hipEventCreate(&ev->ev));
-  for (Event *ev : {&ev_order, &ev_nodes}) HIPCHK(e, hipEventCreateWithFlags(&ev->ev, hipEventDisableTiming));
+  for (Event *ev : {&ev0, &ev1, &evn0, &evn1}) HIPCHK(e, ev->create());
+  for (Event *ev : {&ev_order, &ev_nodes}) HIPCHK(e, ev->create(false));
   bool have_expand = false;  // this level's expansion was issued by the previous iteration
   // Kernel timing inside the level loop is SAMPLED: an event pair around a kernel costs ~12 us of
   // stream time.  Every TIMED_EVERY-th level is timed and the totals are scaled by

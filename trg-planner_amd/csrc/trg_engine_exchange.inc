@@ -60,9 +60,8 @@ struct ExchangeState {
   bool owned = false;  // created by trg_engine_comm_init (destroyed with the engine)
   int nranks = 0, rank = 0;
   DevArr rec, edges, send, recv, all, cnt;
-  long long *h_cnt = nullptr;  // pinned, nranks + 1 words
-  ~ExchangeState() {  // (the DevArrs free themselves)
-    if (h_cnt) (void)hipHostFree(h_cnt);
+  Pinned<long long> h_cnt;  // nranks + 1 words
+  ~ExchangeState() {  // (the buffers free themselves, after this)
     if (comm && owned && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(comm);
   }
 };
@@ -83,13 +82,13 @@ TrgStatus exchange_allgatherv(TrgEngine *e, ExchangeState &x, const void *d_mine
   const int R = x.nranks;
   if ((st = ensure_bytes(e, x.cnt, (size_t)(R + 1) * sizeof(long long))) != TRG_OK) return st;
   long long *d_cnt = (long long *)x.cnt.p;
-  if (!x.h_cnt) HIPCHK(e, hipHostMalloc((void **)&x.h_cnt, (STITCH_MAX_TILES + 1) * sizeof(long long), hipHostMallocDefault));
+  HIPCHK(e, x.h_cnt.ensure(STITCH_MAX_TILES + 1));
   x.h_cnt[R] = n;
   HIPCHK(e, hipMemcpyAsync(d_cnt + R, x.h_cnt + R, sizeof(long long), hipMemcpyHostToDevice, s));
   RCCLCHK(e, g_rccl.AllGather(d_cnt + R, d_cnt, 1, ncclInt64, x.comm, s));
   HIPCHK(e, hipMemcpyAsync(x.h_cnt, d_cnt, (size_t)R * sizeof(long long), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
-  counts.assign(x.h_cnt, x.h_cnt + R);
+  counts.assign(x.h_cnt.p, x.h_cnt.p + R);
   long long pad = 1, total = 0;
   for (long long c : counts) {
     if (c < 0) return e->fail(TRG_ERR_DEVICE, "stitch exchange: another rank reported a failure");
@@ -113,12 +112,6 @@ TrgStatus exchange_allgatherv(TrgEngine *e, ExchangeState &x, const void *d_mine
   return TRG_OK;
 }
 
-void exchange_release(TrgEngine *e) {
-  if (!e->exchange) return;
-  delete e->exchange;
-  e->exchange = nullptr;
-}
-
 }  // namespace
 
 extern "C" {
@@ -138,7 +131,7 @@ TrgStatus trg_engine_comm_init(TrgEngine *e, const uint8_t id[TRG_COMM_ID_BYTES]
   if (!id || nranks < 1 || nranks > STITCH_MAX_TILES || rank < 0 || rank >= nranks)
     return e->fail(TRG_ERR_INVALID_ARG, "comm_init: bad arguments");
   if (!g_rccl.load()) return e->fail(TRG_ERR_DEVICE, g_rccl.err);
-  if (!e->exchange) e->exchange = new ExchangeState();
+  if (!e->exchange) e->exchange.reset(new ExchangeState());
   ExchangeState &x = *e->exchange;
   if (x.comm && x.owned) (void)g_rccl.CommDestroy(x.comm);
   x.comm = nullptr;
@@ -155,7 +148,7 @@ TrgStatus trg_engine_comm_adopt(TrgEngine *e, void *nccl_comm) {
   REQUIRE_DEVICE(e);
   if (!nccl_comm) return e->fail(TRG_ERR_INVALID_ARG, "comm_adopt: null communicator");
   if (!g_rccl.load()) return e->fail(TRG_ERR_DEVICE, g_rccl.err);
-  if (!e->exchange) e->exchange = new ExchangeState();
+  if (!e->exchange) e->exchange.reset(new ExchangeState());
   ExchangeState &x = *e->exchange;
   if (x.comm && x.owned) (void)g_rccl.CommDestroy(x.comm);
   x.comm = (ncclComm_t)nccl_comm;
@@ -169,7 +162,7 @@ TrgStatus trg_engine_comm_adopt(TrgEngine *e, void *nccl_comm) {
 TrgStatus trg_engine_comm_destroy(TrgEngine *e) {
   if (!e) return TRG_ERR_INVALID_ARG;
   (void)hipSetDevice(e->device);
-  exchange_release(e);
+  e->exchange.reset();
   return TRG_OK;
 }
 

@@ -17,17 +17,10 @@ struct FieldBufs {
   float ec_sf = 0.0f;
   double mean_cost = 0.0;    // over relaxable edges
   bool bad_cost = false;
-  FieldState *h_state = nullptr;      // pinned
-  FieldEdgeStats *h_stats = nullptr;  // pinned
-  int *h_reached = nullptr;           // pinned
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  ~FieldBufs() {
-    if (h_state) (void)hipHostFree(h_state);
-    if (h_stats) (void)hipHostFree(h_stats);
-    if (h_reached) (void)hipHostFree(h_reached);
-    if (t0) (void)hipEventDestroy(t0);
-    if (t1) (void)hipEventDestroy(t1);
-  }
+  Pinned<FieldState> h_state;
+  Pinned<FieldEdgeStats> h_stats;
+  Pinned<int> h_reached;
+  Event t0, t1;
 };
 
 void field_release(TrgEngine *e) {
@@ -36,8 +29,7 @@ void field_release(TrgEngine *e) {
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->s_main);
   }
-  delete e->field;
-  e->field = nullptr;
+  e->field.reset();
 }
 
 TrgStatus field_solve(TrgEngine *e, int32_t source_id, const float *source_xy, float *cost, int32_t *hops,
@@ -49,18 +41,16 @@ TrgStatus field_solve(TrgEngine *e, int32_t source_id, const float *source_xy, f
   int src = source_id;
   if (source_id == -1) {
     if (!source_xy) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no source");
-    src = plan_nearest_node(e, source_xy[0], source_xy[1], e->plan_scratch->tied);  // planSafePath's start node
+    src = plan_nearest_node(e, source_xy[0], source_xy[1], e->plan_scratch.tied);  // planSafePath's start node
   }
   if (src < 0 || src >= V) return e->fail(TRG_ERR_INVALID_ARG, "cost field: source out of range");
-  if (!e->field) e->field = new FieldBufs();
+  if (!e->field) e->field.reset(new FieldBufs());
   FieldBufs &fb = *e->field;
-  if (!fb.h_state) {
-    HIPCHK(e, hipHostMalloc((void **)&fb.h_state, sizeof(FieldState), hipHostMallocDefault));
-    HIPCHK(e, hipHostMalloc((void **)&fb.h_stats, sizeof(FieldEdgeStats), hipHostMallocDefault));
-    HIPCHK(e, hipHostMalloc((void **)&fb.h_reached, sizeof(int), hipHostMallocDefault));
-    HIPCHK(e, hipEventCreate(&fb.t0));
-    HIPCHK(e, hipEventCreate(&fb.t1));
-  }
+  HIPCHK(e, fb.h_state.ensure(1));
+  HIPCHK(e, fb.h_stats.ensure(1));
+  HIPCHK(e, fb.h_reached.ensure(1));
+  HIPCHK(e, fb.t0.create());
+  HIPCHK(e, fb.t1.create());
   hipStream_t s = e->s_main;
   int syncs = 0;
 

@@ -13,9 +13,9 @@ TrgStatus build_map(TrgEngine *e, DevMap &m, const float *d_xyz, size_t n, size_
   }
   if (n > (size_t)0x7FFFFFF0) return e->fail(TRG_ERR_CAPACITY, "more than 2^31 map points");
   hipStream_t s = e->s_main;
-  hipEvent_t ev0, ev1;
-  HIPCHK(e, hipEventCreate(&ev0));
-  HIPCHK(e, hipEventCreate(&ev1));
+  Event ev0, ev1;  // around the index kernels
+  HIPCHK(e, ev0.create());
+  HIPCHK(e, ev1.create());
   HIPCHK(e, hipEventRecord(ev0, s));
   launch_init_bounds(e->d_bounds, s);
   launch_bounds(d_xyz, n, stride, e->d_bounds, s);
@@ -38,75 +38,31 @@ TrgStatus build_map(TrgEngine *e, DevMap &m, const float *d_xyz, size_t n, size_
   const int H = (int)floorf((y1 - y0) * inv_g) + 1;
   const size_t ncell = (size_t)W * H;
 
-  if (m.cap_pts < n) {
-    if (m.x) (void)hipFree(m.x);
-    if (m.y) (void)hipFree(m.y);
-    if (m.z) (void)hipFree(m.z);
-    if (m.perm) (void)hipFree(m.perm);
-    if (m.pt) (void)hipFree(m.pt);
-    m.x = m.y = m.z = nullptr;
-    m.perm = nullptr;
-    m.pt = nullptr;
-    HIPCHK(e, hipMalloc((void **)&m.pt, n * sizeof(float4)));
-    HIPCHK(e, hipMalloc((void **)&m.x, n * sizeof(float)));
-    HIPCHK(e, hipMalloc((void **)&m.y, n * sizeof(float)));
-    HIPCHK(e, hipMalloc((void **)&m.z, n * sizeof(float)));
-    HIPCHK(e, hipMalloc((void **)&m.perm, n * sizeof(int)));
-    m.cap_pts = n;
-  }
-  if (m.cap_cells < ncell + 1) {
-    if (m.cell_start) (void)hipFree(m.cell_start);
-    m.cell_start = nullptr;
-    HIPCHK(e, hipMalloc((void **)&m.cell_start, (ncell + 1) * sizeof(int)));
-    m.cap_cells = ncell + 1;
-  }
-  // scratch of the build, kept with the engine (allocating and freeing 240 MB per build costs as much as
-  // a kernel of it)
+  // the map's arrays and the scratch of the build are kept from build to build and grow to exactly the size a
+  // larger cloud needs (allocating and freeing 240 MB of scratch per build costs as much as a kernel of it)
+  HIPCHK(e, m.pt.ensure(n));
+  HIPCHK(e, m.x.ensure(n));
+  HIPCHK(e, m.y.ensure(n));
+  HIPCHK(e, m.z.ensure(n));
+  HIPCHK(e, m.perm.ensure(n));
+  HIPCHK(e, m.cell_start.ensure(ncell + 1));
   IndexScratch &sc = e->idx_scratch;
-  if (sc.cap_pts < n) {
-    if (sc.aos) (void)hipFree(sc.aos);
-    sc.aos = nullptr;
-    sc.cap_pts = 0;
-    HIPCHK(e, hipMalloc((void **)&sc.aos, n * 16));
-    sc.cap_pts = n;
-  }
+  HIPCHK(e, sc.aos.ensure(n));
   int bin_shift = 0, nbins = 0, nwg = 0;
   if (!getenv("TRG_INDEX_DIRECT") && index_bins_plan(n, ncell, &bin_shift, &nbins, &nwg)) {
     // through bins of ~one cell row (trg_kernels.hip): no global atomics, no random line per point
     const size_t nb = (size_t)nbins * nwg;
-    if (sc.cap_bins < nb) {
-      if (sc.hist) (void)hipFree(sc.hist);
-      if (sc.base) (void)hipFree(sc.base);
-      if (sc.bin_tmp) (void)hipFree(sc.bin_tmp);
-      sc.hist = sc.base = sc.bin_tmp = nullptr;
-      sc.cap_bins = 0;
-      HIPCHK(e, hipMalloc((void **)&sc.hist, (nb + 1) * sizeof(int)));
-      HIPCHK(e, hipMalloc((void **)&sc.base, (nb + 1) * sizeof(int)));
-      HIPCHK(e, hipMalloc((void **)&sc.bin_tmp, (nb / 2048 + 4) * sizeof(int)));
-      sc.cap_bins = nb;
-    }
+    HIPCHK(e, sc.hist.ensure(nb + 1));
+    HIPCHK(e, sc.base.ensure(nb + 1));
+    HIPCHK(e, sc.bin_tmp.ensure(nb / 2048 + 4));
     // (the map's own record array is the first scratch: it is rewritten by the last kernel)
     launch_index_bins(d_xyz, n, stride, x0, y0, inv_g, W, H, (int)ncell, bin_shift, nbins, nwg, sc.hist, sc.base,
-                      sc.bin_tmp, m.pt, (float4 *)sc.aos, m.cell_start, m.x, m.y, m.z, m.perm, m.pt, s);
+                      sc.bin_tmp, m.pt, sc.aos, m.cell_start, m.x, m.y, m.z, m.perm, m.pt, s);
   } else {
-    if (sc.cap_direct < n) {
-      if (sc.cell_of) (void)hipFree(sc.cell_of);
-      if (sc.rank) (void)hipFree(sc.rank);
-      sc.cell_of = sc.rank = nullptr;
-      sc.cap_direct = 0;
-      HIPCHK(e, hipMalloc((void **)&sc.cell_of, n * sizeof(int)));
-      HIPCHK(e, hipMalloc((void **)&sc.rank, n * sizeof(int)));
-      sc.cap_direct = n;
-    }
-    if (sc.cap_cells < ncell) {
-      if (sc.counts) (void)hipFree(sc.counts);
-      if (sc.tmp) (void)hipFree(sc.tmp);
-      sc.counts = sc.tmp = nullptr;
-      sc.cap_cells = 0;
-      HIPCHK(e, hipMalloc((void **)&sc.counts, ncell * sizeof(int)));
-      HIPCHK(e, hipMalloc((void **)&sc.tmp, (ncell / 2048 + 4) * sizeof(int)));
-      sc.cap_cells = ncell;
-    }
+    HIPCHK(e, sc.cell_of.ensure(n));
+    HIPCHK(e, sc.rank.ensure(n));
+    HIPCHK(e, sc.counts.ensure(ncell));
+    HIPCHK(e, sc.tmp.ensure(ncell / 2048 + 4));
     int *d_cell_of = sc.cell_of, *d_rank = sc.rank, *d_counts = sc.counts, *d_tmp = sc.tmp;
     HIPCHK(e, hipMemsetAsync(d_counts, 0, ncell * sizeof(int), s));
     launch_cell_count(d_xyz, n, stride, x0, y0, inv_g, W, H, d_cell_of, d_rank, d_counts, s);
@@ -119,8 +75,6 @@ TrgStatus build_map(TrgEngine *e, DevMap &m, const float *d_xyz, size_t n, size_
   HIPCHK(e, hipGetLastError());
   float ms = 0;
   (void)hipEventElapsedTime(&ms, ev0, ev1);
-  (void)hipEventDestroy(ev0);
-  (void)hipEventDestroy(ev1);
 
   m.n = n;
   m.g = g;
@@ -163,21 +117,10 @@ TrgStatus build_map(TrgEngine *e, DevMap &m, const float *d_xyz, size_t n, size_
 constexpr int UP_THREADS = 4, UP_SLOTS = 2;
 constexpr size_t UP_CHUNK = (size_t)8 << 20;
 struct Uploader {
-  char *pinned = nullptr;  // UP_THREADS * UP_SLOTS chunks
-  hipStream_t st[UP_THREADS] = {};
-  hipEvent_t ev[UP_THREADS][UP_SLOTS] = {};
-  float *d_in = nullptr;   // device staging of the raw cloud (kept across calls)
-  size_t d_cap = 0;
-  void release() {
-    if (pinned) (void)hipHostFree(pinned);
-    for (auto &s : st)
-      if (s) (void)hipStreamDestroy(s);
-    for (auto &row : ev)
-      for (auto &x : row)
-        if (x) (void)hipEventDestroy(x);
-    if (d_in) (void)hipFree(d_in);
-    *this = Uploader();
-  }
+  Pinned<char> pinned;  // UP_THREADS * UP_SLOTS chunks
+  Stream st[UP_THREADS];
+  Event ev[UP_THREADS][UP_SLOTS];
+  DevBuf<float> d_in;  // device staging of the raw cloud (kept across calls)
 };
 
 TrgStatus staged_upload(TrgEngine *e, void *d_dst, const void *src, size_t bytes) {
@@ -190,12 +133,12 @@ TrgStatus staged_upload(TrgEngine *e, void *d_dst, const void *src, size_t bytes
     HIPCHK(e, hipStreamSynchronize(e->s_main));
     return TRG_OK;
   }
-  if (!u.pinned) {
-    HIPCHK(e, hipHostMalloc((void **)&u.pinned, UP_CHUNK * UP_THREADS * UP_SLOTS, hipHostMallocDefault));
-    for (int t = 0; t < UP_THREADS; ++t) {
-      HIPCHK(e, hipStreamCreateWithFlags(&u.st[t], hipStreamNonBlocking));
-      for (int k = 0; k < UP_SLOTS; ++k) HIPCHK(e, hipEventCreateWithFlags(&u.ev[t][k], hipEventDisableTiming));
-    }
+  // (made on the first cloud that goes this way; each of these keeps what it has, so a set that a failure left
+  // half made is completed here)
+  HIPCHK(e, u.pinned.ensure(UP_CHUNK * UP_THREADS * UP_SLOTS));
+  for (int t = 0; t < UP_THREADS; ++t) {
+    HIPCHK(e, u.st[t].create());
+    for (int k = 0; k < UP_SLOTS; ++k) HIPCHK(e, u.ev[t][k].create(false));
   }
   const size_t nchunk = (bytes + UP_CHUNK - 1) / UP_CHUNK;
   std::atomic<int> bad{0};
@@ -232,13 +175,7 @@ TrgStatus upload_and_build(TrgEngine *e, DevMap &m, const float *xyz, size_t n, 
   }
   Uploader &u = *e->uploader;
   const size_t floats = n * stride;
-  if (u.d_cap < floats) {
-    if (u.d_in) (void)hipFree(u.d_in);
-    u.d_in = nullptr;
-    u.d_cap = 0;
-    HIPCHK(e, hipMalloc((void **)&u.d_in, floats * sizeof(float)));
-    u.d_cap = floats;
-  }
+  HIPCHK(e, u.d_in.ensure(floats));
   auto t0 = Clock::now();
   TrgStatus st = staged_upload(e, u.d_in, xyz, floats * sizeof(float));
   e->stats.ms_upload = ms_since(t0);

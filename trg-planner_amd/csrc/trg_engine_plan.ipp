@@ -182,7 +182,6 @@ TrgStatus plan_prepare(TrgEngine *e) {
     snapshot_csr(e, e->csr_global);
   }
   ensure_host_grid(e);
-  if (!e->plan_scratch) e->plan_scratch = new PlanScratch();
   return TRG_OK;
 }
 
@@ -197,7 +196,7 @@ TrgStatus trg_engine_plan(TrgEngine *e, const float start_xy[2], const float goa
   info->num_points = 0;
   TrgStatus st = plan_prepare(e);
   if (st != TRG_OK) return st;
-  PlanScratch &ps = *e->plan_scratch;
+  PlanScratch &ps = e->plan_scratch;
   // setGoal
   e->goal_pose2d[0] = goal_xyz[0];
   e->goal_pose2d[1] = goal_xyz[1];
@@ -221,7 +220,7 @@ TrgStatus trg_engine_plan_batch(TrgEngine *e, const float *starts_xy, const floa
   if (m == 0) return TRG_OK;
   TrgStatus st = plan_prepare(e);
   if (st != TRG_OK) return st;
-  PlanScratch &ps0 = *e->plan_scratch;
+  PlanScratch &ps0 = e->plan_scratch;
   std::vector<int> starts(m), goals(m);
   for (size_t k = 0; k < m; ++k) {
     infos[k].direct_dist = infos[k].path_length = infos[k].avg_risk = 0.0f;

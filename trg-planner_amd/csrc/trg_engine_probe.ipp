@@ -2,19 +2,15 @@
 // nearest map point, single edges) and the exact nearest-map-point tie-break against the reference's kd-tree order.
 // ---- synchronous probes ------------------------------------------------------------------------
 TrgStatus ensure_sync_scratch(TrgEngine *e, size_t m) {
-  if (e->sy_cap >= m) return TRG_OK;
-  size_t cap = std::max<size_t>(m, 1024);
-  HIPCHK(e, alloc_pinned(e->sy_in, cap * 3));
-  HIPCHK(e, alloc_pinned(e->sy_in2, cap * 3));
-  HIPCHK(e, alloc_pinned(e->sy_f0, cap));
-  HIPCHK(e, alloc_pinned(e->sy_f1, cap));
-  HIPCHK(e, alloc_pinned(e->sy_i0, cap));
-  HIPCHK(e, alloc_pinned(e->sy_i1, cap));
-  HIPCHK(e, alloc_pinned(e->sy_i2, cap));
-  if (e->sy_mid) (void)hipFree(e->sy_mid);
-  e->sy_mid = nullptr;
-  HIPCHK(e, hipMalloc((void **)&e->sy_mid, edge_mid_floats(cap) * sizeof(float)));
-  e->sy_cap = cap;
+  const size_t cap = std::max<size_t>(m, 1024);  // (each of these is a comparison once it is large enough)
+  HIPCHK(e, e->sy_in.ensure(cap * 3));
+  HIPCHK(e, e->sy_in2.ensure(cap * 3));
+  HIPCHK(e, e->sy_f0.ensure(cap));
+  HIPCHK(e, e->sy_f1.ensure(cap));
+  HIPCHK(e, e->sy_i0.ensure(cap));
+  HIPCHK(e, e->sy_i1.ensure(cap));
+  HIPCHK(e, e->sy_i2.ensure(cap));
+  HIPCHK(e, e->sy_mid.ensure(edge_mid_floats(cap)));
   return TRG_OK;
 }
 
@@ -80,11 +76,8 @@ struct TiePoint {
 };
 
 TrgStatus ensure_tie_scratch(TrgEngine *e) {
-  if (e->mt_set_d) return TRG_OK;
-  HIPCHK(e, hipMalloc((void **)&e->mt_set_d, sizeof(MapTieSet)));
-  HIPCHK(e, hipMalloc((void **)&e->mt_walk_d, sizeof(MapTieWalk)));
-  HIPCHK(e, hipHostMalloc((void **)&e->mt_set_h, sizeof(MapTieSet), hipHostMallocDefault));
-  HIPCHK(e, hipHostMalloc((void **)&e->mt_walk_h, sizeof(MapTieWalk), hipHostMallocDefault));
+  HIPCHK(e, e->mt_set.ensure(1));
+  HIPCHK(e, e->mt_walk.ensure(1));
   return TRG_OK;
 }
 
@@ -120,13 +113,12 @@ TrgStatus ensure_map_top(TrgEngine *e, DevMap &m) {
   m.top_wait();  // (the global map's top is prepared beside the build)
   if (m.top_m > 0) return TRG_OK;
   const int M = (int)std::min<size_t>(m.n, MAP_TOP_POINTS);
-  float *d_xy = nullptr;
-  HIPCHK(e, hipMalloc((void **)&d_xy, (size_t)M * 2 * sizeof(float)));
+  DevBuf<float> d_xy;
+  HIPCHK(e, d_xy.ensure((size_t)M * 2));
   launch_collect_first(m.view, M, d_xy, e->s_aux);
   m.top_xy.resize((size_t)M * 2);
   hipError_t he = hipMemcpyAsync(m.top_xy.data(), d_xy, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost, e->s_aux);
   if (he == hipSuccess) he = hipStreamSynchronize(e->s_aux);
-  (void)hipFree(d_xy);
   if (he != hipSuccess) return e->fail(TRG_ERR_DEVICE, std::string("map top: ") + hipGetErrorString(he));
   insert_map_top(m, M);
   return TRG_OK;
@@ -142,11 +134,9 @@ void start_map_top(TrgEngine *e, DevMap &m) {
   if (m.n == 0) return;
   if (ensure_tie_scratch(e) != TRG_OK) return;
   const int M = (int)std::min<size_t>(m.n, MAP_TOP_POINTS);
-  if (!e->top_xy_d && hipMalloc((void **)&e->top_xy_d, (size_t)MAP_TOP_POINTS * 2 * sizeof(float)) != hipSuccess) return;
-  if (!e->top_xy_h &&
-      hipHostMalloc((void **)&e->top_xy_h, (size_t)MAP_TOP_POINTS * 2 * sizeof(float), hipHostMallocDefault) != hipSuccess)
+  if (e->top_xy_d.ensure((size_t)MAP_TOP_POINTS * 2) != hipSuccess ||
+      e->top_xy_h.ensure((size_t)MAP_TOP_POINTS * 2) != hipSuccess || e->top_ev.create(false) != hipSuccess)
     return;
-  if (!e->top_ev && hipEventCreateWithFlags(&e->top_ev, hipEventDisableTiming) != hipSuccess) return;
   launch_collect_first(m.view, M, e->top_xy_d, e->s_aux);
   if (hipMemcpyAsync(e->top_xy_h, e->top_xy_d, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost, e->s_aux) !=
           hipSuccess ||
@@ -225,19 +215,19 @@ TrgStatus map_first_of_two(TrgEngine *e, DevMap &m, float qx, float qy, const Ti
       cur = child;
     }
   }
-  *e->mt_walk_h = w;
-  HIPCHK(e, hipMemcpyAsync(e->mt_walk_d, e->mt_walk_h, sizeof(MapTieWalk), hipMemcpyHostToDevice, s));
+  *e->mt_walk.h = w;
+  HIPCHK(e, hipMemcpyAsync(e->mt_walk.d, e->mt_walk.h, sizeof(MapTieWalk), hipMemcpyHostToDevice, s));
   for (int batch = 0; batch < 64; ++batch) {
     // what is left of the region after the top of the tree holds ~N / 8192 points: one workgroup walks it
     // (a full-size region -- a map smaller than the top -- cannot get here)
-    launch_map_tie_walk(m.view, e->mt_walk_d, 0, 64, s);
-    HIPCHK(e, hipMemcpyAsync(e->mt_walk_h, e->mt_walk_d, sizeof(MapTieWalk), hipMemcpyDeviceToHost, s));
+    launch_map_tie_walk(m.view, e->mt_walk.d, 0, 64, s);
+    HIPCHK(e, hipMemcpyAsync(e->mt_walk.h, e->mt_walk.d, sizeof(MapTieWalk), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
-    if (e->mt_walk_h->done == 1) {
-      *first = e->mt_walk_h->first;
+    if (e->mt_walk.h->done == 1) {
+      *first = e->mt_walk.h->first;
       return TRG_OK;
     }
-    if (e->mt_walk_h->done) break;
+    if (e->mt_walk.h->done) break;
   }
   return e->fail(TRG_ERR_DEVICE, "nearest-point tie-break lost its candidates (internal error)");
 }
@@ -247,10 +237,10 @@ TrgStatus map_nn_exact(TrgEngine *e, DevMap &m, float qx, float qy, float *z, bo
   TrgStatus st = ensure_tie_scratch(e);
   if (st != TRG_OK) return st;
   hipStream_t s = e->s_aux;  // (the map is read-only here; the main stream may hold speculative work)
-  launch_map_tied_set(m.view, qx, qy, e->prm.robot_size, e->mt_set_d, s);
-  HIPCHK(e, hipMemcpyAsync(e->mt_set_h, e->mt_set_d, sizeof(MapTieSet), hipMemcpyDeviceToHost, s));
+  launch_map_tied_set(m.view, qx, qy, e->prm.robot_size, e->mt_set.d, s);
+  HIPCHK(e, hipMemcpyAsync(e->mt_set.h, e->mt_set.d, sizeof(MapTieSet), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
-  const MapTieSet T = *e->mt_set_h;
+  const MapTieSet T = *e->mt_set.h;
   *found = T.count > 0;
   if (!*found) return TRG_OK;
   const int n = std::min(T.count, MAPTIE_SET_CAP);

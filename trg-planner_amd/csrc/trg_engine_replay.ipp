@@ -2,9 +2,10 @@
 // (trg.cpp:372-454) over chunks of GPU-evaluated samples and edges -- updateGraph's path and the fallback of the
 // device-resident BFS (trg_engine_bfs.inc).
 // ---- chunk pipeline ----------------------------------------------------------------------------
+// made on the first replay; every owner keeps what it has, so this is cheap to repeat and completes a set that a
+// failure left half made
 TrgStatus ensure_chunks(TrgEngine *e) {
   const int S = e->prm.sample_num;
-  if (e->chunk_S == S && e->chunks[0].done) return TRG_OK;
   const size_t cmax = TrgEngine::CHUNK_MAX;
   const size_t slots = cmax * (size_t)std::max(S, 1);
   Chunk *all_chunks[TrgEngine::NCHUNK + 1];
@@ -12,38 +13,22 @@ TrgStatus ensure_chunks(TrgEngine *e) {
   all_chunks[TrgEngine::NCHUNK] = &e->root_chunk;
   for (Chunk *cp : all_chunks) {
     Chunk &c = *cp;
-    if (!c.done) {
-      HIPCHK(e, hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
-      HIPCHK(e, hipEventCreate(&c.t0));
-      HIPCHK(e, hipEventCreate(&c.t1));
-      HIPCHK(e, hipEventCreate(&c.t2));
-    }
-    HIPCHK(e, alloc_pinned(c.in_blob, 6 * cmax));
-    HIPCHK(e, alloc_pinned(c.out_blob, 2 * cmax + 6 * slots));
-    HIPCHK(e, alloc_pinned(c.mt, 4 + 4 * (size_t)MAPTIE_CAP));
-    if (c.mid_cap < slots) {
-      if (c.d_mid) (void)hipFree(c.d_mid);
-      c.d_mid = nullptr;
-      HIPCHK(e, hipMalloc((void **)&c.d_mid, edge_mid_floats(slots) * sizeof(float)));
-      c.mid_cap = slots;
-    }
+    HIPCHK(e, c.done.create(false));
+    for (Event *ev : {&c.t0, &c.t1, &c.t2}) HIPCHK(e, ev->create());
+    HIPCHK(e, c.in_blob.ensure(6 * cmax));
+    HIPCHK(e, c.out_blob.ensure(2 * cmax + 6 * slots));
+    HIPCHK(e, c.mt.ensure(4 + 4 * (size_t)MAPTIE_CAP));
+    HIPCHK(e, c.mid.ensure(edge_mid_floats(slots)));
   }
+  const size_t emax = TrgEngine::EBATCH_MAX;
   for (EdgeBatch &b : e->ebatches) {
-    if (!b.done) {
-      HIPCHK(e, hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
-      HIPCHK(e, hipEventCreate(&b.t0));
-      HIPCHK(e, hipEventCreate(&b.t1));
-    }
-    HIPCHK(e, alloc_pinned(b.p1, (size_t)TrgEngine::EBATCH_MAX * 3));
-    HIPCHK(e, alloc_pinned(b.p2, (size_t)TrgEngine::EBATCH_MAX * 3));
-    HIPCHK(e, alloc_pinned(b.weight, (size_t)TrgEngine::EBATCH_MAX));
-    HIPCHK(e, alloc_pinned(b.dist, (size_t)TrgEngine::EBATCH_MAX));
-    HIPCHK(e, alloc_pinned(b.status, (size_t)TrgEngine::EBATCH_MAX));
-    if (!b.d_mid)
-      HIPCHK(e, hipMalloc((void **)&b.d_mid,
-                          edge_mid_floats(TrgEngine::EBATCH_MAX) * sizeof(float)));
+    HIPCHK(e, b.done.create(false));
+    for (Event *ev : {&b.t0, &b.t1}) HIPCHK(e, ev->create());
+    for (PinnedBuf<float> *p : {&b.p1, &b.p2}) HIPCHK(e, p->ensure(emax * 3));
+    for (PinnedBuf<float> *p : {&b.weight, &b.dist}) HIPCHK(e, p->ensure(emax));
+    HIPCHK(e, b.status.ensure(emax));
+    HIPCHK(e, b.mid.ensure(edge_mid_floats(emax)));
   }
-  e->chunk_S = S;
   return TRG_OK;
 }
 
@@ -72,7 +57,7 @@ TrgStatus submit_chunk(TrgEngine *e, Chunk &c, int first, int count) {
                       c.sy.d, c.sz.d, e->d_ctr, c.mt.d, (MapTieRec *)(c.mt.d + 4), s);
   HIPCHK(e, hipEventRecord(c.t1, s));
   launch_spec_edges(e->gmap.view, q, c.node_xyz.d, count, c.n_acc.d, c.sx.d, c.sy.d, c.sz.d,
-                    c.d_mid, c.status.d, nullptr, c.weight.d, c.dist.d, e->d_ctr, s);
+                    c.mid, c.status.d, nullptr, c.weight.d, c.dist.d, e->d_ctr, s);
   HIPCHK(e, hipEventRecord(c.t2, s));
   HIPCHK(e, hipMemcpyAsync(c.out_blob.h, c.out_blob.d, c.out_words * sizeof(uint32_t),
                            hipMemcpyDeviceToHost, s));
@@ -187,7 +172,7 @@ TrgStatus flush_pending(TrgEngine *e, bool all) {
     HIPCHK(e, hipMemcpyAsync(b->p2.d, b->p2.h, (size_t)cnt * 3 * sizeof(float),
                              hipMemcpyHostToDevice, s));
     HIPCHK(e, hipEventRecord(b->t0, s));
-    launch_edges(e->gmap.view, qparams(e), b->p1.d, b->p2.d, cnt, b->d_mid, b->status.d, nullptr,
+    launch_edges(e->gmap.view, qparams(e), b->p1.d, b->p2.d, cnt, b->mid, b->status.d, nullptr,
                  b->weight.d, b->dist.d, e->d_ctr, s);
     HIPCHK(e, hipEventRecord(b->t1, s));
     HIPCHK(e, hipMemcpyAsync(b->status.h, b->status.d, (size_t)cnt * sizeof(int),
