@@ -59,7 +59,10 @@ __device__ __forceinline__ void outcome_store(int *p, int v) {
 }
 
 // waves per SIMD the speculative-edge kernel is compiled for: 6 (80 registers, 3 spilled) measured best once the
-// per-disc ratio division became a branch (4: +0.7 ms, 5: +0.4, 7: see DESIGN, 8: +2.9 -- the LDS tiles allow 30 per CU)
+// per-disc ratio division became a branch (4: +0.7 ms, 5: +0.4, 7: see DESIGN, 8: +2.9 -- the LDS tiles allow 30 per CU).
+// Measured again with the status-only edge evaluation (GATHER_STATUS: the 18 registers of the moments are gone, but
+// the disc sweep is where the registers are short): 6 (80 registers, 5 spilled) is still best -- 7 (72 registers,
+// 26 spilled): +0.9 ms per C3 build, 8 (64 registers, 27 spilled): +3.1 ms (profiles/r05_spec_status_ab.txt)
 #ifndef SPEC_WAVES_PER_SIMD
 #define SPEC_WAVES_PER_SIMD 6
 #endif

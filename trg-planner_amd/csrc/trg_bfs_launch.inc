@@ -100,6 +100,12 @@ void launch_bfs_stats(const BfsDev &B, int V, unsigned long long *out, hipStream
   hipLaunchKernelGGL(k_bfs_stats, dim3(nb), dim3(256), 0, s, B, V, out);
 }
 
+void launch_node_cov(const MapView &m, QueryParams p, const BfsDev &B, int v_lo, int v_hi, hipStream_t s) {
+  v_lo = std::max(v_lo, 1);  // node 0 is the root
+  if (v_hi <= v_lo) return;
+  hipLaunchKernelGGL(k_node_cov, dim3((v_hi - v_lo + NCW - 1) / NCW), dim3(NCW * WAVE), 0, s, m, p, B, v_lo, v_hi);
+}
+
 void launch_node_weights(const BfsDev &B, int V, hipStream_t s) {
   if (V <= 1) return;
   hipLaunchKernelGGL(k_node_weights, dim3((V - 1 + 255) / 256), dim3(256), 0, s, B, V);

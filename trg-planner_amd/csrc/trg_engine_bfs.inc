@@ -608,7 +608,9 @@ TrgStatus Build::replay_level(Level &lv) {
         call_st[slot] = sr.status & EDGE_STATUS_MASK;  // the weight follows after the loop (k_node_weights)
         call_d[slot] = sr.dist;
         next_front.push_back(id);
-        for (int q = 0; q < 6; ++q) nc.cov[q] = sr.cov[q];
+        // the covariance follows on the device (k_node_cov, after the loop) unless the host re-evaluated the
+        // edge and left its weight
+        if (sr.w_given) nc.cov[0] = sr.cov[0];
         nc.w_given = sr.w_given;
         nc.call = (int)(lv.call_base + (long long)slot);
       } else {
@@ -1075,8 +1077,13 @@ TrgStatus Build::finish_deferred() {
     HIPCHK(e, hipMemsetAsync(F.ht_key, 0xFF, (size_t)fht * sizeof(unsigned long long), s));
     HIPCHK(e, hipMemsetAsync(F.ht_seq, 0x7F, (size_t)fht * sizeof(int), s));
   }
-  launch_node_weights(B, V, s);  // weights of the edges to the nodes the BFS created (the commit kept
-                                 // their covariances); touches only the calls that created a node
+  // The covariances of the edges that created the nodes (the level loop only decided whether those edges hold):
+  // all nodes in ONE launch, here, where every level is final and the main stream is idle while the deferred
+  // stream finishes its last batches.  (Handed over level by level beside the loop, like the call batches, the
+  // same work comes as ~370 small launches that take vector issue from the level kernels: DESIGN.md section 4.)
+  launch_node_cov(m.view, qp, B, 1, V, s);
+  launch_node_weights(B, V, s);  // weights of the edges to the nodes the BFS created, from those covariances (same
+                                 // stream: ordered behind k_node_cov); touches only the calls that created a node
   if (e->step3) {
     // step 3 (trg.cpp:429-444): the node tree rebuilt on the device, every valid node's neighbour calls into
     // the entries behind its creating call; the deferred pipeline below takes them like all other calls

@@ -195,7 +195,7 @@ struct alignas(16) SlotRec {
                    // new node; SLOT_TIE: the nearest pre-level node was not unique
   int status;      // speculative parent edge (candidates): EDGE_* code and flags
   float dist;      //   its length
-  float cov[6];    //   covariance of its gather (xx xy xz yy yz zz), or cov[0] = weight when w_given
+  float cov[6];    //   cov[0] = weight when w_given (set by the host), else unused: k_node_cov computes the covariance
   int w_given;     //   1: the weight itself is stored (host re-evaluation after a map tie)
   int hits;        //   map points inside the edge's query radii (instrumentation)
 };
@@ -224,7 +224,8 @@ struct alignas(16) RescueRec {
   int slot[RESC_MAX];  // ... their slots
 };
 struct alignas(16) NodeCov {  // what the edge to a node created by the BFS still needs: its weight
-  float cov[6];               // is computed after the level loop (k_node_weights)
+  float cov[6];               // is computed after the level loop (k_node_weights) from the covariance of the gather
+                              // (xx xy xz yy yz zz, k_node_cov), or cov[0] is the weight when w_given
   int w_given;
   int call;                   // the wireEdge call that created the node
 };
@@ -314,7 +315,10 @@ typedef int TrgStatus_t;  // 0 ok
 // neighbour calls of every valid node into the call log behind its creating call; scratch: 6 V + 8 ints
 TrgStatus_t launch_step3_calls(const BfsDev &B, int V, float range, int *scratch, int *h_left, hipStream_t s);
 void launch_bfs_stats(const BfsDev &B, int V, unsigned long long *out, hipStream_t s);
-// weights of the edges to the nodes [1, V) the BFS created (covariance -> SVD -> weight)
+// covariances of the gathers of the edges that created the valid nodes [v_lo, v_hi) (their levels are final)
+void launch_node_cov(const MapView &m, QueryParams p, const BfsDev &B, int v_lo, int v_hi, hipStream_t s);
+// weights of the edges to the nodes [1, V) the BFS created (covariance -> SVD -> weight); after launch_node_cov
+// has covered every node
 void launch_node_weights(const BfsDev &B, int V, hipStream_t s);
 // deferred wireEdge evaluations of the calls list[0..count) (count_dev != nullptr: count is an upper
 // bound, the kernels take min(count, *count_dev))

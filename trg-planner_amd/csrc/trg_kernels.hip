@@ -21,6 +21,7 @@
 
 #include <float.h>
 #include <limits.h>
+#include <type_traits>
 
 namespace trg {
 
@@ -580,6 +581,27 @@ __device__ __forceinline__ bool ellipse_point(const EllipseParams &ep, float px,
   return keep;
 }
 
+// The membership tests of ellipse_point alone, for callers that only need how many points the gather keeps
+// (edge_gather<GATHER_STATUS>): the same fp32 expressions, no moments, no fp64.
+struct EllipseCounts {
+  int kept = 0, in_range = 0;
+};
+__device__ __forceinline__ bool ellipse_point(const EllipseParams &ep, float px, float py, float /*pz*/,
+                                              EllipseCounts &mo) {
+  const float ddx = px - ep.cx, ddy = py - ep.cy;
+  const float d2 = ddx * ddx + ddy * ddy;
+  bool keep = false;
+  if (d2 <= ep.a2) {
+    mo.in_range++;
+    const float X = ep.r00 * ddx + ep.r01 * ddy;
+    const float Y = ep.r10 * ddx + ep.r11 * ddy;
+    keep = ep.is_circle;
+    if (!ep.is_circle) keep = (X * X) * ep.bb + (Y * Y) * ep.a2 < ep.aabb;
+    if (keep) mo.kept++;
+  }
+  return keep;
+}
+
 // ---- LDS-staged neighbour tile -------------------------------------------------------------------
 // All map queries of one edge (the segment-walk discs and the ellipse gather) fall inside one
 // small box.  The wave loads the candidate points of that box ONCE -- every row segment is a
@@ -933,6 +955,16 @@ __device__ __forceinline__ void sweep_discs(const WaveTile &tile, int T, const f
 // One wave: the position-only part of TRG::wireEdge up to the moments of the covariance
 // (trg.cpp:269-338).  Writes the nine moments of an accepted edge into rec; the caller stores the
 // record header from the returned fields.
+//   GATHER_FULL     all of it.
+//   GATHER_STATUS   up to the decision (status and flags, dist, hits, n_pts as FULL returns them): the ellipse
+//                   sweep only counts the points it keeps -- no moments, no fp64, rec is not touched.  For the
+//                   level loop, which needs to know whether a candidate's parent edge holds and nothing else.
+//   GATHER_MOMENTS  for an edge FULL / STATUS found EDGE_OK: the moments alone (and n_pts).  Stages the SAME tile
+//                   (same box, same filter) and sums in the same order -- a lane's partial sums follow tile
+//                   order in the fast and in the general path alike, the reduction order is fixed -- so rec
+//                   gets bit for bit what FULL writes.  No segment walk, no counters.
+enum : int { GATHER_FULL = 0, GATHER_STATUS = 1, GATHER_MOMENTS = 2 };
+template <int MODE = GATHER_FULL>
 __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float x1, float y1,
                                   float z1, float x2, float y2, float z2, WaveTile &tile,
                                   float *rec, DeviceCounters *ctr) {
@@ -942,7 +974,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
   o.hits = 0;
   const EdgeGeom g = edge_geometry(p, x1, y1, z1, x2, y2, z2);
   o.dist = g.dist;
-  if (g.gated) {
+  if (MODE != GATHER_MOMENTS && g.gated) {
     o.status = EDGE_GATE;
     return o;
   }
@@ -1002,11 +1034,13 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
 
   unsigned long long hits = 0;
   const float ds = p.robot_size * 0.5f;
+  // what the ellipse sweeps accumulate per lane: the moments, or only the counts
+  typedef typename std::conditional<MODE == GATHER_STATUS, EllipseCounts, Moments>::type Gathered;
 
   // Fast path: ONE sweep over the staged tile serves every segment-walk disc; the per-disc
   // statistics are then examined in walk order, so the early exit on the first colliding disc --
   // and the hit count the reference would have produced up to it -- are unchanged.
-  if (T >= 0 && ds > 0.0f) {
+  if (MODE != GATHER_MOMENTS && T >= 0 && ds > 0.0f) {
     f2 q[KMAX];
     int K = 0;
     bool fits = true;
@@ -1104,7 +1138,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
       }
       EDGE_CUT(4)  // + disc reductions, medians, decisions
       // second sweep: ellipse gather (kept apart from the disc sweep to bound register pressure)
-      Moments mo;
+      Gathered mo;
       int kept = 0;
       for (int base = 0; base < T; base += WAVE) {
         const int i = base + lane;
@@ -1115,7 +1149,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
         }
         kept += __popcll(ballot(keep));
       }
-      if (TRG_EDGE_STAGE_CUT == 5) {  // + ellipse sweep
+      if constexpr (TRG_EDGE_STAGE_CUT == 5 && MODE == GATHER_FULL) {  // + ellipse sweep
         o.status = EDGE_SEG + (mo.s_x + mo.s_y + mo.s_z + mo.s_xx + mo.s_xy + mo.s_xz + mo.s_yy +
                                    mo.s_yz + mo.s_zz == 12345.0) + (kept > 100000);
         return o;
@@ -1132,7 +1166,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
         o.status = EDGE_FEW | g.uncertain;
         return o;
       }
-      reduce_store_moments(tile, mo, rec);
+      if constexpr (MODE == GATHER_FULL) reduce_store_moments(tile, mo, rec);
       o.status = EDGE_OK | g.uncertain;
       return o;
     }
@@ -1141,7 +1175,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
   // general path: one disc at a time (long edges, oversized boxes, dense maps)
   // segment walk, trg.cpp:282-288 (float accumulation of i is part of the semantics)
   int guard = 0;
-  for (float i = 0; i < g.dist; i += ds) {
+  for (float i = 0; MODE != GATHER_MOMENTS && i < g.dist; i += ds) {
     const float qx = x1 + i * g.dirx;
     const float qy = y1 + i * g.diry;
     bool col;
@@ -1165,7 +1199,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
   }
 
   // gather + rotate + filter (trg.cpp:304-325)
-  Moments mo;
+  Gathered mo;
   if (T >= 0) {
     for (int i = lane; i < T; i += WAVE) {
       const f2 pt = tile.xy[i];
@@ -1176,14 +1210,21 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
     for (int cyi = cr.cy0; cyi <= cr.cy1; ++cyi) {
       const int s = m.cell_start[cyi * m.W + cr.cx0];
       const int e = m.cell_start[cyi * m.W + cr.cx1 + 1];
+      // (not unrolled: with counts alone the unrolled loop takes ~90 registers more than the kernel has)
+#pragma clang loop unroll(disable)
       for (int i = s + lane; i < e; i += WAVE) ellipse_point(ep, m.x[i], m.y[i], m.z[i], mo);
     }
   }
   const int in_range = (T >= 0) ? staged_in_range : wave_sum(mo.in_range);
   const int kept = wave_sum(mo.kept);
+  o.n_pts = kept;
+  if constexpr (MODE == GATHER_MOMENTS) {
+    reduce_store_moments(tile, mo, rec);
+    o.status = EDGE_OK;
+    return o;
+  }
   hits += (unsigned long long)in_range;
   o.hits = (int)hits;
-  o.n_pts = kept;
   if (in_range == 0) {
     o.status = EDGE_EMPTY | g.uncertain;
     return o;
@@ -1192,7 +1233,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
     o.status = EDGE_FEW | g.uncertain;
     return o;
   }
-  reduce_store_moments(tile, mo, rec);
+  if constexpr (MODE == GATHER_FULL) reduce_store_moments(tile, mo, rec);
   o.status = EDGE_OK | g.uncertain;
   return o;
 }

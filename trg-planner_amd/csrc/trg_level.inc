@@ -8,8 +8,8 @@
 //                    every accepted sample (:408-413, from an LDS copy of the node grid around the
 //                    parent).  Samples with no pre-level node within robot_size may create a node
 //                    ("candidates"); they are entered into the level's hash (cell -> sample slot).
-//   k_level_spec     one wave per candidate: its speculative parent edge (wireEdge :269-338, up to the
-//                    covariance of the gather).
+//   k_level_spec     one wave per candidate: whether its speculative parent edge holds (wireEdge :269-338 up to
+//                    the decision; the covariance of the gather is left to k_node_cov).
 //   k_level_resolve  one wave per sample slot: what the sequential loop would have done with this
 //                    sample given everything EARLIER in the level (trg.cpp:406-452) -- skip, merge with
 //                    an existing or a newly created node, or create a node -- by waiting only for the
@@ -22,8 +22,9 @@
 // from a prefix over the whole level): it stores a reference to the creating call instead
 // (call_ref), the commit leaves the id in newid_of_call[], and the first pass over the call log
 // (k_first_insert) replaces references by ids.  The weight of the edge to a created node is not
-// needed inside the loop either (only whether the edge exists): the commit keeps the covariance
-// with the node and k_node_weights runs the SVDs (trg.cpp:339-363) for all nodes after the loop.
+// needed inside the loop either (only whether the edge exists): three candidates out of four never create
+// a node, so the covariance of the gather is computed for the created nodes alone (k_node_cov) and
+// k_node_weights runs the SVDs (trg.cpp:339-363), both for all nodes after the loop.
 
 __device__ __forceinline__ int call_ref(long long at) { return -(int)(at + 2); }       // <= -2
 // The call log holds B.cstride entries per sample slot: entry 0 is the slot's own wireEdge call (trg.cpp:416,
@@ -636,8 +637,10 @@ __global__ __launch_bounds__(NW *WAVE, NW == LSW ? LV_WAVES_PER_SIMD : 4) void k
 // The speculative parent edge of every candidate (a new node is Invalid iff that edge fails,
 // trg.cpp:425, 447-449): one wave per sample slot, the waves of non-candidates leave at once.  The
 // edge is evaluated like every other one (edge_gather: the capsule around the segment and the
-// gather disc staged into a per-wave LDS tile from the L2-resident map), up to the covariance of the
-// gather (trg.cpp:269-338); the SVD follows after the level loop.
+// gather disc staged into a per-wave LDS tile from the L2-resident map), up to its decision (trg.cpp:269-331):
+// the level loop reads the status and the length of a slot's edge and nothing else, so the ellipse sweep only
+// counts (GATHER_STATUS: no fp64 moments, no reduction, no covariance).  The covariance of the edges that did
+// create a node follows in k_node_cov, the SVD after the level loop.
 #ifndef TRG_LQW
 #define TRG_LQW 1
 #endif
@@ -677,27 +680,15 @@ __device__ __forceinline__ bool level_hash_insert(const BfsDev &B, int tag, int 
   return placed;
 }
 
-// one candidate's speculative parent edge (one wave): edge_gather up to the covariance, results into the slot's record
+// one candidate's speculative parent edge (one wave): edge_gather up to the decision, results into the slot's
+// record (its cov words are not written here: the host sets them together with w_given, nobody else reads them)
 __device__ __forceinline__ void spec_one(const MapView &m, const QueryParams &p, const BfsDev &B, int slot, int node,
-                                         int unit, float4 par, float qx, float qy, float qz, WaveTile &tile, float *rec,
+                                         int unit, float4 par, float qx, float qy, float qz, WaveTile &tile,
                                          int parity, DeviceCounters *ctr, int tl_tag) {
   const int lane = lane_id();
   if (lane == 0) TL_MARK(tl_tag, 2, unit);
-  const EdgeMidOut o = edge_gather(m, p, par.x, par.y, par.z, qx, qy, qz, tile, rec, ctr);
-  // the covariance of an accepted edge: its six entries on six lanes
-  float cv = 0.0f;
-  if ((o.status & EDGE_STATUS_MASK) == EDGE_OK) {
-    wave_lds_sync();  // the moments edge_gather left in rec
-    if (lane < 6) {
-      double sm[9];
-      const double *src = (const double *)(rec + MID_MOMENTS);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) sm[i] = src[i];
-      cv = cov_entry(sm, o.n_pts, lane);
-    }
-  }
+  const EdgeMidOut o = edge_gather<GATHER_STATUS>(m, p, par.x, par.y, par.z, qx, qy, qz, tile, nullptr, ctr);
   float *out = (float *)&B.slot_rec[slot];
-  if (lane < 6) out[8 + lane] = cv;
   if (lane == 0) {
     out[6] = __int_as_float(o.status);
     out[7] = o.dist;
@@ -733,7 +724,6 @@ __global__ __launch_bounds__(LQW *WAVE, SPEC_WAVES_PER_SIMD) void k_level_spec(M
                                                                             int node_base, int parity,
                                                                             DeviceCounters *ctr, int tl_tag) {
   __shared__ WaveTile tiles[LQW];
-  __shared__ alignas(16) float mids[LQW][MID_STRIDE];
   const int w = threadIdx.x >> 6;
   const int S = p.sample_num;
   if (count_dev) count = min(count, *count_dev);
@@ -753,7 +743,7 @@ __global__ __launch_bounds__(LQW *WAVE, SPEC_WAVES_PER_SIMD) void k_level_spec(M
   // vector register to spare)
   const float sqx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(r0.x)));
   const float sqy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(r0.y)));
-  spec_one(m, p, B, slot, node, slot - node_base * S, par, r0.x, r0.y, r0.z, tiles[w], mids[w], parity, ctr, tl_tag);
+  spec_one(m, p, B, slot, node, slot - node_base * S, par, r0.x, r0.y, r0.z, tiles[w], parity, ctr, tl_tag);
   if (!level_hash_insert(B, tl_tag, slot, sqx, sqy)) atomicOr(&B.ctrs[BFS_CTR_ERR], BFS_ERR_HASH);
 }
 
@@ -1396,7 +1386,10 @@ __device__ __forceinline__ void commit_role(CommitLds &C, const BfsDev &B, int m
     B.nz[id] = r0.z;
     B.nstate[id] = flag == 2 ? new_state : -1;
     B.nhits[id] = s3.w;  // map points inside the parent-edge queries (trg.cpp:425)
-    if (flag == 2) {  // what the weight of the creating edge still needs
+    if (flag == 2) {  // what the weight of the creating edge still needs: w_given (then cov[0] is the weight) and
+                      // the call.  The cov words of a slot without w_given are stale (k_level_spec does not write
+                      // them) and are copied all the same -- one 16-byte store, no branch: k_node_cov overwrites
+                      // all six before k_node_weights reads them
       int4 *dst = (int4 *)&B.ncov[id];
       dst[0] = s2;
       dst[1] = make_int4(s3.x, s3.y, s3.z, (int)call_at(B, call_base, slot));
@@ -1472,6 +1465,42 @@ __global__ __launch_bounds__(256) void k_bfs_stats(BfsDev B, int V, unsigned lon
   if (threadIdx.x < 6) {
     const unsigned long long t = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
     if (t) atomicAdd(&out[threadIdx.x], t);
+  }
+}
+
+// The covariance of the gather (trg.cpp:304-338) of the edge parent -> created node, for the nodes [v_lo, v_hi)
+// of levels that are final (the driver: all of them in one launch after the loop): one wave per node.
+// k_level_spec found the edge EDGE_OK with the same two positions (the parent's nx / ny / nz, and the sample's
+// x, y, z the commit stored as the node's), so GATHER_MOMENTS stages the same tile and leaves the same moments a
+// full evaluation would have.  Skips Invalid nodes, nodes whose weight the host supplied (w_given) and nodes
+// whose creating edge failed (step 3 rescued them).  Counts nothing: the edge's map hits were counted when
+// k_level_spec evaluated it.
+// Invariant: every NodeCov that k_node_weights reads without w_given was written here in this build.
+constexpr int NCW = 4;  // waves (= nodes) per workgroup, like the other edge kernels (measured at C3: single-wave
+                        // workgroups +0.05 ms per build, 8 waves +0.2)
+__global__ __launch_bounds__(NCW *WAVE, EDGE_WAVES_PER_SIMD) void k_node_cov(MapView m, QueryParams p, BfsDev B, int v_lo,
+                                                                          int v_hi) {
+  __shared__ WaveTile tiles[NCW];
+  __shared__ alignas(16) float mids[NCW][MID_STRIDE];
+  const int w = threadIdx.x >> 6, lane = lane_id();
+  const int id = v_lo + blockIdx.x * NCW + w;
+  if (id < 1 || id >= min(v_hi, B.vcap) || B.nstate[id] == -1) return;  // (wave-uniform, like every exit below)
+  const int2 gc = *(const int2 *)&B.ncov[id].w_given;  // w_given, call
+  if (gc.x) return;
+  const size_t at = (size_t)gc.y;
+  const int st = B.call_status[at];
+  if (st < 0 || (st & EDGE_STATUS_MASK) != EDGE_OK) return;
+  const int par = B.call_n1[at];
+  float *rec = mids[w];
+  const EdgeMidOut o = edge_gather<GATHER_MOMENTS>(m, p, B.nx[par], B.ny[par], B.nz[par], B.nx[id], B.ny[id],
+                                                   B.nz[id], tiles[w], rec, nullptr);
+  wave_lds_sync();  // the moments edge_gather left in rec
+  if (lane < 6) {   // the six entries on six lanes
+    double sm[9];
+    const double *src = (const double *)(rec + MID_MOMENTS);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) sm[i] = src[i];
+    B.ncov[id].cov[lane] = cov_entry(sm, o.n_pts, lane);
   }
 }
 
