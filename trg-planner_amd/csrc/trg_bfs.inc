@@ -420,7 +420,14 @@ __global__ __launch_bounds__(256) void k_fin_clean_deg(FinDev F, const int *new2
 // One 16-lane group per node, one entry per lane and pass: every entry is loaded once (a thread per node
 // that walked its row once per entry fetched 1.5-3 GB from HBM for 0.1 GB of entries -- the rows of a wave
 // are scattered and do not survive in the L2 between two walks).
+// PARTS: what a launch writes.  FIN_ALL is the whole cleaned graph.  A build whose creating-edge weights are
+// computed beside the copy of the cleaned graph to the host (Build::clean_and_fetch) launches FIN_STRUCTURE
+// first -- everything but w, none of which depends on a weight -- and FIN_WEIGHTS once k_node_weights has run:
+// the same traversal and ranks, w alone, taken from the call that made the entry (F.seq; F.w holds what
+// k_fin_scatter saw, which is older than k_node_weights there).
+enum : int { FIN_WEIGHTS = 1, FIN_STRUCTURE = 2, FIN_ALL = 3 };
 constexpr int FIN_ROW = 16;
+template <int PARTS>
 __global__ __launch_bounds__(256) void k_fin_clean_copy(FinDev F, BfsDev B, const int *new2old,
                                                         const int *old2new, const int *vn,
                                                         const int *rowptr_new, int *col, float *w,
@@ -429,7 +436,7 @@ __global__ __launch_bounds__(256) void k_fin_clean_copy(FinDev F, BfsDev B, cons
   const int l = threadIdx.x % FIN_ROW;
   if (k >= *vn) return;  // (whole groups leave together)
   const int o = new2old[k];
-  if (l == 0) {
+  if ((PARTS & FIN_STRUCTURE) && l == 0) {
     xyz[3 * k] = B.nx[o];
     xyz[3 * k + 1] = B.ny[o];
     xyz[3 * k + 2] = B.nz[o];
@@ -447,12 +454,13 @@ __global__ __launch_bounds__(256) void k_fin_clean_copy(FinDev F, BfsDev B, cons
 #pragma unroll
       for (int j = 0; j < FIN_ROW; ++j) rank += __shfl(other, j, FIN_ROW) < ks;
     }
-    if (have) {
+    if (have && (PARTS & FIN_STRUCTURE)) {
       const int nc = old2new[F.col[e]];
       if (nc < 0) atomicOr(&B.ctrs[BFS_CTR_ERR], BFS_ERR_CLEAN);
       col[dst0 + rank] = nc;
-      w[dst0 + rank] = F.w[e];
       dist[dst0 + rank] = F.dist[e];
     }
+    if (have && PARTS == FIN_ALL) w[dst0 + rank] = F.w[e];
+    if (have && PARTS == FIN_WEIGHTS) w[dst0 + rank] = B.call_w[ks];
   }
 }

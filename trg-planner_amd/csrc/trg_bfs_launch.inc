@@ -173,7 +173,8 @@ void launch_fin_rowsort(const FinDev &F, int V, hipStream_t s) {
 
 // cleanGraph on the device: keep flags in container order -> new ids -> compacted, remapped, ordered
 // rows.  keep_pos[V] (= rowptr of the flags) is the number of surviving nodes, rowptr_new[V] the edge
-// count; the host reads both afterwards.
+// count; the host reads both afterwards.  w == nullptr: everything but the weights, which
+// launch_fin_clean_weights writes later.
 void launch_fin_clean(const FinDev &F, const BfsDev &B, const int *map_order, int V, int *keep_flag,
                       int *keep_pos, int *new2old, int *old2new, int *deg_new, int *rowptr_new,
                       int *scan_tmp, int *col, float *w, float *dist, float *xyz, int *state,
@@ -187,6 +188,19 @@ void launch_fin_clean(const FinDev &F, const BfsDev &B, const int *map_order, in
   const int *vn = keep_pos + V;
   hipLaunchKernelGGL(k_fin_clean_deg, dim3(nb), dim3(256), 0, s, F, (const int *)new2old, vn, V, deg_new);
   launch_exclusive_scan(deg_new, rowptr_new, V, scan_tmp, s);
-  hipLaunchKernelGGL(k_fin_clean_copy, dim3((unsigned)(((long long)V * FIN_ROW + 255) / 256)), dim3(256), 0, s, F, B, (const int *)new2old,
-                     (const int *)old2new, vn, (const int *)rowptr_new, col, w, dist, xyz, state);
+  const dim3 grid((unsigned)(((long long)V * FIN_ROW + 255) / 256));
+  if (w)
+    hipLaunchKernelGGL(k_fin_clean_copy<FIN_ALL>, grid, dim3(256), 0, s, F, B, (const int *)new2old,
+                       (const int *)old2new, vn, (const int *)rowptr_new, col, w, dist, xyz, state);
+  else
+    hipLaunchKernelGGL(k_fin_clean_copy<FIN_STRUCTURE>, grid, dim3(256), 0, s, F, B, (const int *)new2old,
+                       (const int *)old2new, vn, (const int *)rowptr_new, col, w, dist, xyz, state);
+}
+
+void launch_fin_clean_weights(const FinDev &F, const BfsDev &B, int V, const int *keep_pos, const int *new2old,
+                              const int *rowptr_new, float *w, hipStream_t s) {
+  if (V <= 0) return;
+  hipLaunchKernelGGL(k_fin_clean_copy<FIN_WEIGHTS>, dim3((unsigned)(((long long)V * FIN_ROW + 255) / 256)), dim3(256),
+                     0, s, F, B, new2old, (const int *)nullptr, keep_pos + V, rowptr_new, (int *)nullptr, w,
+                     (float *)nullptr, (float *)nullptr, (int *)nullptr);
 }

@@ -587,6 +587,7 @@ struct TrgEngine {
   bool keep_preclean = false;    // instrumentation: snapshot the graph before cleanGraph
   bool use_device_bfs = true;    // device-resident BFS (off: host replay)
   bool defer_overlap = true;     // deferred edge evaluations pipelined behind the level loop on a 2nd stream
+  bool tail_overlap = true;      // after the loop: the creating edges' covariances beside the cleaned graph's copy to the host
   uint64_t graph_version = 1;    // bumped by everything that changes the global graph (queries cache per version)
   // planner state (A* runs straight on csr_global, see plan_on_csr): positions in the node tree's insertion
   // order for the rare order questions (nearest-node ties, several goal hits), and the search scratch
@@ -1132,6 +1133,7 @@ TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value
   } options[] = {
       {"replay", HOST_OR_DEVICE, &e->use_device_bfs},
       {"defer_overlap", ZERO_OR_ONE, &e->defer_overlap},
+      {"tail_overlap", ZERO_OR_ONE, &e->tail_overlap},
       {"tie_inplace", BOOL, &e->tie_inplace},
       {"keep_preclean", BOOL, &e->keep_preclean},
       {"resolve_tickets", INT, &e->resolve_tickets},

@@ -40,9 +40,11 @@ struct LevelSet {
 constexpr int H_CLEAN_TOTALS = 32;  // 2 words: nodes and edges that survive cleanGraph
 constexpr int H_ROUND2_CALLS = 34;  // calls round 2 of the deferred evaluations selected
 constexpr int H_STEP3_LEFT = 40;    // step 3's device node tree: nodes not yet placed
-constexpr int H_CTRS_WORDS = 64;
+constexpr int H_STATS64 = 64;       // 16 x 64 bit: the first words of B.stats64 (report_stats)
+constexpr int H_CTRS_WORDS = 96;
 static_assert(BFS_CTR_COUNT <= H_CLEAN_TOTALS && H_CLEAN_TOTALS + 2 <= H_ROUND2_CALLS &&
-                  H_ROUND2_CALLS < H_STEP3_LEFT && H_STEP3_LEFT < H_CTRS_WORDS,
+                  H_ROUND2_CALLS < H_STEP3_LEFT && H_STEP3_LEFT < H_STATS64 && H_STATS64 % 2 == 0 &&
+                  H_STATS64 + 32 <= H_CTRS_WORDS,
               "pinned words overlap");
 
 // words of B.stats64 the host reads: calls the deferred selections kept, longest resolve wait, rows that went
@@ -53,6 +55,7 @@ enum : int {
   S64_DEF_KEPT = 5, S64_MAX_SPIN, S64_MULTIPASS, S64_DRAWS, S64_SAMPLES, S64_DISC_HITS, S64_SPEC_HITS,
   S64_CANDIDATES, S64_PARENT_HITS, S64_PHASES = 16, S64_WORDS = 16 + 1024 * 8
 };
+static_assert(S64_PARENT_HITS < S64_PHASES, "report_stats fetches the words in front of S64_PHASES");
 
 struct BfsBuffers {
   BfsDev B{};
@@ -214,13 +217,31 @@ struct Build {
   long long def_lo = 0;  // first call not yet handed to the deferred pipeline
   size_t n_eval_batches = 0;
   std::vector<std::pair<Event, Event>> def_events;
-  Event ev0, ev1, evn0, evn1, ev_order, ev_nodes;
+  Event ev0, ev1, evn0, evn1, ev_order, ev_nodes, ev_structure, ev_weights;
+  // The tail as two resources.  The weights of the edges that created the nodes (k_node_cov, k_node_weights)
+  // feed ONE array of the result, w: with tail_split they run on the second stream beside the copies of the
+  // other six arrays to the host, and w follows as the last copy (clean_and_fetch).  Without it (builds with
+  // step 3, whose neighbour calls go between the weights and the deferred pipeline; keep_preclean, which
+  // downloads F.w; option tail_overlap=0) they run in the main stream in front of the deferred calls.
+  bool tail_split = false;
+  bool edge_stream_busy = false;  // the second stream was given work of the tail that nothing has waited for yet
   Clock::time_point t_fin;  // finalize: its start, TRG_TIMING set
   bool trace_fin = false;
 
   explicit Build(TrgEngine *e_)
       : e(e_), bb(*e_->bfs), B(bb.B), F(bb.F), m(e_->gmap), qp(qparams(e_)), s(e_->s_main),
-        S(e_->prm.sample_num), CS((e_->step3 || e_->debug_call_stride) ? LEVEL_STEP3_STRIDE : 1) {}
+        S(e_->prm.sample_num), CS((e_->step3 || e_->debug_call_stride) ? LEVEL_STEP3_STRIDE : 1),
+        tail_split(e_->tail_overlap && !e_->step3 && !e_->keep_preclean) {}
+  // Whichever way a build ends, nothing of its tail stays in flight: a return between the hand-over to the
+  // second stream and the last synchronisation (an error, a fallback to the host replay, which reuses these
+  // buffers) leaves both streams drained.
+  ~Build() {
+    if (!edge_stream_busy) return;
+    (void)hipStreamSynchronize(e->s_edge);
+    (void)hipStreamSynchronize(s);
+  }
+  Build(const Build &) = delete;
+  Build &operator=(const Build &) = delete;
   TrgStatus fallback(const std::string &why) {
     e->bfs_fallback_reason = why;
     return TRG_ERR_CAPACITY;
@@ -228,6 +249,7 @@ struct Build {
   void lap(const char *what) {
     if (!trace_fin) return;
     (void)hipStreamSynchronize(s);
+    if (edge_stream_busy) (void)hipStreamSynchronize(e->s_edge);
     fprintf(stderr, "[trg finalize] %-28s %8.3f ms\n", what, ms_since(t_fin));
   }
   void mark(const char *what) {  // host time only: the stream keeps running
@@ -255,6 +277,7 @@ struct Build {
   TrgStatus resolve_uncertain(int n_unc, void *status_base, size_t stride, int list_parity, int ctr_index);
   TrgStatus grow_call_log(size_t need);
   TrgStatus launch_deferred(long long c1, bool in_loop);
+  void launch_creating_edge_weights(hipStream_t st);
 };
 
 TrgStatus Build::read_ctrs() {
@@ -937,7 +960,7 @@ TrgStatus Build::grow_call_log(size_t need) {
 TrgStatus Build::level_loop() {
   TrgStatus st;
   for (Event *ev : {&ev0, &ev1, &evn0, &evn1}) HIPCHK(e, ev->create());
-  for (Event *ev : {&ev_order, &ev_nodes}) HIPCHK(e, ev->create(false));
+  for (Event *ev : {&ev_order, &ev_nodes, &ev_structure, &ev_weights}) HIPCHK(e, ev->create(false));
   bool have_expand = false;  // this level's expansion was issued by the previous iteration
   // Kernel timing inside the level loop is SAMPLED: an event pair around a kernel costs ~12 us of
   // stream time.  Every TIMED_EVERY-th level is timed and the totals are scaled by
@@ -1067,6 +1090,16 @@ TrgStatus Build::level_loop() {
   return TRG_OK;
 }
 
+// The covariances of the edges that created the nodes (the level loop only decided whether those edges hold) and
+// the weights from them (same stream: ordered), all nodes in ONE launch each, after the loop, where every level
+// is final.  (Handed over level by level beside the loop, like the call batches, the same work comes as ~370
+// small launches that take vector issue from the level kernels: DESIGN.md section 4.)  k_node_weights touches
+// only the calls that created a node: their call_w, and call_status outside EDGE_STATUS_MASK.
+void Build::launch_creating_edge_weights(hipStream_t st) {
+  launch_node_cov(m.view, qp, B, 1, V, st);
+  launch_node_weights(B, V, st);
+}
+
 // ---- phase 4: the rest of the deferred wireEdge evaluations (round 1), then round 2 ----------------------
 TrgStatus Build::finish_deferred() {
   TrgStatus st;
@@ -1077,13 +1110,7 @@ TrgStatus Build::finish_deferred() {
     HIPCHK(e, hipMemsetAsync(F.ht_key, 0xFF, (size_t)fht * sizeof(unsigned long long), s));
     HIPCHK(e, hipMemsetAsync(F.ht_seq, 0x7F, (size_t)fht * sizeof(int), s));
   }
-  // The covariances of the edges that created the nodes (the level loop only decided whether those edges hold):
-  // all nodes in ONE launch, here, where every level is final and the main stream is idle while the deferred
-  // stream finishes its last batches.  (Handed over level by level beside the loop, like the call batches, the
-  // same work comes as ~370 small launches that take vector issue from the level kernels: DESIGN.md section 4.)
-  launch_node_cov(m.view, qp, B, 1, V, s);
-  launch_node_weights(B, V, s);  // weights of the edges to the nodes the BFS created, from those covariances (same
-                                 // stream: ordered behind k_node_cov); touches only the calls that created a node
+  if (!tail_split) launch_creating_edge_weights(s);  // (tail_split: beside the copies of clean_and_fetch)
   if (e->step3) {
     // step 3 (trg.cpp:429-444): the node tree rebuilt on the device, every valid node's neighbour calls into
     // the entries behind its creating call; the deferred pipeline below takes them like all other calls
@@ -1108,6 +1135,9 @@ TrgStatus Build::finish_deferred() {
   if (V > 0)
     HIPCHK(e, hipMemcpyAsync(bb.map_order.p, map_order.data(), (size_t)V * sizeof(int), hipMemcpyHostToDevice,
                              e->s_edge));
+  // ... and behind it the sums of the expansion's statistics (their inputs are final since the loop ended): a
+  // small kernel beside the evaluations instead of one at the very end of the build
+  launch_bfs_stats(B, V, B.stats64 + S64_DRAWS, e->s_edge);  // draws, samples, disc hits, speculative-edge hits, candidates, parent-edge hits
   HIPCHK(e, hipEventRecord(ev_order.ev, e->s_edge));
   HIPCHK(e, hipStreamSynchronize(s_def));
   if (s_def != s) HIPCHK(e, hipStreamSynchronize(s));  // (the evaluations after the loop run in the main stream)
@@ -1215,15 +1245,23 @@ TrgStatus Build::assemble_csr() {
 // the cleaned graph to the host ----
 TrgStatus Build::clean_and_fetch() {
   TrgStatus st;
-  // (the order went to the device while the deferred evaluations ran)
+  // (the order went to the device while the deferred evaluations ran, the statistics were summed behind it)
   HIPCHK(e, hipStreamWaitEvent(s, ev_order.ev, 0));
+  // tail_split: the structure only.  Nothing in it depends on a weight: the kernels up to here and these read
+  // call_status & EDGE_STATUS_MASK, call_n1 / _n2, call_dist and the node arrays.
   launch_fin_clean(F, B, (int *)bb.map_order.p, V, (int *)bb.keep_flag.p, (int *)bb.keep_pos.p,
                    (int *)bb.new2old.p, (int *)bb.old2new.p, (int *)bb.deg_new.p, (int *)bb.rowptr_new.p,
-                   (int *)bb.scan_tmp.p, (int *)bb.col2.p, (float *)bb.w2.p, (float *)bb.dist2.p,
-                   (float *)bb.xyz2.p, (int *)bb.state2.p, s);
+                   (int *)bb.scan_tmp.p, (int *)bb.col2.p, tail_split ? nullptr : (float *)bb.w2.p,
+                   (float *)bb.dist2.p, (float *)bb.xyz2.p, (int *)bb.state2.p, s);
+  // The second stream starts behind the structure kernels, never beside them (k_node_weights rewrites words of
+  // call_status / call_w that k_fin_* read).
+  if (tail_split) HIPCHK(e, hipEventRecord(ev_structure.ev, s));
   int *h_tot = bb.h_ctrs + H_CLEAN_TOTALS;
   HIPCHK(e, hipMemcpyAsync(h_tot, (int *)bb.keep_pos.p + V, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipMemcpyAsync(h_tot + 1, F.rowptr + V, sizeof(int), hipMemcpyDeviceToHost, s));
+  // the statistics, for report_stats (S64_DEF_KEPT is final since round 2)
+  HIPCHK(e, hipMemcpyAsync(bb.h_ctrs + H_STATS64, B.stats64, S64_PHASES * sizeof(unsigned long long),
+                           hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   const int Vn = h_tot[0], E = h_tot[1];
   lap("clean kernels");
@@ -1240,15 +1278,29 @@ TrgStatus Build::clean_and_fetch() {
     g.col.resize(En);
     g.w.resize(En);
     g.dist.resize(En);
+    // node arrays first: the host rebuilds its node state from them while the edge arrays travel
     HIPCHK(e, hipMemcpyAsync(g.xyz.data(), bb.xyz2.p, 3 * (size_t)Vn * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (tail_split && En) {
+      // The compute units have nothing to do during these copies: the covariances, the SVDs and the weights of
+      // the cleaned graph (a pass over its rows that writes w2 alone) run now, on the second stream, and w2
+      // goes last.  (Enqueued behind the first copy so that the copy is under way when the chip fills up.)
+      hipStream_t s2 = e->s_edge;
+      HIPCHK(e, hipStreamWaitEvent(s2, ev_structure.ev, 0));
+      edge_stream_busy = true;
+      launch_creating_edge_weights(s2);
+      launch_fin_clean_weights(F, B, V, (int *)bb.keep_pos.p, (int *)bb.new2old.p, (int *)bb.rowptr_new.p,
+                               (float *)bb.w2.p, s2);
+      HIPCHK(e, hipEventRecord(ev_weights.ev, s2));
+    }
     HIPCHK(e, hipMemcpyAsync(g.state.data(), bb.state2.p, (size_t)Vn * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipMemcpyAsync(g.cid.data(), bb.new2old.p, (size_t)Vn * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipEventRecord(ev_nodes.ev, s));
     HIPCHK(e, hipMemcpyAsync(g.rowptr.data(), bb.rowptr_new.p, ((size_t)Vn + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
     if (En) {
       HIPCHK(e, hipMemcpyAsync(g.col.data(), bb.col2.p, (size_t)En * sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(e, hipMemcpyAsync(g.w.data(), bb.w2.p, (size_t)En * sizeof(float), hipMemcpyDeviceToHost, s));
       HIPCHK(e, hipMemcpyAsync(g.dist.data(), bb.dist2.p, (size_t)En * sizeof(float), hipMemcpyDeviceToHost, s));
+      if (tail_split) HIPCHK(e, hipStreamWaitEvent(s, ev_weights.ev, 0));
+      HIPCHK(e, hipMemcpyAsync(g.w.data(), bb.w2.p, (size_t)En * sizeof(float), hipMemcpyDeviceToHost, s));
     }
     mark("copies enqueued");
     // while the copies run: global_graph.nodes = new_nodes (trg.cpp:526) -- the copy takes over the
@@ -1275,7 +1327,8 @@ TrgStatus Build::clean_and_fetch() {
       e->nstate[k] = g.state[k];
     }
     mark("host node state");
-    if ((st = read_ctrs()) != TRG_OK) return st;
+    if ((st = read_ctrs()) != TRG_OK) return st;  // (the main stream waited for the second one: both are drained)
+    edge_stream_busy = false;
     if (bb.h_ctrs[BFS_CTR_ERR]) return fallback(err_text(bb.h_ctrs[BFS_CTR_ERR]));
     if (g.rowptr[Vn] != En) return e->fail(TRG_ERR_DEVICE, "cleanGraph edge count mismatch");
   } else {
@@ -1307,10 +1360,9 @@ TrgStatus Build::clean_and_fetch() {
 
 // ---- phase 7: statistics and instrumentation reports -------------------------------------------------
 TrgStatus Build::report_stats() {
-  unsigned long long s64[16] = {0};
-  launch_bfs_stats(B, V, B.stats64 + S64_DRAWS, s);  // draws, samples, disc hits, speculative-edge hits, candidates, parent-edge hits
-  HIPCHK(e, hipStreamSynchronize(s));  // (s does not synchronise with the plain copy below)
-  HIPCHK(e, hipMemcpy(s64, B.stats64, sizeof(s64), hipMemcpyDeviceToHost));
+  // (summed in finish_deferred, fetched into pinned memory in front of clean_and_fetch's first synchronisation)
+  unsigned long long s64[S64_PHASES];
+  memcpy(s64, bb.h_ctrs + H_STATS64, sizeof(s64));
   if (getenv("TRG_DEBUG_STATS")) {  // the reduction against a host sum of the same arrays
     std::vector<int> hs(V), hx(4 * (size_t)V);
     HIPCHK(e, hipMemcpy(hs.data(), B.nstate, (size_t)V * sizeof(int), hipMemcpyDeviceToHost));

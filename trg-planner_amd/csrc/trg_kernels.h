@@ -283,7 +283,9 @@ struct FinDev {
   int *call_slot;
   int *deg, *fill, *rowptr;
   int *col, *seq;
-  float *w, *dist;
+  float *w, *dist;  // w: call_w as k_fin_scatter found it.  In a build that computes the creating edges' weights
+                    // after the scatter (Build::tail_split) those entries are stale and w has no reader: the
+                    // cleaned graph takes its weights from call_w (launch_fin_clean_weights)
 };
 
 void launch_bfs_insert_nodes(const BfsDev &B, int first, int count, hipStream_t s);
@@ -338,6 +340,10 @@ void launch_fin_clean(const FinDev &F, const BfsDev &B, const int *map_order, in
                       int *keep_pos, int *new2old, int *old2new, int *deg_new, int *rowptr_new,
                       int *scan_tmp, int *col, float *w, float *dist, float *xyz, int *state,
                       hipStream_t s);
+// the weights launch_fin_clean left out (w == nullptr there): w[...] = call_w of the call that made the entry, for
+// the rows launch_fin_clean laid out; after launch_node_weights
+void launch_fin_clean_weights(const FinDev &F, const BfsDev &B, int V, const int *keep_pos, const int *new2old,
+                              const int *rowptr_new, float *w, hipStream_t s);
 
 // ---- tile-boundary stitch of the tiled build (trg_stitch.inc) ----------------------------------------
 struct StitchRec {  // a boundary node: local id and position (16 bytes; layout of TrgBoundaryRec)
