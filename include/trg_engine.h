@@ -324,13 +324,15 @@ const char *trg_engine_fallback_reason(const TrgEngine *e);
  *   hops[v]    hop count of that key, -1 if unreachable
  *   parent[v]  smallest u with an edge u->v whose extension of u's key is v's key; -1 for the source and
  *              for unreachable nodes
+ * A fold may saturate: a node whose least cost is +inf is reached, with hops >= 0 and a parent, and is
+ * expanded like any other; unreachable is hops == -1, not cost == +inf.
  * Source: source_id >= 0, or, with source_id == -1, the node planSafePath starts from for source_xy.
  * The output arrays are host memory of num_nodes entries; any of them may be NULL.
  * TRG_ERR_NO_GRAPH on an empty graph; TRG_ERR_INVALID_ARG for a source out of range or when an edge cost
  * is negative or not finite; TRG_ERR_DEVICE if the relaxation does not converge. */
 typedef struct TrgFieldInfo {
   int32_t source;     /* the resolved source node */
-  int32_t reached;    /* nodes with a finite key */
+  int32_t reached;    /* nodes with a key (hops >= 0), a cost of +inf included */
   int32_t rounds;     /* relaxation rounds that did work */
   int32_t host_syncs; /* times the host waited for the device */
   double ms_device;   /* hipEvent time of the solve */

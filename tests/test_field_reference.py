@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import field_ref
+from field_graphs import random_graph as _random_graph
 
 F32 = np.float32
 INVALID = -1
@@ -43,43 +44,6 @@ def _py_field(V, rowptr, col, w, dist, state, sf, src):
             parent[v] = u
     cost = np.array([np.inf if c is None else c for c in cost], np.float32)
     return cost, np.array(hops, np.int32), np.array(parent, np.int32)
-
-
-def _random_graph(rng, V):
-    """Edges: a symmetric core, directed-only extras, duplicates with other weights, zero-dist edges and
-    sub-ulp costs; two components (ids >= V // 2 + 3 only link among themselves); a few Invalid nodes."""
-    edges = []
-    half = V // 2 + 3
-    for _ in range(3 * V):
-        a = int(rng.integers(0, half))
-        b = int(rng.integers(0, half))
-        if a == b:
-            continue
-        w = F32(rng.choice([0.0, rng.uniform(0.1, 1.0)]))
-        d = F32(rng.choice([0.0, 1e-9, rng.uniform(0.3, 0.6), rng.uniform(100.0, 200.0)], p=[0.1, 0.1, 0.6, 0.2]))
-        edges.append((a, b, w, d))
-        r = rng.uniform()
-        if r < 0.6:
-            edges.append((b, a, w, d))  # symmetric
-        elif r < 0.8:
-            edges.append((a, b, F32(rng.uniform(0.1, 1.0)), d))  # duplicate, another weight
-    for _ in range(V):
-        a = int(rng.integers(half, V))
-        b = int(rng.integers(half, V))
-        if a != b:
-            edges.append((a, b, F32(rng.uniform(0.1, 1.0)), F32(rng.uniform(0.3, 0.6))))
-    state = np.zeros(V, np.int32)
-    state[rng.choice(V, size=max(1, V // 8), replace=False)] = INVALID
-    state[rng.choice(V, size=max(1, V // 8), replace=False)] = 1  # Frontier: an ordinary node here
-    order = sorted(range(len(edges)), key=lambda i: edges[i][0])  # rows in push order
-    rowptr = np.zeros(V + 1, np.int32)
-    for i in order:
-        rowptr[edges[i][0] + 1] += 1
-    rowptr = np.cumsum(rowptr).astype(np.int32)
-    col = np.array([edges[i][1] for i in order], np.int32)
-    w = np.array([edges[i][2] for i in order], np.float32)
-    d = np.array([edges[i][3] for i in order], np.float32)
-    return rowptr, col, w, d, state
 
 
 @pytest.fixture(scope="module")

@@ -60,10 +60,15 @@ __device__ __forceinline__ int wave_reserve(bool pred, int *tail) {
   return base + __popcll(m & ((1ull << lane_id()) - 1ull));
 }
 
-// the next bucket's threshold above the least live far cost (strictly above it, whatever delta is)
-__device__ __forceinline__ float next_threshold(float fmin, float delta) {
+__device__ __forceinline__ unsigned key_cost_bits(unsigned long long k) { return (unsigned)(k >> 32); }
+
+// The next bucket's threshold above the least live far cost (strictly above it, whatever delta is).  Thresholds
+// are kept and compared as bits: costs are >= +0, so their bits order as they do, and the word after a least
+// cost of +inf (no float: a NaN pattern) is still a threshold that +inf lies below.
+__device__ __forceinline__ unsigned next_threshold(unsigned fminb, float delta) {
+  const float fmin = __uint_as_float(fminb);
   const float t = fmin + delta;
-  return t > fmin ? t : __uint_as_float(__float_as_uint(fmin) + 1u);
+  return t > fmin ? __float_as_uint(t) : fminb + 1u;
 }
 
 __global__ __launch_bounds__(THREADS) void k_field_edge_cost(const int *__restrict__ col, const float *__restrict__ w,
@@ -120,7 +125,7 @@ __global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, int src, flo
     s.work = 1;
     s.rounds = 0;
     s.overflow = 0;
-    s.thr = delta;
+    s.thr = __float_as_uint(delta);
     s.delta = delta;
     s.phase = 1;
     s.far_sel = 0;
@@ -131,7 +136,7 @@ __global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, int src, flo
 __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, int stamp) {
   const int n = min(F.ctrl->c.n[par], F.V);  // (past V only after an overflow, which the host then reports)
   if (n == 0) return;
-  const float thr = F.ctrl->s.thr;
+  const unsigned thr = F.ctrl->s.thr;
   const unsigned phase = F.ctrl->s.phase;
   const int fs = F.ctrl->s.far_sel;
   const int V = F.V;
@@ -169,7 +174,7 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
           if (tight && nk < F.key[v]) {  // plain load first: the atomic only on an improvement
             const unsigned long long old = atomicMin(&F.key[v], nk);
             if (nk < old) {
-              if (key_cost(nk) < thr)
+              if (key_cost_bits(nk) < thr)
                 to_near = atomicExch(&F.stamp_near[v], stamp) != stamp;
               else
                 to_far = atomicExch(&F.stamp_far[v], phase) != phase;
@@ -197,14 +202,14 @@ __global__ __launch_bounds__(THREADS) void k_field_far_min(FieldDev F, int par) 
   if (F.ctrl->c.n[par ^ 1] != 0) return;
   const int fs = F.ctrl->s.far_sel;
   const int nf = min(F.ctrl->c.nfar[fs], F.V);
-  const float thr = F.ctrl->s.thr;
+  const unsigned thr = F.ctrl->s.thr;
   const int *__restrict__ far = F.far[fs];
   unsigned best = ~0u;
   const int n_iter = (nf + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
   for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
     if (i < nf) {
-      const float c = key_cost(F.key[far[i]]);
-      if (c >= thr) best = min(best, __float_as_uint(c));  // (costs are >= +0: their bits order as they do)
+      const unsigned c = key_cost_bits(F.key[far[i]]);
+      if (c >= thr) best = min(best, c);
     }
   }
 #pragma unroll
@@ -220,9 +225,8 @@ __global__ __launch_bounds__(THREADS) void k_field_far_split(FieldDev F, int par
   if (fminb == ~0u) return;
   const int fs = F.ctrl->s.far_sel;
   const int nf = min(F.ctrl->c.nfar[fs], F.V);
-  const float thr = F.ctrl->s.thr;
-  const float fmin = __uint_as_float(fminb);
-  const float thr_new = next_threshold(fmin, F.ctrl->s.delta);
+  const unsigned thr = F.ctrl->s.thr;
+  const unsigned thr_new = next_threshold(fminb, F.ctrl->s.delta);
   const unsigned phase_new = F.ctrl->s.phase + 1u;
   const int V = F.V;
   const int *__restrict__ far = F.far[fs];
@@ -234,9 +238,9 @@ __global__ __launch_bounds__(THREADS) void k_field_far_split(FieldDev F, int par
     int v = 0;
     if (i < nf) {
       v = far[i];
-      const float c = key_cost(F.key[v]);
+      const unsigned c = key_cost_bits(F.key[v]);
       if (c >= thr) {
-        to_near = c < thr_new || c == fmin;  // (c == fmin: a least cost of +inf still makes progress)
+        to_near = c < thr_new;  // (thr_new > fmin: the least live cost always makes progress, +inf too)
         to_far = !to_near;
       }
     }
@@ -265,7 +269,7 @@ __global__ void k_field_round_end(FieldDev F, int par) {
     c.nfar[s.far_sel] = 0;
     s.far_sel ^= 1;
     s.phase += 1u;
-    s.thr = next_threshold(__uint_as_float(c.fmin), s.delta);
+    s.thr = next_threshold(c.fmin, s.delta);
     c.fmin = ~0u;
   } else if (c.n[par ^ 1] == 0) {
     c.nfar[s.far_sel] = 0;  // converged: what is left in the far pile is stale

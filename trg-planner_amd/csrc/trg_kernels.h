@@ -398,7 +398,7 @@ struct alignas(128) FieldState {
   int work;        // near-queue entries after the last round: 0 = converged
   int rounds;      // rounds that did work
   int overflow;
-  float thr;       // near bucket: cost < thr
+  unsigned thr;    // near bucket: cost bits < thr (bits, so that the bucket above a least cost of +inf exists)
   float delta;     // bucket width
   unsigned phase;  // far-pile stamp of the current bucket
   int far_sel;

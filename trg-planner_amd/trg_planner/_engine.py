@@ -397,8 +397,9 @@ class Engine:
     def cost_field(self, source_xy=None, source_id=-1):
         """Least risk cost from one node to every node of the global graph, on the GPU (DESIGN.md
         section 2, "Cost field").  The source is node `source_id`, or, with source_id == -1, the node
-        planSafePath starts from for `source_xy`.  -> (cost float32 (+inf: unreachable), hops int32 (-1),
-        parent int32 (-1 for the source and unreachable nodes), TrgFieldInfo)."""
+        planSafePath starts from for `source_xy`.  -> (cost float32 (+inf: unreachable, or a fold that
+        saturated), hops int32 (-1: unreachable), parent int32 (-1 for the source and unreachable nodes),
+        TrgFieldInfo)."""
         if source_id == -1 and source_xy is None:
             raise ValueError("cost_field needs source_xy or source_id")
         xy = None if source_xy is None else np.ascontiguousarray(source_xy, dtype=np.float32).reshape(2)
