@@ -340,6 +340,35 @@ typedef struct TrgFieldInfo {
 } TrgFieldInfo;
 TrgStatus trg_engine_cost_field(TrgEngine *e, int32_t source_id, const float source_xy[2],
                                 float *cost, int32_t *hops, int32_t *parent, TrgFieldInfo *info);
+/* m fields in ONE solve (trg_engine_cost_field is its m == 1 call): m fields of a graph are one field of the
+ * disjoint union of m copies of it, so they share the relaxation rounds, the bucket threshold and the host
+ * waits instead of repeating them.  Field k follows the semantics above, from source_ids[k], or, where
+ * source_ids is NULL or source_ids[k] == -1, from the node planSafePath starts from for source_xy[2k, 2k+1].
+ * Duplicate sources are allowed and give identical fields.
+ *   cost, hops, parent     m x num_nodes each (row k = field k), host memory; any may be NULL
+ *   targets, n_targets     optional node ids (duplicates allowed) at which the fields are read on the device:
+ *   cost_at, hops_at       m x n_targets each, [k * n_targets + j] = field k at targets[j]; any may be NULL.
+ *                          With only these requested, nothing of num_nodes entries is copied to the host.
+ *   sources_out            m resolved sources, may be NULL
+ *   reached_out            m counts of nodes with a key, may be NULL
+ *   info                   source = field 0's, reached = the sum over the fields, rounds / host_syncs / ms_* of
+ *                          the whole solve; may be NULL
+ * With every output NULL but sources_out the call resolves the sources and solves nothing.
+ * TRG_ERR_INVALID_ARG (the message names the offending index where there is one) for m < 1 or
+ * m > TRG_FIELD_BATCH_MAX, a source or target out of range, n_targets < 0, a missing source_xy where one is
+ * needed, a negative or non-finite edge cost; TRG_ERR_CAPACITY when the m * num_nodes items do not fit a 32-bit
+ * index or device memory runs out; TRG_ERR_NO_GRAPH and TRG_ERR_DEVICE as for the single call. */
+#define TRG_FIELD_BATCH_MAX 64
+TrgStatus trg_engine_cost_field_batch(
+    TrgEngine *e, int32_t m,
+    const int32_t *source_ids,   /* m entries, or NULL: all from source_xy            */
+    const float *source_xy,      /* m x 2, used where source_ids is NULL or [k] == -1 */
+    float *cost, int32_t *hops, int32_t *parent,   /* m x num_nodes each, any may be NULL */
+    const int32_t *targets, int32_t n_targets,     /* optional                        */
+    float *cost_at, int32_t *hops_at,              /* m x n_targets, any may be NULL  */
+    int32_t *sources_out,        /* m resolved sources, may be NULL                   */
+    int32_t *reached_out,        /* m, may be NULL                                    */
+    TrgFieldInfo *info);
 
 /* ---- instrumentation ------------------------------------------------------------------------- */
 TrgStatus trg_engine_get_stats(const TrgEngine *e, TrgStats *out);

@@ -1,6 +1,7 @@
 // Part of trg_engine.cpp (included at file scope): the cost field of the global graph -- the least (cost, hops)
-// key from one node to every node, on the device (kernels: trg_field.hip; an extension, the reference has no
-// such call) -- and its C ABI entry.
+// key from one node to every node, on the device, for up to TRG_FIELD_BATCH_MAX sources in one solve (kernels:
+// trg_field.hip; an extension, the reference has no such call) -- and its C ABI entries.  One solver: the
+// single-source entry is its m == 1 call.
 
 namespace {
 
@@ -9,7 +10,9 @@ constexpr int FIELD_BATCH = 32;
 
 // device buffers of the cost field, owned by the engine
 struct FieldBufs {
-  DevArr ec, stats, key, q0, q1, far0, far1, stamp_near, stamp_far, parent, cost, hops, ctrl;
+  DevArr ec, stats, ctrl;
+  DevArr key, q0, q1, far0, far1, stamp_near, stamp_far, parent, cost, hops;  // per item: m x V entries
+  DevArr targets, cost_at, hops_at;                                           // n_targets, m x n_targets
   DevArr up_rowptr, up_col, up_w, up_dist, up_state;  // csr_global + nstate when the device build's CSR is stale
   uint64_t up_version = 0;   // graph_version of the upload (0: none)
   uint64_t ec_version = 0;   // graph_version of the edge costs (0: none)
@@ -19,7 +22,7 @@ struct FieldBufs {
   bool bad_cost = false;
   Pinned<FieldState> h_state;
   Pinned<FieldEdgeStats> h_stats;
-  Pinned<int> h_reached;
+  Pinned<int> h_reached;  // per field
   Event t0, t1;
 };
 
@@ -32,23 +35,67 @@ void field_release(TrgEngine *e) {
   e->field.reset();
 }
 
-TrgStatus field_solve(TrgEngine *e, int32_t source_id, const float *source_xy, float *cost, int32_t *hops,
-                      int32_t *parent, TrgFieldInfo *info) {
+static_assert(FIELD_MAX_SOURCES == TRG_FIELD_BATCH_MAX, "the kernels' and the header's batch limit differ");
+
+struct FieldRequest {
+  int32_t m;
+  const int32_t *source_ids;  // m, or nullptr: all from source_xy
+  const float *source_xy;     // m x 2
+  float *cost;                // m x V each, any may be nullptr
+  int32_t *hops, *parent;
+  const int32_t *targets;     // n_targets node ids
+  int32_t n_targets;
+  float *cost_at;             // m x n_targets each, any may be nullptr
+  int32_t *hops_at;
+  int32_t *sources_out, *reached_out;  // m
+  bool resolve_only;          // nothing but sources_out is wanted: no solve
+};
+
+TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) {
   const auto t_total = Clock::now();
   TrgStatus st = plan_prepare(e);  // graph present, CSR rows and node grid current
   if (st != TRG_OK) return st;
   const int V = (int)e->nx.size();
-  int src = source_id;
-  if (source_id == -1) {
-    if (!source_xy) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no source");
-    src = plan_nearest_node(e, source_xy[0], source_xy[1], e->plan_scratch.tied);  // planSafePath's start node
+  const int m = rq.m;
+  FieldSources sources{};
+  for (int k = 0; k < m; ++k) {
+    int src = rq.source_ids ? rq.source_ids[k] : -1;
+    if (src == -1) {
+      if (!rq.source_xy)
+        return e->fail(TRG_ERR_INVALID_ARG, m == 1 ? "cost field: no source"
+                                                   : "cost field: source " + std::to_string(k) + " needs source_xy");
+      // planSafePath's start node
+      src = plan_nearest_node(e, rq.source_xy[2 * k], rq.source_xy[2 * k + 1], e->plan_scratch.tied);
+    }
+    if (src < 0 || src >= V)
+      return e->fail(TRG_ERR_INVALID_ARG, m == 1 ? "cost field: source out of range"
+                                                 : "cost field: source " + std::to_string(k) + " out of range");
+    sources.id[k] = src;
   }
-  if (src < 0 || src >= V) return e->fail(TRG_ERR_INVALID_ARG, "cost field: source out of range");
+  if (rq.resolve_only) {
+    for (int k = 0; k < m; ++k) rq.sources_out[k] = sources.id[k];
+    info->source = sources.id[0];
+    info->ms_total = ms_since(t_total);
+    return TRG_OK;
+  }
+  const bool gather = rq.n_targets > 0 && (rq.cost_at || rq.hops_at);
+  if (rq.n_targets > 0 && !rq.targets) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no targets");
+  for (int j = 0; j < rq.n_targets; ++j)
+    if (rq.targets[j] < 0 || rq.targets[j] >= V)
+      return e->fail(TRG_ERR_INVALID_ARG, "cost field: target " + std::to_string(j) + " out of range");
+  // items are indexed in 32 bits (and the grid-stride loops step past the last one)
+  const long long N64 = (long long)m * V;
+  if (N64 > (long long)INT_MAX - (1 << 20))
+    return e->fail(TRG_ERR_CAPACITY, "cost field: " + std::to_string(m) + " fields of " + std::to_string(V) +
+                                         " nodes do not fit a 32-bit item index");
+  if (gather && (long long)m * rq.n_targets > (long long)INT_MAX - (1 << 20))
+    return e->fail(TRG_ERR_CAPACITY, "cost field: too many targets");
+  const int N = (int)N64;
   if (!e->field) e->field.reset(new FieldBufs());
   FieldBufs &fb = *e->field;
   HIPCHK(e, fb.h_state.ensure(1));
   HIPCHK(e, fb.h_stats.ensure(1));
-  HIPCHK(e, fb.h_reached.ensure(1));
+  HIPCHK(e, fb.h_reached.ensure(TRG_FIELD_BATCH_MAX));
   HIPCHK(e, fb.t0.create());
   HIPCHK(e, fb.t1.create());
   hipStream_t s = e->s_main;
@@ -110,18 +157,25 @@ TrgStatus field_solve(TrgEngine *e, int32_t source_id, const float *source_xy, f
   }
   if (fb.bad_cost) return e->fail(TRG_ERR_INVALID_ARG, "cost field: an edge cost is negative or not finite");
 
-  // work arrays
-  const size_t nV = (size_t)V + 4;
-  if ((st = ensure_bytes(e, fb.key, nV * sizeof(unsigned long long))) != TRG_OK) return st;
+  // work arrays, per item
+  const size_t nV = (size_t)N + 4;
+  const auto grow = [e](DevArr &a, size_t bytes) {  // an allocation that fails is a matter of capacity
+    if (ensure_bytes(e, a, bytes) == TRG_OK) return TRG_OK;
+    (void)hipGetLastError();
+    return e->fail(TRG_ERR_CAPACITY, "cost field: no device memory for " + std::to_string(bytes) + " bytes (" + e->err + ")");
+  };
+  if ((st = grow(fb.key, nV * sizeof(unsigned long long))) != TRG_OK) return st;
   for (DevArr *a : {&fb.q0, &fb.q1, &fb.far0, &fb.far1, &fb.stamp_near, &fb.stamp_far, &fb.parent, &fb.cost,
                     &fb.hops})
-    if ((st = ensure_bytes(e, *a, nV * sizeof(int))) != TRG_OK) return st;
+    if ((st = grow(*a, nV * sizeof(int))) != TRG_OK) return st;
   if ((st = ensure_bytes(e, fb.ctrl, sizeof(FieldCtrl))) != TRG_OK) return st;
   FieldDev F{};
   F.rowptr = d_rowptr;
   F.col = d_col;
   F.ec = (const float *)fb.ec.p;
   F.V = V;
+  F.m = m;
+  F.N = N;
   F.key = (unsigned long long *)fb.key.p;
   F.q[0] = (int *)fb.q0.p;
   F.q[1] = (int *)fb.q1.p;
@@ -135,11 +189,11 @@ TrgStatus field_solve(TrgEngine *e, int32_t source_id, const float *source_xy, f
   // near-far rounds, enqueued in batches; the bucket width is a fixed multiple of the mean edge cost.
   // Pass 1 finds the least costs, pass 2 the hops over the tight edges (trg_field.hip).
   const float delta = fb.mean_cost > 0.0 ? (float)(e->field_delta_scale * fb.mean_cost) : 0.0f;
-  const long long cap = 4LL * V + 64;
+  const long long cap = 4LL * N + 64;
   int rounds = 0;
   for (int pass = 0; pass < 2; ++pass) {
     F.tight = pass ? (const unsigned *)fb.cost.p : nullptr;
-    launch_field_init(F, src, delta, s);
+    launch_field_init(F, sources, delta, s);
     for (int round = 0;;) {
       for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s);
       HIPCHK(e, hipGetLastError());
@@ -153,24 +207,59 @@ TrgStatus field_solve(TrgEngine *e, int32_t source_id, const float *source_xy, f
     rounds += fb.h_state->rounds;
     if (pass == 0) launch_field_cost_bits(F, (unsigned *)fb.cost.p, s);
   }
-  launch_field_finish(F, (float *)fb.cost.p, (int *)fb.hops.p, s);
+  launch_field_finish(F, (float *)fb.cost.p, (int *)fb.hops.p, rq.parent != nullptr, s);
+  if (gather) {
+    const size_t nt = (size_t)rq.n_targets, nat = (size_t)m * nt;
+    if ((st = grow(fb.targets, nt * sizeof(int))) != TRG_OK) return st;
+    if ((st = grow(fb.cost_at, nat * sizeof(float))) != TRG_OK) return st;
+    if ((st = grow(fb.hops_at, nat * sizeof(int))) != TRG_OK) return st;
+    HIPCHK(e, hipMemcpyAsync(fb.targets.p, rq.targets, nt * sizeof(int), hipMemcpyHostToDevice, s));
+    launch_field_gather(F, (const int *)fb.targets.p, rq.n_targets, rq.cost_at ? (float *)fb.cost_at.p : nullptr,
+                        rq.hops_at ? (int *)fb.hops_at.p : nullptr, s);
+  }
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
-  HIPCHK(e, hipMemcpyAsync(fb.h_reached, &F.ctrl->c.reached, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (cost) HIPCHK(e, hipMemcpyAsync(cost, fb.cost.p, (size_t)V * sizeof(float), hipMemcpyDeviceToHost, s));
-  if (hops) HIPCHK(e, hipMemcpyAsync(hops, fb.hops.p, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, s));
-  if (parent) HIPCHK(e, hipMemcpyAsync(parent, fb.parent.p, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipMemcpyAsync(fb.h_reached, F.ctrl->reached, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
+  // only what was asked for comes back
+  const size_t nN = (size_t)N;
+  if (rq.cost) HIPCHK(e, hipMemcpyAsync(rq.cost, fb.cost.p, nN * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (rq.hops) HIPCHK(e, hipMemcpyAsync(rq.hops, fb.hops.p, nN * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (rq.parent) HIPCHK(e, hipMemcpyAsync(rq.parent, fb.parent.p, nN * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (gather) {
+    const size_t nat = (size_t)m * rq.n_targets;
+    if (rq.cost_at) HIPCHK(e, hipMemcpyAsync(rq.cost_at, fb.cost_at.p, nat * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (rq.hops_at) HIPCHK(e, hipMemcpyAsync(rq.hops_at, fb.hops_at.p, nat * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
   HIPCHK(e, hipStreamSynchronize(s));
   syncs++;
   float ms_dev = 0.0f;
   HIPCHK(e, hipEventElapsedTime(&ms_dev, fb.t0, fb.t1));
-  info->source = src;
-  info->reached = *fb.h_reached;
+  long long reached = 0;
+  for (int k = 0; k < m; ++k) {
+    reached += fb.h_reached[k];
+    if (rq.sources_out) rq.sources_out[k] = sources.id[k];
+    if (rq.reached_out) rq.reached_out[k] = fb.h_reached[k];
+  }
+  info->source = sources.id[0];
+  info->reached = (int32_t)reached;
   info->rounds = rounds;
   info->host_syncs = syncs;
   info->ms_device = ms_dev;
   info->ms_total = ms_since(t_total);
   return TRG_OK;
+}
+
+// the entries' common guard
+TrgStatus field_guarded(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) {
+  try {
+    return field_solve(e, rq, info);
+  } catch (const std::bad_alloc &) {
+    return e->fail(TRG_ERR_CAPACITY, "cost field: out of host memory");
+  } catch (const std::exception &x) {
+    return e->fail(TRG_ERR_DEVICE, std::string("cost field: ") + x.what());
+  } catch (...) {
+    return e->fail(TRG_ERR_DEVICE, "cost field: unknown exception");
+  }
 }
 
 }  // namespace
@@ -185,15 +274,39 @@ TrgStatus trg_engine_cost_field(TrgEngine *e, int32_t source_id, const float sou
   *info = TrgFieldInfo{};
   info->source = -1;
   if (source_id < -1) return e->fail(TRG_ERR_INVALID_ARG, "cost field: source out of range");
-  try {
-    return field_solve(e, source_id, source_xy, cost, hops, parent, info);
-  } catch (const std::bad_alloc &) {
-    return e->fail(TRG_ERR_CAPACITY, "cost field: out of host memory");
-  } catch (const std::exception &x) {
-    return e->fail(TRG_ERR_DEVICE, std::string("cost field: ") + x.what());
-  } catch (...) {
-    return e->fail(TRG_ERR_DEVICE, "cost field: unknown exception");
-  }
+  FieldRequest rq{};
+  rq.m = 1;
+  rq.source_ids = &source_id;
+  rq.source_xy = source_xy;
+  rq.cost = cost;
+  rq.hops = hops;
+  rq.parent = parent;
+  return field_guarded(e, rq, info);
+}
+
+TrgStatus trg_engine_cost_field_batch(TrgEngine *e, int32_t m, const int32_t *source_ids, const float *source_xy,
+                                      float *cost, int32_t *hops, int32_t *parent, const int32_t *targets,
+                                      int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *sources_out,
+                                      int32_t *reached_out, TrgFieldInfo *info) {
+  REQUIRE_DEVICE(e);
+  // every output NULL but sources_out: the caller wants the sources resolved, nothing solved
+  const bool resolve_only = sources_out && !cost && !hops && !parent && !cost_at && !hops_at && !reached_out && !info;
+  TrgFieldInfo local{};
+  if (!info) info = &local;
+  *info = TrgFieldInfo{};
+  info->source = -1;
+  if (m < 1 || m > TRG_FIELD_BATCH_MAX)
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field: a batch of " + std::to_string(m) + " fields (1.." +
+                                            std::to_string(TRG_FIELD_BATCH_MAX) + ")");
+  if (n_targets < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field: n_targets < 0");
+  if (!source_ids && !source_xy) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no sources");
+  if (source_ids)
+    for (int k = 0; k < m; ++k)
+      if (source_ids[k] < -1)
+        return e->fail(TRG_ERR_INVALID_ARG, "cost field: source " + std::to_string(k) + " out of range");
+  FieldRequest rq{m, source_ids, source_xy, cost, hops, parent, targets, n_targets, cost_at, hops_at, sources_out,
+                  reached_out, resolve_only};
+  return field_guarded(e, rq, info);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // trg_field.hip -- gfx950 kernels of the cost field: the least (cost, hops) key from one node to every node of
-// the global graph (an extension; the reference answers only single-pair queries, planSafePath trg.cpp:603-690).
+// the global graph (an extension; the reference answers only single-pair queries, planSafePath trg.cpp:603-690),
+// for m sources in one solve.
 //
 // Semantics ("Cost field"): an edge costs (safety_factor * w + 1) * dist, every operation
 // rounded to fp32 (the A* step of trg.cpp:674 on OptimizeNode's float g_); a walk's cost is the left fold
@@ -19,6 +20,14 @@
 // [least live far cost, + delta) from the far pile.  Pushes are deduplicated by per-round / per-bucket
 // stamps and reserved with one atomicAdd per wave (ballot + prefix).  No launch waits for another
 // workgroup: sizes are read from device memory, the host enqueues rounds in batches.
+//
+// Batches: m fields are one field of the disjoint union of m copies of the graph with m sources -- still one
+// least fixed point, so the same relaxation, with ONE threshold, phase, far-pile selector and round counter for
+// the union, reaches it.  A work item is (field k, node v) = k * V + v; queues, piles, stamps, keys and parents
+// are per item, the CSR and the edge costs are shared.  The relax loop decodes an item once (one 32-bit
+// division, MULTI only) and adds the field's first item to every column it reads; with m == 1 the template
+// drops both.  The other kernels either never look inside an item (far min, far split, cost bits) or take the
+// field from blockIdx.y.
 //
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"
@@ -104,25 +113,31 @@ __global__ __launch_bounds__(THREADS) void k_field_edge_cost(const int *__restri
   }
 }
 
-__global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, int src, float delta) {
+// grid.y = field
+__global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources S, float delta) {
   const int V = F.V;
+  const int f = blockIdx.y;
+  const int src = S.id[f];
+  const int fbase = f * V;
   for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
-    F.key[v] = v == src ? 0ull : FIELD_KEY_NONE;
-    F.parent[v] = INT_MAX;
-    F.stamp_near[v] = 0;
-    F.stamp_far[v] = 0u;
+    F.key[fbase + v] = v == src ? 0ull : FIELD_KEY_NONE;
+    F.parent[fbase + v] = INT_MAX;
+    F.stamp_near[fbase + v] = 0;
+    F.stamp_far[fbase + v] = 0u;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    F.q[0][0] = src;
+    F.q[0][f] = fbase + src;
+    F.ctrl->reached[f] = 0;
+  }
+  if (blockIdx.x == 0 && f == 0 && threadIdx.x == 0) {
     FieldCounters &c = F.ctrl->c;
-    c.n[0] = 1;
+    c.n[0] = F.m;
     c.n[1] = 0;
     c.nfar[0] = c.nfar[1] = 0;
     c.fmin = ~0u;
     c.overflow = 0;
-    c.reached = 0;
     FieldState &s = F.ctrl->s;
-    s.work = 1;
+    s.work = F.m;
     s.rounds = 0;
     s.overflow = 0;
     s.thr = __float_as_uint(delta);
@@ -132,14 +147,16 @@ __global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, int src, flo
   }
 }
 
-// Expand the near queue of this round: one 16-lane group per queued node, four per wave.
+// Expand the near queue of this round: one 16-lane group per queued item, four per wave.
+// MULTI: more than one field (an item is decoded into its field's first item and its node); else item == node.
+template <bool MULTI>
 __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, int stamp) {
-  const int n = min(F.ctrl->c.n[par], F.V);  // (past V only after an overflow, which the host then reports)
+  const int N = MULTI ? F.N : F.V;
+  const int n = min(F.ctrl->c.n[par], N);  // (past N only after an overflow, which the host then reports)
   if (n == 0) return;
   const unsigned thr = F.ctrl->s.thr;
   const unsigned phase = F.ctrl->s.phase;
   const int fs = F.ctrl->s.far_sel;
-  const int V = F.V;
   const int *__restrict__ q_cur = F.q[par];
   int *q_next = F.q[par ^ 1];
   int *far = F.far[fs];
@@ -154,9 +171,15 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
     const int item = base + gw;
     unsigned long long ku = 0;
     int k = 0, kend = 0;
+    int fbase = 0;  // the first item of the queued item's field
     if (item < n) {
-      const int u = q_cur[item];
-      ku = F.key[u];
+      const int iu = q_cur[item];
+      ku = F.key[iu];
+      int u = iu;
+      if constexpr (MULTI) {
+        fbase = (int)((unsigned)iu / (unsigned)F.V) * F.V;
+        u = iu - fbase;
+      }
       k = F.rowptr[u] + sub;
       kend = F.rowptr[u + 1];
     }
@@ -169,6 +192,7 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
         const float c = F.ec[k];
         if (__float_as_uint(c) != FIELD_EDGE_SKIP) {
           v = F.col[k];
+          if constexpr (MULTI) v += fbase;  // the target item: an edge never leaves its field
           const unsigned long long nk = key_extend(ku, c);
           const bool tight = !F.tight || (unsigned)(nk >> 32) == F.tight[v];  // (pass 2: tight edges only)
           if (tight && nk < F.key[v]) {  // plain load first: the atomic only on an improvement
@@ -184,24 +208,24 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
       }
       const int sn = wave_reserve(to_near, next_tail);
       if (to_near) {
-        if (sn < V) q_next[sn] = v;
+        if (sn < N) q_next[sn] = v;
         else atomicOr(&F.ctrl->c.overflow, 1);
       }
       const int sf = wave_reserve(to_far, far_tail);
       if (to_far) {
-        if (sf < V) far[sf] = v;
+        if (sf < N) far[sf] = v;
         else atomicOr(&F.ctrl->c.overflow, 1);
       }
     }
   }
 }
 
-// The least live cost of the far pile (live: not below the threshold; an entry below it was pushed near
-// and expanded since) -- only when this round's relaxation pushed nothing near.
+// The least live cost of the far pile, over all fields (live: not below the threshold; an entry below it was
+// pushed near and expanded since) -- only when this round's relaxation pushed nothing near in any field.
 __global__ __launch_bounds__(THREADS) void k_field_far_min(FieldDev F, int par) {
   if (F.ctrl->c.n[par ^ 1] != 0) return;
   const int fs = F.ctrl->s.far_sel;
-  const int nf = min(F.ctrl->c.nfar[fs], F.V);
+  const int nf = min(F.ctrl->c.nfar[fs], F.N);
   const unsigned thr = F.ctrl->s.thr;
   const int *__restrict__ far = F.far[fs];
   unsigned best = ~0u;
@@ -224,11 +248,11 @@ __global__ __launch_bounds__(THREADS) void k_field_far_split(FieldDev F, int par
   const unsigned fminb = F.ctrl->c.fmin;
   if (fminb == ~0u) return;
   const int fs = F.ctrl->s.far_sel;
-  const int nf = min(F.ctrl->c.nfar[fs], F.V);
+  const int nf = min(F.ctrl->c.nfar[fs], F.N);
   const unsigned thr = F.ctrl->s.thr;
   const unsigned thr_new = next_threshold(fminb, F.ctrl->s.delta);
   const unsigned phase_new = F.ctrl->s.phase + 1u;
-  const int V = F.V;
+  const int N = F.N;
   const int *__restrict__ far = F.far[fs];
   int *far_new = F.far[fs ^ 1];
   int *q_next = F.q[par ^ 1];
@@ -246,13 +270,13 @@ __global__ __launch_bounds__(THREADS) void k_field_far_split(FieldDev F, int par
     }
     const int sn = wave_reserve(to_near, &F.ctrl->c.n[par ^ 1]);
     if (to_near) {
-      if (sn < V) q_next[sn] = v;
+      if (sn < N) q_next[sn] = v;
       else atomicOr(&F.ctrl->c.overflow, 1);
     }
     const int sf = wave_reserve(to_far, &F.ctrl->c.nfar[fs ^ 1]);
     if (to_far) {
       F.stamp_far[v] = phase_new;
-      if (sf < V) far_new[sf] = v;
+      if (sf < N) far_new[sf] = v;
       else atomicOr(&F.ctrl->c.overflow, 1);
     }
   }
@@ -279,44 +303,60 @@ __global__ void k_field_round_end(FieldDev F, int par) {
   s.overflow = c.overflow;
 }
 
-// Parents: the smallest u with an edge u -> v whose extension of key[u] is key[v].
+// Parents: the smallest u with an edge u -> v whose extension of key[u] is key[v], in each field (grid.y).
 __global__ __launch_bounds__(THREADS) void k_field_parent(FieldDev F) {
   const int sub = threadIdx.x & (GROUP - 1);
   const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
   const int ng = gridDim.x * blockDim.x / GROUP;
+  const int fbase = blockIdx.y * F.V;
   for (int u = g0; u < F.V; u += ng) {
-    const unsigned long long ku = F.key[u];
+    const unsigned long long ku = F.key[fbase + u];
     if (ku == FIELD_KEY_NONE) continue;
     for (int k = F.rowptr[u] + sub, kend = F.rowptr[u + 1]; k < kend; k += GROUP) {
       const float c = F.ec[k];
       if (__float_as_uint(c) == FIELD_EDGE_SKIP) continue;
-      const int v = F.col[k];
+      const int v = fbase + F.col[k];
       if (key_extend(ku, c) == F.key[v]) atomicMin(&F.parent[v], u);
     }
   }
 }
 
+// grid.y = field: a wave's items are of one field, one atomicAdd per wave into its count
 __global__ __launch_bounds__(THREADS) void k_field_output(FieldDev F, float *cost, int *hops) {
   const int V = F.V;
+  const int fbase = blockIdx.y * V;
   const int n_iter = (V + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
   for (int it = 0, v = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, v += gridDim.x * blockDim.x) {
     bool reached = false;
     if (v < V) {
-      const unsigned long long k = F.key[v];
+      const unsigned long long k = F.key[fbase + v];
       reached = k != FIELD_KEY_NONE;
-      cost[v] = reached ? key_cost(k) : __builtin_huge_valf();
-      hops[v] = reached ? (int)(unsigned)k : -1;
-      if (F.parent[v] == INT_MAX) F.parent[v] = -1;
+      cost[fbase + v] = reached ? key_cost(k) : __builtin_huge_valf();
+      hops[fbase + v] = reached ? (int)(unsigned)k : -1;
+      if (F.parent[fbase + v] == INT_MAX) F.parent[fbase + v] = -1;
     }
     const unsigned long long m = ballot(reached);
-    if (lane_id() == 0 && m) atomicAdd(&F.ctrl->c.reached, __popcll(m));
+    if (lane_id() == 0 && m) atomicAdd(&F.ctrl->reached[blockIdx.y], __popcll(m));
   }
 }
 
 // pass 1 -> pass 2: the least costs as bits (unreached: ~0)
 __global__ __launch_bounds__(THREADS) void k_field_cost_bits(FieldDev F, unsigned *bits) {
-  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < F.V; v += gridDim.x * blockDim.x)
-    bits[v] = (unsigned)(F.key[v] >> 32);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < F.N; i += gridDim.x * blockDim.x)
+    bits[i] = (unsigned)(F.key[i] >> 32);
+}
+
+// The finished keys at the target nodes, in each field (grid.y).
+__global__ __launch_bounds__(THREADS) void k_field_gather(FieldDev F, const int *__restrict__ targets, int n_t,
+                                                          float *cost_at, int *hops_at) {
+  const int fbase = blockIdx.y * F.V;
+  const long long obase = (long long)blockIdx.y * n_t;
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n_t; j += gridDim.x * blockDim.x) {
+    const unsigned long long k = F.key[fbase + targets[j]];
+    const bool reached = k != FIELD_KEY_NONE;
+    if (cost_at) cost_at[obase + j] = reached ? key_cost(k) : __builtin_huge_valf();
+    if (hops_at) hops_at[obase + j] = reached ? (int)(unsigned)k : -1;
+  }
 }
 
 int field_blocks(long long items, int per_block) {
@@ -334,26 +374,38 @@ void launch_field_edge_cost(const int *col, const float *w, const float *dist, c
                      state, V, E, safety_factor, ec, st);
 }
 
-void launch_field_init(const FieldDev &F, int source, float delta, hipStream_t s) {
-  hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS)), dim3(THREADS), 0, s, F, source, delta);
+void launch_field_init(const FieldDev &F, const FieldSources &sources, float delta, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, sources, delta);
 }
 
 void launch_field_round(const FieldDev &F, int round, hipStream_t s) {
   const int par = round & 1;
-  hipLaunchKernelGGL(k_field_relax, dim3(field_blocks((long long)F.V * GROUP, THREADS)), dim3(THREADS), 0, s, F,
-                     par, round + 1);
-  hipLaunchKernelGGL(k_field_far_min, dim3(field_blocks(F.V, THREADS)), dim3(THREADS), 0, s, F, par);
-  hipLaunchKernelGGL(k_field_far_split, dim3(field_blocks(F.V, THREADS)), dim3(THREADS), 0, s, F, par);
+  const dim3 relax_grid(field_blocks((long long)F.N * GROUP, THREADS));
+  if (F.m == 1)
+    hipLaunchKernelGGL(k_field_relax<false>, relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+  else
+    hipLaunchKernelGGL(k_field_relax<true>, relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+  hipLaunchKernelGGL(k_field_far_min, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
+  hipLaunchKernelGGL(k_field_far_split, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
   hipLaunchKernelGGL(k_field_round_end, dim3(1), dim3(64), 0, s, F, par);
 }
 
 void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s) {
-  hipLaunchKernelGGL(k_field_cost_bits, dim3(field_blocks(F.V, THREADS)), dim3(THREADS), 0, s, F, bits);
+  hipLaunchKernelGGL(k_field_cost_bits, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, bits);
 }
 
-void launch_field_finish(const FieldDev &F, float *cost, int *hops, hipStream_t s) {
-  hipLaunchKernelGGL(k_field_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS)), dim3(THREADS), 0, s, F);
-  hipLaunchKernelGGL(k_field_output, dim3(field_blocks(F.V, THREADS)), dim3(THREADS), 0, s, F, cost, hops);
+void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents, hipStream_t s) {
+  if (parents)
+    hipLaunchKernelGGL(k_field_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s,
+                       F);
+  hipLaunchKernelGGL(k_field_output, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, cost, hops);
+}
+
+void launch_field_gather(const FieldDev &F, const int *targets, int n_t, float *cost_at, int *hops_at,
+                         hipStream_t s) {
+  if (n_t <= 0) return;
+  hipLaunchKernelGGL(k_field_gather, dim3(field_blocks(n_t, THREADS), F.m), dim3(THREADS), 0, s, F, targets, n_t,
+                     cost_at, hops_at);
 }
 
 }  // namespace trg

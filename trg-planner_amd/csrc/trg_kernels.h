@@ -373,26 +373,29 @@ void launch_stitch_assemble(const StitchEdge *edges, int n_edges, int tile, int 
                             int phase, hipStream_t s);
 
 // ---- cost field of the global graph (trg_field.hip; an extension) ----------------
-// A node's key is (fp32 cost bits << 32 | hops); unreached = FIELD_KEY_NONE.  Edge costs are
+// m fields (m sources) are solved at once as ONE field of the disjoint union of m copies of the graph.  A
+// work item is the pair (field k, node v), indexed k * V + v; an edge (k, u) -> (k, col) stays in its field.
+// Every per-node array is per item (N = m * V entries); rowptr, col and the edge costs are one shared copy.
+// An item's key is (fp32 cost bits << 32 | hops); unreached = FIELD_KEY_NONE.  Edge costs are
 // (safety_factor * w + 1) * dist in fp32; FIELD_EDGE_SKIP marks an edge never relaxed (into an Invalid
 // node, or a column out of range).
 constexpr unsigned long long FIELD_KEY_NONE = ~0ull;
 constexpr unsigned FIELD_EDGE_SKIP = 0xFFFFFFFFu;
 constexpr int FIELD_NODE_INVALID = -1;  // TRG_NODE_INVALID
+constexpr int FIELD_MAX_SOURCES = 64;   // TRG_FIELD_BATCH_MAX
 // per graph: the edge costs' sum and count over relaxable edges (the bucket width) and the bad-cost flag
 struct alignas(128) FieldEdgeStats {
   double sum;
   int count;
   int bad;   // some edge cost is negative or not finite
 };
-// Round control.  Words updated by atomics inside a launch and words written by the one-thread round
-// end live on separate 128-byte lines.
+// Round control, one set for all fields (it describes the union graph).  Words updated by atomics inside a
+// launch and words written by the one-thread round end live on separate 128-byte lines.
 struct alignas(128) FieldCounters {
   int n[2];        // near-queue sizes, by round parity
   int nfar[2];     // far-pile sizes, by far_sel
   unsigned fmin;   // least live far cost (bits) when a round relaxed nothing into the near queue; ~0 = none
   int overflow;    // a push past a queue's capacity (the stamps make it impossible; checked anyway)
-  int reached;
 };
 struct alignas(128) FieldState {
   int work;        // near-queue entries after the last round: 0 = converged
@@ -406,31 +409,44 @@ struct alignas(128) FieldState {
 struct FieldCtrl {
   FieldCounters c;
   FieldState s;
+  alignas(128) int reached[FIELD_MAX_SOURCES];  // per field: items with a key
+};
+struct FieldSources {
+  int id[FIELD_MAX_SOURCES];
 };
 struct FieldDev {
   const int *rowptr, *col;
   const float *ec;             // edge costs
-  int V;
+  int V;                       // nodes
+  int m;                       // fields
+  int N;                       // items: m * V
   unsigned long long *key;
-  int *q[2];                   // near queues (V entries each), by round parity
-  int *far[2];                 // far piles (V entries each), by far_sel
-  int *stamp_near;             // round that last pushed the node to a near queue
-  unsigned *stamp_far;         // phase that last pushed the node to a far pile
-  int *parent;
+  int *q[2];                   // near queues of items (N entries each), by round parity
+  int *far[2];                 // far piles of items (N entries each), by far_sel
+  int *stamp_near;             // round that last pushed the item to a near queue
+  unsigned *stamp_far;         // phase that last pushed the item to a far pile
+  int *parent;                 // node ids, per item
   FieldCtrl *ctrl;
-  const unsigned *tight;       // pass 2: the least costs of pass 1 (bits); only edges with fl(cost[u] + c) ==
-                               // cost[v] are relaxed.  nullptr in pass 1.
+  const unsigned *tight;       // pass 2: the least costs of pass 1 (bits), per item; only edges with
+                               // fl(cost[u] + c) == cost[v] are relaxed.  nullptr in pass 1.
 };
 void launch_field_edge_cost(const int *col, const float *w, const float *dist, const int *state, int V, int E,
                             float safety_factor, float *ec, FieldEdgeStats *st, hipStream_t s);
-void launch_field_init(const FieldDev &F, int source, float delta, hipStream_t s);
+// field k starts at node sources.id[k], k < F.m (duplicates give identical fields)
+void launch_field_init(const FieldDev &F, const FieldSources &sources, float delta, hipStream_t s);
 // one relaxation round (round >= 0, consecutive from 0): relax the near queue, and when that pushed
-// nothing near, open the next bucket from the far pile; every launch reads its sizes from F.ctrl
+// nothing near in ANY field, open the next bucket from the least live far cost over all fields; every
+// launch reads its sizes from F.ctrl
 void launch_field_round(const FieldDev &F, int round, hipStream_t s);
-// pass 1 -> pass 2: bits[v] = cost word of key[v]
+// pass 1 -> pass 2: bits[item] = cost word of key[item]
 void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s);
-// parents (smallest id among the edges that realise a node's key) and the outputs: cost (+inf),
-// hops (-1) and parent (-1) of unreached nodes; F.ctrl->c.reached counts the reached nodes
-void launch_field_finish(const FieldDev &F, float *cost, int *hops, hipStream_t s);
+// parents (smallest id among the edges that realise an item's key; only if `parents`) and the outputs, m x V
+// each: cost (+inf), hops (-1) and parent (-1) of unreached items; F.ctrl->reached[k] counts field k's reached
+// nodes
+void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents, hipStream_t s);
+// the finished keys at n_t target nodes: cost_at / hops_at[k * n_t + j] of (field k, targets[j]), +inf and
+// -1 where unreached
+void launch_field_gather(const FieldDev &F, const int *targets, int n_t, float *cost_at, int *hops_at,
+                         hipStream_t s);
 
 }  // namespace trg

@@ -96,8 +96,10 @@ EXPORTS = [
     "trg_engine_stitch_boundary", "trg_engine_stitch_cross", "trg_engine_stitch_assemble",
     "trg_engine_graph_sizes",
     "trg_engine_comm_unique_id", "trg_engine_comm_init", "trg_engine_comm_adopt", "trg_engine_comm_destroy",
-    "trg_engine_stitch_exchange", "trg_engine_cost_field",
+    "trg_engine_stitch_exchange", "trg_engine_cost_field", "trg_engine_cost_field_batch",
 ]
+
+TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
 
 
 def build_library(force=False):
@@ -178,6 +180,8 @@ def load_library():
     L.trg_engine_stitch_exchange.argtypes = [vp, fp, C.c_int32, C.c_int32, ip, ip]
     L.trg_engine_set_option.argtypes = [vp, C.c_char_p, C.c_char_p]
     L.trg_engine_cost_field.argtypes = [vp, C.c_int32, fp, fp, ip, ip, C.POINTER(TrgFieldInfo)]
+    L.trg_engine_cost_field_batch.argtypes = [vp, C.c_int32, ip, fp, fp, ip, ip, ip, C.c_int32, fp, ip, ip, ip,
+                                              C.POINTER(TrgFieldInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
     L.trg_engine_fallback_reason.restype = C.c_char_p
     _lib = L
@@ -190,6 +194,20 @@ def _f(a):
 
 def _i(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def choose_frontier(ids, cost, hops):
+    """Of the candidate nodes `ids` with their `cost` and `hops` (arrays of one length): the node of the least
+    (cost, hops, id) among those with a finite cost and hops >= 0 -> (node, index into ids), or None if
+    there is none."""
+    ids = np.asarray(ids)
+    cost = np.asarray(cost)
+    hops = np.asarray(hops)
+    ok = np.flatnonzero(np.isfinite(cost) & (hops >= 0))
+    if ok.size == 0:
+        return None
+    j = int(ok[np.lexsort((ids[ok], hops[ok], cost[ok]))[0]])
+    return int(ids[j]), j
 
 
 class CsrGraph:
@@ -441,6 +459,93 @@ class Engine:
             return None
         best = int(ids[np.lexsort((ids, hops[ids], cost[ids]))[0]])
         return best, float(cost[best]), self.field_path(parent, best, int(info.source))
+
+    def cost_fields(self, sources_xy=None, source_ids=None, targets=None, full=True):
+        """m cost fields in one solve on the GPU (trg_engine_cost_field_batch; each field as cost_field's).
+        Field k starts at source_ids[k], or, where source_ids is None or source_ids[k] == -1, at the node
+        planSafePath starts from for sources_xy[k].  -> dict: with `full`, the (m, V) arrays "cost", "hops",
+        "parent"; with `targets` (node ids), the (m, n_t) arrays "cost_at", "hops_at", read on the device
+        (with full=False nothing of V entries is copied back); always "sources" (m resolved nodes), "reached"
+        (m counts) and "info" (TrgFieldInfo of the whole solve)."""
+        if sources_xy is None and source_ids is None:
+            raise ValueError("cost_fields needs sources_xy or source_ids")
+        ids = None if source_ids is None else np.ascontiguousarray(source_ids, dtype=np.int32).reshape(-1)
+        xy = None if sources_xy is None else np.ascontiguousarray(sources_xy, dtype=np.float32).reshape(-1, 2)
+        m = ids.shape[0] if ids is not None else xy.shape[0]
+        if ids is not None and xy is not None and xy.shape[0] != m:
+            raise ValueError("cost_fields: sources_xy and source_ids differ in length")
+        V, _ = self.graph_sizes("global")
+        out = {}
+        if full:
+            out["cost"] = np.empty((m, V), np.float32)
+            out["hops"] = np.empty((m, V), np.int32)
+            out["parent"] = np.empty((m, V), np.int32)
+        tg, nt = None, 0
+        if targets is not None:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+            nt = tg.shape[0]
+            out["cost_at"] = np.empty((m, nt), np.float32)
+            out["hops_at"] = np.empty((m, nt), np.int32)
+        out["sources"] = np.full(m, -1, np.int32)
+        out["reached"] = np.zeros(m, np.int32)
+        info = TrgFieldInfo()
+        self._chk(self.L.trg_engine_cost_field_batch(
+            self.h, m, None if ids is None else _i(ids), None if xy is None else _f(xy),
+            _f(out["cost"]) if full else None, _i(out["hops"]) if full else None,
+            _i(out["parent"]) if full else None, None if tg is None else _i(tg), nt,
+            None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
+            _i(out["sources"]), _i(out["reached"]), C.byref(info)))
+        out["info"] = info
+        return out
+
+    def cost_matrix(self, nodes_or_xy):
+        """Least costs between m waypoints -> (cost (m, m) float32, hops (m, m) int32, node ids (m,)): entry
+        [a, b] is from waypoint a to waypoint b.  `nodes_or_xy` is a list of node ids or an (m, 2) array of
+        positions (each resolved as cost_field resolves a source).  The fields are read at the waypoints on
+        the device; more than TRG_FIELD_BATCH_MAX waypoints run in chunks of sources."""
+        a = np.asarray(nodes_or_xy)
+        if a.ndim == 1 and np.issubdtype(a.dtype, np.integer):
+            nodes = np.ascontiguousarray(a, dtype=np.int32)
+        else:
+            # every chunk's targets are ALL waypoints: resolve the positions first (no solve, see the header)
+            xy = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 2)
+            nodes = np.empty(xy.shape[0], np.int32)
+            for k0 in range(0, xy.shape[0], TRG_FIELD_BATCH_MAX):
+                part = np.ascontiguousarray(xy[k0:k0 + TRG_FIELD_BATCH_MAX])
+                got = np.empty(part.shape[0], np.int32)
+                self._chk(self.L.trg_engine_cost_field_batch(self.h, part.shape[0], None, _f(part), None, None, None,
+                                                             None, 0, None, None, _i(got), None, None))
+                nodes[k0:k0 + TRG_FIELD_BATCH_MAX] = got
+        m = nodes.shape[0]
+        cost = np.empty((m, m), np.float32)
+        hops = np.empty((m, m), np.int32)
+        for k0 in range(0, m, TRG_FIELD_BATCH_MAX):
+            r = self.cost_fields(source_ids=nodes[k0:k0 + TRG_FIELD_BATCH_MAX], targets=nodes, full=False)
+            cost[k0:k0 + TRG_FIELD_BATCH_MAX] = r["cost_at"]
+            hops[k0:k0 + TRG_FIELD_BATCH_MAX] = r["hops_at"]
+        return cost, hops, nodes
+
+    def cheapest_frontiers(self, poses):
+        """cheapest_frontier for every pose of `poses` (m, 2), from one batch of fields read at the Frontier
+        nodes -> list of (node, cost, path ids) or None, per pose."""
+        xy = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 2)
+        v = TrgCsrView()
+        self._chk(self.L.trg_engine_export_csr(self.h, KIND_GLOBAL, C.byref(v)))
+        frontier = np.empty(0, np.int32)  # (an empty graph: the batch call says so, as cheapest_frontier's does)
+        if v.num_nodes:
+            state = np.ctypeslib.as_array(v.node_state, shape=(v.num_nodes,))
+            frontier = np.flatnonzero(state == 1).astype(np.int32)
+        out = []
+        for k0 in range(0, xy.shape[0], TRG_FIELD_BATCH_MAX):
+            r = self.cost_fields(sources_xy=xy[k0:k0 + TRG_FIELD_BATCH_MAX], targets=frontier)
+            for k in range(r["sources"].shape[0]):
+                pick = choose_frontier(frontier, r["cost_at"][k], r["hops_at"][k])
+                if pick is None:
+                    out.append(None)
+                    continue
+                best, j = pick
+                out.append((best, float(r["cost_at"][k, j]), self.field_path(r["parent"][k], best, int(r["sources"][k]))))
+        return out
 
     def check_reached(self, pos2d):
         p = np.ascontiguousarray(pos2d, dtype=np.float32)
