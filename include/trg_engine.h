@@ -369,6 +369,42 @@ TrgStatus trg_engine_cost_field_batch(
     int32_t *sources_out,        /* m resolved sources, may be NULL                   */
     int32_t *reached_out,        /* m, may be NULL                                    */
     TrgFieldInfo *info);
+/* Routes: the paths behind the keys of the LAST cost-field solve, walked on the device (DESIGN.md section 2,
+ * "Routes").  A successful trg_engine_cost_field / _batch solve stays on the device; a new solve replaces it,
+ * and init_graph, update_graph (from its start, also when it fails), load_json, a reset of the global graph
+ * end it.
+ * Route r is field route_field[r] (0 .. m-1 of that solve) to node route_target[r].  With h = hops there:
+ *   h == -1   the empty route: num_nodes 0, cost +inf, path_length and avg_risk 0;
+ *   else      the h + 1 nodes source = p_0, ..., p_h = target with p_{i-1} = parent[p_i].  The route edge into
+ *             p_i is the edge of least CSR index in row p_{i-1} whose col is p_i, which is relaxable (not into
+ *             an Invalid node) and whose extension of p_{i-1}'s key is p_i's key -- this decides among
+ *             duplicate edges.  path_length is the fp32 left fold of the route edges' dist, taken from the
+ *             target end backwards (the order in which planSafePath's backtrack sums); avg_risk the same
+ *             fold of their weight, divided by num_nodes in fp32; cost the key's cost word (+inf for a node
+ *             reached by a saturated fold, which has a route like any other).  A target equal to the source:
+ *             one node, zeros.
+ * Capacity as trg_engine_plan_batch: route r's nodes are [offsets[r], offsets[r+1]) of node_ids (and of xyz,
+ * x 3); a route that no longer fits in cap is truncated (its first nodes are kept), later routes are empty
+ * ranges; infos[r].num_nodes always keeps the full length, so a second call with enough room -- which needs
+ * no new solve -- gets all of it.  With node_ids and xyz both NULL (or cap == 0) the call returns infos only
+ * and every offset is 0.  If the solve was asked for no parent output, the first routes call runs the parent
+ * sweep; the routes are those of a solve that was.
+ * TRG_ERR_INVALID_ARG when no solve of the current graph is retained (the message says whether there is none
+ * or the graph changed), for n_routes < 0, cap < 0, a field or target out of range (the message names it and
+ * the route); n_routes == 0 is TRG_OK.  TRG_ERR_CAPACITY when device memory runs out; TRG_ERR_DEVICE if a
+ * walk does not end at its field's source (the retained arrays are damaged; nothing is returned as a route). */
+typedef struct TrgRouteInfo {
+  int32_t num_nodes;  /* full length of the route, 0 if the target is unreachable */
+  float cost, path_length, avg_risk;
+} TrgRouteInfo;
+TrgStatus trg_engine_field_routes(TrgEngine *e, int32_t n_routes,
+    const int32_t *route_field, const int32_t *route_target,
+    int32_t *offsets,      /* n_routes + 1 */
+    int32_t *node_ids,     /* room for cap ids, may be NULL */
+    float *xyz,            /* room for cap x 3, may be NULL (filled on the host from the ids) */
+    int32_t cap,
+    TrgRouteInfo *infos,   /* n_routes, may be NULL */
+    TrgFieldInfo *info);   /* ms_device / ms_total / host_syncs of this call, may be NULL */
 
 /* ---- instrumentation ------------------------------------------------------------------------- */
 TrgStatus trg_engine_get_stats(const TrgEngine *e, TrgStats *out);

@@ -20,6 +20,19 @@ struct FieldBufs {
   float ec_sf = 0.0f;
   double mean_cost = 0.0;    // over relaxable edges
   bool bad_cost = false;
+  // The last solve, kept on the device for trg_engine_field_routes: set by a successful solve, cleared when a
+  // solve begins its device work; a graph_version other than the engine's (init_graph, update_graph, load_json,
+  // a reset) makes it stale, so does a device-build CSR that is no longer valid (an update_graph that began,
+  // whether or not it finished), and field_release drops it with the buffers.
+  struct Last {
+    uint64_t version = 0;    // graph_version of the solve (0: none)
+    FieldDev F{};            // keys, parents and the CSR it ran on
+    const float *w = nullptr, *dist = nullptr;  // that CSR's edge arrays
+    FieldSources sources{};  // a walk must end at its field's
+    bool parents = false;    // the parent sweep ran
+    bool dev_csr = false;    // F's CSR is the device build's (gone stale when an update_graph begins)
+  } last;
+  DevArr route_field, route_target, route_len, route_off, route_ids, route_info;
   Pinned<FieldState> h_state;
   Pinned<FieldEdgeStats> h_stats;
   Pinned<int> h_reached;  // per field
@@ -50,6 +63,13 @@ struct FieldRequest {
   int32_t *sources_out, *reached_out;  // m
   bool resolve_only;          // nothing but sources_out is wanted: no solve
 };
+
+// an allocation that fails is a matter of capacity
+TrgStatus field_grow(TrgEngine *e, DevArr &a, size_t bytes) {
+  if (ensure_bytes(e, a, bytes) == TRG_OK) return TRG_OK;
+  (void)hipGetLastError();
+  return e->fail(TRG_ERR_CAPACITY, "cost field: no device memory for " + std::to_string(bytes) + " bytes (" + e->err + ")");
+}
 
 TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) {
   const auto t_total = Clock::now();
@@ -93,6 +113,7 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
   const int N = (int)N64;
   if (!e->field) e->field.reset(new FieldBufs());
   FieldBufs &fb = *e->field;
+  fb.last = FieldBufs::Last{};  // from here on the work arrays change
   HIPCHK(e, fb.h_state.ensure(1));
   HIPCHK(e, fb.h_stats.ensure(1));
   HIPCHK(e, fb.h_reached.ensure(TRG_FIELD_BATCH_MAX));
@@ -159,11 +180,7 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
 
   // work arrays, per item
   const size_t nV = (size_t)N + 4;
-  const auto grow = [e](DevArr &a, size_t bytes) {  // an allocation that fails is a matter of capacity
-    if (ensure_bytes(e, a, bytes) == TRG_OK) return TRG_OK;
-    (void)hipGetLastError();
-    return e->fail(TRG_ERR_CAPACITY, "cost field: no device memory for " + std::to_string(bytes) + " bytes (" + e->err + ")");
-  };
+  const auto grow = [e](DevArr &a, size_t bytes) { return field_grow(e, a, bytes); };
   if ((st = grow(fb.key, nV * sizeof(unsigned long long))) != TRG_OK) return st;
   for (DevArr *a : {&fb.q0, &fb.q1, &fb.far0, &fb.far1, &fb.stamp_near, &fb.stamp_far, &fb.parent, &fb.cost,
                     &fb.hops})
@@ -246,6 +263,14 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
   info->host_syncs = syncs;
   info->ms_device = ms_dev;
   info->ms_total = ms_since(t_total);
+  fb.last.version = e->graph_version;
+  fb.last.F = F;
+  fb.last.F.tight = nullptr;  // (its array holds the cost output now)
+  fb.last.w = d_w;
+  fb.last.dist = d_dist;
+  fb.last.sources = sources;
+  fb.last.parents = rq.parent != nullptr;
+  fb.last.dev_csr = d_col != (const int *)fb.up_col.p;
   return TRG_OK;
 }
 
@@ -260,6 +285,128 @@ TrgStatus field_guarded(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info
   } catch (...) {
     return e->fail(TRG_ERR_DEVICE, "cost field: unknown exception");
   }
+}
+
+static_assert(sizeof(TrgRouteInfo) == sizeof(FieldRouteInfo) && offsetof(TrgRouteInfo, num_nodes) == 0 &&
+                  offsetof(TrgRouteInfo, cost) == offsetof(FieldRouteInfo, cost) &&
+                  offsetof(TrgRouteInfo, path_length) == offsetof(FieldRouteInfo, path_length) &&
+                  offsetof(TrgRouteInfo, avg_risk) == offsetof(FieldRouteInfo, avg_risk),
+              "the kernels' and the header's route info differ");
+
+struct RouteRequest {
+  int32_t n;
+  const int32_t *field, *target;  // n each
+  int32_t *offsets;               // n + 1
+  int32_t *node_ids;              // cap, may be nullptr
+  float *xyz;                     // cap x 3, may be nullptr
+  int32_t cap;
+  TrgRouteInfo *infos;            // n, may be nullptr
+};
+
+// Routes of the retained solve ("Routes"): lengths on the device, their clipped prefix sum
+// on the host, then the walk.  Two host waits with ids or positions, one without.
+TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info) {
+  const auto t_total = Clock::now();
+  if (rq.n < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: n_routes < 0");
+  if (rq.cap < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: cap < 0");
+  if (!e->field || e->field->last.version == 0)
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: no cost-field solve is retained (solve first)");
+  FieldBufs &fb = *e->field;
+  if (fb.last.version != e->graph_version || (fb.last.dev_csr && !e->dev_csr_valid))
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: the retained solve is of an earlier graph (solve again)");
+  const FieldDev &F = fb.last.F;
+  if (rq.n > 0 && (!rq.field || !rq.target || !rq.offsets))
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: null route_field, route_target or offsets");
+  for (int r = 0; r < rq.n; ++r) {
+    if (rq.field[r] < 0 || rq.field[r] >= F.m)
+      return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: field " + std::to_string(rq.field[r]) + " of route " +
+                                              std::to_string(r) + " out of range (the solve has " +
+                                              std::to_string(F.m) + ")");
+    if (rq.target[r] < 0 || rq.target[r] >= F.V)
+      return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: target " + std::to_string(rq.target[r]) + " of route " +
+                                              std::to_string(r) + " out of range");
+  }
+  if (rq.n == 0) {
+    if (rq.offsets) rq.offsets[0] = 0;
+    info->ms_total = ms_since(t_total);
+    return TRG_OK;
+  }
+  const bool want_ids = (rq.node_ids || rq.xyz) && rq.cap > 0;
+  const size_t n = (size_t)rq.n;
+  TrgStatus st;
+  if ((st = field_grow(e, fb.route_field, n * sizeof(int))) != TRG_OK) return st;
+  if ((st = field_grow(e, fb.route_target, n * sizeof(int))) != TRG_OK) return st;
+  if ((st = field_grow(e, fb.route_info, n * sizeof(FieldRouteInfo))) != TRG_OK) return st;
+  HIPCHK(e, fb.t0.create());
+  HIPCHK(e, fb.t1.create());
+  hipStream_t s = e->s_main;
+  int syncs = 0;
+  HIPCHK(e, hipMemcpyAsync(fb.route_field.p, rq.field, n * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipMemcpyAsync(fb.route_target.p, rq.target, n * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipEventRecord(fb.t0, s));
+  if (!fb.last.parents) {
+    launch_field_parents_late(F, s);
+    HIPCHK(e, hipGetLastError());
+    fb.last.parents = true;
+  }
+  const int *d_field = (const int *)fb.route_field.p, *d_target = (const int *)fb.route_target.p;
+  std::vector<int32_t> ids;
+  int total = 0;
+  std::fill(rq.offsets, rq.offsets + n + 1, 0);
+  if (want_ids) {
+    if ((st = field_grow(e, fb.route_len, n * sizeof(int))) != TRG_OK) return st;
+    if ((st = field_grow(e, fb.route_off, (n + 1) * sizeof(int))) != TRG_OK) return st;
+    launch_field_route_len(F, d_field, d_target, rq.n, (int *)fb.route_len.p, s);
+    HIPCHK(e, hipGetLastError());
+    std::vector<int32_t> len(n);
+    HIPCHK(e, hipMemcpyAsync(len.data(), fb.route_len.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    syncs++;
+    // a route that no longer fits is truncated, later routes are empty ranges
+    for (size_t r = 0; r < n; ++r)
+      rq.offsets[r + 1] = (int32_t)std::min<long long>((long long)rq.offsets[r] + len[r], rq.cap);
+    total = rq.offsets[n];
+    if ((st = field_grow(e, fb.route_ids, ((size_t)total + 4) * sizeof(int))) != TRG_OK) return st;
+    HIPCHK(e, hipMemcpyAsync(fb.route_off.p, rq.offsets, (n + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  }
+  std::vector<FieldRouteInfo> infos(n);
+  launch_field_route_walk(F, fb.last.w, fb.last.dist, d_field, d_target, rq.n,
+                          want_ids ? (const int *)fb.route_off.p : nullptr, want_ids ? (int *)fb.route_ids.p : nullptr,
+                          (FieldRouteInfo *)fb.route_info.p, fb.last.sources, s);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipEventRecord(fb.t1, s));
+  int32_t *ids_out = rq.node_ids;
+  if (total > 0) {
+    if (!ids_out) {
+      ids.resize((size_t)total);
+      ids_out = ids.data();
+    }
+    HIPCHK(e, hipMemcpyAsync(ids_out, fb.route_ids.p, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(e, hipMemcpyAsync(infos.data(), fb.route_info.p, n * sizeof(FieldRouteInfo), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  syncs++;
+  for (size_t r = 0; r < n; ++r)
+    if (infos[r].num_nodes == FIELD_ROUTE_BROKEN)
+      return e->fail(TRG_ERR_DEVICE, "cost field routes: the walk of route " + std::to_string(r) +
+                                         " did not end at its field's source");
+  if (rq.infos)
+    for (size_t r = 0; r < n; ++r)
+      rq.infos[r] = TrgRouteInfo{infos[r].num_nodes, infos[r].cost, infos[r].path_length, infos[r].avg_risk};
+  if (rq.xyz)
+    for (int i = 0; i < total; ++i) {
+      const int id = ids_out[i];
+      if (id < 0 || id >= F.V) return e->fail(TRG_ERR_DEVICE, "cost field routes: a walk left the graph");
+      rq.xyz[3 * i] = e->nx[id];
+      rq.xyz[3 * i + 1] = e->ny[id];
+      rq.xyz[3 * i + 2] = e->nz[id];
+    }
+  float ms_dev = 0.0f;
+  HIPCHK(e, hipEventElapsedTime(&ms_dev, fb.t0, fb.t1));
+  info->host_syncs = syncs;
+  info->ms_device = ms_dev;
+  info->ms_total = ms_since(t_total);
+  return TRG_OK;
 }
 
 }  // namespace
@@ -307,6 +454,26 @@ TrgStatus trg_engine_cost_field_batch(TrgEngine *e, int32_t m, const int32_t *so
   FieldRequest rq{m, source_ids, source_xy, cost, hops, parent, targets, n_targets, cost_at, hops_at, sources_out,
                   reached_out, resolve_only};
   return field_guarded(e, rq, info);
+}
+
+TrgStatus trg_engine_field_routes(TrgEngine *e, int32_t n_routes, const int32_t *route_field,
+                                  const int32_t *route_target, int32_t *offsets, int32_t *node_ids, float *xyz,
+                                  int32_t cap, TrgRouteInfo *infos, TrgFieldInfo *info) {
+  REQUIRE_DEVICE(e);
+  TrgFieldInfo local{};
+  if (!info) info = &local;
+  *info = TrgFieldInfo{};
+  info->source = -1;
+  const RouteRequest rq{n_routes, route_field, route_target, offsets, node_ids, xyz, cap, infos};
+  try {
+    return field_routes(e, rq, info);
+  } catch (const std::bad_alloc &) {
+    return e->fail(TRG_ERR_CAPACITY, "cost field routes: out of host memory");
+  } catch (const std::exception &x) {
+    return e->fail(TRG_ERR_DEVICE, std::string("cost field routes: ") + x.what());
+  } catch (...) {
+    return e->fail(TRG_ERR_DEVICE, "cost field routes: unknown exception");
+  }
 }
 
 }  // extern "C"

@@ -359,6 +359,101 @@ __global__ __launch_bounds__(THREADS) void k_field_gather(FieldDev F, const int 
   }
 }
 
+// The lazy parent sweep of a solve that skipped it: every parent word equal to `from` becomes `to`
+// (-1 -> INT_MAX before k_field_parent, INT_MAX -> -1 after it, as k_field_init / k_field_output leave them).
+__global__ __launch_bounds__(THREADS) void k_field_parent_mark(FieldDev F, int from, int to) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < F.N; i += gridDim.x * blockDim.x)
+    if (F.parent[i] == from) F.parent[i] = to;
+}
+
+// Route lengths: hops + 1 at (field, target), 0 where the target has no key.
+__global__ __launch_bounds__(THREADS) void k_field_route_len(FieldDev F, const int *__restrict__ route_field,
+                                                             const int *__restrict__ route_target, int n_routes,
+                                                             int *len) {
+  for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n_routes; r += gridDim.x * blockDim.x) {
+    const unsigned long long k = F.key[route_field[r] * F.V + route_target[r]];
+    len[r] = k == FIELD_KEY_NONE ? 0 : (int)(unsigned)k + 1;
+  }
+}
+
+// Routes ("Routes"): one 16-lane group per route, grid-stride.  The group walks the parents
+// from the target back to the source -- hops[target] steps, the hops drop by one per step -- and writes the node
+// ids at descending positions of the route's segment [offsets[r], offsets[r + 1]) (a truncated segment keeps the
+// source end; the sums cover the whole route).  The route edge into v from its parent u is the least CSR index
+// of row u with col == v, a cost that is not the skip marker and key_extend(key[u], ec) == key[v]: the lanes
+// read 16 consecutive entries per trip, so the lowest matching lane of the first trip with a match is that
+// edge.  Everything the loops branch on is uniform over the group; the ballot is masked to the group's lanes.
+// A walk that loses its way -- a parent out of range, no route edge, an end that is not the field's source; none
+// can happen on the keys and parents of a finished solve -- reports num_nodes = FIELD_ROUTE_BROKEN, which the
+// host turns into an error, instead of a route that looks right.
+__global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const float *__restrict__ w,
+                                                              const float *__restrict__ dist,
+                                                              const int *__restrict__ route_field,
+                                                              const int *__restrict__ route_target, int n_routes,
+                                                              const int *__restrict__ offsets, int *node_ids,
+                                                              FieldRouteInfo *infos, FieldSources S) {
+  const int V = F.V;
+  const int sub = threadIdx.x & (GROUP - 1);
+  const int gshift = lane_id() & ~(GROUP - 1);  // the group's first lane within the wave
+  const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
+  const int ng = gridDim.x * blockDim.x / GROUP;
+  for (int r = g0; r < n_routes; r += ng) {
+    const int fbase = route_field[r] * V;
+    int v = route_target[r];
+    unsigned long long kv = F.key[fbase + v];
+    FieldRouteInfo out;
+    out.num_nodes = 0;
+    out.cost = __builtin_huge_valf();
+    out.path_length = 0.0f;
+    out.avg_risk = 0.0f;
+    if (kv != FIELD_KEY_NONE) {
+      const int h = (int)(unsigned)kv;
+      const int off = node_ids ? offsets[r] : 0;
+      const int room = node_ids ? offsets[r + 1] - off : 0;
+      float sum_dist = 0.0f, sum_w = 0.0f;
+      bool broken = false;
+      for (int i = h;; --i) {
+        if (sub == 0 && i < room) node_ids[off + i] = v;
+        if (i == 0) break;
+        const int u = F.parent[fbase + v];
+        if (u < 0 || u >= V) {  // (never for a node with a key and hops > 0: the parent sweep ran)
+          broken = true;
+          break;
+        }
+        const unsigned long long ku = F.key[fbase + u];
+        int edge = -1;
+        for (int k0 = F.rowptr[u], kend = F.rowptr[u + 1]; k0 < kend; k0 += GROUP) {
+          const int k = k0 + sub;
+          bool hit = false;
+          if (k < kend && F.col[k] == v) {
+            const float c = F.ec[k];
+            hit = __float_as_uint(c) != FIELD_EDGE_SKIP && key_extend(ku, c) == kv;
+          }
+          const unsigned hits = (unsigned)(ballot(hit) >> gshift) & ((1u << GROUP) - 1u);
+          if (hits) {
+            edge = k0 + __ffs(hits) - 1;
+            break;
+          }
+        }
+        if (edge < 0) {  // (never: the parent is a node with such an edge)
+          broken = true;
+          break;
+        }
+        sum_dist += dist[edge];
+        sum_w += w[edge];
+        v = u;
+        kv = ku;
+      }
+      if (v != S.id[route_field[r]]) broken = true;  // h steps back from the target end at the source
+      out.num_nodes = broken ? FIELD_ROUTE_BROKEN : h + 1;
+      out.cost = key_cost(F.key[fbase + route_target[r]]);
+      out.path_length = sum_dist;
+      out.avg_risk = sum_w / (float)(h + 1);
+    }
+    if (sub == 0 && infos) infos[r] = out;
+  }
+}
+
 int field_blocks(long long items, int per_block) {
   const long long b = (items + per_block - 1) / per_block;
   return (int)std::max(1ll, std::min<long long>(b, MAX_BLOCKS));
@@ -406,6 +501,28 @@ void launch_field_gather(const FieldDev &F, const int *targets, int n_t, float *
   if (n_t <= 0) return;
   hipLaunchKernelGGL(k_field_gather, dim3(field_blocks(n_t, THREADS), F.m), dim3(THREADS), 0, s, F, targets, n_t,
                      cost_at, hops_at);
+}
+
+void launch_field_parents_late(const FieldDev &F, hipStream_t s) {
+  const dim3 grid(field_blocks(F.N, THREADS));
+  hipLaunchKernelGGL(k_field_parent_mark, grid, dim3(THREADS), 0, s, F, -1, INT_MAX);
+  hipLaunchKernelGGL(k_field_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s, F);
+  hipLaunchKernelGGL(k_field_parent_mark, grid, dim3(THREADS), 0, s, F, INT_MAX, -1);
+}
+
+void launch_field_route_len(const FieldDev &F, const int *route_field, const int *route_target, int n_routes,
+                            int *len, hipStream_t s) {
+  if (n_routes <= 0) return;
+  hipLaunchKernelGGL(k_field_route_len, dim3(field_blocks(n_routes, THREADS)), dim3(THREADS), 0, s, F, route_field,
+                     route_target, n_routes, len);
+}
+
+void launch_field_route_walk(const FieldDev &F, const float *w, const float *dist, const int *route_field,
+                             const int *route_target, int n_routes, const int *offsets, int *node_ids,
+                             FieldRouteInfo *infos, const FieldSources &sources, hipStream_t s) {
+  if (n_routes <= 0) return;
+  hipLaunchKernelGGL(k_field_route_walk, dim3(field_blocks((long long)n_routes * GROUP, THREADS)), dim3(THREADS), 0,
+                     s, F, w, dist, route_field, route_target, n_routes, offsets, node_ids, infos, sources);
 }
 
 }  // namespace trg

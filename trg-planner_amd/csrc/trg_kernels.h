@@ -448,5 +448,23 @@ void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents
 // -1 where unreached
 void launch_field_gather(const FieldDev &F, const int *targets, int n_t, float *cost_at, int *hops_at,
                          hipStream_t s);
+// Routes of a finished solve ("Routes").  Layout of TrgRouteInfo (include/trg_engine.h).
+struct FieldRouteInfo {
+  int num_nodes;
+  float cost, path_length, avg_risk;
+};
+constexpr int FIELD_ROUTE_BROKEN = -1;  // num_nodes of a walk that did not end at its field's source
+// the parent sweep of a finished solve whose launch_field_finish ran without `parents`: F.parent as with it
+void launch_field_parents_late(const FieldDev &F, hipStream_t s);
+// len[r] = hops + 1 of (field route_field[r], node route_target[r]), 0 where unreached
+void launch_field_route_len(const FieldDev &F, const int *route_field, const int *route_target, int n_routes,
+                            int *len, hipStream_t s);
+// Walks route r from its target back along F.parent: node ids at [offsets[r], offsets[r + 1]) (the first ids of
+// a route that is longer), infos[r] over the whole route; w / dist are the CSR's edge arrays, sources the
+// solve's (a walk must end at its field's, else infos[r].num_nodes = FIELD_ROUTE_BROKEN).  node_ids may be
+// nullptr (offsets is then not read), infos may be nullptr.
+void launch_field_route_walk(const FieldDev &F, const float *w, const float *dist, const int *route_field,
+                             const int *route_target, int n_routes, const int *offsets, int *node_ids,
+                             FieldRouteInfo *infos, const FieldSources &sources, hipStream_t s);
 
 }  // namespace trg

@@ -60,6 +60,11 @@ class TrgFieldInfo(C.Structure):
                 ("host_syncs", C.c_int32), ("ms_device", C.c_double), ("ms_total", C.c_double)]
 
 
+class TrgRouteInfo(C.Structure):
+    _fields_ = [("num_nodes", C.c_int32), ("cost", C.c_float), ("path_length", C.c_float),
+                ("avg_risk", C.c_float)]
+
+
 class TrgStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "map_points", "expanded_nodes", "trials", "samples", "created_nodes", "invalid_nodes",
@@ -97,6 +102,7 @@ EXPORTS = [
     "trg_engine_graph_sizes",
     "trg_engine_comm_unique_id", "trg_engine_comm_init", "trg_engine_comm_adopt", "trg_engine_comm_destroy",
     "trg_engine_stitch_exchange", "trg_engine_cost_field", "trg_engine_cost_field_batch",
+    "trg_engine_field_routes",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -182,6 +188,8 @@ def load_library():
     L.trg_engine_cost_field.argtypes = [vp, C.c_int32, fp, fp, ip, ip, C.POINTER(TrgFieldInfo)]
     L.trg_engine_cost_field_batch.argtypes = [vp, C.c_int32, ip, fp, fp, ip, ip, ip, C.c_int32, fp, ip, ip, ip,
                                               C.POINTER(TrgFieldInfo)]
+    L.trg_engine_field_routes.argtypes = [vp, C.c_int32, ip, ip, ip, ip, fp, C.c_int32, C.POINTER(TrgRouteInfo),
+                                          C.POINTER(TrgFieldInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
     L.trg_engine_fallback_reason.restype = C.c_char_p
     _lib = L
@@ -527,7 +535,8 @@ class Engine:
 
     def cheapest_frontiers(self, poses):
         """cheapest_frontier for every pose of `poses` (m, 2), from one batch of fields read at the Frontier
-        nodes -> list of (node, cost, path ids) or None, per pose."""
+        nodes and one routes call for the chosen nodes (nothing of V entries is copied back) -> list of
+        (node, cost, path ids) or None, per pose."""
         xy = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 2)
         v = TrgCsrView()
         self._chk(self.L.trg_engine_export_csr(self.h, KIND_GLOBAL, C.byref(v)))
@@ -537,15 +546,66 @@ class Engine:
             frontier = np.flatnonzero(state == 1).astype(np.int32)
         out = []
         for k0 in range(0, xy.shape[0], TRG_FIELD_BATCH_MAX):
-            r = self.cost_fields(sources_xy=xy[k0:k0 + TRG_FIELD_BATCH_MAX], targets=frontier)
-            for k in range(r["sources"].shape[0]):
-                pick = choose_frontier(frontier, r["cost_at"][k], r["hops_at"][k])
-                if pick is None:
-                    out.append(None)
-                    continue
-                best, j = pick
-                out.append((best, float(r["cost_at"][k, j]), self.field_path(r["parent"][k], best, int(r["sources"][k]))))
+            r = self.cost_fields(sources_xy=xy[k0:k0 + TRG_FIELD_BATCH_MAX], targets=frontier, full=False)
+            picks = [choose_frontier(frontier, r["cost_at"][k], r["hops_at"][k]) for k in range(r["sources"].shape[0])]
+            chosen = [(k, p) for k, p in enumerate(picks) if p is not None]
+            routes = self.routes([k for k, _ in chosen], [p[0] for _, p in chosen], xyz=False,
+                                 hops_at=[r["hops_at"][k, p[1]] for k, p in chosen]) if chosen else []
+            paths = {k: ids.tolist() for (k, _), (ids, _, _) in zip(chosen, routes)}
+            for k, pick in enumerate(picks):
+                out.append(None if pick is None else (pick[0], float(r["cost_at"][k, pick[1]]), paths[k]))
         return out
+
+    def routes(self, fields, targets, xyz=True, hops_at=None, with_info=False):
+        """Paths of the last cost_field / cost_fields solve, walked on the GPU (trg_engine_field_routes; DESIGN.md
+        section 2, "Routes"): route r runs from the source of field fields[r] of that solve to node targets[r].
+        -> list of (ids int32 (n,), xyz float32 (n, 3) or None, TrgRouteInfo) per route; an unreachable target
+        gives empty arrays and num_nodes == 0.  The buffers are sized from `hops_at` (hops of the routes'
+        targets, as cost_fields gathers them) when given, else from a first call that returns the lengths only;
+        no new solve either way.  with_info: -> (that list, TrgFieldInfo of the last call)."""
+        f = np.ascontiguousarray(fields, dtype=np.int32).reshape(-1)
+        t = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+        if f.shape[0] != t.shape[0]:
+            raise ValueError("routes: fields and targets differ in length")
+        n = f.shape[0]
+        infos = (TrgRouteInfo * max(n, 1))()
+        off = np.zeros(n + 1, np.int32)
+        info = TrgFieldInfo()
+        if hops_at is not None:
+            cap = int((np.asarray(hops_at, np.int64).reshape(-1) + 1).sum())
+        else:
+            self._chk(self.L.trg_engine_field_routes(self.h, n, _i(f), _i(t), _i(off), None, None, 0, infos,
+                                                     C.byref(info)))
+            cap = sum(infos[r].num_nodes for r in range(n))
+        if cap > 2**31 - 1:
+            raise ValueError(f"routes: {cap} nodes in all do not fit one call's 32-bit capacity; ask for fewer routes")
+        ids = np.empty(max(cap, 1), np.int32)
+        pts = np.empty((max(cap, 1), 3), np.float32) if xyz else None
+        self._chk(self.L.trg_engine_field_routes(self.h, n, _i(f), _i(t), _i(off), _i(ids),
+                                                 None if pts is None else _f(pts), cap, infos, C.byref(info)))
+        out = []
+        for r in range(n):
+            a, b = int(off[r]), int(off[r + 1])
+            one = TrgRouteInfo(infos[r].num_nodes, infos[r].cost, infos[r].path_length, infos[r].avg_risk)
+            out.append((ids[a:b].copy(), None if pts is None else pts[a:b].copy(), one))
+        return (out, info) if with_info else out
+
+    def plan_many(self, start_xy, goals_xy):
+        """Paths from one start to many goals from ONE cost field: the field from the node planSafePath starts
+        from for `start_xy`, every goal of `goals_xy` (n, 2) resolved to a node the same way, one routes call
+        -> list of (path xyz float32 (k, 3), TrgRouteInfo) per goal; an unreachable goal gives an empty path and
+        num_nodes == 0.  Each path is the least fp32 fold of edge costs to its goal node (cost_field's
+        semantics), not planSafePath's A* result."""
+        goals = np.ascontiguousarray(goals_xy, dtype=np.float32).reshape(-1, 2)
+        self.cost_fields(sources_xy=np.ascontiguousarray(start_xy, dtype=np.float32).reshape(1, 2), full=False)
+        nodes = np.empty(goals.shape[0], np.int32)
+        for k0 in range(0, goals.shape[0], TRG_FIELD_BATCH_MAX):
+            part = np.ascontiguousarray(goals[k0:k0 + TRG_FIELD_BATCH_MAX])
+            got = np.empty(part.shape[0], np.int32)
+            self._chk(self.L.trg_engine_cost_field_batch(self.h, part.shape[0], None, _f(part), None, None, None,
+                                                         None, 0, None, None, _i(got), None, None))
+            nodes[k0:k0 + TRG_FIELD_BATCH_MAX] = got
+        return [(pts, one) for _, pts, one in self.routes(np.zeros(nodes.shape[0], np.int32), nodes)]
 
     def check_reached(self, pos2d):
         p = np.ascontiguousarray(pos2d, dtype=np.float32)
