@@ -369,6 +369,49 @@ TrgStatus trg_engine_cost_field_batch(
     int32_t *sources_out,        /* m resolved sources, may be NULL                   */
     int32_t *reached_out,        /* m, may be NULL                                    */
     TrgFieldInfo *info);
+/* Bounded fields ("Bounded fields"): trg_engine_cost_field_batch with a bound per field.
+ * The field truncated at bound b (an fp32 cost >= 0, +inf allowed) is the full field with every node whose least
+ * cost is greater than b reported as unreached: cost +inf, hops -1, parent -1, not counted in reached.  Every
+ * node with cost <= b -- equal bits included -- keeps its cost bits, hops and parent; b = +inf is the full field
+ * (nodes reached at a saturated +inf stay reached).  The result is exact: fl(a + c) >= a, so a node within b has a
+ * least walk within b, and so has every candidate parent of it.
+ * Field k is truncated at bound[k] = min(budget[k], settle_k):
+ *   budget     m costs, NULL: +inf each
+ *   settle     over the entries of `targets`:
+ *                TRG_FIELD_SETTLE_NONE  settle_k = +inf
+ *                TRG_FIELD_SETTLE_ANY   the least full-field cost of field k over the targets
+ *                TRG_FIELD_SETTLE_ALL   the greatest such cost
+ *              a mode whose value would come from a target without a key gives +inf: ANY with no reachable
+ *              target, ALL with an unreachable or Invalid one, solve the full field.
+ *   bound_out  m: bound[k], a function of the graph, the sources and the arguments alone; may be NULL
+ * The solve stops expanding a field once its bound is known, so a bound that few nodes lie within costs few
+ * rounds.  Everything else is trg_engine_cost_field_batch's: the sources, the outputs (cost_at / hops_at read the
+ * truncated field), the resolve-only call (bound_out NULL as well), the errors, and the solve retained for
+ * trg_engine_field_routes (a target beyond its field's bound has the empty route, one within it the route it
+ * has in the full field) and trg_engine_field_reached.  trg_engine_cost_field_batch is this call with budget
+ * NULL, TRG_FIELD_SETTLE_NONE and bound_out NULL.
+ * TRG_ERR_INVALID_ARG also for a budget that is negative or NaN (the message names the field), a settle value
+ * outside the enum, a settle mode other than NONE with n_targets == 0 or targets NULL. */
+enum { TRG_FIELD_SETTLE_NONE = 0, TRG_FIELD_SETTLE_ANY = 1, TRG_FIELD_SETTLE_ALL = 2 };
+TrgStatus trg_engine_cost_field_bounded(
+    TrgEngine *e, int32_t m, const int32_t *source_ids, const float *source_xy,
+    const float *budget,         /* m, or NULL: +inf each */
+    int32_t settle,              /* TRG_FIELD_SETTLE_*, over `targets` */
+    float *cost, int32_t *hops, int32_t *parent,
+    const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at,
+    int32_t *sources_out, int32_t *reached_out,
+    float *bound_out,            /* m: the bound each field ended with, may be NULL */
+    TrgFieldInfo *info);
+/* The nodes of field `field` (0 .. m-1) of the retained solve that have a key, compacted on the device: their
+ * ids in ascending order with cost and hops, so that a bounded field that reaches few nodes is read without
+ * copying anything of num_nodes entries.  *n_out is always the full count; node_ids, cost and hops (room for cap
+ * entries each, any may be NULL) get the first min(cap, count) entries; with all three NULL the call returns the
+ * count only.  info: source = the field's, reached = the count, ms_* / host_syncs of this call; may be NULL.
+ * The retained solve and its staleness are trg_engine_field_routes' (below), with the same two messages.
+ * TRG_ERR_INVALID_ARG also for a field out of range and cap < 0. */
+TrgStatus trg_engine_field_reached(TrgEngine *e, int32_t field,
+    int32_t *node_ids, float *cost, int32_t *hops,   /* room for cap each, any may be NULL */
+    int32_t cap, int32_t *n_out, TrgFieldInfo *info);
 /* Routes: the paths behind the keys of the LAST cost-field solve, walked on the device (DESIGN.md section 2,
  * "Routes").  A successful trg_engine_cost_field / _batch solve stays on the device; a new solve replaces it,
  * and init_graph, update_graph (from its start, also when it fails), load_json, a reset of the global graph

@@ -1,12 +1,23 @@
 // Part of trg_engine.cpp (included at file scope): the cost field of the global graph -- the least (cost, hops)
 // key from one node to every node, on the device, for up to TRG_FIELD_BATCH_MAX sources in one solve (kernels:
 // trg_field.hip; an extension, the reference has no such call) -- and its C ABI entries.  One solver: the
-// single-source entry is its m == 1 call.
+// single-source entry is its m == 1 call, the batch entry the bounded one's call without budgets or a settle mode.
 
 namespace {
 
 // rounds enqueued between two looks at the pinned "work left" word
 constexpr int FIELD_BATCH = 32;
+
+inline uint32_t float_bits(float f) {
+  uint32_t b;
+  memcpy(&b, &f, sizeof b);
+  return b;
+}
+inline float bits_float(uint32_t b) {
+  float f;
+  memcpy(&f, &b, sizeof f);
+  return f;
+}
 
 // device buffers of the cost field, owned by the engine
 struct FieldBufs {
@@ -33,6 +44,8 @@ struct FieldBufs {
     bool dev_csr = false;    // F's CSR is the device build's (gone stale when an update_graph begins)
   } last;
   DevArr route_field, route_target, route_len, route_off, route_ids, route_info;
+  DevArr list_counts, list_off, list_tmp, list_ids, list_cost, list_hops;  // trg_engine_field_reached
+  Pinned<unsigned> h_bound;  // per field, as cost bits (bounded solves)
   Pinned<FieldState> h_state;
   Pinned<FieldEdgeStats> h_stats;
   Pinned<int> h_reached;  // per field
@@ -62,6 +75,9 @@ struct FieldRequest {
   int32_t *hops_at;
   int32_t *sources_out, *reached_out;  // m
   bool resolve_only;          // nothing but sources_out is wanted: no solve
+  const float *budget;        // m, or nullptr: +inf each
+  int32_t settle;             // TRG_FIELD_SETTLE_*, over `targets`
+  float *bound_out;           // m, may be nullptr
 };
 
 // an allocation that fails is a matter of capacity
@@ -111,12 +127,23 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
   if (gather && (long long)m * rq.n_targets > (long long)INT_MAX - (1 << 20))
     return e->fail(TRG_ERR_CAPACITY, "cost field: too many targets");
   const int N = (int)N64;
+  // A bounded solve ("Bounded fields"): some budget below +inf, or a settle mode.  Without
+  // either, the launches below are those of a solve that knows nothing of bounds.
+  FieldBounds budgets;
+  bool bounded = rq.settle != TRG_FIELD_SETTLE_NONE;
+  const uint32_t inf_bits = float_bits(std::numeric_limits<float>::infinity());
+  for (int k = 0; k < m; ++k) {
+    const float b = rq.budget ? rq.budget[k] : std::numeric_limits<float>::infinity();
+    budgets.bits[k] = b == 0.0f ? 0u : float_bits(b);  // (-0.0 orders as +0.0)
+    bounded = bounded || budgets.bits[k] != inf_bits;
+  }
   if (!e->field) e->field.reset(new FieldBufs());
   FieldBufs &fb = *e->field;
   fb.last = FieldBufs::Last{};  // from here on the work arrays change
   HIPCHK(e, fb.h_state.ensure(1));
   HIPCHK(e, fb.h_stats.ensure(1));
   HIPCHK(e, fb.h_reached.ensure(TRG_FIELD_BATCH_MAX));
+  HIPCHK(e, fb.h_bound.ensure(TRG_FIELD_BATCH_MAX));
   HIPCHK(e, fb.t0.create());
   HIPCHK(e, fb.t1.create());
   hipStream_t s = e->s_main;
@@ -208,11 +235,25 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
   const float delta = fb.mean_cost > 0.0 ? (float)(e->field_delta_scale * fb.mean_cost) : 0.0f;
   const long long cap = 4LL * N + 64;
   int rounds = 0;
+  const bool settle = rq.settle != TRG_FIELD_SETTLE_NONE;
+  if (settle) {  // the settle step reads the targets during pass 1
+    if ((st = grow(fb.targets, (size_t)rq.n_targets * sizeof(int))) != TRG_OK) return st;
+    HIPCHK(e, hipMemcpyAsync(fb.targets.p, rq.targets, (size_t)rq.n_targets * sizeof(int), hipMemcpyHostToDevice, s));
+  }
+  if (bounded) launch_field_bounds(F, budgets, s);
   for (int pass = 0; pass < 2; ++pass) {
+    // the bounds act in pass 1 only: it ends with the keys above them removed, and no pass-2 extension matches
+    // the tight word of a node without a key
+    const bool under_bounds = bounded && pass == 0;
     F.tight = pass ? (const unsigned *)fb.cost.p : nullptr;
     launch_field_init(F, sources, delta, s);
     for (int round = 0;;) {
-      for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s);
+      for (int i = 0; i < FIELD_BATCH; ++i, ++round) {
+        if (under_bounds)
+          launch_field_round_bounded(F, round, (const int *)fb.targets.p, rq.n_targets, rq.settle, s);
+        else
+          launch_field_round(F, round, s);
+      }
       HIPCHK(e, hipGetLastError());
       HIPCHK(e, hipMemcpyAsync(fb.h_state, &F.ctrl->s, sizeof(FieldState), hipMemcpyDeviceToHost, s));
       HIPCHK(e, hipStreamSynchronize(s));
@@ -222,6 +263,10 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
       if (fb.h_state->rounds >= cap) return e->fail(TRG_ERR_DEVICE, "cost field did not converge");
     }
     rounds += fb.h_state->rounds;
+    if (under_bounds) {
+      launch_field_trim(F, s);
+      HIPCHK(e, hipMemcpyAsync(fb.h_bound, F.ctrl->bound, (size_t)m * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    }
     if (pass == 0) launch_field_cost_bits(F, (unsigned *)fb.cost.p, s);
   }
   launch_field_finish(F, (float *)fb.cost.p, (int *)fb.hops.p, rq.parent != nullptr, s);
@@ -230,7 +275,7 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
     if ((st = grow(fb.targets, nt * sizeof(int))) != TRG_OK) return st;
     if ((st = grow(fb.cost_at, nat * sizeof(float))) != TRG_OK) return st;
     if ((st = grow(fb.hops_at, nat * sizeof(int))) != TRG_OK) return st;
-    HIPCHK(e, hipMemcpyAsync(fb.targets.p, rq.targets, nt * sizeof(int), hipMemcpyHostToDevice, s));
+    if (!settle) HIPCHK(e, hipMemcpyAsync(fb.targets.p, rq.targets, nt * sizeof(int), hipMemcpyHostToDevice, s));
     launch_field_gather(F, (const int *)fb.targets.p, rq.n_targets, rq.cost_at ? (float *)fb.cost_at.p : nullptr,
                         rq.hops_at ? (int *)fb.hops_at.p : nullptr, s);
   }
@@ -256,6 +301,7 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
     reached += fb.h_reached[k];
     if (rq.sources_out) rq.sources_out[k] = sources.id[k];
     if (rq.reached_out) rq.reached_out[k] = fb.h_reached[k];
+    if (rq.bound_out) rq.bound_out[k] = bits_float(bounded ? fb.h_bound[k] : inf_bits);
   }
   info->source = sources.id[0];
   info->reached = (int32_t)reached;
@@ -409,6 +455,64 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   return TRG_OK;
 }
 
+// The reached list of one field of the retained solve: count, scan, emit on the device; the count comes back
+// first, then as many entries as were written.
+TrgStatus field_reached(TrgEngine *e, int32_t field, int32_t *node_ids, float *cost, int32_t *hops, int32_t cap,
+                        int32_t *n_out, TrgFieldInfo *info) {
+  const auto t_total = Clock::now();
+  if (cap < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field reached: cap < 0");
+  if (!e->field || e->field->last.version == 0)
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field reached: no cost-field solve is retained (solve first)");
+  FieldBufs &fb = *e->field;
+  if (fb.last.version != e->graph_version || (fb.last.dev_csr && !e->dev_csr_valid))
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field reached: the retained solve is of an earlier graph (solve again)");
+  const FieldDev &F = fb.last.F;
+  if (field < 0 || field >= F.m)
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field reached: field " + std::to_string(field) +
+                                            " out of range (the solve has " + std::to_string(F.m) + ")");
+  const bool want = cap > 0 && (node_ids || cost || hops);
+  const int room = want ? std::min<int>(cap, F.V) : 0;
+  const size_t nb = ((size_t)F.V + 255) / 256;
+  TrgStatus st;
+  if ((st = field_grow(e, fb.list_counts, (nb + 1) * sizeof(int))) != TRG_OK) return st;
+  if ((st = field_grow(e, fb.list_off, (nb + 1) * sizeof(int))) != TRG_OK) return st;
+  if ((st = field_grow(e, fb.list_tmp, (nb / 2048 + 8) * sizeof(int))) != TRG_OK) return st;
+  if (node_ids && (st = field_grow(e, fb.list_ids, ((size_t)room + 4) * sizeof(int))) != TRG_OK) return st;
+  if (cost && (st = field_grow(e, fb.list_cost, ((size_t)room + 4) * sizeof(float))) != TRG_OK) return st;
+  if (hops && (st = field_grow(e, fb.list_hops, ((size_t)room + 4) * sizeof(int))) != TRG_OK) return st;
+  HIPCHK(e, fb.t0.create());
+  HIPCHK(e, fb.t1.create());
+  hipStream_t s = e->s_main;
+  int syncs = 0;
+  HIPCHK(e, hipEventRecord(fb.t0, s));
+  launch_field_reached_list(F, field, (int *)fb.list_counts.p, (int *)fb.list_off.p, (int *)fb.list_tmp.p, room,
+                            node_ids ? (int *)fb.list_ids.p : nullptr, cost ? (float *)fb.list_cost.p : nullptr,
+                            hops ? (int *)fb.list_hops.p : nullptr, s);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipEventRecord(fb.t1, s));
+  int total = 0;
+  HIPCHK(e, hipMemcpyAsync(&total, (const int *)fb.list_off.p + nb, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  syncs++;
+  const size_t n = (size_t)std::min(total, room);
+  if (n > 0) {
+    if (node_ids) HIPCHK(e, hipMemcpyAsync(node_ids, fb.list_ids.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (cost) HIPCHK(e, hipMemcpyAsync(cost, fb.list_cost.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (hops) HIPCHK(e, hipMemcpyAsync(hops, fb.list_hops.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    syncs++;
+  }
+  if (n_out) *n_out = total;
+  float ms_dev = 0.0f;
+  HIPCHK(e, hipEventElapsedTime(&ms_dev, fb.t0, fb.t1));
+  info->source = fb.last.sources.id[field];
+  info->reached = total;
+  info->host_syncs = syncs;
+  info->ms_device = ms_dev;
+  info->ms_total = ms_since(t_total);
+  return TRG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -435,9 +539,19 @@ TrgStatus trg_engine_cost_field_batch(TrgEngine *e, int32_t m, const int32_t *so
                                       float *cost, int32_t *hops, int32_t *parent, const int32_t *targets,
                                       int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *sources_out,
                                       int32_t *reached_out, TrgFieldInfo *info) {
+  return trg_engine_cost_field_bounded(e, m, source_ids, source_xy, nullptr, TRG_FIELD_SETTLE_NONE, cost, hops, parent,
+                                       targets, n_targets, cost_at, hops_at, sources_out, reached_out, nullptr, info);
+}
+
+TrgStatus trg_engine_cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *source_ids, const float *source_xy,
+                                        const float *budget, int32_t settle, float *cost, int32_t *hops,
+                                        int32_t *parent, const int32_t *targets, int32_t n_targets, float *cost_at,
+                                        int32_t *hops_at, int32_t *sources_out, int32_t *reached_out,
+                                        float *bound_out, TrgFieldInfo *info) {
   REQUIRE_DEVICE(e);
   // every output NULL but sources_out: the caller wants the sources resolved, nothing solved
-  const bool resolve_only = sources_out && !cost && !hops && !parent && !cost_at && !hops_at && !reached_out && !info;
+  const bool resolve_only =
+      sources_out && !cost && !hops && !parent && !cost_at && !hops_at && !reached_out && !bound_out && !info;
   TrgFieldInfo local{};
   if (!info) info = &local;
   *info = TrgFieldInfo{};
@@ -451,9 +565,36 @@ TrgStatus trg_engine_cost_field_batch(TrgEngine *e, int32_t m, const int32_t *so
     for (int k = 0; k < m; ++k)
       if (source_ids[k] < -1)
         return e->fail(TRG_ERR_INVALID_ARG, "cost field: source " + std::to_string(k) + " out of range");
+  if (budget)
+    for (int k = 0; k < m; ++k)
+      if (!(budget[k] >= 0.0f))
+        return e->fail(TRG_ERR_INVALID_ARG, "cost field: the budget of field " + std::to_string(k) +
+                                                " is negative or not a number");
+  if (settle != TRG_FIELD_SETTLE_NONE && settle != TRG_FIELD_SETTLE_ANY && settle != TRG_FIELD_SETTLE_ALL)
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field: settle mode " + std::to_string(settle) + " (0..2)");
+  if (settle != TRG_FIELD_SETTLE_NONE && (n_targets == 0 || !targets))
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field: settle mode " + std::to_string(settle) + " needs targets");
   FieldRequest rq{m, source_ids, source_xy, cost, hops, parent, targets, n_targets, cost_at, hops_at, sources_out,
-                  reached_out, resolve_only};
+                  reached_out, resolve_only, budget, settle, bound_out};
   return field_guarded(e, rq, info);
+}
+
+TrgStatus trg_engine_field_reached(TrgEngine *e, int32_t field, int32_t *node_ids, float *cost, int32_t *hops,
+                                   int32_t cap, int32_t *n_out, TrgFieldInfo *info) {
+  REQUIRE_DEVICE(e);
+  TrgFieldInfo local{};
+  if (!info) info = &local;
+  *info = TrgFieldInfo{};
+  info->source = -1;
+  try {
+    return field_reached(e, field, node_ids, cost, hops, cap, n_out, info);
+  } catch (const std::bad_alloc &) {
+    return e->fail(TRG_ERR_CAPACITY, "cost field reached: out of host memory");
+  } catch (const std::exception &x) {
+    return e->fail(TRG_ERR_DEVICE, std::string("cost field reached: ") + x.what());
+  } catch (...) {
+    return e->fail(TRG_ERR_DEVICE, "cost field reached: unknown exception");
+  }
 }
 
 TrgStatus trg_engine_field_routes(TrgEngine *e, int32_t n_routes, const int32_t *route_field,

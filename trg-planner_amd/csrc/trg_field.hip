@@ -29,6 +29,12 @@
 // drops both.  The other kernels either never look inside an item (far min, far split, cost bits) or take the
 // field from blockIdx.y.
 //
+// Bounded solves ("Bounded fields"): field k is truncated at a bound, its budget lowered
+// by the settle step once its targets are settled -- every node dearer than the bound comes out unreached, every
+// other node as in the full field.  Pass 1 runs the BOUNDED instantiations of the round kernels with the settle
+// step between far min and far split, and ends with the keys above the bounds removed; pass 2 and everything after
+// it are the plain kernels.  A solve without bounds launches none of this.
+//
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"
 
@@ -78,6 +84,11 @@ __device__ __forceinline__ unsigned next_threshold(unsigned fminb, float delta) 
   const float fmin = __uint_as_float(fminb);
   const float t = fmin + delta;
   return t > fmin ? __float_as_uint(t) : fminb + 1u;
+}
+
+// (bounded solves) the bound of the field that item i belongs to, as cost bits
+__device__ __forceinline__ unsigned field_bound(const FieldDev &F, int i) {
+  return F.ctrl->bound[(unsigned)i / (unsigned)F.V];
 }
 
 __global__ __launch_bounds__(THREADS) void k_field_edge_cost(const int *__restrict__ col, const float *__restrict__ w,
@@ -149,7 +160,9 @@ __global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources
 
 // Expand the near queue of this round: one 16-lane group per queued item, four per wave.
 // MULTI: more than one field (an item is decoded into its field's first item and its node); else item == node.
-template <bool MULTI>
+// BOUNDED: pass 1 of a bounded solve -- an item above its field's bound is not expanded (it was queued before the
+// settle step lowered the bound), an extension above the bound is neither written nor pushed.
+template <bool MULTI, bool BOUNDED>
 __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, int stamp) {
   const int N = MULTI ? F.N : F.V;
   const int n = min(F.ctrl->c.n[par], N);  // (past N only after an overflow, which the host then reports)
@@ -172,16 +185,22 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
     unsigned long long ku = 0;
     int k = 0, kend = 0;
     int fbase = 0;  // the first item of the queued item's field
+    unsigned bnd = 0;  // (BOUNDED) that field's bound
     if (item < n) {
       const int iu = q_cur[item];
       ku = F.key[iu];
       int u = iu;
+      int f = 0;
       if constexpr (MULTI) {
-        fbase = (int)((unsigned)iu / (unsigned)F.V) * F.V;
+        f = (int)((unsigned)iu / (unsigned)F.V);
+        fbase = f * F.V;
         u = iu - fbase;
       }
-      k = F.rowptr[u] + sub;
-      kend = F.rowptr[u + 1];
+      if constexpr (BOUNDED) bnd = F.ctrl->bound[f];
+      if (!BOUNDED || key_cost_bits(ku) <= bnd) {
+        k = F.rowptr[u] + sub;
+        kend = F.rowptr[u + 1];
+      }
     }
     for (;; k += GROUP) {
       const bool act = k < kend;
@@ -195,7 +214,8 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
           if constexpr (MULTI) v += fbase;  // the target item: an edge never leaves its field
           const unsigned long long nk = key_extend(ku, c);
           const bool tight = !F.tight || (unsigned)(nk >> 32) == F.tight[v];  // (pass 2: tight edges only)
-          if (tight && nk < F.key[v]) {  // plain load first: the atomic only on an improvement
+          const bool within = !BOUNDED || key_cost_bits(nk) <= bnd;
+          if (tight && within && nk < F.key[v]) {  // plain load first: the atomic only on an improvement
             const unsigned long long old = atomicMin(&F.key[v], nk);
             if (nk < old) {
               if (key_cost_bits(nk) < thr)
@@ -222,6 +242,9 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
 
 // The least live cost of the far pile, over all fields (live: not below the threshold; an entry below it was
 // pushed near and expanded since) -- only when this round's relaxation pushed nothing near in any field.
+// BOUNDED: an entry above its field's bound is not live either -- else a field that the settle step stopped would
+// keep opening buckets of nothing until its pile drained.
+template <bool BOUNDED>
 __global__ __launch_bounds__(THREADS) void k_field_far_min(FieldDev F, int par) {
   if (F.ctrl->c.n[par ^ 1] != 0) return;
   const int fs = F.ctrl->s.far_sel;
@@ -232,8 +255,9 @@ __global__ __launch_bounds__(THREADS) void k_field_far_min(FieldDev F, int par) 
   const int n_iter = (nf + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
   for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
     if (i < nf) {
-      const unsigned c = key_cost_bits(F.key[far[i]]);
-      if (c >= thr) best = min(best, c);
+      const int v = far[i];
+      const unsigned c = key_cost_bits(F.key[v]);
+      if (c >= thr && (!BOUNDED || c <= field_bound(F, v))) best = min(best, c);
     }
   }
 #pragma unroll
@@ -244,6 +268,7 @@ __global__ __launch_bounds__(THREADS) void k_field_far_min(FieldDev F, int par) 
 // Open the next bucket: live far entries below the new threshold go to the (empty) next near queue, the
 // rest to the other far pile, stamped with the next phase.
 // (Whether to split is told by fmin, which only k_field_far_min sets: the near-queue size changes here.)
+template <bool BOUNDED>
 __global__ __launch_bounds__(THREADS) void k_field_far_split(FieldDev F, int par) {
   const unsigned fminb = F.ctrl->c.fmin;
   if (fminb == ~0u) return;
@@ -263,7 +288,7 @@ __global__ __launch_bounds__(THREADS) void k_field_far_split(FieldDev F, int par
     if (i < nf) {
       v = far[i];
       const unsigned c = key_cost_bits(F.key[v]);
-      if (c >= thr) {
+      if (c >= thr && (!BOUNDED || c <= field_bound(F, v))) {
         to_near = c < thr_new;  // (thr_new > fmin: the least live cost always makes progress, +inf too)
         to_far = !to_near;
       }
@@ -283,6 +308,9 @@ __global__ __launch_bounds__(THREADS) void k_field_far_split(FieldDev F, int par
 }
 
 // One thread: the next near queue becomes the current one; a split switches the far pile and the bucket.
+// BOUNDED: the least live far cost was found before the settle step ran, so a split may have moved nothing near
+// (that cost's field was stopped) and yet have left live entries of other fields in the far pile: they are work.
+template <bool BOUNDED>
 __global__ void k_field_round_end(FieldDev F, int par) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   FieldCounters &c = F.ctrl->c;
@@ -300,7 +328,110 @@ __global__ void k_field_round_end(FieldDev F, int par) {
   }
   if (worked) s.rounds++;
   s.work = c.n[par ^ 1];
+  if constexpr (BOUNDED) s.work += c.nfar[s.far_sel];
   s.overflow = c.overflow;
+}
+
+// ---- bounded fields ("Bounded fields") ---------------------------------------------------
+
+__global__ void k_field_bounds(FieldDev F, FieldBounds B) {
+  if (blockIdx.x == 0 && threadIdx.x < F.m) F.ctrl->bound[threadIdx.x] = B.bits[threadIdx.x];
+}
+
+// The settle step, one block per field, between k_field_far_min and k_field_far_split of a round that pushed
+// nothing near: the near queue is empty, so every key below the least live far cost fmin (every key, when nothing
+// is live: convergence) is final, and every other key of the union lies at or above fmin.  A target is settled
+// when it has a key below fmin.  ANY: the least cost of the settled targets is the least over all targets.  ALL,
+// when every target is settled: their greatest cost.  The field's bound drops to that cost; only this block
+// writes the word, and no other kernel runs beside it.
+__global__ __launch_bounds__(THREADS) void k_field_settle(FieldDev F, int par, const int *__restrict__ targets,
+                                                          int n_t, int mode) {
+  if (F.ctrl->c.n[par ^ 1] != 0) return;
+  __shared__ unsigned s_lo[THREADS / WAVE], s_hi[THREADS / WAVE];
+  __shared__ int s_unmet[THREADS / WAVE];
+  const unsigned fmin = F.ctrl->c.fmin;
+  const int fbase = blockIdx.x * F.V;
+  unsigned lo = ~0u, hi = 0u;
+  int unmet = 0;
+  for (int j = threadIdx.x; j < n_t; j += blockDim.x) {
+    const unsigned long long k = F.key[fbase + targets[j]];
+    const unsigned c = key_cost_bits(k);
+    if (k != FIELD_KEY_NONE && c < fmin) {
+      lo = min(lo, c);
+      hi = max(hi, c);
+    } else {
+      unmet = 1;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    lo = min(lo, (unsigned)__shfl_xor((int)lo, m));
+    hi = max(hi, (unsigned)__shfl_xor((int)hi, m));
+    unmet |= __shfl_xor(unmet, m);
+  }
+  if (lane_id() == 0) {
+    s_lo[threadIdx.x / WAVE] = lo;
+    s_hi[threadIdx.x / WAVE] = hi;
+    s_unmet[threadIdx.x / WAVE] = unmet;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < THREADS / WAVE; ++w) {
+      lo = min(lo, s_lo[w]);
+      hi = max(hi, s_hi[w]);
+      unmet |= s_unmet[w];
+    }
+    unsigned b = ~0u;
+    if (mode == FIELD_SETTLE_ANY && lo != ~0u) b = lo;
+    if (mode == FIELD_SETTLE_ALL && !unmet && n_t > 0) b = hi;
+    if (b < F.ctrl->bound[blockIdx.x]) F.ctrl->bound[blockIdx.x] = b;
+  }
+}
+
+// grid.y = field: after pass 1, a key above its field's bound is no key
+__global__ __launch_bounds__(THREADS) void k_field_trim(FieldDev F) {
+  const int fbase = blockIdx.y * F.V;
+  const unsigned bnd = F.ctrl->bound[blockIdx.y];
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < F.V; v += gridDim.x * blockDim.x) {
+    const unsigned long long k = F.key[fbase + v];
+    if (k != FIELD_KEY_NONE && key_cost_bits(k) > bnd) F.key[fbase + v] = FIELD_KEY_NONE;
+  }
+}
+
+// The reached list of one field: block b covers the nodes [b * THREADS, (b + 1) * THREADS).  Count per block, an
+// exclusive scan of the counts (launch_exclusive_scan), then every block writes its nodes from its offset on, in
+// id order: a wave's lanes by the ballot's prefix, the block's waves by the sums of the waves before.
+__global__ __launch_bounds__(THREADS) void k_field_list_count(FieldDev F, int field, int *counts) {
+  __shared__ int s_n[THREADS / WAVE];
+  const int v = blockIdx.x * THREADS + threadIdx.x;
+  const bool has = v < F.V && F.key[field * F.V + v] != FIELD_KEY_NONE;
+  const unsigned long long m = ballot(has);
+  if (lane_id() == 0) s_n[threadIdx.x / WAVE] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int n = 0;
+    for (int w = 0; w < THREADS / WAVE; ++w) n += s_n[w];
+    counts[blockIdx.x] = n;
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void k_field_list_emit(FieldDev F, int field, const int *__restrict__ offsets,
+                                                             int cap, int *ids, float *cost, int *hops) {
+  __shared__ int s_n[THREADS / WAVE];
+  const int v = blockIdx.x * THREADS + threadIdx.x;
+  unsigned long long k = FIELD_KEY_NONE;
+  if (v < F.V) k = F.key[field * F.V + v];
+  const bool has = k != FIELD_KEY_NONE;
+  const unsigned long long m = ballot(has);
+  if (lane_id() == 0) s_n[threadIdx.x / WAVE] = __popcll(m);
+  __syncthreads();
+  int pos = offsets[blockIdx.x] + __popcll(m & ((1ull << lane_id()) - 1ull));
+  for (int w = 0; w < (int)threadIdx.x / WAVE; ++w) pos += s_n[w];
+  if (has && pos < cap) {
+    if (ids) ids[pos] = v;
+    if (cost) cost[pos] = key_cost(k);
+    if (hops) hops[pos] = (int)(unsigned)k;
+  }
 }
 
 // Parents: the smallest u with an edge u -> v whose extension of key[u] is key[v], in each field (grid.y).
@@ -477,12 +608,43 @@ void launch_field_round(const FieldDev &F, int round, hipStream_t s) {
   const int par = round & 1;
   const dim3 relax_grid(field_blocks((long long)F.N * GROUP, THREADS));
   if (F.m == 1)
-    hipLaunchKernelGGL(k_field_relax<false>, relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+    hipLaunchKernelGGL((k_field_relax<false, false>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
   else
-    hipLaunchKernelGGL(k_field_relax<true>, relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
-  hipLaunchKernelGGL(k_field_far_min, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
-  hipLaunchKernelGGL(k_field_far_split, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
-  hipLaunchKernelGGL(k_field_round_end, dim3(1), dim3(64), 0, s, F, par);
+    hipLaunchKernelGGL((k_field_relax<true, false>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+  hipLaunchKernelGGL(k_field_far_min<false>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
+  hipLaunchKernelGGL(k_field_far_split<false>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
+  hipLaunchKernelGGL(k_field_round_end<false>, dim3(1), dim3(64), 0, s, F, par);
+}
+
+void launch_field_bounds(const FieldDev &F, const FieldBounds &budgets, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_bounds, dim3(1), dim3(FIELD_MAX_SOURCES), 0, s, F, budgets);
+}
+
+void launch_field_round_bounded(const FieldDev &F, int round, const int *targets, int n_t, int mode, hipStream_t s) {
+  const int par = round & 1;
+  const dim3 relax_grid(field_blocks((long long)F.N * GROUP, THREADS));
+  if (F.m == 1)
+    hipLaunchKernelGGL((k_field_relax<false, true>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+  else
+    hipLaunchKernelGGL((k_field_relax<true, true>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+  hipLaunchKernelGGL(k_field_far_min<true>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
+  if (mode != FIELD_SETTLE_NONE)
+    hipLaunchKernelGGL(k_field_settle, dim3(F.m), dim3(THREADS), 0, s, F, par, targets, n_t, mode);
+  hipLaunchKernelGGL(k_field_far_split<true>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
+  hipLaunchKernelGGL(k_field_round_end<true>, dim3(1), dim3(64), 0, s, F, par);
+}
+
+void launch_field_trim(const FieldDev &F, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_trim, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F);
+}
+
+void launch_field_reached_list(const FieldDev &F, int field, int *counts, int *offsets, int *tmp, int cap, int *ids,
+                               float *cost, int *hops, hipStream_t s) {
+  const int nb = (F.V + THREADS - 1) / THREADS;
+  hipLaunchKernelGGL(k_field_list_count, dim3(nb), dim3(THREADS), 0, s, F, field, counts);
+  launch_exclusive_scan(counts, offsets, nb, tmp, s);
+  if (cap > 0 && (ids || cost || hops))
+    hipLaunchKernelGGL(k_field_list_emit, dim3(nb), dim3(THREADS), 0, s, F, field, offsets, cap, ids, cost, hops);
 }
 
 void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s) {

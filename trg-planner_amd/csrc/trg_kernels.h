@@ -410,7 +410,17 @@ struct FieldCtrl {
   FieldCounters c;
   FieldState s;
   alignas(128) int reached[FIELD_MAX_SOURCES];  // per field: items with a key
+  // Bounded solves only ("Bounded fields"): field k's bound as cost bits -- the caller's
+  // budget at first, lowered by the settle step; nothing above it is relaxed, and pass 1 ends with the keys
+  // above it removed.
+  alignas(128) unsigned bound[FIELD_MAX_SOURCES];
 };
+struct FieldBounds {
+  unsigned bits[FIELD_MAX_SOURCES];
+};
+constexpr int FIELD_SETTLE_NONE = 0;  // TRG_FIELD_SETTLE_*
+constexpr int FIELD_SETTLE_ANY = 1;
+constexpr int FIELD_SETTLE_ALL = 2;
 struct FieldSources {
   int id[FIELD_MAX_SOURCES];
 };
@@ -438,6 +448,22 @@ void launch_field_init(const FieldDev &F, const FieldSources &sources, float del
 // nothing near in ANY field, open the next bucket from the least live far cost over all fields; every
 // launch reads its sizes from F.ctrl
 void launch_field_round(const FieldDev &F, int round, hipStream_t s);
+// Bounded solves, pass 1 (pass 2 runs the plain rounds: a removed key's tight word matches no extension).
+// F.ctrl->bound[k] = budgets.bits[k], before the first round
+void launch_field_bounds(const FieldDev &F, const FieldBounds &budgets, hipStream_t s);
+// launch_field_round under the bounds: an item above its field's bound is not expanded, an extension above it
+// neither written nor pushed, a far-pile entry above it not live.  With mode ANY / ALL and n_t targets (device
+// ids), a round that opens a bucket or converges lowers the bound of every field whose targets are settled --
+// some (ANY) or all (ALL) of them have a key below the least live far cost -- to the least (greatest) of those
+// costs.
+void launch_field_round_bounded(const FieldDev &F, int round, const int *targets, int n_t, int mode, hipStream_t s);
+// after the last round of pass 1: keys above their field's bound become FIELD_KEY_NONE
+void launch_field_trim(const FieldDev &F, hipStream_t s);
+// The nodes of one field of a finished solve that have a key, in ascending id: ids / cost / hops (any may be
+// nullptr) get the first `cap` of them, offsets[(V + 255) / 256] their total.  counts: (V + 255) / 256 ints,
+// offsets one more, tmp (V / 256) / 2048 + 8.
+void launch_field_reached_list(const FieldDev &F, int field, int *counts, int *offsets, int *tmp, int cap, int *ids,
+                               float *cost, int *hops, hipStream_t s);
 // pass 1 -> pass 2: bits[item] = cost word of key[item]
 void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s);
 // parents (smallest id among the edges that realise an item's key; only if `parents`) and the outputs, m x V

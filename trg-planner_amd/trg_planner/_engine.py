@@ -102,10 +102,13 @@ EXPORTS = [
     "trg_engine_graph_sizes",
     "trg_engine_comm_unique_id", "trg_engine_comm_init", "trg_engine_comm_adopt", "trg_engine_comm_destroy",
     "trg_engine_stitch_exchange", "trg_engine_cost_field", "trg_engine_cost_field_batch",
-    "trg_engine_field_routes",
+    "trg_engine_field_routes", "trg_engine_cost_field_bounded", "trg_engine_field_reached",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
+# include/trg_engine.h: TRG_FIELD_SETTLE_*
+SETTLE_NONE, SETTLE_ANY, SETTLE_ALL = 0, 1, 2
+_SETTLE = {None: SETTLE_NONE, "any": SETTLE_ANY, "all": SETTLE_ALL}
 
 
 def build_library(force=False):
@@ -190,6 +193,9 @@ def load_library():
                                               C.POINTER(TrgFieldInfo)]
     L.trg_engine_field_routes.argtypes = [vp, C.c_int32, ip, ip, ip, ip, fp, C.c_int32, C.POINTER(TrgRouteInfo),
                                           C.POINTER(TrgFieldInfo)]
+    L.trg_engine_cost_field_bounded.argtypes = [vp, C.c_int32, ip, fp, fp, C.c_int32, fp, ip, ip, ip, C.c_int32, fp, ip,
+                                                ip, ip, fp, C.POINTER(TrgFieldInfo)]
+    L.trg_engine_field_reached.argtypes = [vp, C.c_int32, ip, fp, ip, C.c_int32, ip, C.POINTER(TrgFieldInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
     L.trg_engine_fallback_reason.restype = C.c_char_p
     _lib = L
@@ -453,9 +459,13 @@ class Engine:
             path.append(p)
         return path[::-1]
 
-    def cheapest_frontier(self, source_xy):
+    def cheapest_frontier(self, source_xy, early_exit=False):
         """The Frontier node that is cheapest to reach from `source_xy`: the least (cost, hops, id) among
-        Frontier nodes with a finite cost -> (node, cost, path ids) or None."""
+        Frontier nodes with a finite cost -> (node, cost, path ids) or None.  early_exit: the same answer from a
+        solve that stops once the cheapest Frontier node is settled (cheapest_frontiers' path with one pose)."""
+        if early_exit:
+            return self.cheapest_frontiers(np.ascontiguousarray(source_xy, dtype=np.float32).reshape(1, 2),
+                                           early_exit=True)[0]
         cost, hops, parent, info = self.cost_field(source_xy=source_xy)
         v = TrgCsrView()
         self._chk(self.L.trg_engine_export_csr(self.h, KIND_GLOBAL, C.byref(v)))
@@ -468,15 +478,22 @@ class Engine:
         best = int(ids[np.lexsort((ids, hops[ids], cost[ids]))[0]])
         return best, float(cost[best]), self.field_path(parent, best, int(info.source))
 
-    def cost_fields(self, sources_xy=None, source_ids=None, targets=None, full=True):
+    def cost_fields(self, sources_xy=None, source_ids=None, targets=None, full=True, budget=None, settle=None):
         """m cost fields in one solve on the GPU (trg_engine_cost_field_batch; each field as cost_field's).
         Field k starts at source_ids[k], or, where source_ids is None or source_ids[k] == -1, at the node
         planSafePath starts from for sources_xy[k].  -> dict: with `full`, the (m, V) arrays "cost", "hops",
         "parent"; with `targets` (node ids), the (m, n_t) arrays "cost_at", "hops_at", read on the device
         (with full=False nothing of V entries is copied back); always "sources" (m resolved nodes), "reached"
-        (m counts) and "info" (TrgFieldInfo of the whole solve)."""
+        (m counts) and "info" (TrgFieldInfo of the whole solve).
+        Bounded fields (trg_engine_cost_field_bounded; DESIGN.md section 2, "Bounded fields"): `budget`, a cost or
+        m costs, and `settle`, "any" or "all" over `targets`, truncate field k at bound[k] = min(budget[k], the least
+        ("any") or greatest ("all") cost of field k over the targets): every node dearer than the bound comes back
+        as unreached, every other node exactly as in the full field, and the solve stops early.  With either
+        given the result also has "bound" (m float32)."""
         if sources_xy is None and source_ids is None:
             raise ValueError("cost_fields needs sources_xy or source_ids")
+        if settle not in _SETTLE:
+            raise ValueError(f"cost_fields: settle {settle!r} (\"any\", \"all\" or None)")
         ids = None if source_ids is None else np.ascontiguousarray(source_ids, dtype=np.int32).reshape(-1)
         xy = None if sources_xy is None else np.ascontiguousarray(sources_xy, dtype=np.float32).reshape(-1, 2)
         m = ids.shape[0] if ids is not None else xy.shape[0]
@@ -497,20 +514,65 @@ class Engine:
         out["sources"] = np.full(m, -1, np.int32)
         out["reached"] = np.zeros(m, np.int32)
         info = TrgFieldInfo()
-        self._chk(self.L.trg_engine_cost_field_batch(
+        if budget is None and settle is None:
+            self._chk(self.L.trg_engine_cost_field_batch(
+                self.h, m, None if ids is None else _i(ids), None if xy is None else _f(xy),
+                _f(out["cost"]) if full else None, _i(out["hops"]) if full else None,
+                _i(out["parent"]) if full else None, None if tg is None else _i(tg), nt,
+                None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
+                _i(out["sources"]), _i(out["reached"]), C.byref(info)))
+            out["info"] = info
+            return out
+        bud = None
+        if budget is not None:
+            bud = np.ascontiguousarray(np.broadcast_to(np.asarray(budget, dtype=np.float32).reshape(-1), (m,)))
+        out["bound"] = np.empty(m, np.float32)
+        self._chk(self.L.trg_engine_cost_field_bounded(
             self.h, m, None if ids is None else _i(ids), None if xy is None else _f(xy),
+            None if bud is None else _f(bud), _SETTLE[settle],
             _f(out["cost"]) if full else None, _i(out["hops"]) if full else None,
             _i(out["parent"]) if full else None, None if tg is None else _i(tg), nt,
             None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
-            _i(out["sources"]), _i(out["reached"]), C.byref(info)))
+            _i(out["sources"]), _i(out["reached"]), _f(out["bound"]), C.byref(info)))
         out["info"] = info
         return out
 
-    def cost_matrix(self, nodes_or_xy):
+    def field_reached(self, field=0, cap=None, with_info=False):
+        """The nodes that field `field` of the last cost_field / cost_fields solve reached, compacted on the GPU
+        (trg_engine_field_reached) -> (ids int32 ascending, cost float32, hops int32); nothing of V entries is
+        copied back.  cap: at most that many entries (the first, by id); cap == 0 -> the count only, as an int.
+        with_info: -> (that, TrgFieldInfo of the call, whose `reached` is the full count)."""
+        n = C.c_int32(0)
+        info = TrgFieldInfo()
+        if cap is None:
+            self._chk(self.L.trg_engine_field_reached(self.h, int(field), None, None, None, 0, C.byref(n), None))
+            cap = n.value
+        elif cap == 0:
+            self._chk(self.L.trg_engine_field_reached(self.h, int(field), None, None, None, 0, C.byref(n),
+                                                      C.byref(info)))
+            return (n.value, info) if with_info else n.value
+        ids = np.empty(max(cap, 1), np.int32)
+        cost = np.empty(max(cap, 1), np.float32)
+        hops = np.empty(max(cap, 1), np.int32)
+        self._chk(self.L.trg_engine_field_reached(self.h, int(field), _i(ids), _f(cost), _i(hops), int(cap),
+                                                  C.byref(n), C.byref(info)))
+        k = min(n.value, int(cap))
+        out = (ids[:k].copy(), cost[:k].copy(), hops[:k].copy())
+        return (out, info) if with_info else out
+
+    def reachable(self, source_xy, budget, source_id=-1):
+        """What can be reached from `source_xy` (or node `source_id`) for at most `budget`: one bounded solve without
+        full outputs, then the reached list -> (ids int32 ascending, cost float32, hops int32)."""
+        r = self.cost_fields(sources_xy=None if source_xy is None else np.asarray(source_xy, np.float32).reshape(1, 2),
+                             source_ids=None if source_id == -1 else [int(source_id)], full=False, budget=budget)
+        return self.field_reached(0, cap=max(int(r["reached"][0]), 1))
+
+    def cost_matrix(self, nodes_or_xy, early_exit=False):
         """Least costs between m waypoints -> (cost (m, m) float32, hops (m, m) int32, node ids (m,)): entry
         [a, b] is from waypoint a to waypoint b.  `nodes_or_xy` is a list of node ids or an (m, 2) array of
         positions (each resolved as cost_field resolves a source).  The fields are read at the waypoints on
-        the device; more than TRG_FIELD_BATCH_MAX waypoints run in chunks of sources."""
+        the device; more than TRG_FIELD_BATCH_MAX waypoints run in chunks of sources.  early_exit: every field stops
+        once all waypoints are settled in it (settle "all"); the result is the same."""
         a = np.asarray(nodes_or_xy)
         if a.ndim == 1 and np.issubdtype(a.dtype, np.integer):
             nodes = np.ascontiguousarray(a, dtype=np.int32)
@@ -528,15 +590,18 @@ class Engine:
         cost = np.empty((m, m), np.float32)
         hops = np.empty((m, m), np.int32)
         for k0 in range(0, m, TRG_FIELD_BATCH_MAX):
-            r = self.cost_fields(source_ids=nodes[k0:k0 + TRG_FIELD_BATCH_MAX], targets=nodes, full=False)
+            r = self.cost_fields(source_ids=nodes[k0:k0 + TRG_FIELD_BATCH_MAX], targets=nodes, full=False,
+                                 settle="all" if early_exit and m else None)
             cost[k0:k0 + TRG_FIELD_BATCH_MAX] = r["cost_at"]
             hops[k0:k0 + TRG_FIELD_BATCH_MAX] = r["hops_at"]
         return cost, hops, nodes
 
-    def cheapest_frontiers(self, poses):
+    def cheapest_frontiers(self, poses, early_exit=False):
         """cheapest_frontier for every pose of `poses` (m, 2), from one batch of fields read at the Frontier
         nodes and one routes call for the chosen nodes (nothing of V entries is copied back) -> list of
-        (node, cost, path ids) or None, per pose."""
+        (node, cost, path ids) or None, per pose.  early_exit: every field stops once its cheapest Frontier node is
+        settled (settle "any": the Frontier nodes of that cost keep their keys, every dearer one reads as
+        unreached, and choose_frontier picks among the same least ones); the result is the same."""
         xy = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 2)
         v = TrgCsrView()
         self._chk(self.L.trg_engine_export_csr(self.h, KIND_GLOBAL, C.byref(v)))
@@ -546,7 +611,8 @@ class Engine:
             frontier = np.flatnonzero(state == 1).astype(np.int32)
         out = []
         for k0 in range(0, xy.shape[0], TRG_FIELD_BATCH_MAX):
-            r = self.cost_fields(sources_xy=xy[k0:k0 + TRG_FIELD_BATCH_MAX], targets=frontier, full=False)
+            r = self.cost_fields(sources_xy=xy[k0:k0 + TRG_FIELD_BATCH_MAX], targets=frontier, full=False,
+                                 settle="any" if early_exit and frontier.size else None)
             picks = [choose_frontier(frontier, r["cost_at"][k], r["hops_at"][k]) for k in range(r["sources"].shape[0])]
             chosen = [(k, p) for k, p in enumerate(picks) if p is not None]
             routes = self.routes([k for k, _ in chosen], [p[0] for _, p in chosen], xyz=False,
@@ -590,14 +656,17 @@ class Engine:
             out.append((ids[a:b].copy(), None if pts is None else pts[a:b].copy(), one))
         return (out, info) if with_info else out
 
-    def plan_many(self, start_xy, goals_xy):
+    def plan_many(self, start_xy, goals_xy, early_exit=False):
         """Paths from one start to many goals from ONE cost field: the field from the node planSafePath starts
         from for `start_xy`, every goal of `goals_xy` (n, 2) resolved to a node the same way, one routes call
         -> list of (path xyz float32 (k, 3), TrgRouteInfo) per goal; an unreachable goal gives an empty path and
         num_nodes == 0.  Each path is the least fp32 fold of edge costs to its goal node (cost_field's
-        semantics), not planSafePath's A* result."""
+        semantics), not planSafePath's A* result.  early_exit: the field stops once every goal node is settled
+        (settle "all"); the result is the same."""
         goals = np.ascontiguousarray(goals_xy, dtype=np.float32).reshape(-1, 2)
-        self.cost_fields(sources_xy=np.ascontiguousarray(start_xy, dtype=np.float32).reshape(1, 2), full=False)
+        start = np.ascontiguousarray(start_xy, dtype=np.float32).reshape(1, 2)
+        if not (early_exit and goals.shape[0]):
+            self.cost_fields(sources_xy=start, full=False)
         nodes = np.empty(goals.shape[0], np.int32)
         for k0 in range(0, goals.shape[0], TRG_FIELD_BATCH_MAX):
             part = np.ascontiguousarray(goals[k0:k0 + TRG_FIELD_BATCH_MAX])
@@ -605,6 +674,8 @@ class Engine:
             self._chk(self.L.trg_engine_cost_field_batch(self.h, part.shape[0], None, _f(part), None, None, None,
                                                          None, 0, None, None, _i(got), None, None))
             nodes[k0:k0 + TRG_FIELD_BATCH_MAX] = got
+        if early_exit and goals.shape[0]:  # (the goals are the settle targets: resolved first)
+            self.cost_fields(sources_xy=start, targets=nodes, full=False, settle="all")
         return [(pts, one) for _, pts, one in self.routes(np.zeros(nodes.shape[0], np.int32), nodes)]
 
     def check_reached(self, pos2d):
