@@ -13,7 +13,6 @@ import pytest
 
 import field_graphs as fg
 import field_ref
-from test_field_reference import _py_field
 
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -49,7 +48,7 @@ def test_reference_matches_python_on_families(ref, name):
         st, cost, hops, parent = field_ref.field(ref, *g[:5], 3.0, src)
         assert st == 0
         with np.errstate(over="ignore"):
-            pc, ph, pp = _py_field(V, *g[:5], 3.0, src)
+            pc, ph, pp = field_ref.py_field(V, *g[:5], 3.0, src)
         assert np.array_equal(cost.view(np.uint32), pc.view(np.uint32)), (name, src)
         assert np.array_equal(hops, ph), (name, src)
         assert np.array_equal(parent, pp), (name, src)

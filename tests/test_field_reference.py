@@ -9,41 +9,6 @@ import field_ref
 from field_graphs import random_graph as _random_graph
 
 F32 = np.float32
-INVALID = -1
-
-
-def _py_field(V, rowptr, col, w, dist, state, sf, src):
-    """The definition, restated apart from any Dijkstra: cost = the least fp32 fold over all walks (a
-    Bellman-Ford on the cost alone: fl(a + c) is monotone in a); hops = the BFS depth of the tight subgraph
-    (edges with fl(cost[u] + c) == cost[v]); parent = the smallest tight u with hops[u] + 1 == hops[v]."""
-    sf = F32(sf)
-    ec = [(sf * F32(w[k]) + F32(1.0)) * F32(dist[k]) for k in range(len(col))]
-    edges = [(u, int(col[k]), ec[k]) for u in range(V) for k in range(rowptr[u], rowptr[u + 1])
-             if state[int(col[k])] != INVALID]
-    cost = [None] * V
-    cost[src] = F32(0.0)
-    changed = True
-    while changed:
-        changed = False
-        for u, v, c in edges:
-            if cost[u] is not None and (cost[v] is None or F32(cost[u] + c) < cost[v]):
-                cost[v] = F32(cost[u] + c)
-                changed = True
-    tight = [(u, v) for u, v, c in edges if cost[u] is not None and F32(cost[u] + c) == cost[v]]
-    hops = [-1] * V
-    hops[src] = 0
-    level = [src]
-    while level:
-        nxt = sorted({v for u, v in tight if u in level and hops[v] < 0})
-        for v in nxt:
-            hops[v] = hops[level[0]] + 1
-        level = nxt
-    parent = [-1] * V
-    for u, v in tight:
-        if v != src and hops[u] + 1 == hops[v] and (parent[v] < 0 or u < parent[v]):
-            parent[v] = u
-    cost = np.array([np.inf if c is None else c for c in cost], np.float32)
-    return cost, np.array(hops, np.int32), np.array(parent, np.int32)
 
 
 @pytest.fixture(scope="module")
@@ -60,7 +25,7 @@ def test_reference_matches_python(ref, seed):
     for src in (0, int(rng.integers(0, V)), V - 1):
         st, cost, hops, parent = field_ref.field(ref, rowptr, col, w, d, state, sf, src)
         assert st == 0
-        pc, ph, pp = _py_field(V, rowptr, col, w, d, state, sf, src)
+        pc, ph, pp = field_ref.py_field(V, rowptr, col, w, d, state, sf, src)
         assert np.array_equal(cost.view(np.uint32), pc.view(np.uint32)), (seed, src)
         assert np.array_equal(hops, ph), (seed, src)
         assert np.array_equal(parent, pp), (seed, src)

@@ -27,7 +27,7 @@ def _sha(a, dt):
 def test_c3_fullsize_against_oracle_digest(synth):
     import trg_planner
     from conftest import weight_report
-    from test_gpu_scale import _invariants
+    from graph_support import graph_invariants
     dg = json.load(open(os.path.join(GOLD, "c3_digest.json")))
     ws = np.load(os.path.join(GOLD, "c3_w_sample.npz"))
     nx, ny = 3200, 3125
@@ -70,4 +70,4 @@ def test_c3_fullsize_against_oracle_digest(synth):
     wd = json.load(open(os.path.join(GOLD, "c3_witness_digest.json")))
     assert (g.V, g.E) == (wd["V"], wd["E"])
     assert _sha(g.w, np.float32) == wd["w_sha256_fp64_witness"]
-    _invariants(g, prm["expand_dist"])
+    graph_invariants(g, prm["expand_dist"])

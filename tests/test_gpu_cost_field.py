@@ -1,25 +1,18 @@
 """GPU: the cost field (trg_engine_cost_field, Engine.cost_field) against the host Dijkstra of
 tests/cpp/field_reference.cpp on the same (cost, hops) key: cost (as bits), hops and parent equal, exactly.
 Device-built graphs, host replay + updateGraph (the upload path and the graph_version cache), hand-written
-JSON graphs with the error cases, agreement with planSafePath, and the C3 graph at full size."""
-import json
-
+JSON graphs with the error cases, agreement with planSafePath, the C3 graph at full size, and the pinned counts of
+host waits and rounds."""
 import numpy as np
 import pytest
 
+import field_graphs as fg
 import field_ref
+from field_support import MOUNTAIN, load_graph, ref, write_graph  # noqa: F401 (ref: a fixture)
+from graph_support import obs_crop
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-MOUNTAIN = dict(expand_dist=0.6, robot_size=0.3, sample_num=7, height_threshold=0.16, collision_threshold=0.1,
-                update_collision_threshold=0.5, safety_factor=3.0, goal_tolerance=0.8)
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return field_ref.compile_reference(tmp_path_factory.mktemp("field_ref"))
-
-
 def _check_against_reference(ref, e, g, src, cost, hops, parent, sf=3.0):
     st, rc, rh, rp = field_ref.field_of_graph(ref, g, sf, src)
     assert st == 0
@@ -74,7 +67,6 @@ def test_cost_field_device_built(ref, mountain_small):
 
 def test_cost_field_host_replay_and_updates(ref, mountain_gentle):
     import trg_planner
-    from test_gpu_update import _obs_crop
     prm = dict(MOUNTAIN, update_collision_threshold=0.2)
     e = trg_planner.Engine(**prm)
     e.set_sampler(5, 16)
@@ -87,7 +79,7 @@ def test_cost_field_host_replay_and_updates(ref, mountain_gentle):
     sizes = {g.V}
     frontier_seen = False
     for pose in [(12.0, 12.0), (13.0, 12.5), (14.0, 13.0)]:
-        obs = _obs_crop(mountain_gentle, pose, 4.0, box=(pose[0] + 2.0, pose[1] + 1.0, 0.6))
+        obs = obs_crop(mountain_gentle, pose, 4.0, box=(pose[0] + 2.0, pose[1] + 1.0, 0.6))
         e.set_local_map(pose, obs)
         e.update_graph()
         g = e.graph("global")
@@ -109,13 +101,6 @@ def test_cost_field_host_replay_and_updates(ref, mountain_gentle):
     assert len(sizes) > 1 and frontier_seen
 
 
-def _write_graph(path, nodes, edges):
-    doc = {"nodes": [{"id": i, "pos": list(p), "state": s} for i, (p, s) in enumerate(nodes)],
-           "edges": [{"source": a, "target": b, "weight": w, "dist": d} for a, b, w, d in edges]}
-    with open(path, "w") as f:
-        json.dump(doc, f)
-
-
 def test_cost_field_json_graph(ref, tmp_path):
     import trg_planner
     nodes = [((0.0, 0.0, 0.0), 0), ((1.0, 0.0, 0.0), 0), ((2.0, 0.0, 0.0), 0), ((0.0, 1.0, 0.0), 0),
@@ -129,7 +114,7 @@ def test_cost_field_json_graph(ref, tmp_path):
              (6, 7, 0.3, 1.0), (7, 6, 0.3, 1.0),   # a second component
              (8, 0, 0.1, 1.0)]                     # directed only, towards the source
     p = tmp_path / "g.json"
-    _write_graph(p, nodes, edges)
+    write_graph(p, nodes, edges)
     e = trg_planner.Engine(**MOUNTAIN)
     e.load_json(str(p))
     g = e.graph("global")
@@ -157,14 +142,14 @@ def test_cost_field_json_graph(ref, tmp_path):
         assert ei.value.status == 1, str(ei.value)  # TRG_ERR_INVALID_ARG
     # an edge with safety_factor * weight + 1 < 0
     q = tmp_path / "neg.json"
-    _write_graph(q, nodes, edges + [(1, 2, -1.0, 1.0)])
+    write_graph(q, nodes, edges + [(1, 2, -1.0, 1.0)])
     e.load_json(str(q))
     with pytest.raises(trg_planner.TrgError) as ei:
         e.cost_field(source_id=0)
     assert ei.value.status == 1, str(ei.value)
     # an empty graph
     r = tmp_path / "empty.json"
-    _write_graph(r, [], [])
+    write_graph(r, [], [])
     e.load_json(str(r))
     with pytest.raises(trg_planner.TrgError) as ei:
         e.cost_field(source_id=0)
@@ -221,3 +206,55 @@ def test_cost_field_c3_fullsize(ref, synth):
     assert 0 < info.rounds < 4 * g.V
     print(f"C3 field: reached {info.reached} of {g.V}, {info.rounds} rounds, {info.host_syncs} host syncs, "
           f"{info.ms_device:.2f} ms device, {info.ms_total:.2f} ms total")
+
+
+# (host_syncs, rounds) of the first solve on a freshly loaded graph and of the same solve repeated, by
+# (graph, field_delta_scale, m, mode).  Measured on an MI355X at commit 77d9b5b, the last one before field_solve
+# was split into phases; literal on purpose: nothing here is derived from the code under test.
+WAITS = {
+    ('chain100', '4', 1, 'settle_all'): ((10, 200), (9, 200)),
+    ('chain100', '4', 1, 'unbounded'): ((10, 200), (9, 200)),
+    ('chain100', '4', 4, 'settle_all'): ((12, 280), (11, 280)),
+    ('chain100', '4', 4, 'unbounded'): ((12, 280), (11, 280)),
+    ('chain100', 'inf', 1, 'settle_all'): ((10, 200), (9, 200)),
+    ('chain100', 'inf', 1, 'unbounded'): ((10, 200), (9, 200)),
+    ('chain100', 'inf', 4, 'settle_all'): ((10, 200), (9, 200)),
+    ('chain100', 'inf', 4, 'unbounded'): ((10, 200), (9, 200)),
+    ('one_node', '4', 1, 'settle_all'): ((4, 2), (3, 2)),
+    ('one_node', '4', 1, 'unbounded'): ((4, 2), (3, 2)),
+    ('one_node', '4', 4, 'settle_all'): ((4, 2), (3, 2)),
+    ('one_node', '4', 4, 'unbounded'): ((4, 2), (3, 2)),
+    ('one_node', 'inf', 1, 'settle_all'): ((4, 2), (3, 2)),
+    ('one_node', 'inf', 1, 'unbounded'): ((4, 2), (3, 2)),
+    ('one_node', 'inf', 4, 'settle_all'): ((4, 2), (3, 2)),
+    ('one_node', 'inf', 4, 'unbounded'): ((4, 2), (3, 2)),
+}
+
+
+def test_host_waits_pinned(tmp_path):
+    """How often a solve waits for the device, and how many rounds it runs, are pinned: the edge-cost wait (first
+    solve on a graph only), one wait per batch of 32 rounds in each of the two passes, one for the outputs.  The
+    one-node graph and a directed chain of 100 nodes (one node per round, so more than one batch per pass; see
+    tests/test_gpu_cost_field_batch.py for why its round count is a function of the graph), at two bucket widths,
+    for m = 1 and m = 4, unbounded and with settle "all" on the last node."""
+    import trg_planner
+    graphs = {"one_node": fg.oddities()["one_node"][0], "chain100": fg.chain(100)}
+    e = trg_planner.Engine(**MOUNTAIN)
+    got = {}
+    for name, g in graphs.items():
+        V = len(g.state)
+        for scale in ("inf", "4"):
+            e.set_option("field_delta_scale", scale)
+            for m in (1, 4):
+                for mode in ("unbounded", "settle_all"):
+                    load_graph(e, g, tmp_path, name)  # a new graph_version: the next solve is the first on it
+                    kw = dict(targets=[V - 1], settle="all") if mode == "settle_all" else {}
+                    pair = []
+                    for _ in range(2):
+                        info = e.cost_fields(source_ids=[min(k, V - 1) for k in range(m)], **kw)["info"]
+                        pair.append((info.host_syncs, info.rounds))
+                    got[name, scale, m, mode] = tuple(pair)
+    e.close()
+    for key in sorted(got):
+        print(f"    {key!r}: {got[key]!r},")
+    assert got == WAITS

@@ -19,27 +19,15 @@ Wall time on an MI355X: 10.8 s for this file, next to 8.2 s for tests/test_gpu_c
 case in the same run (24.8 s before the longest chain went from 20 000 to 8 000 nodes and the graphs of 8 000
 nodes and more to three of the five widths and fewer sources; every family still runs all five widths at some
 size).  What is left is mostly host work -- the generators, JSON, the reference -- and a chain's launches."""
-import functools
-
 import numpy as np
 import pytest
 
 import field_graphs as fg
 import field_ref
+from field_support import PARAMS, SCALES, SCALES_LARGE, load_graph, random_large, ref  # noqa: F401 (ref: a fixture)
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-SCALES = ("4", "0.5", "1e-6", "1e3", "inf")
-SCALES_LARGE = ("4", "1e-6", "inf")  # near-far, a bucket per distinct cost, Bellman-Ford
-PARAMS = dict(expand_dist=0.6, robot_size=0.3, sample_num=7, height_threshold=0.16, collision_threshold=0.1,
-              update_collision_threshold=0.5, goal_tolerance=0.8)
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return field_ref.compile_reference(tmp_path_factory.mktemp("field_ref"))
-
-
 @pytest.fixture(scope="module")
 def engine_of():
     """safety_factor -> one engine (no map), shared by the tests of this module: every load_json replaces the
@@ -55,27 +43,6 @@ def engine_of():
     yield get
     for e in made.values():
         e.close()
-
-
-@functools.lru_cache(maxsize=None)
-def _random_large(seed, V, scale):
-    return fg.with_positions(fg.random_graph(np.random.default_rng(seed), V, scale))
-
-
-def _load(e, g, tmp_path, name="g"):
-    """g through load_json -> the exported CSR, checked against g: V, E, rows in order with float bits, states."""
-    p = tmp_path / f"{name}.json"
-    fg.write_json(p, g)
-    e.load_json(str(p))
-    x = e.graph("global")
-    assert x.V == len(g.state) and x.E == len(g.col), (x.V, x.E)
-    assert np.array_equal(x.rowptr, g.rowptr)
-    assert np.array_equal(x.col, g.col)
-    assert np.array_equal(x.w.view(np.uint32), g.w.view(np.uint32))
-    assert np.array_equal(x.dist.view(np.uint32), g.dist.view(np.uint32))
-    assert np.array_equal(x.state, g.state)
-    assert np.array_equal(x.xyz.view(np.uint32), g.pos.view(np.uint32))
-    return x
 
 
 def _check_walks(x, sf, src, cost, hops, parent, rng):
@@ -149,15 +116,15 @@ def test_random_small(ref, engine_of, tmp_path, seed):
     sf = [3.0, 0.5, 1.0][seed % 3]
     g = fg.with_positions(fg.random_small(seed))
     e = engine_of(sf)
-    x = _load(e, g, tmp_path)
+    x = load_graph(e, g, tmp_path)
     _check_field(ref, e, x, sf, _sources(x.V, seed), seed=seed)
 
 
 @pytest.mark.parametrize("seed,V,scale", [c for size in sorted(fg.RANDOM_LARGE) for c in fg.RANDOM_LARGE[size]])
 def test_random_large(ref, engine_of, tmp_path, seed, V, scale):
-    g = _random_large(seed, V, scale)
+    g = random_large(seed, V, scale)
     e = engine_of()
-    x = _load(e, g, tmp_path)
+    x = load_graph(e, g, tmp_path)
     if x.V <= 3000:
         _check_field(ref, e, x, 3.0, _sources(x.V, seed, x.V // 4), seed=seed)
     else:
@@ -172,7 +139,7 @@ def test_chain(ref, engine_of, tmp_path, V, symmetric):
     sources (the launches of one of its solves cost as much as a whole other family)."""
     g = fg.chain(V, symmetric)
     e = engine_of()
-    x = _load(e, g, tmp_path)
+    x = load_graph(e, g, tmp_path)
     if V <= 3000:
         want = _check_field(ref, e, x, 3.0, [0, V - 1, V // 2])
     else:
@@ -188,7 +155,7 @@ def test_star(ref, engine_of, tmp_path, deg, hubs):
     both sides of the first threshold; the leaves' edges back make every leaf improve its hub."""
     g = fg.star(deg, hubs)
     e = engine_of()
-    x = _load(e, g, tmp_path)
+    x = load_graph(e, g, tmp_path)
     assert x.rowptr[1] - x.rowptr[0] == deg // hubs + (hubs > 1)
     if deg <= 4096:
         _check_field(ref, e, x, 3.0, _sources(x.V, hubs, hubs + deg // 3))
@@ -203,7 +170,7 @@ def test_lattice(ref, engine_of, tmp_path, n, zero_band):
     is the smallest id among them."""
     g = fg.lattice(n, n, zero_band)
     e = engine_of()
-    x = _load(e, g, tmp_path)
+    x = load_graph(e, g, tmp_path)
     if n <= 24:
         want = _check_field(ref, e, x, 3.0, _sources(x.V, n, (n // 2) * n + n // 2, n - 1))
     else:
@@ -223,7 +190,7 @@ def test_cost_ranges(ref, engine_of, tmp_path, family, V):
     denormal: subnormal costs, a subnormal or zero width; heavy_tail: costs over 60 decades."""
     g = getattr(fg, family)(V, seed=V)
     e = engine_of()
-    x = _load(e, g, tmp_path)
+    x = load_graph(e, g, tmp_path)
     want = _check_field(ref, e, x, 3.0, _sources(V, V))
     rc, rh, _ = want[0]
     assert np.all(rh >= 0)  # connected
@@ -238,7 +205,7 @@ def test_saturating(ref, engine_of, tmp_path, name):
     """A fold that saturates: a node first reached at +inf is reached, with hops and a parent, and is expanded."""
     g = getattr(fg, name)()
     e = engine_of()
-    x = _load(e, g, tmp_path)
+    x = load_graph(e, g, tmp_path)
     want = _check_field(ref, e, x, 3.0, range(x.V))
     rc, rh, rp = want[0]
     if name == "saturating_chain":
@@ -255,7 +222,7 @@ ODDITIES = fg.oddities()
 def test_oddities(ref, engine_of, tmp_path, name):
     g, sources = ODDITIES[name]
     e = engine_of()
-    x = _load(e, g, tmp_path)
+    x = load_graph(e, g, tmp_path)
     _check_field(ref, e, x, 3.0, sources)
 
 
@@ -264,7 +231,7 @@ def test_engine_state_sequence(ref, tmp_path):
     graph again -- the graph_version and column-pointer caches of the edge costs and the reuse of oversized
     buffers.  Every result equals a fresh engine's (and the reference's)."""
     import trg_planner
-    big = _random_large(*fg.RANDOM_LARGE[2000][0])
+    big = random_large(*fg.RANDOM_LARGE[2000][0])
     small = fg.with_positions(fg.random_small(5))
     e = trg_planner.Engine(safety_factor=3.0, **PARAMS)
 
@@ -274,7 +241,7 @@ def test_engine_state_sequence(ref, tmp_path):
 
     def fresh(g, scale, sources, name):
         f = trg_planner.Engine(safety_factor=3.0, **PARAMS)
-        out = solve(f, _load(f, g, tmp_path, name), scale, sources)
+        out = solve(f, load_graph(f, g, tmp_path, name), scale, sources)
         f.close()
         return out
 
@@ -283,15 +250,15 @@ def test_engine_state_sequence(ref, tmp_path):
 
     Vb, Vs = len(big.state), len(small.state)
     src_big, src_small = [0, Vb // 4], [0, Vs - 1]
-    xb = _load(e, big, tmp_path, "big")
+    xb = load_graph(e, big, tmp_path, "big")
     first = solve(e, xb, "4", src_big)
     assert same(first, fresh(big, "4", src_big, "big_fresh"))
     assert same(solve(e, xb, "0.5", src_big), first)
-    xs = _load(e, small, tmp_path, "small")
+    xs = load_graph(e, small, tmp_path, "small")
     assert xs.E != xb.E and Vs * 40 < Vb
     assert same(solve(e, xs, "0.5", src_small), fresh(small, "0.5", src_small, "small_fresh"))
     _check_field(ref, e, xs, 3.0, src_small)
-    xb = _load(e, big, tmp_path, "big_again")
+    xb = load_graph(e, big, tmp_path, "big_again")
     assert same(solve(e, xb, "1e3", src_big), first)
     _check_field(ref, e, xb, 3.0, src_big, scales=("1e3", "4"))
     e.close()

@@ -28,64 +28,26 @@ import numpy as np
 import pytest
 
 import field_graphs as fg
-import field_ref
-from test_gpu_cost_field_adversarial import PARAMS, SCALES, _load, _random_large
+from field_support import (INVALID_ARG, MOUNTAIN, PARAMS, SCALES, assert_rows, bits, engine, load_graph,  # noqa: F401
+                           random_large, ref, reference_fields, small_sources, with_isolated_node, write_graph)
+from graph_support import obs_crop
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-MOUNTAIN = dict(PARAMS, safety_factor=3.0)
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return field_ref.compile_reference(tmp_path_factory.mktemp("field_ref_batch"))
-
-
-@pytest.fixture(scope="module")
-def engine():
-    """One engine without a map for the JSON graphs of this module: every load_json and every batch size reuses
-    the field buffers of the one before."""
-    import trg_planner
-    e = trg_planner.Engine(safety_factor=3.0, **PARAMS)
-    yield e
-    e.close()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _assert_rows(at, what, got, want, as_bits=False):
-    a, b = (_bits(got), _bits(want)) if as_bits else (got, want)
-    bad = np.argwhere(a != b)
-    assert bad.shape[0] == 0, at + (f"{bad.shape[0]} {what} differ, first at field {bad[0][0]}, node {bad[0][1]}: "
-                                    f"{got[tuple(bad[0])]!r} != {want[tuple(bad[0])]!r}")
-
-
-def _reference(ref, x, sf, sources):
-    """(m, V) cost, hops, parent of the host Dijkstra, one solve per distinct source."""
-    one = {}
-    for s in dict.fromkeys(int(s) for s in sources):
-        st, rc, rh, rp = field_ref.field_of_graph(ref, x, sf, s)
-        assert st == 0
-        one[s] = rc, rh, rp
-    return tuple(np.stack([one[int(s)][i] for s in sources]) for i in range(3))
-
-
 def _check_batch(ref, e, x, sources, scales=SCALES, targets=None, sf=3.0, one_walk_per_node=False):
     """One batch per bucket width against the reference and against the single solves of its sources."""
     V, m = x.V, len(sources)
     sources = [int(s) for s in sources]
-    rc, rh, rp = _reference(ref, x, sf, sources)
+    rc, rh, rp = reference_fields(ref, x, sf, sources)
     r = None
     for scale in scales:
         e.set_option("field_delta_scale", scale)
         at = f"field_delta_scale {scale}, m {m}: "
         r = e.cost_fields(source_ids=sources, targets=targets)
         assert r["cost"].shape == r["hops"].shape == r["parent"].shape == (m, V), at
-        _assert_rows(at, "costs", r["cost"], rc, as_bits=True)
-        _assert_rows(at, "hops", r["hops"], rh)
-        _assert_rows(at, "parents", r["parent"], rp)
+        assert_rows(at, "costs", r["cost"], rc, as_bits=True)
+        assert_rows(at, "hops", r["hops"], rh)
+        assert_rows(at, "parents", r["parent"], rp)
         info = r["info"]
         assert r["sources"].tolist() == sources and info.source == sources[0], at
         assert np.array_equal(r["reached"], (r["hops"] >= 0).sum(axis=1)), at + str(r["reached"])
@@ -97,7 +59,7 @@ def _check_batch(ref, e, x, sources, scales=SCALES, targets=None, sf=3.0, one_wa
                 continue
             cost, hops, parent, one = e.cost_field(source_id=s)
             sat = at + f"single field of source {s}: "
-            assert np.array_equal(_bits(cost), _bits(r["cost"][k])), sat + "costs differ"
+            assert np.array_equal(bits(cost), bits(r["cost"][k])), sat + "costs differ"
             assert np.array_equal(hops, r["hops"][k]) and np.array_equal(parent, r["parent"][k]), sat
             assert one.reached == r["reached"][k], sat
             single_rounds = max(single_rounds, one.rounds)
@@ -108,39 +70,17 @@ def _check_batch(ref, e, x, sources, scales=SCALES, targets=None, sf=3.0, one_wa
         if targets is not None:
             t = np.asarray(targets, np.int64)
             assert r["cost_at"].shape == r["hops_at"].shape == (m, t.size), at
-            assert np.array_equal(_bits(r["cost_at"]), _bits(r["cost"][:, t])), at + "cost_at"
+            assert np.array_equal(bits(r["cost_at"]), bits(r["cost"][:, t])), at + "cost_at"
             assert np.array_equal(r["hops_at"], r["hops"][:, t]), at + "hops_at"
     return r
-
-
-def _with_isolated_node(g):
-    """g plus one node without edges (the last id)."""
-    V = len(g.state)
-    pos = np.concatenate([g.pos, g.pos.max(axis=0, keepdims=True) + F32([3.0, 3.0, 0.0])])
-    return fg.FieldGraph(np.append(g.rowptr, g.rowptr[-1]).astype(np.int32), g.col, g.w, g.dist,
-                         np.append(g.state, 0).astype(np.int32), pos.astype(np.float32))
-
-
-def _small_sources(g, m, seed):
-    """m sources of a random_small graph with an isolated last node: a node of each component, a duplicate, an
-    Invalid node and the isolated one first (rotated by the seed, so that the short batches meet every kind),
-    then nodes all over the graph."""
-    V = len(g.state)
-    invalid = int(np.flatnonzero(g.state == fg.INVALID)[0])
-    half = (V - 1) // 2 + 3  # ids from here on only link among themselves
-    first = int(np.flatnonzero(g.state[:half] != fg.INVALID)[0])
-    second = half + int(np.flatnonzero(g.state[half:V - 1] != fg.INVALID)[0])
-    kinds = [first, second, first, invalid, V - 1]
-    kinds = kinds[seed % 5:] + kinds[:seed % 5]
-    return (kinds + [(7 * i + seed) % V for i in range(m)])[:m]
 
 
 @pytest.mark.parametrize("m", [1, 2, 5, 64])
 @pytest.mark.parametrize("seed", [0, 7, 13])
 def test_random_small(ref, engine, tmp_path, seed, m):
-    g = _with_isolated_node(fg.with_positions(fg.random_small(seed)))
-    x = _load(engine, g, tmp_path)
-    sources = _small_sources(g, m, seed)
+    g = with_isolated_node(fg.with_positions(fg.random_small(seed)))
+    x = load_graph(engine, g, tmp_path)
+    sources = small_sources(g, m, seed)
     if m >= 5:
         assert len(set(sources[:5])) == 4 and x.state[sources].min() == fg.INVALID and x.V - 1 in sources
     _check_batch(ref, engine, x, sources, targets=[x.V - 1, 0, 0, x.V // 2])
@@ -153,7 +93,7 @@ ODDITIES = fg.oddities()
 def test_oddities(ref, engine, tmp_path, name):
     """Three fields on every degenerate shape; V == 1 is three items on one node."""
     g, sources = ODDITIES[name]
-    x = _load(engine, g, tmp_path)
+    x = load_graph(engine, g, tmp_path)
     r = _check_batch(ref, engine, x, (list(sources) * 3)[:3])
     if name == "one_node":
         assert x.V == 1 and r["cost"].tolist() == [[0.0]] * 3 and r["hops"].tolist() == [[0]] * 3
@@ -166,7 +106,7 @@ def test_chain(ref, engine, tmp_path, symmetric):
     node 0 the whole chain, from the middle half of it (both halves at once if symmetric), from the last node
     of a directed chain one round, from the one before it two."""
     V = 3000
-    x = _load(engine, fg.chain(V, symmetric), tmp_path)
+    x = load_graph(engine, fg.chain(V, symmetric), tmp_path)
     r = _check_batch(ref, engine, x, [0, V - 1, V // 2, V - 2], scales=("4", "1e-6", "inf"),
                      one_walk_per_node=not symmetric)
     assert r["reached"].tolist() == ([V, V, V, V] if symmetric else [V, 1, V - V // 2, 2])
@@ -176,19 +116,19 @@ def test_chain(ref, engine, tmp_path, symmetric):
 def test_star_long_row(ref, engine, tmp_path):
     """The hub's row of 30 000 (1 875 sixteen-lane trips) in one field while the two leaves' fields have one
     short row each in the same launch."""
-    x = _load(engine, fg.star(30000), tmp_path)
+    x = load_graph(engine, fg.star(30000), tmp_path)
     _check_batch(ref, engine, x, [0, 1, 1 + 30000 // 2], scales=("4", "0.5", "inf"))
 
 
 def test_star_four_hubs(ref, engine, tmp_path):
-    x = _load(engine, fg.star(4096, 4), tmp_path)
+    x = load_graph(engine, fg.star(4096, 4), tmp_path)
     _check_batch(ref, engine, x, [x.V - 1, 0, 4 + 4096 // 3])
 
 
 def test_lattice(ref, engine, tmp_path):
     """Massive exact ties in eight fields at once: the parent rule (smallest id) holds per field."""
     n = 200
-    x = _load(engine, fg.lattice(n, n), tmp_path)
+    x = load_graph(engine, fg.lattice(n, n), tmp_path)
     centre = (n // 2) * n + n // 2
     sources = [0, n - 1, n * (n - 1), n * n - 1, centre, 0, n // 2, centre + 1]
     r = _check_batch(ref, engine, x, sources, scales=("4", "inf"))
@@ -202,7 +142,7 @@ def test_lattice(ref, engine, tmp_path):
 @pytest.mark.parametrize("name", ["saturating_chain", "saturating_branch"])
 def test_saturating(ref, engine, tmp_path, name):
     g = getattr(fg, name)()
-    x = _load(engine, g, tmp_path)
+    x = load_graph(engine, g, tmp_path)
     r = _check_batch(ref, engine, x, [0, 2, 1])
     assert np.isinf(r["cost"][0][r["hops"][0] >= 0]).any()  # reached at +inf
 
@@ -211,7 +151,7 @@ def test_saturating(ref, engine, tmp_path, name):
 @pytest.mark.parametrize("family", ["all_zero", "denormal"])
 def test_cost_ranges(ref, engine, tmp_path, family, V):
     """A bucket width of zero (the threshold moves by the one-ulp bump alone) and a subnormal one, shared."""
-    x = _load(engine, getattr(fg, family)(V, seed=V), tmp_path)
+    x = load_graph(engine, getattr(fg, family)(V, seed=V), tmp_path)
     _check_batch(ref, engine, x, [0, V - 1, V // 3])
 
 
@@ -223,7 +163,7 @@ def _large_sources(V, m=16):
 
 
 def test_random_large(ref, engine, tmp_path):
-    x = _load(engine, _random_large(*LARGE), tmp_path)
+    x = load_graph(engine, random_large(*LARGE), tmp_path)
     assert x.V % 4 and (16 * x.V) % 64
     targets = np.random.default_rng(3).integers(0, x.V, size=700)  # more than one block, duplicates
     _check_batch(ref, engine, x, _large_sources(x.V), targets=targets)
@@ -232,7 +172,7 @@ def test_random_large(ref, engine, tmp_path):
 def test_targets(ref, engine, tmp_path):
     """The gathered arrays are the full arrays at the targets: duplicates, an unreached node, an Invalid one and
     a saturated one; no targets at all; and only the gathered arrays with full=False."""
-    x = _load(engine, fg.saturating_branch(), tmp_path)
+    x = load_graph(engine, fg.saturating_branch(), tmp_path)
     sources = [0, 7, 2]
     targets = [3, 3, 12, 5, 0, 11, 7, 3]
     r = _check_batch(ref, engine, x, sources, targets=targets)
@@ -241,7 +181,7 @@ def test_targets(ref, engine, tmp_path):
     assert r["cost_at"][1, 6] == 0 and r["hops_at"][1, 6] == 0              # a source among the targets
     g = engine.cost_fields(source_ids=sources, targets=targets, full=False)
     assert sorted(g) == ["cost_at", "hops_at", "info", "reached", "sources"]
-    assert np.array_equal(_bits(g["cost_at"]), _bits(r["cost_at"])) and np.array_equal(g["hops_at"], r["hops_at"])
+    assert np.array_equal(bits(g["cost_at"]), bits(r["cost_at"])) and np.array_equal(g["hops_at"], r["hops_at"])
     assert g["reached"].tolist() == r["reached"].tolist() and g["sources"].tolist() == sources
     z = engine.cost_fields(source_ids=sources, targets=[], full=False)
     assert z["cost_at"].shape == z["hops_at"].shape == (3, 0) and z["reached"].tolist() == r["reached"].tolist()
@@ -254,20 +194,20 @@ def test_engine_state_sequence(ref, tmp_path):
     again -- buffers sized for m * V serve V and a smaller m * V, and every solve initialises its own stamps."""
     import trg_planner
     e = trg_planner.Engine(safety_factor=3.0, **PARAMS)
-    big = _random_large(*LARGE)
-    xb = _load(e, big, tmp_path, "big")
+    big = random_large(*LARGE)
+    xb = load_graph(e, big, tmp_path, "big")
     src_big = _large_sources(xb.V)
     first = _check_batch(ref, e, xb, src_big, scales=("4",))
     cost, hops, parent, info = e.cost_field(source_id=src_big[2])
-    assert np.array_equal(_bits(cost), _bits(first["cost"][2])) and np.array_equal(hops, first["hops"][2])
+    assert np.array_equal(bits(cost), bits(first["cost"][2])) and np.array_equal(hops, first["hops"][2])
     assert np.array_equal(parent, first["parent"][2]) and info.reached == first["reached"][2]
-    xs = _load(e, _with_isolated_node(fg.with_positions(fg.random_small(5))), tmp_path, "small")
+    xs = load_graph(e, with_isolated_node(fg.with_positions(fg.random_small(5))), tmp_path, "small")
     assert xs.V * 40 < xb.V
     _check_batch(ref, e, xs, [0, xs.V - 1, 0], scales=("4",))
-    xb = _load(e, big, tmp_path, "big_again")
+    xb = load_graph(e, big, tmp_path, "big_again")
     again = _check_batch(ref, e, xb, src_big, scales=("4",))
     for key in ("cost", "hops", "parent"):
-        assert np.array_equal(_bits(again[key]), _bits(first[key])), key
+        assert np.array_equal(bits(again[key]), bits(first[key])), key
     e.close()
 
 
@@ -282,12 +222,12 @@ def _check_poses(ref, e, g, poses):
     want_src = [int(s[3].source) for s in singles]
     r = e.cost_fields(sources_xy=poses)
     assert r["sources"].tolist() == want_src
-    rc, rh, rp = _reference(ref, g, 3.0, want_src)
-    _assert_rows("sources_xy: ", "costs", r["cost"], rc, as_bits=True)
-    _assert_rows("sources_xy: ", "hops", r["hops"], rh)
-    _assert_rows("sources_xy: ", "parents", r["parent"], rp)
+    rc, rh, rp = reference_fields(ref, g, 3.0, want_src)
+    assert_rows("sources_xy: ", "costs", r["cost"], rc, as_bits=True)
+    assert_rows("sources_xy: ", "hops", r["hops"], rh)
+    assert_rows("sources_xy: ", "parents", r["parent"], rp)
     for k, (cost, hops, parent, info) in enumerate(singles):
-        assert np.array_equal(_bits(cost), _bits(r["cost"][k])) and np.array_equal(hops, r["hops"][k])
+        assert np.array_equal(bits(cost), bits(r["cost"][k])) and np.array_equal(hops, r["hops"][k])
         assert np.array_equal(parent, r["parent"][k]) and info.reached == r["reached"][k]
     # a mix of ids and positions: -1 takes the position
     mixed = e.cost_fields(sources_xy=poses, source_ids=[-1, want_src[1]] + [-1] * (len(poses) - 2), full=False)
@@ -308,7 +248,7 @@ def _check_poses(ref, e, g, poses):
     for arg in (poses, np.array(want_src, np.int32)):
         mc, mh, nodes = e.cost_matrix(arg)
         assert nodes.tolist() == want_src
-        assert np.array_equal(_bits(mc), _bits(rc[:, want_src])) and np.array_equal(mh, rh[:, want_src])
+        assert np.array_equal(bits(mc), bits(rc[:, want_src])) and np.array_equal(mh, rh[:, want_src])
         assert not mc.diagonal().any() and not mh.diagonal().any()
     return chosen
 
@@ -317,7 +257,6 @@ def test_device_built_graph(ref, mountain_small):
     """Sources from positions on the CSR the device build left in HBM, then on the uploaded CSR after an
     updateGraph."""
     import trg_planner
-    from test_gpu_update import _obs_crop
     e = trg_planner.Engine(**MOUNTAIN)
     e.set_sampler(7, 16)
     e.set_global_map(mountain_small)
@@ -327,7 +266,7 @@ def test_device_built_graph(ref, mountain_small):
     g = e.graph("global")
     _check_poses(ref, e, g, poses)
     pose = (12.0, 12.0)
-    e.set_local_map(pose, _obs_crop(mountain_small, pose, 4.0, box=(pose[0] + 2.0, pose[1] + 1.0, 0.6)))
+    e.set_local_map(pose, obs_crop(mountain_small, pose, 4.0, box=(pose[0] + 2.0, pose[1] + 1.0, 0.6)))
     e.update_graph()
     g2 = e.graph("global")
     _check_poses(ref, e, g2, poses)
@@ -337,7 +276,7 @@ def test_device_built_graph(ref, mountain_small):
 def test_cheapest_frontiers_json_graph(ref, engine, tmp_path):
     """Frontier nodes for certain: the random family marks an eighth of its nodes Frontier."""
     g = fg.with_positions(fg.random_small(3))
-    x = _load(engine, g, tmp_path)
+    x = load_graph(engine, g, tmp_path)
     engine.set_option("field_delta_scale", "4")
     poses = g.pos[[0, 1, x.V - 1, x.V // 2, 0], :2].copy()
     assert _check_poses(ref, engine, x, poses) >= 1
@@ -345,27 +284,26 @@ def test_cheapest_frontiers_json_graph(ref, engine, tmp_path):
 
 def test_matrix_in_chunks(ref, engine, tmp_path):
     """More waypoints than one batch holds: chunks of sources against the full target list."""
-    x = _load(engine, fg.lattice(24, 24), tmp_path)
+    x = load_graph(engine, fg.lattice(24, 24), tmp_path)
     engine.set_option("field_delta_scale", "4")
     nodes = (np.arange(70) * 8) % x.V
     mc, mh, ids = engine.cost_matrix(nodes.astype(np.int32))
-    rc, rh, _ = _reference(ref, x, 3.0, nodes)
+    rc, rh, _ = reference_fields(ref, x, 3.0, nodes)
     assert ids.tolist() == nodes.tolist() and mc.shape == mh.shape == (70, 70)
-    assert np.array_equal(_bits(mc), _bits(rc[:, nodes])) and np.array_equal(mh, rh[:, nodes])
+    assert np.array_equal(bits(mc), bits(rc[:, nodes])) and np.array_equal(mh, rh[:, nodes])
 
 
 def test_errors(ref, engine, tmp_path):
     import trg_planner
-    from test_gpu_cost_field import _write_graph
 
     def status_of(**kw):
         with pytest.raises(trg_planner.TrgError) as ei:
             engine.cost_fields(**kw)
         return ei.value.status, str(ei.value)
 
-    x = _load(engine, fg.with_positions(fg.random_small(1)), tmp_path)
+    x = load_graph(engine, fg.with_positions(fg.random_small(1)), tmp_path)
     V = x.V
-    INVALID_ARG, NO_GRAPH = 1, 5
+    NO_GRAPH = 5
     assert status_of(source_ids=[])[0] == INVALID_ARG                     # m = 0
     assert status_of(source_ids=[0] * 65)[0] == INVALID_ARG               # m = 65
     st, msg = status_of(source_ids=[0, 1, -2])
@@ -382,10 +320,10 @@ def test_errors(ref, engine, tmp_path):
     _check_batch(ref, engine, x, [0, V - 1], scales=("4",))
     nodes = [((0.0, 0.0, 0.0), 0), ((1.0, 0.0, 0.0), 0), ((2.0, 0.0, 0.0), 0)]
     p = tmp_path / "neg.json"
-    _write_graph(p, nodes, [(0, 1, 0.0, 1.0), (1, 2, -1.0, 1.0)])         # safety_factor * weight + 1 < 0
+    write_graph(p, nodes, [(0, 1, 0.0, 1.0), (1, 2, -1.0, 1.0)])         # safety_factor * weight + 1 < 0
     engine.load_json(str(p))
     assert status_of(source_ids=[0, 1])[0] == INVALID_ARG
     p = tmp_path / "empty.json"
-    _write_graph(p, [], [])
+    write_graph(p, [], [])
     engine.load_json(str(p))
     assert status_of(source_ids=[0, 0])[0] == NO_GRAPH

@@ -16,36 +16,15 @@ import pytest
 
 import bound_ref
 import field_graphs as fg
-import field_ref
 import route_ref
-from test_gpu_cost_field_adversarial import PARAMS, SCALES, _load, _random_large
+from field_support import (INVALID_ARG, MOUNTAIN, PARAMS, SCALES, assert_rows, bits, engine, load_graph,  # noqa: F401
+                           random_large, ref, reference_fields)
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 INF = F32(np.inf)
 FLT_MAX = np.finfo(np.float32).max
 SF = 3.0
-MOUNTAIN = dict(PARAMS, safety_factor=SF)
-INVALID_ARG = 1
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return field_ref.compile_reference(tmp_path_factory.mktemp("field_ref_bounded_gpu"))
-
-
-@pytest.fixture(scope="module")
-def engine():
-    import trg_planner
-    e = trg_planner.Engine(safety_factor=SF, **PARAMS)
-    yield e
-    e.close()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
 def _b1(v):
     """The bits of one float32."""
     return int(np.float32(v).view(np.uint32))
@@ -54,23 +33,6 @@ def _b1(v):
 def _below(c):
     """The float just below the cost c (0 stays 0: no budget is negative)."""
     return F32(np.nextafter(F32(c), F32(-np.inf))) if c > 0 else F32(0.0)
-
-
-def _reference(ref, x, sources):
-    """(m, V) cost, hops, parent of the host Dijkstra: the full fields, computed once per graph."""
-    one = {}
-    for s in dict.fromkeys(int(s) for s in sources):
-        st, rc, rh, rp = field_ref.field_of_graph(ref, x, SF, s)
-        assert st == 0
-        one[s] = rc, rh, rp
-    return tuple(np.stack([one[int(s)][i] for s in sources]) for i in range(3))
-
-
-def _assert_rows(at, what, got, want, as_bits=False):
-    a, b = (_bits(got), _bits(want)) if as_bits else (got, want)
-    bad = np.argwhere(a != b)
-    assert bad.shape[0] == 0, at + (f"{bad.shape[0]} {what} differ, first at field {bad[0][0]}, node {bad[0][1]}: "
-                                    f"{got[tuple(bad[0])]!r} != {want[tuple(bad[0])]!r}")
 
 
 def _check(e, full, sources, at, budget=None, settle=None, targets=None, want_full=True):
@@ -82,17 +44,17 @@ def _check(e, full, sources, at, budget=None, settle=None, targets=None, want_fu
     tc, th, tp = bound_ref.truncate(rc, rh, rp, want_bound)
     r = e.cost_fields(source_ids=[int(s) for s in sources], targets=targets, budget=budget, settle=settle,
                       full=want_full)
-    assert np.array_equal(_bits(r["bound"]), _bits(want_bound)), at + f"bound {r['bound']!r} != {want_bound!r}"
+    assert np.array_equal(bits(r["bound"]), bits(want_bound)), at + f"bound {r['bound']!r} != {want_bound!r}"
     assert np.array_equal(r["reached"], (th >= 0).sum(axis=1)), at + f"reached {r['reached']}"
     assert r["info"].reached == int(r["reached"].sum()), at
     if want_full:
-        _assert_rows(at, "costs", r["cost"], tc, as_bits=True)
-        _assert_rows(at, "hops", r["hops"], th)
-        _assert_rows(at, "parents", r["parent"], tp)
+        assert_rows(at, "costs", r["cost"], tc, as_bits=True)
+        assert_rows(at, "hops", r["hops"], th)
+        assert_rows(at, "parents", r["parent"], tp)
         assert np.array_equal(r["reached"], (r["hops"] >= 0).sum(axis=1)), at
     if targets is not None:
         t = np.asarray(targets, np.int64)
-        assert np.array_equal(_bits(r["cost_at"]), _bits(tc[:, t])), at + "cost_at"
+        assert np.array_equal(bits(r["cost_at"]), bits(tc[:, t])), at + "cost_at"
         assert np.array_equal(r["hops_at"], th[:, t]), at + "hops_at"
     return r
 
@@ -124,9 +86,9 @@ def test_budgets(ref, engine, tmp_path, name):
     (dropped), a finite budget above every finite cost (on the saturating graph the +inf nodes go) and +inf (equal
     to the unbounded call); one batch of five different budgets, +inf among them, next to one budget for all."""
     e = engine
-    x = _load(e, BUDGET_GRAPHS[name](), tmp_path)
+    x = load_graph(e, BUDGET_GRAPHS[name](), tmp_path)
     sources = _five_sources(x) if name != "chain_3000" else [0, 1, 700, 1500, 2990]
-    full5 = _reference(ref, x, sources)
+    full5 = reference_fields(ref, x, SF, sources)
     full1 = tuple(a[:1] for a in full5)
     rc, rh, _ = full5
     exact = [_a_cost(rc[k], rh[k]) for k in range(5)]
@@ -173,11 +135,11 @@ def _settle_lists(x, rc0, rh0, src):
 @pytest.mark.parametrize("mode", ["any", "all"])
 def test_settle(ref, engine, tmp_path, mode):
     e = engine
-    x = _load(e, fg.with_positions(fg.random_small(7)), tmp_path)
+    x = load_graph(e, fg.with_positions(fg.random_small(7)), tmp_path)
     valid = np.flatnonzero(x.state != fg.INVALID)
     src = int(valid[0])
     sources = [src, int(valid[1]), int(valid[-1])]  # (the last one: the other component)
-    full = _reference(ref, x, sources)
+    full = reference_fields(ref, x, SF, sources)
     rc, rh, _ = full
     lists = _settle_lists(x, rc[0], rh[0], src)
     for scale in SCALES:
@@ -212,11 +174,11 @@ def test_settle_batch_of_eight(ref, engine, tmp_path, mode):
     """Eight fields over one target list on the 1 950-node random graph: the fields settle buckets apart, so the
     shared threshold carries finished fields next to running ones."""
     e = engine
-    x = _load(e, _random_large(*fg.RANDOM_LARGE[2000][2]), tmp_path)
+    x = load_graph(e, random_large(*fg.RANDOM_LARGE[2000][2]), tmp_path)
     assert x.V == 1950
     valid = np.flatnonzero(x.state != fg.INVALID)
     sources = [int(valid[(i * len(valid)) // 8]) for i in range(8)]
-    full = _reference(ref, x, sources)
+    full = reference_fields(ref, x, SF, sources)
     rc, rh, _ = full
     both = np.flatnonzero((rh[0] > 0) & np.isfinite(rc[0]))
     order = both[np.argsort(rc[0][both], kind="stable")]
@@ -235,8 +197,8 @@ def test_it_really_stops(ref, engine, tmp_path):
     e = engine
     e.set_option("field_delta_scale", "4")
     a = np.arange(4095)
-    x = _load(e, fg.from_edges(4096, a, a + 1, np.zeros(4095), np.ones(4095)), tmp_path)
-    full = _reference(ref, x, [0])
+    x = load_graph(e, fg.from_edges(4096, a, a + 1, np.zeros(4095), np.ones(4095)), tmp_path)
+    full = reference_fields(ref, x, SF, [0])
     rc, rh, _ = full
     assert np.array_equal(rc[0], np.arange(4096, dtype=F32)) and np.array_equal(rh[0], np.arange(4096))
     by_budget = _check(e, full, [0], "unit chain, budget: ", budget=rc[0][40])
@@ -271,12 +233,12 @@ def test_reached_list(ref, engine, tmp_path):
     import trg_planner
     e = engine
     e.set_option("field_delta_scale", "4")
-    g = _random_large(*fg.RANDOM_LARGE[2000][2])
-    x = _load(e, g, tmp_path)
+    g = random_large(*fg.RANDOM_LARGE[2000][2])
+    x = load_graph(e, g, tmp_path)
     assert x.V % 64 != 0
     valid = np.flatnonzero(x.state != fg.INVALID)
     sources = [int(valid[0]), int(valid[len(valid) // 3]), int(valid[-1])]
-    full = _reference(ref, x, sources)
+    full = reference_fields(ref, x, SF, sources)
     rc, rh, _ = full
     budgets = [_a_cost(rc[0], rh[0]), INF, F32(0.0)]
     r = _check(e, full, sources, "reached list: ", budget=budgets)
@@ -284,7 +246,7 @@ def test_reached_list(ref, engine, tmp_path):
         want = np.flatnonzero(r["hops"][k] >= 0)
         ids, cost, hops = e.field_reached(k)
         assert ids.dtype == np.int32 and np.array_equal(ids, want), f"field {k}: ids"
-        assert np.array_equal(_bits(cost), _bits(r["cost"][k][want])) and np.array_equal(hops, r["hops"][k][want]), k
+        assert np.array_equal(bits(cost), bits(r["cost"][k][want])) and np.array_equal(hops, r["hops"][k][want]), k
         assert e.field_reached(k, cap=0) == want.size  # the count only
         n, a, c, h, info = _raw_reached(e, k, 0, ids=False, cost=False, hops=False)
         assert n == want.size and info.reached == want.size and info.source == sources[k] and info.host_syncs == 1
@@ -296,14 +258,14 @@ def test_reached_list(ref, engine, tmp_path):
         k = min(cap, want.size)
         assert n == want.size, cap
         assert np.array_equal(a[:k], want[:k]) and np.all(a[k:] == -7), cap
-        assert np.array_equal(_bits(c[:k]), _bits(r["cost"][0][want[:k]])) and np.all(np.isnan(c[k:])), cap
+        assert np.array_equal(bits(c[:k]), bits(r["cost"][0][want[:k]])) and np.all(np.isnan(c[k:])), cap
         assert np.array_equal(h[:k], r["hops"][0][want[:k]]) and np.all(h[k:] == -7), cap
     n, a, c, h, _ = _raw_reached(e, 1, 64, cost=False)  # one array missing
     want1 = np.flatnonzero(r["hops"][1] >= 0)
     assert n == want1.size and np.array_equal(a[:64], want1[:64]) and np.array_equal(h[:64], r["hops"][1][want1[:64]])
     # reachable: one bounded solve, then the list
     ids, cost, hops = e.reachable(None, budgets[0], source_id=sources[0])
-    assert np.array_equal(ids, want) and np.array_equal(_bits(cost), _bits(r["cost"][0][want]))
+    assert np.array_equal(ids, want) and np.array_equal(bits(cost), bits(r["cost"][0][want]))
     assert np.array_equal(hops, r["hops"][0][want])
 
     def refused(field, cap=4):
@@ -315,10 +277,10 @@ def test_reached_list(ref, engine, tmp_path):
     assert "field 1" in refused(1)  # (reachable's solve has one field)
     assert "field -1" in refused(-1)
     refused(0, cap=-1)
-    _load(e, g, tmp_path, "again")
+    load_graph(e, g, tmp_path, "again")
     assert "earlier graph" in refused(0)
     fresh = trg_planner.Engine(safety_factor=SF, **PARAMS)
-    _load(fresh, fg.with_positions(fg.random_small(1)), tmp_path, "fresh")
+    load_graph(fresh, fg.with_positions(fg.random_small(1)), tmp_path, "fresh")
     with pytest.raises(trg_planner.TrgError) as ei:
         fresh.field_reached(0)
     assert ei.value.status == INVALID_ARG and "no cost-field solve" in str(ei.value)
@@ -330,10 +292,10 @@ def test_routes_of_a_bounded_solve(ref, engine, tmp_path, with_parents):
     """Routes to every node, inside and outside the bounds, against tests/route_ref.py on the truncated arrays."""
     e = engine
     e.set_option("field_delta_scale", "4")
-    x = _load(e, fg.with_positions(fg.random_small(13)), tmp_path)
+    x = load_graph(e, fg.with_positions(fg.random_small(13)), tmp_path)
     valid = np.flatnonzero(x.state != fg.INVALID)
     sources = [int(valid[0]), int(valid[1]), int(valid[-1])]
-    full = _reference(ref, x, sources)
+    full = reference_fields(ref, x, SF, sources)
     rc, rh, _ = full
     budgets = np.array([_a_cost(rc[0], rh[0]), _below(_a_cost(rc[1], rh[1])), np.inf], F32)
     _check(e, full, sources, "routes: ", budget=budgets, want_full=with_parents)
@@ -347,7 +309,7 @@ def test_routes_of_a_bounded_solve(ref, engine, tmp_path, with_parents):
     for (f, t), (ids, pts, one), w in zip(pairs, got, want):
         at = f"field {f}, target {t}: "
         assert np.array_equal(ids, w.ids), at + f"ids {ids.tolist()} != {w.ids.tolist()}"
-        assert pts.shape == (len(w.ids), 3) and np.array_equal(_bits(pts), _bits(x.xyz[w.ids])), at
+        assert pts.shape == (len(w.ids), 3) and np.array_equal(bits(pts), bits(x.xyz[w.ids])), at
         assert one.num_nodes == len(w.ids), at
         for nm in ("cost", "path_length", "avg_risk"):
             assert _b1(getattr(one, nm)) == _b1(getattr(w, nm)), at + nm
@@ -373,11 +335,11 @@ def test_frontiers_early_exit_json_graph(engine, tmp_path):
     """Frontier nodes for certain (the random family marks an eighth of its nodes Frontier), at the 1 950-node size
     and the small one, whose second component has poses without a reachable Frontier node or with few."""
     engine.set_option("field_delta_scale", "4")
-    g = _random_large(*fg.RANDOM_LARGE[2000][2])
-    x = _load(engine, g, tmp_path)
+    g = random_large(*fg.RANDOM_LARGE[2000][2])
+    x = load_graph(engine, g, tmp_path)
     assert _same_frontiers(engine, g.pos[[0, 5, x.V // 3, x.V // 2, x.V - 1], :2].copy()) >= 2
     g = fg.with_positions(fg.random_small(3))
-    x = _load(engine, g, tmp_path, "small")
+    x = load_graph(engine, g, tmp_path, "small")
     assert _same_frontiers(engine, g.pos[[0, 1, x.V - 1, x.V // 2, 0], :2].copy()) >= 1
 
 
@@ -396,13 +358,13 @@ def test_helpers_early_exit(mountain_small):
     on = e.plan_many(poses[0], goals, early_exit=True)
     assert len(on) == 4 and any(len(p) for p, _ in off)
     for (pa, ia), (pb, ib) in zip(on, off):
-        assert np.array_equal(_bits(pa), _bits(pb))
+        assert np.array_equal(bits(pa), bits(pb))
         assert (ia.num_nodes, _b1(ia.cost), _b1(ia.path_length), _b1(ia.avg_risk)) == \
                (ib.num_nodes, _b1(ib.cost), _b1(ib.path_length), _b1(ib.avg_risk))
     nodes = [g.V // 9, g.V // 5, g.V // 3, g.V // 2, g.V - 2]
     c0, h0, n0 = e.cost_matrix(nodes)
     c1, h1, n1 = e.cost_matrix(nodes, early_exit=True)
-    assert np.array_equal(_bits(c0), _bits(c1)) and np.array_equal(h0, h1) and np.array_equal(n0, n1)
+    assert np.array_equal(bits(c0), bits(c1)) and np.array_equal(h0, h1) and np.array_equal(n0, n1)
     # reachable agrees with filtering cost_field
     cost, hops, _, info = e.cost_field(source_xy=poses[0])
     reached = np.sort(cost[hops >= 0])
@@ -410,7 +372,7 @@ def test_helpers_early_exit(mountain_small):
     ids, c, h = e.reachable(poses[0], budget)
     want = np.flatnonzero((hops >= 0) & (cost <= budget))
     assert 0 < want.size < reached.size
-    assert np.array_equal(ids, want) and np.array_equal(_bits(c), _bits(cost[want])) and np.array_equal(h, hops[want])
+    assert np.array_equal(ids, want) and np.array_equal(bits(c), bits(cost[want])) and np.array_equal(h, hops[want])
     e.close()
 
 
@@ -418,7 +380,7 @@ def test_errors(engine, tmp_path):
     import trg_planner
     from trg_planner._engine import TrgFieldInfo, _f, _i
     e = engine
-    x = _load(e, fg.with_positions(fg.random_small(1)), tmp_path)
+    x = load_graph(e, fg.with_positions(fg.random_small(1)), tmp_path)
     src = np.array([0, x.V - 1, 0], np.int32)
     out = np.zeros(3, np.int32)
 

@@ -17,41 +17,18 @@ import pytest
 import field_graphs as fg
 import field_ref
 import route_ref
-from test_gpu_cost_field_adversarial import PARAMS, _load, _random_large
+from field_support import (INVALID_ARG, MOUNTAIN, PARAMS, bits, engine, load_graph, random_large, ref,  # noqa: F401
+                           reference_fields, small_sources, with_isolated_node)
+from graph_support import obs_crop
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 SF = 3.0
-MOUNTAIN = dict(PARAMS, safety_factor=SF)
-INVALID_ARG = 1
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return field_ref.compile_reference(tmp_path_factory.mktemp("field_ref_routes"))
-
-
-@pytest.fixture(scope="module")
-def engine():
-    import trg_planner
-    e = trg_planner.Engine(safety_factor=SF, **PARAMS)
-    e.set_option("field_delta_scale", "4")
-    yield e
-    e.close()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).reshape(-1).view(np.uint32)
+FIELD_DELTA_SCALE = "4"  # of this module's `engine`
 
 
 def _reference_fields(ref, x, sources):
-    """(src, cost, hops, parent) of the host Dijkstra per field, one solve per distinct source."""
-    one = {}
-    for s in dict.fromkeys(int(s) for s in sources):
-        st, rc, rh, rp = field_ref.field_of_graph(ref, x, SF, s)
-        assert st == 0
-        one[s] = (s, rc, rh, rp)
-    return [one[int(s)] for s in sources]
+    return reference_fields(ref, x, SF, sources, stacked=False)
 
 
 def _raw(e, fields, targets, cap, ids=True, xyz=False):
@@ -74,7 +51,7 @@ def _assert_info(at, got, want):
     assert got.num_nodes == len(want.ids), at + f"num_nodes {got.num_nodes} != {len(want.ids)}"
     for name in ("cost", "path_length", "avg_risk"):
         a, b = F32(getattr(got, name)), F32(getattr(want, name))
-        assert _bits(a)[0] == _bits(b)[0], at + f"{name} {a!r} != {b!r}"
+        assert bits(a)[0] == bits(b)[0], at + f"{name} {a!r} != {b!r}"
 
 
 def _check_routes(e, x, fields_ref, pairs):
@@ -86,7 +63,7 @@ def _check_routes(e, x, fields_ref, pairs):
     for (f, t), (ids, pts, one), w in zip(pairs, got, want):
         at = f"field {f} (source {fields_ref[f][0]}), target {t}: "
         assert np.array_equal(ids, w.ids), at + f"ids {ids.tolist()} != {w.ids.tolist()}"
-        assert pts.shape == (len(w.ids), 3) and np.array_equal(_bits(pts), _bits(x.xyz[w.ids])), at + "positions"
+        assert pts.shape == (len(w.ids), 3) and np.array_equal(bits(pts), bits(x.xyz[w.ids])), at + "positions"
         _assert_info(at, one, w)
     assert 1 <= info.host_syncs <= 2, info.host_syncs
     return want, got
@@ -96,32 +73,13 @@ def _solve(e, sources, full=False, targets=None):
     return e.cost_fields(source_ids=[int(s) for s in sources], full=full, targets=targets)
 
 
-def _with_isolated_node(g):
-    V = len(g.state)
-    pos = np.concatenate([g.pos, g.pos.max(axis=0, keepdims=True) + F32([3.0, 3.0, 0.0])])
-    return fg.FieldGraph(np.append(g.rowptr, g.rowptr[-1]).astype(np.int32), g.col, g.w, g.dist,
-                         np.append(g.state, 0).astype(np.int32), pos.astype(np.float32))
-
-
-def _small_sources(g, m, seed):
-    """As the batch test's: a node of each component, a duplicate, an Invalid node and the isolated one first."""
-    V = len(g.state)
-    invalid = int(np.flatnonzero(g.state == fg.INVALID)[0])
-    half = (V - 1) // 2 + 3
-    first = int(np.flatnonzero(g.state[:half] != fg.INVALID)[0])
-    second = half + int(np.flatnonzero(g.state[half:V - 1] != fg.INVALID)[0])
-    kinds = [first, second, first, invalid, V - 1]
-    kinds = kinds[seed % 5:] + kinds[:seed % 5]
-    return (kinds + [(7 * i + seed) % V for i in range(m)])[:m]
-
-
 @pytest.mark.parametrize("m", [1, 5, 64])
 @pytest.mark.parametrize("seed", [0, 7, 13])
 def test_random_small(ref, engine, tmp_path, seed, m):
     """Every (field, node) pair as a route."""
-    g = _with_isolated_node(fg.with_positions(fg.random_small(seed)))
-    x = _load(engine, g, tmp_path)
-    sources = _small_sources(g, m, seed)
+    g = with_isolated_node(fg.with_positions(fg.random_small(seed)))
+    x = load_graph(engine, g, tmp_path)
+    sources = small_sources(g, m, seed)
     fields_ref = _reference_fields(ref, x, sources)
     _solve(engine, sources)
     pairs = [(k, t) for k in range(m) for t in range(x.V)]
@@ -137,7 +95,7 @@ ODDITIES = fg.oddities()
 @pytest.mark.parametrize("name", sorted(ODDITIES))
 def test_oddities(ref, engine, tmp_path, name):
     g, sources = ODDITIES[name]
-    x = _load(engine, g, tmp_path)
+    x = load_graph(engine, g, tmp_path)
     sources = (list(sources) * 3)[:3]
     fields_ref = _reference_fields(ref, x, sources)
     _solve(engine, sources)
@@ -157,7 +115,7 @@ def test_oddities(ref, engine, tmp_path, name):
 def test_chain(ref, engine, tmp_path, symmetric):
     """One route of 3 000 nodes (field 0 to the last node), and what the other three fields reach of it."""
     V = 3000
-    x = _load(engine, fg.chain(V, symmetric), tmp_path)
+    x = load_graph(engine, fg.chain(V, symmetric), tmp_path)
     sources = [0, V - 1, V // 2, V - 2]
     fields_ref = _reference_fields(ref, x, sources)
     _solve(engine, sources)
@@ -168,7 +126,7 @@ def test_chain(ref, engine, tmp_path, symmetric):
 def test_star_long_row(ref, engine, tmp_path):
     """Leaf -> hub -> leaf: the route edge out of the hub is searched in a row of 30 000."""
     deg = 30000
-    x = _load(engine, fg.star(deg), tmp_path)
+    x = load_graph(engine, fg.star(deg), tmp_path)
     sources = [1, 1 + deg // 2, 0]
     fields_ref = _reference_fields(ref, x, sources)
     _solve(engine, sources)
@@ -181,7 +139,7 @@ def test_star_long_row(ref, engine, tmp_path):
 
 
 def test_star_four_hubs(ref, engine, tmp_path):
-    x = _load(engine, fg.star(4096, 4), tmp_path)
+    x = load_graph(engine, fg.star(4096, 4), tmp_path)
     sources = [x.V - 1, 0, 4 + 4096 // 3]
     fields_ref = _reference_fields(ref, x, sources)
     _solve(engine, sources)
@@ -192,7 +150,7 @@ def test_star_four_hubs(ref, engine, tmp_path):
 def test_lattice(ref, engine, tmp_path):
     """Exact ties everywhere: the smallest-parent rule decides every step of every route."""
     n = 200
-    x = _load(engine, fg.lattice(n, n), tmp_path)
+    x = load_graph(engine, fg.lattice(n, n), tmp_path)
     centre = (n // 2) * n + n // 2
     sources = [0, n - 1, n * (n - 1), n * n - 1, centre, 0, n // 2, centre + 1]
     fields_ref = _reference_fields(ref, x, sources)
@@ -205,7 +163,7 @@ def test_lattice(ref, engine, tmp_path):
 @pytest.mark.parametrize("name", ["saturating_chain", "saturating_branch"])
 def test_saturating(ref, engine, tmp_path, name):
     """Routes to nodes reached at +inf."""
-    x = _load(engine, getattr(fg, name)(), tmp_path)
+    x = load_graph(engine, getattr(fg, name)(), tmp_path)
     sources = [0, 2, 1]
     fields_ref = _reference_fields(ref, x, sources)
     _solve(engine, sources)
@@ -218,7 +176,7 @@ LARGE = fg.RANDOM_LARGE[2000][2]  # V = 1 950
 
 def test_random_large(ref, engine, tmp_path):
     """16 fields x 700 random targets with duplicates: 11 200 routes, more groups than one pass of the grid."""
-    x = _load(engine, _random_large(*LARGE), tmp_path)
+    x = load_graph(engine, random_large(*LARGE), tmp_path)
     V = x.V
     sources = [0, V - 1, V // 4, 0] + [int(s) for s in np.random.default_rng(16).integers(0, V, size=12)]
     fields_ref = _reference_fields(ref, x, sources)
@@ -232,14 +190,14 @@ def test_random_large(ref, engine, tmp_path):
     for (f, t), (ids, pts, one), w in zip(pairs, got, want):
         at = f"field {f}, target {t}: "
         assert np.array_equal(ids, w.ids), at
-        assert np.array_equal(_bits(pts), _bits(x.xyz[w.ids])), at
+        assert np.array_equal(bits(pts), bits(x.xyz[w.ids])), at
         _assert_info(at, one, w)
     assert info.host_syncs <= 2
 
 
 def test_capacity(ref, engine, tmp_path):
     """cap at the total, one below it, in the middle of a route and at 0."""
-    x = _load(engine, fg.with_positions(fg.random_small(7)), tmp_path)
+    x = load_graph(engine, fg.with_positions(fg.random_small(7)), tmp_path)
     sources = [int(np.flatnonzero(x.state != fg.INVALID)[0]), x.V // 2]
     fields_ref = _reference_fields(ref, x, sources)
     solve = _solve(engine, sources)
@@ -259,7 +217,7 @@ def test_capacity(ref, engine, tmp_path):
         assert np.array_equal(off, np.minimum(full_off, cap)), at + str(off)
         assert np.array_equal(ids[:off[-1]], full_ids[:min(cap, total)]), at  # a truncated route keeps its first nodes
         assert np.all(ids[off[-1]:] == -7), at + "ids written past the last offset"
-        assert np.array_equal(_bits(pts[:off[-1]]), _bits(x.xyz[full_ids[:off[-1]]])), at
+        assert np.array_equal(bits(pts[:off[-1]]), bits(x.xyz[full_ids[:off[-1]]])), at
         for r, (one, w) in enumerate(zip(infos, want)):
             _assert_info(at + f"route {r}: ", one, w)  # full num_nodes and sums whatever fits
     # lengths only, then a second call with the right cap: complete, and no new solve
@@ -272,7 +230,7 @@ def test_capacity(ref, engine, tmp_path):
     assert info.host_syncs == 2 < solve["info"].host_syncs and info.rounds == 0
     # ids without positions, positions without ids
     off, ids, pts, infos, info = _raw(engine, f, t, cap, ids=False, xyz=True)
-    assert np.array_equal(off, full_off) and np.array_equal(_bits(pts[:cap]), _bits(x.xyz[full_ids]))
+    assert np.array_equal(off, full_off) and np.array_equal(bits(pts[:cap]), bits(x.xyz[full_ids]))
     # no routes at all
     off, ids, pts, infos, info = _raw(engine, [], [], 5)
     assert off.tolist() == [0]
@@ -281,7 +239,7 @@ def test_capacity(ref, engine, tmp_path):
 def test_retained_solve(ref, engine, tmp_path):
     """Routes after a solve without parents (the sweep runs late) equal those after one with; two calls in a row
     are equal; after another solve the routes follow it."""
-    x = _load(engine, fg.with_positions(fg.random_small(13)), tmp_path)
+    x = load_graph(engine, fg.with_positions(fg.random_small(13)), tmp_path)
     valid = np.flatnonzero(x.state != fg.INVALID)
     sources = [int(valid[0]), int(valid[1]), int(valid[-1])]
     fields_ref = _reference_fields(ref, x, sources)
@@ -291,7 +249,7 @@ def test_retained_solve(ref, engine, tmp_path):
     def snapshot():
         off, ids, _, infos, _ = _raw(engine, f, t, 3 * x.V * x.V)
         return (off.tolist(), ids[:off[-1]].tolist(),
-                [(i.num_nodes, _bits(i.cost)[0], _bits(i.path_length)[0], _bits(i.avg_risk)[0]) for i in infos])
+                [(i.num_nodes, bits(i.cost)[0], bits(i.path_length)[0], bits(i.avg_risk)[0]) for i in infos])
 
     full = _solve(engine, sources, full=True)
     _check_routes(engine, x, fields_ref, pairs)
@@ -325,7 +283,7 @@ def test_errors(ref, tmp_path, mountain_small):
         return str(ei.value)
 
     g = fg.with_positions(fg.random_small(1))
-    x = _load(e, g, tmp_path)
+    x = load_graph(e, g, tmp_path)
     assert "no cost-field solve" in refused([0], [0])  # before any solve
     sources = [0, x.V - 1]
     fields_ref = _reference_fields(ref, x, sources)
@@ -344,13 +302,12 @@ def test_errors(ref, tmp_path, mountain_small):
     assert ei.value.status == INVALID_ARG
     _check_routes(e, x, fields_ref, [(k, t) for k in range(2) for t in range(x.V)])  # still works
     # the graph changes: the solve is gone until the next one
-    x = _load(e, g, tmp_path, "again")
+    x = load_graph(e, g, tmp_path, "again")
     assert "earlier graph" in refused([0], [0])
     _solve(e, sources)
     _check_routes(e, x, fields_ref, [(0, x.V - 1), (1, 0)])
     e.close()
     # update_graph on a built graph
-    from test_gpu_update import _obs_crop
     e = trg_planner.Engine(**MOUNTAIN)
     e.set_sampler(7, 16)
     e.set_global_map(mountain_small)
@@ -358,7 +315,7 @@ def test_errors(ref, tmp_path, mountain_small):
     e.cost_fields(sources_xy=[(15.0, 15.0)], full=False)
     assert len(e.routes([0], [0])) == 1
     pose = (12.0, 12.0)
-    e.set_local_map(pose, _obs_crop(mountain_small, pose, 4.0, box=(pose[0] + 2.0, pose[1] + 1.0, 0.6)))
+    e.set_local_map(pose, obs_crop(mountain_small, pose, 4.0, box=(pose[0] + 2.0, pose[1] + 1.0, 0.6)))
     e.update_graph()
     assert "earlier graph" in refused([0], [0])
     e.cost_fields(sources_xy=[(15.0, 15.0)], full=False)
@@ -385,12 +342,7 @@ def _plan_refold(e, g, costs, pose, goal_xyz, id_of):
 
 def _resolve(e, xy):
     """The nodes the engine resolves positions to (trg_engine_cost_field_batch's resolve-only call)."""
-    from trg_planner._engine import _f, _i
-    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
-    got = np.empty(xy.shape[0], np.int32)
-    e._chk(e.L.trg_engine_cost_field_batch(e.h, xy.shape[0], None, _f(xy), None, None, None, None, 0, None, None,
-                                           _i(got), None, None))
-    return got
+    return e._resolve_nodes(xy)
 
 
 def _check_plan_many(ref, e, g, poses, goals):
@@ -407,7 +359,7 @@ def _check_plan_many(ref, e, g, poses, goals):
         assert len(got) == len(goals)
         for j, ((pts, one), w) in enumerate(zip(got, want)):
             at = f"pose {pose.tolist()}, goal {j} (node {goal_nodes[j]}): "
-            assert pts.shape == (len(w.ids), 3) and np.array_equal(_bits(pts), _bits(g.xyz[w.ids])), at
+            assert pts.shape == (len(w.ids), 3) and np.array_equal(bits(pts), bits(g.xyz[w.ids])), at
             _assert_info(at, one, w)
             reached += len(w.ids) > 0
             # A* on the same graph: its path is one walk, so its fp32 refold is no less than the field's cost at
@@ -425,7 +377,6 @@ def _check_plan_many(ref, e, g, poses, goals):
 
 def test_plan_many_device_built_graph(ref, mountain_small):
     import trg_planner
-    from test_gpu_update import _obs_crop
     e = trg_planner.Engine(**MOUNTAIN)
     e.set_sampler(7, 16)
     e.set_global_map(mountain_small)
@@ -439,7 +390,7 @@ def test_plan_many_device_built_graph(ref, mountain_small):
     print(f"device-built graph: {reached} routes with a path, {compared} compared with A* at the same goal node")
     assert reached >= 1 and compared >= 1
     pose = (12.0, 12.0)
-    e.set_local_map(pose, _obs_crop(mountain_small, pose, 4.0, box=(pose[0] + 2.0, pose[1] + 1.0, 0.6)))
+    e.set_local_map(pose, obs_crop(mountain_small, pose, 4.0, box=(pose[0] + 2.0, pose[1] + 1.0, 0.6)))
     e.update_graph()
     g2 = e.graph("global")
     reached, compared = _check_plan_many(ref, e, g2, poses, goals)

@@ -5,23 +5,9 @@ device-resident BFS and the sequential host replay -- must agree bit for bit on 
 import numpy as np
 import pytest
 
+from graph_support import graph_invariants
+
 pytestmark = pytest.mark.gpu
-
-
-def _invariants(g, expand_dist):
-    assert (g.state != -1).all() and (np.diff(g.rowptr) >= 1).all()       # cleanGraph post-condition
-    assert (g.dist < 2.5 * expand_dist).all()                              # trg.cpp:279
-    nz = g.w[g.w != 0]
-    assert ((nz >= 0.1) & (nz <= 0.4761)).all()                            # trg.cpp:359-363
-    src = np.repeat(np.arange(g.V, dtype=np.int64), np.diff(g.rowptr))
-    key = src * g.V + g.col
-    rev = g.col.astype(np.int64) * g.V + src
-    assert np.array_equal(np.sort(key), np.sort(rev))                      # edges are symmetric
-    assert np.unique(key).size == key.size                                 # wireEdge's dedupe
-    # nodes are at least robot_size apart only in a statistical sense (merge test is against the
-    # NEAREST node); what must hold exactly: every edge length equals the fp32 node distance
-    d = np.sqrt(((g.xyz[src, 0] - g.xyz[g.col, 0]) ** 2 + (g.xyz[src, 1] - g.xyz[g.col, 1]) ** 2))
-    assert np.abs(d - g.dist).max() < 1e-5
 
 
 def test_c2_size_against_the_live_oracle(oa, synth):
@@ -127,7 +113,7 @@ def test_c2_size_device_and_host_replay_agree(synth):
     assert np.array_equal(gd.w.view(np.uint32), gh.w.view(np.uint32))       # same kernels: bitwise
     for k in ("expanded_nodes", "trials", "samples", "created_nodes", "invalid_nodes"):
         assert sd[k] == sh[k], k
-    _invariants(gd, prm["expand_dist"])
+    graph_invariants(gd, prm["expand_dist"])
     # five start/goal pairs in the style of the reference's run_trg_planner.py:35-43
     e = trg_planner.Engine(**prm)
     e.set_sampler(7, 16)

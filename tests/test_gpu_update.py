@@ -5,18 +5,10 @@ import numpy as np
 import pytest
 
 from conftest import assert_graph_equal
+from graph_support import obs_crop
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-
-
-def _obs_crop(cloud, centre, half, box=None):
-    m = (np.abs(cloud[:, 0] - centre[0]) < half) & (np.abs(cloud[:, 1] - centre[1]) < half)
-    obs = cloud[m].copy()
-    if box is not None:  # raise a block of points: an obstacle that was not in the global map
-        b = (np.abs(obs[:, 0] - box[0]) < box[2]) & (np.abs(obs[:, 1] - box[1]) < box[2])
-        obs[b, 2] += np.float32(1.0) * (np.arange(b.sum()) % 2).astype(np.float32)
-    return obs
 
 
 @pytest.mark.parametrize("replay", ["device", "host"])
@@ -43,7 +35,7 @@ def test_update_graph_parity(oa, mountain_gentle, replay):
 
     poses = [(12.0, 12.0), (13.0, 12.5), (14.0, 13.0)]
     for k, pose in enumerate(poses):
-        obs = _obs_crop(mountain_gentle, pose, 4.0, box=(pose[0] + 2.0, pose[1] + 1.0, 0.6))
+        obs = obs_crop(mountain_gentle, pose, 4.0, box=(pose[0] + 2.0, pose[1] + 1.0, 0.6))
         e.set_local_map(pose, obs)
         o.set_local_map(pose, obs)
         o2.set_local_map(pose, obs)

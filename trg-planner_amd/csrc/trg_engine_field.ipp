@@ -22,7 +22,7 @@ inline float bits_float(uint32_t b) {
 // device buffers of the cost field, owned by the engine
 struct FieldBufs {
   DevArr ec, stats, ctrl;
-  DevArr key, q0, q1, far0, far1, stamp_near, stamp_far, parent, cost, hops;  // per item: m x V entries
+  DevArr key, q[2], far[2], stamp_near, stamp_far, parent, cost, hops;  // per item: m x V entries
   DevArr targets, cost_at, hops_at;                                           // n_targets, m x n_targets
   DevArr up_rowptr, up_col, up_w, up_dist, up_state;  // csr_global + nstate when the device build's CSR is stale
   uint64_t up_version = 0;   // graph_version of the upload (0: none)
@@ -87,13 +87,35 @@ TrgStatus field_grow(TrgEngine *e, DevArr &a, size_t bytes) {
   return e->fail(TRG_ERR_CAPACITY, "cost field: no device memory for " + std::to_string(bytes) + " bytes (" + e->err + ")");
 }
 
-TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) {
-  const auto t_total = Clock::now();
-  TrgStatus st = plan_prepare(e);  // graph present, CSR rows and node grid current
-  if (st != TRG_OK) return st;
-  const int V = (int)e->nx.size();
-  const int m = rq.m;
+// One solve on its way through the phases below: the request, what the checks derived from it, the graph and the
+// work arrays on the device, and the counts that end up in `info`.
+struct FieldRun {
+  const FieldRequest &rq;
+  TrgFieldInfo *info;
+  Clock::time_point t_total;
+  FieldDev F{};             // the kernels' view; V, m and N from the checks on
   FieldSources sources{};
+  FieldBounds budgets{};
+  bool bounded = false;     // some budget below +inf, or a settle mode ("Bounded fields")
+  bool gather = false;      // cost_at / hops_at are wanted
+  // the CSR the solve runs on: the device build's in place, or the engine's upload of csr_global
+  struct Graph {
+    const int *rowptr, *col, *state;
+    const float *w, *dist;
+    int E;
+    bool dev_csr;
+  } G{};
+  int syncs = 0, rounds = 0;
+};
+
+constexpr uint32_t FIELD_INF_BITS = 0x7f800000u;
+
+// Request checks, in the order a caller sees them: the sources (a resolve-only call ends after them), the targets,
+// the 32-bit item index, and the budgets as cost bits.
+TrgStatus field_check_request(TrgEngine *e, FieldRun &run) {
+  const FieldRequest &rq = run.rq;
+  const int V = run.F.V = (int)e->nx.size();
+  const int m = run.F.m = rq.m;
   for (int k = 0; k < m; ++k) {
     int src = rq.source_ids ? rq.source_ids[k] : -1;
     if (src == -1) {
@@ -106,15 +128,15 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
     if (src < 0 || src >= V)
       return e->fail(TRG_ERR_INVALID_ARG, m == 1 ? "cost field: source out of range"
                                                  : "cost field: source " + std::to_string(k) + " out of range");
-    sources.id[k] = src;
+    run.sources.id[k] = src;
   }
   if (rq.resolve_only) {
-    for (int k = 0; k < m; ++k) rq.sources_out[k] = sources.id[k];
-    info->source = sources.id[0];
-    info->ms_total = ms_since(t_total);
+    for (int k = 0; k < m; ++k) rq.sources_out[k] = run.sources.id[k];
+    run.info->source = run.sources.id[0];
+    run.info->ms_total = ms_since(run.t_total);
     return TRG_OK;
   }
-  const bool gather = rq.n_targets > 0 && (rq.cost_at || rq.hops_at);
+  run.gather = rq.n_targets > 0 && (rq.cost_at || rq.hops_at);
   if (rq.n_targets > 0 && !rq.targets) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no targets");
   for (int j = 0; j < rq.n_targets; ++j)
     if (rq.targets[j] < 0 || rq.targets[j] >= V)
@@ -124,19 +146,22 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
   if (N64 > (long long)INT_MAX - (1 << 20))
     return e->fail(TRG_ERR_CAPACITY, "cost field: " + std::to_string(m) + " fields of " + std::to_string(V) +
                                          " nodes do not fit a 32-bit item index");
-  if (gather && (long long)m * rq.n_targets > (long long)INT_MAX - (1 << 20))
+  if (run.gather && (long long)m * rq.n_targets > (long long)INT_MAX - (1 << 20))
     return e->fail(TRG_ERR_CAPACITY, "cost field: too many targets");
-  const int N = (int)N64;
-  // A bounded solve ("Bounded fields"): some budget below +inf, or a settle mode.  Without
-  // either, the launches below are those of a solve that knows nothing of bounds.
-  FieldBounds budgets;
-  bool bounded = rq.settle != TRG_FIELD_SETTLE_NONE;
-  const uint32_t inf_bits = float_bits(std::numeric_limits<float>::infinity());
+  run.F.N = (int)N64;
+  // A bounded solve: some budget below +inf, or a settle mode.  Without either, the launches are those of a solve
+  // that knows nothing of bounds.
+  run.bounded = rq.settle != TRG_FIELD_SETTLE_NONE;
   for (int k = 0; k < m; ++k) {
     const float b = rq.budget ? rq.budget[k] : std::numeric_limits<float>::infinity();
-    budgets.bits[k] = b == 0.0f ? 0u : float_bits(b);  // (-0.0 orders as +0.0)
-    bounded = bounded || budgets.bits[k] != inf_bits;
+    run.budgets.bits[k] = b == 0.0f ? 0u : float_bits(b);  // (-0.0 orders as +0.0)
+    run.bounded = run.bounded || run.budgets.bits[k] != FIELD_INF_BITS;
   }
+  return TRG_OK;
+}
+
+// the engine's field buffers; from here on the retained solve is gone
+TrgStatus field_begin(TrgEngine *e, FieldRun &) {
   if (!e->field) e->field.reset(new FieldBufs());
   FieldBufs &fb = *e->field;
   fb.last = FieldBufs::Last{};  // from here on the work arrays change
@@ -146,191 +171,222 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
   HIPCHK(e, fb.h_bound.ensure(TRG_FIELD_BATCH_MAX));
   HIPCHK(e, fb.t0.create());
   HIPCHK(e, fb.t1.create());
-  hipStream_t s = e->s_main;
-  int syncs = 0;
+  return TRG_OK;
+}
 
-  // the graph on the device: the device build's CSR in place, else csr_global uploaded once per version
+// the graph on the device: the device build's CSR in place, else csr_global uploaded once per version
+TrgStatus field_graph(TrgEngine *e, FieldRun &run) {
+  FieldBufs &fb = *e->field;
+  hipStream_t s = e->s_main;
   const Csr &G = e->csr_global;
-  const int E = G.rowptr.empty() ? 0 : G.rowptr[V];
-  const int *d_rowptr, *d_col, *d_state;
-  const float *d_w, *d_dist;
+  const int V = run.F.V, E = G.rowptr.empty() ? 0 : G.rowptr[V];
   if (e->dev_csr_valid && e->bfs && e->bfs->rowptr_new.p) {
     const BfsBuffers &bb = *e->bfs;
-    d_rowptr = (const int *)bb.rowptr_new.p;
-    d_col = (const int *)bb.col2.p;
-    d_w = (const float *)bb.w2.p;
-    d_dist = (const float *)bb.dist2.p;
-    d_state = (const int *)bb.state2.p;
+    run.G = {(const int *)bb.rowptr_new.p, (const int *)bb.col2.p, (const int *)bb.state2.p,
+             (const float *)bb.w2.p, (const float *)bb.dist2.p, E, true};
   } else {
     if (fb.up_version != e->graph_version) {
       fb.up_version = 0;
-      if ((st = ensure_bytes(e, fb.up_rowptr, ((size_t)V + 1) * sizeof(int))) != TRG_OK) return st;
-      if ((st = ensure_bytes(e, fb.up_state, (size_t)V * sizeof(int))) != TRG_OK) return st;
-      if ((st = ensure_bytes(e, fb.up_col, (size_t)E * sizeof(int) + 16)) != TRG_OK) return st;
-      if ((st = ensure_bytes(e, fb.up_w, (size_t)E * sizeof(float) + 16)) != TRG_OK) return st;
-      if ((st = ensure_bytes(e, fb.up_dist, (size_t)E * sizeof(float) + 16)) != TRG_OK) return st;
-      HIPCHK(e, hipMemcpyAsync(fb.up_rowptr.p, G.rowptr.data(), ((size_t)V + 1) * sizeof(int),
-                               hipMemcpyHostToDevice, s));
-      HIPCHK(e, hipMemcpyAsync(fb.up_state.p, e->nstate.data(), (size_t)V * sizeof(int), hipMemcpyHostToDevice, s));
-      if (E) {
-        HIPCHK(e, hipMemcpyAsync(fb.up_col.p, G.col.data(), (size_t)E * sizeof(int), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(fb.up_w.p, G.w.data(), (size_t)E * sizeof(float), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(fb.up_dist.p, G.dist.data(), (size_t)E * sizeof(float), hipMemcpyHostToDevice, s));
-      }
+      const struct { DevArr &a; const void *src; size_t bytes, slack; } up[] = {
+          {fb.up_rowptr, G.rowptr.data(), ((size_t)V + 1) * sizeof(int), 0},
+          {fb.up_state, e->nstate.data(), (size_t)V * sizeof(int), 0},
+          {fb.up_col, G.col.data(), (size_t)E * sizeof(int), 16},
+          {fb.up_w, G.w.data(), (size_t)E * sizeof(float), 16},
+          {fb.up_dist, G.dist.data(), (size_t)E * sizeof(float), 16}};
+      for (const auto &u : up)
+        if (const TrgStatus st = ensure_bytes(e, u.a, u.bytes + u.slack); st != TRG_OK) return st;
+      for (const auto &u : up)
+        if (u.bytes) HIPCHK(e, hipMemcpyAsync(u.a.p, u.src, u.bytes, hipMemcpyHostToDevice, s));
       fb.up_version = e->graph_version;
     }
-    d_rowptr = (const int *)fb.up_rowptr.p;
-    d_col = (const int *)fb.up_col.p;
-    d_w = (const float *)fb.up_w.p;
-    d_dist = (const float *)fb.up_dist.p;
-    d_state = (const int *)fb.up_state.p;
+    run.G = {(const int *)fb.up_rowptr.p, (const int *)fb.up_col.p, (const int *)fb.up_state.p,
+             (const float *)fb.up_w.p, (const float *)fb.up_dist.p, E, false};
   }
   HIPCHK(e, hipEventRecord(fb.t0, s));
+  return TRG_OK;
+}
 
-  // edge costs and the bad-cost flag, once per graph version and safety factor
+// edge costs and the bad-cost flag, once per graph version and safety factor (one host wait when they are computed)
+TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
+  FieldBufs &fb = *e->field;
+  hipStream_t s = e->s_main;
+  const FieldRun::Graph &G = run.G;
   const float sf = e->prm.safety_factor;
-  if (fb.ec_version != e->graph_version || fb.ec_col != (const void *)d_col || fb.ec_sf != sf) {
+  if (fb.ec_version != e->graph_version || fb.ec_col != (const void *)G.col || fb.ec_sf != sf) {
     fb.ec_version = 0;
-    if ((st = ensure_bytes(e, fb.ec, (size_t)E * sizeof(float) + 16)) != TRG_OK) return st;
+    TrgStatus st;
+    if ((st = ensure_bytes(e, fb.ec, (size_t)G.E * sizeof(float) + 16)) != TRG_OK) return st;
     if ((st = ensure_bytes(e, fb.stats, sizeof(FieldEdgeStats))) != TRG_OK) return st;
-    launch_field_edge_cost(d_col, d_w, d_dist, d_state, V, E, sf, (float *)fb.ec.p, (FieldEdgeStats *)fb.stats.p, s);
+    launch_field_edge_cost(G.col, G.w, G.dist, G.state, run.F.V, G.E, sf, (float *)fb.ec.p,
+                           (FieldEdgeStats *)fb.stats.p, s);
     HIPCHK(e, hipMemcpyAsync(fb.h_stats, fb.stats.p, sizeof(FieldEdgeStats), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
-    syncs++;
+    run.syncs++;
     fb.bad_cost = fb.h_stats->bad != 0;
     fb.mean_cost = fb.h_stats->count ? fb.h_stats->sum / fb.h_stats->count : 0.0;
     fb.ec_version = e->graph_version;
-    fb.ec_col = d_col;
+    fb.ec_col = G.col;
     fb.ec_sf = sf;
   }
   if (fb.bad_cost) return e->fail(TRG_ERR_INVALID_ARG, "cost field: an edge cost is negative or not finite");
+  return TRG_OK;
+}
 
-  // work arrays, per item
-  const size_t nV = (size_t)N + 4;
-  const auto grow = [e](DevArr &a, size_t bytes) { return field_grow(e, a, bytes); };
-  if ((st = grow(fb.key, nV * sizeof(unsigned long long))) != TRG_OK) return st;
-  for (DevArr *a : {&fb.q0, &fb.q1, &fb.far0, &fb.far1, &fb.stamp_near, &fb.stamp_far, &fb.parent, &fb.cost,
+// work arrays, per item, and the kernels' view of them
+TrgStatus field_work_arrays(TrgEngine *e, FieldRun &run) {
+  FieldBufs &fb = *e->field;
+  const size_t nV = (size_t)run.F.N + 4;
+  TrgStatus st;
+  if ((st = field_grow(e, fb.key, nV * sizeof(unsigned long long))) != TRG_OK) return st;
+  for (DevArr *a : {&fb.q[0], &fb.q[1], &fb.far[0], &fb.far[1], &fb.stamp_near, &fb.stamp_far, &fb.parent, &fb.cost,
                     &fb.hops})
-    if ((st = grow(*a, nV * sizeof(int))) != TRG_OK) return st;
+    if ((st = field_grow(e, *a, nV * sizeof(int))) != TRG_OK) return st;
   if ((st = ensure_bytes(e, fb.ctrl, sizeof(FieldCtrl))) != TRG_OK) return st;
-  FieldDev F{};
-  F.rowptr = d_rowptr;
-  F.col = d_col;
+  FieldDev &F = run.F;
+  F.rowptr = run.G.rowptr;
+  F.col = run.G.col;
   F.ec = (const float *)fb.ec.p;
-  F.V = V;
-  F.m = m;
-  F.N = N;
   F.key = (unsigned long long *)fb.key.p;
-  F.q[0] = (int *)fb.q0.p;
-  F.q[1] = (int *)fb.q1.p;
-  F.far[0] = (int *)fb.far0.p;
-  F.far[1] = (int *)fb.far1.p;
+  for (int i = 0; i < 2; ++i) {
+    F.q[i] = (int *)fb.q[i].p;
+    F.far[i] = (int *)fb.far[i].p;
+  }
   F.stamp_near = (int *)fb.stamp_near.p;
   F.stamp_far = (unsigned *)fb.stamp_far.p;
   F.parent = (int *)fb.parent.p;
   F.ctrl = (FieldCtrl *)fb.ctrl.p;
+  return TRG_OK;
+}
 
-  // near-far rounds, enqueued in batches; the bucket width is a fixed multiple of the mean edge cost.
-  // Pass 1 finds the least costs, pass 2 the hops over the tight edges (trg_field.hip).
+// Near-far rounds, enqueued in batches; the bucket width is a fixed multiple of the mean edge cost.  Pass 1 finds
+// the least costs, pass 2 the hops over the tight edges (trg_field.hip).
+TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
+  FieldBufs &fb = *e->field;
+  const FieldRequest &rq = run.rq;
+  FieldDev &F = run.F;
+  hipStream_t s = e->s_main;
   const float delta = fb.mean_cost > 0.0 ? (float)(e->field_delta_scale * fb.mean_cost) : 0.0f;
-  const long long cap = 4LL * N + 64;
-  int rounds = 0;
-  const bool settle = rq.settle != TRG_FIELD_SETTLE_NONE;
-  if (settle) {  // the settle step reads the targets during pass 1
-    if ((st = grow(fb.targets, (size_t)rq.n_targets * sizeof(int))) != TRG_OK) return st;
+  const long long cap = 4LL * F.N + 64;
+  if (rq.settle != TRG_FIELD_SETTLE_NONE || run.gather) {  // the target list: read by the settle step, the gather
+    const TrgStatus st = field_grow(e, fb.targets, (size_t)rq.n_targets * sizeof(int));
+    if (st != TRG_OK) return st;
     HIPCHK(e, hipMemcpyAsync(fb.targets.p, rq.targets, (size_t)rq.n_targets * sizeof(int), hipMemcpyHostToDevice, s));
   }
-  if (bounded) launch_field_bounds(F, budgets, s);
+  const FieldSettle under{(const int *)fb.targets.p, rq.n_targets, rq.settle};
+  if (run.bounded) launch_field_bounds(F, run.budgets, s);
   for (int pass = 0; pass < 2; ++pass) {
     // the bounds act in pass 1 only: it ends with the keys above them removed, and no pass-2 extension matches
     // the tight word of a node without a key
-    const bool under_bounds = bounded && pass == 0;
+    const bool under_bounds = run.bounded && pass == 0;
     F.tight = pass ? (const unsigned *)fb.cost.p : nullptr;
-    launch_field_init(F, sources, delta, s);
+    launch_field_init(F, run.sources, delta, s);
     for (int round = 0;;) {
-      for (int i = 0; i < FIELD_BATCH; ++i, ++round) {
-        if (under_bounds)
-          launch_field_round_bounded(F, round, (const int *)fb.targets.p, rq.n_targets, rq.settle, s);
-        else
-          launch_field_round(F, round, s);
-      }
+      for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s, under_bounds ? &under : nullptr);
       HIPCHK(e, hipGetLastError());
       HIPCHK(e, hipMemcpyAsync(fb.h_state, &F.ctrl->s, sizeof(FieldState), hipMemcpyDeviceToHost, s));
       HIPCHK(e, hipStreamSynchronize(s));
-      syncs++;
+      run.syncs++;
       if (fb.h_state->overflow) return e->fail(TRG_ERR_DEVICE, "cost field: queue overflow");
       if (fb.h_state->work == 0) break;
       if (fb.h_state->rounds >= cap) return e->fail(TRG_ERR_DEVICE, "cost field did not converge");
     }
-    rounds += fb.h_state->rounds;
+    run.rounds += fb.h_state->rounds;
     if (under_bounds) {
       launch_field_trim(F, s);
-      HIPCHK(e, hipMemcpyAsync(fb.h_bound, F.ctrl->bound, (size_t)m * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipMemcpyAsync(fb.h_bound, F.ctrl->bound, (size_t)F.m * sizeof(unsigned), hipMemcpyDeviceToHost, s));
     }
     if (pass == 0) launch_field_cost_bits(F, (unsigned *)fb.cost.p, s);
   }
+  return TRG_OK;
+}
+
+// finish, gather, the copies of only what was asked for, `info`, and the retained-solve record
+TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
+  FieldBufs &fb = *e->field;
+  const FieldRequest &rq = run.rq;
+  const FieldDev &F = run.F;
+  hipStream_t s = e->s_main;
+  const int m = F.m;
+  const size_t nN = (size_t)F.N, nat = (size_t)m * rq.n_targets;
   launch_field_finish(F, (float *)fb.cost.p, (int *)fb.hops.p, rq.parent != nullptr, s);
-  if (gather) {
-    const size_t nt = (size_t)rq.n_targets, nat = (size_t)m * nt;
-    if ((st = grow(fb.targets, nt * sizeof(int))) != TRG_OK) return st;
-    if ((st = grow(fb.cost_at, nat * sizeof(float))) != TRG_OK) return st;
-    if ((st = grow(fb.hops_at, nat * sizeof(int))) != TRG_OK) return st;
-    if (!settle) HIPCHK(e, hipMemcpyAsync(fb.targets.p, rq.targets, nt * sizeof(int), hipMemcpyHostToDevice, s));
+  if (run.gather) {
+    TrgStatus st;
+    if ((st = field_grow(e, fb.cost_at, nat * sizeof(float))) != TRG_OK) return st;
+    if ((st = field_grow(e, fb.hops_at, nat * sizeof(int))) != TRG_OK) return st;
     launch_field_gather(F, (const int *)fb.targets.p, rq.n_targets, rq.cost_at ? (float *)fb.cost_at.p : nullptr,
                         rq.hops_at ? (int *)fb.hops_at.p : nullptr, s);
   }
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
   HIPCHK(e, hipMemcpyAsync(fb.h_reached, F.ctrl->reached, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
-  // only what was asked for comes back
-  const size_t nN = (size_t)N;
   if (rq.cost) HIPCHK(e, hipMemcpyAsync(rq.cost, fb.cost.p, nN * sizeof(float), hipMemcpyDeviceToHost, s));
   if (rq.hops) HIPCHK(e, hipMemcpyAsync(rq.hops, fb.hops.p, nN * sizeof(int), hipMemcpyDeviceToHost, s));
   if (rq.parent) HIPCHK(e, hipMemcpyAsync(rq.parent, fb.parent.p, nN * sizeof(int), hipMemcpyDeviceToHost, s));
-  if (gather) {
-    const size_t nat = (size_t)m * rq.n_targets;
-    if (rq.cost_at) HIPCHK(e, hipMemcpyAsync(rq.cost_at, fb.cost_at.p, nat * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (rq.hops_at) HIPCHK(e, hipMemcpyAsync(rq.hops_at, fb.hops_at.p, nat * sizeof(int), hipMemcpyDeviceToHost, s));
-  }
+  if (run.gather && rq.cost_at)
+    HIPCHK(e, hipMemcpyAsync(rq.cost_at, fb.cost_at.p, nat * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (run.gather && rq.hops_at)
+    HIPCHK(e, hipMemcpyAsync(rq.hops_at, fb.hops_at.p, nat * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
-  syncs++;
+  run.syncs++;
   float ms_dev = 0.0f;
   HIPCHK(e, hipEventElapsedTime(&ms_dev, fb.t0, fb.t1));
   long long reached = 0;
   for (int k = 0; k < m; ++k) {
     reached += fb.h_reached[k];
-    if (rq.sources_out) rq.sources_out[k] = sources.id[k];
+    if (rq.sources_out) rq.sources_out[k] = run.sources.id[k];
     if (rq.reached_out) rq.reached_out[k] = fb.h_reached[k];
-    if (rq.bound_out) rq.bound_out[k] = bits_float(bounded ? fb.h_bound[k] : inf_bits);
+    if (rq.bound_out) rq.bound_out[k] = bits_float(run.bounded ? fb.h_bound[k] : FIELD_INF_BITS);
   }
-  info->source = sources.id[0];
-  info->reached = (int32_t)reached;
-  info->rounds = rounds;
-  info->host_syncs = syncs;
-  info->ms_device = ms_dev;
-  info->ms_total = ms_since(t_total);
-  fb.last.version = e->graph_version;
-  fb.last.F = F;
+  run.info->source = run.sources.id[0];
+  run.info->reached = (int32_t)reached;
+  run.info->rounds = run.rounds;
+  run.info->host_syncs = run.syncs;
+  run.info->ms_device = ms_dev;
+  run.info->ms_total = ms_since(run.t_total);
+  fb.last = FieldBufs::Last{e->graph_version, F, run.G.w, run.G.dist, run.sources, rq.parent != nullptr, run.G.dev_csr};
   fb.last.F.tight = nullptr;  // (its array holds the cost output now)
-  fb.last.w = d_w;
-  fb.last.dist = d_dist;
-  fb.last.sources = sources;
-  fb.last.parents = rq.parent != nullptr;
-  fb.last.dev_csr = d_col != (const int *)fb.up_col.p;
   return TRG_OK;
 }
 
-// the entries' common guard
-TrgStatus field_guarded(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) {
+TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) {
+  FieldRun run{rq, info, Clock::now()};
+  TrgStatus st = plan_prepare(e);  // graph present, CSR rows and node grid current
+  if (st != TRG_OK) return st;
+  if ((st = field_check_request(e, run)) != TRG_OK || rq.resolve_only) return st;
+  for (const auto phase : {field_begin, field_graph, field_edge_costs, field_work_arrays,
+                           field_passes, field_outputs})
+    if ((st = phase(e, run)) != TRG_OK) return st;
+  return TRG_OK;
+}
+
+// The C entries' common frame: `info` defaulted, zeroed and without a source, then `body(info)` behind the
+// exception ladder; `call` is the entry's message prefix.
+template <typename Body>
+TrgStatus field_entry(TrgEngine *e, TrgFieldInfo *info, const char *call, Body body) {
+  REQUIRE_DEVICE(e);
+  TrgFieldInfo local{};
+  if (!info) info = &local;
+  *info = TrgFieldInfo{};
+  info->source = -1;
   try {
-    return field_solve(e, rq, info);
+    return body(info);
   } catch (const std::bad_alloc &) {
-    return e->fail(TRG_ERR_CAPACITY, "cost field: out of host memory");
+    return e->fail(TRG_ERR_CAPACITY, std::string(call) + ": out of host memory");
   } catch (const std::exception &x) {
-    return e->fail(TRG_ERR_DEVICE, std::string("cost field: ") + x.what());
+    return e->fail(TRG_ERR_DEVICE, std::string(call) + ": " + x.what());
   } catch (...) {
-    return e->fail(TRG_ERR_DEVICE, "cost field: unknown exception");
+    return e->fail(TRG_ERR_DEVICE, std::string(call) + ": unknown exception");
   }
+}
+
+// the retained solve for `call` ("cost field routes", ...), or that call's refusal
+TrgStatus field_retained(TrgEngine *e, const char *call, FieldBufs::Last *&last) {
+  if (!e->field || e->field->last.version == 0)
+    return e->fail(TRG_ERR_INVALID_ARG, std::string(call) + ": no cost-field solve is retained (solve first)");
+  last = &e->field->last;
+  if (last->version != e->graph_version || (last->dev_csr && !e->dev_csr_valid))
+    return e->fail(TRG_ERR_INVALID_ARG, std::string(call) + ": the retained solve is of an earlier graph (solve again)");
+  return TRG_OK;
 }
 
 static_assert(sizeof(TrgRouteInfo) == sizeof(FieldRouteInfo) && offsetof(TrgRouteInfo, num_nodes) == 0 &&
@@ -355,12 +411,11 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   const auto t_total = Clock::now();
   if (rq.n < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: n_routes < 0");
   if (rq.cap < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: cap < 0");
-  if (!e->field || e->field->last.version == 0)
-    return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: no cost-field solve is retained (solve first)");
+  FieldBufs::Last *last;
+  TrgStatus st = field_retained(e, "cost field routes", last);
+  if (st != TRG_OK) return st;
   FieldBufs &fb = *e->field;
-  if (fb.last.version != e->graph_version || (fb.last.dev_csr && !e->dev_csr_valid))
-    return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: the retained solve is of an earlier graph (solve again)");
-  const FieldDev &F = fb.last.F;
+  const FieldDev &F = last->F;
   if (rq.n > 0 && (!rq.field || !rq.target || !rq.offsets))
     return e->fail(TRG_ERR_INVALID_ARG, "cost field routes: null route_field, route_target or offsets");
   for (int r = 0; r < rq.n; ++r) {
@@ -379,7 +434,6 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   }
   const bool want_ids = (rq.node_ids || rq.xyz) && rq.cap > 0;
   const size_t n = (size_t)rq.n;
-  TrgStatus st;
   if ((st = field_grow(e, fb.route_field, n * sizeof(int))) != TRG_OK) return st;
   if ((st = field_grow(e, fb.route_target, n * sizeof(int))) != TRG_OK) return st;
   if ((st = field_grow(e, fb.route_info, n * sizeof(FieldRouteInfo))) != TRG_OK) return st;
@@ -390,10 +444,10 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   HIPCHK(e, hipMemcpyAsync(fb.route_field.p, rq.field, n * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(e, hipMemcpyAsync(fb.route_target.p, rq.target, n * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(e, hipEventRecord(fb.t0, s));
-  if (!fb.last.parents) {
+  if (!last->parents) {
     launch_field_parents_late(F, s);
     HIPCHK(e, hipGetLastError());
-    fb.last.parents = true;
+    last->parents = true;
   }
   const int *d_field = (const int *)fb.route_field.p, *d_target = (const int *)fb.route_target.p;
   std::vector<int32_t> ids;
@@ -416,9 +470,9 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
     HIPCHK(e, hipMemcpyAsync(fb.route_off.p, rq.offsets, (n + 1) * sizeof(int), hipMemcpyHostToDevice, s));
   }
   std::vector<FieldRouteInfo> infos(n);
-  launch_field_route_walk(F, fb.last.w, fb.last.dist, d_field, d_target, rq.n,
+  launch_field_route_walk(F, last->w, last->dist, d_field, d_target, rq.n,
                           want_ids ? (const int *)fb.route_off.p : nullptr, want_ids ? (int *)fb.route_ids.p : nullptr,
-                          (FieldRouteInfo *)fb.route_info.p, fb.last.sources, s);
+                          (FieldRouteInfo *)fb.route_info.p, last->sources, s);
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
   int32_t *ids_out = rq.node_ids;
@@ -461,19 +515,17 @@ TrgStatus field_reached(TrgEngine *e, int32_t field, int32_t *node_ids, float *c
                         int32_t *n_out, TrgFieldInfo *info) {
   const auto t_total = Clock::now();
   if (cap < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field reached: cap < 0");
-  if (!e->field || e->field->last.version == 0)
-    return e->fail(TRG_ERR_INVALID_ARG, "cost field reached: no cost-field solve is retained (solve first)");
+  FieldBufs::Last *last;
+  TrgStatus st = field_retained(e, "cost field reached", last);
+  if (st != TRG_OK) return st;
   FieldBufs &fb = *e->field;
-  if (fb.last.version != e->graph_version || (fb.last.dev_csr && !e->dev_csr_valid))
-    return e->fail(TRG_ERR_INVALID_ARG, "cost field reached: the retained solve is of an earlier graph (solve again)");
-  const FieldDev &F = fb.last.F;
+  const FieldDev &F = last->F;
   if (field < 0 || field >= F.m)
     return e->fail(TRG_ERR_INVALID_ARG, "cost field reached: field " + std::to_string(field) +
                                             " out of range (the solve has " + std::to_string(F.m) + ")");
   const bool want = cap > 0 && (node_ids || cost || hops);
   const int room = want ? std::min<int>(cap, F.V) : 0;
   const size_t nb = ((size_t)F.V + 255) / 256;
-  TrgStatus st;
   if ((st = field_grow(e, fb.list_counts, (nb + 1) * sizeof(int))) != TRG_OK) return st;
   if ((st = field_grow(e, fb.list_off, (nb + 1) * sizeof(int))) != TRG_OK) return st;
   if ((st = field_grow(e, fb.list_tmp, (nb / 2048 + 8) * sizeof(int))) != TRG_OK) return st;
@@ -505,7 +557,7 @@ TrgStatus field_reached(TrgEngine *e, int32_t field, int32_t *node_ids, float *c
   if (n_out) *n_out = total;
   float ms_dev = 0.0f;
   HIPCHK(e, hipEventElapsedTime(&ms_dev, fb.t0, fb.t1));
-  info->source = fb.last.sources.id[field];
+  info->source = last->sources.id[field];
   info->reached = total;
   info->host_syncs = syncs;
   info->ms_device = ms_dev;
@@ -519,20 +571,11 @@ extern "C" {
 
 TrgStatus trg_engine_cost_field(TrgEngine *e, int32_t source_id, const float source_xy[2], float *cost,
                                 int32_t *hops, int32_t *parent, TrgFieldInfo *info) {
-  REQUIRE_DEVICE(e);
-  TrgFieldInfo local{};
-  if (!info) info = &local;
-  *info = TrgFieldInfo{};
-  info->source = -1;
-  if (source_id < -1) return e->fail(TRG_ERR_INVALID_ARG, "cost field: source out of range");
-  FieldRequest rq{};
-  rq.m = 1;
-  rq.source_ids = &source_id;
-  rq.source_xy = source_xy;
-  rq.cost = cost;
-  rq.hops = hops;
-  rq.parent = parent;
-  return field_guarded(e, rq, info);
+  return field_entry(e, info, "cost field", [&](TrgFieldInfo *out) {
+    if (source_id < -1) return e->fail(TRG_ERR_INVALID_ARG, "cost field: source out of range");
+    const FieldRequest rq{1, &source_id, source_xy, cost, hops, parent};  // no targets, budgets or settle mode
+    return field_solve(e, rq, out);
+  });
 }
 
 TrgStatus trg_engine_cost_field_batch(TrgEngine *e, int32_t m, const int32_t *source_ids, const float *source_xy,
@@ -548,73 +591,48 @@ TrgStatus trg_engine_cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *
                                         int32_t *parent, const int32_t *targets, int32_t n_targets, float *cost_at,
                                         int32_t *hops_at, int32_t *sources_out, int32_t *reached_out,
                                         float *bound_out, TrgFieldInfo *info) {
-  REQUIRE_DEVICE(e);
   // every output NULL but sources_out: the caller wants the sources resolved, nothing solved
   const bool resolve_only =
       sources_out && !cost && !hops && !parent && !cost_at && !hops_at && !reached_out && !bound_out && !info;
-  TrgFieldInfo local{};
-  if (!info) info = &local;
-  *info = TrgFieldInfo{};
-  info->source = -1;
-  if (m < 1 || m > TRG_FIELD_BATCH_MAX)
-    return e->fail(TRG_ERR_INVALID_ARG, "cost field: a batch of " + std::to_string(m) + " fields (1.." +
-                                            std::to_string(TRG_FIELD_BATCH_MAX) + ")");
-  if (n_targets < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field: n_targets < 0");
-  if (!source_ids && !source_xy) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no sources");
-  if (source_ids)
-    for (int k = 0; k < m; ++k)
-      if (source_ids[k] < -1)
-        return e->fail(TRG_ERR_INVALID_ARG, "cost field: source " + std::to_string(k) + " out of range");
-  if (budget)
-    for (int k = 0; k < m; ++k)
-      if (!(budget[k] >= 0.0f))
-        return e->fail(TRG_ERR_INVALID_ARG, "cost field: the budget of field " + std::to_string(k) +
-                                                " is negative or not a number");
-  if (settle != TRG_FIELD_SETTLE_NONE && settle != TRG_FIELD_SETTLE_ANY && settle != TRG_FIELD_SETTLE_ALL)
-    return e->fail(TRG_ERR_INVALID_ARG, "cost field: settle mode " + std::to_string(settle) + " (0..2)");
-  if (settle != TRG_FIELD_SETTLE_NONE && (n_targets == 0 || !targets))
-    return e->fail(TRG_ERR_INVALID_ARG, "cost field: settle mode " + std::to_string(settle) + " needs targets");
-  FieldRequest rq{m, source_ids, source_xy, cost, hops, parent, targets, n_targets, cost_at, hops_at, sources_out,
-                  reached_out, resolve_only, budget, settle, bound_out};
-  return field_guarded(e, rq, info);
+  return field_entry(e, info, "cost field", [&](TrgFieldInfo *out) {
+    if (m < 1 || m > TRG_FIELD_BATCH_MAX)
+      return e->fail(TRG_ERR_INVALID_ARG, "cost field: a batch of " + std::to_string(m) + " fields (1.." +
+                                              std::to_string(TRG_FIELD_BATCH_MAX) + ")");
+    if (n_targets < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field: n_targets < 0");
+    if (!source_ids && !source_xy) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no sources");
+    if (source_ids)
+      for (int k = 0; k < m; ++k)
+        if (source_ids[k] < -1)
+          return e->fail(TRG_ERR_INVALID_ARG, "cost field: source " + std::to_string(k) + " out of range");
+    if (budget)
+      for (int k = 0; k < m; ++k)
+        if (!(budget[k] >= 0.0f))
+          return e->fail(TRG_ERR_INVALID_ARG, "cost field: the budget of field " + std::to_string(k) +
+                                                  " is negative or not a number");
+    if (settle != TRG_FIELD_SETTLE_NONE && settle != TRG_FIELD_SETTLE_ANY && settle != TRG_FIELD_SETTLE_ALL)
+      return e->fail(TRG_ERR_INVALID_ARG, "cost field: settle mode " + std::to_string(settle) + " (0..2)");
+    if (settle != TRG_FIELD_SETTLE_NONE && (n_targets == 0 || !targets))
+      return e->fail(TRG_ERR_INVALID_ARG, "cost field: settle mode " + std::to_string(settle) + " needs targets");
+    const FieldRequest rq{m, source_ids, source_xy, cost, hops, parent, targets, n_targets, cost_at, hops_at,
+                          sources_out, reached_out, resolve_only, budget, settle, bound_out};
+    return field_solve(e, rq, out);
+  });
 }
 
 TrgStatus trg_engine_field_reached(TrgEngine *e, int32_t field, int32_t *node_ids, float *cost, int32_t *hops,
                                    int32_t cap, int32_t *n_out, TrgFieldInfo *info) {
-  REQUIRE_DEVICE(e);
-  TrgFieldInfo local{};
-  if (!info) info = &local;
-  *info = TrgFieldInfo{};
-  info->source = -1;
-  try {
-    return field_reached(e, field, node_ids, cost, hops, cap, n_out, info);
-  } catch (const std::bad_alloc &) {
-    return e->fail(TRG_ERR_CAPACITY, "cost field reached: out of host memory");
-  } catch (const std::exception &x) {
-    return e->fail(TRG_ERR_DEVICE, std::string("cost field reached: ") + x.what());
-  } catch (...) {
-    return e->fail(TRG_ERR_DEVICE, "cost field reached: unknown exception");
-  }
+  return field_entry(e, info, "cost field reached", [&](TrgFieldInfo *out) {
+    return field_reached(e, field, node_ids, cost, hops, cap, n_out, out);
+  });
 }
 
 TrgStatus trg_engine_field_routes(TrgEngine *e, int32_t n_routes, const int32_t *route_field,
                                   const int32_t *route_target, int32_t *offsets, int32_t *node_ids, float *xyz,
                                   int32_t cap, TrgRouteInfo *infos, TrgFieldInfo *info) {
-  REQUIRE_DEVICE(e);
-  TrgFieldInfo local{};
-  if (!info) info = &local;
-  *info = TrgFieldInfo{};
-  info->source = -1;
-  const RouteRequest rq{n_routes, route_field, route_target, offsets, node_ids, xyz, cap, infos};
-  try {
-    return field_routes(e, rq, info);
-  } catch (const std::bad_alloc &) {
-    return e->fail(TRG_ERR_CAPACITY, "cost field routes: out of host memory");
-  } catch (const std::exception &x) {
-    return e->fail(TRG_ERR_DEVICE, std::string("cost field routes: ") + x.what());
-  } catch (...) {
-    return e->fail(TRG_ERR_DEVICE, "cost field routes: unknown exception");
-  }
+  return field_entry(e, info, "cost field routes", [&](TrgFieldInfo *out) {
+    const RouteRequest rq{n_routes, route_field, route_target, offsets, node_ids, xyz, cap, infos};
+    return field_routes(e, rq, out);
+  });
 }
 
 }  // extern "C"

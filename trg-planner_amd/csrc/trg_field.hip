@@ -590,6 +590,23 @@ int field_blocks(long long items, int per_block) {
   return (int)std::max(1ll, std::min<long long>(b, MAX_BLOCKS));
 }
 
+// one round's launches; the settle step only under bounds with a settle mode
+template <bool BOUNDED>
+void field_round(const FieldDev &F, int round, const FieldSettle *settle, hipStream_t s) {
+  const int par = round & 1;
+  const dim3 relax_grid(field_blocks((long long)F.N * GROUP, THREADS));
+  if (F.m == 1)
+    hipLaunchKernelGGL((k_field_relax<false, BOUNDED>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+  else
+    hipLaunchKernelGGL((k_field_relax<true, BOUNDED>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+  hipLaunchKernelGGL(k_field_far_min<BOUNDED>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
+  if (BOUNDED && settle->mode != FIELD_SETTLE_NONE)
+    hipLaunchKernelGGL(k_field_settle, dim3(F.m), dim3(THREADS), 0, s, F, par, settle->targets, settle->n_t,
+                       settle->mode);
+  hipLaunchKernelGGL(k_field_far_split<BOUNDED>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
+  hipLaunchKernelGGL(k_field_round_end<BOUNDED>, dim3(1), dim3(64), 0, s, F, par);
+}
+
 }  // namespace
 
 void launch_field_edge_cost(const int *col, const float *w, const float *dist, const int *state, int V, int E,
@@ -604,34 +621,15 @@ void launch_field_init(const FieldDev &F, const FieldSources &sources, float del
   hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, sources, delta);
 }
 
-void launch_field_round(const FieldDev &F, int round, hipStream_t s) {
-  const int par = round & 1;
-  const dim3 relax_grid(field_blocks((long long)F.N * GROUP, THREADS));
-  if (F.m == 1)
-    hipLaunchKernelGGL((k_field_relax<false, false>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+void launch_field_round(const FieldDev &F, int round, hipStream_t s, const FieldSettle *under_bounds) {
+  if (under_bounds)
+    field_round<true>(F, round, under_bounds, s);
   else
-    hipLaunchKernelGGL((k_field_relax<true, false>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
-  hipLaunchKernelGGL(k_field_far_min<false>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
-  hipLaunchKernelGGL(k_field_far_split<false>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
-  hipLaunchKernelGGL(k_field_round_end<false>, dim3(1), dim3(64), 0, s, F, par);
+    field_round<false>(F, round, nullptr, s);
 }
 
 void launch_field_bounds(const FieldDev &F, const FieldBounds &budgets, hipStream_t s) {
   hipLaunchKernelGGL(k_field_bounds, dim3(1), dim3(FIELD_MAX_SOURCES), 0, s, F, budgets);
-}
-
-void launch_field_round_bounded(const FieldDev &F, int round, const int *targets, int n_t, int mode, hipStream_t s) {
-  const int par = round & 1;
-  const dim3 relax_grid(field_blocks((long long)F.N * GROUP, THREADS));
-  if (F.m == 1)
-    hipLaunchKernelGGL((k_field_relax<false, true>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
-  else
-    hipLaunchKernelGGL((k_field_relax<true, true>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
-  hipLaunchKernelGGL(k_field_far_min<true>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
-  if (mode != FIELD_SETTLE_NONE)
-    hipLaunchKernelGGL(k_field_settle, dim3(F.m), dim3(THREADS), 0, s, F, par, targets, n_t, mode);
-  hipLaunchKernelGGL(k_field_far_split<true>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
-  hipLaunchKernelGGL(k_field_round_end<true>, dim3(1), dim3(64), 0, s, F, par);
 }
 
 void launch_field_trim(const FieldDev &F, hipStream_t s) {

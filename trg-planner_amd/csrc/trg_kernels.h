@@ -444,19 +444,23 @@ void launch_field_edge_cost(const int *col, const float *w, const float *dist, c
                             float safety_factor, float *ec, FieldEdgeStats *st, hipStream_t s);
 // field k starts at node sources.id[k], k < F.m (duplicates give identical fields)
 void launch_field_init(const FieldDev &F, const FieldSources &sources, float delta, hipStream_t s);
-// one relaxation round (round >= 0, consecutive from 0): relax the near queue, and when that pushed
-// nothing near in ANY field, open the next bucket from the least live far cost over all fields; every
-// launch reads its sizes from F.ctrl
-void launch_field_round(const FieldDev &F, int round, hipStream_t s);
-// Bounded solves, pass 1 (pass 2 runs the plain rounds: a removed key's tight word matches no extension).
-// F.ctrl->bound[k] = budgets.bits[k], before the first round
-void launch_field_bounds(const FieldDev &F, const FieldBounds &budgets, hipStream_t s);
-// launch_field_round under the bounds: an item above its field's bound is not expanded, an extension above it
-// neither written nor pushed, a far-pile entry above it not live.  With mode ANY / ALL and n_t targets (device
-// ids), a round that opens a bucket or converges lowers the bound of every field whose targets are settled --
+// the settle step of a bounded round: n_t target nodes (device ids) and the mode, FIELD_SETTLE_*
+struct FieldSettle {
+  const int *targets;
+  int n_t;
+  int mode;
+};
+// One relaxation round (round >= 0, consecutive from 0): relax the near queue, and when that pushed nothing near
+// in ANY field, open the next bucket from the least live far cost over all fields; every launch reads its sizes
+// from F.ctrl.  under_bounds == nullptr: a round that knows nothing of bounds (every pass 2 is such: a removed
+// key's tight word matches no extension).  Else pass 1 of a bounded solve: an item above its field's bound is not
+// expanded, an extension above it neither written nor pushed, a far-pile entry above it not live; and with mode
+// ANY / ALL, a round that opens a bucket or converges lowers the bound of every field whose targets are settled --
 // some (ANY) or all (ALL) of them have a key below the least live far cost -- to the least (greatest) of those
 // costs.
-void launch_field_round_bounded(const FieldDev &F, int round, const int *targets, int n_t, int mode, hipStream_t s);
+void launch_field_round(const FieldDev &F, int round, hipStream_t s, const FieldSettle *under_bounds = nullptr);
+// F.ctrl->bound[k] = budgets.bits[k], before the first round of a bounded solve
+void launch_field_bounds(const FieldDev &F, const FieldBounds &budgets, hipStream_t s);
 // after the last round of pass 1: keys above their field's bound become FIELD_KEY_NONE
 void launch_field_trim(const FieldDev &F, hipStream_t s);
 // The nodes of one field of a finished solve that have a key, in ascending id: ids / cost / hops (any may be

@@ -467,16 +467,19 @@ class Engine:
             return self.cheapest_frontiers(np.ascontiguousarray(source_xy, dtype=np.float32).reshape(1, 2),
                                            early_exit=True)[0]
         cost, hops, parent, info = self.cost_field(source_xy=source_xy)
+        frontier = self._frontier_ids()
+        pick = choose_frontier(frontier, cost[frontier], hops[frontier])
+        if pick is None:
+            return None
+        return pick[0], float(cost[pick[0]]), self.field_path(parent, pick[0], int(info.source))
+
+    def _frontier_ids(self):
+        """The ids of the global graph's Frontier nodes, ascending (none for an empty graph)."""
         v = TrgCsrView()
         self._chk(self.L.trg_engine_export_csr(self.h, KIND_GLOBAL, C.byref(v)))
         if v.num_nodes == 0:
-            return None
-        state = np.ctypeslib.as_array(v.node_state, shape=(v.num_nodes,))
-        ids = np.flatnonzero((state == 1) & np.isfinite(cost) & (hops >= 0))
-        if ids.size == 0:
-            return None
-        best = int(ids[np.lexsort((ids, hops[ids], cost[ids]))[0]])
-        return best, float(cost[best]), self.field_path(parent, best, int(info.source))
+            return np.empty(0, np.int32)
+        return np.flatnonzero(np.ctypeslib.as_array(v.node_state, shape=(v.num_nodes,)) == 1).astype(np.int32)
 
     def cost_fields(self, sources_xy=None, source_ids=None, targets=None, full=True, budget=None, settle=None):
         """m cost fields in one solve on the GPU (trg_engine_cost_field_batch; each field as cost_field's).
@@ -514,26 +517,23 @@ class Engine:
         out["sources"] = np.full(m, -1, np.int32)
         out["reached"] = np.zeros(m, np.int32)
         info = TrgFieldInfo()
-        if budget is None and settle is None:
-            self._chk(self.L.trg_engine_cost_field_batch(
-                self.h, m, None if ids is None else _i(ids), None if xy is None else _f(xy),
-                _f(out["cost"]) if full else None, _i(out["hops"]) if full else None,
-                _i(out["parent"]) if full else None, None if tg is None else _i(tg), nt,
-                None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
-                _i(out["sources"]), _i(out["reached"]), C.byref(info)))
-            out["info"] = info
-            return out
+        bounded = budget is not None or settle is not None
         bud = None
         if budget is not None:
             bud = np.ascontiguousarray(np.broadcast_to(np.asarray(budget, dtype=np.float32).reshape(-1), (m,)))
-        out["bound"] = np.empty(m, np.float32)
-        self._chk(self.L.trg_engine_cost_field_bounded(
-            self.h, m, None if ids is None else _i(ids), None if xy is None else _f(xy),
-            None if bud is None else _f(bud), _SETTLE[settle],
-            _f(out["cost"]) if full else None, _i(out["hops"]) if full else None,
-            _i(out["parent"]) if full else None, None if tg is None else _i(tg), nt,
-            None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
-            _i(out["sources"]), _i(out["reached"]), _f(out["bound"]), C.byref(info)))
+        if bounded:
+            out["bound"] = np.empty(m, np.float32)
+        # the bounded entry's arguments; the batch entry's are these without budget, settle and bound_out
+        sources = [self.h, m, None if ids is None else _i(ids), None if xy is None else _f(xy)]
+        bounds = [None if bud is None else _f(bud), _SETTLE[settle]]
+        outputs = [_f(out["cost"]) if full else None, _i(out["hops"]) if full else None,
+                   _i(out["parent"]) if full else None, None if tg is None else _i(tg), nt,
+                   None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
+                   _i(out["sources"]), _i(out["reached"])]
+        if bounded:
+            self._chk(self.L.trg_engine_cost_field_bounded(*sources, *bounds, *outputs, _f(out["bound"]), C.byref(info)))
+        else:
+            self._chk(self.L.trg_engine_cost_field_batch(*sources, *outputs, C.byref(info)))
         out["info"] = info
         return out
 
@@ -567,6 +567,19 @@ class Engine:
                              source_ids=None if source_id == -1 else [int(source_id)], full=False, budget=budget)
         return self.field_reached(0, cap=max(int(r["reached"][0]), 1))
 
+    def _resolve_nodes(self, xy):
+        """The node of every position of `xy` (n, 2), each resolved as cost_field resolves a source: the batch entry's
+        resolve-only call (no solve, see the header), in chunks of TRG_FIELD_BATCH_MAX."""
+        xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+        nodes = np.empty(xy.shape[0], np.int32)
+        for k0 in range(0, xy.shape[0], TRG_FIELD_BATCH_MAX):
+            part = np.ascontiguousarray(xy[k0:k0 + TRG_FIELD_BATCH_MAX])
+            got = np.empty(part.shape[0], np.int32)
+            self._chk(self.L.trg_engine_cost_field_batch(self.h, part.shape[0], None, _f(part), None, None, None,
+                                                         None, 0, None, None, _i(got), None, None))
+            nodes[k0:k0 + TRG_FIELD_BATCH_MAX] = got
+        return nodes
+
     def cost_matrix(self, nodes_or_xy, early_exit=False):
         """Least costs between m waypoints -> (cost (m, m) float32, hops (m, m) int32, node ids (m,)): entry
         [a, b] is from waypoint a to waypoint b.  `nodes_or_xy` is a list of node ids or an (m, 2) array of
@@ -578,14 +591,7 @@ class Engine:
             nodes = np.ascontiguousarray(a, dtype=np.int32)
         else:
             # every chunk's targets are ALL waypoints: resolve the positions first (no solve, see the header)
-            xy = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 2)
-            nodes = np.empty(xy.shape[0], np.int32)
-            for k0 in range(0, xy.shape[0], TRG_FIELD_BATCH_MAX):
-                part = np.ascontiguousarray(xy[k0:k0 + TRG_FIELD_BATCH_MAX])
-                got = np.empty(part.shape[0], np.int32)
-                self._chk(self.L.trg_engine_cost_field_batch(self.h, part.shape[0], None, _f(part), None, None, None,
-                                                             None, 0, None, None, _i(got), None, None))
-                nodes[k0:k0 + TRG_FIELD_BATCH_MAX] = got
+            nodes = self._resolve_nodes(a)
         m = nodes.shape[0]
         cost = np.empty((m, m), np.float32)
         hops = np.empty((m, m), np.int32)
@@ -603,12 +609,7 @@ class Engine:
         settled (settle "any": the Frontier nodes of that cost keep their keys, every dearer one reads as
         unreached, and choose_frontier picks among the same least ones); the result is the same."""
         xy = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 2)
-        v = TrgCsrView()
-        self._chk(self.L.trg_engine_export_csr(self.h, KIND_GLOBAL, C.byref(v)))
-        frontier = np.empty(0, np.int32)  # (an empty graph: the batch call says so, as cheapest_frontier's does)
-        if v.num_nodes:
-            state = np.ctypeslib.as_array(v.node_state, shape=(v.num_nodes,))
-            frontier = np.flatnonzero(state == 1).astype(np.int32)
+        frontier = self._frontier_ids()  # (an empty graph: the batch call says so, as cheapest_frontier's does)
         out = []
         for k0 in range(0, xy.shape[0], TRG_FIELD_BATCH_MAX):
             r = self.cost_fields(sources_xy=xy[k0:k0 + TRG_FIELD_BATCH_MAX], targets=frontier, full=False,
@@ -667,13 +668,7 @@ class Engine:
         start = np.ascontiguousarray(start_xy, dtype=np.float32).reshape(1, 2)
         if not (early_exit and goals.shape[0]):
             self.cost_fields(sources_xy=start, full=False)
-        nodes = np.empty(goals.shape[0], np.int32)
-        for k0 in range(0, goals.shape[0], TRG_FIELD_BATCH_MAX):
-            part = np.ascontiguousarray(goals[k0:k0 + TRG_FIELD_BATCH_MAX])
-            got = np.empty(part.shape[0], np.int32)
-            self._chk(self.L.trg_engine_cost_field_batch(self.h, part.shape[0], None, _f(part), None, None, None,
-                                                         None, 0, None, None, _i(got), None, None))
-            nodes[k0:k0 + TRG_FIELD_BATCH_MAX] = got
+        nodes = self._resolve_nodes(goals)
         if early_exit and goals.shape[0]:  # (the goals are the settle targets: resolved first)
             self.cost_fields(sources_xy=start, targets=nodes, full=False, settle="all")
         return [(pts, one) for _, pts, one in self.routes(np.zeros(nodes.shape[0], np.int32), nodes)]
