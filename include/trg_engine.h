@@ -402,6 +402,41 @@ TrgStatus trg_engine_cost_field_bounded(
     int32_t *sources_out, int32_t *reached_out,
     float *bound_out,            /* m: the bound each field ended with, may be NULL */
     TrgFieldInfo *info);
+/* Source sets ("Source sets"): field k starts from EVERY member of a set of nodes,
+ * set k = set_ids[set_ptr[k] .. set_ptr[k+1]), each member at cost +0 and hops 0 -- for every node, the nearest member
+ * by risk cost, that cost, and through trg_engine_field_routes the route from it.  A set is non-empty and may hold
+ * any number of ids, duplicates and Invalid nodes (a source like any other) among them.  One field of num_nodes
+ * items per set, whatever its size: a set field costs about what a field from one source costs.
+ *   cost[v]    the least fp32 left fold over all walks from any member to v: bit for bit the minimum over the
+ *              members' single fields
+ *   hops[v]    BFS depth of v in the tight subgraph from all members at depth 0 (NOT in general the minimum of the
+ *              members' hops); -1 when unreachable
+ *   parent[v]  as trg_engine_cost_field's; -1 for every member and every unreachable node
+ *   owner[v]   an entry of set k, counted from set_ptr[k]: for a member the least entry that names it, for any
+ *              other reached node owner[parent[v]] -- where v's route starts; -1 when unreachable
+ *   owned      set_ptr[m] counts: owned[set_ptr[k] + j] = nodes of field k whose owner is j (0 for an entry that a
+ *              smaller entry of the same node shadows); their sum over a set is that field's reached count
+ *   cost_at, hops_at, owner_at   m x n_targets, the fields read at `targets` on the device
+ * budget, settle, bound_out, reached_out, info and the truncation are trg_engine_cost_field_bounded's (a truncated
+ * node has owner -1); info->source is set 0's first id.  The owners cost one more pass (pointer jumping over the
+ * parents, sweeps logarithmic in the greatest hop count) that runs only when owner, owner_at or owned is asked for.
+ * The solve is retained like any other: trg_engine_field_reached works on it unchanged, and a route of
+ * trg_engine_field_routes runs from the member that owns its target (ids[0] == set_ids[set_ptr[k] + owner]); the
+ * first routes call after a solve without owners runs the owner pass (its sweeps come back in info->rounds).
+ * trg_engine_cost_field_batch and _bounded are untouched by this call and keep their limit of one source per field.
+ * TRG_ERR_INVALID_ARG (the message names the set, and the entry where there is one) for m < 1 or
+ * m > TRG_FIELD_BATCH_MAX, set_ptr[0] != 0, an empty set or a descending set_ptr, an id out of range, and the
+ * target, budget and settle errors of the bounded call; the other codes as there. */
+TrgStatus trg_engine_cost_field_sets(
+    TrgEngine *e, int32_t m,
+    const int32_t *set_ptr,      /* m + 1, set_ptr[0] == 0, strictly ascending */
+    const int32_t *set_ids,      /* set_ptr[m] node ids */
+    const float *budget, int32_t settle,                           /* as trg_engine_cost_field_bounded */
+    float *cost, int32_t *hops, int32_t *parent, int32_t *owner,   /* m x num_nodes each, any may be NULL */
+    const int32_t *targets, int32_t n_targets,
+    float *cost_at, int32_t *hops_at, int32_t *owner_at,           /* m x n_targets, any may be NULL */
+    int32_t *owned,              /* set_ptr[m], may be NULL */
+    int32_t *reached_out, float *bound_out, TrgFieldInfo *info);
 /* The nodes of field `field` (0 .. m-1) of the retained solve that have a key, compacted on the device: their
  * ids in ascending order with cost and hops, so that a bounded field that reaches few nodes is read without
  * copying anything of num_nodes entries.  *n_out is always the full count; node_ids, cost and hops (room for cap

@@ -42,7 +42,12 @@ struct FieldBufs {
     FieldSources sources{};  // a walk must end at its field's
     bool parents = false;    // the parent sweep ran
     bool dev_csr = false;    // F's CSR is the device build's (gone stale when an update_graph begins)
+    bool sets = false;       // a set solve ("Source sets"): S is its sets, on the device
+    FieldSets S{};
+    bool owners = false;     // ... and the owner pass ran: S.owner is filled
   } last;
+  DevArr set_ptr, set_ids, owner, owner_at, owned, own_changed;  // set solves; owner: m x V, only when asked for
+  Pinned<int> h_changed;     // the owner pass's "a sweep moved something" word
   DevArr route_field, route_target, route_len, route_off, route_ids, route_info;
   DevArr list_counts, list_off, list_tmp, list_ids, list_cost, list_hops;  // trg_engine_field_reached
   Pinned<unsigned> h_bound;  // per field, as cost bits (bounded solves)
@@ -78,6 +83,11 @@ struct FieldRequest {
   const float *budget;        // m, or nullptr: +inf each
   int32_t settle;             // TRG_FIELD_SETTLE_*, over `targets`
   float *bound_out;           // m, may be nullptr
+  // a set solve (trg_engine_cost_field_sets): field k starts from set_ids[set_ptr[k] .. set_ptr[k + 1])
+  const int32_t *set_ptr = nullptr, *set_ids = nullptr;
+  int32_t *owner = nullptr;     // m x V
+  int32_t *owner_at = nullptr;  // m x n_targets
+  int32_t *owned = nullptr;     // set_ptr[m]
 };
 
 // an allocation that fails is a matter of capacity
@@ -97,7 +107,9 @@ struct FieldRun {
   FieldSources sources{};
   FieldBounds budgets{};
   bool bounded = false;     // some budget below +inf, or a settle mode ("Bounded fields")
-  bool gather = false;      // cost_at / hops_at are wanted
+  bool gather = false;      // cost_at / hops_at (/ owner_at) are wanted
+  FieldSets sets{};         // a set solve: n from the checks on, the device arrays from the passes on
+  bool owners = false;      // owner, owner_at or owned is wanted: the owner pass runs
   // the CSR the solve runs on: the device build's in place, or the engine's upload of csr_global
   struct Graph {
     const int *rowptr, *col, *state;
@@ -110,13 +122,39 @@ struct FieldRun {
 
 constexpr uint32_t FIELD_INF_BITS = 0x7f800000u;
 
+// The sets of a set solve (trg_engine_cost_field_sets): set_ptr from 0 and strictly ascending, every id a node.
+// Field k's source, for `info` and the reached list, is its set's first id.
+TrgStatus field_check_sets(TrgEngine *e, FieldRun &run) {
+  const FieldRequest &rq = run.rq;
+  const int V = run.F.V, m = run.F.m;
+  if (rq.set_ptr[0] != 0)
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field sets: set_ptr[0] is " + std::to_string(rq.set_ptr[0]) + ", not 0");
+  for (int k = 0; k < m; ++k) {
+    if (rq.set_ptr[k + 1] <= rq.set_ptr[k])
+      return e->fail(TRG_ERR_INVALID_ARG, "cost field sets: set " + std::to_string(k) + " is empty or set_ptr descends (" +
+                                              std::to_string(rq.set_ptr[k]) + ", then " +
+                                              std::to_string(rq.set_ptr[k + 1]) + ")");
+    for (int j = rq.set_ptr[k]; j < rq.set_ptr[k + 1]; ++j)
+      if (rq.set_ids[j] < 0 || rq.set_ids[j] >= V)
+        return e->fail(TRG_ERR_INVALID_ARG, "cost field sets: entry " + std::to_string(j - rq.set_ptr[k]) + " of set " +
+                                                std::to_string(k) + " (node " + std::to_string(rq.set_ids[j]) +
+                                                ") out of range");
+    run.sources.id[k] = rq.set_ids[rq.set_ptr[k]];
+  }
+  run.sets.n = rq.set_ptr[m];
+  run.owners = rq.owner || rq.owned || (rq.owner_at && rq.n_targets > 0);
+  return TRG_OK;
+}
+
 // Request checks, in the order a caller sees them: the sources (a resolve-only call ends after them), the targets,
 // the 32-bit item index, and the budgets as cost bits.
 TrgStatus field_check_request(TrgEngine *e, FieldRun &run) {
   const FieldRequest &rq = run.rq;
   const int V = run.F.V = (int)e->nx.size();
   const int m = run.F.m = rq.m;
-  for (int k = 0; k < m; ++k) {
+  if (rq.set_ptr)
+    if (const TrgStatus st = field_check_sets(e, run); st != TRG_OK) return st;
+  for (int k = 0; !rq.set_ptr && k < m; ++k) {  // (a set solve has its sources)
     int src = rq.source_ids ? rq.source_ids[k] : -1;
     if (src == -1) {
       if (!rq.source_xy)
@@ -136,7 +174,7 @@ TrgStatus field_check_request(TrgEngine *e, FieldRun &run) {
     run.info->ms_total = ms_since(run.t_total);
     return TRG_OK;
   }
-  run.gather = rq.n_targets > 0 && (rq.cost_at || rq.hops_at);
+  run.gather = rq.n_targets > 0 && (rq.cost_at || rq.hops_at || rq.owner_at);
   if (rq.n_targets > 0 && !rq.targets) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no targets");
   for (int j = 0; j < rq.n_targets; ++j)
     if (rq.targets[j] < 0 || rq.targets[j] >= V)
@@ -272,6 +310,16 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
     if (st != TRG_OK) return st;
     HIPCHK(e, hipMemcpyAsync(fb.targets.p, rq.targets, (size_t)rq.n_targets * sizeof(int), hipMemcpyHostToDevice, s));
   }
+  if (rq.set_ptr) {  // the sets, uploaded once per solve
+    FieldSets &S = run.sets;
+    TrgStatus st;
+    if ((st = field_grow(e, fb.set_ptr, ((size_t)F.m + 1) * sizeof(int))) != TRG_OK) return st;
+    if ((st = field_grow(e, fb.set_ids, (size_t)S.n * sizeof(int))) != TRG_OK) return st;
+    HIPCHK(e, hipMemcpyAsync(fb.set_ptr.p, rq.set_ptr, ((size_t)F.m + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(fb.set_ids.p, rq.set_ids, (size_t)S.n * sizeof(int), hipMemcpyHostToDevice, s));
+    S.ptr = (const int *)fb.set_ptr.p;
+    S.ids = (const int *)fb.set_ids.p;
+  }
   const FieldSettle under{(const int *)fb.targets.p, rq.n_targets, rq.settle};
   if (run.bounded) launch_field_bounds(F, run.budgets, s);
   for (int pass = 0; pass < 2; ++pass) {
@@ -279,7 +327,10 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
     // the tight word of a node without a key
     const bool under_bounds = run.bounded && pass == 0;
     F.tight = pass ? (const unsigned *)fb.cost.p : nullptr;
-    launch_field_init(F, run.sources, delta, s);
+    if (rq.set_ptr)
+      launch_field_init_sets(F, run.sets, delta, s);
+    else
+      launch_field_init(F, run.sources, delta, s);
     for (int round = 0;;) {
       for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s, under_bounds ? &under : nullptr);
       HIPCHK(e, hipGetLastError());
@@ -300,6 +351,37 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
   return TRG_OK;
 }
 
+// sweeps enqueued between two looks at the owner pass's pinned "moved" word
+constexpr int FIELD_OWNER_BATCH = 8;
+static_assert(FIELD_OWNER_SWEEPS_MAX % FIELD_OWNER_BATCH == 0, "the owner pass looks after whole batches");
+
+// The owner pass of a set solve whose parent sweep ran (trg_field.hip; DESIGN.md section 2, "Source sets"): pointer
+// jumping in the idle near queues until a sweep moves nothing -- about log2 of the greatest hop count of them --
+// then S.owner, whose m x V words are allocated here.  One host wait per FIELD_OWNER_BATCH sweeps.
+TrgStatus field_owner_pass(TrgEngine *e, const FieldDev &F, FieldSets &S, int &syncs, int &sweeps) {
+  FieldBufs &fb = *e->field;
+  hipStream_t s = e->s_main;
+  TrgStatus st;
+  if ((st = field_grow(e, fb.owner, ((size_t)F.N + 4) * sizeof(int))) != TRG_OK) return st;
+  if ((st = field_grow(e, fb.own_changed, FIELD_OWNER_SWEEPS_MAX * sizeof(int))) != TRG_OK) return st;
+  HIPCHK(e, fb.h_changed.ensure(1));
+  S.owner = (int *)fb.owner.p;
+  int *changed = (int *)fb.own_changed.p;
+  launch_field_owner_begin(F, changed, s);
+  for (sweeps = 0;;) {
+    for (int i = 0; i < FIELD_OWNER_BATCH; ++i, ++sweeps) launch_field_owner_sweep(F, sweeps, changed, s);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(fb.h_changed, changed + sweeps - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    syncs++;
+    if (fb.h_changed[0] == 0) break;
+    if (sweeps >= FIELD_OWNER_SWEEPS_MAX) return e->fail(TRG_ERR_DEVICE, "cost field sets: the owner pass did not end");
+  }
+  launch_field_owner_end(F, S, sweeps, s);
+  HIPCHK(e, hipGetLastError());
+  return TRG_OK;
+}
+
 // finish, gather, the copies of only what was asked for, `info`, and the retained-solve record
 TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   FieldBufs &fb = *e->field;
@@ -308,13 +390,26 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   hipStream_t s = e->s_main;
   const int m = F.m;
   const size_t nN = (size_t)F.N, nat = (size_t)m * rq.n_targets;
-  launch_field_finish(F, (float *)fb.cost.p, (int *)fb.hops.p, rq.parent != nullptr, s);
+  const bool parents = rq.parent != nullptr || run.owners;  // (owners follow parents)
+  launch_field_finish(F, (float *)fb.cost.p, (int *)fb.hops.p, parents, s);
+  TrgStatus st;
+  int sweeps = 0;
+  if (run.owners && (st = field_owner_pass(e, F, run.sets, run.syncs, sweeps)) != TRG_OK) return st;
   if (run.gather) {
-    TrgStatus st;
     if ((st = field_grow(e, fb.cost_at, nat * sizeof(float))) != TRG_OK) return st;
     if ((st = field_grow(e, fb.hops_at, nat * sizeof(int))) != TRG_OK) return st;
-    launch_field_gather(F, (const int *)fb.targets.p, rq.n_targets, rq.cost_at ? (float *)fb.cost_at.p : nullptr,
-                        rq.hops_at ? (int *)fb.hops_at.p : nullptr, s);
+    if (rq.owner_at && (st = field_grow(e, fb.owner_at, nat * sizeof(int))) != TRG_OK) return st;
+    float *d_cost_at = rq.cost_at ? (float *)fb.cost_at.p : nullptr;
+    int *d_hops_at = rq.hops_at ? (int *)fb.hops_at.p : nullptr;
+    if (rq.set_ptr)
+      launch_field_gather_sets(F, run.sets, (const int *)fb.targets.p, rq.n_targets, d_cost_at, d_hops_at,
+                               rq.owner_at ? (int *)fb.owner_at.p : nullptr, s);
+    else
+      launch_field_gather(F, (const int *)fb.targets.p, rq.n_targets, d_cost_at, d_hops_at, s);
+  }
+  if (rq.owned) {
+    if ((st = field_grow(e, fb.owned, (size_t)run.sets.n * sizeof(int))) != TRG_OK) return st;
+    launch_field_owned(F, run.sets, (int *)fb.owned.p, s);
   }
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
@@ -326,6 +421,11 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
     HIPCHK(e, hipMemcpyAsync(rq.cost_at, fb.cost_at.p, nat * sizeof(float), hipMemcpyDeviceToHost, s));
   if (run.gather && rq.hops_at)
     HIPCHK(e, hipMemcpyAsync(rq.hops_at, fb.hops_at.p, nat * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (rq.owner) HIPCHK(e, hipMemcpyAsync(rq.owner, fb.owner.p, nN * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (run.gather && rq.owner_at)
+    HIPCHK(e, hipMemcpyAsync(rq.owner_at, fb.owner_at.p, nat * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (rq.owned)
+    HIPCHK(e, hipMemcpyAsync(rq.owned, fb.owned.p, (size_t)run.sets.n * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   run.syncs++;
   float ms_dev = 0.0f;
@@ -343,7 +443,8 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   run.info->host_syncs = run.syncs;
   run.info->ms_device = ms_dev;
   run.info->ms_total = ms_since(run.t_total);
-  fb.last = FieldBufs::Last{e->graph_version, F, run.G.w, run.G.dist, run.sources, rq.parent != nullptr, run.G.dev_csr};
+  fb.last = FieldBufs::Last{e->graph_version, F, run.G.w, run.G.dist, run.sources, parents, run.G.dev_csr,
+                            rq.set_ptr != nullptr, run.sets, run.owners};
   fb.last.F.tight = nullptr;  // (its array holds the cost output now)
   return TRG_OK;
 }
@@ -449,6 +550,12 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
     HIPCHK(e, hipGetLastError());
     last->parents = true;
   }
+  if (last->sets && !last->owners) {  // a walk of a set solve ends at its target's owner
+    int sweeps = 0;
+    if ((st = field_owner_pass(e, F, last->S, syncs, sweeps)) != TRG_OK) return st;
+    last->owners = true;
+    info->rounds = sweeps;
+  }
   const int *d_field = (const int *)fb.route_field.p, *d_target = (const int *)fb.route_target.p;
   std::vector<int32_t> ids;
   int total = 0;
@@ -470,9 +577,14 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
     HIPCHK(e, hipMemcpyAsync(fb.route_off.p, rq.offsets, (n + 1) * sizeof(int), hipMemcpyHostToDevice, s));
   }
   std::vector<FieldRouteInfo> infos(n);
-  launch_field_route_walk(F, last->w, last->dist, d_field, d_target, rq.n,
-                          want_ids ? (const int *)fb.route_off.p : nullptr, want_ids ? (int *)fb.route_ids.p : nullptr,
-                          (FieldRouteInfo *)fb.route_info.p, last->sources, s);
+  const int *d_off = want_ids ? (const int *)fb.route_off.p : nullptr;
+  int *d_ids = want_ids ? (int *)fb.route_ids.p : nullptr;
+  if (last->sets)
+    launch_field_route_walk_sets(F, last->S, last->w, last->dist, d_field, d_target, rq.n, d_off, d_ids,
+                                 (FieldRouteInfo *)fb.route_info.p, s);
+  else
+    launch_field_route_walk(F, last->w, last->dist, d_field, d_target, rq.n, d_off, d_ids,
+                            (FieldRouteInfo *)fb.route_info.p, last->sources, s);
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
   int32_t *ids_out = rq.node_ids;
@@ -565,6 +677,21 @@ TrgStatus field_reached(TrgEngine *e, int32_t field, int32_t *node_ids, float *c
   return TRG_OK;
 }
 
+// the budget and settle checks that the bounded and the set entry share
+TrgStatus field_check_bounds(TrgEngine *e, int32_t m, const float *budget, int32_t settle, const int32_t *targets,
+                             int32_t n_targets) {
+  if (budget)
+    for (int k = 0; k < m; ++k)
+      if (!(budget[k] >= 0.0f))
+        return e->fail(TRG_ERR_INVALID_ARG, "cost field: the budget of field " + std::to_string(k) +
+                                                " is negative or not a number");
+  if (settle != TRG_FIELD_SETTLE_NONE && settle != TRG_FIELD_SETTLE_ANY && settle != TRG_FIELD_SETTLE_ALL)
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field: settle mode " + std::to_string(settle) + " (0..2)");
+  if (settle != TRG_FIELD_SETTLE_NONE && (n_targets == 0 || !targets))
+    return e->fail(TRG_ERR_INVALID_ARG, "cost field: settle mode " + std::to_string(settle) + " needs targets");
+  return TRG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -604,17 +731,32 @@ TrgStatus trg_engine_cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *
       for (int k = 0; k < m; ++k)
         if (source_ids[k] < -1)
           return e->fail(TRG_ERR_INVALID_ARG, "cost field: source " + std::to_string(k) + " out of range");
-    if (budget)
-      for (int k = 0; k < m; ++k)
-        if (!(budget[k] >= 0.0f))
-          return e->fail(TRG_ERR_INVALID_ARG, "cost field: the budget of field " + std::to_string(k) +
-                                                  " is negative or not a number");
-    if (settle != TRG_FIELD_SETTLE_NONE && settle != TRG_FIELD_SETTLE_ANY && settle != TRG_FIELD_SETTLE_ALL)
-      return e->fail(TRG_ERR_INVALID_ARG, "cost field: settle mode " + std::to_string(settle) + " (0..2)");
-    if (settle != TRG_FIELD_SETTLE_NONE && (n_targets == 0 || !targets))
-      return e->fail(TRG_ERR_INVALID_ARG, "cost field: settle mode " + std::to_string(settle) + " needs targets");
+    if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
     const FieldRequest rq{m, source_ids, source_xy, cost, hops, parent, targets, n_targets, cost_at, hops_at,
                           sources_out, reached_out, resolve_only, budget, settle, bound_out};
+    return field_solve(e, rq, out);
+  });
+}
+
+TrgStatus trg_engine_cost_field_sets(TrgEngine *e, int32_t m, const int32_t *set_ptr, const int32_t *set_ids,
+                                     const float *budget, int32_t settle, float *cost, int32_t *hops, int32_t *parent,
+                                     int32_t *owner, const int32_t *targets, int32_t n_targets, float *cost_at,
+                                     int32_t *hops_at, int32_t *owner_at, int32_t *owned, int32_t *reached_out,
+                                     float *bound_out, TrgFieldInfo *info) {
+  return field_entry(e, info, "cost field sets", [&](TrgFieldInfo *out) {
+    if (m < 1 || m > TRG_FIELD_BATCH_MAX)
+      return e->fail(TRG_ERR_INVALID_ARG, "cost field sets: a batch of " + std::to_string(m) + " sets (1.." +
+                                              std::to_string(TRG_FIELD_BATCH_MAX) + ")");
+    if (!set_ptr || !set_ids) return e->fail(TRG_ERR_INVALID_ARG, "cost field sets: null set_ptr or set_ids");
+    if (n_targets < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field sets: n_targets < 0");
+    if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
+    FieldRequest rq{m, nullptr, nullptr, cost, hops, parent, targets, n_targets, cost_at, hops_at,
+                    nullptr, reached_out, false, budget, settle, bound_out};
+    rq.set_ptr = set_ptr;
+    rq.set_ids = set_ids;
+    rq.owner = owner;
+    rq.owner_at = owner_at;
+    rq.owned = owned;
     return field_solve(e, rq, out);
   });
 }

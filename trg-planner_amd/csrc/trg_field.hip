@@ -35,6 +35,12 @@
 // step between far min and far split, and ends with the keys above the bounds removed; pass 2 and everything after
 // it are the plain kernels.  A solve without bounds launches none of this.
 //
+// Source sets ("Source sets"): a field may start from a set of nodes, every member at key
+// (0, 0) -- the same least fixed point with more seeds, so the round kernels are the plain ones; only the seeding
+// differs.  After the parent sweep every reached node hangs on exactly one member through its parents; the owner
+// pass finds that member by pointer jumping, in sweeps logarithmic in the greatest hop count.  A solve from single
+// sources launches none of this.
+//
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"
 
@@ -585,6 +591,220 @@ __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const 
   }
 }
 
+// ---- source sets ("Source sets") ----------------------------------------------------------
+
+// grid.y = field: k_field_init without a source -- no item has a key, the near queue is empty
+__global__ __launch_bounds__(THREADS) void k_field_init_sets(FieldDev F, float delta) {
+  const int V = F.V;
+  const int fbase = blockIdx.y * V;
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
+    F.key[fbase + v] = FIELD_KEY_NONE;
+    F.parent[fbase + v] = INT_MAX;
+    F.stamp_near[fbase + v] = 0;
+    F.stamp_far[fbase + v] = 0u;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) F.ctrl->reached[blockIdx.y] = 0;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    FieldCounters &c = F.ctrl->c;
+    c.n[0] = c.n[1] = 0;
+    c.nfar[0] = c.nfar[1] = 0;
+    c.fmin = ~0u;
+    c.overflow = 0;
+    FieldState &s = F.ctrl->s;
+    s.work = 0;
+    s.rounds = 0;
+    s.overflow = 0;
+    s.thr = __float_as_uint(delta);
+    s.delta = delta;
+    s.phase = 1;
+    s.far_sel = 0;
+  }
+}
+
+// One thread per entry of all sets: its item gets key (0, 0) and the least entry that names it (atomicMin on the
+// member word, see FieldSets); the entry that finds the word unmarked pushes the item, so a duplicate is queued
+// once.  The queue size and `work` grow by one atomicAdd per wave each.
+__global__ __launch_bounds__(THREADS) void k_field_seed(FieldDev F, FieldSets S) {
+  const int n_iter = (S.n + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, e = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, e += gridDim.x * blockDim.x) {
+    bool first = false;
+    int item = 0;
+    if (e < S.n) {
+      int lo = 0, hi = F.m;  // the set of entry e: the last k with ptr[k] <= e
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (S.ptr[mid] <= e) lo = mid;
+        else hi = mid;
+      }
+      item = lo * F.V + S.ids[e];
+      F.key[item] = 0ull;
+      first = atomicMin(&F.stamp_near[item], FIELD_MEMBER | e) >= 0;
+    }
+    const unsigned long long mk = ballot(first);
+    const int slot = wave_reserve(first, &F.ctrl->c.n[0]);
+    if (mk && lane_id() == __ffsll(mk) - 1) atomicAdd(&F.ctrl->s.work, __popcll(mk));
+    if (first) {
+      if (slot < F.N) F.q[0][slot] = item;
+      else atomicOr(&F.ctrl->c.overflow, 1);
+    }
+  }
+}
+
+// grid.y = field: the first ancestor of every item -- itself for a member, its parent's item for another item with
+// a key, -1 without one
+__global__ __launch_bounds__(THREADS) void k_field_owner_begin(FieldDev F) {
+  const int fbase = blockIdx.y * F.V;
+  int *anc = F.q[0];
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < F.V; v += gridDim.x * blockDim.x) {
+    const int i = fbase + v;
+    int a = -1;
+    if (F.key[i] != FIELD_KEY_NONE) {
+      const int p = F.parent[i];
+      a = F.stamp_near[i] < 0 ? i : (p >= 0 && p < F.V ? fbase + p : -1);
+    }
+    anc[i] = a;
+  }
+}
+
+// One pointer-jumping sweep: out[i] = in[in[i]].  `in` is only read and `out` only written in this launch, so no
+// workgroup reads a word another one writes; *changed is set (to the one value anybody stores) when an entry moved.
+__global__ __launch_bounds__(THREADS) void k_field_owner_sweep(const int *__restrict__ in, int *__restrict__ out,
+                                                               int N, int *changed) {
+  bool moved = false;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
+    const int a = in[i];
+    int b = a;
+    if (a >= 0) {
+      b = in[a];
+      moved |= b != a;
+    }
+    out[i] = b;
+  }
+  if (moved) *changed = 1;
+}
+
+// grid.y = field: the owner of an item is the entry its last ancestor, a member, is marked with
+__global__ __launch_bounds__(THREADS) void k_field_owner_end(FieldDev F, FieldSets S, const int *__restrict__ anc) {
+  const int fbase = blockIdx.y * F.V;
+  const int e0 = S.ptr[blockIdx.y];
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < F.V; v += gridDim.x * blockDim.x) {
+    const int a = anc[fbase + v];
+    int o = -1;
+    if (a >= 0) {
+      const int mark = F.stamp_near[a];
+      if (mark < 0) o = (mark & INT_MAX) - e0;
+    }
+    S.owner[fbase + v] = o;
+  }
+}
+
+// grid.y = field: a histogram of the owners, one atomicAdd per wave and distinct owner among its lanes
+__global__ __launch_bounds__(THREADS) void k_field_owned(FieldDev F, FieldSets S, int *owned) {
+  const int V = F.V;
+  const int fbase = blockIdx.y * V;
+  int *mine = owned + S.ptr[blockIdx.y];
+  const int n_iter = (V + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, v = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, v += gridDim.x * blockDim.x) {
+    const int o = v < V ? S.owner[fbase + v] : -1;
+    unsigned long long rest = ballot(o >= 0);
+    while (rest) {  // (wave-uniform)
+      const int leader = __ffsll(rest) - 1;
+      const int lo = __shfl(o, leader);
+      const unsigned long long same = ballot(o == lo);
+      if (lane_id() == leader) atomicAdd(&mine[lo], __popcll(same));
+      rest &= ~same;
+    }
+  }
+}
+
+// k_field_gather with the owners, in each field (grid.y)
+__global__ __launch_bounds__(THREADS) void k_field_gather_sets(FieldDev F, FieldSets S,
+                                                               const int *__restrict__ targets, int n_t,
+                                                               float *cost_at, int *hops_at, int *owner_at) {
+  const int fbase = blockIdx.y * F.V;
+  const long long obase = (long long)blockIdx.y * n_t;
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n_t; j += gridDim.x * blockDim.x) {
+    const unsigned long long k = F.key[fbase + targets[j]];
+    const bool reached = k != FIELD_KEY_NONE;
+    if (cost_at) cost_at[obase + j] = reached ? key_cost(k) : __builtin_huge_valf();
+    if (hops_at) hops_at[obase + j] = reached ? (int)(unsigned)k : -1;
+    if (owner_at) owner_at[obase + j] = S.owner[fbase + targets[j]];
+  }
+}
+
+// k_field_route_walk for a set solve: the same walk, and hops[target] steps back from the target it must stand on
+// the member that owns the target, ids[ptr[field] + owner[target]] -- any other end is FIELD_ROUTE_BROKEN.
+__global__ __launch_bounds__(THREADS) void k_field_route_walk_sets(FieldDev F, FieldSets S,
+                                                                   const float *__restrict__ w,
+                                                                   const float *__restrict__ dist,
+                                                                   const int *__restrict__ route_field,
+                                                                   const int *__restrict__ route_target,
+                                                                   int n_routes, const int *__restrict__ offsets,
+                                                                   int *node_ids, FieldRouteInfo *infos) {
+  const int V = F.V;
+  const int sub = threadIdx.x & (GROUP - 1);
+  const int gshift = lane_id() & ~(GROUP - 1);
+  const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
+  const int ng = gridDim.x * blockDim.x / GROUP;
+  for (int r = g0; r < n_routes; r += ng) {
+    const int fbase = route_field[r] * V;
+    int v = route_target[r];
+    unsigned long long kv = F.key[fbase + v];
+    FieldRouteInfo out;
+    out.num_nodes = 0;
+    out.cost = __builtin_huge_valf();
+    out.path_length = 0.0f;
+    out.avg_risk = 0.0f;
+    if (kv != FIELD_KEY_NONE) {
+      const int h = (int)(unsigned)kv;
+      const int off = node_ids ? offsets[r] : 0;
+      const int room = node_ids ? offsets[r + 1] - off : 0;
+      float sum_dist = 0.0f, sum_w = 0.0f;
+      bool broken = false;
+      for (int i = h;; --i) {
+        if (sub == 0 && i < room) node_ids[off + i] = v;
+        if (i == 0) break;
+        const int u = F.parent[fbase + v];
+        if (u < 0 || u >= V) {
+          broken = true;
+          break;
+        }
+        const unsigned long long ku = F.key[fbase + u];
+        int edge = -1;
+        for (int k0 = F.rowptr[u], kend = F.rowptr[u + 1]; k0 < kend; k0 += GROUP) {
+          const int k = k0 + sub;
+          bool hit = false;
+          if (k < kend && F.col[k] == v) {
+            const float c = F.ec[k];
+            hit = __float_as_uint(c) != FIELD_EDGE_SKIP && key_extend(ku, c) == kv;
+          }
+          const unsigned hits = (unsigned)(ballot(hit) >> gshift) & ((1u << GROUP) - 1u);
+          if (hits) {
+            edge = k0 + __ffs(hits) - 1;
+            break;
+          }
+        }
+        if (edge < 0) {
+          broken = true;
+          break;
+        }
+        sum_dist += dist[edge];
+        sum_w += w[edge];
+        v = u;
+        kv = ku;
+      }
+      const int o = S.owner[fbase + route_target[r]];
+      const int e = S.ptr[route_field[r]] + o;
+      if (o < 0 || e >= S.n || v != S.ids[e]) broken = true;
+      out.num_nodes = broken ? FIELD_ROUTE_BROKEN : h + 1;
+      out.cost = key_cost(F.key[fbase + route_target[r]]);
+      out.path_length = sum_dist;
+      out.avg_risk = sum_w / (float)(h + 1);
+    }
+    if (sub == 0 && infos) infos[r] = out;
+  }
+}
+
 int field_blocks(long long items, int per_block) {
   const long long b = (items + per_block - 1) / per_block;
   return (int)std::max(1ll, std::min<long long>(b, MAX_BLOCKS));
@@ -683,6 +903,46 @@ void launch_field_route_walk(const FieldDev &F, const float *w, const float *dis
   if (n_routes <= 0) return;
   hipLaunchKernelGGL(k_field_route_walk, dim3(field_blocks((long long)n_routes * GROUP, THREADS)), dim3(THREADS), 0,
                      s, F, w, dist, route_field, route_target, n_routes, offsets, node_ids, infos, sources);
+}
+
+void launch_field_init_sets(const FieldDev &F, const FieldSets &S, float delta, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_init_sets, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, delta);
+  hipLaunchKernelGGL(k_field_seed, dim3(field_blocks(S.n, THREADS)), dim3(THREADS), 0, s, F, S);
+}
+
+void launch_field_owner_begin(const FieldDev &F, int *changed, hipStream_t s) {
+  (void)hipMemsetAsync(changed, 0, FIELD_OWNER_SWEEPS_MAX * sizeof(int), s);
+  hipLaunchKernelGGL(k_field_owner_begin, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F);
+}
+
+void launch_field_owner_sweep(const FieldDev &F, int sweep, int *changed, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_owner_sweep, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F.q[sweep & 1],
+                     F.q[~sweep & 1], F.N, changed + sweep);
+}
+
+void launch_field_owner_end(const FieldDev &F, const FieldSets &S, int sweeps, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_owner_end, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, S,
+                     F.q[sweeps & 1]);
+}
+
+void launch_field_owned(const FieldDev &F, const FieldSets &S, int *owned, hipStream_t s) {
+  (void)hipMemsetAsync(owned, 0, (size_t)S.n * sizeof(int), s);
+  hipLaunchKernelGGL(k_field_owned, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, S, owned);
+}
+
+void launch_field_gather_sets(const FieldDev &F, const FieldSets &S, const int *targets, int n_t, float *cost_at,
+                              int *hops_at, int *owner_at, hipStream_t s) {
+  if (n_t <= 0) return;
+  hipLaunchKernelGGL(k_field_gather_sets, dim3(field_blocks(n_t, THREADS), F.m), dim3(THREADS), 0, s, F, S, targets,
+                     n_t, cost_at, hops_at, owner_at);
+}
+
+void launch_field_route_walk_sets(const FieldDev &F, const FieldSets &S, const float *w, const float *dist,
+                                  const int *route_field, const int *route_target, int n_routes, const int *offsets,
+                                  int *node_ids, FieldRouteInfo *infos, hipStream_t s) {
+  if (n_routes <= 0) return;
+  hipLaunchKernelGGL(k_field_route_walk_sets, dim3(field_blocks((long long)n_routes * GROUP, THREADS)),
+                     dim3(THREADS), 0, s, F, S, w, dist, route_field, route_target, n_routes, offsets, node_ids, infos);
 }
 
 }  // namespace trg

@@ -497,4 +497,38 @@ void launch_field_route_walk(const FieldDev &F, const float *w, const float *dis
                              const int *route_target, int n_routes, const int *offsets, int *node_ids,
                              FieldRouteInfo *infos, const FieldSources &sources, hipStream_t s);
 
+// ---- source sets ("Source sets") ------------------------------------------------------
+// Field k starts from every member of set k = ids[ptr[k] .. ptr[k + 1]) at key (0, 0) instead of from one node.
+// An entry is an index into ids; the owner of an item is an entry of its field's set, counted from ptr[k].
+// Which entry stands for a member item is kept in the item's stamp_near word: FIELD_MEMBER | its least entry.
+// A round stamp is >= 1 and k_field_init leaves 0, so the word is negative for members only, and it stays so:
+// a member's key (0, 0) is never improved, hence the relaxation never pushes, and never stamps, a member.
+struct FieldSets {
+  const int *ptr;   // m + 1 entry offsets, ptr[0] == 0 (device)
+  const int *ids;   // ptr[m] node ids (device)
+  int n;            // ptr[m]
+  int *owner;       // per item: the owning entry of its field's set, -1 without a key; nullptr until asked for
+};
+constexpr int FIELD_MEMBER = INT32_MIN;
+constexpr int FIELD_OWNER_SWEEPS_MAX = 40;  // pointer jumping doubles: 2^31 hops need 31 sweeps and one that finds nothing
+// launch_field_init for a set solve: every item without a key, then every distinct member item seeded and
+// pushed once to near queue 0; F.ctrl's queue size and work are the count of distinct member items
+void launch_field_init_sets(const FieldDev &F, const FieldSets &S, float delta, hipStream_t s);
+// Owners of a finished set solve whose parent sweep ran, by pointer jumping over the parents.  begin: the first
+// ancestors into F.q[0] (a member itself, another reached item its parent, -1 without a key); sweep i reads
+// F.q[i & 1], writes F.q[~i & 1] = anc[anc[.]] and sets changed[i] when some entry moved (changed: zeroed by
+// begin, FIELD_OWNER_SWEEPS_MAX words); end: S.owner from F.q[sweeps & 1] once a sweep moved nothing.
+void launch_field_owner_begin(const FieldDev &F, int *changed, hipStream_t s);
+void launch_field_owner_sweep(const FieldDev &F, int sweep, int *changed, hipStream_t s);
+void launch_field_owner_end(const FieldDev &F, const FieldSets &S, int sweeps, hipStream_t s);
+// owned[entry] = items whose owner is that entry (S.n counts, zeroed here)
+void launch_field_owned(const FieldDev &F, const FieldSets &S, int *owned, hipStream_t s);
+// launch_field_gather with the owners: owner_at[k * n_t + j] = S.owner of (field k, targets[j]); any may be nullptr
+void launch_field_gather_sets(const FieldDev &F, const FieldSets &S, const int *targets, int n_t, float *cost_at,
+                              int *hops_at, int *owner_at, hipStream_t s);
+// launch_field_route_walk of a set solve with owners: a walk must end at the member that owns its target
+void launch_field_route_walk_sets(const FieldDev &F, const FieldSets &S, const float *w, const float *dist,
+                                  const int *route_field, const int *route_target, int n_routes, const int *offsets,
+                                  int *node_ids, FieldRouteInfo *infos, hipStream_t s);
+
 }  // namespace trg

@@ -103,6 +103,7 @@ EXPORTS = [
     "trg_engine_comm_unique_id", "trg_engine_comm_init", "trg_engine_comm_adopt", "trg_engine_comm_destroy",
     "trg_engine_stitch_exchange", "trg_engine_cost_field", "trg_engine_cost_field_batch",
     "trg_engine_field_routes", "trg_engine_cost_field_bounded", "trg_engine_field_reached",
+    "trg_engine_cost_field_sets",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -196,6 +197,8 @@ def load_library():
     L.trg_engine_cost_field_bounded.argtypes = [vp, C.c_int32, ip, fp, fp, C.c_int32, fp, ip, ip, ip, C.c_int32, fp, ip,
                                                 ip, ip, fp, C.POINTER(TrgFieldInfo)]
     L.trg_engine_field_reached.argtypes = [vp, C.c_int32, ip, fp, ip, C.c_int32, ip, C.POINTER(TrgFieldInfo)]
+    L.trg_engine_cost_field_sets.argtypes = [vp, C.c_int32, ip, ip, fp, C.c_int32, fp, ip, ip, ip, ip, C.c_int32, fp, ip,
+                                             ip, ip, ip, fp, C.POINTER(TrgFieldInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
     L.trg_engine_fallback_reason.restype = C.c_char_p
     _lib = L
@@ -579,6 +582,99 @@ class Engine:
                                                          None, 0, None, None, _i(got), None, None))
             nodes[k0:k0 + TRG_FIELD_BATCH_MAX] = got
         return nodes
+
+    def cost_fields_from(self, sets, targets=None, full=True, budget=None, settle=None):
+        """m cost fields in one solve, field k from EVERY node of sets[k] (a non-empty list of node ids; duplicates
+        and Invalid nodes allowed) at cost 0: trg_engine_cost_field_sets, DESIGN.md section 2, "Source sets".
+        -> cost_fields' dict ("cost", "hops", "parent" (m, V) with `full`; "cost_at", "hops_at" (m, n_t) with
+        `targets`; "reached", "info", "bound" under budget / settle) plus "owner" (m, V) with `full` and "owner_at"
+        with `targets` -- the index into sets[k] of the member a node's route starts from, -1 where unreached --
+        "owned" (a list of m int32 arrays: nodes per entry of sets[k]) and "sets" (the m int32 arrays as solved);
+        "sources" is every set's first id."""
+        if settle not in _SETTLE:
+            raise ValueError(f"cost_fields_from: settle {settle!r} (\"any\", \"all\" or None)")
+        sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
+        m = len(sets)
+        ptr = np.zeros(m + 1, np.int64)
+        np.cumsum([s.shape[0] for s in sets], out=ptr[1:])
+        if ptr[-1] > 2**31 - 1:
+            raise ValueError(f"cost_fields_from: {int(ptr[-1])} source entries do not fit 32 bits")
+        ptr = ptr.astype(np.int32)
+        ids = np.ascontiguousarray(np.concatenate(sets) if m else np.empty(0, np.int32), dtype=np.int32)
+        V, _ = self.graph_sizes("global")
+        out = {}
+        if full:
+            out["cost"] = np.empty((m, V), np.float32)
+            out["hops"] = np.empty((m, V), np.int32)
+            out["parent"] = np.empty((m, V), np.int32)
+            out["owner"] = np.empty((m, V), np.int32)
+        tg, nt = None, 0
+        if targets is not None:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+            nt = tg.shape[0]
+            out["cost_at"] = np.empty((m, nt), np.float32)
+            out["hops_at"] = np.empty((m, nt), np.int32)
+            out["owner_at"] = np.empty((m, nt), np.int32)
+        out["reached"] = np.zeros(max(m, 1), np.int32)
+        owned = np.zeros(max(int(ptr[-1]), 1), np.int32)
+        bounded = budget is not None or settle is not None
+        bud = None
+        if budget is not None:
+            bud = np.ascontiguousarray(np.broadcast_to(np.asarray(budget, dtype=np.float32).reshape(-1), (m,)))
+        if bounded:
+            out["bound"] = np.empty(max(m, 1), np.float32)
+        info = TrgFieldInfo()
+        self._chk(self.L.trg_engine_cost_field_sets(
+            self.h, m, _i(ptr), _i(ids), None if bud is None else _f(bud), _SETTLE[settle],
+            _f(out["cost"]) if full else None, _i(out["hops"]) if full else None, _i(out["parent"]) if full else None,
+            _i(out["owner"]) if full else None, None if tg is None else _i(tg), nt,
+            None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
+            None if tg is None else _i(out["owner_at"]), _i(owned), _i(out["reached"]),
+            _f(out["bound"]) if bounded else None, C.byref(info)))
+        out["owned"] = [owned[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
+        out["sets"] = sets
+        out["sources"] = np.array([s[0] for s in sets], np.int32)
+        out["info"] = info
+        return out
+
+    def nearest_source(self, nodes_or_xy, targets=None, budget=None):
+        """For every node, the nearest of the given nodes by risk cost: ONE set field from all of them.
+        `nodes_or_xy` is a list of node ids or an (n, 2) array of positions (each resolved as cost_field resolves a
+        source).  -> (cost float32, hops int32, owner int32, nodes int32): owner[v] is the index into `nodes` of the
+        node v's route starts from (the first of equal nodes), -1 where v is unreached or dearer than `budget`; over
+        the graph, or, with `targets` (node ids), at the targets only -- nothing of V entries is copied back."""
+        a = np.asarray(nodes_or_xy)
+        if a.ndim == 1 and np.issubdtype(a.dtype, np.integer):
+            nodes = np.ascontiguousarray(a, dtype=np.int32)
+        else:
+            nodes = self._resolve_nodes(a)
+        r = self.cost_fields_from([nodes], targets=targets, full=targets is None, budget=budget)
+        if targets is None:
+            return r["cost"][0], r["hops"][0], r["owner"][0], nodes
+        return r["cost_at"][0], r["hops_at"][0], r["owner_at"][0], nodes
+
+    def assign_frontiers(self, poses, budget=None):
+        """Every Frontier node to the pose of `poses` (m, 2) that reaches it cheapest: one set field from the poses'
+        nodes read at the Frontier nodes, and one routes call.  -> per pose (Frontier node ids it owns, ascending;
+        pick), where pick is choose_frontier over the pose's own Frontier nodes as (node, cost, path ids), or None
+        when it owns none.  No two poses get the same node; of two poses that resolve to one node the first owns
+        everything.  Without a Frontier node every pose gets (empty, None)."""
+        xy = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 2)
+        frontier = self._frontier_ids()
+        none = np.empty(0, np.int32)
+        if frontier.size == 0 or xy.shape[0] == 0:
+            return [(none, None) for _ in range(xy.shape[0])]
+        r = self.cost_fields_from([self._resolve_nodes(xy)], targets=frontier, full=False, budget=budget)
+        cost, hops, owner = r["cost_at"][0], r["hops_at"][0], r["owner_at"][0]
+        mine = [np.flatnonzero(owner == k) for k in range(xy.shape[0])]
+        picks = [choose_frontier(frontier[j], cost[j], hops[j]) for j in mine]
+        chosen = [(k, mine[k][p[1]]) for k, p in enumerate(picks) if p is not None]  # (pose, index into frontier)
+        routes = self.routes([0] * len(chosen), [frontier[j] for _, j in chosen], xyz=False,
+                             hops_at=[hops[j] for _, j in chosen]) if chosen else []
+        paths = {k: ids.tolist() for (k, _), (ids, _, _) in zip(chosen, routes)}
+        at = dict(chosen)
+        return [(frontier[mine[k]], None if k not in at else (int(frontier[at[k]]), float(cost[at[k]]), paths[k]))
+                for k in range(xy.shape[0])]
 
     def cost_matrix(self, nodes_or_xy, early_exit=False):
         """Least costs between m waypoints -> (cost (m, m) float32, hops (m, m) int32, node ids (m,)): entry
