@@ -4,6 +4,9 @@
 # by a few percent, runs on one box by well under one).
 #   bash scripts/ab.sh                      every ab/lib*.so, default environment
 #   bash scripts/ab.sh name=lib[,VAR=val]…  named variants: library (file under ab/ or "product") + environment
+# The series ends at the first run whose bench.py exits non-zero (a fault, an abort, the time limit): nothing more
+# is started on the GPU after it, and the script exits with that status.
+set -o pipefail
 R="${GRAFT_REPO_ROOT:-$(pwd)}"
 cat > /tmp/ab_fmt.py <<'PY'
 import json, sys
@@ -26,5 +29,11 @@ for i in 1 2 3; do
     envs=("TRG_ENGINE_LIB=$libpath" "TRG_BENCH_FAST=1")
     for ((k=1; k<${#parts[@]}; k++)); do envs+=("${parts[$k]}"); done
     env "${envs[@]}" timeout -k 10 "${AB_TIMEOUT:-150}" python3 "$R/bench.py" --steps "${AB_STEPS:-10}" --warmup 2 --no-cpu-baseline 2>/dev/null | python3 /tmp/ab_fmt.py "$name"
+    rc=("${PIPESTATUS[@]}")
+    if [ "${rc[0]}" -ne 0 ]; then
+      echo "$name: bench.py exited with ${rc[0]}: series stopped" >&2
+      exit "${rc[0]}"
+    fi
+    if [ "${rc[1]}" -ne 0 ]; then exit "${rc[1]}"; fi
   done
 done

@@ -90,6 +90,8 @@ __global__ void k_bfs_clear_tie(BfsDev B) {
 // newest entries of the cell).  Works from the slots' outcomes, so it also serves a launch whose
 // numbering never completed (look-back run-out).
 __global__ __launch_bounds__(256) void k_bfs_undo_slots(BfsDev B, int slots) {
+  // (the next level's expansion ran in between and is void: the repeat of resolve must not take its stamp)
+  if (blockIdx.x == 0 && threadIdx.x == 0) B.stats64[STATS64_EXPAND_START] = 0ull;
   const int slot = blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= slots) return;
   const int o = B.c_outcome[slot];
@@ -178,8 +180,12 @@ __device__ __forceinline__ uint32_t hash64(unsigned long long k) {
 //   round 2 evaluates every other call of the (few) pairs whose first call failed or could not be
 //   called by the device (uncertain slope gate) -- more than the reference strictly evaluates, which
 //   is harmless: the finalize pass below keeps the first SUCCESSFUL call of each pair.
-// k_first_insert: table pair -> smallest call number over ALL calls of the pair.
-__global__ __launch_bounds__(256) void k_first_insert(FinDev F, BfsDev B, long long c0, long long ncalls) {
+// k_first_insert: table pair -> smallest call number over ALL calls of the pair.  Its first thread also zeroes
+// *sel_count, the count word of the selection that follows it in the stream (the evaluations of the batch
+// before, which read the word, are complete by then: same stream).
+__global__ __launch_bounds__(256) void k_first_insert(FinDev F, BfsDev B, long long c0, long long ncalls,
+                                                      int *sel_count) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *sel_count = 0;
   const long long i = c0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ncalls) return;
   F.call_slot[i] = -1;
@@ -206,22 +212,37 @@ __global__ __launch_bounds__(256) void k_first_insert(FinDev F, BfsDev B, long l
   atomicOr(&B.ctrs[BFS_CTR_ERR], BFS_ERR_HASH);
 }
 
-__global__ __launch_bounds__(256) void k_calls_select(FinDev F, BfsDev B, long long c0, long long ncalls,
-                                                      int round, int *flag) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long i = c0 + t;
-  if (i >= ncalls) return;
-  int sel = 0;
-  if (B.call_status[i] == CALL_PENDING) {
-    const int first = F.ht_seq[F.call_slot[i]];
-    if (round == 1) {
-      sel = first == (int)i;
-    } else if (first != (int)i) {
-      const int fst = B.call_status[first];  // evaluated in round 1 or speculatively during the BFS
-      sel = (fst & EDGE_STATUS_MASK) != EDGE_OK || (fst & EDGE_GATE_UNCERTAIN);
+// Round-1 selection of the calls [c0, ncalls): per unordered pair the first call on it in program order,
+// appended to list in any order (record q of the evaluation is call list[q], and every result is stored under
+// its call number); *count = how many (zeroed by k_first_insert).  One atomic per workgroup that selected
+// anything: a batch beside the level loop is ~74 workgroups, the whole log after the loop ~30 k.  The same
+// thread adds the workgroup's number to *total (instrumentation).
+__global__ __launch_bounds__(256) void k_calls_select_append(FinDev F, BfsDev B, long long c0, long long ncalls,
+                                                             int *list, int *count, unsigned long long *total) {
+  __shared__ int wave_cnt[4];
+  __shared__ int wg_base;
+  const long long i = c0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  bool sel = false;
+  if (i < ncalls && B.call_status[i] == CALL_PENDING) {
+    const int slot = F.call_slot[i];  // (-1: the pair table was full, BFS_ERR_HASH is raised)
+    sel = slot >= 0 && F.ht_seq[slot] == (int)i;
+  }
+  const unsigned long long m = ballot(sel);
+  const int w = threadIdx.x >> 6;
+  if (lane_id() == 0) wave_cnt[w] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int tot = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    if (tot) {
+      wg_base = atomicAdd(count, tot);
+      if (total) atomicAdd(total, (unsigned long long)tot);
     }
   }
-  flag[t] = sel;
+  __syncthreads();
+  if (!sel) return;
+  int rank = __popcll(m & lanemask_lt());
+  for (int k = 0; k < w; ++k) rank += wave_cnt[k];
+  list[wg_base + rank] = (int)i;
 }
 
 // Round-2 selection over the whole call log in one pass: the calls that are NOT the first of their
@@ -247,21 +268,6 @@ __global__ __launch_bounds__(256) void k_calls_select2_append(FinDev F, BfsDev B
   }
   base = __shfl(base, 0);
   if (sel) list[base + __popcll(m & lanemask_lt())] = (int)i;
-}
-
-// list[off[t]] = c0 + t for the selected calls of [c0, c0 + n); the last thread adds their number to
-// *total (instrumentation)
-__global__ __launch_bounds__(256) void k_calls_compact(const int *flag, const int *off, long long c0,
-                                                       long long n, int *list, unsigned long long *total,
-                                                       int *count_out) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  if (flag[t]) list[off[t]] = (int)(c0 + t);
-  if (t == n - 1) {
-    const int kept = off[t] + (flag[t] ? 1 : 0);
-    if (total) atomicAdd(total, (unsigned long long)kept);
-    if (count_out) *count_out = kept;  // (off is scratch shared by the batches: a later evaluation reads this)
-  }
 }
 
 // A pair's edge comes from its first SUCCESSFUL call.  Every call already knows its pair's entry of the

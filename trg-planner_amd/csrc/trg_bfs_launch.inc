@@ -129,23 +129,19 @@ void launch_calls_eval(const MapView &m, QueryParams p, const BfsDev &B, const i
                      count_dev, ctr);
 }
 
-void launch_first_insert(const FinDev &F, const BfsDev &B, long long c0, long long c1, hipStream_t s) {
+void launch_first_insert(const FinDev &F, const BfsDev &B, long long c0, long long c1, int *sel_count,
+                         hipStream_t s) {
   if (c1 <= c0) return;
-  hipLaunchKernelGGL(k_first_insert, dim3((unsigned)((c1 - c0 + 255) / 256)), dim3(256), 0, s, F, B, c0, c1);
+  hipLaunchKernelGGL(k_first_insert, dim3((unsigned)((c1 - c0 + 255) / 256)), dim3(256), 0, s, F, B, c0, c1,
+                     sel_count);
 }
 
-// calls [c0, c1): flag[t] = call c0 + t is to be evaluated in this round; off = exclusive scan of flag
-// (off[c1 - c0] = how many); list = their indices in program order
-void launch_calls_select(const FinDev &F, const BfsDev &B, long long c0, long long c1, int round,
-                         int *flag, int *off, int *scan_tmp, int *list, unsigned long long *total,
-                         hipStream_t s, int *count_out) {
+// round 1 of the calls [c0, c1): list = the first call of every pair, in any order; *count = how many
+void launch_calls_select_append(const FinDev &F, const BfsDev &B, long long c0, long long c1, int *list,
+                                int *count, unsigned long long *total, hipStream_t s) {
   if (c1 <= c0) return;
-  const long long n = c1 - c0;
-  const unsigned nb = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(k_calls_select, dim3(nb), dim3(256), 0, s, F, B, c0, c1, round, flag);
-  launch_exclusive_scan(flag, off, (int)n, scan_tmp, s);
-  hipLaunchKernelGGL(k_calls_compact, dim3(nb), dim3(256), 0, s, (const int *)flag, (const int *)off, c0,
-                     n, list, total, count_out);
+  hipLaunchKernelGGL(k_calls_select_append, dim3((unsigned)((c1 - c0 + 255) / 256)), dim3(256), 0, s, F, B, c0,
+                     c1, list, count, total);
 }
 
 void launch_calls_select2_append(const FinDev &F, const BfsDev &B, long long ncalls, int *list, int *count,

@@ -512,6 +512,7 @@ struct TrgEngine {
   ~TrgEngine();
   TrgParams prm{};
   int device = 0;
+  int wall_clock_khz = 0;  // rate of the device's constant wall clock (wall_clock64)
   std::string err;
   std::string arch;
   bool device_ok = false;  // create went through: the entry points run (REQUIRE_DEVICE)
@@ -915,6 +916,8 @@ TrgStatus trg_engine_create(const TrgParams *params, int device, TrgEngine **out
   if (e->arch.rfind("gfx950", 0) != 0) {
     return e->fail(TRG_ERR_DEVICE, "kernels are built for gfx950 only, device is " + e->arch);
   }
+  HIPCHK(e, hipDeviceGetAttribute(&e->wall_clock_khz, hipDeviceAttributeWallClockRate, device));
+  if (e->wall_clock_khz <= 0) return e->fail(TRG_ERR_DEVICE, "the device reports no wall-clock rate");
   // (whatever exists when one of these fails is released by trg_engine_destroy)
   HIPCHK(e, e->s_main.create());
   // the deferred stream at the main stream's priority (the lowest leaves a longer tail after the loop:

@@ -50,12 +50,15 @@ static_assert(BFS_CTR_COUNT <= H_CLEAN_TOTALS && H_CLEAN_TOTALS + 2 <= H_ROUND2_
 // words of B.stats64 the host reads: calls the deferred selections kept, longest resolve wait, rows that went
 // multi-pass; then launch_bfs_stats's draws, samples, map points inside sampling discs and inside
 // speculative-edge queries, speculative parent edges (candidates) and the map points of the parent edges of
-// created nodes; from S64_PHASES 1024 shards x 8 phases of cycles (profiling builds)
+// created nodes; the start stamp of the expansion in flight and the wall-clock ticks of all expansions so far
+// (k_level_sample / k_level_resolve); from S64_PHASES 1024 shards x 8 phases of cycles (profiling builds)
 enum : int {
   S64_DEF_KEPT = 5, S64_MAX_SPIN, S64_MULTIPASS, S64_DRAWS, S64_SAMPLES, S64_DISC_HITS, S64_SPEC_HITS,
-  S64_CANDIDATES, S64_PARENT_HITS, S64_PHASES = 16, S64_WORDS = 16 + 1024 * 8
+  S64_CANDIDATES, S64_PARENT_HITS, S64_EXPAND_START = STATS64_EXPAND_START, S64_EXPAND_TICKS = STATS64_EXPAND_TICKS,
+  S64_PHASES = 16, S64_WORDS = 16 + 1024 * 8
 };
-static_assert(S64_PARENT_HITS < S64_PHASES, "report_stats fetches the words in front of S64_PHASES");
+static_assert(S64_PARENT_HITS < S64_EXPAND_START && S64_EXPAND_START < S64_EXPAND_TICKS && S64_EXPAND_TICKS < S64_PHASES,
+              "report_stats fetches the words in front of S64_PHASES");
 
 struct BfsBuffers {
   BfsDev B{};
@@ -65,8 +68,9 @@ struct BfsBuffers {
   DevArr nx, ny, nz, nstate, gcell, ncov, nexp, nhits, front0, front1, fxy0, fxy1;
   DevArr mid, unc_list, unc_rec, mt_rec, ctrs, stats64, wg_state, c_cell, tl, scan_tmp, s3_scratch;
   DevArr call_n1, call_n2, call_status, call_w, call_dist, newid_of_call, call_slot;  // the call log
-  // selection of the deferred calls that need evaluating (flags, their scan, the index list), round 2's count
-  DevArr sel_flag, sel_off, sel_list, sel_tmp, def_counts;
+  // selection of the deferred calls that need evaluating: the index list; def_counts: round 2's count, then the
+  // count of the round-1 batch in flight
+  DevArr sel_list, def_counts;
   // finalize: pair table, CSR in creation order, cleanGraph's renumbering and the cleaned graph
   DevArr ht_key, ht_seq, ok_seq, deg, fill, rowptr, col, seq, w, dist;
   DevArr map_order, keep_flag, keep_pos, new2old, old2new, deg_new, rowptr_new, col2, w2, dist2, xyz2, state2;
@@ -217,7 +221,7 @@ struct Build {
   long long def_lo = 0;  // first call not yet handed to the deferred pipeline
   size_t n_eval_batches = 0;
   std::vector<std::pair<Event, Event>> def_events;
-  Event ev0, ev1, evn0, evn1, ev_order, ev_nodes, ev_structure, ev_weights;
+  Event ev_order, ev_nodes, ev_structure, ev_weights;
   // The tail as two resources.  The weights of the edges that created the nodes (k_node_cov, k_node_weights)
   // feed ONE array of the result, w: with tail_split they run on the second stream beside the copies of the
   // other six arrays to the host, and w follows as the last copy (clean_and_fetch).  Without it (builds with
@@ -288,7 +292,7 @@ TrgStatus Build::read_ctrs() {
   return TRG_OK;
 }
 
-// The level's counters reach the host without a copy in the stream: the last workgroup of the next
+// The level's counters reach the host without a copy in the stream: the first workgroup of the next
 // level's k_level_sample writes them into pinned host memory with the level's stamp; the host polls the
 // stamp.
 TrgStatus Build::wait_stamp(int stamp) {
@@ -865,10 +869,8 @@ TrgStatus Build::allocate() {
   calls_bound = std::min<size_t>(vcap * (size_t)std::max(S, 1) * (size_t)CS, 0x7FFFFFF0u);
   fht = 1024;
   while ((unsigned long long)fht < (unsigned long long)calls_bound && fht < (1u << 31)) fht <<= 1;
-  const size_t sel_cap = (size_t)CALL_EVAL_BATCH + 2;
   if ((st = ensure_all(e, {{&bb.ht_key, fht * sizeof(unsigned long long)}, {&bb.ht_seq, fht * I},
-                           {&bb.ok_seq, fht * I}, {&bb.sel_flag, sel_cap * I}, {&bb.sel_off, (sel_cap + 1) * I},
-                           {&bb.sel_tmp, (sel_cap / 2048 + 16) * I}, {&bb.def_counts, I}})) != TRG_OK)
+                           {&bb.ok_seq, fht * I}, {&bb.def_counts, 2 * I}})) != TRG_OK)
     return st;
   F.ht_key = (unsigned long long *)bb.ht_key.p;
   F.ht_seq = (int *)bb.ht_seq.p;
@@ -904,15 +906,18 @@ TrgStatus Build::seed_root(float root_x, float root_y, float root_z) {
 }
 
 // ---- deferred wireEdge evaluations -------------------------------------------------------------------------
-// calls [def_lo, c1) of finished levels -> pair table, first-of-pair selection, evaluation
+// calls [def_lo, c1) of finished levels -> pair table, first-of-pair selection, evaluation: four launches per
+// batch.  The batches share one count word (and the edge scratch B.mid): each is ordered behind the one before
+// it, by the stream, and the first batch on the main stream by finish_deferred's wait for the deferred stream.
 TrgStatus Build::launch_deferred(long long c1, bool in_loop) {
+  int *sel_count = (int *)bb.def_counts.p + 1;
   while (def_lo < c1) {
     const long long c_hi = std::min<long long>(c1, def_lo + CALL_EVAL_BATCH);
     const long long n = c_hi - def_lo;
     hipStream_t st_ = in_loop ? s_def : s;
-    launch_first_insert(F, B, def_lo, c_hi, st_);
-    launch_calls_select(F, B, def_lo, c_hi, 1, (int *)bb.sel_flag.p, (int *)bb.sel_off.p, (int *)bb.sel_tmp.p,
-                        (int *)bb.sel_list.p + def_lo, B.stats64 + S64_DEF_KEPT, st_);
+    launch_first_insert(F, B, def_lo, c_hi, sel_count, st_);
+    launch_calls_select_append(F, B, def_lo, c_hi, (int *)bb.sel_list.p + def_lo, sel_count,
+                               B.stats64 + S64_DEF_KEPT, st_);
     // the evaluations, timed like the level kernels: every 8th batch, scaled up afterwards (an event pair per
     // batch was a fifth of the host's launch work per level)
     Event t0, t1;
@@ -922,7 +927,7 @@ TrgStatus Build::launch_deferred(long long c1, bool in_loop) {
       HIPCHK(e, hipEventRecord(t0.ev, st_));
     }
     // the number of selected calls lives on the device: the grid is an upper bound
-    launch_calls_eval(m.view, qp, B, (int *)bb.sel_list.p + def_lo, (int)n, (int *)bb.sel_off.p + n, e->d_ctr, st_);
+    launch_calls_eval(m.view, qp, B, (int *)bb.sel_list.p + def_lo, (int)n, sel_count, e->d_ctr, st_);
     e->stats.launches_edge_kernel++;
     if (t0.ev) {
       HIPCHK(e, hipEventRecord(t1.ev, st_));
@@ -959,16 +964,11 @@ TrgStatus Build::grow_call_log(size_t need) {
 // ---- phase 3: the level loop ---------------------------------------------------------------------------
 TrgStatus Build::level_loop() {
   TrgStatus st;
-  for (Event *ev : {&ev0, &ev1, &evn0, &evn1}) HIPCHK(e, ev->create());
   for (Event *ev : {&ev_order, &ev_nodes, &ev_structure, &ev_weights}) HIPCHK(e, ev->create(false));
   bool have_expand = false;  // this level's expansion was issued by the previous iteration
-  // Kernel timing inside the level loop is SAMPLED: an event pair around a kernel costs ~12 us of
-  // stream time.  Every TIMED_EVERY-th level is timed and the totals are scaled by
-  // launches / timed launches at the end (levels change slowly, so the subsample is unbiased).
-  constexpr int TIMED_EVERY = 8;
-  double ms_expand_timed = 0;
-  uint64_t n_expand_timed = 0, n_expand_all = 0;
-  bool expand_events_valid = false;  // ev0/ev1 bracket the expand launch of the current level
+  // The level kernels time every expansion themselves (B.stats64[S64_EXPAND_TICKS], report_stats): no event
+  // is recorded in this stream (a pair around a kernel costs ~12 us of stream time).
+  uint64_t n_expand_all = 0;
   int mcur = 1;
   int v_now = 1;  // nodes that exist before the current level (the root)
   long long call_base = 0;
@@ -990,11 +990,8 @@ TrgStatus Build::level_loop() {
       cur_tag = ++tag_serial;
       cur_ht = hash_size((size_t)mcur, S);
       B.ht_size = cur_ht;
-      HIPCHK(e, hipEventRecord(ev0.ev, s));
       launch_level_expand(m.view, qp, e->d_cos, e->d_sin, e->sampler.table_bits, e->sampler.seed,
                           e->epoch, B, mcur, nullptr, 0, parity, cur_tag, 0, e->d_ctr, s);
-      HIPCHK(e, hipEventRecord(ev1.ev, s));
-      expand_events_valid = true;
     }
     B.ht_size = cur_ht;
     // The rest of the level is launched at once and the host looks at the counters once, at the end.
@@ -1014,28 +1011,16 @@ TrgStatus Build::level_loop() {
     int spec_bound = (int)std::min<size_t>(
         (size_t)B.fcap, std::min<size_t>(level_slots, (size_t)(mcur + std::max(128, mcur / 4))));
     if (e->debug_spec_bound > 0) spec_bound = std::min(spec_bound, e->debug_spec_bound);
-    const bool next_timed = (levels + 1) % TIMED_EVERY == 0;
     int next_tag = ++tag_serial;
     const int stall_hook = levels == e->debug_stall_level ? 1 : (levels == e->debug_lookback_level ? 2 : 0);
     launch_level_resolve_commit(B, qp, mcur, TRG_NODE_VALID, call_base, lv.V0, cur_tag, ++res_epoch, s,
                                 stall_hook, e->resolve_tickets != 0, &ticket_base);
     const int stamp = ++bb.stamp_serial;  // published by the next level's expansion, launched right below
-    if (next_timed) HIPCHK(e, hipEventRecord(evn0.ev, s));
     launch_level_expand(m.view, qp, e->d_cos, e->d_sin, e->sampler.table_bits, e->sampler.seed,
                         e->epoch, Bn, spec_bound, B.ctrs + BFS_CTR_MNEXT, 0, parity ^ 1, next_tag, stamp,
                         e->d_ctr, s);
-    if (next_timed) HIPCHK(e, hipEventRecord(evn1.ev, s));
-    bool next_events_valid = next_timed;
     if ((st = wait_stamp(stamp)) != TRG_OK) return st;
-    {
-      float ms = 0;
-      if (expand_events_valid && hipEventQuery(ev1.ev) == hipSuccess &&
-          hipEventElapsedTime(&ms, ev0.ev, ev1.ev) == hipSuccess) {
-        ms_expand_timed += ms;
-        n_expand_timed++;
-      }
-      n_expand_all++;
-    }
+    n_expand_all++;
     read_level(lv, true);
     if (lv.err && getenv("TRG_TRACE_LEVELS"))
       fprintf(stderr, "[trg bfs] level %d: err=%d (%s) mcur=%d v=%d mnext=%d\n", levels, lv.err,
@@ -1055,7 +1040,6 @@ TrgStatus Build::level_loop() {
       HIPCHK(e, hipMemcpy(B.ctrs + ((parity ^ 1) ? BFS_CTR_NUNC1 : BFS_CTR_NUNC), ctr_fix, sizeof(int),
                           hipMemcpyHostToDevice));
       have_expand = false;  // issued at the top of the next iteration with a fresh tag
-      next_events_valid = false;
     } else {
       if (lv.mnext > spec_bound)
         launch_level_expand(m.view, qp, e->d_cos, e->d_sin, e->sampler.table_bits, e->sampler.seed,
@@ -1064,9 +1048,6 @@ TrgStatus Build::level_loop() {
       cur_tag = next_tag;
       cur_ht = next_ht;
     }
-    std::swap(ev0, evn0);
-    std::swap(ev1, evn1);
-    expand_events_valid = next_events_valid;
     v_now = lv.v_after;
     std::swap(B.front_cur, B.front_next);
     std::swap(B.fxy_cur, B.fxy_next);
@@ -1079,11 +1060,7 @@ TrgStatus Build::level_loop() {
   }
   HIPCHK(e, hipStreamSynchronize(s));
   e->stats.ms_bfs_loop = ms_since(t_loop);
-  // the expansion holds the sampling AND the speculative parent edges of a level: its time is
-  // reported as the "sample kernel", its algorithmic bytes are bytes_sample + bytes_spec
-  if (n_expand_timed)
-    e->stats.ms_sample_kernel += ms_expand_timed * (double)n_expand_all / (double)n_expand_timed;
-  e->stats.launches_sample_kernel += n_expand_all;
+  e->stats.launches_sample_kernel += n_expand_all;  // (their time: report_stats)
   V = v_now;
   ncalls = call_base;
   e->stats.sync_batches += (uint64_t)levels;
@@ -1157,15 +1134,18 @@ TrgStatus Build::finish_deferred() {
   HIPCHK(e, hipStreamSynchronize(s));
   const int nsel = *h_n2;
   // (a batch of evaluations shares the edge scratch: at most CALL_EVAL_BATCH at a time)
+  Event t0, t1;
   for (long long q0 = 0; q0 < nsel; q0 += CALL_EVAL_BATCH) {
     const int nq = (int)std::min<long long>(CALL_EVAL_BATCH, nsel - q0);
-    HIPCHK(e, hipEventRecord(ev0.ev, s));
+    HIPCHK(e, t0.create());
+    HIPCHK(e, t1.create());
+    HIPCHK(e, hipEventRecord(t0.ev, s));
     launch_calls_eval(m.view, qp, B, (int *)bb.sel_list.p + q0, nq, nullptr, e->d_ctr, s);
     e->stats.launches_edge_kernel++;
-    HIPCHK(e, hipEventRecord(ev1.ev, s));
-    HIPCHK(e, hipEventSynchronize(ev1.ev));
+    HIPCHK(e, hipEventRecord(t1.ev, s));
+    HIPCHK(e, hipEventSynchronize(t1.ev));
     float ms = 0;
-    if (hipEventElapsedTime(&ms, ev0.ev, ev1.ev) == hipSuccess) ms_edges += ms;
+    if (hipEventElapsedTime(&ms, t0.ev, t1.ev) == hipSuccess) ms_edges += ms;
   }
   e->stats.ms_edge_kernel += ms_edges;
   if ((st = read_ctrs()) != TRG_OK) return st;
@@ -1430,6 +1410,10 @@ TrgStatus Build::report_stats() {
   e->stats.ms_finalize_host = ms_since(t_fin);
   e->stats.bfs_levels = (uint64_t)levels;
   e->stats.bfs_max_spin = s64[S64_MAX_SPIN];
+  // the expansion holds the sampling AND the speculative parent edges of a level: its time is reported as the
+  // "sample kernel" (every level's, in ticks of the device's wall clock), its algorithmic bytes are
+  // bytes_sample + bytes_spec
+  e->stats.ms_sample_kernel += (double)s64[S64_EXPAND_TICKS] / (double)e->wall_clock_khz;
   e->stats.bfs_multipass_rows = s64[S64_MULTIPASS];
   return TRG_OK;
 }

@@ -271,9 +271,12 @@ struct BfsDev {
   // counters
   int *ctrs;
   int *host_ctrs;      // pinned host copy of ctrs + stamp, written by the next level's k_level_sample (may be null)
-  unsigned long long *stats64;  // [6]: longest resolve wait; [8..13]: expand phase cycles (profiling)
+  unsigned long long *stats64;  // [6]: longest resolve wait; [7]: multi-pass rows; [14], [15]: expansion timing (below)
   unsigned long long *tl;       // wall-clock marks of a few levels (-DLV_TIMELINE builds with TRG_TIMELINE set; else null)
 };
+// Words of stats64 that time the expansion of every level on the device: k_level_sample's first workgroup
+// stamps the wall clock, the first resolve workgroup of the k_level_resolve behind it adds the ticks since.
+constexpr int STATS64_EXPAND_START = 14, STATS64_EXPAND_TICKS = 15;
 
 struct FinDev {
   unsigned long long *ht_key;
@@ -326,10 +329,13 @@ void launch_node_weights(const BfsDev &B, int V, hipStream_t s);
 // bound, the kernels take min(count, *count_dev))
 void launch_calls_eval(const MapView &m, QueryParams p, const BfsDev &B, const int *list, int count,
                        const int *count_dev, DeviceCounters *ctr, hipStream_t s);
-void launch_first_insert(const FinDev &F, const BfsDev &B, long long c0, long long c1, hipStream_t s);
-void launch_calls_select(const FinDev &F, const BfsDev &B, long long c0, long long c1, int round,
-                         int *flag, int *off, int *scan_tmp, int *list, unsigned long long *total,
-                         hipStream_t s, int *count_out = nullptr);
+// pair table of the calls [c0, c1); zeroes *sel_count for the selection that follows in the same stream
+void launch_first_insert(const FinDev &F, const BfsDev &B, long long c0, long long c1, int *sel_count,
+                         hipStream_t s);
+// round 1 of the calls [c0, c1) in one launch: the first call of every pair appended to list in any order,
+// *count = how many (zero on entry: launch_first_insert), *total += that number
+void launch_calls_select_append(const FinDev &F, const BfsDev &B, long long c0, long long c1, int *list,
+                                int *count, unsigned long long *total, hipStream_t s);
 // round 2 over the whole log in one pass (*count must be zero): calls whose pair's first call failed
 void launch_calls_select2_append(const FinDev &F, const BfsDev &B, long long ncalls, int *list, int *count,
                                  unsigned long long *total, hipStream_t s);

@@ -467,6 +467,8 @@ __device__ __forceinline__ void sample_body(SampleSide<NW> &SS, const MapView &m
     if (threadIdx.x == BFS_CTR_DONE || threadIdx.x == BFS_CTR_COUNT - 1) v = pub_stamp;
     __hip_atomic_store(&B.host_ctrs[threadIdx.x], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+  // the expansion's start, for the k_level_resolve behind it (a top-up launch, node_base > 0, is inside the bracket)
+  if (node == 0 && threadIdx.x == 0) B.stats64[STATS64_EXPAND_START] = (unsigned long long)wall_clock64();
   if (count_dev) count = min(count, *count_dev);
   if (node >= count) return;
   const int tid = threadIdx.x;
@@ -1430,6 +1432,16 @@ __global__ __launch_bounds__(RWV *WAVE, (MULTI || STEP3) ? RESOLVE_WAVES_PER_SIM
     bid = wg_ticket;
   }
   if (bid >= nR + nC) return;
+  // The expansion in front of this launch (sampling, speculative edges, a top-up launch, the kernel boundaries up
+  // to here) has drained: its wall-clock ticks into the sum, and the stamp cleared, so that a rerun of this
+  // launch adds nothing.  One thread, plain loads and stores: the kernels of one stream order them.
+  if (bid == 0 && threadIdx.x == 0) {
+    const unsigned long long t0 = B.stats64[STATS64_EXPAND_START];
+    if (t0) {
+      B.stats64[STATS64_EXPAND_TICKS] += (unsigned long long)wall_clock64() - t0;
+      B.stats64[STATS64_EXPAND_START] = 0ull;
+    }
+  }
   if (bid >= nR) {
     commit_role(sh.C, B, m, S, call_base, stall_test, max_spin, V0, new_state, epoch, bid - nR, nR, nC, tag + 1);
   } else {
