@@ -275,6 +275,47 @@ def test_routes(engine, tmp_path, how):
         assert np.array_equal(hops, refs[k].hops[want]), k
 
 
+def test_single_sources_as_sets_of_one(engine, tmp_path):
+    """The two paths share their init, gather and walk kernels: three single sources -- one valid node of each
+    component and the isolated node -- solved by cost_fields and as three sets of one by cost_fields_from give the
+    same fields and the same routes to every node.  Only the equivalence is asserted; either side's values are
+    checked against field_ref / set_ref elsewhere."""
+    e = engine
+    e.set_option("field_delta_scale", "4")
+    g = with_isolated_node(fg.with_positions(fg.random_small(13)))
+    x = load_graph(e, g, tmp_path)
+    assert x.V == 44
+    first, second, _, isolated = _kinds(g)
+    sources = [first, second, isolated]
+    targets = [first, isolated, second, x.V // 2, 0]
+    pairs = [(k, t) for k in range(3) for t in range(x.V)]
+
+    def solve(call):
+        r = call()
+        routes = e.routes([k for k, _ in pairs], [t for _, t in pairs], hops_at=r["hops"].reshape(-1))
+        return r, routes
+
+    a, routes_a = solve(lambda: e.cost_fields(source_ids=sources, targets=targets, full=True))
+    b, routes_b = solve(lambda: e.cost_fields_from([[s] for s in sources], targets=targets, full=True))
+    assert np.array_equal(a["sources"], b["sources"]) and a["sources"].tolist() == sources
+    assert_rows("sets of one: ", "costs", b["cost"], a["cost"], as_bits=True)
+    for name in ("hops", "parent"):
+        assert_rows("sets of one: ", name, b[name], a[name])
+    assert np.array_equal(a["reached"], b["reached"]), (a["reached"], b["reached"])
+    assert a["reached"][2] == 1 and np.all(a["reached"][:2] > 1)  # the isolated node reaches itself only
+    assert np.array_equal(bits(a["cost_at"]), bits(b["cost_at"])) and np.array_equal(a["hops_at"], b["hops_at"])
+    assert np.array_equal(b["owner"], np.where(b["hops"] >= 0, 0, -1)), b["owner"]
+    assert np.array_equal(b["owner_at"], np.where(b["hops_at"] >= 0, 0, -1)), b["owner_at"]
+    assert len(routes_a) == len(routes_b) == len(pairs)
+    for (k, t), (ids_a, xyz_a, one_a), (ids_b, xyz_b, one_b) in zip(pairs, routes_a, routes_b):
+        at = f"sets of one, field {k}, target {t}: "
+        assert np.array_equal(ids_a, ids_b), at + f"ids {ids_a.tolist()} != {ids_b.tolist()}"
+        assert np.array_equal(bits(xyz_a), bits(xyz_b)), at
+        assert one_a.num_nodes == one_b.num_nodes == ids_a.size == a["hops"][k, t] + 1, at
+        for nm in ("cost", "path_length", "avg_risk"):
+            assert _b1(getattr(one_a, nm)) == _b1(getattr(one_b, nm)), at + nm
+
+
 BOUND_GRAPHS = {"random_small_7": (lambda: fg.with_positions(fg.random_small(7)), None),
                 "chain_3000": (lambda: fg.chain(3000), [0, 1700])}
 

@@ -27,6 +27,7 @@
 #include <fstream>
 #include <functional>
 #include <memory>
+#include <optional>
 #include <queue>
 #include <sstream>
 #include <string>

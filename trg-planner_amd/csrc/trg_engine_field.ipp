@@ -42,9 +42,8 @@ struct FieldBufs {
     FieldSources sources{};  // a walk must end at its field's
     bool parents = false;    // the parent sweep ran
     bool dev_csr = false;    // F's CSR is the device build's (gone stale when an update_graph begins)
-    bool sets = false;       // a set solve ("Source sets"): S is its sets, on the device
-    FieldSets S{};
-    bool owners = false;     // ... and the owner pass ran: S.owner is filled
+    std::optional<FieldSets> sets;  // of a set solve ("Source sets"), on the device
+    bool owners = false;     // ... and the owner pass ran: sets->owner is filled
   } last;
   DevArr set_ptr, set_ids, owner, owner_at, owned, own_changed;  // set solves; owner: m x V, only when asked for
   Pinned<int> h_changed;     // the owner pass's "a sweep moved something" word
@@ -327,10 +326,7 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
     // the tight word of a node without a key
     const bool under_bounds = run.bounded && pass == 0;
     F.tight = pass ? (const unsigned *)fb.cost.p : nullptr;
-    if (rq.set_ptr)
-      launch_field_init_sets(F, run.sets, delta, s);
-    else
-      launch_field_init(F, run.sources, delta, s);
+    launch_field_init(F, run.sources, rq.set_ptr ? &run.sets : nullptr, delta, s);
     for (int round = 0;;) {
       for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s, under_bounds ? &under : nullptr);
       HIPCHK(e, hipGetLastError());
@@ -401,11 +397,8 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
     if (rq.owner_at && (st = field_grow(e, fb.owner_at, nat * sizeof(int))) != TRG_OK) return st;
     float *d_cost_at = rq.cost_at ? (float *)fb.cost_at.p : nullptr;
     int *d_hops_at = rq.hops_at ? (int *)fb.hops_at.p : nullptr;
-    if (rq.set_ptr)
-      launch_field_gather_sets(F, run.sets, (const int *)fb.targets.p, rq.n_targets, d_cost_at, d_hops_at,
-                               rq.owner_at ? (int *)fb.owner_at.p : nullptr, s);
-    else
-      launch_field_gather(F, (const int *)fb.targets.p, rq.n_targets, d_cost_at, d_hops_at, s);
+    launch_field_gather(F, rq.set_ptr ? &run.sets : nullptr, (const int *)fb.targets.p, rq.n_targets, d_cost_at,
+                        d_hops_at, rq.owner_at ? (int *)fb.owner_at.p : nullptr, s);
   }
   if (rq.owned) {
     if ((st = field_grow(e, fb.owned, (size_t)run.sets.n * sizeof(int))) != TRG_OK) return st;
@@ -444,7 +437,7 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   run.info->ms_device = ms_dev;
   run.info->ms_total = ms_since(run.t_total);
   fb.last = FieldBufs::Last{e->graph_version, F, run.G.w, run.G.dist, run.sources, parents, run.G.dev_csr,
-                            rq.set_ptr != nullptr, run.sets, run.owners};
+                            rq.set_ptr ? std::optional<FieldSets>(run.sets) : std::nullopt, run.owners};
   fb.last.F.tight = nullptr;  // (its array holds the cost output now)
   return TRG_OK;
 }
@@ -552,7 +545,7 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   }
   if (last->sets && !last->owners) {  // a walk of a set solve ends at its target's owner
     int sweeps = 0;
-    if ((st = field_owner_pass(e, F, last->S, syncs, sweeps)) != TRG_OK) return st;
+    if ((st = field_owner_pass(e, F, *last->sets, syncs, sweeps)) != TRG_OK) return st;
     last->owners = true;
     info->rounds = sweeps;
   }
@@ -579,12 +572,8 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   std::vector<FieldRouteInfo> infos(n);
   const int *d_off = want_ids ? (const int *)fb.route_off.p : nullptr;
   int *d_ids = want_ids ? (int *)fb.route_ids.p : nullptr;
-  if (last->sets)
-    launch_field_route_walk_sets(F, last->S, last->w, last->dist, d_field, d_target, rq.n, d_off, d_ids,
-                                 (FieldRouteInfo *)fb.route_info.p, s);
-  else
-    launch_field_route_walk(F, last->w, last->dist, d_field, d_target, rq.n, d_off, d_ids,
-                            (FieldRouteInfo *)fb.route_info.p, last->sources, s);
+  launch_field_route_walk(F, last->w, last->dist, d_field, d_target, rq.n, d_off, d_ids,
+                          (FieldRouteInfo *)fb.route_info.p, last->sources, last->sets ? &*last->sets : nullptr, s);
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
   int32_t *ids_out = rq.node_ids;
@@ -677,6 +666,18 @@ TrgStatus field_reached(TrgEngine *e, int32_t field, int32_t *node_ids, float *c
   return TRG_OK;
 }
 
+// The shape checks that the bounded and the set entry share: the entry's message prefix, its noun for a field, and
+// `also`, the refusal of its own that stands between the two (nullptr: none).
+TrgStatus field_check_shape(TrgEngine *e, const std::string &call, const char *noun, int32_t m, int32_t n_targets,
+                            const char *also = nullptr) {
+  if (m < 1 || m > TRG_FIELD_BATCH_MAX)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": a batch of " + std::to_string(m) + " " + noun + " (1.." +
+                                            std::to_string(TRG_FIELD_BATCH_MAX) + ")");
+  if (also) return e->fail(TRG_ERR_INVALID_ARG, call + ": " + also);
+  if (n_targets < 0) return e->fail(TRG_ERR_INVALID_ARG, call + ": n_targets < 0");
+  return TRG_OK;
+}
+
 // the budget and settle checks that the bounded and the set entry share
 TrgStatus field_check_bounds(TrgEngine *e, int32_t m, const float *budget, int32_t settle, const int32_t *targets,
                              int32_t n_targets) {
@@ -722,10 +723,7 @@ TrgStatus trg_engine_cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *
   const bool resolve_only =
       sources_out && !cost && !hops && !parent && !cost_at && !hops_at && !reached_out && !bound_out && !info;
   return field_entry(e, info, "cost field", [&](TrgFieldInfo *out) {
-    if (m < 1 || m > TRG_FIELD_BATCH_MAX)
-      return e->fail(TRG_ERR_INVALID_ARG, "cost field: a batch of " + std::to_string(m) + " fields (1.." +
-                                              std::to_string(TRG_FIELD_BATCH_MAX) + ")");
-    if (n_targets < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field: n_targets < 0");
+    if (const TrgStatus st = field_check_shape(e, "cost field", "fields", m, n_targets); st != TRG_OK) return st;
     if (!source_ids && !source_xy) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no sources");
     if (source_ids)
       for (int k = 0; k < m; ++k)
@@ -744,11 +742,9 @@ TrgStatus trg_engine_cost_field_sets(TrgEngine *e, int32_t m, const int32_t *set
                                      int32_t *hops_at, int32_t *owner_at, int32_t *owned, int32_t *reached_out,
                                      float *bound_out, TrgFieldInfo *info) {
   return field_entry(e, info, "cost field sets", [&](TrgFieldInfo *out) {
-    if (m < 1 || m > TRG_FIELD_BATCH_MAX)
-      return e->fail(TRG_ERR_INVALID_ARG, "cost field sets: a batch of " + std::to_string(m) + " sets (1.." +
-                                              std::to_string(TRG_FIELD_BATCH_MAX) + ")");
-    if (!set_ptr || !set_ids) return e->fail(TRG_ERR_INVALID_ARG, "cost field sets: null set_ptr or set_ids");
-    if (n_targets < 0) return e->fail(TRG_ERR_INVALID_ARG, "cost field sets: n_targets < 0");
+    const char *no_sets = !set_ptr || !set_ids ? "null set_ptr or set_ids" : nullptr;
+    if (const TrgStatus st = field_check_shape(e, "cost field sets", "sets", m, n_targets, no_sets); st != TRG_OK)
+      return st;
     if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
     FieldRequest rq{m, nullptr, nullptr, cost, hops, parent, targets, n_targets, cost_at, hops_at,
                     nullptr, reached_out, false, budget, settle, bound_out};

@@ -38,8 +38,11 @@
 // Source sets ("Source sets"): a field may start from a set of nodes, every member at key
 // (0, 0) -- the same least fixed point with more seeds, so the round kernels are the plain ones; only the seeding
 // differs.  After the parent sweep every reached node hangs on exactly one member through its parents; the owner
-// pass finds that member by pointer jumping, in sweeps logarithmic in the greatest hop count.  A solve from single
-// sources launches none of this.
+// pass finds that member by pointer jumping, in sweeps logarithmic in the greatest hop count.  A single source is a
+// set of one whose owner is known without that pass: both kinds share k_field_init (which seeds single sources
+// itself and leaves sets to k_field_seed), k_field_gather (the owners at the targets where there are any) and the
+// route walk (which differs in where a walk must end); k_field_seed and the owner kernels a solve from single
+// sources never launches.
 //
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"
@@ -47,6 +50,7 @@
 #include <limits.h>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace trg {
 
@@ -130,11 +134,12 @@ __global__ __launch_bounds__(THREADS) void k_field_edge_cost(const int *__restri
   }
 }
 
-// grid.y = field
-__global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources S, float delta) {
+// grid.y = field.  `single`: field f starts at node S.id[f], keyed (0, 0) and queued here; else (a set solve) no
+// item has a key and the near queue is empty, for k_field_seed
+__global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources S, float delta, bool single) {
   const int V = F.V;
   const int f = blockIdx.y;
-  const int src = S.id[f];
+  const int src = single ? S.id[f] : -1;
   const int fbase = f * V;
   for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
     F.key[fbase + v] = v == src ? 0ull : FIELD_KEY_NONE;
@@ -143,18 +148,18 @@ __global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources
     F.stamp_far[fbase + v] = 0u;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    F.q[0][f] = fbase + src;
+    if (single) F.q[0][f] = fbase + src;
     F.ctrl->reached[f] = 0;
   }
   if (blockIdx.x == 0 && f == 0 && threadIdx.x == 0) {
     FieldCounters &c = F.ctrl->c;
-    c.n[0] = F.m;
+    c.n[0] = single ? F.m : 0;
     c.n[1] = 0;
     c.nfar[0] = c.nfar[1] = 0;
     c.fmin = ~0u;
     c.overflow = 0;
     FieldState &s = F.ctrl->s;
-    s.work = F.m;
+    s.work = single ? F.m : 0;
     s.rounds = 0;
     s.overflow = 0;
     s.thr = __float_as_uint(delta);
@@ -483,9 +488,11 @@ __global__ __launch_bounds__(THREADS) void k_field_cost_bits(FieldDev F, unsigne
     bits[i] = (unsigned)(F.key[i] >> 32);
 }
 
-// The finished keys at the target nodes, in each field (grid.y).
+// The finished keys at the target nodes, in each field (grid.y); with `owner` (a set solve's, per item) the
+// targets' owners as well.
 __global__ __launch_bounds__(THREADS) void k_field_gather(FieldDev F, const int *__restrict__ targets, int n_t,
-                                                          float *cost_at, int *hops_at) {
+                                                          float *cost_at, int *hops_at,
+                                                          const int *__restrict__ owner, int *owner_at) {
   const int fbase = blockIdx.y * F.V;
   const long long obase = (long long)blockIdx.y * n_t;
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n_t; j += gridDim.x * blockDim.x) {
@@ -493,6 +500,7 @@ __global__ __launch_bounds__(THREADS) void k_field_gather(FieldDev F, const int 
     const bool reached = k != FIELD_KEY_NONE;
     if (cost_at) cost_at[obase + j] = reached ? key_cost(k) : __builtin_huge_valf();
     if (hops_at) hops_at[obase + j] = reached ? (int)(unsigned)k : -1;
+    if (owner_at) owner_at[obase + j] = owner[fbase + targets[j]];
   }
 }
 
@@ -520,15 +528,20 @@ __global__ __launch_bounds__(THREADS) void k_field_route_len(FieldDev F, const i
 // of row u with col == v, a cost that is not the skip marker and key_extend(key[u], ec) == key[v]: the lanes
 // read 16 consecutive entries per trip, so the lowest matching lane of the first trip with a match is that
 // edge.  Everything the loops branch on is uniform over the group; the ballot is masked to the group's lanes.
-// A walk that loses its way -- a parent out of range, no route edge, an end that is not the field's source; none
+// A walk that loses its way -- a parent out of range, no route edge, an end that is not where it must end; none
 // can happen on the keys and parents of a finished solve -- reports num_nodes = FIELD_ROUTE_BROKEN, which the
 // host turns into an error, instead of a route that looks right.
+// Where it must end is all that SETS changes: at the field's source S.id[field], or, for a set solve (S its sets,
+// the owner pass has run), at the member that owns the target, ids[ptr[field] + owner[target]].  The single-source
+// instantiation has no owner array to read.
+template <bool SETS>
 __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const float *__restrict__ w,
                                                               const float *__restrict__ dist,
                                                               const int *__restrict__ route_field,
                                                               const int *__restrict__ route_target, int n_routes,
                                                               const int *__restrict__ offsets, int *node_ids,
-                                                              FieldRouteInfo *infos, FieldSources S) {
+                                                              FieldRouteInfo *infos,
+                                                              std::conditional_t<SETS, FieldSets, FieldSources> S) {
   const int V = F.V;
   const int sub = threadIdx.x & (GROUP - 1);
   const int gshift = lane_id() & ~(GROUP - 1);  // the group's first lane within the wave
@@ -581,7 +594,13 @@ __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const 
         v = u;
         kv = ku;
       }
-      if (v != S.id[route_field[r]]) broken = true;  // h steps back from the target end at the source
+      if constexpr (SETS) {  // h steps back from the target end at the member that owns it
+        const int o = S.owner[fbase + route_target[r]];
+        const int e = S.ptr[route_field[r]] + o;
+        if (o < 0 || e >= S.n || v != S.ids[e]) broken = true;
+      } else {  // ... at the source
+        if (v != S.id[route_field[r]]) broken = true;
+      }
       out.num_nodes = broken ? FIELD_ROUTE_BROKEN : h + 1;
       out.cost = key_cost(F.key[fbase + route_target[r]]);
       out.path_length = sum_dist;
@@ -592,34 +611,6 @@ __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const 
 }
 
 // ---- source sets ("Source sets") ----------------------------------------------------------
-
-// grid.y = field: k_field_init without a source -- no item has a key, the near queue is empty
-__global__ __launch_bounds__(THREADS) void k_field_init_sets(FieldDev F, float delta) {
-  const int V = F.V;
-  const int fbase = blockIdx.y * V;
-  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
-    F.key[fbase + v] = FIELD_KEY_NONE;
-    F.parent[fbase + v] = INT_MAX;
-    F.stamp_near[fbase + v] = 0;
-    F.stamp_far[fbase + v] = 0u;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) F.ctrl->reached[blockIdx.y] = 0;
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-    FieldCounters &c = F.ctrl->c;
-    c.n[0] = c.n[1] = 0;
-    c.nfar[0] = c.nfar[1] = 0;
-    c.fmin = ~0u;
-    c.overflow = 0;
-    FieldState &s = F.ctrl->s;
-    s.work = 0;
-    s.rounds = 0;
-    s.overflow = 0;
-    s.thr = __float_as_uint(delta);
-    s.delta = delta;
-    s.phase = 1;
-    s.far_sel = 0;
-  }
-}
 
 // One thread per entry of all sets: its item gets key (0, 0) and the least entry that names it (atomicMin on the
 // member word, see FieldSets); the entry that finds the word unmarked pushes the item, so a duplicate is queued
@@ -717,94 +708,6 @@ __global__ __launch_bounds__(THREADS) void k_field_owned(FieldDev F, FieldSets S
   }
 }
 
-// k_field_gather with the owners, in each field (grid.y)
-__global__ __launch_bounds__(THREADS) void k_field_gather_sets(FieldDev F, FieldSets S,
-                                                               const int *__restrict__ targets, int n_t,
-                                                               float *cost_at, int *hops_at, int *owner_at) {
-  const int fbase = blockIdx.y * F.V;
-  const long long obase = (long long)blockIdx.y * n_t;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n_t; j += gridDim.x * blockDim.x) {
-    const unsigned long long k = F.key[fbase + targets[j]];
-    const bool reached = k != FIELD_KEY_NONE;
-    if (cost_at) cost_at[obase + j] = reached ? key_cost(k) : __builtin_huge_valf();
-    if (hops_at) hops_at[obase + j] = reached ? (int)(unsigned)k : -1;
-    if (owner_at) owner_at[obase + j] = S.owner[fbase + targets[j]];
-  }
-}
-
-// k_field_route_walk for a set solve: the same walk, and hops[target] steps back from the target it must stand on
-// the member that owns the target, ids[ptr[field] + owner[target]] -- any other end is FIELD_ROUTE_BROKEN.
-__global__ __launch_bounds__(THREADS) void k_field_route_walk_sets(FieldDev F, FieldSets S,
-                                                                   const float *__restrict__ w,
-                                                                   const float *__restrict__ dist,
-                                                                   const int *__restrict__ route_field,
-                                                                   const int *__restrict__ route_target,
-                                                                   int n_routes, const int *__restrict__ offsets,
-                                                                   int *node_ids, FieldRouteInfo *infos) {
-  const int V = F.V;
-  const int sub = threadIdx.x & (GROUP - 1);
-  const int gshift = lane_id() & ~(GROUP - 1);
-  const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
-  const int ng = gridDim.x * blockDim.x / GROUP;
-  for (int r = g0; r < n_routes; r += ng) {
-    const int fbase = route_field[r] * V;
-    int v = route_target[r];
-    unsigned long long kv = F.key[fbase + v];
-    FieldRouteInfo out;
-    out.num_nodes = 0;
-    out.cost = __builtin_huge_valf();
-    out.path_length = 0.0f;
-    out.avg_risk = 0.0f;
-    if (kv != FIELD_KEY_NONE) {
-      const int h = (int)(unsigned)kv;
-      const int off = node_ids ? offsets[r] : 0;
-      const int room = node_ids ? offsets[r + 1] - off : 0;
-      float sum_dist = 0.0f, sum_w = 0.0f;
-      bool broken = false;
-      for (int i = h;; --i) {
-        if (sub == 0 && i < room) node_ids[off + i] = v;
-        if (i == 0) break;
-        const int u = F.parent[fbase + v];
-        if (u < 0 || u >= V) {
-          broken = true;
-          break;
-        }
-        const unsigned long long ku = F.key[fbase + u];
-        int edge = -1;
-        for (int k0 = F.rowptr[u], kend = F.rowptr[u + 1]; k0 < kend; k0 += GROUP) {
-          const int k = k0 + sub;
-          bool hit = false;
-          if (k < kend && F.col[k] == v) {
-            const float c = F.ec[k];
-            hit = __float_as_uint(c) != FIELD_EDGE_SKIP && key_extend(ku, c) == kv;
-          }
-          const unsigned hits = (unsigned)(ballot(hit) >> gshift) & ((1u << GROUP) - 1u);
-          if (hits) {
-            edge = k0 + __ffs(hits) - 1;
-            break;
-          }
-        }
-        if (edge < 0) {
-          broken = true;
-          break;
-        }
-        sum_dist += dist[edge];
-        sum_w += w[edge];
-        v = u;
-        kv = ku;
-      }
-      const int o = S.owner[fbase + route_target[r]];
-      const int e = S.ptr[route_field[r]] + o;
-      if (o < 0 || e >= S.n || v != S.ids[e]) broken = true;
-      out.num_nodes = broken ? FIELD_ROUTE_BROKEN : h + 1;
-      out.cost = key_cost(F.key[fbase + route_target[r]]);
-      out.path_length = sum_dist;
-      out.avg_risk = sum_w / (float)(h + 1);
-    }
-    if (sub == 0 && infos) infos[r] = out;
-  }
-}
-
 int field_blocks(long long items, int per_block) {
   const long long b = (items + per_block - 1) / per_block;
   return (int)std::max(1ll, std::min<long long>(b, MAX_BLOCKS));
@@ -837,8 +740,11 @@ void launch_field_edge_cost(const int *col, const float *w, const float *dist, c
                      state, V, E, safety_factor, ec, st);
 }
 
-void launch_field_init(const FieldDev &F, const FieldSources &sources, float delta, hipStream_t s) {
-  hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, sources, delta);
+void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets, float delta,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, sources, delta,
+                     sets == nullptr);
+  if (sets) hipLaunchKernelGGL(k_field_seed, dim3(field_blocks(sets->n, THREADS)), dim3(THREADS), 0, s, F, *sets);
 }
 
 void launch_field_round(const FieldDev &F, int round, hipStream_t s, const FieldSettle *under_bounds) {
@@ -876,11 +782,12 @@ void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents
   hipLaunchKernelGGL(k_field_output, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, cost, hops);
 }
 
-void launch_field_gather(const FieldDev &F, const int *targets, int n_t, float *cost_at, int *hops_at,
-                         hipStream_t s) {
+void launch_field_gather(const FieldDev &F, const FieldSets *sets, const int *targets, int n_t, float *cost_at,
+                         int *hops_at, int *owner_at, hipStream_t s) {
   if (n_t <= 0) return;
+  const int *owner = sets ? sets->owner : nullptr;
   hipLaunchKernelGGL(k_field_gather, dim3(field_blocks(n_t, THREADS), F.m), dim3(THREADS), 0, s, F, targets, n_t,
-                     cost_at, hops_at);
+                     cost_at, hops_at, owner, owner ? owner_at : nullptr);
 }
 
 void launch_field_parents_late(const FieldDev &F, hipStream_t s) {
@@ -899,15 +806,16 @@ void launch_field_route_len(const FieldDev &F, const int *route_field, const int
 
 void launch_field_route_walk(const FieldDev &F, const float *w, const float *dist, const int *route_field,
                              const int *route_target, int n_routes, const int *offsets, int *node_ids,
-                             FieldRouteInfo *infos, const FieldSources &sources, hipStream_t s) {
+                             FieldRouteInfo *infos, const FieldSources &sources, const FieldSets *sets,
+                             hipStream_t s) {
   if (n_routes <= 0) return;
-  hipLaunchKernelGGL(k_field_route_walk, dim3(field_blocks((long long)n_routes * GROUP, THREADS)), dim3(THREADS), 0,
-                     s, F, w, dist, route_field, route_target, n_routes, offsets, node_ids, infos, sources);
-}
-
-void launch_field_init_sets(const FieldDev &F, const FieldSets &S, float delta, hipStream_t s) {
-  hipLaunchKernelGGL(k_field_init_sets, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, delta);
-  hipLaunchKernelGGL(k_field_seed, dim3(field_blocks(S.n, THREADS)), dim3(THREADS), 0, s, F, S);
+  const dim3 grid(field_blocks((long long)n_routes * GROUP, THREADS));
+  if (sets)
+    hipLaunchKernelGGL(k_field_route_walk<true>, grid, dim3(THREADS), 0, s, F, w, dist, route_field, route_target,
+                       n_routes, offsets, node_ids, infos, *sets);
+  else
+    hipLaunchKernelGGL(k_field_route_walk<false>, grid, dim3(THREADS), 0, s, F, w, dist, route_field, route_target,
+                       n_routes, offsets, node_ids, infos, sources);
 }
 
 void launch_field_owner_begin(const FieldDev &F, int *changed, hipStream_t s) {
@@ -928,21 +836,6 @@ void launch_field_owner_end(const FieldDev &F, const FieldSets &S, int sweeps, h
 void launch_field_owned(const FieldDev &F, const FieldSets &S, int *owned, hipStream_t s) {
   (void)hipMemsetAsync(owned, 0, (size_t)S.n * sizeof(int), s);
   hipLaunchKernelGGL(k_field_owned, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, S, owned);
-}
-
-void launch_field_gather_sets(const FieldDev &F, const FieldSets &S, const int *targets, int n_t, float *cost_at,
-                              int *hops_at, int *owner_at, hipStream_t s) {
-  if (n_t <= 0) return;
-  hipLaunchKernelGGL(k_field_gather_sets, dim3(field_blocks(n_t, THREADS), F.m), dim3(THREADS), 0, s, F, S, targets,
-                     n_t, cost_at, hops_at, owner_at);
-}
-
-void launch_field_route_walk_sets(const FieldDev &F, const FieldSets &S, const float *w, const float *dist,
-                                  const int *route_field, const int *route_target, int n_routes, const int *offsets,
-                                  int *node_ids, FieldRouteInfo *infos, hipStream_t s) {
-  if (n_routes <= 0) return;
-  hipLaunchKernelGGL(k_field_route_walk_sets, dim3(field_blocks((long long)n_routes * GROUP, THREADS)),
-                     dim3(THREADS), 0, s, F, S, w, dist, route_field, route_target, n_routes, offsets, node_ids, infos);
 }
 
 }  // namespace trg

@@ -430,6 +430,19 @@ constexpr int FIELD_SETTLE_ALL = 2;
 struct FieldSources {
   int id[FIELD_MAX_SOURCES];
 };
+// Source sets ("Source sets"), which a solve may take in place of single sources: field k
+// starts from every member of set k = ids[ptr[k] .. ptr[k + 1]) at key (0, 0) instead of from one node.
+// An entry is an index into ids; the owner of an item is an entry of its field's set, counted from ptr[k].
+// Which entry stands for a member item is kept in the item's stamp_near word: FIELD_MEMBER | its least entry.
+// A round stamp is >= 1 and k_field_init leaves 0, so the word is negative for members only, and it stays so:
+// a member's key (0, 0) is never improved, hence the relaxation never pushes, and never stamps, a member.
+struct FieldSets {
+  const int *ptr;   // m + 1 entry offsets, ptr[0] == 0 (device)
+  const int *ids;   // ptr[m] node ids (device)
+  int n;            // ptr[m]
+  int *owner;       // per item: the owning entry of its field's set, -1 without a key; nullptr until asked for
+};
+constexpr int FIELD_MEMBER = INT32_MIN;
 struct FieldDev {
   const int *rowptr, *col;
   const float *ec;             // edge costs
@@ -448,8 +461,11 @@ struct FieldDev {
 };
 void launch_field_edge_cost(const int *col, const float *w, const float *dist, const int *state, int V, int E,
                             float safety_factor, float *ec, FieldEdgeStats *st, hipStream_t s);
-// field k starts at node sources.id[k], k < F.m (duplicates give identical fields)
-void launch_field_init(const FieldDev &F, const FieldSources &sources, float delta, hipStream_t s);
+// Field k starts at node sources.id[k], k < F.m (duplicates give identical fields).  With `sets` (a set solve; else
+// nullptr) sources is not read: every item is left without a key, then a second launch seeds every distinct member
+// item and pushes it once to near queue 0; F.ctrl's queue size and work are the count of distinct member items.
+void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets, float delta,
+                       hipStream_t s);
 // the settle step of a bounded round: n_t target nodes (device ids) and the mode, FIELD_SETTLE_*
 struct FieldSettle {
   const int *targets;
@@ -481,9 +497,10 @@ void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s);
 // nodes
 void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents, hipStream_t s);
 // the finished keys at n_t target nodes: cost_at / hops_at[k * n_t + j] of (field k, targets[j]), +inf and
-// -1 where unreached
-void launch_field_gather(const FieldDev &F, const int *targets, int n_t, float *cost_at, int *hops_at,
-                         hipStream_t s);
+// -1 where unreached; of a set solve whose owner pass ran (`sets`, else nullptr) owner_at likewise, sets->owner of
+// (field k, targets[j]).  Any output may be nullptr.
+void launch_field_gather(const FieldDev &F, const FieldSets *sets, const int *targets, int n_t, float *cost_at,
+                         int *hops_at, int *owner_at, hipStream_t s);
 // Routes of a finished solve ("Routes").  Layout of TrgRouteInfo (include/trg_engine.h).
 struct FieldRouteInfo {
   int num_nodes;
@@ -497,29 +514,16 @@ void launch_field_route_len(const FieldDev &F, const int *route_field, const int
                             int *len, hipStream_t s);
 // Walks route r from its target back along F.parent: node ids at [offsets[r], offsets[r + 1]) (the first ids of
 // a route that is longer), infos[r] over the whole route; w / dist are the CSR's edge arrays, sources the
-// solve's (a walk must end at its field's, else infos[r].num_nodes = FIELD_ROUTE_BROKEN).  node_ids may be
-// nullptr (offsets is then not read), infos may be nullptr.
+// solve's (a walk must end at its field's, else infos[r].num_nodes = FIELD_ROUTE_BROKEN).  Of a set solve, `sets`
+// are its sets with the owners filled (else nullptr): a walk must end at the member that owns its target, and
+// sources is not read.  node_ids may be nullptr (offsets is then not read), infos may be nullptr.
 void launch_field_route_walk(const FieldDev &F, const float *w, const float *dist, const int *route_field,
                              const int *route_target, int n_routes, const int *offsets, int *node_ids,
-                             FieldRouteInfo *infos, const FieldSources &sources, hipStream_t s);
+                             FieldRouteInfo *infos, const FieldSources &sources, const FieldSets *sets,
+                             hipStream_t s);
 
-// ---- source sets ("Source sets") ------------------------------------------------------
-// Field k starts from every member of set k = ids[ptr[k] .. ptr[k + 1]) at key (0, 0) instead of from one node.
-// An entry is an index into ids; the owner of an item is an entry of its field's set, counted from ptr[k].
-// Which entry stands for a member item is kept in the item's stamp_near word: FIELD_MEMBER | its least entry.
-// A round stamp is >= 1 and k_field_init leaves 0, so the word is negative for members only, and it stays so:
-// a member's key (0, 0) is never improved, hence the relaxation never pushes, and never stamps, a member.
-struct FieldSets {
-  const int *ptr;   // m + 1 entry offsets, ptr[0] == 0 (device)
-  const int *ids;   // ptr[m] node ids (device)
-  int n;            // ptr[m]
-  int *owner;       // per item: the owning entry of its field's set, -1 without a key; nullptr until asked for
-};
-constexpr int FIELD_MEMBER = INT32_MIN;
+// ---- the owner pass of a set solve ("Source sets") -------------------------------------
 constexpr int FIELD_OWNER_SWEEPS_MAX = 40;  // pointer jumping doubles: 2^31 hops need 31 sweeps and one that finds nothing
-// launch_field_init for a set solve: every item without a key, then every distinct member item seeded and
-// pushed once to near queue 0; F.ctrl's queue size and work are the count of distinct member items
-void launch_field_init_sets(const FieldDev &F, const FieldSets &S, float delta, hipStream_t s);
 // Owners of a finished set solve whose parent sweep ran, by pointer jumping over the parents.  begin: the first
 // ancestors into F.q[0] (a member itself, another reached item its parent, -1 without a key); sweep i reads
 // F.q[i & 1], writes F.q[~i & 1] = anc[anc[.]] and sets changed[i] when some entry moved (changed: zeroed by
@@ -529,12 +533,5 @@ void launch_field_owner_sweep(const FieldDev &F, int sweep, int *changed, hipStr
 void launch_field_owner_end(const FieldDev &F, const FieldSets &S, int sweeps, hipStream_t s);
 // owned[entry] = items whose owner is that entry (S.n counts, zeroed here)
 void launch_field_owned(const FieldDev &F, const FieldSets &S, int *owned, hipStream_t s);
-// launch_field_gather with the owners: owner_at[k * n_t + j] = S.owner of (field k, targets[j]); any may be nullptr
-void launch_field_gather_sets(const FieldDev &F, const FieldSets &S, const int *targets, int n_t, float *cost_at,
-                              int *hops_at, int *owner_at, hipStream_t s);
-// launch_field_route_walk of a set solve with owners: a walk must end at the member that owns its target
-void launch_field_route_walk_sets(const FieldDev &F, const FieldSets &S, const float *w, const float *dist,
-                                  const int *route_field, const int *route_target, int n_routes, const int *offsets,
-                                  int *node_ids, FieldRouteInfo *infos, hipStream_t s);
 
 }  // namespace trg

@@ -484,6 +484,34 @@ class Engine:
             return np.empty(0, np.int32)
         return np.flatnonzero(np.ctypeslib.as_array(v.node_state, shape=(v.num_nodes,)) == 1).astype(np.int32)
 
+    def _field_outputs(self, who, m, targets, full, budget, settle, owners=False):
+        """What cost_fields and cost_fields_from (`who`) share: `settle` checked, then the result dict with its
+        output arrays -- "cost", "hops", "parent" (and "owner") (m, V) with `full`; "cost_at", "hops_at" (and
+        "owner_at") (m, n_t) with `targets`; "reached"; "bound" under budget / settle -- and the arrays passed
+        beside them -> (dict, targets int32 or None, n_t, budget broadcast to m float32 or None)."""
+        if settle not in _SETTLE:
+            raise ValueError(f"{who}: settle {settle!r} (\"any\", \"all\" or None)")
+        V, _ = self.graph_sizes("global")
+        out = {}
+        if full:
+            out["cost"] = np.empty((m, V), np.float32)
+            for key in ("hops", "parent") + (("owner",) if owners else ()):
+                out[key] = np.empty((m, V), np.int32)
+        tg, nt = None, 0
+        if targets is not None:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+            nt = tg.shape[0]
+            out["cost_at"] = np.empty((m, nt), np.float32)
+            for key in ("hops_at",) + (("owner_at",) if owners else ()):
+                out[key] = np.empty((m, nt), np.int32)
+        out["reached"] = np.zeros(max(m, 1), np.int32)  # (m == 0 is refused by the call: no result has that size)
+        bud = None
+        if budget is not None:
+            bud = np.ascontiguousarray(np.broadcast_to(np.asarray(budget, dtype=np.float32).reshape(-1), (m,)))
+        if budget is not None or settle is not None:
+            out["bound"] = np.empty(max(m, 1), np.float32)
+        return out, tg, nt, bud
+
     def cost_fields(self, sources_xy=None, source_ids=None, targets=None, full=True, budget=None, settle=None):
         """m cost fields in one solve on the GPU (trg_engine_cost_field_batch; each field as cost_field's).
         Field k starts at source_ids[k], or, where source_ids is None or source_ids[k] == -1, at the node
@@ -498,34 +526,14 @@ class Engine:
         given the result also has "bound" (m float32)."""
         if sources_xy is None and source_ids is None:
             raise ValueError("cost_fields needs sources_xy or source_ids")
-        if settle not in _SETTLE:
-            raise ValueError(f"cost_fields: settle {settle!r} (\"any\", \"all\" or None)")
         ids = None if source_ids is None else np.ascontiguousarray(source_ids, dtype=np.int32).reshape(-1)
         xy = None if sources_xy is None else np.ascontiguousarray(sources_xy, dtype=np.float32).reshape(-1, 2)
         m = ids.shape[0] if ids is not None else xy.shape[0]
+        out, tg, nt, bud = self._field_outputs("cost_fields", m, targets, full, budget, settle)
         if ids is not None and xy is not None and xy.shape[0] != m:
             raise ValueError("cost_fields: sources_xy and source_ids differ in length")
-        V, _ = self.graph_sizes("global")
-        out = {}
-        if full:
-            out["cost"] = np.empty((m, V), np.float32)
-            out["hops"] = np.empty((m, V), np.int32)
-            out["parent"] = np.empty((m, V), np.int32)
-        tg, nt = None, 0
-        if targets is not None:
-            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
-            nt = tg.shape[0]
-            out["cost_at"] = np.empty((m, nt), np.float32)
-            out["hops_at"] = np.empty((m, nt), np.int32)
         out["sources"] = np.full(m, -1, np.int32)
-        out["reached"] = np.zeros(m, np.int32)
         info = TrgFieldInfo()
-        bounded = budget is not None or settle is not None
-        bud = None
-        if budget is not None:
-            bud = np.ascontiguousarray(np.broadcast_to(np.asarray(budget, dtype=np.float32).reshape(-1), (m,)))
-        if bounded:
-            out["bound"] = np.empty(m, np.float32)
         # the bounded entry's arguments; the batch entry's are these without budget, settle and bound_out
         sources = [self.h, m, None if ids is None else _i(ids), None if xy is None else _f(xy)]
         bounds = [None if bud is None else _f(bud), _SETTLE[settle]]
@@ -533,7 +541,7 @@ class Engine:
                    _i(out["parent"]) if full else None, None if tg is None else _i(tg), nt,
                    None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
                    _i(out["sources"]), _i(out["reached"])]
-        if bounded:
+        if "bound" in out:
             self._chk(self.L.trg_engine_cost_field_bounded(*sources, *bounds, *outputs, _f(out["bound"]), C.byref(info)))
         else:
             self._chk(self.L.trg_engine_cost_field_batch(*sources, *outputs, C.byref(info)))
@@ -591,38 +599,16 @@ class Engine:
         with `targets` -- the index into sets[k] of the member a node's route starts from, -1 where unreached --
         "owned" (a list of m int32 arrays: nodes per entry of sets[k]) and "sets" (the m int32 arrays as solved);
         "sources" is every set's first id."""
-        if settle not in _SETTLE:
-            raise ValueError(f"cost_fields_from: settle {settle!r} (\"any\", \"all\" or None)")
         sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
         m = len(sets)
+        out, tg, nt, bud = self._field_outputs("cost_fields_from", m, targets, full, budget, settle, owners=True)
         ptr = np.zeros(m + 1, np.int64)
         np.cumsum([s.shape[0] for s in sets], out=ptr[1:])
         if ptr[-1] > 2**31 - 1:
             raise ValueError(f"cost_fields_from: {int(ptr[-1])} source entries do not fit 32 bits")
         ptr = ptr.astype(np.int32)
         ids = np.ascontiguousarray(np.concatenate(sets) if m else np.empty(0, np.int32), dtype=np.int32)
-        V, _ = self.graph_sizes("global")
-        out = {}
-        if full:
-            out["cost"] = np.empty((m, V), np.float32)
-            out["hops"] = np.empty((m, V), np.int32)
-            out["parent"] = np.empty((m, V), np.int32)
-            out["owner"] = np.empty((m, V), np.int32)
-        tg, nt = None, 0
-        if targets is not None:
-            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
-            nt = tg.shape[0]
-            out["cost_at"] = np.empty((m, nt), np.float32)
-            out["hops_at"] = np.empty((m, nt), np.int32)
-            out["owner_at"] = np.empty((m, nt), np.int32)
-        out["reached"] = np.zeros(max(m, 1), np.int32)
         owned = np.zeros(max(int(ptr[-1]), 1), np.int32)
-        bounded = budget is not None or settle is not None
-        bud = None
-        if budget is not None:
-            bud = np.ascontiguousarray(np.broadcast_to(np.asarray(budget, dtype=np.float32).reshape(-1), (m,)))
-        if bounded:
-            out["bound"] = np.empty(max(m, 1), np.float32)
         info = TrgFieldInfo()
         self._chk(self.L.trg_engine_cost_field_sets(
             self.h, m, _i(ptr), _i(ids), None if bud is None else _f(bud), _SETTLE[settle],
@@ -630,7 +616,7 @@ class Engine:
             _i(out["owner"]) if full else None, None if tg is None else _i(tg), nt,
             None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
             None if tg is None else _i(out["owner_at"]), _i(owned), _i(out["reached"]),
-            _f(out["bound"]) if bounded else None, C.byref(info)))
+            _f(out["bound"]) if "bound" in out else None, C.byref(info)))
         out["owned"] = [owned[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
         out["sets"] = sets
         out["sources"] = np.array([s[0] for s in sets], np.int32)
