@@ -87,7 +87,8 @@ typedef struct TrgCsrView {
   const int32_t *col;       /* num_edges, Edge::dst_id_ */
   const float *weight;      /* num_edges, Edge::weight_ */
   const float *dist;        /* num_edges, Edge::dist_ */
-  const int32_t *creation_id; /* num_nodes: index of the node in creation order of the last build */
+  const int32_t *creation_id; /* num_nodes: index of the node among all nodes created since the last build began
+                               * (the nodes updates create count on; the index of a dropped node is not reused) */
 } TrgCsrView;
 
 /* Output of trg_engine_plan: reference TRG::planSafePath out-params (trg.cpp:603-608). */

@@ -540,7 +540,8 @@ struct TrgEngine {
   // graph state: slot == id (ids are dense at all times)
   std::vector<float> nx, ny, nz;
   std::vector<int> nstate;
-  std::vector<int> ncid;  // creation index inside the last build
+  std::vector<int> ncid;  // creation index since the last build began
+  int next_cid = 0;       // ... of the next node: counts every node created, the dropped ones too, through the updates
   std::unordered_map<int, int> order_map;  // mirrors trgStruct::nodes (iteration order only)
   // After a device build the container history is carried by an O(n) replica of the hashtable's
   // iteration order (map_order_sim.h); the real map is rebuilt from it only if a host path needs it.
@@ -753,6 +754,7 @@ void reset_graph_global(TrgEngine *e) {
   e->nz.clear();
   e->nstate.clear();
   e->ncid.clear();
+  e->next_cid = 0;
   e->order_map.clear();
   e->edges.reset(0);
   e->node_id = 0;
@@ -832,7 +834,7 @@ int add_node_host(TrgEngine *e, float x, float y, float z, int state) {
   e->ny.push_back(y);
   e->nz.push_back(z);
   e->nstate.push_back(state);
-  e->ncid.push_back((int)e->ncid.size());
+  e->ncid.push_back(e->next_cid++);
   // graph.nodes[node_id] = node (trg.cpp:248): into whichever representation of the container is current
   // (after a device build or a cleanGraph the keys are dense and ascending: the O(1) replica serves)
   if (e->real_map_stale) {
@@ -1405,6 +1407,7 @@ TrgStatus trg_engine_load_json(TrgEngine *e, const char *path) {
     e->kd_insert_order.push_back(n.id);  // kd_insert2 in file order (trg.cpp:103)
   }
   e->node_id = (int)V;
+  e->next_cid = (int)V;
   for (auto &ed : eds) e->edges.push(ed.s, ed.t, ed.w, ed.d);
   e->kd_valid = false;
   grid_rebuild(e);

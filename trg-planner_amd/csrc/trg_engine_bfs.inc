@@ -1105,6 +1105,7 @@ TrgStatus Build::finish_deferred() {
   // order (trg.cpp:248); cleanGraph iterates this container below
   e->nodes_sim.clear();  // resetGraph("global") -> nodes.clear(): buckets and policy persist
   e->nodes_sim.fill((size_t)V);
+  e->next_cid = V;  // (cleanGraph drops some of them; the nodes of later updates count on from all that were created)
   std::vector<int> map_order;
   e->nodes_sim.iteration_order(map_order);
   // ... and goes to the device on the (idle) second stream, for the renumbering kernels of cleanGraph
