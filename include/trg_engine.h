@@ -484,6 +484,37 @@ TrgStatus trg_engine_field_routes(TrgEngine *e, int32_t n_routes,
     int32_t cap,
     TrgRouteInfo *infos,   /* n_routes, may be NULL */
     TrgFieldInfo *info);   /* ms_device / ms_total / host_syncs of this call, may be NULL */
+/* Refresh ("Refresh"): the retained solve of an EARLIER graph brought to the current graph.
+ * The result -- cost bits, hops, parents, owners -- is that of a fresh solve from the same sources on the current
+ * graph; the work follows what changed between the graphs, not the graph's size.  The sources are the nodes the
+ * retained solve started from, wherever they are now; the number of fields is that solve's.
+ *   new2old, n_map   n_map == num_nodes entries: new2old[v] is the id node v had in the retained solve's graph, -1
+ *                    for a node that graph did not have.  NULL, 0: the map the engine recorded over the
+ *                    update_graph calls since that solve (init_graph, load_json, a reset and a failed update leave
+ *                    none).  The map only says where old keys are tried: a wrong entry costs work, never exactness;
+ *                    what it decides is where the sources are -- field k starts at the first node whose entry is
+ *                    its old source, a set at the first such node of every member.
+ *   cost .. reached_out   as trg_engine_cost_field_batch's; owner, owner_at as trg_engine_cost_field_sets', and
+ *                    only for a retained set solve; sources_out: the sources as ids of the current graph (a set's
+ *                    first member)
+ *   carried_out      m counts: the nodes whose old key was still that of a walk of the current graph and was
+ *                    kept as a starting point -- the sources alone when nothing could be used; may be NULL
+ *   info             as the batch call's; rounds counts the relaxation rounds of both warm passes, 0 when the
+ *                    graph change touched nothing the fields depend on
+ * Afterwards the retained solve is the refreshed one, of the current graph: trg_engine_field_routes and
+ * trg_engine_field_reached answer from it.
+ * TRG_ERR_INVALID_ARG, with the retained solve left as it was, when none is retained, when it is a bounded one,
+ * when it is already of the current graph, when new2old is NULL and the engine has no map (pass one, or solve
+ * again), when n_map != num_nodes or an entry is below -1 or not below the old node count, when a source has no
+ * node in the current graph (the message names the field, and for a set the member), when owner or owner_at is
+ * asked of a solve without sets, and for the target errors of the batch call.  The other codes as there. */
+TrgStatus trg_engine_cost_field_refresh(TrgEngine *e,
+    const int32_t *new2old, int32_t n_map,   /* NULL, 0: the map the engine recorded over its update_graph calls */
+    float *cost, int32_t *hops, int32_t *parent,            /* m x num_nodes each, any may be NULL */
+    const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at,
+    int32_t *owner, int32_t *owner_at,                      /* set solves only */
+    int32_t *sources_out, int32_t *reached_out, int32_t *carried_out,   /* m */
+    TrgFieldInfo *info);
 
 /* ---- instrumentation ------------------------------------------------------------------------- */
 TrgStatus trg_engine_get_stats(const TrgEngine *e, TrgStats *out);

@@ -604,6 +604,12 @@ struct TrgEngine {
                                             // exchange, made by trg_engine_comm_init / comm_adopt
   std::unique_ptr<FieldBufs> field;  // cost field: work arrays, edge costs and uploaded CSR (cached per graph_version)
   double field_delta_scale = 4.0;  // cost field: bucket width in mean edge costs (a measurement knob, see set_option)
+  // The node map of trg_engine_cost_field_refresh: for every node of the current graph its id in the graph of the
+  // retained cost-field solve, -1 for a node made since.  A solve starts it as the identity, update_graph composes
+  // it with its cleanGraph's renumbering; a new solve's start, every reset_graph_global (init_graph, load_json, a
+  // reset) and an update that fails leave none.
+  enum { FIELD_MAP_NONE, FIELD_MAP_IDENTITY, FIELD_MAP_EXPLICIT } field_map_state = FIELD_MAP_NONE;
+  std::vector<int> field_map;
   bool pool_valid = true;        // e->edges mirrors csr_global
   bool host_grid_valid = true;   // e->grid holds the current node set
   bool kd_order_dirty = false;   // kd_insert_order must be re-derived from order_map
@@ -764,6 +770,7 @@ void reset_graph_global(TrgEngine *e) {
   e->kd_insert_order.clear();
   e->goal_node = -1;
   e->graph_version++;
+  e->field_map_state = TrgEngine::FIELD_MAP_NONE;
   invalidate_stitched(e);
 }
 
@@ -1210,6 +1217,9 @@ TrgStatus trg_engine_update_graph(TrgEngine *e) {
   if (st != TRG_OK) return st;
   e->epoch++;
   e->dev_csr_valid = false;
+  const size_t nodes_before = e->nx.size();
+  const auto map_before = e->field_map_state;
+  e->field_map_state = TrgEngine::FIELD_MAP_NONE;  // (an update that fails leaves no map)
   const bool trace_up = getenv("TRG_TIMING") != nullptr;
   auto t_up = Clock::now();
   auto lap_up = [&](const char *what) {
@@ -1298,6 +1308,16 @@ TrgStatus trg_engine_update_graph(TrgEngine *e) {
     member_new[k] = member_old[e->last_new2old[k]];
   st = set_local_graph(e, &member_new);
   lap_up("setLocalGraph");
+  if (st == TRG_OK && map_before != TrgEngine::FIELD_MAP_NONE) {
+    // the cost field's node map through this update: a pre-clean id from nodes_before on is a node made here
+    std::vector<int> map(e->last_new2old.size());
+    for (size_t k = 0; k < map.size(); ++k) {
+      const int pre = e->last_new2old[k];
+      map[k] = (size_t)pre >= nodes_before ? -1 : map_before == TrgEngine::FIELD_MAP_IDENTITY ? pre : e->field_map[pre];
+    }
+    e->field_map.swap(map);
+    e->field_map_state = TrgEngine::FIELD_MAP_EXPLICIT;
+  }
   return st;  // cleanGraph(true) -> setLocalGraph (trg.cpp:532-534)
 }
 

@@ -1,7 +1,9 @@
 // Part of trg_engine.cpp (included at file scope): the cost field of the global graph -- the least (cost, hops)
 // key from one node to every node, on the device, for up to TRG_FIELD_BATCH_MAX sources in one solve (kernels:
 // trg_field.hip; an extension, the reference has no such call) -- and its C ABI entries.  One solver: the
-// single-source entry is its m == 1 call, the batch entry the bounded one's call without budgets or a settle mode.
+// single-source entry is its m == 1 call, the batch entry the bounded one's call without budgets or a settle mode;
+// the refresh (trg_engine_cost_field_refresh) is the same phases with the retained keys carried in before the work
+// arrays and warm passes in place of cold ones.
 
 namespace {
 
@@ -44,8 +46,13 @@ struct FieldBufs {
     bool dev_csr = false;    // F's CSR is the device build's (gone stale when an update_graph begins)
     std::optional<FieldSets> sets;  // of a set solve ("Source sets"), on the device
     bool owners = false;     // ... and the owner pass ran: sets->owner is filled
+    bool bounded = false;    // keys above a bound were removed: nothing a refresh can start from
+    // (F.V and F.m are the node count of its graph and its fields: what a refresh reads the old keys by)
   } last;
   DevArr set_ptr, set_ids, owner, owner_at, owned, own_changed;  // set solves; owner: m x V, only when asked for
+  std::vector<int32_t> h_set_ptr, h_set_ids;  // the sets as uploaded, for a refresh to carry to the next graph
+  DevArr key0, node_map, carried;  // refresh: the carried, then the anchored keys (m x V); new2old (V); counts (m)
+  Pinned<int> h_carried;     // per field
   Pinned<int> h_changed;     // the owner pass's "a sweep moved something" word
   DevArr route_field, route_target, route_len, route_off, route_ids, route_info;
   DevArr list_counts, list_off, list_tmp, list_ids, list_cost, list_hops;  // trg_engine_field_reached
@@ -87,6 +94,9 @@ struct FieldRequest {
   int32_t *owner = nullptr;     // m x V
   int32_t *owner_at = nullptr;  // m x n_targets
   int32_t *owned = nullptr;     // set_ptr[m]
+  // a refresh (trg_engine_cost_field_refresh): the retained keys carried through new2old instead of a cold start
+  const int32_t *new2old = nullptr;  // num_nodes entries, checked
+  int32_t *carried_out = nullptr;    // m
 };
 
 // an allocation that fails is a matter of capacity
@@ -202,6 +212,7 @@ TrgStatus field_begin(TrgEngine *e, FieldRun &) {
   if (!e->field) e->field.reset(new FieldBufs());
   FieldBufs &fb = *e->field;
   fb.last = FieldBufs::Last{};  // from here on the work arrays change
+  e->field_map_state = TrgEngine::FIELD_MAP_NONE;  // (the node map is of the retained solve's graph)
   HIPCHK(e, fb.h_state.ensure(1));
   HIPCHK(e, fb.h_stats.ensure(1));
   HIPCHK(e, fb.h_reached.ensure(TRG_FIELD_BATCH_MAX));
@@ -295,15 +306,12 @@ TrgStatus field_work_arrays(TrgEngine *e, FieldRun &run) {
   return TRG_OK;
 }
 
-// Near-far rounds, enqueued in batches; the bucket width is a fixed multiple of the mean edge cost.  Pass 1 finds
-// the least costs, pass 2 the hops over the tight edges (trg_field.hip).
-TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
+// what the passes read beside the graph: the target list and the sets
+TrgStatus field_uploads(TrgEngine *e, FieldRun &run) {
   FieldBufs &fb = *e->field;
   const FieldRequest &rq = run.rq;
   FieldDev &F = run.F;
   hipStream_t s = e->s_main;
-  const float delta = fb.mean_cost > 0.0 ? (float)(e->field_delta_scale * fb.mean_cost) : 0.0f;
-  const long long cap = 4LL * F.N + 64;
   if (rq.settle != TRG_FIELD_SETTLE_NONE || run.gather) {  // the target list: read by the settle step, the gather
     const TrgStatus st = field_grow(e, fb.targets, (size_t)rq.n_targets * sizeof(int));
     if (st != TRG_OK) return st;
@@ -318,7 +326,45 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
     HIPCHK(e, hipMemcpyAsync(fb.set_ids.p, rq.set_ids, (size_t)S.n * sizeof(int), hipMemcpyHostToDevice, s));
     S.ptr = (const int *)fb.set_ptr.p;
     S.ids = (const int *)fb.set_ids.p;
+    fb.h_set_ptr.assign(rq.set_ptr, rq.set_ptr + F.m + 1);
+    fb.h_set_ids.assign(rq.set_ids, rq.set_ids + S.n);
   }
+  return TRG_OK;
+}
+
+// the bucket width: a fixed multiple of the mean edge cost
+float field_delta(const TrgEngine *e) {
+  const FieldBufs &fb = *e->field;
+  return fb.mean_cost > 0.0 ? (float)(e->field_delta_scale * fb.mean_cost) : 0.0f;
+}
+
+// the rounds of one pass from round 0 on, enqueued in batches, until no work is left
+TrgStatus field_rounds(TrgEngine *e, FieldRun &run, const FieldSettle *under) {
+  FieldBufs &fb = *e->field;
+  const FieldDev &F = run.F;
+  hipStream_t s = e->s_main;
+  const long long cap = 4LL * F.N + 64;
+  for (int round = 0;;) {
+    for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s, under);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(fb.h_state, &F.ctrl->s, sizeof(FieldState), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    run.syncs++;
+    if (fb.h_state->overflow) return e->fail(TRG_ERR_DEVICE, "cost field: queue overflow");
+    if (fb.h_state->work == 0) break;
+    if (fb.h_state->rounds >= cap) return e->fail(TRG_ERR_DEVICE, "cost field did not converge");
+  }
+  run.rounds += fb.h_state->rounds;
+  return TRG_OK;
+}
+
+// Near-far rounds; pass 1 finds the least costs, pass 2 the hops over the tight edges (trg_field.hip).
+TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
+  FieldBufs &fb = *e->field;
+  const FieldRequest &rq = run.rq;
+  FieldDev &F = run.F;
+  hipStream_t s = e->s_main;
+  const float delta = field_delta(e);
   const FieldSettle under{(const int *)fb.targets.p, rq.n_targets, rq.settle};
   if (run.bounded) launch_field_bounds(F, run.budgets, s);
   for (int pass = 0; pass < 2; ++pass) {
@@ -327,17 +373,7 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
     const bool under_bounds = run.bounded && pass == 0;
     F.tight = pass ? (const unsigned *)fb.cost.p : nullptr;
     launch_field_init(F, run.sources, rq.set_ptr ? &run.sets : nullptr, delta, s);
-    for (int round = 0;;) {
-      for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s, under_bounds ? &under : nullptr);
-      HIPCHK(e, hipGetLastError());
-      HIPCHK(e, hipMemcpyAsync(fb.h_state, &F.ctrl->s, sizeof(FieldState), hipMemcpyDeviceToHost, s));
-      HIPCHK(e, hipStreamSynchronize(s));
-      run.syncs++;
-      if (fb.h_state->overflow) return e->fail(TRG_ERR_DEVICE, "cost field: queue overflow");
-      if (fb.h_state->work == 0) break;
-      if (fb.h_state->rounds >= cap) return e->fail(TRG_ERR_DEVICE, "cost field did not converge");
-    }
-    run.rounds += fb.h_state->rounds;
+    if (const TrgStatus st = field_rounds(e, run, under_bounds ? &under : nullptr); st != TRG_OK) return st;
     if (under_bounds) {
       launch_field_trim(F, s);
       HIPCHK(e, hipMemcpyAsync(fb.h_bound, F.ctrl->bound, (size_t)F.m * sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -351,19 +387,13 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
 constexpr int FIELD_OWNER_BATCH = 8;
 static_assert(FIELD_OWNER_SWEEPS_MAX % FIELD_OWNER_BATCH == 0, "the owner pass looks after whole batches");
 
-// The owner pass of a set solve whose parent sweep ran (trg_field.hip; DESIGN.md section 2, "Source sets"): pointer
-// jumping in the idle near queues until a sweep moves nothing -- about log2 of the greatest hop count of them --
-// then S.owner, whose m x V words are allocated here.  One host wait per FIELD_OWNER_BATCH sweeps.
-TrgStatus field_owner_pass(TrgEngine *e, const FieldDev &F, FieldSets &S, int &syncs, int &sweeps) {
+// The jumping sweeps between a begin and an end launch (the owner pass, a refresh's anchors), in the idle near
+// queues until a sweep moves nothing -- about log2 of the longest chain of them.  One host wait per
+// FIELD_OWNER_BATCH sweeps.
+TrgStatus field_jump(TrgEngine *e, const FieldDev &F, const char *what, int &syncs, int &sweeps) {
   FieldBufs &fb = *e->field;
   hipStream_t s = e->s_main;
-  TrgStatus st;
-  if ((st = field_grow(e, fb.owner, ((size_t)F.N + 4) * sizeof(int))) != TRG_OK) return st;
-  if ((st = field_grow(e, fb.own_changed, FIELD_OWNER_SWEEPS_MAX * sizeof(int))) != TRG_OK) return st;
-  HIPCHK(e, fb.h_changed.ensure(1));
-  S.owner = (int *)fb.owner.p;
   int *changed = (int *)fb.own_changed.p;
-  launch_field_owner_begin(F, changed, s);
   for (sweeps = 0;;) {
     for (int i = 0; i < FIELD_OWNER_BATCH; ++i, ++sweeps) launch_field_owner_sweep(F, sweeps, changed, s);
     HIPCHK(e, hipGetLastError());
@@ -371,8 +401,30 @@ TrgStatus field_owner_pass(TrgEngine *e, const FieldDev &F, FieldSets &S, int &s
     HIPCHK(e, hipStreamSynchronize(s));
     syncs++;
     if (fb.h_changed[0] == 0) break;
-    if (sweeps >= FIELD_OWNER_SWEEPS_MAX) return e->fail(TRG_ERR_DEVICE, "cost field sets: the owner pass did not end");
+    if (sweeps >= FIELD_OWNER_SWEEPS_MAX) return e->fail(TRG_ERR_DEVICE, std::string(what) + " did not end");
   }
+  return TRG_OK;
+}
+
+// the words of the jumping sweeps' "moved" flags
+TrgStatus field_jump_arrays(TrgEngine *e) {
+  FieldBufs &fb = *e->field;
+  if (const TrgStatus st = field_grow(e, fb.own_changed, FIELD_OWNER_SWEEPS_MAX * sizeof(int)); st != TRG_OK) return st;
+  HIPCHK(e, fb.h_changed.ensure(1));
+  return TRG_OK;
+}
+
+// The owner pass of a set solve whose parent sweep ran (trg_field.hip; DESIGN.md section 2, "Source sets"): pointer
+// jumping over the parents, then S.owner, whose m x V words are allocated here.
+TrgStatus field_owner_pass(TrgEngine *e, const FieldDev &F, FieldSets &S, int &syncs, int &sweeps) {
+  FieldBufs &fb = *e->field;
+  hipStream_t s = e->s_main;
+  TrgStatus st;
+  if ((st = field_grow(e, fb.owner, ((size_t)F.N + 4) * sizeof(int))) != TRG_OK) return st;
+  if ((st = field_jump_arrays(e)) != TRG_OK) return st;
+  S.owner = (int *)fb.owner.p;
+  launch_field_owner_begin(F, (int *)fb.own_changed.p, s);
+  if ((st = field_jump(e, F, "cost field sets: the owner pass", syncs, sweeps)) != TRG_OK) return st;
   launch_field_owner_end(F, S, sweeps, s);
   HIPCHK(e, hipGetLastError());
   return TRG_OK;
@@ -429,6 +481,7 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
     if (rq.sources_out) rq.sources_out[k] = run.sources.id[k];
     if (rq.reached_out) rq.reached_out[k] = fb.h_reached[k];
     if (rq.bound_out) rq.bound_out[k] = bits_float(run.bounded ? fb.h_bound[k] : FIELD_INF_BITS);
+    if (rq.carried_out) rq.carried_out[k] = fb.h_carried[k];
   }
   run.info->source = run.sources.id[0];
   run.info->reached = (int32_t)reached;
@@ -439,6 +492,67 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   fb.last = FieldBufs::Last{e->graph_version, F, run.G.w, run.G.dist, run.sources, parents, run.G.dev_csr,
                             rq.set_ptr ? std::optional<FieldSets>(run.sets) : std::nullopt, run.owners};
   fb.last.F.tight = nullptr;  // (its array holds the cost output now)
+  fb.last.bounded = run.bounded;
+  e->field_map_state = TrgEngine::FIELD_MAP_IDENTITY;  // update_graph takes the node map on from here
+  return TRG_OK;
+}
+
+// A refresh's stand-in for field_work_arrays' neighbour on the other side: the old keys, still in the retained
+// solve's array, gathered through the node map into a buffer of their own -- before field_work_arrays regrows
+// anything.  `old` is the retained solve as field_begin found it.
+TrgStatus field_carry(TrgEngine *e, FieldRun &run, const FieldDev &old) {
+  FieldBufs &fb = *e->field;
+  hipStream_t s = e->s_main;
+  const FieldDev &F = run.F;
+  TrgStatus st;
+  if ((st = field_grow(e, fb.key0, ((size_t)F.N + 4) * sizeof(unsigned long long))) != TRG_OK) return st;
+  if ((st = field_grow(e, fb.node_map, (size_t)F.V * sizeof(int))) != TRG_OK) return st;
+  if ((st = field_grow(e, fb.carried, TRG_FIELD_BATCH_MAX * sizeof(int))) != TRG_OK) return st;
+  if ((st = field_jump_arrays(e)) != TRG_OK) return st;
+  HIPCHK(e, fb.h_carried.ensure(TRG_FIELD_BATCH_MAX));
+  HIPCHK(e, hipMemcpyAsync(fb.node_map.p, run.rq.new2old, (size_t)F.V * sizeof(int), hipMemcpyHostToDevice, s));
+  launch_field_carry(old.key, old.V, (const int *)fb.node_map.p, F.V, F.m, (unsigned long long *)fb.key0.p, s);
+  HIPCHK(e, hipGetLastError());
+  return TRG_OK;
+}
+
+// one anchor of a refresh (trg_field.hip): begin, the jumping sweeps, end
+TrgStatus field_anchor(TrgEngine *e, FieldRun &run, bool first) {
+  FieldBufs &fb = *e->field;
+  hipStream_t s = e->s_main;
+  const FieldDev &F = run.F;
+  unsigned long long *key0 = (unsigned long long *)fb.key0.p;
+  launch_field_anchor_begin(F, run.sources, !run.rq.set_ptr, first ? nullptr : key0, (int *)fb.own_changed.p, s);
+  int sweeps = 0;
+  if (const TrgStatus st = field_jump(e, F, "cost field refresh: an anchor", run.syncs, sweeps); st != TRG_OK) return st;
+  launch_field_anchor_end(F, sweeps, first ? key0 : nullptr, first ? (int *)fb.carried.p : nullptr, s);
+  HIPCHK(e, hipGetLastError());
+  return TRG_OK;
+}
+
+// The passes of a refresh ("Refresh"), in field_passes' place: the carried keys anchored to the
+// new graph, pass 1 warm from them, the anchor again over the keys pass 1 left alone, pass 2 warm from those.  The
+// rounds are field_passes'.
+TrgStatus field_refresh_passes(TrgEngine *e, FieldRun &run) {
+  FieldBufs &fb = *e->field;
+  FieldDev &F = run.F;
+  hipStream_t s = e->s_main;
+  const float delta = field_delta(e);
+  TrgStatus st;
+  F.tight = nullptr;
+  launch_field_carry_init(F, (const unsigned long long *)fb.key0.p, run.sources, run.rq.set_ptr ? &run.sets : nullptr, s);
+  launch_field_supporters(F, s);
+  if ((st = field_anchor(e, run, true)) != TRG_OK) return st;
+  HIPCHK(e, hipMemcpyAsync(fb.h_carried, fb.carried.p, (size_t)F.m * sizeof(int), hipMemcpyDeviceToHost, s));
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 1) {
+      if ((st = field_anchor(e, run, false)) != TRG_OK) return st;
+      F.tight = (const unsigned *)fb.cost.p;
+    }
+    launch_field_warm_start(F, delta, pass == 1, s);
+    if ((st = field_rounds(e, run, nullptr)) != TRG_OK) return st;
+    if (pass == 0) launch_field_cost_bits(F, (unsigned *)fb.cost.p, s);
+  }
   return TRG_OK;
 }
 
@@ -447,8 +561,106 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
   TrgStatus st = plan_prepare(e);  // graph present, CSR rows and node grid current
   if (st != TRG_OK) return st;
   if ((st = field_check_request(e, run)) != TRG_OK || rq.resolve_only) return st;
-  for (const auto phase : {field_begin, field_graph, field_edge_costs, field_work_arrays,
+  for (const auto phase : {field_begin, field_graph, field_edge_costs, field_work_arrays, field_uploads,
                            field_passes, field_outputs})
+    if ((st = phase(e, run)) != TRG_OK) return st;
+  return TRG_OK;
+}
+
+struct RefreshRequest {
+  const int32_t *new2old;  // n_map entries, or nullptr: the engine's map
+  int32_t n_map;
+  float *cost;
+  int32_t *hops, *parent;
+  const int32_t *targets;
+  int32_t n_targets;
+  float *cost_at;
+  int32_t *hops_at, *owner, *owner_at, *sources_out, *reached_out, *carried_out;
+};
+
+// The retained solve of an earlier graph brought to the current one ("Refresh").  Every
+// refusal of its own comes before field_begin: the retained solve is then as it was.  After them it is a solve
+// like any other -- the same phases, with the carry before the work arrays and its own passes.
+TrgStatus field_refresh(TrgEngine *e, const RefreshRequest &rr, TrgFieldInfo *info) {
+  const auto t_total = Clock::now();
+  const std::string call = "cost field refresh";
+  TrgStatus st = plan_prepare(e);
+  if (st != TRG_OK) return st;
+  if (!e->field || e->field->last.version == 0)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": no cost-field solve is retained (solve first)");
+  const FieldBufs::Last old = e->field->last;
+  if (old.bounded)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is bounded (a bounded solve cannot be refreshed)");
+  if (old.version == e->graph_version && !(old.dev_csr && !e->dev_csr_valid))
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is already of the current graph");
+  const int V = (int)e->nx.size(), V_old = old.F.V, m = old.F.m;
+  std::vector<int32_t> identity;
+  const int32_t *map = rr.new2old;
+  int32_t n_map = rr.n_map;
+  if (!map) {
+    if (e->field_map_state == TrgEngine::FIELD_MAP_NONE)
+      return e->fail(TRG_ERR_INVALID_ARG, call + ": no node map is given and the engine has none for this graph "
+                                                 "(pass new2old, or solve again)");
+    if (e->field_map_state == TrgEngine::FIELD_MAP_IDENTITY) {
+      identity.resize((size_t)V_old);
+      for (int v = 0; v < V_old; ++v) identity[v] = v;
+      map = identity.data();
+      n_map = V_old;
+    } else {
+      map = e->field_map.data();
+      n_map = (int32_t)e->field_map.size();
+    }
+  }
+  if (n_map != V)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": the node map has " + std::to_string(n_map) + " entries, the graph " +
+                                            std::to_string(V) + " nodes");
+  std::vector<int32_t> first((size_t)V_old, -1);  // the first node of the current graph that names an old one
+  for (int v = 0; v < V; ++v) {
+    const int o = map[v];
+    if (o < -1 || o >= V_old)
+      return e->fail(TRG_ERR_INVALID_ARG, call + ": node map entry " + std::to_string(v) + " (" + std::to_string(o) +
+                                              ") is no node of the retained solve's graph (" + std::to_string(V_old) +
+                                              " nodes) and not -1");
+    if (o >= 0 && first[o] < 0) first[o] = v;
+  }
+  if ((rr.owner || rr.owner_at) && !old.sets)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": owner / owner_at asked of a solve without sets");
+  if (rr.n_targets < 0) return e->fail(TRG_ERR_INVALID_ARG, call + ": n_targets < 0");
+  // the sources, as ids of the current graph
+  std::vector<int32_t> src((size_t)m), set_ids;
+  const FieldBufs &fb0 = *e->field;
+  if (old.sets) {
+    set_ids.resize(fb0.h_set_ids.size());
+    for (int k = 0; k < m; ++k)
+      for (int j = fb0.h_set_ptr[k]; j < fb0.h_set_ptr[k + 1]; ++j)
+        if ((set_ids[j] = first[fb0.h_set_ids[j]]) < 0)
+          return e->fail(TRG_ERR_INVALID_ARG, call + ": member " + std::to_string(j - fb0.h_set_ptr[k]) + " of set " +
+                                                  std::to_string(k) + " (node " + std::to_string(fb0.h_set_ids[j]) +
+                                                  " of the retained solve's graph) has no node in the current graph");
+  } else {
+    for (int k = 0; k < m; ++k)
+      if ((src[k] = first[old.sources.id[k]]) < 0)
+        return e->fail(TRG_ERR_INVALID_ARG, call + ": the source of field " + std::to_string(k) + " (node " +
+                                                std::to_string(old.sources.id[k]) +
+                                                " of the retained solve's graph) has no node in the current graph");
+  }
+  const std::vector<int32_t> set_ptr = old.sets ? fb0.h_set_ptr : std::vector<int32_t>();
+  FieldRequest rq{m, old.sets ? nullptr : src.data(), nullptr, rr.cost, rr.hops, rr.parent, rr.targets, rr.n_targets,
+                  rr.cost_at, rr.hops_at, rr.sources_out, rr.reached_out, false, nullptr, TRG_FIELD_SETTLE_NONE, nullptr};
+  if (old.sets) {
+    rq.set_ptr = set_ptr.data();
+    rq.set_ids = set_ids.data();
+    rq.owner = rr.owner;
+    rq.owner_at = rr.owner_at;
+  }
+  rq.new2old = map;  // (the engine's own stays in place through the phases: field_begin only marks it ended)
+  rq.carried_out = rr.carried_out;
+  FieldRun run{rq, info, t_total};
+  if ((st = field_check_request(e, run)) != TRG_OK) return st;  // the targets, the 32-bit item index
+  for (const auto phase : {field_begin, field_graph, field_edge_costs})
+    if ((st = phase(e, run)) != TRG_OK) return st;
+  if ((st = field_carry(e, run, old.F)) != TRG_OK) return st;
+  for (const auto phase : {field_work_arrays, field_uploads, field_refresh_passes, field_outputs})
     if ((st = phase(e, run)) != TRG_OK) return st;
   return TRG_OK;
 }
@@ -754,6 +966,18 @@ TrgStatus trg_engine_cost_field_sets(TrgEngine *e, int32_t m, const int32_t *set
     rq.owner_at = owner_at;
     rq.owned = owned;
     return field_solve(e, rq, out);
+  });
+}
+
+TrgStatus trg_engine_cost_field_refresh(TrgEngine *e, const int32_t *new2old, int32_t n_map, float *cost,
+                                        int32_t *hops, int32_t *parent, const int32_t *targets, int32_t n_targets,
+                                        float *cost_at, int32_t *hops_at, int32_t *owner, int32_t *owner_at,
+                                        int32_t *sources_out, int32_t *reached_out, int32_t *carried_out,
+                                        TrgFieldInfo *info) {
+  return field_entry(e, info, "cost field refresh", [&](TrgFieldInfo *out) {
+    const RefreshRequest rr{new2old, n_map, cost, hops, parent, targets, n_targets, cost_at, hops_at,
+                            owner, owner_at, sources_out, reached_out, carried_out};
+    return field_refresh(e, rr, out);
   });
 }
 

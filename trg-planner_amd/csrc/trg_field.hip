@@ -44,6 +44,13 @@
 // route walk (which differs in where a walk must end); k_field_seed and the owner kernels a solve from single
 // sources never launches.
 //
+// Refresh ("Refresh"): the keys of a solve on an earlier graph, carried through a node map,
+// are starting points on the current one once the anchor has dropped every key that is not a walk's of the current
+// graph: the supporter forest of k_field_parent, pointer-jumped with the owner pass's sweep, keeps what hangs on a
+// source.  Both passes then start warm -- k_field_warm_seed queues every item one of whose edges improves its target,
+// the round kernels run as they are -- with a second anchor between them that cuts every key pass 1 changed, so that
+// the hops pass 2 starts from are those of tight walks.  The relaxation kernels know nothing of this.
+//
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"
 
@@ -708,6 +715,168 @@ __global__ __launch_bounds__(THREADS) void k_field_owned(FieldDev F, FieldSets S
   }
 }
 
+// ---- refresh ("Refresh") --------------------------------------------------------------------
+
+// grid.y = field: the keys of the retained solve (V_old nodes per field) at the nodes of the new graph, none where
+// the map names no old node.  `out` is not one of the old solve's arrays: they are regrown only after this ran.
+__global__ __launch_bounds__(THREADS) void k_field_carry(const unsigned long long *__restrict__ old_key, int V_old,
+                                                         const int *__restrict__ new2old, int V,
+                                                         unsigned long long *__restrict__ out) {
+  const long long obase = (long long)blockIdx.y * V_old;
+  const int fbase = blockIdx.y * V;
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
+    const int o = new2old[v];
+    out[fbase + v] = o >= 0 && o < V_old ? old_key[obase + o] : FIELD_KEY_NONE;
+  }
+}
+
+// grid.y = field: the carried keys into the work arrays, as k_field_init leaves them otherwise -- a single source at
+// (0, 0) (sets: k_field_seed follows, which needs the queue size this zeroes), no parents, no stamps.
+__global__ __launch_bounds__(THREADS) void k_field_carry_init(FieldDev F, const unsigned long long *__restrict__ carried,
+                                                              FieldSources S, bool single) {
+  const int V = F.V;
+  const int f = blockIdx.y;
+  const int src = single ? S.id[f] : -1;
+  const int fbase = f * V;
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
+    F.key[fbase + v] = v == src ? 0ull : carried[fbase + v];
+    F.parent[fbase + v] = INT_MAX;
+    F.stamp_near[fbase + v] = 0;
+    F.stamp_far[fbase + v] = 0u;
+  }
+  if (blockIdx.x == 0 && f == 0 && threadIdx.x == 0) {
+    F.ctrl->c.n[0] = F.ctrl->c.n[1] = 0;
+    F.ctrl->c.overflow = 0;
+    F.ctrl->s.work = 0;
+  }
+}
+
+// is item i (node v of field f) a source: a member of its set by its mark (FieldSets), else its field's one source
+__device__ __forceinline__ bool field_is_source(const FieldDev &F, const FieldSources &S, bool single, int f, int v) {
+  return single ? v == S.id[f] : F.stamp_near[f * F.V + v] < 0;
+}
+
+// grid.y = field: the first ancestor of every item in the supporter forest that k_field_parent left in F.parent --
+// itself for a source, its supporter's item for another item with a key, -1 without one or without a supporter.
+// With key0 (the second anchor) an item whose key is no longer key0's is cut: -1.
+__global__ __launch_bounds__(THREADS) void k_field_anchor_begin(FieldDev F, FieldSources S, bool single,
+                                                                const unsigned long long *__restrict__ key0) {
+  const int fbase = blockIdx.y * F.V;
+  int *anc = F.q[0];
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < F.V; v += gridDim.x * blockDim.x) {
+    const int i = fbase + v;
+    const unsigned long long k = F.key[i];
+    int a = -1;
+    if (k != FIELD_KEY_NONE && (!key0 || k == key0[i])) {
+      const int p = F.parent[i];
+      a = field_is_source(F, S, single, blockIdx.y, v) ? i : (p >= 0 && p < F.V ? fbase + p : -1);
+    }
+    anc[i] = a;
+  }
+}
+
+// grid.y = field: an item whose last ancestor is no source (-1: only a source points to itself) loses its key.
+// key0 / carried (the first anchor): the keys as they are now, and per field the count of items that kept theirs.
+__global__ __launch_bounds__(THREADS) void k_field_anchor_end(FieldDev F, const int *__restrict__ anc,
+                                                              unsigned long long *__restrict__ key0, int *carried) {
+  const int V = F.V;
+  const int fbase = blockIdx.y * V;
+  const int n_iter = (V + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, v = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, v += gridDim.x * blockDim.x) {
+    bool kept = false;
+    if (v < V) {
+      unsigned long long k = F.key[fbase + v];
+      if (anc[fbase + v] < 0 && k != FIELD_KEY_NONE) F.key[fbase + v] = k = FIELD_KEY_NONE;
+      if (key0) key0[fbase + v] = k;
+      kept = k != FIELD_KEY_NONE;
+    }
+    const unsigned long long m = ballot(kept);
+    if (carried && lane_id() == 0 && m) atomicAdd(&carried[blockIdx.y], __popcll(m));
+  }
+}
+
+// The control block and the stamps of a warm pass: threshold 0 (every push goes far, every far entry is live), both
+// queues and both piles empty, for k_field_warm_seed to fill far pile 0 at phase 1.  A member's mark stays
+// (FieldSets).  reset_parents: before the last parent sweep, the forest of the anchors is no longer needed.
+__global__ __launch_bounds__(THREADS) void k_field_warm_init(FieldDev F, float delta, bool reset_parents) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < F.N; i += gridDim.x * blockDim.x) {
+    if (F.stamp_near[i] > 0) F.stamp_near[i] = 0;
+    F.stamp_far[i] = 0u;
+    if (reset_parents) F.parent[i] = INT_MAX;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < F.m) F.ctrl->reached[threadIdx.x] = 0;  // (k_field_output counts into it)
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    FieldCounters &c = F.ctrl->c;
+    c.n[0] = c.n[1] = 0;
+    c.nfar[0] = c.nfar[1] = 0;
+    c.fmin = ~0u;
+    c.overflow = 0;
+    FieldState &s = F.ctrl->s;
+    s.work = 0;
+    s.rounds = 0;
+    s.overflow = 0;
+    s.thr = 0u;
+    s.delta = delta;
+    s.phase = 1;
+    s.far_sel = 0;
+  }
+}
+
+// The seeding sweep of a warm pass: one 16-lane group per item, four per wave, as k_field_relax -- but over every
+// item with a key, writing no key: an item one of whose edges would improve its target is pushed, once, to far
+// pile 0, stamped with phase 1.  TIGHT: pass 2, tight edges only.
+template <bool MULTI, bool TIGHT>
+__global__ __launch_bounds__(THREADS) void k_field_warm_seed(FieldDev F) {
+  const int N = MULTI ? F.N : F.V;
+  const int sub = threadIdx.x & (GROUP - 1);
+  const int gw = lane_id() / GROUP;
+  const int gshift = lane_id() & ~(GROUP - 1);
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  const int nwaves = gridDim.x * blockDim.x / WAVE;
+  constexpr int PER_WAVE = WAVE / GROUP;
+  for (int base = wave * PER_WAVE; base < N; base += nwaves * PER_WAVE) {  // (wave-uniform)
+    const int iu = base + gw;
+    unsigned long long ku = 0;
+    int k = 0, kend = 0;
+    int fbase = 0;
+    if (iu < N) {
+      ku = F.key[iu];
+      int u = iu;
+      if constexpr (MULTI) {
+        fbase = (int)((unsigned)iu / (unsigned)F.V) * F.V;
+        u = iu - fbase;
+      }
+      if (ku != FIELD_KEY_NONE) {
+        k = F.rowptr[u] + sub;
+        kend = F.rowptr[u + 1];
+      }
+    }
+    bool any = false;
+    for (;; k += GROUP) {
+      const bool act = k < kend;
+      if (ballot(act) == 0) break;  // (wave-uniform: the longest row of the wave's four)
+      if (act) {
+        const float c = F.ec[k];
+        if (__float_as_uint(c) != FIELD_EDGE_SKIP) {
+          int v = F.col[k];
+          if constexpr (MULTI) v += fbase;
+          const unsigned long long nk = key_extend(ku, c);
+          const bool tight = !TIGHT || (unsigned)(nk >> 32) == F.tight[v];
+          any |= tight && nk < F.key[v];
+        }
+      }
+    }
+    const unsigned hits = (unsigned)(ballot(any) >> gshift) & ((1u << GROUP) - 1u);
+    const bool push = sub == 0 && hits != 0;
+    const int slot = wave_reserve(push, &F.ctrl->c.nfar[0]);
+    if (push) {
+      F.stamp_far[iu] = 1u;
+      if (slot < F.N) F.far[0][slot] = iu;
+      else atomicOr(&F.ctrl->c.overflow, 1);
+    }
+  }
+}
+
 int field_blocks(long long items, int per_block) {
   const long long b = (items + per_block - 1) / per_block;
   return (int)std::max(1ll, std::min<long long>(b, MAX_BLOCKS));
@@ -831,6 +1000,49 @@ void launch_field_owner_sweep(const FieldDev &F, int sweep, int *changed, hipStr
 void launch_field_owner_end(const FieldDev &F, const FieldSets &S, int sweeps, hipStream_t s) {
   hipLaunchKernelGGL(k_field_owner_end, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, S,
                      F.q[sweeps & 1]);
+}
+
+void launch_field_carry(const unsigned long long *old_key, int V_old, const int *new2old, int V, int m,
+                        unsigned long long *out, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_carry, dim3(field_blocks(V, THREADS), m), dim3(THREADS), 0, s, old_key, V_old, new2old, V,
+                     out);
+}
+
+void launch_field_carry_init(const FieldDev &F, const unsigned long long *carried, const FieldSources &sources,
+                             const FieldSets *sets, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_carry_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, carried,
+                     sources, sets == nullptr);
+  if (sets) hipLaunchKernelGGL(k_field_seed, dim3(field_blocks(sets->n, THREADS)), dim3(THREADS), 0, s, F, *sets);
+}
+
+void launch_field_supporters(const FieldDev &F, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s, F);
+}
+
+void launch_field_anchor_begin(const FieldDev &F, const FieldSources &sources, bool single,
+                               const unsigned long long *key0, int *changed, hipStream_t s) {
+  (void)hipMemsetAsync(changed, 0, FIELD_OWNER_SWEEPS_MAX * sizeof(int), s);
+  hipLaunchKernelGGL(k_field_anchor_begin, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, sources,
+                     single, key0);
+}
+
+void launch_field_anchor_end(const FieldDev &F, int sweeps, unsigned long long *key0, int *carried, hipStream_t s) {
+  if (carried) (void)hipMemsetAsync(carried, 0, (size_t)F.m * sizeof(int), s);
+  hipLaunchKernelGGL(k_field_anchor_end, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F,
+                     F.q[sweeps & 1], key0, carried);
+}
+
+void launch_field_warm_start(const FieldDev &F, float delta, bool reset_parents, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_warm_init, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, delta,
+                     reset_parents);
+  const dim3 grid(field_blocks((long long)F.N * GROUP, THREADS));
+  if (F.m == 1) {
+    if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<false, true>), grid, dim3(THREADS), 0, s, F);
+    else hipLaunchKernelGGL((k_field_warm_seed<false, false>), grid, dim3(THREADS), 0, s, F);
+  } else {
+    if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<true, true>), grid, dim3(THREADS), 0, s, F);
+    else hipLaunchKernelGGL((k_field_warm_seed<true, false>), grid, dim3(THREADS), 0, s, F);
+  }
 }
 
 void launch_field_owned(const FieldDev &F, const FieldSets &S, int *owned, hipStream_t s) {

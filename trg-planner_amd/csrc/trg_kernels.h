@@ -534,4 +534,31 @@ void launch_field_owner_end(const FieldDev &F, const FieldSets &S, int sweeps, h
 // owned[entry] = items whose owner is that entry (S.n counts, zeroed here)
 void launch_field_owned(const FieldDev &F, const FieldSets &S, int *owned, hipStream_t s);
 
+// ---- refresh: the retained solve of an earlier graph brought to the current one ("Refresh") --
+// out[k * V + v] = old_key[k * V_old + new2old[v]], FIELD_KEY_NONE where new2old[v] is no node of the old graph; m
+// fields.  `out` is a buffer of its own (m * V keys): the old solve's arrays may be regrown once this is enqueued.
+void launch_field_carry(const unsigned long long *old_key, int V_old, const int *new2old, int V, int m,
+                        unsigned long long *out, hipStream_t s);
+// The work arrays as launch_field_init leaves them, but with the carried keys: the sources at (0, 0) -- sources.id,
+// or with `sets` every member, seeded and marked as by launch_field_init -- no parents, no stamps.  The queue that
+// the seeding of sets fills is not used: the warm start below empties it.
+void launch_field_carry_init(const FieldDev &F, const unsigned long long *carried, const FieldSources &sources,
+                             const FieldSets *sets, hipStream_t s);
+// F.parent[item] = the item's supporter under the keys as they are: the smallest u with an edge u -> v and
+// key_extend(key[u], c) == key[v], INT_MAX without one (launch_field_finish's parent sweep on its own)
+void launch_field_supporters(const FieldDev &F, hipStream_t s);
+// The anchor: an item keeps its key if its chain of supporters (F.parent) ends at a source.  begin: the first
+// ancestors into F.q[0] (a source itself; with key0, an item whose key differs from key0's is cut) and `changed`
+// zeroed; then launch_field_owner_sweep until a sweep moves nothing; end: every item whose last ancestor is no
+// source loses its key, key0 (may be nullptr) gets the keys after that and carried[k] (may be nullptr; m ints)
+// the number of field k's items that kept one.
+void launch_field_anchor_begin(const FieldDev &F, const FieldSources &sources, bool single,
+                               const unsigned long long *key0, int *changed, hipStream_t s);
+void launch_field_anchor_end(const FieldDev &F, int sweeps, unsigned long long *key0, int *carried, hipStream_t s);
+// A warm pass starts from the keys as they are: stamps cleared (a member's mark stays), threshold 0, both queues
+// empty, and in far pile 0 every item with a key one of whose edges (F.tight set: tight edges) improves its target.
+// launch_field_round from round 0 on then runs to the same fixed point as a pass from launch_field_init, provided
+// every key is one that a walk of the graph has.  reset_parents: F.parent = INT_MAX, for the last parent sweep.
+void launch_field_warm_start(const FieldDev &F, float delta, bool reset_parents, hipStream_t s);
+
 }  // namespace trg

@@ -103,7 +103,7 @@ EXPORTS = [
     "trg_engine_comm_unique_id", "trg_engine_comm_init", "trg_engine_comm_adopt", "trg_engine_comm_destroy",
     "trg_engine_stitch_exchange", "trg_engine_cost_field", "trg_engine_cost_field_batch",
     "trg_engine_field_routes", "trg_engine_cost_field_bounded", "trg_engine_field_reached",
-    "trg_engine_cost_field_sets",
+    "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -199,6 +199,8 @@ def load_library():
     L.trg_engine_field_reached.argtypes = [vp, C.c_int32, ip, fp, ip, C.c_int32, ip, C.POINTER(TrgFieldInfo)]
     L.trg_engine_cost_field_sets.argtypes = [vp, C.c_int32, ip, ip, fp, C.c_int32, fp, ip, ip, ip, ip, C.c_int32, fp, ip,
                                              ip, ip, ip, fp, C.POINTER(TrgFieldInfo)]
+    L.trg_engine_cost_field_refresh.argtypes = [vp, ip, C.c_int32, fp, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, ip, ip,
+                                                C.POINTER(TrgFieldInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
     L.trg_engine_fallback_reason.restype = C.c_char_p
     _lib = L
@@ -446,6 +448,7 @@ class Engine:
         self._chk(self.L.trg_engine_cost_field(self.h, int(source_id), None if xy is None else _f(xy), _f(cost),
                                                _i(hops), _i(parent), C.byref(info)))
         self._field_source = int(info.source)
+        self._field_shape = (1, False)
         return cost, hops, parent, info
 
     def field_path(self, parent, node, source=None):
@@ -545,6 +548,35 @@ class Engine:
             self._chk(self.L.trg_engine_cost_field_bounded(*sources, *bounds, *outputs, _f(out["bound"]), C.byref(info)))
         else:
             self._chk(self.L.trg_engine_cost_field_batch(*sources, *outputs, C.byref(info)))
+        self._field_shape = (m, False)
+        out["info"] = info
+        return out
+
+    def refresh_fields(self, new2old=None, targets=None, full=True):
+        """The retained solve of an EARLIER graph (cost_field, cost_fields or cost_fields_from before the last
+        update_graph calls) brought to the current graph: trg_engine_cost_field_refresh, DESIGN.md section 2,
+        "Refresh".  The result is that of a fresh solve from the same sources on the current graph, for work that
+        follows what the graph change touched.  new2old: for every node of the current graph its id in the
+        retained solve's graph, -1 for a new node; None: the map the engine recorded over its update_graph calls.
+        -> cost_fields' dict ("cost", "hops", "parent" (m, V) with `full`; "cost_at", "hops_at" (m, n_t) with
+        `targets`; "sources" as ids of the current graph, "reached", "info") plus "carried" (m counts of nodes whose
+        old key could be kept as a starting point), and for a retained set solve "owner" / "owner_at".  Afterwards
+        routes and field_reached answer from the refreshed solve."""
+        # (fields, from sets) of the retained solve, which only this object's solves can have left; without one the
+        # call refuses before it writes anything
+        m, sets = getattr(self, "_field_shape", (1, False))
+        n2o = None if new2old is None else np.ascontiguousarray(new2old, dtype=np.int32).reshape(-1)
+        out, tg, nt, _ = self._field_outputs("refresh_fields", m, targets, full, None, None, owners=sets)
+        out["sources"] = np.full(m, -1, np.int32)
+        out["carried"] = np.zeros(m, np.int32)
+        info = TrgFieldInfo()
+        self._chk(self.L.trg_engine_cost_field_refresh(
+            self.h, None if n2o is None else _i(n2o), 0 if n2o is None else n2o.shape[0],
+            _f(out["cost"]) if full else None, _i(out["hops"]) if full else None, _i(out["parent"]) if full else None,
+            None if tg is None else _i(tg), nt, None if tg is None else _f(out["cost_at"]),
+            None if tg is None else _i(out["hops_at"]), _i(out["owner"]) if full and sets else None,
+            _i(out["owner_at"]) if tg is not None and sets else None, _i(out["sources"]), _i(out["reached"]),
+            _i(out["carried"]), C.byref(info)))
         out["info"] = info
         return out
 
@@ -617,6 +649,7 @@ class Engine:
             None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
             None if tg is None else _i(out["owner_at"]), _i(owned), _i(out["reached"]),
             _f(out["bound"]) if "bound" in out else None, C.byref(info)))
+        self._field_shape = (m, True)
         out["owned"] = [owned[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
         out["sets"] = sets
         out["sources"] = np.array([s[0] for s in sets], np.int32)
