@@ -179,8 +179,9 @@ res["ratios"] = {
                                      v[f"b_batch_argmin_n{n}"]["ms_device_median"] for n in SIZES},
     "set_over_batch_argmin_wall": {str(n): v[f"a_set_n{n}"]["ms_wall_median"] /
                                    v[f"b_batch_argmin_n{n}"]["ms_wall_median"] for n in SIZES},
-    "set_of_n_over_single_source_set_device": {str(n): v[f"a_set_n{n}"]["ms_device_median"] / one
-                                               for n in SIZES + (4096,) if n != 1},
+    "set_of_n_over_single_source_set_device": {
+        **{str(n): v[f"a_set_n{n}"]["ms_device_median"] / one for n in SIZES if n != 1},
+        "4096": v["c_set_n4096"]["ms_device_median"] / one},
     "owner_pass_ms_device_n1": v["d_late_parents_owner_pass_and_walk_n1"]["ms_device_median"] -
                                v["d_late_parents_and_walk"]["ms_device_median"],
     "owner_pass_ms_device_n64": v["d_late_parents_owner_pass_and_walk_n64"]["ms_device_median"] -

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import field_graphs as fg
 import refresh_pairs as rp
 import refresh_ref as rr
 import route_ref
@@ -308,3 +309,75 @@ def test_refresh_through_update_graph(oa, mountain_gentle, ref):
         assert_fields("two updates: ", r, reference_fields(ref, g, prm["safety_factor"], r["sources"]))
     finally:
         e.close()
+
+
+def chain_without_last_link(V):
+    """fg.chain(V) with the link V-2 -> V-1 removed: the last node is cut off."""
+    g = fg.chain(V)
+    a = np.arange(V - 2)
+    return fg.from_edges(V, a, a + 1, g.w[:V - 2], g.dist[:V - 2])
+
+
+# (host waits, rounds) of the solve, then (host waits, rounds, carried per field) of its refresh, as the parent of
+# the commit that folded the refresh into the one solver gave them in two separate processes
+# (profiles/r14_field_refresh_fold.md).  Keys: graphs, bucket width, fields or "sets".
+REFRESH_WAITS = {
+    ('chain_cut', '4', 'sets'): ((11, 250), (7, 0, (99, 89))),
+    ('chain_cut', '4', 1): ((10, 200), (6, 0, (99,))),
+    ('chain_cut', '4', 4): ((12, 280), (6, 0, (99, 98, 97, 96))),
+    ('chain_cut', 'inf', 'sets'): ((11, 200), (7, 0, (99, 89))),
+    ('chain_cut', 'inf', 1): ((10, 200), (6, 0, (99,))),
+    ('chain_cut', 'inf', 4): ((10, 200), (6, 0, (99, 98, 97, 96))),
+    ('chain_restored', '4', 'sets'): ((11, 246), (7, 8, (99, 89))),
+    ('chain_restored', '4', 1): ((10, 198), (6, 4, (99,))),
+    ('chain_restored', '4', 4): ((12, 276), (6, 8, (99, 98, 97, 96))),
+    ('chain_restored', 'inf', 'sets'): ((11, 198), (7, 4, (99, 89))),
+    ('chain_restored', 'inf', 1): ((10, 198), (6, 4, (99,))),
+    ('chain_restored', 'inf', 4): ((10, 198), (6, 4, (99, 98, 97, 96))),
+    ('one_node', '4', 1): ((4, 2), (6, 0, (1,))),
+    ('one_node', '4', 4): ((4, 2), (6, 0, (1, 1, 1, 1))),
+    ('one_node', 'inf', 1): ((4, 2), (6, 0, (1,))),
+    ('one_node', 'inf', 4): ((4, 2), (6, 0, (1, 1, 1, 1))),
+}
+
+
+def refresh_waits(tmp_path):
+    """The table that test_refresh_host_waits_pinned pins, measured."""
+    import trg_planner
+    chain, cut = fg.chain(100), chain_without_last_link(100)
+    one = fg.oddities()["one_node"][0]
+    pairs = {"chain_cut": (chain, cut), "chain_restored": (cut, chain), "one_node": (one, one)}
+    sets = [[0], [10, 50]]
+    e = trg_planner.Engine(**MOUNTAIN)
+    got = {}
+    for name, (a, b) in pairs.items():
+        V = len(a.state)
+        for scale in ("inf", "4"):
+            e.set_option("field_delta_scale", scale)
+            for m in (1, 4) + (("sets",) if V > 1 else ()):
+                load_graph(e, a, tmp_path, name + "_a")  # a new graph_version: the next solve is the first on it
+                if m == "sets":
+                    info = e.cost_fields_from(sets)["info"]
+                else:
+                    info = e.cost_fields(source_ids=[min(k, V - 1) for k in range(m)])["info"]
+                load_graph(e, b, tmp_path, name + "_b")
+                r = e.refresh_fields(new2old=np.arange(V, dtype=np.int32))
+                assert m != "sets" or r["owner"].shape == (2, V)
+                got[name, scale, m] = ((info.host_syncs, info.rounds),
+                                       (r["info"].host_syncs, r["info"].rounds, tuple(r["carried"].tolist())))
+    e.close()
+    return got
+
+
+def test_refresh_host_waits_pinned(tmp_path):
+    """The refresh's counterpart of tests/test_gpu_cost_field.py::test_host_waits_pinned: how often a refresh waits
+    for the device (the edge costs of the new graph, one wait per 8 jumping sweeps of each of the two anchors and of
+    the owner pass, one per batch of 32 rounds in each pass, one for the outputs), how many rounds it runs and how
+    many keys it carries are pinned, next to the waits and rounds of the solve before it.  The directed chain of 100
+    nodes to the same chain without its last link and back, through the identity map (round counts on a directed
+    chain are a function of the graph), and the one-node graph onto a reload of itself; bucket widths inf and 4;
+    one field and four from single sources, and two sets of one and two members refreshed with the owners."""
+    got = refresh_waits(tmp_path)
+    for key in sorted(got, key=repr):
+        print(f"    {key!r}: {got[key]!r},")
+    assert got == REFRESH_WAITS

@@ -2,8 +2,8 @@
 // key from one node to every node, on the device, for up to TRG_FIELD_BATCH_MAX sources in one solve (kernels:
 // trg_field.hip; an extension, the reference has no such call) -- and its C ABI entries.  One solver: the
 // single-source entry is its m == 1 call, the batch entry the bounded one's call without budgets or a settle mode;
-// the refresh (trg_engine_cost_field_refresh) is the same phases with the retained keys carried in before the work
-// arrays and warm passes in place of cold ones.
+// the refresh (trg_engine_cost_field_refresh) is a request of its own kind to the same field_solve: a check phase
+// before the others, the retained keys carried in before the work arrays, and passes that start warm.
 
 namespace {
 
@@ -74,6 +74,8 @@ void field_release(TrgEngine *e) {
 
 static_assert(FIELD_MAX_SOURCES == TRG_FIELD_BATCH_MAX, "the kernels' and the header's batch limit differ");
 
+// What an entry asks of field_solve.  Every entry value-initialises one and names what it sets: all else is null, 0,
+// false, TRG_FIELD_SETTLE_NONE.
 struct FieldRequest {
   int32_t m;
   const int32_t *source_ids;  // m, or nullptr: all from source_xy
@@ -90,14 +92,18 @@ struct FieldRequest {
   int32_t settle;             // TRG_FIELD_SETTLE_*, over `targets`
   float *bound_out;           // m, may be nullptr
   // a set solve (trg_engine_cost_field_sets): field k starts from set_ids[set_ptr[k] .. set_ptr[k + 1])
-  const int32_t *set_ptr = nullptr, *set_ids = nullptr;
-  int32_t *owner = nullptr;     // m x V
-  int32_t *owner_at = nullptr;  // m x n_targets
-  int32_t *owned = nullptr;     // set_ptr[m]
-  // a refresh (trg_engine_cost_field_refresh): the retained keys carried through new2old instead of a cold start
-  const int32_t *new2old = nullptr;  // num_nodes entries, checked
-  int32_t *carried_out = nullptr;    // m
+  const int32_t *set_ptr, *set_ids;
+  int32_t *owner;     // m x V
+  int32_t *owner_at;  // m x n_targets
+  int32_t *owned;     // set_ptr[m]
+  // a refresh (trg_engine_cost_field_refresh): m and the sources or sets are the retained solve's, filled in by
+  // field_check_refresh, and its keys are carried through new2old instead of a cold start
+  bool refresh;
+  const int32_t *new2old;  // n_map entries, or nullptr: the engine's map
+  int32_t n_map;
+  int32_t *carried_out;    // m
 };
+static_assert(TRG_FIELD_SETTLE_NONE == 0, "a value-initialised request has no settle mode");
 
 // an allocation that fails is a matter of capacity
 TrgStatus field_grow(TrgEngine *e, DevArr &a, size_t bytes) {
@@ -109,7 +115,7 @@ TrgStatus field_grow(TrgEngine *e, DevArr &a, size_t bytes) {
 // One solve on its way through the phases below: the request, what the checks derived from it, the graph and the
 // work arrays on the device, and the counts that end up in `info`.
 struct FieldRun {
-  const FieldRequest &rq;
+  FieldRequest rq;          // the entry's; of a refresh, completed by field_check_refresh
   TrgFieldInfo *info;
   Clock::time_point t_total;
   FieldDev F{};             // the kernels' view; V, m and N from the checks on
@@ -127,9 +133,98 @@ struct FieldRun {
     bool dev_csr;
   } G{};
   int syncs = 0, rounds = 0;
+  // a refresh: the retained solve's view, whose keys field_carry reads, and what field_check_refresh built for rq
+  // to point at -- the identity map, the sources or the sets as ids of the current graph
+  FieldDev old{};
+  std::vector<int32_t> identity, src, set_ptr, set_ids;
 };
 
 constexpr uint32_t FIELD_INF_BITS = 0x7f800000u;
+
+// is the retained solve one of the engine's graph as it is now, its CSR still there
+bool field_last_current(const TrgEngine *e, const FieldBufs::Last &last) {
+  return last.version == e->graph_version && !(last.dev_csr && !e->dev_csr_valid);
+}
+
+// the retained solve for `call` ("cost field routes", ...), or that call's refusal; `current`: a stale one is refused
+TrgStatus field_retained(TrgEngine *e, const std::string &call, FieldBufs::Last *&last, bool current = true) {
+  if (!e->field || e->field->last.version == 0)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": no cost-field solve is retained (solve first)");
+  last = &e->field->last;
+  if (current && !field_last_current(e, *last))
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is of an earlier graph (solve again)");
+  return TRG_OK;
+}
+
+// The check phase of a refresh ("Refresh"), before field_check_request's: the retained solve
+// must be there, unbounded and stale; the node map is the given one, the engine's, or the identity; and m and the
+// sources or sets of the request become the retained solve's, as ids of the current graph.  Like every refusal
+// before field_begin, these leave the retained solve as it was.
+TrgStatus field_check_refresh(TrgEngine *e, FieldRun &run) {
+  FieldRequest &rq = run.rq;
+  const std::string call = "cost field refresh";
+  FieldBufs::Last *last;
+  if (const TrgStatus st = field_retained(e, call, last, false); st != TRG_OK) return st;
+  const FieldBufs::Last &old = *last;
+  if (old.bounded)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is bounded (a bounded solve cannot be refreshed)");
+  if (field_last_current(e, old))
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is already of the current graph");
+  const int V = (int)e->nx.size(), V_old = old.F.V, m = old.F.m;
+  if (!rq.new2old) {
+    if (e->field_map_state == TrgEngine::FIELD_MAP_NONE)
+      return e->fail(TRG_ERR_INVALID_ARG, call + ": no node map is given and the engine has none for this graph "
+                                                 "(pass new2old, or solve again)");
+    if (e->field_map_state == TrgEngine::FIELD_MAP_IDENTITY) {
+      run.identity.resize((size_t)V_old);
+      for (int v = 0; v < V_old; ++v) run.identity[v] = v;
+      rq.new2old = run.identity.data();
+      rq.n_map = V_old;
+    } else {  // (the engine's own stays in place through the phases: field_begin only marks it ended)
+      rq.new2old = e->field_map.data();
+      rq.n_map = (int32_t)e->field_map.size();
+    }
+  }
+  if (rq.n_map != V)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": the node map has " + std::to_string(rq.n_map) +
+                                            " entries, the graph " + std::to_string(V) + " nodes");
+  std::vector<int32_t> first((size_t)V_old, -1);  // the first node of the current graph that names an old one
+  for (int v = 0; v < V; ++v) {
+    const int o = rq.new2old[v];
+    if (o < -1 || o >= V_old)
+      return e->fail(TRG_ERR_INVALID_ARG, call + ": node map entry " + std::to_string(v) + " (" + std::to_string(o) +
+                                              ") is no node of the retained solve's graph (" + std::to_string(V_old) +
+                                              " nodes) and not -1");
+    if (o >= 0 && first[o] < 0) first[o] = v;
+  }
+  if ((rq.owner || rq.owner_at) && !old.sets)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": owner / owner_at asked of a solve without sets");
+  if (rq.n_targets < 0) return e->fail(TRG_ERR_INVALID_ARG, call + ": n_targets < 0");
+  const FieldBufs &fb = *e->field;
+  if (old.sets) {
+    run.set_ptr = fb.h_set_ptr;  // (a copy: field_uploads writes the host record again)
+    run.set_ids.resize(fb.h_set_ids.size());
+    for (int k = 0; k < m; ++k)
+      for (int j = fb.h_set_ptr[k]; j < fb.h_set_ptr[k + 1]; ++j)
+        if ((run.set_ids[j] = first[fb.h_set_ids[j]]) < 0)
+          return e->fail(TRG_ERR_INVALID_ARG, call + ": member " + std::to_string(j - fb.h_set_ptr[k]) + " of set " +
+                                                  std::to_string(k) + " (node " + std::to_string(fb.h_set_ids[j]) +
+                                                  " of the retained solve's graph) has no node in the current graph");
+    rq.set_ptr = run.set_ptr.data();
+    rq.set_ids = run.set_ids.data();
+  } else {
+    run.src.resize((size_t)m);
+    for (int k = 0; k < m; ++k)
+      if ((run.src[k] = first[old.sources.id[k]]) < 0)
+        return e->fail(TRG_ERR_INVALID_ARG, call + ": the source of field " + std::to_string(k) + " (node " +
+                                                std::to_string(old.sources.id[k]) +
+                                                " of the retained solve's graph) has no node in the current graph");
+    rq.source_ids = run.src.data();
+  }
+  rq.m = m;
+  run.old = old.F;
+  return TRG_OK;
+}
 
 // The sets of a set solve (trg_engine_cost_field_sets): set_ptr from 0 and strictly ascending, every id a node.
 // Field k's source, for `info` and the reached list, is its set's first id.
@@ -230,8 +325,8 @@ TrgStatus field_graph(TrgEngine *e, FieldRun &run) {
   const int V = run.F.V, E = G.rowptr.empty() ? 0 : G.rowptr[V];
   if (e->dev_csr_valid && e->bfs && e->bfs->rowptr_new.p) {
     const BfsBuffers &bb = *e->bfs;
-    run.G = {(const int *)bb.rowptr_new.p, (const int *)bb.col2.p, (const int *)bb.state2.p,
-             (const float *)bb.w2.p, (const float *)bb.dist2.p, E, true};
+    run.G = {bb.rowptr_new.as<int>(), bb.col2.as<int>(), bb.state2.as<int>(), bb.w2.as<float>(), bb.dist2.as<float>(),
+             E, true};
   } else {
     if (fb.up_version != e->graph_version) {
       fb.up_version = 0;
@@ -247,8 +342,8 @@ TrgStatus field_graph(TrgEngine *e, FieldRun &run) {
         if (u.bytes) HIPCHK(e, hipMemcpyAsync(u.a.p, u.src, u.bytes, hipMemcpyHostToDevice, s));
       fb.up_version = e->graph_version;
     }
-    run.G = {(const int *)fb.up_rowptr.p, (const int *)fb.up_col.p, (const int *)fb.up_state.p,
-             (const float *)fb.up_w.p, (const float *)fb.up_dist.p, E, false};
+    run.G = {fb.up_rowptr.as<int>(), fb.up_col.as<int>(), fb.up_state.as<int>(), fb.up_w.as<float>(),
+             fb.up_dist.as<float>(), E, false};
   }
   HIPCHK(e, hipEventRecord(fb.t0, s));
   return TRG_OK;
@@ -265,8 +360,8 @@ TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
     TrgStatus st;
     if ((st = ensure_bytes(e, fb.ec, (size_t)G.E * sizeof(float) + 16)) != TRG_OK) return st;
     if ((st = ensure_bytes(e, fb.stats, sizeof(FieldEdgeStats))) != TRG_OK) return st;
-    launch_field_edge_cost(G.col, G.w, G.dist, G.state, run.F.V, G.E, sf, (float *)fb.ec.p,
-                           (FieldEdgeStats *)fb.stats.p, s);
+    launch_field_edge_cost(G.col, G.w, G.dist, G.state, run.F.V, G.E, sf, fb.ec.as<float>(),
+                           fb.stats.as<FieldEdgeStats>(), s);
     HIPCHK(e, hipMemcpyAsync(fb.h_stats, fb.stats.p, sizeof(FieldEdgeStats), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     run.syncs++;
@@ -277,6 +372,24 @@ TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
     fb.ec_sf = sf;
   }
   if (fb.bad_cost) return e->fail(TRG_ERR_INVALID_ARG, "cost field: an edge cost is negative or not finite");
+  return TRG_OK;
+}
+
+// A refresh only: the old keys, still in the retained solve's array (run.old, as field_begin found it), gathered
+// through the node map into a buffer of their own -- before field_work_arrays regrows anything.
+TrgStatus field_carry(TrgEngine *e, FieldRun &run) {
+  if (!run.rq.refresh) return TRG_OK;
+  FieldBufs &fb = *e->field;
+  hipStream_t s = e->s_main;
+  const FieldDev &F = run.F;
+  TrgStatus st;
+  if ((st = field_grow(e, fb.key0, ((size_t)F.N + 4) * sizeof(unsigned long long))) != TRG_OK) return st;
+  if ((st = field_grow(e, fb.node_map, (size_t)F.V * sizeof(int))) != TRG_OK) return st;
+  if ((st = field_grow(e, fb.carried, TRG_FIELD_BATCH_MAX * sizeof(int))) != TRG_OK) return st;
+  HIPCHK(e, fb.h_carried.ensure(TRG_FIELD_BATCH_MAX));
+  HIPCHK(e, hipMemcpyAsync(fb.node_map.p, run.rq.new2old, (size_t)F.V * sizeof(int), hipMemcpyHostToDevice, s));
+  launch_field_carry(run.old.key, run.old.V, fb.node_map.as<int>(), F.V, F.m, fb.key0.as<unsigned long long>(), s);
+  HIPCHK(e, hipGetLastError());
   return TRG_OK;
 }
 
@@ -293,16 +406,16 @@ TrgStatus field_work_arrays(TrgEngine *e, FieldRun &run) {
   FieldDev &F = run.F;
   F.rowptr = run.G.rowptr;
   F.col = run.G.col;
-  F.ec = (const float *)fb.ec.p;
-  F.key = (unsigned long long *)fb.key.p;
+  F.ec = fb.ec.as<float>();
+  F.key = fb.key.as<unsigned long long>();
   for (int i = 0; i < 2; ++i) {
-    F.q[i] = (int *)fb.q[i].p;
-    F.far[i] = (int *)fb.far[i].p;
+    F.q[i] = fb.q[i].as<int>();
+    F.far[i] = fb.far[i].as<int>();
   }
-  F.stamp_near = (int *)fb.stamp_near.p;
-  F.stamp_far = (unsigned *)fb.stamp_far.p;
-  F.parent = (int *)fb.parent.p;
-  F.ctrl = (FieldCtrl *)fb.ctrl.p;
+  F.stamp_near = fb.stamp_near.as<int>();
+  F.stamp_far = fb.stamp_far.as<unsigned>();
+  F.parent = fb.parent.as<int>();
+  F.ctrl = fb.ctrl.as<FieldCtrl>();
   return TRG_OK;
 }
 
@@ -324,8 +437,8 @@ TrgStatus field_uploads(TrgEngine *e, FieldRun &run) {
     if ((st = field_grow(e, fb.set_ids, (size_t)S.n * sizeof(int))) != TRG_OK) return st;
     HIPCHK(e, hipMemcpyAsync(fb.set_ptr.p, rq.set_ptr, ((size_t)F.m + 1) * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(fb.set_ids.p, rq.set_ids, (size_t)S.n * sizeof(int), hipMemcpyHostToDevice, s));
-    S.ptr = (const int *)fb.set_ptr.p;
-    S.ids = (const int *)fb.set_ids.p;
+    S.ptr = fb.set_ptr.as<int>();
+    S.ids = fb.set_ids.as<int>();
     fb.h_set_ptr.assign(rq.set_ptr, rq.set_ptr + F.m + 1);
     fb.h_set_ids.assign(rq.set_ids, rq.set_ids + S.n);
   }
@@ -358,42 +471,23 @@ TrgStatus field_rounds(TrgEngine *e, FieldRun &run, const FieldSettle *under) {
   return TRG_OK;
 }
 
-// Near-far rounds; pass 1 finds the least costs, pass 2 the hops over the tight edges (trg_field.hip).
-TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
-  FieldBufs &fb = *e->field;
-  const FieldRequest &rq = run.rq;
-  FieldDev &F = run.F;
-  hipStream_t s = e->s_main;
-  const float delta = field_delta(e);
-  const FieldSettle under{(const int *)fb.targets.p, rq.n_targets, rq.settle};
-  if (run.bounded) launch_field_bounds(F, run.budgets, s);
-  for (int pass = 0; pass < 2; ++pass) {
-    // the bounds act in pass 1 only: it ends with the keys above them removed, and no pass-2 extension matches
-    // the tight word of a node without a key
-    const bool under_bounds = run.bounded && pass == 0;
-    F.tight = pass ? (const unsigned *)fb.cost.p : nullptr;
-    launch_field_init(F, run.sources, rq.set_ptr ? &run.sets : nullptr, delta, s);
-    if (const TrgStatus st = field_rounds(e, run, under_bounds ? &under : nullptr); st != TRG_OK) return st;
-    if (under_bounds) {
-      launch_field_trim(F, s);
-      HIPCHK(e, hipMemcpyAsync(fb.h_bound, F.ctrl->bound, (size_t)F.m * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    }
-    if (pass == 0) launch_field_cost_bits(F, (unsigned *)fb.cost.p, s);
-  }
-  return TRG_OK;
-}
-
-// sweeps enqueued between two looks at the owner pass's pinned "moved" word
+// sweeps enqueued between two looks at a forest pass's pinned "moved" word
 constexpr int FIELD_OWNER_BATCH = 8;
-static_assert(FIELD_OWNER_SWEEPS_MAX % FIELD_OWNER_BATCH == 0, "the owner pass looks after whole batches");
+static_assert(FIELD_OWNER_SWEEPS_MAX % FIELD_OWNER_BATCH == 0, "a forest pass looks after whole batches");
 
-// The jumping sweeps between a begin and an end launch (the owner pass, a refresh's anchors), in the idle near
-// queues until a sweep moves nothing -- about log2 of the longest chain of them.  One host wait per
-// FIELD_OWNER_BATCH sweeps.
-TrgStatus field_jump(TrgEngine *e, const FieldDev &F, const char *what, int &syncs, int &sweeps) {
+// One jump over the forest in F.parent (the owner pass, a refresh's anchors; trg_field.hip): the begin launch for
+// `single` sources or marked members and `key0`, the jumping sweeps in the idle near queues until a sweep moves
+// nothing -- about log2 of the longest chain of them, one host wait per FIELD_OWNER_BATCH sweeps -- then `end`'s
+// launch, given the sweep count.
+template <typename End>
+TrgStatus field_forest_pass(TrgEngine *e, const FieldDev &F, const FieldSources *single,
+                            const unsigned long long *key0, const char *what, int &syncs, int &sweeps, End end) {
   FieldBufs &fb = *e->field;
   hipStream_t s = e->s_main;
-  int *changed = (int *)fb.own_changed.p;
+  if (const TrgStatus st = field_grow(e, fb.own_changed, FIELD_OWNER_SWEEPS_MAX * sizeof(int)); st != TRG_OK) return st;
+  HIPCHK(e, fb.h_changed.ensure(1));
+  int *changed = fb.own_changed.as<int>();
+  launch_field_forest_begin(F, single, key0, changed, s);
   for (sweeps = 0;;) {
     for (int i = 0; i < FIELD_OWNER_BATCH; ++i, ++sweeps) launch_field_owner_sweep(F, sweeps, changed, s);
     HIPCHK(e, hipGetLastError());
@@ -403,30 +497,84 @@ TrgStatus field_jump(TrgEngine *e, const FieldDev &F, const char *what, int &syn
     if (fb.h_changed[0] == 0) break;
     if (sweeps >= FIELD_OWNER_SWEEPS_MAX) return e->fail(TRG_ERR_DEVICE, std::string(what) + " did not end");
   }
+  end(sweeps);
+  HIPCHK(e, hipGetLastError());
   return TRG_OK;
 }
 
-// the words of the jumping sweeps' "moved" flags
-TrgStatus field_jump_arrays(TrgEngine *e) {
-  FieldBufs &fb = *e->field;
-  if (const TrgStatus st = field_grow(e, fb.own_changed, FIELD_OWNER_SWEEPS_MAX * sizeof(int)); st != TRG_OK) return st;
-  HIPCHK(e, fb.h_changed.ensure(1));
-  return TRG_OK;
-}
-
-// The owner pass of a set solve whose parent sweep ran (trg_field.hip; DESIGN.md section 2, "Source sets"): pointer
-// jumping over the parents, then S.owner, whose m x V words are allocated here.
+// The owner pass of a set solve whose parent sweep ran ("Source sets"): the forest of the
+// parents, then S.owner, whose m x V words are allocated here.
 TrgStatus field_owner_pass(TrgEngine *e, const FieldDev &F, FieldSets &S, int &syncs, int &sweeps) {
   FieldBufs &fb = *e->field;
+  if (const TrgStatus st = field_grow(e, fb.owner, ((size_t)F.N + 4) * sizeof(int)); st != TRG_OK) return st;
+  S.owner = fb.owner.as<int>();
+  return field_forest_pass(e, F, nullptr, nullptr, "cost field sets: the owner pass", syncs, sweeps,
+                           [&](int n) { launch_field_owner_end(F, S, n, e->s_main); });
+}
+
+// One anchor of a refresh ("Refresh"): the forest of the supporters; the first leaves the
+// anchored keys in key0 and counts them, the second cuts every key that is no longer key0's.
+TrgStatus field_anchor(TrgEngine *e, FieldRun &run, bool first) {
+  FieldBufs &fb = *e->field;
+  const FieldDev &F = run.F;
+  unsigned long long *key0 = fb.key0.as<unsigned long long>();
+  int sweeps = 0;
+  return field_forest_pass(e, F, run.rq.set_ptr ? nullptr : &run.sources, first ? nullptr : key0,
+                           "cost field refresh: an anchor", run.syncs, sweeps, [&](int n) {
+                             launch_field_anchor_end(F, n, first ? key0 : nullptr,
+                                                     first ? fb.carried.as<int>() : nullptr, e->s_main);
+                           });
+}
+
+// Near-far rounds; pass 1 finds the least costs, pass 2 the hops over the tight edges (trg_field.hip).  A solve
+// starts each pass cold, from the sources.  A refresh starts pass 1 from the carried keys, anchored to the new graph,
+// and pass 2 from the keys that pass 1 left alone, anchored again: warm starts both.  The rounds are the same.
+TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
+  FieldBufs &fb = *e->field;
+  const FieldRequest &rq = run.rq;
+  FieldDev &F = run.F;
   hipStream_t s = e->s_main;
+  const float delta = field_delta(e);
+  const FieldSettle under{fb.targets.as<int>(), rq.n_targets, rq.settle};
+  const FieldSets *sets = rq.set_ptr ? &run.sets : nullptr;
   TrgStatus st;
-  if ((st = field_grow(e, fb.owner, ((size_t)F.N + 4) * sizeof(int))) != TRG_OK) return st;
-  if ((st = field_jump_arrays(e)) != TRG_OK) return st;
-  S.owner = (int *)fb.owner.p;
-  launch_field_owner_begin(F, (int *)fb.own_changed.p, s);
-  if ((st = field_jump(e, F, "cost field sets: the owner pass", syncs, sweeps)) != TRG_OK) return st;
-  launch_field_owner_end(F, S, sweeps, s);
-  HIPCHK(e, hipGetLastError());
+  if (run.bounded) launch_field_bounds(F, run.budgets, s);
+  for (int pass = 0; pass < 2; ++pass) {
+    // the bounds act in pass 1 only: it ends with the keys above them removed, and no pass-2 extension matches
+    // the tight word of a node without a key
+    const bool under_bounds = run.bounded && pass == 0;
+    F.tight = pass ? fb.cost.as<unsigned>() : nullptr;
+    if (!rq.refresh) {
+      launch_field_init(F, run.sources, sets, nullptr, delta, s);
+    } else {
+      if (pass == 0) {
+        launch_field_init(F, run.sources, sets, fb.key0.as<unsigned long long>(), delta, s);
+        launch_field_supporters(F, s);
+      }
+      if ((st = field_anchor(e, run, pass == 0)) != TRG_OK) return st;
+      if (pass == 0)
+        HIPCHK(e, hipMemcpyAsync(fb.h_carried, fb.carried.p, (size_t)F.m * sizeof(int), hipMemcpyDeviceToHost, s));
+      launch_field_warm_start(F, delta, pass == 1, s);
+    }
+    if ((st = field_rounds(e, run, under_bounds ? &under : nullptr)) != TRG_OK) return st;
+    if (under_bounds) {
+      launch_field_trim(F, s);
+      HIPCHK(e, hipMemcpyAsync(fb.h_bound, F.ctrl->bound, (size_t)F.m * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    }
+    if (pass == 0) launch_field_cost_bits(F, fb.cost.as<unsigned>(), s);
+  }
+  return TRG_OK;
+}
+
+// The end of every call that timed device work between the engine's two events (created by field_begin, so there
+// for every retained solve): the event time, the host waits and the wall time into `info`.
+TrgStatus field_timing(TrgEngine *e, TrgFieldInfo *info, int syncs, Clock::time_point t_total) {
+  FieldBufs &fb = *e->field;
+  float ms_dev = 0.0f;
+  HIPCHK(e, hipEventElapsedTime(&ms_dev, fb.t0, fb.t1));
+  info->host_syncs = syncs;
+  info->ms_device = ms_dev;
+  info->ms_total = ms_since(t_total);
   return TRG_OK;
 }
 
@@ -439,7 +587,7 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   const int m = F.m;
   const size_t nN = (size_t)F.N, nat = (size_t)m * rq.n_targets;
   const bool parents = rq.parent != nullptr || run.owners;  // (owners follow parents)
-  launch_field_finish(F, (float *)fb.cost.p, (int *)fb.hops.p, parents, s);
+  launch_field_finish(F, fb.cost.as<float>(), fb.hops.as<int>(), parents, s);
   TrgStatus st;
   int sweeps = 0;
   if (run.owners && (st = field_owner_pass(e, F, run.sets, run.syncs, sweeps)) != TRG_OK) return st;
@@ -447,14 +595,14 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
     if ((st = field_grow(e, fb.cost_at, nat * sizeof(float))) != TRG_OK) return st;
     if ((st = field_grow(e, fb.hops_at, nat * sizeof(int))) != TRG_OK) return st;
     if (rq.owner_at && (st = field_grow(e, fb.owner_at, nat * sizeof(int))) != TRG_OK) return st;
-    float *d_cost_at = rq.cost_at ? (float *)fb.cost_at.p : nullptr;
-    int *d_hops_at = rq.hops_at ? (int *)fb.hops_at.p : nullptr;
-    launch_field_gather(F, rq.set_ptr ? &run.sets : nullptr, (const int *)fb.targets.p, rq.n_targets, d_cost_at,
-                        d_hops_at, rq.owner_at ? (int *)fb.owner_at.p : nullptr, s);
+    float *d_cost_at = rq.cost_at ? fb.cost_at.as<float>() : nullptr;
+    int *d_hops_at = rq.hops_at ? fb.hops_at.as<int>() : nullptr;
+    launch_field_gather(F, rq.set_ptr ? &run.sets : nullptr, fb.targets.as<int>(), rq.n_targets, d_cost_at,
+                        d_hops_at, rq.owner_at ? fb.owner_at.as<int>() : nullptr, s);
   }
   if (rq.owned) {
     if ((st = field_grow(e, fb.owned, (size_t)run.sets.n * sizeof(int))) != TRG_OK) return st;
-    launch_field_owned(F, run.sets, (int *)fb.owned.p, s);
+    launch_field_owned(F, run.sets, fb.owned.as<int>(), s);
   }
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
@@ -473,8 +621,6 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
     HIPCHK(e, hipMemcpyAsync(rq.owned, fb.owned.p, (size_t)run.sets.n * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   run.syncs++;
-  float ms_dev = 0.0f;
-  HIPCHK(e, hipEventElapsedTime(&ms_dev, fb.t0, fb.t1));
   long long reached = 0;
   for (int k = 0; k < m; ++k) {
     reached += fb.h_reached[k];
@@ -486,181 +632,22 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   run.info->source = run.sources.id[0];
   run.info->reached = (int32_t)reached;
   run.info->rounds = run.rounds;
-  run.info->host_syncs = run.syncs;
-  run.info->ms_device = ms_dev;
-  run.info->ms_total = ms_since(run.t_total);
   fb.last = FieldBufs::Last{e->graph_version, F, run.G.w, run.G.dist, run.sources, parents, run.G.dev_csr,
                             rq.set_ptr ? std::optional<FieldSets>(run.sets) : std::nullopt, run.owners};
   fb.last.F.tight = nullptr;  // (its array holds the cost output now)
   fb.last.bounded = run.bounded;
   e->field_map_state = TrgEngine::FIELD_MAP_IDENTITY;  // update_graph takes the node map on from here
-  return TRG_OK;
-}
-
-// A refresh's stand-in for field_work_arrays' neighbour on the other side: the old keys, still in the retained
-// solve's array, gathered through the node map into a buffer of their own -- before field_work_arrays regrows
-// anything.  `old` is the retained solve as field_begin found it.
-TrgStatus field_carry(TrgEngine *e, FieldRun &run, const FieldDev &old) {
-  FieldBufs &fb = *e->field;
-  hipStream_t s = e->s_main;
-  const FieldDev &F = run.F;
-  TrgStatus st;
-  if ((st = field_grow(e, fb.key0, ((size_t)F.N + 4) * sizeof(unsigned long long))) != TRG_OK) return st;
-  if ((st = field_grow(e, fb.node_map, (size_t)F.V * sizeof(int))) != TRG_OK) return st;
-  if ((st = field_grow(e, fb.carried, TRG_FIELD_BATCH_MAX * sizeof(int))) != TRG_OK) return st;
-  if ((st = field_jump_arrays(e)) != TRG_OK) return st;
-  HIPCHK(e, fb.h_carried.ensure(TRG_FIELD_BATCH_MAX));
-  HIPCHK(e, hipMemcpyAsync(fb.node_map.p, run.rq.new2old, (size_t)F.V * sizeof(int), hipMemcpyHostToDevice, s));
-  launch_field_carry(old.key, old.V, (const int *)fb.node_map.p, F.V, F.m, (unsigned long long *)fb.key0.p, s);
-  HIPCHK(e, hipGetLastError());
-  return TRG_OK;
-}
-
-// one anchor of a refresh (trg_field.hip): begin, the jumping sweeps, end
-TrgStatus field_anchor(TrgEngine *e, FieldRun &run, bool first) {
-  FieldBufs &fb = *e->field;
-  hipStream_t s = e->s_main;
-  const FieldDev &F = run.F;
-  unsigned long long *key0 = (unsigned long long *)fb.key0.p;
-  launch_field_anchor_begin(F, run.sources, !run.rq.set_ptr, first ? nullptr : key0, (int *)fb.own_changed.p, s);
-  int sweeps = 0;
-  if (const TrgStatus st = field_jump(e, F, "cost field refresh: an anchor", run.syncs, sweeps); st != TRG_OK) return st;
-  launch_field_anchor_end(F, sweeps, first ? key0 : nullptr, first ? (int *)fb.carried.p : nullptr, s);
-  HIPCHK(e, hipGetLastError());
-  return TRG_OK;
-}
-
-// The passes of a refresh ("Refresh"), in field_passes' place: the carried keys anchored to the
-// new graph, pass 1 warm from them, the anchor again over the keys pass 1 left alone, pass 2 warm from those.  The
-// rounds are field_passes'.
-TrgStatus field_refresh_passes(TrgEngine *e, FieldRun &run) {
-  FieldBufs &fb = *e->field;
-  FieldDev &F = run.F;
-  hipStream_t s = e->s_main;
-  const float delta = field_delta(e);
-  TrgStatus st;
-  F.tight = nullptr;
-  launch_field_carry_init(F, (const unsigned long long *)fb.key0.p, run.sources, run.rq.set_ptr ? &run.sets : nullptr, s);
-  launch_field_supporters(F, s);
-  if ((st = field_anchor(e, run, true)) != TRG_OK) return st;
-  HIPCHK(e, hipMemcpyAsync(fb.h_carried, fb.carried.p, (size_t)F.m * sizeof(int), hipMemcpyDeviceToHost, s));
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 1) {
-      if ((st = field_anchor(e, run, false)) != TRG_OK) return st;
-      F.tight = (const unsigned *)fb.cost.p;
-    }
-    launch_field_warm_start(F, delta, pass == 1, s);
-    if ((st = field_rounds(e, run, nullptr)) != TRG_OK) return st;
-    if (pass == 0) launch_field_cost_bits(F, (unsigned *)fb.cost.p, s);
-  }
-  return TRG_OK;
+  return field_timing(e, run.info, run.syncs, run.t_total);
 }
 
 TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) {
   FieldRun run{rq, info, Clock::now()};
   TrgStatus st = plan_prepare(e);  // graph present, CSR rows and node grid current
   if (st != TRG_OK) return st;
+  if (rq.refresh && (st = field_check_refresh(e, run)) != TRG_OK) return st;
   if ((st = field_check_request(e, run)) != TRG_OK || rq.resolve_only) return st;
-  for (const auto phase : {field_begin, field_graph, field_edge_costs, field_work_arrays, field_uploads,
+  for (const auto phase : {field_begin, field_graph, field_edge_costs, field_carry, field_work_arrays, field_uploads,
                            field_passes, field_outputs})
-    if ((st = phase(e, run)) != TRG_OK) return st;
-  return TRG_OK;
-}
-
-struct RefreshRequest {
-  const int32_t *new2old;  // n_map entries, or nullptr: the engine's map
-  int32_t n_map;
-  float *cost;
-  int32_t *hops, *parent;
-  const int32_t *targets;
-  int32_t n_targets;
-  float *cost_at;
-  int32_t *hops_at, *owner, *owner_at, *sources_out, *reached_out, *carried_out;
-};
-
-// The retained solve of an earlier graph brought to the current one ("Refresh").  Every
-// refusal of its own comes before field_begin: the retained solve is then as it was.  After them it is a solve
-// like any other -- the same phases, with the carry before the work arrays and its own passes.
-TrgStatus field_refresh(TrgEngine *e, const RefreshRequest &rr, TrgFieldInfo *info) {
-  const auto t_total = Clock::now();
-  const std::string call = "cost field refresh";
-  TrgStatus st = plan_prepare(e);
-  if (st != TRG_OK) return st;
-  if (!e->field || e->field->last.version == 0)
-    return e->fail(TRG_ERR_INVALID_ARG, call + ": no cost-field solve is retained (solve first)");
-  const FieldBufs::Last old = e->field->last;
-  if (old.bounded)
-    return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is bounded (a bounded solve cannot be refreshed)");
-  if (old.version == e->graph_version && !(old.dev_csr && !e->dev_csr_valid))
-    return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is already of the current graph");
-  const int V = (int)e->nx.size(), V_old = old.F.V, m = old.F.m;
-  std::vector<int32_t> identity;
-  const int32_t *map = rr.new2old;
-  int32_t n_map = rr.n_map;
-  if (!map) {
-    if (e->field_map_state == TrgEngine::FIELD_MAP_NONE)
-      return e->fail(TRG_ERR_INVALID_ARG, call + ": no node map is given and the engine has none for this graph "
-                                                 "(pass new2old, or solve again)");
-    if (e->field_map_state == TrgEngine::FIELD_MAP_IDENTITY) {
-      identity.resize((size_t)V_old);
-      for (int v = 0; v < V_old; ++v) identity[v] = v;
-      map = identity.data();
-      n_map = V_old;
-    } else {
-      map = e->field_map.data();
-      n_map = (int32_t)e->field_map.size();
-    }
-  }
-  if (n_map != V)
-    return e->fail(TRG_ERR_INVALID_ARG, call + ": the node map has " + std::to_string(n_map) + " entries, the graph " +
-                                            std::to_string(V) + " nodes");
-  std::vector<int32_t> first((size_t)V_old, -1);  // the first node of the current graph that names an old one
-  for (int v = 0; v < V; ++v) {
-    const int o = map[v];
-    if (o < -1 || o >= V_old)
-      return e->fail(TRG_ERR_INVALID_ARG, call + ": node map entry " + std::to_string(v) + " (" + std::to_string(o) +
-                                              ") is no node of the retained solve's graph (" + std::to_string(V_old) +
-                                              " nodes) and not -1");
-    if (o >= 0 && first[o] < 0) first[o] = v;
-  }
-  if ((rr.owner || rr.owner_at) && !old.sets)
-    return e->fail(TRG_ERR_INVALID_ARG, call + ": owner / owner_at asked of a solve without sets");
-  if (rr.n_targets < 0) return e->fail(TRG_ERR_INVALID_ARG, call + ": n_targets < 0");
-  // the sources, as ids of the current graph
-  std::vector<int32_t> src((size_t)m), set_ids;
-  const FieldBufs &fb0 = *e->field;
-  if (old.sets) {
-    set_ids.resize(fb0.h_set_ids.size());
-    for (int k = 0; k < m; ++k)
-      for (int j = fb0.h_set_ptr[k]; j < fb0.h_set_ptr[k + 1]; ++j)
-        if ((set_ids[j] = first[fb0.h_set_ids[j]]) < 0)
-          return e->fail(TRG_ERR_INVALID_ARG, call + ": member " + std::to_string(j - fb0.h_set_ptr[k]) + " of set " +
-                                                  std::to_string(k) + " (node " + std::to_string(fb0.h_set_ids[j]) +
-                                                  " of the retained solve's graph) has no node in the current graph");
-  } else {
-    for (int k = 0; k < m; ++k)
-      if ((src[k] = first[old.sources.id[k]]) < 0)
-        return e->fail(TRG_ERR_INVALID_ARG, call + ": the source of field " + std::to_string(k) + " (node " +
-                                                std::to_string(old.sources.id[k]) +
-                                                " of the retained solve's graph) has no node in the current graph");
-  }
-  const std::vector<int32_t> set_ptr = old.sets ? fb0.h_set_ptr : std::vector<int32_t>();
-  FieldRequest rq{m, old.sets ? nullptr : src.data(), nullptr, rr.cost, rr.hops, rr.parent, rr.targets, rr.n_targets,
-                  rr.cost_at, rr.hops_at, rr.sources_out, rr.reached_out, false, nullptr, TRG_FIELD_SETTLE_NONE, nullptr};
-  if (old.sets) {
-    rq.set_ptr = set_ptr.data();
-    rq.set_ids = set_ids.data();
-    rq.owner = rr.owner;
-    rq.owner_at = rr.owner_at;
-  }
-  rq.new2old = map;  // (the engine's own stays in place through the phases: field_begin only marks it ended)
-  rq.carried_out = rr.carried_out;
-  FieldRun run{rq, info, t_total};
-  if ((st = field_check_request(e, run)) != TRG_OK) return st;  // the targets, the 32-bit item index
-  for (const auto phase : {field_begin, field_graph, field_edge_costs})
-    if ((st = phase(e, run)) != TRG_OK) return st;
-  if ((st = field_carry(e, run, old.F)) != TRG_OK) return st;
-  for (const auto phase : {field_work_arrays, field_uploads, field_refresh_passes, field_outputs})
     if ((st = phase(e, run)) != TRG_OK) return st;
   return TRG_OK;
 }
@@ -683,16 +670,6 @@ TrgStatus field_entry(TrgEngine *e, TrgFieldInfo *info, const char *call, Body b
   } catch (...) {
     return e->fail(TRG_ERR_DEVICE, std::string(call) + ": unknown exception");
   }
-}
-
-// the retained solve for `call` ("cost field routes", ...), or that call's refusal
-TrgStatus field_retained(TrgEngine *e, const char *call, FieldBufs::Last *&last) {
-  if (!e->field || e->field->last.version == 0)
-    return e->fail(TRG_ERR_INVALID_ARG, std::string(call) + ": no cost-field solve is retained (solve first)");
-  last = &e->field->last;
-  if (last->version != e->graph_version || (last->dev_csr && !e->dev_csr_valid))
-    return e->fail(TRG_ERR_INVALID_ARG, std::string(call) + ": the retained solve is of an earlier graph (solve again)");
-  return TRG_OK;
 }
 
 static_assert(sizeof(TrgRouteInfo) == sizeof(FieldRouteInfo) && offsetof(TrgRouteInfo, num_nodes) == 0 &&
@@ -743,8 +720,6 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   if ((st = field_grow(e, fb.route_field, n * sizeof(int))) != TRG_OK) return st;
   if ((st = field_grow(e, fb.route_target, n * sizeof(int))) != TRG_OK) return st;
   if ((st = field_grow(e, fb.route_info, n * sizeof(FieldRouteInfo))) != TRG_OK) return st;
-  HIPCHK(e, fb.t0.create());
-  HIPCHK(e, fb.t1.create());
   hipStream_t s = e->s_main;
   int syncs = 0;
   HIPCHK(e, hipMemcpyAsync(fb.route_field.p, rq.field, n * sizeof(int), hipMemcpyHostToDevice, s));
@@ -761,14 +736,14 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
     last->owners = true;
     info->rounds = sweeps;
   }
-  const int *d_field = (const int *)fb.route_field.p, *d_target = (const int *)fb.route_target.p;
+  const int *d_field = fb.route_field.as<int>(), *d_target = fb.route_target.as<int>();
   std::vector<int32_t> ids;
   int total = 0;
   std::fill(rq.offsets, rq.offsets + n + 1, 0);
   if (want_ids) {
     if ((st = field_grow(e, fb.route_len, n * sizeof(int))) != TRG_OK) return st;
     if ((st = field_grow(e, fb.route_off, (n + 1) * sizeof(int))) != TRG_OK) return st;
-    launch_field_route_len(F, d_field, d_target, rq.n, (int *)fb.route_len.p, s);
+    launch_field_route_len(F, d_field, d_target, rq.n, fb.route_len.as<int>(), s);
     HIPCHK(e, hipGetLastError());
     std::vector<int32_t> len(n);
     HIPCHK(e, hipMemcpyAsync(len.data(), fb.route_len.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -782,10 +757,10 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
     HIPCHK(e, hipMemcpyAsync(fb.route_off.p, rq.offsets, (n + 1) * sizeof(int), hipMemcpyHostToDevice, s));
   }
   std::vector<FieldRouteInfo> infos(n);
-  const int *d_off = want_ids ? (const int *)fb.route_off.p : nullptr;
-  int *d_ids = want_ids ? (int *)fb.route_ids.p : nullptr;
+  const int *d_off = want_ids ? fb.route_off.as<int>() : nullptr;
+  int *d_ids = want_ids ? fb.route_ids.as<int>() : nullptr;
   launch_field_route_walk(F, last->w, last->dist, d_field, d_target, rq.n, d_off, d_ids,
-                          (FieldRouteInfo *)fb.route_info.p, last->sources, last->sets ? &*last->sets : nullptr, s);
+                          fb.route_info.as<FieldRouteInfo>(), last->sources, last->sets ? &*last->sets : nullptr, s);
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
   int32_t *ids_out = rq.node_ids;
@@ -814,12 +789,7 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
       rq.xyz[3 * i + 1] = e->ny[id];
       rq.xyz[3 * i + 2] = e->nz[id];
     }
-  float ms_dev = 0.0f;
-  HIPCHK(e, hipEventElapsedTime(&ms_dev, fb.t0, fb.t1));
-  info->host_syncs = syncs;
-  info->ms_device = ms_dev;
-  info->ms_total = ms_since(t_total);
-  return TRG_OK;
+  return field_timing(e, info, syncs, t_total);
 }
 
 // The reached list of one field of the retained solve: count, scan, emit on the device; the count comes back
@@ -845,18 +815,16 @@ TrgStatus field_reached(TrgEngine *e, int32_t field, int32_t *node_ids, float *c
   if (node_ids && (st = field_grow(e, fb.list_ids, ((size_t)room + 4) * sizeof(int))) != TRG_OK) return st;
   if (cost && (st = field_grow(e, fb.list_cost, ((size_t)room + 4) * sizeof(float))) != TRG_OK) return st;
   if (hops && (st = field_grow(e, fb.list_hops, ((size_t)room + 4) * sizeof(int))) != TRG_OK) return st;
-  HIPCHK(e, fb.t0.create());
-  HIPCHK(e, fb.t1.create());
   hipStream_t s = e->s_main;
   int syncs = 0;
   HIPCHK(e, hipEventRecord(fb.t0, s));
-  launch_field_reached_list(F, field, (int *)fb.list_counts.p, (int *)fb.list_off.p, (int *)fb.list_tmp.p, room,
-                            node_ids ? (int *)fb.list_ids.p : nullptr, cost ? (float *)fb.list_cost.p : nullptr,
-                            hops ? (int *)fb.list_hops.p : nullptr, s);
+  launch_field_reached_list(F, field, fb.list_counts.as<int>(), fb.list_off.as<int>(), fb.list_tmp.as<int>(), room,
+                            node_ids ? fb.list_ids.as<int>() : nullptr, cost ? fb.list_cost.as<float>() : nullptr,
+                            hops ? fb.list_hops.as<int>() : nullptr, s);
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
   int total = 0;
-  HIPCHK(e, hipMemcpyAsync(&total, (const int *)fb.list_off.p + nb, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipMemcpyAsync(&total, fb.list_off.as<int>() + nb, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   syncs++;
   const size_t n = (size_t)std::min(total, room);
@@ -868,14 +836,9 @@ TrgStatus field_reached(TrgEngine *e, int32_t field, int32_t *node_ids, float *c
     syncs++;
   }
   if (n_out) *n_out = total;
-  float ms_dev = 0.0f;
-  HIPCHK(e, hipEventElapsedTime(&ms_dev, fb.t0, fb.t1));
   info->source = last->sources.id[field];
   info->reached = total;
-  info->host_syncs = syncs;
-  info->ms_device = ms_dev;
-  info->ms_total = ms_since(t_total);
-  return TRG_OK;
+  return field_timing(e, info, syncs, t_total);
 }
 
 // The shape checks that the bounded and the set entry share: the entry's message prefix, its noun for a field, and
@@ -905,6 +868,22 @@ TrgStatus field_check_bounds(TrgEngine *e, int32_t m, const float *budget, int32
   return TRG_OK;
 }
 
+// the request members that every entry with targets sets, by name
+FieldRequest field_request(int32_t m, float *cost, int32_t *hops, int32_t *parent, const int32_t *targets,
+                           int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *reached_out) {
+  FieldRequest rq{};
+  rq.m = m;
+  rq.cost = cost;
+  rq.hops = hops;
+  rq.parent = parent;
+  rq.targets = targets;
+  rq.n_targets = n_targets;
+  rq.cost_at = cost_at;
+  rq.hops_at = hops_at;
+  rq.reached_out = reached_out;
+  return rq;
+}
+
 }  // namespace
 
 extern "C" {
@@ -913,7 +892,13 @@ TrgStatus trg_engine_cost_field(TrgEngine *e, int32_t source_id, const float sou
                                 int32_t *hops, int32_t *parent, TrgFieldInfo *info) {
   return field_entry(e, info, "cost field", [&](TrgFieldInfo *out) {
     if (source_id < -1) return e->fail(TRG_ERR_INVALID_ARG, "cost field: source out of range");
-    const FieldRequest rq{1, &source_id, source_xy, cost, hops, parent};  // no targets, budgets or settle mode
+    FieldRequest rq{};  // no targets, budgets or settle mode
+    rq.m = 1;
+    rq.source_ids = &source_id;
+    rq.source_xy = source_xy;
+    rq.cost = cost;
+    rq.hops = hops;
+    rq.parent = parent;
     return field_solve(e, rq, out);
   });
 }
@@ -942,8 +927,14 @@ TrgStatus trg_engine_cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *
         if (source_ids[k] < -1)
           return e->fail(TRG_ERR_INVALID_ARG, "cost field: source " + std::to_string(k) + " out of range");
     if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
-    const FieldRequest rq{m, source_ids, source_xy, cost, hops, parent, targets, n_targets, cost_at, hops_at,
-                          sources_out, reached_out, resolve_only, budget, settle, bound_out};
+    FieldRequest rq = field_request(m, cost, hops, parent, targets, n_targets, cost_at, hops_at, reached_out);
+    rq.source_ids = source_ids;
+    rq.source_xy = source_xy;
+    rq.sources_out = sources_out;
+    rq.resolve_only = resolve_only;
+    rq.budget = budget;
+    rq.settle = settle;
+    rq.bound_out = bound_out;
     return field_solve(e, rq, out);
   });
 }
@@ -958,8 +949,10 @@ TrgStatus trg_engine_cost_field_sets(TrgEngine *e, int32_t m, const int32_t *set
     if (const TrgStatus st = field_check_shape(e, "cost field sets", "sets", m, n_targets, no_sets); st != TRG_OK)
       return st;
     if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
-    FieldRequest rq{m, nullptr, nullptr, cost, hops, parent, targets, n_targets, cost_at, hops_at,
-                    nullptr, reached_out, false, budget, settle, bound_out};
+    FieldRequest rq = field_request(m, cost, hops, parent, targets, n_targets, cost_at, hops_at, reached_out);
+    rq.budget = budget;
+    rq.settle = settle;
+    rq.bound_out = bound_out;
     rq.set_ptr = set_ptr;
     rq.set_ids = set_ids;
     rq.owner = owner;
@@ -975,9 +968,16 @@ TrgStatus trg_engine_cost_field_refresh(TrgEngine *e, const int32_t *new2old, in
                                         int32_t *sources_out, int32_t *reached_out, int32_t *carried_out,
                                         TrgFieldInfo *info) {
   return field_entry(e, info, "cost field refresh", [&](TrgFieldInfo *out) {
-    const RefreshRequest rr{new2old, n_map, cost, hops, parent, targets, n_targets, cost_at, hops_at,
-                            owner, owner_at, sources_out, reached_out, carried_out};
-    return field_refresh(e, rr, out);
+    // (m and the sources or sets are the retained solve's: field_check_refresh)
+    FieldRequest rq = field_request(0, cost, hops, parent, targets, n_targets, cost_at, hops_at, reached_out);
+    rq.refresh = true;
+    rq.new2old = new2old;
+    rq.n_map = n_map;
+    rq.owner = owner;
+    rq.owner_at = owner_at;
+    rq.sources_out = sources_out;
+    rq.carried_out = carried_out;
+    return field_solve(e, rq, out);
   });
 }
 

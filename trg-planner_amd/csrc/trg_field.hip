@@ -41,15 +41,17 @@
 // pass finds that member by pointer jumping, in sweeps logarithmic in the greatest hop count.  A single source is a
 // set of one whose owner is known without that pass: both kinds share k_field_init (which seeds single sources
 // itself and leaves sets to k_field_seed), k_field_gather (the owners at the targets where there are any) and the
-// route walk (which differs in where a walk must end); k_field_seed and the owner kernels a solve from single
+// route walk (which differs in where a walk must end); k_field_seed and the owner pass a solve from single
 // sources never launches.
 //
 // Refresh ("Refresh"): the keys of a solve on an earlier graph, carried through a node map,
 // are starting points on the current one once the anchor has dropped every key that is not a walk's of the current
-// graph: the supporter forest of k_field_parent, pointer-jumped with the owner pass's sweep, keeps what hangs on a
-// source.  Both passes then start warm -- k_field_warm_seed queues every item one of whose edges improves its target,
-// the round kernels run as they are -- with a second anchor between them that cuts every key pass 1 changed, so that
-// the hops pass 2 starts from are those of tight walks.  The relaxation kernels know nothing of this.
+// graph: the supporter forest of k_field_parent, pointer-jumped as the owner pass jumps the parents (one begin kernel,
+// k_field_forest_begin, and one sweep for both), keeps what hangs on a source.  The carried keys enter through
+// k_field_init, in the place of "no key".  Both passes then start warm -- k_field_warm_seed queues every item one
+// of whose edges improves its target, the round kernels run as they are -- with a second anchor between them that
+// cuts every key pass 1 changed, so that the hops pass 2 starts from are those of tight walks.  The relaxation
+// kernels know nothing of this.
 //
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"
@@ -141,15 +143,38 @@ __global__ __launch_bounds__(THREADS) void k_field_edge_cost(const int *__restri
   }
 }
 
+// The control block before the first round of a pass (one thread): `queued` items in near queue 0, as much work,
+// nothing else queued or piled, the near bucket below `thr`, phase 1.
+__device__ __forceinline__ void field_ctrl_reset(const FieldDev &F, unsigned thr, float delta, int queued) {
+  FieldCounters &c = F.ctrl->c;
+  c.n[0] = queued;
+  c.n[1] = 0;
+  c.nfar[0] = c.nfar[1] = 0;
+  c.fmin = ~0u;
+  c.overflow = 0;
+  FieldState &s = F.ctrl->s;
+  s.work = queued;
+  s.rounds = 0;
+  s.overflow = 0;
+  s.thr = thr;
+  s.delta = delta;
+  s.phase = 1;
+  s.far_sel = 0;
+}
+
 // grid.y = field.  `single`: field f starts at node S.id[f], keyed (0, 0) and queued here; else (a set solve) no
-// item has a key and the near queue is empty, for k_field_seed
-__global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources S, float delta, bool single) {
+// item is a source and the near queue is empty, for k_field_seed.  Every other item gets no key, or, with `carried`
+// (a refresh; per item), its carried one.  The control block of a carried init is the cold one all the same: no
+// launch reads it before k_field_warm_init writes every word of it again (k_field_seed only adds to the queue size
+// and the work), and the first anchor overwrites q[0].
+__global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources S, float delta, bool single,
+                                                        const unsigned long long *__restrict__ carried) {
   const int V = F.V;
   const int f = blockIdx.y;
   const int src = single ? S.id[f] : -1;
   const int fbase = f * V;
   for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
-    F.key[fbase + v] = v == src ? 0ull : FIELD_KEY_NONE;
+    F.key[fbase + v] = v == src ? 0ull : carried ? carried[fbase + v] : FIELD_KEY_NONE;
     F.parent[fbase + v] = INT_MAX;
     F.stamp_near[fbase + v] = 0;
     F.stamp_far[fbase + v] = 0u;
@@ -158,22 +183,8 @@ __global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources
     if (single) F.q[0][f] = fbase + src;
     F.ctrl->reached[f] = 0;
   }
-  if (blockIdx.x == 0 && f == 0 && threadIdx.x == 0) {
-    FieldCounters &c = F.ctrl->c;
-    c.n[0] = single ? F.m : 0;
-    c.n[1] = 0;
-    c.nfar[0] = c.nfar[1] = 0;
-    c.fmin = ~0u;
-    c.overflow = 0;
-    FieldState &s = F.ctrl->s;
-    s.work = single ? F.m : 0;
-    s.rounds = 0;
-    s.overflow = 0;
-    s.thr = __float_as_uint(delta);
-    s.delta = delta;
-    s.phase = 1;
-    s.far_sel = 0;
-  }
+  if (blockIdx.x == 0 && f == 0 && threadIdx.x == 0)
+    field_ctrl_reset(F, __float_as_uint(delta), delta, single ? F.m : 0);
 }
 
 // Expand the near queue of this round: one 16-lane group per queued item, four per wave.
@@ -648,17 +659,26 @@ __global__ __launch_bounds__(THREADS) void k_field_seed(FieldDev F, FieldSets S)
   }
 }
 
-// grid.y = field: the first ancestor of every item -- itself for a member, its parent's item for another item with
-// a key, -1 without one
-__global__ __launch_bounds__(THREADS) void k_field_owner_begin(FieldDev F) {
+// is item i (node v of field f) a source: a member of its set by its mark (FieldSets), else its field's one source
+__device__ __forceinline__ bool field_is_source(const FieldDev &F, const FieldSources &S, bool single, int f, int v) {
+  return single ? v == S.id[f] : F.stamp_near[f * F.V + v] < 0;
+}
+
+// grid.y = field: the first ancestor of every item in the forest that k_field_parent left in F.parent -- itself for
+// a source, its parent's (supporter's) item for another item with a key, -1 without one or without a supporter.
+// The owner pass of a set solve and both anchors of a refresh begin here.  With key0 (the second anchor) an item
+// whose key is no longer key0's is cut: -1.
+__global__ __launch_bounds__(THREADS) void k_field_forest_begin(FieldDev F, FieldSources S, bool single,
+                                                                const unsigned long long *__restrict__ key0) {
   const int fbase = blockIdx.y * F.V;
   int *anc = F.q[0];
   for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < F.V; v += gridDim.x * blockDim.x) {
     const int i = fbase + v;
+    const unsigned long long k = F.key[i];
     int a = -1;
-    if (F.key[i] != FIELD_KEY_NONE) {
+    if (k != FIELD_KEY_NONE && (!key0 || k == key0[i])) {
       const int p = F.parent[i];
-      a = F.stamp_near[i] < 0 ? i : (p >= 0 && p < F.V ? fbase + p : -1);
+      a = field_is_source(F, S, single, blockIdx.y, v) ? i : (p >= 0 && p < F.V ? fbase + p : -1);
     }
     anc[i] = a;
   }
@@ -730,51 +750,6 @@ __global__ __launch_bounds__(THREADS) void k_field_carry(const unsigned long lon
   }
 }
 
-// grid.y = field: the carried keys into the work arrays, as k_field_init leaves them otherwise -- a single source at
-// (0, 0) (sets: k_field_seed follows, which needs the queue size this zeroes), no parents, no stamps.
-__global__ __launch_bounds__(THREADS) void k_field_carry_init(FieldDev F, const unsigned long long *__restrict__ carried,
-                                                              FieldSources S, bool single) {
-  const int V = F.V;
-  const int f = blockIdx.y;
-  const int src = single ? S.id[f] : -1;
-  const int fbase = f * V;
-  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
-    F.key[fbase + v] = v == src ? 0ull : carried[fbase + v];
-    F.parent[fbase + v] = INT_MAX;
-    F.stamp_near[fbase + v] = 0;
-    F.stamp_far[fbase + v] = 0u;
-  }
-  if (blockIdx.x == 0 && f == 0 && threadIdx.x == 0) {
-    F.ctrl->c.n[0] = F.ctrl->c.n[1] = 0;
-    F.ctrl->c.overflow = 0;
-    F.ctrl->s.work = 0;
-  }
-}
-
-// is item i (node v of field f) a source: a member of its set by its mark (FieldSets), else its field's one source
-__device__ __forceinline__ bool field_is_source(const FieldDev &F, const FieldSources &S, bool single, int f, int v) {
-  return single ? v == S.id[f] : F.stamp_near[f * F.V + v] < 0;
-}
-
-// grid.y = field: the first ancestor of every item in the supporter forest that k_field_parent left in F.parent --
-// itself for a source, its supporter's item for another item with a key, -1 without one or without a supporter.
-// With key0 (the second anchor) an item whose key is no longer key0's is cut: -1.
-__global__ __launch_bounds__(THREADS) void k_field_anchor_begin(FieldDev F, FieldSources S, bool single,
-                                                                const unsigned long long *__restrict__ key0) {
-  const int fbase = blockIdx.y * F.V;
-  int *anc = F.q[0];
-  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < F.V; v += gridDim.x * blockDim.x) {
-    const int i = fbase + v;
-    const unsigned long long k = F.key[i];
-    int a = -1;
-    if (k != FIELD_KEY_NONE && (!key0 || k == key0[i])) {
-      const int p = F.parent[i];
-      a = field_is_source(F, S, single, blockIdx.y, v) ? i : (p >= 0 && p < F.V ? fbase + p : -1);
-    }
-    anc[i] = a;
-  }
-}
-
 // grid.y = field: an item whose last ancestor is no source (-1: only a source points to itself) loses its key.
 // key0 / carried (the first anchor): the keys as they are now, and per field the count of items that kept theirs.
 __global__ __launch_bounds__(THREADS) void k_field_anchor_end(FieldDev F, const int *__restrict__ anc,
@@ -805,21 +780,7 @@ __global__ __launch_bounds__(THREADS) void k_field_warm_init(FieldDev F, float d
     if (reset_parents) F.parent[i] = INT_MAX;
   }
   if (blockIdx.x == 0 && threadIdx.x < F.m) F.ctrl->reached[threadIdx.x] = 0;  // (k_field_output counts into it)
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    FieldCounters &c = F.ctrl->c;
-    c.n[0] = c.n[1] = 0;
-    c.nfar[0] = c.nfar[1] = 0;
-    c.fmin = ~0u;
-    c.overflow = 0;
-    FieldState &s = F.ctrl->s;
-    s.work = 0;
-    s.rounds = 0;
-    s.overflow = 0;
-    s.thr = 0u;
-    s.delta = delta;
-    s.phase = 1;
-    s.far_sel = 0;
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) field_ctrl_reset(F, 0u, delta, 0);
 }
 
 // The seeding sweep of a warm pass: one 16-lane group per item, four per wave, as k_field_relax -- but over every
@@ -909,10 +870,10 @@ void launch_field_edge_cost(const int *col, const float *w, const float *dist, c
                      state, V, E, safety_factor, ec, st);
 }
 
-void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets, float delta,
-                       hipStream_t s) {
+void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets,
+                       const unsigned long long *carried, float delta, hipStream_t s) {
   hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, sources, delta,
-                     sets == nullptr);
+                     sets == nullptr, carried);
   if (sets) hipLaunchKernelGGL(k_field_seed, dim3(field_blocks(sets->n, THREADS)), dim3(THREADS), 0, s, F, *sets);
 }
 
@@ -945,9 +906,7 @@ void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s) {
 }
 
 void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents, hipStream_t s) {
-  if (parents)
-    hipLaunchKernelGGL(k_field_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s,
-                       F);
+  if (parents) launch_field_supporters(F, s);
   hipLaunchKernelGGL(k_field_output, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, cost, hops);
 }
 
@@ -962,7 +921,7 @@ void launch_field_gather(const FieldDev &F, const FieldSets *sets, const int *ta
 void launch_field_parents_late(const FieldDev &F, hipStream_t s) {
   const dim3 grid(field_blocks(F.N, THREADS));
   hipLaunchKernelGGL(k_field_parent_mark, grid, dim3(THREADS), 0, s, F, -1, INT_MAX);
-  hipLaunchKernelGGL(k_field_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s, F);
+  launch_field_supporters(F, s);
   hipLaunchKernelGGL(k_field_parent_mark, grid, dim3(THREADS), 0, s, F, INT_MAX, -1);
 }
 
@@ -987,11 +946,6 @@ void launch_field_route_walk(const FieldDev &F, const float *w, const float *dis
                        n_routes, offsets, node_ids, infos, sources);
 }
 
-void launch_field_owner_begin(const FieldDev &F, int *changed, hipStream_t s) {
-  (void)hipMemsetAsync(changed, 0, FIELD_OWNER_SWEEPS_MAX * sizeof(int), s);
-  hipLaunchKernelGGL(k_field_owner_begin, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F);
-}
-
 void launch_field_owner_sweep(const FieldDev &F, int sweep, int *changed, hipStream_t s) {
   hipLaunchKernelGGL(k_field_owner_sweep, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F.q[sweep & 1],
                      F.q[~sweep & 1], F.N, changed + sweep);
@@ -1008,22 +962,15 @@ void launch_field_carry(const unsigned long long *old_key, int V_old, const int 
                      out);
 }
 
-void launch_field_carry_init(const FieldDev &F, const unsigned long long *carried, const FieldSources &sources,
-                             const FieldSets *sets, hipStream_t s) {
-  hipLaunchKernelGGL(k_field_carry_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, carried,
-                     sources, sets == nullptr);
-  if (sets) hipLaunchKernelGGL(k_field_seed, dim3(field_blocks(sets->n, THREADS)), dim3(THREADS), 0, s, F, *sets);
-}
-
 void launch_field_supporters(const FieldDev &F, hipStream_t s) {
   hipLaunchKernelGGL(k_field_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s, F);
 }
 
-void launch_field_anchor_begin(const FieldDev &F, const FieldSources &sources, bool single,
-                               const unsigned long long *key0, int *changed, hipStream_t s) {
+void launch_field_forest_begin(const FieldDev &F, const FieldSources *single, const unsigned long long *key0,
+                               int *changed, hipStream_t s) {
   (void)hipMemsetAsync(changed, 0, FIELD_OWNER_SWEEPS_MAX * sizeof(int), s);
-  hipLaunchKernelGGL(k_field_anchor_begin, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, sources,
-                     single, key0);
+  hipLaunchKernelGGL(k_field_forest_begin, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F,
+                     single ? *single : FieldSources{}, single != nullptr, key0);
 }
 
 void launch_field_anchor_end(const FieldDev &F, int sweeps, unsigned long long *key0, int *carried, hipStream_t s) {

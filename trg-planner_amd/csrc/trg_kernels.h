@@ -464,8 +464,10 @@ void launch_field_edge_cost(const int *col, const float *w, const float *dist, c
 // Field k starts at node sources.id[k], k < F.m (duplicates give identical fields).  With `sets` (a set solve; else
 // nullptr) sources is not read: every item is left without a key, then a second launch seeds every distinct member
 // item and pushes it once to near queue 0; F.ctrl's queue size and work are the count of distinct member items.
-void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets, float delta,
-                       hipStream_t s);
+// With `carried` (a refresh's launch_field_carry output, per item; else nullptr) every item that is no source starts
+// with its carried key instead of none; the queue is then not used: the warm start empties it.
+void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets,
+                       const unsigned long long *carried, float delta, hipStream_t s);
 // the settle step of a bounded round: n_t target nodes (device ids) and the mode, FIELD_SETTLE_*
 struct FieldSettle {
   const int *targets;
@@ -524,11 +526,16 @@ void launch_field_route_walk(const FieldDev &F, const float *w, const float *dis
 
 // ---- the owner pass of a set solve ("Source sets") -------------------------------------
 constexpr int FIELD_OWNER_SWEEPS_MAX = 40;  // pointer jumping doubles: 2^31 hops need 31 sweeps and one that finds nothing
-// Owners of a finished set solve whose parent sweep ran, by pointer jumping over the parents.  begin: the first
-// ancestors into F.q[0] (a member itself, another reached item its parent, -1 without a key); sweep i reads
-// F.q[i & 1], writes F.q[~i & 1] = anc[anc[.]] and sets changed[i] when some entry moved (changed: zeroed by
-// begin, FIELD_OWNER_SWEEPS_MAX words); end: S.owner from F.q[sweeps & 1] once a sweep moved nothing.
-void launch_field_owner_begin(const FieldDev &F, int *changed, hipStream_t s);
+// Owners of a finished set solve whose parent sweep ran, by pointer jumping over the parents.  begin
+// (launch_field_forest_begin without single sources or key0): the first ancestors into F.q[0] (a member itself,
+// another reached item its parent, -1 without a key); sweep i reads F.q[i & 1], writes F.q[~i & 1] = anc[anc[.]] and
+// sets changed[i] when some entry moved (changed: zeroed by begin, FIELD_OWNER_SWEEPS_MAX words); end: S.owner from
+// F.q[sweeps & 1] once a sweep moved nothing.
+// The begin of every jump over the forest in F.parent, the owner pass's and a refresh's anchors': a source is its
+// own first ancestor -- node single->id[k] of field k, or with single == nullptr (a set solve) every member, told by
+// its mark -- and with key0 (may be nullptr) an item whose key differs from key0's is cut.
+void launch_field_forest_begin(const FieldDev &F, const FieldSources *single, const unsigned long long *key0,
+                               int *changed, hipStream_t s);
 void launch_field_owner_sweep(const FieldDev &F, int sweep, int *changed, hipStream_t s);
 void launch_field_owner_end(const FieldDev &F, const FieldSets &S, int sweeps, hipStream_t s);
 // owned[entry] = items whose owner is that entry (S.n counts, zeroed here)
@@ -539,21 +546,14 @@ void launch_field_owned(const FieldDev &F, const FieldSets &S, int *owned, hipSt
 // fields.  `out` is a buffer of its own (m * V keys): the old solve's arrays may be regrown once this is enqueued.
 void launch_field_carry(const unsigned long long *old_key, int V_old, const int *new2old, int V, int m,
                         unsigned long long *out, hipStream_t s);
-// The work arrays as launch_field_init leaves them, but with the carried keys: the sources at (0, 0) -- sources.id,
-// or with `sets` every member, seeded and marked as by launch_field_init -- no parents, no stamps.  The queue that
-// the seeding of sets fills is not used: the warm start below empties it.
-void launch_field_carry_init(const FieldDev &F, const unsigned long long *carried, const FieldSources &sources,
-                             const FieldSets *sets, hipStream_t s);
 // F.parent[item] = the item's supporter under the keys as they are: the smallest u with an edge u -> v and
-// key_extend(key[u], c) == key[v], INT_MAX without one (launch_field_finish's parent sweep on its own)
+// key_extend(key[u], c) == key[v], INT_MAX without one: the parent sweep, which launch_field_finish and
+// launch_field_parents_late run through this
 void launch_field_supporters(const FieldDev &F, hipStream_t s);
-// The anchor: an item keeps its key if its chain of supporters (F.parent) ends at a source.  begin: the first
-// ancestors into F.q[0] (a source itself; with key0, an item whose key differs from key0's is cut) and `changed`
-// zeroed; then launch_field_owner_sweep until a sweep moves nothing; end: every item whose last ancestor is no
-// source loses its key, key0 (may be nullptr) gets the keys after that and carried[k] (may be nullptr; m ints)
-// the number of field k's items that kept one.
-void launch_field_anchor_begin(const FieldDev &F, const FieldSources &sources, bool single,
-                               const unsigned long long *key0, int *changed, hipStream_t s);
+// The anchor: an item keeps its key if its chain of supporters (F.parent) ends at a source.  begin:
+// launch_field_forest_begin; then launch_field_owner_sweep until a sweep moves nothing; end: every item whose last
+// ancestor is no source loses its key, key0 (may be nullptr) gets the keys after that and carried[k] (may be nullptr;
+// m ints) the number of field k's items that kept one.
 void launch_field_anchor_end(const FieldDev &F, int sweeps, unsigned long long *key0, int *carried, hipStream_t s);
 // A warm pass starts from the keys as they are: stamps cleared (a member's mark stays), threshold 0, both queues
 // empty, and in far pile 0 every item with a key one of whose edges (F.tight set: tight edges) improves its target.

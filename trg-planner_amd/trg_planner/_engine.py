@@ -488,10 +488,12 @@ class Engine:
         return np.flatnonzero(np.ctypeslib.as_array(v.node_state, shape=(v.num_nodes,)) == 1).astype(np.int32)
 
     def _field_outputs(self, who, m, targets, full, budget, settle, owners=False):
-        """What cost_fields and cost_fields_from (`who`) share: `settle` checked, then the result dict with its
-        output arrays -- "cost", "hops", "parent" (and "owner") (m, V) with `full`; "cost_at", "hops_at" (and
-        "owner_at") (m, n_t) with `targets`; "reached"; "bound" under budget / settle -- and the arrays passed
-        beside them -> (dict, targets int32 or None, n_t, budget broadcast to m float32 or None)."""
+        """What cost_fields, refresh_fields and cost_fields_from (`who`) share: `settle` checked, then the result dict
+        with its output arrays -- "cost", "hops", "parent" (and "owner") (m, V) with `full`; "cost_at", "hops_at" (and
+        "owner_at") (m, n_t) with `targets`; "reached"; "bound" under budget / settle -- and the C entries' argument
+        groups for them, ready to splat, None where an array is not there -> (dict, groups): "full" (cost, hops,
+        parent), "at" (targets, n_t, cost_at, hops_at), and the single arguments "owner", "owner_at", "reached",
+        "budget" (broadcast to m float32) and "bound"."""
         if settle not in _SETTLE:
             raise ValueError(f"{who}: settle {settle!r} (\"any\", \"all\" or None)")
         V, _ = self.graph_sizes("global")
@@ -513,7 +515,14 @@ class Engine:
             bud = np.ascontiguousarray(np.broadcast_to(np.asarray(budget, dtype=np.float32).reshape(-1), (m,)))
         if budget is not None or settle is not None:
             out["bound"] = np.empty(max(m, 1), np.float32)
-        return out, tg, nt, bud
+
+        def arg(key, conv=_i):
+            return conv(out[key]) if key in out else None
+        groups = {"full": [arg("cost", _f), arg("hops"), arg("parent")],
+                  "at": [None if tg is None else _i(tg), nt, arg("cost_at", _f), arg("hops_at")],
+                  "owner": arg("owner"), "owner_at": arg("owner_at"), "reached": arg("reached"),
+                  "budget": None if bud is None else _f(bud), "bound": arg("bound", _f)}
+        return out, groups
 
     def cost_fields(self, sources_xy=None, source_ids=None, targets=None, full=True, budget=None, settle=None):
         """m cost fields in one solve on the GPU (trg_engine_cost_field_batch; each field as cost_field's).
@@ -532,20 +541,17 @@ class Engine:
         ids = None if source_ids is None else np.ascontiguousarray(source_ids, dtype=np.int32).reshape(-1)
         xy = None if sources_xy is None else np.ascontiguousarray(sources_xy, dtype=np.float32).reshape(-1, 2)
         m = ids.shape[0] if ids is not None else xy.shape[0]
-        out, tg, nt, bud = self._field_outputs("cost_fields", m, targets, full, budget, settle)
+        out, a = self._field_outputs("cost_fields", m, targets, full, budget, settle)
         if ids is not None and xy is not None and xy.shape[0] != m:
             raise ValueError("cost_fields: sources_xy and source_ids differ in length")
         out["sources"] = np.full(m, -1, np.int32)
         info = TrgFieldInfo()
         # the bounded entry's arguments; the batch entry's are these without budget, settle and bound_out
         sources = [self.h, m, None if ids is None else _i(ids), None if xy is None else _f(xy)]
-        bounds = [None if bud is None else _f(bud), _SETTLE[settle]]
-        outputs = [_f(out["cost"]) if full else None, _i(out["hops"]) if full else None,
-                   _i(out["parent"]) if full else None, None if tg is None else _i(tg), nt,
-                   None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
-                   _i(out["sources"]), _i(out["reached"])]
+        outputs = [*a["full"], *a["at"], _i(out["sources"]), a["reached"]]
         if "bound" in out:
-            self._chk(self.L.trg_engine_cost_field_bounded(*sources, *bounds, *outputs, _f(out["bound"]), C.byref(info)))
+            self._chk(self.L.trg_engine_cost_field_bounded(*sources, a["budget"], _SETTLE[settle], *outputs, a["bound"],
+                                                           C.byref(info)))
         else:
             self._chk(self.L.trg_engine_cost_field_batch(*sources, *outputs, C.byref(info)))
         self._field_shape = (m, False)
@@ -566,17 +572,13 @@ class Engine:
         # call refuses before it writes anything
         m, sets = getattr(self, "_field_shape", (1, False))
         n2o = None if new2old is None else np.ascontiguousarray(new2old, dtype=np.int32).reshape(-1)
-        out, tg, nt, _ = self._field_outputs("refresh_fields", m, targets, full, None, None, owners=sets)
+        out, a = self._field_outputs("refresh_fields", m, targets, full, None, None, owners=sets)
         out["sources"] = np.full(m, -1, np.int32)
         out["carried"] = np.zeros(m, np.int32)
         info = TrgFieldInfo()
         self._chk(self.L.trg_engine_cost_field_refresh(
-            self.h, None if n2o is None else _i(n2o), 0 if n2o is None else n2o.shape[0],
-            _f(out["cost"]) if full else None, _i(out["hops"]) if full else None, _i(out["parent"]) if full else None,
-            None if tg is None else _i(tg), nt, None if tg is None else _f(out["cost_at"]),
-            None if tg is None else _i(out["hops_at"]), _i(out["owner"]) if full and sets else None,
-            _i(out["owner_at"]) if tg is not None and sets else None, _i(out["sources"]), _i(out["reached"]),
-            _i(out["carried"]), C.byref(info)))
+            self.h, None if n2o is None else _i(n2o), 0 if n2o is None else n2o.shape[0], *a["full"], *a["at"],
+            a["owner"], a["owner_at"], _i(out["sources"]), a["reached"], _i(out["carried"]), C.byref(info)))
         out["info"] = info
         return out
 
@@ -633,7 +635,7 @@ class Engine:
         "sources" is every set's first id."""
         sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
         m = len(sets)
-        out, tg, nt, bud = self._field_outputs("cost_fields_from", m, targets, full, budget, settle, owners=True)
+        out, a = self._field_outputs("cost_fields_from", m, targets, full, budget, settle, owners=True)
         ptr = np.zeros(m + 1, np.int64)
         np.cumsum([s.shape[0] for s in sets], out=ptr[1:])
         if ptr[-1] > 2**31 - 1:
@@ -643,12 +645,8 @@ class Engine:
         owned = np.zeros(max(int(ptr[-1]), 1), np.int32)
         info = TrgFieldInfo()
         self._chk(self.L.trg_engine_cost_field_sets(
-            self.h, m, _i(ptr), _i(ids), None if bud is None else _f(bud), _SETTLE[settle],
-            _f(out["cost"]) if full else None, _i(out["hops"]) if full else None, _i(out["parent"]) if full else None,
-            _i(out["owner"]) if full else None, None if tg is None else _i(tg), nt,
-            None if tg is None else _f(out["cost_at"]), None if tg is None else _i(out["hops_at"]),
-            None if tg is None else _i(out["owner_at"]), _i(owned), _i(out["reached"]),
-            _f(out["bound"]) if "bound" in out else None, C.byref(info)))
+            self.h, m, _i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
+            _i(owned), a["reached"], a["bound"], C.byref(info)))
         self._field_shape = (m, True)
         out["owned"] = [owned[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
         out["sets"] = sets
