@@ -69,8 +69,9 @@ def drive(engine, oracle, witness, steps, check=None, *, clouds, prm):
     engine=None: the two oracles alone, compared with each other (structure bit for bit, weights as above).
     A failure names the step and the first differing field.  check(i, step, record) runs after every init / update.
     -> the records: dict(i, kind, V, E, xyz, deg0 (the rows without an edge), frontier (the number of Frontier nodes),
-    wire_calls (wireEdge calls of an update), local_V, stats) of the ORACLE's graph after the step (local_V, stats:
-    the engine's local-graph size before an update and its stats() after the step, else None)."""
+    nonzero_w (the number of non-zero weights), wire_calls (wireEdge calls of an update), local_V, stats) of the
+    ORACLE's graph after the step (local_V, stats: the engine's local-graph size before an update and its stats()
+    after the step, else None)."""
     from concurrent.futures import ThreadPoolExecutor
     # the two oracles work beside the engine, each on a thread of its own (their calls hold no Python lock)
     with ThreadPoolExecutor(2) as pool:
@@ -144,6 +145,7 @@ def _drive(pool, engine, oracle, witness, steps, check, clouds, prm):
                                f"by {float(np.abs(ge.w - gw.w).max())} at the most"
         rec = dict(i=i, kind="update" if kind == "update" else "init", V=go.V, E=go.E, xyz=go.xyz,
                    deg0=np.flatnonzero(np.diff(go.rowptr) == 0), frontier=int((go.state == 1).sum()),
+                   nonzero_w=int((go.w != 0).sum()),
                    wire_calls=oracle.counters()["wire_calls"] - calls_before if kind == "update" else None,
                    local_V=local_V if kind == "update" else None, stats=None if engine is None else engine.stats())
         hist.append(rec)

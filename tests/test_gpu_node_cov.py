@@ -94,9 +94,11 @@ def test_creating_edge_weights_equal_the_fp64_witness(oa, mountain_small, mounta
 
 
 def test_step3_build_structure_and_states(oa, indoor_small):
-    """expandGraph's step 3 on (indoor.yaml): a node can be valid although its parent edge failed, and
-    k_node_cov must pass over it.  Every weight of this fixture is 0 -- flat floors -- so this pins structure
-    and states only; it says nothing about weights."""
+    """expandGraph's step 3 on (indoor.yaml) on a flat floor: this pins the tree order of the neighbour calls
+    (k_kd_*, k_step3_calls) through structure and states, and nothing else.  No parent edge of this fixture fails
+    (test_step3_cases_cpu.py keeps that on record) and every weight is 0, so no node is rescued and k_node_cov
+    passes over none: nodes that are valid although their parent edge failed, and their weights, are
+    test_gpu_step3.py's."""
     import trg_planner
     prm = dict(oa.INDOOR)
     start = [1.5, 1.5, 0.0]

@@ -19,6 +19,7 @@ from collections import namedtuple
 import numpy as np
 
 from graph_support import obs_crop
+from step3_cases import r160
 
 Scenario = namedtuple("Scenario", "name base overrides seed replays steps")
 # base: the oracle_api parameter set by name; overrides: changes to it; seed: sampler seed (table_bits 16);
@@ -30,8 +31,10 @@ START_GENTLE = [15.0, 15.0, 0.0]
 
 
 def scenario_clouds(synth, mountain_gentle, indoor_small):
-    """The clouds the steps name: B, 20 m x 20 m (V=2288 from START_B under MOUNTAIN, seed 5); the two fixtures."""
-    return {"B": synth.mountain_cloud(200, 200, seed=1), "gentle": mountain_gentle, "indoor": indoor_small}
+    """The clouds the steps name: B, 20 m x 20 m (V=2288 from START_B under MOUNTAIN, seed 5); the two fixtures;
+    rough, the 16 m x 16 m of step3_cases.py on which step 3 rescues nodes."""
+    return {"B": synth.mountain_cloud(200, 200, seed=1), "gentle": mountain_gentle, "indoor": indoor_small,
+            "rough": r160(synth)}
 
 
 def params(oa, sc):
@@ -150,6 +153,13 @@ SCENARIOS = [
         ("local", node_fraction(1, 2, frozen=True), crop(3.0, (1.0, 0.5, 0.5))), ("update",),
         ("local", node_fraction(2, 3, frozen=True), crop(3.0, (1.0, 0.5, 0.5))), ("update",),
         ("local", remembered("first"), crop(3.0)), ("update",)]),
+    # the same on rough ground (step3_cases.py), where step 3 decides something: parent edges fail, nodes are rescued
+    # by a neighbour, weights are non-zero -- in the build and in the expansions of every update
+    Scenario("terrain_step3_updates", "INDOOR", dict(UPDATE_OVERRIDES), 5, BOTH, [
+        ("map", "rough"), ("init", [8.0, 8.0, 0.0]),
+        ("local", node_fraction(1, 3, "first", frozen=True), crop(3.0, (1.0, 0.5, 0.5))), ("update",),
+        ("local", node_fraction(1, 2, frozen=True), crop(3.0, (1.0, 0.5, 0.5))), ("update",),
+        ("local", remembered("first"), crop(3.0)), ("update",)]),
     # one engine through a build, an update and a build on another map: ids follow the container's history
     _mountain("history_rebuild",
               [("map", "gentle"), ("init", START_GENTLE)] + _UPDATE_A +
@@ -206,6 +216,13 @@ def check_indoor_step3_updates(hist):
     assert any(h["frontier"] > 0 for h in _updates(hist)), [h["frontier"] for h in hist]
 
 
+def check_terrain_step3_updates(hist):
+    ups = _updates(hist)
+    assert len(ups) == 3 and all(h["wire_calls"] > 1000 for h in ups), [h["wire_calls"] for h in hist]
+    assert all(h["frontier"] > 0 for h in ups), [h["frontier"] for h in hist]
+    assert hist[-1]["nonzero_w"] > 1000, hist[-1]["nonzero_w"]
+
+
 def check_renumber_only(hist):
     build, first = hist[0], hist[1]
     assert (first["V"], first["E"]) == (build["V"], build["E"]), (build["V"], build["E"], first["V"], first["E"])
@@ -232,5 +249,6 @@ def check_many_roots(hist):
 
 
 PRECONDITIONS = {"many_roots": check_many_roots, "indoor_step3_updates": check_indoor_step3_updates,
+                 "terrain_step3_updates": check_terrain_step3_updates,
                  "renumber_only": check_renumber_only,
                  "isolated_node": check_isolated_node, "stripes": check_stripes}
