@@ -438,6 +438,35 @@ TrgStatus trg_engine_cost_field_sets(
     float *cost_at, int32_t *hops_at, int32_t *owner_at,           /* m x n_targets, any may be NULL */
     int32_t *owned,              /* set_ptr[m], may be NULL */
     int32_t *reached_out, float *bound_out, TrgFieldInfo *info);
+/* Cost models ("Cost models"): trg_engine_cost_field_sets with a cost model per field, so that one
+ * solve answers the same query at several risk attitudes.  A model is (safety_factor s, max_weight tau), both fp32.
+ * In a field with that model an edge is admitted iff it is relaxable (its target a node, and not Invalid) and its
+ * weight is <= tau, compared in fp32 (tau = +inf admits every weight); an admitted edge costs
+ * (s * weight + 1) * dist, every operation rounded to fp32.  Keys, hops, parents, owners, the saturation rule, the
+ * truncation at a bound and the routes are the set call's, over the field's own admitted edges and costs: the field
+ * is bit for bit the one an engine created with safety_factor s computes on the graph without the edges of weight
+ * > tau, and a route edge is the admitted edge of least CSR index with the matching extension (so a ceiling also
+ * decides among duplicate edges).  models == NULL, or (the engine's safety_factor, +inf) for a field, is
+ * trg_engine_cost_field_sets' behaviour; a single source is a set of one.
+ * The solve is retained with its models: trg_engine_field_routes, trg_engine_field_reached and
+ * trg_engine_cost_field_refresh (which derives the models' costs again on the updated graph) answer from it with
+ * them.  Edge costs are cached per distinct model and graph; the engine's own model is never dropped from the cache.
+ * TRG_ERR_INVALID_ARG, naming the field, for a safety_factor that is NaN, negative or infinite, a max_weight that is
+ * NaN or negative, and for a model under which some edge cost is negative or not finite; TRG_ERR_CAPACITY when the
+ * edge costs of the models do not fit the device; everything else as trg_engine_cost_field_sets. */
+typedef struct TrgFieldModel {
+  float safety_factor;  /* finite, >= 0 */
+  float max_weight;     /* the risk ceiling: >= 0, +inf for none */
+} TrgFieldModel;
+TrgStatus trg_engine_cost_field_models(
+    TrgEngine *e, int32_t m,
+    const TrgFieldModel *models, /* m, or NULL: the engine's model for every field */
+    const int32_t *set_ptr, const int32_t *set_ids,
+    const float *budget, int32_t settle,
+    float *cost, int32_t *hops, int32_t *parent, int32_t *owner,
+    const int32_t *targets, int32_t n_targets,
+    float *cost_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info);
 /* The nodes of field `field` (0 .. m-1) of the retained solve that have a key, compacted on the device: their
  * ids in ascending order with cost and hops, so that a bounded field that reaches few nodes is read without
  * copying anything of num_nodes entries.  *n_out is always the full count; node_ids, cost and hops (room for cap

@@ -28,11 +28,22 @@ struct FieldBufs {
   DevArr targets, cost_at, hops_at;                                           // n_targets, m x n_targets
   DevArr up_rowptr, up_col, up_w, up_dist, up_state;  // csr_global + nstate when the device build's CSR is stale
   uint64_t up_version = 0;   // graph_version of the upload (0: none)
+  // The edge-cost cache ("Cost models"): `ec` holds slot i at i * ec_stride, one slot per
+  // cost model met, for one graph_version and column array.  Slot 0 is the engine's own model and is never given
+  // away; the others go to the model a solve needs and does not find, the least recently used first.
+  struct CostSlot {
+    uint32_t sf_bits, tau_bits;  // the model, as bits
+    bool valid;                  // the costs and the three words below are computed
+    double sum;                  // over admitted edges
+    long long count;
+    bool bad;                    // some edge cost is negative or not finite
+    uint64_t used;               // ec_tick of the last solve that read it
+  };
+  std::vector<CostSlot> slots;
+  size_t ec_stride = 0;      // entries from one slot to the next
+  uint64_t ec_tick = 0;
   uint64_t ec_version = 0;   // graph_version of the edge costs (0: none)
   const void *ec_col = nullptr;  // ... and the column array they were computed from
-  float ec_sf = 0.0f;
-  double mean_cost = 0.0;    // over relaxable edges
-  bool bad_cost = false;
   // The last solve, kept on the device for trg_engine_field_routes: set by a successful solve, cleared when a
   // solve begins its device work; a graph_version other than the engine's (init_graph, update_graph, load_json,
   // a reset) makes it stale, so does a device-build CSR that is no longer valid (an update_graph that began,
@@ -47,6 +58,11 @@ struct FieldBufs {
     std::optional<FieldSets> sets;  // of a set solve ("Source sets"), on the device
     bool owners = false;     // ... and the owner pass ran: sets->owner is filled
     bool bounded = false;    // keys above a bound were removed: nothing a refresh can start from
+    // its cost models ("Cost models"): per field, empty when the request named none; F.ec is
+    // the slot all fields share, or with `many` slot 0 and `models` the table the kernels take
+    std::vector<TrgFieldModel> pairs;
+    FieldModels models{};
+    bool many = false;
     // (F.V and F.m are the node count of its graph and its fields: what a refresh reads the old keys by)
   } last;
   DevArr set_ptr, set_ids, owner, owner_at, owned, own_changed;  // set solves; owner: m x V, only when asked for
@@ -73,6 +89,8 @@ void field_release(TrgEngine *e) {
 }
 
 static_assert(FIELD_MAX_SOURCES == TRG_FIELD_BATCH_MAX, "the kernels' and the header's batch limit differ");
+// the engine's own slot and one per field of the largest batch
+constexpr int FIELD_SLOTS_MAX = FIELD_MAX_SOURCES + 1;
 
 // What an entry asks of field_solve.  Every entry value-initialises one and names what it sets: all else is null, 0,
 // false, TRG_FIELD_SETTLE_NONE.
@@ -96,6 +114,8 @@ struct FieldRequest {
   int32_t *owner;     // m x V
   int32_t *owner_at;  // m x n_targets
   int32_t *owned;     // set_ptr[m]
+  // a cost model per field (trg_engine_cost_field_models), or nullptr: the engine's for every field
+  const TrgFieldModel *models;  // m
   // a refresh (trg_engine_cost_field_refresh): m and the sources or sets are the retained solve's, filled in by
   // field_check_refresh, and its keys are carried through new2old instead of a cold start
   bool refresh;
@@ -137,6 +157,14 @@ struct FieldRun {
   // to point at -- the identity map, the sources or the sets as ids of the current graph
   FieldDev old{};
   std::vector<int32_t> identity, src, set_ptr, set_ids;
+  std::vector<TrgFieldModel> pairs;  // ... and its models
+  // the edge costs of this solve (field_edge_costs): the slot table, whether the fields read more than one slot
+  // (else F.ec is the one they share and no kernel takes the table), and the mean over its distinct slots
+  FieldModels models{};
+  bool many_models = false;
+  const float *ec = nullptr;
+  double mean_cost = 0.0;
+  const FieldModels *model_table() const { return many_models ? &models : nullptr; }
 };
 
 constexpr uint32_t FIELD_INF_BITS = 0x7f800000u;
@@ -223,6 +251,10 @@ TrgStatus field_check_refresh(TrgEngine *e, FieldRun &run) {
   }
   rq.m = m;
   run.old = old.F;
+  if (!old.pairs.empty()) {  // the retained models, whose costs field_edge_costs derives again on this graph
+    run.pairs = old.pairs;
+    rq.models = run.pairs.data();
+  }
   return TRG_OK;
 }
 
@@ -309,7 +341,7 @@ TrgStatus field_begin(TrgEngine *e, FieldRun &) {
   fb.last = FieldBufs::Last{};  // from here on the work arrays change
   e->field_map_state = TrgEngine::FIELD_MAP_NONE;  // (the node map is of the retained solve's graph)
   HIPCHK(e, fb.h_state.ensure(1));
-  HIPCHK(e, fb.h_stats.ensure(1));
+  HIPCHK(e, fb.h_stats.ensure(FIELD_SLOTS_MAX));
   HIPCHK(e, fb.h_reached.ensure(TRG_FIELD_BATCH_MAX));
   HIPCHK(e, fb.h_bound.ensure(TRG_FIELD_BATCH_MAX));
   HIPCHK(e, fb.t0.create());
@@ -349,29 +381,95 @@ TrgStatus field_graph(TrgEngine *e, FieldRun &run) {
   return TRG_OK;
 }
 
-// edge costs and the bad-cost flag, once per graph version and safety factor (one host wait when they are computed)
+// Edge costs ("Cost models"): every field's model gets a slot of the cache, found or taken;
+// only the slots that are missing are computed, one launch each and ONE host wait for all their stats.  The bucket
+// width's mean is over the solve's distinct slots.
 TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
   FieldBufs &fb = *e->field;
   hipStream_t s = e->s_main;
   const FieldRun::Graph &G = run.G;
-  const float sf = e->prm.safety_factor;
-  if (fb.ec_version != e->graph_version || fb.ec_col != (const void *)G.col || fb.ec_sf != sf) {
-    fb.ec_version = 0;
-    TrgStatus st;
-    if ((st = ensure_bytes(e, fb.ec, (size_t)G.E * sizeof(float) + 16)) != TRG_OK) return st;
-    if ((st = ensure_bytes(e, fb.stats, sizeof(FieldEdgeStats))) != TRG_OK) return st;
-    launch_field_edge_cost(G.col, G.w, G.dist, G.state, run.F.V, G.E, sf, fb.ec.as<float>(),
-                           fb.stats.as<FieldEdgeStats>(), s);
-    HIPCHK(e, hipMemcpyAsync(fb.h_stats, fb.stats.p, sizeof(FieldEdgeStats), hipMemcpyDeviceToHost, s));
+  const int m = run.F.m;
+  const uint32_t sf0 = float_bits(e->prm.safety_factor);
+  const size_t stride = ((size_t)G.E + 4 + 3) & ~(size_t)3;  // (slots start 16-byte aligned, 16 bytes of slack each)
+  if (fb.ec_version != e->graph_version || fb.ec_col != (const void *)G.col || fb.ec_stride != stride ||
+      fb.slots.empty() || fb.slots[0].sf_bits != sf0)
+    fb.slots.assign(1, FieldBufs::CostSlot{sf0, FIELD_INF_BITS, false, 0.0, 0, false, 0});
+  fb.ec_version = 0;  // (until this phase is through: a failure half-way leaves no cache)
+  const uint64_t tick = ++fb.ec_tick;
+  std::vector<int> fresh;  // the slots to compute
+  for (int k = 0; k < m; ++k) {
+    const uint32_t sfb = run.rq.models ? float_bits(run.rq.models[k].safety_factor) : sf0;
+    const uint32_t taub = run.rq.models ? float_bits(run.rq.models[k].max_weight) : FIELD_INF_BITS;
+    int slot = -1;
+    for (size_t i = 0; i < fb.slots.size() && slot < 0; ++i)
+      if (fb.slots[i].sf_bits == sfb && fb.slots[i].tau_bits == taub) slot = (int)i;
+    if (slot < 0) {
+      if ((int)fb.slots.size() < FIELD_SLOTS_MAX) {
+        slot = (int)fb.slots.size();
+        fb.slots.push_back({});
+      } else {  // (a solve reads at most FIELD_MAX_SOURCES slots: one beside slot 0 is not this solve's)
+        for (size_t i = 1; i < fb.slots.size(); ++i)
+          if (fb.slots[i].used != tick && (slot < 0 || fb.slots[i].used < fb.slots[slot].used)) slot = (int)i;
+      }
+      if (slot < 0)
+        return e->fail(TRG_ERR_CAPACITY, "cost field: no cache slot left for the model of field " + std::to_string(k));
+      fb.slots[slot] = FieldBufs::CostSlot{sfb, taub, false, 0.0, 0, false, tick};
+    }
+    FieldBufs::CostSlot &cs = fb.slots[slot];
+    if (!cs.valid && std::find(fresh.begin(), fresh.end(), slot) == fresh.end()) fresh.push_back(slot);
+    cs.used = tick;
+    run.models.slot[k] = slot;
+  }
+  if (!fresh.empty() || !fb.ec.p) {
+    const size_t bytes = fb.slots.size() * stride * sizeof(float);
+    if (ensure_bytes(e, fb.ec, bytes, true) != TRG_OK ||
+        ensure_bytes(e, fb.stats, FIELD_SLOTS_MAX * sizeof(FieldEdgeStats)) != TRG_OK) {
+      (void)hipGetLastError();
+      return e->fail(TRG_ERR_CAPACITY, "cost field: no device memory for the edge costs of " +
+                                           std::to_string(fb.slots.size()) + " cost models (" + e->err + ")");
+    }
+  }
+  if (!fresh.empty()) {
+    FieldEdgeStats *d_stats = fb.stats.as<FieldEdgeStats>();
+    for (size_t j = 0; j < fresh.size(); ++j) {
+      const FieldBufs::CostSlot &cs = fb.slots[fresh[j]];
+      launch_field_edge_cost(G.col, G.w, G.dist, G.state, run.F.V, G.E, bits_float(cs.sf_bits), bits_float(cs.tau_bits),
+                             fb.ec.as<float>() + (size_t)fresh[j] * stride, d_stats + j, s);
+    }
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(fb.h_stats, d_stats, fresh.size() * sizeof(FieldEdgeStats), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     run.syncs++;
-    fb.bad_cost = fb.h_stats->bad != 0;
-    fb.mean_cost = fb.h_stats->count ? fb.h_stats->sum / fb.h_stats->count : 0.0;
-    fb.ec_version = e->graph_version;
-    fb.ec_col = G.col;
-    fb.ec_sf = sf;
+    for (size_t j = 0; j < fresh.size(); ++j) {
+      FieldBufs::CostSlot &cs = fb.slots[fresh[j]];
+      cs.sum = fb.h_stats[j].sum;
+      cs.count = fb.h_stats[j].count;
+      cs.bad = fb.h_stats[j].bad != 0;
+      cs.valid = true;
+    }
   }
-  if (fb.bad_cost) return e->fail(TRG_ERR_INVALID_ARG, "cost field: an edge cost is negative or not finite");
+  fb.ec_version = e->graph_version;
+  fb.ec_col = G.col;
+  fb.ec_stride = stride;
+  double sum = 0.0;
+  long long count = 0;
+  for (int k = 0; k < m; ++k) {
+    const int slot = run.models.slot[k];
+    const FieldBufs::CostSlot &cs = fb.slots[slot];
+    if (cs.bad)
+      return e->fail(TRG_ERR_INVALID_ARG,
+                     "cost field: an edge cost is negative or not finite under the model of field " + std::to_string(k));
+    bool seen = false;
+    for (int j = 0; j < k && !seen; ++j) seen = run.models.slot[j] == slot;
+    if (!seen) {
+      sum += cs.sum;
+      count += cs.count;
+    }
+    run.many_models = run.many_models || slot != run.models.slot[0];
+  }
+  run.mean_cost = count ? sum / (double)count : 0.0;
+  run.models.stride = (long long)stride;
+  run.ec = fb.ec.as<float>() + (run.many_models ? 0 : (size_t)run.models.slot[0] * stride);
   return TRG_OK;
 }
 
@@ -406,7 +504,7 @@ TrgStatus field_work_arrays(TrgEngine *e, FieldRun &run) {
   FieldDev &F = run.F;
   F.rowptr = run.G.rowptr;
   F.col = run.G.col;
-  F.ec = fb.ec.as<float>();
+  F.ec = run.ec;
   F.key = fb.key.as<unsigned long long>();
   for (int i = 0; i < 2; ++i) {
     F.q[i] = fb.q[i].as<int>();
@@ -446,9 +544,8 @@ TrgStatus field_uploads(TrgEngine *e, FieldRun &run) {
 }
 
 // the bucket width: a fixed multiple of the mean edge cost
-float field_delta(const TrgEngine *e) {
-  const FieldBufs &fb = *e->field;
-  return fb.mean_cost > 0.0 ? (float)(e->field_delta_scale * fb.mean_cost) : 0.0f;
+float field_delta(const TrgEngine *e, const FieldRun &run) {
+  return run.mean_cost > 0.0 ? (float)(e->field_delta_scale * run.mean_cost) : 0.0f;
 }
 
 // the rounds of one pass from round 0 on, enqueued in batches, until no work is left
@@ -458,7 +555,7 @@ TrgStatus field_rounds(TrgEngine *e, FieldRun &run, const FieldSettle *under) {
   hipStream_t s = e->s_main;
   const long long cap = 4LL * F.N + 64;
   for (int round = 0;;) {
-    for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s, under);
+    for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s, under, run.model_table());
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(fb.h_state, &F.ctrl->s, sizeof(FieldState), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
@@ -534,7 +631,8 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
   const FieldRequest &rq = run.rq;
   FieldDev &F = run.F;
   hipStream_t s = e->s_main;
-  const float delta = field_delta(e);
+  const float delta = field_delta(e, run);
+  const FieldModels *models = run.model_table();
   const FieldSettle under{fb.targets.as<int>(), rq.n_targets, rq.settle};
   const FieldSets *sets = rq.set_ptr ? &run.sets : nullptr;
   TrgStatus st;
@@ -549,12 +647,12 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
     } else {
       if (pass == 0) {
         launch_field_init(F, run.sources, sets, fb.key0.as<unsigned long long>(), delta, s);
-        launch_field_supporters(F, s);
+        launch_field_supporters(F, s, models);
       }
       if ((st = field_anchor(e, run, pass == 0)) != TRG_OK) return st;
       if (pass == 0)
         HIPCHK(e, hipMemcpyAsync(fb.h_carried, fb.carried.p, (size_t)F.m * sizeof(int), hipMemcpyDeviceToHost, s));
-      launch_field_warm_start(F, delta, pass == 1, s);
+      launch_field_warm_start(F, delta, pass == 1, s, models);
     }
     if ((st = field_rounds(e, run, under_bounds ? &under : nullptr)) != TRG_OK) return st;
     if (under_bounds) {
@@ -587,7 +685,7 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   const int m = F.m;
   const size_t nN = (size_t)F.N, nat = (size_t)m * rq.n_targets;
   const bool parents = rq.parent != nullptr || run.owners;  // (owners follow parents)
-  launch_field_finish(F, fb.cost.as<float>(), fb.hops.as<int>(), parents, s);
+  launch_field_finish(F, fb.cost.as<float>(), fb.hops.as<int>(), parents, s, run.model_table());
   TrgStatus st;
   int sweeps = 0;
   if (run.owners && (st = field_owner_pass(e, F, run.sets, run.syncs, sweeps)) != TRG_OK) return st;
@@ -636,6 +734,9 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
                             rq.set_ptr ? std::optional<FieldSets>(run.sets) : std::nullopt, run.owners};
   fb.last.F.tight = nullptr;  // (its array holds the cost output now)
   fb.last.bounded = run.bounded;
+  if (rq.models) fb.last.pairs.assign(rq.models, rq.models + m);
+  fb.last.models = run.models;
+  fb.last.many = run.many_models;
   e->field_map_state = TrgEngine::FIELD_MAP_IDENTITY;  // update_graph takes the node map on from here
   return field_timing(e, run.info, run.syncs, run.t_total);
 }
@@ -726,7 +827,7 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   HIPCHK(e, hipMemcpyAsync(fb.route_target.p, rq.target, n * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(e, hipEventRecord(fb.t0, s));
   if (!last->parents) {
-    launch_field_parents_late(F, s);
+    launch_field_parents_late(F, s, last->many ? &last->models : nullptr);
     HIPCHK(e, hipGetLastError());
     last->parents = true;
   }
@@ -760,7 +861,8 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   const int *d_off = want_ids ? fb.route_off.as<int>() : nullptr;
   int *d_ids = want_ids ? fb.route_ids.as<int>() : nullptr;
   launch_field_route_walk(F, last->w, last->dist, d_field, d_target, rq.n, d_off, d_ids,
-                          fb.route_info.as<FieldRouteInfo>(), last->sources, last->sets ? &*last->sets : nullptr, s);
+                          fb.route_info.as<FieldRouteInfo>(), last->sources, last->sets ? &*last->sets : nullptr, s,
+                          last->many ? &last->models : nullptr);
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
   int32_t *ids_out = rq.node_ids;
@@ -868,6 +970,19 @@ TrgStatus field_check_bounds(TrgEngine *e, int32_t m, const float *budget, int32
   return TRG_OK;
 }
 
+// the model checks of trg_engine_cost_field_models: a safety factor is a finite number >= 0, a ceiling a number >= 0
+TrgStatus field_check_models(TrgEngine *e, int32_t m, const TrgFieldModel *models) {
+  for (int k = 0; models && k < m; ++k) {
+    if (!(models[k].safety_factor >= 0.0f) || std::isinf(models[k].safety_factor))
+      return e->fail(TRG_ERR_INVALID_ARG, "cost field: the safety factor of field " + std::to_string(k) +
+                                              " is negative or not finite");
+    if (!(models[k].max_weight >= 0.0f))
+      return e->fail(TRG_ERR_INVALID_ARG, "cost field: the risk ceiling of field " + std::to_string(k) +
+                                              " is negative or not a number");
+  }
+  return TRG_OK;
+}
+
 // the request members that every entry with targets sets, by name
 FieldRequest field_request(int32_t m, float *cost, int32_t *hops, int32_t *parent, const int32_t *targets,
                            int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *reached_out) {
@@ -944,10 +1059,20 @@ TrgStatus trg_engine_cost_field_sets(TrgEngine *e, int32_t m, const int32_t *set
                                      int32_t *owner, const int32_t *targets, int32_t n_targets, float *cost_at,
                                      int32_t *hops_at, int32_t *owner_at, int32_t *owned, int32_t *reached_out,
                                      float *bound_out, TrgFieldInfo *info) {
+  return trg_engine_cost_field_models(e, m, nullptr, set_ptr, set_ids, budget, settle, cost, hops, parent, owner,
+                                      targets, n_targets, cost_at, hops_at, owner_at, owned, reached_out, bound_out, info);
+}
+
+TrgStatus trg_engine_cost_field_models(TrgEngine *e, int32_t m, const TrgFieldModel *models, const int32_t *set_ptr,
+                                       const int32_t *set_ids, const float *budget, int32_t settle, float *cost,
+                                       int32_t *hops, int32_t *parent, int32_t *owner, const int32_t *targets,
+                                       int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
+                                       int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info) {
   return field_entry(e, info, "cost field sets", [&](TrgFieldInfo *out) {
     const char *no_sets = !set_ptr || !set_ids ? "null set_ptr or set_ids" : nullptr;
     if (const TrgStatus st = field_check_shape(e, "cost field sets", "sets", m, n_targets, no_sets); st != TRG_OK)
       return st;
+    if (const TrgStatus st = field_check_models(e, m, models); st != TRG_OK) return st;
     if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
     FieldRequest rq = field_request(m, cost, hops, parent, targets, n_targets, cost_at, hops_at, reached_out);
     rq.budget = budget;
@@ -958,6 +1083,7 @@ TrgStatus trg_engine_cost_field_sets(TrgEngine *e, int32_t m, const int32_t *set
     rq.owner = owner;
     rq.owner_at = owner_at;
     rq.owned = owned;
+    rq.models = models;
     return field_solve(e, rq, out);
   });
 }

@@ -53,6 +53,12 @@
 // cuts every key pass 1 changed, so that the hops pass 2 starts from are those of tight walks.  The relaxation
 // kernels know nothing of this.
 //
+// Cost models ("Cost models"): the fields of a solve need not price an edge alike -- nothing in
+// the argument above asks the copies of the union to carry the same costs.  The costs of a solve's distinct models
+// lie in slots of one array; the four kernels that read an edge cost (relax, parent sweep, route walk, warm seed)
+// have a MODELS instantiation that takes the slot from the item's field, one table read per queued item or route.
+// A solve whose fields share one model runs the plain instantiations on that slot.
+//
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"
 
@@ -110,10 +116,22 @@ __device__ __forceinline__ unsigned field_bound(const FieldDev &F, int i) {
   return F.ctrl->bound[(unsigned)i / (unsigned)F.V];
 }
 
+// what a kernel with a MODELS parameter takes last: the slot table, or nothing
+struct FieldNoModels {};
+template <bool MODELS>
+using FieldModelsArg = std::conditional_t<MODELS, FieldModels, FieldNoModels>;
+
+// the edge costs that field f reads
+template <bool MODELS>
+__device__ __forceinline__ const float *field_costs(const FieldDev &F, const FieldModelsArg<MODELS> &M, int f) {
+  if constexpr (MODELS) return F.ec + (long long)M.slot[f] * M.stride;
+  else return F.ec;
+}
+
 __global__ __launch_bounds__(THREADS) void k_field_edge_cost(const int *__restrict__ col, const float *__restrict__ w,
                                                              const float *__restrict__ dist,
                                                              const int *__restrict__ state, int V, int E, float sf,
-                                                             float *__restrict__ ec, FieldEdgeStats *st) {
+                                                             float tau, float *__restrict__ ec, FieldEdgeStats *st) {
   double sum = 0.0;
   int cnt = 0, bad = 0;
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < E; k += gridDim.x * blockDim.x) {
@@ -122,6 +140,7 @@ __global__ __launch_bounds__(THREADS) void k_field_edge_cost(const int *__restri
     const int v = col[k];
     bool skip = v < 0 || v >= V;
     if (!skip) skip = state[v] == FIELD_NODE_INVALID;
+    skip = skip || w[k] > tau;  // (the ceiling; +inf: no weight is above it)
     ec[k] = skip ? __uint_as_float(FIELD_EDGE_SKIP) : c;
     if (!skip) {
       sum += (double)c;
@@ -191,8 +210,10 @@ __global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources
 // MULTI: more than one field (an item is decoded into its field's first item and its node); else item == node.
 // BOUNDED: pass 1 of a bounded solve -- an item above its field's bound is not expanded (it was queued before the
 // settle step lowered the bound), an extension above the bound is neither written nor pushed.
-template <bool MULTI, bool BOUNDED>
-__global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, int stamp) {
+// MODELS (with MULTI): the edge costs are those of the item's field.
+template <bool MULTI, bool BOUNDED, bool MODELS>
+__global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, int stamp, FieldModelsArg<MODELS> M) {
+  static_assert(MULTI || !MODELS, "one field has one model: the host points F.ec at its slot");
   const int N = MULTI ? F.N : F.V;
   const int n = min(F.ctrl->c.n[par], N);  // (past N only after an overflow, which the host then reports)
   if (n == 0) return;
@@ -215,6 +236,7 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
     int k = 0, kend = 0;
     int fbase = 0;  // the first item of the queued item's field
     unsigned bnd = 0;  // (BOUNDED) that field's bound
+    const float *__restrict__ ec = F.ec;
     if (item < n) {
       const int iu = q_cur[item];
       ku = F.key[iu];
@@ -225,6 +247,7 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
         fbase = f * F.V;
         u = iu - fbase;
       }
+      ec = field_costs<MODELS>(F, M, f);
       if constexpr (BOUNDED) bnd = F.ctrl->bound[f];
       if (!BOUNDED || key_cost_bits(ku) <= bnd) {
         k = F.rowptr[u] + sub;
@@ -237,7 +260,7 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
       bool to_near = false, to_far = false;
       int v = 0;
       if (act) {
-        const float c = F.ec[k];
+        const float c = ec[k];
         if (__float_as_uint(c) != FIELD_EDGE_SKIP) {
           v = F.col[k];
           if constexpr (MULTI) v += fbase;  // the target item: an edge never leaves its field
@@ -464,7 +487,9 @@ __global__ __launch_bounds__(THREADS) void k_field_list_emit(FieldDev F, int fie
 }
 
 // Parents: the smallest u with an edge u -> v whose extension of key[u] is key[v], in each field (grid.y).
-__global__ __launch_bounds__(THREADS) void k_field_parent(FieldDev F) {
+template <bool MODELS>
+__global__ __launch_bounds__(THREADS) void k_field_parent(FieldDev F, FieldModelsArg<MODELS> M) {
+  const float *__restrict__ ec = field_costs<MODELS>(F, M, blockIdx.y);
   const int sub = threadIdx.x & (GROUP - 1);
   const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
   const int ng = gridDim.x * blockDim.x / GROUP;
@@ -473,7 +498,7 @@ __global__ __launch_bounds__(THREADS) void k_field_parent(FieldDev F) {
     const unsigned long long ku = F.key[fbase + u];
     if (ku == FIELD_KEY_NONE) continue;
     for (int k = F.rowptr[u] + sub, kend = F.rowptr[u + 1]; k < kend; k += GROUP) {
-      const float c = F.ec[k];
+      const float c = ec[k];
       if (__float_as_uint(c) == FIELD_EDGE_SKIP) continue;
       const int v = fbase + F.col[k];
       if (key_extend(ku, c) == F.key[v]) atomicMin(&F.parent[v], u);
@@ -551,15 +576,16 @@ __global__ __launch_bounds__(THREADS) void k_field_route_len(FieldDev F, const i
 // host turns into an error, instead of a route that looks right.
 // Where it must end is all that SETS changes: at the field's source S.id[field], or, for a set solve (S its sets,
 // the owner pass has run), at the member that owns the target, ids[ptr[field] + owner[target]].  The single-source
-// instantiation has no owner array to read.
-template <bool SETS>
+// instantiation has no owner array to read.  MODELS: the edge costs are those of the route's field.
+template <bool SETS, bool MODELS>
 __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const float *__restrict__ w,
                                                               const float *__restrict__ dist,
                                                               const int *__restrict__ route_field,
                                                               const int *__restrict__ route_target, int n_routes,
                                                               const int *__restrict__ offsets, int *node_ids,
                                                               FieldRouteInfo *infos,
-                                                              std::conditional_t<SETS, FieldSets, FieldSources> S) {
+                                                              std::conditional_t<SETS, FieldSets, FieldSources> S,
+                                                              FieldModelsArg<MODELS> M) {
   const int V = F.V;
   const int sub = threadIdx.x & (GROUP - 1);
   const int gshift = lane_id() & ~(GROUP - 1);  // the group's first lane within the wave
@@ -567,6 +593,7 @@ __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const 
   const int ng = gridDim.x * blockDim.x / GROUP;
   for (int r = g0; r < n_routes; r += ng) {
     const int fbase = route_field[r] * V;
+    const float *__restrict__ ec = field_costs<MODELS>(F, M, route_field[r]);
     int v = route_target[r];
     unsigned long long kv = F.key[fbase + v];
     FieldRouteInfo out;
@@ -594,7 +621,7 @@ __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const 
           const int k = k0 + sub;
           bool hit = false;
           if (k < kend && F.col[k] == v) {
-            const float c = F.ec[k];
+            const float c = ec[k];
             hit = __float_as_uint(c) != FIELD_EDGE_SKIP && key_extend(ku, c) == kv;
           }
           const unsigned hits = (unsigned)(ballot(hit) >> gshift) & ((1u << GROUP) - 1u);
@@ -785,9 +812,10 @@ __global__ __launch_bounds__(THREADS) void k_field_warm_init(FieldDev F, float d
 
 // The seeding sweep of a warm pass: one 16-lane group per item, four per wave, as k_field_relax -- but over every
 // item with a key, writing no key: an item one of whose edges would improve its target is pushed, once, to far
-// pile 0, stamped with phase 1.  TIGHT: pass 2, tight edges only.
-template <bool MULTI, bool TIGHT>
-__global__ __launch_bounds__(THREADS) void k_field_warm_seed(FieldDev F) {
+// pile 0, stamped with phase 1.  TIGHT: pass 2, tight edges only.  MODELS: as k_field_relax's.
+template <bool MULTI, bool TIGHT, bool MODELS>
+__global__ __launch_bounds__(THREADS) void k_field_warm_seed(FieldDev F, FieldModelsArg<MODELS> M) {
+  static_assert(MULTI || !MODELS, "one field has one model: the host points F.ec at its slot");
   const int N = MULTI ? F.N : F.V;
   const int sub = threadIdx.x & (GROUP - 1);
   const int gw = lane_id() / GROUP;
@@ -800,12 +828,15 @@ __global__ __launch_bounds__(THREADS) void k_field_warm_seed(FieldDev F) {
     unsigned long long ku = 0;
     int k = 0, kend = 0;
     int fbase = 0;
+    const float *__restrict__ ec = F.ec;
     if (iu < N) {
       ku = F.key[iu];
       int u = iu;
       if constexpr (MULTI) {
-        fbase = (int)((unsigned)iu / (unsigned)F.V) * F.V;
+        const int f = (int)((unsigned)iu / (unsigned)F.V);
+        fbase = f * F.V;
         u = iu - fbase;
+        ec = field_costs<MODELS>(F, M, f);
       }
       if (ku != FIELD_KEY_NONE) {
         k = F.rowptr[u] + sub;
@@ -817,7 +848,7 @@ __global__ __launch_bounds__(THREADS) void k_field_warm_seed(FieldDev F) {
       const bool act = k < kend;
       if (ballot(act) == 0) break;  // (wave-uniform: the longest row of the wave's four)
       if (act) {
-        const float c = F.ec[k];
+        const float c = ec[k];
         if (__float_as_uint(c) != FIELD_EDGE_SKIP) {
           int v = F.col[k];
           if constexpr (MULTI) v += fbase;
@@ -845,13 +876,18 @@ int field_blocks(long long items, int per_block) {
 
 // one round's launches; the settle step only under bounds with a settle mode
 template <bool BOUNDED>
-void field_round(const FieldDev &F, int round, const FieldSettle *settle, hipStream_t s) {
+void field_round(const FieldDev &F, int round, const FieldSettle *settle, const FieldModels *models, hipStream_t s) {
   const int par = round & 1;
   const dim3 relax_grid(field_blocks((long long)F.N * GROUP, THREADS));
   if (F.m == 1)
-    hipLaunchKernelGGL((k_field_relax<false, BOUNDED>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+    hipLaunchKernelGGL((k_field_relax<false, BOUNDED, false>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1,
+                       FieldNoModels{});
+  else if (!models)
+    hipLaunchKernelGGL((k_field_relax<true, BOUNDED, false>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1,
+                       FieldNoModels{});
   else
-    hipLaunchKernelGGL((k_field_relax<true, BOUNDED>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1);
+    hipLaunchKernelGGL((k_field_relax<true, BOUNDED, true>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1,
+                       *models);
   hipLaunchKernelGGL(k_field_far_min<BOUNDED>, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, par);
   if (BOUNDED && settle->mode != FIELD_SETTLE_NONE)
     hipLaunchKernelGGL(k_field_settle, dim3(F.m), dim3(THREADS), 0, s, F, par, settle->targets, settle->n_t,
@@ -863,11 +899,11 @@ void field_round(const FieldDev &F, int round, const FieldSettle *settle, hipStr
 }  // namespace
 
 void launch_field_edge_cost(const int *col, const float *w, const float *dist, const int *state, int V, int E,
-                            float safety_factor, float *ec, FieldEdgeStats *st, hipStream_t s) {
+                            float safety_factor, float max_weight, float *ec, FieldEdgeStats *st, hipStream_t s) {
   (void)hipMemsetAsync(st, 0, sizeof(FieldEdgeStats), s);
   if (E == 0) return;
   hipLaunchKernelGGL(k_field_edge_cost, dim3(field_blocks(E, THREADS * 8)), dim3(THREADS), 0, s, col, w, dist,
-                     state, V, E, safety_factor, ec, st);
+                     state, V, E, safety_factor, max_weight, ec, st);
 }
 
 void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets,
@@ -877,11 +913,12 @@ void launch_field_init(const FieldDev &F, const FieldSources &sources, const Fie
   if (sets) hipLaunchKernelGGL(k_field_seed, dim3(field_blocks(sets->n, THREADS)), dim3(THREADS), 0, s, F, *sets);
 }
 
-void launch_field_round(const FieldDev &F, int round, hipStream_t s, const FieldSettle *under_bounds) {
+void launch_field_round(const FieldDev &F, int round, hipStream_t s, const FieldSettle *under_bounds,
+                        const FieldModels *models) {
   if (under_bounds)
-    field_round<true>(F, round, under_bounds, s);
+    field_round<true>(F, round, under_bounds, models, s);
   else
-    field_round<false>(F, round, nullptr, s);
+    field_round<false>(F, round, nullptr, models, s);
 }
 
 void launch_field_bounds(const FieldDev &F, const FieldBounds &budgets, hipStream_t s) {
@@ -905,8 +942,9 @@ void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s) {
   hipLaunchKernelGGL(k_field_cost_bits, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, bits);
 }
 
-void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents, hipStream_t s) {
-  if (parents) launch_field_supporters(F, s);
+void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents, hipStream_t s,
+                         const FieldModels *models) {
+  if (parents) launch_field_supporters(F, s, models);
   hipLaunchKernelGGL(k_field_output, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, cost, hops);
 }
 
@@ -918,10 +956,10 @@ void launch_field_gather(const FieldDev &F, const FieldSets *sets, const int *ta
                      cost_at, hops_at, owner, owner ? owner_at : nullptr);
 }
 
-void launch_field_parents_late(const FieldDev &F, hipStream_t s) {
+void launch_field_parents_late(const FieldDev &F, hipStream_t s, const FieldModels *models) {
   const dim3 grid(field_blocks(F.N, THREADS));
   hipLaunchKernelGGL(k_field_parent_mark, grid, dim3(THREADS), 0, s, F, -1, INT_MAX);
-  launch_field_supporters(F, s);
+  launch_field_supporters(F, s, models);
   hipLaunchKernelGGL(k_field_parent_mark, grid, dim3(THREADS), 0, s, F, INT_MAX, -1);
 }
 
@@ -935,15 +973,21 @@ void launch_field_route_len(const FieldDev &F, const int *route_field, const int
 void launch_field_route_walk(const FieldDev &F, const float *w, const float *dist, const int *route_field,
                              const int *route_target, int n_routes, const int *offsets, int *node_ids,
                              FieldRouteInfo *infos, const FieldSources &sources, const FieldSets *sets,
-                             hipStream_t s) {
+                             hipStream_t s, const FieldModels *models) {
   if (n_routes <= 0) return;
   const dim3 grid(field_blocks((long long)n_routes * GROUP, THREADS));
-  if (sets)
-    hipLaunchKernelGGL(k_field_route_walk<true>, grid, dim3(THREADS), 0, s, F, w, dist, route_field, route_target,
-                       n_routes, offsets, node_ids, infos, *sets);
+  if (sets && models)
+    hipLaunchKernelGGL((k_field_route_walk<true, true>), grid, dim3(THREADS), 0, s, F, w, dist, route_field,
+                       route_target, n_routes, offsets, node_ids, infos, *sets, *models);
+  else if (sets)
+    hipLaunchKernelGGL((k_field_route_walk<true, false>), grid, dim3(THREADS), 0, s, F, w, dist, route_field,
+                       route_target, n_routes, offsets, node_ids, infos, *sets, FieldNoModels{});
+  else if (models)
+    hipLaunchKernelGGL((k_field_route_walk<false, true>), grid, dim3(THREADS), 0, s, F, w, dist, route_field,
+                       route_target, n_routes, offsets, node_ids, infos, sources, *models);
   else
-    hipLaunchKernelGGL(k_field_route_walk<false>, grid, dim3(THREADS), 0, s, F, w, dist, route_field, route_target,
-                       n_routes, offsets, node_ids, infos, sources);
+    hipLaunchKernelGGL((k_field_route_walk<false, false>), grid, dim3(THREADS), 0, s, F, w, dist, route_field,
+                       route_target, n_routes, offsets, node_ids, infos, sources, FieldNoModels{});
 }
 
 void launch_field_owner_sweep(const FieldDev &F, int sweep, int *changed, hipStream_t s) {
@@ -962,8 +1006,10 @@ void launch_field_carry(const unsigned long long *old_key, int V_old, const int 
                      out);
 }
 
-void launch_field_supporters(const FieldDev &F, hipStream_t s) {
-  hipLaunchKernelGGL(k_field_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s, F);
+void launch_field_supporters(const FieldDev &F, hipStream_t s, const FieldModels *models) {
+  const dim3 grid(field_blocks((long long)F.V * GROUP, THREADS), F.m);
+  if (models) hipLaunchKernelGGL(k_field_parent<true>, grid, dim3(THREADS), 0, s, F, *models);
+  else hipLaunchKernelGGL(k_field_parent<false>, grid, dim3(THREADS), 0, s, F, FieldNoModels{});
 }
 
 void launch_field_forest_begin(const FieldDev &F, const FieldSources *single, const unsigned long long *key0,
@@ -979,16 +1025,21 @@ void launch_field_anchor_end(const FieldDev &F, int sweeps, unsigned long long *
                      F.q[sweeps & 1], key0, carried);
 }
 
-void launch_field_warm_start(const FieldDev &F, float delta, bool reset_parents, hipStream_t s) {
+void launch_field_warm_start(const FieldDev &F, float delta, bool reset_parents, hipStream_t s,
+                             const FieldModels *models) {
   hipLaunchKernelGGL(k_field_warm_init, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, delta,
                      reset_parents);
   const dim3 grid(field_blocks((long long)F.N * GROUP, THREADS));
+  const FieldNoModels none{};
   if (F.m == 1) {
-    if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<false, true>), grid, dim3(THREADS), 0, s, F);
-    else hipLaunchKernelGGL((k_field_warm_seed<false, false>), grid, dim3(THREADS), 0, s, F);
+    if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<false, true, false>), grid, dim3(THREADS), 0, s, F, none);
+    else hipLaunchKernelGGL((k_field_warm_seed<false, false, false>), grid, dim3(THREADS), 0, s, F, none);
+  } else if (!models) {
+    if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<true, true, false>), grid, dim3(THREADS), 0, s, F, none);
+    else hipLaunchKernelGGL((k_field_warm_seed<true, false, false>), grid, dim3(THREADS), 0, s, F, none);
   } else {
-    if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<true, true>), grid, dim3(THREADS), 0, s, F);
-    else hipLaunchKernelGGL((k_field_warm_seed<true, false>), grid, dim3(THREADS), 0, s, F);
+    if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<true, true, true>), grid, dim3(THREADS), 0, s, F, *models);
+    else hipLaunchKernelGGL((k_field_warm_seed<true, false, true>), grid, dim3(THREADS), 0, s, F, *models);
   }
 }
 

@@ -430,6 +430,13 @@ constexpr int FIELD_SETTLE_ALL = 2;
 struct FieldSources {
   int id[FIELD_MAX_SOURCES];
 };
+// Cost models ("Cost models"): the edge costs of a solve whose fields do not all price an edge
+// alike lie in one array of slots, slot * stride + e, one slot per distinct model; field k reads slot[k].  F.ec is
+// slot 0's first entry.  A solve whose fields share one slot gets no table: its F.ec points at that slot.
+struct FieldModels {
+  long long stride;  // entries from one slot to the next
+  int slot[FIELD_MAX_SOURCES];
+};
 // Source sets ("Source sets"), which a solve may take in place of single sources: field k
 // starts from every member of set k = ids[ptr[k] .. ptr[k + 1]) at key (0, 0) instead of from one node.
 // An entry is an index into ids; the owner of an item is an entry of its field's set, counted from ptr[k].
@@ -459,8 +466,10 @@ struct FieldDev {
   const unsigned *tight;       // pass 2: the least costs of pass 1 (bits), per item; only edges with
                                // fl(cost[u] + c) == cost[v] are relaxed.  nullptr in pass 1.
 };
+// ec[e] = (safety_factor * w[e] + 1) * dist[e], FIELD_EDGE_SKIP for an edge that is not relaxable or whose weight
+// is above max_weight (+inf: none is); *st (zeroed here) over the edges that got a cost, its bad flag over all.
 void launch_field_edge_cost(const int *col, const float *w, const float *dist, const int *state, int V, int E,
-                            float safety_factor, float *ec, FieldEdgeStats *st, hipStream_t s);
+                            float safety_factor, float max_weight, float *ec, FieldEdgeStats *st, hipStream_t s);
 // Field k starts at node sources.id[k], k < F.m (duplicates give identical fields).  With `sets` (a set solve; else
 // nullptr) sources is not read: every item is left without a key, then a second launch seeds every distinct member
 // item and pushes it once to near queue 0; F.ctrl's queue size and work are the count of distinct member items.
@@ -482,7 +491,9 @@ struct FieldSettle {
 // ANY / ALL, a round that opens a bucket or converges lowers the bound of every field whose targets are settled --
 // some (ANY) or all (ALL) of them have a key below the least live far cost -- to the least (greatest) of those
 // costs.
-void launch_field_round(const FieldDev &F, int round, hipStream_t s, const FieldSettle *under_bounds = nullptr);
+// models (here and below; nullptr: every field reads F.ec): the slot table of a solve with more than one cost model.
+void launch_field_round(const FieldDev &F, int round, hipStream_t s, const FieldSettle *under_bounds = nullptr,
+                        const FieldModels *models = nullptr);
 // F.ctrl->bound[k] = budgets.bits[k], before the first round of a bounded solve
 void launch_field_bounds(const FieldDev &F, const FieldBounds &budgets, hipStream_t s);
 // after the last round of pass 1: keys above their field's bound become FIELD_KEY_NONE
@@ -497,7 +508,8 @@ void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s);
 // parents (smallest id among the edges that realise an item's key; only if `parents`) and the outputs, m x V
 // each: cost (+inf), hops (-1) and parent (-1) of unreached items; F.ctrl->reached[k] counts field k's reached
 // nodes
-void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents, hipStream_t s);
+void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents, hipStream_t s,
+                         const FieldModels *models = nullptr);
 // the finished keys at n_t target nodes: cost_at / hops_at[k * n_t + j] of (field k, targets[j]), +inf and
 // -1 where unreached; of a set solve whose owner pass ran (`sets`, else nullptr) owner_at likewise, sets->owner of
 // (field k, targets[j]).  Any output may be nullptr.
@@ -510,7 +522,7 @@ struct FieldRouteInfo {
 };
 constexpr int FIELD_ROUTE_BROKEN = -1;  // num_nodes of a walk that did not end at its field's source
 // the parent sweep of a finished solve whose launch_field_finish ran without `parents`: F.parent as with it
-void launch_field_parents_late(const FieldDev &F, hipStream_t s);
+void launch_field_parents_late(const FieldDev &F, hipStream_t s, const FieldModels *models = nullptr);
 // len[r] = hops + 1 of (field route_field[r], node route_target[r]), 0 where unreached
 void launch_field_route_len(const FieldDev &F, const int *route_field, const int *route_target, int n_routes,
                             int *len, hipStream_t s);
@@ -522,7 +534,7 @@ void launch_field_route_len(const FieldDev &F, const int *route_field, const int
 void launch_field_route_walk(const FieldDev &F, const float *w, const float *dist, const int *route_field,
                              const int *route_target, int n_routes, const int *offsets, int *node_ids,
                              FieldRouteInfo *infos, const FieldSources &sources, const FieldSets *sets,
-                             hipStream_t s);
+                             hipStream_t s, const FieldModels *models = nullptr);
 
 // ---- the owner pass of a set solve ("Source sets") -------------------------------------
 constexpr int FIELD_OWNER_SWEEPS_MAX = 40;  // pointer jumping doubles: 2^31 hops need 31 sweeps and one that finds nothing
@@ -549,7 +561,7 @@ void launch_field_carry(const unsigned long long *old_key, int V_old, const int 
 // F.parent[item] = the item's supporter under the keys as they are: the smallest u with an edge u -> v and
 // key_extend(key[u], c) == key[v], INT_MAX without one: the parent sweep, which launch_field_finish and
 // launch_field_parents_late run through this
-void launch_field_supporters(const FieldDev &F, hipStream_t s);
+void launch_field_supporters(const FieldDev &F, hipStream_t s, const FieldModels *models = nullptr);
 // The anchor: an item keeps its key if its chain of supporters (F.parent) ends at a source.  begin:
 // launch_field_forest_begin; then launch_field_owner_sweep until a sweep moves nothing; end: every item whose last
 // ancestor is no source loses its key, key0 (may be nullptr) gets the keys after that and carried[k] (may be nullptr;
@@ -559,6 +571,7 @@ void launch_field_anchor_end(const FieldDev &F, int sweeps, unsigned long long *
 // empty, and in far pile 0 every item with a key one of whose edges (F.tight set: tight edges) improves its target.
 // launch_field_round from round 0 on then runs to the same fixed point as a pass from launch_field_init, provided
 // every key is one that a walk of the graph has.  reset_parents: F.parent = INT_MAX, for the last parent sweep.
-void launch_field_warm_start(const FieldDev &F, float delta, bool reset_parents, hipStream_t s);
+void launch_field_warm_start(const FieldDev &F, float delta, bool reset_parents, hipStream_t s,
+                             const FieldModels *models = nullptr);
 
 }  // namespace trg

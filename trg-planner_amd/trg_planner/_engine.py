@@ -65,6 +65,10 @@ class TrgRouteInfo(C.Structure):
                 ("avg_risk", C.c_float)]
 
 
+class TrgFieldModel(C.Structure):
+    _fields_ = [("safety_factor", C.c_float), ("max_weight", C.c_float)]
+
+
 class TrgStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "map_points", "expanded_nodes", "trials", "samples", "created_nodes", "invalid_nodes",
@@ -103,7 +107,7 @@ EXPORTS = [
     "trg_engine_comm_unique_id", "trg_engine_comm_init", "trg_engine_comm_adopt", "trg_engine_comm_destroy",
     "trg_engine_stitch_exchange", "trg_engine_cost_field", "trg_engine_cost_field_batch",
     "trg_engine_field_routes", "trg_engine_cost_field_bounded", "trg_engine_field_reached",
-    "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh",
+    "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh", "trg_engine_cost_field_models",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -199,6 +203,8 @@ def load_library():
     L.trg_engine_field_reached.argtypes = [vp, C.c_int32, ip, fp, ip, C.c_int32, ip, C.POINTER(TrgFieldInfo)]
     L.trg_engine_cost_field_sets.argtypes = [vp, C.c_int32, ip, ip, fp, C.c_int32, fp, ip, ip, ip, ip, C.c_int32, fp, ip,
                                              ip, ip, ip, fp, C.POINTER(TrgFieldInfo)]
+    L.trg_engine_cost_field_models.argtypes = [vp, C.c_int32, C.POINTER(TrgFieldModel), ip, ip, fp, C.c_int32, fp, ip,
+                                               ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, fp, C.POINTER(TrgFieldInfo)]
     L.trg_engine_cost_field_refresh.argtypes = [vp, ip, C.c_int32, fp, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, ip, ip,
                                                 C.POINTER(TrgFieldInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
@@ -524,7 +530,28 @@ class Engine:
                   "budget": None if bud is None else _f(bud), "bound": arg("bound", _f)}
         return out, groups
 
-    def cost_fields(self, sources_xy=None, source_ids=None, targets=None, full=True, budget=None, settle=None):
+    def _models(self, who, models, m):
+        """`models` of cost_fields / cost_fields_from as the C entry's array: m entries, each None (the engine's
+        model), a safety factor (no ceiling) or (safety_factor, max_risk) -> (TrgFieldModel * m, the (m, 2) float32
+        pairs)."""
+        models = list(models)
+        if len(models) != m:
+            raise ValueError(f"{who}: {len(models)} models for {m} fields")
+        pairs = np.empty((m, 2), np.float32)
+        for k, one in enumerate(models):
+            if one is None:
+                pairs[k] = self.params.safety_factor, np.inf
+            elif np.ndim(one) == 0:
+                pairs[k] = one, np.inf
+            else:
+                pairs[k] = one
+        arr = (TrgFieldModel * max(m, 1))()
+        for k in range(m):
+            arr[k] = TrgFieldModel(float(pairs[k, 0]), float(pairs[k, 1]))
+        return arr, pairs
+
+    def cost_fields(self, sources_xy=None, source_ids=None, targets=None, full=True, budget=None, settle=None,
+                    models=None):
         """m cost fields in one solve on the GPU (trg_engine_cost_field_batch; each field as cost_field's).
         Field k starts at source_ids[k], or, where source_ids is None or source_ids[k] == -1, at the node
         planSafePath starts from for sources_xy[k].  -> dict: with `full`, the (m, V) arrays "cost", "hops",
@@ -535,7 +562,11 @@ class Engine:
         m costs, and `settle`, "any" or "all" over `targets`, truncate field k at bound[k] = min(budget[k], the least
         ("any") or greatest ("all") cost of field k over the targets): every node dearer than the bound comes back
         as unreached, every other node exactly as in the full field, and the solve stops early.  With either
-        given the result also has "bound" (m float32)."""
+        given the result also has "bound" (m float32).
+        Cost models (trg_engine_cost_field_models; DESIGN.md section 2, "Cost models"): `models`, m entries, each
+        None (the engine's model), a safety factor, or (safety_factor, max_risk) -- field k prices an edge with its
+        own safety factor and uses no edge of weight above max_risk.  The sources are resolved first (no solve), then
+        every field runs as a set of one; the result also has "models", the (m, 2) float32 pairs as solved."""
         if sources_xy is None and source_ids is None:
             raise ValueError("cost_fields needs sources_xy or source_ids")
         ids = None if source_ids is None else np.ascontiguousarray(source_ids, dtype=np.int32).reshape(-1)
@@ -544,8 +575,22 @@ class Engine:
         out, a = self._field_outputs("cost_fields", m, targets, full, budget, settle)
         if ids is not None and xy is not None and xy.shape[0] != m:
             raise ValueError("cost_fields: sources_xy and source_ids differ in length")
-        out["sources"] = np.full(m, -1, np.int32)
         info = TrgFieldInfo()
+        if models is not None:
+            marr, out["models"] = self._models("cost_fields", models, m)
+            nodes = np.full(m, -1, np.int32)
+            self._chk(self.L.trg_engine_cost_field_batch(self.h, m, None if ids is None else _i(ids),
+                                                         None if xy is None else _f(xy), None, None, None, None, 0,
+                                                         None, None, _i(nodes), None, None))
+            ptr = np.arange(m + 1, dtype=np.int32)
+            self._chk(self.L.trg_engine_cost_field_models(
+                self.h, m, marr, _i(ptr), _i(nodes), a["budget"], _SETTLE[settle], *a["full"], None, *a["at"], None,
+                None, a["reached"], a["bound"], C.byref(info)))
+            self._field_shape = (m, False)
+            out["sources"] = nodes
+            out["info"] = info
+            return out
+        out["sources"] = np.full(m, -1, np.int32)
         # the bounded entry's arguments; the batch entry's are these without budget, settle and bound_out
         sources = [self.h, m, None if ids is None else _i(ids), None if xy is None else _f(xy)]
         outputs = [*a["full"], *a["at"], _i(out["sources"]), a["reached"]]
@@ -633,8 +678,18 @@ class Engine:
         with `targets` -- the index into sets[k] of the member a node's route starts from, -1 where unreached --
         "owned" (a list of m int32 arrays: nodes per entry of sets[k]) and "sets" (the m int32 arrays as solved);
         "sources" is every set's first id."""
+        return self._cost_fields_from(sets, None, targets, full, budget, settle)
+
+    def cost_fields_from_models(self, sets, models, targets=None, full=True, budget=None, settle=None):
+        """cost_fields_from with a cost model per field (trg_engine_cost_field_models; DESIGN.md section 2, "Cost
+        models"): `models` as cost_fields', m entries or None.  The result also has "models", the (m, 2) float32 pairs
+        as solved."""
+        return self._cost_fields_from(sets, models, targets, full, budget, settle)
+
+    def _cost_fields_from(self, sets, models, targets, full, budget, settle):
         sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
         m = len(sets)
+        marr, pairs = (None, None) if models is None else self._models("cost_fields_from_models", models, m)
         out, a = self._field_outputs("cost_fields_from", m, targets, full, budget, settle, owners=True)
         ptr = np.zeros(m + 1, np.int64)
         np.cumsum([s.shape[0] for s in sets], out=ptr[1:])
@@ -644,9 +699,13 @@ class Engine:
         ids = np.ascontiguousarray(np.concatenate(sets) if m else np.empty(0, np.int32), dtype=np.int32)
         owned = np.zeros(max(int(ptr[-1]), 1), np.int32)
         info = TrgFieldInfo()
-        self._chk(self.L.trg_engine_cost_field_sets(
-            self.h, m, _i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
-            _i(owned), a["reached"], a["bound"], C.byref(info)))
+        tail = [_i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
+                _i(owned), a["reached"], a["bound"], C.byref(info)]
+        if marr is None:
+            self._chk(self.L.trg_engine_cost_field_sets(self.h, m, *tail))
+        else:
+            self._chk(self.L.trg_engine_cost_field_models(self.h, m, marr, *tail))
+            out["models"] = pairs
         self._field_shape = (m, True)
         out["owned"] = [owned[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
         out["sets"] = sets
@@ -785,6 +844,69 @@ class Engine:
         if early_exit and goals.shape[0]:  # (the goals are the settle targets: resolved first)
             self.cost_fields(sources_xy=start, targets=nodes, full=False, settle="all")
         return [(pts, one) for _, pts, one in self.routes(np.zeros(nodes.shape[0], np.int32), nodes)]
+
+    def _route_record(self, model, ids, xyz, one):
+        """One route of plan_tradeoff / min_risk_ceiling as a dict."""
+        return {"model": (float(model[0]), float(model[1])), "reachable": one.num_nodes > 0, "ids": ids, "xyz": xyz,
+                "cost": float(one.cost), "path_length": float(one.path_length), "avg_risk": float(one.avg_risk)}
+
+    def plan_tradeoff(self, start_xy, goal_xy, models, early_exit=True):
+        """The same start-to-goal query under several cost models (each None, a safety factor, or (safety_factor,
+        max_risk), as cost_fields'): one field per model from the node planSafePath starts from for `start_xy`, in ONE
+        solve, the goal resolved to a node as plan_many resolves it, the routes walked on the device.  early_exit:
+        every field stops once the goal is settled in it (settle "any"); the result is the same.  More than
+        TRG_FIELD_BATCH_MAX models run in chunks.  -> one dict per model: "model" (safety_factor, max_risk),
+        "reachable", "ids" (int32 node ids start .. goal, empty when unreachable), "xyz" (n, 3), "cost" (+inf when
+        unreachable), "path_length", "avg_risk"."""
+        models = list(models)
+        start, goal = (int(v) for v in self._resolve_nodes([np.asarray(start_xy, np.float32).reshape(2),
+                                                            np.asarray(goal_xy, np.float32).reshape(2)]))
+        out = []
+        for k0 in range(0, len(models), TRG_FIELD_BATCH_MAX):
+            part = models[k0:k0 + TRG_FIELD_BATCH_MAX]
+            r = self.cost_fields(source_ids=[start] * len(part), targets=[goal], full=False,
+                                 settle="any" if early_exit else None, models=part)
+            routes = self.routes(np.arange(len(part)), [goal] * len(part), hops_at=r["hops_at"][:, 0])
+            out += [self._route_record(r["models"][k], *routes[k]) for k in range(len(part))]
+        return out
+
+    def min_risk_ceiling(self, start_xy, goal_xy):
+        """The minimax ("safest possible") route: the least ceiling among the graph's distinct edge weights (of edges
+        into valid nodes) under which the goal is reachable from the start, and the route at that ceiling under the
+        engine's safety factor -> (max_risk, route dict as plan_tradeoff's), or None when the goal is unreachable
+        without any ceiling.  Reachability is monotone in the ceiling, so the search is exact: every solve tries up to
+        TRG_FIELD_BATCH_MAX evenly spaced candidates in one batch (settle "any" at the goal), and the interval between
+        the last that fails and the first that succeeds is searched again until it holds one weight.  With goal ==
+        start every ceiling succeeds: the least weight (0 for a graph without such an edge)."""
+        start, goal = (int(v) for v in self._resolve_nodes([np.asarray(start_xy, np.float32).reshape(2),
+                                                            np.asarray(goal_xy, np.float32).reshape(2)]))
+        g = self.graph("global")
+        ok = (g.col >= 0) & (g.col < g.V)
+        ok[ok] = g.state[g.col[ok]] != -1  # TRG_NODE_INVALID
+        ws = np.unique(g.w[ok & ~np.isnan(g.w)])
+        if ws.size == 0:
+            ws = np.zeros(1, np.float32)
+        sf = self.params.safety_factor
+        lo, hi = -1, None  # the greatest index known to fail, the least known to succeed
+        while hi is None or hi - lo > 1:
+            top = ws.size - 1 if hi is None else hi - 1
+            idx = np.unique(np.rint(np.linspace(lo + 1, top, min(TRG_FIELD_BATCH_MAX, top - lo))).astype(np.int64))
+            r = self.cost_fields(source_ids=[start] * idx.size, targets=[goal], full=False, settle="any",
+                                 models=[(sf, ws[i]) for i in idx])
+            good = np.flatnonzero(r["hops_at"][:, 0] >= 0)
+            if good.size == 0:
+                if hi is None:
+                    return None
+                lo = int(idx[-1])
+            else:
+                j = int(good[0])
+                hi = int(idx[j])
+                if j > 0:
+                    lo = int(idx[j - 1])
+        tau = float(ws[hi])
+        r = self.cost_fields(source_ids=[start], targets=[goal], full=False, settle="any", models=[(sf, tau)])
+        route = self.routes([0], [goal], hops_at=r["hops_at"][:, 0])[0]
+        return tau, self._route_record(r["models"][0], *route)
 
     def check_reached(self, pos2d):
         p = np.ascontiguousarray(pos2d, dtype=np.float32)
