@@ -467,6 +467,42 @@ TrgStatus trg_engine_cost_field_models(
     const int32_t *targets, int32_t n_targets,
     float *cost_at, int32_t *hops_at, int32_t *owner_at,
     int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info);
+/* Risk fields ("Risk fields"): for every node, how risky is the worst edge that must be crossed
+ * to get there -- trg_engine_cost_field_sets with max in the place of +, exact, for every node in one solve.
+ * An edge of CSR index e is relaxable exactly as in a cost field (its col a node, and not Invalid); its risk is
+ * r[e] = weight[e] + 0.0f in fp32, so that a weight of -0 counts as +0.  Node v's key is (risk, hops):
+ *   risk[v]    the least, over all walks of relaxable edges from a member of the set (key (+0, 0)) to v, of the
+ *              greatest r[e] on the walk: +0 for a member, +inf (hops -1) when unreachable, always the weight of
+ *              some edge or +0.  max never rounds, so there is no saturation rule.
+ *   hops[v]    with an edge u -> v TIGHT iff it is relaxable, u has a key and max(risk[u], r[e]) == risk[v] as bits:
+ *              the BFS depth of v in the subgraph of tight edges from the members at depth 0 -- what a host Dijkstra on
+ *              the key (risk, hops) with the extension (max(risk, r), hops + 1) computes.  NOT in general the fewest
+ *              hops among all walks that attain risk[v]: such a walk may detour, in its interior, over edges riskier
+ *              than the risk of the node it leaves, and those edges are not tight.
+ *   parent[v]  the smallest u with a tight edge into v and hops[u] + 1 == hops[v]; -1 for members and unreached nodes
+ *   owner, owned, owner_at, reached_out   trg_engine_cost_field_sets' definitions, over these keys
+ *   risk_at, hops_at   m x n_targets, the fields read at `targets` on the device
+ * budget[k] is a CEILING: field k truncated at bound b is the full risk field with every node of risk > b reported
+ * as unreached and the rest untouched; settle ANY / ALL over `targets` lowers the bound as for costs, bound_out gets
+ * it, and the solve stops early as a bounded cost solve does.  A solve is a cost solve or a risk solve, never both in
+ * one batch (their thresholds are in different units), and cost models do not apply: a ceiling here is the budget.
+ * A single source is a set of one; positions are resolved through trg_engine_cost_field_batch's resolve-only call.
+ * The solve is retained like any other.  trg_engine_field_reached answers from it (its cost output is the risk).
+ * trg_engine_field_routes walks the parents; the route edge into p_i is the relaxable edge of least CSR index in row
+ * p_{i-1} with col p_i that is tight and steps the hops by one; TrgRouteInfo.cost is risk[target], path_length and
+ * avg_risk are as for a cost solve.  trg_engine_cost_field_refresh refuses a retained risk solve
+ * (TRG_ERR_INVALID_ARG, the message says so) and leaves it answering routes, as it does for a bounded one.
+ * TRG_ERR_INVALID_ARG when some edge weight is NaN, negative (-0 is not) or infinite -- taken over ALL edges, as the
+ * bad-cost flag of a cost solve is, and like it after the previously retained solve is gone; the other argument,
+ * capacity and device errors are trg_engine_cost_field_sets'. */
+TrgStatus trg_engine_risk_field_sets(
+    TrgEngine *e, int32_t m,
+    const int32_t *set_ptr, const int32_t *set_ids,
+    const float *budget, int32_t settle,
+    float *risk, int32_t *hops, int32_t *parent, int32_t *owner,   /* m x num_nodes each, any may be NULL */
+    const int32_t *targets, int32_t n_targets,
+    float *risk_at, int32_t *hops_at, int32_t *owner_at,           /* m x n_targets, any may be NULL */
+    int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info);
 /* The nodes of field `field` (0 .. m-1) of the retained solve that have a key, compacted on the device: their
  * ids in ascending order with cost and hops, so that a bounded field that reaches few nodes is read without
  * copying anything of num_nodes entries.  *n_out is always the full count; node_ids, cost and hops (room for cap

@@ -3,7 +3,9 @@
 // trg_field.hip; an extension, the reference has no such call) -- and its C ABI entries.  One solver: the
 // single-source entry is its m == 1 call, the batch entry the bounded one's call without budgets or a settle mode;
 // the refresh (trg_engine_cost_field_refresh) is a request of its own kind to the same field_solve: a check phase
-// before the others, the retained keys carried in before the work arrays, and passes that start warm.
+// before the others, the retained keys carried in before the work arrays, and passes that start warm.  A risk field
+// (trg_engine_risk_field_sets; DESIGN.md section 2, "Risk fields") is the set entry's request with one flag: the
+// edge risks in the place of the edge costs, and kernels that extend a key by max instead of +.
 
 namespace {
 
@@ -32,7 +34,7 @@ struct FieldBufs {
   // cost model met, for one graph_version and column array.  Slot 0 is the engine's own model and is never given
   // away; the others go to the model a solve needs and does not find, the least recently used first.
   struct CostSlot {
-    uint32_t sf_bits, tau_bits;  // the model, as bits
+    uint32_t sf_bits, tau_bits;  // the model, as bits; (FIELD_RISK_SLOT, FIELD_RISK_SLOT): the edge risks
     bool valid;                  // the costs and the three words below are computed
     double sum;                  // over admitted edges
     long long count;
@@ -58,6 +60,7 @@ struct FieldBufs {
     std::optional<FieldSets> sets;  // of a set solve ("Source sets"), on the device
     bool owners = false;     // ... and the owner pass ran: sets->owner is filled
     bool bounded = false;    // keys above a bound were removed: nothing a refresh can start from
+    bool risk = false;       // a risk solve ("Risk fields"): F.ec holds the edge risks
     // its cost models ("Cost models"): per field, empty when the request named none; F.ec is
     // the slot all fields share, or with `many` slot 0 and `models` the table the kernels take
     std::vector<TrgFieldModel> pairs;
@@ -91,6 +94,10 @@ void field_release(TrgEngine *e) {
 static_assert(FIELD_MAX_SOURCES == TRG_FIELD_BATCH_MAX, "the kernels' and the header's batch limit differ");
 // the engine's own slot and one per field of the largest batch
 constexpr int FIELD_SLOTS_MAX = FIELD_MAX_SOURCES + 1;
+// The key of the slot that holds the edge risks ("Risk fields"): a NaN pattern in both words,
+// which no model has (field_check_models refuses a NaN).  It is never slot 0, lives and dies with the cache like any
+// other slot (graph_version, column array), and is taken or given away by the same least-recently-used rule.
+constexpr uint32_t FIELD_RISK_SLOT = 0xFFFFFFFFu;
 
 // What an entry asks of field_solve.  Every entry value-initialises one and names what it sets: all else is null, 0,
 // false, TRG_FIELD_SETTLE_NONE.
@@ -122,6 +129,8 @@ struct FieldRequest {
   const int32_t *new2old;  // n_map entries, or nullptr: the engine's map
   int32_t n_map;
   int32_t *carried_out;    // m
+  // a risk solve (trg_engine_risk_field_sets): cost / cost_at / budget / bound_out are risks; never with models
+  bool risk;
 };
 static_assert(TRG_FIELD_SETTLE_NONE == 0, "a value-initialised request has no settle mode");
 
@@ -194,6 +203,9 @@ TrgStatus field_check_refresh(TrgEngine *e, FieldRun &run) {
   FieldBufs::Last *last;
   if (const TrgStatus st = field_retained(e, call, last, false); st != TRG_OK) return st;
   const FieldBufs::Last &old = *last;
+  if (old.risk)
+    return e->fail(TRG_ERR_INVALID_ARG,
+                   call + ": the retained solve is a risk field (a risk field cannot be refreshed)");
   if (old.bounded)
     return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is bounded (a bounded solve cannot be refreshed)");
   if (field_last_current(e, old))
@@ -398,8 +410,9 @@ TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
   const uint64_t tick = ++fb.ec_tick;
   std::vector<int> fresh;  // the slots to compute
   for (int k = 0; k < m; ++k) {
-    const uint32_t sfb = run.rq.models ? float_bits(run.rq.models[k].safety_factor) : sf0;
-    const uint32_t taub = run.rq.models ? float_bits(run.rq.models[k].max_weight) : FIELD_INF_BITS;
+    uint32_t sfb = run.rq.models ? float_bits(run.rq.models[k].safety_factor) : sf0;
+    uint32_t taub = run.rq.models ? float_bits(run.rq.models[k].max_weight) : FIELD_INF_BITS;
+    if (run.rq.risk) sfb = taub = FIELD_RISK_SLOT;  // (every field of a risk solve reads the edge risks)
     int slot = -1;
     for (size_t i = 0; i < fb.slots.size() && slot < 0; ++i)
       if (fb.slots[i].sf_bits == sfb && fb.slots[i].tau_bits == taub) slot = (int)i;
@@ -433,8 +446,12 @@ TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
     FieldEdgeStats *d_stats = fb.stats.as<FieldEdgeStats>();
     for (size_t j = 0; j < fresh.size(); ++j) {
       const FieldBufs::CostSlot &cs = fb.slots[fresh[j]];
-      launch_field_edge_cost(G.col, G.w, G.dist, G.state, run.F.V, G.E, bits_float(cs.sf_bits), bits_float(cs.tau_bits),
-                             fb.ec.as<float>() + (size_t)fresh[j] * stride, d_stats + j, s);
+      float *slot = fb.ec.as<float>() + (size_t)fresh[j] * stride;
+      if (cs.sf_bits == FIELD_RISK_SLOT && cs.tau_bits == FIELD_RISK_SLOT)
+        launch_field_edge_risk(G.col, G.w, G.state, run.F.V, G.E, slot, d_stats + j, s);
+      else
+        launch_field_edge_cost(G.col, G.w, G.dist, G.state, run.F.V, G.E, bits_float(cs.sf_bits),
+                               bits_float(cs.tau_bits), slot, d_stats + j, s);
     }
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(fb.h_stats, d_stats, fresh.size() * sizeof(FieldEdgeStats), hipMemcpyDeviceToHost, s));
@@ -456,6 +473,8 @@ TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
   for (int k = 0; k < m; ++k) {
     const int slot = run.models.slot[k];
     const FieldBufs::CostSlot &cs = fb.slots[slot];
+    if (cs.bad && run.rq.risk)
+      return e->fail(TRG_ERR_INVALID_ARG, "risk field: an edge weight is negative or not finite");
     if (cs.bad)
       return e->fail(TRG_ERR_INVALID_ARG,
                      "cost field: an edge cost is negative or not finite under the model of field " + std::to_string(k));
@@ -555,7 +574,8 @@ TrgStatus field_rounds(TrgEngine *e, FieldRun &run, const FieldSettle *under) {
   hipStream_t s = e->s_main;
   const long long cap = 4LL * F.N + 64;
   for (int round = 0;;) {
-    for (int i = 0; i < FIELD_BATCH; ++i, ++round) launch_field_round(F, round, s, under, run.model_table());
+    for (int i = 0; i < FIELD_BATCH; ++i, ++round)
+      launch_field_round(F, round, s, under, run.model_table(), run.rq.risk);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(fb.h_state, &F.ctrl->s, sizeof(FieldState), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
@@ -685,7 +705,7 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   const int m = F.m;
   const size_t nN = (size_t)F.N, nat = (size_t)m * rq.n_targets;
   const bool parents = rq.parent != nullptr || run.owners;  // (owners follow parents)
-  launch_field_finish(F, fb.cost.as<float>(), fb.hops.as<int>(), parents, s, run.model_table());
+  launch_field_finish(F, fb.cost.as<float>(), fb.hops.as<int>(), parents, s, run.model_table(), rq.risk);
   TrgStatus st;
   int sweeps = 0;
   if (run.owners && (st = field_owner_pass(e, F, run.sets, run.syncs, sweeps)) != TRG_OK) return st;
@@ -734,6 +754,7 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
                             rq.set_ptr ? std::optional<FieldSets>(run.sets) : std::nullopt, run.owners};
   fb.last.F.tight = nullptr;  // (its array holds the cost output now)
   fb.last.bounded = run.bounded;
+  fb.last.risk = rq.risk;
   if (rq.models) fb.last.pairs.assign(rq.models, rq.models + m);
   fb.last.models = run.models;
   fb.last.many = run.many_models;
@@ -827,7 +848,7 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   HIPCHK(e, hipMemcpyAsync(fb.route_target.p, rq.target, n * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(e, hipEventRecord(fb.t0, s));
   if (!last->parents) {
-    launch_field_parents_late(F, s, last->many ? &last->models : nullptr);
+    launch_field_parents_late(F, s, last->many ? &last->models : nullptr, last->risk);
     HIPCHK(e, hipGetLastError());
     last->parents = true;
   }
@@ -862,7 +883,7 @@ TrgStatus field_routes(TrgEngine *e, const RouteRequest &rq, TrgFieldInfo *info)
   int *d_ids = want_ids ? fb.route_ids.as<int>() : nullptr;
   launch_field_route_walk(F, last->w, last->dist, d_field, d_target, rq.n, d_off, d_ids,
                           fb.route_info.as<FieldRouteInfo>(), last->sources, last->sets ? &*last->sets : nullptr, s,
-                          last->many ? &last->models : nullptr);
+                          last->many ? &last->models : nullptr, last->risk);
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipEventRecord(fb.t1, s));
   int32_t *ids_out = rq.node_ids;
@@ -1084,6 +1105,30 @@ TrgStatus trg_engine_cost_field_models(TrgEngine *e, int32_t m, const TrgFieldMo
     rq.owner_at = owner_at;
     rq.owned = owned;
     rq.models = models;
+    return field_solve(e, rq, out);
+  });
+}
+
+TrgStatus trg_engine_risk_field_sets(TrgEngine *e, int32_t m, const int32_t *set_ptr, const int32_t *set_ids,
+                                     const float *budget, int32_t settle, float *risk, int32_t *hops, int32_t *parent,
+                                     int32_t *owner, const int32_t *targets, int32_t n_targets, float *risk_at,
+                                     int32_t *hops_at, int32_t *owner_at, int32_t *owned, int32_t *reached_out,
+                                     float *bound_out, TrgFieldInfo *info) {
+  return field_entry(e, info, "risk field sets", [&](TrgFieldInfo *out) {
+    const char *no_sets = !set_ptr || !set_ids ? "null set_ptr or set_ids" : nullptr;
+    if (const TrgStatus st = field_check_shape(e, "risk field sets", "sets", m, n_targets, no_sets); st != TRG_OK)
+      return st;
+    if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
+    FieldRequest rq = field_request(m, risk, hops, parent, targets, n_targets, risk_at, hops_at, reached_out);
+    rq.budget = budget;
+    rq.settle = settle;
+    rq.bound_out = bound_out;
+    rq.set_ptr = set_ptr;
+    rq.set_ids = set_ids;
+    rq.owner = owner;
+    rq.owner_at = owner_at;
+    rq.owned = owned;
+    rq.risk = true;
     return field_solve(e, rq, out);
   });
 }

@@ -59,6 +59,15 @@
 // have a MODELS instantiation that takes the slot from the item's field, one table read per queued item or route.
 // A solve whose fields share one model runs the plain instantiations on that slot.
 //
+// Risk fields ("Risk fields"): the least, over all walks, of the GREATEST edge weight on the walk.
+// The extension is (max(risk, r), hops + 1) with r = w + 0 -- monotone in the risk word and never below it, which is
+// all the argument above asks of fl(a + c), and it never rounds.  The hop word is no more monotone than under
+// rounding (a < a' gives max(a, r) == max(a', r) for every r >= a'), so the two passes stay.  The kernels that read an
+// edge value (relax, parent sweep, route walk) have a RISK instantiation whose only difference is that extension; it
+// never combines with MODELS (a risk solve has no cost model), and a risk solve is never refreshed, so there is no RISK
+// warm seed.  The edge risks lie in a slot of the edge-cost array (k_field_edge_risk); every kernel that looks at cost
+// bits only is used as it is.
+//
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"
 
@@ -80,9 +89,12 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 
 __device__ __forceinline__ unsigned long long ballot(bool pred) { return __builtin_amdgcn_ballot_w64(pred); }
 
-// the key of a walk extended by an edge of cost c: (fl(cost + c), hops + 1)
+// the key of a walk extended by an edge of cost c: (fl(cost + c), hops + 1); RISK: by an edge of risk c (>= +0, no
+// NaN: a select gives the greater word as it is), (max(risk, c), hops + 1)
+template <bool RISK = false>
 __device__ __forceinline__ unsigned long long key_extend(unsigned long long k, float c) {
-  const float g = __uint_as_float((unsigned)(k >> 32)) + c;
+  const float a = __uint_as_float((unsigned)(k >> 32));
+  const float g = RISK ? (c > a ? c : a) : a + c;
   return ((unsigned long long)__float_as_uint(g) << 32) | (unsigned)((unsigned)k + 1u);
 }
 
@@ -162,6 +174,40 @@ __global__ __launch_bounds__(THREADS) void k_field_edge_cost(const int *__restri
   }
 }
 
+// Risk fields: r[e] = w[e] + 0 (a weight of -0 counts as +0), FIELD_EDGE_SKIP for an edge that is not relaxable; the
+// sum and count over relaxable edges, and `bad` over ALL edges for a weight that is NaN, negative or infinite.
+__global__ __launch_bounds__(THREADS) void k_field_edge_risk(const int *__restrict__ col, const float *__restrict__ w,
+                                                             const int *__restrict__ state, int V, int E,
+                                                             float *__restrict__ er, FieldEdgeStats *st) {
+  double sum = 0.0;
+  int cnt = 0, bad = 0;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < E; k += gridDim.x * blockDim.x) {
+    const float r = w[k] + 0.0f;
+    if (!(r >= 0.0f) || r == __builtin_huge_valf()) bad = 1;
+    const int v = col[k];
+    bool skip = v < 0 || v >= V;
+    if (!skip) skip = state[v] == FIELD_NODE_INVALID;
+    er[k] = skip ? __uint_as_float(FIELD_EDGE_SKIP) : r;
+    if (!skip) {
+      sum += (double)r;
+      cnt++;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    sum += __shfl_xor(sum, m);
+    cnt += __shfl_xor(cnt, m);
+    bad |= __shfl_xor(bad, m);
+  }
+  if (lane_id() == 0) {
+    if (cnt) {
+      atomicAdd(&st->sum, sum);
+      atomicAdd(&st->count, cnt);
+    }
+    if (bad) atomicOr(&st->bad, 1);
+  }
+}
+
 // The control block before the first round of a pass (one thread): `queued` items in near queue 0, as much work,
 // nothing else queued or piled, the near bucket below `thr`, phase 1.
 __device__ __forceinline__ void field_ctrl_reset(const FieldDev &F, unsigned thr, float delta, int queued) {
@@ -211,9 +257,11 @@ __global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources
 // BOUNDED: pass 1 of a bounded solve -- an item above its field's bound is not expanded (it was queued before the
 // settle step lowered the bound), an extension above the bound is neither written nor pushed.
 // MODELS (with MULTI): the edge costs are those of the item's field.
-template <bool MULTI, bool BOUNDED, bool MODELS>
+// RISK (never with MODELS): a risk field -- F.ec holds the edge risks, the extension is the maximum.
+template <bool MULTI, bool BOUNDED, bool MODELS, bool RISK = false>
 __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, int stamp, FieldModelsArg<MODELS> M) {
   static_assert(MULTI || !MODELS, "one field has one model: the host points F.ec at its slot");
+  static_assert(!(RISK && MODELS), "a risk field has no cost model");
   const int N = MULTI ? F.N : F.V;
   const int n = min(F.ctrl->c.n[par], N);  // (past N only after an overflow, which the host then reports)
   if (n == 0) return;
@@ -264,7 +312,7 @@ __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, in
         if (__float_as_uint(c) != FIELD_EDGE_SKIP) {
           v = F.col[k];
           if constexpr (MULTI) v += fbase;  // the target item: an edge never leaves its field
-          const unsigned long long nk = key_extend(ku, c);
+          const unsigned long long nk = key_extend<RISK>(ku, c);
           const bool tight = !F.tight || (unsigned)(nk >> 32) == F.tight[v];  // (pass 2: tight edges only)
           const bool within = !BOUNDED || key_cost_bits(nk) <= bnd;
           if (tight && within && nk < F.key[v]) {  // plain load first: the atomic only on an improvement
@@ -487,8 +535,9 @@ __global__ __launch_bounds__(THREADS) void k_field_list_emit(FieldDev F, int fie
 }
 
 // Parents: the smallest u with an edge u -> v whose extension of key[u] is key[v], in each field (grid.y).
-template <bool MODELS>
+template <bool MODELS, bool RISK = false>
 __global__ __launch_bounds__(THREADS) void k_field_parent(FieldDev F, FieldModelsArg<MODELS> M) {
+  static_assert(!(RISK && MODELS), "a risk field has no cost model");
   const float *__restrict__ ec = field_costs<MODELS>(F, M, blockIdx.y);
   const int sub = threadIdx.x & (GROUP - 1);
   const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
@@ -501,7 +550,7 @@ __global__ __launch_bounds__(THREADS) void k_field_parent(FieldDev F, FieldModel
       const float c = ec[k];
       if (__float_as_uint(c) == FIELD_EDGE_SKIP) continue;
       const int v = fbase + F.col[k];
-      if (key_extend(ku, c) == F.key[v]) atomicMin(&F.parent[v], u);
+      if (key_extend<RISK>(ku, c) == F.key[v]) atomicMin(&F.parent[v], u);
     }
   }
 }
@@ -576,8 +625,9 @@ __global__ __launch_bounds__(THREADS) void k_field_route_len(FieldDev F, const i
 // host turns into an error, instead of a route that looks right.
 // Where it must end is all that SETS changes: at the field's source S.id[field], or, for a set solve (S its sets,
 // the owner pass has run), at the member that owns the target, ids[ptr[field] + owner[target]].  The single-source
-// instantiation has no owner array to read.  MODELS: the edge costs are those of the route's field.
-template <bool SETS, bool MODELS>
+// instantiation has no owner array to read.  MODELS: the edge costs are those of the route's field.  RISK (never with
+// MODELS): the retained solve is a risk solve -- the matching extension is the maximum, `cost` the risk word.
+template <bool SETS, bool MODELS, bool RISK = false>
 __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const float *__restrict__ w,
                                                               const float *__restrict__ dist,
                                                               const int *__restrict__ route_field,
@@ -622,7 +672,7 @@ __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const 
           bool hit = false;
           if (k < kend && F.col[k] == v) {
             const float c = ec[k];
-            hit = __float_as_uint(c) != FIELD_EDGE_SKIP && key_extend(ku, c) == kv;
+            hit = __float_as_uint(c) != FIELD_EDGE_SKIP && key_extend<RISK>(ku, c) == kv;
           }
           const unsigned hits = (unsigned)(ballot(hit) >> gshift) & ((1u << GROUP) - 1u);
           if (hits) {
@@ -876,10 +926,17 @@ int field_blocks(long long items, int per_block) {
 
 // one round's launches; the settle step only under bounds with a settle mode
 template <bool BOUNDED>
-void field_round(const FieldDev &F, int round, const FieldSettle *settle, const FieldModels *models, hipStream_t s) {
+void field_round(const FieldDev &F, int round, const FieldSettle *settle, const FieldModels *models, bool risk,
+                 hipStream_t s) {
   const int par = round & 1;
   const dim3 relax_grid(field_blocks((long long)F.N * GROUP, THREADS));
-  if (F.m == 1)
+  if (risk && F.m == 1)
+    hipLaunchKernelGGL((k_field_relax<false, BOUNDED, false, true>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1,
+                       FieldNoModels{});
+  else if (risk)
+    hipLaunchKernelGGL((k_field_relax<true, BOUNDED, false, true>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1,
+                       FieldNoModels{});
+  else if (F.m == 1)
     hipLaunchKernelGGL((k_field_relax<false, BOUNDED, false>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1,
                        FieldNoModels{});
   else if (!models)
@@ -906,6 +963,14 @@ void launch_field_edge_cost(const int *col, const float *w, const float *dist, c
                      state, V, E, safety_factor, max_weight, ec, st);
 }
 
+void launch_field_edge_risk(const int *col, const float *w, const int *state, int V, int E, float *er,
+                            FieldEdgeStats *st, hipStream_t s) {
+  (void)hipMemsetAsync(st, 0, sizeof(FieldEdgeStats), s);
+  if (E == 0) return;
+  hipLaunchKernelGGL(k_field_edge_risk, dim3(field_blocks(E, THREADS * 8)), dim3(THREADS), 0, s, col, w, state, V, E,
+                     er, st);
+}
+
 void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets,
                        const unsigned long long *carried, float delta, hipStream_t s) {
   hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, sources, delta,
@@ -914,11 +979,11 @@ void launch_field_init(const FieldDev &F, const FieldSources &sources, const Fie
 }
 
 void launch_field_round(const FieldDev &F, int round, hipStream_t s, const FieldSettle *under_bounds,
-                        const FieldModels *models) {
+                        const FieldModels *models, bool risk) {
   if (under_bounds)
-    field_round<true>(F, round, under_bounds, models, s);
+    field_round<true>(F, round, under_bounds, models, risk, s);
   else
-    field_round<false>(F, round, nullptr, models, s);
+    field_round<false>(F, round, nullptr, models, risk, s);
 }
 
 void launch_field_bounds(const FieldDev &F, const FieldBounds &budgets, hipStream_t s) {
@@ -943,8 +1008,8 @@ void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s) {
 }
 
 void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents, hipStream_t s,
-                         const FieldModels *models) {
-  if (parents) launch_field_supporters(F, s, models);
+                         const FieldModels *models, bool risk) {
+  if (parents) launch_field_supporters(F, s, models, risk);
   hipLaunchKernelGGL(k_field_output, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, cost, hops);
 }
 
@@ -956,10 +1021,10 @@ void launch_field_gather(const FieldDev &F, const FieldSets *sets, const int *ta
                      cost_at, hops_at, owner, owner ? owner_at : nullptr);
 }
 
-void launch_field_parents_late(const FieldDev &F, hipStream_t s, const FieldModels *models) {
+void launch_field_parents_late(const FieldDev &F, hipStream_t s, const FieldModels *models, bool risk) {
   const dim3 grid(field_blocks(F.N, THREADS));
   hipLaunchKernelGGL(k_field_parent_mark, grid, dim3(THREADS), 0, s, F, -1, INT_MAX);
-  launch_field_supporters(F, s, models);
+  launch_field_supporters(F, s, models, risk);
   hipLaunchKernelGGL(k_field_parent_mark, grid, dim3(THREADS), 0, s, F, INT_MAX, -1);
 }
 
@@ -973,10 +1038,16 @@ void launch_field_route_len(const FieldDev &F, const int *route_field, const int
 void launch_field_route_walk(const FieldDev &F, const float *w, const float *dist, const int *route_field,
                              const int *route_target, int n_routes, const int *offsets, int *node_ids,
                              FieldRouteInfo *infos, const FieldSources &sources, const FieldSets *sets,
-                             hipStream_t s, const FieldModels *models) {
+                             hipStream_t s, const FieldModels *models, bool risk) {
   if (n_routes <= 0) return;
   const dim3 grid(field_blocks((long long)n_routes * GROUP, THREADS));
-  if (sets && models)
+  if (risk && sets)
+    hipLaunchKernelGGL((k_field_route_walk<true, false, true>), grid, dim3(THREADS), 0, s, F, w, dist, route_field,
+                       route_target, n_routes, offsets, node_ids, infos, *sets, FieldNoModels{});
+  else if (risk)
+    hipLaunchKernelGGL((k_field_route_walk<false, false, true>), grid, dim3(THREADS), 0, s, F, w, dist, route_field,
+                       route_target, n_routes, offsets, node_ids, infos, sources, FieldNoModels{});
+  else if (sets && models)
     hipLaunchKernelGGL((k_field_route_walk<true, true>), grid, dim3(THREADS), 0, s, F, w, dist, route_field,
                        route_target, n_routes, offsets, node_ids, infos, *sets, *models);
   else if (sets)
@@ -1006,9 +1077,10 @@ void launch_field_carry(const unsigned long long *old_key, int V_old, const int 
                      out);
 }
 
-void launch_field_supporters(const FieldDev &F, hipStream_t s, const FieldModels *models) {
+void launch_field_supporters(const FieldDev &F, hipStream_t s, const FieldModels *models, bool risk) {
   const dim3 grid(field_blocks((long long)F.V * GROUP, THREADS), F.m);
-  if (models) hipLaunchKernelGGL(k_field_parent<true>, grid, dim3(THREADS), 0, s, F, *models);
+  if (risk) hipLaunchKernelGGL((k_field_parent<false, true>), grid, dim3(THREADS), 0, s, F, FieldNoModels{});
+  else if (models) hipLaunchKernelGGL(k_field_parent<true>, grid, dim3(THREADS), 0, s, F, *models);
   else hipLaunchKernelGGL(k_field_parent<false>, grid, dim3(THREADS), 0, s, F, FieldNoModels{});
 }
 

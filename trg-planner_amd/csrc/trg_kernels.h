@@ -470,6 +470,11 @@ struct FieldDev {
 // is above max_weight (+inf: none is); *st (zeroed here) over the edges that got a cost, its bad flag over all.
 void launch_field_edge_cost(const int *col, const float *w, const float *dist, const int *state, int V, int E,
                             float safety_factor, float max_weight, float *ec, FieldEdgeStats *st, hipStream_t s);
+// Risk fields ("Risk fields"): er[e] = w[e] + 0, FIELD_EDGE_SKIP for an edge that is not
+// relaxable; *st (zeroed here) over the relaxable edges, its bad flag over all (a weight that is NaN, negative or
+// infinite).  `er` is a slot of the edge-cost array: a risk solve's F.ec points at it.
+void launch_field_edge_risk(const int *col, const float *w, const int *state, int V, int E, float *er,
+                            FieldEdgeStats *st, hipStream_t s);
 // Field k starts at node sources.id[k], k < F.m (duplicates give identical fields).  With `sets` (a set solve; else
 // nullptr) sources is not read: every item is left without a key, then a second launch seeds every distinct member
 // item and pushes it once to near queue 0; F.ctrl's queue size and work are the count of distinct member items.
@@ -492,8 +497,10 @@ struct FieldSettle {
 // some (ANY) or all (ALL) of them have a key below the least live far cost -- to the least (greatest) of those
 // costs.
 // models (here and below; nullptr: every field reads F.ec): the slot table of a solve with more than one cost model.
+// risk (here and below; never with models): a risk solve -- F.ec holds edge risks and a walk's key is extended by
+// (max(risk, r), hops + 1) instead of (fl(cost + c), hops + 1).
 void launch_field_round(const FieldDev &F, int round, hipStream_t s, const FieldSettle *under_bounds = nullptr,
-                        const FieldModels *models = nullptr);
+                        const FieldModels *models = nullptr, bool risk = false);
 // F.ctrl->bound[k] = budgets.bits[k], before the first round of a bounded solve
 void launch_field_bounds(const FieldDev &F, const FieldBounds &budgets, hipStream_t s);
 // after the last round of pass 1: keys above their field's bound become FIELD_KEY_NONE
@@ -509,7 +516,7 @@ void launch_field_cost_bits(const FieldDev &F, unsigned *bits, hipStream_t s);
 // each: cost (+inf), hops (-1) and parent (-1) of unreached items; F.ctrl->reached[k] counts field k's reached
 // nodes
 void launch_field_finish(const FieldDev &F, float *cost, int *hops, bool parents, hipStream_t s,
-                         const FieldModels *models = nullptr);
+                         const FieldModels *models = nullptr, bool risk = false);
 // the finished keys at n_t target nodes: cost_at / hops_at[k * n_t + j] of (field k, targets[j]), +inf and
 // -1 where unreached; of a set solve whose owner pass ran (`sets`, else nullptr) owner_at likewise, sets->owner of
 // (field k, targets[j]).  Any output may be nullptr.
@@ -522,7 +529,8 @@ struct FieldRouteInfo {
 };
 constexpr int FIELD_ROUTE_BROKEN = -1;  // num_nodes of a walk that did not end at its field's source
 // the parent sweep of a finished solve whose launch_field_finish ran without `parents`: F.parent as with it
-void launch_field_parents_late(const FieldDev &F, hipStream_t s, const FieldModels *models = nullptr);
+void launch_field_parents_late(const FieldDev &F, hipStream_t s, const FieldModels *models = nullptr,
+                               bool risk = false);
 // len[r] = hops + 1 of (field route_field[r], node route_target[r]), 0 where unreached
 void launch_field_route_len(const FieldDev &F, const int *route_field, const int *route_target, int n_routes,
                             int *len, hipStream_t s);
@@ -534,7 +542,7 @@ void launch_field_route_len(const FieldDev &F, const int *route_field, const int
 void launch_field_route_walk(const FieldDev &F, const float *w, const float *dist, const int *route_field,
                              const int *route_target, int n_routes, const int *offsets, int *node_ids,
                              FieldRouteInfo *infos, const FieldSources &sources, const FieldSets *sets,
-                             hipStream_t s, const FieldModels *models = nullptr);
+                             hipStream_t s, const FieldModels *models = nullptr, bool risk = false);
 
 // ---- the owner pass of a set solve ("Source sets") -------------------------------------
 constexpr int FIELD_OWNER_SWEEPS_MAX = 40;  // pointer jumping doubles: 2^31 hops need 31 sweeps and one that finds nothing
@@ -561,7 +569,8 @@ void launch_field_carry(const unsigned long long *old_key, int V_old, const int 
 // F.parent[item] = the item's supporter under the keys as they are: the smallest u with an edge u -> v and
 // key_extend(key[u], c) == key[v], INT_MAX without one: the parent sweep, which launch_field_finish and
 // launch_field_parents_late run through this
-void launch_field_supporters(const FieldDev &F, hipStream_t s, const FieldModels *models = nullptr);
+void launch_field_supporters(const FieldDev &F, hipStream_t s, const FieldModels *models = nullptr,
+                             bool risk = false);
 // The anchor: an item keeps its key if its chain of supporters (F.parent) ends at a source.  begin:
 // launch_field_forest_begin; then launch_field_owner_sweep until a sweep moves nothing; end: every item whose last
 // ancestor is no source loses its key, key0 (may be nullptr) gets the keys after that and carried[k] (may be nullptr;

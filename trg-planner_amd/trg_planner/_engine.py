@@ -108,6 +108,7 @@ EXPORTS = [
     "trg_engine_stitch_exchange", "trg_engine_cost_field", "trg_engine_cost_field_batch",
     "trg_engine_field_routes", "trg_engine_cost_field_bounded", "trg_engine_field_reached",
     "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh", "trg_engine_cost_field_models",
+    "trg_engine_risk_field_sets",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -205,6 +206,7 @@ def load_library():
                                              ip, ip, ip, fp, C.POINTER(TrgFieldInfo)]
     L.trg_engine_cost_field_models.argtypes = [vp, C.c_int32, C.POINTER(TrgFieldModel), ip, ip, fp, C.c_int32, fp, ip,
                                                ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, fp, C.POINTER(TrgFieldInfo)]
+    L.trg_engine_risk_field_sets.argtypes = L.trg_engine_cost_field_sets.argtypes
     L.trg_engine_cost_field_refresh.argtypes = [vp, ip, C.c_int32, fp, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, ip, ip,
                                                 C.POINTER(TrgFieldInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
@@ -907,6 +909,104 @@ class Engine:
         r = self.cost_fields(source_ids=[start], targets=[goal], full=False, settle="any", models=[(sf, tau)])
         route = self.routes([0], [goal], hops_at=r["hops_at"][:, 0])[0]
         return tau, self._route_record(r["models"][0], *route)
+
+    def risk_fields(self, sources_xy=None, source_ids=None, targets=None, full=True, budget=None, settle=None):
+        """m risk fields in one solve on the GPU (trg_engine_risk_field_sets; DESIGN.md section 2, "Risk fields"): for
+        every node the least, over all walks from the source, of the greatest edge weight on the walk -- the least risk
+        ceiling under which the node can be reached at all -- exactly.  Sources as cost_fields' (resolved first, no
+        solve; every field then runs as a set of one).  -> cost_fields' dict with "risk" / "risk_at" where that has
+        "cost" / "cost_at": "risk" float32 (+inf: unreachable), "hops" (the BFS depth over tight edges, -1:
+        unreachable), "parent" (m, V) with `full`; "risk_at", "hops_at" (m, n_t) with `targets`; "sources", "reached",
+        "info".  `budget` is a risk ceiling (a node of greater risk comes back unreached, every other one as in the full
+        field), `settle` "any" / "all" lowers it to the least / greatest risk over `targets`; with either the result
+        has "bound".  The solve is retained: routes and field_reached answer from it (a route's cost is its target's
+        risk); refresh_fields refuses it."""
+        if sources_xy is None and source_ids is None:
+            raise ValueError("risk_fields needs sources_xy or source_ids")
+        ids = None if source_ids is None else np.ascontiguousarray(source_ids, dtype=np.int32).reshape(-1)
+        xy = None if sources_xy is None else np.ascontiguousarray(sources_xy, dtype=np.float32).reshape(-1, 2)
+        m = ids.shape[0] if ids is not None else xy.shape[0]
+        if ids is not None and xy is not None and xy.shape[0] != m:
+            raise ValueError("risk_fields: sources_xy and source_ids differ in length")
+        nodes = np.full(max(m, 1), -1, np.int32)
+        self._chk(self.L.trg_engine_cost_field_batch(self.h, m, None if ids is None else _i(ids),
+                                                     None if xy is None else _f(xy), None, None, None, None, 0,
+                                                     None, None, _i(nodes), None, None))
+        # (a set of one owns all it reaches: no owner pass)
+        return self._risk_fields_from("risk_fields", [nodes[k:k + 1] for k in range(m)], targets, full, budget, settle,
+                                      owners=False)
+
+    def risk_fields_from(self, sets, targets=None, full=True, budget=None, settle=None):
+        """m risk fields in one solve, field k from EVERY node of sets[k] at risk 0 (trg_engine_risk_field_sets):
+        cost_fields_from's dict with "risk" / "risk_at" where that has "cost" / "cost_at" -- "owner", "owner_at",
+        "owned" and "sets" as there, over the (risk, hops) keys."""
+        return self._risk_fields_from("risk_fields_from", sets, targets, full, budget, settle, owners=True)
+
+    def _risk_fields_from(self, who, sets, targets, full, budget, settle, owners):
+        sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
+        m = len(sets)
+        out, a = self._field_outputs(who, m, targets, full, budget, settle, owners=owners)
+        ptr = np.zeros(m + 1, np.int64)
+        np.cumsum([s.shape[0] for s in sets], out=ptr[1:])
+        if ptr[-1] > 2**31 - 1:
+            raise ValueError(f"{who}: {int(ptr[-1])} source entries do not fit 32 bits")
+        ptr = ptr.astype(np.int32)
+        ids = np.ascontiguousarray(np.concatenate(sets) if m else np.empty(0, np.int32), dtype=np.int32)
+        owned = np.zeros(max(int(ptr[-1]), 1), np.int32)
+        info = TrgFieldInfo()
+        self._chk(self.L.trg_engine_risk_field_sets(
+            self.h, m, _i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
+            _i(owned) if owners else None, a["reached"], a["bound"], C.byref(info)))
+        self._field_shape = (m, True)
+        for old, new in (("cost", "risk"), ("cost_at", "risk_at")):
+            if old in out:
+                out[new] = out.pop(old)
+        if owners:
+            out["owned"] = [owned[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
+            out["sets"] = sets
+        out["sources"] = np.array([s[0] for s in sets], np.int32)
+        out["info"] = info
+        return out
+
+    def safest_route(self, start_xy, goal_xy):
+        """min_risk_ceiling's answer from two solves: one risk field from the start, stopped once the goal is settled
+        (its risk there IS the least ceiling under which the goal is reachable), then one cost field under (the
+        engine's safety factor, that ceiling) with a routes call -> (max_risk, route dict as plan_tradeoff's), or None
+        when the goal is unreachable.  For a goal node other than the start node the result equals
+        min_risk_ceiling's bit for bit.  For goal == start the ceiling is 0.0 (no edge has to be crossed;
+        min_risk_ceiling names the graph's least weight there) and the route is the one node.  Two more differences:
+        on a graph with a NaN, negative or infinite weight this raises TrgError (the risk solve refuses the graph)
+        where min_risk_ceiling leaves NaN out and may answer, and a ceiling of zero is always +0.0 here, where
+        min_risk_ceiling may name a weight of -0.0 (equal, not the same bits)."""
+        start, goal = (int(v) for v in self._resolve_nodes([np.asarray(start_xy, np.float32).reshape(2),
+                                                            np.asarray(goal_xy, np.float32).reshape(2)]))
+        r = self.risk_fields(source_ids=[start], targets=[goal], full=False, settle="any")
+        if r["hops_at"][0, 0] < 0:
+            return None
+        tau = float(r["risk_at"][0, 0])
+        r = self.cost_fields(source_ids=[start], targets=[goal], full=False, settle="any",
+                             models=[(self.params.safety_factor, tau)])
+        route = self.routes([0], [goal], hops_at=r["hops_at"][:, 0])[0]
+        return tau, self._route_record(r["models"][0], *route)
+
+    def frontier_ceilings(self, pose_xy):
+        """For every Frontier node the least risk ceiling under which it can be reached from `pose_xy`: one risk field
+        read at the Frontier nodes on the device -> (frontier ids int32 ascending, risk float32 (+inf: unreachable),
+        hops int32 (-1: unreachable)); nothing of V entries is copied back."""
+        frontier = self._frontier_ids()
+        r = self.risk_fields(sources_xy=np.asarray(pose_xy, np.float32).reshape(1, 2), targets=frontier, full=False)
+        return frontier, r["risk_at"][0], r["hops_at"][0]
+
+    def safest_frontier(self, pose_xy):
+        """The Frontier node that is safest to reach from `pose_xy`: the least (risk, hops, id) among the reachable
+        Frontier nodes, with its route in the minimax tree from one routes call -> (node, risk, path ids), or None
+        without a reachable one."""
+        frontier, risk, hops = self.frontier_ceilings(pose_xy)
+        pick = choose_frontier(frontier, risk, hops)
+        if pick is None:
+            return None
+        ids, _, _ = self.routes([0], [pick[0]], xyz=False, hops_at=[hops[pick[1]]])[0]
+        return pick[0], float(risk[pick[1]]), ids.tolist()
 
     def check_reached(self, pos2d):
         p = np.ascontiguousarray(pos2d, dtype=np.float32)
