@@ -86,7 +86,8 @@ void plan_goal_node(TrgEngine *e, PlanScratch &ps, const float goal_xyz[3], int 
 
 // planSafePath (trg.cpp:603-690) on the CSR of the global graph: a row's entries are the node's edges in
 // the reference's push order, the heap is std::push_heap / std::pop_heap with the reference's comparator
-// (f_cost greater-than), so equal-cost ties fall exactly as in the reference's std::priority_queue.
+// (f_cost greater-than), so equal-cost ties fall exactly as in the reference's std::priority_queue
+// (tests/test_gpu_plan_exact.py).
 TrgStatus plan_on_csr(TrgEngine *e, PlanScratch &ps, int start, int goal, float *path_xyz, int32_t max_points,
                       TrgPathInfo *info) {
   const Csr &G = e->csr_global;
@@ -101,7 +102,9 @@ TrgStatus plan_on_csr(TrgEngine *e, PlanScratch &ps, int start, int goal, float 
   std::vector<int> &heap = ps.heap;
   auto cmp = [&pool](int a, int b) { return pool[a].f > pool[b].f; };
   const float gx = nx[goal], gy = ny[goal];
-  const double sf = e->prm.safety_factor;
+  // a float, as the reference's param_.safety_factor: the step cost below is then an all-float expression (four fp32
+  // roundings, trg.cpp:674) that is widened only afterwards -- routes that tie as real numbers fall as they do there
+  const float sf = e->prm.safety_factor;
 
   info->direct_dist = norm2f(gx - nx[start], gy - ny[start]);
   {
