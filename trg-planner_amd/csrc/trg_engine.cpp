@@ -537,28 +537,50 @@ struct TrgEngine {
   uint32_t epoch_base = 0;  // tiled builds: sampler epoch of this tile
   float core[4] = {-INFINITY, -INFINITY, INFINITY, INFINITY};  // tiled builds: node creation region
 
-  // graph state: slot == id (ids are dense at all times)
+  // ---- host graph state ("Host graph state and its views") -----------------------------------------
+  // The global graph is the node arrays (slot == id, ids dense at all times) and the container history; all else is a
+  // view, stamped with the graph_version it is current for.  Only its ensure_* reads the stamp; graph_changed() commits.
+  //   view             data                         brought up to date by                        asked for by
+  //   VIEW_POOL        edges                        host build, update, load; ensure_pool        update, save_json, graph("local")
+  //   VIEW_GRID        grid                         the same; ensure_host_grid                   update, plan, cost field, is_frontier
+  //   VIEW_KD_ORDER    kd_insert_order              the same; ensure_kd_order                    kd_sync, ensure_kd_order_arrays, update
+  //   VIEW_KD          kd, a prefix of the order    kd_sync                                      distance ties, hits near a radius
+  //   VIEW_KDO         kdo_x / kdo_y / kdo_index    ensure_kd_order_arrays                       plan, cost field: order questions
+  //   VIEW_CSR         csr_global                   every build, update, load; ensure_csr_global plan, cost field, graph("global"), stitch
+  //   VIEW_DEV_CSR     the cleaned CSR in HBM       device build; update drops it (dev_csr)      cost field, stitch: spares an upload
+  //   VIEW_STITCH_DEV  csr_stitched's edges in HBM  stitch_assemble; stitch_fetch un-stamps      graph("stitched")
+  // (the cost field's uploaded CSR and edge costs carry their own stamps in FieldBufs)
+  enum GraphView { VIEW_POOL, VIEW_GRID, VIEW_KD_ORDER, VIEW_KD, VIEW_KDO, VIEW_CSR, VIEW_DEV_CSR, VIEW_STITCH_DEV,
+                   VIEW_COUNT };
+  uint64_t graph_version = 1;            // bumped by graph_changed() alone
+  uint64_t view_stamp[VIEW_COUNT] = {};  // graph_version each view is current for (0: none)
+  bool current(GraphView v) const { return view_stamp[v] == graph_version; }
   std::vector<float> nx, ny, nz;
   std::vector<int> nstate;
   std::vector<int> ncid;  // creation index since the last build began
   int next_cid = 0;       // ... of the next node: counts every node created, the dropped ones too, through the updates
+  int node_id = 0;
   std::unordered_map<int, int> order_map;  // mirrors trgStruct::nodes (iteration order only)
   // After a device build the container history is carried by an O(n) replica of the hashtable's
   // iteration order (map_order_sim.h); the real map is rebuilt from it only if a host path needs it.
   MapOrderSim nodes_sim;
-  bool real_map_stale = false;
+  // Which of the two carries the container history: nodes_sim (true, from a device build on) or order_map (false,
+  // from ensure_real_map on).  Not a view and no validity flag: graph_changed() never touches it.
+  bool history_in_sim = false;
   std::vector<int> last_new2old;  // of the last host cleanGraph: old id of every surviving node
   EdgePool edges;
-  int node_id = 0;
+  NodeGrid grid;
+  std::vector<int> kd_insert_order;  // ids in the order the reference inserted them
+  NodeKd kd;                         // reference-shaped index of the current node set
+  std::vector<float> kdo_x, kdo_y;   // positions in the node tree's insertion order, for the planner's rare order
+  std::vector<int> kdo_index;        // questions (nearest-node ties, several goal hits): node id -> position
+  Csr csr_global;
+  Csr csr_stitched;        // tiled builds: this tile's rows of the stitched global graph
+  int stitched_edges = 0;  // ... and their edge count (the edge arrays may still be in HBM only)
   float root_pos[2] = {0, 0};
   float local_root[2] = {0, 0};
   std::unordered_map<int, int> local_map;  // mirrors local trgStruct::nodes (iteration order)
   std::vector<int> local_nodes;  // ids in local_map's iteration order
-  NodeGrid grid;
-  NodeKd kd;          // reference-shaped index of the CURRENT global node set
-  bool kd_valid = false;
-  std::vector<int> kd_insert_order;  // ids in the order the reference inserted them
-  NodeKd lkd;         // local node tree (isFrontier does not use it; kept for completeness)
   bool step3 = false;
 
   // build scratch
@@ -581,23 +603,13 @@ struct TrgEngine {
   PinnedBuf<MapTieSet> mt_set;
   PinnedBuf<MapTieWalk> mt_walk;
 
-  Csr csr_global, csr_pre, csr_local;
-  Csr csr_stitched;              // tiled builds: this tile's rows of the stitched global graph
-  bool stitched_on_device = false;  // ... their edge arrays are still in HBM only (fetched on export)
-  int stitched_edges = 0;
-  bool dev_csr_valid = false;    // the cleaned global CSR of the last device build is still in HBM
+  Csr csr_pre, csr_local;
   std::unique_ptr<StitchBufs> stitch;
   bool keep_preclean = false;    // instrumentation: snapshot the graph before cleanGraph
   bool use_device_bfs = true;    // device-resident BFS (off: host replay)
   bool defer_overlap = true;     // deferred edge evaluations pipelined behind the level loop on a 2nd stream
   bool tail_overlap = true;      // after the loop: the creating edges' covariances beside the cleaned graph's copy to the host
-  uint64_t graph_version = 1;    // bumped by everything that changes the global graph (queries cache per version)
-  // planner state (A* runs straight on csr_global, see plan_on_csr): positions in the node tree's insertion
-  // order for the rare order questions (nearest-node ties, several goal hits), and the search scratch
-  std::vector<float> kdo_x, kdo_y;
-  std::vector<int> kdo_index;    // node id -> position in the insertion order
-  uint64_t kdo_version = 0;
-  PlanScratch plan_scratch;
+  PlanScratch plan_scratch;  // the planner's search scratch (A* runs straight on csr_global, see plan_on_csr)
   std::unique_ptr<Uploader> uploader;  // host cloud -> HBM staging (upload_and_build): pinned slots, streams and events
                                        // of its copy threads, made on the first cloud that needs them
   std::unique_ptr<ExchangeState> exchange;  // tiled builds: RCCL communicator and buffers of the native stitch
@@ -606,13 +618,10 @@ struct TrgEngine {
   double field_delta_scale = 4.0;  // cost field: bucket width in mean edge costs (a measurement knob, see set_option)
   // The node map of trg_engine_cost_field_refresh: for every node of the current graph its id in the graph of the
   // retained cost-field solve, -1 for a node made since.  A solve starts it as the identity, update_graph composes
-  // it with its cleanGraph's renumbering; a new solve's start, every reset_graph_global (init_graph, load_json, a
-  // reset) and an update that fails leave none.
+  // it with its cleanGraph's renumbering; a new solve's start, every graph_changed() (init_graph, load_json, a
+  // reset, an update's own before it composes) and an update that fails leave none.
   enum { FIELD_MAP_NONE, FIELD_MAP_IDENTITY, FIELD_MAP_EXPLICIT } field_map_state = FIELD_MAP_NONE;
   std::vector<int> field_map;
-  bool pool_valid = true;        // e->edges mirrors csr_global
-  bool host_grid_valid = true;   // e->grid holds the current node set
-  bool kd_order_dirty = false;   // kd_insert_order must be re-derived from order_map
   int debug_tie_every = 0;       // test hook: treat every n-th BFS level as tie-affected
   int debug_spec_bound = 0;      // test hook: cap the speculative sampling launch at n nodes
   int debug_fallback_level = -1; // test hook: the device BFS declines at this level
@@ -745,16 +754,19 @@ inline float sampler_uniform(const TrgEngine *e, uint32_t k) {
 
 #include "trg_engine_probe.ipp"
 
-// the stitched rows belong to the graph they were assembled from: every change of the global graph voids them
-void invalidate_stitched(TrgEngine *e) {
-  e->stitched_on_device = false;
+// ---- graph state helpers -----------------------------------------------------------------------
+// The one commit point: every change of the global graph ends here.  `fresh` names the views the caller has just
+// brought up to date; every other view is stale from here on, until its ensure_* is next asked for it.  The stitched
+// rows and the cost field's node map belong to the graph that was (update_graph composes a new map afterwards).
+void graph_changed(TrgEngine *e, std::initializer_list<TrgEngine::GraphView> fresh) {
+  e->graph_version++;
+  for (const auto v : fresh) e->view_stamp[v] = e->graph_version;
   e->stitched_edges = 0;
   e->csr_stitched.clear();
+  e->field_map_state = TrgEngine::FIELD_MAP_NONE;
 }
 
-// ---- graph state helpers -----------------------------------------------------------------------
 void reset_graph_global(TrgEngine *e) {
-  e->dev_csr_valid = false;
   e->nx.clear();
   e->ny.clear();
   e->nz.clear();
@@ -765,18 +777,15 @@ void reset_graph_global(TrgEngine *e) {
   e->edges.reset(0);
   e->node_id = 0;
   e->kd.clear();
-  e->kd_valid = true;  // empty tree is trivially in sync
-  e->kd_order_dirty = false;
   e->kd_insert_order.clear();
   e->goal_node = -1;
-  e->graph_version++;
-  e->field_map_state = TrgEngine::FIELD_MAP_NONE;
-  invalidate_stitched(e);
+  // (the empty pool, order and tree are those of the empty graph; the grid and the CSR still hold the old one)
+  graph_changed(e, {TrgEngine::VIEW_POOL, TrgEngine::VIEW_KD_ORDER, TrgEngine::VIEW_KD});
 }
 
 // the node map's keys in iteration order, whichever representation is current
 void node_map_order(const TrgEngine *e, std::vector<int> &out) {
-  if (e->real_map_stale) {
+  if (e->history_in_sim) {
     e->nodes_sim.iteration_order(out);
   } else {
     out.clear();
@@ -787,12 +796,12 @@ void node_map_order(const TrgEngine *e, std::vector<int> &out) {
 // rebuild the real container exactly as cleanGraph left it: new_nodes[new_id] for the dense new ids,
 // then nodes = new_nodes (trg.cpp:502, 526)
 void ensure_real_map(TrgEngine *e) {
-  if (!e->real_map_stale) return;
+  if (!e->history_in_sim) return;
   std::unordered_map<int, int> fresh;
   const int n = (int)e->nodes_sim.size();
   for (int k = 0; k < n; ++k) fresh[k] = k;
   e->order_map = std::move(fresh);
-  e->real_map_stale = false;
+  e->history_in_sim = false;
 }
 
 void grid_rebuild(TrgEngine *e) {
@@ -816,18 +825,17 @@ void grid_rebuild(TrgEngine *e) {
 // for ties and for step 3; queries need it for hit order)
 // after a device build the node-tree refill order (the node map's iteration order, trg.cpp:528-530)
 // is derived on demand
-void materialize_kd_order(TrgEngine *e) {
-  if (!e->kd_order_dirty) return;
+void ensure_kd_order(TrgEngine *e) {
+  if (e->current(TrgEngine::VIEW_KD_ORDER)) return;
   node_map_order(e, e->kd_insert_order);
-  e->kd_order_dirty = false;
-  e->kd_valid = false;
+  e->view_stamp[TrgEngine::VIEW_KD_ORDER] = e->graph_version;
 }
 
 void kd_sync(TrgEngine *e) {
-  materialize_kd_order(e);
-  if (!e->kd_valid) {
+  ensure_kd_order(e);
+  if (!e->current(TrgEngine::VIEW_KD)) {
     e->kd.clear();
-    e->kd_valid = true;
+    e->view_stamp[TrgEngine::VIEW_KD] = e->graph_version;
   }
   while (e->kd.size() < e->kd_insert_order.size()) {
     const int id = e->kd_insert_order[e->kd.size()];
@@ -844,7 +852,7 @@ int add_node_host(TrgEngine *e, float x, float y, float z, int state) {
   e->ncid.push_back(e->next_cid++);
   // graph.nodes[node_id] = node (trg.cpp:248): into whichever representation of the container is current
   // (after a device build or a cleanGraph the keys are dense and ascending: the O(1) replica serves)
-  if (e->real_map_stale) {
+  if (e->history_in_sim) {
     e->nodes_sim.insert_next();
   } else {
     e->order_map[id] = id;
@@ -880,7 +888,7 @@ int nearest_node(TrgEngine *e, float qx, float qy) {
 namespace {
 // host-side edge pool / node grid rebuilt from the CSR after a device build (lazy)
 void ensure_pool(TrgEngine *e) {
-  if (e->pool_valid) return;
+  if (e->current(TrgEngine::VIEW_POOL)) return;
   const Csr &g = e->csr_global;
   const size_t V = g.state.size();
   std::vector<int> offs(g.rowptr.data(), g.rowptr.data() + V + 1);
@@ -895,12 +903,32 @@ void ensure_pool(TrgEngine *e) {
     }
     e->edges.link_rows(offs, i0, i1);
   });
-  e->pool_valid = true;
+  e->view_stamp[TrgEngine::VIEW_POOL] = e->graph_version;
 }
 void ensure_host_grid(TrgEngine *e) {
-  if (e->host_grid_valid) return;
+  if (e->current(TrgEngine::VIEW_GRID)) return;
   grid_rebuild(e);
-  e->host_grid_valid = true;
+  e->view_stamp[TrgEngine::VIEW_GRID] = e->graph_version;
+}
+// the commit of the host paths (host build, update_graph, load_json): pool, grid and insertion order are the
+// caller's work, the CSR is taken from the pool here
+void host_graph_changed(TrgEngine *e) {
+  snapshot_csr(e, e->csr_global);
+  graph_changed(e, {TrgEngine::VIEW_POOL, TrgEngine::VIEW_GRID, TrgEngine::VIEW_KD_ORDER, TrgEngine::VIEW_CSR});
+}
+// csr_global from the pool; false: neither is of the current graph.  (The size test covers an update_graph that
+// failed midway: it has added nodes under an unchanged version.)
+bool ensure_csr_global(TrgEngine *e) {
+  if (e->current(TrgEngine::VIEW_CSR) && e->csr_global.state.size() == e->nx.size()) return true;
+  if (!e->current(TrgEngine::VIEW_POOL)) return false;
+  snapshot_csr(e, e->csr_global);
+  e->view_stamp[TrgEngine::VIEW_CSR] = e->graph_version;
+  return true;
+}
+// the cleaned CSR of the last device build while it is the current graph's (else the consumers upload csr_global)
+const BfsBuffers *dev_csr(const TrgEngine *e) {
+  const BfsBuffers *bb = e->bfs.get();
+  return e->current(TrgEngine::VIEW_DEV_CSR) && bb && bb->xyz2.p && bb->rowptr_new.p ? bb : nullptr;
 }
 }  // namespace
 
@@ -1016,7 +1044,6 @@ TrgStatus trg_engine_reset_graph(TrgEngine *e, TrgKind kind) {
   if (kind == TRG_KIND_LOCAL) {
     e->local_nodes.clear();
     e->local_map.clear();
-    e->lkd.clear();
   } else {
     ensure_real_map(e);
     reset_graph_global(e);
@@ -1048,13 +1075,10 @@ TrgStatus trg_engine_init_graph(TrgEngine *e, const float start_xyz[3], const Tr
   if (!e->use_device_bfs) ensure_real_map(e);
   MapOrderSim sim_before;  // container history as of before this build (for the fallback)
   if (e->use_device_bfs) {
-    if (!e->real_map_stale) e->nodes_sim.adopt_bucket_state(e->order_map);
+    if (!e->history_in_sim) e->nodes_sim.adopt_bucket_state(e->order_map);
     sim_before = e->nodes_sim;
   }
-  const bool stale_before = e->real_map_stale;
   reset_graph_global(e);
-  e->real_map_stale = stale_before;
-  e->pool_valid = true;
   e->epoch = e->epoch_base;
   e->calls.clear();
   e->pending_calls.clear();
@@ -1104,13 +1128,11 @@ TrgStatus trg_engine_init_graph(TrgEngine *e, const float start_xyz[3], const Tr
     HIPCHK(e, hipMemset(e->d_ctr, 0, COUNTER_SHARDS * sizeof(DeviceCounters)));
     e->lv_hits_sample = e->lv_hits_spec = 0;
     e->nodes_sim = sim_before;
-    e->real_map_stale = stale_before;
     ensure_real_map(e);
-    reset_graph_global(e);
+    reset_graph_global(e);  // (the abandoned attempt may have written the node arrays: clean_and_fetch)
   }
 
-  grid_rebuild(e);
-  e->host_grid_valid = true;
+  grid_rebuild(e);  // (empty, over the map's extent: add_node_host fills it, host_graph_changed names it)
   add_node_host(e, rx, ry, rz, TRG_NODE_VALID);
   st = expand_bfs(e, e->node_id - 1);
   if (st != TRG_OK) return st;
@@ -1120,9 +1142,7 @@ TrgStatus trg_engine_init_graph(TrgEngine *e, const float start_xyz[3], const Tr
   apply_calls(e, 0);
   if (e->keep_preclean) snapshot_csr(e, e->csr_pre);
   clean_graph(e);
-  snapshot_csr(e, e->csr_global);
-  e->graph_version++;
-  invalidate_stitched(e);
+  host_graph_changed(e);
   e->stats.ms_finalize_host = ms_since(t_fin);
   read_counters(e);
   e->stats.ms_init_graph_total = ms_since(t_total);
@@ -1216,7 +1236,7 @@ TrgStatus trg_engine_update_graph(TrgEngine *e) {
   TrgStatus st = ensure_sampler(e, nullptr);
   if (st != TRG_OK) return st;
   e->epoch++;
-  e->dev_csr_valid = false;
+  e->view_stamp[TrgEngine::VIEW_DEV_CSR] = 0;  // dropped before anything can fail (the cost field's retained solve)
   const size_t nodes_before = e->nx.size();
   const auto map_before = e->field_map_state;
   e->field_map_state = TrgEngine::FIELD_MAP_NONE;  // (an update that fails leaves no map)
@@ -1227,7 +1247,7 @@ TrgStatus trg_engine_update_graph(TrgEngine *e) {
   };
   ensure_pool(e);
   ensure_host_grid(e);
-  materialize_kd_order(e);  // nodes created below are appended to the existing insertion order
+  ensure_kd_order(e);  // nodes created below are appended to the existing insertion order
   e->calls.clear();
   e->pending_calls.clear();
   lap_up("host structures ready");
@@ -1298,9 +1318,7 @@ TrgStatus trg_engine_update_graph(TrgEngine *e) {
   if (e->keep_preclean) snapshot_csr(e, e->csr_pre);
   clean_graph(e);
   lap_up("cleanGraph");
-  snapshot_csr(e, e->csr_global);
-  e->graph_version++;
-  invalidate_stitched(e);
+  host_graph_changed(e);
   lap_up("CSR snapshot");
   read_counters(e);
   std::vector<int32_t> member_new(e->nx.size(), 0);
@@ -1326,7 +1344,7 @@ TrgStatus trg_engine_export_csr(TrgEngine *e, TrgKind kind, TrgCsrView *out) {
   Csr *c = nullptr;
   if (kind == TRG_KIND_GLOBAL) {
     c = &e->csr_global;
-    if (e->pool_valid && (c->rowptr.empty() || c->state.size() != e->nx.size())) snapshot_csr(e, *c);
+    (void)ensure_csr_global(e);  // (false: neither the CSR nor the pool is current, the old rows stay in place)
   } else if (kind == TRG_KIND_PRECLEAN) {
     c = &e->csr_pre;
   } else if (kind == TRG_KIND_STITCHED) {
@@ -1429,13 +1447,8 @@ TrgStatus trg_engine_load_json(TrgEngine *e, const char *path) {
   e->node_id = (int)V;
   e->next_cid = (int)V;
   for (auto &ed : eds) e->edges.push(ed.s, ed.t, ed.w, ed.d);
-  e->kd_valid = false;
   grid_rebuild(e);
-  e->host_grid_valid = true;
-  e->pool_valid = true;
-  snapshot_csr(e, e->csr_global);
-  e->graph_version++;
-  invalidate_stitched(e);
+  host_graph_changed(e);
   return TRG_OK;
 }
 

@@ -1326,16 +1326,11 @@ TrgStatus Build::clean_and_fetch() {
   lap("clean kernels + CSR to host");
   e->node_id = Vn;
   lap("host graph state");
-  e->dev_csr_valid = Vn > 0;  // xyz2 / rowptr_new / col2 / w2 / dist2 / state2 hold the cleaned graph
-  e->real_map_stale = true;  // the real std::unordered_map is rebuilt only if a host path needs it
-  e->kd_order_dirty = true;  // node-tree refill order (trg.cpp:528-530) derived on demand
-  e->kd_valid = false;
-  e->graph_version++;
-  e->stitched_on_device = false;  // (the stitched rows belonged to the previous graph)
-  e->stitched_edges = 0;
-  e->csr_stitched.clear();
-  e->pool_valid = false;      // the host edge pool / node grid are rebuilt from the CSR on demand
-  e->host_grid_valid = false;
+  e->history_in_sim = true;  // the real std::unordered_map is rebuilt only if a host path needs it
+  // csr_global is here, and xyz2 / rowptr_new / col2 / w2 / dist2 / state2 hold the cleaned graph in HBM; the edge
+  // pool, the node grid and the node tree's refill order (trg.cpp:528-530) are derived on demand
+  if (Vn > 0) graph_changed(e, {TrgEngine::VIEW_CSR, TrgEngine::VIEW_DEV_CSR});
+  else graph_changed(e, {TrgEngine::VIEW_CSR});  // (nothing was cleaned into HBM)
   return TRG_OK;
 }
 

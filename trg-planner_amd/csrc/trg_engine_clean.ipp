@@ -106,7 +106,7 @@ void clean_graph(TrgEngine *e) {
   // new_nodes[new_id] = node for the dense new ids (trg.cpp:502), global_graph.nodes = new_nodes (:526:
   // bucket count, policy and element order of the source are taken over -- what moving it in leaves
   // behind); then the node tree is refilled in that map's iteration order
-  if (e->real_map_stale) {
+  if (e->history_in_sim) {
     MapOrderSim new_nodes;
     new_nodes.fill((size_t)Vn);
     e->nodes_sim.assign_from(new_nodes);
@@ -118,14 +118,10 @@ void clean_graph(TrgEngine *e) {
     e->kd_insert_order.clear();
     for (auto &kv : e->order_map) e->kd_insert_order.push_back(kv.first);
   }
-  e->kd_order_dirty = false;
-  e->kd_valid = false;
   lapc("container replica");
   grid_rebuild(e);
   lapc("node grid");
-  e->host_grid_valid = true;
-  e->pool_valid = true;
-}
+}  // (the caller commits: host_graph_changed)
 
 void read_counters(TrgEngine *e) {
   std::vector<DeviceCounters> h(COUNTER_SHARDS);
@@ -177,7 +173,6 @@ TrgStatus local_membership(TrgEngine *e, std::vector<int32_t> &n) {
 // cleanGraph, while the GPU is still awake: after ~10 ms without work the first launch takes ~2 ms)
 TrgStatus set_local_graph(TrgEngine *e, const std::vector<int32_t> *member = nullptr) {
   e->local_nodes.clear();
-  e->lkd.clear();
   const size_t V = e->nx.size();
   if (V == 0) {
     e->local_map.clear();
@@ -196,7 +191,6 @@ TrgStatus set_local_graph(TrgEngine *e, const std::vector<int32_t> *member = nul
   for (int id : global_order) {
     if (n[id] == 0) continue;
     e->local_map[id] = id;
-    e->lkd.insert(e->nx[id], e->ny[id], id);
   }
   for (auto &kv : e->local_map) e->local_nodes.push_back(kv.first);
   return TRG_OK;

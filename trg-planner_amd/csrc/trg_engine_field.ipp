@@ -180,7 +180,7 @@ constexpr uint32_t FIELD_INF_BITS = 0x7f800000u;
 
 // is the retained solve one of the engine's graph as it is now, its CSR still there
 bool field_last_current(const TrgEngine *e, const FieldBufs::Last &last) {
-  return last.version == e->graph_version && !(last.dev_csr && !e->dev_csr_valid);
+  return last.version == e->graph_version && (!last.dev_csr || dev_csr(e));
 }
 
 // the retained solve for `call` ("cost field routes", ...), or that call's refusal; `current`: a stale one is refused
@@ -367,8 +367,8 @@ TrgStatus field_graph(TrgEngine *e, FieldRun &run) {
   hipStream_t s = e->s_main;
   const Csr &G = e->csr_global;
   const int V = run.F.V, E = G.rowptr.empty() ? 0 : G.rowptr[V];
-  if (e->dev_csr_valid && e->bfs && e->bfs->rowptr_new.p) {
-    const BfsBuffers &bb = *e->bfs;
+  if (const BfsBuffers *dev = dev_csr(e)) {
+    const BfsBuffers &bb = *dev;
     run.G = {bb.rowptr_new.as<int>(), bb.col2.as<int>(), bb.state2.as<int>(), bb.w2.as<float>(), bb.dist2.as<float>(),
              E, true};
   } else {

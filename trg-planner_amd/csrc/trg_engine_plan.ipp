@@ -1,13 +1,15 @@
 // Part of trg_engine.cpp (included at file scope): planSafePath / setGoal / refinePath on the CSR (host A*,
 // trg.cpp:537-565, 603-730) and their C ABI entries.
+// In a text section of its own: the search loop's speed hangs by 1 to 2 % on where its code lies.
+#pragma clang section text = ".text.trg_plan"
 
 namespace {
 
 // positions in the node tree's insertion order (cleanGraph refills the tree in the node map's iteration
 // order, trg.cpp:525-530): only built when an answer really hangs on the tree's shape
 void ensure_kd_order_arrays(TrgEngine *e) {
-  if (e->kdo_version == e->graph_version) return;
-  materialize_kd_order(e);
+  if (e->current(TrgEngine::VIEW_KDO)) return;
+  ensure_kd_order(e);
   const size_t K = e->kd_insert_order.size();
   e->kdo_x.resize(K);
   e->kdo_y.resize(K);
@@ -18,7 +20,7 @@ void ensure_kd_order_arrays(TrgEngine *e) {
     e->kdo_y[k] = e->ny[id];
     e->kdo_index[id] = (int)k;
   }
-  e->kdo_version = e->graph_version;
+  e->view_stamp[TrgEngine::VIEW_KDO] = e->graph_version;
 }
 
 // kd_nearest2 on node_tree (trg.cpp:615): the grid answers; an exact fp32 distance tie goes to the
@@ -177,13 +179,8 @@ TrgStatus plan_on_csr(TrgEngine *e, PlanScratch &ps, int start, int goal, float 
 
 // common head of plan / plan_batch: graph present, CSR rows and node grid current
 TrgStatus plan_prepare(TrgEngine *e) {
-  const size_t V = e->nx.size();
-  if (V == 0) return e->fail(TRG_ERR_NO_GRAPH, "graph is empty");
-  const Csr &G = e->csr_global;
-  if (G.rowptr.size() != V + 1 || G.state.size() != V) {
-    if (!e->pool_valid) return e->fail(TRG_ERR_NO_GRAPH, "no CSR of the current graph");
-    snapshot_csr(e, e->csr_global);
-  }
+  if (e->nx.empty()) return e->fail(TRG_ERR_NO_GRAPH, "graph is empty");
+  if (!ensure_csr_global(e)) return e->fail(TRG_ERR_NO_GRAPH, "no CSR of the current graph");
   ensure_host_grid(e);
   return TRG_OK;
 }
@@ -344,3 +341,4 @@ int32_t trg_engine_refine_path(const float *in_xyz, int32_t n_in, float *out_xyz
 }
 
 }  // extern "C"
+#pragma clang section text = ""

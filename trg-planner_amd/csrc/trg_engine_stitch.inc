@@ -16,16 +16,15 @@ struct DevGraph {
 TrgStatus stitch_dev_graph(TrgEngine *e, bool need_edges, DevGraph *g) {
   StitchBufs &sb = *e->stitch;
   Csr &c = e->csr_global;
-  if (e->pool_valid && (c.rowptr.empty() || c.state.size() != e->nx.size())) snapshot_csr(e, c);
+  (void)ensure_csr_global(e);  // (false: neither the CSR nor the pool is current, the old rows stay in place)
   g->V = (int)c.state.size();
   g->E = (int)c.col.size();
-  BfsBuffers &bb = *e->bfs;
-  if (e->dev_csr_valid && bb.xyz2.p && bb.rowptr_new.p) {
-    g->xyz = (const float *)bb.xyz2.p;
-    g->rowptr = (const int *)bb.rowptr_new.p;
-    g->col = (const int *)bb.col2.p;
-    g->w = (const float *)bb.w2.p;
-    g->dist = (const float *)bb.dist2.p;
+  if (const BfsBuffers *bb = dev_csr(e)) {
+    g->xyz = (const float *)bb->xyz2.p;
+    g->rowptr = (const int *)bb->rowptr_new.p;
+    g->col = (const int *)bb->col2.p;
+    g->w = (const float *)bb->w2.p;
+    g->dist = (const float *)bb->dist2.p;
     return TRG_OK;
   }
   TrgStatus st;
@@ -57,7 +56,7 @@ TrgStatus stitch_dev_graph(TrgEngine *e, bool need_edges, DevGraph *g) {
 
 // the stitched rows from HBM into the host CSR (lazily, on the first export after an assemble)
 TrgStatus stitch_fetch(TrgEngine *e) {
-  if (!e->stitched_on_device) return TRG_OK;
+  if (!e->current(TrgEngine::VIEW_STITCH_DEV)) return TRG_OK;
   StitchBufs &sb = *e->stitch;
   Csr &out = e->csr_stitched;
   hipStream_t s = e->s_main;
@@ -74,7 +73,7 @@ TrgStatus stitch_fetch(TrgEngine *e) {
     HIPCHK(e, hipMemcpyAsync(out.dist.data(), sb.dist_new.p, (size_t)En * 4, hipMemcpyDeviceToHost, s));
   }
   HIPCHK(e, hipStreamSynchronize(s));
-  e->stitched_on_device = false;
+  e->view_stamp[TrgEngine::VIEW_STITCH_DEV] = 0;
   return TRG_OK;
 }
 
@@ -202,7 +201,7 @@ TrgStatus trg_engine_stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles,
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_assemble: node_offsets do not match this tile's graph");
   Csr &out = e->csr_stitched;
   out.clear();
-  e->stitched_on_device = false;
+  e->view_stamp[TrgEngine::VIEW_STITCH_DEV] = 0;
   e->stitched_edges = 0;
   const Csr &c = e->csr_global;
   out.xyz = c.xyz;
@@ -238,14 +237,14 @@ TrgStatus trg_engine_stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles,
                          (int *)sb.fill.p, (int *)sb.col_new.p, (float *)sb.w_new.p, (float *)sb.dist_new.p, 1, s);
   // the rows stay in HBM; trg_engine_export_csr(TRG_KIND_STITCHED) fetches them when asked
   e->stitched_edges = En;
-  e->stitched_on_device = true;
+  e->view_stamp[TrgEngine::VIEW_STITCH_DEV] = e->graph_version;
   HIPCHK(e, hipGetLastError());
   return TRG_OK;
 }
 
 TrgStatus trg_engine_graph_sizes(TrgEngine *e, TrgKind kind, int32_t *num_nodes, int32_t *num_edges) {
   if (!e || !num_nodes || !num_edges) return TRG_ERR_INVALID_ARG;
-  if (kind == TRG_KIND_STITCHED && e->stitched_on_device) {
+  if (kind == TRG_KIND_STITCHED) {  // (without fetching rows that are still in HBM)
     *num_nodes = (int32_t)e->csr_stitched.state.size();
     *num_edges = e->stitched_edges;
     return TRG_OK;
