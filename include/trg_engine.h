@@ -491,7 +491,8 @@ TrgStatus trg_engine_cost_field_models(
  * trg_engine_field_routes walks the parents; the route edge into p_i is the relaxable edge of least CSR index in row
  * p_{i-1} with col p_i that is tight and steps the hops by one; TrgRouteInfo.cost is risk[target], path_length and
  * avg_risk are as for a cost solve.  trg_engine_cost_field_refresh refuses a retained risk solve
- * (TRG_ERR_INVALID_ARG, the message says so) and leaves it answering routes, as it does for a bounded one.
+ * (TRG_ERR_INVALID_ARG, the message says so) and leaves it answering routes, as it does for a bounded one;
+ * trg_engine_risk_field_refresh (below) is the call that refreshes it.
  * TRG_ERR_INVALID_ARG when some edge weight is NaN, negative (-0 is not) or infinite -- taken over ALL edges, as the
  * bad-cost flag of a cost solve is, and like it after the previously retained solve is gone; the other argument,
  * capacity and device errors are trg_engine_cost_field_sets'. */
@@ -579,6 +580,20 @@ TrgStatus trg_engine_cost_field_refresh(TrgEngine *e,
     const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at,
     int32_t *owner, int32_t *owner_at,                      /* set solves only */
     int32_t *sources_out, int32_t *reached_out, int32_t *carried_out,   /* m */
+    TrgFieldInfo *info);
+/* trg_engine_cost_field_refresh for a retained RISK solve ("Risk fields"): the same steps with
+ * the edge risks in the place of the edge costs and max in the place of +, and the result -- risk bits, hops,
+ * parents, owners, reached -- that of a fresh trg_engine_risk_field_sets call from the same sets on the current
+ * graph.  The differences: risk / risk_at are risks; a retained COST solve is refused (TRG_ERR_INVALID_ARG, the
+ * message names trg_engine_cost_field_refresh) and left answering, as that call refuses a risk solve; and an edge
+ * weight of the current graph that is NaN, negative or infinite is TRG_ERR_INVALID_ARG as in a fresh risk solve --
+ * found after the retained solve is gone, so nothing is retained afterwards. */
+TrgStatus trg_engine_risk_field_refresh(TrgEngine *e,
+    const int32_t *new2old, int32_t n_map,
+    float *risk, int32_t *hops, int32_t *parent,
+    const int32_t *targets, int32_t n_targets, float *risk_at, int32_t *hops_at,
+    int32_t *owner, int32_t *owner_at,
+    int32_t *sources_out, int32_t *reached_out, int32_t *carried_out,
     TrgFieldInfo *info);
 
 /* ---- instrumentation ------------------------------------------------------------------------- */

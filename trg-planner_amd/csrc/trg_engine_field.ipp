@@ -5,7 +5,8 @@
 // the refresh (trg_engine_cost_field_refresh) is a request of its own kind to the same field_solve: a check phase
 // before the others, the retained keys carried in before the work arrays, and passes that start warm.  A risk field
 // (trg_engine_risk_field_sets; DESIGN.md section 2, "Risk fields") is the set entry's request with one flag: the
-// edge risks in the place of the edge costs, and kernels that extend a key by max instead of +.
+// edge risks in the place of the edge costs, and kernels that extend a key by max instead of +; its refresh
+// (trg_engine_risk_field_refresh) is the refresh request with that flag.
 
 namespace {
 
@@ -129,7 +130,9 @@ struct FieldRequest {
   const int32_t *new2old;  // n_map entries, or nullptr: the engine's map
   int32_t n_map;
   int32_t *carried_out;    // m
-  // a risk solve (trg_engine_risk_field_sets): cost / cost_at / budget / bound_out are risks; never with models
+  // a risk solve (trg_engine_risk_field_sets): cost / cost_at / budget / bound_out are risks; never with models.
+  // With `refresh` (trg_engine_risk_field_refresh): the objective the entry refreshes, which the retained solve's
+  // must match.
   bool risk;
 };
 static_assert(TRG_FIELD_SETTLE_NONE == 0, "a value-initialised request has no settle mode");
@@ -196,16 +199,21 @@ TrgStatus field_retained(TrgEngine *e, const std::string &call, FieldBufs::Last 
 // The check phase of a refresh ("Refresh"), before field_check_request's: the retained solve
 // must be there, unbounded and stale; the node map is the given one, the engine's, or the identity; and m and the
 // sources or sets of the request become the retained solve's, as ids of the current graph.  Like every refusal
-// before field_begin, these leave the retained solve as it was.
+// before field_begin, these leave the retained solve as it was.  rq.risk is the objective of the entry that was
+// called: each entry refreshes the solves of its own objective only, and a match takes the flag from the retained solve.
 TrgStatus field_check_refresh(TrgEngine *e, FieldRun &run) {
   FieldRequest &rq = run.rq;
-  const std::string call = "cost field refresh";
+  const std::string call = rq.risk ? "risk field refresh" : "cost field refresh";
   FieldBufs::Last *last;
   if (const TrgStatus st = field_retained(e, call, last, false); st != TRG_OK) return st;
   const FieldBufs::Last &old = *last;
-  if (old.risk)
-    return e->fail(TRG_ERR_INVALID_ARG,
-                   call + ": the retained solve is a risk field (a risk field cannot be refreshed)");
+  if (old.risk && !rq.risk)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is a risk field (this call refreshes a cost "
+                                               "field; use trg_engine_risk_field_refresh)");
+  if (!old.risk && rq.risk)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is a cost field (this call refreshes a risk "
+                                               "field; use trg_engine_cost_field_refresh)");
+  rq.risk = old.risk;
   if (old.bounded)
     return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is bounded (a bounded solve cannot be refreshed)");
   if (field_last_current(e, old))
@@ -667,12 +675,12 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
     } else {
       if (pass == 0) {
         launch_field_init(F, run.sources, sets, fb.key0.as<unsigned long long>(), delta, s);
-        launch_field_supporters(F, s, models);
+        launch_field_supporters(F, s, models, rq.risk);
       }
       if ((st = field_anchor(e, run, pass == 0)) != TRG_OK) return st;
       if (pass == 0)
         HIPCHK(e, hipMemcpyAsync(fb.h_carried, fb.carried.p, (size_t)F.m * sizeof(int), hipMemcpyDeviceToHost, s));
-      launch_field_warm_start(F, delta, pass == 1, s, models);
+      launch_field_warm_start(F, delta, pass == 1, s, models, rq.risk);
     }
     if ((st = field_rounds(e, run, under_bounds ? &under : nullptr)) != TRG_OK) return st;
     if (under_bounds) {
@@ -1148,6 +1156,25 @@ TrgStatus trg_engine_cost_field_refresh(TrgEngine *e, const int32_t *new2old, in
     rq.owner_at = owner_at;
     rq.sources_out = sources_out;
     rq.carried_out = carried_out;
+    return field_solve(e, rq, out);
+  });
+}
+
+TrgStatus trg_engine_risk_field_refresh(TrgEngine *e, const int32_t *new2old, int32_t n_map, float *risk,
+                                        int32_t *hops, int32_t *parent, const int32_t *targets, int32_t n_targets,
+                                        float *risk_at, int32_t *hops_at, int32_t *owner, int32_t *owner_at,
+                                        int32_t *sources_out, int32_t *reached_out, int32_t *carried_out,
+                                        TrgFieldInfo *info) {
+  return field_entry(e, info, "risk field refresh", [&](TrgFieldInfo *out) {
+    FieldRequest rq = field_request(0, risk, hops, parent, targets, n_targets, risk_at, hops_at, reached_out);
+    rq.refresh = true;
+    rq.new2old = new2old;
+    rq.n_map = n_map;
+    rq.owner = owner;
+    rq.owner_at = owner_at;
+    rq.sources_out = sources_out;
+    rq.carried_out = carried_out;
+    rq.risk = true;  // (the objective this entry refreshes: field_check_refresh)
     return field_solve(e, rq, out);
   });
 }

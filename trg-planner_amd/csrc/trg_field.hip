@@ -63,10 +63,13 @@
 // The extension is (max(risk, r), hops + 1) with r = w + 0 -- monotone in the risk word and never below it, which is
 // all the argument above asks of fl(a + c), and it never rounds.  The hop word is no more monotone than under
 // rounding (a < a' gives max(a, r) == max(a', r) for every r >= a'), so the two passes stay.  The kernels that read an
-// edge value (relax, parent sweep, route walk) have a RISK instantiation whose only difference is that extension; it
-// never combines with MODELS (a risk solve has no cost model), and a risk solve is never refreshed, so there is no RISK
-// warm seed.  The edge risks lie in a slot of the edge-cost array (k_field_edge_risk); every kernel that looks at cost
-// bits only is used as it is.
+// edge value (relax, parent sweep, route walk, warm seed) have a RISK instantiation whose only difference is that
+// extension; it never combines with MODELS (a risk solve has no cost model).  The edge risks lie in a slot of the
+// edge-cost array (k_field_edge_risk); every kernel that looks at cost bits only is used as it is.  A risk solve is
+// refreshed by the steps of the cost refresh ("Risk fields"): carry, anchors, warm init, rounds
+// and finish look at key bits only or have their RISK form, and the RISK warm seed queues by the maximum.  A bucket
+// width of 0 (all-zero weights) takes the warm control block, which starts at threshold 0, down the path of a cold one:
+// every push goes far, and next_threshold opens the bucket one word above the least live risk.
 //
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"
@@ -862,10 +865,11 @@ __global__ __launch_bounds__(THREADS) void k_field_warm_init(FieldDev F, float d
 
 // The seeding sweep of a warm pass: one 16-lane group per item, four per wave, as k_field_relax -- but over every
 // item with a key, writing no key: an item one of whose edges would improve its target is pushed, once, to far
-// pile 0, stamped with phase 1.  TIGHT: pass 2, tight edges only.  MODELS: as k_field_relax's.
-template <bool MULTI, bool TIGHT, bool MODELS>
+// pile 0, stamped with phase 1.  TIGHT: pass 2, tight edges only.  MODELS, RISK: as k_field_relax's.
+template <bool MULTI, bool TIGHT, bool MODELS, bool RISK = false>
 __global__ __launch_bounds__(THREADS) void k_field_warm_seed(FieldDev F, FieldModelsArg<MODELS> M) {
   static_assert(MULTI || !MODELS, "one field has one model: the host points F.ec at its slot");
+  static_assert(!(RISK && MODELS), "a risk field has no cost model");
   const int N = MULTI ? F.N : F.V;
   const int sub = threadIdx.x & (GROUP - 1);
   const int gw = lane_id() / GROUP;
@@ -902,7 +906,7 @@ __global__ __launch_bounds__(THREADS) void k_field_warm_seed(FieldDev F, FieldMo
         if (__float_as_uint(c) != FIELD_EDGE_SKIP) {
           int v = F.col[k];
           if constexpr (MULTI) v += fbase;
-          const unsigned long long nk = key_extend(ku, c);
+          const unsigned long long nk = key_extend<RISK>(ku, c);
           const bool tight = !TIGHT || (unsigned)(nk >> 32) == F.tight[v];
           any |= tight && nk < F.key[v];
         }
@@ -1098,12 +1102,18 @@ void launch_field_anchor_end(const FieldDev &F, int sweeps, unsigned long long *
 }
 
 void launch_field_warm_start(const FieldDev &F, float delta, bool reset_parents, hipStream_t s,
-                             const FieldModels *models) {
+                             const FieldModels *models, bool risk) {
   hipLaunchKernelGGL(k_field_warm_init, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, F, delta,
                      reset_parents);
   const dim3 grid(field_blocks((long long)F.N * GROUP, THREADS));
   const FieldNoModels none{};
-  if (F.m == 1) {
+  if (risk && F.m == 1) {
+    if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<false, true, false, true>), grid, dim3(THREADS), 0, s, F, none);
+    else hipLaunchKernelGGL((k_field_warm_seed<false, false, false, true>), grid, dim3(THREADS), 0, s, F, none);
+  } else if (risk) {
+    if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<true, true, false, true>), grid, dim3(THREADS), 0, s, F, none);
+    else hipLaunchKernelGGL((k_field_warm_seed<true, false, false, true>), grid, dim3(THREADS), 0, s, F, none);
+  } else if (F.m == 1) {
     if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<false, true, false>), grid, dim3(THREADS), 0, s, F, none);
     else hipLaunchKernelGGL((k_field_warm_seed<false, false, false>), grid, dim3(THREADS), 0, s, F, none);
   } else if (!models) {

@@ -581,6 +581,6 @@ void launch_field_anchor_end(const FieldDev &F, int sweeps, unsigned long long *
 // launch_field_round from round 0 on then runs to the same fixed point as a pass from launch_field_init, provided
 // every key is one that a walk of the graph has.  reset_parents: F.parent = INT_MAX, for the last parent sweep.
 void launch_field_warm_start(const FieldDev &F, float delta, bool reset_parents, hipStream_t s,
-                             const FieldModels *models = nullptr);
+                             const FieldModels *models = nullptr, bool risk = false);
 
 }  // namespace trg

@@ -108,7 +108,7 @@ EXPORTS = [
     "trg_engine_stitch_exchange", "trg_engine_cost_field", "trg_engine_cost_field_batch",
     "trg_engine_field_routes", "trg_engine_cost_field_bounded", "trg_engine_field_reached",
     "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh", "trg_engine_cost_field_models",
-    "trg_engine_risk_field_sets",
+    "trg_engine_risk_field_sets", "trg_engine_risk_field_refresh",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -209,6 +209,7 @@ def load_library():
     L.trg_engine_risk_field_sets.argtypes = L.trg_engine_cost_field_sets.argtypes
     L.trg_engine_cost_field_refresh.argtypes = [vp, ip, C.c_int32, fp, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, ip, ip,
                                                 C.POINTER(TrgFieldInfo)]
+    L.trg_engine_risk_field_refresh.argtypes = L.trg_engine_cost_field_refresh.argtypes
     L.trg_engine_fallback_reason.argtypes = [vp]
     L.trg_engine_fallback_reason.restype = C.c_char_p
     _lib = L
@@ -272,6 +273,7 @@ class Engine:
                 self.h = C.c_void_p()
             raise TrgError(st, msg)
         self.sampler = TrgSampler(1, 16)
+        self.last_reuse = None  # frontier_ceilings(reuse=True): the refresh's dict when it was taken
 
     def close(self):
         if getattr(self, "h", None):
@@ -614,7 +616,8 @@ class Engine:
         -> cost_fields' dict ("cost", "hops", "parent" (m, V) with `full`; "cost_at", "hops_at" (m, n_t) with
         `targets`; "sources" as ids of the current graph, "reached", "info") plus "carried" (m counts of nodes whose
         old key could be kept as a starting point), and for a retained set solve "owner" / "owner_at".  Afterwards
-        routes and field_reached answer from the refreshed solve."""
+        routes and field_reached answer from the refreshed solve.  A retained risk solve is refused:
+        refresh_risk_fields is its call."""
         # (fields, from sets) of the retained solve, which only this object's solves can have left; without one the
         # call refuses before it writes anything
         m, sets = getattr(self, "_field_shape", (1, False))
@@ -920,7 +923,8 @@ class Engine:
         "info".  `budget` is a risk ceiling (a node of greater risk comes back unreached, every other one as in the full
         field), `settle` "any" / "all" lowers it to the least / greatest risk over `targets`; with either the result
         has "bound".  The solve is retained: routes and field_reached answer from it (a route's cost is its target's
-        risk); refresh_fields refuses it."""
+        risk); after update_graph calls refresh_risk_fields brings it to the current graph (refresh_fields, the cost
+        fields' call, refuses it)."""
         if sources_xy is None and source_ids is None:
             raise ValueError("risk_fields needs sources_xy or source_ids")
         ids = None if source_ids is None else np.ascontiguousarray(source_ids, dtype=np.int32).reshape(-1)
@@ -958,6 +962,9 @@ class Engine:
             self.h, m, _i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
             _i(owned) if owners else None, a["reached"], a["bound"], C.byref(info)))
         self._field_shape = (m, True)
+        # what refresh_risk_fields has to know of this solve: its fields, whether it came from risk_fields_from (the
+        # owners are then part of the result), and whether it is one field from a set of one (what `reuse` asks for)
+        self._risk_shape = (m, owners, m == 1 and sets[0].shape[0] == 1)
         for old, new in (("cost", "risk"), ("cost_at", "risk_at")):
             if old in out:
                 out[new] = out.pop(old)
@@ -989,19 +996,67 @@ class Engine:
         route = self.routes([0], [goal], hops_at=r["hops_at"][:, 0])[0]
         return tau, self._route_record(r["models"][0], *route)
 
-    def frontier_ceilings(self, pose_xy):
+    def refresh_risk_fields(self, new2old=None, targets=None, full=True):
+        """refresh_fields for a retained RISK solve (risk_fields or risk_fields_from before the last update_graph
+        calls): trg_engine_risk_field_refresh, DESIGN.md section 2, "Risk fields".  The result is that of a fresh risk
+        solve from the same sources or sets on the current graph, bit for bit.  new2old as refresh_fields'.
+        -> refresh_fields' dict with "risk" / "risk_at" where that has "cost" / "cost_at" ("hops", "parent" (m, V) with
+        `full`; "hops_at" with `targets`; "sources", "reached", "carried", "info"), and "owner" / "owner_at" only when
+        the retained solve came from risk_fields_from.  A retained cost solve is refused (refresh_fields is its call),
+        as are a bounded risk solve and one that is already current; a refused call leaves the retained solve answering.
+        A NaN, negative or infinite weight on the current graph raises as in risk_fields, and nothing is retained
+        afterwards.  Afterwards routes and field_reached answer from the refreshed solve."""
+        m, owners, _ = getattr(self, "_risk_shape", (1, False, False))
+        n2o = None if new2old is None else np.ascontiguousarray(new2old, dtype=np.int32).reshape(-1)
+        out, a = self._field_outputs("refresh_risk_fields", m, targets, full, None, None, owners=owners)
+        out["sources"] = np.full(m, -1, np.int32)
+        out["carried"] = np.zeros(m, np.int32)
+        info = TrgFieldInfo()
+        self._chk(self.L.trg_engine_risk_field_refresh(
+            self.h, None if n2o is None else _i(n2o), 0 if n2o is None else n2o.shape[0], *a["full"], *a["at"],
+            a["owner"], a["owner_at"], _i(out["sources"]), a["reached"], _i(out["carried"]), C.byref(info)))
+        for old, new in (("cost", "risk"), ("cost_at", "risk_at")):
+            if old in out:
+                out[new] = out.pop(old)
+        out["info"] = info
+        return out
+
+    def _risk_field_reused(self, node, frontier):
+        """frontier_ceilings' `reuse`: the retained risk solve refreshed and read at `frontier`, if it is one field from
+        the one node `node` (an id of the current graph) -> refresh_risk_fields' dict, or None: solve afresh.  Whatever
+        the refresh refuses (nothing retained, a cost solve, a bounded one, already current, no map) ends here too."""
+        if not getattr(self, "_risk_shape", (1, False, False))[2]:
+            return None
+        try:
+            r = self.refresh_risk_fields(targets=frontier, full=False)
+        except TrgError:
+            return None
+        return r if int(r["sources"][0]) == node else None
+
+    def frontier_ceilings(self, pose_xy, reuse=False):
         """For every Frontier node the least risk ceiling under which it can be reached from `pose_xy`: one risk field
         read at the Frontier nodes on the device -> (frontier ids int32 ascending, risk float32 (+inf: unreachable),
-        hops int32 (-1: unreachable)); nothing of V entries is copied back."""
+        hops int32 (-1: unreachable)); nothing of V entries is copied back.
+        reuse: first try to refresh the retained risk solve (refresh_risk_fields) instead of solving -- taken only when
+        that solve is one field from one node, that node is the one `pose_xy` resolves to on the current graph, and the
+        refresh does not refuse; else the field is solved afresh.  The result is the same bit for bit either way.  It
+        pays when the pose still resolves to the same node as at the last call, with update_graph calls in between.
+        `last_reuse` is then the refresh's dict ("carried", "info"), None when the field was solved afresh."""
         frontier = self._frontier_ids()
-        r = self.risk_fields(sources_xy=np.asarray(pose_xy, np.float32).reshape(1, 2), targets=frontier, full=False)
+        xy = np.asarray(pose_xy, np.float32).reshape(1, 2)
+        self.last_reuse = None
+        if reuse:
+            self.last_reuse = self._risk_field_reused(int(self._resolve_nodes(xy)[0]), frontier)
+        r = self.last_reuse
+        if r is None:
+            r = self.risk_fields(sources_xy=xy, targets=frontier, full=False)
         return frontier, r["risk_at"][0], r["hops_at"][0]
 
-    def safest_frontier(self, pose_xy):
+    def safest_frontier(self, pose_xy, reuse=False):
         """The Frontier node that is safest to reach from `pose_xy`: the least (risk, hops, id) among the reachable
         Frontier nodes, with its route in the minimax tree from one routes call -> (node, risk, path ids), or None
-        without a reachable one."""
-        frontier, risk, hops = self.frontier_ceilings(pose_xy)
+        without a reachable one.  reuse: as frontier_ceilings'."""
+        frontier, risk, hops = self.frontier_ceilings(pose_xy, reuse=reuse)
         pick = choose_frontier(frontier, risk, hops)
         if pick is None:
             return None
