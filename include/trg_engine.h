@@ -6,6 +6,13 @@
  * (reference: cpp/trg_planner/core/trg_planner/include/graph/trg.h:50-98 and
  * src/graph/trg.cpp).  Plain pointers and sizes only; no C++/torch types; no exceptions cross
  * the boundary; every call returns a TrgStatus and trg_engine_last_error() explains failures.
+ * A failure inside the library itself (host memory exhausted, a thread or a stream that cannot be
+ * made) comes back the same way: TRG_ERR_CAPACITY "<call>: out of host memory", or TRG_ERR_DEVICE
+ * with the cause.  After such a status, as after any failed HIP call in the middle of a build or an
+ * update, trg_engine_last_error explains it and trg_engine_destroy, trg_engine_reset_graph and
+ * trg_engine_init_graph are safe; the graph of the call that failed mid-way is unspecified until
+ * one of those.  (The three entries that answer with a number -- check_reached, check_replan,
+ * refine_path -- answer 0.)
  *
  * Each entry point cites the reference interface it replaces.  The C++ `TRG`/`TRGPlanner`
  * shims, the Python mirror (trg-planner_amd/trg_planner) and the reference-side binding shown
@@ -168,7 +175,9 @@ typedef struct TrgStats {
 } TrgStats;
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
-/* reference: TRG::TRG(...) trg.cpp:11-34.  device = HIP device ordinal. */
+/* reference: TRG::TRG(...) trg.cpp:11-34.  device = HIP device ordinal.  On failure *out is an engine that
+ * explains it (trg_engine_last_error) and is to be destroyed, or NULL where not even that could be made
+ * (TRG_ERR_CAPACITY). */
 TrgStatus trg_engine_create(const TrgParams *params, int device, TrgEngine **out);
 void trg_engine_destroy(TrgEngine *e);
 const char *trg_engine_last_error(const TrgEngine *e);
@@ -302,7 +311,8 @@ TrgStatus trg_engine_stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles,
  * run time): steps 1-3 above with an all-gather of counts + an all-gather of padded payloads between them.
  * rank = tile, ranks = cols * rows.  The communicator is either made here from a unique id that ONE rank
  * draws and the application hands to every rank (MPI_Bcast, a file, torch.distributed ...), or adopted
- * from the caller (an ncclComm_t of the SAME librccl instance).  A rank whose own step fails announces it
+ * from the caller (an ncclComm_t of the SAME librccl instance; one that is refused, for more ranks than the
+ * stitch has tiles, is not kept, and the engine is then without a communicator).  A rank whose own step fails announces it
  * in the next count exchange, so its peers return an error instead of waiting.  Read the result with
  * trg_engine_export_csr(TRG_KIND_STITCHED).  (Replaces nothing in the reference: TRG has no multi-device
  * build) */

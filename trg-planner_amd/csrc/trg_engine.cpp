@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/trg_engine.h"
+#include "abi_frame.h"
 #include "graph_json.h"
 #include "host_index.h"
 #include "map_order_sim.h"
@@ -55,15 +56,8 @@ inline float norm2f(float dx, float dy) { return sqrtf(dx * dx + dy * dy); }
 template <typename F>
 void parallel_ranges(size_t n, F fn) {
   const size_t hw = std::max(1u, std::thread::hardware_concurrency());
-  const size_t T = std::min<size_t>(std::min<size_t>(8, hw), (n + 65535) / 65536);
-  if (T <= 1) {
-    fn((size_t)0, n);
-    return;
-  }
-  std::vector<std::thread> thr;
-  for (size_t t = 1; t < T; ++t) thr.emplace_back(fn, n * t / T, n * (t + 1) / T);
-  fn((size_t)0, n / T);
-  for (auto &th : thr) th.join();
+  const size_t T = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(8, hw), (n + 65535) / 65536));
+  fork_join(T, [&](size_t t) { fn(n * t / T, n * (t + 1) / T); });
 }
 
 // ---- owners of GPU resources ---------------------------------------------------------------------
@@ -516,7 +510,7 @@ struct TrgEngine {
   int wall_clock_khz = 0;  // rate of the device's constant wall clock (wall_clock64)
   std::string err;
   std::string arch;
-  bool device_ok = false;  // create went through: the entry points run (REQUIRE_DEVICE)
+  bool device_ok = false;  // create went through: the entry points run (entry(), DEVICE)
 
   Stream s_main, s_edge;
   Stream s_aux;  // rare-event work (nearest-point tie walks) beside whatever the main stream holds
@@ -660,6 +654,21 @@ namespace {
       return (e)->fail(TRG_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_err)); \
     }                                                                                     \
   } while (0)
+
+// The frame of every C entry that takes an engine: the engine is there (ENGINE), it has a device and that device is
+// current (DEVICE), and body() runs behind the exception ladder of abi_frame.h with `call` as the message's prefix.
+enum EntryNeed { ENGINE, DEVICE };
+template <typename Body>
+TrgStatus entry(TrgEngine *e, const char *call, EntryNeed need, Body body) {
+  if (!e) return TRG_ERR_INVALID_ARG;
+  return abi_guard(call, [e](TrgStatus s, const std::string &m) { return e->fail(s, m); }, [&]() -> TrgStatus {
+    if (need == DEVICE) {
+      if (!e->device_ok) return e->fail(TRG_ERR_DEVICE, "engine has no usable device");
+      if (hipSetDevice(e->device) != hipSuccess) return e->fail(TRG_ERR_DEVICE, "hipSetDevice failed");
+    }
+    return body();
+  });
+}
 
 // growth with head-room for arrays that creep up from build to build (keep: the contents move along)
 TrgStatus ensure_bytes(TrgEngine *e, DevArr &a, size_t need, bool keep = false) {
@@ -933,11 +942,12 @@ const BfsBuffers *dev_csr(const TrgEngine *e) {
 }  // namespace
 
 // =================================== C ABI ======================================================
-extern "C" {
+// Every entry reads the same way: the argument checks that need no engine, then entry() around a named function of
+// this namespace (the probes, the planner, the fields, the stitch and the exchange follow in their own files).  No
+// code calls a trg_engine_* symbol: what two entries share is a function here.
+namespace {
 
-TrgStatus trg_engine_create(const TrgParams *params, int device, TrgEngine **out) {
-  if (!params || !out) return TRG_ERR_INVALID_ARG;
-  *out = nullptr;
+TrgStatus create_engine(const TrgParams *params, int device, TrgEngine **out) {
   TrgEngine *e = new TrgEngine();
   e->prm = *params;
   e->device = device;
@@ -976,30 +986,7 @@ TrgStatus trg_engine_create(const TrgParams *params, int device, TrgEngine **out
   return TRG_OK;
 }
 
-void trg_engine_destroy(TrgEngine *e) {
-  if (!e) return;
-  // the main stream is the first thing create makes on the device: without it every owner is empty, and
-  // nothing below needs a device (there may be none)
-  if (e->s_main) {
-    (void)hipSetDevice(e->device);
-    (void)hipDeviceSynchronize();
-  }
-  delete e;  // the order of release is the members' order, see TrgEngine
-}
-
-const char *trg_engine_last_error(const TrgEngine *e) { return e ? e->err.c_str() : "null engine"; }
-const char *trg_engine_device_arch(const TrgEngine *e) { return e ? e->arch.c_str() : ""; }
-
-#define REQUIRE_DEVICE(e)                                                              \
-  do {                                                                                 \
-    if (!(e)) return TRG_ERR_INVALID_ARG;                                              \
-    if (!(e)->device_ok) return (e)->fail(TRG_ERR_DEVICE, "engine has no usable device"); \
-    if (hipSetDevice((e)->device) != hipSuccess)                                       \
-      return (e)->fail(TRG_ERR_DEVICE, "hipSetDevice failed");                         \
-  } while (0)
-
-TrgStatus trg_engine_set_global_map(TrgEngine *e, const float *xyz, size_t n, size_t stride) {
-  REQUIRE_DEVICE(e);
+TrgStatus set_global_map(TrgEngine *e, const float *xyz, size_t n, size_t stride) {
   if ((n && !xyz) || stride < 3) return e->fail(TRG_ERR_INVALID_ARG, "bad map arguments");
   auto t0 = Clock::now();
   TrgStatus st = upload_and_build(e, e->gmap, xyz, n, stride);
@@ -1007,9 +994,7 @@ TrgStatus trg_engine_set_global_map(TrgEngine *e, const float *xyz, size_t n, si
   return st;
 }
 
-TrgStatus trg_engine_set_global_map_device(TrgEngine *e, const float *d_xyz, size_t n,
-                                           size_t stride) {
-  REQUIRE_DEVICE(e);
+TrgStatus set_global_map_device(TrgEngine *e, const float *d_xyz, size_t n, size_t stride) {
   if ((n && !d_xyz) || stride < 3) return e->fail(TRG_ERR_INVALID_ARG, "bad map arguments");
   if (n == 0) {
     e->gmap.n = 0;
@@ -1019,9 +1004,7 @@ TrgStatus trg_engine_set_global_map_device(TrgEngine *e, const float *d_xyz, siz
   return build_map(e, e->gmap, d_xyz, n, stride);
 }
 
-TrgStatus trg_engine_set_local_map(TrgEngine *e, const float start_xy[2], const float *xyz,
-                                   size_t n, size_t stride) {
-  REQUIRE_DEVICE(e);
+TrgStatus set_local_map(TrgEngine *e, const float start_xy[2], const float *xyz, size_t n, size_t stride) {
   if (!start_xy || (n && !xyz) || stride < 3) return e->fail(TRG_ERR_INVALID_ARG, "bad arguments");
   e->local_root[0] = start_xy[0];
   e->local_root[1] = start_xy[1];
@@ -1030,8 +1013,7 @@ TrgStatus trg_engine_set_local_map(TrgEngine *e, const float start_xy[2], const 
   return set_local_graph(e);
 }
 
-TrgStatus trg_engine_reset_map(TrgEngine *e, TrgKind kind) {
-  REQUIRE_DEVICE(e);
+TrgStatus reset_map(TrgEngine *e, TrgKind kind) {
   DevMap *m = pick_map(e, kind);
   m->top_wait();  // (a helper preparing the map's tie-break structures still reads it)
   m->n = 0;
@@ -1039,8 +1021,7 @@ TrgStatus trg_engine_reset_map(TrgEngine *e, TrgKind kind) {
   return TRG_OK;
 }
 
-TrgStatus trg_engine_reset_graph(TrgEngine *e, TrgKind kind) {
-  REQUIRE_DEVICE(e);
+TrgStatus reset_graph(TrgEngine *e, TrgKind kind) {
   if (kind == TRG_KIND_LOCAL) {
     e->local_nodes.clear();
     e->local_map.clear();
@@ -1053,8 +1034,7 @@ TrgStatus trg_engine_reset_graph(TrgEngine *e, TrgKind kind) {
   return TRG_OK;
 }
 
-TrgStatus trg_engine_init_graph(TrgEngine *e, const float start_xyz[3], const TrgSampler *sampler) {
-  REQUIRE_DEVICE(e);
+TrgStatus init_graph(TrgEngine *e, const float start_xyz[3], const TrgSampler *sampler) {
   if (!start_xyz) return e->fail(TRG_ERR_INVALID_ARG, "null start");
   if (!e->gmap.valid || e->gmap.n == 0) return e->fail(TRG_ERR_NO_MAP, "Map is empty");
   auto t_total = Clock::now();
@@ -1149,8 +1129,7 @@ TrgStatus trg_engine_init_graph(TrgEngine *e, const float start_xyz[3], const Tr
   return TRG_OK;
 }
 
-TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value) {
-  if (!e || !key || !value) return TRG_ERR_INVALID_ARG;
+TrgStatus set_option(TrgEngine *e, const char *key, const char *value) {
   enum Kind {
     INT,             // atoi
     BOOL,            // anything but "0" is true
@@ -1214,8 +1193,7 @@ TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value
   return e->fail(TRG_ERR_INVALID_ARG, "unknown option " + k);
 }
 
-TrgStatus trg_engine_set_tile(TrgEngine *e, const float core_xyxy[4], uint32_t epoch) {
-  if (!e) return TRG_ERR_INVALID_ARG;
+TrgStatus set_tile(TrgEngine *e, const float core_xyxy[4], uint32_t epoch) {
   if (core_xyxy) {
     for (int i = 0; i < 4; ++i) e->core[i] = core_xyxy[i];
   } else {
@@ -1226,12 +1204,9 @@ TrgStatus trg_engine_set_tile(TrgEngine *e, const float core_xyxy[4], uint32_t e
   return TRG_OK;
 }
 
-const char *trg_engine_fallback_reason(const TrgEngine *e) {
-  return e ? e->bfs_fallback_reason.c_str() : "";
-}
+TrgStatus is_frontier_batch(TrgEngine *e, const float *xy, size_t m, int32_t *flag);  // (with the probes, below)
 
-TrgStatus trg_engine_update_graph(TrgEngine *e) {
-  REQUIRE_DEVICE(e);
+TrgStatus update_graph(TrgEngine *e) {
   if (!e->gmap.valid) return e->fail(TRG_ERR_NO_MAP, "Map is empty");
   TrgStatus st = ensure_sampler(e, nullptr);
   if (st != TRG_OK) return st;
@@ -1264,7 +1239,7 @@ TrgStatus trg_engine_update_graph(TrgEngine *e) {
     st = collision_sync(e, e->lmap, e->prm.update_collision_threshold, xy.data(), L, col.data(),
                         nullptr, nullptr);
     if (st != TRG_OK) return st;
-    st = trg_engine_is_frontier_batch(e, xy.data(), L, fro.data());
+    st = is_frontier_batch(e, xy.data(), L, fro.data());
     if (st != TRG_OK) return st;
   }
   std::vector<int> expand_queue;
@@ -1339,8 +1314,7 @@ TrgStatus trg_engine_update_graph(TrgEngine *e) {
   return st;  // cleanGraph(true) -> setLocalGraph (trg.cpp:532-534)
 }
 
-TrgStatus trg_engine_export_csr(TrgEngine *e, TrgKind kind, TrgCsrView *out) {
-  if (!e || !out) return TRG_ERR_INVALID_ARG;
+TrgStatus export_csr(TrgEngine *e, TrgKind kind, TrgCsrView *out) {
   Csr *c = nullptr;
   if (kind == TRG_KIND_GLOBAL) {
     c = &e->csr_global;
@@ -1385,8 +1359,7 @@ TrgStatus trg_engine_export_csr(TrgEngine *e, TrgKind kind, TrgCsrView *out) {
 }
 
 // ---- JSON persistence (schema of trg.cpp:130-177) ---------------------------------------------
-TrgStatus trg_engine_save_json(TrgEngine *e, const char *path) {
-  if (!e || !path) return TRG_ERR_INVALID_ARG;
+TrgStatus save_json(TrgEngine *e, const char *path) {
   std::string p(path);
   // save_path.extension().empty() -> append ".json" (trg.cpp:135-137)
   {
@@ -1413,8 +1386,7 @@ TrgStatus trg_engine_save_json(TrgEngine *e, const char *path) {
   return TRG_OK;
 }
 
-TrgStatus trg_engine_load_json(TrgEngine *e, const char *path) {
-  REQUIRE_DEVICE(e);
+TrgStatus load_json(TrgEngine *e, const char *path) {
   if (!path) return TRG_ERR_INVALID_ARG;
   std::ifstream f(path);
   if (!f) return e->fail(TRG_ERR_IO, std::string("File not found: ") + path);
@@ -1452,39 +1424,26 @@ TrgStatus trg_engine_load_json(TrgEngine *e, const char *path) {
   return TRG_OK;
 }
 
-// ---- planning (host A*, trg.cpp:537-565, 603-690): trg_engine_plan.ipp ----------------------------
-}  // extern "C"
-
-#include "trg_engine_plan.ipp"
-#include "trg_engine_field.ipp"
-
-extern "C" {
-
 // ---- probes --------------------------------------------------------------------------------------
-TrgStatus trg_engine_is_collision_batch(TrgEngine *e, TrgKind map, float threshold, const float *xy,
-                                        size_t m, int32_t *flag, int32_t *cnt, int32_t *n) {
-  REQUIRE_DEVICE(e);
+TrgStatus is_collision_batch(TrgEngine *e, TrgKind map, float threshold, const float *xy, size_t m, int32_t *flag,
+                             int32_t *cnt, int32_t *n) {
   if (m && !xy) return e->fail(TRG_ERR_INVALID_ARG, "null positions");
   return collision_sync(e, *pick_map(e, map), threshold, xy, m, flag, cnt, n);
 }
 
-TrgStatus trg_engine_nearest_z_batch(TrgEngine *e, TrgKind map, const float *xy, size_t m, float *z) {
-  REQUIRE_DEVICE(e);
+TrgStatus nearest_z_batch(TrgEngine *e, TrgKind map, const float *xy, size_t m, float *z) {
   if (m && (!xy || !z)) return e->fail(TRG_ERR_INVALID_ARG, "null arguments");
   return nearest_z_sync(e, *pick_map(e, map), xy, m, z, nullptr);
 }
 
-TrgStatus trg_engine_edge_risk_batch(TrgEngine *e, TrgKind map, const float *p1_xyz,
-                                     const float *p2_xyz, size_t m, int32_t *status, int32_t *n_pts,
-                                     float *weight, float *dist) {
-  REQUIRE_DEVICE(e);
+TrgStatus edge_risk_batch(TrgEngine *e, TrgKind map, const float *p1_xyz, const float *p2_xyz, size_t m,
+                          int32_t *status, int32_t *n_pts, float *weight, float *dist) {
   if (m && (!p1_xyz || !p2_xyz)) return e->fail(TRG_ERR_INVALID_ARG, "null arguments");
   return edges_sync(e, *pick_map(e, map), p1_xyz, p2_xyz, m, status, n_pts, weight, dist, true);
 }
 
-TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size_t stride, float leaf,
-                                  float *out_xyz, size_t *n_out, int32_t *passthrough) {
-  REQUIRE_DEVICE(e);
+TrgStatus voxel_filter(TrgEngine *e, const float *xyz, size_t n, size_t stride, float leaf, float *out_xyz,
+                       size_t *n_out, int32_t *passthrough) {
   if (!n_out || (n && (!xyz || !out_xyz))) return e->fail(TRG_ERR_INVALID_ARG, "null arguments");
   if (stride < 3) return e->fail(TRG_ERR_INVALID_ARG, "stride must be >= 3 floats");
   if (!(leaf > 0.0f)) return e->fail(TRG_ERR_INVALID_ARG, "leaf size must be positive");
@@ -1508,8 +1467,7 @@ TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size
   return TRG_OK;
 }
 
-TrgStatus trg_engine_is_frontier_batch(TrgEngine *e, const float *xy, size_t m, int32_t *flag) {
-  REQUIRE_DEVICE(e);
+TrgStatus is_frontier_batch(TrgEngine *e, const float *xy, size_t m, int32_t *flag) {
   if (m && (!xy || !flag)) return e->fail(TRG_ERR_INVALID_ARG, "null arguments");
   // trg.cpp:780-803: check = pos + 2*robot_size*normalize(pos - local root); frontier iff no global
   // node within robot_size of check AND no local-map point within robot_size/2 of it
@@ -1549,14 +1507,7 @@ TrgStatus trg_engine_is_frontier_batch(TrgEngine *e, const float *xy, size_t m, 
   return TRG_OK;
 }
 
-TrgStatus trg_engine_get_stats(const TrgEngine *e, TrgStats *out) {
-  if (!e || !out) return TRG_ERR_INVALID_ARG;
-  *out = e->stats;
-  return TRG_OK;
-}
-
-TrgStatus trg_engine_get_sampler_table(TrgEngine *e, float *cos_out, float *sin_out) {
-  REQUIRE_DEVICE(e);
+TrgStatus get_sampler_table(TrgEngine *e, float *cos_out, float *sin_out) {
   TrgStatus st = ensure_sampler(e, nullptr);
   if (st != TRG_OK) return st;
   if (cos_out) memcpy(cos_out, e->cos_t.data(), e->cos_t.size() * sizeof(float));
@@ -1564,9 +1515,8 @@ TrgStatus trg_engine_get_sampler_table(TrgEngine *e, float *cos_out, float *sin_
   return TRG_OK;
 }
 
-TrgStatus trg_engine_debug_map_index(TrgEngine *e, TrgKind map, float *x, float *y, float *z,
-                                     int32_t *perm, int32_t *grid_wh, float *origin_cell) {
-  REQUIRE_DEVICE(e);
+TrgStatus debug_map_index(TrgEngine *e, TrgKind map, float *x, float *y, float *z, int32_t *perm, int32_t *grid_wh,
+                          float *origin_cell) {
   DevMap &m = *pick_map(e, map);
   if (!m.valid) return e->fail(TRG_ERR_NO_MAP, "no map");
   if (x) HIPCHK(e, hipMemcpy(x, m.x, m.n * sizeof(float), hipMemcpyDeviceToHost));
@@ -1583,6 +1533,130 @@ TrgStatus trg_engine_debug_map_index(TrgEngine *e, TrgKind map, float *x, float 
     origin_cell[2] = m.g;
   }
   return TRG_OK;
+}
+
+}  // namespace
+
+#include "trg_engine_plan.ipp"
+#include "trg_engine_field.ipp"
+
+extern "C" {
+
+TrgStatus trg_engine_create(const TrgParams *params, int device, TrgEngine **out) {
+  if (!params || !out) return TRG_ERR_INVALID_ARG;
+  *out = nullptr;  // (stays so where the engine itself cannot be made: TRG_ERR_CAPACITY)
+  return abi_guard("create", [out](TrgStatus s, const std::string &m) { return *out ? (*out)->fail(s, m) : s; },
+                   [&] { return create_engine(params, device, out); });
+}
+
+void trg_engine_destroy(TrgEngine *e) {
+  if (!e) return;
+  // the main stream is the first thing create makes on the device: without it every owner is empty, and
+  // nothing below needs a device (there may be none)
+  if (e->s_main) {
+    (void)hipSetDevice(e->device);
+    (void)hipDeviceSynchronize();
+  }
+  delete e;  // the order of release is the members' order, see TrgEngine
+}
+
+const char *trg_engine_last_error(const TrgEngine *e) { return e ? e->err.c_str() : "null engine"; }
+const char *trg_engine_device_arch(const TrgEngine *e) { return e ? e->arch.c_str() : ""; }
+const char *trg_engine_fallback_reason(const TrgEngine *e) { return e ? e->bfs_fallback_reason.c_str() : ""; }
+
+TrgStatus trg_engine_set_global_map(TrgEngine *e, const float *xyz, size_t n, size_t stride) {
+  return entry(e, "set_global_map", DEVICE, [&] { return set_global_map(e, xyz, n, stride); });
+}
+
+TrgStatus trg_engine_set_global_map_device(TrgEngine *e, const float *d_xyz, size_t n, size_t stride) {
+  return entry(e, "set_global_map_device", DEVICE, [&] { return set_global_map_device(e, d_xyz, n, stride); });
+}
+
+TrgStatus trg_engine_set_local_map(TrgEngine *e, const float start_xy[2], const float *xyz, size_t n,
+                                   size_t stride) {
+  return entry(e, "set_local_map", DEVICE, [&] { return set_local_map(e, start_xy, xyz, n, stride); });
+}
+
+TrgStatus trg_engine_reset_map(TrgEngine *e, TrgKind kind) {
+  return entry(e, "reset_map", DEVICE, [&] { return reset_map(e, kind); });
+}
+
+TrgStatus trg_engine_reset_graph(TrgEngine *e, TrgKind kind) {
+  return entry(e, "reset_graph", DEVICE, [&] { return reset_graph(e, kind); });
+}
+
+TrgStatus trg_engine_init_graph(TrgEngine *e, const float start_xyz[3], const TrgSampler *sampler) {
+  return entry(e, "init_graph", DEVICE, [&] { return init_graph(e, start_xyz, sampler); });
+}
+
+TrgStatus trg_engine_update_graph(TrgEngine *e) {
+  return entry(e, "update_graph", DEVICE, [&] { return update_graph(e); });
+}
+
+TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value) {
+  if (!key || !value) return TRG_ERR_INVALID_ARG;
+  return entry(e, "set_option", ENGINE, [&] { return set_option(e, key, value); });
+}
+
+TrgStatus trg_engine_set_tile(TrgEngine *e, const float core_xyxy[4], uint32_t epoch) {
+  return entry(e, "set_tile", ENGINE, [&] { return set_tile(e, core_xyxy, epoch); });
+}
+
+TrgStatus trg_engine_export_csr(TrgEngine *e, TrgKind kind, TrgCsrView *out) {
+  if (!out) return TRG_ERR_INVALID_ARG;
+  return entry(e, "export_csr", ENGINE, [&] { return export_csr(e, kind, out); });
+}
+
+TrgStatus trg_engine_save_json(TrgEngine *e, const char *path) {
+  if (!path) return TRG_ERR_INVALID_ARG;
+  return entry(e, "save_json", ENGINE, [&] { return save_json(e, path); });
+}
+
+TrgStatus trg_engine_load_json(TrgEngine *e, const char *path) {
+  return entry(e, "load_json", DEVICE, [&] { return load_json(e, path); });
+}
+
+TrgStatus trg_engine_is_collision_batch(TrgEngine *e, TrgKind map, float threshold, const float *xy, size_t m,
+                                        int32_t *flag, int32_t *cnt, int32_t *n) {
+  return entry(e, "is_collision_batch", DEVICE,
+               [&] { return is_collision_batch(e, map, threshold, xy, m, flag, cnt, n); });
+}
+
+TrgStatus trg_engine_nearest_z_batch(TrgEngine *e, TrgKind map, const float *xy, size_t m, float *z) {
+  return entry(e, "nearest_z_batch", DEVICE, [&] { return nearest_z_batch(e, map, xy, m, z); });
+}
+
+TrgStatus trg_engine_edge_risk_batch(TrgEngine *e, TrgKind map, const float *p1_xyz, const float *p2_xyz, size_t m,
+                                     int32_t *status, int32_t *n_pts, float *weight, float *dist) {
+  return entry(e, "edge_risk_batch", DEVICE,
+               [&] { return edge_risk_batch(e, map, p1_xyz, p2_xyz, m, status, n_pts, weight, dist); });
+}
+
+TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size_t stride, float leaf, float *out_xyz,
+                                  size_t *n_out, int32_t *passthrough) {
+  return entry(e, "voxel_filter", DEVICE,
+               [&] { return voxel_filter(e, xyz, n, stride, leaf, out_xyz, n_out, passthrough); });
+}
+
+TrgStatus trg_engine_is_frontier_batch(TrgEngine *e, const float *xy, size_t m, int32_t *flag) {
+  return entry(e, "is_frontier_batch", DEVICE, [&] { return is_frontier_batch(e, xy, m, flag); });
+}
+
+TrgStatus trg_engine_get_stats(const TrgEngine *e, TrgStats *out) {
+  if (!out) return TRG_ERR_INVALID_ARG;
+  return entry(const_cast<TrgEngine *>(e), "get_stats", ENGINE, [&] {
+    *out = e->stats;
+    return TRG_OK;
+  });
+}
+
+TrgStatus trg_engine_get_sampler_table(TrgEngine *e, float *cos_out, float *sin_out) {
+  return entry(e, "get_sampler_table", DEVICE, [&] { return get_sampler_table(e, cos_out, sin_out); });
+}
+
+TrgStatus trg_engine_debug_map_index(TrgEngine *e, TrgKind map, float *x, float *y, float *z, int32_t *perm,
+                                     int32_t *grid_wh, float *origin_cell) {
+  return entry(e, "debug_map_index", DEVICE, [&] { return debug_map_index(e, map, x, y, z, perm, grid_wh, origin_cell); });
 }
 
 }  // extern "C"

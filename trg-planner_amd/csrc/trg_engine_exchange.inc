@@ -112,12 +112,7 @@ TrgStatus exchange_allgatherv(TrgEngine *e, ExchangeState &x, const void *d_mine
   return TRG_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-TrgStatus trg_engine_comm_unique_id(TrgEngine *e, uint8_t id[TRG_COMM_ID_BYTES]) {
-  if (!e || !id) return TRG_ERR_INVALID_ARG;
+TrgStatus comm_unique_id(TrgEngine *e, uint8_t id[TRG_COMM_ID_BYTES]) {
   if (!g_rccl.load()) return e->fail(TRG_ERR_DEVICE, g_rccl.err);
   static_assert(TRG_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "id size");
   ncclUniqueId u;
@@ -126,8 +121,7 @@ TrgStatus trg_engine_comm_unique_id(TrgEngine *e, uint8_t id[TRG_COMM_ID_BYTES])
   return TRG_OK;
 }
 
-TrgStatus trg_engine_comm_init(TrgEngine *e, const uint8_t id[TRG_COMM_ID_BYTES], int32_t nranks, int32_t rank) {
-  REQUIRE_DEVICE(e);
+TrgStatus comm_init(TrgEngine *e, const uint8_t id[TRG_COMM_ID_BYTES], int32_t nranks, int32_t rank) {
   if (!id || nranks < 1 || nranks > STITCH_MAX_TILES || rank < 0 || rank >= nranks)
     return e->fail(TRG_ERR_INVALID_ARG, "comm_init: bad arguments");
   if (!g_rccl.load()) return e->fail(TRG_ERR_DEVICE, g_rccl.err);
@@ -144,31 +138,35 @@ TrgStatus trg_engine_comm_init(TrgEngine *e, const uint8_t id[TRG_COMM_ID_BYTES]
   return TRG_OK;
 }
 
-TrgStatus trg_engine_comm_adopt(TrgEngine *e, void *nccl_comm) {
-  REQUIRE_DEVICE(e);
+// A communicator the engine refuses is not kept: the one it had is gone (as after a comm_init that failed), and a
+// later stitch_exchange finds none instead of indexing its count buffers with the refused communicator's size.
+TrgStatus comm_adopt(TrgEngine *e, void *nccl_comm) {
   if (!nccl_comm) return e->fail(TRG_ERR_INVALID_ARG, "comm_adopt: null communicator");
   if (!g_rccl.load()) return e->fail(TRG_ERR_DEVICE, g_rccl.err);
   if (!e->exchange) e->exchange.reset(new ExchangeState());
   ExchangeState &x = *e->exchange;
   if (x.comm && x.owned) (void)g_rccl.CommDestroy(x.comm);
-  x.comm = (ncclComm_t)nccl_comm;
+  x.comm = nullptr;
   x.owned = false;
-  RCCLCHK(e, g_rccl.CommCount(x.comm, &x.nranks));
-  RCCLCHK(e, g_rccl.CommUserRank(x.comm, &x.rank));
-  if (x.nranks > STITCH_MAX_TILES) return e->fail(TRG_ERR_INVALID_ARG, "comm_adopt: too many ranks");
+  const ncclComm_t comm = (ncclComm_t)nccl_comm;
+  int nranks = 0, rank = 0;
+  RCCLCHK(e, g_rccl.CommCount(comm, &nranks));
+  RCCLCHK(e, g_rccl.CommUserRank(comm, &rank));
+  if (nranks > STITCH_MAX_TILES) return e->fail(TRG_ERR_INVALID_ARG, "comm_adopt: too many ranks");
+  x.comm = comm;
+  x.nranks = nranks;
+  x.rank = rank;
   return TRG_OK;
 }
 
-TrgStatus trg_engine_comm_destroy(TrgEngine *e) {
-  if (!e) return TRG_ERR_INVALID_ARG;
+TrgStatus comm_destroy(TrgEngine *e) {
   (void)hipSetDevice(e->device);
   e->exchange.reset();
   return TRG_OK;
 }
 
-TrgStatus trg_engine_stitch_exchange(TrgEngine *e, const float core_xyxy[4], int32_t cols, int32_t rows,
-                                     int32_t *n_boundary, int32_t *n_cross) {
-  REQUIRE_DEVICE(e);
+TrgStatus stitch_exchange(TrgEngine *e, const float core_xyxy[4], int32_t cols, int32_t rows, int32_t *n_boundary,
+                          int32_t *n_cross) {
   if (!e->exchange || !e->exchange->comm) return e->fail(TRG_ERR_INVALID_ARG, "stitch_exchange: no communicator (trg_engine_comm_init)");
   ExchangeState &x = *e->exchange;
   const int R = x.nranks, tile = x.rank;
@@ -182,12 +180,12 @@ TrgStatus trg_engine_stitch_exchange(TrgEngine *e, const float core_xyxy[4], int
   if ((st = ensure_bytes(e, x.rec, (size_t)(1 << 14) * sizeof(TrgBoundaryRec))) != TRG_OK) return st;
   for (;;) {
     const int32_t cap = (int32_t)(x.rec.bytes / sizeof(TrgBoundaryRec)) - 1;
-    st = trg_engine_stitch_boundary(e, core_xyxy, cols, rows, tile, (TrgBoundaryRec *)x.rec.p, cap, &nb);
+    st = stitch_boundary(e, core_xyxy, cols, rows, tile, (TrgBoundaryRec *)x.rec.p, cap, &nb);
     if (st != TRG_ERR_CAPACITY) break;
     if ((st = ensure_bytes(e, x.rec, (size_t)(2 * nb + 2) * sizeof(TrgBoundaryRec))) != TRG_OK) break;
   }
   int32_t V = 0, E_ = 0;
-  if (st == TRG_OK) st = trg_engine_graph_sizes(e, TRG_KIND_GLOBAL, &V, &E_);
+  if (st == TRG_OK) st = graph_sizes(e, TRG_KIND_GLOBAL, &V, &E_);
   if (st != TRG_OK) {  // tell the others instead of leaving them in the collective
     deferred = st;
     deferred_msg = e->err;
@@ -232,7 +230,7 @@ TrgStatus trg_engine_stitch_exchange(TrgEngine *e, const float core_xyxy[4], int
   if ((st = ensure_bytes(e, x.edges, (size_t)(1 << 15) * sizeof(TrgCrossEdge))) != TRG_OK) return st;
   for (;;) {
     const int32_t cap = (int32_t)(x.edges.bytes / sizeof(TrgCrossEdge));
-    st = trg_engine_stitch_cross(e, tile, R, d_recs, rec_off.data(), (TrgCrossEdge *)x.edges.p, cap, &nc);
+    st = stitch_cross(e, tile, R, d_recs, rec_off.data(), (TrgCrossEdge *)x.edges.p, cap, &nc);
     if (st != TRG_ERR_CAPACITY) break;
     if ((st = ensure_bytes(e, x.edges, (size_t)(2 * nc + 2) * sizeof(TrgCrossEdge))) != TRG_OK) break;
   }
@@ -249,11 +247,38 @@ TrgStatus trg_engine_stitch_exchange(TrgEngine *e, const float core_xyxy[4], int
   long long ne = 0;
   for (long long c : ecounts) ne += c;
   // ---- 3: this tile's rows of the global graph ---------------------------------------------------------------------
-  st = trg_engine_stitch_assemble(e, tile, R, node_off.data(), (const TrgCrossEdge *)d_all_edges, (int32_t)ne);
+  st = stitch_assemble(e, tile, R, node_off.data(), (const TrgCrossEdge *)d_all_edges, (int32_t)ne);
   if (st != TRG_OK) return st;
   if (n_boundary) *n_boundary = rec_off[R];
   if (n_cross) *n_cross = (int32_t)ne;
   return TRG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+TrgStatus trg_engine_comm_unique_id(TrgEngine *e, uint8_t id[TRG_COMM_ID_BYTES]) {
+  if (!id) return TRG_ERR_INVALID_ARG;
+  return entry(e, "comm_unique_id", ENGINE, [&] { return comm_unique_id(e, id); });
+}
+
+TrgStatus trg_engine_comm_init(TrgEngine *e, const uint8_t id[TRG_COMM_ID_BYTES], int32_t nranks, int32_t rank) {
+  return entry(e, "comm_init", DEVICE, [&] { return comm_init(e, id, nranks, rank); });
+}
+
+TrgStatus trg_engine_comm_adopt(TrgEngine *e, void *nccl_comm) {
+  return entry(e, "comm_adopt", DEVICE, [&] { return comm_adopt(e, nccl_comm); });
+}
+
+TrgStatus trg_engine_comm_destroy(TrgEngine *e) {
+  return entry(e, "comm_destroy", ENGINE, [&] { return comm_destroy(e); });
+}
+
+TrgStatus trg_engine_stitch_exchange(TrgEngine *e, const float core_xyxy[4], int32_t cols, int32_t rows,
+                                     int32_t *n_boundary, int32_t *n_cross) {
+  return entry(e, "stitch_exchange", DEVICE,
+               [&] { return stitch_exchange(e, core_xyxy, cols, rows, n_boundary, n_cross); });
 }
 
 }  // extern "C"

@@ -782,24 +782,17 @@ TrgStatus field_solve(TrgEngine *e, const FieldRequest &rq, TrgFieldInfo *info) 
   return TRG_OK;
 }
 
-// The C entries' common frame: `info` defaulted, zeroed and without a source, then `body(info)` behind the
-// exception ladder; `call` is the entry's message prefix.
+// The field entries' common frame: entry() with `info` defaulted, zeroed and without a source for `body(info)`;
+// `call` is the entry's message prefix.
 template <typename Body>
 TrgStatus field_entry(TrgEngine *e, TrgFieldInfo *info, const char *call, Body body) {
-  REQUIRE_DEVICE(e);
-  TrgFieldInfo local{};
-  if (!info) info = &local;
-  *info = TrgFieldInfo{};
-  info->source = -1;
-  try {
-    return body(info);
-  } catch (const std::bad_alloc &) {
-    return e->fail(TRG_ERR_CAPACITY, std::string(call) + ": out of host memory");
-  } catch (const std::exception &x) {
-    return e->fail(TRG_ERR_DEVICE, std::string(call) + ": " + x.what());
-  } catch (...) {
-    return e->fail(TRG_ERR_DEVICE, std::string(call) + ": unknown exception");
-  }
+  return entry(e, call, DEVICE, [&] {
+    TrgFieldInfo local{};
+    TrgFieldInfo *out = info ? info : &local;
+    *out = TrgFieldInfo{};
+    out->source = -1;
+    return body(out);
+  });
 }
 
 static_assert(sizeof(TrgRouteInfo) == sizeof(FieldRouteInfo) && offsetof(TrgRouteInfo, num_nodes) == 0 &&
@@ -1028,6 +1021,58 @@ FieldRequest field_request(int32_t m, float *cost, int32_t *hops, int32_t *paren
   return rq;
 }
 
+// the solve behind trg_engine_cost_field_bounded and, without bounds, trg_engine_cost_field_batch (no_info: the caller
+// gave no TrgFieldInfo)
+TrgStatus cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *source_ids, const float *source_xy,
+                             const float *budget, int32_t settle, float *cost, int32_t *hops, int32_t *parent,
+                             const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at,
+                             int32_t *sources_out, int32_t *reached_out, float *bound_out, bool no_info,
+                             TrgFieldInfo *out) {
+  // every output NULL but sources_out: the caller wants the sources resolved, nothing solved
+  const bool resolve_only =
+      sources_out && !cost && !hops && !parent && !cost_at && !hops_at && !reached_out && !bound_out && no_info;
+  if (const TrgStatus st = field_check_shape(e, "cost field", "fields", m, n_targets); st != TRG_OK) return st;
+  if (!source_ids && !source_xy) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no sources");
+  if (source_ids)
+    for (int k = 0; k < m; ++k)
+      if (source_ids[k] < -1)
+        return e->fail(TRG_ERR_INVALID_ARG, "cost field: source " + std::to_string(k) + " out of range");
+  if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
+  FieldRequest rq = field_request(m, cost, hops, parent, targets, n_targets, cost_at, hops_at, reached_out);
+  rq.source_ids = source_ids;
+  rq.source_xy = source_xy;
+  rq.sources_out = sources_out;
+  rq.resolve_only = resolve_only;
+  rq.budget = budget;
+  rq.settle = settle;
+  rq.bound_out = bound_out;
+  return field_solve(e, rq, out);
+}
+
+// ... and the one behind trg_engine_cost_field_models and, without models, trg_engine_cost_field_sets
+TrgStatus cost_field_models(TrgEngine *e, int32_t m, const TrgFieldModel *models, const int32_t *set_ptr,
+                            const int32_t *set_ids, const float *budget, int32_t settle, float *cost, int32_t *hops,
+                            int32_t *parent, int32_t *owner, const int32_t *targets, int32_t n_targets, float *cost_at,
+                            int32_t *hops_at, int32_t *owner_at, int32_t *owned, int32_t *reached_out, float *bound_out,
+                            TrgFieldInfo *out) {
+  const char *no_sets = !set_ptr || !set_ids ? "null set_ptr or set_ids" : nullptr;
+  if (const TrgStatus st = field_check_shape(e, "cost field sets", "sets", m, n_targets, no_sets); st != TRG_OK)
+    return st;
+  if (const TrgStatus st = field_check_models(e, m, models); st != TRG_OK) return st;
+  if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
+  FieldRequest rq = field_request(m, cost, hops, parent, targets, n_targets, cost_at, hops_at, reached_out);
+  rq.budget = budget;
+  rq.settle = settle;
+  rq.bound_out = bound_out;
+  rq.set_ptr = set_ptr;
+  rq.set_ids = set_ids;
+  rq.owner = owner;
+  rq.owner_at = owner_at;
+  rq.owned = owned;
+  rq.models = models;
+  return field_solve(e, rq, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1051,8 +1096,10 @@ TrgStatus trg_engine_cost_field_batch(TrgEngine *e, int32_t m, const int32_t *so
                                       float *cost, int32_t *hops, int32_t *parent, const int32_t *targets,
                                       int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *sources_out,
                                       int32_t *reached_out, TrgFieldInfo *info) {
-  return trg_engine_cost_field_bounded(e, m, source_ids, source_xy, nullptr, TRG_FIELD_SETTLE_NONE, cost, hops, parent,
-                                       targets, n_targets, cost_at, hops_at, sources_out, reached_out, nullptr, info);
+  return field_entry(e, info, "cost field", [&](TrgFieldInfo *out) {  // the bounded solve without bounds
+    return cost_field_bounded(e, m, source_ids, source_xy, nullptr, TRG_FIELD_SETTLE_NONE, cost, hops, parent, targets,
+                              n_targets, cost_at, hops_at, sources_out, reached_out, nullptr, !info, out);
+  });
 }
 
 TrgStatus trg_engine_cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *source_ids, const float *source_xy,
@@ -1060,26 +1107,9 @@ TrgStatus trg_engine_cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *
                                         int32_t *parent, const int32_t *targets, int32_t n_targets, float *cost_at,
                                         int32_t *hops_at, int32_t *sources_out, int32_t *reached_out,
                                         float *bound_out, TrgFieldInfo *info) {
-  // every output NULL but sources_out: the caller wants the sources resolved, nothing solved
-  const bool resolve_only =
-      sources_out && !cost && !hops && !parent && !cost_at && !hops_at && !reached_out && !bound_out && !info;
   return field_entry(e, info, "cost field", [&](TrgFieldInfo *out) {
-    if (const TrgStatus st = field_check_shape(e, "cost field", "fields", m, n_targets); st != TRG_OK) return st;
-    if (!source_ids && !source_xy) return e->fail(TRG_ERR_INVALID_ARG, "cost field: no sources");
-    if (source_ids)
-      for (int k = 0; k < m; ++k)
-        if (source_ids[k] < -1)
-          return e->fail(TRG_ERR_INVALID_ARG, "cost field: source " + std::to_string(k) + " out of range");
-    if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
-    FieldRequest rq = field_request(m, cost, hops, parent, targets, n_targets, cost_at, hops_at, reached_out);
-    rq.source_ids = source_ids;
-    rq.source_xy = source_xy;
-    rq.sources_out = sources_out;
-    rq.resolve_only = resolve_only;
-    rq.budget = budget;
-    rq.settle = settle;
-    rq.bound_out = bound_out;
-    return field_solve(e, rq, out);
+    return cost_field_bounded(e, m, source_ids, source_xy, budget, settle, cost, hops, parent, targets, n_targets,
+                              cost_at, hops_at, sources_out, reached_out, bound_out, !info, out);
   });
 }
 
@@ -1088,8 +1118,10 @@ TrgStatus trg_engine_cost_field_sets(TrgEngine *e, int32_t m, const int32_t *set
                                      int32_t *owner, const int32_t *targets, int32_t n_targets, float *cost_at,
                                      int32_t *hops_at, int32_t *owner_at, int32_t *owned, int32_t *reached_out,
                                      float *bound_out, TrgFieldInfo *info) {
-  return trg_engine_cost_field_models(e, m, nullptr, set_ptr, set_ids, budget, settle, cost, hops, parent, owner,
-                                      targets, n_targets, cost_at, hops_at, owner_at, owned, reached_out, bound_out, info);
+  return field_entry(e, info, "cost field sets", [&](TrgFieldInfo *out) {
+    return cost_field_models(e, m, nullptr, set_ptr, set_ids, budget, settle, cost, hops, parent, owner, targets,
+                             n_targets, cost_at, hops_at, owner_at, owned, reached_out, bound_out, out);
+  });
 }
 
 TrgStatus trg_engine_cost_field_models(TrgEngine *e, int32_t m, const TrgFieldModel *models, const int32_t *set_ptr,
@@ -1098,22 +1130,8 @@ TrgStatus trg_engine_cost_field_models(TrgEngine *e, int32_t m, const TrgFieldMo
                                        int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
                                        int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info) {
   return field_entry(e, info, "cost field sets", [&](TrgFieldInfo *out) {
-    const char *no_sets = !set_ptr || !set_ids ? "null set_ptr or set_ids" : nullptr;
-    if (const TrgStatus st = field_check_shape(e, "cost field sets", "sets", m, n_targets, no_sets); st != TRG_OK)
-      return st;
-    if (const TrgStatus st = field_check_models(e, m, models); st != TRG_OK) return st;
-    if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
-    FieldRequest rq = field_request(m, cost, hops, parent, targets, n_targets, cost_at, hops_at, reached_out);
-    rq.budget = budget;
-    rq.settle = settle;
-    rq.bound_out = bound_out;
-    rq.set_ptr = set_ptr;
-    rq.set_ids = set_ids;
-    rq.owner = owner;
-    rq.owner_at = owner_at;
-    rq.owned = owned;
-    rq.models = models;
-    return field_solve(e, rq, out);
+    return cost_field_models(e, m, models, set_ptr, set_ids, budget, settle, cost, hops, parent, owner, targets,
+                             n_targets, cost_at, hops_at, owner_at, owned, reached_out, bound_out, out);
   });
 }
 

@@ -142,15 +142,15 @@ TrgStatus staged_upload(TrgEngine *e, void *d_dst, const void *src, size_t bytes
   }
   const size_t nchunk = (bytes + UP_CHUNK - 1) / UP_CHUNK;
   std::atomic<int> bad{0};
-  auto work = [&](int t) {
+  fork_join(UP_THREADS, [&](size_t t) {
     if (hipSetDevice(e->device) != hipSuccess) {
       bad = 1;
       return;
     }
     int use = 0;
-    for (size_t c = (size_t)t; c < nchunk; c += UP_THREADS, ++use) {
+    for (size_t c = t; c < nchunk; c += UP_THREADS, ++use) {
       const int k = use % UP_SLOTS;
-      char *slot = u.pinned + ((size_t)t * UP_SLOTS + k) * UP_CHUNK;
+      char *slot = u.pinned + (t * UP_SLOTS + k) * UP_CHUNK;
       if (use >= UP_SLOTS && hipEventSynchronize(u.ev[t][k]) != hipSuccess) bad = 1;  // the slot's last transfer
       const size_t off = c * UP_CHUNK, len = std::min(UP_CHUNK, bytes - off);
       memcpy(slot, (const char *)src + off, len);
@@ -158,11 +158,7 @@ TrgStatus staged_upload(TrgEngine *e, void *d_dst, const void *src, size_t bytes
       if (hipEventRecord(u.ev[t][k], u.st[t]) != hipSuccess) bad = 1;
     }
     if (hipStreamSynchronize(u.st[t]) != hipSuccess) bad = 1;
-  };
-  std::vector<std::thread> thr;
-  for (int t = 1; t < UP_THREADS; ++t) thr.emplace_back(work, t);
-  work(0);
-  for (auto &th : thr) th.join();
+  });
   if (bad) return e->fail(TRG_ERR_DEVICE, "staged upload of the cloud failed");
   return TRG_OK;
 }

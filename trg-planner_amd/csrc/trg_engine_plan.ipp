@@ -185,13 +185,8 @@ TrgStatus plan_prepare(TrgEngine *e) {
   return TRG_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-TrgStatus trg_engine_plan(TrgEngine *e, const float start_xy[2], const float goal_xyz[3],
-                          float *path_xyz, int32_t max_points, TrgPathInfo *info) {
-  if (!e || !start_xy || !goal_xyz || !info) return TRG_ERR_INVALID_ARG;
+TrgStatus plan(TrgEngine *e, const float start_xy[2], const float goal_xyz[3], float *path_xyz, int32_t max_points,
+               TrgPathInfo *info) {
   info->direct_dist = info->path_length = info->avg_risk = 0.0f;
   info->num_points = 0;
   TrgStatus st = plan_prepare(e);
@@ -210,11 +205,8 @@ TrgStatus trg_engine_plan(TrgEngine *e, const float start_xy[2], const float goa
 // m consecutive planSafePath calls.  The searches are independent and only read the graph: the start /
 // goal nodes are looked up in call order (the goal state the last call leaves is the reference's), the
 // searches themselves run on up to 8 host threads, each with its own scratch.
-TrgStatus trg_engine_plan_batch(TrgEngine *e, const float *starts_xy, const float *goals_xyz,
-                                size_t m, float *path_xyz, int32_t path_cap, int32_t *offsets,
-                                TrgPathInfo *infos) {
-  if (!e || !offsets || (m && (!starts_xy || !goals_xyz || !infos)))
-    return TRG_ERR_INVALID_ARG;
+TrgStatus plan_batch(TrgEngine *e, const float *starts_xy, const float *goals_xyz, size_t m, float *path_xyz,
+                     int32_t path_cap, int32_t *offsets, TrgPathInfo *infos) {
   if (path_cap < 0 || (path_cap > 0 && !path_xyz)) return e->fail(TRG_ERR_INVALID_ARG, "path buffer");
   offsets[0] = 0;
   if (m == 0) return TRG_OK;
@@ -235,7 +227,9 @@ TrgStatus trg_engine_plan_batch(TrgEngine *e, const float *starts_xy, const floa
   std::vector<TrgStatus> sts(m, TRG_OK);
   const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
   const size_t nthr = std::min<size_t>(std::min<size_t>(m, 8), hw);
-  auto work = [&](size_t t, PlanScratch &ps) {
+  std::vector<PlanScratch> extra(nthr - 1);  // (thread 0 searches in the engine's own scratch)
+  fork_join(nthr, [&](size_t t) {
+    PlanScratch &ps = t == 0 ? ps0 : extra[t - 1];
     for (size_t k = t; k < m; k += nthr) {
       TrgPathInfo probe;
       probe.direct_dist = probe.path_length = probe.avg_risk = 0.0f;
@@ -252,16 +246,7 @@ TrgStatus trg_engine_plan_batch(TrgEngine *e, const float *starts_xy, const floa
       }
       infos[k] = probe;
     }
-  };
-  if (nthr <= 1) {
-    work(0, ps0);
-  } else {
-    std::vector<PlanScratch> extra(nthr - 1);
-    std::vector<std::thread> thr;
-    for (size_t t = 1; t < nthr; ++t) thr.emplace_back(work, t, std::ref(extra[t - 1]));
-    work(0, ps0);
-    for (auto &th : thr) th.join();
-  }
+  });
   int32_t used = 0;
   for (size_t k = 0; k < m; ++k) {
     if (sts[k] != TRG_OK && sts[k] != TRG_ERR_NOT_FOUND) return e->fail(sts[k], "plan_batch");
@@ -275,16 +260,14 @@ TrgStatus trg_engine_plan_batch(TrgEngine *e, const float *starts_xy, const floa
   return TRG_OK;
 }
 
-// reference: TRG::checkReadched (sic) trg.cpp:567-574 and TRG::checkReplan trg.cpp:576-601
-int32_t trg_engine_check_reached(TrgEngine *e, const float pos_xy[2]) {
-  if (!e || !pos_xy) return 0;
+// reference: TRG::checkReadched (sic) trg.cpp:567-574 and TRG::checkReplan trg.cpp:576-601; their entries and
+// refine_path's answer with a number, 0 where an exception was caught
+int32_t check_reached(const TrgEngine *e, const float pos_xy[2]) {
   const float dist = norm2f(e->goal_pose2d[0] - pos_xy[0], e->goal_pose2d[1] - pos_xy[1]);
   return dist < e->prm.goal_tolerance ? 1 : 0;
 }
 
-int32_t trg_engine_check_replan(TrgEngine *e, const float pos_xy[2], const float *path_xyz,
-                                int32_t n_path) {
-  if (!e || !pos_xy) return 0;
+int32_t check_replan(TrgEngine *e, const float pos_xy[2], const float *path_xyz, int32_t n_path) {
   if (e->goal_node < 0 || e->goal_node >= (int)e->nx.size()) return 0;
   const int g = e->goal_node;
   const float dist2subgoal = norm2f(e->nx[g] - pos_xy[0], e->ny[g] - pos_xy[1]);
@@ -304,8 +287,7 @@ int32_t trg_engine_check_replan(TrgEngine *e, const float pos_xy[2], const float
   return 0;
 }
 
-int32_t trg_engine_refine_path(const float *in_xyz, int32_t n_in, float *out_xyz, int32_t max_out) {
-  if (!in_xyz || n_in <= 0) return 0;
+int32_t refine_path(const float *in_xyz, int32_t n_in, float *out_xyz, int32_t max_out) {
   // point_between == 1: p0,p1,p1,p2,p2,...  then a 3-tap mean, last point passed through
   std::vector<float> dense;
   for (int i = 0; i + 1 < n_in; ++i) {
@@ -338,6 +320,45 @@ int32_t trg_engine_refine_path(const float *in_xyz, int32_t n_in, float *out_xyz
     written++;
   }
   return written;
+}
+
+}  // namespace
+
+extern "C" {
+
+TrgStatus trg_engine_plan(TrgEngine *e, const float start_xy[2], const float goal_xyz[3], float *path_xyz,
+                          int32_t max_points, TrgPathInfo *info) {
+  if (!start_xy || !goal_xyz || !info) return TRG_ERR_INVALID_ARG;
+  return entry(e, "plan", ENGINE, [&] { return plan(e, start_xy, goal_xyz, path_xyz, max_points, info); });
+}
+
+TrgStatus trg_engine_plan_batch(TrgEngine *e, const float *starts_xy, const float *goals_xyz, size_t m,
+                                float *path_xyz, int32_t path_cap, int32_t *offsets, TrgPathInfo *infos) {
+  if (!offsets || (m && (!starts_xy || !goals_xyz || !infos))) return TRG_ERR_INVALID_ARG;
+  return entry(e, "plan_batch", ENGINE,
+               [&] { return plan_batch(e, starts_xy, goals_xyz, m, path_xyz, path_cap, offsets, infos); });
+}
+
+int32_t trg_engine_check_reached(TrgEngine *e, const float pos_xy[2]) {
+  if (!e || !pos_xy) return 0;
+  int32_t r = 0;
+  (void)entry(e, "check_reached", ENGINE, [&] { return r = check_reached(e, pos_xy), TRG_OK; });
+  return r;
+}
+
+int32_t trg_engine_check_replan(TrgEngine *e, const float pos_xy[2], const float *path_xyz, int32_t n_path) {
+  if (!e || !pos_xy) return 0;
+  int32_t r = 0;
+  (void)entry(e, "check_replan", ENGINE, [&] { return r = check_replan(e, pos_xy, path_xyz, n_path), TRG_OK; });
+  return r;
+}
+
+int32_t trg_engine_refine_path(const float *in_xyz, int32_t n_in, float *out_xyz, int32_t max_out) {
+  if (!in_xyz || n_in <= 0) return 0;
+  int32_t r = 0;
+  (void)abi_guard("refine_path", [](TrgStatus s, const std::string &) { return s; },
+                  [&] { return r = refine_path(in_xyz, n_in, out_xyz, max_out), TRG_OK; });
+  return r;
 }
 
 }  // extern "C"

@@ -77,13 +77,8 @@ TrgStatus stitch_fetch(TrgEngine *e) {
   return TRG_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-TrgStatus trg_engine_stitch_boundary(TrgEngine *e, const float core_xyxy[4], int32_t cols, int32_t rows,
-                                     int32_t tile, TrgBoundaryRec *d_rec, int32_t cap, int32_t *n_out) {
-  REQUIRE_DEVICE(e);
+TrgStatus stitch_boundary(TrgEngine *e, const float core_xyxy[4], int32_t cols, int32_t rows, int32_t tile,
+                          TrgBoundaryRec *d_rec, int32_t cap, int32_t *n_out) {
   if (!core_xyxy || !n_out || cols < 1 || rows < 1 || tile < 0 || tile >= cols * rows || cap < 0)
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_boundary: bad arguments");
   StitchBufs &sb = *e->stitch;
@@ -108,10 +103,8 @@ TrgStatus trg_engine_stitch_boundary(TrgEngine *e, const float core_xyxy[4], int
   return TRG_OK;
 }
 
-TrgStatus trg_engine_stitch_cross(TrgEngine *e, int32_t tile, int32_t ntiles, const TrgBoundaryRec *d_all_rec,
-                                  const int32_t *rec_offsets, TrgCrossEdge *d_edges, int32_t cap,
-                                  int32_t *n_out) {
-  REQUIRE_DEVICE(e);
+TrgStatus stitch_cross(TrgEngine *e, int32_t tile, int32_t ntiles, const TrgBoundaryRec *d_all_rec,
+                       const int32_t *rec_offsets, TrgCrossEdge *d_edges, int32_t cap, int32_t *n_out) {
   if (!rec_offsets || !n_out || ntiles < 1 || ntiles > STITCH_MAX_TILES || tile < 0 || tile >= ntiles)
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_cross: bad arguments");
   if (!e->gmap.valid) return e->fail(TRG_ERR_NO_MAP, "stitch_cross: no map");
@@ -187,9 +180,8 @@ TrgStatus trg_engine_stitch_cross(TrgEngine *e, int32_t tile, int32_t ntiles, co
   return TRG_OK;
 }
 
-TrgStatus trg_engine_stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles, const int32_t *node_offsets,
-                                     const TrgCrossEdge *d_all_edges, int32_t n_edges) {
-  REQUIRE_DEVICE(e);
+TrgStatus stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles, const int32_t *node_offsets,
+                          const TrgCrossEdge *d_all_edges, int32_t n_edges) {
   if (!node_offsets || ntiles < 1 || ntiles > STITCH_MAX_TILES || tile < 0 || tile >= ntiles || n_edges < 0)
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_assemble: bad arguments");
   StitchBufs &sb = *e->stitch;
@@ -235,26 +227,52 @@ TrgStatus trg_engine_stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles,
   launch_stitch_assemble(edges, n_edges, tile, ntiles, node_offsets, g.rowptr, g.col, g.w, g.dist, g.V,
                          (int *)sb.extra.p, (int *)sb.deg.p, (int *)sb.rowptr_new.p, (int *)sb.scan_tmp.p,
                          (int *)sb.fill.p, (int *)sb.col_new.p, (float *)sb.w_new.p, (float *)sb.dist_new.p, 1, s);
-  // the rows stay in HBM; trg_engine_export_csr(TRG_KIND_STITCHED) fetches them when asked
+  // the rows stay in HBM; an export of TRG_KIND_STITCHED fetches them when asked
   e->stitched_edges = En;
   e->view_stamp[TrgEngine::VIEW_STITCH_DEV] = e->graph_version;
   HIPCHK(e, hipGetLastError());
   return TRG_OK;
 }
 
-TrgStatus trg_engine_graph_sizes(TrgEngine *e, TrgKind kind, int32_t *num_nodes, int32_t *num_edges) {
-  if (!e || !num_nodes || !num_edges) return TRG_ERR_INVALID_ARG;
+TrgStatus graph_sizes(TrgEngine *e, TrgKind kind, int32_t *num_nodes, int32_t *num_edges) {
   if (kind == TRG_KIND_STITCHED) {  // (without fetching rows that are still in HBM)
     *num_nodes = (int32_t)e->csr_stitched.state.size();
     *num_edges = e->stitched_edges;
     return TRG_OK;
   }
   TrgCsrView v;
-  const TrgStatus st = trg_engine_export_csr(e, kind, &v);
+  const TrgStatus st = export_csr(e, kind, &v);
   if (st != TRG_OK) return st;
   *num_nodes = v.num_nodes;
   *num_edges = v.num_edges;
   return TRG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+TrgStatus trg_engine_stitch_boundary(TrgEngine *e, const float core_xyxy[4], int32_t cols, int32_t rows,
+                                     int32_t tile, TrgBoundaryRec *d_rec, int32_t cap, int32_t *n_out) {
+  return entry(e, "stitch_boundary", DEVICE,
+               [&] { return stitch_boundary(e, core_xyxy, cols, rows, tile, d_rec, cap, n_out); });
+}
+
+TrgStatus trg_engine_stitch_cross(TrgEngine *e, int32_t tile, int32_t ntiles, const TrgBoundaryRec *d_all_rec,
+                                  const int32_t *rec_offsets, TrgCrossEdge *d_edges, int32_t cap, int32_t *n_out) {
+  return entry(e, "stitch_cross", DEVICE,
+               [&] { return stitch_cross(e, tile, ntiles, d_all_rec, rec_offsets, d_edges, cap, n_out); });
+}
+
+TrgStatus trg_engine_stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles, const int32_t *node_offsets,
+                                     const TrgCrossEdge *d_all_edges, int32_t n_edges) {
+  return entry(e, "stitch_assemble", DEVICE,
+               [&] { return stitch_assemble(e, tile, ntiles, node_offsets, d_all_edges, n_edges); });
+}
+
+TrgStatus trg_engine_graph_sizes(TrgEngine *e, TrgKind kind, int32_t *num_nodes, int32_t *num_edges) {
+  if (!num_nodes || !num_edges) return TRG_ERR_INVALID_ARG;
+  return entry(e, "graph_sizes", ENGINE, [&] { return graph_sizes(e, kind, num_nodes, num_edges); });
 }
 
 }  // extern "C"
