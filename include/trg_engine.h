@@ -251,6 +251,29 @@ TrgStatus trg_engine_edge_risk_batch(TrgEngine *e, TrgKind map, const float *p1_
                                      float *weight, float *dist);
 /* reference: TRG::isFrontier trg.cpp:780-803 */
 TrgStatus trg_engine_is_frontier_batch(TrgEngine *e, const float *xy, size_t m, int32_t *flag);
+/* Pose links ("Pose links"; an extension): the verified links from a position to the global
+ * graph, each judged on the GLOBAL map as the reference would judge an edge from a node at that position.
+ * For pose k at p = (x, y):
+ *   z             the elevation addNode would give a node at p (trg_engine_nearest_z_batch, map ties included)
+ *   status        1 when isCollision(p, collision_threshold) holds -- the reference refuses a root there,
+ *                 trg.cpp:236-241 -- and the pose then has no candidates and no links; else 0
+ *   n_candidates  the nodes v with state != Invalid and d <= radius, d = sqrtf(dx * dx + dy * dy) in fp32 without
+ *                 contraction (wireEdge's dist, trg.cpp:276)
+ *   n_links       a candidate at d == 0 is a link of weight 0 and dist 0 without evaluation (the pose is that node);
+ *                 every other candidate is evaluated as trg_engine_edge_risk_batch(GLOBAL, p1 = (x, y, z),
+ *                 p2 = the node's xyz) and is a link, with that weight and dist, when its status is 0
+ * Links are sorted by (dist bits, node id) ascending and the first min(cap, n_links) are written to row k of
+ * link_node / link_weight / link_dist (m x cap each, any may be NULL); both counts are always the full ones.
+ * All poses of a call share one collision batch, one elevation batch and one edge batch.
+ * TRG_ERR_NO_MAP without a global map, TRG_ERR_NO_GRAPH for an empty graph, TRG_ERR_INVALID_ARG (naming the pose
+ * where there is one) for m < 0, cap < 0, a NaN position, or a radius that is NaN, <= 0 or >= 2.5 * expand_dist
+ * (wireEdge's own assert, trg.cpp:279).  m == 0 is TRG_OK. */
+typedef struct TrgPoseInfo {
+  int32_t status, n_candidates, n_links;
+  float z;
+} TrgPoseInfo;
+TrgStatus trg_engine_pose_links(TrgEngine *e, const float *poses_xy, int32_t m, float radius, int32_t cap,
+                                int32_t *link_node, float *link_weight, float *link_dist, TrgPoseInfo *infos);
 
 /* ---- map ingest: voxel-grid filter --------------------------------------------------------------- */
 /* reference: the pcl::VoxelGrid step of TRGPlanner::loadPrebuiltMap, trg_planner.cpp:91-94
@@ -472,6 +495,37 @@ TrgStatus trg_engine_cost_field_models(
     TrgEngine *e, int32_t m,
     const TrgFieldModel *models, /* m, or NULL: the engine's model for every field */
     const int32_t *set_ptr, const int32_t *set_ids,
+    const float *budget, int32_t settle,
+    float *cost, int32_t *hops, int32_t *parent, int32_t *owner,
+    const int32_t *targets, int32_t n_targets,
+    float *cost_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info);
+/* Start costs ("Start costs"): trg_engine_cost_field_models with a start cost per set entry, so
+ * that a robot with a head start, a handicapped source or a pose joined to the graph by verified links
+ * (trg_engine_pose_links) starts a field.  Field k is the single-source field from a virtual node rho_k added to the
+ * graph: for every entry j of set k one arc rho_k -> set_ids[j] of cost c0 = set_cost0[j] + 0.0f, nothing enters
+ * rho_k, and the arcs are exempt from the Invalid rule as set members are.  Hops are counted from the members' level:
+ *   cost[v]    that field's cost bits
+ *   hops[v]    its hops - 1
+ *   parent[v]  its parent, rho_k reported as -1
+ * A node whose parent is rho_k is a ROOT: a member whose final cost is, bit for bit, its least start cost.  A cheaper
+ * walk from another root strictly beats a start cost, an equal-cost walk does not ((c0, 0) is the smaller key); a
+ * member that is not a root is an ordinary node with a parent and an owner.
+ *   owner[v]   for a root, the least entry naming it whose c0 bits equal its cost; else owner[parent[v]]
+ * owned, reached_out, owner_at, budget / settle / bound_out and the truncation are the set call's, over these keys: a
+ * member whose start cost lies above the bound is unreached.  models pass through unchanged.
+ * The solve is retained: trg_engine_field_reached works on it; trg_engine_field_routes ends a route at a root, with
+ * TrgRouteInfo.cost the key's cost, start cost included, and path_length, avg_risk and num_nodes over graph edges and
+ * nodes only; trg_engine_cost_field_refresh refuses it (TRG_ERR_INVALID_ARG, the message says why) and leaves it
+ * answering, as it does a bounded one.  set_cost0 == NULL is trg_engine_cost_field_models, bit for bit on every
+ * output.  Risk solves take no start values.
+ * TRG_ERR_INVALID_ARG, naming set and entry, for a start cost that is NaN, negative (-0 is not) or infinite;
+ * everything else as trg_engine_cost_field_models. */
+TrgStatus trg_engine_cost_field_seeded(
+    TrgEngine *e, int32_t m,
+    const TrgFieldModel *models,
+    const int32_t *set_ptr, const int32_t *set_ids,
+    const float *set_cost0,      /* set_ptr[m] start costs, or NULL: +0 each */
     const float *budget, int32_t settle,
     float *cost, int32_t *hops, int32_t *parent, int32_t *owner,
     const int32_t *targets, int32_t n_targets,

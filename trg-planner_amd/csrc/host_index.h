@@ -341,6 +341,25 @@ class NodeGrid {
         }
   }
 
+  // Every slot of the cells that the disc of radius r around (qx, qy) touches, with room for the rounding of the
+  // cell arithmetic: a superset of the slots within r, in no particular order; the caller applies its own test.
+  void disc_cells(float qx, float qy, float r, std::vector<int> &out) const {
+    out.clear();
+    const float rad = r * 1.01f + 1e-3f;
+    // (a position far outside the grid: clamped as a float, before the conversion)
+    const auto cell = [&](float c, int step, int n) {
+      const float f = std::floor(c * inv_);
+      return f < 0.0f ? 0 : f >= (float)n ? n - 1 : clampi((int)f + step, 0, n - 1);
+    };
+    const int cx0 = cell(qx - rad - x0_, -1, W_), cx1 = cell(qx + rad - x0_, 1, W_);
+    const int cy0 = cell(qy - rad - y0_, -1, H_), cy1 = cell(qy + rad - y0_, 1, H_);
+    if (qx + rad < x0_ || qy + rad < y0_ || qx - rad > x0_ + (float)W_ * g_ + g_ || qy - rad > y0_ + (float)H_ * g_ + g_)
+      return;  // the disc lies outside every cell
+    for (int yy = cy0; yy <= cy1; ++yy)
+      for (int xx = cx0; xx <= cx1; ++xx)
+        for (int s = head_[(size_t)yy * W_ + xx]; s >= 0; s = next_[s]) out.push_back(s);
+  }
+
   void insert(float x, float y) {  // slot index == insertion order
     const int slot = (int)px_.size();
     px_.push_back(x);

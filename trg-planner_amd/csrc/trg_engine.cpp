@@ -1507,6 +1507,97 @@ TrgStatus is_frontier_batch(TrgEngine *e, const float *xy, size_t m, int32_t *fl
   return TRG_OK;
 }
 
+// Pose links ("Pose links"): the candidates of every pose from the node grid, then ONE collision
+// batch, ONE elevation batch and ONE edge batch for all poses, and the sort per pose on the host.
+TrgStatus pose_links(TrgEngine *e, const float *xy, int32_t m, float radius, int32_t cap, int32_t *link_node,
+                     float *link_weight, float *link_dist, TrgPoseInfo *infos) {
+  if (m < 0) return e->fail(TRG_ERR_INVALID_ARG, "m < 0");
+  if (cap < 0) return e->fail(TRG_ERR_INVALID_ARG, "cap < 0");
+  // wireEdge asserts dist < 2.5 * expand_dist (trg.cpp:279), the product taken in double
+  if (!(radius > 0.0f) || !((double)radius < 2.5 * (double)e->prm.expand_dist))
+    return e->fail(TRG_ERR_INVALID_ARG, "radius " + std::to_string(radius) + " is not a number in (0, 2.5 * expand_dist = " +
+                                            std::to_string(2.5 * (double)e->prm.expand_dist) + ")");
+  if (m == 0) return TRG_OK;
+  if (!xy || !infos) return e->fail(TRG_ERR_INVALID_ARG, "null poses_xy or infos");
+  for (int k = 0; k < m; ++k)
+    if (std::isnan(xy[2 * k]) || std::isnan(xy[2 * k + 1]))
+      return e->fail(TRG_ERR_INVALID_ARG, "the position of pose " + std::to_string(k) + " is not a number");
+  if (!e->gmap.valid) return e->fail(TRG_ERR_NO_MAP, "no global map");
+  if (e->nx.empty()) return e->fail(TRG_ERR_NO_GRAPH, "graph is empty");
+  ensure_host_grid(e);
+  const size_t M = (size_t)m;
+  std::vector<int32_t> hit(M);
+  std::vector<float> z(M);
+  TrgStatus st = collision_sync(e, e->gmap, e->prm.collision_threshold, xy, M, hit.data(), nullptr, nullptr);
+  if (st != TRG_OK) return st;
+  if ((st = nearest_z_sync(e, e->gmap, xy, M, z.data(), nullptr)) != TRG_OK) return st;
+  // a link before the sort; `eval`: its place in the edge batch, -1 for the node the pose stands on
+  struct Link {
+    int node, eval;
+    float w, d;
+  };
+  std::vector<std::vector<Link>> links(M);
+  std::vector<float> p1, p2;
+  std::vector<int> slots;
+  const int V = (int)e->nx.size();
+  for (size_t k = 0; k < M; ++k) {
+    infos[k] = TrgPoseInfo{hit[k] ? 1 : 0, 0, 0, z[k]};
+    if (hit[k]) continue;
+    const float px = xy[2 * k], py = xy[2 * k + 1];
+    const auto candidate = [&](int v) {
+      if (e->nstate[v] == TRG_NODE_INVALID) return;
+      const float dx = px - e->nx[v], dy = py - e->ny[v];
+      const float xx = dx * dx, yy = dy * dy;  // (each product rounded on its own: no contraction)
+      const float d = sqrtf(xx + yy);
+      if (!(d <= radius)) return;
+      infos[k].n_candidates++;
+      if (d == 0.0f) {
+        links[k].push_back({v, -1, 0.0f, 0.0f});
+        return;
+      }
+      links[k].push_back({v, (int)(p1.size() / 3), 0.0f, 0.0f});
+      p1.insert(p1.end(), {px, py, z[k]});
+      p2.insert(p2.end(), {e->nx[v], e->ny[v], e->nz[v]});
+    };
+    if (e->grid.ready() && e->grid.size() == (size_t)V) {
+      e->grid.disc_cells(px, py, radius, slots);
+      for (int v : slots) candidate(v);
+    } else {
+      for (int v = 0; v < V; ++v) candidate(v);
+    }
+  }
+  const size_t n_eval = p1.size() / 3;
+  std::vector<int32_t> status(n_eval);
+  std::vector<float> w(n_eval), d(n_eval);
+  if (n_eval && (st = edges_sync(e, e->gmap, p1.data(), p2.data(), n_eval, status.data(), nullptr, w.data(), d.data(),
+                                 true)) != TRG_OK)
+    return st;
+  for (size_t k = 0; k < M; ++k) {
+    std::vector<Link> &L = links[k];
+    size_t n = 0;
+    for (const Link &c : L) {
+      if (c.eval >= 0 && status[c.eval] != EDGE_OK) continue;
+      L[n++] = c.eval < 0 ? c : Link{c.node, c.eval, w[c.eval], d[c.eval]};
+    }
+    L.resize(n);
+    const auto bits = [](float f) {
+      uint32_t b;
+      memcpy(&b, &f, sizeof b);
+      return b;
+    };
+    std::sort(L.begin(), L.end(), [&](const Link &a, const Link &b) {
+      return bits(a.d) != bits(b.d) ? bits(a.d) < bits(b.d) : a.node < b.node;
+    });
+    infos[k].n_links = (int32_t)n;
+    for (size_t i = 0; i < std::min<size_t>(n, (size_t)cap); ++i) {
+      if (link_node) link_node[k * cap + i] = L[i].node;
+      if (link_weight) link_weight[k * cap + i] = L[i].w;
+      if (link_dist) link_dist[k * cap + i] = L[i].d;
+    }
+  }
+  return TRG_OK;
+}
+
 TrgStatus get_sampler_table(TrgEngine *e, float *cos_out, float *sin_out) {
   TrgStatus st = ensure_sampler(e, nullptr);
   if (st != TRG_OK) return st;
@@ -1648,6 +1739,12 @@ TrgStatus trg_engine_get_stats(const TrgEngine *e, TrgStats *out) {
     *out = e->stats;
     return TRG_OK;
   });
+}
+
+TrgStatus trg_engine_pose_links(TrgEngine *e, const float *poses_xy, int32_t m, float radius, int32_t cap,
+                                int32_t *link_node, float *link_weight, float *link_dist, TrgPoseInfo *infos) {
+  return entry(e, "pose_links", DEVICE,
+               [&] { return pose_links(e, poses_xy, m, radius, cap, link_node, link_weight, link_dist, infos); });
 }
 
 TrgStatus trg_engine_get_sampler_table(TrgEngine *e, float *cos_out, float *sin_out) {

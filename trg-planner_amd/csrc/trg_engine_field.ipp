@@ -62,6 +62,7 @@ struct FieldBufs {
     bool owners = false;     // ... and the owner pass ran: sets->owner is filled
     bool bounded = false;    // keys above a bound were removed: nothing a refresh can start from
     bool risk = false;       // a risk solve ("Risk fields"): F.ec holds the edge risks
+    bool seeded = false;     // its members had start costs ("Start costs"): no refresh either
     // its cost models ("Cost models"): per field, empty when the request named none; F.ec is
     // the slot all fields share, or with `many` slot 0 and `models` the table the kernels take
     std::vector<TrgFieldModel> pairs;
@@ -70,6 +71,7 @@ struct FieldBufs {
     // (F.V and F.m are the node count of its graph and its fields: what a refresh reads the old keys by)
   } last;
   DevArr set_ptr, set_ids, owner, owner_at, owned, own_changed;  // set solves; owner: m x V, only when asked for
+  DevArr set_cost0;          // ... with start costs: one cost word per entry
   std::vector<int32_t> h_set_ptr, h_set_ids;  // the sets as uploaded, for a refresh to carry to the next graph
   DevArr key0, node_map, carried;  // refresh: the carried, then the anchored keys (m x V); new2old (V); counts (m)
   Pinned<int> h_carried;     // per field
@@ -119,6 +121,7 @@ struct FieldRequest {
   float *bound_out;           // m, may be nullptr
   // a set solve (trg_engine_cost_field_sets): field k starts from set_ids[set_ptr[k] .. set_ptr[k + 1])
   const int32_t *set_ptr, *set_ids;
+  const float *set_cost0;  // set_ptr[m] start costs (trg_engine_cost_field_seeded), or nullptr: +0 each
   int32_t *owner;     // m x V
   int32_t *owner_at;  // m x n_targets
   int32_t *owned;     // set_ptr[m]
@@ -170,6 +173,7 @@ struct FieldRun {
   FieldDev old{};
   std::vector<int32_t> identity, src, set_ptr, set_ids;
   std::vector<TrgFieldModel> pairs;  // ... and its models
+  std::vector<uint32_t> cost0;       // a seeded solve: the start costs as cost bits (-0 as +0), per entry
   // the edge costs of this solve (field_edge_costs): the slot table, whether the fields read more than one slot
   // (else F.ec is the one they share and no kernel takes the table), and the mean over its distinct slots
   FieldModels models{};
@@ -216,6 +220,9 @@ TrgStatus field_check_refresh(TrgEngine *e, FieldRun &run) {
   rq.risk = old.risk;
   if (old.bounded)
     return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is bounded (a bounded solve cannot be refreshed)");
+  if (old.seeded)
+    return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve has start costs (a seeded solve cannot be "
+                                               "refreshed: its members' keys are not carried)");
   if (field_last_current(e, old))
     return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is already of the current graph");
   const int V = (int)e->nx.size(), V_old = old.F.V, m = old.F.m;
@@ -278,7 +285,8 @@ TrgStatus field_check_refresh(TrgEngine *e, FieldRun &run) {
   return TRG_OK;
 }
 
-// The sets of a set solve (trg_engine_cost_field_sets): set_ptr from 0 and strictly ascending, every id a node.
+// The sets of a set solve (trg_engine_cost_field_sets): set_ptr from 0 and strictly ascending, every id a node; a
+// start cost (trg_engine_cost_field_seeded) is a finite number >= 0, kept as cost bits with -0 as +0.
 // Field k's source, for `info` and the reached list, is its set's first id.
 TrgStatus field_check_sets(TrgEngine *e, FieldRun &run) {
   const FieldRequest &rq = run.rq;
@@ -298,6 +306,18 @@ TrgStatus field_check_sets(TrgEngine *e, FieldRun &run) {
     run.sources.id[k] = rq.set_ids[rq.set_ptr[k]];
   }
   run.sets.n = rq.set_ptr[m];
+  if (rq.set_cost0) {
+    run.cost0.resize((size_t)run.sets.n);
+    for (int k = 0; k < m; ++k)
+      for (int j = rq.set_ptr[k]; j < rq.set_ptr[k + 1]; ++j) {
+        const float c0 = rq.set_cost0[j];
+        if (!(c0 >= 0.0f) || std::isinf(c0))
+          return e->fail(TRG_ERR_INVALID_ARG, "cost field sets: the start cost of entry " +
+                                                  std::to_string(j - rq.set_ptr[k]) + " of set " + std::to_string(k) +
+                                                  " is negative or not finite");
+        run.cost0[j] = float_bits(c0 + 0.0f);
+      }
+  }
   run.owners = rq.owner || rq.owned || (rq.owner_at && rq.n_targets > 0);
   return TRG_OK;
 }
@@ -566,6 +586,11 @@ TrgStatus field_uploads(TrgEngine *e, FieldRun &run) {
     S.ids = fb.set_ids.as<int>();
     fb.h_set_ptr.assign(rq.set_ptr, rq.set_ptr + F.m + 1);
     fb.h_set_ids.assign(rq.set_ids, rq.set_ids + S.n);
+    if (rq.set_cost0) {
+      if ((st = field_grow(e, fb.set_cost0, (size_t)S.n * sizeof(unsigned))) != TRG_OK) return st;
+      HIPCHK(e, hipMemcpyAsync(fb.set_cost0.p, run.cost0.data(), (size_t)S.n * sizeof(unsigned),
+                               hipMemcpyHostToDevice, s));
+    }
   }
   return TRG_OK;
 }
@@ -663,6 +688,7 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
   const FieldModels *models = run.model_table();
   const FieldSettle under{fb.targets.as<int>(), rq.n_targets, rq.settle};
   const FieldSets *sets = rq.set_ptr ? &run.sets : nullptr;
+  const unsigned *cost0 = rq.set_cost0 ? fb.set_cost0.as<unsigned>() : nullptr;
   TrgStatus st;
   if (run.bounded) launch_field_bounds(F, run.budgets, s);
   for (int pass = 0; pass < 2; ++pass) {
@@ -671,10 +697,10 @@ TrgStatus field_passes(TrgEngine *e, FieldRun &run) {
     const bool under_bounds = run.bounded && pass == 0;
     F.tight = pass ? fb.cost.as<unsigned>() : nullptr;
     if (!rq.refresh) {
-      launch_field_init(F, run.sources, sets, nullptr, delta, s);
+      launch_field_init(F, run.sources, sets, cost0, nullptr, delta, s);
     } else {
       if (pass == 0) {
-        launch_field_init(F, run.sources, sets, fb.key0.as<unsigned long long>(), delta, s);
+        launch_field_init(F, run.sources, sets, nullptr, fb.key0.as<unsigned long long>(), delta, s);
         launch_field_supporters(F, s, models, rq.risk);
       }
       if ((st = field_anchor(e, run, pass == 0)) != TRG_OK) return st;
@@ -763,6 +789,7 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   fb.last.F.tight = nullptr;  // (its array holds the cost output now)
   fb.last.bounded = run.bounded;
   fb.last.risk = rq.risk;
+  fb.last.seeded = rq.set_cost0 != nullptr;
   if (rq.models) fb.last.pairs.assign(rq.models, rq.models + m);
   fb.last.models = run.models;
   fb.last.many = run.many_models;
@@ -1049,9 +1076,10 @@ TrgStatus cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *source_ids,
   return field_solve(e, rq, out);
 }
 
-// ... and the one behind trg_engine_cost_field_models and, without models, trg_engine_cost_field_sets
+// ... and the one behind trg_engine_cost_field_seeded, without start costs trg_engine_cost_field_models and, without
+// models either, trg_engine_cost_field_sets
 TrgStatus cost_field_models(TrgEngine *e, int32_t m, const TrgFieldModel *models, const int32_t *set_ptr,
-                            const int32_t *set_ids, const float *budget, int32_t settle, float *cost, int32_t *hops,
+                            const int32_t *set_ids, const float *set_cost0, const float *budget, int32_t settle, float *cost, int32_t *hops,
                             int32_t *parent, int32_t *owner, const int32_t *targets, int32_t n_targets, float *cost_at,
                             int32_t *hops_at, int32_t *owner_at, int32_t *owned, int32_t *reached_out, float *bound_out,
                             TrgFieldInfo *out) {
@@ -1066,6 +1094,7 @@ TrgStatus cost_field_models(TrgEngine *e, int32_t m, const TrgFieldModel *models
   rq.bound_out = bound_out;
   rq.set_ptr = set_ptr;
   rq.set_ids = set_ids;
+  rq.set_cost0 = set_cost0;
   rq.owner = owner;
   rq.owner_at = owner_at;
   rq.owned = owned;
@@ -1119,7 +1148,7 @@ TrgStatus trg_engine_cost_field_sets(TrgEngine *e, int32_t m, const int32_t *set
                                      int32_t *hops_at, int32_t *owner_at, int32_t *owned, int32_t *reached_out,
                                      float *bound_out, TrgFieldInfo *info) {
   return field_entry(e, info, "cost field sets", [&](TrgFieldInfo *out) {
-    return cost_field_models(e, m, nullptr, set_ptr, set_ids, budget, settle, cost, hops, parent, owner, targets,
+    return cost_field_models(e, m, nullptr, set_ptr, set_ids, nullptr, budget, settle, cost, hops, parent, owner, targets,
                              n_targets, cost_at, hops_at, owner_at, owned, reached_out, bound_out, out);
   });
 }
@@ -1130,8 +1159,20 @@ TrgStatus trg_engine_cost_field_models(TrgEngine *e, int32_t m, const TrgFieldMo
                                        int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
                                        int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info) {
   return field_entry(e, info, "cost field sets", [&](TrgFieldInfo *out) {
-    return cost_field_models(e, m, models, set_ptr, set_ids, budget, settle, cost, hops, parent, owner, targets,
-                             n_targets, cost_at, hops_at, owner_at, owned, reached_out, bound_out, out);
+    return cost_field_models(e, m, models, set_ptr, set_ids, nullptr, budget, settle, cost, hops, parent, owner,
+                             targets, n_targets, cost_at, hops_at, owner_at, owned, reached_out, bound_out, out);
+  });
+}
+
+TrgStatus trg_engine_cost_field_seeded(TrgEngine *e, int32_t m, const TrgFieldModel *models, const int32_t *set_ptr,
+                                       const int32_t *set_ids, const float *set_cost0, const float *budget,
+                                       int32_t settle, float *cost, int32_t *hops, int32_t *parent, int32_t *owner,
+                                       const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at,
+                                       int32_t *owner_at, int32_t *owned, int32_t *reached_out, float *bound_out,
+                                       TrgFieldInfo *info) {
+  return field_entry(e, info, "cost field sets", [&](TrgFieldInfo *out) {
+    return cost_field_models(e, m, models, set_ptr, set_ids, set_cost0, budget, settle, cost, hops, parent, owner,
+                             targets, n_targets, cost_at, hops_at, owner_at, owned, reached_out, bound_out, out);
   });
 }
 

@@ -44,6 +44,11 @@
 // route walk (which differs in where a walk must end); k_field_seed and the owner pass a solve from single
 // sources never launches.
 //
+// Start costs ("Start costs"): a set entry may start at a cost of its own -- the field from a
+// virtual node joined to the members by arcs of those costs, still one least fixed point.  Only k_field_seed knows:
+// its COST0 instantiation seeds entry e at (cost0[e], 0), in pass 2 only where that is the item's least cost, so that
+// the member marks name the roots; the relaxation, the owner pass and the route walk are the set solve's.
+//
 // Refresh ("Refresh"): the keys of a solve on an earlier graph, carried through a node map,
 // are starting points on the current one once the anchor has dropped every key that is not a walk's of the current
 // graph: the supporter forest of k_field_parent, pointer-jumped as the owner pass jumps the parents (one begin kernel,
@@ -710,10 +715,21 @@ __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const 
 
 // ---- source sets ("Source sets") ----------------------------------------------------------
 
+// what k_field_seed takes last: the start costs of a seeded solve, or nothing
+struct FieldNoCost0 {};
+template <bool COST0>
+using FieldCost0Arg = std::conditional_t<COST0, const unsigned *, FieldNoCost0>;
+
 // One thread per entry of all sets: its item gets key (0, 0) and the least entry that names it (atomicMin on the
 // member word, see FieldSets); the entry that finds the word unmarked pushes the item, so a duplicate is queued
 // once.  The queue size and `work` grow by one atomicAdd per wave each.
-__global__ __launch_bounds__(THREADS) void k_field_seed(FieldDev F, FieldSets S) {
+// COST0 ("Start costs"): entry e starts at key (cost0[e], 0), cost bits.  Pass 1: the item's
+// key is the least of its entries' (atomicMin), and it is queued in near queue 0 whatever its cost; the relaxation
+// may improve it and then overwrites its mark, which nobody reads before pass 2 seeds again.  Pass 2 (F.tight):
+// only an entry whose start cost is the item's least cost seeds it -- the item is a root, no tight extension is
+// below (cost, 0), so its mark stays and names the least such entry; every other member is an ordinary node.
+template <bool COST0>
+__global__ __launch_bounds__(THREADS) void k_field_seed(FieldDev F, FieldSets S, FieldCost0Arg<COST0> cost0) {
   const int n_iter = (S.n + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
   for (int it = 0, e = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, e += gridDim.x * blockDim.x) {
     bool first = false;
@@ -726,8 +742,20 @@ __global__ __launch_bounds__(THREADS) void k_field_seed(FieldDev F, FieldSets S)
         else hi = mid;
       }
       item = lo * F.V + S.ids[e];
-      F.key[item] = 0ull;
-      first = atomicMin(&F.stamp_near[item], FIELD_MEMBER | e) >= 0;
+      if constexpr (COST0) {
+        const unsigned c0 = cost0[e];
+        const unsigned long long k0 = (unsigned long long)c0 << 32;
+        if (!F.tight) {
+          atomicMin(&F.key[item], k0);
+          first = atomicMin(&F.stamp_near[item], FIELD_MEMBER | e) >= 0;
+        } else if (c0 == F.tight[item]) {
+          F.key[item] = k0;  // (every entry that gets here writes this word)
+          first = atomicMin(&F.stamp_near[item], FIELD_MEMBER | e) >= 0;
+        }
+      } else {
+        F.key[item] = 0ull;
+        first = atomicMin(&F.stamp_near[item], FIELD_MEMBER | e) >= 0;
+      }
     }
     const unsigned long long mk = ballot(first);
     const int slot = wave_reserve(first, &F.ctrl->c.n[0]);
@@ -975,11 +1003,14 @@ void launch_field_edge_risk(const int *col, const float *w, const int *state, in
                      er, st);
 }
 
-void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets,
+void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets, const unsigned *cost0,
                        const unsigned long long *carried, float delta, hipStream_t s) {
   hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, sources, delta,
                      sets == nullptr, carried);
-  if (sets) hipLaunchKernelGGL(k_field_seed, dim3(field_blocks(sets->n, THREADS)), dim3(THREADS), 0, s, F, *sets);
+  if (!sets) return;
+  const dim3 grid(field_blocks(sets->n, THREADS));
+  if (cost0) hipLaunchKernelGGL(k_field_seed<true>, grid, dim3(THREADS), 0, s, F, *sets, cost0);
+  else hipLaunchKernelGGL(k_field_seed<false>, grid, dim3(THREADS), 0, s, F, *sets, FieldNoCost0{});
 }
 
 void launch_field_round(const FieldDev &F, int round, hipStream_t s, const FieldSettle *under_bounds,

@@ -443,6 +443,8 @@ struct FieldModels {
 // Which entry stands for a member item is kept in the item's stamp_near word: FIELD_MEMBER | its least entry.
 // A round stamp is >= 1 and k_field_init leaves 0, so the word is negative for members only, and it stays so:
 // a member's key (0, 0) is never improved, hence the relaxation never pushes, and never stamps, a member.
+// With start costs ("Start costs") that holds for pass 2 only, which marks the roots alone -- the
+// members whose key is their least start cost; pass 1 may overwrite a mark, and nothing reads one before pass 2.
 struct FieldSets {
   const int *ptr;   // m + 1 entry offsets, ptr[0] == 0 (device)
   const int *ids;   // ptr[m] node ids (device)
@@ -478,9 +480,12 @@ void launch_field_edge_risk(const int *col, const float *w, const int *state, in
 // Field k starts at node sources.id[k], k < F.m (duplicates give identical fields).  With `sets` (a set solve; else
 // nullptr) sources is not read: every item is left without a key, then a second launch seeds every distinct member
 // item and pushes it once to near queue 0; F.ctrl's queue size and work are the count of distinct member items.
+// With `cost0` (a seeded solve, DESIGN.md section 2, "Start costs"; sets->n cost words on the device, else nullptr)
+// entry e seeds its item at key (cost0[e], 0): in pass 1 the least of an item's entries, in pass 2 (F.tight set) only
+// the entries whose start cost is the item's least cost, so that the member marks then name exactly the roots.
 // With `carried` (a refresh's launch_field_carry output, per item; else nullptr) every item that is no source starts
 // with its carried key instead of none; the queue is then not used: the warm start empties it.
-void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets,
+void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets, const unsigned *cost0,
                        const unsigned long long *carried, float delta, hipStream_t s);
 // the settle step of a bounded round: n_t target nodes (device ids) and the mode, FIELD_SETTLE_*
 struct FieldSettle {

@@ -69,6 +69,10 @@ class TrgFieldModel(C.Structure):
     _fields_ = [("safety_factor", C.c_float), ("max_weight", C.c_float)]
 
 
+class TrgPoseInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_candidates", C.c_int32), ("n_links", C.c_int32), ("z", C.c_float)]
+
+
 class TrgStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "map_points", "expanded_nodes", "trials", "samples", "created_nodes", "invalid_nodes",
@@ -109,6 +113,7 @@ EXPORTS = [
     "trg_engine_field_routes", "trg_engine_cost_field_bounded", "trg_engine_field_reached",
     "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh", "trg_engine_cost_field_models",
     "trg_engine_risk_field_sets", "trg_engine_risk_field_refresh",
+    "trg_engine_pose_links", "trg_engine_cost_field_seeded",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -206,6 +211,10 @@ def load_library():
                                              ip, ip, ip, fp, C.POINTER(TrgFieldInfo)]
     L.trg_engine_cost_field_models.argtypes = [vp, C.c_int32, C.POINTER(TrgFieldModel), ip, ip, fp, C.c_int32, fp, ip,
                                                ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, fp, C.POINTER(TrgFieldInfo)]
+    L.trg_engine_cost_field_seeded.argtypes = [vp, C.c_int32, C.POINTER(TrgFieldModel), ip, ip, fp, fp, C.c_int32, fp,
+                                               ip, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, fp,
+                                               C.POINTER(TrgFieldInfo)]
+    L.trg_engine_pose_links.argtypes = [vp, fp, C.c_int32, C.c_float, C.c_int32, ip, fp, fp, C.POINTER(TrgPoseInfo)]
     L.trg_engine_risk_field_sets.argtypes = L.trg_engine_cost_field_sets.argtypes
     L.trg_engine_cost_field_refresh.argtypes = [vp, ip, C.c_int32, fp, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, ip, ip,
                                                 C.POINTER(TrgFieldInfo)]
@@ -691,9 +700,23 @@ class Engine:
         as solved."""
         return self._cost_fields_from(sets, models, targets, full, budget, settle)
 
-    def _cost_fields_from(self, sets, models, targets, full, budget, settle):
+    def cost_fields_seeded(self, sets, start_costs, targets=None, full=True, budget=None, settle=None, models=None):
+        """cost_fields_from with a start cost per set entry (trg_engine_cost_field_seeded; DESIGN.md section 2, "Start
+        costs"): start_costs[k][j] is the cost at which entry j of sets[k] starts, a finite number >= 0; None is
+        cost_fields_from (every entry at +0).  A member reached cheaper from another one is an ordinary node of the
+        field; "owner" names, for a node, the entry its route starts from.  -> cost_fields_from's dict, plus
+        "start_costs" (the m float32 arrays as solved) and, with `models`, "models"."""
+        return self._cost_fields_from(sets, models, targets, full, budget, settle, start_costs=start_costs)
+
+    def _cost_fields_from(self, sets, models, targets, full, budget, settle, start_costs=None):
         sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
         m = len(sets)
+        c0 = None
+        if start_costs is not None:
+            starts = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in start_costs]
+            if len(starts) != m or any(c.shape != s.shape for c, s in zip(starts, sets)):
+                raise ValueError("cost_fields_seeded: start_costs and sets differ in shape")
+            c0 = np.ascontiguousarray(np.concatenate(starts) if m else np.empty(0, np.float32), dtype=np.float32)
         marr, pairs = (None, None) if models is None else self._models("cost_fields_from_models", models, m)
         out, a = self._field_outputs("cost_fields_from", m, targets, full, budget, settle, owners=True)
         ptr = np.zeros(m + 1, np.int64)
@@ -706,7 +729,12 @@ class Engine:
         info = TrgFieldInfo()
         tail = [_i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
                 _i(owned), a["reached"], a["bound"], C.byref(info)]
-        if marr is None:
+        if c0 is not None:
+            self._chk(self.L.trg_engine_cost_field_seeded(self.h, m, marr, *tail[:2], _f(c0), *tail[2:]))
+            out["start_costs"] = starts
+            if marr is not None:
+                out["models"] = pairs
+        elif marr is None:
             self._chk(self.L.trg_engine_cost_field_sets(self.h, m, *tail))
         else:
             self._chk(self.L.trg_engine_cost_field_models(self.h, m, marr, *tail))
@@ -1107,6 +1135,90 @@ class Engine:
         self._chk(self.L.trg_engine_edge_risk_batch(self.h, _KINDS[kind], _f(p1), _f(p2), m,
                                                     _i(status), _i(n_pts), _f(w), _f(d)))
         return status, n_pts, w, d
+
+    # ---- poses: verified links onto the graph, fields and plans that start from them ------------------------
+    def pose_links(self, poses_xy, radius=None, cap=32):
+        """The verified links from every position of `poses_xy` (m, 2) to the global graph (trg_engine_pose_links;
+        DESIGN.md section 2, "Pose links"): the non-Invalid nodes within `radius` (None: expand_dist, the range of
+        expandGraph's step 3) that an edge from a node at the pose would reach -- slope gate, segment collision walk and
+        risk weight as wireEdge's.  -> one dict per pose: "status" (1: the pose is in collision and has no links),
+        "z" (the elevation addNode would give it), "n_candidates", "n_links" (the full counts) and, for the first `cap`
+        links by (dist, node), "nodes" int32, "weight", "dist" and "cost" float32 -- cost is the engine's own edge
+        cost, (safety_factor * weight + 1) * dist in fp32."""
+        xy = np.ascontiguousarray(poses_xy, dtype=np.float32).reshape(-1, 2)
+        m, cap = xy.shape[0], int(cap)
+        if radius is None:
+            radius = self.params.expand_dist
+        room = max(m * max(cap, 0), 1)
+        nodes = np.full(room, -1, np.int32)
+        w = np.zeros(room, np.float32)
+        d = np.zeros(room, np.float32)
+        infos = (TrgPoseInfo * max(m, 1))()
+        self._chk(self.L.trg_engine_pose_links(self.h, _f(xy), m, C.c_float(radius), cap, _i(nodes), _f(w), _f(d),
+                                               infos))
+        sf = np.float32(self.params.safety_factor)
+        out = []
+        for k in range(m):
+            n = min(infos[k].n_links, cap)
+            a = k * cap
+            wk, dk = w[a:a + n].copy(), d[a:a + n].copy()
+            out.append({"status": infos[k].status, "z": np.float32(infos[k].z), "n_candidates": infos[k].n_candidates,
+                        "n_links": infos[k].n_links, "nodes": nodes[a:a + n].copy(), "weight": wk, "dist": dk,
+                        "cost": (sf * wk + np.float32(1)) * dk})
+        return out
+
+    def cost_fields_from_poses(self, poses_xy, radius=None, targets=None, full=True, budget=None, settle=None):
+        """m cost fields in one solve, field k from the pose poses_xy[k] itself: its link nodes (pose_links) are the
+        set, the link costs the start costs, so the field is the exact cost from the pose over the verified links and
+        the graph.  -> cost_fields_seeded's dict plus "links" (pose_links' records); "owner" is the index of the link
+        a node's route enters the graph by.  A pose in collision or without links raises TrgError(INVALID_ARG) naming
+        it: the caller decides whether to fall back to the snapped node (cost_fields)."""
+        links = self.pose_links(poses_xy, radius)
+        for k, one in enumerate(links):
+            if one["status"] != 0:
+                raise TrgError(1, f"cost_fields_from_poses: pose {k} is in collision")
+            if one["nodes"].size == 0:
+                raise TrgError(1, f"cost_fields_from_poses: pose {k} has no links to the graph")
+        r = self.cost_fields_seeded([one["nodes"] for one in links], [one["cost"] for one in links], targets=targets,
+                                    full=full, budget=budget, settle=settle)
+        r["links"] = links
+        return r
+
+    def plan_anchored(self, start_xy, goal_xy, radius=None):
+        """A least-cost path between two POSITIONS over verified links: both poses' links from one pose_links call, one
+        seeded solve from the start's links that stops once every goal link node is settled, the field read at those
+        nodes on the device, and one routes call.  Goal link j, from the goal pose to node b_j at link cost c_j (a goal
+        link is evaluated from the goal pose, like any other), ends a path of key (fl(cost[b_j] + c_j), hops[b_j] + 1);
+        the least key wins, the earlier link on a tie.  -> dict: "found"; "cost", the winning key's cost; "node_ids";
+        "path" float32 (n + 2, 3): the start pose's xyz, the route's, the goal pose's; "start_link" and "goal_link" as
+        (node, weight, dist); "num_nodes", "path_length" and "avg_risk" of the route (graph nodes and edges only);
+        "info", the solve's TrgFieldInfo.
+        found is False when either pose has no links or no goal link node is reached.  There is no direct
+        pose-to-pose segment: two poses that see each other still go through a node."""
+        xy = np.ascontiguousarray([start_xy, goal_xy], dtype=np.float32).reshape(2, 2)
+        start, goal = self.pose_links(xy, radius)
+        none = {"found": False, "cost": float("inf"), "node_ids": np.empty(0, np.int32),
+                "path": np.empty((0, 3), np.float32), "start_link": None, "goal_link": None, "num_nodes": 0,
+                "path_length": 0.0, "avg_risk": 0.0}
+        if start["nodes"].size == 0 or goal["nodes"].size == 0:
+            return none
+        r = self.cost_fields_seeded([start["nodes"]], [start["cost"]], targets=goal["nodes"], full=False, settle="all")
+        cost, hops = r["cost_at"][0], r["hops_at"][0]
+        ok = np.flatnonzero(hops >= 0)
+        if ok.size == 0:
+            return none
+        total = cost[ok] + goal["cost"][ok]  # (float32 + float32: one rounded add)
+        j = int(ok[np.lexsort((ok, hops[ok], total))[0]])
+        b = int(goal["nodes"][j])
+        (ids, pts, one), = self.routes([0], [b], hops_at=[hops[j]])
+        i = int(r["owner_at"][0][j])  # (the start link the route enters the graph by)
+        path = np.concatenate([[[xy[0, 0], xy[0, 1], start["z"]]], pts, [[xy[1, 0], xy[1, 1], goal["z"]]]])
+        return {"found": True, "cost": float(cost[j] + goal["cost"][j]), "node_ids": ids,
+                "path": path.astype(np.float32),
+                "start_link": (int(start["nodes"][i]), float(start["weight"][i]), float(start["dist"][i])),
+                "goal_link": (b, float(goal["weight"][j]), float(goal["dist"][j])),
+                "num_nodes": one.num_nodes, "path_length": float(one.path_length), "avg_risk": float(one.avg_risk),
+                "info": r["info"]}
 
     def voxel_filter(self, xyz, leaf):
         """pcl::VoxelGrid of TRGPlanner::loadPrebuiltMap (trg_planner.cpp:91-94) on the GPU."""
