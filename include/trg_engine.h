@@ -172,6 +172,9 @@ typedef struct TrgStats {
   double ms_upload;            /* host cloud -> HBM of the last setGlobalMap / setLocalMap from a host pointer */
   uint64_t presampled_nodes;   /* always 0: the variant that drew samples inside the previous level's resolve
                                   launch was removed; the field keeps the struct's layout */
+  uint64_t stitch_gate_retries; /* trg_engine_stitch_cross calls that ran their edge selection a second time, after the
+                                  host's libm decided slope gates the device could not call */
+  uint64_t stitch_regrows;     /* trg_engine_stitch_exchange: times a record or edge buffer was too small and grew */
 } TrgStats;
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
@@ -302,7 +305,10 @@ TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size
  * BFS_ERR_STALL -> the level is taken back and replayed on the host), "debug_lookback_level" = n (one
  * workgroup's commit look-back gives up at level n -> BFS_ERR_LOOKBACK -> whole-build host replay),
  * "resolve_tickets" = "1" (every resolve launch takes its workgroup indices from start tickets -- by
- * default only the repeat of a launch whose bounded wait ran out). */
+ * default only the repeat of a launch whose bounded wait ran out), "debug_stitch_cap" = n (first capacity, in rows,
+ * of trg_engine_stitch_exchange's record and edge buffers, so that small tilings reach its regrow loops; 0: the
+ * default).  "comm_wait_seconds" = x > 0 (default 20): the longest an engine of an in-process group
+ * (trg_engine_comm_join_local) waits for the other ranks -- a cap, the exchanges take milliseconds. */
 TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value);
 /* Tiled builds (multi-GPU; an extension, not a reference interface): restrict
  * node creation to the core region [x0,x1) x [y0,y1) -- a sample outside it counts as a rejected
@@ -343,6 +349,16 @@ TrgStatus trg_engine_stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles,
 TrgStatus trg_engine_comm_unique_id(TrgEngine *e, uint8_t id[TRG_COMM_ID_BYTES]);
 TrgStatus trg_engine_comm_init(TrgEngine *e, const uint8_t id[TRG_COMM_ID_BYTES], int32_t nranks, int32_t rank);
 TrgStatus trg_engine_comm_adopt(TrgEngine *e, void *nccl_comm);
+/* The in-process transport, for tests of the exchange's own logic with more than one rank where RCCL cannot run
+ * (it refuses two ranks on one device): the engine becomes rank `rank` of the group `group_name`, which the first
+ * engine to name it makes, with `nranks` ranks, in a process-wide table.  The members are engines on the SAME device
+ * in the same process, each entered from its own thread.  An all-gather of such a group is device-to-device copies on
+ * the engine's own stream between two host barriers; every wait is on the host, in a condition variable, and ends
+ * after "comm_wait_seconds" at the latest with TRG_ERR_DEVICE and a message naming a rank that did not arrive.
+ * After that, or once a member left (trg_engine_comm_destroy, trg_engine_destroy, another join), the group fails
+ * every all-gather at once; a new one needs a new name or all members gone.  TRG_ERR_INVALID_ARG for nranks < 1 or
+ * > 64, a rank outside [0, nranks), a group of another size, a rank that is taken.  Never chosen unless asked for. */
+TrgStatus trg_engine_comm_join_local(TrgEngine *e, const char *group_name, int32_t nranks, int32_t rank);
 TrgStatus trg_engine_comm_destroy(TrgEngine *e);
 TrgStatus trg_engine_stitch_exchange(TrgEngine *e, const float core_xyxy[4], int32_t cols, int32_t rows,
                                      int32_t *n_boundary, int32_t *n_cross);

@@ -106,6 +106,8 @@ def refusal_table(cloud):
         r("comm_init rank", L.trg_engine_comm_init(h, ident, 2, 2))
         r("comm_adopt null", L.trg_engine_comm_adopt(h, None))
         r("stitch_exchange no communicator", L.trg_engine_stitch_exchange(h, f4, 1, 1, None, None))
+        r("comm_join_local null name", L.trg_engine_comm_join_local(h, None, 2, 0))
+        r("comm_join_local rank", L.trg_engine_comm_join_local(h, b"refusals", 2, 2))
 
     cases("null engine", None)
     row("null engine:comm_destroy", None, L.trg_engine_comm_destroy(None))

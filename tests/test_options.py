@@ -25,6 +25,8 @@ ACCEPTED = {
     "debug_fallback_level": ["6", "-1", "abc"],
     "keep_preclean": ["1", "0", "2"],
     "field_delta_scale": ["4", "0.5", "inf", "1e3", "2x"],
+    "debug_stitch_cap": ["4", "0", "-1", "abc"],
+    "comm_wait_seconds": ["20", "0.5", "1e3"],
 }
 
 # (key, value, the error text)
@@ -40,6 +42,8 @@ REJECTED = [
     ("field_delta_scale", "abc", "field_delta_scale must be > 0"),
     ("field_delta_scale", "nan", "field_delta_scale must be > 0"),
     ("field_delta_scale", "", "field_delta_scale must be > 0"),
+    ("comm_wait_seconds", "0", "comm_wait_seconds must be > 0"),
+    ("comm_wait_seconds", "-2", "comm_wait_seconds must be > 0"),
     ("no_such_option", "1", "unknown option no_such_option"),
     ("", "1", "unknown option "),
     ("Replay", "host", "unknown option Replay"),

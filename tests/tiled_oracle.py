@@ -20,22 +20,32 @@ def stitch_oracle(tiled, prm, cols, rows, cores, oracles):
     return graphs, stitched, tiled.assemble_global(graphs, stitched)
 
 
-def build_tiled_oracle(oa, synth, tiled, prm, cols, rows, nx, ny, halo_pts, seed, sampler_seed,
-                       terrain=None, return_oracles=False):
-    cores = tiled.tile_cores(cols, rows, nx, ny)
+def build_tiled_oracle_explicit(oa, synth, tiled, prm, cols, rows, cores, windows, seed, sampler_seed,
+                                terrain=None, no_graph=()):
+    """The tiled oracle on explicit core rectangles and lattice windows (a split_tile cut, a tile whose cloud is
+    an island inside its core); the tiles in `no_graph` get their map and no init_graph, so they hold no node.
+    Returns (tile graphs, stitched, global graph, oracles)."""
     terrain = terrain or {}
     oracles = []
-    for t, core in enumerate(cores):
-        win = tiled.tile_lattice_window(t, cols, rows, nx, ny, halo_pts)
+    for t, (core, win) in enumerate(zip(cores, windows)):
         cloud = synth.mountain_tile(*win, seed=seed, **terrain)
         o = oa.Oracle(**prm)
         o.set_sampler(sampler_seed, 0, 16)
         o.set_tile(core, epoch=t)
         o.set_global_map(cloud)
-        start = [0.5 * (core[0] + core[2]), 0.5 * (core[1] + core[3]), 0.0]
-        assert o.init_graph(start), f"tile {t}: no root"
+        if t not in no_graph:
+            start = [0.5 * (core[0] + core[2]), 0.5 * (core[1] + core[3]), 0.0]
+            assert o.init_graph(start), f"tile {t}: no root"
         oracles.append(o)
-    graphs, stitched, G = stitch_oracle(tiled, prm, cols, rows, cores, oracles)
+    return stitch_oracle(tiled, prm, cols, rows, cores, oracles) + (oracles,)
+
+
+def build_tiled_oracle(oa, synth, tiled, prm, cols, rows, nx, ny, halo_pts, seed, sampler_seed,
+                       terrain=None, return_oracles=False):
+    cores = tiled.tile_cores(cols, rows, nx, ny)
+    windows = [tiled.tile_lattice_window(t, cols, rows, nx, ny, halo_pts) for t in range(cols * rows)]
+    graphs, stitched, G, oracles = build_tiled_oracle_explicit(oa, synth, tiled, prm, cols, rows, cores, windows,
+                                                               seed, sampler_seed, terrain)
     if return_oracles:
         return graphs, stitched, G, oracles
     return graphs, stitched, G

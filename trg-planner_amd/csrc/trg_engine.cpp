@@ -455,7 +455,7 @@ struct EdgeBatch {
 struct BfsBuffers;  // device-resident BFS state (trg_engine_bfs.inc)
 struct StitchBufs;  // scratch of the tile-boundary stitch (trg_engine_stitch.inc)
 struct Uploader;    // host cloud -> HBM staging (trg_engine_map.ipp)
-struct ExchangeState;  // RCCL communicator + buffers of the native stitch exchange (trg_engine_exchange.inc)
+struct ExchangeState;  // transport (RCCL communicator or in-process group) + buffers of the native stitch exchange (trg_engine_exchange.inc)
 struct FieldBufs;      // device buffers of the cost field (trg_engine_field.ipp)
 
 }  // namespace
@@ -627,6 +627,8 @@ struct TrgEngine {
   int resolve_tickets = 0;       // 1: every resolve launch takes its workgroup indices from start tickets (default: only
                                  // the repeat of a launch whose bounded wait ran out)
   float gate_margin = 1e-4f;     // band in which the slope gate is left to the host's libm
+  int debug_stitch_cap = 0;      // test hook: first row capacity of the exchange's record and edge buffers (0: the default)
+  double comm_wait_seconds = 20.0;  // in-process exchange transport: the longest wait for the other ranks (a cap)
   std::unique_ptr<BfsBuffers> bfs;
   std::string bfs_fallback_reason;
   // map points inside the queries of the level kernels of the last device build (instrumentation;
@@ -1159,6 +1161,8 @@ TrgStatus set_option(TrgEngine *e, const char *key, const char *value) {
       {"debug_fallback_level", INT, &e->debug_fallback_level},
       {"debug_call_stride", BOOL, &e->debug_call_stride},
       {"debug_wait_rerun", BOOL, &e->debug_wait_rerun},
+      {"debug_stitch_cap", INT, &e->debug_stitch_cap},
+      {"comm_wait_seconds", POSITIVE_DOUBLE, &e->comm_wait_seconds},
   };
   const std::string k(key), v(value);
   for (const auto &o : options) {

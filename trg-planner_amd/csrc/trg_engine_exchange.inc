@@ -9,9 +9,16 @@
 //
 // librccl is resolved at run time (dlopen): the engine has no link-time dependency on it, and a process
 // that already loaded an RCCL (torch's) shares that instance when the soname matches.
+//
+// The all-gathers go through a Transport.  RCCL is the one a product uses.  The in-process transport
+// (trg_engine_comm_join_local, never chosen unless asked for) lets R engines on one device in one process,
+// each entered from its own thread, run the exchange's own logic -- counts, padded slots, the tail row,
+// compaction, buffer reuse, the failure announcement -- where RCCL refuses two ranks on one device.
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
+
+#include "local_group.h"
 
 namespace {
 
@@ -55,22 +62,71 @@ struct RcclApi {
 };
 RcclApi g_rccl;
 
-struct ExchangeState {
-  ncclComm_t comm = nullptr;
-  bool owned = false;  // created by trg_engine_comm_init (destroyed with the engine)
-  int nranks = 0, rank = 0;
-  DevArr rec, edges, send, recv, all, cnt;
-  Pinned<long long> h_cnt;  // nranks + 1 words
-  ~ExchangeState() {  // (the buffers free themselves, after this)
-    if (comm && owned && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(comm);
-  }
-};
-
 #define RCCLCHK(e, call)                                                                            \
   do {                                                                                              \
     const ncclResult_t r_ = (call);                                                                 \
     if (r_ != ncclSuccess) return (e)->fail(TRG_ERR_DEVICE, std::string(#call ": ") + g_rccl.GetErrorString(r_)); \
   } while (0)
+
+// what carries the exchange's two all-gathers: every rank gives `count` elements of `elem_bytes` (8: the
+// counts, 1: the padded payload) and receives the ranks' blocks in rank order
+struct Transport {
+  virtual ~Transport() = default;
+  virtual TrgStatus all_gather(TrgEngine *e, const void *d_send, void *d_recv, size_t count, size_t elem_bytes,
+                               hipStream_t s) = 0;
+};
+
+struct RcclTransport : Transport {
+  ncclComm_t comm = nullptr;
+  bool owned = false;  // created by trg_engine_comm_init (destroyed with the engine)
+  ~RcclTransport() override {
+    if (comm && owned && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(comm);
+  }
+  TrgStatus all_gather(TrgEngine *e, const void *d_send, void *d_recv, size_t count, size_t elem_bytes,
+                       hipStream_t s) override {
+    RCCLCHK(e, g_rccl.AllGather(d_send, d_recv, count, elem_bytes == 8 ? ncclInt64 : ncclChar, comm, s));
+    return TRG_OK;
+  }
+};
+
+// The in-process transport: the group's host side (barriers bounded by the engine's comm_wait_seconds, the send
+// pointers) is local_group.h; the all-gather is device-to-device copies on the own stream between two barriers.
+// Nothing waits on the device.
+struct LocalTransport : Transport {
+  std::shared_ptr<LocalGroup> group;
+  int rank = 0;
+  const double *wait_seconds = nullptr;  // the engine's option, read at every wait
+  ~LocalTransport() override {
+    if (group) group->leave(rank);
+  }
+  TrgStatus barrier(TrgEngine *e) {
+    const std::string why = group->barrier(rank, *wait_seconds);
+    return why.empty() ? TRG_OK : e->fail(TRG_ERR_DEVICE, "local exchange: " + why);
+  }
+  TrgStatus all_gather(TrgEngine *e, const void *d_send, void *d_recv, size_t count, size_t elem_bytes,
+                       hipStream_t s) override {
+    const size_t bytes = count * elem_bytes;
+    HIPCHK(e, hipStreamSynchronize(s));  // what the peers will read is written
+    group->show(rank, d_send);
+    TrgStatus st = barrier(e);
+    if (st != TRG_OK) return st;
+    const std::vector<const void *> from = group->shown();
+    hipError_t he = hipSuccess;
+    for (int k = 0; k < group->nranks() && he == hipSuccess; ++k)
+      he = hipMemcpyAsync((char *)d_recv + (size_t)k * bytes, from[k], bytes, hipMemcpyDeviceToDevice, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    st = barrier(e);  // (entered on every path: the peers' send buffers are theirs again after it)
+    if (he != hipSuccess) return e->fail(TRG_ERR_DEVICE, std::string("local exchange copy: ") + hipGetErrorString(he));
+    return st;
+  }
+};
+
+struct ExchangeState {
+  std::unique_ptr<Transport> transport;
+  int nranks = 0, rank = 0;
+  DevArr rec, edges, send, recv, all, cnt;
+  Pinned<long long> h_cnt;  // nranks + 1 words
+};
 
 // all-gather-v of `n` records of `rec_bytes` each, on the device: out = the ranks' records in rank order,
 // counts[k] = rank k's number (n < 0 announces "this rank failed": every rank then returns an error
@@ -85,7 +141,7 @@ TrgStatus exchange_allgatherv(TrgEngine *e, ExchangeState &x, const void *d_mine
   HIPCHK(e, x.h_cnt.ensure(STITCH_MAX_TILES + 1));
   x.h_cnt[R] = n;
   HIPCHK(e, hipMemcpyAsync(d_cnt + R, x.h_cnt + R, sizeof(long long), hipMemcpyHostToDevice, s));
-  RCCLCHK(e, g_rccl.AllGather(d_cnt + R, d_cnt, 1, ncclInt64, x.comm, s));
+  if ((st = x.transport->all_gather(e, d_cnt + R, d_cnt, 1, sizeof(long long), s)) != TRG_OK) return st;
   HIPCHK(e, hipMemcpyAsync(x.h_cnt, d_cnt, (size_t)R * sizeof(long long), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   counts.assign(x.h_cnt.p, x.h_cnt.p + R);
@@ -101,7 +157,7 @@ TrgStatus exchange_allgatherv(TrgEngine *e, ExchangeState &x, const void *d_mine
   if ((st = ensure_bytes(e, x.all, (size_t)std::max<long long>(total, 1) * rec_bytes)) != TRG_OK) return st;
   HIPCHK(e, hipMemsetAsync(x.send.p, 0, slot, s));
   if (n > 0) HIPCHK(e, hipMemcpyAsync(x.send.p, d_mine, (size_t)n * rec_bytes, hipMemcpyDeviceToDevice, s));
-  RCCLCHK(e, g_rccl.AllGather(x.send.p, x.recv.p, slot, ncclChar, x.comm, s));
+  if ((st = x.transport->all_gather(e, x.send.p, x.recv.p, slot, 1, s)) != TRG_OK) return st;
   size_t off = 0;
   for (int k = 0; k < R; ++k) {
     const size_t nb = (size_t)counts[k] * rec_bytes;
@@ -127,12 +183,13 @@ TrgStatus comm_init(TrgEngine *e, const uint8_t id[TRG_COMM_ID_BYTES], int32_t n
   if (!g_rccl.load()) return e->fail(TRG_ERR_DEVICE, g_rccl.err);
   if (!e->exchange) e->exchange.reset(new ExchangeState());
   ExchangeState &x = *e->exchange;
-  if (x.comm && x.owned) (void)g_rccl.CommDestroy(x.comm);
-  x.comm = nullptr;
+  x.transport.reset();
   ncclUniqueId u;
   memcpy(u.internal, id, TRG_COMM_ID_BYTES);
-  RCCLCHK(e, g_rccl.CommInitRank(&x.comm, nranks, u, rank));
-  x.owned = true;
+  std::unique_ptr<RcclTransport> t(new RcclTransport());
+  RCCLCHK(e, g_rccl.CommInitRank(&t->comm, nranks, u, rank));
+  t->owned = true;
+  x.transport = std::move(t);
   x.nranks = nranks;
   x.rank = rank;
   return TRG_OK;
@@ -145,15 +202,35 @@ TrgStatus comm_adopt(TrgEngine *e, void *nccl_comm) {
   if (!g_rccl.load()) return e->fail(TRG_ERR_DEVICE, g_rccl.err);
   if (!e->exchange) e->exchange.reset(new ExchangeState());
   ExchangeState &x = *e->exchange;
-  if (x.comm && x.owned) (void)g_rccl.CommDestroy(x.comm);
-  x.comm = nullptr;
-  x.owned = false;
+  x.transport.reset();
   const ncclComm_t comm = (ncclComm_t)nccl_comm;
   int nranks = 0, rank = 0;
   RCCLCHK(e, g_rccl.CommCount(comm, &nranks));
   RCCLCHK(e, g_rccl.CommUserRank(comm, &rank));
   if (nranks > STITCH_MAX_TILES) return e->fail(TRG_ERR_INVALID_ARG, "comm_adopt: too many ranks");
-  x.comm = comm;
+  std::unique_ptr<RcclTransport> t(new RcclTransport());
+  t->comm = comm;
+  x.transport = std::move(t);
+  x.nranks = nranks;
+  x.rank = rank;
+  return TRG_OK;
+}
+
+// Rank `rank` of the in-process group `name` (made by whoever joins first; gone with its last member).  Joining does
+// not wait for the others: the first all-gather does.
+TrgStatus comm_join_local(TrgEngine *e, const char *name, int32_t nranks, int32_t rank) {
+  if (nranks < 1 || nranks > STITCH_MAX_TILES || rank < 0 || rank >= nranks)
+    return e->fail(TRG_ERR_INVALID_ARG, "comm_join_local: bad arguments");
+  if (!e->exchange) e->exchange.reset(new ExchangeState());
+  ExchangeState &x = *e->exchange;
+  x.transport.reset();  // (leaves the group it was in)
+  std::unique_ptr<LocalTransport> t(new LocalTransport());
+  std::string why;
+  t->group = LocalGroup::join(name, nranks, rank, why);
+  if (!t->group) return e->fail(TRG_ERR_INVALID_ARG, "comm_join_local: " + why);
+  t->rank = rank;
+  t->wait_seconds = &e->comm_wait_seconds;
+  x.transport = std::move(t);
   x.nranks = nranks;
   x.rank = rank;
   return TRG_OK;
@@ -167,7 +244,7 @@ TrgStatus comm_destroy(TrgEngine *e) {
 
 TrgStatus stitch_exchange(TrgEngine *e, const float core_xyxy[4], int32_t cols, int32_t rows, int32_t *n_boundary,
                           int32_t *n_cross) {
-  if (!e->exchange || !e->exchange->comm) return e->fail(TRG_ERR_INVALID_ARG, "stitch_exchange: no communicator (trg_engine_comm_init)");
+  if (!e->exchange || !e->exchange->transport) return e->fail(TRG_ERR_INVALID_ARG, "stitch_exchange: no communicator (trg_engine_comm_init)");
   ExchangeState &x = *e->exchange;
   const int R = x.nranks, tile = x.rank;
   if (!core_xyxy || cols < 1 || rows < 1 || cols * rows != R)
@@ -177,22 +254,28 @@ TrgStatus stitch_exchange(TrgEngine *e, const float core_xyxy[4], int32_t cols, 
   std::string deferred_msg;
   // ---- 1: this tile's boundary records; the tile's node count rides behind them ---------------------------
   int32_t nb = 0;
-  if ((st = ensure_bytes(e, x.rec, (size_t)(1 << 14) * sizeof(TrgBoundaryRec))) != TRG_OK) return st;
+  // (debug_stitch_cap: the first capacity in rows of rec and edges, so that tests reach the regrow loops)
+  const size_t rec_rows = e->debug_stitch_cap > 0 ? (size_t)e->debug_stitch_cap + 1 : (size_t)1 << 14;
+  const size_t edge_rows = e->debug_stitch_cap > 0 ? (size_t)e->debug_stitch_cap : (size_t)1 << 15;
+  if ((st = ensure_bytes(e, x.rec, rec_rows * sizeof(TrgBoundaryRec))) != TRG_OK) return st;
   for (;;) {
     const int32_t cap = (int32_t)(x.rec.bytes / sizeof(TrgBoundaryRec)) - 1;
     st = stitch_boundary(e, core_xyxy, cols, rows, tile, (TrgBoundaryRec *)x.rec.p, cap, &nb);
     if (st != TRG_ERR_CAPACITY) break;
+    ++e->stats.stitch_regrows;
     if ((st = ensure_bytes(e, x.rec, (size_t)(2 * nb + 2) * sizeof(TrgBoundaryRec))) != TRG_OK) break;
   }
   int32_t V = 0, E_ = 0;
   if (st == TRG_OK) st = graph_sizes(e, TRG_KIND_GLOBAL, &V, &E_);
+  if (st == TRG_OK) {
+    const TrgBoundaryRec tail = {V, 0.0f, 0.0f, 0.0f};
+    hipError_t he = hipMemcpyAsync((TrgBoundaryRec *)x.rec.p + nb, &tail, sizeof(tail), hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);  // (tail is a stack object)
+    if (he != hipSuccess) st = e->fail(TRG_ERR_DEVICE, std::string("stitch exchange tail row: ") + hipGetErrorString(he));
+  }
   if (st != TRG_OK) {  // tell the others instead of leaving them in the collective
     deferred = st;
     deferred_msg = e->err;
-  } else {
-    const TrgBoundaryRec tail = {V, 0.0f, 0.0f, 0.0f};
-    HIPCHK(e, hipMemcpyAsync((TrgBoundaryRec *)x.rec.p + nb, &tail, sizeof(tail), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipStreamSynchronize(s));  // (tail is a stack object)
   }
   std::vector<long long> counts;
   void *d_all = nullptr;
@@ -227,11 +310,12 @@ TrgStatus stitch_exchange(TrgEngine *e, const float core_xyxy[4], int32_t cols, 
   const TrgBoundaryRec *d_recs = (const TrgBoundaryRec *)x.recv.p;  // (recv is free again: the payload was copied out)
   // ---- 2: the cross edges this tile owns ------------------------------------------------------------------------
   int32_t nc = 0;
-  if ((st = ensure_bytes(e, x.edges, (size_t)(1 << 15) * sizeof(TrgCrossEdge))) != TRG_OK) return st;
+  if ((st = ensure_bytes(e, x.edges, edge_rows * sizeof(TrgCrossEdge))) != TRG_OK) return st;
   for (;;) {
     const int32_t cap = (int32_t)(x.edges.bytes / sizeof(TrgCrossEdge));
     st = stitch_cross(e, tile, R, d_recs, rec_off.data(), (TrgCrossEdge *)x.edges.p, cap, &nc);
     if (st != TRG_ERR_CAPACITY) break;
+    ++e->stats.stitch_regrows;
     if ((st = ensure_bytes(e, x.edges, (size_t)(2 * nc + 2) * sizeof(TrgCrossEdge))) != TRG_OK) break;
   }
   if (st != TRG_OK) {
@@ -269,6 +353,11 @@ TrgStatus trg_engine_comm_init(TrgEngine *e, const uint8_t id[TRG_COMM_ID_BYTES]
 
 TrgStatus trg_engine_comm_adopt(TrgEngine *e, void *nccl_comm) {
   return entry(e, "comm_adopt", DEVICE, [&] { return comm_adopt(e, nccl_comm); });
+}
+
+TrgStatus trg_engine_comm_join_local(TrgEngine *e, const char *group_name, int32_t nranks, int32_t rank) {
+  if (!group_name) return TRG_ERR_INVALID_ARG;
+  return entry(e, "comm_join_local", DEVICE, [&] { return comm_join_local(e, group_name, nranks, rank); });
 }
 
 TrgStatus trg_engine_comm_destroy(TrgEngine *e) {

@@ -166,6 +166,7 @@ TrgStatus stitch_cross(TrgEngine *e, int32_t tile, int32_t ntiles, const TrgBoun
       break;
     }
     // slope gates the device could not call: the reference's own libm decides (trg.cpp:269-274)
+    ++e->stats.stitch_gate_retries;
     std::vector<int> hs(np_);
     std::vector<float> hd(np_), h1(3 * np_), h2(3 * np_);
     HIPCHK(e, hipMemcpy(hs.data(), sb.status.p, np_ * 4, hipMemcpyDeviceToHost));
@@ -218,9 +219,11 @@ TrgStatus stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles, const int3
   HIPCHK(e, hipMemcpyAsync(&En, (int *)sb.rowptr_new.p + g.V, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipMemcpyAsync(&n_bad, (int *)sb.extra.p + g.V, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
-  if (n_bad)
+  if (n_bad) {
+    out.clear();  // (no rows at all: a view of V nodes without their V + 1 row pointers must not be exported)
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_assemble: " + std::to_string(n_bad) +
                                             " cross edges name a tile or a node outside node_offsets");
+  }
   if ((st = ensure_bytes(e, sb.col_new, (size_t)En * 4 + 16)) != TRG_OK) return st;
   if ((st = ensure_bytes(e, sb.w_new, (size_t)En * 4 + 16)) != TRG_OK) return st;
   if ((st = ensure_bytes(e, sb.dist_new, (size_t)En * 4 + 16)) != TRG_OK) return st;

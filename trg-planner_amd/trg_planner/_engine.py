@@ -91,7 +91,8 @@ class TrgStats(C.Structure):
         ("map_nn_resolved", C.c_uint64), ("map_nn_unresolved", C.c_uint64),
         ("bfs_tie_fixups", C.c_uint64), ("bytes_spec_created", C.c_uint64),
         ("ms_rare_events", C.c_double), ("bfs_ticket_reruns", C.c_uint64),
-        ("bfs_multipass_rows", C.c_uint64), ("ms_upload", C.c_double), ("presampled_nodes", C.c_uint64)]
+        ("bfs_multipass_rows", C.c_uint64), ("ms_upload", C.c_double), ("presampled_nodes", C.c_uint64),
+        ("stitch_gate_retries", C.c_uint64), ("stitch_regrows", C.c_uint64)]
 
 
 # every symbol include/trg_engine.h declares (tests check that the library exports all of them)
@@ -109,6 +110,7 @@ EXPORTS = [
     "trg_engine_stitch_boundary", "trg_engine_stitch_cross", "trg_engine_stitch_assemble",
     "trg_engine_graph_sizes",
     "trg_engine_comm_unique_id", "trg_engine_comm_init", "trg_engine_comm_adopt", "trg_engine_comm_destroy",
+    "trg_engine_comm_join_local",
     "trg_engine_stitch_exchange", "trg_engine_cost_field", "trg_engine_cost_field_batch",
     "trg_engine_field_routes", "trg_engine_cost_field_bounded", "trg_engine_field_reached",
     "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh", "trg_engine_cost_field_models",
@@ -197,6 +199,7 @@ def load_library():
     L.trg_engine_comm_init.argtypes = [vp, u8p, C.c_int32, C.c_int32]
     L.trg_engine_comm_adopt.argtypes = [vp, vp]
     L.trg_engine_comm_destroy.argtypes = [vp]
+    L.trg_engine_comm_join_local.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32]
     L.trg_engine_stitch_exchange.argtypes = [vp, fp, C.c_int32, C.c_int32, ip, ip]
     L.trg_engine_set_option.argtypes = [vp, C.c_char_p, C.c_char_p]
     L.trg_engine_cost_field.argtypes = [vp, C.c_int32, fp, fp, ip, ip, C.POINTER(TrgFieldInfo)]
@@ -342,6 +345,12 @@ class Engine:
     def comm_init(self, unique_id, nranks, rank):
         buf = (C.c_uint8 * 128).from_buffer_copy(bytes(unique_id))
         self._chk(self.L.trg_engine_comm_init(self.h, buf, nranks, rank))
+        self._comm_ranks = nranks
+
+    def comm_join_local(self, group_name, nranks, rank):
+        """Rank `rank` of an in-process group of engines on one device, one thread per engine (tests of the exchange
+        with more than one rank; RCCL refuses two ranks on one device)."""
+        self._chk(self.L.trg_engine_comm_join_local(self.h, str(group_name).encode(), nranks, rank))
         self._comm_ranks = nranks
 
     def comm_destroy(self):
