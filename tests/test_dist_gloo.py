@@ -119,3 +119,64 @@ def test_two_rank_allgatherv_and_stitch():
     assert all(t[0] == 0 and t[2] == 1 for t in r0[3])  # owned by the lower tile
     assert all(dd < 0.6 for dd in r0[4])
     assert r0[5] == r1[5] and r0[5] > 0
+
+
+AUX_ROWS = (3, 0, 5)  # rows of each rank: ragged, one rank with none
+
+
+def _aux_rows(rank):
+    n = AUX_ROWS[rank]
+    return (np.arange(n * 4, dtype=np.int32).reshape(n, 4) + 1000 * rank)
+
+
+def _aux_worker(rank, world, port, q):
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "trg-planner_amd"))
+    from trg_planner import tiled
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    t = torch.from_numpy(_aux_rows(rank))
+    cat, counts, auxs = tiled.allgatherv_aux_t(t, (1 << 40) + 7 * rank, dist)  # (a word wider than 32 bits)
+    cat2, counts2 = tiled.allgatherv_t(t, dist)
+    q.put((rank, cat.numpy().tolist(), counts, auxs, cat2.numpy().tolist(), counts2, str(cat.dtype), tuple(cat.shape)))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_three_rank_allgatherv_with_a_word_per_rank():
+    """allgatherv_aux_t: the ranks' rows, counts and integers come back in rank order on every rank, through ragged
+    counts and a rank with no rows; allgatherv_t is the same gather without the integers."""
+    world = len(AUX_ROWS)
+    port = _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_aux_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    out = sorted(q.get(timeout=120) for _ in range(world))
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    want = np.concatenate([_aux_rows(r) for r in range(world)], 0).tolist()
+    for rank, cat, counts, auxs, cat2, counts2, dtype, shape in out:
+        assert cat == want and counts == list(AUX_ROWS), rank
+        assert auxs == [(1 << 40) + 7 * r for r in range(world)], rank
+        assert all(type(c) is int for c in counts + auxs + counts2)
+        assert cat2 == want and counts2 == list(AUX_ROWS), rank
+        assert dtype == "torch.int32" and shape == (sum(AUX_ROWS), 4)
+
+
+def test_allgatherv_without_a_process_group():
+    """No process group: the tensor itself, its count and its integer; allgatherv_t as before."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "trg-planner_amd"))
+    from trg_planner import tiled
+    t = torch.from_numpy(_aux_rows(2))
+    for d in (None, dist):  # (dist is not initialised here)
+        cat, counts, auxs = tiled.allgatherv_aux_t(t, 41, d)
+        assert cat is t and counts == [5] and auxs == [41]
+        cat, counts = tiled.allgatherv_t(t, d)
+        assert cat is t and counts == [5]

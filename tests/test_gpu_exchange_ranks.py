@@ -1,6 +1,6 @@
-"""GPU: trg_engine_stitch_exchange's own logic with 2, 3, 4 and 9 ranks -- per-rank counts and padded slots, the tail
-row with the node count, rec_off / node_off, the compaction, the second exchange on the first one's buffers, the
-failure announcement -- over the in-process transport (trg_engine_comm_join_local): one process, one engine and one
+"""GPU: trg_engine_stitch_exchange's own logic with 2, 3, 4 and 9 ranks -- per-rank counts and padded slots, the
+node count in the count exchange, rec_off / node_off, the second exchange on the first one's buffers, the failure
+announcement -- over the in-process transport (trg_engine_comm_join_local): one process, one engine and one
 thread per rank, all on one device.  The kernels and their inputs are those of tiled.stitch_emulated, only the data
 movement differs, so every rank's rows must equal the emulated ones bit for bit, weights included; through
 test_gpu_stitch_steps.py those equal the tiled oracle's.  RCCL itself with more than one rank is not run here (it

@@ -458,6 +458,14 @@ struct Uploader;    // host cloud -> HBM staging (trg_engine_map.ipp)
 struct ExchangeState;  // transport (RCCL communicator or in-process group) + buffers of the native stitch exchange (trg_engine_exchange.inc)
 struct FieldBufs;      // device buffers of the cost field (trg_engine_field.ipp)
 
+// the engine's own copy of the cleaned global graph in HBM, for when the device build's is not current
+// (ensure_dev_graph): its two parts, and the sizes they were copied at
+struct DevGraphUpload {
+  DevArr xyz, state;             // VIEW_UP_NODES
+  DevArr rowptr, col, w, dist;   // VIEW_UP_EDGES
+  long long nodes_of = -1, edges_of = -1;  // V, and V << 32 | E
+};
+
 }  // namespace
 
 struct TrgEngine;
@@ -542,10 +550,12 @@ struct TrgEngine {
   //   VIEW_KDO         kdo_x / kdo_y / kdo_index    ensure_kd_order_arrays                       plan, cost field: order questions
   //   VIEW_CSR         csr_global                   every build, update, load; ensure_csr_global plan, cost field, graph("global"), stitch
   //   VIEW_DEV_CSR     the cleaned CSR in HBM       device build; update drops it (dev_csr)      cost field, stitch: spares an upload
+  //   VIEW_UP_NODES    dev_up: xyz, state           ensure_dev_graph, when no VIEW_DEV_CSR       cost field, stitch
+  //   VIEW_UP_EDGES    dev_up: rowptr, col, w, dist ensure_dev_graph, when no VIEW_DEV_CSR       cost field, stitch_assemble
   //   VIEW_STITCH_DEV  csr_stitched's edges in HBM  stitch_assemble; stitch_fetch un-stamps      graph("stitched")
-  // (the cost field's uploaded CSR and edge costs carry their own stamps in FieldBufs)
-  enum GraphView { VIEW_POOL, VIEW_GRID, VIEW_KD_ORDER, VIEW_KD, VIEW_KDO, VIEW_CSR, VIEW_DEV_CSR, VIEW_STITCH_DEV,
-                   VIEW_COUNT };
+  // (the cost field's edge costs carry their own stamp in FieldBufs)
+  enum GraphView { VIEW_POOL, VIEW_GRID, VIEW_KD_ORDER, VIEW_KD, VIEW_KDO, VIEW_CSR, VIEW_DEV_CSR, VIEW_UP_NODES,
+                   VIEW_UP_EDGES, VIEW_STITCH_DEV, VIEW_COUNT };
   uint64_t graph_version = 1;            // bumped by graph_changed() alone
   uint64_t view_stamp[VIEW_COUNT] = {};  // graph_version each view is current for (0: none)
   bool current(GraphView v) const { return view_stamp[v] == graph_version; }
@@ -569,6 +579,7 @@ struct TrgEngine {
   std::vector<float> kdo_x, kdo_y;   // positions in the node tree's insertion order, for the planner's rare order
   std::vector<int> kdo_index;        // questions (nearest-node ties, several goal hits): node id -> position
   Csr csr_global;
+  DevGraphUpload dev_up;   // csr_global and nstate in HBM (VIEW_UP_NODES, VIEW_UP_EDGES)
   Csr csr_stitched;        // tiled builds: this tile's rows of the stitched global graph
   int stitched_edges = 0;  // ... and their edge count (the edge arrays may still be in HBM only)
   float root_pos[2] = {0, 0};
@@ -608,7 +619,7 @@ struct TrgEngine {
                                        // of its copy threads, made on the first cloud that needs them
   std::unique_ptr<ExchangeState> exchange;  // tiled builds: RCCL communicator and buffers of the native stitch
                                             // exchange, made by trg_engine_comm_init / comm_adopt
-  std::unique_ptr<FieldBufs> field;  // cost field: work arrays, edge costs and uploaded CSR (cached per graph_version)
+  std::unique_ptr<FieldBufs> field;  // cost field: work arrays and edge costs (cached per graph_version)
   double field_delta_scale = 4.0;  // cost field: bucket width in mean edge costs (a measurement knob, see set_option)
   // The node map of trg_engine_cost_field_refresh: for every node of the current graph its id in the graph of the
   // retained cost-field solve, -1 for a node made since.  A solve starts it as the identity, update_graph composes
@@ -936,10 +947,78 @@ bool ensure_csr_global(TrgEngine *e) {
   e->view_stamp[TrgEngine::VIEW_CSR] = e->graph_version;
   return true;
 }
-// the cleaned CSR of the last device build while it is the current graph's (else the consumers upload csr_global)
+// the cleaned CSR of the last device build while it is the current graph's
 const BfsBuffers *dev_csr(const TrgEngine *e) {
   const BfsBuffers *bb = e->bfs.get();
   return e->current(TrgEngine::VIEW_DEV_CSR) && bb && bb->xyz2.p && bb->rowptr_new.p ? bb : nullptr;
+}
+
+// The cleaned global graph of this engine on the device, for the cost field and the stitch: the device build's
+// arrays in place while they are the current graph's, else the engine's upload of csr_global and nstate.
+struct DevGraph {
+  const int *rowptr = nullptr, *col = nullptr;
+  const float *w = nullptr, *dist = nullptr;
+  const int *state = nullptr;
+  const float *xyz = nullptr;
+  int V = 0, E = 0;
+  bool dev_build = false;
+};
+enum { DEV_NODES = 1, DEV_EDGES = 2 };
+
+// `need`: the parts (DEV_NODES | DEV_EDGES) the caller will read.  A part of the upload is copied when it is asked for
+// and is not of this graph_version (the size test is ensure_csr_global's: an update_graph that failed midway).  One
+// that is current is neither copied nor regrown, so what was handed out stays good for as long as the version does.
+// need == 0 copies nothing and hands out what is current, null for the rest: "are these still the graph's arrays".
+TrgStatus ensure_dev_graph(TrgEngine *e, int need, DevGraph *g) {
+  *g = DevGraph{};
+  if (need) (void)ensure_csr_global(e);  // (false: neither the CSR nor the pool is current, the old rows stay in place)
+  const Csr &c = e->csr_global;
+  const int V = g->V = (int)c.state.size(), E = g->E = (int)c.col.size();
+  if (const BfsBuffers *bb = dev_csr(e)) {
+    *g = {bb->rowptr_new.as<int>(), bb->col2.as<int>(), bb->w2.as<float>(), bb->dist2.as<float>(),
+          bb->state2.as<int>(), bb->xyz2.as<float>(), V, E, true};
+    return TRG_OK;
+  }
+  DevGraphUpload &up = e->dev_up;
+  struct Copy { DevArr &a; const void *src; size_t bytes; };
+  // one part: current, or copied now when `need` names it (stale and not asked for: left alone, *current false)
+  const auto part = [&](TrgEngine::GraphView view, int flag, long long &have, long long want,
+                        std::initializer_list<Copy> copies, bool *current) -> TrgStatus {
+    *current = e->view_stamp[view] == e->graph_version && have == want;
+    if (*current || !(need & flag)) return TRG_OK;
+    e->view_stamp[view] = 0;
+    for (const Copy &k : copies)
+      if (const TrgStatus st = ensure_bytes(e, k.a, k.bytes + 16); st != TRG_OK) return st;
+    for (const Copy &k : copies)
+      if (k.bytes) HIPCHK(e, hipMemcpyAsync(k.a.p, k.src, k.bytes, hipMemcpyHostToDevice, e->s_main));
+    have = want;
+    e->view_stamp[view] = e->graph_version;
+    *current = true;
+    return TRG_OK;
+  };
+  static const int no_rows[1] = {0};  // the row pointers of the empty graph
+  const size_t nv = (size_t)V, ne = (size_t)E;
+  bool nodes = false, edges = false;
+  TrgStatus st = part(TrgEngine::VIEW_UP_NODES, DEV_NODES, up.nodes_of, V,
+                      {{up.xyz, c.xyz.data(), nv * 12}, {up.state, e->nstate.data(), std::min(nv, e->nstate.size()) * 4}},
+                      &nodes);
+  if (st == TRG_OK)
+    st = part(TrgEngine::VIEW_UP_EDGES, DEV_EDGES, up.edges_of, (long long)V << 32 | E,
+              {{up.rowptr, c.rowptr.empty() ? no_rows : c.rowptr.data(), (nv + 1) * 4},
+               {up.col, c.col.data(), ne * 4}, {up.w, c.w.data(), ne * 4}, {up.dist, c.dist.data(), ne * 4}},
+              &edges);
+  if (st != TRG_OK) return st;
+  if (nodes) {
+    g->xyz = up.xyz.as<float>();
+    g->state = up.state.as<int>();
+  }
+  if (edges) {
+    g->rowptr = up.rowptr.as<int>();
+    g->col = up.col.as<int>();
+    g->w = up.w.as<float>();
+    g->dist = up.dist.as<float>();
+  }
+  return TRG_OK;
 }
 }  // namespace
 
@@ -980,7 +1059,6 @@ TrgStatus create_engine(const TrgParams *params, int device, TrgEngine **out) {
   // step 3 of expandGraph is compiled in or out by this fp comparison (trg.cpp:429)
   e->step3 = (e->prm.expand_dist - e->prm.robot_size) < 0.25 * e->prm.expand_dist;
   e->bfs.reset(new BfsBuffers());
-  e->stitch.reset(new StitchBufs());
   e->uploader.reset(new Uploader());
   e->device_ok = true;
   if (const char *env = getenv("TRG_REPLAY")) e->use_device_bfs = std::string(env) != "host";

@@ -9,14 +9,6 @@
 
 namespace {
 
-// scratch of the tile-boundary stitch (trg_engine_stitch.inc)
-struct StitchBufs {
-  DevArr flag, off, cnt, pair_a, pair_b, p1, p2, mid, status, npts, weight, dist, n_unc;
-  DevArr extra, deg, rowptr_new, fill, col_new, w_new, dist_new;
-  DevArr up_xyz, up_rowptr, up_col, up_w, up_dist;  // uploads when the device copy of the graph is stale
-  DevArr scan_tmp;
-};
-
 // Everything the expansion (k_level_sample + k_level_spec) writes exists twice (level parity): the next level is expanded while the
 // host still looks at the counters of this one, and a level whose second half has to be redone must
 // find its first half untouched.

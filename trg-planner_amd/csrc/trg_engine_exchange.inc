@@ -1,8 +1,9 @@
 // trg_engine_exchange.inc -- the tile-boundary stitch with its two exchanges done natively over RCCL
 // (included by trg_engine.cpp).  One call runs DESIGN.md section 7 for this rank's tile: boundary records
 // -> all-gather-v -> cross edges -> all-gather-v -> this tile's rows of the global graph.  RCCL has no
-// all-gather-v: each exchange is an all-gather of one count per rank (the only host round trip), then an
-// all-gather of payloads padded to the largest count, compacted on the device.  xGMI is point-to-point
+// all-gather-v: each exchange is an all-gather of one count and one auxiliary word per rank (the only host round
+// trip; the first exchange's word is the tile's node count), then an all-gather of payloads padded to the largest
+// count, compacted on the device.  xGMI is point-to-point
 // and these payloads are a few 10 KB, so latency decides: two small collectives per exchange, nothing
 // bucketed.  A C / C++ consumer (the ROS nodes inherit TRGPlanner) needs no Python for N > 1;
 // trg_planner/tiled.py::stitch_device calls the same entry point through ctypes.
@@ -12,7 +13,7 @@
 //
 // The all-gathers go through a Transport.  RCCL is the one a product uses.  The in-process transport
 // (trg_engine_comm_join_local, never chosen unless asked for) lets R engines on one device in one process,
-// each entered from its own thread, run the exchange's own logic -- counts, padded slots, the tail row,
+// each entered from its own thread, run the exchange's own logic -- counts and node counts, padded slots,
 // compaction, buffer reuse, the failure announcement -- where RCCL refuses two ranks on one device.
 
 #include <dlfcn.h>
@@ -69,7 +70,7 @@ RcclApi g_rccl;
   } while (0)
 
 // what carries the exchange's two all-gathers: every rank gives `count` elements of `elem_bytes` (8: the
-// counts, 1: the padded payload) and receives the ranks' blocks in rank order
+// count and the word, 1: the padded payload) and receives the ranks' blocks in rank order
 struct Transport {
   virtual ~Transport() = default;
   virtual TrgStatus all_gather(TrgEngine *e, const void *d_send, void *d_recv, size_t count, size_t elem_bytes,
@@ -125,47 +126,76 @@ struct ExchangeState {
   std::unique_ptr<Transport> transport;
   int nranks = 0, rank = 0;
   DevArr rec, edges, send, recv, all, cnt;
-  Pinned<long long> h_cnt;  // nranks + 1 words
+  Pinned<long long> h_cnt;  // 2 (nranks + 1) words
 };
 
-// all-gather-v of `n` records of `rec_bytes` each, on the device: out = the ranks' records in rank order,
-// counts[k] = rank k's number (n < 0 announces "this rank failed": every rank then returns an error
-// instead of waiting in the payload collective).  One host round trip (the counts).
-TrgStatus exchange_allgatherv(TrgEngine *e, ExchangeState &x, const void *d_mine, long long n, size_t rec_bytes,
-                              std::vector<long long> &counts, void **d_all_out) {
+// all-gather-v of `n` records of `rec_bytes` each, on the device, with one word `aux` per rank beside the count:
+// out = the ranks' records in rank order, counts[k] = rank k's number, words[k] = its word (n < 0 announces "this
+// rank failed": every rank then returns an error instead of waiting in the payload collective).  One host round
+// trip: the counts and the words travel together.  The only function that enters collectives.
+TrgStatus exchange_allgatherv(TrgEngine *e, ExchangeState &x, const void *d_mine, long long n, long long aux,
+                              size_t rec_bytes, std::vector<long long> &counts, std::vector<long long> &words,
+                              void **d_all_out) {
   hipStream_t s = e->s_main;
   TrgStatus st;
   const int R = x.nranks;
-  if ((st = ensure_bytes(e, x.cnt, (size_t)(R + 1) * sizeof(long long))) != TRG_OK) return st;
-  long long *d_cnt = (long long *)x.cnt.p;
-  HIPCHK(e, x.h_cnt.ensure(STITCH_MAX_TILES + 1));
-  x.h_cnt[R] = n;
-  HIPCHK(e, hipMemcpyAsync(d_cnt + R, x.h_cnt + R, sizeof(long long), hipMemcpyHostToDevice, s));
-  if ((st = x.transport->all_gather(e, d_cnt + R, d_cnt, 1, sizeof(long long), s)) != TRG_OK) return st;
-  HIPCHK(e, hipMemcpyAsync(x.h_cnt, d_cnt, (size_t)R * sizeof(long long), hipMemcpyDeviceToHost, s));
+  if ((st = ensure_bytes(e, x.cnt, (size_t)(R + 1) * 2 * sizeof(long long))) != TRG_OK) return st;
+  long long *d_cnt = x.cnt.as<long long>(), *d_own = d_cnt + 2 * R;
+  HIPCHK(e, x.h_cnt.ensure(2 * (STITCH_MAX_TILES + 1)));
+  long long *h_own = x.h_cnt + 2 * R;
+  h_own[0] = n;
+  h_own[1] = aux;
+  HIPCHK(e, hipMemcpyAsync(d_own, h_own, 2 * sizeof(long long), hipMemcpyHostToDevice, s));
+  if ((st = x.transport->all_gather(e, d_own, d_cnt, 2, sizeof(long long), s)) != TRG_OK) return st;
+  HIPCHK(e, hipMemcpyAsync(x.h_cnt, d_cnt, (size_t)R * 2 * sizeof(long long), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
-  counts.assign(x.h_cnt.p, x.h_cnt.p + R);
+  counts.resize(R);
+  words.resize(R);
   long long pad = 1, total = 0;
-  for (long long c : counts) {
-    if (c < 0) return e->fail(TRG_ERR_DEVICE, "stitch exchange: another rank reported a failure");
-    pad = std::max(pad, c);
-    total += c;
+  for (int k = 0; k < R; ++k) {
+    counts[k] = x.h_cnt[2 * k];
+    words[k] = x.h_cnt[2 * k + 1];
+    if (counts[k] < 0) return e->fail(TRG_ERR_DEVICE, "stitch exchange: another rank reported a failure");
+    pad = std::max(pad, counts[k]);
+    total += counts[k];
   }
   const size_t slot = (size_t)pad * rec_bytes;
-  if ((st = ensure_bytes(e, x.send, slot)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, x.recv, slot * (size_t)R)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, x.all, (size_t)std::max<long long>(total, 1) * rec_bytes)) != TRG_OK) return st;
+  if ((st = ensure_all(e, {{&x.send, slot}, {&x.recv, slot * (size_t)R},
+                           {&x.all, (size_t)std::max<long long>(total, 1) * rec_bytes}})) != TRG_OK)
+    return st;
   HIPCHK(e, hipMemsetAsync(x.send.p, 0, slot, s));
   if (n > 0) HIPCHK(e, hipMemcpyAsync(x.send.p, d_mine, (size_t)n * rec_bytes, hipMemcpyDeviceToDevice, s));
   if ((st = x.transport->all_gather(e, x.send.p, x.recv.p, slot, 1, s)) != TRG_OK) return st;
   size_t off = 0;
   for (int k = 0; k < R; ++k) {
     const size_t nb = (size_t)counts[k] * rec_bytes;
-    if (nb) HIPCHK(e, hipMemcpyAsync((char *)x.all.p + off, (char *)x.recv.p + (size_t)k * slot, nb, hipMemcpyDeviceToDevice, s));
+    if (nb) HIPCHK(e, hipMemcpyAsync(x.all.as<char>() + off, x.recv.as<char>() + (size_t)k * slot, nb, hipMemcpyDeviceToDevice, s));
     off += nb;
   }
   *d_all_out = x.all.p;
   return TRG_OK;
+}
+
+// One exchange of stitch_exchange after the step that made its payload: a failure of that step (`local`, its message
+// in e->err) is announced in the count exchange, so that no rank waits for this one, and then returned as it was.
+TrgStatus exchange_after(TrgEngine *e, ExchangeState &x, TrgStatus local, const void *d_mine, long long n, long long aux,
+                         size_t rec_bytes, std::vector<long long> &counts, std::vector<long long> &words,
+                         void **d_all_out) {
+  const std::string local_msg = e->err;
+  const TrgStatus st = exchange_allgatherv(e, x, d_mine, local == TRG_OK ? n : -1, aux, rec_bytes, counts, words, d_all_out);
+  return local == TRG_OK ? st : e->fail(local, local_msg);
+}
+
+// A step that writes up to `cap` rows into `buf` and reports in *n how many it has, run until they fit: a step that
+// ends with TRG_ERR_CAPACITY gets twice the rows it asked for (stats.stitch_regrows counts these).
+template <typename Step>
+TrgStatus stitch_grown(TrgEngine *e, DevArr &buf, size_t row_bytes, const int32_t *n, Step step) {
+  TrgStatus st;
+  while ((st = step((int32_t)(buf.bytes / row_bytes))) == TRG_ERR_CAPACITY) {
+    ++e->stats.stitch_regrows;
+    if ((st = ensure_bytes(e, buf, (size_t)(2 * *n + 2) * row_bytes)) != TRG_OK) break;
+  }
+  return st;
 }
 
 TrgStatus comm_unique_id(TrgEngine *e, uint8_t id[TRG_COMM_ID_BYTES]) {
@@ -177,43 +207,53 @@ TrgStatus comm_unique_id(TrgEngine *e, uint8_t id[TRG_COMM_ID_BYTES]) {
   return TRG_OK;
 }
 
-TrgStatus comm_init(TrgEngine *e, const uint8_t id[TRG_COMM_ID_BYTES], int32_t nranks, int32_t rank) {
-  if (!id || nranks < 1 || nranks > STITCH_MAX_TILES || rank < 0 || rank >= nranks)
-    return e->fail(TRG_ERR_INVALID_ARG, "comm_init: bad arguments");
-  if (!g_rccl.load()) return e->fail(TRG_ERR_DEVICE, g_rccl.err);
+// Installs the transport that `make` builds.  The one the engine had goes first (an owned communicator is destroyed, a
+// local one leaves its group), and when `make` refuses, none is kept: a later stitch_exchange finds no communicator
+// instead of indexing its count buffers with the size of one that was refused.
+template <typename Make>
+TrgStatus comm_install(TrgEngine *e, Make make) {
   if (!e->exchange) e->exchange.reset(new ExchangeState());
   ExchangeState &x = *e->exchange;
   x.transport.reset();
-  ncclUniqueId u;
-  memcpy(u.internal, id, TRG_COMM_ID_BYTES);
-  std::unique_ptr<RcclTransport> t(new RcclTransport());
-  RCCLCHK(e, g_rccl.CommInitRank(&t->comm, nranks, u, rank));
-  t->owned = true;
+  std::unique_ptr<Transport> t;
+  int nranks = 0, rank = 0;
+  const TrgStatus st = make(t, nranks, rank);
+  if (st != TRG_OK) return st;
   x.transport = std::move(t);
   x.nranks = nranks;
   x.rank = rank;
   return TRG_OK;
 }
 
-// A communicator the engine refuses is not kept: the one it had is gone (as after a comm_init that failed), and a
-// later stitch_exchange finds none instead of indexing its count buffers with the refused communicator's size.
+TrgStatus comm_init(TrgEngine *e, const uint8_t id[TRG_COMM_ID_BYTES], int32_t nranks, int32_t rank) {
+  if (!id || nranks < 1 || nranks > STITCH_MAX_TILES || rank < 0 || rank >= nranks)
+    return e->fail(TRG_ERR_INVALID_ARG, "comm_init: bad arguments");
+  if (!g_rccl.load()) return e->fail(TRG_ERR_DEVICE, g_rccl.err);
+  return comm_install(e, [&](std::unique_ptr<Transport> &out, int &n, int &r) {
+    ncclUniqueId u;
+    memcpy(u.internal, id, TRG_COMM_ID_BYTES);
+    std::unique_ptr<RcclTransport> t(new RcclTransport());
+    RCCLCHK(e, g_rccl.CommInitRank(&t->comm, nranks, u, rank));
+    t->owned = true;
+    out = std::move(t);
+    n = nranks;
+    r = rank;
+    return TRG_OK;
+  });
+}
+
 TrgStatus comm_adopt(TrgEngine *e, void *nccl_comm) {
   if (!nccl_comm) return e->fail(TRG_ERR_INVALID_ARG, "comm_adopt: null communicator");
   if (!g_rccl.load()) return e->fail(TRG_ERR_DEVICE, g_rccl.err);
-  if (!e->exchange) e->exchange.reset(new ExchangeState());
-  ExchangeState &x = *e->exchange;
-  x.transport.reset();
-  const ncclComm_t comm = (ncclComm_t)nccl_comm;
-  int nranks = 0, rank = 0;
-  RCCLCHK(e, g_rccl.CommCount(comm, &nranks));
-  RCCLCHK(e, g_rccl.CommUserRank(comm, &rank));
-  if (nranks > STITCH_MAX_TILES) return e->fail(TRG_ERR_INVALID_ARG, "comm_adopt: too many ranks");
-  std::unique_ptr<RcclTransport> t(new RcclTransport());
-  t->comm = comm;
-  x.transport = std::move(t);
-  x.nranks = nranks;
-  x.rank = rank;
-  return TRG_OK;
+  return comm_install(e, [&](std::unique_ptr<Transport> &out, int &n, int &r) {
+    std::unique_ptr<RcclTransport> t(new RcclTransport());
+    t->comm = (ncclComm_t)nccl_comm;  // (not owned: the caller destroys it)
+    RCCLCHK(e, g_rccl.CommCount(t->comm, &n));
+    RCCLCHK(e, g_rccl.CommUserRank(t->comm, &r));
+    if (n > STITCH_MAX_TILES) return e->fail(TRG_ERR_INVALID_ARG, "comm_adopt: too many ranks");
+    out = std::move(t);
+    return TRG_OK;
+  });
 }
 
 // Rank `rank` of the in-process group `name` (made by whoever joins first; gone with its last member).  Joining does
@@ -221,19 +261,18 @@ TrgStatus comm_adopt(TrgEngine *e, void *nccl_comm) {
 TrgStatus comm_join_local(TrgEngine *e, const char *name, int32_t nranks, int32_t rank) {
   if (nranks < 1 || nranks > STITCH_MAX_TILES || rank < 0 || rank >= nranks)
     return e->fail(TRG_ERR_INVALID_ARG, "comm_join_local: bad arguments");
-  if (!e->exchange) e->exchange.reset(new ExchangeState());
-  ExchangeState &x = *e->exchange;
-  x.transport.reset();  // (leaves the group it was in)
-  std::unique_ptr<LocalTransport> t(new LocalTransport());
-  std::string why;
-  t->group = LocalGroup::join(name, nranks, rank, why);
-  if (!t->group) return e->fail(TRG_ERR_INVALID_ARG, "comm_join_local: " + why);
-  t->rank = rank;
-  t->wait_seconds = &e->comm_wait_seconds;
-  x.transport = std::move(t);
-  x.nranks = nranks;
-  x.rank = rank;
-  return TRG_OK;
+  return comm_install(e, [&](std::unique_ptr<Transport> &out, int &n, int &r) {
+    std::unique_ptr<LocalTransport> t(new LocalTransport());
+    std::string why;
+    t->group = LocalGroup::join(name, nranks, rank, why);
+    if (!t->group) return e->fail(TRG_ERR_INVALID_ARG, "comm_join_local: " + why);
+    t->rank = rank;
+    t->wait_seconds = &e->comm_wait_seconds;
+    out = std::move(t);
+    n = nranks;
+    r = rank;
+    return TRG_OK;
+  });
 }
 
 TrgStatus comm_destroy(TrgEngine *e) {
@@ -249,87 +288,39 @@ TrgStatus stitch_exchange(TrgEngine *e, const float core_xyxy[4], int32_t cols, 
   const int R = x.nranks, tile = x.rank;
   if (!core_xyxy || cols < 1 || rows < 1 || cols * rows != R)
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_exchange: cols x rows must equal the communicator's size");
-  hipStream_t s = e->s_main;
-  TrgStatus st, deferred = TRG_OK;
-  std::string deferred_msg;
-  // ---- 1: this tile's boundary records; the tile's node count rides behind them ---------------------------
-  int32_t nb = 0;
-  // (debug_stitch_cap: the first capacity in rows of rec and edges, so that tests reach the regrow loops)
-  const size_t rec_rows = e->debug_stitch_cap > 0 ? (size_t)e->debug_stitch_cap + 1 : (size_t)1 << 14;
+  // (debug_stitch_cap: the first capacity in rows of rec and edges, so that tests reach the regrows)
+  const size_t rec_rows = e->debug_stitch_cap > 0 ? (size_t)e->debug_stitch_cap : (size_t)1 << 14;
   const size_t edge_rows = e->debug_stitch_cap > 0 ? (size_t)e->debug_stitch_cap : (size_t)1 << 15;
-  if ((st = ensure_bytes(e, x.rec, rec_rows * sizeof(TrgBoundaryRec))) != TRG_OK) return st;
-  for (;;) {
-    const int32_t cap = (int32_t)(x.rec.bytes / sizeof(TrgBoundaryRec)) - 1;
-    st = stitch_boundary(e, core_xyxy, cols, rows, tile, (TrgBoundaryRec *)x.rec.p, cap, &nb);
-    if (st != TRG_ERR_CAPACITY) break;
-    ++e->stats.stitch_regrows;
-    if ((st = ensure_bytes(e, x.rec, (size_t)(2 * nb + 2) * sizeof(TrgBoundaryRec))) != TRG_OK) break;
-  }
-  int32_t V = 0, E_ = 0;
-  if (st == TRG_OK) st = graph_sizes(e, TRG_KIND_GLOBAL, &V, &E_);
-  if (st == TRG_OK) {
-    const TrgBoundaryRec tail = {V, 0.0f, 0.0f, 0.0f};
-    hipError_t he = hipMemcpyAsync((TrgBoundaryRec *)x.rec.p + nb, &tail, sizeof(tail), hipMemcpyHostToDevice, s);
-    if (he == hipSuccess) he = hipStreamSynchronize(s);  // (tail is a stack object)
-    if (he != hipSuccess) st = e->fail(TRG_ERR_DEVICE, std::string("stitch exchange tail row: ") + hipGetErrorString(he));
-  }
-  if (st != TRG_OK) {  // tell the others instead of leaving them in the collective
-    deferred = st;
-    deferred_msg = e->err;
-  }
-  std::vector<long long> counts;
+  TrgStatus st;
+  std::vector<long long> counts, words;
   void *d_all = nullptr;
-  st = exchange_allgatherv(e, x, x.rec.p, deferred == TRG_OK ? (long long)nb + 1 : -1, sizeof(TrgBoundaryRec), counts, &d_all);
-  if (deferred != TRG_OK) return e->fail(deferred, deferred_msg);
+  // ---- 1: this tile's boundary records; the tile's node count rides in the count exchange ----------------------
+  int32_t nb = 0, V = 0, E_ = 0;
+  if ((st = ensure_bytes(e, x.rec, rec_rows * sizeof(TrgBoundaryRec))) != TRG_OK) return st;
+  st = stitch_grown(e, x.rec, sizeof(TrgBoundaryRec), &nb, [&](int32_t cap) {
+    return stitch_boundary(e, core_xyxy, cols, rows, tile, x.rec.as<TrgBoundaryRec>(), cap, &nb);
+  });
+  if (st == TRG_OK) st = graph_sizes(e, TRG_KIND_GLOBAL, &V, &E_);
+  st = exchange_after(e, x, st, x.rec.p, nb, V, sizeof(TrgBoundaryRec), counts, words, &d_all);
   if (st != TRG_OK) return st;
-  // the gathered block holds, per rank, its records and then the count row: split the two
+  const TrgBoundaryRec *d_recs = (const TrgBoundaryRec *)d_all;  // (the gathered block as it is)
   std::vector<int32_t> rec_off(R + 1, 0), node_off(R + 1, 0);
-  {
-    long long off = 0;
-    std::vector<TrgBoundaryRec> tails(R);
-    for (int k = 0; k < R; ++k) {
-      off += counts[k];
-      HIPCHK(e, hipMemcpyAsync(&tails[k], (TrgBoundaryRec *)d_all + (off - 1), sizeof(TrgBoundaryRec), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(e, hipStreamSynchronize(s));
-    for (int k = 0; k < R; ++k) {
-      rec_off[k + 1] = rec_off[k] + (int32_t)(counts[k] - 1);
-      node_off[k + 1] = node_off[k] + tails[k].local_id;
-    }
-    // compact in place, front to back (rank k's records move down by k rows: memmove semantics per block)
-    long long src = 0;
-    for (int k = 0; k < R; ++k) {
-      const size_t nbk = (size_t)(counts[k] - 1) * sizeof(TrgBoundaryRec);
-      if (k > 0 && nbk)
-        HIPCHK(e, hipMemcpyAsync((TrgBoundaryRec *)x.recv.p + rec_off[k], (TrgBoundaryRec *)d_all + src, nbk, hipMemcpyDeviceToDevice, s));
-      else if (nbk)
-        HIPCHK(e, hipMemcpyAsync(x.recv.p, d_all, nbk, hipMemcpyDeviceToDevice, s));
-      src += counts[k];
-    }
+  for (int k = 0; k < R; ++k) {
+    rec_off[k + 1] = rec_off[k] + (int32_t)counts[k];
+    node_off[k + 1] = node_off[k] + (int32_t)words[k];
   }
-  const TrgBoundaryRec *d_recs = (const TrgBoundaryRec *)x.recv.p;  // (recv is free again: the payload was copied out)
   // ---- 2: the cross edges this tile owns ------------------------------------------------------------------------
   int32_t nc = 0;
   if ((st = ensure_bytes(e, x.edges, edge_rows * sizeof(TrgCrossEdge))) != TRG_OK) return st;
-  for (;;) {
-    const int32_t cap = (int32_t)(x.edges.bytes / sizeof(TrgCrossEdge));
-    st = stitch_cross(e, tile, R, d_recs, rec_off.data(), (TrgCrossEdge *)x.edges.p, cap, &nc);
-    if (st != TRG_ERR_CAPACITY) break;
-    ++e->stats.stitch_regrows;
-    if ((st = ensure_bytes(e, x.edges, (size_t)(2 * nc + 2) * sizeof(TrgCrossEdge))) != TRG_OK) break;
-  }
-  if (st != TRG_OK) {
-    deferred = st;
-    deferred_msg = e->err;
-  }
-  // (the gathered records in recv are dead from here on: the exchange below reuses send / recv / all)
-  std::vector<long long> ecounts;
+  st = stitch_grown(e, x.edges, sizeof(TrgCrossEdge), &nc, [&](int32_t cap) {
+    return stitch_cross(e, tile, R, d_recs, rec_off.data(), x.edges.as<TrgCrossEdge>(), cap, &nc);
+  });
+  // (the gathered records are dead from here on: the exchange below reuses send / recv / all)
   void *d_all_edges = nullptr;
-  st = exchange_allgatherv(e, x, x.edges.p, deferred == TRG_OK ? (long long)nc : -1, sizeof(TrgCrossEdge), ecounts, &d_all_edges);
-  if (deferred != TRG_OK) return e->fail(deferred, deferred_msg);
+  st = exchange_after(e, x, st, x.edges.p, nc, 0, sizeof(TrgCrossEdge), counts, words, &d_all_edges);
   if (st != TRG_OK) return st;
   long long ne = 0;
-  for (long long c : ecounts) ne += c;
+  for (long long c : counts) ne += c;
   // ---- 3: this tile's rows of the global graph ---------------------------------------------------------------------
   st = stitch_assemble(e, tile, R, node_off.data(), (const TrgCrossEdge *)d_all_edges, (int32_t)ne);
   if (st != TRG_OK) return st;

@@ -29,8 +29,6 @@ struct FieldBufs {
   DevArr ec, stats, ctrl;
   DevArr key, q[2], far[2], stamp_near, stamp_far, parent, cost, hops;  // per item: m x V entries
   DevArr targets, cost_at, hops_at;                                           // n_targets, m x n_targets
-  DevArr up_rowptr, up_col, up_w, up_dist, up_state;  // csr_global + nstate when the device build's CSR is stale
-  uint64_t up_version = 0;   // graph_version of the upload (0: none)
   // The edge-cost cache ("Cost models"): `ec` holds slot i at i * ec_stride, one slot per
   // cost model met, for one graph_version and column array.  Slot 0 is the engine's own model and is never given
   // away; the others go to the model a solve needs and does not find, the least recently used first.
@@ -49,15 +47,15 @@ struct FieldBufs {
   const void *ec_col = nullptr;  // ... and the column array they were computed from
   // The last solve, kept on the device for trg_engine_field_routes: set by a successful solve, cleared when a
   // solve begins its device work; a graph_version other than the engine's (init_graph, update_graph, load_json,
-  // a reset) makes it stale, so does a device-build CSR that is no longer valid (an update_graph that began,
-  // whether or not it finished), and field_release drops it with the buffers.
+  // a reset) makes it stale, so does a device graph (ensure_dev_graph) that is no longer the one it ran on (the
+  // device build's, once an update_graph began, whether or not it finished), and field_release drops it with the
+  // buffers.
   struct Last {
     uint64_t version = 0;    // graph_version of the solve (0: none)
-    FieldDev F{};            // keys, parents and the CSR it ran on
+    FieldDev F{};            // keys, parents and the CSR it ran on (ensure_dev_graph's, as are w and dist)
     const float *w = nullptr, *dist = nullptr;  // that CSR's edge arrays
     FieldSources sources{};  // a walk must end at its field's
     bool parents = false;    // the parent sweep ran
-    bool dev_csr = false;    // F's CSR is the device build's (gone stale when an update_graph begins)
     std::optional<FieldSets> sets;  // of a set solve ("Source sets"), on the device
     bool owners = false;     // ... and the owner pass ran: sets->owner is filled
     bool bounded = false;    // keys above a bound were removed: nothing a refresh can start from
@@ -160,13 +158,7 @@ struct FieldRun {
   bool gather = false;      // cost_at / hops_at (/ owner_at) are wanted
   FieldSets sets{};         // a set solve: n from the checks on, the device arrays from the passes on
   bool owners = false;      // owner, owner_at or owned is wanted: the owner pass runs
-  // the CSR the solve runs on: the device build's in place, or the engine's upload of csr_global
-  struct Graph {
-    const int *rowptr, *col, *state;
-    const float *w, *dist;
-    int E;
-    bool dev_csr;
-  } G{};
+  DevGraph G{};             // the graph the solve runs on (ensure_dev_graph)
   int syncs = 0, rounds = 0;
   // a refresh: the retained solve's view, whose keys field_carry reads, and what field_check_refresh built for rq
   // to point at -- the identity map, the sources or the sets as ids of the current graph
@@ -185,9 +177,10 @@ struct FieldRun {
 
 constexpr uint32_t FIELD_INF_BITS = 0x7f800000u;
 
-// is the retained solve one of the engine's graph as it is now, its CSR still there
-bool field_last_current(const TrgEngine *e, const FieldBufs::Last &last) {
-  return last.version == e->graph_version && (!last.dev_csr || dev_csr(e));
+// is the retained solve one of the engine's graph as it is now, the device graph it ran on still current
+bool field_last_current(TrgEngine *e, const FieldBufs::Last &last) {
+  DevGraph now;
+  return last.version == e->graph_version && ensure_dev_graph(e, 0, &now) == TRG_OK && now.rowptr == last.F.rowptr;
 }
 
 // the retained solve for `call` ("cost field routes", ...), or that call's refusal; `current`: a stale one is refused
@@ -389,35 +382,10 @@ TrgStatus field_begin(TrgEngine *e, FieldRun &) {
   return TRG_OK;
 }
 
-// the graph on the device: the device build's CSR in place, else csr_global uploaded once per version
+// the graph on the device (ensure_dev_graph: plan_prepare has made csr_global current); t0 follows its uploads
 TrgStatus field_graph(TrgEngine *e, FieldRun &run) {
-  FieldBufs &fb = *e->field;
-  hipStream_t s = e->s_main;
-  const Csr &G = e->csr_global;
-  const int V = run.F.V, E = G.rowptr.empty() ? 0 : G.rowptr[V];
-  if (const BfsBuffers *dev = dev_csr(e)) {
-    const BfsBuffers &bb = *dev;
-    run.G = {bb.rowptr_new.as<int>(), bb.col2.as<int>(), bb.state2.as<int>(), bb.w2.as<float>(), bb.dist2.as<float>(),
-             E, true};
-  } else {
-    if (fb.up_version != e->graph_version) {
-      fb.up_version = 0;
-      const struct { DevArr &a; const void *src; size_t bytes, slack; } up[] = {
-          {fb.up_rowptr, G.rowptr.data(), ((size_t)V + 1) * sizeof(int), 0},
-          {fb.up_state, e->nstate.data(), (size_t)V * sizeof(int), 0},
-          {fb.up_col, G.col.data(), (size_t)E * sizeof(int), 16},
-          {fb.up_w, G.w.data(), (size_t)E * sizeof(float), 16},
-          {fb.up_dist, G.dist.data(), (size_t)E * sizeof(float), 16}};
-      for (const auto &u : up)
-        if (const TrgStatus st = ensure_bytes(e, u.a, u.bytes + u.slack); st != TRG_OK) return st;
-      for (const auto &u : up)
-        if (u.bytes) HIPCHK(e, hipMemcpyAsync(u.a.p, u.src, u.bytes, hipMemcpyHostToDevice, s));
-      fb.up_version = e->graph_version;
-    }
-    run.G = {fb.up_rowptr.as<int>(), fb.up_col.as<int>(), fb.up_state.as<int>(), fb.up_w.as<float>(),
-             fb.up_dist.as<float>(), E, false};
-  }
-  HIPCHK(e, hipEventRecord(fb.t0, s));
+  if (const TrgStatus st = ensure_dev_graph(e, DEV_NODES | DEV_EDGES, &run.G); st != TRG_OK) return st;
+  HIPCHK(e, hipEventRecord(e->field->t0, e->s_main));
   return TRG_OK;
 }
 
@@ -427,7 +395,7 @@ TrgStatus field_graph(TrgEngine *e, FieldRun &run) {
 TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
   FieldBufs &fb = *e->field;
   hipStream_t s = e->s_main;
-  const FieldRun::Graph &G = run.G;
+  const DevGraph &G = run.G;
   const int m = run.F.m;
   const uint32_t sf0 = float_bits(e->prm.safety_factor);
   const size_t stride = ((size_t)G.E + 4 + 3) & ~(size_t)3;  // (slots start 16-byte aligned, 16 bytes of slack each)
@@ -784,7 +752,7 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   run.info->source = run.sources.id[0];
   run.info->reached = (int32_t)reached;
   run.info->rounds = run.rounds;
-  fb.last = FieldBufs::Last{e->graph_version, F, run.G.w, run.G.dist, run.sources, parents, run.G.dev_csr,
+  fb.last = FieldBufs::Last{e->graph_version, F, run.G.w, run.G.dist, run.sources, parents,
                             rq.set_ptr ? std::optional<FieldSets>(run.sets) : std::nullopt, run.owners};
   fb.last.F.tight = nullptr;  // (its array holds the cost output now)
   fb.last.bounded = run.bounded;

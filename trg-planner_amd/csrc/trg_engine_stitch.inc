@@ -4,60 +4,22 @@
 
 namespace {
 
-// the cleaned global graph of this engine on the device: still resident after a device build, else
-// uploaded from the host copy
-struct DevGraph {
-  const float *xyz = nullptr;
-  const int *rowptr = nullptr, *col = nullptr;
-  const float *w = nullptr, *dist = nullptr;
-  int V = 0, E = 0;
+// scratch of the three steps, and the stitched rows until an export fetches them; made on first use
+struct StitchBufs {
+  DevArr flag, off, cnt, pair_a, pair_b, p1, p2, mid, status, npts, weight, dist, n_unc;
+  DevArr extra, deg, rowptr_new, fill, col_new, w_new, dist_new;
+  DevArr scan_tmp;
 };
 
-TrgStatus stitch_dev_graph(TrgEngine *e, bool need_edges, DevGraph *g) {
-  StitchBufs &sb = *e->stitch;
-  Csr &c = e->csr_global;
-  (void)ensure_csr_global(e);  // (false: neither the CSR nor the pool is current, the old rows stay in place)
-  g->V = (int)c.state.size();
-  g->E = (int)c.col.size();
-  if (const BfsBuffers *bb = dev_csr(e)) {
-    g->xyz = (const float *)bb->xyz2.p;
-    g->rowptr = (const int *)bb->rowptr_new.p;
-    g->col = (const int *)bb->col2.p;
-    g->w = (const float *)bb->w2.p;
-    g->dist = (const float *)bb->dist2.p;
-    return TRG_OK;
-  }
-  TrgStatus st;
-  hipStream_t s = e->s_main;
-  if ((st = ensure_bytes(e, sb.up_xyz, (size_t)g->V * 12 + 16)) != TRG_OK) return st;
-  if (g->V) HIPCHK(e, hipMemcpyAsync(sb.up_xyz.p, c.xyz.data(), (size_t)g->V * 12, hipMemcpyHostToDevice, s));
-  g->xyz = (const float *)sb.up_xyz.p;
-  if (need_edges) {
-    if ((st = ensure_bytes(e, sb.up_rowptr, ((size_t)g->V + 1) * 4)) != TRG_OK) return st;
-    if ((st = ensure_bytes(e, sb.up_col, (size_t)g->E * 4 + 16)) != TRG_OK) return st;
-    if ((st = ensure_bytes(e, sb.up_w, (size_t)g->E * 4 + 16)) != TRG_OK) return st;
-    if ((st = ensure_bytes(e, sb.up_dist, (size_t)g->E * 4 + 16)) != TRG_OK) return st;
-    std::vector<int> rp(1, 0);
-    const int *rowptr_h = c.rowptr.empty() ? rp.data() : c.rowptr.data();
-    HIPCHK(e, hipMemcpyAsync(sb.up_rowptr.p, rowptr_h, ((size_t)g->V + 1) * 4, hipMemcpyHostToDevice, s));
-    if (g->E) {
-      HIPCHK(e, hipMemcpyAsync(sb.up_col.p, c.col.data(), (size_t)g->E * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(e, hipMemcpyAsync(sb.up_w.p, c.w.data(), (size_t)g->E * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(e, hipMemcpyAsync(sb.up_dist.p, c.dist.data(), (size_t)g->E * 4, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(e, hipStreamSynchronize(s));  // (rp is a stack object)
-    g->rowptr = (const int *)sb.up_rowptr.p;
-    g->col = (const int *)sb.up_col.p;
-    g->w = (const float *)sb.up_w.p;
-    g->dist = (const float *)sb.up_dist.p;
-  }
-  return TRG_OK;
+StitchBufs &stitch_bufs(TrgEngine *e) {
+  if (!e->stitch) e->stitch.reset(new StitchBufs());
+  return *e->stitch;
 }
 
 // the stitched rows from HBM into the host CSR (lazily, on the first export after an assemble)
 TrgStatus stitch_fetch(TrgEngine *e) {
   if (!e->current(TrgEngine::VIEW_STITCH_DEV)) return TRG_OK;
-  StitchBufs &sb = *e->stitch;
+  StitchBufs &sb = *e->stitch;  // (stitch_assemble made it)
   Csr &out = e->csr_stitched;
   hipStream_t s = e->s_main;
   const size_t V = out.state.size();
@@ -81,22 +43,22 @@ TrgStatus stitch_boundary(TrgEngine *e, const float core_xyxy[4], int32_t cols, 
                           TrgBoundaryRec *d_rec, int32_t cap, int32_t *n_out) {
   if (!core_xyxy || !n_out || cols < 1 || rows < 1 || tile < 0 || tile >= cols * rows || cap < 0)
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_boundary: bad arguments");
-  StitchBufs &sb = *e->stitch;
+  StitchBufs &sb = stitch_bufs(e);
   DevGraph g;
-  TrgStatus st = stitch_dev_graph(e, false, &g);
+  TrgStatus st = ensure_dev_graph(e, DEV_NODES, &g);
   if (st != TRG_OK) return st;
   *n_out = 0;
   if (g.V == 0) return TRG_OK;
   const int c = tile % cols, r = tile / cols;
   const int sides = (c > 0 ? 1 : 0) | (c < cols - 1 ? 2 : 0) | (r > 0 ? 4 : 0) | (r < rows - 1 ? 8 : 0);
-  if ((st = ensure_bytes(e, sb.flag, ((size_t)g.V + 1) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.off, ((size_t)g.V + 2) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.scan_tmp, ((size_t)g.V / 2048 + 16) * 4)) != TRG_OK) return st;
+  const size_t V = (size_t)g.V;
+  if ((st = ensure_all(e, {{&sb.flag, (V + 1) * 4}, {&sb.off, (V + 2) * 4}, {&sb.scan_tmp, (V / 2048 + 16) * 4}})) != TRG_OK)
+    return st;
   hipStream_t s = e->s_main;
-  launch_stitch_boundary(g.xyz, g.V, core_xyxy, sides, e->prm.expand_dist, (int *)sb.flag.p, (int *)sb.off.p,
-                         (int *)sb.scan_tmp.p, (StitchRec *)d_rec, d_rec ? cap : 0, s);
+  launch_stitch_boundary(g.xyz, g.V, core_xyxy, sides, e->prm.expand_dist, sb.flag.as<int>(), sb.off.as<int>(),
+                         sb.scan_tmp.as<int>(), (StitchRec *)d_rec, d_rec ? cap : 0, s);
   int n = 0;
-  HIPCHK(e, hipMemcpyAsync(&n, (int *)sb.off.p + g.V, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipMemcpyAsync(&n, sb.off.as<int>() + g.V, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   *n_out = n;
   if (d_rec && n > cap) return e->fail(TRG_ERR_CAPACITY, "stitch_boundary: record buffer too small");
@@ -109,7 +71,7 @@ TrgStatus stitch_cross(TrgEngine *e, int32_t tile, int32_t ntiles, const TrgBoun
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_cross: bad arguments");
   if (!e->gmap.valid) return e->fail(TRG_ERR_NO_MAP, "stitch_cross: no map");
   *n_out = 0;
-  StitchBufs &sb = *e->stitch;
+  StitchBufs &sb = stitch_bufs(e);
   hipStream_t s = e->s_main;
   const int na = rec_offsets[tile + 1] - rec_offsets[tile];
   const int U = ntiles - tile - 1;
@@ -117,48 +79,38 @@ TrgStatus stitch_cross(TrgEngine *e, int32_t tile, int32_t ntiles, const TrgBoun
   const StitchRec *all = (const StitchRec *)d_all_rec;
   TrgStatus st;
   const size_t cells = (size_t)U * na;
-  if ((st = ensure_bytes(e, sb.cnt, (cells + 1) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.off, (cells + 2) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.scan_tmp, (cells / 2048 + 16) * 4)) != TRG_OK) return st;
-  launch_stitch_pairs(all, rec_offsets, tile, ntiles, e->prm.expand_dist, 0, (int *)sb.cnt.p, nullptr, nullptr,
-                      nullptr, s);
-  launch_exclusive_scan((const int *)sb.cnt.p, (int *)sb.off.p, (int)cells, (int *)sb.scan_tmp.p, s);
+  if ((st = ensure_all(e, {{&sb.cnt, (cells + 1) * 4}, {&sb.off, (cells + 2) * 4},
+                           {&sb.scan_tmp, (cells / 2048 + 16) * 4}})) != TRG_OK)
+    return st;
+  launch_stitch_pairs(all, rec_offsets, tile, ntiles, e->prm.expand_dist, 0, sb.cnt.as<int>(), nullptr, nullptr, nullptr, s);
+  launch_exclusive_scan(sb.cnt.as<int>(), sb.off.as<int>(), (int)cells, sb.scan_tmp.as<int>(), s);
   int npairs = 0;
-  HIPCHK(e, hipMemcpyAsync(&npairs, (int *)sb.off.p + cells, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipMemcpyAsync(&npairs, sb.off.as<int>() + cells, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   if (npairs <= 0) return TRG_OK;
   const size_t np_ = (size_t)npairs;
-  if ((st = ensure_bytes(e, sb.pair_a, np_ * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.pair_b, np_ * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.p1, np_ * 12)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.p2, np_ * 12)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.mid, edge_mid_floats(np_) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.status, np_ * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.npts, np_ * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.weight, np_ * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.dist, np_ * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.flag, (np_ + 1) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.n_unc, 16)) != TRG_OK) return st;
-  launch_stitch_pairs(all, rec_offsets, tile, ntiles, e->prm.expand_dist, 1, nullptr, (const int *)sb.off.p,
-                      (int *)sb.pair_a.p, (int *)sb.pair_b.p, s);
-  launch_stitch_pair_points(all, (const int *)sb.pair_a.p, (const int *)sb.pair_b.p, npairs, (float *)sb.p1.p,
-                            (float *)sb.p2.p, s);
+  if ((st = ensure_all(e, {{&sb.pair_a, np_ * 4}, {&sb.pair_b, np_ * 4}, {&sb.p1, np_ * 12}, {&sb.p2, np_ * 12},
+                           {&sb.mid, edge_mid_floats(np_) * 4}, {&sb.status, np_ * 4}, {&sb.npts, np_ * 4},
+                           {&sb.weight, np_ * 4}, {&sb.dist, np_ * 4}, {&sb.flag, (np_ + 1) * 4}, {&sb.n_unc, 16}})) !=
+      TRG_OK)
+    return st;
+  int *pair_a = sb.pair_a.as<int>(), *pair_b = sb.pair_b.as<int>(), *status = sb.status.as<int>();
+  float *p1 = sb.p1.as<float>(), *p2 = sb.p2.as<float>(), *weight = sb.weight.as<float>(), *dist = sb.dist.as<float>();
+  launch_stitch_pairs(all, rec_offsets, tile, ntiles, e->prm.expand_dist, 1, nullptr, sb.off.as<int>(), pair_a, pair_b, s);
+  launch_stitch_pair_points(all, pair_a, pair_b, npairs, p1, p2, s);
   // wireEdge's position-only part for (a, b) on this tile's map (trg.cpp:269-363)
-  launch_edges(e->gmap.view, qparams(e), (const float *)sb.p1.p, (const float *)sb.p2.p, npairs,
-               (float *)sb.mid.p, (int *)sb.status.p, (int *)sb.npts.p, (float *)sb.weight.p,
-               (float *)sb.dist.p, e->d_ctr, s);
+  launch_edges(e->gmap.view, qparams(e), p1, p2, npairs, sb.mid.as<float>(), status, sb.npts.as<int>(), weight, dist,
+               e->d_ctr, s);
   e->stats.edge_evals_gpu += (uint64_t)npairs;
   // pair offsets are no longer needed: off is reused for the scan of the success flags
-  if ((st = ensure_bytes(e, sb.off, (np_ + 2) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.scan_tmp, (np_ / 2048 + 16) * 4)) != TRG_OK) return st;
+  if ((st = ensure_all(e, {{&sb.off, (np_ + 2) * 4}, {&sb.scan_tmp, (np_ / 2048 + 16) * 4}})) != TRG_OK) return st;
   for (int attempt = 0; attempt < 2; ++attempt) {
     HIPCHK(e, hipMemsetAsync(sb.n_unc.p, 0, 4, s));
-    launch_stitch_edge_select(all, rec_offsets, tile, ntiles, (const int *)sb.pair_a.p, (const int *)sb.pair_b.p,
-                              (const int *)sb.status.p, (const float *)sb.weight.p, (const float *)sb.dist.p,
-                              npairs, (int *)sb.flag.p, (int *)sb.off.p, (int *)sb.scan_tmp.p, (int *)sb.n_unc.p,
+    launch_stitch_edge_select(all, rec_offsets, tile, ntiles, pair_a, pair_b, status, weight, dist, npairs,
+                              sb.flag.as<int>(), sb.off.as<int>(), sb.scan_tmp.as<int>(), sb.n_unc.as<int>(),
                               (StitchEdge *)d_edges, d_edges ? cap : 0, s);
     int tail[2] = {0, 0};
-    HIPCHK(e, hipMemcpyAsync(&tail[0], (int *)sb.off.p + npairs, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(&tail[0], sb.off.as<int>() + npairs, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipMemcpyAsync(&tail[1], sb.n_unc.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     if (tail[1] == 0 || attempt == 1) {
@@ -185,10 +137,10 @@ TrgStatus stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles, const int3
                           const TrgCrossEdge *d_all_edges, int32_t n_edges) {
   if (!node_offsets || ntiles < 1 || ntiles > STITCH_MAX_TILES || tile < 0 || tile >= ntiles || n_edges < 0)
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_assemble: bad arguments");
-  StitchBufs &sb = *e->stitch;
+  StitchBufs &sb = stitch_bufs(e);
   hipStream_t s = e->s_main;
   DevGraph g;
-  TrgStatus st = stitch_dev_graph(e, true, &g);
+  TrgStatus st = ensure_dev_graph(e, DEV_EDGES, &g);
   if (st != TRG_OK) return st;
   if (node_offsets[tile + 1] - node_offsets[tile] != g.V)
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_assemble: node_offsets do not match this tile's graph");
@@ -204,32 +156,32 @@ TrgStatus stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles, const int3
   out.rowptr.assign(1, 0);
   if (g.V == 0) return TRG_OK;
   const size_t V = (size_t)g.V;
-  if ((st = ensure_bytes(e, sb.extra, (V + 1) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.fill, (V + 1) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.deg, (V + 1) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.rowptr_new, (V + 2) * 4)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.scan_tmp, (V / 2048 + 16) * 4)) != TRG_OK) return st;
+  if ((st = ensure_all(e, {{&sb.extra, (V + 1) * 4}, {&sb.fill, (V + 1) * 4}, {&sb.deg, (V + 1) * 4},
+                           {&sb.rowptr_new, (V + 2) * 4}, {&sb.scan_tmp, (V / 2048 + 16) * 4}})) != TRG_OK)
+    return st;
   HIPCHK(e, hipMemsetAsync(sb.extra.p, 0, (V + 1) * 4, s));
   HIPCHK(e, hipMemsetAsync(sb.fill.p, 0, (V + 1) * 4, s));
   const StitchEdge *edges = (const StitchEdge *)d_all_edges;
-  launch_stitch_assemble(edges, n_edges, tile, ntiles, node_offsets, g.rowptr, g.col, g.w, g.dist, g.V,
-                         (int *)sb.extra.p, (int *)sb.deg.p, (int *)sb.rowptr_new.p, (int *)sb.scan_tmp.p,
-                         (int *)sb.fill.p, nullptr, nullptr, nullptr, 0, s);
+  // pass 0 counts the rows, pass 1 (with the edge arrays) fills them
+  const auto pass = [&](int fill) {
+    launch_stitch_assemble(edges, n_edges, tile, ntiles, node_offsets, g.rowptr, g.col, g.w, g.dist, g.V,
+                           sb.extra.as<int>(), sb.deg.as<int>(), sb.rowptr_new.as<int>(), sb.scan_tmp.as<int>(),
+                           sb.fill.as<int>(), fill ? sb.col_new.as<int>() : nullptr,
+                           fill ? sb.w_new.as<float>() : nullptr, fill ? sb.dist_new.as<float>() : nullptr, fill, s);
+  };
+  pass(0);
   int En = 0, n_bad = 0;
-  HIPCHK(e, hipMemcpyAsync(&En, (int *)sb.rowptr_new.p + g.V, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(e, hipMemcpyAsync(&n_bad, (int *)sb.extra.p + g.V, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipMemcpyAsync(&En, sb.rowptr_new.as<int>() + g.V, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipMemcpyAsync(&n_bad, sb.extra.as<int>() + g.V, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   if (n_bad) {
     out.clear();  // (no rows at all: a view of V nodes without their V + 1 row pointers must not be exported)
     return e->fail(TRG_ERR_INVALID_ARG, "stitch_assemble: " + std::to_string(n_bad) +
                                             " cross edges name a tile or a node outside node_offsets");
   }
-  if ((st = ensure_bytes(e, sb.col_new, (size_t)En * 4 + 16)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.w_new, (size_t)En * 4 + 16)) != TRG_OK) return st;
-  if ((st = ensure_bytes(e, sb.dist_new, (size_t)En * 4 + 16)) != TRG_OK) return st;
-  launch_stitch_assemble(edges, n_edges, tile, ntiles, node_offsets, g.rowptr, g.col, g.w, g.dist, g.V,
-                         (int *)sb.extra.p, (int *)sb.deg.p, (int *)sb.rowptr_new.p, (int *)sb.scan_tmp.p,
-                         (int *)sb.fill.p, (int *)sb.col_new.p, (float *)sb.w_new.p, (float *)sb.dist_new.p, 1, s);
+  const size_t eb = (size_t)En * 4 + 16;
+  if ((st = ensure_all(e, {{&sb.col_new, eb}, {&sb.w_new, eb}, {&sb.dist_new, eb}})) != TRG_OK) return st;
+  pass(1);
   // the rows stay in HBM; an export of TRG_KIND_STITCHED fetches them when asked
   e->stitched_edges = En;
   e->view_stamp[TrgEngine::VIEW_STITCH_DEV] = e->graph_version;

@@ -9,7 +9,8 @@ tiled build is defined as follows (the CPU oracle implements the same rule, test
    one change: a sample outside core_t counts as a rejected draw, so every node of tile t lies in
    core_t.  Sampler: same seed, epoch = tile index.  cleanGraph runs per tile.
 2. Boundary nodes = nodes closer than expand_dist to a core border shared with another tile.
-   Every rank publishes them (all-gather-v: local id, x, y, z).
+   Every rank publishes them (all-gather-v: local id, x, y, z; the tile's node count travels with the
+   record count).
 3. For every pair (a in tile t, b in tile u, t < u) with ||a - b|| < expand_dist (fp32 norm as
    trg.cpp:414) rank t evaluates wireEdge's position-only part for (a, b) on its own map; the
    successful ones are published (second all-gather-v).
@@ -82,25 +83,33 @@ def boundary_nodes(xyz, core, cols, rows, tile, dist):
     return np.nonzero(m)[0].astype(np.int32)
 
 
-def allgatherv_t(t, dist=None):
+def allgatherv_aux_t(t, aux, dist=None):
     """All-gather of per-rank torch tensors with different leading sizes ON THE DEVICE THEY LIVE ON
-    (device tensors over RCCL, host tensors over gloo): counts first, then padded payloads (RCCL has
-    no native allgatherv).  Returns (concatenation in rank order, counts list)."""
+    (device tensors over RCCL, host tensors over gloo), and of one integer `aux` per rank: the counts
+    and the integers first, in one collective, then padded payloads (RCCL has no native allgatherv).
+    Returns (concatenation in rank order, counts list, the ranks' integers)."""
     import torch
     if dist is None or not dist.is_initialized() or (
             dist.get_world_size() == 1 and not os.environ.get("TRG_FORCE_COLLECTIVES")):
-        return t, [int(t.shape[0])]  # (TRG_FORCE_COLLECTIVES: tests run the exchange with one rank)
+        return t, [int(t.shape[0])], [int(aux)]  # (TRG_FORCE_COLLECTIVES: tests run the exchange with one rank)
     world = dist.get_world_size()
-    n = torch.tensor([t.shape[0]], dtype=torch.int64, device=t.device)
-    counts = [torch.zeros(1, dtype=torch.int64, device=t.device) for _ in range(world)]
-    dist.all_gather(counts, n)
-    counts = torch.cat(counts).cpu().tolist()  # the one host round trip of the exchange
+    n = torch.tensor([t.shape[0], int(aux)], dtype=torch.int64, device=t.device)
+    heads = [torch.zeros(2, dtype=torch.int64, device=t.device) for _ in range(world)]
+    dist.all_gather(heads, n)
+    heads = torch.stack(heads).cpu()  # the one host round trip of the exchange
+    counts, auxs = heads[:, 0].tolist(), heads[:, 1].tolist()
     pad = max(max(counts), 1)
     buf = torch.zeros((pad,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
     buf[:t.shape[0]] = t
     outs = [torch.empty_like(buf) for _ in range(world)]
     dist.all_gather(outs, buf)
-    return torch.cat([o[:c] for o, c in zip(outs, counts)], 0), counts
+    return torch.cat([o[:c] for o, c in zip(outs, counts)], 0), counts, auxs
+
+
+def allgatherv_t(t, dist=None):
+    """allgatherv_aux_t without the integer.  Returns (concatenation in rank order, counts list)."""
+    got, counts, _ = allgatherv_aux_t(t, 0, dist)
+    return got, counts
 
 
 def native_comm(eng, dist):
@@ -157,41 +166,33 @@ def stitch_device(eng, my_tile, core, cols, rows, dist=None, gather_dev=None):
         bufs = eng._stitch_bufs = {"rec": torch.empty((1 << 14, 4), dtype=torch.int32, device=dev),
                                    "edges": torch.empty((1 << 15, 6), dtype=torch.int32, device=dev)}
     from ._engine import TrgError
-    while True:
-        rec = bufs["rec"]
-        try:
-            nb = eng.stitch_boundary(core, cols, rows, my_tile, rec.data_ptr(), rec.shape[0])
-            break
-        except TrgError as ex:
-            if ex.status != 8:  # TRG_ERR_CAPACITY
-                raise
-            need = eng.stitch_boundary(core, cols, rows, my_tile)
-            bufs["rec"] = torch.empty((2 * need, 4), dtype=torch.int32, device=dev)
-    # exchange 1: the boundary records, and riding behind them one row with this tile's node count
+
+    def grown(key, width, step):
+        """(buffer, rows) of step(pointer, capacity) -> rows, once the rows fit the engine's `key` buffer; one that
+        is too small makes way for one of twice the rows the step counts (it counts when given no buffer)."""
+        while True:
+            buf = bufs[key]
+            try:
+                return buf, step(buf.data_ptr(), buf.shape[0])
+            except TrgError as ex:
+                if ex.status != 8:  # TRG_ERR_CAPACITY
+                    raise
+                bufs[key] = torch.empty((2 * step(None, 0), width), dtype=torch.int32, device=dev)
+
+    rec, nb = grown("rec", 4, lambda p, cap: eng.stitch_boundary(core, cols, rows, my_tile, p, cap))
+    # exchange 1: the boundary records, and beside their count this tile's node count
     V = eng.graph_sizes("global")[0]
-    send = torch.cat([rec[:nb], torch.tensor([[V, 0, 0, 0]], dtype=torch.int32, device=dev)], 0)
-    got, counts = allgatherv_t(send.to(gdev), dist)
+    all_rec, counts, sizes = allgatherv_aux_t(rec[:nb].to(gdev), V, dist)
     if len(counts) != ntiles:  # single process: nothing to stitch against
         node_off = np.array([0, V], np.int32)
         eng.stitch_assemble(0, 1, node_off, None, 0)
         return dict(n_boundary=0, n_cross=0, node_offsets=node_off, backend="none")
-    ends = np.cumsum(counts)
-    got = got.to(dev)
-    node_off = np.concatenate([[0], np.cumsum(got[torch.as_tensor(ends - 1, device=dev), 0].cpu().numpy())]
-                              ).astype(np.int32)
-    all_rec = torch.cat([got[e - c:e - 1] for e, c in zip(ends, counts)], 0).contiguous()
-    rec_off = np.concatenate([[0], np.cumsum([c - 1 for c in counts])]).astype(np.int32)
+    node_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    rec_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    all_rec = all_rec.to(dev).contiguous()
     torch.cuda.synchronize()
-    while True:
-        edges = bufs["edges"]
-        try:
-            nc = eng.stitch_cross(my_tile, ntiles, all_rec.data_ptr(), rec_off, edges.data_ptr(), edges.shape[0])
-            break
-        except TrgError as ex:
-            if ex.status != 8:
-                raise
-            bufs["edges"] = torch.empty((2 * edges.shape[0], 6), dtype=torch.int32, device=dev)
-    all_edges, ecounts = allgatherv_t(edges[:nc].to(gdev), dist)
+    edges, nc = grown("edges", 6, lambda p, cap: eng.stitch_cross(my_tile, ntiles, all_rec.data_ptr(), rec_off, p, cap))
+    all_edges, _ = allgatherv_t(edges[:nc].to(gdev), dist)
     all_edges = all_edges.to(dev).contiguous()
     torch.cuda.synchronize()
     eng.stitch_assemble(my_tile, ntiles, node_off, all_edges.data_ptr(), int(all_edges.shape[0]))
