@@ -676,6 +676,45 @@ TrgStatus trg_engine_risk_field_refresh(TrgEngine *e,
     int32_t *sources_out, int32_t *reached_out, int32_t *carried_out,
     TrgFieldInfo *info);
 
+/* ---- cost fields across tiles ("Cost fields across tiles") -------------------------------
+ * The cost field of the GLOBAL stitched graph, solved by all ranks together: a collective call, made by every rank
+ * of the engine's communicator (trg_engine_comm_init / comm_adopt / comm_join_local) with the same m and sources,
+ * after a stitch (trg_engine_stitch_exchange, or trg_engine_stitch_assemble with the ranks' own exchanges) that is
+ * still current -- the tile's graph has not changed since.  The global graph G is the concatenation of the tiles'
+ * stitched rows; node `local id` of tile t has the global id node_offsets[t] + local id, with the node_offsets of
+ * that stitch, which the engine keeps (trg_engine_stitch_ids).  Field k is what trg_engine_cost_field defines, on G,
+ * from global id source_gids[k]: cost bits, hops and parents equal a host Dijkstra on G.  A rank receives its own
+ * nodes' part:
+ *   cost, hops, parent   m x (this tile's nodes) each, host memory, any may be NULL; parents are GLOBAL ids, the
+ *                        smallest global id u with an edge u->v whose extension of u's key is v's key; -1 for the
+ *                        source and for unreached nodes (hops == -1)
+ * The ranks relax their own rows and trade the keys of their border nodes (16-byte records through the stitch's
+ * all-gather-v) until an exchange in which no rank has news, once per pass of the solve.
+ * TRG_ERR_INVALID_ARG, before any collective and with the group still usable, for what every rank judges alike: no
+ * communicator, m < 1 or m > TRG_FIELD_BATCH_MAX, a NULL source_gids, a source outside [0, nodes of G).  A failure
+ * of one rank's own -- no current stitched rows (TRG_ERR_INVALID_ARG), an edge cost that is negative or not finite
+ * (TRG_ERR_INVALID_ARG), m x (nodes + ghosts) beyond the solver's 32-bit item index or no device memory
+ * (TRG_ERR_CAPACITY), a queue overflow (TRG_ERR_DEVICE) -- is announced in the next count exchange: that rank returns
+ * its error, every other rank TRG_ERR_DEVICE "another rank reported a failure", none waits.  TRG_ERR_DEVICE on every
+ * rank at once when the exchanges do not converge.  Source sets, start costs, bounds, cost models, risk fields,
+ * refresh and device-side routes are not offered for this call, and it leaves the retained single-engine solve alone. */
+typedef struct TrgTiledFieldInfo {
+  int32_t exchanges;     /* all-gather-v exchanges of both passes, the two that found no news included */
+  int32_t rounds;        /* relaxation rounds of this rank that did work */
+  int32_t ghosts;        /* distinct other ends of this tile's cross edges */
+  int32_t border_nodes;  /* this tile's nodes with a cross edge */
+  int64_t records_sent;  /* records this rank published */
+  float ms_device;       /* hipEvent time from the start of this rank's local work to its publish, summed over the
+                          * exchanges, plus the parent sweep and outputs: the waits for other ranks are not in it */
+  float ms_total;        /* host wall time */
+} TrgTiledFieldInfo;
+TrgStatus trg_engine_tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *source_gids,
+    float *cost, int32_t *hops, int32_t *parent,   /* m x (this tile's nodes), any may be NULL */
+    TrgTiledFieldInfo *info);                      /* may be NULL */
+/* The global ids of the current stitch: this tile's first global id, its node count and the global graph's.
+ * TRG_ERR_INVALID_ARG without current stitched rows. */
+TrgStatus trg_engine_stitch_ids(TrgEngine *e, int32_t *first_gid, int32_t *num_nodes, int32_t *total_nodes);
+
 /* ---- instrumentation ------------------------------------------------------------------------- */
 TrgStatus trg_engine_get_stats(const TrgEngine *e, TrgStats *out);
 /* the direction table the engine uses (2^table_bits entries each) */

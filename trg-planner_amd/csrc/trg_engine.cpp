@@ -457,6 +457,7 @@ struct StitchBufs;  // scratch of the tile-boundary stitch (trg_engine_stitch.in
 struct Uploader;    // host cloud -> HBM staging (trg_engine_map.ipp)
 struct ExchangeState;  // transport (RCCL communicator or in-process group) + buffers of the native stitch exchange (trg_engine_exchange.inc)
 struct FieldBufs;      // device buffers of the cost field (trg_engine_field.ipp)
+struct TiledFieldBufs; // solve graph and work arrays of the cost field across tiles (trg_engine_field_tiled.inc)
 
 // the engine's own copy of the cleaned global graph in HBM, for when the device build's is not current
 // (ensure_dev_graph): its two parts, and the sizes they were copied at
@@ -553,7 +554,7 @@ struct TrgEngine {
   //   VIEW_UP_NODES    dev_up: xyz, state           ensure_dev_graph, when no VIEW_DEV_CSR       cost field, stitch
   //   VIEW_UP_EDGES    dev_up: rowptr, col, w, dist ensure_dev_graph, when no VIEW_DEV_CSR       cost field, stitch_assemble
   //   VIEW_STITCH_DEV  csr_stitched's edges in HBM  stitch_assemble; stitch_fetch un-stamps      graph("stitched")
-  // (the cost field's edge costs carry their own stamp in FieldBufs)
+  // (the cost field's edge costs carry their own stamp in FieldBufs, the tiled cost field's solve graph in TiledFieldBufs)
   enum GraphView { VIEW_POOL, VIEW_GRID, VIEW_KD_ORDER, VIEW_KD, VIEW_KDO, VIEW_CSR, VIEW_DEV_CSR, VIEW_UP_NODES,
                    VIEW_UP_EDGES, VIEW_STITCH_DEV, VIEW_COUNT };
   uint64_t graph_version = 1;            // bumped by graph_changed() alone
@@ -582,6 +583,11 @@ struct TrgEngine {
   DevGraphUpload dev_up;   // csr_global and nstate in HBM (VIEW_UP_NODES, VIEW_UP_EDGES)
   Csr csr_stitched;        // tiled builds: this tile's rows of the stitched global graph
   int stitched_edges = 0;  // ... and their edge count (the edge arrays may still be in HBM only)
+  // the node offsets and the tile of the last stitch_assemble that went through (kept when the rows are voided: the
+  // tiled cost field judges its sources by them), and a count of such stitches, the stamp of what is built from the rows
+  std::vector<int32_t> stitch_node_off;
+  int stitch_tile = -1;
+  uint64_t stitch_serial = 0;
   float root_pos[2] = {0, 0};
   float local_root[2] = {0, 0};
   std::unordered_map<int, int> local_map;  // mirrors local trgStruct::nodes (iteration order)
@@ -620,6 +626,7 @@ struct TrgEngine {
   std::unique_ptr<ExchangeState> exchange;  // tiled builds: RCCL communicator and buffers of the native stitch
                                             // exchange, made by trg_engine_comm_init / comm_adopt
   std::unique_ptr<FieldBufs> field;  // cost field: work arrays and edge costs (cached per graph_version)
+  std::unique_ptr<TiledFieldBufs> tiled;  // cost field across tiles: the solve graph (per stitch) and its work arrays
   double field_delta_scale = 4.0;  // cost field: bucket width in mean edge costs (a measurement knob, see set_option)
   // The node map of trg_engine_cost_field_refresh: for every node of the current graph its id in the graph of the
   // retained cost-field solve, -1 for a node made since.  A solve starts it as the identity, update_graph composes
@@ -1842,7 +1849,8 @@ TrgStatus trg_engine_debug_map_index(TrgEngine *e, TrgKind map, float *x, float 
 
 #include "trg_engine_stitch.inc"
 #include "trg_engine_exchange.inc"
+#include "trg_engine_field_tiled.inc"
 
-// (here BfsBuffers, StitchBufs, Uploader, ExchangeState and FieldBufs are complete types)
+// (here BfsBuffers, StitchBufs, Uploader, ExchangeState, FieldBufs and TiledFieldBufs are complete types)
 TrgEngine::TrgEngine() = default;
 TrgEngine::~TrgEngine() = default;

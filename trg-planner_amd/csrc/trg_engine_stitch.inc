@@ -154,7 +154,15 @@ TrgStatus stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles, const int3
   out.cid.resize(g.V);
   for (int i = 0; i < g.V; ++i) out.cid[i] = node_offsets[tile] + i;  // global id of the row
   out.rowptr.assign(1, 0);
-  if (g.V == 0) return TRG_OK;
+  const auto stitched = [&] {  // this tile has rows of the global graph, with these offsets
+    e->stitch_node_off.assign(node_offsets, node_offsets + ntiles + 1);
+    e->stitch_tile = tile;
+    ++e->stitch_serial;
+  };
+  if (g.V == 0) {
+    stitched();
+    return TRG_OK;
+  }
   const size_t V = (size_t)g.V;
   if ((st = ensure_all(e, {{&sb.extra, (V + 1) * 4}, {&sb.fill, (V + 1) * 4}, {&sb.deg, (V + 1) * 4},
                            {&sb.rowptr_new, (V + 2) * 4}, {&sb.scan_tmp, (V / 2048 + 16) * 4}})) != TRG_OK)
@@ -186,6 +194,7 @@ TrgStatus stitch_assemble(TrgEngine *e, int32_t tile, int32_t ntiles, const int3
   e->stitched_edges = En;
   e->view_stamp[TrgEngine::VIEW_STITCH_DEV] = e->graph_version;
   HIPCHK(e, hipGetLastError());
+  stitched();
   return TRG_OK;
 }
 

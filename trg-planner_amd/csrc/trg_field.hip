@@ -76,6 +76,12 @@
 // width of 0 (all-zero weights) takes the warm control block, which starts at threshold 0, down the path of a cold one:
 // every push goes far, and next_threshold opens the bucket one word above the least live risk.
 //
+// Across tiles ("Cost fields across tiles"; trg_field_tiled.inc, included at the end): the field
+// of the stitched global graph, each rank relaxing its own rows plus mirrors of the other ends of its cross edges and
+// trading border keys between runs of the round kernels -- one more relaxation order to the same fixed point.  The
+// round kernels run on that rank's solve graph as they are; the tiled kernels build the graph, seed, publish, merge
+// and take the parents as least GLOBAL ids.
+//
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"
 
@@ -1160,5 +1166,7 @@ void launch_field_owned(const FieldDev &F, const FieldSets &S, int *owned, hipSt
   (void)hipMemsetAsync(owned, 0, (size_t)S.n * sizeof(int), s);
   hipLaunchKernelGGL(k_field_owned, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, S, owned);
 }
+
+#include "trg_field_tiled.inc"
 
 }  // namespace trg

@@ -1,0 +1,280 @@
+// trg_field_tiled.inc -- kernels of the cost field across tiles (DESIGN.md section 7, "Cost fields across tiles");
+// part of trg_field.hip, whose round kernels run on the solve graph built here as they are.
+//
+// The solve graph of a rank: its V local nodes, then its G ghosts -- the distinct other ends of this tile's cross
+// edges, in ascending global id.  The ghost table is a flag per GLOBAL node and the exclusive scan of the flags
+// (ghost_off), which sorts, uniques and looks up in one: the ghost index of global id g is ghost_off[g] where
+// ghost_flag[g] is set.  Local rows keep their order with columns as solve-graph indices; ghost j's row holds the
+// reverse of every cross edge that names it, with that edge's weight and length (one record serves both directions,
+// so the costs are the owner's bit for bit).  Ghosts carry the Invalid state in the solve graph's state array, so
+// k_field_edge_cost gives every edge INTO a ghost the skip marker: no relaxation here ever writes a ghost's key, it
+// only mirrors its owner's (k_tiled_merge).
+//
+// All kernels: wave64, bounds taken from the arguments, no scalar memory writes, nothing waits on another workgroup.
+
+namespace {
+
+// 16 bytes: what a rank tells the others about a border node whose key dropped
+struct TiledRec {
+  int field, gid;
+  unsigned long long key;
+};
+static_assert(sizeof(TiledRec) == 16 && sizeof(TiledRec) == FIELD_TILED_REC_BYTES, "record layout");
+
+// One thread per local row: flags the remote ends of its cross edges in the global table and the row as a border
+// row.  (Several rows may flag one ghost: every store writes the same word.)
+__global__ __launch_bounds__(THREADS) void k_tiled_mark(const int *__restrict__ rowptr, const int *__restrict__ col,
+                                                        int V, int lo, int Vg, int *ghost_flag, int *border_flag) {
+  for (int u = blockIdx.x * blockDim.x + threadIdx.x; u < V; u += gridDim.x * blockDim.x) {
+    int border = 0;
+    for (int k = rowptr[u], kend = rowptr[u + 1]; k < kend; ++k) {
+      const int c = col[k];
+      if (c >= 0 && c < Vg && (c < lo || c >= lo + V)) {
+        ghost_flag[c] = 1;
+        border = 1;
+      }
+    }
+    border_flag[u] = border;
+  }
+}
+
+// After the scans of both flag arrays: the ghosts' global ids and the border rows' local ids, in ascending order,
+// and the solve-graph-index -> global-id table with the solve graph's node states (a ghost: Invalid, see above).
+__global__ __launch_bounds__(THREADS) void k_tiled_tables(FieldTiled T, const int *__restrict__ state,
+                                                          const int *__restrict__ border_flag,
+                                                          const int *__restrict__ border_off) {
+  const int n_all = max(T.Vg, T.V);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_all; i += gridDim.x * blockDim.x) {
+    if (i < T.Vg && T.ghost_flag[i]) {
+      const int j = T.ghost_off[i];
+      if (j < T.G) {
+        T.gid_of[T.V + j] = i;
+        T.state[T.V + j] = FIELD_NODE_INVALID;
+      }
+    }
+    if (i < T.V) {
+      T.gid_of[i] = T.lo + i;
+      T.state[i] = state[i];
+      if (border_flag[i]) {
+        const int b = border_off[i];
+        if (b < T.B) T.border[b] = i;
+      }
+    }
+  }
+}
+
+// one thread per local row: the degree of every ghost = the cross edges that name it
+__global__ __launch_bounds__(THREADS) void k_tiled_ghost_deg(FieldTiled T, const int *__restrict__ rowptr,
+                                                             const int *__restrict__ col, int *ghost_deg) {
+  for (int u = blockIdx.x * blockDim.x + threadIdx.x; u < T.V; u += gridDim.x * blockDim.x)
+    for (int k = rowptr[u], kend = rowptr[u + 1]; k < kend; ++k) {
+      const int c = col[k];
+      if (c >= 0 && c < T.Vg && (c < T.lo || c >= T.lo + T.V)) atomicAdd(&ghost_deg[T.ghost_off[c]], 1);
+    }
+}
+
+// One thread per local row writes the row with solve-graph columns and, for each of its cross edges, the reverse
+// edge into the ghost's row (slots within a ghost's row by an atomic: their order decides nothing, the parent sweep
+// takes a minimum; E2 is the solve graph's edge count, the arrays' size).  Threads past the rows write the ghosts'
+// row pointers: rowptr[V + j] = E_local + ghost_row[j].
+__global__ __launch_bounds__(THREADS) void k_tiled_fill(FieldTiled T, const int *__restrict__ rowptr,
+                                                        const int *__restrict__ col, const float *__restrict__ w,
+                                                        const float *__restrict__ dist, int E_local, int E2,
+                                                        const int *__restrict__ ghost_row, int *ghost_fill,
+                                                        int *rowptr2, int *col2, float *w2, float *dist2) {
+  const int n_all = T.V + T.G + 1;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_all; i += gridDim.x * blockDim.x) {
+    if (i >= T.V) {
+      rowptr2[i] = E_local + ghost_row[i - T.V];
+      continue;
+    }
+    rowptr2[i] = rowptr[i];
+    for (int k = rowptr[i], kend = rowptr[i + 1]; k < kend; ++k) {
+      const int c = col[k];
+      w2[k] = w[k];
+      dist2[k] = dist[k];
+      if (c >= T.lo && c < T.lo + T.V) {
+        col2[k] = c - T.lo;
+      } else if (c >= 0 && c < T.Vg) {
+        const int j = T.ghost_off[c];
+        col2[k] = T.V + j;
+        const int slot = E_local + ghost_row[j] + atomicAdd(&ghost_fill[j], 1);
+        if (slot < E2) {
+          col2[slot] = i;
+          w2[slot] = w[k];
+          dist2[slot] = dist[k];
+        }
+      } else {
+        col2[k] = -1;  // (never: stitch_assemble range-checks its edges; k_field_edge_cost skips such a column)
+      }
+    }
+  }
+}
+
+// One thread per field, after k_field_init without sources: a field whose source is this rank's node starts there.
+__global__ void k_tiled_seed(FieldDev F, FieldSources S) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= F.m) return;
+  const int src = S.id[f];
+  if (src < 0 || src >= F.V) return;
+  const int item = f * F.V + src;
+  F.key[item] = 0ull;
+  const int slot = atomicAdd(&F.ctrl->c.n[0], 1);
+  F.q[0][slot] = item;  // (slot < m <= N)
+  atomicAdd(&F.ctrl->s.work, 1);
+}
+
+// Publish: over (field, border row) pairs, those whose key is below what this rank last published become records,
+// compacted with one atomic per wave.  `published` has m * B words, `rec` room for as many records.
+__global__ __launch_bounds__(THREADS) void k_tiled_publish(FieldDev F, FieldTiled T, unsigned long long *published,
+                                                           TiledRec *rec, int *n_rec) {
+  const int items = F.m * T.B;
+  const int n_iter = (items + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
+    bool news = false;
+    TiledRec r{};
+    if (i < items) {
+      const int f = i / T.B;
+      const int v = T.border[i - f * T.B];
+      const unsigned long long k = F.key[f * F.V + v];
+      news = k < published[i];
+      if (news) {
+        published[i] = k;
+        r.field = f;
+        r.gid = T.lo + v;
+        r.key = k;
+      }
+    }
+    const int slot = wave_reserve(news, n_rec);
+    if (news && slot < items) rec[slot] = r;
+  }
+}
+
+// Merge: one thread per gathered record.  A record of another rank that names one of this rank's ghosts lowers the
+// ghost's key to its owner's (only this thread writes the word: an owner publishes a node once per exchange) and
+// queues the ghost item in the live far pile at the current phase.  The threshold drops to 0, so that the next round
+// opens a bucket at the least merged cost: the rounds then run on as after a warm start.
+__global__ __launch_bounds__(THREADS) void k_tiled_merge(FieldDev F, FieldTiled T, const TiledRec *__restrict__ rec,
+                                                         int n_rec) {
+  const int fs = F.ctrl->s.far_sel;
+  const unsigned phase = F.ctrl->s.phase;
+  const int n_iter = (n_rec + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
+    bool push = false;
+    int item = 0;
+    if (i < n_rec) {
+      const TiledRec r = rec[i];
+      const bool own = r.gid >= T.lo && r.gid < T.lo + T.V;
+      if (!own && r.gid >= 0 && r.gid < T.Vg && r.field >= 0 && r.field < F.m && T.ghost_flag[r.gid]) {
+        const int j = T.ghost_off[r.gid];
+        if (j < T.G) {
+          item = r.field * F.V + T.V + j;
+          if (r.key < F.key[item]) {
+            F.key[item] = r.key;
+            F.stamp_far[item] = phase;
+            push = true;
+          }
+        }
+      }
+    }
+    const int slot = wave_reserve(push, &F.ctrl->c.nfar[fs]);
+    if (push) {
+      if (slot < F.N) F.far[fs][slot] = item;
+      else atomicOr(&F.ctrl->c.overflow, 1);
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) F.ctrl->s.thr = 0u;
+}
+
+// The parent sweep over the solve graph, ghost rows included: the least GLOBAL id u with an edge u -> v whose
+// extension of key[u] is key[v] (ghosts are not in id order among the solve-graph indices, hence the table).
+__global__ __launch_bounds__(THREADS) void k_tiled_parent(FieldDev F, FieldTiled T) {
+  const int sub = threadIdx.x & (GROUP - 1);
+  const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
+  const int ng = gridDim.x * blockDim.x / GROUP;
+  const int fbase = blockIdx.y * F.V;
+  for (int u = g0; u < F.V; u += ng) {
+    const unsigned long long ku = F.key[fbase + u];
+    if (ku == FIELD_KEY_NONE) continue;
+    const int gu = T.gid_of[u];
+    for (int k = F.rowptr[u] + sub, kend = F.rowptr[u + 1]; k < kend; k += GROUP) {
+      const float c = F.ec[k];
+      if (__float_as_uint(c) == FIELD_EDGE_SKIP) continue;
+      const int v = fbase + F.col[k];
+      if (key_extend(ku, c) == F.key[v]) atomicMin(&F.parent[v], gu);
+    }
+  }
+}
+
+// grid.y = field: this rank's own nodes only, m x V_local
+__global__ __launch_bounds__(THREADS) void k_tiled_output(FieldDev F, FieldTiled T, float *cost, int *hops,
+                                                          int *parent) {
+  const int fbase = blockIdx.y * F.V, obase = blockIdx.y * T.V;
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < T.V; v += gridDim.x * blockDim.x) {
+    const unsigned long long k = F.key[fbase + v];
+    const bool reached = k != FIELD_KEY_NONE;
+    cost[obase + v] = reached ? key_cost(k) : __builtin_huge_valf();
+    hops[obase + v] = reached ? (int)(unsigned)k : -1;
+    const int p = F.parent[fbase + v];
+    parent[obase + v] = p == INT_MAX ? -1 : p;
+  }
+}
+
+}  // namespace
+
+void launch_tiled_mark(const int *rowptr, const int *col, int V, int lo, int Vg, int *ghost_flag, int *border_flag,
+                       hipStream_t s) {
+  (void)hipMemsetAsync(ghost_flag, 0, ((size_t)Vg + 1) * sizeof(int), s);
+  if (V > 0)
+    hipLaunchKernelGGL(k_tiled_mark, dim3(field_blocks(V, THREADS)), dim3(THREADS), 0, s, rowptr, col, V, lo, Vg,
+                       ghost_flag, border_flag);
+}
+
+void launch_tiled_tables(const FieldTiled &T, const int *state, const int *border_flag, const int *border_off,
+                         const int *rowptr, const int *col, int *ghost_deg, hipStream_t s) {
+  hipLaunchKernelGGL(k_tiled_tables, dim3(field_blocks(std::max(T.Vg, T.V), THREADS)), dim3(THREADS), 0, s, T, state,
+                     border_flag, border_off);
+  (void)hipMemsetAsync(ghost_deg, 0, ((size_t)T.G + 1) * sizeof(int), s);
+  hipLaunchKernelGGL(k_tiled_ghost_deg, dim3(field_blocks(T.V, THREADS)), dim3(THREADS), 0, s, T, rowptr, col,
+                     ghost_deg);
+}
+
+void launch_tiled_fill(const FieldTiled &T, const int *rowptr, const int *col, const float *w, const float *dist,
+                       int E_local, int E2, const int *ghost_row, int *ghost_fill, int *rowptr2, int *col2,
+                       float *w2, float *dist2, hipStream_t s) {
+  (void)hipMemsetAsync(ghost_fill, 0, ((size_t)T.G + 1) * sizeof(int), s);
+  hipLaunchKernelGGL(k_tiled_fill, dim3(field_blocks(T.V + T.G + 1, THREADS)), dim3(THREADS), 0, s, T, rowptr, col, w,
+                     dist, E_local, E2, ghost_row, ghost_fill, rowptr2, col2, w2, dist2);
+}
+
+void launch_tiled_begin(const FieldDev &F, const FieldTiled &T, const FieldSources &local_sources, float delta,
+                        unsigned long long *published, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, local_sources,
+                     delta, false, (const unsigned long long *)nullptr);
+  hipLaunchKernelGGL(k_tiled_seed, dim3(1), dim3(FIELD_MAX_SOURCES), 0, s, F, local_sources);
+  (void)hipMemsetAsync(published, 0xFF, ((size_t)F.m * T.B + 1) * sizeof(unsigned long long), s);
+}
+
+void launch_tiled_publish(const FieldDev &F, const FieldTiled &T, unsigned long long *published, void *rec,
+                          int *n_rec, hipStream_t s) {
+  (void)hipMemsetAsync(n_rec, 0, sizeof(int), s);
+  if (T.B > 0)
+    hipLaunchKernelGGL(k_tiled_publish, dim3(field_blocks((long long)F.m * T.B, THREADS)), dim3(THREADS), 0, s, F, T,
+                       published, (TiledRec *)rec, n_rec);
+}
+
+void launch_tiled_merge(const FieldDev &F, const FieldTiled &T, const void *rec, int n_rec, hipStream_t s) {
+  if (n_rec > 0 && T.G > 0)
+    hipLaunchKernelGGL(k_tiled_merge, dim3(field_blocks(n_rec, THREADS)), dim3(THREADS), 0, s, F, T,
+                       (const TiledRec *)rec, n_rec);
+}
+
+void launch_tiled_finish(const FieldDev &F, const FieldTiled &T, float *cost, int *hops, int *parent, bool parents,
+                         hipStream_t s) {
+  if (parents)
+    hipLaunchKernelGGL(k_tiled_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s,
+                       F, T);
+  if (T.V > 0)
+    hipLaunchKernelGGL(k_tiled_output, dim3(field_blocks(T.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, cost, hops,
+                       parent);
+}

@@ -588,4 +588,43 @@ void launch_field_anchor_end(const FieldDev &F, int sweeps, unsigned long long *
 void launch_field_warm_start(const FieldDev &F, float delta, bool reset_parents, hipStream_t s,
                              const FieldModels *models = nullptr, bool risk = false);
 
+// ---- cost fields across tiles (trg_field_tiled.inc; DESIGN.md section 7, "Cost fields across tiles") ----------------
+// A rank's solve graph: its V local nodes (solve-graph index = local id) and then its G ghosts, the distinct other
+// ends of its cross edges in ascending global id.  ghost_flag / ghost_off (Vg + 1 words each) are a flag per global
+// node and its exclusive scan: the ghost index of global id g.  The solve runs the round kernels above on a FieldDev
+// whose V is V + G.
+struct FieldTiled {
+  int V, G, B;            // local nodes, ghosts, border rows (local nodes with a cross edge)
+  int lo, Vg;             // the global id of local node 0; nodes of the global graph
+  const int *ghost_flag, *ghost_off;
+  int *gid_of;            // V + G: solve-graph index -> global id
+  int *state;             // V + G: the local nodes' states, FIELD_NODE_INVALID for every ghost
+  int *border;            // B: the border rows' local ids, ascending
+};
+constexpr int FIELD_TILED_REC_BYTES = 16;  // (field, global id, key): what the ranks exchange
+// the stitched rows (global column ids) -> ghost_flag (zeroed here) and border_flag (V words)
+void launch_tiled_mark(const int *rowptr, const int *col, int V, int lo, int Vg, int *ghost_flag, int *border_flag,
+                       hipStream_t s);
+// after the scans of both flags (T.G, T.B known): T.gid_of, T.state, T.border, and ghost_deg (G + 1 words, zeroed here)
+void launch_tiled_tables(const FieldTiled &T, const int *state, const int *border_flag, const int *border_off,
+                         const int *rowptr, const int *col, int *ghost_deg, hipStream_t s);
+// after the scan of ghost_deg (ghost_row, G + 1 words): the solve graph's CSR, V + G + 1 row pointers and E2 = E_local +
+// ghost_row[G] edges
+void launch_tiled_fill(const FieldTiled &T, const int *rowptr, const int *col, const float *w, const float *dist,
+                       int E_local, int E2, const int *ghost_row, int *ghost_fill, int *rowptr2, int *col2,
+                       float *w2, float *dist2, hipStream_t s);
+// A pass begins: no item has a key but the fields' sources that are this rank's nodes (local_sources: a local id, or
+// -1), which are queued; nothing is published (m * B + 1 words).
+void launch_tiled_begin(const FieldDev &F, const FieldTiled &T, const FieldSources &local_sources, float delta,
+                        unsigned long long *published, hipStream_t s);
+// records (m * B of FIELD_TILED_REC_BYTES at most) of the border items whose key dropped below the published one;
+// *n_rec (zeroed here) counts them
+void launch_tiled_publish(const FieldDev &F, const FieldTiled &T, unsigned long long *published, void *rec,
+                          int *n_rec, hipStream_t s);
+// the gathered records of all ranks into this rank's ghosts; what improved is queued for launch_field_round
+void launch_tiled_merge(const FieldDev &F, const FieldTiled &T, const void *rec, int n_rec, hipStream_t s);
+// parents as least global ids (when asked for), then cost / hops / parent of the local nodes, m x T.V
+void launch_tiled_finish(const FieldDev &F, const FieldTiled &T, float *cost, int *hops, int *parent, bool parents,
+                         hipStream_t s);
+
 }  // namespace trg

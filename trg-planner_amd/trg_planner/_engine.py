@@ -60,6 +60,11 @@ class TrgFieldInfo(C.Structure):
                 ("host_syncs", C.c_int32), ("ms_device", C.c_double), ("ms_total", C.c_double)]
 
 
+class TrgTiledFieldInfo(C.Structure):
+    _fields_ = [("exchanges", C.c_int32), ("rounds", C.c_int32), ("ghosts", C.c_int32), ("border_nodes", C.c_int32),
+                ("records_sent", C.c_int64), ("ms_device", C.c_float), ("ms_total", C.c_float)]
+
+
 class TrgRouteInfo(C.Structure):
     _fields_ = [("num_nodes", C.c_int32), ("cost", C.c_float), ("path_length", C.c_float),
                 ("avg_risk", C.c_float)]
@@ -116,6 +121,7 @@ EXPORTS = [
     "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh", "trg_engine_cost_field_models",
     "trg_engine_risk_field_sets", "trg_engine_risk_field_refresh",
     "trg_engine_pose_links", "trg_engine_cost_field_seeded",
+    "trg_engine_tiled_cost_field", "trg_engine_stitch_ids",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -222,6 +228,8 @@ def load_library():
     L.trg_engine_cost_field_refresh.argtypes = [vp, ip, C.c_int32, fp, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, ip, ip,
                                                 C.POINTER(TrgFieldInfo)]
     L.trg_engine_risk_field_refresh.argtypes = L.trg_engine_cost_field_refresh.argtypes
+    L.trg_engine_tiled_cost_field.argtypes = [vp, C.c_int32, ip, fp, ip, ip, C.POINTER(TrgTiledFieldInfo)]
+    L.trg_engine_stitch_ids.argtypes = [vp, ip, ip, ip]
     L.trg_engine_fallback_reason.argtypes = [vp]
     L.trg_engine_fallback_reason.restype = C.c_char_p
     _lib = L
@@ -363,6 +371,33 @@ class Engine:
         nb, nc = C.c_int32(0), C.c_int32(0)
         self._chk(self.L.trg_engine_stitch_exchange(self.h, _f(c), cols, rows, C.byref(nb), C.byref(nc)))
         return nb.value, nc.value
+
+    # ---- cost fields across tiles ("Cost fields across tiles") ---------------------------
+    def global_ids(self):
+        """(this tile's first global id, its node count) of the current stitch."""
+        first, n, total = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._chk(self.L.trg_engine_stitch_ids(self.h, C.byref(first), C.byref(n), C.byref(total)))
+        return int(first.value), int(n.value)
+
+    def tiled_cost_fields(self, source_gids, parent=True):
+        """The cost fields of the global stitched graph from the global ids `source_gids`, for this tile's nodes: a
+        collective call, made by every rank of the communicator with the same sources after a stitch.  -> dict with
+        cost, hops (m x V_t), parent (global ids; None without `parent`), offset (this tile's first global id) and
+        info (TrgTiledFieldInfo).  tiled.concat_fields joins the ranks' results."""
+        src = np.ascontiguousarray(source_gids, dtype=np.int32).reshape(-1)
+        m = int(src.shape[0])
+        try:
+            offset, V = self.global_ids()
+        except TrgError:
+            offset, V = 0, 0  # (the solve itself reports, and announces, that there are no current rows)
+        rows = max(m, 1)
+        cost = np.empty((rows, V), np.float32)
+        hops = np.empty((rows, V), np.int32)
+        par = np.empty((rows, V), np.int32) if parent else None
+        info = TrgTiledFieldInfo()
+        self._chk(self.L.trg_engine_tiled_cost_field(self.h, m, _i(src), _f(cost), _i(hops),
+                                                     None if par is None else _i(par), C.byref(info)))
+        return dict(cost=cost, hops=hops, parent=par, offset=offset, info=info)
 
     def set_option(self, key, value):
         self._chk(self.L.trg_engine_set_option(self.h, str(key).encode(), str(value).encode()))

@@ -216,6 +216,32 @@ def concat_stitched(parts):
                 offsets=np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64))
 
 
+def concat_fields(parts):
+    """The ranks' Engine.tiled_cost_fields results, in tile order -> dict of m x V arrays cost, hops, parent (global
+    ids; None when a rank solved without parents) of the global stitched graph."""
+    par = None if any(p["parent"] is None for p in parts) else np.concatenate([p["parent"] for p in parts], 1)
+    return dict(cost=np.concatenate([p["cost"] for p in parts], 1), hops=np.concatenate([p["hops"] for p in parts], 1),
+                parent=par)
+
+
+def field_route(fields, k, target_gid):
+    """The route of field k to `target_gid` over concatenated parents (concat_fields): global ids from the field's
+    source to the target, [] when the target is unreached.  A host walk: what a multi-rank application plans with."""
+    hops, parent = fields["hops"][k], fields["parent"][k]
+    v = int(target_gid)
+    if hops[v] < 0:
+        return []
+    out = [v]
+    for _ in range(int(hops[v])):
+        v = int(parent[v])
+        if v < 0:
+            raise ValueError(f"the parents of field {k} do not lead from {int(target_gid)} to a source")
+        out.append(v)
+    if parent[v] != -1 or hops[v] != 0:
+        raise ValueError(f"the parents of field {k} do not lead from {int(target_gid)} to a source")
+    return out[::-1]
+
+
 # ---- reference implementation of the stitch rule in numpy (tests/tiled_oracle.py drives the CPU
 # oracle through it; the product path is stitch_device above) ------------------------------------------
 def cross_pairs(my_tile, records_per_tile, expand_dist):
