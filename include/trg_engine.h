@@ -175,6 +175,9 @@ typedef struct TrgStats {
   uint64_t stitch_gate_retries; /* trg_engine_stitch_cross calls that ran their edge selection a second time, after the
                                   host's libm decided slope gates the device could not call */
   uint64_t stitch_regrows;     /* trg_engine_stitch_exchange: times a record or edge buffer was too small and grew */
+  uint64_t start_discs_known;  /* device path: edge evaluations (of edge_evals_gpu) that did not evaluate the first disc
+                                  of their segment walk: it is the start node's own acceptance disc, whose outcome
+                                  and point count the sampling kept (option "known_start_disc") */
 } TrgStats;
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
@@ -295,7 +298,14 @@ TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size
  * (device BFS: deferred wireEdge evaluations pipelined behind the level loop on a second stream, one
  * batch per level -- default; 0: after the loop);
  * "tie_inplace" = "1" | "0" (device BFS: a nearest-node distance tie is settled for the affected slot alone on
- * the committed level -- off: the whole level is replayed on the host).  All modes give identical
+ * the committed level -- off: the whole level is replayed on the host);
+ * "known_start_disc" = "1" | "0" (device BFS: the first disc of a segment walk that starts at a node the level
+ * loop created -- trg.cpp:283 at i = 0, the node's position bit for bit -- is the disc that accepted the node as
+ * a sample, trg.cpp:398: same position, radius, threshold and map.  It cannot collide and its point count is
+ * kept per node, so the speculative parent edges and the deferred evaluations add that count and start their
+ * walk at the second disc -- default; 0: every disc is evaluated.  The root, nodes of host-replayed levels, and
+ * every evaluation outside the global build -- updates against the local map among them -- never use a kept
+ * count).  All modes give identical
  * graphs; the env var TRG_REPLAY=host sets the default.  Test hooks (never change results):
  * "debug_tie_every" = n (treat every n-th BFS level as tie-affected -> host level replay),
  * "debug_gate_margin" = x (widen the band of slope gates left to the host's libm),

@@ -117,29 +117,39 @@ __global__ __launch_bounds__(QW *WAVE, EDGE_WAVES_PER_SIMD) void k_calls_gather(
   if (B.call_status[at] != CALL_PENDING) return;
   const int a = B.call_n1[at], b = B.call_n2[at];
   float *rec = B.mid + (size_t)q * MID_STRIDE;
+  // the walk starts at node a: its acceptance disc is the walk's first one (B.ndisc; wave-uniform, kept scalar)
+  const int n0 = __builtin_amdgcn_readfirstlane(B.ndisc ? B.ndisc[a] : -1);
   const EdgeMidOut o = edge_gather(m, p, B.nx[a], B.ny[a], B.nz[a], B.nx[b], B.ny[b], B.nz[b],
-                                   lds.w[w], rec, ctr);
-  store_mid(rec, o);
+                                   lds.w[w], rec, ctr, n0);
+  store_mid(rec, o, n0);
 }
 
 __global__ __launch_bounds__(256) void k_calls_finish(BfsDev B, const int *list, int count,
                                                       const int *count_dev, DeviceCounters *ctr) {
-  __shared__ int wave_hits[4];
+  __shared__ int wave_hits[4], wave_known[4];
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (count_dev) count = min(count, *count_dev);
   const size_t at = (size_t)list[q < count ? q : 0];
   const bool live = q < count && B.call_status[at] == CALL_PENDING;
   const float *r = B.mid + (size_t)(live ? q : 0) * MID_STRIDE;
+  const int st_word = live ? __float_as_int(r[0]) : 0;
   const int h = wave_sum(live ? __float_as_int(r[MID_HITS]) : 0);
-  if (lane_id() == 0) wave_hits[threadIdx.x >> 6] = h;
+  const int kn = __popcll(ballot((st_word & MID_START_KNOWN) != 0));  // evaluations that took their first disc as known
+  if (lane_id() == 0) {
+    wave_hits[threadIdx.x >> 6] = h;
+    wave_known[threadIdx.x >> 6] = kn;
+  }
   __syncthreads();
   if (threadIdx.x == 0 && ctr) {
     const unsigned long long tot =
         (unsigned long long)(wave_hits[0] + wave_hits[1] + wave_hits[2] + wave_hits[3]);
     if (tot) atomicAdd(&ctr[blockIdx.x % COUNTER_SHARDS].edge_hits, tot);
+    const unsigned long long tk =
+        (unsigned long long)(wave_known[0] + wave_known[1] + wave_known[2] + wave_known[3]);
+    if (tk) atomicAdd(&ctr[blockIdx.x % COUNTER_SHARDS].start_known, tk);
   }
   if (!live) return;
-  int st = __float_as_int(r[0]);
+  int st = st_word & ~MID_START_KNOWN;
   float w = 0.0f;
   if ((st & EDGE_STATUS_MASK) == EDGE_OK) {
     float cov[3][3];

@@ -619,6 +619,7 @@ struct TrgEngine {
   bool keep_preclean = false;    // instrumentation: snapshot the graph before cleanGraph
   bool use_device_bfs = true;    // device-resident BFS (off: host replay)
   bool defer_overlap = true;     // deferred edge evaluations pipelined behind the level loop on a 2nd stream
+  bool known_start_disc = true;  // edge walks that start at a node the level loop created skip their first disc (BfsDev::ndisc)
   bool tail_overlap = true;      // after the loop: the creating edges' covariances beside the cleaned graph's copy to the host
   PlanScratch plan_scratch;  // the planner's search scratch (A* runs straight on csr_global, see plan_on_csr)
   std::unique_ptr<Uploader> uploader;  // host cloud -> HBM staging (upload_and_build): pinned slots, streams and events
@@ -652,6 +653,7 @@ struct TrgEngine {
   // map points inside the queries of the level kernels of the last device build (instrumentation;
   // counted per committed level, so discarded launches count nothing)
   uint64_t lv_hits_sample = 0, lv_hits_spec = 0;
+  uint64_t lv_start_known = 0;  // speculative parent edges of the last device build that took their first disc as known
   TrgStats stats{};
 
   // goal state (trg.h:121-126)
@@ -1138,7 +1140,7 @@ TrgStatus init_graph(TrgEngine *e, const float start_xyz[3], const TrgSampler *s
   }
   // (in the main stream: it is non-blocking, a plain memset would not be ordered with the kernels)
   HIPCHK(e, hipMemsetAsync(e->d_ctr, 0, COUNTER_SHARDS * sizeof(DeviceCounters), e->s_main));
-  e->lv_hits_sample = e->lv_hits_spec = 0;
+  e->lv_hits_sample = e->lv_hits_spec = e->lv_start_known = 0;
   if (!e->use_device_bfs) ensure_real_map(e);
   MapOrderSim sim_before;  // container history as of before this build (for the fallback)
   if (e->use_device_bfs) {
@@ -1193,7 +1195,7 @@ TrgStatus init_graph(TrgEngine *e, const float start_xyz[3], const TrgSampler *s
     HIPCHK(e, hipStreamSynchronize(e->s_main));
     HIPCHK(e, hipStreamSynchronize(e->s_edge));
     HIPCHK(e, hipMemset(e->d_ctr, 0, COUNTER_SHARDS * sizeof(DeviceCounters)));
-    e->lv_hits_sample = e->lv_hits_spec = 0;
+    e->lv_hits_sample = e->lv_hits_spec = e->lv_start_known = 0;
     e->nodes_sim = sim_before;
     ensure_real_map(e);
     reset_graph_global(e);  // (the abandoned attempt may have written the node arrays: clean_and_fetch)
@@ -1233,6 +1235,7 @@ TrgStatus set_option(TrgEngine *e, const char *key, const char *value) {
       {"replay", HOST_OR_DEVICE, &e->use_device_bfs},
       {"defer_overlap", ZERO_OR_ONE, &e->defer_overlap},
       {"tail_overlap", ZERO_OR_ONE, &e->tail_overlap},
+      {"known_start_disc", ZERO_OR_ONE, &e->known_start_disc},
       {"tie_inplace", BOOL, &e->tie_inplace},
       {"keep_preclean", BOOL, &e->keep_preclean},
       {"resolve_tickets", INT, &e->resolve_tickets},

@@ -45,11 +45,12 @@ static_assert(BFS_CTR_COUNT <= H_CLEAN_TOTALS && H_CLEAN_TOTALS + 2 <= H_ROUND2_
 // created nodes; the start stamp of the expansion in flight and the wall-clock ticks of all expansions so far
 // (k_level_sample / k_level_resolve); from S64_PHASES 1024 shards x 8 phases of cycles (profiling builds)
 enum : int {
+  S64_SPEC_KNOWN = STATS64_SPEC_KNOWN /* 4: the word in front of the block below, filled by launch_bfs_stats too */,
   S64_DEF_KEPT = 5, S64_MAX_SPIN, S64_MULTIPASS, S64_DRAWS, S64_SAMPLES, S64_DISC_HITS, S64_SPEC_HITS,
   S64_CANDIDATES, S64_PARENT_HITS, S64_EXPAND_START = STATS64_EXPAND_START, S64_EXPAND_TICKS = STATS64_EXPAND_TICKS,
   S64_PHASES = 16, S64_WORDS = 16 + 1024 * 8
 };
-static_assert(S64_PARENT_HITS < S64_EXPAND_START && S64_EXPAND_START < S64_EXPAND_TICKS && S64_EXPAND_TICKS < S64_PHASES,
+static_assert(S64_SPEC_KNOWN < S64_DEF_KEPT && S64_PARENT_HITS < S64_EXPAND_START && S64_EXPAND_START < S64_EXPAND_TICKS && S64_EXPAND_TICKS < S64_PHASES,
               "report_stats fetches the words in front of S64_PHASES");
 
 struct BfsBuffers {
@@ -57,7 +58,7 @@ struct BfsBuffers {
   FinDev F{};
   LevelSet lv[2];
   // the arrays behind B's views (the frontier pair swaps its views level by level)
-  DevArr nx, ny, nz, nstate, gcell, ncov, nexp, nhits, front0, front1, fxy0, fxy1;
+  DevArr nx, ny, nz, nstate, ndisc, gcell, ncov, nexp, nhits, front0, front1, fxy0, fxy1;
   DevArr mid, unc_list, unc_rec, mt_rec, ctrs, stats64, wg_state, c_cell, tl, scan_tmp, s3_scratch;
   DevArr call_n1, call_n2, call_status, call_w, call_dist, newid_of_call, call_slot;  // the call log
   // selection of the deferred calls that need evaluating: the index list; def_counts: round 2's count, then the
@@ -653,6 +654,11 @@ TrgStatus Build::replay_level(Level &lv) {
     HIPCHK(e, hipMemcpy(B.nstate + at, bb.hm_state.data() + at, n * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(B.ncov + at, new_cov.data(), n * sizeof(NodeCov), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(B.nhits + at, new_hits.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    // (their disc counts stay unknown: the void device commit numbered other samples with these ids)
+    if (B.ndisc) {
+      const std::vector<int> unknown(n, -1);
+      HIPCHK(e, hipMemcpy(B.ndisc + at, unknown.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    }
     launch_bfs_insert_nodes(B, V0, created, s);
   }
   if (!next_front.empty()) {
@@ -784,6 +790,15 @@ TrgStatus Build::allocate() {
   B.ny = (float *)bb.ny.p;
   B.nz = (float *)bb.nz.p;
   B.nstate = (int *)bb.nstate.p;
+  // per node: the map points inside its acceptance disc, the first disc of every walk that starts at it
+  // (edge_gather's n0).  -1 = unknown wherever the level loop's commit has not written: the root, and the nodes of
+  // a level the host replayed (replay_level sets them again, a void device commit may have written there)
+  B.ndisc = nullptr;
+  if (e->known_start_disc) {
+    if ((st = ensure_bytes(e, bb.ndisc, vcap * I)) != TRG_OK) return st;
+    B.ndisc = (int *)bb.ndisc.p;
+    HIPCHK(e, hipMemsetAsync(B.ndisc, 0xFF, vcap * I, s));
+  }
   B.vcap = (int)std::min<size_t>(vcap, 0x7FFFFFF0);
   B.gcell = (GridCell *)bb.gcell.p;
   B.ncov = (NodeCov *)bb.ncov.p;
@@ -1394,6 +1409,7 @@ TrgStatus Build::report_stats() {
   e->stats.edge_evals_gpu = s64[S64_CANDIDATES] + s64[S64_DEF_KEPT];  // speculative parent edges + deferred
   e->lv_hits_sample = s64[S64_DISC_HITS];
   e->lv_hits_spec = s64[S64_SPEC_HITS];
+  e->lv_start_known = s64[S64_SPEC_KNOWN];
   e->stats.bytes_spec_created = 12ull * s64[S64_PARENT_HITS];
   e->stats.ms_finalize_host = ms_since(t_fin);
   e->stats.bfs_levels = (uint64_t)levels;

@@ -127,17 +127,19 @@ void read_counters(TrgEngine *e) {
   std::vector<DeviceCounters> h(COUNTER_SHARDS);
   if (hipMemcpy(h.data(), e->d_ctr, COUNTER_SHARDS * sizeof(DeviceCounters),
                 hipMemcpyDeviceToHost) == hipSuccess) {
-    unsigned long long sh = 0, eh = 0, ph = 0, ties = 0;
+    unsigned long long sh = 0, eh = 0, ph = 0, ties = 0, known = 0;
     for (const DeviceCounters &c : h) {
       sh += c.sample_hits;
       eh += c.edge_hits;
       ph += c.spec_hits;
       ties += c.nn_ties;
+      known += c.start_known;
     }
     e->stats.bytes_sample_kernel = 12ull * (sh + e->lv_hits_sample);
     e->stats.bytes_edge_kernel = 12ull * eh;
     e->stats.bytes_spec_kernel = 12ull * (ph + e->lv_hits_spec);
     e->stats.map_nn_ties += ties;
+    e->stats.start_discs_known = known + e->lv_start_known;
   }
 }
 

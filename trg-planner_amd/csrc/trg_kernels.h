@@ -74,7 +74,8 @@ struct alignas(128) DeviceCounters {
   unsigned long long spec_hits;    // same, speculative parent edges (k_spec_edges)
   unsigned long long nn_ties;
   unsigned long long overflow;     // disc queries that used the large-disc fallback
-  unsigned long long pad[11];
+  unsigned long long start_known;  // deferred evaluations that took their walk's first disc as known (BfsDev::ndisc)
+  unsigned long long pad[10];
 };
 
 // ---- index build -------------------------------------------------------------------------------
@@ -195,8 +196,13 @@ struct alignas(16) SlotRec {
                    // new node; SLOT_TIE: the nearest pre-level node was not unique
   int status;      // speculative parent edge (candidates): EDGE_* code and flags
   float dist;      //   its length
-  float cov[6];    //   cov[0] = weight when w_given (set by the host), else unused: k_node_cov computes the covariance
-  int w_given;     //   1: the weight itself is stored (host re-evaluation after a map tie)
+  float cov[5];    //   cov[0] = weight when w_given (set by the host), else unused: k_node_cov computes the covariance
+  int ndisc;       // map points inside the sample's acceptance disc (k_level_sample): the commit's BfsDev::ndisc.
+                   // Written for class-2 slots ONLY (stale in every other slot) and read by the commit for slots that
+                   // create a node, which are class 2.  Invariant this rests on: a slot's class (low byte of cls) is
+                   // set once by k_level_sample and no repair changes it -- the fixers change z, nn0, the edge words and the
+                   // SLOT_TIE flag.  A repair that ever promotes a slot to a candidate must set this word (or -1).
+  int w_given;    //   1: the weight itself is stored (host re-evaluation after a map tie)
   int hits;        //   map points inside the edge's query radii (instrumentation)
 };
 enum : int { SLOT_CLS_MASK = 0xFF, SLOT_TIE = 0x100 };
@@ -204,10 +210,12 @@ struct alignas(16) NodeRec {  // per queued node of a level, 48 bytes
   int n_acc, n_draws;         // accepted samples, draws made
   int hits_sample, hits_spec; // map points inside its sampling discs / speculative-edge queries
   unsigned cand_lo, cand_hi;  // bit j: accepted sample j is a candidate
-  int pad1[2];
+  int spec_known;             // its speculative edges that took their first disc as known (k_level_spec)
+  int pad1;
   float px, py, pz;           // the node itself (k_level_spec: its speculative edges start here)
-  int pad2;
+  int pdisc;                  // ... and the map points inside its own acceptance disc (BfsDev::ndisc; -1: unknown)
 };
+static_assert(sizeof(SlotRec) == 64 && sizeof(NodeRec) == 48, "the level kernels address these records by 16-byte words");
 struct alignas(16) HashEnt {  // candidate hash of a level: node-grid cell -> candidate
   unsigned long long tagcell; // level tag << 32 | cell; entries of other levels count as empty
   int slot;
@@ -234,6 +242,9 @@ struct BfsDev {
   // node store (creation order) and its hash grid
   float *nx, *ny, *nz;
   int *nstate;
+  int *ndisc;  // per node: map points of the GLOBAL map inside the robot_size disc around it, when the node is a sample
+               // this build's level loop accepted (that disc did not collide: edge_gather's n0); -1 = unknown (the
+               // root, nodes a host-replayed level created); null: option known_start_disc=0
   NodeCov *ncov;
   int vcap;
   GridCell *gcell;
@@ -277,6 +288,7 @@ struct BfsDev {
 // Words of stats64 that time the expansion of every level on the device: k_level_sample's first workgroup
 // stamps the wall clock, the first resolve workgroup of the k_level_resolve behind it adds the ticks since.
 constexpr int STATS64_EXPAND_START = 14, STATS64_EXPAND_TICKS = 15;
+constexpr int STATS64_SPEC_KNOWN = 4;  // speculative parent edges that took their first disc as known (k_bfs_stats)
 
 struct FinDev {
   unsigned long long *ht_key;

@@ -498,6 +498,7 @@ __device__ float risk_weight(const float cov[3][3], int &clamped) {
 constexpr int MID_STRIDE = 24;
 constexpr int MID_HITS = 3;
 constexpr int MID_MOMENTS = 4;
+constexpr int MID_START_KNOWN = 1 << 8;  // flag in a mid record's status word, above every EDGE_* bit
 
 struct EdgeGeom {
   float dist, dirx, diry, cx, cy;
@@ -963,11 +964,16 @@ __device__ __forceinline__ void sweep_discs(const WaveTile &tile, int T, const f
 //                   (same box, same filter) and sums in the same order -- a lane's partial sums follow tile
 //                   order in the fast and in the general path alike, the reduction order is fixed -- so rec
 //                   gets bit for bit what FULL writes.  No segment walk, no counters.
+// n0 (wave-uniform): the number of map points in the robot_size disc around (x1, y1) when that disc is KNOWN not to
+// collide in this map, else -1.  The walk's first disc (i = 0, trg.cpp:283) sits at node1's position bit for bit,
+// and a node the level loop created passed exactly that isCollision call as a sample (trg.cpp:398) with the
+// count the sampling kernel kept (BfsDev::ndisc): the walk then adds n0 to the hits and starts at i = ds
+// (0 + ds == ds, the float the loop reaches anyway).  Every output is what the evaluated disc would have given.
 enum : int { GATHER_FULL = 0, GATHER_STATUS = 1, GATHER_MOMENTS = 2 };
 template <int MODE = GATHER_FULL>
 __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float x1, float y1,
                                   float z1, float x2, float y2, float z2, WaveTile &tile,
-                                  float *rec, DeviceCounters *ctr) {
+                                  float *rec, DeviceCounters *ctr, int n0 = -1) {
   const int lane = lane_id();
   EdgeMidOut o;
   o.n_pts = 0;
@@ -1032,8 +1038,16 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
     return o;
   }
 
-  unsigned long long hits = 0;
   const float ds = p.robot_size * 0.5f;
+  // the walk has a first disc (0 < dist) and its outcome is known: no collision, n0 points
+  // (wave-uniform like every input of the walk; said so, so that none of it takes a vector register)
+  const bool known =
+      __builtin_amdgcn_readfirstlane((MODE != GATHER_MOMENTS && n0 >= 0 && 0.0f < g.dist) ? 1 : 0) != 0;
+  // (o.hits is the sum's low 32 bits, so 32 bits carry it)
+  unsigned hits = known ? (unsigned)n0 : 0u;
+  const float walk0 = known ? ds : 0.0f;
+  // the walk's length as the scalar it is: its disc count K and the branches on it then stay on the scalar unit
+  const float wdist = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.dist)));
   // what the ellipse sweeps accumulate per lane: the moments, or only the counts
   typedef typename std::conditional<MODE == GATHER_STATUS, EllipseCounts, Moments>::type Gathered;
 
@@ -1046,8 +1060,10 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
     bool fits = true;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) q[k] = f2{0.0f, 0.0f};
-    for (float i = 0; i < g.dist; i += ds) {  // trg.cpp:283 (float accumulation is semantics)
-      if (K == KMAX) {
+    // (K counts the discs that are swept: a known first disc takes one of the KMAX places and is not among them)
+    const int kcap = known ? KMAX - 1 : KMAX;
+    for (float i = walk0; i < wdist; i += ds) {  // trg.cpp:283 (float accumulation is semantics)
+      if (K == kcap) {
         fits = false;
         break;
       }
@@ -1076,7 +1092,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
         case 4: sweep_discs<4>(tile, T, q, r2, cnt, kmn, kmx); break;
         case 5: sweep_discs<5>(tile, T, q, r2, cnt, kmn, kmx); break;
         case 6: sweep_discs<6>(tile, T, q, r2, cnt, kmn, kmx); break;
-        default: break;  // K == 0: zero-length edge, no disc (trg.cpp:283 never enters the loop)
+        default: break;  // K == 0: zero-length edge, no disc (trg.cpp:283 never enters the loop), or one known disc
       }
       if (TRG_EDGE_STAGE_CUT == 3) {  // + disc sweep (keep its results alive)
         o.status = EDGE_SEG + (cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4] + cnt[5] > 1000000) +
@@ -1088,7 +1104,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
       for (int k = 0; k < KMAX; ++k) {
         if (k < K) {
           const int n = cnt[k];
-          hits += (unsigned long long)n;
+          hits += (unsigned)n;
           bool col;
           if (n == 0) {
             col = true;  // trg.cpp:749-752
@@ -1155,7 +1171,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
         return o;
       }
       const int in_range = staged_in_range;  // counted over the whole box, before the capsule cut
-      hits += (unsigned long long)in_range;
+      hits += (unsigned)in_range;
       o.hits = (int)hits;
       o.n_pts = kept;
       if (in_range == 0) {
@@ -1175,7 +1191,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
   // general path: one disc at a time (long edges, oversized boxes, dense maps)
   // segment walk, trg.cpp:282-288 (float accumulation of i is part of the semantics)
   int guard = 0;
-  for (float i = 0; MODE != GATHER_MOMENTS && i < g.dist; i += ds) {
+  for (float i = walk0; MODE != GATHER_MOMENTS && i < wdist; i += ds) {
     const float qx = x1 + i * g.dirx;
     const float qy = y1 + i * g.diry;
     bool col;
@@ -1189,7 +1205,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
       n = d.n;
       col = disc_collides(d, p.collision_threshold);
     }
-    hits += (unsigned long long)n;
+    hits += (unsigned)n;
     if (col) {
       o.status = EDGE_SEG | g.uncertain;
       o.hits = (int)hits;
@@ -1223,7 +1239,7 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
     o.status = EDGE_OK;
     return o;
   }
-  hits += (unsigned long long)in_range;
+  hits += (unsigned)in_range;
   o.hits = (int)hits;
   if (in_range == 0) {
     o.status = EDGE_EMPTY | g.uncertain;
@@ -1238,11 +1254,18 @@ __device__ EdgeMidOut edge_gather(const MapView &m, const QueryParams &p, float 
   return o;
 }
 
-// lane 0 writes the 16-byte header of a mid record (edge_gather wrote the moments)
-__device__ __forceinline__ void store_mid(float *rec, const EdgeMidOut &o) {
+// whether an evaluation that was given n0 took its first disc as known: it got as far as the walk (no slope gate)
+// and the walk has a first disc (edge_gather's own condition, from what it returned)
+__device__ __forceinline__ bool edge_start_known(const EdgeMidOut &o, int n0) {
+  return n0 >= 0 && 0.0f < o.dist && (o.status & EDGE_STATUS_MASK) != EDGE_GATE;
+}
+
+// lane 0 writes the 16-byte header of a mid record (edge_gather wrote the moments); MID_START_KNOWN in the
+// status word: the evaluation took its first disc as known (k_calls_finish counts these and drops the bit)
+__device__ __forceinline__ void store_mid(float *rec, const EdgeMidOut &o, int n0 = -1) {
   if (lane_id() == 0) {
     float4 h;
-    h.x = __int_as_float(o.status);
+    h.x = __int_as_float(o.status | (edge_start_known(o, n0) ? MID_START_KNOWN : 0));
     h.y = __int_as_float(o.n_pts);
     h.z = o.dist;
     h.w = __int_as_float(o.hits);

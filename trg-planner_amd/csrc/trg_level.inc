@@ -114,6 +114,7 @@ struct LevelLds {
   float nd_x[LV_NODE_CAP], nd_y[LV_NODE_CAP];
   int nd_id[LV_NODE_CAP];
   int nd_n;
+  int pdisc;          // BfsDev::ndisc of the node being expanded
   int cand[LV_SMAX];  // class of every sample
 };
 
@@ -176,6 +177,9 @@ constexpr unsigned long long hsort_keep_min_mask(int K, int J) {
 // isCollision + nearest map point of TWO discs (one per half wave), candidates read from the block
 // tile; zb: this wave's hit buffer, SHCAP / 2 floats per half.  cnt = -1: this half's disc does not
 // fit the fast path (more than SHCAP / 2 hits), the caller evaluates it with the whole wave.
+// (The nearest-point tracking stays fused into every trial disc although only one draw in five -- a candidate --
+// needs it.  Taking it out and looking candidates up in a second pass after the classification was measured:
+// k_level_sample<4> 29.6 -> 32.9 us per launch, the build 0.33 ms slower; profiles/r20_known_queries_ab.txt.)
 __device__ Disc2 sample_tile_disc2(const MapView &m, const SampleLds &L, float *zb, float qx, float qy,
                                    float r, float h) {
   const int lane = lane_id();
@@ -306,6 +310,7 @@ __device__ Disc2 sample_tile_disc2(const MapView &m, const SampleLds &L, float *
 template <int NW>
 struct PureLds {
   float sx[LV_SMAX], sy[LV_SMAX], sz[LV_SMAX];
+  int sn[LV_SMAX];  // map points inside the accepted sample's disc (Disc2::n)
   int r_col[2][2 * NW];
   unsigned long long r_hits[NW];
   int r_ties[NW];
@@ -419,6 +424,7 @@ __device__ __forceinline__ void sample_pure_draws(const MapView &m, const QueryP
       P.sx[my_slot] = qx;
       P.sy[my_slot] = qy;
       P.sz[my_slot] = d.nn_z;
+      P.sn[my_slot] = d.n;
       if (d.nn_tie) {
         atomicAdd(&P.r_ties[w], 1);
         const int k = atomicAdd(&B.ctrs[BFS_CTR_NMAPTIE + mt_parity], 1);
@@ -479,6 +485,9 @@ __device__ __forceinline__ void sample_body(SampleSide<NW> &SS, const MapView &m
   const int gid = B.front_cur[node];
   const float2 pxy = B.fxy_cur[node];  // (= nx[gid], ny[gid]: no second round trip before the tile)
   const float px = pxy.x, py = pxy.y, pz = B.nz[gid];
+  // the node's own acceptance disc, the first disc of its edges' walks: loaded beside nz, parked in LDS for the
+  // node record at the end (no register through the sampling)
+  if (tid == 0) V.pdisc = B.ndisc ? B.ndisc[gid] : -1;
   const uint32_t id = (uint32_t)gid;
   if (tid == 0) {
     V.nd_n = 0;
@@ -595,6 +604,7 @@ __device__ __forceinline__ void sample_body(SampleSide<NW> &SS, const MapView &m
         float4 *rec = (float4 *)&B.slot_rec[slot];
         rec[0] = make_float4(qx, qy, acc ? P.sz[j] : 0.0f, d2);
         rec[1] = make_float4(__int_as_float(nn), __int_as_float(cls), __int_as_float(EDGE_GATE), 0.0f);
+        if ((cls & SLOT_CLS_MASK) == 2) B.slot_rec[slot].ndisc = P.sn[j];  // (only a candidate can become a node)
         B.c_outcome[slot] = 0;  // undecided (k_level_resolve polls the candidates' outcomes)
         V.cand[j] = cls & SLOT_CLS_MASK;
       }
@@ -615,7 +625,7 @@ __device__ __forceinline__ void sample_body(SampleSide<NW> &SS, const MapView &m
     int4 *nr = (int4 *)&B.node_rec[node];
     nr[0] = make_int4(n_acc, draws, (int)hits_node, 0);
     nr[1] = make_int4((int)(unsigned)cand_mask, (int)(unsigned)(cand_mask >> 32), 0, 0);
-    ((float4 *)nr)[2] = make_float4(px, py, pz, 0.0f);
+    ((float4 *)nr)[2] = make_float4(px, py, pz, __int_as_float(V.pdisc));
     if (ties_node && ctr) atomicAdd(&ctr[wg % COUNTER_SHARDS].nn_ties, (unsigned long long)ties_node);
     TL_MARK(tag, 1, node);
   }
@@ -689,9 +699,12 @@ __device__ __forceinline__ void spec_one(const MapView &m, const QueryParams &p,
                                          int parity, DeviceCounters *ctr, int tl_tag) {
   const int lane = lane_id();
   if (lane == 0) TL_MARK(tl_tag, 2, unit);
-  const EdgeMidOut o = edge_gather<GATHER_STATUS>(m, p, par.x, par.y, par.z, qx, qy, qz, tile, nullptr, ctr);
+  // (par.w: the parent's own disc count or -1, wave-uniform: a scalar register through the evaluation)
+  const int n0 = __builtin_amdgcn_readfirstlane(__float_as_int(par.w));
+  const EdgeMidOut o = edge_gather<GATHER_STATUS>(m, p, par.x, par.y, par.z, qx, qy, qz, tile, nullptr, ctr, n0);
   float *out = (float *)&B.slot_rec[slot];
   if (lane == 0) {
+    if (edge_start_known(o, n0)) atomicAdd(&B.node_rec[node].spec_known, 1);
     out[6] = __int_as_float(o.status);
     out[7] = o.dist;
     out[14] = __int_as_float(0);  // w_given
@@ -1220,7 +1233,8 @@ __device__ __forceinline__ void resolve_body(ResolveLds &R, const BfsDev &B, int
       const int4 nr = *(const int4 *)&B.node_rec[slot / S];  // n_acc draws hits_sample hits_spec
       const NodeRec &full = B.node_rec[slot / S];
       const int ncand = __popc(full.cand_lo) + __popc(full.cand_hi);
-      *(int4 *)&B.nexp[u] = make_int4(nr.x | (ncand << 8), nr.y, nr.z, nr.w);
+      // (n_acc and the candidates are at most LV_SMAX = 64, and so are the known start discs among them)
+      *(int4 *)&B.nexp[u] = make_int4(nr.x | (ncand << 8) | (full.spec_known << 16), nr.y, nr.z, nr.w);
     }
     if (created) {
       const int cell = bfs_cell_y(B, qy) * B.GW + bfs_cell_x(B, qx);
@@ -1388,6 +1402,7 @@ __device__ __forceinline__ void commit_role(CommitLds &C, const BfsDev &B, int m
     B.nz[id] = r0.z;
     B.nstate[id] = flag == 2 ? new_state : -1;
     B.nhits[id] = s3.w;  // map points inside the parent-edge queries (trg.cpp:425)
+    if (B.ndisc) B.ndisc[id] = s3.y;  // SlotRec::ndisc: the node is this sample, its acceptance disc held that many
     if (flag == 2) {  // what the weight of the creating edge still needs: w_given (then cov[0] is the weight) and
                       // the call.  The cov words of a slot without w_given are stale (k_level_spec does not write
                       // them) and are copied all the same -- one 16-byte store, no branch: k_node_cov overwrites
@@ -1452,10 +1467,11 @@ __global__ __launch_bounds__(RWV *WAVE, (MULTI || STEP3) ? RESOLVE_WAVES_PER_SIM
 // Statistics of the whole expansion, once after the level loop: every valid node was expanded exactly
 // once and left its draw / sample / hit counts in nexp; every created node the map points its parent
 // edge touched.  out[0..5] = draws, samples, hits of sampling discs, hits of speculative edges,
-// candidates, hits of the created nodes' parent edges.
+// candidates, hits of the created nodes' parent edges; stats64[STATS64_SPEC_KNOWN] += speculative edges whose first disc was known.
+constexpr int BFS_STATS_N = 7;
 __global__ __launch_bounds__(256) void k_bfs_stats(BfsDev B, int V, unsigned long long *out) {
-  __shared__ unsigned long long red[6][4];
-  unsigned long long a[6] = {0, 0, 0, 0, 0, 0};
+  __shared__ unsigned long long red[BFS_STATS_N][4];
+  unsigned long long a[BFS_STATS_N] = {0, 0, 0, 0, 0, 0, 0};
   for (int id = blockIdx.x * 256 + threadIdx.x; id < V; id += gridDim.x * 256) {
     if (B.nstate[id] != -1) {
       const int4 n = *(const int4 *)&B.nexp[id];
@@ -1463,20 +1479,24 @@ __global__ __launch_bounds__(256) void k_bfs_stats(BfsDev B, int V, unsigned lon
       a[1] += (unsigned long long)(n.x & 0xFF);
       a[2] += (unsigned long long)n.z;
       a[3] += (unsigned long long)n.w;
-      a[4] += (unsigned long long)((n.x >> 8) & 0x3FFFFF);
+      a[4] += (unsigned long long)((n.x >> 8) & 0xFF);
+      a[6] += (unsigned long long)((n.x >> 16) & 0xFF);
     }
     if (id > 0) a[5] += (unsigned long long)B.nhits[id];
   }
 #pragma unroll
-  for (int q = 0; q < 6; ++q) {
+  for (int q = 0; q < BFS_STATS_N; ++q) {
 #pragma unroll
     for (int msk = 32; msk >= 1; msk >>= 1) a[q] += __shfl_xor(a[q], msk);
     if (lane_id() == 0) red[q][threadIdx.x >> 6] = a[q];
   }
   __syncthreads();
-  if (threadIdx.x < 6) {
+  if (threadIdx.x < BFS_STATS_N) {
     const unsigned long long t = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-    if (t) atomicAdd(&out[threadIdx.x], t);
+    // where sum q goes: the six contiguous words the caller names, and the word of its own behind them
+    unsigned long long *const dst[BFS_STATS_N] = {&out[0], &out[1], &out[2], &out[3], &out[4], &out[5],
+                                                  &B.stats64[STATS64_SPEC_KNOWN]};
+    if (t) atomicAdd(dst[threadIdx.x], t);
   }
 }
 

@@ -97,7 +97,8 @@ class TrgStats(C.Structure):
         ("bfs_tie_fixups", C.c_uint64), ("bytes_spec_created", C.c_uint64),
         ("ms_rare_events", C.c_double), ("bfs_ticket_reruns", C.c_uint64),
         ("bfs_multipass_rows", C.c_uint64), ("ms_upload", C.c_double), ("presampled_nodes", C.c_uint64),
-        ("stitch_gate_retries", C.c_uint64), ("stitch_regrows", C.c_uint64)]
+        ("stitch_gate_retries", C.c_uint64), ("stitch_regrows", C.c_uint64),
+        ("start_discs_known", C.c_uint64)]
 
 
 # every symbol include/trg_engine.h declares (tests check that the library exports all of them)
