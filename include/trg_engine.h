@@ -706,8 +706,9 @@ TrgStatus trg_engine_risk_field_refresh(TrgEngine *e,
  * (TRG_ERR_INVALID_ARG), m x (nodes + ghosts) beyond the solver's 32-bit item index or no device memory
  * (TRG_ERR_CAPACITY), a queue overflow (TRG_ERR_DEVICE) -- is announced in the next count exchange: that rank returns
  * its error, every other rank TRG_ERR_DEVICE "another rank reported a failure", none waits.  TRG_ERR_DEVICE on every
- * rank at once when the exchanges do not converge.  Source sets, start costs, bounds, cost models, risk fields,
- * refresh and device-side routes are not offered for this call, and it leaves the retained single-engine solve alone. */
+ * rank at once when the exchanges do not converge.  Source sets and start costs are the call below; bounds, cost
+ * models, risk fields, refresh and device-side routes are not offered across tiles, and neither call touches the
+ * retained single-engine solve. */
 typedef struct TrgTiledFieldInfo {
   int32_t exchanges;     /* all-gather-v exchanges of both passes, the two that found no news included */
   int32_t rounds;        /* relaxation rounds of this rank that did work */
@@ -721,6 +722,55 @@ typedef struct TrgTiledFieldInfo {
 TrgStatus trg_engine_tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *source_gids,
     float *cost, int32_t *hops, int32_t *parent,   /* m x (this tile's nodes), any may be NULL */
     TrgTiledFieldInfo *info);                      /* may be NULL */
+/* Source sets across tiles ("Source sets across tiles"): m fields of the global stitched graph G
+ * in one collective solve, field k from EVERY entry of set k = set_gids[set_ptr[k] .. set_ptr[k + 1]) (GLOBAL ids;
+ * duplicates and Invalid nodes allowed), entry j at the start cost set_cost0[j] + 0.0f (set_cost0 == NULL: +0 each).
+ * Every rank calls it with the same arguments after a stitch that is still current.  Field k is exactly what
+ * trg_engine_cost_field_seeded defines, on G: the single-source field from a virtual node joined to every entry j of
+ * set k by an arc of that cost, these arcs exempt from the Invalid rule, hops counted from the members' level.  A ROOT
+ * is a member whose final cost is, bit for bit, its least start cost.  A rank receives its own V_t nodes' part (host
+ * memory, any may be NULL):
+ *   cost, hops, parent   m x V_t; parents are GLOBAL ids, the least global id among the tight predecessors one level
+ *                        up, -1 for roots and unreached nodes -- trg_engine_tiled_cost_field's rule
+ *   owner                m x V_t; of a root the least entry of set k naming it whose start-cost bits equal its cost,
+ *                        counted from set_ptr[k]; of every other reached node owner[parent], where the parent may be
+ *                        another rank's node; -1 where unreached
+ *   targets, n_targets   LOCAL ids of this tile, read on the device: cost_at, hops_at, owner_at are m x n_targets,
+ *                        so that a rank that needs its Frontier nodes only downloads nothing of V_t entries
+ *   owned                set_ptr[m] ints: how many of THIS tile's nodes each entry owns (the ranks' arrays sum to the
+ *                        global counts)
+ * With m sets of one entry each and no start costs, cost / hops / parent equal trg_engine_tiled_cost_field's from the
+ * same ids bit for bit.  The owners need the parents of every rank: the parent sweep runs whether `parent` is asked
+ * for or not, and then the ranks trade the owners of their border nodes -- each published once, when it is known --
+ * until an exchange without news; the result is a function of the global parent forest, not of the order.
+ * TRG_ERR_INVALID_ARG before any collective, the group still usable, for what every rank judges alike: no
+ * communicator; m outside [1, TRG_FIELD_BATCH_MAX]; NULL set_ptr or set_gids; set_ptr[0] != 0, a decreasing set_ptr
+ * or an empty set (the message names the set); a gid outside [0, nodes of G) (set and entry; where the stitch's
+ * offsets are known); a start cost that is NaN, negative (-0 is not) or infinite (set and entry); n_targets < 0, or
+ * n_targets > 0 with NULL targets.  A rank's own failure -- no current stitched rows, a target outside its tile
+ * (TRG_ERR_INVALID_ARG), an allocation (TRG_ERR_CAPACITY), a bad edge cost, a queue overflow -- is announced in the
+ * next count exchange, of the owner exchanges as well: that rank returns its error, its peers TRG_ERR_DEVICE "another
+ * rank reported a failure", nobody waits.  An owner loop that outlasts m x (border nodes of all ranks) + 2 exchanges
+ * ends with TRG_ERR_DEVICE on every rank at once.  Bounds, cost models, risk fields, refresh and device-side routes
+ * are not offered across tiles; the retained single-engine solve is left alone. */
+typedef struct TrgTiledSetInfo {
+  int32_t exchanges;           /* all-gather-v exchanges of passes 1 and 2, the two without news included */
+  int32_t owner_exchanges;     /* ... of the owner pass, the one without news included */
+  int32_t rounds;              /* relaxation rounds of this rank that did work */
+  int32_t ghosts;              /* distinct other ends of this tile's cross edges */
+  int32_t border_nodes;        /* this tile's nodes with a cross edge */
+  int32_t roots;               /* roots among this tile's nodes, over all fields */
+  int64_t records_sent;        /* key records this rank published */
+  int64_t owner_records_sent;  /* owner records this rank published */
+  float ms_device;             /* as TrgTiledFieldInfo's, the owner pass's own kernels included */
+  float ms_total;              /* host wall time */
+} TrgTiledSetInfo;
+TrgStatus trg_engine_tiled_cost_field_sets(TrgEngine *e, int32_t m,
+    const int32_t *set_ptr, const int32_t *set_gids, const float *set_cost0,   /* set_cost0 may be NULL */
+    float *cost, int32_t *hops, int32_t *parent, int32_t *owner,   /* m x (this tile's nodes), any may be NULL */
+    const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned,                                                /* set_ptr[m], may be NULL */
+    TrgTiledSetInfo *info);                                        /* may be NULL */
 /* The global ids of the current stitch: this tile's first global id, its node count and the global graph's.
  * TRG_ERR_INVALID_ARG without current stitched rows. */
 TrgStatus trg_engine_stitch_ids(TrgEngine *e, int32_t *first_gid, int32_t *num_nodes, int32_t *total_nodes);

@@ -5,12 +5,18 @@
 // exchange_allgatherv until an exchange carries no news from anybody.  The least fp32 fold over all walks is one
 // least fixed point that every relaxation order reaches (DESIGN.md section 2), and this is one more order; the two
 // passes of the single-engine solve (all edges, then tight edges only) are kept, each with its own exchange loop.
+// A solve starts from one source per field or from source sets with start costs ("Source sets across tiles"): the
+// members are seeded by the ranks that own them, and after the two passes a third loop of the same frame trades the
+// owners of the border nodes over the forest of the global parents.
 
 namespace {
 
 // rounds enqueued between two looks at the "work left" word (fewer than a single-engine solve's: a rank is
 // re-started once per exchange, mostly for a handful of rounds)
 constexpr int TILED_BATCH = 8;
+// jumping sweeps of the owner pass between two looks at the "moved" word
+constexpr int TILED_SWEEP_BATCH = 8;
+static_assert(FIELD_OWNER_SWEEPS_MAX % TILED_SWEEP_BATCH == 0, "the owner pass looks after whole batches");
 
 struct TiledFieldBufs {
   // the solve graph, built once per stitch: stamped with the graph version, the stitch and the cost model
@@ -26,25 +32,56 @@ struct TiledFieldBufs {
   // work arrays, per item (m x (V + G)), and per border item (m x B)
   DevArr key, q[2], far[2], stamp_near, stamp_far, parent, tight, ctrl;
   DevArr published, rec, n_rec, cost, hops, parent_out;
+  // a set solve: this rank's entries, the sets' offsets, owners per item, and the outputs at the targets
+  DevArr entries, set_ptr, owner, own_changed, owner_out, owned, targets, cost_at, hops_at, owner_at;
   Pinned<FieldState> h_state;
   Pinned<FieldEdgeStats> h_stats;
-  Pinned<int> h_n;  // [0] ghosts or records, [1] border rows
+  Pinned<int> h_n;  // [0] ghosts, records or a sweep's "moved" word, [1] border rows or roots
   Event t0, t1;
 };
 
-// One solve on its way: the request, the kernels' view, and what ends up in `info`.
+// One solve on its way: the request, the kernels' view, and what ends up in the caller's info.
 struct TiledRun {
   int32_t m;
-  const int32_t *source_gids;
+  const int32_t *source_gids;  // one source per field, or nullptr: a set solve
   float *cost;
   int32_t *hops, *parent;
-  TrgTiledFieldInfo *info;
+  // a set solve: the sets as the caller gave them (global ids) and what only a set solve puts out
+  const int32_t *set_ptr = nullptr, *set_gids = nullptr;
+  const float *set_cost0 = nullptr;
+  int32_t *owner = nullptr;
+  const int32_t *targets = nullptr;
+  int32_t n_targets = 0;
+  float *cost_at = nullptr;
+  int32_t *hops_at = nullptr, *owner_at = nullptr, *owned = nullptr;
   FieldDev F{};
   FieldSources local{};  // per field: the source as a local id where it is this rank's node, else -1
+  int n_entries = 0;     // a set solve: its entries whose member is this rank's node (tb.entries)
   int round = 0;         // of the current pass
-  int rounds = 0, exchanges = 0;
-  long long records = 0;
+  int rounds = 0, exchanges = 0, owner_exchanges = 0, roots = 0;
+  long long records = 0, owner_records = 0;
   double ms_device = 0.0;
+  bool sets() const { return set_ptr != nullptr; }
+};
+
+// This rank's status through a loop of exchanges.  A step is skipped once one has failed; the failure's status and
+// message are kept for the announcement in the next count exchange (exchange_after).
+struct TiledLocal {
+  TrgEngine *e;
+  TrgStatus st;
+  std::string msg;
+  TiledLocal(TrgEngine *e_, TrgStatus st_) : e(e_), st(st_), msg(e_->err) {}
+  template <typename Body>
+  void step(Body body) {
+    if (st != TRG_OK) return;
+    st = [&]() -> TrgStatus {
+      const TrgStatus r = body();
+      if (r != TRG_OK) return r;
+      HIPCHK(e, hipGetLastError());
+      return TRG_OK;
+    }();
+    if (st != TRG_OK) msg = e->err;
+  }
 };
 
 TrgStatus tiled_grow(TrgEngine *e, DevArr &a, size_t bytes) {
@@ -216,10 +253,45 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
   F.parent = tb.parent.as<int>();
   F.ctrl = tb.ctrl.as<FieldCtrl>();
   F.tight = nullptr;
-  for (int k = 0; k < run.m; ++k) {
-    const long long l = (long long)run.source_gids[k] - T.lo;
-    run.local.id[k] = l >= 0 && l < T.V ? (int)l : -1;
+  if (!run.sets()) {
+    for (int k = 0; k < run.m; ++k) {
+      const long long l = (long long)run.source_gids[k] - T.lo;
+      run.local.id[k] = l >= 0 && l < T.V ? (int)l : -1;
+    }
+    return TRG_OK;
   }
+  // A set solve.  Its targets are this tile's nodes; of the entries this rank seeds those whose member is its own
+  // node (work per entry and per target, none per node).
+  hipStream_t s = e->s_main;
+  for (int j = 0; j < run.n_targets; ++j)
+    if (run.targets[j] < 0 || run.targets[j] >= T.V)
+      return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field sets: target " + std::to_string(j) + " (" + std::to_string(run.targets[j]) +
+                                              ") is outside this tile's [0, " + std::to_string(T.V) + ")");
+  const int n_all = run.set_ptr[run.m];
+  std::vector<TiledEntry> mine;
+  for (int k = 0; k < run.m; ++k)
+    for (int j = run.set_ptr[k]; j < run.set_ptr[k + 1]; ++j) {
+      const long long l = (long long)run.set_gids[j] - T.lo;
+      if (l < 0 || l >= T.V) continue;
+      const float c0 = run.set_cost0 ? run.set_cost0[j] + 0.0f : 0.0f;
+      mine.push_back(TiledEntry{k, (int)l, j, float_bits(c0)});
+    }
+  run.n_entries = (int)mine.size();
+  const size_t nT = (size_t)run.m * (size_t)run.n_targets + 4;
+  if ((st = tiled_grow(e, tb.entries, (mine.size() + 1) * sizeof(TiledEntry))) != TRG_OK ||
+      (st = tiled_grow(e, tb.set_ptr, ((size_t)run.m + 2) * 4)) != TRG_OK || (st = tiled_grow(e, tb.owner, nN * 4)) != TRG_OK ||
+      (st = tiled_grow(e, tb.own_changed, FIELD_OWNER_SWEEPS_MAX * sizeof(int))) != TRG_OK ||
+      (st = tiled_grow(e, tb.owner_out, nO * 4)) != TRG_OK || (st = tiled_grow(e, tb.owned, ((size_t)n_all + 4) * 4)) != TRG_OK ||
+      (st = tiled_grow(e, tb.targets, ((size_t)run.n_targets + 4) * 4)) != TRG_OK)
+    return st;
+  for (DevArr *a : {&tb.cost_at, &tb.hops_at, &tb.owner_at})
+    if ((st = tiled_grow(e, *a, nT * 4)) != TRG_OK) return st;
+  HIPCHK(e, hipMemcpyAsync(tb.set_ptr.p, run.set_ptr, ((size_t)run.m + 1) * 4, hipMemcpyHostToDevice, s));
+  if (!mine.empty())
+    HIPCHK(e, hipMemcpyAsync(tb.entries.p, mine.data(), mine.size() * sizeof(TiledEntry), hipMemcpyHostToDevice, s));
+  if (run.n_targets > 0)
+    HIPCHK(e, hipMemcpyAsync(tb.targets.p, run.targets, (size_t)run.n_targets * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipStreamSynchronize(s));  // (`mine` goes out of scope)
   return TRG_OK;
 }
 
@@ -229,7 +301,7 @@ TrgStatus tiled_prepare(TrgEngine *e, const ExchangeState &x, TiledRun &run) {
   TiledFieldBufs &tb = *e->tiled;
   HIPCHK(e, tb.h_state.ensure(1));
   HIPCHK(e, tb.h_stats.ensure(1));
-  HIPCHK(e, tb.h_n.ensure(2));
+  HIPCHK(e, tb.h_n.ensure(4));
   HIPCHK(e, tb.t0.create());
   HIPCHK(e, tb.t1.create());
   TrgStatus st = tiled_graph(e, x);
@@ -257,6 +329,57 @@ TrgStatus tiled_rounds(TrgEngine *e, TiledRun &run) {
   return TRG_OK;
 }
 
+// The frame of every loop of exchanges, a pass's and the owner pass's.  Per exchange: `launches(exchanges, d_all,
+// gathered)` enqueues this rank's work -- what it does with the records gathered in the exchange before, then its
+// publish into tb.rec / tb.n_rec -- as a step of `mine`, timed from tb.t0 (recorded by the caller before the first)
+// to tb.t1; a failure of this rank is announced in the count exchange; the loop ends at the first exchange in which
+// no rank has news, where every rank reads the same counts and leaves.  One that has exchanged per_item x (m x B) +
+// slack times with news (B the global border count from the auxiliary words) ends with TRG_ERR_DEVICE on every rank
+// at once.  n_exchanges and n_records count what went through.
+template <typename Launches>
+TrgStatus tiled_exchanges(TrgEngine *e, ExchangeState &x, TiledRun &run, TiledLocal &mine, const std::string &what,
+                          long long per_item, long long slack, int &n_exchanges, long long &n_records,
+                          Launches launches) {
+  TiledFieldBufs &tb = *e->tiled;
+  const FieldTiled &T = tb.T;
+  hipStream_t s = e->s_main;
+  const bool work = run.F.N > 0;  // (a tile without nodes only takes part in the exchanges)
+  std::vector<long long> counts, words;
+  const void *d_all = nullptr;
+  long long gathered = 0;
+  for (int exchanges = 0;; ++exchanges) {
+    long long n = 0;
+    mine.step([&]() -> TrgStatus {
+      if (!work) return TRG_OK;
+      if (exchanges) HIPCHK(e, hipEventRecord(tb.t0, s));
+      if (const TrgStatus st = launches(exchanges, d_all, (int)gathered); st != TRG_OK) return st;
+      HIPCHK(e, hipEventRecord(tb.t1, s));
+      HIPCHK(e, hipMemcpyAsync(&tb.h_n[0], tb.n_rec.p, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipStreamSynchronize(s));
+      n = tb.h_n[0];
+      if (n < 0 || n > (long long)run.F.m * T.B) return e->fail(TRG_ERR_DEVICE, what + "bad record count");
+      return tiled_lap(e, run);
+    });
+    e->err = mine.msg;
+    void *all = nullptr;
+    const TrgStatus st = exchange_after(e, x, mine.st, tb.rec.p, n, T.B, FIELD_TILED_REC_BYTES, counts, words, &all);
+    if (st != TRG_OK) return st;
+    d_all = all;
+    ++n_exchanges;
+    n_records += n;
+    long long border = 0;
+    gathered = 0;
+    for (int k = 0; k < x.nranks; ++k) {
+      gathered += counts[k];
+      border += words[k];
+    }
+    if (gathered == 0) break;
+    if (exchanges >= per_item * run.F.m * border + slack) return e->fail(TRG_ERR_DEVICE, what + "the exchanges did not converge");
+    if (gathered > INT_MAX) return e->fail(TRG_ERR_CAPACITY, what + "too many records in one exchange");
+  }
+  return TRG_OK;
+}
+
 // One pass: the outer loop of local rounds, publish, exchange, merge, until an exchange in which no rank has news.
 // `local` is this rank's status so far; a failure of its own is announced in the next count exchange, and every
 // rank leaves the loop in the same exchange.
@@ -265,65 +388,28 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
   const FieldTiled &T = tb.T;
   FieldDev &F = run.F;
   hipStream_t s = e->s_main;
-  const bool work = F.N > 0;  // (a tile without nodes only takes part in the exchanges)
+  const bool work = F.N > 0;
   const float delta = tb.mean_cost > 0.0 ? (float)(e->field_delta_scale * tb.mean_cost) : 0.0f;
-  std::string local_msg = e->err;
-  // a step of this rank: skipped once one has failed, whose status and message are kept for the announcement
-  const auto step = [&](auto body) {
-    if (local != TRG_OK) return;
-    local = [&]() -> TrgStatus {
-      const TrgStatus st = body();
-      if (st != TRG_OK) return st;
-      HIPCHK(e, hipGetLastError());
-      return TRG_OK;
-    }();
-    if (local != TRG_OK) local_msg = e->err;
-  };
-  step([&]() -> TrgStatus {
+  TiledLocal mine(e, local);
+  mine.step([&]() -> TrgStatus {
     if (!work) return TRG_OK;
     F.tight = pass ? tb.tight.as<unsigned>() : nullptr;
     run.round = 0;
     HIPCHK(e, hipEventRecord(tb.t0, s));
-    launch_tiled_begin(F, T, run.local, delta, tb.published.as<unsigned long long>(), s);
+    launch_tiled_begin(F, T, run.local, run.sets() ? tb.entries.as<TiledEntry>() : nullptr, run.n_entries, delta,
+                       tb.published.as<unsigned long long>(), s);
     return TRG_OK;
   });
-  std::vector<long long> counts, words;
-  const void *d_all = nullptr;
-  long long gathered = 0;
-  for (int exchanges = 0;; ++exchanges) {
-    long long n = 0;
-    step([&]() -> TrgStatus {
-      if (!work) return TRG_OK;
-      if (exchanges) HIPCHK(e, hipEventRecord(tb.t0, s));
-      launch_tiled_merge(F, T, d_all, (int)gathered, s);
-      if (const TrgStatus st = tiled_rounds(e, run); st != TRG_OK) return st;
-      launch_tiled_publish(F, T, tb.published.as<unsigned long long>(), tb.rec.p, tb.n_rec.as<int>(), s);
-      HIPCHK(e, hipEventRecord(tb.t1, s));
-      HIPCHK(e, hipMemcpyAsync(&tb.h_n[0], tb.n_rec.p, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(e, hipStreamSynchronize(s));
-      n = tb.h_n[0];
-      if (n < 0 || n > (long long)F.m * T.B) return e->fail(TRG_ERR_DEVICE, "tiled cost field: bad record count");
-      return tiled_lap(e, run);
-    });
-    e->err = local_msg;
-    void *all = nullptr;
-    const TrgStatus st = exchange_after(e, x, local, tb.rec.p, n, T.B, FIELD_TILED_REC_BYTES, counts, words, &all);
-    if (st != TRG_OK) return st;
-    d_all = all;
-    ++run.exchanges;
-    run.records += n;
-    long long border = 0;
-    gathered = 0;
-    for (int k = 0; k < x.nranks; ++k) {
-      gathered += counts[k];
-      border += words[k];
-    }
-    if (gathered == 0) break;  // nobody has news: every rank reads the same counts and leaves here
-    // a key of a border item drops at most a few times per item in practice; the cap is the round cap's shape
-    if (exchanges >= 4 * (long long)F.m * border + 64)
-      return e->fail(TRG_ERR_DEVICE, "tiled cost field: the exchanges did not converge");
-    if (gathered > INT_MAX) return e->fail(TRG_ERR_CAPACITY, "tiled cost field: too many records in one exchange");
-  }
+  // a key of a border item drops at most a few times per item in practice; the cap is the round cap's shape
+  const TrgStatus st = tiled_exchanges(
+      e, x, run, mine, "tiled cost field: ", 4, 64, run.exchanges, run.records,
+      [&](int, const void *d_all, int gathered) -> TrgStatus {
+        launch_tiled_merge(F, T, d_all, gathered, s);
+        if (const TrgStatus r = tiled_rounds(e, run); r != TRG_OK) return r;
+        launch_tiled_publish(F, T, tb.published.as<unsigned long long>(), tb.rec.p, tb.n_rec.as<int>(), s);
+        return TRG_OK;
+      });
+  if (st != TRG_OK) return st;
   if (work) {
     run.rounds += tb.h_state->rounds;
     if (pass == 0) launch_field_cost_bits(F, tb.tight.as<unsigned>(), s);
@@ -332,23 +418,99 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
   return TRG_OK;
 }
 
+// The owner pass of a set solve, after its two passes (DESIGN.md section 7, "Source sets across tiles"): the third
+// use of the frame.  This rank: the parent sweep, the forest of the global parents with the local roots and the
+// ghosts as terminals, jumping sweeps until one moves nothing.  Then the loop: merge the gathered owner records into
+// the ghost items, every item takes its final ancestor's owner where that is known, publish the border items whose
+// owner became known -- each once, so m x B exchanges carry news at most, and one more ends the loop.
+TrgStatus tiled_owner_pass(TrgEngine *e, ExchangeState &x, TiledRun &run) {
+  TiledFieldBufs &tb = *e->tiled;
+  const FieldTiled &T = tb.T;
+  const FieldDev &F = run.F;
+  hipStream_t s = e->s_main;
+  int *owner = tb.owner.as<int>();
+  const int *anc = nullptr;
+  TiledLocal mine(e, TRG_OK);
+  mine.step([&]() -> TrgStatus {
+    if (F.N <= 0) return TRG_OK;
+    int *changed = tb.own_changed.as<int>();
+    HIPCHK(e, hipEventRecord(tb.t0, s));
+    launch_tiled_parents(F, T, s);
+    launch_tiled_forest_begin(F, T, tb.set_ptr.as<int>(), owner, changed, tb.n_rec.as<int>() + 1,
+                              tb.published.as<unsigned long long>(), s);
+    for (int sweeps = 0;;) {
+      for (int i = 0; i < TILED_SWEEP_BATCH; ++i, ++sweeps) launch_field_owner_sweep(F, sweeps, changed, s);
+      HIPCHK(e, hipGetLastError());
+      HIPCHK(e, hipMemcpyAsync(&tb.h_n[0], changed + sweeps - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipMemcpyAsync(&tb.h_n[1], tb.n_rec.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipStreamSynchronize(s));
+      anc = F.q[sweeps & 1];
+      if (tb.h_n[0] == 0) break;
+      if (sweeps >= FIELD_OWNER_SWEEPS_MAX) return e->fail(TRG_ERR_DEVICE, "tiled cost field sets: the owner pass's sweeps did not end");
+    }
+    run.roots = tb.h_n[1];
+    return TRG_OK;
+  });
+  return tiled_exchanges(e, x, run, mine, "tiled cost field sets: owner pass: ", 1, 2, run.owner_exchanges, run.owner_records,
+                         [&](int, const void *d_all, int gathered) -> TrgStatus {
+                           launch_tiled_owner_step(F, T, d_all, gathered, anc, owner, tb.published.as<unsigned long long>(),
+                                                   tb.rec.p, tb.n_rec.as<int>(), s);
+                           return TRG_OK;
+                         });
+}
+
 TrgStatus tiled_outputs(TrgEngine *e, TiledRun &run) {
   TiledFieldBufs &tb = *e->tiled;
   const FieldTiled &T = tb.T;
   hipStream_t s = e->s_main;
+  const int n_entries = run.sets() ? run.set_ptr[run.m] : 0;
+  if (run.owned) std::fill(run.owned, run.owned + n_entries, 0);  // (a tile without nodes owns none)
   if (run.F.N > 0 && T.V > 0) {
-    const size_t nO = (size_t)run.m * T.V;
+    const size_t nO = (size_t)run.m * T.V, nT = (size_t)run.m * (size_t)run.n_targets;
     HIPCHK(e, hipEventRecord(tb.t0, s));
-    launch_tiled_finish(run.F, T, tb.cost.as<float>(), tb.hops.as<int>(), tb.parent_out.as<int>(), run.parent != nullptr, s);
+    // (a set solve's parent sweep ran before its owner pass)
+    launch_tiled_finish(run.F, T, tb.cost.as<float>(), tb.hops.as<int>(), tb.parent_out.as<int>(),
+                        run.parent != nullptr && !run.sets(), s);
+    if (run.sets()) {
+      launch_tiled_owner_outputs(run.F, T, tb.set_ptr.as<int>(), tb.owner.as<int>(), n_entries,
+                                 run.owner ? tb.owner_out.as<int>() : nullptr, run.owned ? tb.owned.as<int>() : nullptr, s);
+      FieldSets S{};
+      S.owner = tb.owner.as<int>();
+      launch_field_gather(run.F, &S, tb.targets.as<int>(), run.n_targets, run.cost_at ? tb.cost_at.as<float>() : nullptr,
+                          run.hops_at ? tb.hops_at.as<int>() : nullptr, run.owner_at ? tb.owner_at.as<int>() : nullptr, s);
+    }
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipEventRecord(tb.t1, s));
     if (run.cost) HIPCHK(e, hipMemcpyAsync(run.cost, tb.cost.p, nO * sizeof(float), hipMemcpyDeviceToHost, s));
     if (run.hops) HIPCHK(e, hipMemcpyAsync(run.hops, tb.hops.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
     if (run.parent) HIPCHK(e, hipMemcpyAsync(run.parent, tb.parent_out.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (run.owner) HIPCHK(e, hipMemcpyAsync(run.owner, tb.owner_out.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (run.owned && n_entries) HIPCHK(e, hipMemcpyAsync(run.owned, tb.owned.p, (size_t)n_entries * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (nT) {
+      if (run.cost_at) HIPCHK(e, hipMemcpyAsync(run.cost_at, tb.cost_at.p, nT * sizeof(float), hipMemcpyDeviceToHost, s));
+      if (run.hops_at) HIPCHK(e, hipMemcpyAsync(run.hops_at, tb.hops_at.p, nT * sizeof(int), hipMemcpyDeviceToHost, s));
+      if (run.owner_at) HIPCHK(e, hipMemcpyAsync(run.owner_at, tb.owner_at.p, nT * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(e, hipStreamSynchronize(s));
     if (const TrgStatus st = tiled_lap(e, run); st != TRG_OK) return st;
   }
   return TRG_OK;
+}
+
+// The collective part of a solve whose arguments passed the checks that every rank makes alike: the two passes, a set
+// solve's owner pass, the outputs.  The owner pass always runs in a set solve: it is a collective, and whether it runs
+// must not hang on which outputs one rank asks for.
+TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
+  ExchangeState &x = *e->exchange;
+  TrgStatus local = tiled_prepare(e, x, run);
+  for (int pass = 0; pass < 2; ++pass) {
+    const TrgStatus st = tiled_pass(e, x, run, local, pass);
+    if (st != TRG_OK) return st;
+    local = TRG_OK;  // (a pass that returns TRG_OK had no failure of this rank left to announce)
+  }
+  if (run.sets())
+    if (const TrgStatus st = tiled_owner_pass(e, x, run); st != TRG_OK) return st;
+  return tiled_outputs(e, run);
 }
 
 TrgStatus tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *source_gids, float *cost, int32_t *hops,
@@ -365,21 +527,80 @@ TrgStatus tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *source_gids, 
       if (source_gids[k] < 0 || source_gids[k] >= e->stitch_node_off.back())
         return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: the source of field " + std::to_string(k) +
                                                 " is outside [0, " + std::to_string(e->stitch_node_off.back()) + ")");
-  ExchangeState &x = *e->exchange;
-  TiledRun run{m, source_gids, cost, hops, parent, info};
-  TrgStatus local = tiled_prepare(e, x, run);
-  for (int pass = 0; pass < 2; ++pass) {
-    const TrgStatus st = tiled_pass(e, x, run, local, pass);
-    if (st != TRG_OK) return st;
-    local = TRG_OK;  // (a pass that returns TRG_OK had no failure of this rank left to announce)
-  }
-  if (const TrgStatus st = tiled_outputs(e, run); st != TRG_OK) return st;
+  TiledRun run{m, source_gids, cost, hops, parent};
+  if (const TrgStatus st = tiled_solve(e, run); st != TRG_OK) return st;
   const FieldTiled &T = e->tiled->T;
   info->exchanges = run.exchanges;
   info->rounds = run.rounds;
   info->ghosts = T.G;
   info->border_nodes = T.B;
   info->records_sent = run.records;
+  info->ms_device = (float)run.ms_device;
+  info->ms_total = (float)ms_since(t_total);
+  return TRG_OK;
+}
+
+struct TiledSetArgs {
+  int32_t m;
+  const int32_t *set_ptr, *set_gids;
+  const float *set_cost0;
+  float *cost;
+  int32_t *hops, *parent, *owner;
+  const int32_t *targets;
+  int32_t n_targets;
+  float *cost_at;
+  int32_t *hops_at, *owner_at, *owned;
+};
+
+TrgStatus tiled_cost_field_sets(TrgEngine *e, const TiledSetArgs &a, TrgTiledSetInfo *info) {
+  const Clock::time_point t_total = Clock::now();
+  const std::string what = "tiled cost field sets: ";
+  // what every rank judges alike is refused before any collective
+  if (!e->exchange || !e->exchange->transport)
+    return e->fail(TRG_ERR_INVALID_ARG, what + "no communicator (trg_engine_comm_init)");
+  if (a.m < 1 || a.m > TRG_FIELD_BATCH_MAX)
+    return e->fail(TRG_ERR_INVALID_ARG, what + "m must be in [1, " + std::to_string(TRG_FIELD_BATCH_MAX) + "]");
+  if (!a.set_ptr || !a.set_gids) return e->fail(TRG_ERR_INVALID_ARG, what + "null set_ptr or set_gids");
+  if (a.set_ptr[0] != 0) return e->fail(TRG_ERR_INVALID_ARG, what + "set_ptr[0] must be 0");
+  for (int k = 0; k < a.m; ++k) {
+    if (a.set_ptr[k + 1] < a.set_ptr[k]) return e->fail(TRG_ERR_INVALID_ARG, what + "set_ptr decreases at set " + std::to_string(k));
+    if (a.set_ptr[k + 1] == a.set_ptr[k]) return e->fail(TRG_ERR_INVALID_ARG, what + "set " + std::to_string(k) + " is empty");
+  }
+  for (int k = 0; k < a.m; ++k)
+    for (int j = a.set_ptr[k]; j < a.set_ptr[k + 1]; ++j) {
+      const std::string where = "entry " + std::to_string(j - a.set_ptr[k]) + " of set " + std::to_string(k);
+      if (!e->stitch_node_off.empty() && (a.set_gids[j] < 0 || a.set_gids[j] >= e->stitch_node_off.back()))
+        return e->fail(TRG_ERR_INVALID_ARG, what + where + " (" + std::to_string(a.set_gids[j]) + ") is outside [0, " +
+                                                std::to_string(e->stitch_node_off.back()) + ")");
+      if (a.set_cost0) {
+        const float c = a.set_cost0[j];
+        if (c != c || c < 0.0f || c == __builtin_huge_valf())
+          return e->fail(TRG_ERR_INVALID_ARG, what + "the start cost of " + where + " is NaN, negative or infinite");
+      }
+    }
+  if (a.n_targets < 0 || (a.n_targets > 0 && !a.targets))
+    return e->fail(TRG_ERR_INVALID_ARG, what + "n_targets < 0, or targets is null with n_targets > 0");
+  TiledRun run{a.m, nullptr, a.cost, a.hops, a.parent};
+  run.set_ptr = a.set_ptr;
+  run.set_gids = a.set_gids;
+  run.set_cost0 = a.set_cost0;
+  run.owner = a.owner;
+  run.targets = a.targets;
+  run.n_targets = a.n_targets;
+  run.cost_at = a.cost_at;
+  run.hops_at = a.hops_at;
+  run.owner_at = a.owner_at;
+  run.owned = a.owned;
+  if (const TrgStatus st = tiled_solve(e, run); st != TRG_OK) return st;
+  const FieldTiled &T = e->tiled->T;
+  info->exchanges = run.exchanges;
+  info->owner_exchanges = run.owner_exchanges;
+  info->rounds = run.rounds;
+  info->ghosts = T.G;
+  info->border_nodes = T.B;
+  info->roots = run.roots;
+  info->records_sent = run.records;
+  info->owner_records_sent = run.owner_records;
   info->ms_device = (float)run.ms_device;
   info->ms_total = (float)ms_since(t_total);
   return TRG_OK;
@@ -406,6 +627,19 @@ TrgStatus trg_engine_tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *so
     TrgTiledFieldInfo *out = info ? info : &local;
     *out = TrgTiledFieldInfo{};
     return tiled_cost_field(e, m, source_gids, cost, hops, parent, out);
+  });
+}
+
+TrgStatus trg_engine_tiled_cost_field_sets(TrgEngine *e, int32_t m, const int32_t *set_ptr, const int32_t *set_gids,
+                                           const float *set_cost0, float *cost, int32_t *hops, int32_t *parent,
+                                           int32_t *owner, const int32_t *targets, int32_t n_targets, float *cost_at,
+                                           int32_t *hops_at, int32_t *owner_at, int32_t *owned, TrgTiledSetInfo *info) {
+  return entry(e, "tiled_cost_field_sets", DEVICE, [&] {
+    TrgTiledSetInfo local{};
+    TrgTiledSetInfo *out = info ? info : &local;
+    *out = TrgTiledSetInfo{};
+    return tiled_cost_field_sets(e, TiledSetArgs{m, set_ptr, set_gids, set_cost0, cost, hops, parent, owner, targets,
+                                                 n_targets, cost_at, hops_at, owner_at, owned}, out);
   });
 }
 

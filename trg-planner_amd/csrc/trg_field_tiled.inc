@@ -10,6 +10,10 @@
 // k_field_edge_cost gives every edge INTO a ghost the skip marker: no relaxation here ever writes a ghost's key, it
 // only mirrors its owner's (k_tiled_merge).
 //
+// A set solve ("Source sets across tiles") adds the seeding of this rank's own entries (k_tiled_seed_sets) and, after
+// the parent sweep, the owner pass: k_tiled_forest_begin, the jumping sweeps of trg_field.hip, then per exchange
+// k_tiled_owner_merge / _resolve / _publish; k_tiled_output_owner and k_tiled_owned write what the rank puts out.
+//
 // All kernels: wave64, bounds taken from the arguments, no scalar memory writes, nothing waits on another workgroup.
 
 namespace {
@@ -124,6 +128,42 @@ __global__ void k_tiled_seed(FieldDev F, FieldSources S) {
   atomicAdd(&F.ctrl->s.work, 1);
 }
 
+// Source sets across tiles (DESIGN.md section 7, "Source sets across tiles"): one thread per entry of this rank's entry
+// table -- the entries of all sets whose member is this rank's node, which the host splits off per call; a member that
+// is a ghost here is seeded by its owner and mirrored like any key.  k_field_seed<true>'s rule with the GLOBAL entry
+// index in the member mark, so that "the least entry" is the same on every rank.  Pass 1: the item's key is the least
+// of its entries' start costs (atomicMin), queued once.  Pass 2 (F.tight, pass 1's cost bits): only an entry whose
+// start cost is the item's least cost seeds it -- a root, whose key (c0, 0) is below every tight extension (hops >= 1),
+// so no relaxation pushes or stamps it and its mark stays.
+__global__ __launch_bounds__(THREADS) void k_tiled_seed_sets(FieldDev F, const TiledEntry *__restrict__ ent, int n) {
+  const int n_iter = (n + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
+    bool first = false;
+    int item = 0;
+    if (i < n) {
+      const TiledEntry t = ent[i];
+      if (t.field >= 0 && t.field < F.m && t.node >= 0 && t.node < F.V && t.entry >= 0) {
+        item = t.field * F.V + t.node;
+        const unsigned long long k0 = (unsigned long long)t.cost0 << 32;
+        if (!F.tight) {
+          atomicMin(&F.key[item], k0);
+          first = atomicMin(&F.stamp_near[item], FIELD_MEMBER | t.entry) >= 0;
+        } else if (t.cost0 == F.tight[item]) {
+          F.key[item] = k0;  // (every entry that gets here writes this word)
+          first = atomicMin(&F.stamp_near[item], FIELD_MEMBER | t.entry) >= 0;
+        }
+      }
+    }
+    const unsigned long long mk = ballot(first);
+    const int slot = wave_reserve(first, &F.ctrl->c.n[0]);
+    if (mk && lane_id() == __ffsll(mk) - 1) atomicAdd(&F.ctrl->s.work, __popcll(mk));
+    if (first) {
+      if (slot < F.N) F.q[0][slot] = item;
+      else atomicOr(&F.ctrl->c.overflow, 1);
+    }
+  }
+}
+
 // Publish: over (field, border row) pairs, those whose key is below what this rank last published become records,
 // compacted with one atomic per wave.  `published` has m * B words, `rec` room for as many records.
 __global__ __launch_bounds__(THREADS) void k_tiled_publish(FieldDev F, FieldTiled T, unsigned long long *published,
@@ -220,6 +260,136 @@ __global__ __launch_bounds__(THREADS) void k_tiled_output(FieldDev F, FieldTiled
   }
 }
 
+// ---- the owner pass across seams (DESIGN.md section 7, "Source sets across tiles") ---------------------------------
+
+// grid.y = field, over the solve graph's items: the first ancestor of every item in the forest of k_tiled_parent's
+// GLOBAL parents, into F.q[0], and the owners known before any exchange.  A local root (by its mark) is its own
+// ancestor and knows its owner, the mark's entry counted from its set's first; a ghost with a key is its own ancestor
+// too -- a terminal, whose owner only the rank that owns the node knows; every other item with a key points at the
+// solve-graph item of its parent, a local node or a ghost.  *n_roots counts the roots, one atomic per wave.
+__global__ __launch_bounds__(THREADS) void k_tiled_forest_begin(FieldDev F, FieldTiled T,
+                                                                const int *__restrict__ set_ptr, int *owner,
+                                                                int *n_roots) {
+  const int fbase = blockIdx.y * F.V;
+  const int e0 = set_ptr[blockIdx.y];
+  int *anc = F.q[0];
+  const int n_iter = (F.V + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, v = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, v += gridDim.x * blockDim.x) {
+    bool root = false;
+    if (v < F.V) {
+      const int i = fbase + v;
+      int a = -1, o = -1;
+      if (F.key[i] != FIELD_KEY_NONE) {
+        const int mark = F.stamp_near[i];
+        if (v >= T.V) {
+          a = i;
+        } else if (mark < 0) {
+          a = i;
+          o = (mark & INT_MAX) - e0;
+          root = true;
+        } else {
+          const int p = F.parent[i];
+          if (p >= T.lo && p < T.lo + T.V) {
+            a = fbase + (p - T.lo);
+          } else if (p >= 0 && p < T.Vg && T.ghost_flag[p]) {
+            const int j = T.ghost_off[p];
+            if (j < T.G) a = fbase + T.V + j;
+          }
+        }
+      }
+      anc[i] = a;
+      owner[i] = o;
+    }
+    const unsigned long long mk = ballot(root);
+    if (mk && lane_id() == __ffsll(mk) - 1) atomicAdd(n_roots, __popcll(mk));
+  }
+}
+
+// One thread per gathered owner record (field, global id, owner in the key word): a record of another rank that names
+// one of this rank's ghosts gives the ghost item its owner.  An owner publishes an item once, so one thread writes
+// the word; only ghost items are written, as in k_tiled_merge.
+__global__ __launch_bounds__(THREADS) void k_tiled_owner_merge(FieldDev F, FieldTiled T,
+                                                               const TiledRec *__restrict__ rec, int n_rec, int *owner) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += gridDim.x * blockDim.x) {
+    const TiledRec r = rec[i];
+    const bool own = r.gid >= T.lo && r.gid < T.lo + T.V;
+    if (!own && r.gid >= 0 && r.gid < T.Vg && r.field >= 0 && r.field < F.m && T.ghost_flag[r.gid]) {
+      const int j = T.ghost_off[r.gid];
+      if (j < T.G) owner[r.field * F.V + T.V + j] = (int)(unsigned)r.key;
+    }
+  }
+}
+
+// One gather over the items: an item without an owner takes its last ancestor's once that is known.  `anc` is final
+// (the sweeps ended), an item that is read here is its own ancestor and is not written here.
+__global__ __launch_bounds__(THREADS) void k_tiled_owner_resolve(const int *__restrict__ anc, int *owner, int N) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
+    const int a = anc[i];
+    if (a < 0 || a >= N || a == i || owner[i] >= 0) continue;
+    const int o = owner[a];
+    if (o >= 0) owner[i] = o;
+  }
+}
+
+// Publish: over (field, border row) pairs, those whose owner is known and not yet published become records, compacted
+// with one atomic per wave.  `published` has m * B words, all ones until the item is published; `rec` room for as
+// many records.
+__global__ __launch_bounds__(THREADS) void k_tiled_owner_publish(FieldDev F, FieldTiled T,
+                                                                 const int *__restrict__ owner,
+                                                                 unsigned long long *published, TiledRec *rec,
+                                                                 int *n_rec) {
+  const int items = F.m * T.B;
+  const int n_iter = (items + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
+    bool news = false;
+    TiledRec r{};
+    if (i < items) {
+      const int f = i / T.B;
+      const int v = T.border[i - f * T.B];
+      const int o = owner[f * F.V + v];
+      news = o >= 0 && published[i] != 0ull;
+      if (news) {
+        published[i] = 0ull;
+        r.field = f;
+        r.gid = T.lo + v;
+        r.key = (unsigned long long)(unsigned)o;
+      }
+    }
+    const int slot = wave_reserve(news, n_rec);
+    if (news && slot < items) rec[slot] = r;
+  }
+}
+
+// grid.y = field: the owners of this rank's own nodes, m x V_local
+__global__ __launch_bounds__(THREADS) void k_tiled_output_owner(FieldDev F, FieldTiled T,
+                                                                const int *__restrict__ owner, int *out) {
+  const int fbase = blockIdx.y * F.V, obase = blockIdx.y * T.V;
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < T.V; v += gridDim.x * blockDim.x)
+    out[obase + v] = owner[fbase + v];
+}
+
+// grid.y = field: a histogram of the owners of this rank's own nodes (k_field_owned's shape, the ghosts left out: the
+// rank that owns a node counts it), one atomicAdd per wave and distinct owner among its lanes
+__global__ __launch_bounds__(THREADS) void k_tiled_owned(FieldDev F, FieldTiled T, const int *__restrict__ set_ptr,
+                                                         const int *__restrict__ owner, int n_entries, int *owned) {
+  const int fbase = blockIdx.y * F.V;
+  const int e0 = set_ptr[blockIdx.y];
+  const int room = min(set_ptr[blockIdx.y + 1], n_entries) - e0;
+  const int n_iter = (T.V + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, v = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, v += gridDim.x * blockDim.x) {
+    int o = v < T.V ? owner[fbase + v] : -1;
+    if (o >= room) o = -1;  // (never: an owner is an entry of its field's set)
+    unsigned long long rest = ballot(o >= 0);
+    while (rest) {  // (wave-uniform)
+      const int leader = __ffsll(rest) - 1;
+      const int lo = __shfl(o, leader);
+      const unsigned long long same = ballot(o == lo);
+      if (lane_id() == leader) atomicAdd(&owned[e0 + lo], __popcll(same));
+      rest &= ~same;
+    }
+  }
+}
+
 }  // namespace
 
 void launch_tiled_mark(const int *rowptr, const int *col, int V, int lo, int Vg, int *ghost_flag, int *border_flag,
@@ -247,11 +417,15 @@ void launch_tiled_fill(const FieldTiled &T, const int *rowptr, const int *col, c
                      dist, E_local, E2, ghost_row, ghost_fill, rowptr2, col2, w2, dist2);
 }
 
-void launch_tiled_begin(const FieldDev &F, const FieldTiled &T, const FieldSources &local_sources, float delta,
-                        unsigned long long *published, hipStream_t s) {
+void launch_tiled_begin(const FieldDev &F, const FieldTiled &T, const FieldSources &local_sources,
+                        const TiledEntry *entries, int n_entries, float delta, unsigned long long *published,
+                        hipStream_t s) {
   hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, local_sources,
                      delta, false, (const unsigned long long *)nullptr);
-  hipLaunchKernelGGL(k_tiled_seed, dim3(1), dim3(FIELD_MAX_SOURCES), 0, s, F, local_sources);
+  if (!entries) hipLaunchKernelGGL(k_tiled_seed, dim3(1), dim3(FIELD_MAX_SOURCES), 0, s, F, local_sources);
+  else if (n_entries > 0)
+    hipLaunchKernelGGL(k_tiled_seed_sets, dim3(field_blocks(n_entries, THREADS)), dim3(THREADS), 0, s, F, entries,
+                       n_entries);
   (void)hipMemsetAsync(published, 0xFF, ((size_t)F.m * T.B + 1) * sizeof(unsigned long long), s);
 }
 
@@ -269,12 +443,45 @@ void launch_tiled_merge(const FieldDev &F, const FieldTiled &T, const void *rec,
                        (const TiledRec *)rec, n_rec);
 }
 
+void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s) {
+  hipLaunchKernelGGL(k_tiled_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s, F,
+                     T);
+}
+
 void launch_tiled_finish(const FieldDev &F, const FieldTiled &T, float *cost, int *hops, int *parent, bool parents,
                          hipStream_t s) {
-  if (parents)
-    hipLaunchKernelGGL(k_tiled_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s,
-                       F, T);
+  if (parents) launch_tiled_parents(F, T, s);
   if (T.V > 0)
     hipLaunchKernelGGL(k_tiled_output, dim3(field_blocks(T.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, cost, hops,
                        parent);
+}
+
+void launch_tiled_forest_begin(const FieldDev &F, const FieldTiled &T, const int *set_ptr, int *owner, int *changed,
+                               int *n_roots, unsigned long long *published, hipStream_t s) {
+  (void)hipMemsetAsync(changed, 0, FIELD_OWNER_SWEEPS_MAX * sizeof(int), s);
+  (void)hipMemsetAsync(n_roots, 0, sizeof(int), s);
+  (void)hipMemsetAsync(published, 0xFF, ((size_t)F.m * T.B + 1) * sizeof(unsigned long long), s);
+  hipLaunchKernelGGL(k_tiled_forest_begin, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, set_ptr,
+                     owner, n_roots);
+}
+
+void launch_tiled_owner_step(const FieldDev &F, const FieldTiled &T, const void *rec_in, int n_in, const int *anc,
+                             int *owner, unsigned long long *published, void *rec, int *n_rec, hipStream_t s) {
+  if (n_in > 0 && T.G > 0)
+    hipLaunchKernelGGL(k_tiled_owner_merge, dim3(field_blocks(n_in, THREADS)), dim3(THREADS), 0, s, F, T,
+                       (const TiledRec *)rec_in, n_in, owner);
+  hipLaunchKernelGGL(k_tiled_owner_resolve, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, anc, owner, F.N);
+  (void)hipMemsetAsync(n_rec, 0, sizeof(int), s);
+  if (T.B > 0)
+    hipLaunchKernelGGL(k_tiled_owner_publish, dim3(field_blocks((long long)F.m * T.B, THREADS)), dim3(THREADS), 0, s,
+                       F, T, owner, published, (TiledRec *)rec, n_rec);
+}
+
+void launch_tiled_owner_outputs(const FieldDev &F, const FieldTiled &T, const int *set_ptr, const int *owner,
+                                int n_entries, int *owner_out, int *owned, hipStream_t s) {
+  if (owned) (void)hipMemsetAsync(owned, 0, (size_t)n_entries * sizeof(int), s);
+  if (T.V <= 0) return;
+  const dim3 grid(field_blocks(T.V, THREADS), F.m);
+  if (owner_out) hipLaunchKernelGGL(k_tiled_output_owner, grid, dim3(THREADS), 0, s, F, T, owner, owner_out);
+  if (owned) hipLaunchKernelGGL(k_tiled_owned, grid, dim3(THREADS), 0, s, F, T, set_ptr, owner, n_entries, owned);
 }

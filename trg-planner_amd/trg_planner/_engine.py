@@ -65,6 +65,12 @@ class TrgTiledFieldInfo(C.Structure):
                 ("records_sent", C.c_int64), ("ms_device", C.c_float), ("ms_total", C.c_float)]
 
 
+class TrgTiledSetInfo(C.Structure):
+    _fields_ = [("exchanges", C.c_int32), ("owner_exchanges", C.c_int32), ("rounds", C.c_int32), ("ghosts", C.c_int32),
+                ("border_nodes", C.c_int32), ("roots", C.c_int32), ("records_sent", C.c_int64),
+                ("owner_records_sent", C.c_int64), ("ms_device", C.c_float), ("ms_total", C.c_float)]
+
+
 class TrgRouteInfo(C.Structure):
     _fields_ = [("num_nodes", C.c_int32), ("cost", C.c_float), ("path_length", C.c_float),
                 ("avg_risk", C.c_float)]
@@ -122,7 +128,7 @@ EXPORTS = [
     "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh", "trg_engine_cost_field_models",
     "trg_engine_risk_field_sets", "trg_engine_risk_field_refresh",
     "trg_engine_pose_links", "trg_engine_cost_field_seeded",
-    "trg_engine_tiled_cost_field", "trg_engine_stitch_ids",
+    "trg_engine_tiled_cost_field", "trg_engine_stitch_ids", "trg_engine_tiled_cost_field_sets",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -231,6 +237,8 @@ def load_library():
     L.trg_engine_risk_field_refresh.argtypes = L.trg_engine_cost_field_refresh.argtypes
     L.trg_engine_tiled_cost_field.argtypes = [vp, C.c_int32, ip, fp, ip, ip, C.POINTER(TrgTiledFieldInfo)]
     L.trg_engine_stitch_ids.argtypes = [vp, ip, ip, ip]
+    L.trg_engine_tiled_cost_field_sets.argtypes = [vp, C.c_int32, ip, ip, fp, fp, ip, ip, ip, ip, C.c_int32, fp, ip, ip,
+                                                   ip, C.POINTER(TrgTiledSetInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
     L.trg_engine_fallback_reason.restype = C.c_char_p
     _lib = L
@@ -399,6 +407,80 @@ class Engine:
         self._chk(self.L.trg_engine_tiled_cost_field(self.h, m, _i(src), _f(cost), _i(hops),
                                                      None if par is None else _i(par), C.byref(info)))
         return dict(cost=cost, hops=hops, parent=par, offset=offset, info=info)
+
+    def tiled_cost_fields_from(self, sets, start_costs=None, targets=None, full=True, parent=True):
+        """Source sets across tiles (trg_engine_tiled_cost_field_sets; DESIGN.md section 7, "Source sets across tiles"):
+        m fields of the global stitched graph in one collective solve, field k from EVERY entry of sets[k] (GLOBAL ids;
+        duplicates and Invalid nodes allowed), entry j at start_costs[k][j] (finite, >= 0; None: +0 each).  Every rank
+        calls it with the same sets and start costs after a stitch; `targets` (LOCAL ids of this tile), `full` and
+        `parent` are this rank's own.  -> dict with "cost", "hops", "parent" (global ids; None without `parent`),
+        "owner" (m x V_t) with `full`; "cost_at", "hops_at", "owner_at" (m x n_t) with `targets`; "owned" (a list of m
+        int32 arrays: THIS tile's nodes per entry of sets[k]); "offset" (this tile's first global id), "info"
+        (TrgTiledSetInfo), "sets" and "start_costs" (the arrays as solved, None without start costs).  An owner is the
+        index into sets[k] of the member a node's route starts from, -1 where unreached.  tiled.concat_fields joins
+        the ranks' results."""
+        sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
+        m = len(sets)
+        starts, c0 = None, None
+        if start_costs is not None:
+            starts = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in start_costs]
+            if len(starts) != m or any(c.shape != s.shape for c, s in zip(starts, sets)):
+                raise ValueError("tiled_cost_fields_from: start_costs and sets differ in shape")
+            c0 = np.ascontiguousarray(np.concatenate(starts) if m else np.empty(0, np.float32), dtype=np.float32)
+        ptr = np.zeros(m + 1, np.int64)
+        np.cumsum([s.shape[0] for s in sets], out=ptr[1:])
+        if ptr[-1] > 2**31 - 1:
+            raise ValueError(f"tiled_cost_fields_from: {int(ptr[-1])} source entries do not fit 32 bits")
+        ptr = ptr.astype(np.int32)
+        ids = np.ascontiguousarray(np.concatenate(sets) if m else np.empty(0, np.int32), dtype=np.int32)
+        try:
+            offset, V = self.global_ids()
+        except TrgError:
+            offset, V = 0, 0  # (the solve itself reports, and announces, that there are no current rows)
+        rows = max(m, 1)
+        out = dict(offset=offset, sets=sets, start_costs=starts)
+        if full:
+            out.update(cost=np.empty((rows, V), np.float32), hops=np.empty((rows, V), np.int32),
+                       parent=np.empty((rows, V), np.int32) if parent else None, owner=np.empty((rows, V), np.int32))
+        tg, n_t = None, 0
+        if targets is not None:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+            n_t = int(tg.shape[0])
+            out.update(cost_at=np.empty((rows, n_t), np.float32), hops_at=np.empty((rows, n_t), np.int32),
+                       owner_at=np.empty((rows, n_t), np.int32))
+        owned = np.zeros(max(int(ptr[-1]), 1), np.int32)
+        info = TrgTiledSetInfo()
+        arr = lambda name, conv: None if out.get(name) is None else conv(out[name])  # noqa: E731
+        self._chk(self.L.trg_engine_tiled_cost_field_sets(
+            self.h, m, _i(ptr), _i(ids), None if c0 is None else _f(c0), arr("cost", _f), arr("hops", _i),
+            arr("parent", _i), arr("owner", _i), None if tg is None or n_t == 0 else _i(tg), n_t, arr("cost_at", _f),
+            arr("hops_at", _i), arr("owner_at", _i), _i(owned), C.byref(info)))
+        out["owned"] = [owned[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
+        out["info"] = info
+        return out
+
+    def tiled_assign_frontiers(self, member_gids, start_costs=None):
+        """Every Frontier node of the global stitched graph to the entry of `member_gids` (GLOBAL ids, e.g. the robots'
+        nodes) that reaches it cheapest: a collective call -- one set field across tiles, read at THIS tile's own
+        Frontier nodes on the device.  -> per entry (the global ids of this tile's Frontier nodes it owns, ascending;
+        pick), pick being choose_frontier's among them as (gid, cost, hops), or None when it owns none here.
+        tiled.merge_frontier_picks joins the ranks' answers."""
+        members = np.ascontiguousarray(member_gids, dtype=np.int32).reshape(-1)
+        try:
+            frontier = self._frontier_ids()
+        except TrgError:
+            frontier = np.empty(0, np.int32)  # (the solve reports what is wrong with this tile)
+        r = self.tiled_cost_fields_from([members], None if start_costs is None else [start_costs], targets=frontier,
+                                        full=False, parent=False)
+        cost, hops, owner = r["cost_at"][0], r["hops_at"][0], r["owner_at"][0]
+        gids = (frontier.astype(np.int64) + r["offset"]).astype(np.int32)
+        out = []
+        for k in range(members.shape[0]):
+            mine = np.flatnonzero(owner == k)
+            pick = choose_frontier(gids[mine], cost[mine], hops[mine])
+            out.append((gids[mine], None if pick is None else
+                        (pick[0], float(cost[mine[pick[1]]]), int(hops[mine[pick[1]]]))))
+        return out
 
     def set_option(self, key, value):
         self._chk(self.L.trg_engine_set_option(self.h, str(key).encode(), str(value).encode()))

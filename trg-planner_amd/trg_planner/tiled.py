@@ -217,11 +217,31 @@ def concat_stitched(parts):
 
 
 def concat_fields(parts):
-    """The ranks' Engine.tiled_cost_fields results, in tile order -> dict of m x V arrays cost, hops, parent (global
-    ids; None when a rank solved without parents) of the global stitched graph."""
+    """The ranks' Engine.tiled_cost_fields (or tiled_cost_fields_from) results, in tile order -> dict of m x V arrays
+    cost, hops, parent (global ids; None when a rank solved without parents) of the global stitched graph, and owner
+    when every part has one (a set solve's full results)."""
     par = None if any(p["parent"] is None for p in parts) else np.concatenate([p["parent"] for p in parts], 1)
-    return dict(cost=np.concatenate([p["cost"] for p in parts], 1), hops=np.concatenate([p["hops"] for p in parts], 1),
-                parent=par)
+    out = dict(cost=np.concatenate([p["cost"] for p in parts], 1), hops=np.concatenate([p["hops"] for p in parts], 1),
+               parent=par)
+    if all(p.get("owner") is not None for p in parts):
+        out["owner"] = np.concatenate([p["owner"] for p in parts], 1)
+    return out
+
+
+def merge_frontier_picks(parts):
+    """The ranks' Engine.tiled_assign_frontiers answers -> per entry (all Frontier global ids it owns, ascending; the
+    least (cost, hops, gid) pick among the ranks' as (gid, cost, hops), or None).  No node goes to two entries: a
+    node is owned once, on the rank whose node it is."""
+    n = len(parts[0]) if parts else 0
+    if any(len(p) != n for p in parts):
+        raise ValueError("merge_frontier_picks: the ranks answered for different numbers of entries")
+    out = []
+    for k in range(n):
+        ids = np.sort(np.concatenate([np.asarray(p[k][0], np.int32) for p in parts])) if parts else np.empty(0, np.int32)
+        picks = [p[k][1] for p in parts if p[k][1] is not None]
+        best = min(picks, key=lambda q: (q[1], q[2], q[0])) if picks else None
+        out.append((ids.astype(np.int32), best))
+    return out
 
 
 def field_route(fields, k, target_gid):
