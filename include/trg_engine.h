@@ -178,6 +178,9 @@ typedef struct TrgStats {
   uint64_t start_discs_known;  /* device path: edge evaluations (of edge_evals_gpu) that did not evaluate the first disc
                                   of their segment walk: it is the start node's own acceptance disc, whose outcome
                                   and point count the sampling kept (option "known_start_disc") */
+  uint64_t map_tie_records;    /* device path: map-point tie records of accepted samples the level loop looked at */
+  uint64_t map_tie_unread;     /* of those, the ones left at "lowest cloud index" without a lookup because nothing
+                                  reads the sample's elevation: the sample created no node (option "lazy_tie_repair") */
 } TrgStats;
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
@@ -305,7 +308,11 @@ TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size
  * kept per node, so the speculative parent edges and the deferred evaluations add that count and start their
  * walk at the second disc -- default; 0: every disc is evaluated.  The root, nodes of host-replayed levels, and
  * every evaluation outside the global build -- updates against the local map among them -- never use a kept
- * count).  All modes give identical
+ * count);
+ * "lazy_tie_repair" = "1" | "0" (device BFS: an accepted sample whose nearest map point was not unique gets the
+ * reference's elevation only if the level's commit made a node of it, or of another tied candidate of its level --
+ * a sample's z is read by nothing but the node it creates and that node's parent edge -- default; 0: every such
+ * sample is looked up and its level's commit redone when a z changed).  All modes give identical
  * graphs; the env var TRG_REPLAY=host sets the default.  Test hooks (never change results):
  * "debug_tie_every" = n (treat every n-th BFS level as tie-affected -> host level replay),
  * "debug_gate_margin" = x (widen the band of slope gates left to the host's libm),

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run on the GPU box: alternate variants of the engine on the same GPU and print ms_per_step / loop /
-# deferred / finalize / set-map / index-kernel times of each run (same-box A/B measurements: boxes differ
-# by a few percent, runs on one box by well under one).
+# deferred / finalize / set-map / index-kernel times, the level count and ms_rare_events of each run (same-box
+# A/B measurements: boxes differ by a few percent, runs on one box by well under one).
 #   bash scripts/ab.sh                      every ab/lib*.so, default environment
 #   bash scripts/ab.sh name=lib[,VAR=val]…  named variants: library (file under ab/ or "product") + environment
 # The series ends at the first run whose bench.py exits non-zero (a fault, an abort, the time limit): nothing more
@@ -14,7 +14,7 @@ d = json.load(sys.stdin)
 b = d["breakdown_last_step"]
 print(sys.argv[1], round(d["ms_per_step"], 2), round(b["ms_bfs_loop"], 2), round(b["ms_deferred"], 2),
       round(b["ms_finalize_host"], 2), round(b["ms_set_map_total"], 2), round(b["ms_index_build_gpu"], 2),
-      b.get("bfs_levels", ""))
+      b.get("bfs_levels", ""), round(b.get("ms_rare_events", 0.0), 2))
 PY
 specs=("$@")
 if [ ${#specs[@]} -eq 0 ]; then

@@ -620,6 +620,7 @@ struct TrgEngine {
   bool use_device_bfs = true;    // device-resident BFS (off: host replay)
   bool defer_overlap = true;     // deferred edge evaluations pipelined behind the level loop on a 2nd stream
   bool known_start_disc = true;  // edge walks that start at a node the level loop created skip their first disc (BfsDev::ndisc)
+  bool lazy_tie_repair = true;   // a map-point tie is looked up only where the sample's elevation is read (fix_map_ties)
   bool tail_overlap = true;      // after the loop: the creating edges' covariances beside the cleaned graph's copy to the host
   PlanScratch plan_scratch;  // the planner's search scratch (A* runs straight on csr_global, see plan_on_csr)
   std::unique_ptr<Uploader> uploader;  // host cloud -> HBM staging (upload_and_build): pinned slots, streams and events
@@ -1236,6 +1237,7 @@ TrgStatus set_option(TrgEngine *e, const char *key, const char *value) {
       {"defer_overlap", ZERO_OR_ONE, &e->defer_overlap},
       {"tail_overlap", ZERO_OR_ONE, &e->tail_overlap},
       {"known_start_disc", ZERO_OR_ONE, &e->known_start_disc},
+      {"lazy_tie_repair", ZERO_OR_ONE, &e->lazy_tie_repair},
       {"tie_inplace", BOOL, &e->tie_inplace},
       {"keep_preclean", BOOL, &e->keep_preclean},
       {"resolve_tickets", INT, &e->resolve_tickets},

@@ -70,15 +70,25 @@ struct BfsBuffers {
   Pinned<int> h_ctrs;  // pinned, device-visible: the counters of a level, its stamp in words 5 and 15
   int stamp_serial = 0;
   // host mirror of the nodes [0, hm_state.size()): states and positions, fetched from the device when a
-  // rare event needs them; it only holds nodes of levels that are final or being examined
-  std::vector<int> hm_state;
-  std::vector<float> hm_x, hm_y;
+  // rare event needs them; it only holds nodes of levels that are final or being examined.  Pinned (late in a
+  // build a fetch is megabytes) and kept from build to build: clear() leaves the capacity.
+  PVec<int> hm_state;
+  PVec<float> hm_x, hm_y;
+  // pinned staging of the tie repairs: records fetched from / patches sent to the device in one batch of
+  // asynchronous copies with a single wait
+  PVec<SlotRec> st_slot;
+  PVec<int> st_int;
   std::vector<int> rp_stamp, rp_head;  // replay_level: cell -> newest node this replay created
   int rp_serial = 0;
   unsigned long long nodes_created = 0, nodes_invalid = 0;  // by the levels that became final
 };
 
-// the host mirror grown to the nodes [0, n)
+// The stream of the tie repairs' batched copies.  Like the synchronous copies they replace they are not ordered
+// behind the main stream, which may hold the next level's expansion: what they read is final since the level's
+// stamp arrived, what they write is read by launches the host issues after the wait.
+inline hipStream_t repair_stream(TrgEngine *e) { return e->s_aux; }
+
+// the host mirror grown to the nodes [0, n): three copies into pinned memory, one wait
 TrgStatus mirror_nodes(TrgEngine *e, BfsBuffers &bb, int n) {
   const size_t at = bb.hm_state.size();
   if ((size_t)n <= at) return TRG_OK;
@@ -86,9 +96,11 @@ TrgStatus mirror_nodes(TrgEngine *e, BfsBuffers &bb, int n) {
   bb.hm_state.resize(n);
   bb.hm_x.resize(n);
   bb.hm_y.resize(n);
-  HIPCHK(e, hipMemcpy(bb.hm_state.data() + at, bb.B.nstate + at, k * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(e, hipMemcpy(bb.hm_x.data() + at, bb.B.nx + at, k * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(e, hipMemcpy(bb.hm_y.data() + at, bb.B.ny + at, k * sizeof(float), hipMemcpyDeviceToHost));
+  const hipStream_t st = repair_stream(e);
+  HIPCHK(e, hipMemcpyAsync(bb.hm_state.data() + at, bb.B.nstate + at, k * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(e, hipMemcpyAsync(bb.hm_x.data() + at, bb.B.nx + at, k * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(e, hipMemcpyAsync(bb.hm_y.data() + at, bb.B.ny + at, k * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(e, hipStreamSynchronize(st));
   return TRG_OK;
 }
 
@@ -186,6 +198,11 @@ struct Level {
   bool reexpand = false;  // the level's commit was redone: the next level's expansion is void
   bool undone = false;    // the commit is taken back and not yet redone
   bool replayed = false;  // replayed on the host (which counted its own nodes)
+  // map-point tie records of candidates that the commit that stands did not make nodes: their elevation is read
+  // by nobody and was left as the device picked it.  A rerun of resolve + commit or a host replay of the level
+  // may create other nodes, so either repairs them first (repair_skipped_map_ties).
+  std::vector<MapTieRec> mt_skipped;
+  std::string repairs;  // what repair_level did, for its trace line
 };
 
 // One device build: what its phases share, the phases and the steps of a level.
@@ -268,6 +285,8 @@ struct Build {
   TrgStatus undo_level(Level &lv);
   TrgStatus redo_commit(Level &lv, bool decide_gates = false, bool ticketed = false, int hook = 0);
   TrgStatus fix_map_ties(Level &lv);
+  TrgStatus repair_map_tie(const MapTieRec &r, SlotRec &sr, bool *z_changed);
+  TrgStatus repair_skipped_map_ties(Level &lv);
   TrgStatus fix_pre_level_ties(Level &lv);
   TrgStatus settle_ties_in_place(Level &lv);
   TrgStatus replay_level(Level &lv);
@@ -360,6 +379,9 @@ TrgStatus Build::undo_level(Level &lv) {
   lv.reexpand = true;
   lv.undone = true;
   HIPCHK(e, hipStreamSynchronize(s));  // the next level's expansion (now void) must be out of the way
+  // whatever follows an undo -- resolve + commit again, the host's replay -- decides anew who creates a node
+  const TrgStatus st_mt = repair_skipped_map_ties(lv);
+  if (st_mt != TRG_OK) return st_mt;
   launch_bfs_undo_slots(B, (int)lv.slots, s);
   // k_level_resolve polls outcomes: a rerun must find them undecided again
   HIPCHK(e, hipMemsetAsync(B.c_outcome, 0, lv.slots * sizeof(int), s));
@@ -398,50 +420,114 @@ TrgStatus Build::redo_commit(Level &lv, bool decide_gates, bool ticketed, int ho
 // accepted samples whose elevation hung on a nearest-map-point tie: the device took the lowest cloud
 // index; fetch the reference's choice and, if a z changed, re-evaluate that sample's speculative edge and
 // redo resolve + commit (sample positions and classes do not depend on z)
+//
+// Only where that elevation is read (option lazy_tie_repair, the default).  A sample's z is the z of the node
+// it creates and the end of that node's parent edge -- nothing else.  A class-1 slot has a pre-level node
+// within robot_size: it merges or is skipped, never creates.  A candidate that the commit decided as 1 or 2
+// did not create either, and its speculative edge reached other slots only as "would be Invalid if created".
+// Such records get no lookup.  One candidate record whose slot created a node repairs every candidate record
+// of the level, since the rerun may let another of them create.
 TrgStatus Build::fix_map_ties(Level &lv) {
   TrgStatus st;
   std::vector<MapTieRec> recs((size_t)std::min(lv.n_mt, MAPTIE_CAP));
   HIPCHK(e, hipMemcpy(recs.data(), B.mt_rec + lv.parity * MAPTIE_CAP, recs.size() * sizeof(MapTieRec),
                       hipMemcpyDeviceToHost));
   if (lv.n_mt > MAPTIE_CAP) e->stats.map_nn_unresolved += (uint64_t)(lv.n_mt - MAPTIE_CAP);
-  bool z_changed = false;
-  for (const MapTieRec &r : recs) {
-    float z_exact = 0;
-    bool found = false;
-    if ((st = map_nn_exact(e, m, r.qx, r.qy, &z_exact, &found)) != TRG_OK) return st;
-    SlotRec sr;
-    HIPCHK(e, hipMemcpy(&sr, B.slot_rec + r.slot, sizeof(SlotRec), hipMemcpyDeviceToHost));
-    if (!found || z_exact == sr.z) continue;
-    sr.z = z_exact;
-    z_changed = true;
-    if ((sr.cls & SLOT_CLS_MASK) == 2) {
-      // the candidate's parent edge with the corrected elevation (position-only part of wireEdge)
-      int parent = 0;
-      float p1[3], p2[3] = {r.qx, r.qy, z_exact}, wgt = 0, dd = 0;
-      HIPCHK(e, hipMemcpy(&parent, B.front_cur + r.slot / S, sizeof(int), hipMemcpyDeviceToHost));
-      HIPCHK(e, hipMemcpy(&p1[0], B.nx + parent, sizeof(float), hipMemcpyDeviceToHost));
-      HIPCHK(e, hipMemcpy(&p1[1], B.ny + parent, sizeof(float), hipMemcpyDeviceToHost));
-      HIPCHK(e, hipMemcpy(&p1[2], B.nz + parent, sizeof(float), hipMemcpyDeviceToHost));
-      int32_t raw = 0;
-      if ((st = edges_sync(e, e->gmap, p1, p2, 1, &raw, nullptr, &wgt, &dd, false)) != TRG_OK) return st;
-      if (raw & EDGE_GATE_UNCERTAIN) {
-        e->stats.gate_uncertain++;
-        raw = host_slope_gate(e, p1[2], p2[2], dd) ? EDGE_GATE : (raw & ~EDGE_GATE_UNCERTAIN);
-      }
-      if ((raw & EDGE_STATUS_MASK) != EDGE_OK) wgt = 0.0f;
-      sr.status = raw;
-      sr.dist = dd;
-      sr.cov[0] = wgt;  // the weight itself (already clamped): k_node_weights takes it as given
-      sr.w_given = 1;
-    }
-    HIPCHK(e, hipMemcpy(B.slot_rec + r.slot, &sr, sizeof(SlotRec), hipMemcpyHostToDevice));
+  e->stats.map_tie_records += recs.size();
+  std::vector<SlotRec> srs(recs.size());
+  for (size_t k = 0; k < recs.size(); ++k) {
+    if (recs[k].slot < 0 || (size_t)recs[k].slot >= lv.slots)
+      return e->fail(TRG_ERR_DEVICE, "map-tie record of a slot outside the level");
+    HIPCHK(e, hipMemcpy(&srs[k], B.slot_rec + recs[k].slot, sizeof(SlotRec), hipMemcpyDeviceToHost));
   }
+  std::vector<char> repair(recs.size(), 1);
+  if (e->lazy_tie_repair) {
+    // the outcomes of the candidates among them, from the commit that stands: one batch of copies, one wait
+    std::vector<size_t> cand;
+    for (size_t k = 0; k < recs.size(); ++k)
+      if ((srs[k].cls & SLOT_CLS_MASK) == 1) repair[k] = 0;
+      else cand.push_back(k);
+    bb.st_int.resize(cand.size());
+    const hipStream_t sr_ = repair_stream(e);
+    for (size_t q = 0; q < cand.size(); ++q)
+      HIPCHK(e, hipMemcpyAsync(bb.st_int.data() + q, B.c_outcome + recs[cand[q]].slot, sizeof(int),
+                               hipMemcpyDeviceToHost, sr_));
+    if (!cand.empty()) HIPCHK(e, hipStreamSynchronize(sr_));
+    bool any_reads_z = false;  // (an outcome that is not final -- a stalled resolve -- counts as one that may create)
+    for (size_t q = 0; q < cand.size(); ++q) any_reads_z |= bb.st_int[q] != 1 && bb.st_int[q] != 2;
+    if (!any_reads_z)
+      for (size_t k : cand) {
+        repair[k] = 0;
+        lv.mt_skipped.push_back(recs[k]);
+      }
+  }
+  bool z_changed = false;
+  size_t unread = 0;
+  for (size_t k = 0; k < recs.size(); ++k) {
+    if (!repair[k])
+      unread++;
+    else if ((st = repair_map_tie(recs[k], srs[k], &z_changed)) != TRG_OK)
+      return st;
+  }
+  e->stats.map_tie_unread += unread;
+  lv.repairs += " fix_map_ties(" + std::to_string(recs.size() - unread) + " of " + std::to_string(recs.size()) +
+                (z_changed ? " looked up, z_changed)" : " looked up)");
   if (z_changed)
     // the level's uncertain gates are decided before the second half runs again (the entry of a
     // re-evaluated slot is stale but harmless: its status no longer carries the flag)
     return redo_commit(lv, true);
   const int zero = 0;
   HIPCHK(e, hipMemcpy(B.ctrs + BFS_CTR_NMAPTIE + lv.parity, &zero, sizeof(int), hipMemcpyHostToDevice));
+  return TRG_OK;
+}
+
+// one record: the reference's elevation and, for a candidate, its parent edge with it; sr is the slot's record
+TrgStatus Build::repair_map_tie(const MapTieRec &r, SlotRec &sr, bool *z_changed) {
+  TrgStatus st;
+  float z_exact = 0;
+  bool found = false;
+  if ((st = map_nn_exact(e, m, r.qx, r.qy, &z_exact, &found)) != TRG_OK) return st;
+  if (!found || z_exact == sr.z) return TRG_OK;
+  sr.z = z_exact;
+  *z_changed = true;
+  if ((sr.cls & SLOT_CLS_MASK) == 2) {
+    // the candidate's parent edge with the corrected elevation (position-only part of wireEdge)
+    int parent = 0;
+    float p1[3], p2[3] = {r.qx, r.qy, z_exact}, wgt = 0, dd = 0;
+    HIPCHK(e, hipMemcpy(&parent, B.front_cur + r.slot / S, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(&p1[0], B.nx + parent, sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(&p1[1], B.ny + parent, sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(&p1[2], B.nz + parent, sizeof(float), hipMemcpyDeviceToHost));
+    int32_t raw = 0;
+    if ((st = edges_sync(e, e->gmap, p1, p2, 1, &raw, nullptr, &wgt, &dd, false)) != TRG_OK) return st;
+    if (raw & EDGE_GATE_UNCERTAIN) {
+      e->stats.gate_uncertain++;
+      raw = host_slope_gate(e, p1[2], p2[2], dd) ? EDGE_GATE : (raw & ~EDGE_GATE_UNCERTAIN);
+    }
+    if ((raw & EDGE_STATUS_MASK) != EDGE_OK) wgt = 0.0f;
+    sr.status = raw;
+    sr.dist = dd;
+    sr.cov[0] = wgt;  // the weight itself (already clamped): k_node_weights takes it as given
+    sr.w_given = 1;
+  }
+  HIPCHK(e, hipMemcpy(B.slot_rec + r.slot, &sr, sizeof(SlotRec), hipMemcpyHostToDevice));
+  return TRG_OK;
+}
+
+// the records fix_map_ties left alone, repaired after all: the level's commit is about to be decided again.
+// The caller has drained the main stream (edges_sync runs there).
+TrgStatus Build::repair_skipped_map_ties(Level &lv) {
+  if (lv.mt_skipped.empty()) return TRG_OK;
+  TrgStatus st;
+  bool z_changed = false;
+  for (const MapTieRec &r : lv.mt_skipped) {
+    SlotRec sr;
+    HIPCHK(e, hipMemcpy(&sr, B.slot_rec + r.slot, sizeof(SlotRec), hipMemcpyDeviceToHost));
+    if ((st = repair_map_tie(r, sr, &z_changed)) != TRG_OK) return st;
+  }
+  e->stats.map_tie_unread -= lv.mt_skipped.size();  // (read after all)
+  lv.repairs += " skipped_map_ties(" + std::to_string(lv.mt_skipped.size()) + (z_changed ? ", z_changed)" : ")");
+  lv.mt_skipped.clear();
   return TRG_OK;
 }
 
@@ -453,6 +539,8 @@ TrgStatus Build::fix_pre_level_ties(Level &lv) {
   std::vector<SlotRec> srec(lv.slots);
   HIPCHK(e, hipMemcpy(srec.data(), B.slot_rec, lv.slots * sizeof(SlotRec), hipMemcpyDeviceToHost));
   Nearest near;
+  std::vector<size_t> patched;  // slots whose records changed: bb.st_slot holds them, in this order
+  bb.st_slot.clear();
   for (size_t sl = 0; sl < lv.slots; ++sl) {
     SlotRec &sr = srec[sl];
     if (!(sr.cls & SLOT_TIE) || (sr.cls & SLOT_CLS_MASK) == 0 || sr.nn0 < 0) continue;
@@ -461,8 +549,14 @@ TrgStatus Build::fix_pre_level_ties(Level &lv) {
     e->stats.nn_ties++;
     sr.nn0 = near.winner(bb, lv.V0, sr.x, sr.y);
     sr.cls &= ~SLOT_TIE;
-    HIPCHK(e, hipMemcpy(B.slot_rec + sl, &sr, sizeof(SlotRec), hipMemcpyHostToDevice));
+    bb.st_slot.push_back(sr);
+    patched.push_back(sl);
   }
+  for (size_t k = 0; k < patched.size(); ++k)
+    HIPCHK(e, hipMemcpyAsync(B.slot_rec + patched[k], bb.st_slot.data() + k, sizeof(SlotRec), hipMemcpyHostToDevice,
+                             repair_stream(e)));
+  if (!patched.empty()) HIPCHK(e, hipStreamSynchronize(repair_stream(e)));
+  lv.repairs += " fix_pre_level_ties(" + std::to_string(patched.size()) + ")";
   lv.err_from_sample = 0;  // settled
   if ((st = redo_commit(lv)) != TRG_OK) return st;
   e->stats.bfs_tie_fixups++;
@@ -488,22 +582,37 @@ TrgStatus Build::settle_ties_in_place(Level &lv) {
   // V0 + the creations of the slots before it
   std::vector<int> oc((size_t)tslots.back() + 1);
   HIPCHK(e, hipMemcpy(oc.data(), B.c_outcome, oc.size() * sizeof(int), hipMemcpyDeviceToHost));
+  const auto t_mirror = Clock::now();
+  const size_t mirrored = bb.hm_state.size();
   if ((st = mirror_nodes(e, bb, lv.v_after)) != TRG_OK) return st;  // (the level's nodes included)
+  const double ms_mirror = ms_since(t_mirror);
   struct Patch {
     size_t at;
     int n2, st;
   };
   std::vector<Patch> patches;
+  // the tied slots' records and parents: one batch of copies, one wait.  st_int: a parent per slot, then room
+  // for the two patch words of each.
+  const size_t nt = tslots.size();
+  const hipStream_t sr_ = repair_stream(e);
+  bb.st_slot.resize(nt);
+  bb.st_int.resize(3 * nt);
+  for (size_t k = 0; k < nt; ++k) {
+    HIPCHK(e, hipMemcpyAsync(bb.st_slot.data() + k, B.slot_rec + tslots[k], sizeof(SlotRec), hipMemcpyDeviceToHost,
+                             sr_));
+    HIPCHK(e, hipMemcpyAsync(bb.st_int.data() + k, B.front_cur + tslots[k] / S, sizeof(int), hipMemcpyDeviceToHost,
+                             sr_));
+  }
+  HIPCHK(e, hipStreamSynchronize(sr_));
   Nearest near;
   size_t scanned = 0;
   int created_before = 0;
-  for (int sl : tslots) {
+  for (size_t k = 0; k < nt; ++k) {
+    const int sl = tslots[k];
     for (; scanned < (size_t)sl; ++scanned) created_before += (oc[scanned] == 3 || oc[scanned] == 4);
     const int V_at = lv.V0 + created_before;
-    SlotRec sr;
-    int u = -1;
-    HIPCHK(e, hipMemcpy(&sr, B.slot_rec + sl, sizeof(SlotRec), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(&u, B.front_cur + sl / S, sizeof(int), hipMemcpyDeviceToHost));
+    const SlotRec &sr = bb.st_slot[k];
+    const int u = bb.st_int[k];
     if ((sr.cls & SLOT_CLS_MASK) == 0) continue;
     near.start(bb, sr, lv.V0);
     for (int i = lv.V0; i < V_at; ++i) near.offer(bb, i, sr.x, sr.y);
@@ -518,9 +627,19 @@ TrgStatus Build::settle_ties_in_place(Level &lv) {
     patches.push_back({(size_t)lv.call_base + (size_t)sl, kind == 2 ? nn : -1,
                        (kind == 2 && nn != u) ? CALL_PENDING : CALL_NONE});
   }
-  for (const Patch &pt : patches) {
-    HIPCHK(e, hipMemcpy(B.call_n2 + pt.at, &pt.n2, sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(B.call_status + pt.at, &pt.st, sizeof(int), hipMemcpyHostToDevice));
+  for (size_t k = 0; k < patches.size(); ++k) {  // (at most one per tied slot)
+    int *words = bb.st_int.data() + nt + 2 * k;
+    words[0] = patches[k].n2;
+    words[1] = patches[k].st;
+    HIPCHK(e, hipMemcpyAsync(B.call_n2 + patches[k].at, words, sizeof(int), hipMemcpyHostToDevice, sr_));
+    HIPCHK(e, hipMemcpyAsync(B.call_status + patches[k].at, words + 1, sizeof(int), hipMemcpyHostToDevice, sr_));
+  }
+  if (!patches.empty()) HIPCHK(e, hipStreamSynchronize(sr_));
+  {
+    char txt[160];
+    snprintf(txt, sizeof txt, " settle_ties_in_place(%zu slots, %zu patched, %zu nodes mirrored in %.3f ms)", nt,
+             patches.size(), bb.hm_state.size() - mirrored, ms_mirror);
+    lv.repairs += txt;
   }
   launch_bfs_clear_tie(B, s);
   lv.err &= ~BFS_ERR_TIE;
@@ -693,6 +812,13 @@ TrgStatus Build::replay_level(Level &lv) {
 // as "not gated" and a nearest-node tie as "lowest id"; when either happened the level's commit is taken
 // back, the host supplies the exact answer, and resolve + commit run again / the level is replayed on the
 // host.
+//
+// Invariant of the map-point ties (step 4): no rerun of resolve + commit and no host replay of a level ever runs
+// with an unrepaired candidate (class-2) tie record of that level.  fix_map_ties may leave such records alone
+// (Level::mt_skipped) only while the commit it looked at stands; redo_commit, the undo_level calls of steps 5
+// and 8, fix_pre_level_ties (through redo_commit) and replay_level (always behind an undo) all pass through
+// undo_level, which repairs them first.  Step 2 runs before any record is skipped, and the filter of step 4
+// reads the outcomes of the commit step 2 left.  Step 7 keeps the commit and changes no creator.
 TrgStatus Build::repair_level(Level &lv) {
   TrgStatus st;
   // 1. step-3 guards
@@ -747,9 +873,12 @@ TrgStatus Build::repair_level(Level &lv) {
   if (any_rare) {
     e->stats.ms_rare_events += ms_since(t_rare);
     if (getenv("TRG_TRACE_LEVELS"))
-      fprintf(stderr, "[trg bfs] level %d: rare events (map ties %d, uncertain gates %d, err %d%s) took %.3f ms\n",
-              lv.index, lv.n_mt, lv.n_unc, lv.err, lv.replayed ? ", host replay" : "",
-              ms_since(t_rare));
+      fprintf(stderr,
+              "[trg bfs] level %d: rare events (map ties %d, uncertain gates %d, err %d%s) took %.3f ms; ran:%s%s, "
+              "commit %s\n",
+              lv.index, lv.n_mt, lv.n_unc, lv.err, lv.replayed ? ", host replay" : "", ms_since(t_rare),
+              lv.repairs.empty() ? " -" : lv.repairs.c_str(), lv.replayed ? " replay_level" : "",
+              lv.reexpand ? "redone" : "kept");
   }
   return TRG_OK;
 }
@@ -1026,6 +1155,12 @@ TrgStatus Build::level_loop() {
     launch_level_expand(m.view, qp, e->d_cos, e->d_sin, e->sampler.table_bits, e->sampler.seed,
                         e->epoch, Bn, spec_bound, B.ctrs + BFS_CTR_MNEXT, 0, parity ^ 1, next_tag, stamp,
                         e->d_ctr, s);
+    // The calls of the levels before this one are final: into the deferred pipeline, a batch at a time.  Behind
+    // the level's own launches, not in front of them: the main stream holds only the running expansion while the
+    // host issues these four or more launches, and on a level of a few hundred nodes that is 25-30 us of work.
+    // (The calls of the last levels stay for finish_deferred.)
+    if (overlap && call_base - def_lo >= DEF_BATCH_MIN && call_base < 0x7FFFFFF0LL)
+      if ((st = launch_deferred(call_base, true)) != TRG_OK) return st;
     if ((st = wait_stamp(stamp)) != TRG_OK) return st;
     n_expand_all++;
     read_level(lv, true);
@@ -1061,9 +1196,6 @@ TrgStatus Build::level_loop() {
     call_base += (long long)level_slots * CS;
     mcur = lv.mnext;
     levels++;
-    // the calls of the levels that are final by now: into the deferred pipeline, a batch at a time
-    if (overlap && call_base - def_lo >= DEF_BATCH_MIN && call_base < 0x7FFFFFF0LL)
-      if ((st = launch_deferred(call_base, true)) != TRG_OK) return st;
   }
   HIPCHK(e, hipStreamSynchronize(s));
   e->stats.ms_bfs_loop = ms_since(t_loop);

@@ -104,7 +104,7 @@ class TrgStats(C.Structure):
         ("ms_rare_events", C.c_double), ("bfs_ticket_reruns", C.c_uint64),
         ("bfs_multipass_rows", C.c_uint64), ("ms_upload", C.c_double), ("presampled_nodes", C.c_uint64),
         ("stitch_gate_retries", C.c_uint64), ("stitch_regrows", C.c_uint64),
-        ("start_discs_known", C.c_uint64)]
+        ("start_discs_known", C.c_uint64), ("map_tie_records", C.c_uint64), ("map_tie_unread", C.c_uint64)]
 
 
 # every symbol include/trg_engine.h declares (tests check that the library exports all of them)
