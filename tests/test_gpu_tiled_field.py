@@ -252,9 +252,8 @@ def test_chain_alternating_between_two_tiles(tmp_path, tiled, ref):
     close(engines)
 
 
-def test_lattice_of_exact_ties_across_seams(tmp_path, tiled, ref):
-    """(b) unit costs on a lattice in three tiles: nearly every node has several tight predecessors, local ones and
-    ghosts of lower and of higher tiles; the parent is the least GLOBAL id among them."""
+def tie_lattice():
+    """unit costs on a 12 x 9 lattice whose cells go to three tiles in diagonal stripes -> (sizes, edges, sources)"""
     nx, ny, R = 12, 9, 3
     tile = lambda x, y: (x // 2 + y) % R  # noqa: E731
     cells = sorted(((tile(x, y), y, x) for x in range(nx) for y in range(ny)))
@@ -267,7 +266,13 @@ def test_lattice_of_exact_ties_across_seams(tmp_path, tiled, ref):
                 edges.append((gid[x, y], gid[x + 1, y], 0.0, 1.0))
             if y + 1 < ny:
                 edges.append((gid[x, y], gid[x, y + 1], 0.0, 1.0))
-    sources = [gid[0, 0], gid[nx - 1, ny - 1], gid[5, 4]]
+    return sizes, edges, [gid[0, 0], gid[nx - 1, ny - 1], gid[5, 4]]
+
+
+def test_lattice_of_exact_ties_across_seams(tmp_path, tiled, ref):
+    """(b) unit costs on a lattice in three tiles: nearly every node has several tight predecessors, local ones and
+    ghosts of lower and of higher tiles; the parent is the least GLOBAL id among them."""
+    sizes, edges, sources = tie_lattice()
     engines, G, want, got = crafted(tmp_path, tiled, ref, sizes, edges, sources, tag="lattice")
     # the precondition: both orders occur among the tight predecessors of some node
     off = G["offsets"]
@@ -310,13 +315,15 @@ def test_zero_cost_cross_edges_and_saturation(tmp_path, tiled, ref):
     close(engines)
 
 
+INVALID_1 = [(0, 1, 0.0, 0.5), (1, 4, 0.0, 0.5), (1, 5, 0.1, 0.5), (0, 2, 0.2, 0.5), (2, 5, 0.0, 0.5), (5, 4, 0.3, 0.5),
+             (4, 6, 0.0, 0.5), (6, 3, 0.0, 0.5), (3, 1, 0.0, 0.5), (6, 7, 0.0, 0.5)]  # in [4, 4]; node 1 is Invalid
+
+
 def test_invalid_border_node(tmp_path, tiled, ref):
     """(e) an Invalid node with cross edges: no walk enters it from either side."""
     state = np.zeros(8, np.int32)
     state[1] = fg.INVALID
-    edges = [(0, 1, 0.0, 0.5), (1, 4, 0.0, 0.5), (1, 5, 0.1, 0.5), (0, 2, 0.2, 0.5), (2, 5, 0.0, 0.5), (5, 4, 0.3, 0.5),
-             (4, 6, 0.0, 0.5), (6, 3, 0.0, 0.5), (3, 1, 0.0, 0.5), (6, 7, 0.0, 0.5)]
-    engines, G, want, got = crafted(tmp_path, tiled, ref, [4, 4], edges, [0, 7, 1], state=state, tag="invalid")
+    engines, G, want, got = crafted(tmp_path, tiled, ref, [4, 4], INVALID_1, [0, 7, 1], state=state, tag="invalid")
     assert want[1][0][1] == -1 and want[1][1][1] == -1 and (np.delete(want[1][0], 1) >= 0).all()
     close(engines)
 
@@ -379,7 +386,62 @@ def test_refusals_leave_the_group_usable(tmp_path, tiled, ref):
     close(engines)
 
 
-# ---- 5. the Python helpers ------------------------------------------------------------------------------------------
+# ---- 5. single sources are sets of one ------------------------------------------------------------------------------
+def invalid_1_state():
+    state = np.zeros(8, np.int32)
+    state[1] = fg.INVALID
+    return state
+
+
+@pytest.mark.parametrize("case", ["ring", "lattice", "invalid"])
+def test_sources_equal_sets_of_one_with_their_counters(tmp_path, case):
+    """Both calls run one seeding: the same fields bit for bit and the same counters, the set call's owner 0 wherever
+    the field reaches.  With a duplicate source, a source that is a border node (a ghost of the other rank) and an
+    Invalid source."""
+    from trg_planner._engine import TrgError
+    if case == "ring":
+        sizes, edges, state, S, twins = [6, 6], RING, None, [0, 0, 7, 5], (0, 1)  # (0 and 5 are border nodes)
+    elif case == "lattice":
+        sizes, edges, sources = tie_lattice()
+        state, S, twins = None, sources + sources[:1], (0, 3)
+    else:
+        sizes, edges, state, S, twins = [4, 4], INVALID_1, invalid_1_state(), [0, 7, 1, 1], (2, 3)
+    engines = craft(tmp_path, sizes, edges, state, tag="one-" + case)
+    one, _ = solve(engines, S)
+    sets, _ = run_ranks(engines, lambda r, e: e.tiled_cost_fields_from([[s] for s in S]))
+    assert not [g for g in sets if isinstance(g, TrgError)], [str(g) for g in sets]
+    for t, (a, b) in enumerate(zip(one, sets)):
+        for name in ("cost", "hops", "parent"):
+            x, y = a[name].view(np.int32), b[name].view(np.int32)
+            assert x.shape == (len(S), sizes[t]) and np.array_equal(x, y), (case, t, name)
+            assert np.array_equal(x[twins[0]], x[twins[1]]), (case, t, name, "the duplicate source's rows differ")
+        assert np.array_equal(b["owner"], np.where(a["hops"] >= 0, 0, -1)), (case, t)
+        for name in ("exchanges", "rounds", "records_sent", "ghosts", "border_nodes"):
+            x, y = getattr(a["info"], name), getattr(b["info"], name)
+            print(case, "rank", t, name, x, y)
+            assert x == y, (case, t, name, x, y)
+    assert sum(int((a["hops"] >= 0).sum()) for a in one) > len(S)  # (the fields left their sources)
+    if case == "invalid":  # no walk enters the Invalid node; as a source it starts there and leaves
+        hops = np.concatenate([a["hops"] for a in one], 1)
+        assert hops[0][1] == -1 and hops[1][1] == -1 and hops[2][1] == 0 and (hops[2] >= 0).all(), hops
+    close(engines)
+
+
+def test_a_tile_without_nodes_between_two_with_cross_edges(tmp_path, tiled, ref):
+    """Sizes [6, 0, 6]: the middle rank has neither nodes nor entries; it only takes part in the exchanges."""
+    S = [0, 8, 5]
+    engines = craft(tmp_path, [6, 0, 6], RING, tag="hollow")
+    G = exported(tiled, engines)
+    got, _ = solve(engines, S)
+    assert_fields("hollow", tiled, got, G, reference(ref, G, S))  # (the empty rank's part: m x 0 arrays)
+    assert got[1]["cost"].shape == (3, 0) and got[1]["hops"].shape == (3, 0) and got[1]["parent"].shape == (3, 0)
+    exchanges = [g["info"].exchanges for g in got]
+    assert exchanges == [exchanges[0]] * 3 and exchanges[0] >= 4, exchanges
+    assert [g["info"].ghosts for g in got] == [2, 0, 2] and [g["info"].border_nodes for g in got] == [2, 0, 2]
+    close(engines)
+
+
+# ---- 6. the Python helpers ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["2x1", "2x2", "3x3"])
 def test_field_route_over_concatenated_fields(oa, synth, tiled, ref, name):
     import trg_planner

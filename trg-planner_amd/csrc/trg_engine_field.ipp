@@ -593,6 +593,22 @@ TrgStatus field_rounds(TrgEngine *e, FieldRun &run, const FieldSettle *under) {
 constexpr int FIELD_OWNER_BATCH = 8;
 static_assert(FIELD_OWNER_SWEEPS_MAX % FIELD_OWNER_BATCH == 0, "a forest pass looks after whole batches");
 
+// The jumping sweeps after a forest's begin launch (which zeroed `changed`), in batches, until one moves nothing:
+// one host wait per batch, on the pinned word `h_moved`.  -> the sweep count, which says where the ancestors lie
+// (F.q[sweeps & 1]).  `what` names the pass in the error of one that does not end.
+TrgStatus field_forest_sweeps(TrgEngine *e, const FieldDev &F, int *changed, int *h_moved, const char *what,
+                              int &sweeps) {
+  hipStream_t s = e->s_main;
+  for (sweeps = 0;;) {
+    for (int i = 0; i < FIELD_OWNER_BATCH; ++i, ++sweeps) launch_field_owner_sweep(F, sweeps, changed, s);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(h_moved, changed + sweeps - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    if (*h_moved == 0) return TRG_OK;
+    if (sweeps >= FIELD_OWNER_SWEEPS_MAX) return e->fail(TRG_ERR_DEVICE, std::string(what) + " did not end");
+  }
+}
+
 // One jump over the forest in F.parent (the owner pass, a refresh's anchors; trg_field.hip): the begin launch for
 // `single` sources or marked members and `key0`, the jumping sweeps in the idle near queues until a sweep moves
 // nothing -- about log2 of the longest chain of them, one host wait per FIELD_OWNER_BATCH sweeps -- then `end`'s
@@ -601,20 +617,13 @@ template <typename End>
 TrgStatus field_forest_pass(TrgEngine *e, const FieldDev &F, const FieldSources *single,
                             const unsigned long long *key0, const char *what, int &syncs, int &sweeps, End end) {
   FieldBufs &fb = *e->field;
-  hipStream_t s = e->s_main;
   if (const TrgStatus st = field_grow(e, fb.own_changed, FIELD_OWNER_SWEEPS_MAX * sizeof(int)); st != TRG_OK) return st;
   HIPCHK(e, fb.h_changed.ensure(1));
   int *changed = fb.own_changed.as<int>();
-  launch_field_forest_begin(F, single, key0, changed, s);
-  for (sweeps = 0;;) {
-    for (int i = 0; i < FIELD_OWNER_BATCH; ++i, ++sweeps) launch_field_owner_sweep(F, sweeps, changed, s);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(fb.h_changed, changed + sweeps - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    syncs++;
-    if (fb.h_changed[0] == 0) break;
-    if (sweeps >= FIELD_OWNER_SWEEPS_MAX) return e->fail(TRG_ERR_DEVICE, std::string(what) + " did not end");
-  }
+  launch_field_forest_begin(F, single, key0, changed, e->s_main);
+  const TrgStatus st = field_forest_sweeps(e, F, changed, fb.h_changed, what, sweeps);
+  syncs += sweeps / FIELD_OWNER_BATCH;  // (one wait per batch)
+  if (st != TRG_OK) return st;
   end(sweeps);
   HIPCHK(e, hipGetLastError());
   return TRG_OK;

@@ -5,18 +5,15 @@
 // exchange_allgatherv until an exchange carries no news from anybody.  The least fp32 fold over all walks is one
 // least fixed point that every relaxation order reaches (DESIGN.md section 2), and this is one more order; the two
 // passes of the single-engine solve (all edges, then tight edges only) are kept, each with its own exchange loop.
-// A solve starts from one source per field or from source sets with start costs ("Source sets across tiles"): the
-// members are seeded by the ranks that own them, and after the two passes a third loop of the same frame trades the
-// owners of the border nodes over the forest of the global parents.
+// A solve starts from source sets with start costs ("Source sets across tiles"), one source per field being m sets of
+// one entry: the members are seeded by the ranks that own them, and for the set call a third loop of the same frame
+// trades, after the two passes, the owners of the border nodes over the forest of the global parents.
 
 namespace {
 
 // rounds enqueued between two looks at the "work left" word (fewer than a single-engine solve's: a rank is
 // re-started once per exchange, mostly for a handful of rounds)
 constexpr int TILED_BATCH = 8;
-// jumping sweeps of the owner pass between two looks at the "moved" word
-constexpr int TILED_SWEEP_BATCH = 8;
-static_assert(FIELD_OWNER_SWEEPS_MAX % TILED_SWEEP_BATCH == 0, "the owner pass looks after whole batches");
 
 struct TiledFieldBufs {
   // the solve graph, built once per stitch: stamped with the graph version, the stitch and the cost model
@@ -32,36 +29,47 @@ struct TiledFieldBufs {
   // work arrays, per item (m x (V + G)), and per border item (m x B)
   DevArr key, q[2], far[2], stamp_near, stamp_far, parent, tight, ctrl;
   DevArr published, rec, n_rec, cost, hops, parent_out;
-  // a set solve: this rank's entries, the sets' offsets, owners per item, and the outputs at the targets
-  DevArr entries, set_ptr, owner, own_changed, owner_out, owned, targets, cost_at, hops_at, owner_at;
+  // this rank's entries, which the copy to `entries` reads after the call that enqueued it has gone on
+  std::vector<TiledEntry> h_entries;
+  DevArr entries;
+  // with owners: the sets' offsets, owners per item, and the outputs at the targets
+  DevArr set_ptr, owner, own_changed, owner_out, owned, targets, cost_at, hops_at, owner_at;
   Pinned<FieldState> h_state;
   Pinned<FieldEdgeStats> h_stats;
   Pinned<int> h_n;  // [0] ghosts, records or a sweep's "moved" word, [1] border rows or roots
   Event t0, t1;
 };
 
-// One solve on its way: the request, the kernels' view, and what ends up in the caller's info.
-struct TiledRun {
+// What a solve is asked for.  Both calls come as source sets in global ids: one source per field is m sets of one
+// entry (set_ptr = 0 .. m) without start costs.
+struct TiledRequest {
   int32_t m;
-  const int32_t *source_gids;  // one source per field, or nullptr: a set solve
+  const int32_t *set_ptr, *set_gids;
+  const float *set_cost0;  // or nullptr: every entry starts at 0
   float *cost;
   int32_t *hops, *parent;
-  // a set solve: the sets as the caller gave them (global ids) and what only a set solve puts out
-  const int32_t *set_ptr = nullptr, *set_gids = nullptr;
-  const float *set_cost0 = nullptr;
+  // The set call: the owner pass runs, and what follows may be asked for.  Fixed by the entry that was called, so
+  // every rank decides alike whether the owner pass, a collective, runs (tiled_solve).
+  bool owners;
+  const char *what;         // the error prefix of the call
+  const char *null_ids;     // the refusal of a null set_ptr or set_gids
+  const char *source_noun;  // of an id out of range: "<noun> k", or with nullptr "entry j of set k (id)"
   int32_t *owner = nullptr;
   const int32_t *targets = nullptr;
   int32_t n_targets = 0;
   float *cost_at = nullptr;
   int32_t *hops_at = nullptr, *owner_at = nullptr, *owned = nullptr;
+};
+
+// One solve on its way: the request, the kernels' view, and what ends up in the caller's info.
+struct TiledRun {
+  const TiledRequest &rq;
   FieldDev F{};
-  FieldSources local{};  // per field: the source as a local id where it is this rank's node, else -1
-  int n_entries = 0;     // a set solve: its entries whose member is this rank's node (tb.entries)
-  int round = 0;         // of the current pass
+  int n_entries = 0;  // the entries whose member is this rank's node (tb.entries)
+  int round = 0;      // of the current pass
   int rounds = 0, exchanges = 0, owner_exchanges = 0, roots = 0;
   long long records = 0, owner_records = 0;
   double ms_device = 0.0;
-  bool sets() const { return set_ptr != nullptr; }
 };
 
 // This rank's status through a loop of exchanges.  A step is skipped once one has failed; the failure's status and
@@ -222,15 +230,16 @@ TrgStatus tiled_graph(TrgEngine *e, const ExchangeState &x) {
 TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
   TiledFieldBufs &tb = *e->tiled;
   const FieldTiled &T = tb.T;
+  const TiledRequest &rq = run.rq;
   if (tb.bad_cost) return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: an edge cost is negative or not finite");
   const long long n = (long long)T.V + T.G;
-  if ((long long)run.m * n + 8 > INT_MAX)
+  if ((long long)rq.m * n + 8 > INT_MAX)
     return e->fail(TRG_ERR_CAPACITY, "tiled cost field: m x (nodes + ghosts) does not fit the solver's 32-bit item index");
   FieldDev &F = run.F;
   F.V = (int)n;
-  F.m = run.m;
-  F.N = (int)(run.m * n);
-  const size_t nN = (size_t)F.N + 4, nB = (size_t)run.m * T.B + 4, nO = (size_t)run.m * T.V + 4;
+  F.m = rq.m;
+  F.N = (int)(rq.m * n);
+  const size_t nN = (size_t)F.N + 4, nB = (size_t)rq.m * T.B + 4, nO = (size_t)rq.m * T.V + 4;
   TrgStatus st;
   if ((st = tiled_grow(e, tb.key, nN * 8)) != TRG_OK) return st;
   for (DevArr *a : {&tb.q[0], &tb.q[1], &tb.far[0], &tb.far[1], &tb.stamp_near, &tb.stamp_far, &tb.parent, &tb.tight})
@@ -253,45 +262,40 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
   F.parent = tb.parent.as<int>();
   F.ctrl = tb.ctrl.as<FieldCtrl>();
   F.tight = nullptr;
-  if (!run.sets()) {
-    for (int k = 0; k < run.m; ++k) {
-      const long long l = (long long)run.source_gids[k] - T.lo;
-      run.local.id[k] = l >= 0 && l < T.V ? (int)l : -1;
-    }
-    return TRG_OK;
-  }
-  // A set solve.  Its targets are this tile's nodes; of the entries this rank seeds those whose member is its own
-  // node (work per entry and per target, none per node).
+  // The targets are this tile's nodes; of the entries this rank seeds those whose member is its own node (work per
+  // entry and per target, none per node).
   hipStream_t s = e->s_main;
-  for (int j = 0; j < run.n_targets; ++j)
-    if (run.targets[j] < 0 || run.targets[j] >= T.V)
-      return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field sets: target " + std::to_string(j) + " (" + std::to_string(run.targets[j]) +
+  for (int j = 0; j < rq.n_targets; ++j)
+    if (rq.targets[j] < 0 || rq.targets[j] >= T.V)
+      return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field sets: target " + std::to_string(j) + " (" + std::to_string(rq.targets[j]) +
                                               ") is outside this tile's [0, " + std::to_string(T.V) + ")");
-  const int n_all = run.set_ptr[run.m];
-  std::vector<TiledEntry> mine;
-  for (int k = 0; k < run.m; ++k)
-    for (int j = run.set_ptr[k]; j < run.set_ptr[k + 1]; ++j) {
-      const long long l = (long long)run.set_gids[j] - T.lo;
+  std::vector<TiledEntry> &mine = tb.h_entries;
+  mine.clear();
+  for (int k = 0; k < rq.m; ++k)
+    for (int j = rq.set_ptr[k]; j < rq.set_ptr[k + 1]; ++j) {
+      const long long l = (long long)rq.set_gids[j] - T.lo;
       if (l < 0 || l >= T.V) continue;
-      const float c0 = run.set_cost0 ? run.set_cost0[j] + 0.0f : 0.0f;
+      const float c0 = rq.set_cost0 ? rq.set_cost0[j] + 0.0f : 0.0f;
       mine.push_back(TiledEntry{k, (int)l, j, float_bits(c0)});
     }
   run.n_entries = (int)mine.size();
-  const size_t nT = (size_t)run.m * (size_t)run.n_targets + 4;
-  if ((st = tiled_grow(e, tb.entries, (mine.size() + 1) * sizeof(TiledEntry))) != TRG_OK ||
-      (st = tiled_grow(e, tb.set_ptr, ((size_t)run.m + 2) * 4)) != TRG_OK || (st = tiled_grow(e, tb.owner, nN * 4)) != TRG_OK ||
+  if ((st = tiled_grow(e, tb.entries, (mine.size() + 1) * sizeof(TiledEntry))) != TRG_OK) return st;
+  if (!mine.empty())
+    HIPCHK(e, hipMemcpyAsync(tb.entries.p, mine.data(), mine.size() * sizeof(TiledEntry), hipMemcpyHostToDevice, s));
+  if (!rq.owners) return TRG_OK;
+  const size_t nT = (size_t)rq.m * (size_t)rq.n_targets + 4;
+  if ((st = tiled_grow(e, tb.set_ptr, ((size_t)rq.m + 2) * 4)) != TRG_OK || (st = tiled_grow(e, tb.owner, nN * 4)) != TRG_OK ||
       (st = tiled_grow(e, tb.own_changed, FIELD_OWNER_SWEEPS_MAX * sizeof(int))) != TRG_OK ||
-      (st = tiled_grow(e, tb.owner_out, nO * 4)) != TRG_OK || (st = tiled_grow(e, tb.owned, ((size_t)n_all + 4) * 4)) != TRG_OK ||
-      (st = tiled_grow(e, tb.targets, ((size_t)run.n_targets + 4) * 4)) != TRG_OK)
+      (st = tiled_grow(e, tb.owner_out, nO * 4)) != TRG_OK ||
+      (st = tiled_grow(e, tb.owned, ((size_t)rq.set_ptr[rq.m] + 4) * 4)) != TRG_OK ||
+      (st = tiled_grow(e, tb.targets, ((size_t)rq.n_targets + 4) * 4)) != TRG_OK)
     return st;
   for (DevArr *a : {&tb.cost_at, &tb.hops_at, &tb.owner_at})
     if ((st = tiled_grow(e, *a, nT * 4)) != TRG_OK) return st;
-  HIPCHK(e, hipMemcpyAsync(tb.set_ptr.p, run.set_ptr, ((size_t)run.m + 1) * 4, hipMemcpyHostToDevice, s));
-  if (!mine.empty())
-    HIPCHK(e, hipMemcpyAsync(tb.entries.p, mine.data(), mine.size() * sizeof(TiledEntry), hipMemcpyHostToDevice, s));
-  if (run.n_targets > 0)
-    HIPCHK(e, hipMemcpyAsync(tb.targets.p, run.targets, (size_t)run.n_targets * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(e, hipStreamSynchronize(s));  // (`mine` goes out of scope)
+  HIPCHK(e, hipMemcpyAsync(tb.set_ptr.p, rq.set_ptr, ((size_t)rq.m + 1) * 4, hipMemcpyHostToDevice, s));
+  if (rq.n_targets > 0)
+    HIPCHK(e, hipMemcpyAsync(tb.targets.p, rq.targets, (size_t)rq.n_targets * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipStreamSynchronize(s));  // (the caller's arrays; a tile without nodes waits for the stream nowhere else)
   return TRG_OK;
 }
 
@@ -396,8 +400,7 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
     F.tight = pass ? tb.tight.as<unsigned>() : nullptr;
     run.round = 0;
     HIPCHK(e, hipEventRecord(tb.t0, s));
-    launch_tiled_begin(F, T, run.local, run.sets() ? tb.entries.as<TiledEntry>() : nullptr, run.n_entries, delta,
-                       tb.published.as<unsigned long long>(), s);
+    launch_tiled_begin(F, T, tb.entries.as<TiledEntry>(), run.n_entries, delta, tb.published.as<unsigned long long>(), s);
     return TRG_OK;
   });
   // a key of a border item drops at most a few times per item in practice; the cap is the round cap's shape
@@ -406,7 +409,7 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
       [&](int, const void *d_all, int gathered) -> TrgStatus {
         launch_tiled_merge(F, T, d_all, gathered, s);
         if (const TrgStatus r = tiled_rounds(e, run); r != TRG_OK) return r;
-        launch_tiled_publish(F, T, tb.published.as<unsigned long long>(), tb.rec.p, tb.n_rec.as<int>(), s);
+        launch_tiled_publish(F, T, nullptr, tb.published.as<unsigned long long>(), tb.rec.p, tb.n_rec.as<int>(), s);
         return TRG_OK;
       });
   if (st != TRG_OK) return st;
@@ -418,7 +421,7 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
   return TRG_OK;
 }
 
-// The owner pass of a set solve, after its two passes (DESIGN.md section 7, "Source sets across tiles"): the third
+// The owner pass of the set call, after its two passes (DESIGN.md section 7, "Source sets across tiles"): the third
 // use of the frame.  This rank: the parent sweep, the forest of the global parents with the local roots and the
 // ghosts as terminals, jumping sweeps until one moves nothing.  Then the loop: merge the gathered owner records into
 // the ghost items, every item takes its final ancestor's owner where that is known, publish the border items whose
@@ -438,17 +441,13 @@ TrgStatus tiled_owner_pass(TrgEngine *e, ExchangeState &x, TiledRun &run) {
     launch_tiled_parents(F, T, s);
     launch_tiled_forest_begin(F, T, tb.set_ptr.as<int>(), owner, changed, tb.n_rec.as<int>() + 1,
                               tb.published.as<unsigned long long>(), s);
-    for (int sweeps = 0;;) {
-      for (int i = 0; i < TILED_SWEEP_BATCH; ++i, ++sweeps) launch_field_owner_sweep(F, sweeps, changed, s);
-      HIPCHK(e, hipGetLastError());
-      HIPCHK(e, hipMemcpyAsync(&tb.h_n[0], changed + sweeps - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(e, hipMemcpyAsync(&tb.h_n[1], tb.n_rec.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(e, hipStreamSynchronize(s));
-      anc = F.q[sweeps & 1];
-      if (tb.h_n[0] == 0) break;
-      if (sweeps >= FIELD_OWNER_SWEEPS_MAX) return e->fail(TRG_ERR_DEVICE, "tiled cost field sets: the owner pass's sweeps did not end");
-    }
-    run.roots = tb.h_n[1];
+    HIPCHK(e, hipMemcpyAsync(&tb.h_n[1], tb.n_rec.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    int sweeps = 0;
+    if (const TrgStatus st = field_forest_sweeps(e, F, changed, &tb.h_n[0], "tiled cost field sets: the owner pass's sweeps", sweeps);
+        st != TRG_OK)
+      return st;
+    anc = F.q[sweeps & 1];
+    run.roots = tb.h_n[1];  // (the first wait of the sweeps was for this copy too)
     return TRG_OK;
   });
   return tiled_exchanges(e, x, run, mine, "tiled cost field sets: owner pass: ", 1, 2, run.owner_exchanges, run.owner_records,
@@ -462,34 +461,34 @@ TrgStatus tiled_owner_pass(TrgEngine *e, ExchangeState &x, TiledRun &run) {
 TrgStatus tiled_outputs(TrgEngine *e, TiledRun &run) {
   TiledFieldBufs &tb = *e->tiled;
   const FieldTiled &T = tb.T;
+  const TiledRequest &rq = run.rq;
   hipStream_t s = e->s_main;
-  const int n_entries = run.sets() ? run.set_ptr[run.m] : 0;
-  if (run.owned) std::fill(run.owned, run.owned + n_entries, 0);  // (a tile without nodes owns none)
+  const int n_entries = rq.set_ptr[rq.m];
+  if (rq.owned) std::fill(rq.owned, rq.owned + n_entries, 0);  // (a tile without nodes owns none)
   if (run.F.N > 0 && T.V > 0) {
-    const size_t nO = (size_t)run.m * T.V, nT = (size_t)run.m * (size_t)run.n_targets;
+    const size_t nO = (size_t)rq.m * T.V, nT = (size_t)rq.m * (size_t)rq.n_targets;
     HIPCHK(e, hipEventRecord(tb.t0, s));
-    // (a set solve's parent sweep ran before its owner pass)
+    // (with owners the parent sweep ran before the owner pass)
     launch_tiled_finish(run.F, T, tb.cost.as<float>(), tb.hops.as<int>(), tb.parent_out.as<int>(),
-                        run.parent != nullptr && !run.sets(), s);
-    if (run.sets()) {
-      launch_tiled_owner_outputs(run.F, T, tb.set_ptr.as<int>(), tb.owner.as<int>(), n_entries,
-                                 run.owner ? tb.owner_out.as<int>() : nullptr, run.owned ? tb.owned.as<int>() : nullptr, s);
+                        rq.parent != nullptr && !rq.owners, tb.owner.as<int>(), rq.owner ? tb.owner_out.as<int>() : nullptr, s);
+    if (rq.owners) {
+      if (rq.owned) launch_tiled_owned(run.F, T, tb.set_ptr.as<int>(), tb.owner.as<int>(), n_entries, tb.owned.as<int>(), s);
       FieldSets S{};
       S.owner = tb.owner.as<int>();
-      launch_field_gather(run.F, &S, tb.targets.as<int>(), run.n_targets, run.cost_at ? tb.cost_at.as<float>() : nullptr,
-                          run.hops_at ? tb.hops_at.as<int>() : nullptr, run.owner_at ? tb.owner_at.as<int>() : nullptr, s);
+      launch_field_gather(run.F, &S, tb.targets.as<int>(), rq.n_targets, rq.cost_at ? tb.cost_at.as<float>() : nullptr,
+                          rq.hops_at ? tb.hops_at.as<int>() : nullptr, rq.owner_at ? tb.owner_at.as<int>() : nullptr, s);
     }
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipEventRecord(tb.t1, s));
-    if (run.cost) HIPCHK(e, hipMemcpyAsync(run.cost, tb.cost.p, nO * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (run.hops) HIPCHK(e, hipMemcpyAsync(run.hops, tb.hops.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (run.parent) HIPCHK(e, hipMemcpyAsync(run.parent, tb.parent_out.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (run.owner) HIPCHK(e, hipMemcpyAsync(run.owner, tb.owner_out.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (run.owned && n_entries) HIPCHK(e, hipMemcpyAsync(run.owned, tb.owned.p, (size_t)n_entries * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (rq.cost) HIPCHK(e, hipMemcpyAsync(rq.cost, tb.cost.p, nO * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (rq.hops) HIPCHK(e, hipMemcpyAsync(rq.hops, tb.hops.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (rq.parent) HIPCHK(e, hipMemcpyAsync(rq.parent, tb.parent_out.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (rq.owner) HIPCHK(e, hipMemcpyAsync(rq.owner, tb.owner_out.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (rq.owned) HIPCHK(e, hipMemcpyAsync(rq.owned, tb.owned.p, (size_t)n_entries * sizeof(int), hipMemcpyDeviceToHost, s));
     if (nT) {
-      if (run.cost_at) HIPCHK(e, hipMemcpyAsync(run.cost_at, tb.cost_at.p, nT * sizeof(float), hipMemcpyDeviceToHost, s));
-      if (run.hops_at) HIPCHK(e, hipMemcpyAsync(run.hops_at, tb.hops_at.p, nT * sizeof(int), hipMemcpyDeviceToHost, s));
-      if (run.owner_at) HIPCHK(e, hipMemcpyAsync(run.owner_at, tb.owner_at.p, nT * sizeof(int), hipMemcpyDeviceToHost, s));
+      if (rq.cost_at) HIPCHK(e, hipMemcpyAsync(rq.cost_at, tb.cost_at.p, nT * sizeof(float), hipMemcpyDeviceToHost, s));
+      if (rq.hops_at) HIPCHK(e, hipMemcpyAsync(rq.hops_at, tb.hops_at.p, nT * sizeof(int), hipMemcpyDeviceToHost, s));
+      if (rq.owner_at) HIPCHK(e, hipMemcpyAsync(rq.owner_at, tb.owner_at.p, nT * sizeof(int), hipMemcpyDeviceToHost, s));
     }
     HIPCHK(e, hipStreamSynchronize(s));
     if (const TrgStatus st = tiled_lap(e, run); st != TRG_OK) return st;
@@ -497,9 +496,9 @@ TrgStatus tiled_outputs(TrgEngine *e, TiledRun &run) {
   return TRG_OK;
 }
 
-// The collective part of a solve whose arguments passed the checks that every rank makes alike: the two passes, a set
-// solve's owner pass, the outputs.  The owner pass always runs in a set solve: it is a collective, and whether it runs
-// must not hang on which outputs one rank asks for.
+// The collective part of a solve whose request passed tiled_check_request: the two passes, with owners the owner pass,
+// the outputs.  The owner pass is a collective: whether it runs hangs on the entry that was called, which every rank
+// decides alike, never on which outputs one rank asks for.
 TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
   ExchangeState &x = *e->exchange;
   TrgStatus local = tiled_prepare(e, x, run);
@@ -508,101 +507,59 @@ TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
     if (st != TRG_OK) return st;
     local = TRG_OK;  // (a pass that returns TRG_OK had no failure of this rank left to announce)
   }
-  if (run.sets())
+  if (run.rq.owners)
     if (const TrgStatus st = tiled_owner_pass(e, x, run); st != TRG_OK) return st;
   return tiled_outputs(e, run);
 }
 
-TrgStatus tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *source_gids, float *cost, int32_t *hops,
-                           int32_t *parent, TrgTiledFieldInfo *info) {
-  const Clock::time_point t_total = Clock::now();
-  // what every rank judges alike is refused before any collective
-  if (!e->exchange || !e->exchange->transport)
-    return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: no communicator (trg_engine_comm_init)");
-  if (m < 1 || m > TRG_FIELD_BATCH_MAX)
-    return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: m must be in [1, " + std::to_string(TRG_FIELD_BATCH_MAX) + "]");
-  if (!source_gids) return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: null source_gids");
-  if (!e->stitch_node_off.empty())
-    for (int k = 0; k < m; ++k)
-      if (source_gids[k] < 0 || source_gids[k] >= e->stitch_node_off.back())
-        return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: the source of field " + std::to_string(k) +
-                                                " is outside [0, " + std::to_string(e->stitch_node_off.back()) + ")");
-  TiledRun run{m, source_gids, cost, hops, parent};
-  if (const TrgStatus st = tiled_solve(e, run); st != TRG_OK) return st;
-  const FieldTiled &T = e->tiled->T;
-  info->exchanges = run.exchanges;
-  info->rounds = run.rounds;
-  info->ghosts = T.G;
-  info->border_nodes = T.B;
-  info->records_sent = run.records;
-  info->ms_device = (float)run.ms_device;
-  info->ms_total = (float)ms_since(t_total);
+// What every rank judges alike, refused before any collective.
+TrgStatus tiled_check_request(TrgEngine *e, const TiledRequest &rq) {
+  const std::string what = rq.what;
+  const auto refuse = [&](const std::string &why) { return e->fail(TRG_ERR_INVALID_ARG, what + why); };
+  if (!e->exchange || !e->exchange->transport) return refuse("no communicator (trg_engine_comm_init)");
+  if (rq.m < 1 || rq.m > TRG_FIELD_BATCH_MAX) return refuse("m must be in [1, " + std::to_string(TRG_FIELD_BATCH_MAX) + "]");
+  if (!rq.set_ptr || !rq.set_gids) return refuse(rq.null_ids);
+  if (rq.set_ptr[0] != 0) return refuse("set_ptr[0] must be 0");
+  for (int k = 0; k < rq.m; ++k) {
+    if (rq.set_ptr[k + 1] < rq.set_ptr[k]) return refuse("set_ptr decreases at set " + std::to_string(k));
+    if (rq.set_ptr[k + 1] == rq.set_ptr[k]) return refuse("set " + std::to_string(k) + " is empty");
+  }
+  const long long n_ids = e->stitch_node_off.empty() ? LLONG_MAX : e->stitch_node_off.back();  // (no stitch: tiled_graph refuses)
+  for (int k = 0; k < rq.m; ++k)
+    for (int j = rq.set_ptr[k]; j < rq.set_ptr[k + 1]; ++j) {
+      const std::string where = "entry " + std::to_string(j - rq.set_ptr[k]) + " of set " + std::to_string(k);
+      if (rq.set_gids[j] < 0 || rq.set_gids[j] >= n_ids)
+        return refuse((rq.source_noun ? rq.source_noun + std::to_string(k) : where + " (" + std::to_string(rq.set_gids[j]) + ")") +
+                      " is outside [0, " + std::to_string(n_ids) + ")");
+      if (rq.set_cost0) {
+        const float c = rq.set_cost0[j];
+        if (c != c || c < 0.0f || c == __builtin_huge_valf())
+          return refuse("the start cost of " + where + " is NaN, negative or infinite");
+      }
+    }
+  if (rq.n_targets < 0 || (rq.n_targets > 0 && !rq.targets))
+    return refuse("n_targets < 0, or targets is null with n_targets > 0");
   return TRG_OK;
 }
 
-struct TiledSetArgs {
-  int32_t m;
-  const int32_t *set_ptr, *set_gids;
-  const float *set_cost0;
-  float *cost;
-  int32_t *hops, *parent, *owner;
-  const int32_t *targets;
-  int32_t n_targets;
-  float *cost_at;
-  int32_t *hops_at, *owner_at, *owned;
-};
-
-TrgStatus tiled_cost_field_sets(TrgEngine *e, const TiledSetArgs &a, TrgTiledSetInfo *info) {
+// One call: the refusals, the solve, the fields that both info structs have, then the call's own through `more`.
+template <typename Info, typename More>
+TrgStatus tiled_call(TrgEngine *e, const TiledRequest &rq, Info *info, More more) {
   const Clock::time_point t_total = Clock::now();
-  const std::string what = "tiled cost field sets: ";
-  // what every rank judges alike is refused before any collective
-  if (!e->exchange || !e->exchange->transport)
-    return e->fail(TRG_ERR_INVALID_ARG, what + "no communicator (trg_engine_comm_init)");
-  if (a.m < 1 || a.m > TRG_FIELD_BATCH_MAX)
-    return e->fail(TRG_ERR_INVALID_ARG, what + "m must be in [1, " + std::to_string(TRG_FIELD_BATCH_MAX) + "]");
-  if (!a.set_ptr || !a.set_gids) return e->fail(TRG_ERR_INVALID_ARG, what + "null set_ptr or set_gids");
-  if (a.set_ptr[0] != 0) return e->fail(TRG_ERR_INVALID_ARG, what + "set_ptr[0] must be 0");
-  for (int k = 0; k < a.m; ++k) {
-    if (a.set_ptr[k + 1] < a.set_ptr[k]) return e->fail(TRG_ERR_INVALID_ARG, what + "set_ptr decreases at set " + std::to_string(k));
-    if (a.set_ptr[k + 1] == a.set_ptr[k]) return e->fail(TRG_ERR_INVALID_ARG, what + "set " + std::to_string(k) + " is empty");
-  }
-  for (int k = 0; k < a.m; ++k)
-    for (int j = a.set_ptr[k]; j < a.set_ptr[k + 1]; ++j) {
-      const std::string where = "entry " + std::to_string(j - a.set_ptr[k]) + " of set " + std::to_string(k);
-      if (!e->stitch_node_off.empty() && (a.set_gids[j] < 0 || a.set_gids[j] >= e->stitch_node_off.back()))
-        return e->fail(TRG_ERR_INVALID_ARG, what + where + " (" + std::to_string(a.set_gids[j]) + ") is outside [0, " +
-                                                std::to_string(e->stitch_node_off.back()) + ")");
-      if (a.set_cost0) {
-        const float c = a.set_cost0[j];
-        if (c != c || c < 0.0f || c == __builtin_huge_valf())
-          return e->fail(TRG_ERR_INVALID_ARG, what + "the start cost of " + where + " is NaN, negative or infinite");
-      }
-    }
-  if (a.n_targets < 0 || (a.n_targets > 0 && !a.targets))
-    return e->fail(TRG_ERR_INVALID_ARG, what + "n_targets < 0, or targets is null with n_targets > 0");
-  TiledRun run{a.m, nullptr, a.cost, a.hops, a.parent};
-  run.set_ptr = a.set_ptr;
-  run.set_gids = a.set_gids;
-  run.set_cost0 = a.set_cost0;
-  run.owner = a.owner;
-  run.targets = a.targets;
-  run.n_targets = a.n_targets;
-  run.cost_at = a.cost_at;
-  run.hops_at = a.hops_at;
-  run.owner_at = a.owner_at;
-  run.owned = a.owned;
+  Info local{};
+  Info &out = info ? *info : local;
+  out = Info{};
+  if (const TrgStatus st = tiled_check_request(e, rq); st != TRG_OK) return st;
+  TiledRun run{rq};
   if (const TrgStatus st = tiled_solve(e, run); st != TRG_OK) return st;
-  const FieldTiled &T = e->tiled->T;
-  info->exchanges = run.exchanges;
-  info->owner_exchanges = run.owner_exchanges;
-  info->rounds = run.rounds;
-  info->ghosts = T.G;
-  info->border_nodes = T.B;
-  info->roots = run.roots;
-  info->records_sent = run.records;
-  info->owner_records_sent = run.owner_records;
-  info->ms_device = (float)run.ms_device;
-  info->ms_total = (float)ms_since(t_total);
+  out.exchanges = run.exchanges;
+  out.rounds = run.rounds;
+  out.ghosts = e->tiled->T.G;
+  out.border_nodes = e->tiled->T.B;
+  out.records_sent = run.records;
+  more(out, run);
+  out.ms_device = (float)run.ms_device;
+  out.ms_total = (float)ms_since(t_total);
   return TRG_OK;
 }
 
@@ -623,10 +580,11 @@ extern "C" {
 TrgStatus trg_engine_tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *source_gids, float *cost, int32_t *hops,
                                       int32_t *parent, TrgTiledFieldInfo *info) {
   return entry(e, "tiled_cost_field", DEVICE, [&] {
-    TrgTiledFieldInfo local{};
-    TrgTiledFieldInfo *out = info ? info : &local;
-    *out = TrgTiledFieldInfo{};
-    return tiled_cost_field(e, m, source_gids, cost, hops, parent, out);
+    int32_t one_each[TRG_FIELD_BATCH_MAX + 1];  // m sets of one entry
+    for (int k = 0; k <= TRG_FIELD_BATCH_MAX; ++k) one_each[k] = k;
+    const TiledRequest rq{m, one_each, source_gids, nullptr, cost, hops, parent, false, "tiled cost field: ",
+                          "null source_gids", "the source of field "};
+    return tiled_call(e, rq, info, [](TrgTiledFieldInfo &, const TiledRun &) {});
   });
 }
 
@@ -635,11 +593,13 @@ TrgStatus trg_engine_tiled_cost_field_sets(TrgEngine *e, int32_t m, const int32_
                                            int32_t *owner, const int32_t *targets, int32_t n_targets, float *cost_at,
                                            int32_t *hops_at, int32_t *owner_at, int32_t *owned, TrgTiledSetInfo *info) {
   return entry(e, "tiled_cost_field_sets", DEVICE, [&] {
-    TrgTiledSetInfo local{};
-    TrgTiledSetInfo *out = info ? info : &local;
-    *out = TrgTiledSetInfo{};
-    return tiled_cost_field_sets(e, TiledSetArgs{m, set_ptr, set_gids, set_cost0, cost, hops, parent, owner, targets,
-                                                 n_targets, cost_at, hops_at, owner_at, owned}, out);
+    const TiledRequest rq{m, set_ptr, set_gids, set_cost0, cost, hops, parent, true, "tiled cost field sets: ",
+                          "null set_ptr or set_gids", nullptr, owner, targets, n_targets, cost_at, hops_at, owner_at, owned};
+    return tiled_call(e, rq, info, [](TrgTiledSetInfo &out, const TiledRun &run) {
+      out.owner_exchanges = run.owner_exchanges;
+      out.roots = run.roots;
+      out.owner_records_sent = run.owner_records;
+    });
   });
 }
 

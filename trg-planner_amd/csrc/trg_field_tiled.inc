@@ -10,9 +10,10 @@
 // k_field_edge_cost gives every edge INTO a ghost the skip marker: no relaxation here ever writes a ghost's key, it
 // only mirrors its owner's (k_tiled_merge).
 //
-// A set solve ("Source sets across tiles") adds the seeding of this rank's own entries (k_tiled_seed_sets) and, after
-// the parent sweep, the owner pass: k_tiled_forest_begin, the jumping sweeps of trg_field.hip, then per exchange
-// k_tiled_owner_merge / _resolve / _publish; k_tiled_output_owner and k_tiled_owned write what the rank puts out.
+// Every solve starts from source sets ("Source sets across tiles"; a single source is a set of one): k_tiled_seed runs
+// over this rank's own entries.  The set call adds, after the parent sweep, the owner pass: k_tiled_forest_begin, the
+// jumping sweeps of trg_field.hip, then per exchange k_tiled_owner_merge / _resolve and the publish kernel again;
+// k_tiled_output writes the owners beside the fields and k_tiled_owned the counts per entry.
 //
 // All kernels: wave64, bounds taken from the arguments, no scalar memory writes, nothing waits on another workgroup.
 
@@ -25,6 +26,25 @@ struct TiledRec {
 };
 static_assert(sizeof(TiledRec) == 16 && sizeof(TiledRec) == FIELD_TILED_REC_BYTES, "record layout");
 
+// Is global id g a node of another tile?  The first half of the ghost lookup, and all that k_tiled_mark can ask: it
+// runs before the ghost table exists.
+__device__ __forceinline__ bool tiled_foreign(int lo, int V, int Vg, int g) {
+  return g >= 0 && g < Vg && (g < lo || g >= lo + V);
+}
+
+// The ghost index of global id g on this rank, or -1: an own node, an id out of range, or a node that is no ghost here.
+__device__ __forceinline__ int tiled_ghost(const FieldTiled &T, int g) {
+  if (!tiled_foreign(T.lo, T.V, T.Vg, g) || !T.ghost_flag[g]) return -1;
+  const int j = T.ghost_off[g];
+  return j < T.G ? j : -1;
+}
+
+// the ghost item that a gathered record names, or -1: a record of this rank's own, or one that names no ghost of it
+__device__ __forceinline__ int tiled_rec_item(const FieldDev &F, const FieldTiled &T, const TiledRec &r) {
+  const int j = r.field >= 0 && r.field < F.m ? tiled_ghost(T, r.gid) : -1;
+  return j < 0 ? -1 : r.field * F.V + T.V + j;
+}
+
 // One thread per local row: flags the remote ends of its cross edges in the global table and the row as a border
 // row.  (Several rows may flag one ghost: every store writes the same word.)
 __global__ __launch_bounds__(THREADS) void k_tiled_mark(const int *__restrict__ rowptr, const int *__restrict__ col,
@@ -33,7 +53,7 @@ __global__ __launch_bounds__(THREADS) void k_tiled_mark(const int *__restrict__ 
     int border = 0;
     for (int k = rowptr[u], kend = rowptr[u + 1]; k < kend; ++k) {
       const int c = col[k];
-      if (c >= 0 && c < Vg && (c < lo || c >= lo + V)) {
+      if (tiled_foreign(lo, V, Vg, c)) {
         ghost_flag[c] = 1;
         border = 1;
       }
@@ -72,8 +92,8 @@ __global__ __launch_bounds__(THREADS) void k_tiled_ghost_deg(FieldTiled T, const
                                                              const int *__restrict__ col, int *ghost_deg) {
   for (int u = blockIdx.x * blockDim.x + threadIdx.x; u < T.V; u += gridDim.x * blockDim.x)
     for (int k = rowptr[u], kend = rowptr[u + 1]; k < kend; ++k) {
-      const int c = col[k];
-      if (c >= 0 && c < T.Vg && (c < T.lo || c >= T.lo + T.V)) atomicAdd(&ghost_deg[T.ghost_off[c]], 1);
+      const int j = tiled_ghost(T, col[k]);
+      if (j >= 0) atomicAdd(&ghost_deg[j], 1);
     }
 }
 
@@ -97,10 +117,10 @@ __global__ __launch_bounds__(THREADS) void k_tiled_fill(FieldTiled T, const int 
       const int c = col[k];
       w2[k] = w[k];
       dist2[k] = dist[k];
+      const int j = tiled_ghost(T, c);
       if (c >= T.lo && c < T.lo + T.V) {
         col2[k] = c - T.lo;
-      } else if (c >= 0 && c < T.Vg) {
-        const int j = T.ghost_off[c];
+      } else if (j >= 0) {
         col2[k] = T.V + j;
         const int slot = E_local + ghost_row[j] + atomicAdd(&ghost_fill[j], 1);
         if (slot < E2) {
@@ -115,27 +135,14 @@ __global__ __launch_bounds__(THREADS) void k_tiled_fill(FieldTiled T, const int 
   }
 }
 
-// One thread per field, after k_field_init without sources: a field whose source is this rank's node starts there.
-__global__ void k_tiled_seed(FieldDev F, FieldSources S) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= F.m) return;
-  const int src = S.id[f];
-  if (src < 0 || src >= F.V) return;
-  const int item = f * F.V + src;
-  F.key[item] = 0ull;
-  const int slot = atomicAdd(&F.ctrl->c.n[0], 1);
-  F.q[0][slot] = item;  // (slot < m <= N)
-  atomicAdd(&F.ctrl->s.work, 1);
-}
-
-// Source sets across tiles (DESIGN.md section 7, "Source sets across tiles"): one thread per entry of this rank's entry
-// table -- the entries of all sets whose member is this rank's node, which the host splits off per call; a member that
-// is a ghost here is seeded by its owner and mirrored like any key.  k_field_seed<true>'s rule with the GLOBAL entry
+// The seeding of every solve (DESIGN.md section 7, "Source sets across tiles"): one thread per entry of this rank's entry
+// table -- the entries of all sets whose member is this rank's node, which the host splits off per call (a single
+// source: a set of one entry at cost 0); a member that is a ghost here is seeded by its owner and mirrored like any key.  k_field_seed<true>'s rule with the GLOBAL entry
 // index in the member mark, so that "the least entry" is the same on every rank.  Pass 1: the item's key is the least
 // of its entries' start costs (atomicMin), queued once.  Pass 2 (F.tight, pass 1's cost bits): only an entry whose
 // start cost is the item's least cost seeds it -- a root, whose key (c0, 0) is below every tight extension (hops >= 1),
 // so no relaxation pushes or stamps it and its mark stays.
-__global__ __launch_bounds__(THREADS) void k_tiled_seed_sets(FieldDev F, const TiledEntry *__restrict__ ent, int n) {
+__global__ __launch_bounds__(THREADS) void k_tiled_seed(FieldDev F, const TiledEntry *__restrict__ ent, int n) {
   const int n_iter = (n + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
   for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
     bool first = false;
@@ -164,10 +171,13 @@ __global__ __launch_bounds__(THREADS) void k_tiled_seed_sets(FieldDev F, const T
   }
 }
 
-// Publish: over (field, border row) pairs, those whose key is below what this rank last published become records,
-// compacted with one atomic per wave.  `published` has m * B words, `rec` room for as many records.
-__global__ __launch_bounds__(THREADS) void k_tiled_publish(FieldDev F, FieldTiled T, unsigned long long *published,
-                                                           TiledRec *rec, int *n_rec) {
+// Publish: over (field, border row) pairs, those with news become records, compacted with one atomic per wave.
+// `published` has m * B words, `rec` room for as many records.  A pass (`owner` is not read): the key is news where it
+// is below what this rank last published, and travels.  OWNERS, the owner pass: the owner is news once it is known, and
+// travels in the key word; the published word is all ones until then, so that an item is published once.
+template <bool OWNERS>
+__global__ __launch_bounds__(THREADS) void k_tiled_publish(FieldDev F, FieldTiled T, const int *__restrict__ owner,
+                                                           unsigned long long *published, TiledRec *rec, int *n_rec) {
   const int items = F.m * T.B;
   const int n_iter = (items + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
   for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
@@ -176,13 +186,19 @@ __global__ __launch_bounds__(THREADS) void k_tiled_publish(FieldDev F, FieldTile
     if (i < items) {
       const int f = i / T.B;
       const int v = T.border[i - f * T.B];
-      const unsigned long long k = F.key[f * F.V + v];
-      news = k < published[i];
+      const int item = f * F.V + v;
+      if constexpr (OWNERS) {
+        const int o = owner[item];
+        news = o >= 0 && published[i] != 0ull;
+        r.key = (unsigned long long)(unsigned)o;
+      } else {
+        r.key = F.key[item];
+        news = r.key < published[i];
+      }
       if (news) {
-        published[i] = k;
+        published[i] = OWNERS ? 0ull : r.key;
         r.field = f;
         r.gid = T.lo + v;
-        r.key = k;
       }
     }
     const int slot = wave_reserve(news, n_rec);
@@ -204,17 +220,11 @@ __global__ __launch_bounds__(THREADS) void k_tiled_merge(FieldDev F, FieldTiled 
     int item = 0;
     if (i < n_rec) {
       const TiledRec r = rec[i];
-      const bool own = r.gid >= T.lo && r.gid < T.lo + T.V;
-      if (!own && r.gid >= 0 && r.gid < T.Vg && r.field >= 0 && r.field < F.m && T.ghost_flag[r.gid]) {
-        const int j = T.ghost_off[r.gid];
-        if (j < T.G) {
-          item = r.field * F.V + T.V + j;
-          if (r.key < F.key[item]) {
-            F.key[item] = r.key;
-            F.stamp_far[item] = phase;
-            push = true;
-          }
-        }
+      item = tiled_rec_item(F, T, r);
+      if (item >= 0 && r.key < F.key[item]) {
+        F.key[item] = r.key;
+        F.stamp_far[item] = phase;
+        push = true;
       }
     }
     const int slot = wave_reserve(push, &F.ctrl->c.nfar[fs]);
@@ -246,9 +256,10 @@ __global__ __launch_bounds__(THREADS) void k_tiled_parent(FieldDev F, FieldTiled
   }
 }
 
-// grid.y = field: this rank's own nodes only, m x V_local
+// grid.y = field: this rank's own nodes only, m x V_local; with owner_out (else nullptr) their owners too
 __global__ __launch_bounds__(THREADS) void k_tiled_output(FieldDev F, FieldTiled T, float *cost, int *hops,
-                                                          int *parent) {
+                                                          int *parent, const int *__restrict__ owner,
+                                                          int *owner_out) {
   const int fbase = blockIdx.y * F.V, obase = blockIdx.y * T.V;
   for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < T.V; v += gridDim.x * blockDim.x) {
     const unsigned long long k = F.key[fbase + v];
@@ -257,6 +268,7 @@ __global__ __launch_bounds__(THREADS) void k_tiled_output(FieldDev F, FieldTiled
     hops[obase + v] = reached ? (int)(unsigned)k : -1;
     const int p = F.parent[fbase + v];
     parent[obase + v] = p == INT_MAX ? -1 : p;
+    if (owner_out) owner_out[obase + v] = owner[fbase + v];
   }
 }
 
@@ -289,12 +301,9 @@ __global__ __launch_bounds__(THREADS) void k_tiled_forest_begin(FieldDev F, Fiel
           root = true;
         } else {
           const int p = F.parent[i];
-          if (p >= T.lo && p < T.lo + T.V) {
-            a = fbase + (p - T.lo);
-          } else if (p >= 0 && p < T.Vg && T.ghost_flag[p]) {
-            const int j = T.ghost_off[p];
-            if (j < T.G) a = fbase + T.V + j;
-          }
+          const int j = tiled_ghost(T, p);
+          if (p >= T.lo && p < T.lo + T.V) a = fbase + (p - T.lo);
+          else if (j >= 0) a = fbase + T.V + j;
         }
       }
       anc[i] = a;
@@ -312,11 +321,8 @@ __global__ __launch_bounds__(THREADS) void k_tiled_owner_merge(FieldDev F, Field
                                                                const TiledRec *__restrict__ rec, int n_rec, int *owner) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += gridDim.x * blockDim.x) {
     const TiledRec r = rec[i];
-    const bool own = r.gid >= T.lo && r.gid < T.lo + T.V;
-    if (!own && r.gid >= 0 && r.gid < T.Vg && r.field >= 0 && r.field < F.m && T.ghost_flag[r.gid]) {
-      const int j = T.ghost_off[r.gid];
-      if (j < T.G) owner[r.field * F.V + T.V + j] = (int)(unsigned)r.key;
-    }
+    const int item = tiled_rec_item(F, T, r);
+    if (item >= 0) owner[item] = (int)(unsigned)r.key;
   }
 }
 
@@ -329,43 +335,6 @@ __global__ __launch_bounds__(THREADS) void k_tiled_owner_resolve(const int *__re
     const int o = owner[a];
     if (o >= 0) owner[i] = o;
   }
-}
-
-// Publish: over (field, border row) pairs, those whose owner is known and not yet published become records, compacted
-// with one atomic per wave.  `published` has m * B words, all ones until the item is published; `rec` room for as
-// many records.
-__global__ __launch_bounds__(THREADS) void k_tiled_owner_publish(FieldDev F, FieldTiled T,
-                                                                 const int *__restrict__ owner,
-                                                                 unsigned long long *published, TiledRec *rec,
-                                                                 int *n_rec) {
-  const int items = F.m * T.B;
-  const int n_iter = (items + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
-  for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
-    bool news = false;
-    TiledRec r{};
-    if (i < items) {
-      const int f = i / T.B;
-      const int v = T.border[i - f * T.B];
-      const int o = owner[f * F.V + v];
-      news = o >= 0 && published[i] != 0ull;
-      if (news) {
-        published[i] = 0ull;
-        r.field = f;
-        r.gid = T.lo + v;
-        r.key = (unsigned long long)(unsigned)o;
-      }
-    }
-    const int slot = wave_reserve(news, n_rec);
-    if (news && slot < items) rec[slot] = r;
-  }
-}
-
-// grid.y = field: the owners of this rank's own nodes, m x V_local
-__global__ __launch_bounds__(THREADS) void k_tiled_output_owner(FieldDev F, FieldTiled T,
-                                                                const int *__restrict__ owner, int *out) {
-  const int fbase = blockIdx.y * F.V, obase = blockIdx.y * T.V;
-  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < T.V; v += gridDim.x * blockDim.x)
-    out[obase + v] = owner[fbase + v];
 }
 
 // grid.y = field: a histogram of the owners of this rank's own nodes (k_field_owned's shape, the ghosts left out: the
@@ -417,24 +386,23 @@ void launch_tiled_fill(const FieldTiled &T, const int *rowptr, const int *col, c
                      dist, E_local, E2, ghost_row, ghost_fill, rowptr2, col2, w2, dist2);
 }
 
-void launch_tiled_begin(const FieldDev &F, const FieldTiled &T, const FieldSources &local_sources,
-                        const TiledEntry *entries, int n_entries, float delta, unsigned long long *published,
-                        hipStream_t s) {
-  hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, local_sources,
-                     delta, false, (const unsigned long long *)nullptr);
-  if (!entries) hipLaunchKernelGGL(k_tiled_seed, dim3(1), dim3(FIELD_MAX_SOURCES), 0, s, F, local_sources);
-  else if (n_entries > 0)
-    hipLaunchKernelGGL(k_tiled_seed_sets, dim3(field_blocks(n_entries, THREADS)), dim3(THREADS), 0, s, F, entries,
-                       n_entries);
+void launch_tiled_begin(const FieldDev &F, const FieldTiled &T, const TiledEntry *entries, int n_entries, float delta,
+                        unsigned long long *published, hipStream_t s) {
+  hipLaunchKernelGGL(k_field_init, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, FieldSources{}, delta,
+                     false, (const unsigned long long *)nullptr);
+  if (n_entries > 0)
+    hipLaunchKernelGGL(k_tiled_seed, dim3(field_blocks(n_entries, THREADS)), dim3(THREADS), 0, s, F, entries, n_entries);
   (void)hipMemsetAsync(published, 0xFF, ((size_t)F.m * T.B + 1) * sizeof(unsigned long long), s);
 }
 
-void launch_tiled_publish(const FieldDev &F, const FieldTiled &T, unsigned long long *published, void *rec,
-                          int *n_rec, hipStream_t s) {
+void launch_tiled_publish(const FieldDev &F, const FieldTiled &T, const int *owner, unsigned long long *published,
+                          void *rec, int *n_rec, hipStream_t s) {
   (void)hipMemsetAsync(n_rec, 0, sizeof(int), s);
-  if (T.B > 0)
-    hipLaunchKernelGGL(k_tiled_publish, dim3(field_blocks((long long)F.m * T.B, THREADS)), dim3(THREADS), 0, s, F, T,
-                       published, (TiledRec *)rec, n_rec);
+  if (T.B <= 0) return;
+  const dim3 grid(field_blocks((long long)F.m * T.B, THREADS));
+  TiledRec *out = (TiledRec *)rec;
+  if (owner) hipLaunchKernelGGL(k_tiled_publish<true>, grid, dim3(THREADS), 0, s, F, T, owner, published, out, n_rec);
+  else hipLaunchKernelGGL(k_tiled_publish<false>, grid, dim3(THREADS), 0, s, F, T, owner, published, out, n_rec);
 }
 
 void launch_tiled_merge(const FieldDev &F, const FieldTiled &T, const void *rec, int n_rec, hipStream_t s) {
@@ -449,11 +417,11 @@ void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s)
 }
 
 void launch_tiled_finish(const FieldDev &F, const FieldTiled &T, float *cost, int *hops, int *parent, bool parents,
-                         hipStream_t s) {
+                         const int *owner, int *owner_out, hipStream_t s) {
   if (parents) launch_tiled_parents(F, T, s);
   if (T.V > 0)
     hipLaunchKernelGGL(k_tiled_output, dim3(field_blocks(T.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, cost, hops,
-                       parent);
+                       parent, owner, owner_out);
 }
 
 void launch_tiled_forest_begin(const FieldDev &F, const FieldTiled &T, const int *set_ptr, int *owner, int *changed,
@@ -471,17 +439,13 @@ void launch_tiled_owner_step(const FieldDev &F, const FieldTiled &T, const void 
     hipLaunchKernelGGL(k_tiled_owner_merge, dim3(field_blocks(n_in, THREADS)), dim3(THREADS), 0, s, F, T,
                        (const TiledRec *)rec_in, n_in, owner);
   hipLaunchKernelGGL(k_tiled_owner_resolve, dim3(field_blocks(F.N, THREADS)), dim3(THREADS), 0, s, anc, owner, F.N);
-  (void)hipMemsetAsync(n_rec, 0, sizeof(int), s);
-  if (T.B > 0)
-    hipLaunchKernelGGL(k_tiled_owner_publish, dim3(field_blocks((long long)F.m * T.B, THREADS)), dim3(THREADS), 0, s,
-                       F, T, owner, published, (TiledRec *)rec, n_rec);
+  launch_tiled_publish(F, T, owner, published, rec, n_rec, s);
 }
 
-void launch_tiled_owner_outputs(const FieldDev &F, const FieldTiled &T, const int *set_ptr, const int *owner,
-                                int n_entries, int *owner_out, int *owned, hipStream_t s) {
-  if (owned) (void)hipMemsetAsync(owned, 0, (size_t)n_entries * sizeof(int), s);
-  if (T.V <= 0) return;
-  const dim3 grid(field_blocks(T.V, THREADS), F.m);
-  if (owner_out) hipLaunchKernelGGL(k_tiled_output_owner, grid, dim3(THREADS), 0, s, F, T, owner, owner_out);
-  if (owned) hipLaunchKernelGGL(k_tiled_owned, grid, dim3(THREADS), 0, s, F, T, set_ptr, owner, n_entries, owned);
+void launch_tiled_owned(const FieldDev &F, const FieldTiled &T, const int *set_ptr, const int *owner, int n_entries,
+                        int *owned, hipStream_t s) {
+  (void)hipMemsetAsync(owned, 0, (size_t)n_entries * sizeof(int), s);
+  if (T.V > 0)
+    hipLaunchKernelGGL(k_tiled_owned, dim3(field_blocks(T.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, set_ptr, owner,
+                       n_entries, owned);
 }

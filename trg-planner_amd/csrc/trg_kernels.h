@@ -625,48 +625,45 @@ void launch_tiled_tables(const FieldTiled &T, const int *state, const int *borde
 void launch_tiled_fill(const FieldTiled &T, const int *rowptr, const int *col, const float *w, const float *dist,
                        int E_local, int E2, const int *ghost_row, int *ghost_fill, int *rowptr2, int *col2,
                        float *w2, float *dist2, hipStream_t s);
-// Source sets across tiles ("Source sets across tiles"): one entry of a set whose member is this
-// rank's node, as the host splits them off per call.  `entry` is the GLOBAL index into the call's set_gids, which the
-// member marks carry, so that the least entry of a node is the same on every rank.
+// One entry of a source set whose member is this rank's node, as the host splits them off per call (DESIGN.md
+// section 7, "Source sets across tiles"; a single source is a set of one).  `entry` is the GLOBAL index into the call's
+// set_gids, which the member marks carry, so that the least entry of a node is the same on every rank.
 struct TiledEntry {
   int field, node;   // the set, and the member's local id
   int entry;         // index into set_gids
   unsigned cost0;    // the start cost, bits of set_cost0[entry] + 0
 };
 static_assert(sizeof(TiledEntry) == 16, "entry layout");
-// A pass begins: no item has a key but the fields' sources that are this rank's nodes, which are queued -- with
-// `entries` == nullptr local_sources (a local id, or -1), else the n_entries set entries of this rank, as
+// A pass begins: no item has a key but the members that are this rank's nodes -- its n_entries entries, queued as
 // launch_field_init's seeded sets: in pass 1 each at its start cost, in pass 2 (F.tight set) the roots only, whose
 // member marks then stay.  Nothing is published (m * B + 1 words).
-void launch_tiled_begin(const FieldDev &F, const FieldTiled &T, const FieldSources &local_sources,
-                        const TiledEntry *entries, int n_entries, float delta, unsigned long long *published,
-                        hipStream_t s);
-// records (m * B of FIELD_TILED_REC_BYTES at most) of the border items whose key dropped below the published one;
-// *n_rec (zeroed here) counts them
-void launch_tiled_publish(const FieldDev &F, const FieldTiled &T, unsigned long long *published, void *rec,
-                          int *n_rec, hipStream_t s);
+void launch_tiled_begin(const FieldDev &F, const FieldTiled &T, const TiledEntry *entries, int n_entries, float delta,
+                        unsigned long long *published, hipStream_t s);
+// records (m * B of FIELD_TILED_REC_BYTES at most; *n_rec, zeroed here, counts them) of the border items with news.
+// owner == nullptr, a pass: the key dropped below the published one.  Else the owner pass: the item's owner is known
+// and unpublished; it travels in the record's key word.
+void launch_tiled_publish(const FieldDev &F, const FieldTiled &T, const int *owner, unsigned long long *published,
+                          void *rec, int *n_rec, hipStream_t s);
 // the gathered records of all ranks into this rank's ghosts; what improved is queued for launch_field_round
 void launch_tiled_merge(const FieldDev &F, const FieldTiled &T, const void *rec, int n_rec, hipStream_t s);
-// parents as least global ids (when asked for), then cost / hops / parent of the local nodes, m x T.V
+// parents as least global ids (when asked for), then cost / hops / parent of the local nodes, m x T.V, and with
+// owner_out (else nullptr) their owners from `owner`, the owner pass's m x (V + G) words
 void launch_tiled_finish(const FieldDev &F, const FieldTiled &T, float *cost, int *hops, int *parent, bool parents,
-                         hipStream_t s);
-// the parent sweep alone (a set solve runs it before its owner pass; launch_tiled_finish then goes without)
+                         const int *owner, int *owner_out, hipStream_t s);
+// the parent sweep alone (the set call runs it before its owner pass; launch_tiled_finish then goes without)
 void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s);
-// The owner pass of a set solve across tiles, after the parent sweep.  begin: F.q[0] = every item's first ancestor (a
-// local root and a ghost with a key: itself; another item with a key: its parent's solve-graph item), owner (m x (V +
-// G)) = the roots' entries counted from set_ptr[field], -1 elsewhere, *n_roots their count; changed
-// (FIELD_OWNER_SWEEPS_MAX words) and published (m * B + 1 words) are reset.  Then launch_field_owner_sweep until a
-// sweep moves nothing.
+// The owner pass of the set call, after the parent sweep.  begin: F.q[0] = every item's first ancestor (a local root
+// and a ghost with a key: itself; another item with a key: its parent's solve-graph item), owner (m x (V + G)) = the
+// roots' entries counted from set_ptr[field], -1 elsewhere, *n_roots their count; changed (FIELD_OWNER_SWEEPS_MAX
+// words) and published (m * B + 1 words) are reset.  Then launch_field_owner_sweep until a sweep moves nothing.
 void launch_tiled_forest_begin(const FieldDev &F, const FieldTiled &T, const int *set_ptr, int *owner, int *changed,
                                int *n_roots, unsigned long long *published, hipStream_t s);
 // One step of the owner exchange: the gathered owner records of all ranks (rec_in, n_in) into this rank's ghost
-// items, every item without an owner takes its final ancestor's (anc) where known, and the border items whose owner
-// is known and unpublished become records (rec, *n_rec zeroed here; the owner travels in the record's key word).
+// items, every item without an owner takes its final ancestor's (anc) where known, then launch_tiled_publish's owners.
 void launch_tiled_owner_step(const FieldDev &F, const FieldTiled &T, const void *rec_in, int n_in, const int *anc,
                              int *owner, unsigned long long *published, void *rec, int *n_rec, hipStream_t s);
-// owner_out (m x T.V, may be nullptr) = the owners of the local nodes; owned (n_entries, zeroed here, may be nullptr) =
-// the local nodes per entry
-void launch_tiled_owner_outputs(const FieldDev &F, const FieldTiled &T, const int *set_ptr, const int *owner,
-                                int n_entries, int *owner_out, int *owned, hipStream_t s);
+// owned (n_entries, zeroed here) = the local nodes per entry
+void launch_tiled_owned(const FieldDev &F, const FieldTiled &T, const int *set_ptr, const int *owner, int n_entries,
+                        int *owned, hipStream_t s);
 
 }  // namespace trg
