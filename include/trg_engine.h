@@ -713,9 +713,9 @@ TrgStatus trg_engine_risk_field_refresh(TrgEngine *e,
  * (TRG_ERR_INVALID_ARG), m x (nodes + ghosts) beyond the solver's 32-bit item index or no device memory
  * (TRG_ERR_CAPACITY), a queue overflow (TRG_ERR_DEVICE) -- is announced in the next count exchange: that rank returns
  * its error, every other rank TRG_ERR_DEVICE "another rank reported a failure", none waits.  TRG_ERR_DEVICE on every
- * rank at once when the exchanges do not converge.  Source sets and start costs are the call below; bounds, cost
- * models, risk fields, refresh and device-side routes are not offered across tiles, and neither call touches the
- * retained single-engine solve. */
+ * rank at once when the exchanges do not converge.  Source sets and start costs are the call below, routes
+ * trg_engine_tiled_field_routes; bounds, cost models, risk fields and refresh are not offered across tiles, and none
+ * of these calls touches the retained single-engine solve. */
 typedef struct TrgTiledFieldInfo {
   int32_t exchanges;     /* all-gather-v exchanges of both passes, the two that found no news included */
   int32_t rounds;        /* relaxation rounds of this rank that did work */
@@ -758,8 +758,8 @@ TrgStatus trg_engine_tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *so
  * (TRG_ERR_INVALID_ARG), an allocation (TRG_ERR_CAPACITY), a bad edge cost, a queue overflow -- is announced in the
  * next count exchange, of the owner exchanges as well: that rank returns its error, its peers TRG_ERR_DEVICE "another
  * rank reported a failure", nobody waits.  An owner loop that outlasts m x (border nodes of all ranks) + 2 exchanges
- * ends with TRG_ERR_DEVICE on every rank at once.  Bounds, cost models, risk fields, refresh and device-side routes
- * are not offered across tiles; the retained single-engine solve is left alone. */
+ * ends with TRG_ERR_DEVICE on every rank at once.  Routes are trg_engine_tiled_field_routes; bounds, cost models, risk
+ * fields and refresh are not offered across tiles; the retained single-engine solve is left alone. */
 typedef struct TrgTiledSetInfo {
   int32_t exchanges;           /* all-gather-v exchanges of passes 1 and 2, the two without news included */
   int32_t owner_exchanges;     /* ... of the owner pass, the one without news included */
@@ -778,6 +778,60 @@ TrgStatus trg_engine_tiled_cost_field_sets(TrgEngine *e, int32_t m,
     const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
     int32_t *owned,                                                /* set_ptr[m], may be NULL */
     TrgTiledSetInfo *info);                                        /* may be NULL */
+/* Routes across tiles ("Routes across tiles"): the paths behind the keys of the LAST tiled solve
+ * (either call above), walked on the devices.  A successful tiled solve stays on every rank's device; a new tiled solve
+ * replaces it from its start (one that fails leaves none), and a change of the tile's graph, a new stitch or another
+ * safety factor makes it stale.  A collective call: every rank makes it with the same arguments.
+ * Route r is field route_field[r] (0 .. m-1 of that solve) to the node with GLOBAL id route_target_gid[r], any rank's
+ * node.  It is exactly what trg_engine_field_routes defines, on the global stitched graph G with the solve's global
+ * parents: the hops + 1 nodes from the root to the target; the route edge into p_i is the tight, relaxable edge of least
+ * CSR index in row p_{i-1} of G; path_length and the risk sum are fp32 left folds from the target end backwards, avg_risk
+ * the risk sum / num_nodes in fp32, cost the key's cost word (a start cost included); an unreached target has the empty
+ * route.  The rank that owns a node walks the route while it stands on its nodes and hands it, with the sums so far, to
+ * the owner of the parent at a seam: the fold is one fold across any number of seams.
+ * Every rank receives the same offsets and the same infos for ALL routes: offsets from the full lengths and cap, clipped
+ * as trg_engine_field_routes clips them (the source end is kept, later routes are empty ranges, infos[r].num_nodes keeps
+ * the full length, and a second call with room needs no new solve).  In node_gids / xyz a rank receives only the
+ * positions of ITS OWN nodes -- the global id, and the position from its node mirror; every other position holds -1 /
+ * NaN.  Position offsets[r] + i holds the node with hops == i, so a route that leaves a tile and comes back fills two
+ * stretches; trg_planner.tiled.join_routes merges the ranks' arrays.  With node_gids and xyz both NULL (or cap == 0)
+ * the call returns infos only and every offset is 0.  If the solve was asked for no parents (the single-source call with
+ * parent == NULL), the call runs the parent sweep first, local work.
+ * The exchanges: one for the lengths (the only records a host downloads: n_routes x 16 bytes), one per stretch of the
+ * route with the most seam crossings, one without news: exactly c + 3 for c crossings, beyond the largest num_nodes + 3
+ * TRG_ERR_DEVICE on every rank at once.
+ * The stitch emits one cross edge per unordered pair of nodes, so the seam edge of a step is unambiguous; for
+ * hand-assembled rows (trg_engine_stitch_assemble) that repeat a pair, which of the tight duplicates the sums take is
+ * unspecified.  Duplicate edges inside a tile are decided by the least CSR index, as on one engine.
+ * TRG_ERR_INVALID_ARG before any collective, the group and the retained solve still usable, for what every rank judges
+ * alike: no communicator; n_routes < 0; cap < 0; NULL route_field, route_target_gid or offsets with n_routes > 0; a
+ * target outside [0, nodes of G) (where the stitch's offsets are known).  n_routes == 0 is TRG_OK without a collective.
+ * A rank's own failure -- no retained tiled solve or a stale one (TRG_ERR_INVALID_ARG; the message says which), a field
+ * outside [0, m) (TRG_ERR_INVALID_ARG; the message names the route), an allocation (TRG_ERR_CAPACITY), a walk that lost
+ * its way (TRG_ERR_DEVICE: damaged arrays) -- is announced in the next count exchange: that rank returns its error, its
+ * peers TRG_ERR_DEVICE "another rank reported a failure", nobody waits.  The retained single-engine solve
+ * (trg_engine_field_routes) is neither read nor touched. */
+typedef struct TrgTiledRouteInfo {
+  int32_t num_nodes;  /* full length of the route, 0 if the target is unreachable */
+  float cost, path_length, avg_risk;
+  int32_t root_gid;   /* the global id of the node the route starts at, -1 for the empty route */
+  int32_t owner;      /* a set solve: the entry of the route's set that root is, counted from set_ptr[k]; else -1 */
+} TrgTiledRouteInfo;
+typedef struct TrgTiledRoutesInfo {
+  int32_t exchanges;     /* all-gather-v exchanges of this call, the one without news included */
+  int32_t max_nodes;     /* the longest route's num_nodes */
+  int64_t records_sent;  /* LEN, HANDOFF and END records this rank published */
+  float ms_device;       /* as TrgTiledFieldInfo's */
+  float ms_total;        /* host wall time */
+} TrgTiledRoutesInfo;
+TrgStatus trg_engine_tiled_field_routes(TrgEngine *e, int32_t n_routes,
+    const int32_t *route_field, const int32_t *route_target_gid,
+    int32_t *offsets,      /* n_routes + 1 */
+    int32_t *node_gids,    /* room for cap global ids, may be NULL */
+    float *xyz,            /* room for cap x 3, may be NULL */
+    int32_t cap,
+    TrgTiledRouteInfo *infos,    /* n_routes, may be NULL */
+    TrgTiledRoutesInfo *info);   /* may be NULL */
 /* The global ids of the current stitch: this tile's first global id, its node count and the global graph's.
  * TRG_ERR_INVALID_ARG without current stitched rows. */
 TrgStatus trg_engine_stitch_ids(TrgEngine *e, int32_t *first_gid, int32_t *num_nodes, int32_t *total_nodes);

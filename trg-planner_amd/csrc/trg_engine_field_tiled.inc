@@ -8,6 +8,8 @@
 // A solve starts from source sets with start costs ("Source sets across tiles"), one source per field being m sets of
 // one entry: the members are seeded by the ranks that own them, and for the set call a third loop of the same frame
 // trades, after the two passes, the owners of the border nodes over the forest of the global parents.
+// A successful solve stays in the work arrays; the routes call ("Routes across tiles") walks its routes on the devices,
+// the fourth use of the frame.
 
 namespace {
 
@@ -36,8 +38,18 @@ struct TiledFieldBufs {
   DevArr set_ptr, owner, own_changed, owner_out, owned, targets, cost_at, hops_at, owner_at;
   Pinned<FieldState> h_state;
   Pinned<FieldEdgeStats> h_stats;
-  Pinned<int> h_n;  // [0] ghosts, records or a sweep's "moved" word, [1] border rows or roots
+  Pinned<int> h_n;  // [0] ghosts, records or a sweep's "moved" word, [1] border rows or roots, [2] a broken walk
   Event t0, t1;
+  // What the last successful solve left in the work arrays, for the routes ("Routes across tiles").  It is of the
+  // graph, the stitch and the safety factor of the stamps above; any new solve clears it at its start.
+  struct Solved {
+    bool valid = false;
+    int m = 0;
+    bool owners = false;   // the owner pass ran: `owner` holds m x (V + G) words
+    bool parents = false;  // the parent sweep ran
+    FieldDev F{};
+  } solved;
+  DevArr route_field, route_target, route_off, route_gids, route_info;
 };
 
 // What a solve is asked for.  Both calls come as source sets in global ids: one source per field is m sets of one
@@ -66,6 +78,7 @@ struct TiledRun {
   const TiledRequest &rq;
   FieldDev F{};
   int n_entries = 0;  // the entries whose member is this rank's node (tb.entries)
+  bool always = false;  // the routes: a tile without nodes still runs its step of every exchange
   int round = 0;      // of the current pass
   int rounds = 0, exchanges = 0, owner_exchanges = 0, roots = 0;
   long long records = 0, owner_records = 0;
@@ -262,6 +275,7 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
   F.parent = tb.parent.as<int>();
   F.ctrl = tb.ctrl.as<FieldCtrl>();
   F.tight = nullptr;
+  HIPCHK(e, hipMemsetAsync(tb.n_rec.p, 0, 16, e->s_main));  // (the word that only a broken walk of the routes sets)
   // The targets are this tile's nodes; of the entries this rank seeds those whose member is its own node (work per
   // entry and per target, none per node).
   hipStream_t s = e->s_main;
@@ -337,17 +351,18 @@ TrgStatus tiled_rounds(TrgEngine *e, TiledRun &run) {
 // gathered)` enqueues this rank's work -- what it does with the records gathered in the exchange before, then its
 // publish into tb.rec / tb.n_rec -- as a step of `mine`, timed from tb.t0 (recorded by the caller before the first)
 // to tb.t1; a failure of this rank is announced in the count exchange; the loop ends at the first exchange in which
-// no rank has news, where every rank reads the same counts and leaves.  One that has exchanged per_item x (m x B) +
-// slack times with news (B the global border count from the auxiliary words) ends with TRG_ERR_DEVICE on every rank
-// at once.  n_exchanges and n_records count what went through.
-template <typename Launches>
+// no rank has news, where every rank reads the same counts and leaves.  `rec_bound` is the most records this rank may
+// publish in one exchange (the room of tb.rec).  One that has exchanged cap(B) times with news (B the global border
+// count from the auxiliary words; the passes and the owner pass: per item x (m x B) + slack) ends with TRG_ERR_DEVICE
+// on every rank at once.  The copy of the record count takes the two words beside it along; the third is set by a walk
+// of the routes that lost its way, to its route + 1.  n_exchanges and n_records count what went through.
+template <typename Cap, typename Launches>
 TrgStatus tiled_exchanges(TrgEngine *e, ExchangeState &x, TiledRun &run, TiledLocal &mine, const std::string &what,
-                          long long per_item, long long slack, int &n_exchanges, long long &n_records,
-                          Launches launches) {
+                          long long rec_bound, Cap cap, int &n_exchanges, long long &n_records, Launches launches) {
   TiledFieldBufs &tb = *e->tiled;
   const FieldTiled &T = tb.T;
   hipStream_t s = e->s_main;
-  const bool work = run.F.N > 0;  // (a tile without nodes only takes part in the exchanges)
+  const bool work = run.F.N > 0 || run.always;  // (a tile without nodes only takes part in the exchanges)
   std::vector<long long> counts, words;
   const void *d_all = nullptr;
   long long gathered = 0;
@@ -358,10 +373,13 @@ TrgStatus tiled_exchanges(TrgEngine *e, ExchangeState &x, TiledRun &run, TiledLo
       if (exchanges) HIPCHK(e, hipEventRecord(tb.t0, s));
       if (const TrgStatus st = launches(exchanges, d_all, (int)gathered); st != TRG_OK) return st;
       HIPCHK(e, hipEventRecord(tb.t1, s));
-      HIPCHK(e, hipMemcpyAsync(&tb.h_n[0], tb.n_rec.p, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipMemcpyAsync(&tb.h_n[0], tb.n_rec.p, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
       HIPCHK(e, hipStreamSynchronize(s));
       n = tb.h_n[0];
-      if (n < 0 || n > (long long)run.F.m * T.B) return e->fail(TRG_ERR_DEVICE, what + "bad record count");
+      if (n < 0 || n > rec_bound) return e->fail(TRG_ERR_DEVICE, what + "bad record count");
+      if (tb.h_n[2] != 0)
+        return e->fail(TRG_ERR_DEVICE, what + "the walk of route " + std::to_string(tb.h_n[2] - 1) +
+                                           " lost its way (the retained arrays are damaged)");
       return tiled_lap(e, run);
     });
     e->err = mine.msg;
@@ -378,7 +396,7 @@ TrgStatus tiled_exchanges(TrgEngine *e, ExchangeState &x, TiledRun &run, TiledLo
       border += words[k];
     }
     if (gathered == 0) break;
-    if (exchanges >= per_item * run.F.m * border + slack) return e->fail(TRG_ERR_DEVICE, what + "the exchanges did not converge");
+    if (exchanges >= cap(border)) return e->fail(TRG_ERR_DEVICE, what + "the exchanges did not converge");
     if (gathered > INT_MAX) return e->fail(TRG_ERR_CAPACITY, what + "too many records in one exchange");
   }
   return TRG_OK;
@@ -405,7 +423,8 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
   });
   // a key of a border item drops at most a few times per item in practice; the cap is the round cap's shape
   const TrgStatus st = tiled_exchanges(
-      e, x, run, mine, "tiled cost field: ", 4, 64, run.exchanges, run.records,
+      e, x, run, mine, "tiled cost field: ", (long long)F.m * T.B, [&](long long border) { return 4 * F.m * border + 64; },
+      run.exchanges, run.records,
       [&](int, const void *d_all, int gathered) -> TrgStatus {
         launch_tiled_merge(F, T, d_all, gathered, s);
         if (const TrgStatus r = tiled_rounds(e, run); r != TRG_OK) return r;
@@ -450,7 +469,8 @@ TrgStatus tiled_owner_pass(TrgEngine *e, ExchangeState &x, TiledRun &run) {
     run.roots = tb.h_n[1];  // (the first wait of the sweeps was for this copy too)
     return TRG_OK;
   });
-  return tiled_exchanges(e, x, run, mine, "tiled cost field sets: owner pass: ", 1, 2, run.owner_exchanges, run.owner_records,
+  return tiled_exchanges(e, x, run, mine, "tiled cost field sets: owner pass: ", (long long)F.m * T.B,
+                         [&](long long border) { return F.m * border + 2; }, run.owner_exchanges, run.owner_records,
                          [&](int, const void *d_all, int gathered) -> TrgStatus {
                            launch_tiled_owner_step(F, T, d_all, gathered, anc, owner, tb.published.as<unsigned long long>(),
                                                    tb.rec.p, tb.n_rec.as<int>(), s);
@@ -501,6 +521,7 @@ TrgStatus tiled_outputs(TrgEngine *e, TiledRun &run) {
 // decides alike, never on which outputs one rank asks for.
 TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
   ExchangeState &x = *e->exchange;
+  if (e->tiled) e->tiled->solved = TiledFieldBufs::Solved{};  // (a solve that fails retains nothing)
   TrgStatus local = tiled_prepare(e, x, run);
   for (int pass = 0; pass < 2; ++pass) {
     const TrgStatus st = tiled_pass(e, x, run, local, pass);
@@ -509,7 +530,10 @@ TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
   }
   if (run.rq.owners)
     if (const TrgStatus st = tiled_owner_pass(e, x, run); st != TRG_OK) return st;
-  return tiled_outputs(e, run);
+  if (const TrgStatus st = tiled_outputs(e, run); st != TRG_OK) return st;
+  // retained for the routes: the keys, marks and parents lie in the work arrays as the kernels left them
+  e->tiled->solved = TiledFieldBufs::Solved{true, run.rq.m, run.rq.owners, run.rq.owners || run.rq.parent != nullptr, run.F};
+  return TRG_OK;
 }
 
 // What every rank judges alike, refused before any collective.
@@ -573,6 +597,192 @@ TrgStatus stitch_ids(TrgEngine *e, int32_t *first_gid, int32_t *num_nodes, int32
   return TRG_OK;
 }
 
+// ---- routes across tiles (DESIGN.md section 7, "Routes across tiles") ------------------------------------------------
+
+static_assert(sizeof(TrgTiledRouteInfo) == sizeof(TiledRouteInfo) && offsetof(TrgTiledRouteInfo, num_nodes) == 0 &&
+                  offsetof(TrgTiledRouteInfo, cost) == offsetof(TiledRouteInfo, cost) &&
+                  offsetof(TrgTiledRouteInfo, path_length) == offsetof(TiledRouteInfo, path_length) &&
+                  offsetof(TrgTiledRouteInfo, avg_risk) == offsetof(TiledRouteInfo, avg_risk) &&
+                  offsetof(TrgTiledRouteInfo, root_gid) == offsetof(TiledRouteInfo, root_gid) &&
+                  offsetof(TrgTiledRouteInfo, owner) == offsetof(TiledRouteInfo, owner),
+              "the kernels' and the header's tiled route info differ");
+
+struct TiledRoutesRequest {
+  int32_t n;
+  const int32_t *field, *target;  // n each; the targets are global ids
+  int32_t *offsets;               // n + 1
+  int32_t *node_gids;             // cap, may be nullptr
+  float *xyz;                     // cap x 3, may be nullptr
+  int32_t cap;
+  TrgTiledRouteInfo *infos;       // n, may be nullptr
+};
+
+// what a LEN record looks like on the host
+struct TiledLenRec {
+  int32_t route, hops;
+  uint32_t cost_bits;
+  int32_t owner;
+};
+static_assert(sizeof(TiledLenRec) == FIELD_TILED_REC_BYTES, "record layout");
+
+// The routes of the retained tiled solve: the fourth use of the frame.  Exchange 0 gathers the LEN records, from
+// which every rank computes the same clipped offsets and the same cap on the exchanges; from exchange 1 on every
+// rank walks what stands on its nodes, until an exchange in which no walk handed over or ended.
+TrgStatus tiled_routes(TrgEngine *e, const TiledRoutesRequest &rq, TrgTiledRoutesInfo *out) {
+  const Clock::time_point t_total = Clock::now();
+  const std::string what = "tiled routes: ";
+  const auto refuse = [&](const std::string &why) { return e->fail(TRG_ERR_INVALID_ARG, what + why); };
+  // what every rank judges alike, before any collective
+  if (!e->exchange || !e->exchange->transport) return refuse("no communicator (trg_engine_comm_init)");
+  if (rq.n < 0) return refuse("n_routes < 0");
+  if (rq.cap < 0) return refuse("cap < 0");
+  if (rq.n > 0 && (!rq.field || !rq.target || !rq.offsets)) return refuse("null route_field, route_target_gid or offsets");
+  if (!e->stitch_node_off.empty()) {
+    const long long n_ids = e->stitch_node_off.back();
+    for (int r = 0; r < rq.n; ++r)
+      if (rq.target[r] < 0 || rq.target[r] >= n_ids)
+        return refuse("target " + std::to_string(rq.target[r]) + " of route " + std::to_string(r) + " is outside [0, " +
+                      std::to_string(n_ids) + ")");
+  }
+  if (rq.n == 0) {
+    if (rq.offsets) rq.offsets[0] = 0;
+    out->ms_total = (float)ms_since(t_total);
+    return TRG_OK;
+  }
+  ExchangeState &x = *e->exchange;
+  if (!e->tiled) e->tiled.reset(new TiledFieldBufs());
+  TiledFieldBufs &tb = *e->tiled;
+  const FieldTiled &T = tb.T;
+  hipStream_t s = e->s_main;
+  const size_t n = (size_t)rq.n;
+  const bool want_ids = (rq.node_gids || rq.xyz) && rq.cap > 0;
+  static const TiledRequest no_request{};
+  TiledRun run{no_request};
+  run.always = true;
+  TiledRoutes R{};
+  std::vector<int32_t> off(n + 1, 0);
+  std::vector<TiledRouteInfo> infos(n);
+  std::vector<TiledLenRec> lens(n);
+  long long max_nodes = -1;  // known after exchange 0
+  // this rank's own part before the first exchange; what fails here is announced in it
+  TiledLocal mine(e, TRG_OK);
+  mine.step([&]() -> TrgStatus {
+    if (!tb.solved.valid) return refuse("no tiled solve is retained (trg_engine_tiled_cost_field or _sets first)");
+    if (tb.version != e->graph_version || tb.serial != e->stitch_serial || tb.sf_bits != float_bits(e->prm.safety_factor))
+      return refuse("the retained tiled solve is stale (the tile's graph, the stitch or the safety factor changed since)");
+    for (int r = 0; r < rq.n; ++r)
+      if (rq.field[r] < 0 || rq.field[r] >= tb.solved.m)
+        return refuse("field " + std::to_string(rq.field[r]) + " of route " + std::to_string(r) +
+                      " out of range (the solve has " + std::to_string(tb.solved.m) + ")");
+    run.F = tb.solved.F;
+    TrgStatus st;
+    if ((st = tiled_grow(e, tb.route_field, n * 4)) != TRG_OK || (st = tiled_grow(e, tb.route_target, n * 4)) != TRG_OK ||
+        (st = tiled_grow(e, tb.route_off, (n + 1) * 4)) != TRG_OK ||
+        (st = tiled_grow(e, tb.route_info, n * sizeof(TiledRouteInfo))) != TRG_OK ||
+        (st = tiled_grow(e, tb.rec, 2 * n * FIELD_TILED_REC_BYTES)) != TRG_OK || (st = tiled_grow(e, tb.n_rec, 16)) != TRG_OK)
+      return st;
+    HIPCHK(e, hipMemcpyAsync(tb.route_field.p, rq.field, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(tb.route_target.p, rq.target, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemsetAsync(tb.n_rec.p, 0, 16, s));
+    HIPCHK(e, hipEventRecord(tb.t0, s));
+    if (!tb.solved.parents) {  // the solve was asked for no parents: local work, no collective
+      if (run.F.N > 0) launch_tiled_parents(run.F, T, s);
+      tb.solved.parents = true;
+    }
+    R.field = tb.route_field.as<int>();
+    R.target = tb.route_target.as<int>();
+    R.n = rq.n;
+    R.w = tb.w.as<float>();
+    R.dist = tb.dist.as<float>();
+    R.owner = tb.solved.owners ? tb.owner.as<int>() : nullptr;
+    R.rec = tb.rec.p;
+    R.rec_cap = (int)std::min<size_t>(2 * n, INT_MAX);
+    R.n_rec = tb.n_rec.as<int>();
+    return TRG_OK;
+  });
+  int exchanges = 0, total = 0;
+  long long records = 0;
+  const TrgStatus st = tiled_exchanges(
+      e, x, run, mine, what, 2 * (long long)n, [&](long long) { return max_nodes < 0 ? LLONG_MAX : max_nodes + 3; },
+      exchanges, records, [&](int exchange, const void *d_all, int gathered) -> TrgStatus {
+        if (exchange == 0) {
+          launch_tiled_route_len(run.F, T, R, s);
+          return TRG_OK;
+        }
+        TiledRouteInfo *d_infos = tb.route_info.as<TiledRouteInfo>();
+        if (exchange > 1) {
+          launch_tiled_route_step(run.F, T, R, d_all, gathered, d_infos, s);
+          return TRG_OK;
+        }
+        // exchange 1: the lengths of all routes -- the one download of records -- then the walks begin
+        if ((size_t)gathered != n) return e->fail(TRG_ERR_DEVICE, what + "the ranks published " + std::to_string(gathered) +
+                                                                      " lengths for " + std::to_string(n) + " routes");
+        HIPCHK(e, hipMemcpyAsync(lens.data(), d_all, n * sizeof(TiledLenRec), hipMemcpyDeviceToHost, s));
+        HIPCHK(e, hipStreamSynchronize(s));
+        for (TiledRouteInfo &o : infos) o = TiledRouteInfo{-1, 0.0f, 0.0f, 0.0f, -1, -1};
+        for (const TiledLenRec &l : lens) {
+          if (l.route < 0 || (size_t)l.route >= n || infos[l.route].num_nodes != -1 || l.hops < -1)
+            return e->fail(TRG_ERR_DEVICE, what + "bad length record");
+          infos[l.route] = TiledRouteInfo{l.hops + 1, bits_float(l.cost_bits), 0.0f, 0.0f, -1, l.owner};
+          max_nodes = std::max<long long>(max_nodes, (long long)l.hops + 1);
+        }
+        max_nodes = std::max<long long>(max_nodes, 0);
+        if (want_ids)  // a route that no longer fits is truncated, later routes are empty ranges
+          for (size_t r = 0; r < n; ++r)
+            off[r + 1] = (int32_t)std::min<long long>((long long)off[r] + infos[r].num_nodes, rq.cap);
+        total = off[n];
+        HIPCHK(e, hipMemcpyAsync(tb.route_info.p, infos.data(), n * sizeof(TiledRouteInfo), hipMemcpyHostToDevice, s));
+        if (want_ids) {
+          if (const TrgStatus g = tiled_grow(e, tb.route_gids, ((size_t)total + 4) * 4); g != TRG_OK) return g;
+          HIPCHK(e, hipMemcpyAsync(tb.route_off.p, off.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
+          HIPCHK(e, hipMemsetAsync(tb.route_gids.p, 0xFF, ((size_t)total + 4) * 4, s));  // -1: another rank's node
+          R.offsets = tb.route_off.as<int>();
+          R.node_gids = tb.route_gids.as<int>();
+        }
+        launch_tiled_route_step(run.F, T, R, nullptr, 0, d_infos, s);
+        return TRG_OK;
+      });
+  if (st != TRG_OK) return st;
+  // every rank holds the same infos; the ids are this rank's own
+  std::vector<int32_t> ids;
+  int32_t *ids_out = rq.node_gids;
+  if (total > 0) {
+    if (!ids_out) {
+      ids.resize((size_t)total);
+      ids_out = ids.data();
+    }
+    HIPCHK(e, hipMemcpyAsync(ids_out, tb.route_gids.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(e, hipMemcpyAsync(infos.data(), tb.route_info.p, n * sizeof(TiledRouteInfo), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  for (size_t r = 0; r < n; ++r)
+    if (infos[r].num_nodes > 0 && infos[r].root_gid < 0)
+      return e->fail(TRG_ERR_DEVICE, what + "the walk of route " + std::to_string(r) + " did not end at a root");
+  std::copy(off.begin(), off.end(), rq.offsets);
+  if (rq.infos)
+    for (size_t r = 0; r < n; ++r)
+      rq.infos[r] = TrgTiledRouteInfo{infos[r].num_nodes, infos[r].cost, infos[r].path_length, infos[r].avg_risk,
+                                      infos[r].root_gid, infos[r].owner};
+  if (rq.xyz) {
+    const float nan = __builtin_nanf("");
+    for (int i = 0; i < total; ++i) {
+      const long long l = (long long)ids_out[i] - T.lo;
+      if (ids_out[i] >= 0 && (l < 0 || l >= T.V || (size_t)l >= e->nx.size()))
+        return e->fail(TRG_ERR_DEVICE, what + "a walk left this tile's nodes");
+      const bool own = ids_out[i] >= 0;
+      rq.xyz[3 * i] = own ? e->nx[l] : nan;
+      rq.xyz[3 * i + 1] = own ? e->ny[l] : nan;
+      rq.xyz[3 * i + 2] = own ? e->nz[l] : nan;
+    }
+  }
+  out->exchanges = exchanges;
+  out->max_nodes = (int32_t)max_nodes;
+  out->records_sent = records;
+  out->ms_device = (float)run.ms_device;
+  out->ms_total = (float)ms_since(t_total);
+  return TRG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -600,6 +810,18 @@ TrgStatus trg_engine_tiled_cost_field_sets(TrgEngine *e, int32_t m, const int32_
       out.roots = run.roots;
       out.owner_records_sent = run.owner_records;
     });
+  });
+}
+
+TrgStatus trg_engine_tiled_field_routes(TrgEngine *e, int32_t n_routes, const int32_t *route_field,
+                                        const int32_t *route_target_gid, int32_t *offsets, int32_t *node_gids,
+                                        float *xyz, int32_t cap, TrgTiledRouteInfo *infos, TrgTiledRoutesInfo *info) {
+  return entry(e, "tiled_field_routes", DEVICE, [&] {
+    TrgTiledRoutesInfo local{};
+    TrgTiledRoutesInfo &out = info ? *info : local;
+    out = TrgTiledRoutesInfo{};
+    return tiled_routes(e, TiledRoutesRequest{n_routes, route_field, route_target_gid, offsets, node_gids, xyz, cap, infos},
+                        &out);
   });
 }
 

@@ -13,7 +13,8 @@
 // Every solve starts from source sets ("Source sets across tiles"; a single source is a set of one): k_tiled_seed runs
 // over this rank's own entries.  The set call adds, after the parent sweep, the owner pass: k_tiled_forest_begin, the
 // jumping sweeps of trg_field.hip, then per exchange k_tiled_owner_merge / _resolve and the publish kernel again;
-// k_tiled_output writes the owners beside the fields and k_tiled_owned the counts per entry.
+// k_tiled_output writes the owners beside the fields and k_tiled_owned the counts per entry.  The routes of a finished
+// solve ("Routes across tiles"): k_tiled_route_len, k_tiled_route_step and k_tiled_route_end.
 //
 // All kernels: wave64, bounds taken from the arguments, no scalar memory writes, nothing waits on another workgroup.
 
@@ -359,7 +360,192 @@ __global__ __launch_bounds__(THREADS) void k_tiled_owned(FieldDev F, FieldTiled 
   }
 }
 
+// ---- routes across tiles (DESIGN.md section 7, "Routes across tiles") -----------------------------------------------
+
+// 16 bytes, the exchange's record again.  LEN (exchange 0 only): {route, hops or -1, cost bits, owner}.  HANDOFF:
+// {route, the parent's global id (>= 0), sum_dist bits, sum_w bits}.  END: {route, -1 - root gid, the sums}.
+struct TiledRouteRec {
+  int route, b;
+  unsigned c, d;
+};
+static_assert(sizeof(TiledRouteRec) == FIELD_TILED_REC_BYTES, "record layout");
+static_assert(sizeof(TiledRouteInfo) == 24, "route info layout");
+
+// One thread per route: the rank that owns the target publishes its LEN record.
+__global__ __launch_bounds__(THREADS) void k_tiled_route_len(FieldDev F, FieldTiled T, TiledRoutes R) {
+  TiledRouteRec *rec = (TiledRouteRec *)R.rec;
+  const int n_iter = (R.n + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, r = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, r += gridDim.x * blockDim.x) {
+    bool mine = false;
+    TiledRouteRec out{};
+    if (r < R.n) {
+      const int f = R.field[r];
+      const long long l = (long long)R.target[r] - T.lo;
+      if (l >= 0 && l < T.V && f >= 0 && f < F.m) {
+        const int item = f * F.V + (int)l;
+        const unsigned long long k = F.key[item];
+        const bool reached = k != FIELD_KEY_NONE;
+        mine = true;
+        out.route = r;
+        out.b = reached ? (int)(unsigned)k : -1;
+        out.c = reached ? key_cost_bits(k) : __float_as_uint(__builtin_huge_valf());
+        out.d = (unsigned)(reached && R.owner ? R.owner[item] : -1);
+      }
+    }
+    const int slot = wave_reserve(mine, R.n_rec);
+    if (mine) {
+      if (slot < R.rec_cap) rec[slot] = out;
+      else atomicMax(R.n_rec + 2, r + 1);
+    }
+  }
+}
+
+// The walks of one exchange: one 16-lane group per item, as k_field_route_walk.  BEGIN (exchange 1): an item is a
+// route, walked from its target by the rank that owns it.  Else an item is a gathered record; a HANDOFF that names
+// one of this rank's nodes is walked on from there with the sums it carries.  A walk writes its node's global id at
+// offsets[r] + hops where that lies inside the clipped segment, finds the tight edge of least index into its node in
+// the parent's row of the solve graph -- a local row keeps G's order, a ghost's row holds each cross edge once, with
+// the owner's bits -- adds its dist and w, and steps to the parent; at a ghost it publishes HANDOFF, at hops == 0,
+// where its node must carry a member mark, END.  Every route has one walker at any time: nothing here is atomic but
+// the record slots (wave_reserve, every lane of the wave gets there: the trip counts are uniform) and the word beside
+// the record count that a walk which lost its way sets to its route + 1.
+template <bool BEGIN>
+__global__ __launch_bounds__(THREADS) void k_tiled_route_step(FieldDev F, FieldTiled T, TiledRoutes R,
+                                                              const TiledRouteRec *__restrict__ in, int n_in) {
+  TiledRouteRec *rec = (TiledRouteRec *)R.rec;
+  const int sub = threadIdx.x & (GROUP - 1);
+  const int gshift = lane_id() & ~(GROUP - 1);
+  const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
+  const int ng = gridDim.x * blockDim.x / GROUP;
+  const int items = BEGIN ? R.n : n_in;
+  const int n_iter = (items + ng - 1) / ng;
+  for (int it = 0, i = g0; it < n_iter; ++it, i += ng) {
+    bool go = false, broken = false, publish = false;
+    int r = 0, v = 0;
+    float sum_dist = 0.0f, sum_w = 0.0f;
+    if (i < items) {
+      long long l = -1;
+      if constexpr (BEGIN) {
+        r = i;
+        l = (long long)R.target[r] - T.lo;
+      } else {
+        const TiledRouteRec h = in[i];
+        r = h.route;
+        if (r >= 0 && r < R.n && h.b >= 0) l = (long long)h.b - T.lo;
+        sum_dist = __uint_as_float(h.c);
+        sum_w = __uint_as_float(h.d);
+      }
+      if (l >= 0 && l < T.V) {
+        v = (int)l;
+        const int f = R.field[r];
+        go = f >= 0 && f < F.m && (!BEGIN || F.key[f * F.V + v] != FIELD_KEY_NONE);
+      }
+    }
+    TiledRouteRec out{};
+    if (go) {
+      const int fbase = R.field[r] * F.V;
+      const int off = R.node_gids ? R.offsets[r] : 0;
+      const int room = R.node_gids ? R.offsets[r + 1] - off : 0;
+      unsigned long long kv = F.key[fbase + v];
+      broken = kv == FIELD_KEY_NONE;
+      while (!broken) {
+        const int h = (int)(unsigned)kv;
+        if (sub == 0 && h < room) R.node_gids[off + h] = T.lo + v;
+        if (h == 0) {  // a root, by its mark
+          if (F.stamp_near[fbase + v] >= 0) broken = true;
+          out.b = -1 - (T.lo + v);
+          publish = true;
+          break;
+        }
+        const int p = F.parent[fbase + v];  // a global id
+        const int j = tiled_ghost(T, p);
+        const int u = p >= T.lo && p < T.lo + T.V ? p - T.lo : j >= 0 ? T.V + j : -1;
+        if (u < 0) {
+          broken = true;
+          break;
+        }
+        const unsigned long long ku = F.key[fbase + u];
+        int edge = -1;
+        for (int k0 = F.rowptr[u], kend = F.rowptr[u + 1]; k0 < kend; k0 += GROUP) {
+          const int k = k0 + sub;
+          bool hit = false;
+          if (k < kend && F.col[k] == v) {
+            const float c = F.ec[k];
+            hit = __float_as_uint(c) != FIELD_EDGE_SKIP && key_extend(ku, c) == kv;
+          }
+          const unsigned hits = (unsigned)(ballot(hit) >> gshift) & ((1u << GROUP) - 1u);
+          if (hits) {
+            edge = k0 + __ffs(hits) - 1;
+            break;
+          }
+        }
+        if (edge < 0) {
+          broken = true;
+          break;
+        }
+        sum_dist += R.dist[edge];
+        sum_w += R.w[edge];
+        if (u >= T.V) {  // the parent is another rank's node: the route goes on there
+          out.b = p;
+          publish = true;
+          break;
+        }
+        v = u;
+        kv = ku;
+      }
+      out.route = r;
+      out.c = __float_as_uint(sum_dist);
+      out.d = __float_as_uint(sum_w);
+      if (broken && sub == 0) atomicMax(R.n_rec + 2, r + 1);
+    }
+    const bool mine = publish && !broken && sub == 0;
+    const int slot = wave_reserve(mine, R.n_rec);
+    if (mine) {
+      if (slot < R.rec_cap) rec[slot] = out;
+      else atomicMax(R.n_rec + 2, r + 1);
+    }
+  }
+}
+
+// One thread per gathered record: an END record gives its route the sums and the root.  Every rank gathers the same
+// records, so every rank's info array ends up the same; a route ends once, so one thread writes its entry.
+__global__ __launch_bounds__(THREADS) void k_tiled_route_end(const TiledRouteRec *__restrict__ in, int n_in,
+                                                             TiledRouteInfo *infos, int n_routes) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_in; i += gridDim.x * blockDim.x) {
+    const TiledRouteRec h = in[i];
+    if (h.b >= 0 || h.route < 0 || h.route >= n_routes) continue;
+    TiledRouteInfo &o = infos[h.route];
+    if (o.num_nodes <= 0) continue;  // (never: only a reached target is walked)
+    o.path_length = __uint_as_float(h.c);
+    o.avg_risk = __uint_as_float(h.d) / (float)o.num_nodes;
+    o.root_gid = -1 - h.b;
+  }
+}
+
 }  // namespace
+
+void launch_tiled_route_len(const FieldDev &F, const FieldTiled &T, const TiledRoutes &R, hipStream_t s) {
+  (void)hipMemsetAsync(R.n_rec, 0, sizeof(int), s);
+  if (R.n > 0 && T.V > 0)
+    hipLaunchKernelGGL(k_tiled_route_len, dim3(field_blocks(R.n, THREADS)), dim3(THREADS), 0, s, F, T, R);
+}
+
+void launch_tiled_route_step(const FieldDev &F, const FieldTiled &T, const TiledRoutes &R, const void *rec_in, int n_in,
+                             TiledRouteInfo *infos, hipStream_t s) {
+  (void)hipMemsetAsync(R.n_rec, 0, sizeof(int), s);
+  const TiledRouteRec *in = (const TiledRouteRec *)rec_in;
+  if (!in) {
+    if (R.n > 0 && T.V > 0)
+      hipLaunchKernelGGL(k_tiled_route_step<true>, dim3(field_blocks((long long)R.n * GROUP, THREADS)), dim3(THREADS), 0,
+                         s, F, T, R, in, 0);
+    return;
+  }
+  if (n_in <= 0) return;
+  if (T.V > 0)
+    hipLaunchKernelGGL(k_tiled_route_step<false>, dim3(field_blocks((long long)n_in * GROUP, THREADS)), dim3(THREADS), 0,
+                       s, F, T, R, in, n_in);
+  hipLaunchKernelGGL(k_tiled_route_end, dim3(field_blocks(n_in, THREADS)), dim3(THREADS), 0, s, in, n_in, infos, R.n);
+}
 
 void launch_tiled_mark(const int *rowptr, const int *col, int V, int lo, int Vg, int *ghost_flag, int *border_flag,
                        hipStream_t s) {

@@ -665,5 +665,32 @@ void launch_tiled_owner_step(const FieldDev &F, const FieldTiled &T, const void 
 // owned (n_entries, zeroed here) = the local nodes per entry
 void launch_tiled_owned(const FieldDev &F, const FieldTiled &T, const int *set_ptr, const int *owner, int n_entries,
                         int *owned, hipStream_t s);
+// Routes across tiles ("Routes across tiles"): the routes of a finished tiled solve whose parent
+// sweep ran, each walked by the rank that owns the node it stands on and handed over at a seam through the exchange's
+// 16-byte records.  Layout of TrgTiledRouteInfo (include/trg_engine.h).
+struct TiledRouteInfo {
+  int num_nodes;
+  float cost, path_length, avg_risk;
+  int root_gid, owner;
+};
+struct TiledRoutes {
+  const int *field, *target;  // n each (device): the field, and the target's GLOBAL id
+  int n;
+  const int *offsets;         // n + 1: the clipped segments; not read while node_gids == nullptr
+  int *node_gids;             // offsets[n] global ids, or nullptr
+  const float *w, *dist;      // the solve graph's edge arrays
+  const int *owner;           // the owner pass's m x (V + G) words, or nullptr (a single-source solve)
+  void *rec;                  // room for rec_cap records of FIELD_TILED_REC_BYTES
+  int rec_cap;
+  int *n_rec;                 // [0] the record count (zeroed by every launch here), [2] route + 1 of a broken walk
+};
+// exchange 0: a LEN record {route, hops or -1, cost bits, owner or -1} per route whose target is this rank's node
+void launch_tiled_route_len(const FieldDev &F, const FieldTiled &T, const TiledRoutes &R, hipStream_t s);
+// Exchange 1 (rec_in == nullptr): the walks of the routes whose target is this rank's node begin.  Later exchanges: the
+// gathered HANDOFF records that name this rank's nodes are walked on, and the gathered END records are written into
+// infos (n entries, device; num_nodes set from the LEN records).  A walk publishes HANDOFF {route, parent gid, sums}
+// where its parent is a ghost and END {route, -1 - root gid, sums} at a root.
+void launch_tiled_route_step(const FieldDev &F, const FieldTiled &T, const TiledRoutes &R, const void *rec_in, int n_in,
+                             TiledRouteInfo *infos, hipStream_t s);
 
 }  // namespace trg

@@ -76,6 +76,16 @@ class TrgRouteInfo(C.Structure):
                 ("avg_risk", C.c_float)]
 
 
+class TrgTiledRouteInfo(C.Structure):
+    _fields_ = [("num_nodes", C.c_int32), ("cost", C.c_float), ("path_length", C.c_float), ("avg_risk", C.c_float),
+                ("root_gid", C.c_int32), ("owner", C.c_int32)]
+
+
+class TrgTiledRoutesInfo(C.Structure):
+    _fields_ = [("exchanges", C.c_int32), ("max_nodes", C.c_int32), ("records_sent", C.c_int64),
+                ("ms_device", C.c_float), ("ms_total", C.c_float)]
+
+
 class TrgFieldModel(C.Structure):
     _fields_ = [("safety_factor", C.c_float), ("max_weight", C.c_float)]
 
@@ -129,6 +139,7 @@ EXPORTS = [
     "trg_engine_risk_field_sets", "trg_engine_risk_field_refresh",
     "trg_engine_pose_links", "trg_engine_cost_field_seeded",
     "trg_engine_tiled_cost_field", "trg_engine_stitch_ids", "trg_engine_tiled_cost_field_sets",
+    "trg_engine_tiled_field_routes",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -239,6 +250,8 @@ def load_library():
     L.trg_engine_stitch_ids.argtypes = [vp, ip, ip, ip]
     L.trg_engine_tiled_cost_field_sets.argtypes = [vp, C.c_int32, ip, ip, fp, fp, ip, ip, ip, ip, C.c_int32, fp, ip, ip,
                                                    ip, C.POINTER(TrgTiledSetInfo)]
+    L.trg_engine_tiled_field_routes.argtypes = [vp, C.c_int32, ip, ip, ip, ip, fp, C.c_int32,
+                                                C.POINTER(TrgTiledRouteInfo), C.POINTER(TrgTiledRoutesInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
     L.trg_engine_fallback_reason.restype = C.c_char_p
     _lib = L
@@ -481,6 +494,50 @@ class Engine:
             out.append((gids[mine], None if pick is None else
                         (pick[0], float(cost[mine[pick[1]]]), int(hops[mine[pick[1]]]))))
         return out
+
+    def tiled_routes(self, route_field, target_gids, cap=None, xyz=True):
+        """Routes across tiles (trg_engine_tiled_field_routes; DESIGN.md section 7, "Routes across tiles"): route r of the
+        last tiled solve runs from the root of field route_field[r] to the node with GLOBAL id target_gids[r], any
+        rank's node.  A collective call: every rank makes it with the same arguments.  cap: the room for node ids in
+        all (None: a first collective call for the lengths, then one with exactly enough room; 0: infos only).
+        -> dict with "offsets" (n + 1) and "infos" (a list of TrgTiledRouteInfo), the same on every rank; "gids" (the
+        global ids at THIS rank's own positions, -1 elsewhere; None with cap == 0), "xyz" (positions there, NaN
+        elsewhere; None without `xyz` or with cap == 0) and "info" (TrgTiledRoutesInfo of the last call).
+        tiled.join_routes merges the ranks' dicts."""
+        f = np.ascontiguousarray(route_field, dtype=np.int32).reshape(-1)
+        t = np.ascontiguousarray(target_gids, dtype=np.int32).reshape(-1)
+        if f.shape[0] != t.shape[0]:
+            raise ValueError("tiled_routes: route_field and target_gids differ in length")
+        n = f.shape[0]
+        infos = (TrgTiledRouteInfo * max(n, 1))()
+        off = np.zeros(n + 1, np.int32)
+        info = TrgTiledRoutesInfo()
+        if cap is None:
+            self._chk(self.L.trg_engine_tiled_field_routes(self.h, n, _i(f), _i(t), _i(off), None, None, 0, infos,
+                                                           C.byref(info)))
+            cap = sum(infos[r].num_nodes for r in range(n))
+            if cap > 2**31 - 1:
+                raise ValueError(f"tiled_routes: {cap} nodes in all do not fit one call's 32-bit capacity")
+        cap = int(cap)
+        gids = np.full(max(cap, 1), -1, np.int32) if cap > 0 else None
+        pts = np.full((max(cap, 1), 3), np.nan, np.float32) if xyz and cap > 0 else None
+        self._chk(self.L.trg_engine_tiled_field_routes(
+            self.h, n, _i(f), _i(t), _i(off), None if gids is None else _i(gids), None if pts is None else _f(pts), cap,
+            infos, C.byref(info)))
+        total = int(off[n])
+        one = [TrgTiledRouteInfo(i.num_nodes, i.cost, i.path_length, i.avg_risk, i.root_gid, i.owner)
+               for i in infos[:n]]
+        return dict(offsets=off, infos=one, gids=None if gids is None else gids[:total],
+                    xyz=None if pts is None else pts[:total], info=info)
+
+    def tiled_plan_many(self, start_gid, goal_gids):
+        """Paths from one node of the global stitched graph to many: ONE tiled solve from `start_gid` (no parents are
+        downloaded) and one tiled_routes call without a capacity -- the lengths first, then the ids -- all
+        ranks alike (a collective call) -> tiled_routes' dict; tiled.join_routes gives the routes.  Each path is the
+        least fp32 fold of edge costs to its goal (tiled_cost_fields' semantics)."""
+        goals = np.ascontiguousarray(goal_gids, dtype=np.int32).reshape(-1)
+        self.tiled_cost_fields([int(start_gid)], parent=False)
+        return self.tiled_routes(np.zeros(goals.shape[0], np.int32), goals)
 
     def set_option(self, key, value):
         self._chk(self.L.trg_engine_set_option(self.h, str(key).encode(), str(value).encode()))

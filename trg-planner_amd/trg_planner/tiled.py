@@ -262,6 +262,42 @@ def field_route(fields, k, target_gid):
     return out[::-1]
 
 
+def join_routes(parts):
+    """The ranks' Engine.tiled_routes dicts -> list of (gids int32 (k,), xyz float32 (k, 3) or None, TrgTiledRouteInfo)
+    per route, root first; k is the route's clipped length (infos keep the full one).  Raises ValueError if the ranks
+    disagree on offsets or infos, or if a position is claimed by two ranks or by none."""
+    if not parts:
+        return []
+    off = np.asarray(parts[0]["offsets"])
+    key = lambda i: (i.num_nodes, np.float32(i.cost).tobytes(), np.float32(i.path_length).tobytes(),  # noqa: E731
+                     np.float32(i.avg_risk).tobytes(), i.root_gid, i.owner)
+    first = [key(i) for i in parts[0]["infos"]]
+    for p in parts[1:]:
+        if not np.array_equal(np.asarray(p["offsets"]), off) or [key(i) for i in p["infos"]] != first:
+            raise ValueError("join_routes: the ranks returned different offsets or infos")
+    total = int(off[-1])
+    gids, pts = None, None
+    if any(p["gids"] is not None for p in parts):
+        if any(p["gids"] is None or p["gids"].shape[0] != total for p in parts):
+            raise ValueError("join_routes: the ranks returned different numbers of positions")
+        claims = np.sum([p["gids"] >= 0 for p in parts], 0) if total else np.zeros(0, np.int64)
+        if (claims > 1).any():
+            raise ValueError(f"join_routes: position {int(np.flatnonzero(claims > 1)[0])} is claimed by two ranks")
+        if (claims < 1).any():
+            raise ValueError(f"join_routes: position {int(np.flatnonzero(claims < 1)[0])} is claimed by no rank")
+        gids = np.max([p["gids"] for p in parts], 0).astype(np.int32) if total else np.empty(0, np.int32)
+        if all(p["xyz"] is not None for p in parts):
+            pts = np.full((total, 3), np.nan, np.float32)
+            for p in parts:
+                mine = p["gids"] >= 0
+                pts[mine] = p["xyz"][mine]
+    out = []
+    for r, i in enumerate(parts[0]["infos"]):
+        a, b = int(off[r]), int(off[r + 1])
+        out.append((None if gids is None else gids[a:b].copy(), None if pts is None else pts[a:b].copy(), i))
+    return out
+
+
 # ---- reference implementation of the stitch rule in numpy (tests/tiled_oracle.py drives the CPU
 # oracle through it; the product path is stitch_device above) ------------------------------------------
 def cross_pairs(my_tile, records_per_tile, expand_dist):
