@@ -1405,12 +1405,21 @@ class Engine:
                 "info": r["info"]}
 
     def voxel_filter(self, xyz, leaf):
-        """pcl::VoxelGrid of TRGPlanner::loadPrebuiltMap (trg_planner.cpp:91-94) on the GPU."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        out = np.empty_like(xyz)
+        """pcl::VoxelGrid of TRGPlanner::loadPrebuiltMap (trg_planner.cpp:91-94) on the GPU.  `xyz` is (N, k) with
+        k >= 3 (columns past z, such as a PCD intensity, are skipped: the row stride is k floats) or a flat array of
+        3 N floats; -> float32 (n_out, 3)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+        if xyz.ndim == 1:
+            if xyz.size % 3:
+                raise ValueError(f"voxel_filter: a flat cloud holds x y z triples, not {xyz.size} floats")
+            xyz = xyz.reshape(-1, 3)
+        if xyz.ndim != 2 or xyz.shape[1] < 3:
+            raise ValueError(f"voxel_filter: the cloud must be (N, k) with k >= 3, not {xyz.shape}")
+        n, stride = xyz.shape
+        out = np.empty((n, 3), np.float32)
         n_out = C.c_size_t(0)
         passthrough = C.c_int32(0)
-        self._chk(self.L.trg_engine_voxel_filter(self.h, _f(xyz), xyz.shape[0], 3, C.c_float(leaf),
+        self._chk(self.L.trg_engine_voxel_filter(self.h, _f(xyz), n, stride, C.c_float(leaf),
                                                  _f(out), C.byref(n_out), C.byref(passthrough)))
         return out[:n_out.value].copy()
 
