@@ -1,6 +1,7 @@
 """Test helper: what the tests of built graphs share -- a local-map crop of a cloud with an obstacle that the global
-map lacks, the driver that takes an engine and the oracle through the steps of update_scenarios.py, and the
-reference's invariants of a built graph.  Test code only."""
+map lacks, the driver that takes an engine and the oracle through the steps of update_scenarios.py, the oracle's
+fp64-covariance witness of a build with the engine build and the bit-for-bit comparison that go with it (_witness,
+_build, _check_build), and the reference's invariants of a built graph.  Test code only."""
 import numpy as np
 
 
@@ -152,6 +153,74 @@ def _drive(pool, engine, oracle, witness, steps, check, clouds, prm):
         if check is not None:
             check(i, step, rec)
     return hist
+
+
+SEED = 7  # sampler seed of _witness and _build (table bits 16)
+
+
+def _assert_same_graph(g, ref, what):
+    assert (g.V, g.E) == (ref.V, ref.E), (what, g.V, ref.V, g.E, ref.E)
+    assert np.array_equal(g.rowptr, ref.rowptr), what
+    assert np.array_equal(g.col, ref.col), what
+    assert np.array_equal(g.state, ref.state), what
+    assert np.array_equal(g.cid, ref.cid), what
+    assert np.array_equal(g.xyz.view(np.uint32), ref.xyz.view(np.uint32)), what
+    assert np.array_equal(g.dist.view(np.uint32), ref.dist.view(np.uint32)), what
+    differ = int((g.w.view(np.uint32) != ref.w.view(np.uint32)).sum())
+    assert differ == 0, (what, differ, float(np.abs(g.w - ref.w).max()))
+
+
+_witnesses = {}
+
+
+def _witness(oa, key, prm, cloud, start, core=None):
+    """(graph before cleanGraph, after it, the oracle's counters) of the fp64-covariance witness, computed once."""
+    if key not in _witnesses:
+        o = oa.Oracle(**prm)
+        o.set_sampler(SEED, 0, 16)
+        o.set_cov_f64(True)
+        if core is not None:
+            o.set_tile(core, epoch=0)
+        o.set_global_map(cloud)
+        assert o.init_graph(start)
+        _witnesses[key] = (o.graph(1), o.graph(0), o.counters())
+        o.close()
+    return _witnesses[key]
+
+
+def _build_any(prm, cloud, start, options, core=None):
+    """An engine built with keep_preclean and `options`, whichever path built it -> (engine, its stats)."""
+    import trg_planner
+    e = trg_planner.Engine(**prm)
+    e.set_sampler(SEED, 16)
+    e.set_option("keep_preclean", 1)
+    for k, v in options.items():
+        e.set_option(k, v)
+    if core is not None:
+        e.set_tile(core, epoch=0)
+    e.set_global_map(cloud)
+    e.init_graph(start)
+    return e, e.stats()
+
+
+def _build(prm, cloud, start, options, core=None):
+    e, st = _build_any(prm, cloud, start, options, core)
+    assert st["used_device_bfs"] == 1 and st["bfs_fallbacks"] == 0, (options, e.fallback_reason)
+    return e, st
+
+
+def _check_build(e, st, witness, what, device=True):
+    """device=False: a build the host replay made, which has no speculative parent edges to count."""
+    pre, clean, c = witness
+    _assert_same_graph(e.graph("preclean"), pre, what + ": before cleanGraph")
+    _assert_same_graph(e.graph("global"), clean, what + ": after cleanGraph")
+    assert st["trials"] == c["trials"], what
+    assert st["samples"] == c["samples"], what
+    assert st["created_nodes"] == c["created"], what
+    assert st["invalid_nodes"] == c["invalid_created"], what
+    assert st["bytes_sample_kernel"] == 12 * c["sample_hits"], (what, st["bytes_sample_kernel"], c["sample_hits"])
+    if device:
+        assert st["bytes_spec_created"] == 12 * c["wire_hits_new"], (what, st["bytes_spec_created"], c["wire_hits_new"])
 
 
 def graph_invariants(g, expand_dist):

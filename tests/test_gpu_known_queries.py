@@ -12,72 +12,13 @@ update against the local map.
 import numpy as np
 import pytest
 
-from graph_support import obs_crop
+from graph_support import _assert_same_graph, _build, _check_build, _witness, _witnesses, obs_crop
 
 pytestmark = pytest.mark.gpu
 
-SEED = 7
 START = [15.0, 15.0, 0.0]
 COMBOS = [{"known_start_disc": 0}, {"known_start_disc": 1}]
 SAME_ACROSS = ("bytes_spec_kernel", "bytes_edge_kernel", "edge_evals_gpu")
-
-
-def _assert_same_graph(g, ref, what):
-    assert (g.V, g.E) == (ref.V, ref.E), (what, g.V, ref.V, g.E, ref.E)
-    assert np.array_equal(g.rowptr, ref.rowptr), what
-    assert np.array_equal(g.col, ref.col), what
-    assert np.array_equal(g.state, ref.state), what
-    assert np.array_equal(g.cid, ref.cid), what
-    assert np.array_equal(g.xyz.view(np.uint32), ref.xyz.view(np.uint32)), what
-    assert np.array_equal(g.dist.view(np.uint32), ref.dist.view(np.uint32)), what
-    differ = int((g.w.view(np.uint32) != ref.w.view(np.uint32)).sum())
-    assert differ == 0, (what, differ, float(np.abs(g.w - ref.w).max()))
-
-
-_witnesses = {}
-
-
-def _witness(oa, key, prm, cloud, start, core=None):
-    """(graph before cleanGraph, after it, the oracle's counters) of the fp64-covariance witness, computed once."""
-    if key not in _witnesses:
-        o = oa.Oracle(**prm)
-        o.set_sampler(SEED, 0, 16)
-        o.set_cov_f64(True)
-        if core is not None:
-            o.set_tile(core, epoch=0)
-        o.set_global_map(cloud)
-        assert o.init_graph(start)
-        _witnesses[key] = (o.graph(1), o.graph(0), o.counters())
-        o.close()
-    return _witnesses[key]
-
-
-def _build(prm, cloud, start, options, core=None):
-    import trg_planner
-    e = trg_planner.Engine(**prm)
-    e.set_sampler(SEED, 16)
-    e.set_option("keep_preclean", 1)
-    for k, v in options.items():
-        e.set_option(k, v)
-    if core is not None:
-        e.set_tile(core, epoch=0)
-    e.set_global_map(cloud)
-    e.init_graph(start)
-    st = e.stats()
-    assert st["used_device_bfs"] == 1 and st["bfs_fallbacks"] == 0, (options, e.fallback_reason)
-    return e, st
-
-
-def _check_build(e, st, witness, what):
-    pre, clean, c = witness
-    _assert_same_graph(e.graph("preclean"), pre, what + ": before cleanGraph")
-    _assert_same_graph(e.graph("global"), clean, what + ": after cleanGraph")
-    assert st["trials"] == c["trials"], what
-    assert st["samples"] == c["samples"], what
-    assert st["created_nodes"] == c["created"], what
-    assert st["invalid_nodes"] == c["invalid_created"], what
-    assert st["bytes_sample_kernel"] == 12 * c["sample_hits"], (what, st["bytes_sample_kernel"], c["sample_hits"])
-    assert st["bytes_spec_created"] == 12 * c["wire_hits_new"], (what, st["bytes_spec_created"], c["wire_hits_new"])
 
 
 def _check_combos(oa, key, prm, cloud, start, core=None, min_nodes=200):

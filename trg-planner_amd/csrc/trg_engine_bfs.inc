@@ -290,7 +290,8 @@ struct Build {
   TrgStatus fix_pre_level_ties(Level &lv);
   TrgStatus settle_ties_in_place(Level &lv);
   TrgStatus replay_level(Level &lv);
-  TrgStatus resolve_uncertain(int n_unc, void *status_base, size_t stride, int list_parity, int ctr_index);
+  TrgStatus resolve_uncertain(int n_unc, void *status_base, size_t stride, int list_parity, int ctr_index,
+                              bool slot_records = false);
   TrgStatus grow_call_log(size_t need);
   TrgStatus launch_deferred(long long c1, bool in_loop);
   void launch_creating_edge_weights(hipStream_t st);
@@ -346,8 +347,11 @@ void Build::read_level(Level &lv, bool first) {
 }
 
 // host decision of the slope gates the device could not call (reference libm, trg.cpp:269-274);
-// list: the parity's half of unc_list / unc_rec, entries index status_array
-TrgStatus Build::resolve_uncertain(int n_unc, void *status_base, size_t stride, int list_parity, int ctr_index) {
+// list: the parity's half of unc_list / unc_rec, entries index status_array.  slot_records: the entries are
+// SlotRecs, whose hits word counts the queries of the evaluation the device ran in case the gate is open; behind a
+// closed gate the reference makes none (trg.cpp:269-276), and the node such a slot creates must count none.
+TrgStatus Build::resolve_uncertain(int n_unc, void *status_base, size_t stride, int list_parity, int ctr_index,
+                                   bool slot_records) {
   unc_changed = false;
   if (n_unc > BFS_UNC_CAP) return fallback("too many uncertain slope gates in one batch");
   std::vector<int> unc_idx(n_unc);
@@ -364,6 +368,11 @@ TrgStatus Build::resolve_uncertain(int n_unc, void *status_base, size_t stride, 
     if (host_slope_gate(e, unc_rec[3 * k], unc_rec[3 * k + 1], unc_rec[3 * k + 2])) {
       stt = EDGE_GATE;
       unc_changed = true;
+      if (slot_records) {
+        const int none = 0;
+        HIPCHK(e, hipMemcpy(addr - offsetof(SlotRec, status) + offsetof(SlotRec, hits), &none, sizeof(int),
+                            hipMemcpyHostToDevice));
+      }
     } else {
       stt &= ~EDGE_GATE_UNCERTAIN;
     }
@@ -403,8 +412,8 @@ TrgStatus Build::redo_commit(Level &lv, bool decide_gates, bool ticketed, int ho
   if ((st = undo_level(lv)) != TRG_OK) return st;  // (also clears the tie / gate counters)
   if (decide_gates && lv.n_unc > 0) {
     void *status = (char *)B.slot_rec + offsetof(SlotRec, status);
-    if ((st = resolve_uncertain(std::min(lv.n_unc, BFS_UNC_CAP), status, sizeof(SlotRec), lv.parity,
-                                lv.unc_ctr)) != TRG_OK)
+    if ((st = resolve_uncertain(std::min(lv.n_unc, BFS_UNC_CAP), status, sizeof(SlotRec), lv.parity, lv.unc_ctr,
+                                true)) != TRG_OK)
       return st;
     lv.n_unc = 0;
   }
@@ -505,6 +514,7 @@ TrgStatus Build::repair_map_tie(const MapTieRec &r, SlotRec &sr, bool *z_changed
       raw = host_slope_gate(e, p1[2], p2[2], dd) ? EDGE_GATE : (raw & ~EDGE_GATE_UNCERTAIN);
     }
     if ((raw & EDGE_STATUS_MASK) != EDGE_OK) wgt = 0.0f;
+    if ((raw & EDGE_STATUS_MASK) == EDGE_GATE) sr.hits = 0;  // (behind a closed gate the reference makes no query)
     sr.status = raw;
     sr.dist = dd;
     sr.cov[0] = wgt;  // the weight itself (already clamped): k_node_weights takes it as given
@@ -853,7 +863,7 @@ TrgStatus Build::repair_level(Level &lv) {
   // 5. uncertain gates: a speculative edge the level relied on that is in fact gated redoes the second half
   if (lv.n_unc > 0) {
     void *status = (char *)B.slot_rec + offsetof(SlotRec, status);
-    if ((st = resolve_uncertain(lv.n_unc, status, sizeof(SlotRec), lv.parity, lv.unc_ctr)) != TRG_OK) return st;
+    if ((st = resolve_uncertain(lv.n_unc, status, sizeof(SlotRec), lv.parity, lv.unc_ctr, true)) != TRG_OK) return st;
     if (unc_changed && (st = (lv.err & BFS_ERR_SOFT) ? undo_level(lv) : redo_commit(lv)) != TRG_OK) return st;
   }
   // 6. ties among pre-level nodes only
