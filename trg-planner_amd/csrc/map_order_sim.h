@@ -16,6 +16,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "map_order_runs.h"
+
 namespace trg {
 
 class MapOrderSim {
@@ -101,6 +103,38 @@ class MapOrderSim {
     } else {
       for (const Run &r : order_) emit(r, false);
     }
+  }
+  // the same order as its runs, first run first: keys [lo, hi), read downwards when descending
+  struct OrderRun {
+    int lo, hi;
+    bool descending;
+  };
+  std::vector<OrderRun> runs() const {
+    std::vector<OrderRun> out;
+    out.reserve(order_.size());
+    if (rev_) {
+      for (auto it = order_.rbegin(); it != order_.rend(); ++it) out.push_back({it->lo, it->hi, !it->front});
+    } else {
+      for (const Run &r : order_) out.push_back({r.lo, r.hi, r.front});
+    }
+    return out;
+  }
+  // ... packed for map_order_at (map_order_runs.h).  False when there are more than cap runs (cap <=
+  // MAP_ORDER_MAX_RUNS): the caller expands the order itself then.
+  bool runs_into(MapOrderRuns &R, int cap = MAP_ORDER_MAX_RUNS) const {
+    const std::vector<OrderRun> rs = runs();
+    if ((int)rs.size() > cap || cap > MAP_ORDER_MAX_RUNS) return false;
+    R.n = 0;
+    R.start[0] = 0;
+    R.descending = 0ull;
+    for (const OrderRun &r : rs) {
+      if (r.hi <= r.lo) continue;
+      R.lo[R.n] = r.lo;
+      if (r.descending) R.descending |= 1ull << R.n;
+      R.start[R.n + 1] = R.start[R.n] + (r.hi - r.lo);
+      ++R.n;
+    }
+    return true;
   }
   // `*this = other` of the real containers: bucket count, policy state and element order are
   // taken over (hashtable copy assignment, _M_assign_elements)

@@ -295,6 +295,43 @@ __global__ __launch_bounds__(256) void k_fin_insert(FinDev F, BfsDev B, long lon
   atomicMin(&F.ok_seq[s], (int)i);
 }
 
+// The same over the round-2 list alone (plain builds: no step 3).  When a pair's first call succeeded, the edge
+// is that call, F.ht_seq[slot], and nothing has to be reduced; ok_seq is needed only for the pairs whose first
+// call did not succeed, and then holds the smallest of their OTHER successful calls.  Those are all on the
+// round-2 list, because a call that is not the first of its pair can carry EDGE_OK only if round 2 evaluated it.
+// Every writer of call_status:
+//   k_level_resolve (and its repeat after an undo): CALL_NONE, CALL_PENDING for a merge, and a speculative status
+//     for the call that CREATES a node -- the first call of its pair, since the pair's other node did not exist
+//     before that slot's turn and every later call has a larger number;
+//   the host replay of a level (Build::replay_level): the same three cases, from the same records;
+//   the tie patches (Build::settle_ties_in_place): CALL_PENDING / CALL_NONE only; all three write a level's
+//     records before its calls are handed to the deferred pipeline;
+//   k_calls_finish: the calls of its list -- a round-1 list holds first calls only (k_calls_select_append:
+//     F.ht_seq[slot] == i, and later batches only add larger numbers), the other list is round 2's;
+//   the gate patches (Build::resolve_uncertain on B.call_status): calls k_calls_finish listed, i.e. evaluated ones;
+//   k_node_weights: creating calls, bits outside EDGE_STATUS_MASK (and it runs after these kernels).
+// (Step 3 adds calls to the log after the loop; those builds take k_fin_insert over the whole log.)
+// INIT: the entries of the listed calls' pairs = INT_MAX (a pass of its own: two listed calls may share a pair);
+// then the minimum over the listed calls that succeeded.  No table-wide clear of ok_seq is needed.
+template <bool INIT>
+__global__ __launch_bounds__(256) void k_fin_insert_listed(FinDev F, BfsDev B, const int *list, int count) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= count) return;
+  const int i = list[q];
+  const int s = F.call_slot[i];
+  if (s < 0) {  // (every listed call went through k_first_insert)
+    atomicOr(&B.ctrs[BFS_CTR_ERR], BFS_ERR_HASH);
+    return;
+  }
+  if (INIT) {
+    F.ok_seq[s] = 0x7FFFFFFF;
+    return;
+  }
+  const int st = B.call_status[i];
+  if (st < 0 || (st & EDGE_STATUS_MASK) != EDGE_OK) return;
+  atomicMin(&F.ok_seq[s], i);
+}
+
 // The calls of one expanded node follow each other in the log and share n1: among the wave's edge lanes, runs
 // of neighbours with the same first node take ONE atomic on that node's counter (the run's first lane), and
 // their entries land side by side in its row.  rank / cnt: this lane's place in its run and the run's length;
@@ -323,6 +360,17 @@ __device__ __forceinline__ EdgeRun edge_runs(bool is_edge, int a) {
   return r;
 }
 
+// FIRST_KNOWN (after k_fin_insert_listed): a successful call is its pair's edge iff it is the pair's first call,
+// or that first call did not succeed and it is the smallest of the others (ok_seq, valid for exactly those pairs).
+template <bool FIRST_KNOWN>
+__device__ __forceinline__ bool fin_is_edge(const FinDev &F, const BfsDev &B, int s, int i) {
+  if (!FIRST_KNOWN) return F.ok_seq[s] == i;
+  const int first = F.ht_seq[s];
+  if (first == i) return true;
+  const int fst = B.call_status[first];
+  return (fst < 0 || (fst & EDGE_STATUS_MASK) != EDGE_OK) && F.ok_seq[s] == i;
+}
+template <bool FIRST_KNOWN>
 __global__ __launch_bounds__(256) void k_fin_count(FinDev F, BfsDev B, long long ncalls) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   bool edge = false;
@@ -331,7 +379,7 @@ __global__ __launch_bounds__(256) void k_fin_count(FinDev F, BfsDev B, long long
     const int s = F.call_slot[i];
     if (s >= 0) {
       const int st = B.call_status[i];
-      if (st < 0 || (st & EDGE_STATUS_MASK) != EDGE_OK || F.ok_seq[s] != (int)i) {
+      if (st < 0 || (st & EDGE_STATUS_MASK) != EDGE_OK || !fin_is_edge<FIRST_KNOWN>(F, B, s, (int)i)) {
         F.call_slot[i] = -1;  // failed, or a later duplicate: no edge
       } else {
         edge = true;
@@ -346,6 +394,9 @@ __global__ __launch_bounds__(256) void k_fin_count(FinDev F, BfsDev B, long long
   atomicAdd(&F.deg[b], 1);
 }
 
+// WITH_W = false: a build whose cleaned graph takes its weights from call_w afterwards (Build::tail_split,
+// FIN_WEIGHTS below) has no reader of F.w: call_w is not read and the two scattered stores per edge are not made.
+template <bool WITH_W>
 __global__ __launch_bounds__(256) void k_fin_scatter(FinDev F, BfsDev B, long long ncalls) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool edge = i < ncalls && F.call_slot[i] >= 0;
@@ -354,7 +405,7 @@ __global__ __launch_bounds__(256) void k_fin_scatter(FinDev F, BfsDev B, long lo
   if (edge) {
     a = B.call_n1[i];
     b = B.call_n2[i];
-    w = B.call_w[i];
+    if (WITH_W) w = B.call_w[i];
     d = B.call_dist[i];
   }
   const EdgeRun r = edge_runs(edge, a);
@@ -364,12 +415,12 @@ __global__ __launch_bounds__(256) void k_fin_scatter(FinDev F, BfsDev B, long lo
   if (!edge) return;
   const int pa = base + r.rank;
   F.col[pa] = b;
-  F.w[pa] = w;
+  if (WITH_W) F.w[pa] = w;
   F.dist[pa] = d;
   F.seq[pa] = (int)i;
   const int pb = F.rowptr[b] + atomicAdd(&F.fill[b], 1);
   F.col[pb] = a;
-  F.w[pb] = w;
+  if (WITH_W) F.w[pb] = w;
   F.dist[pb] = d;
   F.seq[pb] = (int)i;
 }
@@ -397,8 +448,16 @@ __global__ __launch_bounds__(256) void k_fin_rowsort(FinDev F, int V) {
 }
 
 // cleanGraph (trg.cpp:491-535): the new ids follow the iteration order of the reference's node
-// container (map_order, computed on the host from the node count alone while the GPU still evaluates
-// edges); a node survives iff it is not Invalid and has at least one edge.
+// container (map_order, known from the node count alone while the GPU still evaluates edges: expanded from
+// the container's runs by k_map_order_fill, or by the host and uploaded); a node survives iff it is not
+// Invalid and has at least one edge.
+// map_order from the container's runs (map_order_runs.h; the list is a kernel argument): the O(V) expansion of
+// a few (lo, length, direction) entries, which the host otherwise writes and uploads while the GPU waits for it
+__global__ __launch_bounds__(256) void k_map_order_fill(MapOrderRuns R, int V, int *map_order) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= V || k >= R.start[R.n]) return;
+  map_order[k] = map_order_at(R, k);
+}
 __global__ __launch_bounds__(256) void k_fin_keep_flag(FinDev F, BfsDev B, const int *map_order, int V,
                                                        int *flag) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -441,23 +500,28 @@ __global__ __launch_bounds__(256) void k_fin_clean_deg(FinDev F, const int *new2
 // first -- everything but w, none of which depends on a weight -- and FIN_WEIGHTS once k_node_weights has run:
 // the same traversal and ranks, w alone, taken from the call that made the entry (F.seq; F.w holds what
 // k_fin_scatter saw, which is older than k_node_weights there).
-enum : int { FIN_WEIGHTS = 1, FIN_STRUCTURE = 2, FIN_ALL = 3 };
+// FIN_STRUCTURE is two parts of its own: FIN_NODES (xyz, state: they need the renumbering only, not the rows, so a
+// build that sends the node arrays to the host early launches them alone, a thread per node, in front of
+// k_fin_scatter) and FIN_EDGES (col, dist).
+enum : int { FIN_WEIGHTS = 1, FIN_EDGES = 2, FIN_NODES = 4, FIN_STRUCTURE = FIN_EDGES | FIN_NODES, FIN_ALL = 7 };
 constexpr int FIN_ROW = 16;
 template <int PARTS>
 __global__ __launch_bounds__(256) void k_fin_clean_copy(FinDev F, BfsDev B, const int *new2old,
                                                         const int *old2new, const int *vn,
                                                         const int *rowptr_new, int *col, float *w,
                                                         float *dist, float *xyz, int *state) {
-  const int k = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / FIN_ROW);
-  const int l = threadIdx.x % FIN_ROW;
+  constexpr int LANES = PARTS == FIN_NODES ? 1 : FIN_ROW;  // lanes per node
+  const int k = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / LANES);
+  const int l = threadIdx.x % LANES;
   if (k >= *vn) return;  // (whole groups leave together)
   const int o = new2old[k];
-  if ((PARTS & FIN_STRUCTURE) && l == 0) {
+  if ((PARTS & FIN_NODES) && l == 0) {
     xyz[3 * k] = B.nx[o];
     xyz[3 * k + 1] = B.ny[o];
     xyz[3 * k + 2] = B.nz[o];
     state[k] = B.nstate[o];
   }
+  if (PARTS == FIN_NODES) return;
   const int dst0 = rowptr_new[k];
   const int e0 = F.rowptr[o], e1 = F.rowptr[o + 1];
   for (int base = e0; base < e1; base += FIN_ROW) {
@@ -470,7 +534,7 @@ __global__ __launch_bounds__(256) void k_fin_clean_copy(FinDev F, BfsDev B, cons
 #pragma unroll
       for (int j = 0; j < FIN_ROW; ++j) rank += __shfl(other, j, FIN_ROW) < ks;
     }
-    if (have && (PARTS & FIN_STRUCTURE)) {
+    if (have && (PARTS & FIN_EDGES)) {
       const int nc = old2new[F.col[e]];
       if (nc < 0) atomicOr(&B.ctrs[BFS_CTR_ERR], BFS_ERR_CLEAN);
       col[dst0 + rank] = nc;

@@ -155,13 +155,29 @@ void launch_fin_insert_count(const FinDev &F, const BfsDev &B, long long ncalls,
   if (ncalls <= 0) return;
   const unsigned nb = (unsigned)((ncalls + 255) / 256);
   hipLaunchKernelGGL(k_fin_insert, dim3(nb), dim3(256), 0, s, F, B, ncalls);
-  hipLaunchKernelGGL(k_fin_count, dim3(nb), dim3(256), 0, s, F, B, ncalls);
+  hipLaunchKernelGGL(k_fin_count<false>, dim3(nb), dim3(256), 0, s, F, B, ncalls);
+}
+// the same for a build without step 3: ok_seq for the pairs of the round-2 calls list[0..count) only (no
+// table-wide clear of ok_seq is needed), and the count takes a pair's first call when that one succeeded
+void launch_fin_insert_count_listed(const FinDev &F, const BfsDev &B, long long ncalls, const int *list, int count,
+                                    hipStream_t s) {
+  if (ncalls <= 0) return;
+  if (count > 0) {
+    const unsigned nl = (unsigned)((count + 255) / 256);
+    hipLaunchKernelGGL(k_fin_insert_listed<true>, dim3(nl), dim3(256), 0, s, F, B, list, count);
+    hipLaunchKernelGGL(k_fin_insert_listed<false>, dim3(nl), dim3(256), 0, s, F, B, list, count);
+  }
+  hipLaunchKernelGGL(k_fin_count<true>, dim3((unsigned)((ncalls + 255) / 256)), dim3(256), 0, s, F, B, ncalls);
 }
 
-void launch_fin_scatter(const FinDev &F, const BfsDev &B, long long ncalls, hipStream_t s) {
+void launch_fin_scatter(const FinDev &F, const BfsDev &B, long long ncalls, bool with_w, hipStream_t s) {
   if (ncalls <= 0) return;
   const unsigned nb = (unsigned)((ncalls + 255) / 256);
-  hipLaunchKernelGGL(k_fin_scatter, dim3(nb), dim3(256), 0, s, F, B, ncalls);
+  if (with_w) hipLaunchKernelGGL(k_fin_scatter<true>, dim3(nb), dim3(256), 0, s, F, B, ncalls);
+  else hipLaunchKernelGGL(k_fin_scatter<false>, dim3(nb), dim3(256), 0, s, F, B, ncalls);
+}
+void launch_map_order_fill(const MapOrderRuns &R, int V, int *map_order, hipStream_t s) {
+  if (V > 0) hipLaunchKernelGGL(k_map_order_fill, dim3((V + 255) / 256), dim3(256), 0, s, R, V, map_order);
 }
 void launch_fin_rowsort(const FinDev &F, int V, hipStream_t s) {
   if (V > 0) hipLaunchKernelGGL(k_fin_rowsort, dim3((V + 255) / 256), dim3(256), 0, s, F, V);
@@ -171,10 +187,11 @@ void launch_fin_rowsort(const FinDev &F, int V, hipStream_t s) {
 // rows.  keep_pos[V] (= rowptr of the flags) is the number of surviving nodes, rowptr_new[V] the edge
 // count; the host reads both afterwards.  w == nullptr: everything but the weights, which
 // launch_fin_clean_weights writes later.
-void launch_fin_clean(const FinDev &F, const BfsDev &B, const int *map_order, int V, int *keep_flag,
-                      int *keep_pos, int *new2old, int *old2new, int *deg_new, int *rowptr_new,
-                      int *scan_tmp, int *col, float *w, float *dist, float *xyz, int *state,
-                      hipStream_t s) {
+// the renumbering alone: it reads the rows' lengths (F.rowptr), not their entries, so it can run before
+// k_fin_scatter has filled them
+void launch_fin_renumber(const FinDev &F, const BfsDev &B, const int *map_order, int V, int *keep_flag,
+                         int *keep_pos, int *new2old, int *old2new, int *deg_new, int *rowptr_new,
+                         int *scan_tmp, hipStream_t s) {
   if (V <= 0) return;
   const int nb = (V + 255) / 256;
   hipLaunchKernelGGL(k_fin_keep_flag, dim3(nb), dim3(256), 0, s, F, B, map_order, V, keep_flag);
@@ -184,6 +201,31 @@ void launch_fin_clean(const FinDev &F, const BfsDev &B, const int *map_order, in
   const int *vn = keep_pos + V;
   hipLaunchKernelGGL(k_fin_clean_deg, dim3(nb), dim3(256), 0, s, F, (const int *)new2old, vn, V, deg_new);
   launch_exclusive_scan(deg_new, rowptr_new, V, scan_tmp, s);
+}
+// xyz and state of the cleaned graph (after launch_fin_renumber)
+void launch_fin_clean_nodes(const FinDev &F, const BfsDev &B, int V, const int *keep_pos, const int *new2old,
+                            float *xyz, int *state, hipStream_t s) {
+  if (V <= 0) return;
+  hipLaunchKernelGGL(k_fin_clean_copy<FIN_NODES>, dim3((V + 255) / 256), dim3(256), 0, s, F, B, new2old,
+                     (const int *)nullptr, keep_pos + V, (const int *)nullptr, (int *)nullptr, (float *)nullptr,
+                     (float *)nullptr, xyz, state);
+}
+// col and dist of the cleaned graph (after launch_fin_renumber and launch_fin_scatter)
+void launch_fin_clean_edges(const FinDev &F, const BfsDev &B, int V, const int *keep_pos, const int *new2old,
+                            const int *old2new, const int *rowptr_new, int *col, float *dist, hipStream_t s) {
+  if (V <= 0) return;
+  hipLaunchKernelGGL(k_fin_clean_copy<FIN_EDGES>, dim3((unsigned)(((long long)V * FIN_ROW + 255) / 256)), dim3(256),
+                     0, s, F, B, new2old, old2new, keep_pos + V, rowptr_new, col, (float *)nullptr, dist,
+                     (float *)nullptr, (int *)nullptr);
+}
+
+void launch_fin_clean(const FinDev &F, const BfsDev &B, const int *map_order, int V, int *keep_flag,
+                      int *keep_pos, int *new2old, int *old2new, int *deg_new, int *rowptr_new,
+                      int *scan_tmp, int *col, float *w, float *dist, float *xyz, int *state,
+                      hipStream_t s) {
+  if (V <= 0) return;
+  launch_fin_renumber(F, B, map_order, V, keep_flag, keep_pos, new2old, old2new, deg_new, rowptr_new, scan_tmp, s);
+  const int *vn = keep_pos + V;
   const dim3 grid((unsigned)(((long long)V * FIN_ROW + 255) / 256));
   if (w)
     hipLaunchKernelGGL(k_fin_clean_copy<FIN_ALL>, grid, dim3(256), 0, s, F, B, (const int *)new2old,

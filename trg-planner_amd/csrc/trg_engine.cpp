@@ -622,6 +622,8 @@ struct TrgEngine {
   bool known_start_disc = true;  // edge walks that start at a node the level loop created skip their first disc (BfsDev::ndisc)
   bool lazy_tie_repair = true;   // a map-point tie is looked up only where the sample's elevation is read (fix_map_ties)
   bool tail_overlap = true;      // after the loop: the creating edges' covariances beside the cleaned graph's copy to the host
+  bool tail_early_copy = true;   // ... and the node arrays on their way to the host before the rows are filled (plain builds with tail_overlap)
+  int debug_order_run_cap = 0;   // test hook: at most n runs of the container order go to the device (above: host expansion)
   PlanScratch plan_scratch;  // the planner's search scratch (A* runs straight on csr_global, see plan_on_csr)
   std::unique_ptr<Uploader> uploader;  // host cloud -> HBM staging (upload_and_build): pinned slots, streams and events
                                        // of its copy threads, made on the first cloud that needs them
@@ -1236,6 +1238,7 @@ TrgStatus set_option(TrgEngine *e, const char *key, const char *value) {
       {"replay", HOST_OR_DEVICE, &e->use_device_bfs},
       {"defer_overlap", ZERO_OR_ONE, &e->defer_overlap},
       {"tail_overlap", ZERO_OR_ONE, &e->tail_overlap},
+      {"tail_early_copy", ZERO_OR_ONE, &e->tail_early_copy},
       {"known_start_disc", ZERO_OR_ONE, &e->known_start_disc},
       {"lazy_tie_repair", ZERO_OR_ONE, &e->lazy_tie_repair},
       {"tie_inplace", BOOL, &e->tie_inplace},
@@ -1250,6 +1253,7 @@ TrgStatus set_option(TrgEngine *e, const char *key, const char *value) {
       {"debug_lookback_level", INT, &e->debug_lookback_level},
       {"debug_fallback_level", INT, &e->debug_fallback_level},
       {"debug_call_stride", BOOL, &e->debug_call_stride},
+      {"debug_order_run_cap", INT, &e->debug_order_run_cap},
       {"debug_wait_rerun", BOOL, &e->debug_wait_rerun},
       {"debug_stitch_cap", INT, &e->debug_stitch_cap},
       {"comm_wait_seconds", POSITIVE_DOUBLE, &e->comm_wait_seconds},

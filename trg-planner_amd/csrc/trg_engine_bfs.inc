@@ -229,6 +229,7 @@ struct Build {
   long long ncalls = 0;
   // deferred wireEdge evaluations
   long long def_lo = 0;  // first call not yet handed to the deferred pipeline
+  int nsel2 = 0;         // calls round 2 kept: sel_list[0, nsel2) until the build ends
   size_t n_eval_batches = 0;
   std::vector<std::pair<Event, Event>> def_events;
   Event ev_order, ev_nodes, ev_structure, ev_weights;
@@ -238,14 +239,23 @@ struct Build {
   // step 3, whose neighbour calls go between the weights and the deferred pipeline; keep_preclean, which
   // downloads F.w; option tail_overlap=0) they run in the main stream in front of the deferred calls.
   bool tail_split = false;
-  bool edge_stream_busy = false;  // the second stream was given work of the tail that nothing has waited for yet
+  // ... and three with early_copy (option tail_early_copy, tail_split builds): the link is the tail's floor, so
+  // the copies start as early as their sources exist.  xyz, state, cid and rowptr need the degrees and the
+  // renumbering only: they are laid out in front of k_fin_scatter and travel on a copy stream of their own
+  // (copy_stream()) while the main stream fills and orders the rows; col / dist follow behind ev_structure and
+  // w behind ev_weights.  The host learns the sizes from ev_totals, not from a drained stream.
+  bool early_copy = false;
+  Event ev_node_arrays, ev_totals;
+  hipStream_t copy_stream() const { return e->s_aux; }  // (idle in the tail: the level loop's rare events own it)
+  bool edge_stream_busy = false;  // the second stream (and the copy stream) was given work of the tail that nothing has waited for yet
   Clock::time_point t_fin;  // finalize: its start, TRG_TIMING set
   bool trace_fin = false;
 
   explicit Build(TrgEngine *e_)
       : e(e_), bb(*e_->bfs), B(bb.B), F(bb.F), m(e_->gmap), qp(qparams(e_)), s(e_->s_main),
         S(e_->prm.sample_num), CS((e_->step3 || e_->debug_call_stride) ? LEVEL_STEP3_STRIDE : 1),
-        tail_split(e_->tail_overlap && !e_->step3 && !e_->keep_preclean) {}
+        tail_split(e_->tail_overlap && !e_->step3 && !e_->keep_preclean),
+        early_copy(tail_split && e_->tail_early_copy) {}
   // Whichever way a build ends, nothing of its tail stays in flight: a return between the hand-over to the
   // second stream and the last synchronisation (an error, a fallback to the host replay, which reuses these
   // buffers) leaves both streams drained.
@@ -253,6 +263,7 @@ struct Build {
     if (!edge_stream_busy) return;
     (void)hipStreamSynchronize(e->s_edge);
     (void)hipStreamSynchronize(s);
+    if (early_copy) (void)hipStreamSynchronize(copy_stream());
   }
   Build(const Build &) = delete;
   Build &operator=(const Build &) = delete;
@@ -264,6 +275,7 @@ struct Build {
     if (!trace_fin) return;
     (void)hipStreamSynchronize(s);
     if (edge_stream_busy) (void)hipStreamSynchronize(e->s_edge);
+    if (edge_stream_busy && early_copy) (void)hipStreamSynchronize(copy_stream());
     fprintf(stderr, "[trg finalize] %-28s %8.3f ms\n", what, ms_since(t_fin));
   }
   void mark(const char *what) {  // host time only: the stream keeps running
@@ -1026,12 +1038,15 @@ TrgStatus Build::allocate() {
   // loop (trg_step3.inc): "first call of its pair" is not final level by level, so nothing is evaluated beside
   // the loop.
   overlap = !e->step3 && e->defer_overlap;
+  s_def = overlap ? e->s_edge : s;
   if (overlap) {  // (otherwise the table is cleared after the loop, right before its first use)
+    // (In the main stream.  Measured and dropped: these two clears on the deferred stream, in front of its first
+    // batch -- the level loop of a C3 build 0.05-0.15 ms SLOWER in four of four series, profiles/r27_tail_early_copy_ab.txt)
     HIPCHK(e, hipMemsetAsync(F.ht_key, 0xFF, (size_t)fht * sizeof(unsigned long long), s));
     HIPCHK(e, hipMemsetAsync(F.ht_seq, 0x7F, (size_t)fht * sizeof(int), s));
   }
-  HIPCHK(e, hipMemsetAsync(F.ok_seq, 0x7F, (size_t)fht * sizeof(int), s));  // (first used after the loop)
-  s_def = overlap ? e->s_edge : s;
+  // (first used after the loop; early_copy: k_fin_insert_listed sets the few entries that are read)
+  if (!early_copy) HIPCHK(e, hipMemsetAsync(F.ok_seq, 0x7F, (size_t)fht * sizeof(int), s));
   return TRG_OK;
 }
 
@@ -1110,7 +1125,8 @@ TrgStatus Build::grow_call_log(size_t need) {
 // ---- phase 3: the level loop ---------------------------------------------------------------------------
 TrgStatus Build::level_loop() {
   TrgStatus st;
-  for (Event *ev : {&ev_order, &ev_nodes, &ev_structure, &ev_weights}) HIPCHK(e, ev->create(false));
+  for (Event *ev : {&ev_order, &ev_nodes, &ev_structure, &ev_weights, &ev_node_arrays, &ev_totals})
+    HIPCHK(e, ev->create(false));
   bool have_expand = false;  // this level's expansion was issued by the previous iteration
   // The level kernels time every expansion themselves (B.stats64[S64_EXPAND_TICKS], report_stats): no event
   // is recorded in this stream (a pair around a kernel costs ~12 us of stream time).
@@ -1252,22 +1268,35 @@ TrgStatus Build::finish_deferred() {
   if ((st = launch_deferred(ncalls, false)) != TRG_OK) return st;  // round 1 of the calls not yet handed over
   // while the GPU evaluates: the reference's graph.nodes[node_id] = node for ids 0..V-1 in creation
   // order (trg.cpp:248); cleanGraph iterates this container below
+  const auto t_order = Clock::now();
   e->nodes_sim.clear();  // resetGraph("global") -> nodes.clear(): buckets and policy persist
   e->nodes_sim.fill((size_t)V);
   e->next_cid = V;  // (cleanGraph drops some of them; the nodes of later updates count on from all that were created)
-  std::vector<int> map_order;
-  e->nodes_sim.iteration_order(map_order);
-  // ... and goes to the device on the (idle) second stream, for the renumbering kernels of cleanGraph
+  // ... whose order goes to the device on the (idle) second stream, for the renumbering kernels of cleanGraph.
+  // A plain build sends the container's runs (a few dozen words, as a kernel argument) and a kernel expands
+  // them: no vector of V ids is written and uploaded while the GPU has only the last batches left.
   if ((st = ensure_bytes(e, bb.map_order, ((size_t)V + 1) * sizeof(int))) != TRG_OK) return st;
-  if (V > 0)
+  MapOrderRuns runs;
+  std::vector<int> map_order;  // (host expansion only)
+  const int run_cap = e->debug_order_run_cap > 0 ? std::min(e->debug_order_run_cap, MAP_ORDER_MAX_RUNS)
+                                                 : MAP_ORDER_MAX_RUNS;
+  if (tail_split && e->nodes_sim.runs_into(runs, run_cap)) {
+    launch_map_order_fill(runs, V, (int *)bb.map_order.p, e->s_edge);
+  } else if (V > 0) {  // (more runs than the argument holds, or a build that keeps the earlier order of its tail)
+    e->nodes_sim.iteration_order(map_order);
     HIPCHK(e, hipMemcpyAsync(bb.map_order.p, map_order.data(), (size_t)V * sizeof(int), hipMemcpyHostToDevice,
                              e->s_edge));
+  }
   // ... and behind it the sums of the expansion's statistics (their inputs are final since the loop ended): a
   // small kernel beside the evaluations instead of one at the very end of the build
   launch_bfs_stats(B, V, B.stats64 + S64_DRAWS, e->s_edge);  // draws, samples, disc hits, speculative-edge hits, candidates, parent-edge hits
   HIPCHK(e, hipEventRecord(ev_order.ev, e->s_edge));
+  const double ms_order_host = ms_since(t_order);
   HIPCHK(e, hipStreamSynchronize(s_def));
   if (s_def != s) HIPCHK(e, hipStreamSynchronize(s));  // (the evaluations after the loop run in the main stream)
+  if (getenv("TRG_TIMING"))  // who ends this phase last: the host's part against its wait for the last batches
+    fprintf(stderr, "[trg deferred]   (host) container order  %8.3f ms, then waited %8.3f ms for the GPU\n",
+            ms_order_host, ms_since(t_order) - ms_order_host);
   double ms_edges = 0;
   for (auto &ev : def_events) {
     float ms = 0;
@@ -1283,6 +1312,7 @@ TrgStatus Build::finish_deferred() {
   HIPCHK(e, hipMemcpyAsync(h_n2, d_n2, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   const int nsel = *h_n2;
+  nsel2 = nsel;
   // (a batch of evaluations shares the edge scratch: at most CALL_EVAL_BATCH at a time)
   Event t0, t1;
   for (long long q0 = 0; q0 < nsel; q0 += CALL_EVAL_BATCH) {
@@ -1331,9 +1361,16 @@ TrgStatus Build::assemble_csr() {
   F.dist = (float *)bb.dist.p;
   HIPCHK(e, hipMemsetAsync(F.deg, 0, v1 * sizeof(int), s));
   HIPCHK(e, hipMemsetAsync(F.fill, 0, v1 * sizeof(int), s));
-  launch_fin_insert_count(F, B, ncalls, s);
+  // which call is its pair's edge, and the degrees.  early_copy (no step 3): a pair's first call when it
+  // succeeded, so only the pairs of the round-2 calls are reduced
+  if (early_copy) launch_fin_insert_count_listed(F, B, ncalls, (int *)bb.sel_list.p, nsel2, s);
+  else launch_fin_insert_count(F, B, ncalls, s);
   launch_exclusive_scan(F.deg, F.rowptr, V, (int *)bb.scan_tmp.p, s);
-  launch_fin_scatter(F, B, ncalls, s);
+  if (early_copy) {  // the rows are filled behind the renumbering and the node arrays: clean_and_fetch
+    lap("insert+count+scan");
+    return TRG_OK;
+  }
+  launch_fin_scatter(F, B, ncalls, true, s);
   lap("insert+count+scan+scatter");
   if (!e->keep_preclean) return TRG_OK;
   // the graph before cleanGraph, edges in push order (tests compare it with the oracle's)
@@ -1377,22 +1414,49 @@ TrgStatus Build::clean_and_fetch() {
   TrgStatus st;
   // (the order went to the device while the deferred evaluations ran, the statistics were summed behind it)
   HIPCHK(e, hipStreamWaitEvent(s, ev_order.ev, 0));
-  // tail_split: the structure only.  Nothing in it depends on a weight: the kernels up to here and these read
-  // call_status & EDGE_STATUS_MASK, call_n1 / _n2, call_dist and the node arrays.
-  launch_fin_clean(F, B, (int *)bb.map_order.p, V, (int *)bb.keep_flag.p, (int *)bb.keep_pos.p,
-                   (int *)bb.new2old.p, (int *)bb.old2new.p, (int *)bb.deg_new.p, (int *)bb.rowptr_new.p,
-                   (int *)bb.scan_tmp.p, (int *)bb.col2.p, tail_split ? nullptr : (float *)bb.w2.p,
-                   (float *)bb.dist2.p, (float *)bb.xyz2.p, (int *)bb.state2.p, s);
-  // The second stream starts behind the structure kernels, never beside them (k_node_weights rewrites words of
-  // call_status / call_w that k_fin_* read).
-  if (tail_split) HIPCHK(e, hipEventRecord(ev_structure.ev, s));
   int *h_tot = bb.h_ctrs + H_CLEAN_TOTALS;
-  HIPCHK(e, hipMemcpyAsync(h_tot, (int *)bb.keep_pos.p + V, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(e, hipMemcpyAsync(h_tot + 1, F.rowptr + V, sizeof(int), hipMemcpyDeviceToHost, s));
+  const hipStream_t cs = early_copy ? copy_stream() : s;  // the stream of the copies to the host
+  if (early_copy) {
+    // The renumbering and the node arrays need the degrees only (k_fin_keep_flag and k_fin_clean_deg read
+    // differences of F.rowptr), and both sizes are known after the scans: Vn = keep_pos[V], E = F.rowptr[V] (every
+    // edge survives cleanGraph, checked below).  So they come first, the copy stream takes the sizes and then the
+    // node arrays from there, and the main stream fills and orders the rows meanwhile.
+    launch_fin_renumber(F, B, (int *)bb.map_order.p, V, (int *)bb.keep_flag.p, (int *)bb.keep_pos.p,
+                        (int *)bb.new2old.p, (int *)bb.old2new.p, (int *)bb.deg_new.p, (int *)bb.rowptr_new.p,
+                        (int *)bb.scan_tmp.p, s);
+    launch_fin_clean_nodes(F, B, V, (int *)bb.keep_pos.p, (int *)bb.new2old.p, (float *)bb.xyz2.p,
+                           (int *)bb.state2.p, s);
+    HIPCHK(e, hipEventRecord(ev_node_arrays.ev, s));
+    edge_stream_busy = true;  // (from here on the main stream and the copy stream hold work nobody waited for)
+    HIPCHK(e, hipStreamWaitEvent(cs, ev_node_arrays.ev, 0));
+  } else {
+    // tail_split: the structure only.  Nothing in it depends on a weight: the kernels up to here and these read
+    // call_status & EDGE_STATUS_MASK, call_n1 / _n2, call_dist and the node arrays.
+    launch_fin_clean(F, B, (int *)bb.map_order.p, V, (int *)bb.keep_flag.p, (int *)bb.keep_pos.p,
+                     (int *)bb.new2old.p, (int *)bb.old2new.p, (int *)bb.deg_new.p, (int *)bb.rowptr_new.p,
+                     (int *)bb.scan_tmp.p, (int *)bb.col2.p, tail_split ? nullptr : (float *)bb.w2.p,
+                     (float *)bb.dist2.p, (float *)bb.xyz2.p, (int *)bb.state2.p, s);
+    // The second stream starts behind the structure kernels, never beside them (k_node_weights rewrites words of
+    // call_status / call_w that k_fin_* read).
+    if (tail_split) HIPCHK(e, hipEventRecord(ev_structure.ev, s));
+  }
+  HIPCHK(e, hipMemcpyAsync(h_tot, (int *)bb.keep_pos.p + V, sizeof(int), hipMemcpyDeviceToHost, cs));
+  HIPCHK(e, hipMemcpyAsync(h_tot + 1, F.rowptr + V, sizeof(int), hipMemcpyDeviceToHost, cs));
   // the statistics, for report_stats (S64_DEF_KEPT is final since round 2)
   HIPCHK(e, hipMemcpyAsync(bb.h_ctrs + H_STATS64, B.stats64, S64_PHASES * sizeof(unsigned long long),
-                           hipMemcpyDeviceToHost, s));
-  HIPCHK(e, hipStreamSynchronize(s));
+                           hipMemcpyDeviceToHost, cs));
+  if (early_copy) {
+    HIPCHK(e, hipEventRecord(ev_totals.ev, cs));
+    // the rows: entries in arrival order (no weights: the cleaned graph takes them from call_w, FIN_WEIGHTS),
+    // then col / dist of the cleaned graph in push order
+    launch_fin_scatter(F, B, ncalls, false, s);
+    launch_fin_clean_edges(F, B, V, (int *)bb.keep_pos.p, (int *)bb.new2old.p, (int *)bb.old2new.p,
+                           (int *)bb.rowptr_new.p, (int *)bb.col2.p, (float *)bb.dist2.p, s);
+    HIPCHK(e, hipEventRecord(ev_structure.ev, s));
+    HIPCHK(e, hipEventSynchronize(ev_totals.ev));  // the sizes alone: the main stream keeps running
+  } else {
+    HIPCHK(e, hipStreamSynchronize(s));
+  }
   const int Vn = h_tot[0], E = h_tot[1];
   lap("clean kernels");
   Csr &g = e->csr_global;
@@ -1409,12 +1473,15 @@ TrgStatus Build::clean_and_fetch() {
     g.w.resize(En);
     g.dist.resize(En);
     // node arrays first: the host rebuilds its node state from them while the edge arrays travel
-    HIPCHK(e, hipMemcpyAsync(g.xyz.data(), bb.xyz2.p, 3 * (size_t)Vn * sizeof(float), hipMemcpyDeviceToHost, s));
+    // (early_copy: cs is behind ev_node_arrays already, and rowptr, which needs no more than they do, goes with them)
+    HIPCHK(e, hipMemcpyAsync(g.xyz.data(), bb.xyz2.p, 3 * (size_t)Vn * sizeof(float), hipMemcpyDeviceToHost, cs));
     if (tail_split && En) {
       // The compute units have nothing to do during these copies: the covariances, the SVDs and the weights of
       // the cleaned graph (a pass over its rows that writes w2 alone) run now, on the second stream, and w2
       // goes last.  (Enqueued behind the first copy so that the copy is under way when the chip fills up.)
       hipStream_t s2 = e->s_edge;
+      // (Measured and dropped: k_node_cov, which only reads call_status, in front of this wait, beside
+      // k_fin_scatter -- no gain, 37.78 ms per C3 build either way: w does not wait for its weights.)
       HIPCHK(e, hipStreamWaitEvent(s2, ev_structure.ev, 0));
       edge_stream_busy = true;
       launch_creating_edge_weights(s2);
@@ -1422,15 +1489,16 @@ TrgStatus Build::clean_and_fetch() {
                                (float *)bb.w2.p, s2);
       HIPCHK(e, hipEventRecord(ev_weights.ev, s2));
     }
-    HIPCHK(e, hipMemcpyAsync(g.state.data(), bb.state2.p, (size_t)Vn * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipMemcpyAsync(g.cid.data(), bb.new2old.p, (size_t)Vn * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipEventRecord(ev_nodes.ev, s));
-    HIPCHK(e, hipMemcpyAsync(g.rowptr.data(), bb.rowptr_new.p, ((size_t)Vn + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(g.state.data(), bb.state2.p, (size_t)Vn * sizeof(int), hipMemcpyDeviceToHost, cs));
+    HIPCHK(e, hipMemcpyAsync(g.cid.data(), bb.new2old.p, (size_t)Vn * sizeof(int), hipMemcpyDeviceToHost, cs));
+    HIPCHK(e, hipEventRecord(ev_nodes.ev, cs));
+    HIPCHK(e, hipMemcpyAsync(g.rowptr.data(), bb.rowptr_new.p, ((size_t)Vn + 1) * sizeof(int), hipMemcpyDeviceToHost, cs));
     if (En) {
-      HIPCHK(e, hipMemcpyAsync(g.col.data(), bb.col2.p, (size_t)En * sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(e, hipMemcpyAsync(g.dist.data(), bb.dist2.p, (size_t)En * sizeof(float), hipMemcpyDeviceToHost, s));
-      if (tail_split) HIPCHK(e, hipStreamWaitEvent(s, ev_weights.ev, 0));
-      HIPCHK(e, hipMemcpyAsync(g.w.data(), bb.w2.p, (size_t)En * sizeof(float), hipMemcpyDeviceToHost, s));
+      if (early_copy) HIPCHK(e, hipStreamWaitEvent(cs, ev_structure.ev, 0));  // (the other orders: same stream)
+      HIPCHK(e, hipMemcpyAsync(g.col.data(), bb.col2.p, (size_t)En * sizeof(int), hipMemcpyDeviceToHost, cs));
+      HIPCHK(e, hipMemcpyAsync(g.dist.data(), bb.dist2.p, (size_t)En * sizeof(float), hipMemcpyDeviceToHost, cs));
+      if (tail_split) HIPCHK(e, hipStreamWaitEvent(cs, ev_weights.ev, 0));
+      HIPCHK(e, hipMemcpyAsync(g.w.data(), bb.w2.p, (size_t)En * sizeof(float), hipMemcpyDeviceToHost, cs));
     }
     mark("copies enqueued");
     // while the copies run: global_graph.nodes = new_nodes (trg.cpp:526) -- the copy takes over the
@@ -1457,14 +1525,18 @@ TrgStatus Build::clean_and_fetch() {
       e->nstate[k] = g.state[k];
     }
     mark("host node state");
-    if ((st = read_ctrs()) != TRG_OK) return st;  // (the main stream waited for the second one: both are drained)
-    edge_stream_busy = false;
+    // (the stream of the copies waited for the second one; early_copy: the main stream ended long before them)
+    if ((st = read_ctrs()) != TRG_OK) return st;
+    if (early_copy) HIPCHK(e, hipStreamSynchronize(cs));
+    edge_stream_busy = false;  // all three are drained
     if (bb.h_ctrs[BFS_CTR_ERR]) return fallback(err_text(bb.h_ctrs[BFS_CTR_ERR]));
     if (g.rowptr[Vn] != En) return e->fail(TRG_ERR_DEVICE, "cleanGraph edge count mismatch");
   } else {
     MapOrderSim new_nodes;
     e->nodes_sim.assign_from(new_nodes);
-    if ((st = read_ctrs()) != TRG_OK) return st;
+    if ((st = read_ctrs()) != TRG_OK) return st;  // (no copy was enqueued; early_copy: the rows' kernels end here)
+    if (early_copy) HIPCHK(e, hipStreamSynchronize(cs));
+    edge_stream_busy = false;
     if (bb.h_ctrs[BFS_CTR_ERR]) return fallback(err_text(bb.h_ctrs[BFS_CTR_ERR]));
     e->nx.clear();
     e->ny.clear();

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "map_order_runs.h"
+
 namespace trg {
 
 // Cell-sorted structure-of-arrays map index (replaces the reference's 2-D kd-tree of map points,
@@ -293,14 +295,17 @@ constexpr int STATS64_SPEC_KNOWN = 4;  // speculative parent edges that took the
 struct FinDev {
   unsigned long long *ht_key;
   int *ht_seq;
-  int *ok_seq;  // per table entry: the smallest call number among the pair's SUCCESSFUL calls (its edge)
+  int *ok_seq;  // per table entry: the smallest call number among the pair's SUCCESSFUL calls (its edge); after
+                // launch_fin_insert_count_listed: valid for the pairs of the round-2 calls only, the others' edge
+                // is their first call (ht_seq)
   unsigned ht_size;
   int *call_slot;
   int *deg, *fill, *rowptr;
   int *col, *seq;
   float *w, *dist;  // w: call_w as k_fin_scatter found it.  In a build that computes the creating edges' weights
                     // after the scatter (Build::tail_split) those entries are stale and w has no reader: the
-                    // cleaned graph takes its weights from call_w (launch_fin_clean_weights)
+                    // cleaned graph takes its weights from call_w (launch_fin_clean_weights); with
+                    // launch_fin_scatter(with_w = false) it is not written at all
 };
 
 void launch_bfs_insert_nodes(const BfsDev &B, int first, int count, hipStream_t s);
@@ -352,8 +357,23 @@ void launch_calls_select_append(const FinDev &F, const BfsDev &B, long long c0, 
 void launch_calls_select2_append(const FinDev &F, const BfsDev &B, long long ncalls, int *list, int *count,
                                  unsigned long long *total, hipStream_t s);
 void launch_fin_insert_count(const FinDev &F, const BfsDev &B, long long ncalls, hipStream_t s);
-void launch_fin_scatter(const FinDev &F, const BfsDev &B, long long ncalls, hipStream_t s);
+// builds without step 3: ok_seq over the round-2 calls list[0..count) alone, F.ok_seq needs no clear (trg_bfs.inc)
+void launch_fin_insert_count_listed(const FinDev &F, const BfsDev &B, long long ncalls, const int *list, int count,
+                                    hipStream_t s);
+// with_w = false: F.w is left alone (a build whose cleaned graph takes its weights from call_w: launch_fin_clean_weights)
+void launch_fin_scatter(const FinDev &F, const BfsDev &B, long long ncalls, bool with_w, hipStream_t s);
 void launch_fin_rowsort(const FinDev &F, int V, hipStream_t s);
+// map_order[0..V) expanded on the device from the node container's runs (map_order_runs.h)
+void launch_map_order_fill(const MapOrderRuns &R, int V, int *map_order, hipStream_t s);
+// launch_fin_clean in three steps, for a build that sends the node arrays to the host while the rows are still
+// being filled: the renumbering (needs F.rowptr, not the rows), xyz / state, and col / dist after launch_fin_scatter
+void launch_fin_renumber(const FinDev &F, const BfsDev &B, const int *map_order, int V, int *keep_flag,
+                         int *keep_pos, int *new2old, int *old2new, int *deg_new, int *rowptr_new,
+                         int *scan_tmp, hipStream_t s);
+void launch_fin_clean_nodes(const FinDev &F, const BfsDev &B, int V, const int *keep_pos, const int *new2old,
+                            float *xyz, int *state, hipStream_t s);
+void launch_fin_clean_edges(const FinDev &F, const BfsDev &B, int V, const int *keep_pos, const int *new2old,
+                            const int *old2new, const int *rowptr_new, int *col, float *dist, hipStream_t s);
 void launch_fin_clean(const FinDev &F, const BfsDev &B, const int *map_order, int V, int *keep_flag,
                       int *keep_pos, int *new2old, int *old2new, int *deg_new, int *rowptr_new,
                       int *scan_tmp, int *col, float *w, float *dist, float *xyz, int *state,
