@@ -155,8 +155,8 @@ typedef struct TrgStats {
   double ms_deferred;          /* device path: wall time of the deferred edge evaluations */
   uint64_t map_nn_resolved;    /* of those, the ones an accepted sample / addNode depended on: decided
                                   in the reference's map-tree visiting order (kdtree.c:303-362) */
-  uint64_t map_nn_unresolved;  /* ties left at "lowest cloud index" (more than 16 points tied, or more
-                                  than 256 tied samples in one launch) -- 0 in practice */
+  uint64_t map_nn_unresolved;  /* always 0: every tie is decided, however many points tie and however many
+                                  samples of a launch do (the field keeps its place in the struct) */
   uint64_t bfs_tie_fixups;     /* BFS levels whose only trouble was a distance tie among nodes that existed
                                   before the level: the reference's winner was handed to the device and
                                   resolve + commit ran again (no host replay) */

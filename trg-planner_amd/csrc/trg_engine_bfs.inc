@@ -450,16 +450,23 @@ TrgStatus Build::redo_commit(Level &lv, bool decide_gates, bool ticketed, int ho
 // of the level, since the rerun may let another of them create.
 TrgStatus Build::fix_map_ties(Level &lv) {
   TrgStatus st;
-  std::vector<MapTieRec> recs((size_t)std::min(lv.n_mt, MAPTIE_CAP));
-  HIPCHK(e, hipMemcpy(recs.data(), B.mt_rec + lv.parity * MAPTIE_CAP, recs.size() * sizeof(MapTieRec),
+  if ((size_t)lv.n_mt > lv.slots) return e->fail(TRG_ERR_DEVICE, "more map-tie records than the level has slots");
+  std::vector<MapTieRec> recs((size_t)lv.n_mt);
+  HIPCHK(e, hipMemcpy(recs.data(), B.mt_rec + (size_t)lv.parity * B.mt_cap, recs.size() * sizeof(MapTieRec),
                       hipMemcpyDeviceToHost));
-  if (lv.n_mt > MAPTIE_CAP) e->stats.map_nn_unresolved += (uint64_t)(lv.n_mt - MAPTIE_CAP);
   e->stats.map_tie_records += recs.size();
   std::vector<SlotRec> srs(recs.size());
-  for (size_t k = 0; k < recs.size(); ++k) {
+  for (size_t k = 0; k < recs.size(); ++k)
     if (recs[k].slot < 0 || (size_t)recs[k].slot >= lv.slots)
       return e->fail(TRG_ERR_DEVICE, "map-tie record of a slot outside the level");
-    HIPCHK(e, hipMemcpy(&srs[k], B.slot_rec + recs[k].slot, sizeof(SlotRec), hipMemcpyDeviceToHost));
+  if (recs.size() * 8 >= lv.slots) {
+    // a level where ties are the rule (a twinned cloud): the level's slot records in one copy, not one copy a record
+    std::vector<SlotRec> all(lv.slots);
+    HIPCHK(e, hipMemcpy(all.data(), B.slot_rec, lv.slots * sizeof(SlotRec), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < recs.size(); ++k) srs[k] = all[recs[k].slot];
+  } else {
+    for (size_t k = 0; k < recs.size(); ++k)
+      HIPCHK(e, hipMemcpy(&srs[k], B.slot_rec + recs[k].slot, sizeof(SlotRec), hipMemcpyDeviceToHost));
   }
   std::vector<char> repair(recs.size(), 1);
   if (e->lazy_tie_repair) {
@@ -971,7 +978,7 @@ TrgStatus Build::allocate() {
   // unc_list: even levels, odd levels, deferred evaluations; tied slots
   if ((st = ensure_all(e, {{&bb.mid, edge_mid_floats(CALL_EVAL_BATCH) * FL},
                            {&bb.unc_list, (3 * BFS_UNC_CAP + BFS_TIE_CAP) * I},
-                           {&bb.unc_rec, 3 * 3 * BFS_UNC_CAP * FL}, {&bb.mt_rec, 2 * MAPTIE_CAP * sizeof(MapTieRec)},
+                           {&bb.unc_rec, 3 * 3 * BFS_UNC_CAP * FL}, {&bb.mt_rec, 2 * slots * sizeof(MapTieRec)},
                            {&bb.ctrs, BFS_CTR_COUNT * I}, {&bb.stats64, S64_WORDS * sizeof(unsigned long long)},
                            {&bb.wg_state, wg_words * sizeof(unsigned long long)},
                            {&bb.c_cell, slots * sizeof(unsigned long long)}, {&bb.nexp, vcap * sizeof(int4)},
@@ -982,6 +989,7 @@ TrgStatus Build::allocate() {
   B.tie_list = B.unc_list + 3 * BFS_UNC_CAP;
   B.unc_rec = (float *)bb.unc_rec.p;
   B.mt_rec = (MapTieRec *)bb.mt_rec.p;
+  B.mt_cap = (int)slots;  // (a record per slot of a level, for either parity: k_level_sample drops none)
   B.ctrs = (int *)bb.ctrs.p;
   B.stats64 = (unsigned long long *)bb.stats64.p;
   B.wg_state = (unsigned long long *)bb.wg_state.p;

@@ -82,9 +82,9 @@ TrgStatus ensure_tie_scratch(TrgEngine *e) {
 }
 
 // which of the tied points A, B the nearest-neighbour search for q visits first: 0 = A, 1 = B.  The
-// walk (region scan + decision per tree level, ~30-50 levels on a 10 M-point map) runs on the device
-// without the host in between: the first steps (regions of millions of points) one grid-wide kernel
-// each, enqueued blindly, the rest inside a single workgroup; steps after the decision return at once.
+// walk (region scan + decision per tree level, ~30-50 levels on a shuffled 10 M-point map) starts on the host,
+// in the top of the tree, and goes on inside a single workgroup on the device, 64 levels per launch; steps after
+// the decision return at once.
 constexpr int MAP_TOP_POINTS = 8192;  // points of the host-side top of the map tree
 
 // The first MAP_TOP_POINTS points of the cloud, inserted like kd_insert does (kdtree.c:179-198: `<` goes
@@ -167,7 +167,6 @@ TrgStatus map_first_of_two(TrgEngine *e, DevMap &m, float qx, float qy, const Ti
   TrgStatus st = ensure_map_top(e, m);
   if (st != TRG_OK) return st;
   MapTieWalk w{};
-  w.key = ~0ull;
   w.lo[0] = w.lo[1] = -INFINITY;
   w.hi[0] = w.hi[1] = INFINITY;
   w.cur_perm = -1;
@@ -217,17 +216,20 @@ TrgStatus map_first_of_two(TrgEngine *e, DevMap &m, float qx, float qy, const Ti
   }
   *e->mt_walk.h = w;
   HIPCHK(e, hipMemcpyAsync(e->mt_walk.d, e->mt_walk.h, sizeof(MapTieWalk), hipMemcpyHostToDevice, s));
-  for (int batch = 0; batch < 64; ++batch) {
-    // what is left of the region after the top of the tree holds ~N / 8192 points: one workgroup walks it
-    // (a full-size region -- a map smaller than the top -- cannot get here)
-    launch_map_tie_walk(m.view, e->mt_walk.d, 0, 64, s);
+  // what is left of the region after the top of the tree holds ~N / 8192 points of a shuffled cloud: one workgroup
+  // walks it (a full-size region -- a map smaller than the top -- cannot get here).  Every step descends one level
+  // of the tree, so the map's point count bounds the walk: a cloud in sorted order makes a chain of that depth, and
+  // the launches go on for as long as they advance.
+  for (int steps = w.steps;;) {
+    launch_map_tie_walk(m.view, e->mt_walk.d, 64, s);
     HIPCHK(e, hipMemcpyAsync(e->mt_walk.h, e->mt_walk.d, sizeof(MapTieWalk), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     if (e->mt_walk.h->done == 1) {
       *first = e->mt_walk.h->first;
       return TRG_OK;
     }
-    if (e->mt_walk.h->done) break;
+    if (e->mt_walk.h->done || e->mt_walk.h->steps <= steps || (size_t)e->mt_walk.h->steps > m.n) break;
+    steps = e->mt_walk.h->steps;
   }
   return e->fail(TRG_ERR_DEVICE, "nearest-point tie-break lost its candidates (internal error)");
 }
@@ -237,38 +239,43 @@ TrgStatus map_nn_exact(TrgEngine *e, DevMap &m, float qx, float qy, float *z, bo
   TrgStatus st = ensure_tie_scratch(e);
   if (st != TRG_OK) return st;
   hipStream_t s = e->s_aux;  // (the map is read-only here; the main stream may hold speculative work)
-  launch_map_tied_set(m.view, qx, qy, e->prm.robot_size, e->mt_set.d, s);
-  HIPCHK(e, hipMemcpyAsync(e->mt_set.h, e->mt_set.d, sizeof(MapTieSet), hipMemcpyDeviceToHost, s));
-  HIPCHK(e, hipStreamSynchronize(s));
-  const MapTieSet T = *e->mt_set.h;
-  *found = T.count > 0;
-  if (!*found) return TRG_OK;
-  const int n = std::min(T.count, MAPTIE_SET_CAP);
-  // lowest original index first, so that an unresolved case equals the hot kernels' provisional pick
-  int order[MAPTIE_SET_CAP];
-  for (int i = 0; i < n; ++i) order[i] = i;
-  std::sort(order, order + n, [&](int a, int b) { return T.perm[a] < T.perm[b]; });
-  *z = T.z[order[0]];
-  if (T.count == 1) return TRG_OK;
-  if (T.count > MAPTIE_SET_CAP) {
-    e->stats.map_nn_unresolved++;
-    return TRG_OK;
+  // the tied points, a page of MAPTIE_SET_CAP per launch: every page scans the same cells in the same order, and the
+  // first one's count says how many there are
+  struct Tied {
+    int perm;
+    float x, y, z;
+  };
+  std::vector<Tied> T;
+  for (int skip = 0, count = 1; skip < count; skip += MAPTIE_SET_CAP) {
+    launch_map_tied_set(m.view, qx, qy, e->prm.robot_size, skip, e->mt_set.d, s);
+    HIPCHK(e, hipMemcpyAsync(e->mt_set.h, e->mt_set.d, sizeof(MapTieSet), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    const MapTieSet &P = *e->mt_set.h;
+    if (skip == 0) T.reserve((size_t)std::max(count = P.count, 0));
+    else if (P.count != count) return e->fail(TRG_ERR_DEVICE, "nearest-point tie set changed between its pages");
+    for (int i = 0; i < std::min(count - skip, MAPTIE_SET_CAP); ++i) T.push_back({P.perm[i], P.x[i], P.y[i], P.z[i]});
   }
+  *found = !T.empty();
+  if (!*found) return TRG_OK;
+  // lowest original index first: the hot kernels' provisional pick, and the root if it is among them
+  std::sort(T.begin(), T.end(), [](const Tied &a, const Tied &b) { return a.perm < b.perm; });
+  *z = T[0].z;
+  if (T.size() == 1) return TRG_OK;
   e->stats.map_nn_resolved++;
   bool same_z = true;
-  for (int i = 1; i < n; ++i) same_z = same_z && T.z[order[i]] == T.z[order[0]];
+  for (const Tied &t : T) same_z = same_z && t.z == T[0].z;
   if (same_z) return TRG_OK;
-  if (T.perm[order[0]] == 0) return TRG_OK;  // the root keeps an equal distance (kdtree.c:393-396)
-  int w = order[0];
-  for (int i = 1; i < n; ++i) {
-    const int c = order[i];
-    const TiePoint A{T.perm[w], T.x[w], T.y[w]}, B{T.perm[c], T.x[c], T.y[c]};
+  if (T[0].perm == 0) return TRG_OK;  // the root keeps an equal distance (kdtree.c:393-396)
+  // a linear tournament: the visiting order is a total order, one winner is kept
+  size_t w = 0;
+  for (size_t c = 1; c < T.size(); ++c) {
+    const TiePoint A{T[w].perm, T[w].x, T[w].y}, B{T[c].perm, T[c].x, T[c].y};
     int first = 0;
     st = map_first_of_two(e, m, qx, qy, A, B, &first);
     if (st != TRG_OK) return st;
     if (first == 1) w = c;
   }
-  *z = T.z[w];
+  *z = T[w].z;
   return TRG_OK;
 }
 

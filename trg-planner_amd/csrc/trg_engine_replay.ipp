@@ -17,7 +17,7 @@ TrgStatus ensure_chunks(TrgEngine *e) {
     for (Event *ev : {&c.t0, &c.t1, &c.t2}) HIPCHK(e, ev->create());
     HIPCHK(e, c.in_blob.ensure(6 * cmax));
     HIPCHK(e, c.out_blob.ensure(2 * cmax + 6 * slots));
-    HIPCHK(e, c.mt.ensure(4 + 4 * (size_t)MAPTIE_CAP));
+    HIPCHK(e, c.mt.ensure(4 + 4 * std::max(slots, (size_t)MAPTIE_CAP)));  // (a record per slot: none is dropped)
     HIPCHK(e, c.mid.ensure(edge_mid_floats(slots)));
   }
   const size_t emax = TrgEngine::EBATCH_MAX;
@@ -95,8 +95,11 @@ TrgStatus wait_chunk(TrgEngine *e, Chunk &c) {
   if (n_mt > 0) {
     const int S = e->prm.sample_num;
     const MapTieRec *recs = (const MapTieRec *)(c.mt.h + 4);
-    if (n_mt > MAPTIE_CAP) e->stats.map_nn_unresolved += (uint64_t)(n_mt - MAPTIE_CAP);
-    for (int k = 0; k < std::min(n_mt, MAPTIE_CAP); ++k) {
+    if (n_mt > c.count * S) return e->fail(TRG_ERR_DEVICE, "more map-tie records than the chunk has slots");
+    if (n_mt > MAPTIE_CAP)  // the records past those that came back with the chunk's results
+      HIPCHK(e, hipMemcpy(c.mt.h + 4 + 4 * (size_t)MAPTIE_CAP, c.mt.d + 4 + 4 * (size_t)MAPTIE_CAP,
+                          (size_t)(n_mt - MAPTIE_CAP) * sizeof(MapTieRec), hipMemcpyDeviceToHost));
+    for (int k = 0; k < n_mt; ++k) {
       const MapTieRec &r = recs[k];
       float z = 0;
       bool found = false;

@@ -26,15 +26,16 @@ struct MapView {
 
 // An accepted sample whose nearest map point was not unique (kd_nearest's visiting order decides
 // which one the reference takes, trg.cpp:226-233 -> kdtree.c:303-362); the host resolves these.
-constexpr int MAPTIE_CAP = 256;      // records per sampling launch
-constexpr int MAPTIE_SET_CAP = 16;   // points listed per tie
+// A sampling launch keeps every record (a slot ties at most once, the lists hold one record per slot).
+constexpr int MAPTIE_CAP = 256;      // records the host replay copies back with a chunk's results; more are fetched after
+constexpr int MAPTIE_SET_CAP = 16;   // points of a tie listed per page (k_map_tied_set's `skip`)
 struct MapTieRec {
   int slot;        // sample slot of the launch (node * S + j)
   float qx, qy;    // the sample position
   float d2;        // the tied fp32 squared distance
 };
 struct MapTieSet {
-  int count;
+  int count;                  // all tied points, whichever page was asked for
   float d2;
   int sidx[MAPTIE_SET_CAP];   // index in the cell-sorted arrays
   int perm[MAPTIE_SET_CAP];   // original (insertion) index
@@ -127,12 +128,12 @@ void launch_sample_nodes(const MapView &m, QueryParams p, const float *cos_t, co
                          float *sy, float *sz, DeviceCounters *ctr, int *mt_count,
                          MapTieRec *mt_rec, hipStream_t s);
 // exact nearest-point tie-break helpers (rare path, see map_nn_exact in trg_engine.cpp)
-void launch_map_tied_set(const MapView &m, float qx, float qy, float r0, MapTieSet *d_out,
+// the tied points number skip .. skip + MAPTIE_SET_CAP - 1 in the order of the cell-sorted arrays, and the count of all
+void launch_map_tied_set(const MapView &m, float qx, float qy, float r0, int skip, MapTieSet *d_out,
                          hipStream_t s);
 // State of one walk down the map's insertion tree (which of two tied points kd_nearest visits first):
 // the steps run on the device back to back, the host only looks at the final state.
 struct MapTieWalk {
-  unsigned long long key;  // smallest (original index << 32 | sorted index) of the current scan; ~0 = none
   float lo[2], hi[2];      // half-open region of the current subtree
   int cur_perm;            // its ancestor (points inserted later than this one are in the subtree)
   int axis;
@@ -141,10 +142,9 @@ struct MapTieWalk {
   float ax, ay, bx, by;
   int done;                // 0 walking, 1 decided (first = 0: A, 1: B), 2 lost its candidates
   int first;
-  int steps;
-  int ticket;              // workgroups of the current grid step that have finished
+  int steps;               // tree levels descended so far, the host's part included
 };
-void launch_map_tie_walk(const MapView &m, MapTieWalk *d_state, int grid_steps, int block_steps, hipStream_t s);
+void launch_map_tie_walk(const MapView &m, MapTieWalk *d_state, int block_steps, hipStream_t s);
 // out_xy[2 * k], [2 * k + 1] = position of the point with original index k, for k < M
 void launch_collect_first(const MapView &m, int M, float *d_out_xy, hipStream_t s);
 // Speculative parent edges node -> sample for every accepted sample of a chunk:
@@ -275,7 +275,8 @@ struct BfsDev {
   int *unc_list;
   float *unc_rec;
   int *tie_list;      // BFS_TIE_CAP slots of the current level that met an exact distance tie in k_level_resolve
-  MapTieRec *mt_rec;  // 2 x MAPTIE_CAP records (level parity), counts in ctrs[BFS_CTR_NMAPTIE + parity]
+  MapTieRec *mt_rec;  // 2 x mt_cap records (level parity), counts in ctrs[BFS_CTR_NMAPTIE + parity]
+  int mt_cap;         // = the slots of a level (fcap * sample_num): a slot ties at most once, no record is dropped
   // call log (one record per sample slot, in program order)
   int *call_n1, *call_n2, *call_status;
   float *call_w, *call_dist;

@@ -1655,8 +1655,9 @@ __global__ __launch_bounds__(QW *WAVE) void k_probe_nearest_z(MapView m, QueryPa
 }
 
 // ---- exact nearest-point tie-break (rare path) ----------------------------------------------------
-// One wave: the set of map points at the minimal fp32 distance from (qx, qy).
-__global__ __launch_bounds__(WAVE) void k_map_tied_set(MapView m, float qx, float qy, float r0,
+// One wave: the set of map points at the minimal fp32 distance from (qx, qy).  The count is of all of them; listed
+// is the page of MAPTIE_SET_CAP that starts at number `skip` of the scan's order (cell rows, then the sorted index).
+__global__ __launch_bounds__(WAVE) void k_map_tied_set(MapView m, float qx, float qy, float r0, int skip,
                                                        MapTieSet *out) {
   const int lane = lane_id();
   float R = r0;
@@ -1689,8 +1690,8 @@ __global__ __launch_bounds__(WAVE) void k_map_tied_set(MapView m, float qx, floa
           }
           const unsigned long long mask = __ballot(hit);
           if (hit) {
-            const int pos = n + __popcll(mask & lanemask_lt());
-            if (pos < MAPTIE_SET_CAP) {
+            const int pos = n + __popcll(mask & lanemask_lt()) - skip;
+            if (pos >= 0 && pos < MAPTIE_SET_CAP) {
               out->sidx[pos] = i;
               out->perm[pos] = m.perm[i];
               out->x[pos] = m.x[i];
@@ -1804,35 +1805,8 @@ __global__ __launch_bounds__(256) void k_collect_first(MapView m, int M, float *
   }
 }
 
-// One step with the whole grid scanning (the top of the tree: regions of millions of points); the
-// workgroup that finishes last takes the decision.
-__global__ __launch_bounds__(256) void k_region_walk_grid(MapView m, MapTieWalk *st) {
-  if (st->done) return;  // (every workgroup reads the same value: only the last one of a launch writes it)
-  const WalkRegion g{st->lo[0], st->hi[0], st->lo[1], st->hi[1], st->cur_perm};
-  __shared__ unsigned long long red[4];
-  __shared__ int last;
-  const unsigned long long wbest = region_scan_rows(m, g, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x, 256);
-  if (lane_id() == 0) red[threadIdx.x >> 6] = wbest;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long best = red[0];
-    for (int i = 1; i < 4; ++i) best = red[i] < best ? red[i] : best;
-    if (best != ~0ull) atomicMin(&st->key, best);
-    __threadfence();
-    last = atomicAdd(&st->ticket, 1) == (int)gridDim.x - 1;
-  }
-  __syncthreads();
-  if (last && threadIdx.x == 0) {
-    __threadfence();
-    const unsigned long long key = __hip_atomic_load(&st->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    st->key = ~0ull;
-    st->ticket = 0;
-    region_step(m, st, key);
-  }
-}
-
-// The rest of the walk in one workgroup: after a dozen halvings the region holds a few thousand
-// points, and a step is a scan of a few cell rows.
+// The walk below the host's top of the tree in one workgroup: on a shuffled cloud the region holds a few thousand
+// points after a dozen halvings, and a step is a scan of a few cell rows.
 __global__ __launch_bounds__(1024) void k_region_walk_block(MapView m, MapTieWalk *st, int max_steps) {
   __shared__ unsigned long long red[16];
   __shared__ int done_s;
@@ -2231,7 +2205,7 @@ __global__ __launch_bounds__(SW *WAVE, 8) void k_sample_nodes(MapView m, QueryPa
         ties++;
         if (mt_count) {
           const int k = atomicAdd(mt_count, 1);
-          if (k < MAPTIE_CAP) {
+          if (k < count * S) {  // (a slot ties at most once: the list holds one record per slot of the launch)
             MapTieRec rec;
             rec.slot = slot;
             rec.qx = qx;
@@ -2367,19 +2341,14 @@ void launch_sample_nodes(const MapView &m, QueryParams p, const float *cos_t, co
                      ctr, (const int *)nullptr, (const float *)nullptr, (const float *)nullptr,
                      mt_count, mt_rec, (const int *)nullptr, 0);
 }
-void launch_map_tied_set(const MapView &m, float qx, float qy, float r0, MapTieSet *d_out,
+void launch_map_tied_set(const MapView &m, float qx, float qy, float r0, int skip, MapTieSet *d_out,
                          hipStream_t s) {
-  hipLaunchKernelGGL(k_map_tied_set, dim3(1), dim3(WAVE), 0, s, m, qx, qy, r0, d_out);
+  hipLaunchKernelGGL(k_map_tied_set, dim3(1), dim3(WAVE), 0, s, m, qx, qy, r0, skip, d_out);
 }
 void launch_collect_first(const MapView &m, int M, float *d_out_xy, hipStream_t s) {
   hipLaunchKernelGGL(k_collect_first, dim3(blocks_for(m.n, 256, 4096)), dim3(256), 0, s, m, M, d_out_xy);
 }
-void launch_map_tie_walk(const MapView &m, MapTieWalk *d_state, int grid_steps, int block_steps, hipStream_t s) {
-  // the top of the tree with the whole grid (cell rows strided over the workgroups), the rest in one
-  // workgroup
-  const int rows = m.H < 256 ? m.H : 256;
-  for (int k = 0; k < grid_steps; ++k)
-    hipLaunchKernelGGL(k_region_walk_grid, dim3(rows), dim3(256), 0, s, m, d_state);
+void launch_map_tie_walk(const MapView &m, MapTieWalk *d_state, int block_steps, hipStream_t s) {
   if (block_steps > 0) hipLaunchKernelGGL(k_region_walk_block, dim3(1), dim3(1024), 0, s, m, d_state, block_steps);
 }
 void launch_spec_edges(const MapView &m, QueryParams p, const float *node_xyz, int count,

@@ -428,13 +428,13 @@ __device__ __forceinline__ void sample_pure_draws(const MapView &m, const QueryP
       if (d.nn_tie) {
         atomicAdd(&P.r_ties[w], 1);
         const int k = atomicAdd(&B.ctrs[BFS_CTR_NMAPTIE + mt_parity], 1);
-        if (k < MAPTIE_CAP) {
+        if (k < B.mt_cap) {  // (a slot ties at most once, and the list holds a record per slot: always)
           MapTieRec rec;
           rec.slot = mt_slot_base + my_slot;
           rec.qx = qx;
           rec.qy = qy;
           rec.d2 = d.nn_d2;
-          B.mt_rec[mt_parity * MAPTIE_CAP + k] = rec;
+          B.mt_rec[(size_t)mt_parity * B.mt_cap + k] = rec;
         }
       }
     }
