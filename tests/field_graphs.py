@@ -8,8 +8,7 @@ from collections import namedtuple
 
 import numpy as np
 
-F32 = np.float32
-INVALID = -1
+from field_keys import F32, INVALID, cost_values  # noqa: F401
 
 # rowptr, col, w, dist, state: the CSR the reference takes; pos: (V, 3) float32, at least 1 m apart
 FieldGraph = namedtuple("FieldGraph", "rowptr col w dist state pos")
@@ -92,7 +91,7 @@ def from_edges(V, src, dst, w, dist, state=None, pos=None):
 
 def edge_costs(g, sf):
     """(safety_factor * w + 1) * dist, every operation rounded to fp32."""
-    return (F32(sf) * g.w + F32(1.0)) * g.dist
+    return cost_values(g.w, g.dist, sf)
 
 
 def bucket_width(g, sf, scale):

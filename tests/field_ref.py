@@ -1,24 +1,33 @@
 """Test helper: the host Dijkstra of the cost field (tests/cpp/field_reference.cpp), compiled with g++ into a
-shared library and called through ctypes.  Test code only; the product never links it."""
+shared library and called through ctypes, the one g++ line of every host reference (compile_cpp), and the definition
+of a field restated apart from any Dijkstra (definition_field; py_field binds it to the cost objective,
+risk_ref.py_risk_field to the risk objective).  Test code only; the product never links it."""
 import ctypes as C
 import os
 import subprocess
+from types import SimpleNamespace
 
 import numpy as np
 
-SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp", "field_reference.cpp")
-F32 = np.float32
-INVALID = -1  # a node state: never entered
+from field_keys import F32, INVALID, cost_values, edge_list  # noqa: F401
+
+CPP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp")
 NO_EDGE = 1   # some edge cost is negative or not finite
 BAD_SOURCE = 2
 
 
+def compile_cpp(out_dir, source_name):
+    """tests/cpp/<source_name>.cpp as a shared library in out_dir -> ctypes library.  Every host reference is built
+    with these flags: no contraction and no fast math, so that fp32 expressions round as written."""
+    so = os.path.join(str(out_dir), f"lib{source_name}.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
+                           os.path.join(CPP, source_name + ".cpp"), "-o", so])
+    return C.CDLL(so)
+
+
 def compile_reference(out_dir):
     """-> ctypes library (built into out_dir)."""
-    so = os.path.join(str(out_dir), "libfield_reference.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
-                           SRC, "-o", so])
-    lib = C.CDLL(so)
+    lib = compile_cpp(out_dir, "field_reference")
     ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
     lib.field_reference.argtypes = [C.c_int, ip, ip, fp, fp, ip, C.c_float, C.c_int, fp, ip, ip]
     lib.field_reference.restype = C.c_int
@@ -48,27 +57,28 @@ def field_of_graph(lib, g, sf, src):
     return field(lib, g.rowptr, g.col, g.w, g.dist, g.state, sf, src)
 
 
-def py_field(V, rowptr, col, w, dist, state, sf, src):
-    """The definition, restated apart from any Dijkstra: cost = the least fp32 fold over all walks (a
-    Bellman-Ford on the cost alone: fl(a + c) is monotone in a); hops = the BFS depth of the tight subgraph
-    (edges with fl(cost[u] + c) == cost[v]); parent = the smallest tight u with hops[u] + 1 == hops[v]."""
-    sf = F32(sf)
-    ec = [(sf * F32(w[k]) + F32(1.0)) * F32(dist[k]) for k in range(len(col))]
-    edges = [(u, int(col[k]), ec[k]) for u in range(V) for k in range(rowptr[u], rowptr[u + 1])
-             if state[int(col[k])] != INVALID]
-    cost = [None] * V
-    cost[src] = F32(0.0)
+def definition_field(V, edges, fold, sources):
+    """The definition of a field, restated apart from any Dijkstra, for either objective: value = the least fold over
+    all walks from a source (a Bellman-Ford on the value alone: fold(a, c) is monotone in a); hops = the BFS depth of
+    the tight subgraph (edges with fold(value[u], c) == value[v]) from the sources; parent = the smallest tight u with
+    hops[u] + 1 == hops[v].  edges: field_keys.edge_list's; fold: of two float32 scalars."""
+    sources = sorted({int(s) for s in np.atleast_1d(sources)})
+    edges = [(int(u), int(v), F32(c)) for u, v, c in zip(*edges)]
+    value = [None] * V
+    for s in sources:
+        value[s] = F32(0.0)
     changed = True
     while changed:
         changed = False
         for u, v, c in edges:
-            if cost[u] is not None and (cost[v] is None or F32(cost[u] + c) < cost[v]):
-                cost[v] = F32(cost[u] + c)
+            if value[u] is not None and (value[v] is None or fold(value[u], c) < value[v]):
+                value[v] = fold(value[u], c)
                 changed = True
-    tight = [(u, v) for u, v, c in edges if cost[u] is not None and F32(cost[u] + c) == cost[v]]
+    tight = [(u, v) for u, v, c in edges if value[u] is not None and fold(value[u], c) == value[v]]
     hops = [-1] * V
-    hops[src] = 0
-    level = [src]
+    for s in sources:
+        hops[s] = 0
+    level = sources
     while level:
         nxt = sorted({v for u, v in tight if u in level and hops[v] < 0})
         for v in nxt:
@@ -76,7 +86,13 @@ def py_field(V, rowptr, col, w, dist, state, sf, src):
         level = nxt
     parent = [-1] * V
     for u, v in tight:
-        if v != src and hops[u] + 1 == hops[v] and (parent[v] < 0 or u < parent[v]):
+        if hops[v] > 0 and hops[u] + 1 == hops[v] and (parent[v] < 0 or u < parent[v]):
             parent[v] = u
-    cost = np.array([np.inf if c is None else c for c in cost], np.float32)
-    return cost, np.array(hops, np.int32), np.array(parent, np.int32)
+    value = np.array([np.inf if c is None else c for c in value], np.float32)
+    return value, np.array(hops, np.int32), np.array(parent, np.int32)
+
+
+def py_field(V, rowptr, col, w, dist, state, sf, src):
+    """definition_field for the cost objective: cost = the least fp32 left fold fl(a + c) of c = (sf * w + 1) * dist."""
+    g = SimpleNamespace(rowptr=rowptr, col=col, state=state)
+    return definition_field(V, edge_list(g, cost_values(w, dist, sf)), lambda a, c: F32(a + c), [src])

@@ -9,10 +9,9 @@ import numpy as np
 
 import route_ref
 import set_ref
+from field_keys import F32, INVALID, relaxable
 
-F32 = np.float32
 INF = F32(np.inf)
-INVALID = -1
 
 # the pruned CSR; kept: for every edge of it the CSR index it has in the graph it was pruned from
 Pruned = namedtuple("Pruned", "rowptr col w dist state kept")
@@ -60,11 +59,7 @@ def model_route(g, model, f, members, t, engine_sf=3.0, costs=None):
 
 def distinct_weights(g):
     """The distinct weights of g's edges into valid nodes, ascending (float32)."""
-    col = np.asarray(g.col)
-    V = len(g.state)
-    ok = (col >= 0) & (col < V)
-    ok[ok] = np.asarray(g.state)[col[ok]] != INVALID
-    return np.unique(np.asarray(g.w, F32)[ok])
+    return np.unique(np.asarray(g.w, F32)[relaxable(g.col, g.state)])
 
 
 def reachable_under(g, tau, start, goal):

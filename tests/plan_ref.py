@@ -2,13 +2,12 @@
 and called through ctypes, and the fp32 cost of a route restated in numpy.  Test code only; the product never
 links it."""
 import ctypes as C
-import os
-import subprocess
 from collections import namedtuple
 
 import numpy as np
 
-SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp", "plan_reference.cpp")
+import field_ref
+
 F32 = np.float32
 OK = 0
 NOT_FOUND = 6  # TRG_ERR_NOT_FOUND
@@ -18,11 +17,8 @@ Plan = namedtuple("Plan", "status ids direct_dist path_length avg_risk num_point
 
 
 def compile_reference(out_dir):
-    """-> ctypes library (built into out_dir), with the flags of field_ref.compile_reference."""
-    so = os.path.join(str(out_dir), "libplan_reference.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
-                           SRC, "-o", so])
-    lib = C.CDLL(so)
+    """-> ctypes library (built into out_dir)."""
+    lib = field_ref.compile_cpp(out_dir, "plan_reference")
     ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
     lib.plan_reference.argtypes = [C.c_int, ip, ip, fp, fp, ip, fp, C.c_float, C.c_int, C.c_int, C.c_int, ip,
                                    C.c_int32, fp, ip]

@@ -14,9 +14,7 @@ from collections import namedtuple
 import numpy as np
 
 import bound_ref
-
-F32 = np.float32
-INVALID = -1
+from field_keys import F32, INVALID, cost_values, relaxable  # noqa: F401
 
 # cost float32, hops / parent / owner int32 over the nodes; owned int32 over the set's entries
 SetField = namedtuple("SetField", "cost hops parent owner owned")
@@ -24,15 +22,21 @@ SetField = namedtuple("SetField", "cost hops parent owner owned")
 
 def _edges(g, sf):
     """(source node, cost in fp32, relaxable) per CSR edge."""
-    col = np.asarray(g.col)
-    V = len(g.state)
-    with np.errstate(over="ignore", invalid="ignore"):
-        ec = ((F32(sf) * np.asarray(g.w, F32) + F32(1.0)) * np.asarray(g.dist, F32)).astype(F32)
-    eu = np.repeat(np.arange(V), np.diff(np.asarray(g.rowptr)))
-    inside = (col >= 0) & (col < V)
-    ok = inside.copy()
-    ok[inside] = np.asarray(g.state)[col[inside]] != INVALID
-    return eu, ec, ok
+    eu = np.repeat(np.arange(len(g.state)), np.diff(np.asarray(g.rowptr)))
+    return eu, cost_values(g.w, g.dist, sf), relaxable(g.col, g.state)
+
+
+def owners_of(members, hops, parent):
+    """The owner rule, for either objective: a member's owner is the least index into `members` that names it, any
+    other reached node's is its parent's (taken along the parents in the order of the depths), an unreached node's
+    -1."""
+    owner = np.full(len(hops), -1, np.int32)
+    for j in range(len(members) - 1, -1, -1):
+        owner[members[j]] = j
+    for v in np.argsort(hops, kind="stable").tolist():
+        if hops[v] > 0:
+            owner[v] = owner[parent[v]]
+    return owner
 
 
 def set_field(g, sf, members):
@@ -94,12 +98,7 @@ def set_field(g, sf, members):
     np.minimum.at(parent, col[cand], eu[cand])
     parent[parent == V] = -1
     parent = parent.astype(np.int32)
-    owner = np.full(V, -1, np.int32)
-    for j in range(len(members) - 1, -1, -1):
-        owner[members[j]] = j
-    for v in np.argsort(hops, kind="stable").tolist():
-        if hops[v] > 0:
-            owner[v] = owner[parent[v]]
+    owner = owners_of(members, hops, parent)
     assert np.all((owner >= 0) == reached)
     return SetField(cost, hops, parent, owner, count_owned(owner, len(members)))
 

@@ -7,8 +7,8 @@ from types import SimpleNamespace
 
 import numpy as np
 
-F32 = np.float32
-INVALID = -1
+from field_keys import F32, INVALID, cost_values  # noqa: F401
+
 NONE = None  # no key
 
 
@@ -40,7 +40,7 @@ def solve_graph(G, lo, hi):
 
 
 def _edge_costs(S, sf):
-    return (F32(sf) * S.w + F32(1.0)) * S.dist
+    return cost_values(S.w, S.dist, sf)
 
 
 def _relax(S, ec, key, tight, queue):

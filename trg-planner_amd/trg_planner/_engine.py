@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from collections import namedtuple
 
 import numpy as np
 
@@ -280,6 +281,51 @@ def choose_frontier(ids, cost, hops):
     return int(ids[j]), j
 
 
+def pack_sets(who, sets, start_costs=None, who_starts=None):
+    """Source sets as the set entries take them -> (the m int32 arrays, ptr int32 (m + 1), the concatenated int32 ids,
+    the m float32 start-cost arrays or None, their concatenation or None).  The ValueErrors name the caller, `who`
+    (`who_starts` for the start costs' shape, where another call answers for them)."""
+    sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
+    m = len(sets)
+    starts, c0 = None, None
+    if start_costs is not None:
+        starts = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in start_costs]
+        if len(starts) != m or any(c.shape != s.shape for c, s in zip(starts, sets)):
+            raise ValueError(f"{who_starts or who}: start_costs and sets differ in shape")
+        c0 = np.ascontiguousarray(np.concatenate(starts) if m else np.empty(0, np.float32), dtype=np.float32)
+    ptr = np.zeros(m + 1, np.int64)
+    np.cumsum([s.shape[0] for s in sets], out=ptr[1:])
+    if ptr[-1] > 2**31 - 1:
+        raise ValueError(f"{who}: {int(ptr[-1])} source entries do not fit 32 bits")
+    ids = np.ascontiguousarray(np.concatenate(sets) if m else np.empty(0, np.int32), dtype=np.int32)
+    return sets, ptr.astype(np.int32), ids, starts, c0
+
+
+def _owned_buffer(ptr):
+    """A set solve's `owned` over pack_sets' `ptr` -> (the buffer the entry fills, a call that splits it per set)."""
+    owned = np.zeros(max(int(ptr[-1]), 1), np.int32)
+    return owned, lambda: [owned[ptr[k]:ptr[k + 1]].copy() for k in range(ptr.shape[0] - 1)]
+
+
+def _as_risk(out):
+    """A result dict under the risk fields' names: "risk" / "risk_at" for "cost" / "cost_at"."""
+    for old, new in (("cost", "risk"), ("cost_at", "risk_at")):
+        if old in out:
+            out[new] = out.pop(old)
+    return out
+
+
+def _check_settle(who, settle):
+    if settle not in _SETTLE:
+        raise ValueError(f"{who}: settle {settle!r} (\"any\", \"all\" or None)")
+
+
+# The solve the engine retains, as Engine._retain records it: risk -- the objective; fields -- m; sets -- solved through
+# a set entry; owners -- a refresh returns "owner" / "owner_at"; single -- one field from a set of one (frontier_ceilings'
+# `reuse`); source -- of the last cost_field, for field_path (kept across other solves: the caller holds its parents).
+Retained = namedtuple("Retained", "risk fields sets owners single source", defaults=(False, 1, False, False, False, -1))
+
+
 class CsrGraph:
     """Host copy of a TrgCsrView."""
 
@@ -316,6 +362,7 @@ class Engine:
             raise TrgError(st, msg)
         self.sampler = TrgSampler(1, 16)
         self.last_reuse = None  # frontier_ceilings(reuse=True): the refresh's dict when it was taken
+        self._retained = Retained()  # (nothing solved through this object yet: one field, no sets, source -1)
 
     def close(self):
         if getattr(self, "h", None):
@@ -432,20 +479,8 @@ class Engine:
         (TrgTiledSetInfo), "sets" and "start_costs" (the arrays as solved, None without start costs).  An owner is the
         index into sets[k] of the member a node's route starts from, -1 where unreached.  tiled.concat_fields joins
         the ranks' results."""
-        sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
+        sets, ptr, ids, starts, c0 = pack_sets("tiled_cost_fields_from", sets, start_costs)
         m = len(sets)
-        starts, c0 = None, None
-        if start_costs is not None:
-            starts = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in start_costs]
-            if len(starts) != m or any(c.shape != s.shape for c, s in zip(starts, sets)):
-                raise ValueError("tiled_cost_fields_from: start_costs and sets differ in shape")
-            c0 = np.ascontiguousarray(np.concatenate(starts) if m else np.empty(0, np.float32), dtype=np.float32)
-        ptr = np.zeros(m + 1, np.int64)
-        np.cumsum([s.shape[0] for s in sets], out=ptr[1:])
-        if ptr[-1] > 2**31 - 1:
-            raise ValueError(f"tiled_cost_fields_from: {int(ptr[-1])} source entries do not fit 32 bits")
-        ptr = ptr.astype(np.int32)
-        ids = np.ascontiguousarray(np.concatenate(sets) if m else np.empty(0, np.int32), dtype=np.int32)
         try:
             offset, V = self.global_ids()
         except TrgError:
@@ -461,14 +496,14 @@ class Engine:
             n_t = int(tg.shape[0])
             out.update(cost_at=np.empty((rows, n_t), np.float32), hops_at=np.empty((rows, n_t), np.int32),
                        owner_at=np.empty((rows, n_t), np.int32))
-        owned = np.zeros(max(int(ptr[-1]), 1), np.int32)
+        owned, split_owned = _owned_buffer(ptr)
         info = TrgTiledSetInfo()
         arr = lambda name, conv: None if out.get(name) is None else conv(out[name])  # noqa: E731
         self._chk(self.L.trg_engine_tiled_cost_field_sets(
             self.h, m, _i(ptr), _i(ids), None if c0 is None else _f(c0), arr("cost", _f), arr("hops", _i),
             arr("parent", _i), arr("owner", _i), None if tg is None or n_t == 0 else _i(tg), n_t, arr("cost_at", _f),
             arr("hops_at", _i), arr("owner_at", _i), _i(owned), C.byref(info)))
-        out["owned"] = [owned[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
+        out["owned"] = split_owned()
         out["info"] = info
         return out
 
@@ -650,15 +685,14 @@ class Engine:
         info = TrgFieldInfo()
         self._chk(self.L.trg_engine_cost_field(self.h, int(source_id), None if xy is None else _f(xy), _f(cost),
                                                _i(hops), _i(parent), C.byref(info)))
-        self._field_source = int(info.source)
-        self._field_shape = (1, False)
+        self._retain(risk=False, fields=1, source=int(info.source))
         return cost, hops, parent, info
 
     def field_path(self, parent, node, source=None):
         """Node ids from the field's source to `node` along `parent` (of cost_field; `source` defaults to the
         source of this engine's last cost_field).  Raises ValueError if `node` is unreachable."""
         if source is None:
-            source = getattr(self, "_field_source", -1)
+            source = self._retained.source
         node = int(node)
         path = [node]
         while path[-1] != source:
@@ -697,8 +731,7 @@ class Engine:
         groups for them, ready to splat, None where an array is not there -> (dict, groups): "full" (cost, hops,
         parent), "at" (targets, n_t, cost_at, hops_at), and the single arguments "owner", "owner_at", "reached",
         "budget" (broadcast to m float32) and "bound"."""
-        if settle not in _SETTLE:
-            raise ValueError(f"{who}: settle {settle!r} (\"any\", \"all\" or None)")
+        _check_settle(who, settle)
         V, _ = self.graph_sizes("global")
         out = {}
         if full:
@@ -726,6 +759,30 @@ class Engine:
                   "owner": arg("owner"), "owner_at": arg("owner_at"), "reached": arg("reached"),
                   "budget": None if bud is None else _f(bud), "bound": arg("bound", _f)}
         return out, groups
+
+    def _retain(self, risk, fields, **more):
+        """The record of the retained solve: every solve calls this once its C call has succeeded."""
+        self._retained = Retained(risk, fields, source=self._retained.source)._replace(**more)
+
+    def _sources(self, who, sources_xy, source_ids, settle=None):
+        """The sources of cost_fields / risk_fields (`who`) checked -> (m, ids int32 or None, xy (m, 2) float32 or
+        None).  settle: cost_fields' own, which it has always checked between the two checks made here."""
+        if sources_xy is None and source_ids is None:
+            raise ValueError(f"{who} needs sources_xy or source_ids")
+        _check_settle(who, settle)
+        ids = None if source_ids is None else np.ascontiguousarray(source_ids, dtype=np.int32).reshape(-1)
+        xy = None if sources_xy is None else np.ascontiguousarray(sources_xy, dtype=np.float32).reshape(-1, 2)
+        m = ids.shape[0] if ids is not None else xy.shape[0]
+        if ids is not None and xy is not None and xy.shape[0] != m:
+            raise ValueError(f"{who}: sources_xy and source_ids differ in length")
+        return m, ids, xy
+
+    def _resolve(self, m, ids, xy, nodes):
+        """The batch entry's resolve-only call (no solve, see the header): source k's node into nodes[k]."""
+        self._chk(self.L.trg_engine_cost_field_batch(self.h, m, None if ids is None else _i(ids),
+                                                     None if xy is None else _f(xy), None, None, None, None, 0,
+                                                     None, None, _i(nodes), None, None))
+        return nodes
 
     def _models(self, who, models, m):
         """`models` of cost_fields / cost_fields_from as the C entry's array: m entries, each None (the engine's
@@ -764,40 +821,26 @@ class Engine:
         None (the engine's model), a safety factor, or (safety_factor, max_risk) -- field k prices an edge with its
         own safety factor and uses no edge of weight above max_risk.  The sources are resolved first (no solve), then
         every field runs as a set of one; the result also has "models", the (m, 2) float32 pairs as solved."""
-        if sources_xy is None and source_ids is None:
-            raise ValueError("cost_fields needs sources_xy or source_ids")
-        ids = None if source_ids is None else np.ascontiguousarray(source_ids, dtype=np.int32).reshape(-1)
-        xy = None if sources_xy is None else np.ascontiguousarray(sources_xy, dtype=np.float32).reshape(-1, 2)
-        m = ids.shape[0] if ids is not None else xy.shape[0]
+        m, ids, xy = self._sources("cost_fields", sources_xy, source_ids, settle)
         out, a = self._field_outputs("cost_fields", m, targets, full, budget, settle)
-        if ids is not None and xy is not None and xy.shape[0] != m:
-            raise ValueError("cost_fields: sources_xy and source_ids differ in length")
-        info = TrgFieldInfo()
-        if models is not None:
-            marr, out["models"] = self._models("cost_fields", models, m)
-            nodes = np.full(m, -1, np.int32)
-            self._chk(self.L.trg_engine_cost_field_batch(self.h, m, None if ids is None else _i(ids),
-                                                         None if xy is None else _f(xy), None, None, None, None, 0,
-                                                         None, None, _i(nodes), None, None))
-            ptr = np.arange(m + 1, dtype=np.int32)
-            self._chk(self.L.trg_engine_cost_field_models(
-                self.h, m, marr, _i(ptr), _i(nodes), a["budget"], _SETTLE[settle], *a["full"], None, *a["at"], None,
-                None, a["reached"], a["bound"], C.byref(info)))
-            self._field_shape = (m, False)
-            out["sources"] = nodes
-            out["info"] = info
-            return out
         out["sources"] = np.full(m, -1, np.int32)
+        out["info"] = info = TrgFieldInfo()
         # the bounded entry's arguments; the batch entry's are these without budget, settle and bound_out
         sources = [self.h, m, None if ids is None else _i(ids), None if xy is None else _f(xy)]
         outputs = [*a["full"], *a["at"], _i(out["sources"]), a["reached"]]
-        if "bound" in out:
+        if models is not None:
+            marr, out["models"] = self._models("cost_fields", models, m)
+            self._resolve(m, ids, xy, out["sources"])
+            ptr = np.arange(m + 1, dtype=np.int32)
+            self._chk(self.L.trg_engine_cost_field_models(
+                self.h, m, marr, _i(ptr), _i(out["sources"]), a["budget"], _SETTLE[settle], *a["full"], None, *a["at"],
+                None, None, a["reached"], a["bound"], C.byref(info)))
+        elif "bound" in out:
             self._chk(self.L.trg_engine_cost_field_bounded(*sources, a["budget"], _SETTLE[settle], *outputs, a["bound"],
                                                            C.byref(info)))
         else:
             self._chk(self.L.trg_engine_cost_field_batch(*sources, *outputs, C.byref(info)))
-        self._field_shape = (m, False)
-        out["info"] = info
+        self._retain(risk=False, fields=m)
         return out
 
     def refresh_fields(self, new2old=None, targets=None, full=True):
@@ -811,18 +854,20 @@ class Engine:
         old key could be kept as a starting point), and for a retained set solve "owner" / "owner_at".  Afterwards
         routes and field_reached answer from the refreshed solve.  A retained risk solve is refused:
         refresh_risk_fields is its call."""
-        # (fields, from sets) of the retained solve, which only this object's solves can have left; without one the
-        # call refuses before it writes anything
-        m, sets = getattr(self, "_field_shape", (1, False))
+        return self._refresh(self.L.trg_engine_cost_field_refresh, "refresh_fields", new2old, targets, full)
+
+    def _refresh(self, entry, who, new2old, targets, full):
+        """refresh_fields / refresh_risk_fields (`who`) through their C `entry`, the outputs sized from the record of
+        the retained solve; without one, or for one of the other objective, the call refuses before it writes."""
+        m, owners = self._retained.fields, self._retained.owners
         n2o = None if new2old is None else np.ascontiguousarray(new2old, dtype=np.int32).reshape(-1)
-        out, a = self._field_outputs("refresh_fields", m, targets, full, None, None, owners=sets)
+        out, a = self._field_outputs(who, m, targets, full, None, None, owners=owners)
         out["sources"] = np.full(m, -1, np.int32)
         out["carried"] = np.zeros(m, np.int32)
-        info = TrgFieldInfo()
-        self._chk(self.L.trg_engine_cost_field_refresh(
-            self.h, None if n2o is None else _i(n2o), 0 if n2o is None else n2o.shape[0], *a["full"], *a["at"],
-            a["owner"], a["owner_at"], _i(out["sources"]), a["reached"], _i(out["carried"]), C.byref(info)))
-        out["info"] = info
+        out["info"] = info = TrgFieldInfo()
+        self._chk(entry(self.h, None if n2o is None else _i(n2o), 0 if n2o is None else n2o.shape[0], *a["full"],
+                        *a["at"], a["owner"], a["owner_at"], _i(out["sources"]), a["reached"], _i(out["carried"]),
+                        C.byref(info)))
         return out
 
     def field_reached(self, field=0, cap=None, with_info=False):
@@ -861,11 +906,8 @@ class Engine:
         xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
         nodes = np.empty(xy.shape[0], np.int32)
         for k0 in range(0, xy.shape[0], TRG_FIELD_BATCH_MAX):
-            part = np.ascontiguousarray(xy[k0:k0 + TRG_FIELD_BATCH_MAX])
-            got = np.empty(part.shape[0], np.int32)
-            self._chk(self.L.trg_engine_cost_field_batch(self.h, part.shape[0], None, _f(part), None, None, None,
-                                                         None, 0, None, None, _i(got), None, None))
-            nodes[k0:k0 + TRG_FIELD_BATCH_MAX] = got
+            part = xy[k0:k0 + TRG_FIELD_BATCH_MAX]  # (rows of a contiguous array: contiguous themselves)
+            self._resolve(part.shape[0], None, part, nodes[k0:k0 + TRG_FIELD_BATCH_MAX])
         return nodes
 
     def cost_fields_from(self, sets, targets=None, full=True, budget=None, settle=None):
@@ -893,23 +935,11 @@ class Engine:
         return self._cost_fields_from(sets, models, targets, full, budget, settle, start_costs=start_costs)
 
     def _cost_fields_from(self, sets, models, targets, full, budget, settle, start_costs=None):
-        sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
+        sets, ptr, ids, starts, c0 = pack_sets("cost_fields_from", sets, start_costs, who_starts="cost_fields_seeded")
         m = len(sets)
-        c0 = None
-        if start_costs is not None:
-            starts = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in start_costs]
-            if len(starts) != m or any(c.shape != s.shape for c, s in zip(starts, sets)):
-                raise ValueError("cost_fields_seeded: start_costs and sets differ in shape")
-            c0 = np.ascontiguousarray(np.concatenate(starts) if m else np.empty(0, np.float32), dtype=np.float32)
         marr, pairs = (None, None) if models is None else self._models("cost_fields_from_models", models, m)
         out, a = self._field_outputs("cost_fields_from", m, targets, full, budget, settle, owners=True)
-        ptr = np.zeros(m + 1, np.int64)
-        np.cumsum([s.shape[0] for s in sets], out=ptr[1:])
-        if ptr[-1] > 2**31 - 1:
-            raise ValueError(f"cost_fields_from: {int(ptr[-1])} source entries do not fit 32 bits")
-        ptr = ptr.astype(np.int32)
-        ids = np.ascontiguousarray(np.concatenate(sets) if m else np.empty(0, np.int32), dtype=np.int32)
-        owned = np.zeros(max(int(ptr[-1]), 1), np.int32)
+        owned, split_owned = _owned_buffer(ptr)
         info = TrgFieldInfo()
         tail = [_i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
                 _i(owned), a["reached"], a["bound"], C.byref(info)]
@@ -923,8 +953,8 @@ class Engine:
         else:
             self._chk(self.L.trg_engine_cost_field_models(self.h, m, marr, *tail))
             out["models"] = pairs
-        self._field_shape = (m, True)
-        out["owned"] = [owned[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
+        self._retain(risk=False, fields=m, sets=True, owners=True)
+        out["owned"] = split_owned()
         out["sets"] = sets
         out["sources"] = np.array([s[0] for s in sets], np.int32)
         out["info"] = info
@@ -1137,17 +1167,8 @@ class Engine:
         has "bound".  The solve is retained: routes and field_reached answer from it (a route's cost is its target's
         risk); after update_graph calls refresh_risk_fields brings it to the current graph (refresh_fields, the cost
         fields' call, refuses it)."""
-        if sources_xy is None and source_ids is None:
-            raise ValueError("risk_fields needs sources_xy or source_ids")
-        ids = None if source_ids is None else np.ascontiguousarray(source_ids, dtype=np.int32).reshape(-1)
-        xy = None if sources_xy is None else np.ascontiguousarray(sources_xy, dtype=np.float32).reshape(-1, 2)
-        m = ids.shape[0] if ids is not None else xy.shape[0]
-        if ids is not None and xy is not None and xy.shape[0] != m:
-            raise ValueError("risk_fields: sources_xy and source_ids differ in length")
-        nodes = np.full(max(m, 1), -1, np.int32)
-        self._chk(self.L.trg_engine_cost_field_batch(self.h, m, None if ids is None else _i(ids),
-                                                     None if xy is None else _f(xy), None, None, None, None, 0,
-                                                     None, None, _i(nodes), None, None))
+        m, ids, xy = self._sources("risk_fields", sources_xy, source_ids)
+        nodes = self._resolve(m, ids, xy, np.full(max(m, 1), -1, np.int32))
         # (a set of one owns all it reaches: no owner pass)
         return self._risk_fields_from("risk_fields", [nodes[k:k + 1] for k in range(m)], targets, full, budget, settle,
                                       owners=False)
@@ -1159,29 +1180,18 @@ class Engine:
         return self._risk_fields_from("risk_fields_from", sets, targets, full, budget, settle, owners=True)
 
     def _risk_fields_from(self, who, sets, targets, full, budget, settle, owners):
-        sets = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in sets]
+        sets, ptr, ids, _, _ = pack_sets(who, sets)
         m = len(sets)
         out, a = self._field_outputs(who, m, targets, full, budget, settle, owners=owners)
-        ptr = np.zeros(m + 1, np.int64)
-        np.cumsum([s.shape[0] for s in sets], out=ptr[1:])
-        if ptr[-1] > 2**31 - 1:
-            raise ValueError(f"{who}: {int(ptr[-1])} source entries do not fit 32 bits")
-        ptr = ptr.astype(np.int32)
-        ids = np.ascontiguousarray(np.concatenate(sets) if m else np.empty(0, np.int32), dtype=np.int32)
-        owned = np.zeros(max(int(ptr[-1]), 1), np.int32)
+        owned, split_owned = _owned_buffer(ptr)
         info = TrgFieldInfo()
         self._chk(self.L.trg_engine_risk_field_sets(
             self.h, m, _i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
             _i(owned) if owners else None, a["reached"], a["bound"], C.byref(info)))
-        self._field_shape = (m, True)
-        # what refresh_risk_fields has to know of this solve: its fields, whether it came from risk_fields_from (the
-        # owners are then part of the result), and whether it is one field from a set of one (what `reuse` asks for)
-        self._risk_shape = (m, owners, m == 1 and sets[0].shape[0] == 1)
-        for old, new in (("cost", "risk"), ("cost_at", "risk_at")):
-            if old in out:
-                out[new] = out.pop(old)
+        self._retain(risk=True, fields=m, sets=True, owners=owners, single=m == 1 and sets[0].shape[0] == 1)
+        _as_risk(out)
         if owners:
-            out["owned"] = [owned[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
+            out["owned"] = split_owned()
             out["sets"] = sets
         out["sources"] = np.array([s[0] for s in sets], np.int32)
         out["info"] = info
@@ -1218,26 +1228,14 @@ class Engine:
         as are a bounded risk solve and one that is already current; a refused call leaves the retained solve answering.
         A NaN, negative or infinite weight on the current graph raises as in risk_fields, and nothing is retained
         afterwards.  Afterwards routes and field_reached answer from the refreshed solve."""
-        m, owners, _ = getattr(self, "_risk_shape", (1, False, False))
-        n2o = None if new2old is None else np.ascontiguousarray(new2old, dtype=np.int32).reshape(-1)
-        out, a = self._field_outputs("refresh_risk_fields", m, targets, full, None, None, owners=owners)
-        out["sources"] = np.full(m, -1, np.int32)
-        out["carried"] = np.zeros(m, np.int32)
-        info = TrgFieldInfo()
-        self._chk(self.L.trg_engine_risk_field_refresh(
-            self.h, None if n2o is None else _i(n2o), 0 if n2o is None else n2o.shape[0], *a["full"], *a["at"],
-            a["owner"], a["owner_at"], _i(out["sources"]), a["reached"], _i(out["carried"]), C.byref(info)))
-        for old, new in (("cost", "risk"), ("cost_at", "risk_at")):
-            if old in out:
-                out[new] = out.pop(old)
-        out["info"] = info
-        return out
+        return _as_risk(self._refresh(self.L.trg_engine_risk_field_refresh, "refresh_risk_fields", new2old, targets,
+                                      full))
 
     def _risk_field_reused(self, node, frontier):
         """frontier_ceilings' `reuse`: the retained risk solve refreshed and read at `frontier`, if it is one field from
         the one node `node` (an id of the current graph) -> refresh_risk_fields' dict, or None: solve afresh.  Whatever
         the refresh refuses (nothing retained, a cost solve, a bounded one, already current, no map) ends here too."""
-        if not getattr(self, "_risk_shape", (1, False, False))[2]:
+        if not (self._retained.risk and self._retained.single):
             return None
         try:
             r = self.refresh_risk_fields(targets=frontier, full=False)
