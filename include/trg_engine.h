@@ -325,7 +325,9 @@ TrgStatus trg_engine_voxel_filter(TrgEngine *e, const float *xyz, size_t n, size
  * default only the repeat of a launch whose bounded wait ran out), "debug_stitch_cap" = n (first capacity, in rows,
  * of trg_engine_stitch_exchange's record and edge buffers, so that small tilings reach its regrow loops; 0: the
  * default).  "comm_wait_seconds" = x > 0 (default 20): the longest an engine of an in-process group
- * (trg_engine_comm_join_local) waits for the other ranks -- a cap, the exchanges take milliseconds. */
+ * (trg_engine_comm_join_local) waits for the other ranks -- a cap, the exchanges take milliseconds.
+ * "safety_factor" = x: TrgParams.safety_factor from the next call on -- plans and cost fields price an edge with it, a
+ * retained tiled cost solve becomes stale; risk fields do not know it. */
 TrgStatus trg_engine_set_option(TrgEngine *e, const char *key, const char *value);
 /* Tiled builds (multi-GPU; an extension, not a reference interface): restrict
  * node creation to the core region [x0,x1) x [y0,y1) -- a sample outside it counts as a rejected
@@ -714,8 +716,8 @@ TrgStatus trg_engine_risk_field_refresh(TrgEngine *e,
  * (TRG_ERR_CAPACITY), a queue overflow (TRG_ERR_DEVICE) -- is announced in the next count exchange: that rank returns
  * its error, every other rank TRG_ERR_DEVICE "another rank reported a failure", none waits.  TRG_ERR_DEVICE on every
  * rank at once when the exchanges do not converge.  Source sets and start costs are the call below, routes
- * trg_engine_tiled_field_routes; bounds, cost models, risk fields and refresh are not offered across tiles, and none
- * of these calls touches the retained single-engine solve. */
+ * trg_engine_tiled_field_routes, risk fields trg_engine_tiled_risk_field; bounds, cost models and refresh are not
+ * offered across tiles, and none of these calls touches the retained single-engine solve. */
 typedef struct TrgTiledFieldInfo {
   int32_t exchanges;     /* all-gather-v exchanges of both passes, the two that found no news included */
   int32_t rounds;        /* relaxation rounds of this rank that did work */
@@ -758,8 +760,9 @@ TrgStatus trg_engine_tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *so
  * (TRG_ERR_INVALID_ARG), an allocation (TRG_ERR_CAPACITY), a bad edge cost, a queue overflow -- is announced in the
  * next count exchange, of the owner exchanges as well: that rank returns its error, its peers TRG_ERR_DEVICE "another
  * rank reported a failure", nobody waits.  An owner loop that outlasts m x (border nodes of all ranks) + 2 exchanges
- * ends with TRG_ERR_DEVICE on every rank at once.  Routes are trg_engine_tiled_field_routes; bounds, cost models, risk
- * fields and refresh are not offered across tiles; the retained single-engine solve is left alone. */
+ * ends with TRG_ERR_DEVICE on every rank at once.  Routes are trg_engine_tiled_field_routes, risk fields from sets
+ * trg_engine_tiled_risk_field_sets; bounds, cost models and refresh are not offered across tiles; the retained
+ * single-engine solve is left alone. */
 typedef struct TrgTiledSetInfo {
   int32_t exchanges;           /* all-gather-v exchanges of passes 1 and 2, the two without news included */
   int32_t owner_exchanges;     /* ... of the owner pass, the one without news included */
@@ -778,16 +781,48 @@ TrgStatus trg_engine_tiled_cost_field_sets(TrgEngine *e, int32_t m,
     const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
     int32_t *owned,                                                /* set_ptr[m], may be NULL */
     TrgTiledSetInfo *info);                                        /* may be NULL */
+/* Risk fields across tiles ("Risk fields across tiles"): the least, over all walks of the global
+ * stitched graph G, of the GREATEST edge weight on the walk -- exactly what trg_engine_risk_field_sets defines, on G.
+ * An edge's risk is w + 0.0f (-0 counts as +0), a walk never enters an Invalid node, and risk, hops and parents equal a
+ * host Dijkstra on the key (risk, hops) with the extension (max(risk, r), hops + 1), bit for bit: the maximum never
+ * rounds.  Collective calls like the two above, with the same exchanges, caps and outputs; `risk` stands where `cost`
+ * stood.  Risk solves take no start values: every member of a set is seeded at (+0, 0), so every member is a root, whose
+ * owner is the least entry of its set naming it; every other reached node takes owner[parent].  Parents are GLOBAL ids,
+ * the least global id among the tight predecessors one level up, -1 for members and unreached nodes.  The
+ * single-source call is m sets of one, bit for bit, with the same exchanges, rounds and records.  targets (LOCAL ids),
+ * risk_at / hops_at / owner_at and owned are trg_engine_tiled_cost_field_sets'.
+ * The solve graph's edge risks are computed by the first risk solve after a stitch and kept beside its edge costs: a
+ * change of the safety factor leaves them and the answers as they are, and cost and risk solves may alternate on one
+ * stitch.
+ * TRG_ERR_INVALID_ARG before any collective, the group still usable: the refusals of the cost calls without those of
+ * the start costs.  A rank's own failure, announced in the next count exchange like every other (that rank returns its
+ * error, its peers TRG_ERR_DEVICE "another rank reported a failure", nobody waits): those of the cost calls, and in
+ * the place of the bad edge cost "tiled risk field: an edge weight is negative or not finite" (TRG_ERR_INVALID_ARG),
+ * taken over ALL edges of that rank's solve graph, relaxable or not, as in the single-engine call.
+ * Routes are trg_engine_tiled_field_routes; risk ceilings (budget / settle), cost models and refresh are not offered
+ * across tiles. */
+TrgStatus trg_engine_tiled_risk_field(TrgEngine *e, int32_t m, const int32_t *source_gids,
+    float *risk, int32_t *hops, int32_t *parent,   /* m x (this tile's nodes), any may be NULL */
+    TrgTiledFieldInfo *info);                      /* may be NULL */
+TrgStatus trg_engine_tiled_risk_field_sets(TrgEngine *e, int32_t m,
+    const int32_t *set_ptr, const int32_t *set_gids,
+    float *risk, int32_t *hops, int32_t *parent, int32_t *owner,   /* m x (this tile's nodes), any may be NULL */
+    const int32_t *targets, int32_t n_targets, float *risk_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned,                                                /* set_ptr[m], may be NULL */
+    TrgTiledSetInfo *info);                                        /* may be NULL */
 /* Routes across tiles ("Routes across tiles"): the paths behind the keys of the LAST tiled solve
- * (either call above), walked on the devices.  A successful tiled solve stays on every rank's device; a new tiled solve
+ * (any of the four calls above, whichever objective), walked on the devices.  A successful tiled solve stays on every rank's device; a new tiled solve
  * replaces it from its start (one that fails leaves none), and a change of the tile's graph, a new stitch or another
- * safety factor makes it stale.  A collective call: every rank makes it with the same arguments.
+ * safety factor makes it stale (a risk solve does not know the safety factor and outlives its change).  A collective
+ * call: every rank makes it with the same arguments.
  * Route r is field route_field[r] (0 .. m-1 of that solve) to the node with GLOBAL id route_target_gid[r], any rank's
  * node.  It is exactly what trg_engine_field_routes defines, on the global stitched graph G with the solve's global
  * parents: the hops + 1 nodes from the root to the target; the route edge into p_i is the tight, relaxable edge of least
  * CSR index in row p_{i-1} of G; path_length and the risk sum are fp32 left folds from the target end backwards, avg_risk
  * the risk sum / num_nodes in fp32, cost the key's cost word (a start cost included); an unreached target has the empty
- * route.  The rank that owns a node walks the route while it stands on its nodes and hands it, with the sums so far, to
+ * route.  After a risk solve the routes are trg_engine_field_routes' after a risk solve: tight is tight under the
+ * maximum -- max(risk[p_{i-1}], r) == risk[p_i] with the hops stepping by one -- and cost is risk[target]; the sums are the
+ * same folds of dist and w.  The rank that owns a node walks the route while it stands on its nodes and hands it, with the sums so far, to
  * the owner of the parent at a seam: the fold is one fold across any number of seams.
  * Every rank receives the same offsets and the same infos for ALL routes: offsets from the full lengths and cap, clipped
  * as trg_engine_field_routes clips them (the source end is kept, later routes are empty ranges, infos[r].num_nodes keeps

@@ -1246,6 +1246,9 @@ TrgStatus set_option(TrgEngine *e, const char *key, const char *value) {
       {"resolve_tickets", INT, &e->resolve_tickets},
       // measurement knob: cost-field bucket width in mean edge costs ("inf": Bellman-Ford)
       {"field_delta_scale", POSITIVE_DOUBLE, &e->field_delta_scale},
+      // the safety factor of the planner and of the cost fields from the next call on (every cache of edge costs is
+      // stamped with its bits; the risk fields do not know it)
+      {"safety_factor", FLOAT, &e->prm.safety_factor},
       {"debug_gate_margin", FLOAT, &e->gate_margin},
       {"debug_tie_every", INT, &e->debug_tie_every},
       {"debug_spec_bound", INT, &e->debug_spec_bound},

@@ -1,5 +1,7 @@
-// trg_engine_field_tiled.inc -- host side of the cost field across tiles (included by trg_engine.cpp after the
-// exchange; DESIGN.md section 7, "Cost fields across tiles"; kernels: trg_field_tiled.inc).  A collective call: every
+// trg_engine_field_tiled.inc -- host side of the cost field and the risk field across tiles (included by trg_engine.cpp
+// after the exchange; DESIGN.md section 7, "Cost fields across tiles" and "Risk fields across tiles"; kernels:
+// trg_field_tiled.inc).  What follows is said of the cost objective; a risk solve is the same run on the edge risks of
+// the solve graph, its keys extended by the maximum, which never rounds.  A collective call: every
 // rank of the engine's communicator relaxes the fields over its own rows of the stitched graph plus mirrors
 // ("ghosts") of the other ends of its cross edges, and the ranks trade the keys of their border nodes through
 // exchange_allgatherv until an exchange carries no news from anybody.  The least fp32 fold over all walks is one
@@ -18,16 +20,22 @@ namespace {
 constexpr int TILED_BATCH = 8;
 
 struct TiledFieldBufs {
-  // the solve graph, built once per stitch: stamped with the graph version, the stitch and the cost model
+  // the solve graph, built once per stitch: stamped with the graph version and the stitch
   uint64_t version = 0, serial = 0;
-  uint32_t sf_bits = 0;
   FieldTiled T{};
-  int E2 = 0;              // its edges
-  double mean_cost = 0.0;  // ... and the mean of their costs (the bucket width)
-  bool bad_cost = false;
+  int E2 = 0;  // its edges
+  // One value per edge of the solve graph and objective, each array stamped on its own.  The costs (`ec`) are of the
+  // safety factor as well; the risks (`er`; "Risk fields across tiles") are built by the first risk solve after a
+  // stitch and do not know the safety factor.  `mean` gives the bucket width, `bad` refuses the solve.
+  struct EdgeValues {
+    uint64_t version = 0, serial = 0;
+    uint32_t sf_bits = 0;
+    double mean = 0.0;
+    bool bad = false;
+  } costs, risks;
   DevArr up_rowptr, up_col, up_w, up_dist;  // the stitched rows, uploaded when an export had taken them off the device
   DevArr ghost_flag, ghost_off, border_flag, border_off, ghost_deg, ghost_row, ghost_fill, scan_tmp;
-  DevArr gid_of, state, border, rowptr, col, w, dist, ec, stats;
+  DevArr gid_of, state, border, rowptr, col, w, dist, ec, er, stats;
   // work arrays, per item (m x (V + G)), and per border item (m x B)
   DevArr key, q[2], far[2], stamp_near, stamp_far, parent, tight, ctrl;
   DevArr published, rec, n_rec, cost, hops, parent_out;
@@ -41,12 +49,15 @@ struct TiledFieldBufs {
   Pinned<int> h_n;  // [0] ghosts, records or a sweep's "moved" word, [1] border rows or roots, [2] a broken walk
   Event t0, t1;
   // What the last successful solve left in the work arrays, for the routes ("Routes across tiles").  It is of the
-  // graph, the stitch and the safety factor of the stamps above; any new solve clears it at its start.
+  // graph and the stitch of the stamps above and, a cost solve, of the safety factor it ran with; any new solve clears
+  // it at its start.
   struct Solved {
     bool valid = false;
     int m = 0;
     bool owners = false;   // the owner pass ran: `owner` holds m x (V + G) words
     bool parents = false;  // the parent sweep ran
+    bool risk = false;     // the objective: F.ec is the edge risks, the walk and a late parent sweep take their RISK form
+    uint32_t sf_bits = 0;  // (a cost solve)
     FieldDev F{};
   } solved;
   DevArr route_field, route_target, route_off, route_gids, route_info;
@@ -63,6 +74,9 @@ struct TiledRequest {
   // The set call: the owner pass runs, and what follows may be asked for.  Fixed by the entry that was called, so
   // every rank decides alike whether the owner pass, a collective, runs (tiled_solve).
   bool owners;
+  // The objective: the least worst-edge risk ("Risk fields across tiles") in the place of the least cost fold.  Fixed by
+  // the entry as well: the ranks' round kernels must extend alike.
+  bool risk;
   const char *what;         // the error prefix of the call
   const char *null_ids;     // the refusal of a null set_ptr or set_gids
   const char *source_noun;  // of an id out of range: "<noun> k", or with nullptr "entry j of set k (id)"
@@ -105,6 +119,9 @@ struct TiledLocal {
   }
 };
 
+// the error prefix of what both objectives share
+const char *tiled_what(bool risk) { return risk ? "tiled risk field: " : "tiled cost field: "; }
+
 TrgStatus tiled_grow(TrgEngine *e, DevArr &a, size_t bytes) {
   if (ensure_bytes(e, a, bytes + 16) == TRG_OK) return TRG_OK;
   (void)hipGetLastError();
@@ -120,34 +137,69 @@ TrgStatus tiled_lap(TrgEngine *e, TiledRun &run) {
   return TRG_OK;
 }
 
-// The solve graph of this rank for the current stitch (trg_field_tiled.inc), its edge costs included; built when the
-// graph, the stitch or the safety factor moved since the last one.  The stitched rows are read where they are: in
-// HBM while stitch_assemble's arrays are current, else from the host rows an export fetched.
-TrgStatus tiled_graph(TrgEngine *e, const ExchangeState &x) {
+// The values of the request's objective on the edges of the current solve graph: the costs when the graph or the safety
+// factor moved since they were computed, the risks when the graph did.  Every edge into a ghost is skipped; the
+// single-engine cache is neither read nor evicted.
+TrgStatus tiled_edge_values(TrgEngine *e, bool risk) {
+  TiledFieldBufs &tb = *e->tiled;
+  const FieldTiled &T = tb.T;
+  hipStream_t s = e->s_main;
+  TiledFieldBufs::EdgeValues &ev = risk ? tb.risks : tb.costs;
+  const uint32_t sf_bits = risk ? 0u : float_bits(e->prm.safety_factor);
+  if (ev.version == tb.version && ev.serial == tb.serial && ev.sf_bits == sf_bits) return TRG_OK;
+  ev = TiledFieldBufs::EdgeValues{};
+  if (T.V > 0) {
+    const int n = T.V + T.G;
+    TrgStatus st;
+    if ((st = tiled_grow(e, risk ? tb.er : tb.ec, ((size_t)tb.E2 + 4) * 4)) != TRG_OK ||
+        (st = tiled_grow(e, tb.stats, sizeof(FieldEdgeStats))) != TRG_OK)
+      return st;
+    if (risk)
+      launch_field_edge_risk(tb.col.as<int>(), tb.w.as<float>(), T.state, n, tb.E2, tb.er.as<float>(),
+                             tb.stats.as<FieldEdgeStats>(), s);
+    else
+      launch_field_edge_cost(tb.col.as<int>(), tb.w.as<float>(), tb.dist.as<float>(), T.state, n, tb.E2,
+                             e->prm.safety_factor, bits_float(FIELD_INF_BITS), tb.ec.as<float>(),
+                             tb.stats.as<FieldEdgeStats>(), s);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(tb.h_stats, tb.stats.p, sizeof(FieldEdgeStats), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    ev.mean = tb.h_stats->count ? tb.h_stats->sum / (double)tb.h_stats->count : 0.0;
+    ev.bad = tb.h_stats->bad != 0;
+  }
+  ev.version = tb.version;
+  ev.serial = tb.serial;
+  ev.sf_bits = sf_bits;
+  return TRG_OK;
+}
+
+// The solve graph of this rank for the current stitch (trg_field_tiled.inc), built when the graph or the stitch moved
+// since the last one, and on it the edge values of the objective asked for.  The stitched rows are read where they
+// are: in HBM while stitch_assemble's arrays are current, else from the host rows an export fetched.
+TrgStatus tiled_graph(TrgEngine *e, const ExchangeState &x, bool risk) {
   TiledFieldBufs &tb = *e->tiled;
   hipStream_t s = e->s_main;
   const Csr &rows = e->csr_stitched;
   const int V = (int)rows.state.size();
   const bool on_device = e->current(TrgEngine::VIEW_STITCH_DEV);
+  const std::string what = tiled_what(risk);
   if (rows.rowptr.empty() || e->stitch_node_off.empty() || (V > 0 && !on_device && rows.rowptr.size() != (size_t)V + 1))
-    return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: no current stitched rows (stitch after the tile's graph last changed)");
+    return e->fail(TRG_ERR_INVALID_ARG, what + "no current stitched rows (stitch after the tile's graph last changed)");
   const std::vector<int32_t> &off = e->stitch_node_off;
   const int R = (int)off.size() - 1, tile = e->stitch_tile;
   if (R != x.nranks || tile != x.rank)
-    return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: the stitch's tile is not this rank of the communicator");
+    return e->fail(TRG_ERR_INVALID_ARG, what + "the stitch's tile is not this rank of the communicator");
   if (off[tile + 1] - off[tile] != V)
-    return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: the stitch's node offsets do not match its rows");
-  const uint32_t sf_bits = float_bits(e->prm.safety_factor);
-  if (tb.version == e->graph_version && tb.serial == e->stitch_serial && tb.sf_bits == sf_bits) return TRG_OK;
+    return e->fail(TRG_ERR_INVALID_ARG, what + "the stitch's node offsets do not match its rows");
+  if (tb.version == e->graph_version && tb.serial == e->stitch_serial) return tiled_edge_values(e, risk);
   tb.version = 0;  // (until the build is through)
+  tb.costs = tb.risks = TiledFieldBufs::EdgeValues{};
   FieldTiled &T = tb.T;
   T = FieldTiled{};
   T.V = V;
   T.lo = off[tile];
   T.Vg = off[R];
   tb.E2 = 0;
-  tb.mean_cost = 0.0;
-  tb.bad_cost = false;
   if (V > 0) {
     TrgStatus st;
     const int En = on_device ? e->stitched_edges : (int)rows.col.size();
@@ -177,7 +229,7 @@ TrgStatus tiled_graph(TrgEngine *e, const ExchangeState &x) {
     }
     DevGraph g;
     if ((st = ensure_dev_graph(e, DEV_NODES, &g)) != TRG_OK) return st;
-    if (g.V != V || !g.state) return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: the stitched rows are not of this tile's graph");
+    if (g.V != V || !g.state) return e->fail(TRG_ERR_INVALID_ARG, what + "the stitched rows are not of this tile's graph");
     // ghosts and border rows: flags, scans, counts
     const size_t nVg = (size_t)T.Vg + 2, nV = (size_t)V + 2;
     if ((st = tiled_grow(e, tb.ghost_flag, nVg * 4)) != TRG_OK || (st = tiled_grow(e, tb.ghost_off, nVg * 4)) != TRG_OK ||
@@ -193,8 +245,8 @@ TrgStatus tiled_graph(TrgEngine *e, const ExchangeState &x) {
     HIPCHK(e, hipStreamSynchronize(s));
     T.G = tb.h_n[0];
     T.B = tb.h_n[1];
-    if (T.G < 0 || T.G > T.Vg || T.B < 0 || T.B > V) return e->fail(TRG_ERR_DEVICE, "tiled cost field: bad ghost or border count");
-    if ((long long)V + T.G + 8 > INT_MAX) return e->fail(TRG_ERR_CAPACITY, "tiled cost field: too many nodes and ghosts");
+    if (T.G < 0 || T.G > T.Vg || T.B < 0 || T.B > V) return e->fail(TRG_ERR_DEVICE, what + "bad ghost or border count");
+    if ((long long)V + T.G + 8 > INT_MAX) return e->fail(TRG_ERR_CAPACITY, what + "too many nodes and ghosts");
     const size_t n = (size_t)V + T.G, nG = (size_t)T.G + 2;
     if ((st = tiled_grow(e, tb.gid_of, (n + 1) * 4)) != TRG_OK || (st = tiled_grow(e, tb.state, (n + 1) * 4)) != TRG_OK ||
         (st = tiled_grow(e, tb.border, ((size_t)T.B + 1) * 4)) != TRG_OK || (st = tiled_grow(e, tb.ghost_deg, nG * 4)) != TRG_OK ||
@@ -213,30 +265,20 @@ TrgStatus tiled_graph(TrgEngine *e, const ExchangeState &x) {
     HIPCHK(e, hipMemcpyAsync(&tb.h_n[0], tb.ghost_row.as<int>() + T.G, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     const int X = tb.h_n[0];  // cross edges of this tile's rows
-    if (X < 0 || X > En) return e->fail(TRG_ERR_DEVICE, "tiled cost field: bad cross-edge count");
-    if ((long long)En + X + 8 > INT_MAX) return e->fail(TRG_ERR_CAPACITY, "tiled cost field: too many edges");
+    if (X < 0 || X > En) return e->fail(TRG_ERR_DEVICE, what + "bad cross-edge count");
+    if ((long long)En + X + 8 > INT_MAX) return e->fail(TRG_ERR_CAPACITY, what + "too many edges");
     tb.E2 = En + X;
     const size_t e2 = (size_t)tb.E2 + 4;
     if ((st = tiled_grow(e, tb.rowptr, (n + 2) * 4)) != TRG_OK) return st;
-    for (DevArr *a : {&tb.col, &tb.w, &tb.dist, &tb.ec})
+    for (DevArr *a : {&tb.col, &tb.w, &tb.dist})
       if ((st = tiled_grow(e, *a, e2 * 4)) != TRG_OK) return st;
-    if ((st = tiled_grow(e, tb.stats, sizeof(FieldEdgeStats))) != TRG_OK) return st;
     launch_tiled_fill(T, rowptr, col, w, dist, En, tb.E2, tb.ghost_row.as<int>(), tb.ghost_fill.as<int>(),
                       tb.rowptr.as<int>(), tb.col.as<int>(), tb.w.as<float>(), tb.dist.as<float>(), s);
-    // edge costs of its own (the single-engine cache is neither read nor evicted); every edge into a ghost is skipped
-    launch_field_edge_cost(tb.col.as<int>(), tb.w.as<float>(), tb.dist.as<float>(), T.state, (int)n, tb.E2,
-                           e->prm.safety_factor, bits_float(FIELD_INF_BITS), tb.ec.as<float>(),
-                           tb.stats.as<FieldEdgeStats>(), s);
     HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(tb.h_stats, tb.stats.p, sizeof(FieldEdgeStats), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    tb.mean_cost = tb.h_stats->count ? tb.h_stats->sum / (double)tb.h_stats->count : 0.0;
-    tb.bad_cost = tb.h_stats->bad != 0;
   }
   tb.version = e->graph_version;
   tb.serial = e->stitch_serial;
-  tb.sf_bits = sf_bits;
-  return TRG_OK;
+  return tiled_edge_values(e, risk);
 }
 
 // the work arrays for m fields and the kernels' view of them
@@ -244,10 +286,11 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
   TiledFieldBufs &tb = *e->tiled;
   const FieldTiled &T = tb.T;
   const TiledRequest &rq = run.rq;
-  if (tb.bad_cost) return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: an edge cost is negative or not finite");
+  if (rq.risk && tb.risks.bad) return e->fail(TRG_ERR_INVALID_ARG, "tiled risk field: an edge weight is negative or not finite");
+  if (!rq.risk && tb.costs.bad) return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: an edge cost is negative or not finite");
   const long long n = (long long)T.V + T.G;
   if ((long long)rq.m * n + 8 > INT_MAX)
-    return e->fail(TRG_ERR_CAPACITY, "tiled cost field: m x (nodes + ghosts) does not fit the solver's 32-bit item index");
+    return e->fail(TRG_ERR_CAPACITY, std::string(tiled_what(rq.risk)) + "m x (nodes + ghosts) does not fit the solver's 32-bit item index");
   FieldDev &F = run.F;
   F.V = (int)n;
   F.m = rq.m;
@@ -264,7 +307,7 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
     return st;
   F.rowptr = tb.rowptr.as<int>();
   F.col = tb.col.as<int>();
-  F.ec = tb.ec.as<float>();
+  F.ec = rq.risk ? tb.er.as<float>() : tb.ec.as<float>();
   F.key = tb.key.as<unsigned long long>();
   for (int i = 0; i < 2; ++i) {
     F.q[i] = tb.q[i].as<int>();
@@ -281,7 +324,7 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
   hipStream_t s = e->s_main;
   for (int j = 0; j < rq.n_targets; ++j)
     if (rq.targets[j] < 0 || rq.targets[j] >= T.V)
-      return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field sets: target " + std::to_string(j) + " (" + std::to_string(rq.targets[j]) +
+      return e->fail(TRG_ERR_INVALID_ARG, std::string(rq.what) + "target " + std::to_string(j) + " (" + std::to_string(rq.targets[j]) +
                                               ") is outside this tile's [0, " + std::to_string(T.V) + ")");
   std::vector<TiledEntry> &mine = tb.h_entries;
   mine.clear();
@@ -322,7 +365,7 @@ TrgStatus tiled_prepare(TrgEngine *e, const ExchangeState &x, TiledRun &run) {
   HIPCHK(e, tb.h_n.ensure(4));
   HIPCHK(e, tb.t0.create());
   HIPCHK(e, tb.t1.create());
-  TrgStatus st = tiled_graph(e, x);
+  TrgStatus st = tiled_graph(e, x, run.rq.risk);
   if (st == TRG_OK) st = tiled_work_arrays(e, run);
   return st;
 }
@@ -335,14 +378,14 @@ TrgStatus tiled_rounds(TrgEngine *e, TiledRun &run) {
   const long long cap = 4LL * F.N + 64;
   int first = -1;
   for (;;) {
-    for (int i = 0; i < TILED_BATCH; ++i, ++run.round) launch_field_round(F, run.round, s);
+    for (int i = 0; i < TILED_BATCH; ++i, ++run.round) launch_field_round(F, run.round, s, nullptr, nullptr, run.rq.risk);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(tb.h_state, &F.ctrl->s, sizeof(FieldState), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
-    if (tb.h_state->overflow) return e->fail(TRG_ERR_DEVICE, "tiled cost field: queue overflow");
+    if (tb.h_state->overflow) return e->fail(TRG_ERR_DEVICE, std::string(tiled_what(run.rq.risk)) + "queue overflow");
     if (tb.h_state->work == 0) break;
     if (first < 0) first = tb.h_state->rounds;
-    if (tb.h_state->rounds - first >= cap) return e->fail(TRG_ERR_DEVICE, "tiled cost field: the rounds of a rank did not converge");
+    if (tb.h_state->rounds - first >= cap) return e->fail(TRG_ERR_DEVICE, std::string(tiled_what(run.rq.risk)) + "the rounds of a rank did not converge");
   }
   return TRG_OK;
 }
@@ -411,7 +454,9 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
   FieldDev &F = run.F;
   hipStream_t s = e->s_main;
   const bool work = F.N > 0;
-  const float delta = tb.mean_cost > 0.0 ? (float)(e->field_delta_scale * tb.mean_cost) : 0.0f;
+  // the bucket width from the mean edge value of the objective; all risks zero: width 0 ("Risk fields across tiles")
+  const double mean = run.rq.risk ? tb.risks.mean : tb.costs.mean;
+  const float delta = mean > 0.0 ? (float)(e->field_delta_scale * mean) : 0.0f;
   TiledLocal mine(e, local);
   mine.step([&]() -> TrgStatus {
     if (!work) return TRG_OK;
@@ -423,7 +468,7 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
   });
   // a key of a border item drops at most a few times per item in practice; the cap is the round cap's shape
   const TrgStatus st = tiled_exchanges(
-      e, x, run, mine, "tiled cost field: ", (long long)F.m * T.B, [&](long long border) { return 4 * F.m * border + 64; },
+      e, x, run, mine, tiled_what(run.rq.risk), (long long)F.m * T.B, [&](long long border) { return 4 * F.m * border + 64; },
       run.exchanges, run.records,
       [&](int, const void *d_all, int gathered) -> TrgStatus {
         launch_tiled_merge(F, T, d_all, gathered, s);
@@ -457,19 +502,22 @@ TrgStatus tiled_owner_pass(TrgEngine *e, ExchangeState &x, TiledRun &run) {
     if (F.N <= 0) return TRG_OK;
     int *changed = tb.own_changed.as<int>();
     HIPCHK(e, hipEventRecord(tb.t0, s));
-    launch_tiled_parents(F, T, s);
+    launch_tiled_parents(F, T, s, run.rq.risk);
     launch_tiled_forest_begin(F, T, tb.set_ptr.as<int>(), owner, changed, tb.n_rec.as<int>() + 1,
                               tb.published.as<unsigned long long>(), s);
     HIPCHK(e, hipMemcpyAsync(&tb.h_n[1], tb.n_rec.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, s));
     int sweeps = 0;
-    if (const TrgStatus st = field_forest_sweeps(e, F, changed, &tb.h_n[0], "tiled cost field sets: the owner pass's sweeps", sweeps);
+    if (const TrgStatus st = field_forest_sweeps(e, F, changed, &tb.h_n[0],
+                                                    run.rq.risk ? "tiled risk field sets: the owner pass's sweeps"
+                                                                : "tiled cost field sets: the owner pass's sweeps",
+                                                    sweeps);
         st != TRG_OK)
       return st;
     anc = F.q[sweeps & 1];
     run.roots = tb.h_n[1];  // (the first wait of the sweeps was for this copy too)
     return TRG_OK;
   });
-  return tiled_exchanges(e, x, run, mine, "tiled cost field sets: owner pass: ", (long long)F.m * T.B,
+  return tiled_exchanges(e, x, run, mine, std::string(run.rq.what) + "owner pass: ", (long long)F.m * T.B,
                          [&](long long border) { return F.m * border + 2; }, run.owner_exchanges, run.owner_records,
                          [&](int, const void *d_all, int gathered) -> TrgStatus {
                            launch_tiled_owner_step(F, T, d_all, gathered, anc, owner, tb.published.as<unsigned long long>(),
@@ -490,7 +538,8 @@ TrgStatus tiled_outputs(TrgEngine *e, TiledRun &run) {
     HIPCHK(e, hipEventRecord(tb.t0, s));
     // (with owners the parent sweep ran before the owner pass)
     launch_tiled_finish(run.F, T, tb.cost.as<float>(), tb.hops.as<int>(), tb.parent_out.as<int>(),
-                        rq.parent != nullptr && !rq.owners, tb.owner.as<int>(), rq.owner ? tb.owner_out.as<int>() : nullptr, s);
+                        rq.parent != nullptr && !rq.owners, tb.owner.as<int>(), rq.owner ? tb.owner_out.as<int>() : nullptr, s,
+                        rq.risk);
     if (rq.owners) {
       if (rq.owned) launch_tiled_owned(run.F, T, tb.set_ptr.as<int>(), tb.owner.as<int>(), n_entries, tb.owned.as<int>(), s);
       FieldSets S{};
@@ -532,7 +581,8 @@ TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
     if (const TrgStatus st = tiled_owner_pass(e, x, run); st != TRG_OK) return st;
   if (const TrgStatus st = tiled_outputs(e, run); st != TRG_OK) return st;
   // retained for the routes: the keys, marks and parents lie in the work arrays as the kernels left them
-  e->tiled->solved = TiledFieldBufs::Solved{true, run.rq.m, run.rq.owners, run.rq.owners || run.rq.parent != nullptr, run.F};
+  e->tiled->solved = TiledFieldBufs::Solved{true, run.rq.m, run.rq.owners, run.rq.owners || run.rq.parent != nullptr,
+                                            run.rq.risk, float_bits(e->prm.safety_factor), run.F};
   return TRG_OK;
 }
 
@@ -668,7 +718,8 @@ TrgStatus tiled_routes(TrgEngine *e, const TiledRoutesRequest &rq, TrgTiledRoute
   TiledLocal mine(e, TRG_OK);
   mine.step([&]() -> TrgStatus {
     if (!tb.solved.valid) return refuse("no tiled solve is retained (trg_engine_tiled_cost_field or _sets first)");
-    if (tb.version != e->graph_version || tb.serial != e->stitch_serial || tb.sf_bits != float_bits(e->prm.safety_factor))
+    if (tb.version != e->graph_version || tb.serial != e->stitch_serial ||
+        (!tb.solved.risk && tb.solved.sf_bits != float_bits(e->prm.safety_factor)))
       return refuse("the retained tiled solve is stale (the tile's graph, the stitch or the safety factor changed since)");
     for (int r = 0; r < rq.n; ++r)
       if (rq.field[r] < 0 || rq.field[r] >= tb.solved.m)
@@ -686,7 +737,7 @@ TrgStatus tiled_routes(TrgEngine *e, const TiledRoutesRequest &rq, TrgTiledRoute
     HIPCHK(e, hipMemsetAsync(tb.n_rec.p, 0, 16, s));
     HIPCHK(e, hipEventRecord(tb.t0, s));
     if (!tb.solved.parents) {  // the solve was asked for no parents: local work, no collective
-      if (run.F.N > 0) launch_tiled_parents(run.F, T, s);
+      if (run.F.N > 0) launch_tiled_parents(run.F, T, s, tb.solved.risk);
       tb.solved.parents = true;
     }
     R.field = tb.route_field.as<int>();
@@ -711,7 +762,7 @@ TrgStatus tiled_routes(TrgEngine *e, const TiledRoutesRequest &rq, TrgTiledRoute
         }
         TiledRouteInfo *d_infos = tb.route_info.as<TiledRouteInfo>();
         if (exchange > 1) {
-          launch_tiled_route_step(run.F, T, R, d_all, gathered, d_infos, s);
+          launch_tiled_route_step(run.F, T, R, d_all, gathered, d_infos, s, tb.solved.risk);
           return TRG_OK;
         }
         // exchange 1: the lengths of all routes -- the one download of records -- then the walks begin
@@ -739,7 +790,7 @@ TrgStatus tiled_routes(TrgEngine *e, const TiledRoutesRequest &rq, TrgTiledRoute
           R.offsets = tb.route_off.as<int>();
           R.node_gids = tb.route_gids.as<int>();
         }
-        launch_tiled_route_step(run.F, T, R, nullptr, 0, d_infos, s);
+        launch_tiled_route_step(run.F, T, R, nullptr, 0, d_infos, s, tb.solved.risk);
         return TRG_OK;
       });
   if (st != TRG_OK) return st;
@@ -792,7 +843,7 @@ TrgStatus trg_engine_tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *so
   return entry(e, "tiled_cost_field", DEVICE, [&] {
     int32_t one_each[TRG_FIELD_BATCH_MAX + 1];  // m sets of one entry
     for (int k = 0; k <= TRG_FIELD_BATCH_MAX; ++k) one_each[k] = k;
-    const TiledRequest rq{m, one_each, source_gids, nullptr, cost, hops, parent, false, "tiled cost field: ",
+    const TiledRequest rq{m, one_each, source_gids, nullptr, cost, hops, parent, false, false, "tiled cost field: ",
                           "null source_gids", "the source of field "};
     return tiled_call(e, rq, info, [](TrgTiledFieldInfo &, const TiledRun &) {});
   });
@@ -803,8 +854,34 @@ TrgStatus trg_engine_tiled_cost_field_sets(TrgEngine *e, int32_t m, const int32_
                                            int32_t *owner, const int32_t *targets, int32_t n_targets, float *cost_at,
                                            int32_t *hops_at, int32_t *owner_at, int32_t *owned, TrgTiledSetInfo *info) {
   return entry(e, "tiled_cost_field_sets", DEVICE, [&] {
-    const TiledRequest rq{m, set_ptr, set_gids, set_cost0, cost, hops, parent, true, "tiled cost field sets: ",
+    const TiledRequest rq{m, set_ptr, set_gids, set_cost0, cost, hops, parent, true, false, "tiled cost field sets: ",
                           "null set_ptr or set_gids", nullptr, owner, targets, n_targets, cost_at, hops_at, owner_at, owned};
+    return tiled_call(e, rq, info, [](TrgTiledSetInfo &out, const TiledRun &run) {
+      out.owner_exchanges = run.owner_exchanges;
+      out.roots = run.roots;
+      out.owner_records_sent = run.owner_records;
+    });
+  });
+}
+
+TrgStatus trg_engine_tiled_risk_field(TrgEngine *e, int32_t m, const int32_t *source_gids, float *risk, int32_t *hops,
+                                      int32_t *parent, TrgTiledFieldInfo *info) {
+  return entry(e, "tiled_risk_field", DEVICE, [&] {
+    int32_t one_each[TRG_FIELD_BATCH_MAX + 1];  // m sets of one entry
+    for (int k = 0; k <= TRG_FIELD_BATCH_MAX; ++k) one_each[k] = k;
+    const TiledRequest rq{m, one_each, source_gids, nullptr, risk, hops, parent, false, true, "tiled risk field: ",
+                          "null source_gids", "the source of field "};
+    return tiled_call(e, rq, info, [](TrgTiledFieldInfo &, const TiledRun &) {});
+  });
+}
+
+TrgStatus trg_engine_tiled_risk_field_sets(TrgEngine *e, int32_t m, const int32_t *set_ptr, const int32_t *set_gids,
+                                           float *risk, int32_t *hops, int32_t *parent, int32_t *owner,
+                                           const int32_t *targets, int32_t n_targets, float *risk_at, int32_t *hops_at,
+                                           int32_t *owner_at, int32_t *owned, TrgTiledSetInfo *info) {
+  return entry(e, "tiled_risk_field_sets", DEVICE, [&] {
+    const TiledRequest rq{m, set_ptr, set_gids, nullptr, risk, hops, parent, true, true, "tiled risk field sets: ",
+                          "null set_ptr or set_gids", nullptr, owner, targets, n_targets, risk_at, hops_at, owner_at, owned};
     return tiled_call(e, rq, info, [](TrgTiledSetInfo &out, const TiledRun &run) {
       out.owner_exchanges = run.owner_exchanges;
       out.roots = run.roots;

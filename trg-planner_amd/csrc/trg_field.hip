@@ -80,7 +80,8 @@
 // of the stitched global graph, each rank relaxing its own rows plus mirrors of the other ends of its cross edges and
 // trading border keys between runs of the round kernels -- one more relaxation order to the same fixed point.  The
 // round kernels run on that rank's solve graph as they are; the tiled kernels build the graph, seed, publish, merge
-// and take the parents as least GLOBAL ids.
+// and take the parents as least GLOBAL ids.  A risk field across tiles ("Risk fields across tiles") is the same run with
+// launch_field_round(.., risk = true) on the edge risks of that graph.
 //
 // Compiled with -ffp-contract=off (build.sh): a cost is one fp32 multiply, add, multiply; a fold one add.
 #include "trg_kernels.h"

@@ -1,5 +1,7 @@
-// trg_field_tiled.inc -- kernels of the cost field across tiles (DESIGN.md section 7, "Cost fields across tiles");
-// part of trg_field.hip, whose round kernels run on the solve graph built here as they are.
+// trg_field_tiled.inc -- kernels of the cost field across tiles (DESIGN.md section 7, "Cost fields across tiles") and of
+// the risk field across tiles ("Risk fields across tiles": the same kernels on the edge risks of the solve graph, the
+// parent sweep and the route walk in their RISK form); part of trg_field.hip, whose round kernels run on the solve
+// graph built here as they are.
 //
 // The solve graph of a rank: its V local nodes, then its G ghosts -- the distinct other ends of this tile's cross
 // edges, in ascending global id.  The ghost table is a flag per GLOBAL node and the exclusive scan of the flags
@@ -238,7 +240,9 @@ __global__ __launch_bounds__(THREADS) void k_tiled_merge(FieldDev F, FieldTiled 
 }
 
 // The parent sweep over the solve graph, ghost rows included: the least GLOBAL id u with an edge u -> v whose
-// extension of key[u] is key[v] (ghosts are not in id order among the solve-graph indices, hence the table).
+// extension of key[u] is key[v] (ghosts are not in id order among the solve-graph indices, hence the table).  RISK: F.ec
+// holds the edge risks and the extension is the maximum ("Risk fields across tiles").
+template <bool RISK>
 __global__ __launch_bounds__(THREADS) void k_tiled_parent(FieldDev F, FieldTiled T) {
   const int sub = threadIdx.x & (GROUP - 1);
   const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
@@ -252,7 +256,7 @@ __global__ __launch_bounds__(THREADS) void k_tiled_parent(FieldDev F, FieldTiled
       const float c = F.ec[k];
       if (__float_as_uint(c) == FIELD_EDGE_SKIP) continue;
       const int v = fbase + F.col[k];
-      if (key_extend(ku, c) == F.key[v]) atomicMin(&F.parent[v], gu);
+      if (key_extend<RISK>(ku, c) == F.key[v]) atomicMin(&F.parent[v], gu);
     }
   }
 }
@@ -408,8 +412,9 @@ __global__ __launch_bounds__(THREADS) void k_tiled_route_len(FieldDev F, FieldTi
 // the owner's bits -- adds its dist and w, and steps to the parent; at a ghost it publishes HANDOFF, at hops == 0,
 // where its node must carry a member mark, END.  Every route has one walker at any time: nothing here is atomic but
 // the record slots (wave_reserve, every lane of the wave gets there: the trip counts are uniform) and the word beside
-// the record count that a walk which lost its way sets to its route + 1.
-template <bool BEGIN>
+// the record count that a walk which lost its way sets to its route + 1.  RISK: the tight-edge test extends by the
+// maximum over the edge risks in F.ec; the sums are the folds of dist and w all the same.
+template <bool BEGIN, bool RISK>
 __global__ __launch_bounds__(THREADS) void k_tiled_route_step(FieldDev F, FieldTiled T, TiledRoutes R,
                                                               const TiledRouteRec *__restrict__ in, int n_in) {
   TiledRouteRec *rec = (TiledRouteRec *)R.rec;
@@ -471,7 +476,7 @@ __global__ __launch_bounds__(THREADS) void k_tiled_route_step(FieldDev F, FieldT
           bool hit = false;
           if (k < kend && F.col[k] == v) {
             const float c = F.ec[k];
-            hit = __float_as_uint(c) != FIELD_EDGE_SKIP && key_extend(ku, c) == kv;
+            hit = __float_as_uint(c) != FIELD_EDGE_SKIP && key_extend<RISK>(ku, c) == kv;
           }
           const unsigned hits = (unsigned)(ballot(hit) >> gshift) & ((1u << GROUP) - 1u);
           if (hits) {
@@ -531,19 +536,23 @@ void launch_tiled_route_len(const FieldDev &F, const FieldTiled &T, const TiledR
 }
 
 void launch_tiled_route_step(const FieldDev &F, const FieldTiled &T, const TiledRoutes &R, const void *rec_in, int n_in,
-                             TiledRouteInfo *infos, hipStream_t s) {
+                             TiledRouteInfo *infos, hipStream_t s, bool risk) {
   (void)hipMemsetAsync(R.n_rec, 0, sizeof(int), s);
   const TiledRouteRec *in = (const TiledRouteRec *)rec_in;
   if (!in) {
-    if (R.n > 0 && T.V > 0)
-      hipLaunchKernelGGL(k_tiled_route_step<true>, dim3(field_blocks((long long)R.n * GROUP, THREADS)), dim3(THREADS), 0,
-                         s, F, T, R, in, 0);
+    if (R.n > 0 && T.V > 0) {
+      const dim3 grid(field_blocks((long long)R.n * GROUP, THREADS));
+      if (risk) hipLaunchKernelGGL((k_tiled_route_step<true, true>), grid, dim3(THREADS), 0, s, F, T, R, in, 0);
+      else hipLaunchKernelGGL((k_tiled_route_step<true, false>), grid, dim3(THREADS), 0, s, F, T, R, in, 0);
+    }
     return;
   }
   if (n_in <= 0) return;
-  if (T.V > 0)
-    hipLaunchKernelGGL(k_tiled_route_step<false>, dim3(field_blocks((long long)n_in * GROUP, THREADS)), dim3(THREADS), 0,
-                       s, F, T, R, in, n_in);
+  if (T.V > 0) {
+    const dim3 grid(field_blocks((long long)n_in * GROUP, THREADS));
+    if (risk) hipLaunchKernelGGL((k_tiled_route_step<false, true>), grid, dim3(THREADS), 0, s, F, T, R, in, n_in);
+    else hipLaunchKernelGGL((k_tiled_route_step<false, false>), grid, dim3(THREADS), 0, s, F, T, R, in, n_in);
+  }
   hipLaunchKernelGGL(k_tiled_route_end, dim3(field_blocks(n_in, THREADS)), dim3(THREADS), 0, s, in, n_in, infos, R.n);
 }
 
@@ -597,14 +606,15 @@ void launch_tiled_merge(const FieldDev &F, const FieldTiled &T, const void *rec,
                        (const TiledRec *)rec, n_rec);
 }
 
-void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s) {
-  hipLaunchKernelGGL(k_tiled_parent, dim3(field_blocks((long long)F.V * GROUP, THREADS), F.m), dim3(THREADS), 0, s, F,
-                     T);
+void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s, bool risk) {
+  const dim3 grid(field_blocks((long long)F.V * GROUP, THREADS), F.m);
+  if (risk) hipLaunchKernelGGL(k_tiled_parent<true>, grid, dim3(THREADS), 0, s, F, T);
+  else hipLaunchKernelGGL(k_tiled_parent<false>, grid, dim3(THREADS), 0, s, F, T);
 }
 
 void launch_tiled_finish(const FieldDev &F, const FieldTiled &T, float *cost, int *hops, int *parent, bool parents,
-                         const int *owner, int *owner_out, hipStream_t s) {
-  if (parents) launch_tiled_parents(F, T, s);
+                         const int *owner, int *owner_out, hipStream_t s, bool risk) {
+  if (parents) launch_tiled_parents(F, T, s, risk);
   if (T.V > 0)
     hipLaunchKernelGGL(k_tiled_output, dim3(field_blocks(T.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, cost, hops,
                        parent, owner, owner_out);

@@ -670,9 +670,10 @@ void launch_tiled_merge(const FieldDev &F, const FieldTiled &T, const void *rec,
 // parents as least global ids (when asked for), then cost / hops / parent of the local nodes, m x T.V, and with
 // owner_out (else nullptr) their owners from `owner`, the owner pass's m x (V + G) words
 void launch_tiled_finish(const FieldDev &F, const FieldTiled &T, float *cost, int *hops, int *parent, bool parents,
-                         const int *owner, int *owner_out, hipStream_t s);
-// the parent sweep alone (the set call runs it before its owner pass; launch_tiled_finish then goes without)
-void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s);
+                         const int *owner, int *owner_out, hipStream_t s, bool risk = false);
+// the parent sweep alone (the set call runs it before its owner pass; launch_tiled_finish then goes without); `risk`: F.ec
+// holds edge risks (launch_field_edge_risk over the solve graph) and a key is extended by the maximum
+void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s, bool risk = false);
 // The owner pass of the set call, after the parent sweep.  begin: F.q[0] = every item's first ancestor (a local root
 // and a ghost with a key: itself; another item with a key: its parent's solve-graph item), owner (m x (V + G)) = the
 // roots' entries counted from set_ptr[field], -1 elsewhere, *n_roots their count; changed (FIELD_OWNER_SWEEPS_MAX
@@ -712,6 +713,6 @@ void launch_tiled_route_len(const FieldDev &F, const FieldTiled &T, const TiledR
 // infos (n entries, device; num_nodes set from the LEN records).  A walk publishes HANDOFF {route, parent gid, sums}
 // where its parent is a ghost and END {route, -1 - root gid, sums} at a root.
 void launch_tiled_route_step(const FieldDev &F, const FieldTiled &T, const TiledRoutes &R, const void *rec_in, int n_in,
-                             TiledRouteInfo *infos, hipStream_t s);
+                             TiledRouteInfo *infos, hipStream_t s, bool risk = false);
 
 }  // namespace trg

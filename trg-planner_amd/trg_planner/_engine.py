@@ -140,7 +140,7 @@ EXPORTS = [
     "trg_engine_risk_field_sets", "trg_engine_risk_field_refresh",
     "trg_engine_pose_links", "trg_engine_cost_field_seeded",
     "trg_engine_tiled_cost_field", "trg_engine_stitch_ids", "trg_engine_tiled_cost_field_sets",
-    "trg_engine_tiled_field_routes",
+    "trg_engine_tiled_field_routes", "trg_engine_tiled_risk_field", "trg_engine_tiled_risk_field_sets",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -251,6 +251,9 @@ def load_library():
     L.trg_engine_stitch_ids.argtypes = [vp, ip, ip, ip]
     L.trg_engine_tiled_cost_field_sets.argtypes = [vp, C.c_int32, ip, ip, fp, fp, ip, ip, ip, ip, C.c_int32, fp, ip, ip,
                                                    ip, C.POINTER(TrgTiledSetInfo)]
+    L.trg_engine_tiled_risk_field.argtypes = L.trg_engine_tiled_cost_field.argtypes
+    L.trg_engine_tiled_risk_field_sets.argtypes = [vp, C.c_int32, ip, ip, fp, ip, ip, ip, ip, C.c_int32, fp, ip, ip, ip,
+                                                   C.POINTER(TrgTiledSetInfo)]
     L.trg_engine_tiled_field_routes.argtypes = [vp, C.c_int32, ip, ip, ip, ip, fp, C.c_int32,
                                                 C.POINTER(TrgTiledRouteInfo), C.POINTER(TrgTiledRoutesInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
@@ -573,6 +576,85 @@ class Engine:
         goals = np.ascontiguousarray(goal_gids, dtype=np.int32).reshape(-1)
         self.tiled_cost_fields([int(start_gid)], parent=False)
         return self.tiled_routes(np.zeros(goals.shape[0], np.int32), goals)
+
+    # ---- risk fields across tiles ("Risk fields across tiles") ---------------------------
+    def tiled_risk_fields(self, source_gids, parent=True):
+        """The risk fields of the global stitched graph from the global ids `source_gids`, for this tile's nodes
+        (trg_engine_tiled_risk_field): the least, over all walks, of the greatest edge weight on the walk.  A collective
+        call like tiled_cost_fields -> its dict with "risk" where that has "cost"."""
+        src = np.ascontiguousarray(source_gids, dtype=np.int32).reshape(-1)
+        m = int(src.shape[0])
+        try:
+            offset, V = self.global_ids()
+        except TrgError:
+            offset, V = 0, 0  # (the solve itself reports, and announces, that there are no current rows)
+        rows = max(m, 1)
+        risk = np.empty((rows, V), np.float32)
+        hops = np.empty((rows, V), np.int32)
+        par = np.empty((rows, V), np.int32) if parent else None
+        info = TrgTiledFieldInfo()
+        self._chk(self.L.trg_engine_tiled_risk_field(self.h, m, _i(src), _f(risk), _i(hops),
+                                                     None if par is None else _i(par), C.byref(info)))
+        return dict(risk=risk, hops=hops, parent=par, offset=offset, info=info)
+
+    def tiled_risk_fields_from(self, sets, targets=None, full=True, parent=True):
+        """Risk fields from source sets across tiles (trg_engine_tiled_risk_field_sets): field k from EVERY entry of
+        sets[k] (GLOBAL ids) at risk 0 -- risk solves take no start values.  A collective call like
+        tiled_cost_fields_from -> its dict with "risk" / "risk_at" where that has "cost" / "cost_at" and without
+        "start_costs"."""
+        sets, ptr, ids, _, _ = pack_sets("tiled_risk_fields_from", sets)
+        m = len(sets)
+        try:
+            offset, V = self.global_ids()
+        except TrgError:
+            offset, V = 0, 0  # (the solve itself reports, and announces, that there are no current rows)
+        rows = max(m, 1)
+        out = dict(offset=offset, sets=sets)
+        if full:
+            out.update(risk=np.empty((rows, V), np.float32), hops=np.empty((rows, V), np.int32),
+                       parent=np.empty((rows, V), np.int32) if parent else None, owner=np.empty((rows, V), np.int32))
+        tg, n_t = None, 0
+        if targets is not None:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+            n_t = int(tg.shape[0])
+            out.update(risk_at=np.empty((rows, n_t), np.float32), hops_at=np.empty((rows, n_t), np.int32),
+                       owner_at=np.empty((rows, n_t), np.int32))
+        owned, split_owned = _owned_buffer(ptr)
+        info = TrgTiledSetInfo()
+        arr = lambda name, conv: None if out.get(name) is None else conv(out[name])  # noqa: E731
+        self._chk(self.L.trg_engine_tiled_risk_field_sets(
+            self.h, m, _i(ptr), _i(ids), arr("risk", _f), arr("hops", _i), arr("parent", _i), arr("owner", _i),
+            None if tg is None or n_t == 0 else _i(tg), n_t, arr("risk_at", _f), arr("hops_at", _i),
+            arr("owner_at", _i), _i(owned), C.byref(info)))
+        out["owned"] = split_owned()
+        out["info"] = info
+        return out
+
+    def tiled_safest_routes(self, start_gid, goal_gids):
+        """The safest paths from one node of the global stitched graph to many: ONE tiled risk solve from `start_gid`
+        (no parents are downloaded) and one tiled_routes call without a capacity, all ranks alike (a collective call)
+        -> tiled_routes' dict; tiled.join_routes gives the routes.  Each route's `cost` is the least worst-edge risk to
+        its goal (tiled_risk_fields' semantics)."""
+        goals = np.ascontiguousarray(goal_gids, dtype=np.int32).reshape(-1)
+        self.tiled_risk_fields([int(start_gid)], parent=False)
+        return self.tiled_routes(np.zeros(goals.shape[0], np.int32), goals)
+
+    def tiled_frontier_ceilings(self, member_gids):
+        """For every Frontier node of THIS tile the least risk ceiling under which the nearest entry of `member_gids`
+        (GLOBAL ids, e.g. the robots' nodes) reaches it: a collective call -- one set risk field across tiles, read at
+        this tile's Frontier nodes on the device; no array of V_t entries is downloaded.  -> dict with "gids" (this
+        tile's Frontier nodes, global ids ascending), "risk" (+inf: unreachable), "hops" (-1), "owner" (the entry of
+        member_gids whose tree the node hangs in, -1) and "members" (their number).  tiled.safest_frontier joins the
+        ranks' answers."""
+        members = np.ascontiguousarray(member_gids, dtype=np.int32).reshape(-1)
+        try:
+            frontier = self._frontier_ids()
+        except TrgError:
+            frontier = np.empty(0, np.int32)  # (the solve reports what is wrong with this tile)
+        r = self.tiled_risk_fields_from([members], targets=frontier, full=False, parent=False)
+        gids = (frontier.astype(np.int64) + r["offset"]).astype(np.int32)
+        return dict(gids=gids, risk=r["risk_at"][0], hops=r["hops_at"][0], owner=r["owner_at"][0],
+                    members=int(members.shape[0]), info=r["info"])
 
     def set_option(self, key, value):
         self._chk(self.L.trg_engine_set_option(self.h, str(key).encode(), str(value).encode()))

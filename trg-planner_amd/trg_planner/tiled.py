@@ -219,10 +219,12 @@ def concat_stitched(parts):
 def concat_fields(parts):
     """The ranks' Engine.tiled_cost_fields (or tiled_cost_fields_from) results, in tile order -> dict of m x V arrays
     cost, hops, parent (global ids; None when a rank solved without parents) of the global stitched graph, and owner
-    when every part has one (a set solve's full results)."""
+    when every part has one (a set solve's full results).  The results of Engine.tiled_risk_fields (or
+    tiled_risk_fields_from) join alike, with "risk" where those have "cost"."""
     par = None if any(p["parent"] is None for p in parts) else np.concatenate([p["parent"] for p in parts], 1)
-    out = dict(cost=np.concatenate([p["cost"] for p in parts], 1), hops=np.concatenate([p["hops"] for p in parts], 1),
-               parent=par)
+    name = "risk" if parts and "risk" in parts[0] else "cost"
+    out = {name: np.concatenate([p[name] for p in parts], 1), "hops": np.concatenate([p["hops"] for p in parts], 1),
+           "parent": par}
     if all(p.get("owner") is not None for p in parts):
         out["owner"] = np.concatenate([p["owner"] for p in parts], 1)
     return out
@@ -241,6 +243,29 @@ def merge_frontier_picks(parts):
         picks = [p[k][1] for p in parts if p[k][1] is not None]
         best = min(picks, key=lambda q: (q[1], q[2], q[0])) if picks else None
         out.append((ids.astype(np.int32), best))
+    return out
+
+
+def safest_frontier(parts):
+    """The ranks' Engine.tiled_frontier_ceilings answers -> per member the Frontier node of the global stitched graph
+    that is safest to reach from it among those it owns: the least (risk bits, hops, gid), as (gid, risk, hops), or
+    None when it owns no reachable Frontier node.  A node is owned once, on the rank whose node it is."""
+    n = parts[0]["members"] if parts else 0
+    if any(p["members"] != n for p in parts):
+        raise ValueError("safest_frontier: the ranks answered for different numbers of members")
+    gids = np.concatenate([np.asarray(p["gids"], np.int32) for p in parts]) if parts else np.empty(0, np.int32)
+    risk = np.concatenate([np.asarray(p["risk"], np.float32) for p in parts]) if parts else np.empty(0, np.float32)
+    hops = np.concatenate([np.asarray(p["hops"], np.int32) for p in parts]) if parts else np.empty(0, np.int32)
+    owner = np.concatenate([np.asarray(p["owner"], np.int32) for p in parts]) if parts else np.empty(0, np.int32)
+    bits = risk.view(np.uint32)  # (risks are >= +0: their bits order as they do)
+    out = []
+    for k in range(n):
+        mine = np.flatnonzero((owner == k) & (hops >= 0))
+        if mine.size == 0:
+            out.append(None)
+            continue
+        j = int(mine[np.lexsort((gids[mine], hops[mine], bits[mine]))[0]])
+        out.append((int(gids[j]), float(risk[j]), int(hops[j])))
     return out
 
 
