@@ -14,95 +14,19 @@ exchange costs in host round trips, not what four GPUs would give.
 usage: python scripts/tiled_field_latency.py [--out PATH] [--reps N] [--workload c3|c2|small]
        -> PATH (default profiles/r23_tiled_field.json)
 """
-import json
-import os
-import sys
 import tempfile
-import threading
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "trg-planner_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402,F401  (first, as in tests/conftest.py: one HIP runtime for torch and the engine)
-import trg_planner  # noqa: E402
-from trg_planner import tiled  # noqa: E402
-import bench  # noqa: E402  (terrain_tile, WORKLOADS, MOUNTAIN: the benchmark's own cloud and parameters)
-import field_ref  # noqa: E402  (tests/: the compiled host Dijkstra)
+from tiled_cut import Cut, bench, summary, tiled  # (first: it sets the paths and loads torch before the engine)
+import field_ref  # (tests/: the compiled host Dijkstra)
 
-argv = sys.argv[1:]
-
-
-def option(name, default):
-    if name in argv:
-        i = argv.index(name)
-        v = argv[i + 1]
-        del argv[i:i + 2]
-        return v
-    return default
-
-
-out = os.path.abspath(option("--out", os.path.join(ROOT, "profiles", "r23_tiled_field.json")))
-reps = int(option("--reps", 15))
-workload = option("--workload", "c3")
-nx, ny, S, label = bench.WORKLOADS[workload]
-COLS = ROWS = 2
-R = COLS * ROWS
-SEED = 20250418
-
-engines, cores = [], []
-n_points = 0
-for t in range(R):
-    core, win = tiled.split_tile(t, COLS, ROWS, nx, ny, 11)
-    cloud = bench.terrain_tile(*win, seed=SEED)
-    n_points += int(cloud.shape[0])
-    e = trg_planner.Engine(**dict(bench.MOUNTAIN, sample_num=S))
-    e.set_sampler(7, 16)
-    e.set_tile(core, epoch=t)
-    e.set_global_map(cloud)
-    e.init_graph([0.5 * float(core[0] + core[2]), 0.5 * float(core[1] + core[3]), 0.0])
-    engines.append(e)
-    cores.append(core)
-    del cloud
-for t, e in enumerate(engines):
-    e.comm_join_local(f"tiled-field-latency-{os.getpid()}", R, t)
-
-
-def ranks(call):
-    """call(rank, engine) on every rank, one thread each -> (results, wall ms of the slowest)"""
-    res, err = [None] * R, [None] * R
-
-    def run(r):
-        try:
-            res[r] = call(r, engines[r])
-        except Exception as ex:  # noqa: BLE001
-            err[r] = ex
-
-    th = [threading.Thread(target=run, args=(r,)) for r in range(R)]
-    t0 = time.perf_counter()
-    for x in th:
-        x.start()
-    for x in th:
-        x.join()
-    wall = 1e3 * (time.perf_counter() - t0)
-    if any(err):
-        raise RuntimeError([str(x) for x in err if x])
-    return res, wall
-
-
-(nb_nc, ms_stitch) = ranks(lambda r, e: e.stitch_exchange(cores[r], COLS, ROWS))
-sizes = [e.graph_sizes("stitched") for e in engines]
-off = np.concatenate([[0], np.cumsum([v for v, _ in sizes])]).astype(np.int64)
-
-# sources: the node nearest the centre of each tile's core (global ids); field 0 alone is the m = 1 case
-sources = []
-for t, e in enumerate(engines):
-    xyz = e.node_xyz("global")
-    c = np.array([0.5 * (cores[t][0] + cores[t][2]), 0.5 * (cores[t][1] + cores[t][3])], np.float32)
-    sources.append(int(off[t]) + int(np.argmin(((xyz[:, :2] - c) ** 2).sum(1))))
+cut = Cut("field", "r23_tiled_field.json", reps=15)
+engines, ranks, reps = cut.engines, cut.ranks, cut.reps
+(nb_nc, ms_stitch) = cut.stitch()
+sizes, off = cut.sizes()
+sources = cut.centres(off)  # the node nearest the centre of each tile's core; field 0 alone is the m = 1 case
 
 
 def record(got, wall):
@@ -147,28 +71,20 @@ exact = bool(np.array_equal(f["cost"][0].view(np.uint32), host[1].view(np.uint32
              np.array_equal(f["hops"][0], host[2]) and np.array_equal(f["parent"][0], host[3]))
 
 
-def summary(recs):
-    s = {"exchanges": recs[-1]["exchanges"], "rounds_per_rank": recs[-1]["rounds_per_rank"],
-         "records_per_rank": recs[-1]["records_per_rank"],
-         "ms_wall_median": float(np.median([r["ms_wall"] for r in recs])),
-         "ms_wall_min": float(np.min([r["ms_wall"] for r in recs])),
-         "ms_wall_max": float(np.max([r["ms_wall"] for r in recs]))}
-    for key in ("ms_device_per_rank", "ms_total_per_rank"):
-        s[key + "_median"] = np.median(np.array([r[key] for r in recs]), axis=0).tolist()
+def per_exchange(s):
     s["ms_wall_per_exchange"] = s["ms_wall_median"] / max(1, s["exchanges"])
     return s
 
 
 info0 = [g["info"] for g in first_got]
 res = {
-    "workload": f"{label}: {nx}x{ny} lattice cut {COLS}x{ROWS} (split_tile, 1.1 m halo), {n_points} points in all",
-    "ranks": R, "transport": "in-process (trg_engine_comm_join_local): FOUR RANKS SHARE ONE GPU",
+    **cut.header(),
     "nodes_per_rank": [int(v) for v, _ in sizes], "edges_per_rank": [int(n) for _, n in sizes],
     "ghosts_per_rank": [int(i.ghosts) for i in info0], "border_nodes_per_rank": [int(i.border_nodes) for i in info0],
     "boundary_records_and_cross_edges": [int(x) for x in nb_nc[0]], "ms_stitch_exchange": ms_stitch,
     "sources": sources, "reps": reps,
     "first_call_m1_with_solve_graph_build": first,
-    "solve_m1": summary(samples["m1"]), "solve_m4": summary(samples["m4"]),
+    "solve_m1": per_exchange(summary(samples["m1"])), "solve_m4": per_exchange(summary(samples["m4"])),
     "host_alternative": {"ms_export_and_concat_once_per_stitch": ms_export,
                          "ms_dijkstra_per_field_median": float(np.median(host_ms)),
                          "ms_dijkstra_per_field_min": float(np.min(host_ms)), "V": int(G["V"]),
@@ -179,8 +95,4 @@ res = {
              "exchanges.  The four ranks' kernels and copies share one GPU and one host here, so the wall time is "
              "an upper bound of what an exchange costs in host round trips, not a multi-GPU figure."),
 }
-os.makedirs(os.path.dirname(out), exist_ok=True)
-json.dump(res, open(out, "w"), indent=1)
-print(json.dumps(res, indent=1))
-for e in engines:
-    e.close()
+cut.finish(res)

@@ -17,96 +17,21 @@ exchange costs in host round trips, not what four GPUs would give.  Over RCCL wi
 usage: python scripts/tiled_risk_latency.py [--out PATH] [--reps N] [--workload c3|c2|small]
        -> PATH (default profiles/r29_tiled_risk.json)
 """
-import json
-import os
-import sys
 import tempfile
-import threading
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "trg-planner_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402,F401  (first, as in tests/conftest.py: one HIP runtime for torch and the engine)
-import trg_planner  # noqa: E402
-from trg_planner import tiled  # noqa: E402
-import bench  # noqa: E402  (terrain_tile, WORKLOADS, MOUNTAIN: the benchmark's own cloud and parameters)
-import risk_ref  # noqa: E402  (tests/: the compiled host Dijkstra on the (risk, hops) key)
+from tiled_cut import R, Cut, summary, tiled  # (first: it sets the paths and loads torch before the engine)
+import risk_ref  # (tests/: the compiled host Dijkstra on the (risk, hops) key)
 
-argv = sys.argv[1:]
-
-
-def option(name, default):
-    if name in argv:
-        i = argv.index(name)
-        v = argv[i + 1]
-        del argv[i:i + 2]
-        return v
-    return default
-
-
-out = os.path.abspath(option("--out", os.path.join(ROOT, "profiles", "r29_tiled_risk.json")))
-reps = int(option("--reps", 15))
-workload = option("--workload", "c3")
-nx, ny, S, label = bench.WORKLOADS[workload]
-COLS = ROWS = 2
-R = COLS * ROWS
-SEED = 20250418
-
-engines, cores = [], []
-n_points = 0
-for t in range(R):
-    core, win = tiled.split_tile(t, COLS, ROWS, nx, ny, 11)
-    cloud = bench.terrain_tile(*win, seed=SEED)
-    n_points += int(cloud.shape[0])
-    e = trg_planner.Engine(**dict(bench.MOUNTAIN, sample_num=S))
-    e.set_sampler(7, 16)
-    e.set_tile(core, epoch=t)
-    e.set_global_map(cloud)
-    e.init_graph([0.5 * float(core[0] + core[2]), 0.5 * float(core[1] + core[3]), 0.0])
-    engines.append(e)
-    cores.append(core)
-    del cloud
-for t, e in enumerate(engines):
-    e.comm_join_local(f"tiled-risk-latency-{os.getpid()}", R, t)
-
-
-def ranks(call):
-    """call(rank, engine) on every rank, one thread each -> (results, wall ms of the slowest)"""
-    res, err = [None] * R, [None] * R
-
-    def run(r):
-        try:
-            res[r] = call(r, engines[r])
-        except Exception as ex:  # noqa: BLE001
-            err[r] = ex
-
-    th = [threading.Thread(target=run, args=(r,)) for r in range(R)]
-    t0 = time.perf_counter()
-    for x in th:
-        x.start()
-    for x in th:
-        x.join()
-    wall = 1e3 * (time.perf_counter() - t0)
-    if any(err):
-        raise RuntimeError([str(x) for x in err if x])
-    return res, wall
-
-
-(nb_nc, ms_stitch) = ranks(lambda r, e: e.stitch_exchange(cores[r], COLS, ROWS))
-sizes = [e.graph_sizes("stitched") for e in engines]
-off = np.concatenate([[0], np.cumsum([v for v, _ in sizes])]).astype(np.int64)
-
+cut = Cut("risk", "r29_tiled_risk.json", reps=15)
+engines, ranks, reps = cut.engines, cut.ranks, cut.reps
+(nb_nc, ms_stitch) = cut.stitch()
+sizes, off = cut.sizes()
 # per tile: the node nearest the centre of its core and the node a third of the way through its ids (global ids)
-centres, thirds = [], []
-for t, e in enumerate(engines):
-    xyz = e.node_xyz("global")
-    c = np.array([0.5 * (cores[t][0] + cores[t][2]), 0.5 * (cores[t][1] + cores[t][3])], np.float32)
-    centres.append(int(off[t]) + int(np.argmin(((xyz[:, :2] - c) ** 2).sum(1))))
-    thirds.append(int(off[t]) + sizes[t][0] // 3)
+centres = cut.centres(off)
+thirds = [int(off[t]) + sizes[t][0] // 3 for t in range(R)]
 start = centres[0]
 members = centres + thirds  # the set of 8
 goals = centres[1:] + thirds + [int(off[R]) - 1]  # the 8 goals
@@ -200,28 +125,16 @@ exact["routes_to_8_cost_is_risk_at_goal"] = bool(all(
     i.num_nodes == host["field_m1"][2][g] + 1 for g, (_, _, i) in zip(goals, joined)))
 
 
-def summary(recs):
-    s = {k: recs[-1][k] for k in recs[-1] if not k.startswith("ms_") and "ms_device" not in k}
-    s["ms_wall_median"] = float(np.median([r["ms_wall"] for r in recs]))
-    s["ms_wall_min"] = float(np.min([r["ms_wall"] for r in recs]))
-    s["ms_wall_max"] = float(np.max([r["ms_wall"] for r in recs]))
-    for key in [k for k in recs[-1] if "ms_device" in k]:
-        s[key + "_median"] = np.median(np.array([r[key] for r in recs]), axis=0).tolist()
-        s[key + "_min"] = np.min(np.array([r[key] for r in recs]), axis=0).tolist()
-    return s
-
-
 w = G["w"]
 res = {
-    "workload": f"{label}: {nx}x{ny} lattice cut {COLS}x{ROWS} (split_tile, 1.1 m halo), {n_points} points in all",
-    "ranks": R, "transport": "in-process (trg_engine_comm_join_local): FOUR RANKS SHARE ONE GPU",
+    **cut.header(),
     "nodes_per_rank": [int(v) for v, _ in sizes], "edges_per_rank": [int(n) for _, n in sizes],
     "ghosts_per_rank": [int(g["info"].ghosts) for g in last["field_m1", "risk"]],
     "border_nodes_per_rank": [int(g["info"].border_nodes) for g in last["field_m1", "risk"]],
     "boundary_records_and_cross_edges": [int(x) for x in nb_nc[0]], "ms_stitch_exchange": ms_stitch,
     "edge_weights_exactly_zero": float((w == 0).mean()), "start": start, "members": members, "goals": goals, "reps": reps,
     "first_calls_m1": {"cost_with_solve_graph_build": first["cost"], "risk_with_edge_risk_build": first["risk"]},
-    "shapes": {k: {name: summary(v) for name, v in by.items()} for k, by in samples.items()},
+    "shapes": {k: {name: summary(v, mins=True) for name, v in by.items()} for k, by in samples.items()},
     "host_way": {"ms_export_and_concat_once_per_stitch": ms_export,
                  "ms_risk_reference_median": {k: float(np.median(v)) for k, v in host_ms.items()},
                  "ms_risk_reference_min": {k: float(np.min(v)) for k, v in host_ms.items()},
@@ -233,8 +146,4 @@ res = {
              "exchange costs in host round trips, not a multi-GPU figure; over RCCL with more than one rank this has "
              "not run.  routes_to_8: the solve (without parents) and the two routes calls (lengths, then ids)."),
 }
-os.makedirs(os.path.dirname(out), exist_ok=True)
-json.dump(res, open(out, "w"), indent=1)
-print(json.dumps(res, indent=1))
-for e in engines:
-    e.close()
+cut.finish(res)

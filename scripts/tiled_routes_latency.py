@@ -16,88 +16,21 @@ usage: python scripts/tiled_routes_latency.py [--out PATH] [--reps N] [--workloa
        -> PATH (default profiles/r26_tiled_routes.json)
 """
 import json
-import os
-import sys
-import threading
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "trg-planner_amd"))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402,F401  (first, as in tests/conftest.py: one HIP runtime for torch and the engine)
-import trg_planner  # noqa: E402
-from trg_planner import tiled  # noqa: E402
-import bench  # noqa: E402  (terrain_tile, WORKLOADS, MOUNTAIN: the benchmark's own cloud and parameters)
+from tiled_cut import R, Cut, bench, tiled  # (first: it sets the paths and loads torch before the engine)
 
-argv = sys.argv[1:]
-
-
-def option(name, default):
-    if name in argv:
-        i = argv.index(name)
-        v = argv[i + 1]
-        del argv[i:i + 2]
-        return v
-    return default
-
-
-out = os.path.abspath(option("--out", os.path.join(ROOT, "profiles", "r26_tiled_routes.json")))
-reps = int(option("--reps", 9))
-workload = option("--workload", "c3")
-nx, ny, S, label = bench.WORKLOADS[workload]
-COLS = ROWS = 2
-R = COLS * ROWS
-SEED = 20250418
 F32 = np.float32
-
-engines, cores = [], []
-n_points = 0
-for t in range(R):
-    core, win = tiled.split_tile(t, COLS, ROWS, nx, ny, 11)
-    cloud = bench.terrain_tile(*win, seed=SEED)
-    n_points += int(cloud.shape[0])
-    e = trg_planner.Engine(**dict(bench.MOUNTAIN, sample_num=S))
-    e.set_sampler(7, 16)
-    e.set_tile(core, epoch=t)
-    e.set_global_map(cloud)
-    e.init_graph([0.5 * float(core[0] + core[2]), 0.5 * float(core[1] + core[3]), 0.0])
-    engines.append(e)
-    cores.append(core)
-    del cloud
-for t, e in enumerate(engines):
-    e.comm_join_local(f"tiled-routes-latency-{os.getpid()}", R, t)
-
-
-def ranks(call):
-    """call(rank, engine) on every rank, one thread each -> (results, wall ms of the slowest)"""
-    res, err = [None] * R, [None] * R
-
-    def run(r):
-        try:
-            res[r] = call(r, engines[r])
-        except Exception as ex:  # noqa: BLE001
-            err[r] = ex
-
-    th = [threading.Thread(target=run, args=(r,)) for r in range(R)]
-    t0 = time.perf_counter()
-    for x in th:
-        x.start()
-    for x in th:
-        x.join()
-    wall = 1e3 * (time.perf_counter() - t0)
-    if any(err):
-        raise RuntimeError([str(x) for x in err if x])
-    return res, wall
-
-
-(nb_nc, ms_stitch) = ranks(lambda r, e: e.stitch_exchange(cores[r], COLS, ROWS))
+cut = Cut("routes", "r26_tiled_routes.json", reps=9)
+engines, ranks, reps = cut.engines, cut.ranks, cut.reps
+(nb_nc, ms_stitch) = cut.stitch()
 t0 = time.perf_counter()
 G = tiled.concat_stitched([e.graph("stitched") for e in engines])  # the old way's rows, for the host fold
 ms_export = 1e3 * (time.perf_counter() - t0)
 off = G["offsets"]
-ranks(lambda r, e: e.stitch_exchange(cores[r], COLS, ROWS))  # (rows in HBM again)
+cut.stitch()  # (rows in HBM again)
 rng = np.random.default_rng(26)
 ok = [int(off[t]) + np.flatnonzero((G["state"][off[t]:off[t + 1]] != -1) & (np.diff(G["rowptr"])[off[t]:off[t + 1]] > 0))
       for t in range(R)]
@@ -166,8 +99,7 @@ for n in (1, 8, 64):
     print(f"targets_{n}", json.dumps(cases[f"targets_{n}"]), flush=True)
 
 res = {
-    "workload": f"{label}: {nx}x{ny} lattice cut {COLS}x{ROWS} (split_tile, 1.1 m halo), {n_points} points in all",
-    "ranks": R, "transport": "in-process (trg_engine_comm_join_local): FOUR RANKS SHARE ONE GPU",
+    **cut.header(),
     "nodes_per_rank": [int(off[t + 1] - off[t]) for t in range(R)], "parents_per_field": int(off[-1]),
     "ms_stitch_exchange": ms_stitch, "ms_export_of_the_rows_for_the_host_fold": ms_export, "reps": reps,
     "ms_solve_with_parent_download_median": float(np.median(solve_ms[True])),
@@ -180,8 +112,4 @@ res = {
              "exchanges cost on one shared card, not what four GPUs would give.  Over RCCL with more than one rank it "
              "has not run."),
 }
-os.makedirs(os.path.dirname(out), exist_ok=True)
-json.dump(res, open(out, "w"), indent=1)
-print(json.dumps(res, indent=1))
-for e in engines:
-    e.close()
+cut.finish(res)

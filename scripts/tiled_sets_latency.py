@@ -16,84 +16,16 @@ usage: python scripts/tiled_sets_latency.py [--out PATH] [--reps N] [--workload 
        -> PATH (default profiles/r24_tiled_sets.json)
 """
 import json
-import os
-import sys
-import threading
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "trg-planner_amd"))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402,F401  (first, as in tests/conftest.py: one HIP runtime for torch and the engine)
-import trg_planner  # noqa: E402
-from trg_planner import tiled  # noqa: E402
-import bench  # noqa: E402  (terrain_tile, WORKLOADS, MOUNTAIN: the benchmark's own cloud and parameters)
+from tiled_cut import Cut  # (first: it sets the paths and loads torch before the engine)
 
-argv = sys.argv[1:]
-
-
-def option(name, default):
-    if name in argv:
-        i = argv.index(name)
-        v = argv[i + 1]
-        del argv[i:i + 2]
-        return v
-    return default
-
-
-out = os.path.abspath(option("--out", os.path.join(ROOT, "profiles", "r24_tiled_sets.json")))
-reps = int(option("--reps", 9))
-workload = option("--workload", "c3")
-nx, ny, S, label = bench.WORKLOADS[workload]
-COLS = ROWS = 2
-R = COLS * ROWS
-SEED = 20250418
-
-engines, cores = [], []
-n_points = 0
-for t in range(R):
-    core, win = tiled.split_tile(t, COLS, ROWS, nx, ny, 11)
-    cloud = bench.terrain_tile(*win, seed=SEED)
-    n_points += int(cloud.shape[0])
-    e = trg_planner.Engine(**dict(bench.MOUNTAIN, sample_num=S))
-    e.set_sampler(7, 16)
-    e.set_tile(core, epoch=t)
-    e.set_global_map(cloud)
-    e.init_graph([0.5 * float(core[0] + core[2]), 0.5 * float(core[1] + core[3]), 0.0])
-    engines.append(e)
-    cores.append(core)
-    del cloud
-for t, e in enumerate(engines):
-    e.comm_join_local(f"tiled-sets-latency-{os.getpid()}", R, t)
-
-
-def ranks(call):
-    """call(rank, engine) on every rank, one thread each -> (results, wall ms of the slowest)"""
-    res, err = [None] * R, [None] * R
-
-    def run(r):
-        try:
-            res[r] = call(r, engines[r])
-        except Exception as ex:  # noqa: BLE001
-            err[r] = ex
-
-    th = [threading.Thread(target=run, args=(r,)) for r in range(R)]
-    t0 = time.perf_counter()
-    for x in th:
-        x.start()
-    for x in th:
-        x.join()
-    wall = 1e3 * (time.perf_counter() - t0)
-    if any(err):
-        raise RuntimeError([str(x) for x in err if x])
-    return res, wall
-
-
-(nb_nc, ms_stitch) = ranks(lambda r, e: e.stitch_exchange(cores[r], COLS, ROWS))
-sizes = [e.graph_sizes("stitched") for e in engines]
-off = np.concatenate([[0], np.cumsum([v for v, _ in sizes])]).astype(np.int64)
+cut = Cut("sets", "r24_tiled_sets.json", reps=9)
+engines, ranks, reps = cut.engines, cut.ranks, cut.reps
+(nb_nc, ms_stitch) = cut.stitch()
+sizes, off = cut.sizes()
 
 # members: per tile, valid nodes spread over the core (global ids), taken tile after tile
 rng = np.random.default_rng(24)
@@ -102,7 +34,7 @@ for t, e in enumerate(engines):
     g = e.graph("global")
     ok = np.flatnonzero((g.state != -1) & (np.diff(g.rowptr) > 0))
     per_tile.append((int(off[t]) + rng.choice(ok, 16, replace=False)).astype(np.int32))
-ranks(lambda r, e: e.stitch_exchange(cores[r], COLS, ROWS))  # (the exports took nothing of the stitch: rows in HBM again)
+cut.stitch()  # (the exports took nothing of the stitch: rows in HBM again)
 members = {8: np.concatenate([p[:2] for p in per_tile]), 64: np.concatenate(per_tile)}
 starts = {k: rng.uniform(0.0, 5.0, k).astype(np.float32) for k in members}
 
@@ -163,8 +95,7 @@ for k in (8, 64):
         print(name, json.dumps(cases[name]), flush=True)
 
 res = {
-    "workload": f"{label}: {nx}x{ny} lattice cut {COLS}x{ROWS} (split_tile, 1.1 m halo), {n_points} points in all",
-    "ranks": R, "transport": "in-process (trg_engine_comm_join_local): FOUR RANKS SHARE ONE GPU",
+    **cut.header(),
     "nodes_per_rank": [int(v) for v, _ in sizes], "edges_per_rank": [int(n) for _, n in sizes],
     "ms_stitch_exchange": ms_stitch, "reps": reps, "cases": cases,
     "note": ("ms_wall = host clock around the collective call on all four threads (the slowest rank), downloads of "
@@ -172,8 +103,4 @@ res = {
              "ranks' kernels and copies share one GPU and one host here: this says what the exchanges cost on one "
              "shared card, not what four GPUs would give.  Over RCCL with more than one rank it has not run."),
 }
-os.makedirs(os.path.dirname(out), exist_ok=True)
-json.dump(res, open(out, "w"), indent=1)
-print(json.dumps(res, indent=1))
-for e in engines:
-    e.close()
+cut.finish(res)

@@ -4,124 +4,21 @@ cost bits, hops and parents (global ids) must equal the compiled host Dijkstra (
 concatenation of the rows the engines export.  Built tilings, tilings without cross edges, crafted graphs (tile
 graphs through load_json, crafted cross edges through stitch_assemble), the failure announcement, the refusals, and
 the Python helpers."""
-import itertools
-import threading
-import time
-
 import numpy as np
 import pytest
 
 import field_graphs as fg
-import field_ref
 import stitch_cases as sc
-import tiled_field_ref as tr
-from field_support import MOUNTAIN, ref  # noqa: F401  (ref: the fixture)
+import tiled_ref as tr
+from field_support import MOUNTAIN
+from tiled_support import (INVALID_1, RING, assert_fields, close, craft, exported, join_group, pick_sources, reference,
+                           run_ranks, solve, stitch, tie_lattice)
+from tiled_support import ref, tiled  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 INVALID_ARG, DEVICE = 1, 4
-JOIN_SECONDS = 60
 SF = MOUNTAIN["safety_factor"]
-_group = itertools.count()
 _solved = {}  # tiling -> (G, sources, fields of the m = 3 batch): shared by the tests that only read them
-
-
-@pytest.fixture(scope="module")
-def tiled():
-    from trg_planner import tiled as t
-    return t
-
-
-def join_group(engines, tag):
-    name = f"test-tiled-field-{tag}-{next(_group)}"
-    for r, e in enumerate(engines):
-        e.comm_join_local(name, len(engines), r)
-
-
-def run_ranks(engines, call):
-    """call(rank, engine) on every rank, each from its own thread: [result | TrgError] per rank, wall seconds"""
-    from trg_planner._engine import TrgError
-    out = [None] * len(engines)
-
-    def rank(r):
-        try:
-            out[r] = call(r, engines[r])
-        except TrgError as ex:
-            out[r] = ex
-
-    threads = [threading.Thread(target=rank, args=(r,), daemon=True) for r in range(len(engines))]
-    t0 = time.monotonic()
-    for th in threads:
-        th.start()
-    for th in threads:
-        th.join(max(0.0, JOIN_SECONDS - (time.monotonic() - t0)))
-    alive = [r for r, th in enumerate(threads) if th.is_alive()]
-    assert not alive, f"ranks {alive} did not return within {JOIN_SECONDS} s"
-    return out, time.monotonic() - t0
-
-
-def solve(engines, sources, parent=True):
-    from trg_planner._engine import TrgError
-    got, secs = run_ranks(engines, lambda r, e: e.tiled_cost_fields(sources, parent=parent))
-    bad = [g for g in got if isinstance(g, TrgError)]
-    assert not bad, [str(b) for b in bad]
-    return got, secs
-
-
-def exported(tiled, engines):
-    """The global graph from the rows the engines export (this takes the rows off the device: a solve after it builds
-    its solve graph, if it has none yet, from the host rows)."""
-    return tiled.concat_stitched([e.graph("stitched") for e in engines])
-
-
-def reference(lib, G, sources):
-    out = []
-    for s in sources:
-        st, c, h, p = field_ref.field(lib, G["rowptr"], G["col"], G["w"], G["dist"], G["state"], SF, int(s))
-        assert st == 0, st
-        out.append((c, h, p))
-    return tuple(np.stack([o[i] for o in out]) for i in range(3))
-
-
-def assert_fields(at, tiled, got, G, want):
-    """every rank's part against the reference's rows of that rank; -> the concatenated fields"""
-    off = G["offsets"]
-    for t, g in enumerate(got):
-        a, b = int(off[t]), int(off[t + 1])
-        assert g["offset"] == a and g["cost"].shape == (want[0].shape[0], b - a), (at, t, g["cost"].shape)
-        for name, w in zip(("cost", "hops", "parent"), want):
-            x, y = g[name], w[:, a:b]
-            if name == "cost":
-                x, y = x.view(np.uint32), np.ascontiguousarray(y).view(np.uint32)
-            bad = np.argwhere(x != y)
-            assert bad.shape[0] == 0, (f"{at}: rank {t}: {bad.shape[0]} {name} differ, first at field {bad[0][0]}, "
-                                       f"global id {a + bad[0][1]}: {g[name][tuple(bad[0])]!r} != {w[bad[0][0], a + bad[0][1]]!r}")
-    return tiled.concat_fields(got)
-
-
-def stitch(engines, lay):
-    got, _ = run_ranks(engines, lambda r, e: e.stitch_exchange(lay.cores[r], lay.cols, lay.rows))
-    assert all(isinstance(g, tuple) for g in got), got
-    return got[0]
-
-
-def pick_sources(G, tile=0):
-    """(deep inside `tile`, a border node, a node with cross edges to two other tiles or else another border node)"""
-    off = G["offsets"]
-    rows = np.repeat(np.arange(G["V"]), np.diff(G["rowptr"]))
-    tile_of = np.searchsorted(off, np.arange(G["V"]), side="right") - 1
-    cross = tile_of[rows] != tile_of[G["col"]]
-    valid = G["state"] != fg.INVALID
-    reach = {}
-    for u, v in zip(rows[cross].tolist(), G["col"][cross].tolist()):
-        reach.setdefault(u, set()).add(int(tile_of[v]))
-    multi = sorted(u for u in reach if valid[u] and len(reach[u]) >= 2)
-    border = sorted(u for u in reach if valid[u] and len(reach[u]) == 1)
-    a, b = int(off[tile]), int(off[tile + 1])
-    mine = np.arange(a, b)[valid[a:b] & (np.diff(G["rowptr"])[a:b] > 0)]
-    centre = G["xyz"][a:b, :2].mean(0)
-    deep = int(mine[np.argmin(((G["xyz"][mine, :2] - centre) ** 2).sum(1))])
-    assert deep not in reach
-    return [deep, border[0], multi[0] if multi else border[len(border) // 2]], bool(multi)
 
 
 # ---- 1. built tilings -----------------------------------------------------------------------------------------------
@@ -142,7 +39,7 @@ def solved(oa, synth, tiled, lib, name):
         infos = [g["info"] for g in got]
         print(name, "source", s, "exchanges", infos[0].exchanges, "rounds", [i.rounds for i in infos], "records",
               [i.records_sent for i in infos], "ghosts", [i.ghosts for i in infos], f"{secs * 1e3:.1f} ms")
-        f = assert_fields(f"{name} m=1 source {s}", tiled, got, G, tuple(w[k:k + 1] for w in want))
+        f = assert_fields(f"{name} m=1 source {s}", got, G, tuple(w[k:k + 1] for w in want))
         t_src = int(np.searchsorted(off, s, side="right") - 1)
         others = np.ones(G["V"], bool)
         others[int(off[t_src]):int(off[t_src + 1])] = False
@@ -151,7 +48,7 @@ def solved(oa, synth, tiled, lib, name):
         assert infos[0].exchanges >= 4  # (news crossed a seam in both passes)
     for call in range(2):  # one batch of m = 3, twice
         got, secs = solve(engines, sources)
-        f = assert_fields(f"{name} m=3 call {call}", tiled, got, G, want)
+        f = assert_fields(f"{name} m=3 call {call}", got, G, want)
     _solved[name] = (G, sources, f)
     for e in engines:
         e.comm_destroy()
@@ -174,7 +71,7 @@ def test_no_cross_edges(oa, synth, tiled, ref, name):
     off = G["offsets"]
     src = int(np.flatnonzero((G["state"][:off[1]] != fg.INVALID) & (np.diff(G["rowptr"])[:off[1]] > 0))[0])
     got, _ = solve(engines, [src])
-    f = assert_fields(name, tiled, got, G, reference(ref, G, [src]))
+    f = assert_fields(name, got, G, reference(ref, G, [src]))
     assert (f["hops"][0][off[1]:] == -1).all() and (f["hops"][0][:off[1]] >= 0).sum() > 10
     assert [g["info"].ghosts for g in got] == [0, 0, 0] and [g["info"].exchanges for g in got] == [2, 2, 2]
     for e in engines:
@@ -182,59 +79,18 @@ def test_no_cross_edges(oa, synth, tiled, ref, name):
 
 
 # ---- 3. crafted graphs ----------------------------------------------------------------------------------------------
-def craft(tmp_path, sizes, edges, state=None, tag="craft"):
-    """Engines of len(sizes) tiles holding the symmetric global graph `edges` = [(global a, global b, w, dist)] (no
-    pair twice): a tile's own edges through load_json, the others as cross-edge records through stitch_assemble,
-    every engine a rank of a fresh in-process group.  -> engines"""
-    import torch
-    import trg_planner
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-    V = int(off[-1])
-    state = np.zeros(V, np.int32) if state is None else np.asarray(state, np.int32)
-    tile_of = np.searchsorted(off, np.arange(V), side="right") - 1
-    assert len({(min(a, b), max(a, b)) for a, b, _, _ in edges}) == len(edges)
-    rec = np.array([(tile_of[a], a - off[tile_of[a]], tile_of[b], b - off[tile_of[b]]) if tile_of[a] < tile_of[b] else
-                    (tile_of[b], b - off[tile_of[b]], tile_of[a], a - off[tile_of[a]])
-                    for a, b, _, _ in edges if tile_of[a] != tile_of[b]], np.int32).reshape(-1, 4)
-    wd = np.array([(w, d) for a, b, w, d in edges if tile_of[a] != tile_of[b]], np.float32).reshape(-1, 2)
-    cross = np.concatenate([rec, wd.view(np.int32)], 1)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    cross_t = torch.from_numpy(np.ascontiguousarray(cross)).to(dev) if cross.shape[0] else None
-    torch.cuda.synchronize()
-    engines = []
-    for t, n in enumerate(sizes):
-        own = [(a - off[t], b - off[t], w, d) for a, b, w, d in edges if tile_of[a] == t and tile_of[b] == t]
-        src = [a for a, b, _, _ in own] + [b for a, b, _, _ in own]
-        dst = [b for a, b, _, _ in own] + [a for a, b, _, _ in own]
-        g = fg.from_edges(n, np.array(src, np.int64), np.array(dst, np.int64), [w for _, _, w, _ in own] * 2,
-                          [d for _, _, _, d in own] * 2, state=state[off[t]:off[t + 1]])
-        p = tmp_path / f"{tag}{t}.json"
-        fg.write_json(p, g)
-        e = trg_planner.Engine(**MOUNTAIN)
-        e.load_json(str(p))
-        e.stitch_assemble(t, len(sizes), off, cross_t.data_ptr() if cross_t is not None else None, int(cross.shape[0]))
-        engines.append(e)
-    join_group(engines, tag)
-    return engines
-
-
 def crafted(tmp_path, tiled, lib, sizes, edges, sources, state=None, tag="craft", batch=True):
     """craft, export, solve (each source alone, then all in one batch), compare -> (engines, G, want, last results)"""
-    engines = craft(tmp_path, sizes, edges, state, tag)
+    engines, _ = craft(tmp_path, sizes, edges, state, tag)
     G = exported(tiled, engines)
     want = reference(lib, G, sources)
     got = None
     for k, s in enumerate(sources if batch else []):
         got, _ = solve(engines, [s])
-        assert_fields(f"{tag} source {s}", tiled, got, G, tuple(w[k:k + 1] for w in want))
+        assert_fields(f"{tag} source {s}", got, G, tuple(w[k:k + 1] for w in want))
     got, _ = solve(engines, sources)
-    assert_fields(f"{tag} batch", tiled, got, G, want)
+    assert_fields(f"{tag} batch", got, G, want)
     return engines, G, want, got
-
-
-def close(engines):
-    for e in engines:
-        e.close()
 
 
 def test_chain_alternating_between_two_tiles(tmp_path, tiled, ref):
@@ -250,23 +106,6 @@ def test_chain_alternating_between_two_tiles(tmp_path, tiled, ref):
     # each rank published every one of its nodes, one per exchange, and none twice per pass
     assert [g["info"].records_sent for g in got] == [64, 64] and [g["info"].ghosts for g in got] == [32, 32]
     close(engines)
-
-
-def tie_lattice():
-    """unit costs on a 12 x 9 lattice whose cells go to three tiles in diagonal stripes -> (sizes, edges, sources)"""
-    nx, ny, R = 12, 9, 3
-    tile = lambda x, y: (x // 2 + y) % R  # noqa: E731
-    cells = sorted(((tile(x, y), y, x) for x in range(nx) for y in range(ny)))
-    gid = {(x, y): i for i, (_, y, x) in enumerate(cells)}
-    sizes = [sum(1 for c in cells if c[0] == t) for t in range(R)]
-    edges = []
-    for x in range(nx):
-        for y in range(ny):
-            if x + 1 < nx:
-                edges.append((gid[x, y], gid[x + 1, y], 0.0, 1.0))
-            if y + 1 < ny:
-                edges.append((gid[x, y], gid[x, y + 1], 0.0, 1.0))
-    return sizes, edges, [gid[0, 0], gid[nx - 1, ny - 1], gid[5, 4]]
 
 
 def test_lattice_of_exact_ties_across_seams(tmp_path, tiled, ref):
@@ -315,10 +154,6 @@ def test_zero_cost_cross_edges_and_saturation(tmp_path, tiled, ref):
     close(engines)
 
 
-INVALID_1 = [(0, 1, 0.0, 0.5), (1, 4, 0.0, 0.5), (1, 5, 0.1, 0.5), (0, 2, 0.2, 0.5), (2, 5, 0.0, 0.5), (5, 4, 0.3, 0.5),
-             (4, 6, 0.0, 0.5), (6, 3, 0.0, 0.5), (3, 1, 0.0, 0.5), (6, 7, 0.0, 0.5)]  # in [4, 4]; node 1 is Invalid
-
-
 def test_invalid_border_node(tmp_path, tiled, ref):
     """(e) an Invalid node with cross edges: no walk enters it from either side."""
     state = np.zeros(8, np.int32)
@@ -343,12 +178,9 @@ def test_long_ghost_row_and_publish_across_blocks(tmp_path, tiled, ref):
 
 
 # ---- 4. failure and refusals ----------------------------------------------------------------------------------------
-RING = [(i, (i + 1) % 12, 0.1, 0.5) for i in range(12)]
-
-
 def test_a_rank_without_current_rows_is_announced(tmp_path, tiled, ref):
     from trg_planner._engine import TrgError
-    engines = craft(tmp_path, [6, 6], RING, tag="void")
+    engines, _ = craft(tmp_path, [6, 6], RING, tag="void")
     engines[1].load_json(str(tmp_path / "void1.json"))  # its graph changed after the stitch: its rows are void
     got, secs = run_ranks(engines, lambda r, e: e.tiled_cost_fields([0]))
     assert isinstance(got[1], TrgError) and got[1].status == INVALID_ARG, got[1]
@@ -362,7 +194,7 @@ def test_a_rank_without_current_rows_is_announced(tmp_path, tiled, ref):
 def test_refusals_leave_the_group_usable(tmp_path, tiled, ref):
     import trg_planner
     from trg_planner._engine import TrgError
-    engines = craft(tmp_path, [6, 6], RING, tag="refuse")
+    engines, _ = craft(tmp_path, [6, 6], RING, tag="refuse")
     G = exported(tiled, engines)
     for sources, text in (([], "m must be in [1, 64]"), ([0] * 65, "m must be in [1, 64]"), ([12], "is outside [0, 12)"),
                           ([3, -1], "is outside [0, 12)")):
@@ -379,7 +211,7 @@ def test_refusals_leave_the_group_usable(tmp_path, tiled, ref):
     lone.close()
     # no collective was entered: the group is whole
     got, _ = solve(engines, [0, 7])
-    assert_fields("after the refusals", tiled, got, G, reference(ref, G, [0, 7]))
+    assert_fields("after the refusals", got, G, reference(ref, G, [0, 7]))
     assert engines[1].global_ids() == (6, 6)
     got, _ = solve(engines, [7], parent=False)
     assert got[0]["parent"] is None and tiled.concat_fields(got)["parent"] is None
@@ -406,7 +238,7 @@ def test_sources_equal_sets_of_one_with_their_counters(tmp_path, case):
         state, S, twins = None, sources + sources[:1], (0, 3)
     else:
         sizes, edges, state, S, twins = [4, 4], INVALID_1, invalid_1_state(), [0, 7, 1, 1], (2, 3)
-    engines = craft(tmp_path, sizes, edges, state, tag="one-" + case)
+    engines, _ = craft(tmp_path, sizes, edges, state, tag="one-" + case)
     one, _ = solve(engines, S)
     sets, _ = run_ranks(engines, lambda r, e: e.tiled_cost_fields_from([[s] for s in S]))
     assert not [g for g in sets if isinstance(g, TrgError)], [str(g) for g in sets]
@@ -430,10 +262,10 @@ def test_sources_equal_sets_of_one_with_their_counters(tmp_path, case):
 def test_a_tile_without_nodes_between_two_with_cross_edges(tmp_path, tiled, ref):
     """Sizes [6, 0, 6]: the middle rank has neither nodes nor entries; it only takes part in the exchanges."""
     S = [0, 8, 5]
-    engines = craft(tmp_path, [6, 0, 6], RING, tag="hollow")
+    engines, _ = craft(tmp_path, [6, 0, 6], RING, tag="hollow")
     G = exported(tiled, engines)
     got, _ = solve(engines, S)
-    assert_fields("hollow", tiled, got, G, reference(ref, G, S))  # (the empty rank's part: m x 0 arrays)
+    assert_fields("hollow", got, G, reference(ref, G, S))  # (the empty rank's part: m x 0 arrays)
     assert got[1]["cost"].shape == (3, 0) and got[1]["hops"].shape == (3, 0) and got[1]["parent"].shape == (3, 0)
     exchanges = [g["info"].exchanges for g in got]
     assert exchanges == [exchanges[0]] * 3 and exchanges[0] >= 4, exchanges

@@ -6,6 +6,7 @@ rank's risk bits, hops, parents (global ids) and owners must equal the compiled 
 ghost row, a tile without nodes), sets, objectives alternating on one stitch, the failure announcement, the refusals
 and the Python helpers.  Routes: tests/test_gpu_tiled_risk_routes.py."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -14,86 +15,21 @@ import field_graphs as fg
 import risk_graphs as rg
 import risk_ref
 import stitch_cases as sc
-import tiled_risk_ref as trr
+import tiled_ref as trr
+import tiled_support
 from field_support import MOUNTAIN
-from test_gpu_tiled_field import (INVALID_1, RING, exported, join_group, pick_sources, run_ranks, stitch,
-                                  tie_lattice)
-from test_gpu_tiled_routes import craft as craft_with
+from tiled_support import (INVALID_1, RING, close, exported, join_group, level_lattice, ok, pick_sources, run_ranks,
+                           stitch, tie_lattice)
+from tiled_support import risk_craft as craft, risk_reference as reference
+from tiled_support import risk_solve as solve, risk_solve_sets as solve_sets
+from tiled_support import cost_ref, risk_reference_lib, tiled  # noqa: F401  (fixtures; risk_reference_lib is `ref`)
 
 pytestmark = pytest.mark.gpu
 INVALID_ARG, DEVICE = 1, 4
 F32 = np.float32
 FRONTIER = 1
 PEER = "another rank reported a failure"
-
-
-@pytest.fixture(scope="module")
-def tiled():
-    from trg_planner import tiled as t
-    return t
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return risk_ref.compile_reference(tmp_path_factory.mktemp("tiled_risk"))
-
-
-@pytest.fixture(scope="module")
-def cost_ref(tmp_path_factory):
-    import field_ref
-    return field_ref.compile_reference(tmp_path_factory.mktemp("tiled_risk_cost"))
-
-
-def craft(tmp_path, sizes, edges, state=None, tag="craft", extra=()):
-    return craft_with(tmp_path, sizes, edges, state=state, tag="risk-" + tag, extra=extra)[0]
-
-
-def close(engines):
-    for e in engines:
-        e.close()
-
-
-def ok(got):
-    from trg_planner._engine import TrgError
-    bad = [g for g in got if isinstance(g, TrgError)]
-    assert not bad, [str(b) for b in bad]
-    return got
-
-
-def solve(engines, sources, parent=True):
-    return ok(run_ranks(engines, lambda r, e: e.tiled_risk_fields(sources, parent=parent))[0])
-
-
-def solve_sets(engines, sets, targets=None, full=True, parent=True):
-    return ok(run_ranks(engines, lambda r, e: e.tiled_risk_fields_from(
-        sets, targets=None if targets is None else targets[r], full=full, parent=parent))[0])
-
-
-def reference(lib, G, member_sets):
-    """(risk, hops, parent), each len(member_sets) x V: the compiled reference from a node or a set of nodes"""
-    out = []
-    for members in member_sets:
-        st, r, h, p = risk_ref.risk_field(lib, G["rowptr"], G["col"], G["w"], G["state"], members)
-        assert st == 0, st
-        out.append((r, h, p))
-    return tuple(np.stack([o[i] for o in out]) for i in range(3))
-
-
-def assert_fields(at, got, G, want, names=("risk", "hops", "parent")):
-    """every rank's part against the reference's columns of that rank"""
-    off = G["offsets"]
-    for t, g in enumerate(got):
-        a, b = int(off[t]), int(off[t + 1])
-        assert g["offset"] == a and g["risk"].shape == (want[0].shape[0], b - a), (at, t, g["risk"].shape)
-        for name, w in zip(("risk", "hops", "parent"), want):
-            if name not in names:
-                continue
-            x, y = g[name], np.ascontiguousarray(w[:, a:b])
-            if name == "risk":
-                x, y = x.view(np.uint32), y.view(np.uint32)
-            bad = np.argwhere(x != y)
-            assert bad.shape[0] == 0, (f"{at}: rank {t}: {bad.shape[0]} {name} differ, first at field {bad[0][0]}, "
-                                       f"global id {a + bad[0][1]}: {g[name][tuple(bad[0])]!r} != {w[bad[0][0], a + bad[0][1]]!r}")
+assert_fields = functools.partial(tiled_support.assert_fields, names=("risk", "hops", "parent"))
 
 
 def crafted(tmp_path, tiled, lib, sizes, edges, sources, state=None, tag="craft", extra=(), batch=True):
@@ -285,12 +221,6 @@ def test_a_tile_without_nodes_between_two_with_cross_edges(tmp_path, tiled, ref)
 
 
 # ---- 11. sets ---------------------------------------------------------------------------------------------------------
-def level_lattice():
-    sizes, edges, sources = tie_lattice()
-    levels = rg.LEVELS.tolist()
-    return sizes, [(a, b, levels[(3 * a + 5 * b) % 5], d) for a, b, _, d in edges], sources
-
-
 def assert_sets(at, got, G, lib, sets, targets=None):
     want = reference(lib, G, sets)
     assert_fields(at, got, G, want)
@@ -439,7 +369,7 @@ def test_a_bad_weight_on_one_rank_is_announced(tmp_path, tiled, ref, cost_ref, n
     assert isinstance(got[0], TrgError) and got[0].status == DEVICE and PEER in str(got[0]) and secs < 10.0, got[0]
     # the group is whole: with the weight mended on that rank it solves both objectives
     import field_ref
-    mended = craft_with(tmp_path, [6, 6], good + [(10, 11, 0.3, 0.5)], state=state, tag="risk-bad-" + name)
+    mended = tiled_support.craft(tmp_path, [6, 6], good + [(10, 11, 0.3, 0.5)], state=state, tag="risk-bad-" + name)
     close(mended[0])  # (only its files are wanted: rank 1 loads the mended tile and assembles its rows again)
     mended[1](1, engines[1])
     G = exported(tiled, engines)

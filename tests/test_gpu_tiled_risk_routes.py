@@ -13,10 +13,12 @@ import route_ref
 import stitch_cases as sc
 import tiled_route_ref as trr
 from field_keys import fold_max, relaxable, risk_values
-from test_gpu_tiled_field import exported, join_group, pick_sources, run_ranks, stitch
-from test_gpu_tiled_risk import close, craft, level_lattice, ok, reference, solve, solve_sets
-from test_gpu_tiled_risk import ref, tiled  # noqa: F401  (fixtures)
-from test_gpu_tiled_routes import assert_routes, call_routes, crossing_counts
+from tiled_support import (SF, assert_routes, call_routes, close, crossing_counts, exported, join_group, level_lattice,
+                           ok, pick_sources, run_ranks, stitch)
+from tiled_support import risk_craft as craft, risk_reference as reference
+from tiled_support import risk_solve as solve, risk_solve_sets as solve_sets
+from tiled_support import risk_reference_lib, tiled  # noqa: F401  (fixtures; risk_reference_lib is `ref`)
+from tiled_support import want_routes as cost_routes
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -107,7 +109,6 @@ def duplicates_across_a_seam():
 
 def test_cost_tight_and_risk_tight_edges_differ(tmp_path, tiled, ref):
     import field_ref
-    from test_gpu_tiled_routes import SF, want_routes as cost_routes
     sizes, edges, extra = duplicates_across_a_seam()
     engines = craft(tmp_path, sizes, edges, tag="routes-dup", extra=extra)
     G = exported(tiled, engines)

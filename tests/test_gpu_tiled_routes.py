@@ -13,140 +13,15 @@ import pytest
 import field_graphs as fg
 import stitch_cases as sc
 import tiled_route_ref as trr
-from field_support import MOUNTAIN, ref  # noqa: F401  (ref: the fixture)
-from test_gpu_tiled_field import (INVALID_1, RING, exported, join_group, pick_sources, reference, run_ranks, solve, stitch,
-                                  tie_lattice)
-from test_gpu_tiled_sets import host_fields, solve_sets
+from field_support import MOUNTAIN, bits
+from tiled_support import (INVALID_1, RING, assert_routes, call_routes, close, craft, crossing_counts, exported,
+                           host_fields, join_group, most_crossings, pick_sources, reference, run_ranks, solve,
+                           solve_sets, stitch, tie_lattice, want_routes)
+from tiled_support import ref, tiled  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 INVALID_ARG, DEVICE = 1, 4
-SF = MOUNTAIN["safety_factor"]
 F32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def tiled():
-    from trg_planner import tiled as t
-    return t
-
-
-def bits(x):
-    return np.asarray(x, F32).reshape(-1).view(np.uint32)
-
-
-def craft(tmp_path, sizes, edges, state=None, tag="craft", extra=()):
-    """test_gpu_tiled_field.craft, plus `extra`: further (a, b, w, dist) edges INSIDE a tile that may repeat a pair, and
-    -> (engines, restitch): restitch(t, engine) assembles tile t's rows again, in `engine` (a fresh one loads the
-    tile's graph first)."""
-    import torch
-    import trg_planner
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-    V = int(off[-1])
-    state = np.zeros(V, np.int32) if state is None else np.asarray(state, np.int32)
-    tile_of = np.searchsorted(off, np.arange(V), side="right") - 1
-    assert len({(min(a, b), max(a, b)) for a, b, _, _ in edges}) == len(edges)
-    assert all(tile_of[a] == tile_of[b] for a, b, _, _ in extra)
-    x = [(a, b, w, d) if tile_of[a] < tile_of[b] else (b, a, w, d) for a, b, w, d in edges if tile_of[a] != tile_of[b]]
-    rec = np.array([(tile_of[a], a - off[tile_of[a]], tile_of[b], b - off[tile_of[b]]) for a, b, _, _ in x],
-                   np.int32).reshape(-1, 4)
-    wd = np.array([(w, d) for _, _, w, d in x], F32).reshape(-1, 2)
-    cross = np.ascontiguousarray(np.concatenate([rec, wd.view(np.int32)], 1))
-    dev = torch.device("cuda", torch.cuda.current_device())
-    cross_t = torch.from_numpy(cross).to(dev) if cross.shape[0] else None
-    torch.cuda.synchronize()
-
-    def restitch(t, e=None):
-        if e is None:
-            e = trg_planner.Engine(**MOUNTAIN)
-        e.load_json(str(tmp_path / f"{tag}{t}.json"))
-        e.stitch_assemble(t, len(sizes), off, cross_t.data_ptr() if cross_t is not None else None, int(cross.shape[0]))
-        return e
-
-    engines = []
-    for t, n in enumerate(sizes):
-        own = [(a - off[t], b - off[t], w, d) for a, b, w, d in list(edges) + list(extra)
-               if tile_of[a] == t and tile_of[b] == t]
-        src = [a for a, b, _, _ in own] + [b for a, b, _, _ in own]
-        dst = [b for a, b, _, _ in own] + [a for a, b, _, _ in own]
-        g = fg.from_edges(n, np.array(src, np.int64), np.array(dst, np.int64), [w for _, _, w, _ in own] * 2,
-                          [d for _, _, _, d in own] * 2, state=state[off[t]:off[t + 1]])
-        fg.write_json(tmp_path / f"{tag}{t}.json", g)
-        engines.append(restitch(t))
-    join_group(engines, "routes-" + tag)
-    return engines, restitch
-
-
-def close(engines):
-    for e in engines:
-        e.close()
-
-
-def call_routes(engines, fields, targets, cap=None, xyz=True):
-    from trg_planner._engine import TrgError
-    got, secs = run_ranks(engines, lambda r, e: e.tiled_routes(fields, targets, cap=cap, xyz=xyz))
-    bad = [g for g in got if isinstance(g, TrgError)]
-    assert not bad, [str(b) for b in bad]
-    return got
-
-
-def want_routes(G, fields, pairs):
-    """route_ref's routes; fields: per field (cost, hops, parent) of the uncut graph"""
-    out = [None] * len(pairs)
-    for k, (cost, hops, parent) in enumerate(fields):
-        mine = [i for i, (f, _) in enumerate(pairs) if f == k]
-        for i, r in zip(mine, trr.reference_routes(G, SF, cost, hops, parent, [pairs[i][1] for i in mine])):
-            out[i] = r
-    return out
-
-
-def most_crossings(G, want):
-    return max([trr.crossings(G["offsets"], w) for w in want if len(w.ids)], default=None)
-
-
-def assert_routes(at, tiled, parts, G, want, cap=None, owners=None):
-    """the ranks' parts against the reference routes -> the joined routes"""
-    off = G["offsets"]
-    lengths = [len(w.ids) for w in want]
-    total = sum(lengths)
-    offsets = trr.clipped_offsets(lengths, total if cap is None else cap)
-    key = lambda i: (i.num_nodes, bits(i.cost)[0], bits(i.path_length)[0], bits(i.avg_risk)[0], i.root_gid, i.owner)  # noqa: E731
-    for t, p in enumerate(parts):
-        assert np.array_equal(p["offsets"], offsets), (at, t, p["offsets"], offsets)
-        assert [key(i) for i in p["infos"]] == [key(i) for i in parts[0]["infos"]], (at, t)
-        if p["gids"] is not None:  # exactly its own nodes, and nothing else
-            mine = p["gids"] >= 0
-            assert ((p["gids"][mine] >= off[t]) & (p["gids"][mine] < off[t + 1])).all(), (at, t)
-            if p["xyz"] is not None:
-                assert np.isnan(p["xyz"][~mine]).all() and np.array_equal(p["xyz"][mine], G["xyz"][p["gids"][mine]]), (at, t)
-    joined = tiled.join_routes(parts)
-    for r, (w, (ids, pts, info)) in enumerate(zip(want, joined)):
-        room = int(offsets[r + 1] - offsets[r])
-        if ids is not None:
-            assert ids.tolist() == w.ids[:room].tolist(), f"{at}: route {r}: {ids.tolist()} != {w.ids[:room].tolist()}"
-        assert info.num_nodes == len(w.ids), (at, r, info.num_nodes, len(w.ids))
-        for name in ("cost", "path_length", "avg_risk"):
-            x, y = getattr(info, name), getattr(w, name)
-            assert bits(x)[0] == bits(y)[0], f"{at}: route {r}: {name} {x!r} != {y!r}"
-        assert info.root_gid == (int(w.ids[0]) if len(w.ids) else -1), (at, r)
-        if owners is None:
-            assert info.owner == -1, (at, r)
-    most = most_crossings(G, want)
-    print(at, "routes", len(want), "most crossings", most, "exchanges", [p["info"].exchanges for p in parts], "records",
-          [p["info"].records_sent for p in parts], "ms", [round(p["info"].ms_total, 2) for p in parts])
-    assert [p["info"].exchanges for p in parts] == [2 if most is None else most + 3] * len(parts), at
-    return joined
-
-
-def crossing_counts(G, hops, parent):
-    """per node: how often the route to it steps over a seam (-1: unreached)"""
-    tile_of = np.searchsorted(G["offsets"], np.arange(G["V"]), side="right") - 1
-    out = np.full(G["V"], -1, np.int64)
-    for v in np.argsort(hops, kind="stable"):
-        if hops[v] == 0:
-            out[v] = 0
-        elif hops[v] > 0:
-            out[v] = out[parent[v]] + (tile_of[parent[v]] != tile_of[v])
-    return out
 
 
 # ---- 1. built tilings -----------------------------------------------------------------------------------------------

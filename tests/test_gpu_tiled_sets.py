@@ -14,42 +14,15 @@ import field_graphs as fg
 import field_ref
 import seed_ref
 import stitch_cases as sc
-from field_support import MOUNTAIN, ref  # noqa: F401  (ref: the fixture)
-from test_gpu_tiled_field import craft, join_group, run_ranks
+from field_support import MOUNTAIN
+from tiled_support import RING, close, craft, exported, host_fields, join_group, run_ranks, solve_sets, stitch
+from tiled_support import ref, tiled  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 INVALID_ARG, DEVICE = 1, 4
 SF = MOUNTAIN["safety_factor"]
 FRONTIER = 1
 _built = {}  # tiling -> what test_built_tilings solved: shared by the tests that only read it
-
-
-@pytest.fixture(scope="module")
-def tiled():
-    from trg_planner import tiled as t
-    return t
-
-
-def solve_sets(engines, sets, starts=None, targets=None, full=True, parent=True):
-    """the collective call on every rank (targets: per rank, or None) -> the ranks' dicts"""
-    from trg_planner._engine import TrgError
-    got, secs = run_ranks(engines, lambda r, e: e.tiled_cost_fields_from(
-        sets, starts, targets=None if targets is None else targets[r], full=full, parent=parent))
-    bad = [g for g in got if isinstance(g, TrgError)]
-    assert not bad, [str(b) for b in bad]
-    return got
-
-
-def exported(tiled, engines):
-    return tiled.concat_stitched([e.graph("stitched") for e in engines])
-
-
-def host_fields(G, sets, starts):
-    """the definition in Python: every set's SetField on the uncut graph"""
-    g = SimpleNamespace(**G)
-    with np.errstate(over="ignore"):
-        return [seed_ref.seeded_field(g, SF, s, np.zeros(len(s), np.float32) if starts is None else starts[k])
-                for k, s in enumerate(sets)]
 
 
 def compiled_fields(lib, G, sets, starts):
@@ -83,11 +56,6 @@ def assert_sets(at, got, G, want, parent=True):
         owned = np.sum([g["owned"][k] for g in got], 0)
         assert np.array_equal(owned, w.owned), (at, k, owned, w.owned)
     assert sum(g["info"].roots for g in got) == sum(len(seed_ref.roots(w)) for w in want), at
-
-
-def stitch(engines, lay):
-    got, _ = run_ranks(engines, lambda r, e: e.stitch_exchange(lay.cores[r], lay.cols, lay.rows))
-    assert all(isinstance(g, tuple) for g in got), got
 
 
 def usable(G, tile):
@@ -187,17 +155,12 @@ def test_owners_never_cross_a_gap(oa, synth, tiled, ref):
 # ---- 3. - 7. crafted graphs -----------------------------------------------------------------------------------------
 def crafted(tmp_path, tiled, sizes, edges, sets, starts, state=None, tag="craft"):
     """craft, export, solve, compare with the Python definition -> (engines, G, want, results)"""
-    engines = craft(tmp_path, sizes, edges, state, "sets-" + tag)
+    engines, _ = craft(tmp_path, sizes, edges, state, "sets-" + tag)
     G = exported(tiled, engines)
     want = host_fields(G, sets, starts)
     got = solve_sets(engines, sets, starts)
     assert_sets(tag, got, G, want)
     return engines, G, want, got
-
-
-def close(engines):
-    for e in engines:
-        e.close()
 
 
 def test_chain_alternating_between_two_tiles(tmp_path, tiled):
@@ -303,12 +266,9 @@ def test_fan_seeds_and_publishes_across_blocks(tmp_path, tiled):
 
 
 # ---- 8. failure and refusals ----------------------------------------------------------------------------------------
-RING = [(i, (i + 1) % 12, 0.1, 0.5) for i in range(12)]
-
-
 def test_a_rank_without_current_rows_is_announced(tmp_path, tiled):
     from trg_planner._engine import TrgError
-    engines = craft(tmp_path, [6, 6], RING, tag="sets-void")
+    engines, _ = craft(tmp_path, [6, 6], RING, tag="sets-void")
     engines[1].load_json(str(tmp_path / "sets-void1.json"))  # its graph changed after the stitch: its rows are void
     got, secs = run_ranks(engines, lambda r, e: e.tiled_cost_fields_from([[0, 7]]))
     assert isinstance(got[1], TrgError) and got[1].status == INVALID_ARG, got[1]
@@ -335,7 +295,7 @@ def raw_call(e, ptr, gids, cost0=None, targets=None, n_targets=0, m=None):
 def test_refusals_leave_the_group_usable(tmp_path, tiled):
     import trg_planner
     from trg_planner._engine import TrgError
-    engines = craft(tmp_path, [6, 6], RING, tag="sets-refuse")
+    engines, _ = craft(tmp_path, [6, 6], RING, tag="sets-refuse")
     G = exported(tiled, engines)
     nan, inf = float("nan"), float("inf")
     cases = [
@@ -413,7 +373,7 @@ def test_assign_frontiers_across_tiles(oa, synth, tiled, ref, tmp_path):
     nx, ny, sizes, edges, gid = lattice()
     state = np.zeros(nx * ny, np.int32)
     state[[gid[x, y] for x in range(nx) for y in range(ny) if (x + 2 * y) % 5 == 0]] = FRONTIER
-    engines = craft(tmp_path, sizes, edges, state, "sets-assign-lattice")
+    engines, _ = craft(tmp_path, sizes, edges, state, "sets-assign-lattice")
     G = exported(tiled, engines)
     members, starts = [gid[nx - 1, 0], gid[8, 7], gid[5, 8], gid[8, 7], gid[0, 0]], [0.0, 1.0, 0.0, 1.0, 30.0]
     n, got = assert_assigned(engines, tiled, G, members, starts, host_fields(G, [members], [starts])[0])

@@ -1,4 +1,4 @@
-"""CPU: the protocol of the cost field across tiles (tests/tiled_field_ref.py: solve graphs with ghost mirrors,
+"""CPU: the protocol of the cost field across tiles (tests/tiled_ref.py: solve graphs with ghost mirrors,
 publish / merge until no news, two passes, parents as least global ids) must equal the definition on the UNCUT
 graph (field_ref.py_field) in cost bits, hops and parents -- the exactness claim of DESIGN.md section 7 and the
 pass-2 ghost rule, pinned before any GPU run.  Also the C and Python surface of the feature."""
@@ -10,20 +10,11 @@ import numpy as np
 import pytest
 
 import field_ref
-import tiled_field_ref as tr
+import tiled_ref as tr
+from tiled_support import cuts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SF = 3.0
-
-
-def cuts(rng, V, R, empty=False):
-    """R contiguous id ranges of [0, V) as R + 1 offsets; with `empty`, one range has no nodes."""
-    k = R - 1 - (1 if empty else 0)
-    inner = rng.choice(np.arange(1, V), size=k, replace=False).tolist()
-    if empty:
-        inner.append(inner[int(rng.integers(0, k))])  # a cut twice: the range between is empty
-    inner = np.sort(np.array(inner, np.int64))
-    return np.concatenate([[0], inner, [V]]).astype(np.int64)
 
 
 def check(G, offsets, sources):

@@ -1,4 +1,4 @@
-"""CPU: the protocol of the risk field across tiles (tests/tiled_risk_ref.py: tiled_field_ref's publish / merge loop
+"""CPU: the protocol of the risk field across tiles (tests/tiled_ref.py: the publish / merge loop
 under the extension (max(risk, r), hops + 1)) must equal, on the UNCUT graph, both the definition
 (risk_ref.py_risk_field) and the compiled host Dijkstra (tests/cpp/risk_reference.cpp) in risk bits, hops and parents
 -- the exactness claim of DESIGN.md section 7, "Risk fields across tiles", pinned before any GPU run.  Also the C and
@@ -12,9 +12,8 @@ import pytest
 
 import risk_graphs as rg
 import risk_ref
-import tiled_field_ref as tr
-import tiled_risk_ref as trr
-from test_tiled_field_cpu import cuts
+import tiled_ref as tr
+from tiled_support import cuts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,7 +30,7 @@ def check(ref, G, offsets, member_sets, at=""):
         want = risk_ref.py_risk_field(G["V"], G["rowptr"], G["col"], G["w"], G["state"], members)
         st, *compiled = risk_ref.risk_field(ref, G["rowptr"], G["col"], G["w"], G["state"], members)
         assert st == 0, st
-        risk, hops, parent, info = trr.tiled_risk_field(G, offsets, members)
+        risk, hops, parent, info = tr.tiled_risk_field(G, offsets, members)
         where = f"{at} offsets {np.asarray(offsets).tolist()} members {members}: "
         for other, name in ((want, "the definition"), (compiled, "the compiled reference")):
             assert np.array_equal(risk.view(np.uint32), other[0].view(np.uint32)), where + "risk bits, " + name
@@ -60,7 +59,7 @@ def test_protocol_equals_the_uncut_references(ref, seed, R):
     infos = check(ref, G, offsets, sets)
     assert sum(infos[0]["ghosts"]) > 0 and max(min(i["exchanges"]) for i in infos) >= 2, infos
     # five weight levels: plateaus -- many nodes share a risk word
-    risk = trr.tiled_risk_field(G, offsets, sets[0])[0]
+    risk = tr.tiled_risk_field(G, offsets, sets[0])[0]
     assert len(np.unique(risk[np.isfinite(risk)])) <= len(rg.LEVELS) + 1
 
 
@@ -69,50 +68,59 @@ def test_a_range_without_nodes_and_a_range_without_cross_edges(ref):
     V = 120
     G = plateau_graph(rng, V, 7, blocks=[(50, 80)])
     offsets = np.array([0, 50, 50, 80, V], np.int64)  # rank 1 has no nodes, rank 2 no cross edges
-    ranks = [trr.solve_graph(G, int(offsets[t]), int(offsets[t + 1])) for t in range(4)]
+    ranks = [tr.solve_graph(G, int(offsets[t]), int(offsets[t + 1])) for t in range(4)]
     assert ranks[1].V == 0 and ranks[2].G == 0 and ranks[0].G > 0 and ranks[3].G > 0
     valid = np.flatnonzero(G["state"] != tr.INVALID)
     block = valid[(valid >= 50) & (valid < 80)]
     inside = int(block[np.argmax(np.diff(G["rowptr"])[block])])
     check(ref, G, offsets, [[int(valid[0])], [inside], [int(valid[-1]), inside]])
-    hops = trr.tiled_risk_field(G, offsets, [inside])[1]
+    hops = tr.tiled_risk_field(G, offsets, [inside])[1]
     assert (hops[:50] == -1).all() and (hops[80:] == -1).all() and (hops[50:80] >= 0).sum() > 1
 
 
 def test_solve_graph_is_the_cost_protocols_on_a_symmetric_graph():
+    """solve_graph against the in-edge definition written out: ghosts are the remote nodes with an edge into one of
+    the rank's nodes, their rows hold exactly those edges with their values, the border is the rank's nodes with an
+    edge into another rank's node."""
     rng = np.random.default_rng(11)
     G = tr.symmetric_graph(rng, 60)
+    edges = [(u, int(G["col"][k]), float(G["w"][k]), float(G["dist"][k]))
+             for u in range(60) for k in range(G["rowptr"][u], G["rowptr"][u + 1])]
     for lo, hi in ((0, 25), (25, 25), (25, 60)):
-        a, b = tr.solve_graph(G, lo, hi), trr.solve_graph(G, lo, hi)
-        assert a.V == b.V and a.G == b.G and np.array_equal(a.ghosts, b.ghosts) and np.array_equal(a.border, b.border)
-        for u in range(a.V + a.G):
-            mine = sorted((int(a.col[k]), float(a.w[k] + np.float32(0.0))) for k in range(a.rowptr[u], a.rowptr[u + 1])
-                          if a.col[k] < a.V)
-            assert mine == sorted((v, float(r)) for v, r in b.edges[u]), (lo, hi, u)
+        a = tr.solve_graph(G, lo, hi)
+        mine = lambda x: lo <= x < hi  # noqa: E731
+        ghosts = sorted({u for u, v, _, _ in edges if mine(v) and not mine(u)})
+        border = sorted({u - lo for u, v, _, _ in edges if mine(u) and not mine(v)})
+        assert a.V == hi - lo and a.G == len(ghosts) and a.ghosts.tolist() == ghosts and a.border.tolist() == border
+        assert a.gid_of.tolist() == list(range(lo, hi)) + ghosts and len(a.rowptr) == a.V + a.G + 1
+        for i, g in enumerate(a.gid_of.tolist()):
+            row = sorted((int(a.col[k]), float(a.w[k]), float(a.dist[k])) for k in range(a.rowptr[i], a.rowptr[i + 1]))
+            assert row == sorted((v - lo, w, d) for u, v, w, d in edges if u == g and mine(v)), (lo, hi, g)
+            assert i < a.V or row, (lo, hi, g)  # (a ghost has an edge into the rank)
 
 
 def test_rise_and_fall_alternating_between_two_ranges(ref):
     """Every edge of the chain is a cross edge: one exchange per node, in pass 2 as well, while the risk word has
     stopped moving at the peak."""
-    G, offsets, new = trr.interleaved(rg.rise_and_fall(16))
+    G, offsets, new = tr.interleaved(rg.rise_and_fall(16))
     info, = check(ref, G, offsets, [[int(new[0])]])
     assert info["exchanges"][0] >= 16 and info["exchanges"][1] >= 16, info
-    risk, hops, _, _ = trr.tiled_risk_field(G, offsets, [int(new[0])])
+    risk, hops, _, _ = tr.tiled_risk_field(G, offsets, [int(new[0])])
     assert hops[new[15]] == 15 and len(np.unique(risk[new[8:]])) == 1
 
 
 def test_all_zero_weights_cut_in_three(ref):
     g = rg.all_zero_weights(24)
-    G = trr.as_csr(g)
+    G = tr.as_csr(g)
     infos = check(ref, G, np.array([0, 7, 15, 24], np.int64), [[0], [23], [3, 20]])
-    risk = trr.tiled_risk_field(G, np.array([0, 7, 15, 24]), [0])[0]
+    risk = tr.tiled_risk_field(G, np.array([0, 7, 15, 24]), [0])[0]
     assert (risk.view(np.uint32) == 0).all() and sum(infos[0]["ghosts"]) > 0
 
 
 @pytest.mark.parametrize("name", sorted(rg.cases()))
 def test_hand_written_cases_cut_in_two_everywhere(ref, name):
     g, sources = rg.cases()[name]
-    G = trr.as_csr(g)
+    G = tr.as_csr(g)
     for cut in range(1, G["V"]):
         check(ref, G, np.array([0, cut, G["V"]], np.int64), [[s] for s in sources] + [sources], at=name)
 
@@ -138,14 +146,14 @@ def test_the_second_pass_is_needed_across_a_seam(ref):
     G = stale_hops_graph()
     offsets = np.array([0, 3, 10], np.int64)
     want = risk_ref.py_risk_field(G["V"], G["rowptr"], G["col"], G["w"], G["state"], [0])
-    one = trr.tiled_risk_field(G, offsets, [0], passes=1)
+    one = tr.tiled_risk_field(G, offsets, [0], passes=1)
     assert np.array_equal(one[0].view(np.uint32), want[0].view(np.uint32))  # pass 1's risk words are final
     assert want[1][6] == 4 and one[1][6] == 3, (want[1], one[1])  # the precondition: pass 1 alone keeps stale hops
     check(ref, G, offsets, [[0]])
 
 
 def test_staircase_publishes_every_drop(ref):
-    sizes, edges, s, t = trr.staircase(8)
+    sizes, edges, s, t = tr.staircase(8)
     V = sum(sizes)
     src = [a for a, b, _, _ in edges] + [b for a, b, _, _ in edges]
     dst = [b for a, b, _, _ in edges] + [a for a, b, _, _ in edges]
@@ -156,7 +164,7 @@ def test_staircase_publishes_every_drop(ref):
     offsets = np.array([0, sizes[0], V], np.int64)
     info, = check(ref, G, offsets, [[s]])
     assert info["published"][t] >= 8, info["published"][t]
-    risk, hops, _, _ = trr.tiled_risk_field(G, offsets, [s])
+    risk, hops, _, _ = tr.tiled_risk_field(G, offsets, [s])
     assert risk[t] == np.float32(0.9 - 0.1 * 7) and hops[t] == 16
 
 
@@ -184,14 +192,16 @@ def test_safety_factor_is_an_option():
     """The one way to move the safety factor of a live engine (the tiled risk solves must not notice it): accepted
     through the C ABI, as tests/test_options.py pins the other keys."""
     import ctypes as C
-    from test_options import OK, _library, _params
-    L = _library()
-    prm = _params()
+    import trg_planner
+    from trg_planner._engine import TrgParams
+    trg_planner.build_library()
+    L = trg_planner.load_library()
+    prm = TrgParams(0, 0.6, 0.3, 8, 0.3, 0.2, 0.5, 1.0, 0.5)
     h = C.c_void_p()
     L.trg_engine_create(C.byref(prm), 0, C.byref(h))
     assert h.value
     for v in (b"0.5", b"3", b"0"):
-        assert L.trg_engine_set_option(h, b"safety_factor", v) == OK, v
+        assert L.trg_engine_set_option(h, b"safety_factor", v) == 0, v  # TRG_OK
     L.trg_engine_destroy(h)
 
 

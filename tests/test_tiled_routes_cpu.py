@@ -12,9 +12,9 @@ import pytest
 
 import field_ref
 import seed_ref
-import tiled_field_ref as tr
+import tiled_ref as tr
 import tiled_route_ref as trr
-from test_tiled_field_cpu import cuts
+from tiled_support import cuts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32

@@ -1,4 +1,4 @@
-"""CPU: the protocol of source sets across tiles (tests/tiled_set_ref.py: per-rank seeding, two passes, parents as
+"""CPU: the protocol of source sets across tiles (tests/tiled_ref.py: per-rank seeding, two passes, parents as
 least global ids, the owner loop with ghost terminals and publish-once) must equal the definition on the UNCUT graph
 (seed_ref.seeded_field) in cost bits, hops, parents, owners and owned -- the claim of DESIGN.md section 7, "Source sets
 across tiles", pinned before any GPU run.  Also the C and Python surface of the feature."""
@@ -11,9 +11,8 @@ import numpy as np
 import pytest
 
 import seed_ref
-import tiled_field_ref as tr
-import tiled_set_ref as ts
-from test_tiled_field_cpu import cuts
+import tiled_ref as tr
+from tiled_support import cuts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SF = 3.0
@@ -52,7 +51,7 @@ def check(G, offsets, mem, c0):
     g = SimpleNamespace(**G)
     with np.errstate(over="ignore"):
         want = seed_ref.seeded_field(g, SF, mem, np.zeros(len(mem), np.float32) if c0 is None else c0)
-        got = ts.tiled_set_field(G, offsets, SF, mem, c0)
+        got = tr.tiled_set_field(G, offsets, SF, mem, c0)
     at = f"offsets {offsets.tolist()} members {mem}: "
     assert np.array_equal(got["cost"].view(np.uint32), want.cost.view(np.uint32)), at + "cost bits"
     assert np.array_equal(got["hops"], want.hops), at + "hops"
@@ -89,7 +88,7 @@ def test_one_entry_sets_equal_the_single_source_protocol():
     for src in (3, 40, int(np.flatnonzero(G["state"] == tr.INVALID)[0])):
         with np.errstate(over="ignore"):
             cost, hops, parent, info = tr.tiled_field(G, offsets, SF, src)
-            got = ts.tiled_set_field(G, offsets, SF, [src])
+            got = tr.tiled_set_field(G, offsets, SF, [src])
         assert np.array_equal(got["cost"].view(np.uint32), cost.view(np.uint32))
         assert np.array_equal(got["hops"], hops) and np.array_equal(got["parent"], parent)
         assert got["exchanges"] == info["exchanges"]

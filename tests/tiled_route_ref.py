@@ -1,6 +1,6 @@
 """Test helper: the protocol of the routes across tiles ("Routes across tiles"), restated in numpy
 and plain Python apart from the engine.  Every rank holds what a tiled solve leaves it: its solve graph
-(tiled_field_ref.solve_graph), the keys of its nodes and of its ghosts, the global parents of its nodes.  Exchange 0: the
+(tiled_ref.solve_graph), the keys of its nodes and of its ghosts, the global parents of its nodes.  Exchange 0: the
 owner of each target publishes LEN {route, hops or -1, cost bits, owner}; every rank computes the same clipped offsets.
 From exchange 1 on each rank walks what stands on its nodes -- the route edge is the tight edge of least index into the
 node in the parent's row of ITS solve graph, a ghost's row when the parent is another rank's node -- and publishes
@@ -12,7 +12,8 @@ from types import SimpleNamespace
 import numpy as np
 
 import route_ref
-import tiled_field_ref as tr
+import tiled_ref as tr
+from field_keys import INVALID, cost_values
 
 F32 = np.float32
 
@@ -61,9 +62,8 @@ def tiled_routes(G, offsets, sf, cost, hops, parent, targets, owner=None, cap=No
     ranks = [tr.solve_graph(G, int(offsets[t]), int(offsets[t + 1])) for t in range(R)]
     cost = np.asarray(cost, F32)
     for S in ranks:
-        with np.errstate(over="ignore", invalid="ignore"):
-            S.ec = ((F32(sf) * S.w + F32(1.0)) * S.dist).astype(F32)
-        S.ok = S.state[S.col] != tr.INVALID
+        S.ec = cost_values(S.w, S.dist, sf)
+        S.ok = S.state[S.col] != INVALID
         S.cost, S.hops = cost[S.gid_of], np.asarray(hops)[S.gid_of]  # the ghosts mirror their owners' keys
         S.index = {int(g): i for i, g in enumerate(S.gid_of)}
     rank_of = lambda g: int(np.searchsorted(offsets, g, side="right") - 1)  # noqa: E731

@@ -451,25 +451,86 @@ class Engine:
         self._chk(self.L.trg_engine_stitch_ids(self.h, C.byref(first), C.byref(n), C.byref(total)))
         return int(first.value), int(n.value)
 
+    # (what the cost and the risk calls below share, each keyed by the objective's value name and its C entry or solve)
+    def _tiled_ids(self):
+        """global_ids(), or (0, 0) where that refuses: the solve itself reports, and announces, that there are no
+        current rows."""
+        try:
+            return self.global_ids()
+        except TrgError:
+            return 0, 0
+
+    def _tiled_fields(self, value, entry, source_gids, parent):
+        """tiled_cost_fields and tiled_risk_fields: `value` names the objective's array ("cost" or "risk"), `entry` is
+        its C entry."""
+        src = np.ascontiguousarray(source_gids, dtype=np.int32).reshape(-1)
+        m = int(src.shape[0])
+        offset, V = self._tiled_ids()
+        rows = max(m, 1)
+        val = np.empty((rows, V), np.float32)
+        hops = np.empty((rows, V), np.int32)
+        par = np.empty((rows, V), np.int32) if parent else None
+        info = TrgTiledFieldInfo()
+        self._chk(entry(self.h, m, _i(src), _f(val), _i(hops), None if par is None else _i(par), C.byref(info)))
+        return {value: val, "hops": hops, "parent": par, "offset": offset, "info": info}
+
+    def _tiled_fields_from(self, value, entry, who, sets, start_costs, targets, full, parent):
+        """tiled_cost_fields_from and tiled_risk_fields_from (`who`): `value` names the objective's arrays (`value` and
+        `value`_at), `entry` is its C entry; only the cost entry takes start costs, and only its dict has them."""
+        sets, ptr, ids, starts, c0 = pack_sets(who, sets, start_costs)
+        m = len(sets)
+        offset, V = self._tiled_ids()
+        rows = max(m, 1)
+        at = value + "_at"
+        out = dict(offset=offset, sets=sets)
+        if value == "cost":
+            out["start_costs"] = starts
+        if full:
+            out.update({value: np.empty((rows, V), np.float32), "hops": np.empty((rows, V), np.int32),
+                        "parent": np.empty((rows, V), np.int32) if parent else None,
+                        "owner": np.empty((rows, V), np.int32)})
+        tg, n_t = None, 0
+        if targets is not None:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+            n_t = int(tg.shape[0])
+            out.update({at: np.empty((rows, n_t), np.float32), "hops_at": np.empty((rows, n_t), np.int32),
+                        "owner_at": np.empty((rows, n_t), np.int32)})
+        owned, split_owned = _owned_buffer(ptr)
+        info = TrgTiledSetInfo()
+        arr = lambda name, conv: None if out.get(name) is None else conv(out[name])  # noqa: E731
+        self._chk(entry(
+            self.h, m, _i(ptr), _i(ids), *((None if c0 is None else _f(c0),) if value == "cost" else ()),
+            arr(value, _f), arr("hops", _i), arr("parent", _i), arr("owner", _i),
+            None if tg is None or n_t == 0 else _i(tg), n_t, arr(at, _f), arr("hops_at", _i), arr("owner_at", _i),
+            _i(owned), C.byref(info)))
+        out["owned"] = split_owned()
+        out["info"] = info
+        return out
+
+    def _tiled_at_frontier(self, member_gids, solve):
+        """tiled_assign_frontiers and tiled_frontier_ceilings: solve(sets, targets), the set solve of either objective,
+        from the one set `member_gids` read at this tile's Frontier nodes -> (the members, those nodes' global ids,
+        the solve's dict)."""
+        members = np.ascontiguousarray(member_gids, dtype=np.int32).reshape(-1)
+        try:
+            frontier = self._frontier_ids()
+        except TrgError:
+            frontier = np.empty(0, np.int32)  # (the solve reports what is wrong with this tile)
+        r = solve([members], frontier)
+        return members, (frontier.astype(np.int64) + r["offset"]).astype(np.int32), r
+
+    def _tiled_one_to_many(self, solve, start_gid, goal_gids):
+        """tiled_plan_many and tiled_safest_routes: solve, the single-source solve of either objective."""
+        goals = np.ascontiguousarray(goal_gids, dtype=np.int32).reshape(-1)
+        solve([int(start_gid)], parent=False)
+        return self.tiled_routes(np.zeros(goals.shape[0], np.int32), goals)
+
     def tiled_cost_fields(self, source_gids, parent=True):
         """The cost fields of the global stitched graph from the global ids `source_gids`, for this tile's nodes: a
         collective call, made by every rank of the communicator with the same sources after a stitch.  -> dict with
         cost, hops (m x V_t), parent (global ids; None without `parent`), offset (this tile's first global id) and
         info (TrgTiledFieldInfo).  tiled.concat_fields joins the ranks' results."""
-        src = np.ascontiguousarray(source_gids, dtype=np.int32).reshape(-1)
-        m = int(src.shape[0])
-        try:
-            offset, V = self.global_ids()
-        except TrgError:
-            offset, V = 0, 0  # (the solve itself reports, and announces, that there are no current rows)
-        rows = max(m, 1)
-        cost = np.empty((rows, V), np.float32)
-        hops = np.empty((rows, V), np.int32)
-        par = np.empty((rows, V), np.int32) if parent else None
-        info = TrgTiledFieldInfo()
-        self._chk(self.L.trg_engine_tiled_cost_field(self.h, m, _i(src), _f(cost), _i(hops),
-                                                     None if par is None else _i(par), C.byref(info)))
-        return dict(cost=cost, hops=hops, parent=par, offset=offset, info=info)
+        return self._tiled_fields("cost", self.L.trg_engine_tiled_cost_field, source_gids, parent)
 
     def tiled_cost_fields_from(self, sets, start_costs=None, targets=None, full=True, parent=True):
         """Source sets across tiles (trg_engine_tiled_cost_field_sets; DESIGN.md section 7, "Source sets across tiles"):
@@ -482,33 +543,8 @@ class Engine:
         (TrgTiledSetInfo), "sets" and "start_costs" (the arrays as solved, None without start costs).  An owner is the
         index into sets[k] of the member a node's route starts from, -1 where unreached.  tiled.concat_fields joins
         the ranks' results."""
-        sets, ptr, ids, starts, c0 = pack_sets("tiled_cost_fields_from", sets, start_costs)
-        m = len(sets)
-        try:
-            offset, V = self.global_ids()
-        except TrgError:
-            offset, V = 0, 0  # (the solve itself reports, and announces, that there are no current rows)
-        rows = max(m, 1)
-        out = dict(offset=offset, sets=sets, start_costs=starts)
-        if full:
-            out.update(cost=np.empty((rows, V), np.float32), hops=np.empty((rows, V), np.int32),
-                       parent=np.empty((rows, V), np.int32) if parent else None, owner=np.empty((rows, V), np.int32))
-        tg, n_t = None, 0
-        if targets is not None:
-            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
-            n_t = int(tg.shape[0])
-            out.update(cost_at=np.empty((rows, n_t), np.float32), hops_at=np.empty((rows, n_t), np.int32),
-                       owner_at=np.empty((rows, n_t), np.int32))
-        owned, split_owned = _owned_buffer(ptr)
-        info = TrgTiledSetInfo()
-        arr = lambda name, conv: None if out.get(name) is None else conv(out[name])  # noqa: E731
-        self._chk(self.L.trg_engine_tiled_cost_field_sets(
-            self.h, m, _i(ptr), _i(ids), None if c0 is None else _f(c0), arr("cost", _f), arr("hops", _i),
-            arr("parent", _i), arr("owner", _i), None if tg is None or n_t == 0 else _i(tg), n_t, arr("cost_at", _f),
-            arr("hops_at", _i), arr("owner_at", _i), _i(owned), C.byref(info)))
-        out["owned"] = split_owned()
-        out["info"] = info
-        return out
+        return self._tiled_fields_from("cost", self.L.trg_engine_tiled_cost_field_sets, "tiled_cost_fields_from", sets,
+                                       start_costs, targets, full, parent)
 
     def tiled_assign_frontiers(self, member_gids, start_costs=None):
         """Every Frontier node of the global stitched graph to the entry of `member_gids` (GLOBAL ids, e.g. the robots'
@@ -516,15 +552,9 @@ class Engine:
         Frontier nodes on the device.  -> per entry (the global ids of this tile's Frontier nodes it owns, ascending;
         pick), pick being choose_frontier's among them as (gid, cost, hops), or None when it owns none here.
         tiled.merge_frontier_picks joins the ranks' answers."""
-        members = np.ascontiguousarray(member_gids, dtype=np.int32).reshape(-1)
-        try:
-            frontier = self._frontier_ids()
-        except TrgError:
-            frontier = np.empty(0, np.int32)  # (the solve reports what is wrong with this tile)
-        r = self.tiled_cost_fields_from([members], None if start_costs is None else [start_costs], targets=frontier,
-                                        full=False, parent=False)
+        members, gids, r = self._tiled_at_frontier(member_gids, lambda sets, at: self.tiled_cost_fields_from(
+            sets, None if start_costs is None else [start_costs], targets=at, full=False, parent=False))
         cost, hops, owner = r["cost_at"][0], r["hops_at"][0], r["owner_at"][0]
-        gids = (frontier.astype(np.int64) + r["offset"]).astype(np.int32)
         out = []
         for k in range(members.shape[0]):
             mine = np.flatnonzero(owner == k)
@@ -573,71 +603,29 @@ class Engine:
         downloaded) and one tiled_routes call without a capacity -- the lengths first, then the ids -- all
         ranks alike (a collective call) -> tiled_routes' dict; tiled.join_routes gives the routes.  Each path is the
         least fp32 fold of edge costs to its goal (tiled_cost_fields' semantics)."""
-        goals = np.ascontiguousarray(goal_gids, dtype=np.int32).reshape(-1)
-        self.tiled_cost_fields([int(start_gid)], parent=False)
-        return self.tiled_routes(np.zeros(goals.shape[0], np.int32), goals)
+        return self._tiled_one_to_many(self.tiled_cost_fields, start_gid, goal_gids)
 
     # ---- risk fields across tiles (DESIGN.md section 7, "Risk fields across tiles") ---------------------------
     def tiled_risk_fields(self, source_gids, parent=True):
         """The risk fields of the global stitched graph from the global ids `source_gids`, for this tile's nodes
         (trg_engine_tiled_risk_field): the least, over all walks, of the greatest edge weight on the walk.  A collective
         call like tiled_cost_fields -> its dict with "risk" where that has "cost"."""
-        src = np.ascontiguousarray(source_gids, dtype=np.int32).reshape(-1)
-        m = int(src.shape[0])
-        try:
-            offset, V = self.global_ids()
-        except TrgError:
-            offset, V = 0, 0  # (the solve itself reports, and announces, that there are no current rows)
-        rows = max(m, 1)
-        risk = np.empty((rows, V), np.float32)
-        hops = np.empty((rows, V), np.int32)
-        par = np.empty((rows, V), np.int32) if parent else None
-        info = TrgTiledFieldInfo()
-        self._chk(self.L.trg_engine_tiled_risk_field(self.h, m, _i(src), _f(risk), _i(hops),
-                                                     None if par is None else _i(par), C.byref(info)))
-        return dict(risk=risk, hops=hops, parent=par, offset=offset, info=info)
+        return self._tiled_fields("risk", self.L.trg_engine_tiled_risk_field, source_gids, parent)
 
     def tiled_risk_fields_from(self, sets, targets=None, full=True, parent=True):
         """Risk fields from source sets across tiles (trg_engine_tiled_risk_field_sets): field k from EVERY entry of
         sets[k] (GLOBAL ids) at risk 0 -- risk solves take no start values.  A collective call like
         tiled_cost_fields_from -> its dict with "risk" / "risk_at" where that has "cost" / "cost_at" and without
         "start_costs"."""
-        sets, ptr, ids, _, _ = pack_sets("tiled_risk_fields_from", sets)
-        m = len(sets)
-        try:
-            offset, V = self.global_ids()
-        except TrgError:
-            offset, V = 0, 0  # (the solve itself reports, and announces, that there are no current rows)
-        rows = max(m, 1)
-        out = dict(offset=offset, sets=sets)
-        if full:
-            out.update(risk=np.empty((rows, V), np.float32), hops=np.empty((rows, V), np.int32),
-                       parent=np.empty((rows, V), np.int32) if parent else None, owner=np.empty((rows, V), np.int32))
-        tg, n_t = None, 0
-        if targets is not None:
-            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
-            n_t = int(tg.shape[0])
-            out.update(risk_at=np.empty((rows, n_t), np.float32), hops_at=np.empty((rows, n_t), np.int32),
-                       owner_at=np.empty((rows, n_t), np.int32))
-        owned, split_owned = _owned_buffer(ptr)
-        info = TrgTiledSetInfo()
-        arr = lambda name, conv: None if out.get(name) is None else conv(out[name])  # noqa: E731
-        self._chk(self.L.trg_engine_tiled_risk_field_sets(
-            self.h, m, _i(ptr), _i(ids), arr("risk", _f), arr("hops", _i), arr("parent", _i), arr("owner", _i),
-            None if tg is None or n_t == 0 else _i(tg), n_t, arr("risk_at", _f), arr("hops_at", _i),
-            arr("owner_at", _i), _i(owned), C.byref(info)))
-        out["owned"] = split_owned()
-        out["info"] = info
-        return out
+        return self._tiled_fields_from("risk", self.L.trg_engine_tiled_risk_field_sets, "tiled_risk_fields_from", sets,
+                                       None, targets, full, parent)
 
     def tiled_safest_routes(self, start_gid, goal_gids):
         """The safest paths from one node of the global stitched graph to many: ONE tiled risk solve from `start_gid`
         (no parents are downloaded) and one tiled_routes call without a capacity, all ranks alike (a collective call)
         -> tiled_routes' dict; tiled.join_routes gives the routes.  Each route's `cost` is the least worst-edge risk to
         its goal (tiled_risk_fields' semantics)."""
-        goals = np.ascontiguousarray(goal_gids, dtype=np.int32).reshape(-1)
-        self.tiled_risk_fields([int(start_gid)], parent=False)
-        return self.tiled_routes(np.zeros(goals.shape[0], np.int32), goals)
+        return self._tiled_one_to_many(self.tiled_risk_fields, start_gid, goal_gids)
 
     def tiled_frontier_ceilings(self, member_gids):
         """For every Frontier node of THIS tile the least risk ceiling under which the nearest entry of `member_gids`
@@ -646,13 +634,8 @@ class Engine:
         tile's Frontier nodes, global ids ascending), "risk" (+inf: unreachable), "hops" (-1), "owner" (the entry of
         member_gids whose tree the node hangs in, -1) and "members" (their number).  tiled.safest_frontier joins the
         ranks' answers."""
-        members = np.ascontiguousarray(member_gids, dtype=np.int32).reshape(-1)
-        try:
-            frontier = self._frontier_ids()
-        except TrgError:
-            frontier = np.empty(0, np.int32)  # (the solve reports what is wrong with this tile)
-        r = self.tiled_risk_fields_from([members], targets=frontier, full=False, parent=False)
-        gids = (frontier.astype(np.int64) + r["offset"]).astype(np.int32)
+        members, gids, r = self._tiled_at_frontier(member_gids, lambda sets, at: self.tiled_risk_fields_from(
+            sets, targets=at, full=False, parent=False))
         return dict(gids=gids, risk=r["risk_at"][0], hops=r["hops_at"][0], owner=r["owner_at"][0],
                     members=int(members.shape[0]), info=r["info"])
 
