@@ -716,8 +716,9 @@ TrgStatus trg_engine_risk_field_refresh(TrgEngine *e,
  * (TRG_ERR_CAPACITY), a queue overflow (TRG_ERR_DEVICE) -- is announced in the next count exchange: that rank returns
  * its error, every other rank TRG_ERR_DEVICE "another rank reported a failure", none waits.  TRG_ERR_DEVICE on every
  * rank at once when the exchanges do not converge.  Source sets and start costs are the call below, routes
- * trg_engine_tiled_field_routes, risk fields trg_engine_tiled_risk_field; bounds, cost models and refresh are not
- * offered across tiles, and none of these calls touches the retained single-engine solve. */
+ * trg_engine_tiled_field_routes, risk fields trg_engine_tiled_risk_field, budgets and settle targets
+ * trg_engine_tiled_cost_field_bounded; cost models and refresh are not offered across tiles, and none of these calls
+ * touches the retained single-engine solve. */
 typedef struct TrgTiledFieldInfo {
   int32_t exchanges;     /* all-gather-v exchanges of both passes, the two that found no news included */
   int32_t rounds;        /* relaxation rounds of this rank that did work */
@@ -761,8 +762,8 @@ TrgStatus trg_engine_tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *so
  * next count exchange, of the owner exchanges as well: that rank returns its error, its peers TRG_ERR_DEVICE "another
  * rank reported a failure", nobody waits.  An owner loop that outlasts m x (border nodes of all ranks) + 2 exchanges
  * ends with TRG_ERR_DEVICE on every rank at once.  Routes are trg_engine_tiled_field_routes, risk fields from sets
- * trg_engine_tiled_risk_field_sets; bounds, cost models and refresh are not offered across tiles; the retained
- * single-engine solve is left alone. */
+ * trg_engine_tiled_risk_field_sets, budgets and settle targets trg_engine_tiled_cost_field_bounded; cost models and
+ * refresh are not offered across tiles; the retained single-engine solve is left alone. */
 typedef struct TrgTiledSetInfo {
   int32_t exchanges;           /* all-gather-v exchanges of passes 1 and 2, the two without news included */
   int32_t owner_exchanges;     /* ... of the owner pass, the one without news included */
@@ -799,8 +800,8 @@ TrgStatus trg_engine_tiled_cost_field_sets(TrgEngine *e, int32_t m,
  * error, its peers TRG_ERR_DEVICE "another rank reported a failure", nobody waits): those of the cost calls, and in
  * the place of the bad edge cost "tiled risk field: an edge weight is negative or not finite" (TRG_ERR_INVALID_ARG),
  * taken over ALL edges of that rank's solve graph, relaxable or not, as in the single-engine call.
- * Routes are trg_engine_tiled_field_routes; risk ceilings (budget / settle), cost models and refresh are not offered
- * across tiles. */
+ * Routes are trg_engine_tiled_field_routes, risk ceilings (budget / settle) trg_engine_tiled_risk_field_bounded; cost
+ * models and refresh are not offered across tiles. */
 TrgStatus trg_engine_tiled_risk_field(TrgEngine *e, int32_t m, const int32_t *source_gids,
     float *risk, int32_t *hops, int32_t *parent,   /* m x (this tile's nodes), any may be NULL */
     TrgTiledFieldInfo *info);                      /* may be NULL */
@@ -810,8 +811,67 @@ TrgStatus trg_engine_tiled_risk_field_sets(TrgEngine *e, int32_t m,
     const int32_t *targets, int32_t n_targets, float *risk_at, int32_t *hops_at, int32_t *owner_at,
     int32_t *owned,                                                /* set_ptr[m], may be NULL */
     TrgTiledSetInfo *info);                                        /* may be NULL */
+/* Bounded fields across tiles ("Bounded fields across tiles"): trg_engine_cost_field_bounded's
+ * definition ("Bounded fields") on the global stitched graph G.  Field k is the full tiled field k
+ * -- of trg_engine_tiled_cost_field_sets from the same sets and start costs -- truncated at
+ *   bound[k] = min(budget[k], settle_k):
+ * every node whose cost is greater than the bound comes out unreached (+inf, hops -1, parent -1, owner -1), every node
+ * at or below it, equal bits included, keeps its cost bits, hops, global-id parent and owner.
+ *   budget        m costs >= 0 (+inf allowed), or NULL: +inf each.  Under the risk objective a budget is a risk ceiling.
+ *   settle        TRG_FIELD_SETTLE_NONE: settle_k = +inf.  _ANY: the least full-field value of field k over the settle
+ *                 targets.  _ALL: the greatest.  +inf whenever that value would come from a target without a key.
+ *   settle_gids   n_settle GLOBAL ids, the same list on every rank; duplicates and Invalid nodes allowed
+ *   owners        != 0: the owner pass runs and owner, targets / cost_at / hops_at / owner_at and owned are the set
+ *                 call's, on the truncated field (a truncated node has owner -1).  Every rank passes the same value: the
+ *                 owner pass is a collective.  0: those arguments are neither read nor written, as in the
+ *                 single-source calls (m sets of one entry give their fields).
+ *   bound_out     m, may be NULL: bound[k], the same bits on every rank, a tile without nodes included -- a function of
+ *                 G, the sets, the start costs and these arguments alone
+ *   reached_out   m, may be NULL: how many of THIS tile's nodes lie within field k's bound (the ranks' counts sum to
+ *                 the truncated field's reached nodes)
+ * With budget NULL and TRG_FIELD_SETTLE_NONE the solve is the unbounded calls' bit for bit, with their exchanges, rounds
+ * and records.  Else pass 1 of the solve relaxes nothing above a field's current bound and publishes no key above it;
+ * the ranks lower the bound between the exchanges from the keys their settle targets hold -- upper bounds on the
+ * targets' final values -- told to each other in the same 16-byte records, until an exchange without news, where the
+ * bound is the definition's on every rank.  A wavefront that a bound keeps inside one tile ends with the fewest
+ * exchanges there are.  The solve is retained like any tiled solve: trg_engine_tiled_field_routes answers from it, a
+ * target beyond its field's bound has the empty route, one within it the route it has in the full field.
+ * TRG_ERR_INVALID_ARG before any collective, the group still usable, beside the set call's refusals: a budget that is
+ * negative or NaN (the message names the field); a settle value outside the enum; a settle mode other than NONE with
+ * n_settle <= 0 or NULL settle_gids; a settle target outside [0, nodes of G) (the message names the target).  A rank's
+ * own failure is announced in the next count exchange like every other. */
+TrgStatus trg_engine_tiled_cost_field_bounded(TrgEngine *e, int32_t m,
+    const int32_t *set_ptr, const int32_t *set_gids, const float *set_cost0,   /* set_cost0 may be NULL */
+    int32_t owners,
+    const float *budget,                                           /* m, or NULL */
+    int32_t settle, const int32_t *settle_gids, int32_t n_settle,  /* TRG_FIELD_SETTLE_*, over GLOBAL ids */
+    float *cost, int32_t *hops, int32_t *parent, int32_t *owner,   /* m x (this tile's nodes), any may be NULL */
+    const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned,                                                /* set_ptr[m], may be NULL */
+    float *bound_out, int32_t *reached_out,                        /* m each, may be NULL */
+    TrgTiledSetInfo *info);                                        /* may be NULL */
+/* The same under the risk objective (trg_engine_tiled_risk_field_sets' fields; no start values). */
+TrgStatus trg_engine_tiled_risk_field_bounded(TrgEngine *e, int32_t m,
+    const int32_t *set_ptr, const int32_t *set_gids,
+    int32_t owners,
+    const float *budget,                                           /* m risk ceilings, or NULL */
+    int32_t settle, const int32_t *settle_gids, int32_t n_settle,
+    float *risk, int32_t *hops, int32_t *parent, int32_t *owner,   /* m x (this tile's nodes), any may be NULL */
+    const int32_t *targets, int32_t n_targets, float *risk_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned,                                                /* set_ptr[m], may be NULL */
+    float *bound_out, int32_t *reached_out,                        /* m each, may be NULL */
+    TrgTiledSetInfo *info);                                        /* may be NULL */
+/* THIS tile's reached nodes of field `field` of the retained tiled solve (any tiled field call, bounded or not), in
+ * ascending global id, compacted on the device: gids / value (cost or risk) / hops get the first `cap` of them (any may
+ * be NULL), *n_out their total; cap == 0 returns the count alone.  Local work, no collective: the ranks' lists,
+ * concatenated in tile order, are the field's reached nodes in ascending global id.  TRG_ERR_INVALID_ARG for cap < 0,
+ * without a retained tiled solve, with a stale one (the tile's graph, the stitch or, for a cost solve, the safety
+ * factor changed since), or for a field outside [0, m). */
+TrgStatus trg_engine_tiled_field_reached(TrgEngine *e, int32_t field,
+    int32_t *gids, float *value, int32_t *hops,   /* room for cap each, any may be NULL */
+    int32_t cap, int32_t *n_out);                 /* n_out may be NULL */
 /* Routes across tiles ("Routes across tiles"): the paths behind the keys of the LAST tiled solve
- * (any of the four calls above, whichever objective), walked on the devices.  A successful tiled solve stays on every rank's device; a new tiled solve
+ * (any of the tiled field calls above, whichever objective), walked on the devices.  A successful tiled solve stays on every rank's device; a new tiled solve
  * replaces it from its start (one that fails leaves none), and a change of the tile's graph, a new stitch or another
  * safety factor makes it stale (a risk solve does not know the safety factor and outlives its change).  A collective
  * call: every rank makes it with the same arguments.

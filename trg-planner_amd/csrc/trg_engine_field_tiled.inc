@@ -11,7 +11,9 @@
 // one entry: the members are seeded by the ranks that own them, and for the set call a third loop of the same frame
 // trades, after the two passes, the owners of the border nodes over the forest of the global parents.
 // A successful solve stays in the work arrays; the routes call ("Routes across tiles") walks its routes on the devices,
-// the fourth use of the frame.
+// the fourth use of the frame.  Under a budget or a settle mode ("Bounded fields across tiles") pass 1 runs under
+// bounds that the ranks lower between the exchanges through bound records in the same stream, and ends with a trim;
+// the reached list of a retained solve is local work.
 
 namespace {
 
@@ -61,6 +63,12 @@ struct TiledFieldBufs {
     FieldDev F{};
   } solved;
   DevArr route_field, route_target, route_off, route_gids, route_info;
+  // Bounded solves ("Bounded fields across tiles"): this rank's settle targets (local ids), the words of TiledSettle --
+  // `told` (FIELD_MAX_SOURCES words), then the table -- with the host copies their uploads read, and the bounds that
+  // pass 1 ended with.  The reached counts per field and the list of trg_engine_tiled_field_reached.
+  DevArr settle, bound_words, reached, list_counts, list_off, list_tmp, list_gids, list_value, list_hops;
+  std::vector<int32_t> h_settle;
+  std::vector<uint32_t> h_bound_words, h_bound;
 };
 
 // What a solve is asked for.  Both calls come as source sets in global ids: one source per field is m sets of one
@@ -85,6 +93,15 @@ struct TiledRequest {
   int32_t n_targets = 0;
   float *cost_at = nullptr;
   int32_t *hops_at = nullptr, *owner_at = nullptr, *owned = nullptr;
+  // The bounded entries ("Bounded fields across tiles"): a budget per field (nullptr: +inf each), the settle mode over
+  // the settle targets -- GLOBAL ids, the same list on every rank -- and the outputs: the bound every field ended with
+  // (m, the same on every rank) and how many of THIS tile's nodes lie within it (m).
+  const float *budget = nullptr;
+  int32_t settle = TRG_FIELD_SETTLE_NONE;
+  const int32_t *settle_gids = nullptr;
+  int32_t n_settle = 0;
+  float *bound_out = nullptr;
+  int32_t *reached_out = nullptr;
 };
 
 // One solve on its way: the request, the kernels' view, and what ends up in the caller's info.
@@ -92,7 +109,12 @@ struct TiledRun {
   const TiledRequest &rq;
   FieldDev F{};
   int n_entries = 0;  // the entries whose member is this rank's node (tb.entries)
-  bool always = false;  // the routes: a tile without nodes still runs its step of every exchange
+  bool always = false;  // the routes, pass 1 under a settle mode: a tile without nodes still runs its step of every exchange
+  // Some budget below +inf, or a settle mode: pass 1 runs under bounds.  Without either the launches, exchanges and
+  // records are those of a solve that knows no bounds.
+  bool bounded = false;
+  FieldBounds budgets{};
+  TiledSettle S{};
   int round = 0;      // of the current pass
   int rounds = 0, exchanges = 0, owner_exchanges = 0, roots = 0;
   long long records = 0, owner_records = 0;
@@ -281,6 +303,40 @@ TrgStatus tiled_graph(TrgEngine *e, const ExchangeState &x, bool risk) {
   return tiled_edge_values(e, risk);
 }
 
+// A bounded solve's own arrays: of the settle targets this rank keeps those that are its nodes, as it does the entries;
+// `told` starts at +inf bits; the table of the ALL rule starts at +inf bits for a rank that owns a settle target and at
+// 0 for one that owns none, which every rank derives alike from the stitch's node offsets.
+TrgStatus tiled_settle_arrays(TrgEngine *e, TiledRun &run) {
+  TiledFieldBufs &tb = *e->tiled;
+  const FieldTiled &T = tb.T;
+  const TiledRequest &rq = run.rq;
+  const ExchangeState &x = *e->exchange;
+  const std::vector<int32_t> &off = e->stitch_node_off;
+  hipStream_t s = e->s_main;
+  const bool settles = rq.settle != TRG_FIELD_SETTLE_NONE;
+  std::vector<int32_t> &mine = tb.h_settle;
+  mine.clear();
+  std::vector<uint32_t> &words = tb.h_bound_words;
+  words.assign((size_t)FIELD_MAX_SOURCES + (size_t)rq.m * STITCH_MAX_TILES, 0u);
+  std::fill(words.begin(), words.begin() + FIELD_MAX_SOURCES, FIELD_INF_BITS);
+  for (int j = 0; settles && j < rq.n_settle; ++j) {
+    const int32_t g = rq.settle_gids[j];
+    const int owner = (int)(std::upper_bound(off.begin(), off.end(), g) - off.begin()) - 1;  // (the last of equal offsets)
+    if (owner < 0 || owner >= x.nranks) continue;  // (never: tiled_check_request)
+    for (int k = 0; k < rq.m; ++k) words[(size_t)FIELD_MAX_SOURCES + (size_t)k * STITCH_MAX_TILES + owner] = FIELD_INF_BITS;
+    if (owner == x.rank) mine.push_back(g - T.lo);
+  }
+  TrgStatus st;
+  if ((st = tiled_grow(e, tb.settle, (mine.size() + 1) * 4)) != TRG_OK ||
+      (st = tiled_grow(e, tb.bound_words, words.size() * 4)) != TRG_OK)
+    return st;
+  if (!mine.empty()) HIPCHK(e, hipMemcpyAsync(tb.settle.p, mine.data(), mine.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipMemcpyAsync(tb.bound_words.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, s));
+  run.S = TiledSettle{rq.settle, tb.settle.as<int>(), (int)mine.size(), x.rank, x.nranks, tb.bound_words.as<unsigned>(),
+                      tb.bound_words.as<unsigned>() + FIELD_MAX_SOURCES};
+  return TRG_OK;
+}
+
 // the work arrays for m fields and the kernels' view of them
 TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
   TiledFieldBufs &tb = *e->tiled;
@@ -302,7 +358,9 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
     if ((st = tiled_grow(e, *a, nN * 4)) != TRG_OK) return st;
   for (DevArr *a : {&tb.cost, &tb.hops, &tb.parent_out})
     if ((st = tiled_grow(e, *a, nO * 4)) != TRG_OK) return st;
-  if ((st = tiled_grow(e, tb.published, nB * 8)) != TRG_OK || (st = tiled_grow(e, tb.rec, nB * FIELD_TILED_REC_BYTES)) != TRG_OK ||
+  const size_t n_bound_rec = run.bounded ? (size_t)rq.m : 0;  // (the bound records of one exchange)
+  if ((st = tiled_grow(e, tb.published, nB * 8)) != TRG_OK ||
+      (st = tiled_grow(e, tb.rec, (nB + n_bound_rec) * FIELD_TILED_REC_BYTES)) != TRG_OK ||
       (st = tiled_grow(e, tb.n_rec, 16)) != TRG_OK || (st = tiled_grow(e, tb.ctrl, sizeof(FieldCtrl))) != TRG_OK)
     return st;
   F.rowptr = tb.rowptr.as<int>();
@@ -339,6 +397,8 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
   if ((st = tiled_grow(e, tb.entries, (mine.size() + 1) * sizeof(TiledEntry))) != TRG_OK) return st;
   if (!mine.empty())
     HIPCHK(e, hipMemcpyAsync(tb.entries.p, mine.data(), mine.size() * sizeof(TiledEntry), hipMemcpyHostToDevice, s));
+  if (run.bounded)
+    if ((st = tiled_settle_arrays(e, run)) != TRG_OK) return st;
   if (!rq.owners) return TRG_OK;
   const size_t nT = (size_t)rq.m * (size_t)rq.n_targets + 4;
   if ((st = tiled_grow(e, tb.set_ptr, ((size_t)rq.m + 2) * 4)) != TRG_OK || (st = tiled_grow(e, tb.owner, nN * 4)) != TRG_OK ||
@@ -377,8 +437,12 @@ TrgStatus tiled_rounds(TrgEngine *e, TiledRun &run) {
   hipStream_t s = e->s_main;
   const long long cap = 4LL * F.N + 64;
   int first = -1;
+  // Pass 1 of a bounded solve runs under bounds without the settle step of a single engine, whose rule needs one
+  // global bucket order: the bounds drop between the exchanges instead ("Bounded fields across tiles").
+  const FieldSettle no_settle{nullptr, 0, FIELD_SETTLE_NONE};
+  const FieldSettle *under_bounds = run.bounded && !F.tight ? &no_settle : nullptr;
   for (;;) {
-    for (int i = 0; i < TILED_BATCH; ++i, ++run.round) launch_field_round(F, run.round, s, nullptr, nullptr, run.rq.risk);
+    for (int i = 0; i < TILED_BATCH; ++i, ++run.round) launch_field_round(F, run.round, s, under_bounds, nullptr, run.rq.risk);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(tb.h_state, &F.ctrl->s, sizeof(FieldState), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
@@ -457,30 +521,52 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
   // the bucket width from the mean edge value of the objective; all risks zero: width 0 ("Risk fields across tiles")
   const double mean = run.rq.risk ? tb.risks.mean : tb.costs.mean;
   const float delta = mean > 0.0 ? (float)(e->field_delta_scale * mean) : 0.0f;
+  // Pass 1 of a bounded solve ("Bounded fields across tiles"): the budgets, then per exchange the bound records of all
+  // ranks into the bounds, the rounds under bounds, the bound step and the bounded publish.  Under a settle mode a tile
+  // without nodes runs the merge of the bound records all the same: it must end with the bounds of the others.
+  const bool bounded = run.bounded && pass == 0;
+  const long long n_settle = bounded && run.rq.settle != TRG_FIELD_SETTLE_NONE ? run.rq.n_settle : 0;
+  run.always = bounded && run.rq.settle != TRG_FIELD_SETTLE_NONE;
   TiledLocal mine(e, local);
   mine.step([&]() -> TrgStatus {
-    if (!work) return TRG_OK;
+    if (!work && !bounded) return TRG_OK;
     F.tight = pass ? tb.tight.as<unsigned>() : nullptr;
     run.round = 0;
     HIPCHK(e, hipEventRecord(tb.t0, s));
-    launch_tiled_begin(F, T, tb.entries.as<TiledEntry>(), run.n_entries, delta, tb.published.as<unsigned long long>(), s);
+    if (work)
+      launch_tiled_begin(F, T, tb.entries.as<TiledEntry>(), run.n_entries, delta, tb.published.as<unsigned long long>(), s);
+    if (bounded) launch_field_bounds(F, run.budgets, s);
     return TRG_OK;
   });
-  // a key of a border item drops at most a few times per item in practice; the cap is the round cap's shape
+  // a key of a border item drops at most a few times per item in practice; the cap is the round cap's shape (under a
+  // settle mode a bound record is news as well: the settle targets count beside the border nodes)
   const TrgStatus st = tiled_exchanges(
-      e, x, run, mine, tiled_what(run.rq.risk), (long long)F.m * T.B, [&](long long border) { return 4 * F.m * border + 64; },
-      run.exchanges, run.records,
+      e, x, run, mine, tiled_what(run.rq.risk), (long long)F.m * T.B + (bounded ? F.m : 0),
+      [&](long long border) { return 4 * F.m * (border + n_settle) + 64; }, run.exchanges, run.records,
       [&](int, const void *d_all, int gathered) -> TrgStatus {
+        if (bounded) launch_tiled_bound_merge(F, run.S, d_all, gathered, s);
+        if (!work) return TRG_OK;  // (a tile without nodes under a settle mode: tb.n_rec stays 0)
         launch_tiled_merge(F, T, d_all, gathered, s);
         if (const TrgStatus r = tiled_rounds(e, run); r != TRG_OK) return r;
-        launch_tiled_publish(F, T, nullptr, tb.published.as<unsigned long long>(), tb.rec.p, tb.n_rec.as<int>(), s);
+        if (bounded)
+          launch_tiled_publish_bounded(F, T, run.S, tb.published.as<unsigned long long>(), tb.rec.p, tb.n_rec.as<int>(), s);
+        else
+          launch_tiled_publish(F, T, nullptr, tb.published.as<unsigned long long>(), tb.rec.p, tb.n_rec.as<int>(), s);
         return TRG_OK;
       });
+  run.always = false;
   if (st != TRG_OK) return st;
   if (work) {
     run.rounds += tb.h_state->rounds;
+    // the keys between the final bound and an earlier one go, ghosts included, before they become tight words
+    if (bounded) launch_field_trim(F, s);
     if (pass == 0) launch_field_cost_bits(F, tb.tight.as<unsigned>(), s);
     HIPCHK(e, hipGetLastError());
+  }
+  if (bounded) {  // the same words on every rank: the budgets, lowered by the same bound records
+    tb.h_bound.assign(FIELD_MAX_SOURCES, FIELD_INF_BITS);
+    HIPCHK(e, hipMemcpyAsync(tb.h_bound.data(), F.ctrl->bound, (size_t)F.m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
   }
   return TRG_OK;
 }
@@ -533,6 +619,11 @@ TrgStatus tiled_outputs(TrgEngine *e, TiledRun &run) {
   hipStream_t s = e->s_main;
   const int n_entries = rq.set_ptr[rq.m];
   if (rq.owned) std::fill(rq.owned, rq.owned + n_entries, 0);  // (a tile without nodes owns none)
+  if (rq.reached_out) std::fill(rq.reached_out, rq.reached_out + rq.m, 0);
+  if (rq.bound_out)
+    for (int k = 0; k < rq.m; ++k) rq.bound_out[k] = bits_float(run.bounded ? tb.h_bound[k] : FIELD_INF_BITS);
+  if (rq.reached_out && run.F.N > 0 && T.V > 0)
+    if (const TrgStatus st = tiled_grow(e, tb.reached, ((size_t)rq.m + 1) * sizeof(int)); st != TRG_OK) return st;
   if (run.F.N > 0 && T.V > 0) {
     const size_t nO = (size_t)rq.m * T.V, nT = (size_t)rq.m * (size_t)rq.n_targets;
     HIPCHK(e, hipEventRecord(tb.t0, s));
@@ -547,8 +638,11 @@ TrgStatus tiled_outputs(TrgEngine *e, TiledRun &run) {
       launch_field_gather(run.F, &S, tb.targets.as<int>(), rq.n_targets, rq.cost_at ? tb.cost_at.as<float>() : nullptr,
                           rq.hops_at ? tb.hops_at.as<int>() : nullptr, rq.owner_at ? tb.owner_at.as<int>() : nullptr, s);
     }
+    if (rq.reached_out) launch_tiled_reached(run.F, T, tb.reached.as<int>(), s);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipEventRecord(tb.t1, s));
+    if (rq.reached_out)
+      HIPCHK(e, hipMemcpyAsync(rq.reached_out, tb.reached.p, (size_t)rq.m * sizeof(int), hipMemcpyDeviceToHost, s));
     if (rq.cost) HIPCHK(e, hipMemcpyAsync(rq.cost, tb.cost.p, nO * sizeof(float), hipMemcpyDeviceToHost, s));
     if (rq.hops) HIPCHK(e, hipMemcpyAsync(rq.hops, tb.hops.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
     if (rq.parent) HIPCHK(e, hipMemcpyAsync(rq.parent, tb.parent_out.p, nO * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -571,6 +665,13 @@ TrgStatus tiled_outputs(TrgEngine *e, TiledRun &run) {
 TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
   ExchangeState &x = *e->exchange;
   if (e->tiled) e->tiled->solved = TiledFieldBufs::Solved{};  // (a solve that fails retains nothing)
+  // the budgets as cost bits; every rank decides alike whether the solve is a bounded one
+  for (int k = 0; k < run.rq.m; ++k) {
+    const float b = run.rq.budget ? run.rq.budget[k] : std::numeric_limits<float>::infinity();
+    run.budgets.bits[k] = b == 0.0f ? 0u : float_bits(b);  // (-0.0 orders as +0.0)
+    run.bounded = run.bounded || run.budgets.bits[k] != FIELD_INF_BITS;
+  }
+  run.bounded = run.bounded || run.rq.settle != TRG_FIELD_SETTLE_NONE;
   TrgStatus local = tiled_prepare(e, x, run);
   for (int pass = 0; pass < 2; ++pass) {
     const TrgStatus st = tiled_pass(e, x, run, local, pass);
@@ -613,6 +714,68 @@ TrgStatus tiled_check_request(TrgEngine *e, const TiledRequest &rq) {
     }
   if (rq.n_targets < 0 || (rq.n_targets > 0 && !rq.targets))
     return refuse("n_targets < 0, or targets is null with n_targets > 0");
+  // the bounded entries' own arguments (the others leave them at their defaults)
+  if (rq.budget)
+    for (int k = 0; k < rq.m; ++k)
+      if (!(rq.budget[k] >= 0.0f)) return refuse("the budget of field " + std::to_string(k) + " is negative or NaN");
+  if (rq.settle != TRG_FIELD_SETTLE_NONE && rq.settle != TRG_FIELD_SETTLE_ANY && rq.settle != TRG_FIELD_SETTLE_ALL)
+    return refuse("settle " + std::to_string(rq.settle) + " is no TRG_FIELD_SETTLE_* value");
+  if (rq.settle != TRG_FIELD_SETTLE_NONE) {
+    if (rq.n_settle <= 0 || !rq.settle_gids) return refuse("a settle mode needs settle targets (n_settle > 0 and settle_gids)");
+    for (int j = 0; j < rq.n_settle; ++j)
+      if (rq.settle_gids[j] < 0 || rq.settle_gids[j] >= n_ids)
+        return refuse("settle target " + std::to_string(j) + " (" + std::to_string(rq.settle_gids[j]) + ") is outside [0, " +
+                      std::to_string(n_ids) + ")");
+  }
+  return TRG_OK;
+}
+
+// The reached list of one field of the retained tiled solve over THIS tile's nodes ("Bounded fields across tiles"):
+// count, scan and emit on the device, global ids ascending.  Local work, no collective.
+TrgStatus tiled_field_reached(TrgEngine *e, int32_t field, int32_t *gids, float *value, int32_t *hops, int32_t cap,
+                              int32_t *n_out) {
+  const std::string what = "tiled field reached: ";
+  const auto refuse = [&](const std::string &why) { return e->fail(TRG_ERR_INVALID_ARG, what + why); };
+  if (cap < 0) return refuse("cap < 0");
+  if (!e->tiled || !e->tiled->solved.valid) return refuse("no tiled solve is retained (a tiled field call first)");
+  TiledFieldBufs &tb = *e->tiled;
+  if (tb.version != e->graph_version || tb.serial != e->stitch_serial ||
+      (!tb.solved.risk && tb.solved.sf_bits != float_bits(e->prm.safety_factor)))
+    return refuse("the retained tiled solve is stale (the tile's graph, the stitch or the safety factor changed since)");
+  const FieldDev &F = tb.solved.F;
+  const FieldTiled &T = tb.T;
+  if (field < 0 || field >= tb.solved.m)
+    return refuse("field " + std::to_string(field) + " out of range (the solve has " + std::to_string(tb.solved.m) + ")");
+  if (n_out) *n_out = 0;
+  if (T.V <= 0 || F.N <= 0) return TRG_OK;  // (a tile without nodes)
+  const bool want = cap > 0 && (gids || value || hops);
+  const int room = want ? std::min<int>(cap, T.V) : 0;
+  const size_t nb = ((size_t)T.V + 255) / 256;
+  TrgStatus st;
+  if ((st = tiled_grow(e, tb.list_counts, (nb + 1) * sizeof(int))) != TRG_OK ||
+      (st = tiled_grow(e, tb.list_off, (nb + 1) * sizeof(int))) != TRG_OK ||
+      (st = tiled_grow(e, tb.list_tmp, (nb / 2048 + 8) * sizeof(int))) != TRG_OK)
+    return st;
+  if (gids && (st = tiled_grow(e, tb.list_gids, ((size_t)room + 4) * sizeof(int))) != TRG_OK) return st;
+  if (value && (st = tiled_grow(e, tb.list_value, ((size_t)room + 4) * sizeof(float))) != TRG_OK) return st;
+  if (hops && (st = tiled_grow(e, tb.list_hops, ((size_t)room + 4) * sizeof(int))) != TRG_OK) return st;
+  hipStream_t s = e->s_main;
+  launch_tiled_reached_list(F, T, field, tb.list_counts.as<int>(), tb.list_off.as<int>(), tb.list_tmp.as<int>(), room,
+                            gids ? tb.list_gids.as<int>() : nullptr, value ? tb.list_value.as<float>() : nullptr,
+                            hops ? tb.list_hops.as<int>() : nullptr, s);
+  HIPCHK(e, hipGetLastError());
+  int total = 0;
+  HIPCHK(e, hipMemcpyAsync(&total, tb.list_off.as<int>() + nb, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  if (total < 0 || total > T.V) return e->fail(TRG_ERR_DEVICE, what + "bad count");
+  const size_t n = (size_t)std::min(total, room);
+  if (n > 0) {
+    if (gids) HIPCHK(e, hipMemcpyAsync(gids, tb.list_gids.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (value) HIPCHK(e, hipMemcpyAsync(value, tb.list_value.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (hops) HIPCHK(e, hipMemcpyAsync(hops, tb.list_hops.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+  }
+  if (n_out) *n_out = total;
   return TRG_OK;
 }
 
@@ -635,6 +798,38 @@ TrgStatus tiled_call(TrgEngine *e, const TiledRequest &rq, Info *info, More more
   out.ms_device = (float)run.ms_device;
   out.ms_total = (float)ms_since(t_total);
   return TRG_OK;
+}
+
+// The bounded entries of both objectives ("Bounded fields across tiles"): the set call's request with the `owners` flag
+// that every rank passes alike -- the owner pass is a collective -- and the bounds.  Without owners the outputs that
+// hang on the owner pass (owner, the targets' reads, owned) are neither read nor written: the single-source form.
+TrgStatus tiled_bounded_call(TrgEngine *e, int32_t m, const int32_t *set_ptr, const int32_t *set_gids,
+                             const float *set_cost0, bool owners, bool risk, const char *what, const float *budget,
+                             int32_t settle, const int32_t *settle_gids, int32_t n_settle, float *value, int32_t *hops,
+                             int32_t *parent, int32_t *owner, const int32_t *targets, int32_t n_targets, float *value_at,
+                             int32_t *hops_at, int32_t *owner_at, int32_t *owned, float *bound_out, int32_t *reached_out,
+                             TrgTiledSetInfo *info) {
+  TiledRequest rq{m, set_ptr, set_gids, set_cost0, value, hops, parent, owners, risk, what, "null set_ptr or set_gids", nullptr};
+  if (owners) {
+    rq.owner = owner;
+    rq.targets = targets;
+    rq.n_targets = n_targets;
+    rq.cost_at = value_at;
+    rq.hops_at = hops_at;
+    rq.owner_at = owner_at;
+    rq.owned = owned;
+  }
+  rq.budget = budget;
+  rq.settle = settle;
+  rq.settle_gids = settle_gids;
+  rq.n_settle = n_settle;
+  rq.bound_out = bound_out;
+  rq.reached_out = reached_out;
+  return tiled_call(e, rq, info, [](TrgTiledSetInfo &out, const TiledRun &run) {
+    out.owner_exchanges = run.owner_exchanges;
+    out.roots = run.roots;
+    out.owner_records_sent = run.owner_records;
+  });
 }
 
 TrgStatus stitch_ids(TrgEngine *e, int32_t *first_gid, int32_t *num_nodes, int32_t *total_nodes) {
@@ -888,6 +1083,38 @@ TrgStatus trg_engine_tiled_risk_field_sets(TrgEngine *e, int32_t m, const int32_
       out.owner_records_sent = run.owner_records;
     });
   });
+}
+
+TrgStatus trg_engine_tiled_cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *set_ptr, const int32_t *set_gids,
+                                              const float *set_cost0, int32_t owners, const float *budget, int32_t settle,
+                                              const int32_t *settle_gids, int32_t n_settle, float *cost, int32_t *hops,
+                                              int32_t *parent, int32_t *owner, const int32_t *targets, int32_t n_targets,
+                                              float *cost_at, int32_t *hops_at, int32_t *owner_at, int32_t *owned,
+                                              float *bound_out, int32_t *reached_out, TrgTiledSetInfo *info) {
+  return entry(e, "tiled_cost_field_bounded", DEVICE, [&] {
+    return tiled_bounded_call(e, m, set_ptr, set_gids, set_cost0, owners != 0, false, "tiled cost field bounded: ", budget,
+                              settle, settle_gids, n_settle, cost, hops, parent, owner, targets, n_targets, cost_at,
+                              hops_at, owner_at, owned, bound_out, reached_out, info);
+  });
+}
+
+TrgStatus trg_engine_tiled_risk_field_bounded(TrgEngine *e, int32_t m, const int32_t *set_ptr, const int32_t *set_gids,
+                                              int32_t owners, const float *budget, int32_t settle,
+                                              const int32_t *settle_gids, int32_t n_settle, float *risk, int32_t *hops,
+                                              int32_t *parent, int32_t *owner, const int32_t *targets, int32_t n_targets,
+                                              float *risk_at, int32_t *hops_at, int32_t *owner_at, int32_t *owned,
+                                              float *bound_out, int32_t *reached_out, TrgTiledSetInfo *info) {
+  return entry(e, "tiled_risk_field_bounded", DEVICE, [&] {
+    return tiled_bounded_call(e, m, set_ptr, set_gids, nullptr, owners != 0, true, "tiled risk field bounded: ", budget,
+                              settle, settle_gids, n_settle, risk, hops, parent, owner, targets, n_targets, risk_at,
+                              hops_at, owner_at, owned, bound_out, reached_out, info);
+  });
+}
+
+TrgStatus trg_engine_tiled_field_reached(TrgEngine *e, int32_t field, int32_t *gids, float *value, int32_t *hops,
+                                         int32_t cap, int32_t *n_out) {
+  return entry(e, "tiled_field_reached", DEVICE,
+               [&] { return tiled_field_reached(e, field, gids, value, hops, cap, n_out); });
 }
 
 TrgStatus trg_engine_tiled_field_routes(TrgEngine *e, int32_t n_routes, const int32_t *route_field,

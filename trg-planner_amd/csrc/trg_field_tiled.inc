@@ -16,7 +16,10 @@
 // over this rank's own entries.  The set call adds, after the parent sweep, the owner pass: k_tiled_forest_begin, the
 // jumping sweeps of trg_field.hip, then per exchange k_tiled_owner_merge / _resolve and the publish kernel again;
 // k_tiled_output writes the owners beside the fields and k_tiled_owned the counts per entry.  The routes of a finished
-// solve ("Routes across tiles"): k_tiled_route_len, k_tiled_route_step and k_tiled_route_end.
+// solve ("Routes across tiles"): k_tiled_route_len, k_tiled_route_step and k_tiled_route_end.  Pass 1 of a bounded
+// solve ("Bounded fields across tiles"): k_tiled_bound, the bounded form of k_tiled_publish, k_tiled_bound_merge and
+// k_tiled_bound_fold around trg_field.hip's BOUNDED round kernels; k_tiled_reached and k_tiled_list_count / _emit list
+// a rank's own reached nodes.
 //
 // All kernels: wave64, bounds taken from the arguments, no scalar memory writes, nothing waits on another workgroup.
 
@@ -178,10 +181,15 @@ __global__ __launch_bounds__(THREADS) void k_tiled_seed(FieldDev F, const TiledE
 // `published` has m * B words, `rec` room for as many records.  A pass (`owner` is not read): the key is news where it
 // is below what this rank last published, and travels.  OWNERS, the owner pass: the owner is news once it is known, and
 // travels in the key word; the published word is all ones until then, so that an item is published once.
-template <bool OWNERS>
+// BOUNDED, pass 1 of a bounded solve ("Bounded fields across tiles"): a key above its field's current bound is not news
+// -- the bound only drops, so it never becomes news -- and the records follow the bound records that k_tiled_bound
+// wrote, so the stream has room for m more.
+template <bool OWNERS, bool BOUNDED = false>
 __global__ __launch_bounds__(THREADS) void k_tiled_publish(FieldDev F, FieldTiled T, const int *__restrict__ owner,
                                                            unsigned long long *published, TiledRec *rec, int *n_rec) {
+  static_assert(!(OWNERS && BOUNDED), "the owner pass knows no bounds");
   const int items = F.m * T.B;
+  const int room = BOUNDED ? items + F.m : items;
   const int n_iter = (items + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
   for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
     bool news = false;
@@ -197,6 +205,7 @@ __global__ __launch_bounds__(THREADS) void k_tiled_publish(FieldDev F, FieldTile
       } else {
         r.key = F.key[item];
         news = r.key < published[i];
+        if constexpr (BOUNDED) news = news && key_cost_bits(r.key) <= F.ctrl->bound[f];
       }
       if (news) {
         published[i] = OWNERS ? 0ull : r.key;
@@ -205,7 +214,126 @@ __global__ __launch_bounds__(THREADS) void k_tiled_publish(FieldDev F, FieldTile
       }
     }
     const int slot = wave_reserve(news, n_rec);
-    if (news && slot < items) rec[slot] = r;
+    if (news && slot < room) rec[slot] = r;
+  }
+}
+
+// ---- bounded fields across tiles (DESIGN.md section 7, "Bounded fields across tiles") --------------------------------
+
+constexpr unsigned TILED_INF_BITS = 0x7f800000u;  // the cost word that stands for "no key" among settle values
+
+// The bound step of one rank, one block per field, after its rounds went quiet and before its publish.  Over the settle
+// targets that are THIS rank's nodes (local ids, n_t > 0): the least (ANY) or greatest (ALL) cost word of their keys,
+// +inf bits for a target without one.  Every key is the fold of a real walk, so the value is an upper bound on what the
+// definition's settle value takes from these targets, and it only drops.  ANY lowers the field's bound at once (only
+// this block writes the word, and no other kernel runs beside it).  A value below what this rank last told the others
+// becomes a bound record (field, -1 - rank, value in the key's high word) at the head of the record stream, which the
+// host emptied before this launch.
+template <bool ALL>
+__global__ __launch_bounds__(THREADS) void k_tiled_bound(FieldDev F, const int *__restrict__ targets, int n_t, int rank,
+                                                         unsigned *told, TiledRec *rec, int *n_rec, int room) {
+  __shared__ unsigned s_v[THREADS / WAVE];
+  const int f = blockIdx.x;
+  const int fbase = f * F.V;
+  unsigned v = ALL ? 0u : TILED_INF_BITS;
+  for (int j = threadIdx.x; j < n_t; j += blockDim.x) {
+    const int t = targets[j];
+    unsigned c = TILED_INF_BITS;
+    if (t >= 0 && t < F.V) {
+      const unsigned long long k = F.key[fbase + t];
+      if (k != FIELD_KEY_NONE) c = key_cost_bits(k);
+    }
+    v = ALL ? max(v, c) : min(v, c);
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned o = (unsigned)__shfl_xor((int)v, m);
+    v = ALL ? max(v, o) : min(v, o);
+  }
+  if (lane_id() == 0) s_v[threadIdx.x / WAVE] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < THREADS / WAVE; ++w) v = ALL ? max(v, s_v[w]) : min(v, s_v[w]);
+    if (!ALL && v < F.ctrl->bound[f]) F.ctrl->bound[f] = v;
+    if (v < told[f]) {
+      told[f] = v;
+      const int slot = atomicAdd(n_rec, 1);
+      if (slot < room) rec[slot] = TiledRec{f, -1 - rank, (unsigned long long)v << 32};
+    }
+  }
+}
+
+// One thread per gathered record, on every rank and over the records of all ranks, its own included: a bound record
+// (gid < 0) lowers its field's bound (ANY), or takes its rank's place in the field's row of the table (ALL; a rank
+// tells a field's value once per exchange, so one thread writes the word).  The key merge ignores these records: their
+// gid names no node.
+template <bool ALL>
+__global__ __launch_bounds__(THREADS) void k_tiled_bound_merge(FieldDev F, const TiledRec *__restrict__ rec, int n_rec,
+                                                               int n_ranks, unsigned *table) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += gridDim.x * blockDim.x) {
+    const TiledRec r = rec[i];
+    const int rank = -1 - r.gid;
+    if (r.gid >= 0 || rank >= n_ranks || r.field < 0 || r.field >= F.m) continue;
+    const unsigned v = (unsigned)(r.key >> 32);
+    if constexpr (ALL) table[r.field * STITCH_MAX_TILES + rank] = v;
+    else atomicMin(&F.ctrl->bound[r.field], v);
+  }
+}
+
+// ALL, after the merge: one thread per field folds its row of the table -- +inf bits for a rank that owns a settle
+// target and has told nothing yet, 0 for a rank that owns none -- and lowers the field's bound to the greatest entry.
+__global__ void k_tiled_bound_fold(FieldDev F, int n_ranks, const unsigned *__restrict__ table) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= F.m) return;
+  unsigned v = 0u;
+  for (int r = 0; r < n_ranks; ++r) v = max(v, table[f * STITCH_MAX_TILES + r]);
+  if (v < F.ctrl->bound[f]) F.ctrl->bound[f] = v;
+}
+
+// grid.y = field: how many of this rank's OWN nodes have a key (the single-engine count would take the ghosts in), one
+// atomicAdd per wave
+__global__ __launch_bounds__(THREADS) void k_tiled_reached(FieldDev F, FieldTiled T, int *counts) {
+  const int fbase = blockIdx.y * F.V;
+  const int n_iter = (T.V + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, v = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, v += gridDim.x * blockDim.x) {
+    const unsigned long long mk = ballot(v < T.V && F.key[fbase + v] != FIELD_KEY_NONE);
+    if (mk && lane_id() == __ffsll(mk) - 1) atomicAdd(&counts[blockIdx.y], __popcll(mk));
+  }
+}
+
+// The reached list of one field over this rank's own nodes: k_field_list_count / k_field_list_emit restricted to
+// v < T.V, emitting global ids.  Block b covers the nodes [b * THREADS, (b + 1) * THREADS).
+__global__ __launch_bounds__(THREADS) void k_tiled_list_count(FieldDev F, FieldTiled T, int field, int *counts) {
+  __shared__ int s_n[THREADS / WAVE];
+  const int v = blockIdx.x * THREADS + threadIdx.x;
+  const bool has = v < T.V && F.key[field * F.V + v] != FIELD_KEY_NONE;
+  const unsigned long long m = ballot(has);
+  if (lane_id() == 0) s_n[threadIdx.x / WAVE] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int n = 0;
+    for (int w = 0; w < THREADS / WAVE; ++w) n += s_n[w];
+    counts[blockIdx.x] = n;
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void k_tiled_list_emit(FieldDev F, FieldTiled T, int field,
+                                                             const int *__restrict__ offsets, int cap, int *gids,
+                                                             float *value, int *hops) {
+  __shared__ int s_n[THREADS / WAVE];
+  const int v = blockIdx.x * THREADS + threadIdx.x;
+  unsigned long long k = FIELD_KEY_NONE;
+  if (v < T.V) k = F.key[field * F.V + v];
+  const bool has = k != FIELD_KEY_NONE;
+  const unsigned long long m = ballot(has);
+  if (lane_id() == 0) s_n[threadIdx.x / WAVE] = __popcll(m);
+  __syncthreads();
+  int pos = offsets[blockIdx.x] + __popcll(m & ((1ull << lane_id()) - 1ull));
+  for (int w = 0; w < (int)threadIdx.x / WAVE; ++w) pos += s_n[w];
+  if (has && pos < cap) {
+    if (gids) gids[pos] = T.lo + v;
+    if (value) value[pos] = key_cost(k);
+    if (hops) hops[pos] = (int)(unsigned)k;
   }
 }
 
@@ -598,6 +726,51 @@ void launch_tiled_publish(const FieldDev &F, const FieldTiled &T, const int *own
   TiledRec *out = (TiledRec *)rec;
   if (owner) hipLaunchKernelGGL(k_tiled_publish<true>, grid, dim3(THREADS), 0, s, F, T, owner, published, out, n_rec);
   else hipLaunchKernelGGL(k_tiled_publish<false>, grid, dim3(THREADS), 0, s, F, T, owner, published, out, n_rec);
+}
+
+void launch_tiled_publish_bounded(const FieldDev &F, const FieldTiled &T, const TiledSettle &S,
+                                  unsigned long long *published, void *rec, int *n_rec, hipStream_t s) {
+  (void)hipMemsetAsync(n_rec, 0, sizeof(int), s);
+  if (F.N <= 0) return;
+  TiledRec *out = (TiledRec *)rec;
+  const int room = F.m * T.B + F.m;
+  if (S.mode == FIELD_SETTLE_ANY && S.n_t > 0)
+    hipLaunchKernelGGL(k_tiled_bound<false>, dim3(F.m), dim3(THREADS), 0, s, F, S.targets, S.n_t, S.rank, S.told, out,
+                       n_rec, room);
+  else if (S.mode == FIELD_SETTLE_ALL && S.n_t > 0)
+    hipLaunchKernelGGL(k_tiled_bound<true>, dim3(F.m), dim3(THREADS), 0, s, F, S.targets, S.n_t, S.rank, S.told, out,
+                       n_rec, room);
+  if (T.B > 0)
+    hipLaunchKernelGGL((k_tiled_publish<false, true>), dim3(field_blocks((long long)F.m * T.B, THREADS)), dim3(THREADS),
+                       0, s, F, T, (const int *)nullptr, published, out, n_rec);
+}
+
+void launch_tiled_bound_merge(const FieldDev &F, const TiledSettle &S, const void *rec, int n_rec, hipStream_t s) {
+  if (n_rec <= 0 || S.mode == FIELD_SETTLE_NONE) return;
+  const dim3 grid(field_blocks(n_rec, THREADS));
+  if (S.mode == FIELD_SETTLE_ANY) {
+    hipLaunchKernelGGL(k_tiled_bound_merge<false>, grid, dim3(THREADS), 0, s, F, (const TiledRec *)rec, n_rec,
+                       S.n_ranks, S.table);
+    return;
+  }
+  hipLaunchKernelGGL(k_tiled_bound_merge<true>, grid, dim3(THREADS), 0, s, F, (const TiledRec *)rec, n_rec, S.n_ranks,
+                     S.table);
+  hipLaunchKernelGGL(k_tiled_bound_fold, dim3(1), dim3(FIELD_MAX_SOURCES), 0, s, F, S.n_ranks, S.table);
+}
+
+void launch_tiled_reached(const FieldDev &F, const FieldTiled &T, int *counts, hipStream_t s) {
+  (void)hipMemsetAsync(counts, 0, (size_t)F.m * sizeof(int), s);
+  if (T.V > 0 && F.N > 0)
+    hipLaunchKernelGGL(k_tiled_reached, dim3(field_blocks(T.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, counts);
+}
+
+void launch_tiled_reached_list(const FieldDev &F, const FieldTiled &T, int field, int *counts, int *offsets, int *tmp,
+                               int cap, int *gids, float *value, int *hops, hipStream_t s) {
+  const int nb = (T.V + THREADS - 1) / THREADS;
+  hipLaunchKernelGGL(k_tiled_list_count, dim3(nb), dim3(THREADS), 0, s, F, T, field, counts);
+  launch_exclusive_scan(counts, offsets, nb, tmp, s);
+  if (cap > 0 && (gids || value || hops))
+    hipLaunchKernelGGL(k_tiled_list_emit, dim3(nb), dim3(THREADS), 0, s, F, T, field, offsets, cap, gids, value, hops);
 }
 
 void launch_tiled_merge(const FieldDev &F, const FieldTiled &T, const void *rec, int n_rec, hipStream_t s) {

@@ -667,6 +667,31 @@ void launch_tiled_publish(const FieldDev &F, const FieldTiled &T, const int *own
                           void *rec, int *n_rec, hipStream_t s);
 // the gathered records of all ranks into this rank's ghosts; what improved is queued for launch_field_round
 void launch_tiled_merge(const FieldDev &F, const FieldTiled &T, const void *rec, int n_rec, hipStream_t s);
+// Bounded fields across tiles ("Bounded fields across tiles"): pass 1 of a bounded tiled solve runs
+// launch_field_round under bounds with the settle mode NONE, and lowers the bounds between the exchanges from the keys
+// the settle targets hold.  targets: the settle targets that are THIS rank's nodes, local ids (device).  told: per field
+// the value this rank last put into a bound record, +inf bits at first.  table (ALL): m rows of STITCH_MAX_TILES words,
+// the ranks' last values -- at first +inf bits for a rank that owns a settle target, 0 for one that owns none.
+struct TiledSettle {
+  int mode;  // FIELD_SETTLE_*
+  const int *targets;
+  int n_t;
+  int rank, n_ranks;
+  unsigned *told, *table;
+};
+// launch_tiled_publish's pass form for pass 1 of a bounded solve: *n_rec is zeroed, the bound step writes this rank's
+// bound records (field, -1 - rank, value << 32; ANY lowers F.ctrl->bound at once), then the border keys with news that
+// lie within their field's bound follow.  m * B + m records at most.
+void launch_tiled_publish_bounded(const FieldDev &F, const FieldTiled &T, const TiledSettle &S,
+                                  unsigned long long *published, void *rec, int *n_rec, hipStream_t s);
+// the bound records among the gathered records of all ranks into F.ctrl->bound; runs on a rank without nodes as well
+void launch_tiled_bound_merge(const FieldDev &F, const TiledSettle &S, const void *rec, int n_rec, hipStream_t s);
+// counts[k] (m ints, zeroed here) = this rank's OWN nodes with a key in field k
+void launch_tiled_reached(const FieldDev &F, const FieldTiled &T, int *counts, hipStream_t s);
+// launch_field_reached_list over this rank's own nodes (T.V > 0), emitting GLOBAL ids: counts (T.V + 255) / 256 ints,
+// offsets one more (the last is the total), tmp (T.V / 256) / 2048 + 8
+void launch_tiled_reached_list(const FieldDev &F, const FieldTiled &T, int field, int *counts, int *offsets, int *tmp,
+                               int cap, int *gids, float *value, int *hops, hipStream_t s);
 // parents as least global ids (when asked for), then cost / hops / parent of the local nodes, m x T.V, and with
 // owner_out (else nullptr) their owners from `owner`, the owner pass's m x (V + G) words
 void launch_tiled_finish(const FieldDev &F, const FieldTiled &T, float *cost, int *hops, int *parent, bool parents,

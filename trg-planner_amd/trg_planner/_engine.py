@@ -141,6 +141,7 @@ EXPORTS = [
     "trg_engine_pose_links", "trg_engine_cost_field_seeded",
     "trg_engine_tiled_cost_field", "trg_engine_stitch_ids", "trg_engine_tiled_cost_field_sets",
     "trg_engine_tiled_field_routes", "trg_engine_tiled_risk_field", "trg_engine_tiled_risk_field_sets",
+    "trg_engine_tiled_cost_field_bounded", "trg_engine_tiled_risk_field_bounded", "trg_engine_tiled_field_reached",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -254,6 +255,13 @@ def load_library():
     L.trg_engine_tiled_risk_field.argtypes = L.trg_engine_tiled_cost_field.argtypes
     L.trg_engine_tiled_risk_field_sets.argtypes = [vp, C.c_int32, ip, ip, fp, ip, ip, ip, ip, C.c_int32, fp, ip, ip, ip,
                                                    C.POINTER(TrgTiledSetInfo)]
+    L.trg_engine_tiled_cost_field_bounded.argtypes = [vp, C.c_int32, ip, ip, fp, C.c_int32, fp, C.c_int32, ip, C.c_int32,
+                                                      fp, ip, ip, ip, ip, C.c_int32, fp, ip, ip, ip, fp, ip,
+                                                      C.POINTER(TrgTiledSetInfo)]
+    L.trg_engine_tiled_risk_field_bounded.argtypes = [vp, C.c_int32, ip, ip, C.c_int32, fp, C.c_int32, ip, C.c_int32,
+                                                      fp, ip, ip, ip, ip, C.c_int32, fp, ip, ip, ip, fp, ip,
+                                                      C.POINTER(TrgTiledSetInfo)]
+    L.trg_engine_tiled_field_reached.argtypes = [vp, C.c_int32, ip, fp, ip, C.c_int32, ip]
     L.trg_engine_tiled_field_routes.argtypes = [vp, C.c_int32, ip, ip, ip, ip, fp, C.c_int32,
                                                 C.POINTER(TrgTiledRouteInfo), C.POINTER(TrgTiledRoutesInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
@@ -507,6 +515,92 @@ class Engine:
         out["info"] = info
         return out
 
+    def _tiled_bounded(self, value, who, sets, start_costs, owners, budget, settle, settle_gids, targets, full, parent):
+        """The bounded tiled entries of either objective (`value`: "cost" or "risk"; DESIGN.md section 7, "Bounded fields
+        across tiles"): sets of GLOBAL ids, `owners` as every rank passes it, budget (a value or one per field, None:
+        +inf), settle ("any" / "all" / None) over the GLOBAL ids settle_gids.  -> _tiled_fields_from's dict (without
+        owners: "owner", "owned" and the targets' reads are absent) plus "bound" (m float32, the same on every rank)
+        and "reached" (m int32: THIS tile's nodes within the bound)."""
+        _check_settle(who, settle)
+        sets, ptr, ids, starts, c0 = pack_sets(who, sets, start_costs)
+        m = len(sets)
+        offset, V = self._tiled_ids()
+        rows = max(m, 1)
+        at = value + "_at"
+        out = dict(offset=offset, sets=sets)
+        if value == "cost":
+            out["start_costs"] = starts
+        if full:
+            out.update({value: np.empty((rows, V), np.float32), "hops": np.empty((rows, V), np.int32),
+                        "parent": np.empty((rows, V), np.int32) if parent else None})
+            if owners:
+                out["owner"] = np.empty((rows, V), np.int32)
+        tg, n_t = None, 0
+        if targets is not None and owners:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+            n_t = int(tg.shape[0])
+            out.update({at: np.empty((rows, n_t), np.float32), "hops_at": np.empty((rows, n_t), np.int32),
+                        "owner_at": np.empty((rows, n_t), np.int32)})
+        bud = None
+        if budget is not None:
+            bud = np.ascontiguousarray(np.broadcast_to(np.asarray(budget, dtype=np.float32).reshape(-1), (rows,)))
+        sg = np.ascontiguousarray([] if settle_gids is None else settle_gids, dtype=np.int32).reshape(-1)
+        out["bound"] = np.empty(rows, np.float32)
+        out["reached"] = np.zeros(rows, np.int32)
+        owned, split_owned = _owned_buffer(ptr)
+        info = TrgTiledSetInfo()
+        arr = lambda name, conv: None if out.get(name) is None else conv(out[name])  # noqa: E731
+        entry = self.L.trg_engine_tiled_cost_field_bounded if value == "cost" else self.L.trg_engine_tiled_risk_field_bounded
+        self._chk(entry(
+            self.h, m, _i(ptr), _i(ids), *((None if c0 is None else _f(c0),) if value == "cost" else ()),
+            1 if owners else 0, None if bud is None else _f(bud), _SETTLE[settle], _i(sg) if sg.shape[0] else None,
+            int(sg.shape[0]), arr(value, _f), arr("hops", _i), arr("parent", _i), arr("owner", _i),
+            None if tg is None or n_t == 0 else _i(tg), n_t, arr(at, _f), arr("hops_at", _i), arr("owner_at", _i),
+            _i(owned) if owners else None, _f(out["bound"]), _i(out["reached"]), C.byref(info)))
+        if owners:
+            out["owned"] = split_owned()
+        out["info"] = info
+        return out
+
+    def _tiled_fields_bounded(self, value, who, source_gids, parent, budget, settle, settle_gids, full=True):
+        """The single-source forms under bounds: m sets of one entry through the bounded entry, owners off ->
+        _tiled_fields' dict plus "bound" and "reached"."""
+        src = np.ascontiguousarray(source_gids, dtype=np.int32).reshape(-1)
+        r = self._tiled_bounded(value, who, [[int(g)] for g in src], None, False, budget, settle, settle_gids, None, full,
+                                parent)
+        out = {"offset": r["offset"], "info": r["info"], "bound": r["bound"], "reached": r["reached"]}
+        if full:
+            out.update({value: r[value], "hops": r["hops"], "parent": r["parent"]})
+        return out
+
+    def tiled_field_reached(self, field=0, cap=None):
+        """THIS tile's reached nodes of field `field` of the last tiled solve (trg_engine_tiled_field_reached), compacted
+        on the device: local work, no collective.  cap: room for that many nodes (None: a first call for the count,
+        then one with exactly enough room; 0: the count alone) -> dict with "gids" (ascending global ids), the
+        values under "value", "hops" -- the first min(cap, count) each -- and "count".  tiled.concat_reached joins the
+        ranks' lists."""
+        n = C.c_int32(0)
+        if cap is None or int(cap) == 0:
+            self._chk(self.L.trg_engine_tiled_field_reached(self.h, int(field), None, None, None, 0, C.byref(n)))
+            if cap is not None or n.value == 0:
+                return dict(gids=np.empty(0, np.int32), value=np.empty(0, np.float32), hops=np.empty(0, np.int32),
+                            count=int(n.value))
+            cap = n.value
+        cap = int(cap)
+        gids = np.empty(max(cap, 1), np.int32)
+        val = np.empty(max(cap, 1), np.float32)
+        hops = np.empty(max(cap, 1), np.int32)
+        self._chk(self.L.trg_engine_tiled_field_reached(self.h, int(field), _i(gids), _f(val), _i(hops), cap, C.byref(n)))
+        k = min(cap, int(n.value))
+        return dict(gids=gids[:k], value=val[:k], hops=hops[:k], count=int(n.value))
+
+    def tiled_reachable(self, source_gid, budget):
+        """THIS tile's nodes of the global stitched graph within the cost `budget` of the global id `source_gid`: one
+        bounded tiled solve without full outputs (a collective call, all ranks alike), then tiled_field_reached's list
+        -> its dict; tiled.concat_reached joins the ranks' lists."""
+        self._tiled_fields_bounded("cost", "tiled_reachable", [int(source_gid)], False, budget, None, None, full=False)
+        return self.tiled_field_reached(0)
+
     def _tiled_at_frontier(self, member_gids, solve):
         """tiled_assign_frontiers and tiled_frontier_ceilings: solve(sets, targets), the set solve of either objective,
         from the one set `member_gids` read at this tile's Frontier nodes -> (the members, those nodes' global ids,
@@ -519,18 +613,33 @@ class Engine:
         r = solve([members], frontier)
         return members, (frontier.astype(np.int64) + r["offset"]).astype(np.int32), r
 
-    def _tiled_one_to_many(self, solve, start_gid, goal_gids):
-        """tiled_plan_many and tiled_safest_routes: solve, the single-source solve of either objective."""
+    def _tiled_one_to_many(self, solve, start_gid, goal_gids, early_exit=False):
+        """tiled_plan_many and tiled_safest_routes (solve: the single-source solve of either objective) and their
+        early-exit forms (solve: its bounded form, which settles "all" over the goals -- nothing beyond the dearest goal
+        is relaxed or traded, the routes are the same)."""
         goals = np.ascontiguousarray(goal_gids, dtype=np.int32).reshape(-1)
-        solve([int(start_gid)], parent=False)
+        if early_exit and goals.shape[0]:
+            solve([int(start_gid)], parent=False, settle="all", settle_gids=goals)
+        else:
+            solve([int(start_gid)], parent=False)
         return self.tiled_routes(np.zeros(goals.shape[0], np.int32), goals)
 
     def tiled_cost_fields(self, source_gids, parent=True):
         """The cost fields of the global stitched graph from the global ids `source_gids`, for this tile's nodes: a
         collective call, made by every rank of the communicator with the same sources after a stitch.  -> dict with
         cost, hops (m x V_t), parent (global ids; None without `parent`), offset (this tile's first global id) and
-        info (TrgTiledFieldInfo).  tiled.concat_fields joins the ranks' results."""
+        info (TrgTiledFieldInfo).  tiled.concat_fields joins the ranks' results.  Under a budget or settle targets:
+        tiled_cost_fields_bounded."""
         return self._tiled_fields("cost", self.L.trg_engine_tiled_cost_field, source_gids, parent)
+
+    def tiled_cost_fields_bounded(self, source_gids, budget=None, settle=None, settle_gids=None, parent=True):
+        """tiled_cost_fields under bounds (trg_engine_tiled_cost_field_bounded; DESIGN.md section 7, "Bounded fields
+        across tiles"): budget (a cost, or one per field; None: +inf), settle ("any" / "all" / None) over the GLOBAL ids
+        settle_gids, every rank alike.  Field k is the full field truncated at min(budget[k], settle_k).  ->
+        tiled_cost_fields' dict with "bound" (m, the same on every rank) and "reached" (m: this tile's nodes within the
+        bound) as well; its info is a TrgTiledSetInfo.  Without budget and settle the solve is tiled_cost_fields'."""
+        return self._tiled_fields_bounded("cost", "tiled_cost_fields_bounded", source_gids, parent, budget, settle,
+                                          settle_gids)
 
     def tiled_cost_fields_from(self, sets, start_costs=None, targets=None, full=True, parent=True):
         """Source sets across tiles (trg_engine_tiled_cost_field_sets; DESIGN.md section 7, "Source sets across tiles"):
@@ -542,17 +651,31 @@ class Engine:
         int32 arrays: THIS tile's nodes per entry of sets[k]); "offset" (this tile's first global id), "info"
         (TrgTiledSetInfo), "sets" and "start_costs" (the arrays as solved, None without start costs).  An owner is the
         index into sets[k] of the member a node's route starts from, -1 where unreached.  tiled.concat_fields joins
-        the ranks' results."""
+        the ranks' results.  Under a budget or settle targets: tiled_cost_fields_from_bounded."""
         return self._tiled_fields_from("cost", self.L.trg_engine_tiled_cost_field_sets, "tiled_cost_fields_from", sets,
                                        start_costs, targets, full, parent)
+
+    def tiled_cost_fields_from_bounded(self, sets, start_costs=None, budget=None, settle=None, settle_gids=None,
+                                       targets=None, full=True, parent=True):
+        """tiled_cost_fields_from under bounds: budget / settle / settle_gids as tiled_cost_fields_bounded takes them ->
+        tiled_cost_fields_from's dict with "bound" and "reached" as well; a truncated node has owner -1."""
+        return self._tiled_bounded("cost", "tiled_cost_fields_from_bounded", sets, start_costs, True, budget, settle,
+                                   settle_gids, targets, full, parent)
 
     def tiled_assign_frontiers(self, member_gids, start_costs=None):
         """Every Frontier node of the global stitched graph to the entry of `member_gids` (GLOBAL ids, e.g. the robots'
         nodes) that reaches it cheapest: a collective call -- one set field across tiles, read at THIS tile's own
         Frontier nodes on the device.  -> per entry (the global ids of this tile's Frontier nodes it owns, ascending;
         pick), pick being choose_frontier's among them as (gid, cost, hops), or None when it owns none here.
-        tiled.merge_frontier_picks joins the ranks' answers."""
-        members, gids, r = self._tiled_at_frontier(member_gids, lambda sets, at: self.tiled_cost_fields_from(
+        tiled.merge_frontier_picks joins the ranks' answers.  Within a budget: tiled_assign_frontiers_within."""
+        return self.tiled_assign_frontiers_within(member_gids, None, start_costs)
+
+    def tiled_assign_frontiers_within(self, member_gids, budget, start_costs=None):
+        """tiled_assign_frontiers within the cost `budget` (None: +inf): no Frontier node dearer than it is assigned,
+        and nothing beyond it is relaxed or traded."""
+        solve = self.tiled_cost_fields_from if budget is None else \
+            (lambda sets, starts, **kw: self.tiled_cost_fields_from_bounded(sets, starts, budget=budget, **kw))
+        members, gids, r = self._tiled_at_frontier(member_gids, lambda sets, at: solve(
             sets, None if start_costs is None else [start_costs], targets=at, full=False, parent=False))
         cost, hops, owner = r["cost_at"][0], r["hops_at"][0], r["owner_at"][0]
         out = []
@@ -605,20 +728,39 @@ class Engine:
         least fp32 fold of edge costs to its goal (tiled_cost_fields' semantics)."""
         return self._tiled_one_to_many(self.tiled_cost_fields, start_gid, goal_gids)
 
+    def tiled_plan_many_early_exit(self, start_gid, goal_gids):
+        """tiled_plan_many whose solve stops at the dearest goal (settle "all" over the goals): the same routes, nothing
+        beyond that goal relaxed or traded."""
+        return self._tiled_one_to_many(self.tiled_cost_fields_bounded, start_gid, goal_gids, early_exit=True)
+
     # ---- risk fields across tiles (DESIGN.md section 7, "Risk fields across tiles") ---------------------------
     def tiled_risk_fields(self, source_gids, parent=True):
         """The risk fields of the global stitched graph from the global ids `source_gids`, for this tile's nodes
         (trg_engine_tiled_risk_field): the least, over all walks, of the greatest edge weight on the walk.  A collective
-        call like tiled_cost_fields -> its dict with "risk" where that has "cost"."""
+        call like tiled_cost_fields -> its dict with "risk" where that has "cost".  Under a risk ceiling or settle
+        targets: tiled_risk_fields_bounded."""
         return self._tiled_fields("risk", self.L.trg_engine_tiled_risk_field, source_gids, parent)
+
+    def tiled_risk_fields_bounded(self, source_gids, budget=None, settle=None, settle_gids=None, parent=True):
+        """tiled_risk_fields under bounds (trg_engine_tiled_risk_field_bounded): tiled_cost_fields_bounded with a risk
+        ceiling as the budget -> its dict with "risk" where that has "cost"."""
+        return self._tiled_fields_bounded("risk", "tiled_risk_fields_bounded", source_gids, parent, budget, settle,
+                                          settle_gids)
 
     def tiled_risk_fields_from(self, sets, targets=None, full=True, parent=True):
         """Risk fields from source sets across tiles (trg_engine_tiled_risk_field_sets): field k from EVERY entry of
         sets[k] (GLOBAL ids) at risk 0 -- risk solves take no start values.  A collective call like
         tiled_cost_fields_from -> its dict with "risk" / "risk_at" where that has "cost" / "cost_at" and without
-        "start_costs"."""
+        "start_costs".  Under a risk ceiling or settle targets: tiled_risk_fields_from_bounded."""
         return self._tiled_fields_from("risk", self.L.trg_engine_tiled_risk_field_sets, "tiled_risk_fields_from", sets,
                                        None, targets, full, parent)
+
+    def tiled_risk_fields_from_bounded(self, sets, budget=None, settle=None, settle_gids=None, targets=None, full=True,
+                                       parent=True):
+        """tiled_risk_fields_from under bounds: tiled_cost_fields_from_bounded with a risk ceiling as the budget and
+        without start costs."""
+        return self._tiled_bounded("risk", "tiled_risk_fields_from_bounded", sets, None, True, budget, settle,
+                                   settle_gids, targets, full, parent)
 
     def tiled_safest_routes(self, start_gid, goal_gids):
         """The safest paths from one node of the global stitched graph to many: ONE tiled risk solve from `start_gid`
@@ -627,14 +769,25 @@ class Engine:
         its goal (tiled_risk_fields' semantics)."""
         return self._tiled_one_to_many(self.tiled_risk_fields, start_gid, goal_gids)
 
+    def tiled_safest_routes_early_exit(self, start_gid, goal_gids):
+        """tiled_safest_routes whose solve stops at the riskiest goal (settle "all" over the goals): the same routes."""
+        return self._tiled_one_to_many(self.tiled_risk_fields_bounded, start_gid, goal_gids, early_exit=True)
+
     def tiled_frontier_ceilings(self, member_gids):
         """For every Frontier node of THIS tile the least risk ceiling under which the nearest entry of `member_gids`
         (GLOBAL ids, e.g. the robots' nodes) reaches it: a collective call -- one set risk field across tiles, read at
         this tile's Frontier nodes on the device; no array of V_t entries is downloaded.  -> dict with "gids" (this
         tile's Frontier nodes, global ids ascending), "risk" (+inf: unreachable), "hops" (-1), "owner" (the entry of
         member_gids whose tree the node hangs in, -1) and "members" (their number).  tiled.safest_frontier joins the
-        ranks' answers."""
-        members, gids, r = self._tiled_at_frontier(member_gids, lambda sets, at: self.tiled_risk_fields_from(
+        ranks' answers.  Under a risk ceiling: tiled_frontier_ceilings_within."""
+        return self.tiled_frontier_ceilings_within(member_gids, None)
+
+    def tiled_frontier_ceilings_within(self, member_gids, budget):
+        """tiled_frontier_ceilings under the risk ceiling `budget` (None: +inf): a Frontier node above it comes out
+        unreachable, and nothing above it is relaxed or traded."""
+        solve = self.tiled_risk_fields_from if budget is None else \
+            (lambda sets, **kw: self.tiled_risk_fields_from_bounded(sets, budget=budget, **kw))
+        members, gids, r = self._tiled_at_frontier(member_gids, lambda sets, at: solve(
             sets, targets=at, full=False, parent=False))
         return dict(gids=gids, risk=r["risk_at"][0], hops=r["hops_at"][0], owner=r["owner_at"][0],
                     members=int(members.shape[0]), info=r["info"])

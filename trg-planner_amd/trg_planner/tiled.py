@@ -230,6 +230,18 @@ def concat_fields(parts):
     return out
 
 
+def concat_reached(parts):
+    """The ranks' Engine.tiled_field_reached (or tiled_reachable) dicts, in tile order -> dict of "gids" (ascending
+    global ids of the global stitched graph), "value", "hops" and "count" (the ranks' counts summed).  Raises ValueError
+    if the joined ids do not ascend: the parts are not in tile order."""
+    gids = np.concatenate([np.asarray(p["gids"], np.int32) for p in parts]) if parts else np.empty(0, np.int32)
+    if gids.size > 1 and (np.diff(gids) <= 0).any():
+        raise ValueError("concat_reached: the ranks' lists are not in tile order")
+    value = np.concatenate([np.asarray(p["value"], np.float32) for p in parts]) if parts else np.empty(0, np.float32)
+    hops = np.concatenate([np.asarray(p["hops"], np.int32) for p in parts]) if parts else np.empty(0, np.int32)
+    return dict(gids=gids, value=value, hops=hops, count=int(sum(int(p["count"]) for p in parts)))
+
+
 def merge_frontier_picks(parts):
     """The ranks' Engine.tiled_assign_frontiers answers -> per entry (all Frontier global ids it owns, ascending; the
     least (cost, hops, gid) pick among the ranks' as (gid, cost, hops), or None).  No node goes to two entries: a
