@@ -717,8 +717,8 @@ TrgStatus trg_engine_risk_field_refresh(TrgEngine *e,
  * its error, every other rank TRG_ERR_DEVICE "another rank reported a failure", none waits.  TRG_ERR_DEVICE on every
  * rank at once when the exchanges do not converge.  Source sets and start costs are the call below, routes
  * trg_engine_tiled_field_routes, risk fields trg_engine_tiled_risk_field, budgets and settle targets
- * trg_engine_tiled_cost_field_bounded; cost models and refresh are not offered across tiles, and none of these calls
- * touches the retained single-engine solve. */
+ * trg_engine_tiled_cost_field_bounded; refresh is not offered across tiles; cost models are
+ * trg_engine_tiled_cost_field_models.  None of these calls touches the retained single-engine solve. */
 typedef struct TrgTiledFieldInfo {
   int32_t exchanges;     /* all-gather-v exchanges of both passes, the two that found no news included */
   int32_t rounds;        /* relaxation rounds of this rank that did work */
@@ -762,8 +762,9 @@ TrgStatus trg_engine_tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *so
  * next count exchange, of the owner exchanges as well: that rank returns its error, its peers TRG_ERR_DEVICE "another
  * rank reported a failure", nobody waits.  An owner loop that outlasts m x (border nodes of all ranks) + 2 exchanges
  * ends with TRG_ERR_DEVICE on every rank at once.  Routes are trg_engine_tiled_field_routes, risk fields from sets
- * trg_engine_tiled_risk_field_sets, budgets and settle targets trg_engine_tiled_cost_field_bounded; cost models and
- * refresh are not offered across tiles; the retained single-engine solve is left alone. */
+ * trg_engine_tiled_risk_field_sets, budgets and settle targets trg_engine_tiled_cost_field_bounded; refresh is not
+ * offered across tiles; cost models are trg_engine_tiled_cost_field_models; the retained single-engine solve is left
+ * alone. */
 typedef struct TrgTiledSetInfo {
   int32_t exchanges;           /* all-gather-v exchanges of passes 1 and 2, the two without news included */
   int32_t owner_exchanges;     /* ... of the owner pass, the one without news included */
@@ -800,8 +801,9 @@ TrgStatus trg_engine_tiled_cost_field_sets(TrgEngine *e, int32_t m,
  * error, its peers TRG_ERR_DEVICE "another rank reported a failure", nobody waits): those of the cost calls, and in
  * the place of the bad edge cost "tiled risk field: an edge weight is negative or not finite" (TRG_ERR_INVALID_ARG),
  * taken over ALL edges of that rank's solve graph, relaxable or not, as in the single-engine call.
- * Routes are trg_engine_tiled_field_routes, risk ceilings (budget / settle) trg_engine_tiled_risk_field_bounded; cost
- * models and refresh are not offered across tiles. */
+ * Routes are trg_engine_tiled_field_routes, risk ceilings (budget / settle) trg_engine_tiled_risk_field_bounded;
+ * refresh is not offered across tiles; cost models are trg_engine_tiled_cost_field_models (of the cost objective: a
+ * risk field has no cost model). */
 TrgStatus trg_engine_tiled_risk_field(TrgEngine *e, int32_t m, const int32_t *source_gids,
     float *risk, int32_t *hops, int32_t *parent,   /* m x (this tile's nodes), any may be NULL */
     TrgTiledFieldInfo *info);                      /* may be NULL */
@@ -850,7 +852,47 @@ TrgStatus trg_engine_tiled_cost_field_bounded(TrgEngine *e, int32_t m,
     int32_t *owned,                                                /* set_ptr[m], may be NULL */
     float *bound_out, int32_t *reached_out,                        /* m each, may be NULL */
     TrgTiledSetInfo *info);                                        /* may be NULL */
-/* The same under the risk objective (trg_engine_tiled_risk_field_sets' fields; no start values). */
+/* Cost models across tiles ("Cost models across tiles"): trg_engine_tiled_cost_field_bounded with
+ * a cost model (safety_factor s_k, max_weight tau_k) per field.  On the global stitched graph G, field k is exactly what
+ * trg_engine_cost_field_seeded with models defines on one engine:
+ *   - an edge of G is admitted iff it is relaxable and w <= tau_k, compared in fp32 (tau = +inf admits every weight);
+ *   - an admitted edge costs (s_k * w + 1) * dist, each operation rounded to fp32;
+ *   - everything else keeps its definition over the field's own admitted edges and costs: keys, hops, global-id parents
+ *     (the least global id among the tight predecessors one level up), the saturation rule, roots, owners, owned, the
+ *     truncation at min(budget, settle value), bound_out, reached_out, the reached lists and the routes;
+ *   - a route edge is the ADMITTED tight edge of least CSR index in the parent's row.
+ * As an equation between programs: the tiled field of (s, tau) on G is, bit for bit, the tiled field that engines
+ * created with safety_factor s compute on G without the edges of weight > tau, CSR order kept.  One stitch record
+ * serves both directions of a cross edge, so both ranks judge its admission and its cost from the same w and dist bits.
+ * models == NULL is trg_engine_tiled_cost_field_bounded bit for bit on every output; a solve whose models all equal
+ * (the engine's safety_factor, +inf) gives the plain call's fields and the same exchanges, rounds and records_sent.
+ * The arguments after `models` are trg_engine_tiled_cost_field_bounded's, in its order; every rank passes the same
+ * models.  The edge costs are cached per distinct model on the rank's solve graph, for one tile graph and stitch: room
+ * for TRG_FIELD_BATCH_MAX + 1 models, the engine's own never dropped, the least recently used that the solve does not
+ * read given away first; the single-engine cache is neither read nor evicted.  The solve is retained with its models:
+ * trg_engine_tiled_field_routes (the walk, and the late parent sweep after a solve without parents) and
+ * trg_engine_tiled_field_reached answer under them.  Staleness is one rule: a new graph, a new stitch or a change of the
+ * engine's safety factor makes any cost solve stale, even where every field names its own s.
+ * TRG_ERR_INVALID_ARG before any collective, the group and the retained tiled solve still usable, naming the field:
+ * a safety_factor that is NaN, negative or infinite, a max_weight that is NaN or negative; beside them the bounded
+ * call's refusals.  A rank's own failure, announced in the next count exchange like every other (that rank returns its
+ * error, its peers TRG_ERR_DEVICE "another rank reported a failure", nobody waits): a model under which some edge cost of
+ * THIS rank's solve graph is negative or not finite (TRG_ERR_INVALID_ARG naming the first such field; taken over all
+ * edges, those above the ceiling included), and edge costs that do not fit the device (TRG_ERR_CAPACITY).
+ * Refresh is not offered across tiles. */
+TrgStatus trg_engine_tiled_cost_field_models(TrgEngine *e, int32_t m,
+    const TrgFieldModel *models,   /* m, or NULL: the engine's model for every field */
+    const int32_t *set_ptr, const int32_t *set_gids, const float *set_cost0,   /* set_cost0 may be NULL */
+    int32_t owners,
+    const float *budget,                                           /* m, or NULL */
+    int32_t settle, const int32_t *settle_gids, int32_t n_settle,  /* TRG_FIELD_SETTLE_*, over GLOBAL ids */
+    float *cost, int32_t *hops, int32_t *parent, int32_t *owner,   /* m x (this tile's nodes), any may be NULL */
+    const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned,                                                /* set_ptr[m], may be NULL */
+    float *bound_out, int32_t *reached_out,                        /* m each, may be NULL */
+    TrgTiledSetInfo *info);                                        /* may be NULL */
+/* trg_engine_tiled_cost_field_bounded under the risk objective (trg_engine_tiled_risk_field_sets' fields; no start
+ * values, no cost models). */
 TrgStatus trg_engine_tiled_risk_field_bounded(TrgEngine *e, int32_t m,
     const int32_t *set_ptr, const int32_t *set_gids,
     int32_t owners,

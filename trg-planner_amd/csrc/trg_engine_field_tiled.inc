@@ -14,6 +14,9 @@
 // the fourth use of the frame.  Under a budget or a settle mode ("Bounded fields across tiles") pass 1 runs under
 // bounds that the ranks lower between the exchanges through bound records in the same stream, and ends with a trim;
 // the reached list of a retained solve is local work.
+// A cost solve may name a cost model per field ("Cost models across tiles"): the edge costs of every distinct model lie
+// in a slot of `ec`, cached per solve graph, the round kernels, the parent sweep and the walk take the slot table where
+// the fields read more than one slot, and the retained solve answers under its models.
 
 namespace {
 
@@ -26,15 +29,28 @@ struct TiledFieldBufs {
   uint64_t version = 0, serial = 0;
   FieldTiled T{};
   int E2 = 0;  // its edges
-  // One value per edge of the solve graph and objective, each array stamped on its own.  The costs (`ec`) are of the
-  // safety factor as well; the risks (`er`; "Risk fields across tiles") are built by the first risk solve after a
-  // stitch and do not know the safety factor.  `mean` gives the bucket width, `bad` refuses the solve.
+  // One value per edge of the solve graph and objective.  The risks (`er`; "Risk fields across tiles") are built by the
+  // first risk solve after a stitch, stamped on their own: `mean` gives the bucket width, `bad` refuses the solve.
   struct EdgeValues {
     uint64_t version = 0, serial = 0;
-    uint32_t sf_bits = 0;
     double mean = 0.0;
     bool bad = false;
-  } costs, risks;
+  } risks;
+  // The costs ("Cost models across tiles"): `ec` holds slot i at i * ec_stride, one slot per cost model met on this
+  // solve graph -- the cache is of one (version, serial) above and a new solve graph empties it.  Slot 0 is the
+  // engine's own model (its safety factor, no ceiling) and is never given away; the others go to the model a solve
+  // needs and does not find, the least recently used first.  The single-engine cache (FieldBufs::slots) is another.
+  struct CostSlot {
+    uint32_t sf_bits, tau_bits;  // the model, as bits
+    bool valid;                  // the costs and the three words below are computed
+    double sum;                  // over admitted edges
+    long long count;
+    bool bad;                    // some edge cost is negative or not finite (over all edges, those above the ceiling too)
+    uint64_t used;               // ec_tick of the last solve that read it
+  };
+  std::vector<CostSlot> slots;
+  size_t ec_stride = 0;  // entries from one slot to the next
+  uint64_t ec_tick = 0;
   DevArr up_rowptr, up_col, up_w, up_dist;  // the stitched rows, uploaded when an export had taken them off the device
   DevArr ghost_flag, ghost_off, border_flag, border_off, ghost_deg, ghost_row, ghost_fill, scan_tmp;
   DevArr gid_of, state, border, rowptr, col, w, dist, ec, er, stats;
@@ -61,6 +77,13 @@ struct TiledFieldBufs {
     bool risk = false;     // the objective: F.ec is the edge risks, the walk and a late parent sweep take their RISK form
     uint32_t sf_bits = 0;  // (a cost solve)
     FieldDev F{};
+    // a cost solve's models ("Cost models across tiles"): the pairs as solved (empty: the request named none), the slot
+    // table, and whether the fields read more than one slot -- then the walk and a late parent sweep take the table,
+    // else F.ec is the one slot.  No solve comes between this one and its routes, so its slots are not given away.
+    std::vector<TrgFieldModel> pairs;
+    FieldModels models{};
+    bool many = false;
+    const FieldModels *model_table() const { return many ? &models : nullptr; }
   } solved;
   DevArr route_field, route_target, route_off, route_gids, route_info;
   // Bounded solves ("Bounded fields across tiles"): this rank's settle targets (local ids), the words of TiledSettle --
@@ -102,6 +125,8 @@ struct TiledRequest {
   int32_t n_settle = 0;
   float *bound_out = nullptr;
   int32_t *reached_out = nullptr;
+  // a cost model per field ("Cost models across tiles"; never with risk), or nullptr: the engine's for every field
+  const TrgFieldModel *models = nullptr;
 };
 
 // One solve on its way: the request, the kernels' view, and what ends up in the caller's info.
@@ -115,6 +140,12 @@ struct TiledRun {
   bool bounded = false;
   FieldBounds budgets{};
   TiledSettle S{};
+  // the edge costs of this solve (tiled_edge_costs): the slot table, whether the fields read more than one slot (else
+  // F.ec is the one they share and no kernel takes the table), and the mean over its distinct slots
+  FieldModels models{};
+  bool many_models = false;
+  double mean_cost = 0.0;
+  const FieldModels *model_table() const { return many_models ? &models : nullptr; }
   int round = 0;      // of the current pass
   int rounds = 0, exchanges = 0, owner_exchanges = 0, roots = 0;
   long long records = 0, owner_records = 0;
@@ -159,30 +190,23 @@ TrgStatus tiled_lap(TrgEngine *e, TiledRun &run) {
   return TRG_OK;
 }
 
-// The values of the request's objective on the edges of the current solve graph: the costs when the graph or the safety
-// factor moved since they were computed, the risks when the graph did.  Every edge into a ghost is skipped; the
-// single-engine cache is neither read nor evicted.
-TrgStatus tiled_edge_values(TrgEngine *e, bool risk) {
+// The edge risks of the current solve graph ("Risk fields across tiles"), computed when the graph moved since they
+// were.  Every edge into a ghost is skipped.
+TrgStatus tiled_edge_risks(TrgEngine *e) {
   TiledFieldBufs &tb = *e->tiled;
   const FieldTiled &T = tb.T;
   hipStream_t s = e->s_main;
-  TiledFieldBufs::EdgeValues &ev = risk ? tb.risks : tb.costs;
-  const uint32_t sf_bits = risk ? 0u : float_bits(e->prm.safety_factor);
-  if (ev.version == tb.version && ev.serial == tb.serial && ev.sf_bits == sf_bits) return TRG_OK;
+  TiledFieldBufs::EdgeValues &ev = tb.risks;
+  if (ev.version == tb.version && ev.serial == tb.serial) return TRG_OK;
   ev = TiledFieldBufs::EdgeValues{};
   if (T.V > 0) {
     const int n = T.V + T.G;
     TrgStatus st;
-    if ((st = tiled_grow(e, risk ? tb.er : tb.ec, ((size_t)tb.E2 + 4) * 4)) != TRG_OK ||
+    if ((st = tiled_grow(e, tb.er, ((size_t)tb.E2 + 4) * 4)) != TRG_OK ||
         (st = tiled_grow(e, tb.stats, sizeof(FieldEdgeStats))) != TRG_OK)
       return st;
-    if (risk)
-      launch_field_edge_risk(tb.col.as<int>(), tb.w.as<float>(), T.state, n, tb.E2, tb.er.as<float>(),
-                             tb.stats.as<FieldEdgeStats>(), s);
-    else
-      launch_field_edge_cost(tb.col.as<int>(), tb.w.as<float>(), tb.dist.as<float>(), T.state, n, tb.E2,
-                             e->prm.safety_factor, bits_float(FIELD_INF_BITS), tb.ec.as<float>(),
-                             tb.stats.as<FieldEdgeStats>(), s);
+    launch_field_edge_risk(tb.col.as<int>(), tb.w.as<float>(), T.state, n, tb.E2, tb.er.as<float>(),
+                           tb.stats.as<FieldEdgeStats>(), s);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(tb.h_stats, tb.stats.p, sizeof(FieldEdgeStats), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
@@ -191,12 +215,108 @@ TrgStatus tiled_edge_values(TrgEngine *e, bool risk) {
   }
   ev.version = tb.version;
   ev.serial = tb.serial;
-  ev.sf_bits = sf_bits;
+  return TRG_OK;
+}
+
+// The edge costs of a cost solve on the current solve graph ("Cost models across tiles"): every field's model gets a
+// slot of the cache, found or taken; only the slots that are missing are computed, one launch each on the solve
+// graph's arrays -- ghosts are Invalid there, so every edge into a ghost stays skipped under every model -- and ONE host
+// wait for all their stats.  The bucket width's mean is over the solve's distinct slots: without models that is the one
+// slot of the engine's model.  The single-engine cache is neither read nor evicted.
+TrgStatus tiled_edge_costs(TrgEngine *e, TiledRun &run) {
+  TiledFieldBufs &tb = *e->tiled;
+  const FieldTiled &T = tb.T;
+  const TiledRequest &rq = run.rq;
+  hipStream_t s = e->s_main;
+  const int m = rq.m;
+  const uint32_t sf0 = float_bits(e->prm.safety_factor);
+  const size_t stride = ((size_t)tb.E2 + 4 + 3) & ~(size_t)3;  // (slots start 16-byte aligned, 16 bytes of slack each)
+  run.models = FieldModels{};
+  run.models.stride = (long long)stride;
+  run.many_models = false;
+  run.mean_cost = 0.0;
+  if (T.V <= 0) return TRG_OK;  // (a tile without nodes has no edges: nothing reads a cost)
+  if (tb.slots.empty() || tb.ec_stride != stride || tb.slots[0].sf_bits != sf0)
+    tb.slots.assign(1, TiledFieldBufs::CostSlot{sf0, FIELD_INF_BITS, false, 0.0, 0, false, 0});
+  tb.ec_stride = 0;  // (until this phase is through: a failure half-way leaves no cache)
+  const uint64_t tick = ++tb.ec_tick;
+  std::vector<int> fresh;  // the slots to compute
+  for (int k = 0; k < m; ++k) {
+    const uint32_t sfb = rq.models ? float_bits(rq.models[k].safety_factor) : sf0;
+    const uint32_t taub = rq.models ? float_bits(rq.models[k].max_weight) : FIELD_INF_BITS;
+    int slot = -1;
+    for (size_t i = 0; i < tb.slots.size() && slot < 0; ++i)
+      if (tb.slots[i].sf_bits == sfb && tb.slots[i].tau_bits == taub) slot = (int)i;
+    if (slot < 0) {
+      if ((int)tb.slots.size() < FIELD_SLOTS_MAX) {
+        slot = (int)tb.slots.size();
+        tb.slots.push_back({});
+      } else {  // (a solve reads at most FIELD_MAX_SOURCES slots: one beside slot 0 is not this solve's)
+        for (size_t i = 1; i < tb.slots.size(); ++i)
+          if (tb.slots[i].used != tick && (slot < 0 || tb.slots[i].used < tb.slots[slot].used)) slot = (int)i;
+      }
+      if (slot < 0)
+        return e->fail(TRG_ERR_CAPACITY, std::string(rq.what) + "no cache slot left for the model of field " + std::to_string(k));
+      tb.slots[slot] = TiledFieldBufs::CostSlot{sfb, taub, false, 0.0, 0, false, tick};
+    }
+    TiledFieldBufs::CostSlot &cs = tb.slots[slot];
+    if (!cs.valid && std::find(fresh.begin(), fresh.end(), slot) == fresh.end()) fresh.push_back(slot);
+    cs.used = tick;
+    run.models.slot[k] = slot;
+  }
+  if (!fresh.empty() || !tb.ec.p) {  // whole slots, contents kept
+    const size_t bytes = tb.slots.size() * stride * sizeof(float) + 16;
+    if (ensure_bytes(e, tb.ec, bytes, true) != TRG_OK ||
+        ensure_bytes(e, tb.stats, FIELD_SLOTS_MAX * sizeof(FieldEdgeStats)) != TRG_OK) {
+      (void)hipGetLastError();
+      return e->fail(TRG_ERR_CAPACITY, std::string(rq.what) + "no device memory for the edge costs of " +
+                                           std::to_string(tb.slots.size()) + " cost models (" + e->err + ")");
+    }
+  }
+  if (!fresh.empty()) {
+    FieldEdgeStats *d_stats = tb.stats.as<FieldEdgeStats>();
+    const int n = T.V + T.G;
+    for (size_t j = 0; j < fresh.size(); ++j) {
+      const TiledFieldBufs::CostSlot &cs = tb.slots[fresh[j]];
+      launch_field_edge_cost(tb.col.as<int>(), tb.w.as<float>(), tb.dist.as<float>(), T.state, n, tb.E2,
+                             bits_float(cs.sf_bits), bits_float(cs.tau_bits), tb.ec.as<float>() + (size_t)fresh[j] * stride,
+                             d_stats + j, s);
+    }
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(tb.h_stats, d_stats, fresh.size() * sizeof(FieldEdgeStats), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    for (size_t j = 0; j < fresh.size(); ++j) {
+      TiledFieldBufs::CostSlot &cs = tb.slots[fresh[j]];
+      cs.sum = tb.h_stats[j].sum;
+      cs.count = tb.h_stats[j].count;
+      cs.bad = tb.h_stats[j].bad != 0;
+      cs.valid = true;
+    }
+  }
+  tb.ec_stride = stride;
+  double sum = 0.0;
+  long long count = 0;
+  for (int k = 0; k < m; ++k) {
+    const int slot = run.models.slot[k];
+    const TiledFieldBufs::CostSlot &cs = tb.slots[slot];
+    if (cs.bad)
+      return e->fail(TRG_ERR_INVALID_ARG, rq.models ? std::string(rq.what) + "an edge cost is negative or not finite under the model of field " +
+                                                          std::to_string(k)
+                                                    : std::string("tiled cost field: an edge cost is negative or not finite"));
+    bool seen = false;
+    for (int j = 0; j < k && !seen; ++j) seen = run.models.slot[j] == slot;
+    if (!seen) {
+      sum += cs.sum;
+      count += cs.count;
+    }
+    run.many_models = run.many_models || slot != run.models.slot[0];
+  }
+  run.mean_cost = count ? sum / (double)count : 0.0;
   return TRG_OK;
 }
 
 // The solve graph of this rank for the current stitch (trg_field_tiled.inc), built when the graph or the stitch moved
-// since the last one, and on it the edge values of the objective asked for.  The stitched rows are read where they
+// since the last one; a new one empties the caches of its edge values.  The stitched rows are read where they
 // are: in HBM while stitch_assemble's arrays are current, else from the host rows an export fetched.
 TrgStatus tiled_graph(TrgEngine *e, const ExchangeState &x, bool risk) {
   TiledFieldBufs &tb = *e->tiled;
@@ -213,9 +333,11 @@ TrgStatus tiled_graph(TrgEngine *e, const ExchangeState &x, bool risk) {
     return e->fail(TRG_ERR_INVALID_ARG, what + "the stitch's tile is not this rank of the communicator");
   if (off[tile + 1] - off[tile] != V)
     return e->fail(TRG_ERR_INVALID_ARG, what + "the stitch's node offsets do not match its rows");
-  if (tb.version == e->graph_version && tb.serial == e->stitch_serial) return tiled_edge_values(e, risk);
+  if (tb.version == e->graph_version && tb.serial == e->stitch_serial) return TRG_OK;
   tb.version = 0;  // (until the build is through)
-  tb.costs = tb.risks = TiledFieldBufs::EdgeValues{};
+  tb.risks = TiledFieldBufs::EdgeValues{};
+  tb.slots.clear();
+  tb.ec_stride = 0;
   FieldTiled &T = tb.T;
   T = FieldTiled{};
   T.V = V;
@@ -300,7 +422,7 @@ TrgStatus tiled_graph(TrgEngine *e, const ExchangeState &x, bool risk) {
   }
   tb.version = e->graph_version;
   tb.serial = e->stitch_serial;
-  return tiled_edge_values(e, risk);
+  return TRG_OK;
 }
 
 // A bounded solve's own arrays: of the settle targets this rank keeps those that are its nodes, as it does the entries;
@@ -343,7 +465,6 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
   const FieldTiled &T = tb.T;
   const TiledRequest &rq = run.rq;
   if (rq.risk && tb.risks.bad) return e->fail(TRG_ERR_INVALID_ARG, "tiled risk field: an edge weight is negative or not finite");
-  if (!rq.risk && tb.costs.bad) return e->fail(TRG_ERR_INVALID_ARG, "tiled cost field: an edge cost is negative or not finite");
   const long long n = (long long)T.V + T.G;
   if ((long long)rq.m * n + 8 > INT_MAX)
     return e->fail(TRG_ERR_CAPACITY, std::string(tiled_what(rq.risk)) + "m x (nodes + ghosts) does not fit the solver's 32-bit item index");
@@ -365,7 +486,9 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
     return st;
   F.rowptr = tb.rowptr.as<int>();
   F.col = tb.col.as<int>();
-  F.ec = rq.risk ? tb.er.as<float>() : tb.ec.as<float>();
+  // (a cost solve whose fields share one slot reads that slot through F.ec, and no kernel takes the table)
+  F.ec = rq.risk ? tb.er.as<float>()
+                 : tb.ec.as<float>() + (run.many_models ? 0 : (size_t)run.models.slot[0] * (size_t)run.models.stride);
   F.key = tb.key.as<unsigned long long>();
   for (int i = 0; i < 2; ++i) {
     F.q[i] = tb.q[i].as<int>();
@@ -421,11 +544,12 @@ TrgStatus tiled_prepare(TrgEngine *e, const ExchangeState &x, TiledRun &run) {
   if (!e->tiled) e->tiled.reset(new TiledFieldBufs());
   TiledFieldBufs &tb = *e->tiled;
   HIPCHK(e, tb.h_state.ensure(1));
-  HIPCHK(e, tb.h_stats.ensure(1));
+  HIPCHK(e, tb.h_stats.ensure(FIELD_SLOTS_MAX));
   HIPCHK(e, tb.h_n.ensure(4));
   HIPCHK(e, tb.t0.create());
   HIPCHK(e, tb.t1.create());
   TrgStatus st = tiled_graph(e, x, run.rq.risk);
+  if (st == TRG_OK) st = run.rq.risk ? tiled_edge_risks(e) : tiled_edge_costs(e, run);
   if (st == TRG_OK) st = tiled_work_arrays(e, run);
   return st;
 }
@@ -442,7 +566,7 @@ TrgStatus tiled_rounds(TrgEngine *e, TiledRun &run) {
   const FieldSettle no_settle{nullptr, 0, FIELD_SETTLE_NONE};
   const FieldSettle *under_bounds = run.bounded && !F.tight ? &no_settle : nullptr;
   for (;;) {
-    for (int i = 0; i < TILED_BATCH; ++i, ++run.round) launch_field_round(F, run.round, s, under_bounds, nullptr, run.rq.risk);
+    for (int i = 0; i < TILED_BATCH; ++i, ++run.round) launch_field_round(F, run.round, s, under_bounds, run.model_table(), run.rq.risk);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(tb.h_state, &F.ctrl->s, sizeof(FieldState), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
@@ -519,7 +643,7 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
   hipStream_t s = e->s_main;
   const bool work = F.N > 0;
   // the bucket width from the mean edge value of the objective; all risks zero: width 0 ("Risk fields across tiles")
-  const double mean = run.rq.risk ? tb.risks.mean : tb.costs.mean;
+  const double mean = run.rq.risk ? tb.risks.mean : run.mean_cost;
   const float delta = mean > 0.0 ? (float)(e->field_delta_scale * mean) : 0.0f;
   // Pass 1 of a bounded solve ("Bounded fields across tiles"): the budgets, then per exchange the bound records of all
   // ranks into the bounds, the rounds under bounds, the bound step and the bounded publish.  Under a settle mode a tile
@@ -588,7 +712,7 @@ TrgStatus tiled_owner_pass(TrgEngine *e, ExchangeState &x, TiledRun &run) {
     if (F.N <= 0) return TRG_OK;
     int *changed = tb.own_changed.as<int>();
     HIPCHK(e, hipEventRecord(tb.t0, s));
-    launch_tiled_parents(F, T, s, run.rq.risk);
+    launch_tiled_parents(F, T, s, run.rq.risk, run.model_table());
     launch_tiled_forest_begin(F, T, tb.set_ptr.as<int>(), owner, changed, tb.n_rec.as<int>() + 1,
                               tb.published.as<unsigned long long>(), s);
     HIPCHK(e, hipMemcpyAsync(&tb.h_n[1], tb.n_rec.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -630,7 +754,7 @@ TrgStatus tiled_outputs(TrgEngine *e, TiledRun &run) {
     // (with owners the parent sweep ran before the owner pass)
     launch_tiled_finish(run.F, T, tb.cost.as<float>(), tb.hops.as<int>(), tb.parent_out.as<int>(),
                         rq.parent != nullptr && !rq.owners, tb.owner.as<int>(), rq.owner ? tb.owner_out.as<int>() : nullptr, s,
-                        rq.risk);
+                        rq.risk, run.model_table());
     if (rq.owners) {
       if (rq.owned) launch_tiled_owned(run.F, T, tb.set_ptr.as<int>(), tb.owner.as<int>(), n_entries, tb.owned.as<int>(), s);
       FieldSets S{};
@@ -682,8 +806,12 @@ TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
     if (const TrgStatus st = tiled_owner_pass(e, x, run); st != TRG_OK) return st;
   if (const TrgStatus st = tiled_outputs(e, run); st != TRG_OK) return st;
   // retained for the routes: the keys, marks and parents lie in the work arrays as the kernels left them
-  e->tiled->solved = TiledFieldBufs::Solved{true, run.rq.m, run.rq.owners, run.rq.owners || run.rq.parent != nullptr,
-                                            run.rq.risk, float_bits(e->prm.safety_factor), run.F};
+  TiledFieldBufs::Solved &kept = e->tiled->solved;
+  kept = TiledFieldBufs::Solved{true, run.rq.m, run.rq.owners, run.rq.owners || run.rq.parent != nullptr,
+                                run.rq.risk, float_bits(e->prm.safety_factor), run.F};
+  if (run.rq.models) kept.pairs.assign(run.rq.models, run.rq.models + run.rq.m);
+  kept.models = run.models;
+  kept.many = run.many_models;
   return TRG_OK;
 }
 
@@ -712,6 +840,13 @@ TrgStatus tiled_check_request(TrgEngine *e, const TiledRequest &rq) {
           return refuse("the start cost of " + where + " is NaN, negative or infinite");
       }
     }
+  // a model is a finite safety factor >= 0 and a ceiling >= 0 (+inf: none), as on one engine
+  for (int k = 0; rq.models && k < rq.m; ++k) {
+    if (!(rq.models[k].safety_factor >= 0.0f) || std::isinf(rq.models[k].safety_factor))
+      return refuse("the safety factor of field " + std::to_string(k) + " is negative or not finite");
+    if (!(rq.models[k].max_weight >= 0.0f))
+      return refuse("the risk ceiling of field " + std::to_string(k) + " is negative or not a number");
+  }
   if (rq.n_targets < 0 || (rq.n_targets > 0 && !rq.targets))
     return refuse("n_targets < 0, or targets is null with n_targets > 0");
   // the bounded entries' own arguments (the others leave them at their defaults)
@@ -808,7 +943,7 @@ TrgStatus tiled_bounded_call(TrgEngine *e, int32_t m, const int32_t *set_ptr, co
                              int32_t settle, const int32_t *settle_gids, int32_t n_settle, float *value, int32_t *hops,
                              int32_t *parent, int32_t *owner, const int32_t *targets, int32_t n_targets, float *value_at,
                              int32_t *hops_at, int32_t *owner_at, int32_t *owned, float *bound_out, int32_t *reached_out,
-                             TrgTiledSetInfo *info) {
+                             TrgTiledSetInfo *info, const TrgFieldModel *models = nullptr) {
   TiledRequest rq{m, set_ptr, set_gids, set_cost0, value, hops, parent, owners, risk, what, "null set_ptr or set_gids", nullptr};
   if (owners) {
     rq.owner = owner;
@@ -825,6 +960,7 @@ TrgStatus tiled_bounded_call(TrgEngine *e, int32_t m, const int32_t *set_ptr, co
   rq.n_settle = n_settle;
   rq.bound_out = bound_out;
   rq.reached_out = reached_out;
+  rq.models = models;
   return tiled_call(e, rq, info, [](TrgTiledSetInfo &out, const TiledRun &run) {
     out.owner_exchanges = run.owner_exchanges;
     out.roots = run.roots;
@@ -932,7 +1068,7 @@ TrgStatus tiled_routes(TrgEngine *e, const TiledRoutesRequest &rq, TrgTiledRoute
     HIPCHK(e, hipMemsetAsync(tb.n_rec.p, 0, 16, s));
     HIPCHK(e, hipEventRecord(tb.t0, s));
     if (!tb.solved.parents) {  // the solve was asked for no parents: local work, no collective
-      if (run.F.N > 0) launch_tiled_parents(run.F, T, s, tb.solved.risk);
+      if (run.F.N > 0) launch_tiled_parents(run.F, T, s, tb.solved.risk, tb.solved.model_table());
       tb.solved.parents = true;
     }
     R.field = tb.route_field.as<int>();
@@ -957,7 +1093,7 @@ TrgStatus tiled_routes(TrgEngine *e, const TiledRoutesRequest &rq, TrgTiledRoute
         }
         TiledRouteInfo *d_infos = tb.route_info.as<TiledRouteInfo>();
         if (exchange > 1) {
-          launch_tiled_route_step(run.F, T, R, d_all, gathered, d_infos, s, tb.solved.risk);
+          launch_tiled_route_step(run.F, T, R, d_all, gathered, d_infos, s, tb.solved.risk, tb.solved.model_table());
           return TRG_OK;
         }
         // exchange 1: the lengths of all routes -- the one download of records -- then the walks begin
@@ -985,7 +1121,7 @@ TrgStatus tiled_routes(TrgEngine *e, const TiledRoutesRequest &rq, TrgTiledRoute
           R.offsets = tb.route_off.as<int>();
           R.node_gids = tb.route_gids.as<int>();
         }
-        launch_tiled_route_step(run.F, T, R, nullptr, 0, d_infos, s, tb.solved.risk);
+        launch_tiled_route_step(run.F, T, R, nullptr, 0, d_infos, s, tb.solved.risk, tb.solved.model_table());
         return TRG_OK;
       });
   if (st != TRG_OK) return st;
@@ -1095,6 +1231,20 @@ TrgStatus trg_engine_tiled_cost_field_bounded(TrgEngine *e, int32_t m, const int
     return tiled_bounded_call(e, m, set_ptr, set_gids, set_cost0, owners != 0, false, "tiled cost field bounded: ", budget,
                               settle, settle_gids, n_settle, cost, hops, parent, owner, targets, n_targets, cost_at,
                               hops_at, owner_at, owned, bound_out, reached_out, info);
+  });
+}
+
+TrgStatus trg_engine_tiled_cost_field_models(TrgEngine *e, int32_t m, const TrgFieldModel *models, const int32_t *set_ptr,
+                                             const int32_t *set_gids, const float *set_cost0, int32_t owners,
+                                             const float *budget, int32_t settle, const int32_t *settle_gids,
+                                             int32_t n_settle, float *cost, int32_t *hops, int32_t *parent, int32_t *owner,
+                                             const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at,
+                                             int32_t *owner_at, int32_t *owned, float *bound_out, int32_t *reached_out,
+                                             TrgTiledSetInfo *info) {
+  return entry(e, "tiled_cost_field_models", DEVICE, [&] {
+    return tiled_bounded_call(e, m, set_ptr, set_gids, set_cost0, owners != 0, false, "tiled cost field models: ", budget,
+                              settle, settle_gids, n_settle, cost, hops, parent, owner, targets, n_targets, cost_at,
+                              hops_at, owner_at, owned, bound_out, reached_out, info, models);
   });
 }
 

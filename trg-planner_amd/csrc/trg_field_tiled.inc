@@ -19,7 +19,9 @@
 // solve ("Routes across tiles"): k_tiled_route_len, k_tiled_route_step and k_tiled_route_end.  Pass 1 of a bounded
 // solve ("Bounded fields across tiles"): k_tiled_bound, the bounded form of k_tiled_publish, k_tiled_bound_merge and
 // k_tiled_bound_fold around trg_field.hip's BOUNDED round kernels; k_tiled_reached and k_tiled_list_count / _emit list
-// a rank's own reached nodes.
+// a rank's own reached nodes.  A cost model per field ("Cost models across tiles"): the only kernels here that read an
+// edge cost, k_tiled_parent and k_tiled_route_step, have a MODELS form that takes the slot of the block's or the route's
+// field from a FieldModels table, as trg_field.hip's round kernels do.
 //
 // All kernels: wave64, bounds taken from the arguments, no scalar memory writes, nothing waits on another workgroup.
 
@@ -369,9 +371,12 @@ __global__ __launch_bounds__(THREADS) void k_tiled_merge(FieldDev F, FieldTiled 
 
 // The parent sweep over the solve graph, ghost rows included: the least GLOBAL id u with an edge u -> v whose
 // extension of key[u] is key[v] (ghosts are not in id order among the solve-graph indices, hence the table).  RISK: F.ec
-// holds the edge risks and the extension is the maximum ("Risk fields across tiles").
-template <bool RISK>
-__global__ __launch_bounds__(THREADS) void k_tiled_parent(FieldDev F, FieldTiled T) {
+// holds the edge risks and the extension is the maximum ("Risk fields across tiles").  MODELS (never with RISK): the
+// edge costs are those of the block's field ("Cost models across tiles"), one table read per (block, field).
+template <bool RISK, bool MODELS>
+__global__ __launch_bounds__(THREADS) void k_tiled_parent(FieldDev F, FieldTiled T, FieldModelsArg<MODELS> M) {
+  static_assert(!(RISK && MODELS), "a risk field has no cost model");
+  const float *__restrict__ ec = field_costs<MODELS>(F, M, blockIdx.y);
   const int sub = threadIdx.x & (GROUP - 1);
   const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
   const int ng = gridDim.x * blockDim.x / GROUP;
@@ -381,7 +386,7 @@ __global__ __launch_bounds__(THREADS) void k_tiled_parent(FieldDev F, FieldTiled
     if (ku == FIELD_KEY_NONE) continue;
     const int gu = T.gid_of[u];
     for (int k = F.rowptr[u] + sub, kend = F.rowptr[u + 1]; k < kend; k += GROUP) {
-      const float c = F.ec[k];
+      const float c = ec[k];
       if (__float_as_uint(c) == FIELD_EDGE_SKIP) continue;
       const int v = fbase + F.col[k];
       if (key_extend<RISK>(ku, c) == F.key[v]) atomicMin(&F.parent[v], gu);
@@ -541,10 +546,14 @@ __global__ __launch_bounds__(THREADS) void k_tiled_route_len(FieldDev F, FieldTi
 // where its node must carry a member mark, END.  Every route has one walker at any time: nothing here is atomic but
 // the record slots (wave_reserve, every lane of the wave gets there: the trip counts are uniform) and the word beside
 // the record count that a walk which lost its way sets to its route + 1.  RISK: the tight-edge test extends by the
-// maximum over the edge risks in F.ec; the sums are the folds of dist and w all the same.
-template <bool BEGIN, bool RISK>
+// maximum over the edge risks in F.ec; the sums are the folds of dist and w all the same.  MODELS (never with RISK):
+// the edge costs are those of the route's field, one table read per item -- an edge above the field's ceiling is
+// skipped there, so the route edge is the ADMITTED tight edge of least index.
+template <bool BEGIN, bool RISK, bool MODELS>
 __global__ __launch_bounds__(THREADS) void k_tiled_route_step(FieldDev F, FieldTiled T, TiledRoutes R,
-                                                              const TiledRouteRec *__restrict__ in, int n_in) {
+                                                              const TiledRouteRec *__restrict__ in, int n_in,
+                                                              FieldModelsArg<MODELS> M) {
+  static_assert(!(RISK && MODELS), "a risk field has no cost model");
   TiledRouteRec *rec = (TiledRouteRec *)R.rec;
   const int sub = threadIdx.x & (GROUP - 1);
   const int gshift = lane_id() & ~(GROUP - 1);
@@ -577,6 +586,7 @@ __global__ __launch_bounds__(THREADS) void k_tiled_route_step(FieldDev F, FieldT
     TiledRouteRec out{};
     if (go) {
       const int fbase = R.field[r] * F.V;
+      const float *__restrict__ ec = field_costs<MODELS>(F, M, R.field[r]);
       const int off = R.node_gids ? R.offsets[r] : 0;
       const int room = R.node_gids ? R.offsets[r + 1] - off : 0;
       unsigned long long kv = F.key[fbase + v];
@@ -603,7 +613,7 @@ __global__ __launch_bounds__(THREADS) void k_tiled_route_step(FieldDev F, FieldT
           const int k = k0 + sub;
           bool hit = false;
           if (k < kend && F.col[k] == v) {
-            const float c = F.ec[k];
+            const float c = ec[k];
             hit = __float_as_uint(c) != FIELD_EDGE_SKIP && key_extend<RISK>(ku, c) == kv;
           }
           const unsigned hits = (unsigned)(ballot(hit) >> gshift) & ((1u << GROUP) - 1u);
@@ -664,22 +674,27 @@ void launch_tiled_route_len(const FieldDev &F, const FieldTiled &T, const TiledR
 }
 
 void launch_tiled_route_step(const FieldDev &F, const FieldTiled &T, const TiledRoutes &R, const void *rec_in, int n_in,
-                             TiledRouteInfo *infos, hipStream_t s, bool risk) {
+                             TiledRouteInfo *infos, hipStream_t s, bool risk, const FieldModels *models) {
+  const FieldNoModels none{};
   (void)hipMemsetAsync(R.n_rec, 0, sizeof(int), s);
   const TiledRouteRec *in = (const TiledRouteRec *)rec_in;
   if (!in) {
     if (R.n > 0 && T.V > 0) {
       const dim3 grid(field_blocks((long long)R.n * GROUP, THREADS));
-      if (risk) hipLaunchKernelGGL((k_tiled_route_step<true, true>), grid, dim3(THREADS), 0, s, F, T, R, in, 0);
-      else hipLaunchKernelGGL((k_tiled_route_step<true, false>), grid, dim3(THREADS), 0, s, F, T, R, in, 0);
+      if (risk) hipLaunchKernelGGL((k_tiled_route_step<true, true, false>), grid, dim3(THREADS), 0, s, F, T, R, in, 0, none);
+      else if (models)
+        hipLaunchKernelGGL((k_tiled_route_step<true, false, true>), grid, dim3(THREADS), 0, s, F, T, R, in, 0, *models);
+      else hipLaunchKernelGGL((k_tiled_route_step<true, false, false>), grid, dim3(THREADS), 0, s, F, T, R, in, 0, none);
     }
     return;
   }
   if (n_in <= 0) return;
   if (T.V > 0) {
     const dim3 grid(field_blocks((long long)n_in * GROUP, THREADS));
-    if (risk) hipLaunchKernelGGL((k_tiled_route_step<false, true>), grid, dim3(THREADS), 0, s, F, T, R, in, n_in);
-    else hipLaunchKernelGGL((k_tiled_route_step<false, false>), grid, dim3(THREADS), 0, s, F, T, R, in, n_in);
+    if (risk) hipLaunchKernelGGL((k_tiled_route_step<false, true, false>), grid, dim3(THREADS), 0, s, F, T, R, in, n_in, none);
+    else if (models)
+      hipLaunchKernelGGL((k_tiled_route_step<false, false, true>), grid, dim3(THREADS), 0, s, F, T, R, in, n_in, *models);
+    else hipLaunchKernelGGL((k_tiled_route_step<false, false, false>), grid, dim3(THREADS), 0, s, F, T, R, in, n_in, none);
   }
   hipLaunchKernelGGL(k_tiled_route_end, dim3(field_blocks(n_in, THREADS)), dim3(THREADS), 0, s, in, n_in, infos, R.n);
 }
@@ -779,15 +794,16 @@ void launch_tiled_merge(const FieldDev &F, const FieldTiled &T, const void *rec,
                        (const TiledRec *)rec, n_rec);
 }
 
-void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s, bool risk) {
+void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s, bool risk, const FieldModels *models) {
   const dim3 grid(field_blocks((long long)F.V * GROUP, THREADS), F.m);
-  if (risk) hipLaunchKernelGGL(k_tiled_parent<true>, grid, dim3(THREADS), 0, s, F, T);
-  else hipLaunchKernelGGL(k_tiled_parent<false>, grid, dim3(THREADS), 0, s, F, T);
+  if (risk) hipLaunchKernelGGL((k_tiled_parent<true, false>), grid, dim3(THREADS), 0, s, F, T, FieldNoModels{});
+  else if (models) hipLaunchKernelGGL((k_tiled_parent<false, true>), grid, dim3(THREADS), 0, s, F, T, *models);
+  else hipLaunchKernelGGL((k_tiled_parent<false, false>), grid, dim3(THREADS), 0, s, F, T, FieldNoModels{});
 }
 
 void launch_tiled_finish(const FieldDev &F, const FieldTiled &T, float *cost, int *hops, int *parent, bool parents,
-                         const int *owner, int *owner_out, hipStream_t s, bool risk) {
-  if (parents) launch_tiled_parents(F, T, s, risk);
+                         const int *owner, int *owner_out, hipStream_t s, bool risk, const FieldModels *models) {
+  if (parents) launch_tiled_parents(F, T, s, risk, models);
   if (T.V > 0)
     hipLaunchKernelGGL(k_tiled_output, dim3(field_blocks(T.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, cost, hops,
                        parent, owner, owner_out);

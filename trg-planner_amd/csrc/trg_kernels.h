@@ -695,10 +695,13 @@ void launch_tiled_reached_list(const FieldDev &F, const FieldTiled &T, int field
 // parents as least global ids (when asked for), then cost / hops / parent of the local nodes, m x T.V, and with
 // owner_out (else nullptr) their owners from `owner`, the owner pass's m x (V + G) words
 void launch_tiled_finish(const FieldDev &F, const FieldTiled &T, float *cost, int *hops, int *parent, bool parents,
-                         const int *owner, int *owner_out, hipStream_t s, bool risk = false);
+                         const int *owner, int *owner_out, hipStream_t s, bool risk = false,
+                         const FieldModels *models = nullptr);
 // the parent sweep alone (the set call runs it before its owner pass; launch_tiled_finish then goes without); `risk`: F.ec
-// holds edge risks (launch_field_edge_risk over the solve graph) and a key is extended by the maximum
-void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s, bool risk = false);
+// holds edge risks (launch_field_edge_risk over the solve graph) and a key is extended by the maximum; `models` (never
+// with risk; "Cost models across tiles"): the fields read more than one slot of F.ec, each its own
+void launch_tiled_parents(const FieldDev &F, const FieldTiled &T, hipStream_t s, bool risk = false,
+                          const FieldModels *models = nullptr);
 // The owner pass of the set call, after the parent sweep.  begin: F.q[0] = every item's first ancestor (a local root
 // and a ghost with a key: itself; another item with a key: its parent's solve-graph item), owner (m x (V + G)) = the
 // roots' entries counted from set_ptr[field], -1 elsewhere, *n_roots their count; changed (FIELD_OWNER_SWEEPS_MAX
@@ -738,6 +741,7 @@ void launch_tiled_route_len(const FieldDev &F, const FieldTiled &T, const TiledR
 // infos (n entries, device; num_nodes set from the LEN records).  A walk publishes HANDOFF {route, parent gid, sums}
 // where its parent is a ghost and END {route, -1 - root gid, sums} at a root.
 void launch_tiled_route_step(const FieldDev &F, const FieldTiled &T, const TiledRoutes &R, const void *rec_in, int n_in,
-                             TiledRouteInfo *infos, hipStream_t s, bool risk = false);
+                             TiledRouteInfo *infos, hipStream_t s, bool risk = false,
+                             const FieldModels *models = nullptr);
 
 }  // namespace trg

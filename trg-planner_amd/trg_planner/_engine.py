@@ -142,6 +142,7 @@ EXPORTS = [
     "trg_engine_tiled_cost_field", "trg_engine_stitch_ids", "trg_engine_tiled_cost_field_sets",
     "trg_engine_tiled_field_routes", "trg_engine_tiled_risk_field", "trg_engine_tiled_risk_field_sets",
     "trg_engine_tiled_cost_field_bounded", "trg_engine_tiled_risk_field_bounded", "trg_engine_tiled_field_reached",
+    "trg_engine_tiled_cost_field_models",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -261,6 +262,8 @@ def load_library():
     L.trg_engine_tiled_risk_field_bounded.argtypes = [vp, C.c_int32, ip, ip, C.c_int32, fp, C.c_int32, ip, C.c_int32,
                                                       fp, ip, ip, ip, ip, C.c_int32, fp, ip, ip, ip, fp, ip,
                                                       C.POINTER(TrgTiledSetInfo)]
+    L.trg_engine_tiled_cost_field_models.argtypes = [vp, C.c_int32, C.POINTER(TrgFieldModel)] + \
+        L.trg_engine_tiled_cost_field_bounded.argtypes[2:]
     L.trg_engine_tiled_field_reached.argtypes = [vp, C.c_int32, ip, fp, ip, C.c_int32, ip]
     L.trg_engine_tiled_field_routes.argtypes = [vp, C.c_int32, ip, ip, ip, ip, fp, C.c_int32,
                                                 C.POINTER(TrgTiledRouteInfo), C.POINTER(TrgTiledRoutesInfo)]
@@ -515,15 +518,18 @@ class Engine:
         out["info"] = info
         return out
 
-    def _tiled_bounded(self, value, who, sets, start_costs, owners, budget, settle, settle_gids, targets, full, parent):
+    def _tiled_bounded(self, value, who, sets, start_costs, owners, budget, settle, settle_gids, targets, full, parent,
+                       models=None):
         """The bounded tiled entries of either objective (`value`: "cost" or "risk"; DESIGN.md section 7, "Bounded fields
         across tiles"): sets of GLOBAL ids, `owners` as every rank passes it, budget (a value or one per field, None:
         +inf), settle ("any" / "all" / None) over the GLOBAL ids settle_gids.  -> _tiled_fields_from's dict (without
         owners: "owner", "owned" and the targets' reads are absent) plus "bound" (m float32, the same on every rank)
-        and "reached" (m int32: THIS tile's nodes within the bound)."""
+        and "reached" (m int32: THIS tile's nodes within the bound).  With `models` (cost only; as cost_fields takes
+        them) the call is trg_engine_tiled_cost_field_models and the dict has "models", the (m, 2) pairs as solved."""
         _check_settle(who, settle)
         sets, ptr, ids, starts, c0 = pack_sets(who, sets, start_costs)
         m = len(sets)
+        marr, pairs = (None, None) if models is None else self._models(who, models, m)
         offset, V = self._tiled_ids()
         rows = max(m, 1)
         at = value + "_at"
@@ -551,14 +557,19 @@ class Engine:
         info = TrgTiledSetInfo()
         arr = lambda name, conv: None if out.get(name) is None else conv(out[name])  # noqa: E731
         entry = self.L.trg_engine_tiled_cost_field_bounded if value == "cost" else self.L.trg_engine_tiled_risk_field_bounded
+        if models is not None:
+            entry = self.L.trg_engine_tiled_cost_field_models
         self._chk(entry(
-            self.h, m, _i(ptr), _i(ids), *((None if c0 is None else _f(c0),) if value == "cost" else ()),
+            self.h, m, *(() if models is None else (marr,)), _i(ptr), _i(ids),
+            *((None if c0 is None else _f(c0),) if value == "cost" else ()),
             1 if owners else 0, None if bud is None else _f(bud), _SETTLE[settle], _i(sg) if sg.shape[0] else None,
             int(sg.shape[0]), arr(value, _f), arr("hops", _i), arr("parent", _i), arr("owner", _i),
             None if tg is None or n_t == 0 else _i(tg), n_t, arr(at, _f), arr("hops_at", _i), arr("owner_at", _i),
             _i(owned) if owners else None, _f(out["bound"]), _i(out["reached"]), C.byref(info)))
         if owners:
             out["owned"] = split_owned()
+        if models is not None:
+            out["models"] = pairs
         out["info"] = info
         return out
 
@@ -661,6 +672,42 @@ class Engine:
         tiled_cost_fields_from's dict with "bound" and "reached" as well; a truncated node has owner -1."""
         return self._tiled_bounded("cost", "tiled_cost_fields_from_bounded", sets, start_costs, True, budget, settle,
                                    settle_gids, targets, full, parent)
+
+    def tiled_cost_fields_models(self, sets_or_sources, models, start_costs=None, budget=None, settle=None,
+                                 settle_gids=None, targets=None, full=True, parent=True):
+        """Cost models across tiles (trg_engine_tiled_cost_field_models; DESIGN.md section 7, "Cost models across
+        tiles"): tiled_cost_fields_from_bounded with a cost model per field.  `sets_or_sources`: m sets of GLOBAL ids,
+        or a flat list of global ids -- m sets of one.  `models` as cost_fields(models=) takes them, m entries: each
+        None (the engine's model), a safety factor (no ceiling) or (safety_factor, max_risk); field k admits the edges
+        of G with weight <= max_risk and prices them with its safety factor.  models=None is
+        tiled_cost_fields_from_bounded.  Every rank passes the same sets, start costs, bounds and models.  ->
+        tiled_cost_fields_from_bounded's dict plus "models", the (m, 2) float32 pairs as solved (absent with
+        models=None).  The solve is retained with its models: tiled_routes and tiled_field_reached answer under them."""
+        sets = list(sets_or_sources)
+        if all(np.ndim(one) == 0 for one in sets):
+            sets = [[int(g)] for g in sets]
+        if models is not None:  # what the entry refuses on every rank alike, said here before any call
+            for k, (s, tau) in enumerate(self._models("tiled_cost_fields_models", models, len(sets))[1]):
+                if not s >= 0.0 or np.isinf(s):
+                    raise ValueError(f"tiled_cost_fields_models: the safety factor of field {k} is negative or not finite")
+                if not tau >= 0.0:
+                    raise ValueError(f"tiled_cost_fields_models: the risk ceiling of field {k} is negative or not a number")
+        return self._tiled_bounded("cost", "tiled_cost_fields_models", sets, start_costs, True, budget, settle,
+                                   settle_gids, targets, full, parent, models=models)
+
+    def tiled_plan_tradeoff(self, start_gid, goal_gid, models, early_exit=True):
+        """The same start-to-goal query of the global stitched graph under k cost models (plan_tradeoff across tiles):
+        ONE collective solve of k fields from `start_gid`, field k under models[k] -- with `early_exit` settled "any"
+        at the goal, so that no field goes on past it -- then one tiled_routes call, all ranks alike -> tiled_routes'
+        dict; tiled.join_routes gives route k under model k (empty where model k's ceiling cuts the goal off).  There
+        is no tiled min_risk_ceiling: tiled_safest_routes already answers it from one risk solve -- the least ceiling
+        under which the goal is reachable is that route's `cost`."""
+        models = list(models)
+        k = len(models)
+        goal = int(goal_gid)
+        self.tiled_cost_fields_models([int(start_gid)] * k, models, settle="any" if early_exit else None,
+                                      settle_gids=[goal] if early_exit else None, full=False, parent=False)
+        return self.tiled_routes(np.arange(k, dtype=np.int32), np.full(k, goal, np.int32))
 
     def tiled_assign_frontiers(self, member_gids, start_costs=None):
         """Every Frontier node of the global stitched graph to the entry of `member_gids` (GLOBAL ids, e.g. the robots'
