@@ -717,8 +717,8 @@ TrgStatus trg_engine_risk_field_refresh(TrgEngine *e,
  * its error, every other rank TRG_ERR_DEVICE "another rank reported a failure", none waits.  TRG_ERR_DEVICE on every
  * rank at once when the exchanges do not converge.  Source sets and start costs are the call below, routes
  * trg_engine_tiled_field_routes, risk fields trg_engine_tiled_risk_field, budgets and settle targets
- * trg_engine_tiled_cost_field_bounded; refresh is not offered across tiles; cost models are
- * trg_engine_tiled_cost_field_models.  None of these calls touches the retained single-engine solve. */
+ * trg_engine_tiled_cost_field_bounded; the refresh of a retained solve is trg_engine_tiled_cost_field_refresh; cost
+ * models are trg_engine_tiled_cost_field_models.  None of these calls touches the retained single-engine solve. */
 typedef struct TrgTiledFieldInfo {
   int32_t exchanges;     /* all-gather-v exchanges of both passes, the two that found no news included */
   int32_t rounds;        /* relaxation rounds of this rank that did work */
@@ -762,9 +762,9 @@ TrgStatus trg_engine_tiled_cost_field(TrgEngine *e, int32_t m, const int32_t *so
  * next count exchange, of the owner exchanges as well: that rank returns its error, its peers TRG_ERR_DEVICE "another
  * rank reported a failure", nobody waits.  An owner loop that outlasts m x (border nodes of all ranks) + 2 exchanges
  * ends with TRG_ERR_DEVICE on every rank at once.  Routes are trg_engine_tiled_field_routes, risk fields from sets
- * trg_engine_tiled_risk_field_sets, budgets and settle targets trg_engine_tiled_cost_field_bounded; refresh is not
- * offered across tiles; cost models are trg_engine_tiled_cost_field_models; the retained single-engine solve is left
- * alone. */
+ * trg_engine_tiled_risk_field_sets, budgets and settle targets trg_engine_tiled_cost_field_bounded; the refresh of a
+ * retained solve is trg_engine_tiled_cost_field_refresh; cost models are trg_engine_tiled_cost_field_models; the
+ * retained single-engine solve is left alone. */
 typedef struct TrgTiledSetInfo {
   int32_t exchanges;           /* all-gather-v exchanges of passes 1 and 2, the two without news included */
   int32_t owner_exchanges;     /* ... of the owner pass, the one without news included */
@@ -802,8 +802,8 @@ TrgStatus trg_engine_tiled_cost_field_sets(TrgEngine *e, int32_t m,
  * the place of the bad edge cost "tiled risk field: an edge weight is negative or not finite" (TRG_ERR_INVALID_ARG),
  * taken over ALL edges of that rank's solve graph, relaxable or not, as in the single-engine call.
  * Routes are trg_engine_tiled_field_routes, risk ceilings (budget / settle) trg_engine_tiled_risk_field_bounded;
- * refresh is not offered across tiles; cost models are trg_engine_tiled_cost_field_models (of the cost objective: a
- * risk field has no cost model). */
+ * the refresh of a retained solve is trg_engine_tiled_risk_field_refresh; cost models are
+ * trg_engine_tiled_cost_field_models (of the cost objective: a risk field has no cost model). */
 TrgStatus trg_engine_tiled_risk_field(TrgEngine *e, int32_t m, const int32_t *source_gids,
     float *risk, int32_t *hops, int32_t *parent,   /* m x (this tile's nodes), any may be NULL */
     TrgTiledFieldInfo *info);                      /* may be NULL */
@@ -879,7 +879,8 @@ TrgStatus trg_engine_tiled_cost_field_bounded(TrgEngine *e, int32_t m,
  * error, its peers TRG_ERR_DEVICE "another rank reported a failure", nobody waits): a model under which some edge cost of
  * THIS rank's solve graph is negative or not finite (TRG_ERR_INVALID_ARG naming the first such field; taken over all
  * edges, those above the ceiling included), and edge costs that do not fit the device (TRG_ERR_CAPACITY).
- * Refresh is not offered across tiles. */
+ * Refresh is not offered across tiles for a solve under models, nor for one under bounds or with start costs:
+ * trg_engine_tiled_cost_field_refresh refuses them as trg_engine_cost_field_refresh refuses their single-engine kin. */
 TrgStatus trg_engine_tiled_cost_field_models(TrgEngine *e, int32_t m,
     const TrgFieldModel *models,   /* m, or NULL: the engine's model for every field */
     const int32_t *set_ptr, const int32_t *set_gids, const float *set_cost0,   /* set_cost0 may be NULL */
@@ -903,6 +904,58 @@ TrgStatus trg_engine_tiled_risk_field_bounded(TrgEngine *e, int32_t m,
     int32_t *owned,                                                /* set_ptr[m], may be NULL */
     float *bound_out, int32_t *reached_out,                        /* m each, may be NULL */
     TrgTiledSetInfo *info);                                        /* may be NULL */
+/* Refresh across tiles ("Refresh across tiles"): the retained tiled solve brought to the current
+ * stitch -- trg_engine_cost_field_refresh's steps (carry, anchor, warm pass 1, anchor again, warm pass 2) on the global
+ * stitched graph.  A collective call: every rank makes it when (a) the last tiled solve succeeded and is retained, (b)
+ * any number of ranks have changed their tile graph since (update_graph any number of times, or a replaced graph), and
+ * (c) a new stitch is current on every rank, with the rank count and the tile layout of the solve: nodes never change
+ * tile.  new2old (n_map entries = this tile's nodes now): entry v is the LOCAL id this tile's node v had at the retained
+ * solve, -1 for a new node; NULL takes the engine's own map -- the identity after a tiled solve or refresh, composed
+ * through every update_graph since, none after init_graph, load_json, a reset or a failed update.  The map is a hint: a
+ * wrong entry carries a key that the anchor drops.  It decides only where the members are: a member's node is the first
+ * new local id of its owner tile that the map names as its old local id.
+ * The result is bit for bit what trg_engine_tiled_cost_field_sets / trg_engine_tiled_risk_field_sets computes from
+ * set_gids_out on the current stitch (a retained single-source solve: without the owner pass, and owner, the targets'
+ * reads and owned are neither read nor written): value bits, hops, global parents, owners, owned, the target reads and
+ * the roots.  The refreshed solve is then the retained one: it answers trg_engine_tiled_field_routes and
+ * trg_engine_tiled_field_reached, and can be refreshed again.  set_gids_out (set_ptr[m] of the retained request, the
+ * same on every rank): the NEW global id of every member.  carried_out (m): THIS tile's nodes per field that kept a key
+ * through carry and anchor.  A retained solve that is current on every rank refreshes with 0 rounds.
+ * TRG_ERR_INVALID_ARG before any collective, the retained solve still answering, for what every rank judges alike: no
+ * communicator; no retained tiled solve; a bounded, modelled or start-cost solve (removed keys bound nothing, and members
+ * would need their start costs as anchors); a solve of the other objective; another rank count than the solve's.  A
+ * rank's own failure -- no map, a wrong n_map or an entry that is no old node and not -1, no current stitch, a member
+ * whose node is gone (TRG_ERR_INVALID_ARG), an allocation (TRG_ERR_CAPACITY) -- is announced in the first count exchange:
+ * that rank returns its error, its peers TRG_ERR_DEVICE "another rank reported a failure", nobody waits, and nothing is
+ * retained afterwards. */
+typedef struct TrgTiledRefreshInfo {
+  int32_t exchanges;            /* all-gather-v exchanges of the two warm passes, the two without news included */
+  int32_t anchor_exchanges;     /* ... of the fill and both anchors */
+  int32_t owner_exchanges;      /* ... of the owner pass (0 without owners) */
+  int32_t rounds;               /* relaxation rounds of this rank that did work */
+  int32_t ghosts;
+  int32_t border_nodes;
+  int32_t roots;
+  int32_t m;                    /* fields of the refreshed solve */
+  int32_t owners;               /* 1: the retained solve was a set solve, the owner pass ran */
+  int32_t reserved;
+  int64_t records_sent;         /* key records this rank published in the passes */
+  int64_t anchor_records_sent;  /* carried keys, member records and anchor verdicts */
+  int64_t owner_records_sent;
+  float ms_device;
+  float ms_total;
+} TrgTiledRefreshInfo;
+TrgStatus trg_engine_tiled_cost_field_refresh(TrgEngine *e, const int32_t *new2old, int32_t n_map,
+    float *cost, int32_t *hops, int32_t *parent, int32_t *owner,   /* m x (this tile's nodes), any may be NULL */
+    const int32_t *targets, int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned,                                                /* set_ptr[m], may be NULL */
+    int32_t *set_gids_out,                                         /* set_ptr[m], may be NULL */
+    int32_t *carried_out,                                          /* m, may be NULL */
+    TrgTiledRefreshInfo *info);                                    /* may be NULL */
+TrgStatus trg_engine_tiled_risk_field_refresh(TrgEngine *e, const int32_t *new2old, int32_t n_map,
+    float *risk, int32_t *hops, int32_t *parent, int32_t *owner,
+    const int32_t *targets, int32_t n_targets, float *risk_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned, int32_t *set_gids_out, int32_t *carried_out, TrgTiledRefreshInfo *info);
 /* THIS tile's reached nodes of field `field` of the retained tiled solve (any tiled field call, bounded or not), in
  * ascending global id, compacted on the device: gids / value (cost or risk) / hops get the first `cap` of them (any may
  * be NULL), *n_out their total; cap == 0 returns the count alone.  Local work, no collective: the ranks' lists,

@@ -40,6 +40,7 @@
 #include "graph_json.h"
 #include "host_index.h"
 #include "map_order_sim.h"
+#include "node_map.h"
 #include "trg_kernels.h"
 
 namespace {
@@ -636,8 +637,10 @@ struct TrgEngine {
   // retained cost-field solve, -1 for a node made since.  A solve starts it as the identity, update_graph composes
   // it with its cleanGraph's renumbering; a new solve's start, every graph_changed() (init_graph, load_json, a
   // reset, an update's own before it composes) and an update that fails leave none.
-  enum { FIELD_MAP_NONE, FIELD_MAP_IDENTITY, FIELD_MAP_EXPLICIT } field_map_state = FIELD_MAP_NONE;
-  std::vector<int> field_map;
+  NodeMap field_map;
+  // The same for the retained solve across tiles (trg_engine_tiled_cost_field_refresh): LOCAL ids of this tile's graph
+  // at the tiled solve.  A tiled solve or refresh that succeeds starts it as the identity; the rest is field_map's.
+  NodeMap tiled_map;
   int debug_tie_every = 0;       // test hook: treat every n-th BFS level as tie-affected
   int debug_spec_bound = 0;      // test hook: cap the speculative sampling launch at n nodes
   int debug_fallback_level = -1; // test hook: the device BFS declines at this level
@@ -797,7 +800,8 @@ void graph_changed(TrgEngine *e, std::initializer_list<TrgEngine::GraphView> fre
   for (const auto v : fresh) e->view_stamp[v] = e->graph_version;
   e->stitched_edges = 0;
   e->csr_stitched.clear();
-  e->field_map_state = TrgEngine::FIELD_MAP_NONE;
+  e->field_map.state = NodeMap::NONE;
+  e->tiled_map.state = NodeMap::NONE;
 }
 
 void reset_graph_global(TrgEngine *e) {
@@ -1314,8 +1318,8 @@ TrgStatus update_graph(TrgEngine *e) {
   e->epoch++;
   e->view_stamp[TrgEngine::VIEW_DEV_CSR] = 0;  // dropped before anything can fail (the cost field's retained solve)
   const size_t nodes_before = e->nx.size();
-  const auto map_before = e->field_map_state;
-  e->field_map_state = TrgEngine::FIELD_MAP_NONE;  // (an update that fails leaves no map)
+  const NodeMap::State map_before = e->field_map.state, tiled_map_before = e->tiled_map.state;
+  e->field_map.state = e->tiled_map.state = NodeMap::NONE;  // (an update that fails leaves no map)
   const bool trace_up = getenv("TRG_TIMING") != nullptr;
   auto t_up = Clock::now();
   auto lap_up = [&](const char *what) {
@@ -1402,16 +1406,13 @@ TrgStatus update_graph(TrgEngine *e) {
     member_new[k] = member_old[e->last_new2old[k]];
   st = set_local_graph(e, &member_new);
   lap_up("setLocalGraph");
-  if (st == TRG_OK && map_before != TrgEngine::FIELD_MAP_NONE) {
-    // the cost field's node map through this update: a pre-clean id from nodes_before on is a node made here
-    std::vector<int> map(e->last_new2old.size());
-    for (size_t k = 0; k < map.size(); ++k) {
-      const int pre = e->last_new2old[k];
-      map[k] = (size_t)pre >= nodes_before ? -1 : map_before == TrgEngine::FIELD_MAP_IDENTITY ? pre : e->field_map[pre];
+  // the node maps of the retained solves through this update (node_map.h)
+  for (const auto &[map, before] : {std::pair<NodeMap *, NodeMap::State>{&e->field_map, map_before},
+                                    std::pair<NodeMap *, NodeMap::State>{&e->tiled_map, tiled_map_before}})
+    if (st == TRG_OK && before != NodeMap::NONE) {
+      map->state = before;
+      node_map_compose(*map, e->last_new2old, nodes_before);
     }
-    e->field_map.swap(map);
-    e->field_map_state = TrgEngine::FIELD_MAP_EXPLICIT;
-  }
   return st;  // cleanGraph(true) -> setLocalGraph (trg.cpp:532-534)
 }
 

@@ -220,17 +220,17 @@ TrgStatus field_check_refresh(TrgEngine *e, FieldRun &run) {
     return e->fail(TRG_ERR_INVALID_ARG, call + ": the retained solve is already of the current graph");
   const int V = (int)e->nx.size(), V_old = old.F.V, m = old.F.m;
   if (!rq.new2old) {
-    if (e->field_map_state == TrgEngine::FIELD_MAP_NONE)
+    if (e->field_map.state == NodeMap::NONE)
       return e->fail(TRG_ERR_INVALID_ARG, call + ": no node map is given and the engine has none for this graph "
                                                  "(pass new2old, or solve again)");
-    if (e->field_map_state == TrgEngine::FIELD_MAP_IDENTITY) {
+    if (e->field_map.state == NodeMap::IDENTITY) {
       run.identity.resize((size_t)V_old);
       for (int v = 0; v < V_old; ++v) run.identity[v] = v;
       rq.new2old = run.identity.data();
       rq.n_map = V_old;
     } else {  // (the engine's own stays in place through the phases: field_begin only marks it ended)
-      rq.new2old = e->field_map.data();
-      rq.n_map = (int32_t)e->field_map.size();
+      rq.new2old = e->field_map.ids.data();
+      rq.n_map = (int32_t)e->field_map.ids.size();
     }
   }
   if (rq.n_map != V)
@@ -372,7 +372,7 @@ TrgStatus field_begin(TrgEngine *e, FieldRun &) {
   if (!e->field) e->field.reset(new FieldBufs());
   FieldBufs &fb = *e->field;
   fb.last = FieldBufs::Last{};  // from here on the work arrays change
-  e->field_map_state = TrgEngine::FIELD_MAP_NONE;  // (the node map is of the retained solve's graph)
+  e->field_map.state = NodeMap::NONE;  // (the node map is of the retained solve's graph)
   HIPCHK(e, fb.h_state.ensure(1));
   HIPCHK(e, fb.h_stats.ensure(FIELD_SLOTS_MAX));
   HIPCHK(e, fb.h_reached.ensure(TRG_FIELD_BATCH_MAX));
@@ -770,7 +770,7 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   if (rq.models) fb.last.pairs.assign(rq.models, rq.models + m);
   fb.last.models = run.models;
   fb.last.many = run.many_models;
-  e->field_map_state = TrgEngine::FIELD_MAP_IDENTITY;  // update_graph takes the node map on from here
+  e->field_map.state = NodeMap::IDENTITY;  // update_graph takes the node map on from here
   return field_timing(e, run.info, run.syncs, run.t_total);
 }
 

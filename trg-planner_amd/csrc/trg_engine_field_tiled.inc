@@ -17,6 +17,8 @@
 // A cost solve may name a cost model per field ("Cost models across tiles"): the edge costs of every distinct model lie
 // in a slot of `ec`, cached per solve graph, the round kernels, the parent sweep and the walk take the slot table where
 // the fields read more than one slot, and the retained solve answers under its models.
+// The refresh ("Refresh across tiles") brings the retained solve to a new stitch: the carry before the work arrays are
+// regrown, a fifth use of the frame for the ghost fill and the anchors, the passes started warm, and the solve's tail.
 
 namespace {
 
@@ -84,7 +86,15 @@ struct TiledFieldBufs {
     FieldModels models{};
     bool many = false;
     const FieldModels *model_table() const { return many ? &models : nullptr; }
+    // What a refresh needs of it ("Refresh across tiles"): the request as solved, the stitch's node offsets then (the
+    // ranks' old id ranges: V_old of this tile and, with F.V, the stride its keys lie at), and whether it is one that
+    // cannot be refreshed -- under bounds its removed keys bound nothing, with start costs its members are no anchors.
+    std::vector<int32_t> set_ptr, set_gids, node_off;
+    bool bounded = false, seeded = false;
   } solved;
+  // A refresh: the carried keys (m x V), the anchored ones (m x (V + G)), the node map, the counts per field, the
+  // members' new global ids and the anchors' verdicts (m x (V + G)).
+  DevArr carry, key0, node_map, carried, members, rooted;
   DevArr route_field, route_target, route_off, route_gids, route_info;
   // Bounded solves ("Bounded fields across tiles"): this rank's settle targets (local ids), the words of TiledSettle --
   // `told` (FIELD_MAX_SOURCES words), then the table -- with the host copies their uploads read, and the bounds that
@@ -149,6 +159,11 @@ struct TiledRun {
   int round = 0;      // of the current pass
   int rounds = 0, exchanges = 0, owner_exchanges = 0, roots = 0;
   long long records = 0, owner_records = 0;
+  // a refresh ("Refresh across tiles"): the passes start warm, from what the anchor before them left
+  bool warm = false;
+  int anchor_exchanges = 0;
+  long long anchor_records = 0;
+  std::vector<int32_t> h_members, h_carried;  // what the first anchor brought back: every member's new gid, the counts
   double ms_device = 0.0;
 };
 
@@ -539,8 +554,10 @@ TrgStatus tiled_work_arrays(TrgEngine *e, TiledRun &run) {
   return TRG_OK;
 }
 
-// everything of this rank that comes before the first exchange
-TrgStatus tiled_prepare(TrgEngine *e, const ExchangeState &x, TiledRun &run) {
+// everything of this rank that comes before the first exchange; `between` is a refresh's carry, which needs the new
+// solve graph's node count and must be enqueued before the work arrays are regrown (a solve: nothing)
+template <typename Between>
+TrgStatus tiled_prepare(TrgEngine *e, const ExchangeState &x, TiledRun &run, Between between) {
   if (!e->tiled) e->tiled.reset(new TiledFieldBufs());
   TiledFieldBufs &tb = *e->tiled;
   HIPCHK(e, tb.h_state.ensure(1));
@@ -549,6 +566,7 @@ TrgStatus tiled_prepare(TrgEngine *e, const ExchangeState &x, TiledRun &run) {
   HIPCHK(e, tb.t0.create());
   HIPCHK(e, tb.t1.create());
   TrgStatus st = tiled_graph(e, x, run.rq.risk);
+  if (st == TRG_OK) st = between();
   if (st == TRG_OK) st = run.rq.risk ? tiled_edge_risks(e) : tiled_edge_costs(e, run);
   if (st == TRG_OK) st = tiled_work_arrays(e, run);
   return st;
@@ -657,7 +675,9 @@ TrgStatus tiled_pass(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus lo
     F.tight = pass ? tb.tight.as<unsigned>() : nullptr;
     run.round = 0;
     HIPCHK(e, hipEventRecord(tb.t0, s));
-    if (work)
+    if (work && run.warm)  // (`published` is the anchor's: the border keys it left)
+      launch_field_warm_start(F, delta, pass == 1, s, run.model_table(), run.rq.risk);
+    else if (work)
       launch_tiled_begin(F, T, tb.entries.as<TiledEntry>(), run.n_entries, delta, tb.published.as<unsigned long long>(), s);
     if (bounded) launch_field_bounds(F, run.budgets, s);
     return TRG_OK;
@@ -783,25 +803,9 @@ TrgStatus tiled_outputs(TrgEngine *e, TiledRun &run) {
   return TRG_OK;
 }
 
-// The collective part of a solve whose request passed tiled_check_request: the two passes, with owners the owner pass,
-// the outputs.  The owner pass is a collective: whether it runs hangs on the entry that was called, which every rank
-// decides alike, never on which outputs one rank asks for.
-TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
-  ExchangeState &x = *e->exchange;
-  if (e->tiled) e->tiled->solved = TiledFieldBufs::Solved{};  // (a solve that fails retains nothing)
-  // the budgets as cost bits; every rank decides alike whether the solve is a bounded one
-  for (int k = 0; k < run.rq.m; ++k) {
-    const float b = run.rq.budget ? run.rq.budget[k] : std::numeric_limits<float>::infinity();
-    run.budgets.bits[k] = b == 0.0f ? 0u : float_bits(b);  // (-0.0 orders as +0.0)
-    run.bounded = run.bounded || run.budgets.bits[k] != FIELD_INF_BITS;
-  }
-  run.bounded = run.bounded || run.rq.settle != TRG_FIELD_SETTLE_NONE;
-  TrgStatus local = tiled_prepare(e, x, run);
-  for (int pass = 0; pass < 2; ++pass) {
-    const TrgStatus st = tiled_pass(e, x, run, local, pass);
-    if (st != TRG_OK) return st;
-    local = TRG_OK;  // (a pass that returns TRG_OK had no failure of this rank left to announce)
-  }
+// What a solve and a refresh end with, after pass 2: with owners the owner pass (which runs the parent sweep), the
+// outputs, and the record of the retained solve, from which the routes, the reached list and the next refresh start.
+TrgStatus tiled_tail(TrgEngine *e, ExchangeState &x, TiledRun &run) {
   if (run.rq.owners)
     if (const TrgStatus st = tiled_owner_pass(e, x, run); st != TRG_OK) return st;
   if (const TrgStatus st = tiled_outputs(e, run); st != TRG_OK) return st;
@@ -812,7 +816,36 @@ TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
   if (run.rq.models) kept.pairs.assign(run.rq.models, run.rq.models + run.rq.m);
   kept.models = run.models;
   kept.many = run.many_models;
+  kept.set_ptr.assign(run.rq.set_ptr, run.rq.set_ptr + run.rq.m + 1);
+  kept.set_gids.assign(run.rq.set_gids, run.rq.set_gids + run.rq.set_ptr[run.rq.m]);
+  kept.node_off = e->stitch_node_off;
+  kept.bounded = run.bounded;
+  kept.seeded = run.rq.set_cost0 != nullptr;
+  e->tiled_map.state = NodeMap::IDENTITY;  // update_graph takes the node map on from here
   return TRG_OK;
+}
+
+// The collective part of a solve whose request passed tiled_check_request: the two passes, with owners the owner pass,
+// the outputs.  The owner pass is a collective: whether it runs hangs on the entry that was called, which every rank
+// decides alike, never on which outputs one rank asks for.
+TrgStatus tiled_solve(TrgEngine *e, TiledRun &run) {
+  ExchangeState &x = *e->exchange;
+  if (e->tiled) e->tiled->solved = TiledFieldBufs::Solved{};  // (a solve that fails retains nothing)
+  e->tiled_map.state = NodeMap::NONE;                           // (the node map was of the retained solve's tile graph)
+  // the budgets as cost bits; every rank decides alike whether the solve is a bounded one
+  for (int k = 0; k < run.rq.m; ++k) {
+    const float b = run.rq.budget ? run.rq.budget[k] : std::numeric_limits<float>::infinity();
+    run.budgets.bits[k] = b == 0.0f ? 0u : float_bits(b);  // (-0.0 orders as +0.0)
+    run.bounded = run.bounded || run.budgets.bits[k] != FIELD_INF_BITS;
+  }
+  run.bounded = run.bounded || run.rq.settle != TRG_FIELD_SETTLE_NONE;
+  TrgStatus local = tiled_prepare(e, x, run, [] { return TRG_OK; });
+  for (int pass = 0; pass < 2; ++pass) {
+    const TrgStatus st = tiled_pass(e, x, run, local, pass);
+    if (st != TRG_OK) return st;
+    local = TRG_OK;  // (a pass that returns TRG_OK had no failure of this rank left to announce)
+  }
+  return tiled_tail(e, x, run);
 }
 
 // What every rank judges alike, refused before any collective.
@@ -862,6 +895,245 @@ TrgStatus tiled_check_request(TrgEngine *e, const TiledRequest &rq) {
         return refuse("settle target " + std::to_string(j) + " (" + std::to_string(rq.settle_gids[j]) + ") is outside [0, " +
                       std::to_string(n_ids) + ")");
   }
+  return TRG_OK;
+}
+
+// ---- refresh across tiles (DESIGN.md section 7, "Refresh across tiles") ---------------------------------------------
+
+// One anchor of a refresh, a fifth use of the frame: the owner pass's loop over the forest of the SUPPORTERS, with
+// "this border item hangs on a member" where the owner pass trades owners.  The first anchor opens with the fill
+// exchange -- every border item's carried key and this rank's member records -- and finds the supporters when the
+// ghosts hold their owners' keys; it leaves the anchored keys in key0 and counts them.  The second cuts every item
+// whose key is no longer key0's and jumps the same supporters.  Both end with every item that is not known to hang on a
+// member losing its key, ghosts too, and `published` at the border keys that are left.  A tile without nodes takes
+// part in the first anchor's exchanges all the same: it must end with the members' new ids of the others.
+TrgStatus tiled_anchor(TrgEngine *e, ExchangeState &x, TiledRun &run, TrgStatus local, bool first) {
+  TiledFieldBufs &tb = *e->tiled;
+  const FieldTiled &T = tb.T;
+  const FieldDev &F = run.F;
+  hipStream_t s = e->s_main;
+  const bool work = F.N > 0;
+  const int fill = first ? 1 : 0;
+  const int n_members = run.rq.set_ptr[run.rq.m];
+  int *rooted = tb.rooted.as<int>();
+  unsigned long long *key0 = tb.key0.as<unsigned long long>();
+  unsigned long long *published = tb.published.as<unsigned long long>();
+  const std::string what = std::string(run.rq.what) + "anchor: ";
+  const int *anc = nullptr;
+  const int before = run.anchor_exchanges;
+  run.always = first;
+  TiledLocal mine(e, local);
+  mine.step([&]() -> TrgStatus {
+    HIPCHK(e, hipEventRecord(tb.t0, s));
+    return TRG_OK;
+  });
+  const TrgStatus st = tiled_exchanges(
+      e, x, run, mine, what, (long long)F.m * T.B + (first ? run.n_entries : 0),
+      [&](long long border) { return F.m * border + 2 + fill; }, run.anchor_exchanges, run.anchor_records,
+      [&](int exchange, const void *d_all, int gathered) -> TrgStatus {
+        if (exchange < fill) {
+          if (work)
+            launch_tiled_fill_publish(F, T, tb.entries.as<TiledEntry>(), run.n_entries, published, tb.rec.p, tb.n_rec.as<int>(), s);
+          return TRG_OK;
+        }
+        if (exchange == fill) {
+          if (first) launch_tiled_fill_ghosts(F, T, d_all, gathered, tb.members.as<int>(), n_members, s);
+          if (!work) return TRG_OK;
+          int *changed = tb.own_changed.as<int>();
+          if (first) launch_tiled_parents(F, T, s, run.rq.risk, run.model_table());  // (pass 1 writes no parent)
+          launch_tiled_anchor_begin(F, T, first ? nullptr : key0, rooted, changed, published, s);
+          int sweeps = 0;
+          if (const TrgStatus r = field_forest_sweeps(e, F, changed, &tb.h_n[0], "tiled field refresh: an anchor's sweeps", sweeps);
+              r != TRG_OK)
+            return r;
+          anc = F.q[sweeps & 1];
+          d_all = nullptr;  // (the fill's records are no verdicts)
+          gathered = 0;
+        }
+        if (work) launch_tiled_owner_step(F, T, d_all, gathered, anc, rooted, published, tb.rec.p, tb.n_rec.as<int>(), s);
+        return TRG_OK;
+      });
+  run.always = false;
+  if (st != TRG_OK) return st;
+  if (run.anchor_exchanges - before <= fill)  // (never: some rank owns a member and published its record)
+    return e->fail(TRG_ERR_DEVICE, what + "the fill exchange carried no record");
+  if (work) {
+    HIPCHK(e, hipEventRecord(tb.t0, s));
+    launch_tiled_anchor_end(F, T, rooted, first ? key0 : nullptr, first ? tb.carried.as<int>() : nullptr, published, s);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(tb.t1, s));
+  }
+  if (first) {
+    run.h_members.assign((size_t)n_members, -1);
+    run.h_carried.assign((size_t)F.m, 0);
+    HIPCHK(e, hipMemcpyAsync(run.h_members.data(), tb.members.p, (size_t)n_members * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (work) HIPCHK(e, hipMemcpyAsync(run.h_carried.data(), tb.carried.p, (size_t)F.m * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(e, hipStreamSynchronize(s));
+  return work ? tiled_lap(e, run) : TRG_OK;
+}
+
+// What a refresh is given beside the set call's outputs.
+struct TiledRefreshRequest {
+  bool risk;  // the objective of the entry that was called
+  const int32_t *new2old;
+  int32_t n_map;
+  float *value;
+  int32_t *hops, *parent, *owner;
+  const int32_t *targets;
+  int32_t n_targets;
+  float *value_at;
+  int32_t *hops_at, *owner_at, *owned, *set_gids_out, *carried_out;
+};
+
+// The refresh of the retained tiled solve: DESIGN.md section 2's steps on the stitched graph.  What every rank judges
+// alike is refused first and leaves the retained solve as it was; from there on nothing is retained until the tail.
+TrgStatus tiled_refresh(TrgEngine *e, const TiledRefreshRequest &a, TrgTiledRefreshInfo *info) {
+  const Clock::time_point t_total = Clock::now();
+  TrgTiledRefreshInfo local_info{};
+  TrgTiledRefreshInfo &out = info ? *info : local_info;
+  out = TrgTiledRefreshInfo{};
+  const std::string what = a.risk ? "tiled risk field refresh: " : "tiled cost field refresh: ";
+  const auto refuse = [&](const std::string &why) { return e->fail(TRG_ERR_INVALID_ARG, what + why); };
+  if (!e->exchange || !e->exchange->transport) return refuse("no communicator (trg_engine_comm_init)");
+  if (!e->tiled || !e->tiled->solved.valid) return refuse("no tiled solve is retained (a tiled field call first)");
+  ExchangeState &x = *e->exchange;
+  TiledFieldBufs &tb = *e->tiled;
+  if (tb.solved.bounded) return refuse("the retained solve is bounded (a bounded solve cannot be refreshed: its removed keys bound nothing)");
+  if (!tb.solved.pairs.empty()) return refuse("the retained solve has cost models (a modelled solve cannot be refreshed)");
+  if (tb.solved.seeded)
+    return refuse("the retained solve has start costs (a seeded solve cannot be refreshed: its members' keys are not carried)");
+  if (tb.solved.risk != a.risk)
+    return refuse(a.risk ? "the retained solve is a cost field (use trg_engine_tiled_cost_field_refresh)"
+                         : "the retained solve is a risk field (use trg_engine_tiled_risk_field_refresh)");
+  if ((int)tb.solved.node_off.size() - 1 != x.nranks)
+    return refuse("the communicator has " + std::to_string(x.nranks) + " ranks, the retained solve had " +
+                  std::to_string((int)tb.solved.node_off.size() - 1));
+  if (a.n_targets < 0 || (a.n_targets > 0 && !a.targets)) return refuse("n_targets < 0, or targets is null with n_targets > 0");
+  // ---- collective from here on: nothing is retained until the tail has run ----
+  TiledFieldBufs::Solved old = std::move(tb.solved);
+  tb.solved = TiledFieldBufs::Solved{};
+  const NodeMap::State map_state = e->tiled_map.state;
+  e->tiled_map.state = NodeMap::NONE;
+  const int m = old.m, n_members = old.set_ptr[m];
+  std::vector<int32_t> gids((size_t)n_members, -1);  // the members' new global ids: this rank's own, then all
+  TiledRequest rq{m, old.set_ptr.data(), gids.data(), nullptr, a.value, a.hops, a.parent, old.owners, a.risk, what.c_str(),
+                  "", nullptr};
+  if (old.owners) {
+    rq.owner = a.owner;
+    rq.targets = a.targets;
+    rq.n_targets = a.n_targets;
+    rq.cost_at = a.value_at;
+    rq.hops_at = a.hops_at;
+    rq.owner_at = a.owner_at;
+    rq.owned = a.owned;
+  }
+  TiledRun run{rq};
+  run.warm = true;
+  for (int k = 0; k < m; ++k) run.budgets.bits[k] = FIELD_INF_BITS;
+  hipStream_t s = e->s_main;
+  // Step 1, the carry, between the new solve graph and the regrown work arrays: the map, this rank's members, the keys.
+  const auto carry = [&]() -> TrgStatus {
+    const FieldTiled &T = tb.T;
+    const int rank = x.rank, V = T.V;
+    const int V_old = old.node_off[rank + 1] - old.node_off[rank];
+    const int32_t *map = a.new2old;
+    int32_t n_map = a.n_map;
+    std::vector<int32_t> identity;
+    if (!map) {
+      if (map_state == NodeMap::NONE)
+        return refuse("no node map is given and the engine has none for this tile's graph (pass new2old, or solve again)");
+      if (map_state == NodeMap::IDENTITY) {
+        identity.resize((size_t)V_old);
+        for (int v = 0; v < V_old; ++v) identity[v] = v;
+        map = identity.data();
+        n_map = V_old;
+      } else {
+        map = e->tiled_map.ids.data();
+        n_map = (int32_t)e->tiled_map.ids.size();
+      }
+    }
+    if (n_map != V)
+      return refuse("the node map has " + std::to_string(n_map) + " entries, the tile " + std::to_string(V) + " nodes");
+    std::vector<int32_t> first((size_t)V_old, -1);  // the first node of the tile's graph now that names an old one
+    for (int v = 0; v < V; ++v) {
+      const int o = map[v];
+      if (o < -1 || o >= V_old)
+        return refuse("node map entry " + std::to_string(v) + " (" + std::to_string(o) + ") is no node of this tile at the retained solve (" +
+                      std::to_string(V_old) + " nodes) and not -1");
+      if (o >= 0 && first[o] < 0) first[o] = v;
+    }
+    for (int k = 0; k < m; ++k)
+      for (int j = old.set_ptr[k]; j < old.set_ptr[k + 1]; ++j) {
+        const int32_t g = old.set_gids[j];
+        const int owner = (int)(std::upper_bound(old.node_off.begin(), old.node_off.end(), g) - old.node_off.begin()) - 1;
+        if (owner != rank) continue;
+        const int l = g - old.node_off[rank];
+        if (l < 0 || l >= V_old || first[l] < 0)
+          return refuse("member " + std::to_string(j - old.set_ptr[k]) + " of set " + std::to_string(k) + " (global id " +
+                        std::to_string(g) + " of the retained solve) has no node in this tile's graph");
+        gids[j] = T.lo + first[l];
+      }
+    if (V <= 0) return TRG_OK;
+    TrgStatus st;
+    if ((st = tiled_grow(e, tb.carry, ((size_t)m * V + 4) * sizeof(unsigned long long))) != TRG_OK ||
+        (st = tiled_grow(e, tb.node_map, ((size_t)V + 4) * sizeof(int))) != TRG_OK)
+      return st;
+    HIPCHK(e, hipMemcpyAsync(tb.node_map.p, map, (size_t)V * sizeof(int), hipMemcpyHostToDevice, s));
+    launch_tiled_carry(old.F.key, old.F.V, V_old, tb.node_map.as<int>(), V, m, tb.carry.as<unsigned long long>(), s);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(s));  // (the map may be this call's own vector; the old keys are read before they move)
+    return TRG_OK;
+  };
+  TrgStatus local = tiled_prepare(e, x, run, carry);
+  if (local == TRG_OK)
+    local = [&]() -> TrgStatus {
+      const FieldTiled &T = tb.T;
+      const FieldDev &F = run.F;
+      const size_t nN = (size_t)F.N + 4;
+      TrgStatus st;
+      if ((st = tiled_grow(e, tb.key0, nN * sizeof(unsigned long long))) != TRG_OK ||
+          (st = tiled_grow(e, tb.rooted, nN * sizeof(int))) != TRG_OK ||
+          (st = tiled_grow(e, tb.own_changed, FIELD_OWNER_SWEEPS_MAX * sizeof(int))) != TRG_OK ||
+          (st = tiled_grow(e, tb.carried, (TRG_FIELD_BATCH_MAX + 1) * sizeof(int))) != TRG_OK ||
+          (st = tiled_grow(e, tb.members, ((size_t)n_members + 1) * sizeof(int))) != TRG_OK ||
+          (st = tiled_grow(e, tb.rec, ((size_t)m * T.B + 4 + (size_t)run.n_entries) * FIELD_TILED_REC_BYTES)) != TRG_OK)
+        return st;
+      HIPCHK(e, hipMemsetAsync(tb.members.p, 0xFF, ((size_t)n_members + 1) * sizeof(int), s));
+      if (F.N > 0) {
+        launch_tiled_refresh_begin(F, T, tb.carry.as<unsigned long long>(), tb.entries.as<TiledEntry>(), run.n_entries, 0.0f, s);
+        HIPCHK(e, hipGetLastError());
+      }
+      return TRG_OK;
+    }();
+  // Steps 2 and 3: the ghost fill and the anchor.  Then every rank knows every member's node.
+  TrgStatus st = tiled_anchor(e, x, run, local, true);
+  if (st != TRG_OK) return st;
+  for (int j = 0; j < n_members; ++j) {
+    if (run.h_members[j] < 0 || (gids[j] >= 0 && gids[j] != run.h_members[j]))
+      return e->fail(TRG_ERR_DEVICE, what + "the ranks disagree on where member entry " + std::to_string(j) + " lies");
+    gids[j] = run.h_members[j];
+  }
+  // Steps 4 to 6: pass 1 warm, the second anchor, pass 2 warm; then a solve's tail.
+  if ((st = tiled_pass(e, x, run, TRG_OK, 0)) != TRG_OK || (st = tiled_anchor(e, x, run, TRG_OK, false)) != TRG_OK ||
+      (st = tiled_pass(e, x, run, TRG_OK, 1)) != TRG_OK || (st = tiled_tail(e, x, run)) != TRG_OK)
+    return st;
+  if (a.set_gids_out) std::copy(gids.begin(), gids.end(), a.set_gids_out);
+  if (a.carried_out) std::copy(run.h_carried.begin(), run.h_carried.end(), a.carried_out);
+  out.exchanges = run.exchanges;
+  out.anchor_exchanges = run.anchor_exchanges;
+  out.owner_exchanges = run.owner_exchanges;
+  out.rounds = run.rounds;
+  out.ghosts = tb.T.G;
+  out.border_nodes = tb.T.B;
+  out.roots = run.roots;
+  out.m = m;
+  out.owners = old.owners ? 1 : 0;
+  out.records_sent = run.records;
+  out.anchor_records_sent = run.anchor_records;
+  out.owner_records_sent = run.owner_records;
+  out.ms_device = (float)run.ms_device;
+  out.ms_total = (float)ms_since(t_total);
   return TRG_OK;
 }
 
@@ -1258,6 +1530,30 @@ TrgStatus trg_engine_tiled_risk_field_bounded(TrgEngine *e, int32_t m, const int
     return tiled_bounded_call(e, m, set_ptr, set_gids, nullptr, owners != 0, true, "tiled risk field bounded: ", budget,
                               settle, settle_gids, n_settle, risk, hops, parent, owner, targets, n_targets, risk_at,
                               hops_at, owner_at, owned, bound_out, reached_out, info);
+  });
+}
+
+TrgStatus trg_engine_tiled_cost_field_refresh(TrgEngine *e, const int32_t *new2old, int32_t n_map, float *cost,
+                                              int32_t *hops, int32_t *parent, int32_t *owner, const int32_t *targets,
+                                              int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
+                                              int32_t *owned, int32_t *set_gids_out, int32_t *carried_out,
+                                              TrgTiledRefreshInfo *info) {
+  return entry(e, "tiled_cost_field_refresh", DEVICE, [&] {
+    return tiled_refresh(e, TiledRefreshRequest{false, new2old, n_map, cost, hops, parent, owner, targets, n_targets, cost_at,
+                                                hops_at, owner_at, owned, set_gids_out, carried_out},
+                         info);
+  });
+}
+
+TrgStatus trg_engine_tiled_risk_field_refresh(TrgEngine *e, const int32_t *new2old, int32_t n_map, float *risk,
+                                              int32_t *hops, int32_t *parent, int32_t *owner, const int32_t *targets,
+                                              int32_t n_targets, float *risk_at, int32_t *hops_at, int32_t *owner_at,
+                                              int32_t *owned, int32_t *set_gids_out, int32_t *carried_out,
+                                              TrgTiledRefreshInfo *info) {
+  return entry(e, "tiled_risk_field_refresh", DEVICE, [&] {
+    return tiled_refresh(e, TiledRefreshRequest{true, new2old, n_map, risk, hops, parent, owner, targets, n_targets, risk_at,
+                                                hops_at, owner_at, owned, set_gids_out, carried_out},
+                         info);
   });
 }
 

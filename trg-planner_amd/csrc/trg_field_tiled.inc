@@ -21,7 +21,11 @@
 // k_tiled_bound_fold around trg_field.hip's BOUNDED round kernels; k_tiled_reached and k_tiled_list_count / _emit list
 // a rank's own reached nodes.  A cost model per field ("Cost models across tiles"): the only kernels here that read an
 // edge cost, k_tiled_parent and k_tiled_route_step, have a MODELS form that takes the slot of the block's or the route's
-// field from a FieldModels table, as trg_field.hip's round kernels do.
+// field from a FieldModels table, as trg_field.hip's round kernels do.  The refresh of a retained solve ("Refresh across
+// tiles"): k_tiled_carry and k_tiled_refresh_begin bring this rank's keys to the new solve graph, k_tiled_member_recs and
+// k_tiled_fill_ghosts are the fill exchange's two ends, k_tiled_anchor_begin / _end an anchor around the owner pass's
+// sweeps and step, k_tiled_published_init what a warm pass starts from as published; the passes themselves are
+// trg_field.hip's warm start and round kernels.
 //
 // All kernels: wave64, bounds taken from the arguments, no scalar memory writes, nothing waits on another workgroup.
 
@@ -665,7 +669,192 @@ __global__ __launch_bounds__(THREADS) void k_tiled_route_end(const TiledRouteRec
   }
 }
 
+// ---- refresh across tiles (DESIGN.md section 7, "Refresh across tiles") ---------------------------------------------
+
+// grid.y = field: this rank's keys of the retained solve (V_old local nodes per field, at `old_stride` = V_old + G_old
+// items per field; ghost keys are not carried) at the local nodes of the new tile graph, none where the map names no
+// old node.  `out` (m x V, no ghosts: their number is not known yet) is no array of the old solve.
+__global__ __launch_bounds__(THREADS) void k_tiled_carry(const unsigned long long *__restrict__ old_key,
+                                                         long long old_stride, int V_old,
+                                                         const int *__restrict__ new2old, int V,
+                                                         unsigned long long *__restrict__ out) {
+  const long long obase = (long long)blockIdx.y * old_stride;
+  const int fbase = blockIdx.y * V;
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
+    const int o = new2old[v];
+    out[fbase + v] = o >= 0 && o < V_old ? old_key[obase + o] : FIELD_KEY_NONE;
+  }
+}
+
+// grid.y = field, over the solve graph's items: k_field_init for a refresh.  A local node takes its carried key, a
+// ghost none (the fill gives it its owner's); parents, stamps and the control block as a cold pass starts them, so
+// that k_tiled_seed can force and mark this rank's members.
+__global__ __launch_bounds__(THREADS) void k_tiled_refresh_begin(FieldDev F, FieldTiled T,
+                                                                 const unsigned long long *__restrict__ carried,
+                                                                 float delta) {
+  const int f = blockIdx.y;
+  const int fbase = f * F.V, cbase = f * T.V;
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < F.V; v += gridDim.x * blockDim.x) {
+    F.key[fbase + v] = v < T.V ? carried[cbase + v] : FIELD_KEY_NONE;
+    F.parent[fbase + v] = INT_MAX;
+    F.stamp_near[fbase + v] = 0;
+    F.stamp_far[fbase + v] = 0u;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) F.ctrl->reached[f] = 0;
+  if (blockIdx.x == 0 && f == 0 && threadIdx.x == 0) field_ctrl_reset(F, __float_as_uint(delta), delta, 0);
+}
+
+// One thread per entry of this rank's entry table: a member record (entry, -1, the member's NEW global id) behind the
+// key records of the fill exchange, so that every rank learns where every member of the retained request lies now.
+// The key merges ignore it: its gid names no node.
+__global__ __launch_bounds__(THREADS) void k_tiled_member_recs(FieldTiled T, const TiledEntry *__restrict__ ent, int n,
+                                                               TiledRec *rec, int *n_rec, int room) {
+  const int n_iter = (n + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, i = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, i += gridDim.x * blockDim.x) {
+    const bool mine = i < n;
+    TiledRec r{};
+    if (mine) {
+      const TiledEntry t = ent[i];
+      r.field = t.entry;
+      r.gid = -1;
+      r.key = (unsigned long long)(unsigned)(T.lo + t.node);
+    }
+    const int slot = wave_reserve(mine, n_rec);
+    if (mine && slot < room) rec[slot] = r;
+  }
+}
+
+// The ghost fill, the "set" form of k_tiled_merge: one thread per gathered record of the fill exchange.  A key record
+// of another rank that names one of this rank's ghosts gives the ghost its owner's carried key, by assignment (an owner
+// publishes a node once: one thread writes the word; nothing is queued).  A member record writes its entry's word of
+// `members` (n_members words; an entry has one owner, so one record).
+__global__ __launch_bounds__(THREADS) void k_tiled_fill_ghosts(FieldDev F, FieldTiled T,
+                                                               const TiledRec *__restrict__ rec, int n_rec,
+                                                               int *members, int n_members) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += gridDim.x * blockDim.x) {
+    const TiledRec r = rec[i];
+    if (r.gid < 0) {
+      if (r.gid == -1 && r.field >= 0 && r.field < n_members) members[r.field] = (int)(unsigned)r.key;
+      continue;
+    }
+    const int item = T.G > 0 ? tiled_rec_item(F, T, r) : -1;  // (a tile without nodes has no ghost table)
+    if (item >= 0) F.key[item] = r.key;
+  }
+}
+
+// grid.y = field, over the solve graph's items: the forest of an anchor, k_tiled_forest_begin over the SUPPORTERS that
+// k_tiled_parent found under the carried keys.  `rooted` takes the owner pass's place: >= 0 where an item is known to
+// hang on a member (a marked member at once), -1 where not yet.  A ghost with a key is a terminal whose verdict its
+// owner publishes; an item without a supporter points nowhere and is lost.  With key0 (the second anchor) an item
+// whose key is no longer key0's is cut.
+__global__ __launch_bounds__(THREADS) void k_tiled_anchor_begin(FieldDev F, FieldTiled T,
+                                                                const unsigned long long *__restrict__ key0,
+                                                                int *rooted) {
+  const int fbase = blockIdx.y * F.V;
+  int *anc = F.q[0];
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < F.V; v += gridDim.x * blockDim.x) {
+    const int i = fbase + v;
+    const unsigned long long k = F.key[i];
+    int a = -1, o = -1;
+    if (k != FIELD_KEY_NONE && (!key0 || k == key0[i])) {
+      if (v >= T.V) {
+        a = i;
+      } else if (F.stamp_near[i] < 0) {
+        a = i;
+        o = 0;
+      } else {
+        const int p = F.parent[i];
+        const int j = tiled_ghost(T, p);
+        if (p >= T.lo && p < T.lo + T.V) a = fbase + (p - T.lo);
+        else if (j >= 0) a = fbase + T.V + j;
+      }
+    }
+    anc[i] = a;
+    rooted[i] = o;
+  }
+}
+
+// grid.y = field, over the solve graph's items, after the anchor's exchanges: an item that is not known to hang on a
+// member loses its key, a ghost too.  key0 / carried (the first anchor): the keys as they are now (m x (V + G)), and
+// per field the count of this rank's OWN nodes that kept theirs, one atomic per wave.
+__global__ __launch_bounds__(THREADS) void k_tiled_anchor_end(FieldDev F, FieldTiled T, const int *__restrict__ rooted,
+                                                              unsigned long long *__restrict__ key0, int *carried) {
+  const int fbase = blockIdx.y * F.V;
+  const int n_iter = (F.V + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
+  for (int it = 0, v = blockIdx.x * blockDim.x + threadIdx.x; it < n_iter; ++it, v += gridDim.x * blockDim.x) {
+    bool kept = false;
+    if (v < F.V) {
+      unsigned long long k = F.key[fbase + v];
+      if (rooted[fbase + v] < 0 && k != FIELD_KEY_NONE) F.key[fbase + v] = k = FIELD_KEY_NONE;
+      if (key0) key0[fbase + v] = k;
+      kept = v < T.V && k != FIELD_KEY_NONE;
+    }
+    const unsigned long long mk = ballot(kept);
+    if (carried && mk && lane_id() == __ffsll(mk) - 1) atomicAdd(&carried[blockIdx.y], __popcll(mk));
+  }
+}
+
+// Over (field, border row) pairs: what a warm pass starts from as published -- the border keys as the anchor left
+// them, which every ghost of them mirrors.  A pass then publishes only what its rounds lowered.
+__global__ __launch_bounds__(THREADS) void k_tiled_published_init(FieldDev F, FieldTiled T,
+                                                                  unsigned long long *published) {
+  const int items = F.m * T.B;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < items; i += gridDim.x * blockDim.x) {
+    const int f = i / T.B;
+    published[i] = F.key[f * F.V + T.border[i - f * T.B]];
+  }
+}
+
 }  // namespace
+
+void launch_tiled_carry(const unsigned long long *old_key, long long old_stride, int V_old, const int *new2old, int V,
+                        int m, unsigned long long *out, hipStream_t s) {
+  if (V > 0 && m > 0)
+    hipLaunchKernelGGL(k_tiled_carry, dim3(field_blocks(V, THREADS), m), dim3(THREADS), 0, s, old_key, old_stride, V_old,
+                       new2old, V, out);
+}
+
+void launch_tiled_refresh_begin(const FieldDev &F, const FieldTiled &T, const unsigned long long *carried,
+                                const TiledEntry *entries, int n_entries, float delta, hipStream_t s) {
+  hipLaunchKernelGGL(k_tiled_refresh_begin, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, carried,
+                     delta);
+  if (n_entries > 0)
+    hipLaunchKernelGGL(k_tiled_seed, dim3(field_blocks(n_entries, THREADS)), dim3(THREADS), 0, s, F, entries, n_entries);
+}
+
+void launch_tiled_fill_publish(const FieldDev &F, const FieldTiled &T, const TiledEntry *entries, int n_entries,
+                               unsigned long long *published, void *rec, int *n_rec, hipStream_t s) {
+  (void)hipMemsetAsync(published, 0xFF, ((size_t)F.m * T.B + 1) * sizeof(unsigned long long), s);
+  launch_tiled_publish(F, T, nullptr, published, rec, n_rec, s);
+  if (n_entries > 0)
+    hipLaunchKernelGGL(k_tiled_member_recs, dim3(field_blocks(n_entries, THREADS)), dim3(THREADS), 0, s, T, entries,
+                       n_entries, (TiledRec *)rec, n_rec, F.m * T.B + n_entries);
+}
+
+void launch_tiled_fill_ghosts(const FieldDev &F, const FieldTiled &T, const void *rec, int n_rec, int *members,
+                              int n_members, hipStream_t s) {
+  if (n_rec > 0)
+    hipLaunchKernelGGL(k_tiled_fill_ghosts, dim3(field_blocks(n_rec, THREADS)), dim3(THREADS), 0, s, F, T,
+                       (const TiledRec *)rec, n_rec, members, n_members);
+}
+
+void launch_tiled_anchor_begin(const FieldDev &F, const FieldTiled &T, const unsigned long long *key0, int *rooted,
+                               int *changed, unsigned long long *published, hipStream_t s) {
+  (void)hipMemsetAsync(changed, 0, FIELD_OWNER_SWEEPS_MAX * sizeof(int), s);
+  (void)hipMemsetAsync(published, 0xFF, ((size_t)F.m * T.B + 1) * sizeof(unsigned long long), s);
+  hipLaunchKernelGGL(k_tiled_anchor_begin, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, key0,
+                     rooted);
+}
+
+void launch_tiled_anchor_end(const FieldDev &F, const FieldTiled &T, const int *rooted, unsigned long long *key0,
+                             int *carried, unsigned long long *published, hipStream_t s) {
+  if (carried) (void)hipMemsetAsync(carried, 0, (size_t)F.m * sizeof(int), s);
+  hipLaunchKernelGGL(k_tiled_anchor_end, dim3(field_blocks(F.V, THREADS), F.m), dim3(THREADS), 0, s, F, T, rooted, key0,
+                     carried);
+  if (T.B > 0)
+    hipLaunchKernelGGL(k_tiled_published_init, dim3(field_blocks((long long)F.m * T.B, THREADS)), dim3(THREADS), 0, s, F,
+                       T, published);
+}
 
 void launch_tiled_route_len(const FieldDev &F, const FieldTiled &T, const TiledRoutes &R, hipStream_t s) {
   (void)hipMemsetAsync(R.n_rec, 0, sizeof(int), s);

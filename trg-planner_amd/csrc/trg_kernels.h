@@ -715,6 +715,33 @@ void launch_tiled_owner_step(const FieldDev &F, const FieldTiled &T, const void 
 // owned (n_entries, zeroed here) = the local nodes per entry
 void launch_tiled_owned(const FieldDev &F, const FieldTiled &T, const int *set_ptr, const int *owner, int n_entries,
                         int *owned, hipStream_t s);
+// Refresh across tiles ("Refresh across tiles"): the retained tiled solve brought to a new stitch.
+// carry: out[k * V + v] = old_key[k * old_stride + new2old[v]] over this rank's local nodes, FIELD_KEY_NONE where
+// new2old[v] is no local node of the old tile graph (V_old of them); `out` is no array of the old solve.
+void launch_tiled_carry(const unsigned long long *old_key, long long old_stride, int V_old, const int *new2old, int V,
+                        int m, unsigned long long *out, hipStream_t s);
+// launch_field_init's place in a refresh: the local nodes take their carried keys (m x T.V), the ghosts none; then
+// this rank's members are forced to (0, 0) and marked, as launch_tiled_begin seeds them (entries at cost 0).
+void launch_tiled_refresh_begin(const FieldDev &F, const FieldTiled &T, const unsigned long long *carried,
+                                const TiledEntry *entries, int n_entries, float delta, hipStream_t s);
+// The fill exchange's publish: every border item with a key (published: m * B + 1 words, reset here), then one member
+// record (entry, -1, new global id) per entry of this rank.  m * B + n_entries records at most.
+void launch_tiled_fill_publish(const FieldDev &F, const FieldTiled &T, const TiledEntry *entries, int n_entries,
+                               unsigned long long *published, void *rec, int *n_rec, hipStream_t s);
+// the gathered records of the fill exchange: every ghost takes its owner's carried key by assignment, every member
+// record writes members[entry] (n_members words)
+void launch_tiled_fill_ghosts(const FieldDev &F, const FieldTiled &T, const void *rec, int n_rec, int *members,
+                              int n_members, hipStream_t s);
+// An anchor over the owner frame, after launch_tiled_parents found the supporters.  begin: F.q[0] = every item's first
+// ancestor in the supporter forest, rooted (m x (V + G)) >= 0 for the marked members and -1 elsewhere; with key0 every
+// item whose key is not key0's is cut; changed and published are reset as launch_tiled_forest_begin resets them.  Then
+// launch_field_owner_sweep and launch_tiled_owner_step over `rooted`, as the owner pass runs them over its owners.
+void launch_tiled_anchor_begin(const FieldDev &F, const FieldTiled &T, const unsigned long long *key0, int *rooted,
+                               int *changed, unsigned long long *published, hipStream_t s);
+// end: every item with rooted < 0 loses its key; key0 / carried (the first anchor; else nullptr): the keys as they are
+// now and, per field, this rank's own nodes that kept theirs; published = the border keys as they are now.
+void launch_tiled_anchor_end(const FieldDev &F, const FieldTiled &T, const int *rooted, unsigned long long *key0,
+                             int *carried, unsigned long long *published, hipStream_t s);
 // Routes across tiles ("Routes across tiles"): the routes of a finished tiled solve whose parent
 // sweep ran, each walked by the rank that owns the node it stands on and handed over at a seam through the exchange's
 // 16-byte records.  Layout of TrgTiledRouteInfo (include/trg_engine.h).

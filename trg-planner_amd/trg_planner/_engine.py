@@ -72,6 +72,14 @@ class TrgTiledSetInfo(C.Structure):
                 ("owner_records_sent", C.c_int64), ("ms_device", C.c_float), ("ms_total", C.c_float)]
 
 
+class TrgTiledRefreshInfo(C.Structure):
+    _fields_ = [("exchanges", C.c_int32), ("anchor_exchanges", C.c_int32), ("owner_exchanges", C.c_int32),
+                ("rounds", C.c_int32), ("ghosts", C.c_int32), ("border_nodes", C.c_int32), ("roots", C.c_int32),
+                ("m", C.c_int32), ("owners", C.c_int32), ("reserved", C.c_int32), ("records_sent", C.c_int64),
+                ("anchor_records_sent", C.c_int64), ("owner_records_sent", C.c_int64), ("ms_device", C.c_float),
+                ("ms_total", C.c_float)]
+
+
 class TrgRouteInfo(C.Structure):
     _fields_ = [("num_nodes", C.c_int32), ("cost", C.c_float), ("path_length", C.c_float),
                 ("avg_risk", C.c_float)]
@@ -142,7 +150,7 @@ EXPORTS = [
     "trg_engine_tiled_cost_field", "trg_engine_stitch_ids", "trg_engine_tiled_cost_field_sets",
     "trg_engine_tiled_field_routes", "trg_engine_tiled_risk_field", "trg_engine_tiled_risk_field_sets",
     "trg_engine_tiled_cost_field_bounded", "trg_engine_tiled_risk_field_bounded", "trg_engine_tiled_field_reached",
-    "trg_engine_tiled_cost_field_models",
+    "trg_engine_tiled_cost_field_models", "trg_engine_tiled_cost_field_refresh", "trg_engine_tiled_risk_field_refresh",
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
@@ -265,6 +273,9 @@ def load_library():
     L.trg_engine_tiled_cost_field_models.argtypes = [vp, C.c_int32, C.POINTER(TrgFieldModel)] + \
         L.trg_engine_tiled_cost_field_bounded.argtypes[2:]
     L.trg_engine_tiled_field_reached.argtypes = [vp, C.c_int32, ip, fp, ip, C.c_int32, ip]
+    L.trg_engine_tiled_cost_field_refresh.argtypes = [vp, ip, C.c_int32, fp, ip, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip,
+                                                      ip, C.POINTER(TrgTiledRefreshInfo)]
+    L.trg_engine_tiled_risk_field_refresh.argtypes = L.trg_engine_tiled_cost_field_refresh.argtypes
     L.trg_engine_tiled_field_routes.argtypes = [vp, C.c_int32, ip, ip, ip, ip, fp, C.c_int32,
                                                 C.POINTER(TrgTiledRouteInfo), C.POINTER(TrgTiledRoutesInfo)]
     L.trg_engine_fallback_reason.argtypes = [vp]
@@ -377,6 +388,7 @@ class Engine:
         self.sampler = TrgSampler(1, 16)
         self.last_reuse = None  # frontier_ceilings(reuse=True): the refresh's dict when it was taken
         self._retained = Retained()  # (nothing solved through this object yet: one field, no sets, source -1)
+        self._tiled_retained = None  # the last tiled solve made here: (its sets' offsets, whether its owner pass ran)
 
     def close(self):
         if getattr(self, "h", None):
@@ -483,6 +495,7 @@ class Engine:
         par = np.empty((rows, V), np.int32) if parent else None
         info = TrgTiledFieldInfo()
         self._chk(entry(self.h, m, _i(src), _f(val), _i(hops), None if par is None else _i(par), C.byref(info)))
+        self._tiled_retained = (np.arange(m + 1, dtype=np.int32), False)
         return {value: val, "hops": hops, "parent": par, "offset": offset, "info": info}
 
     def _tiled_fields_from(self, value, entry, who, sets, start_costs, targets, full, parent):
@@ -514,6 +527,7 @@ class Engine:
             arr(value, _f), arr("hops", _i), arr("parent", _i), arr("owner", _i),
             None if tg is None or n_t == 0 else _i(tg), n_t, arr(at, _f), arr("hops_at", _i), arr("owner_at", _i),
             _i(owned), C.byref(info)))
+        self._tiled_retained = (ptr, True)
         out["owned"] = split_owned()
         out["info"] = info
         return out
@@ -566,6 +580,7 @@ class Engine:
             int(sg.shape[0]), arr(value, _f), arr("hops", _i), arr("parent", _i), arr("owner", _i),
             None if tg is None or n_t == 0 else _i(tg), n_t, arr(at, _f), arr("hops_at", _i), arr("owner_at", _i),
             _i(owned) if owners else None, _f(out["bound"]), _i(out["reached"]), C.byref(info)))
+        self._tiled_retained = (ptr, bool(owners))
         if owners:
             out["owned"] = split_owned()
         if models is not None:
@@ -583,6 +598,67 @@ class Engine:
         if full:
             out.update({value: r[value], "hops": r["hops"], "parent": r["parent"]})
         return out
+
+    def _tiled_refresh(self, value, entry, new2old, targets, full, parent):
+        """tiled_refresh_fields and tiled_refresh_risk_fields: `value` names the objective's arrays, `entry` is its C
+        entry.  The shapes are those of the last tiled solve made through this object (its sets' offsets and whether
+        its owner pass ran); without one the entry is called without outputs and answers with its refusal."""
+        ptr, owners = self._tiled_retained or (None, False)
+        n2o = None if new2old is None else np.ascontiguousarray(new2old, dtype=np.int32).reshape(-1)
+        info = TrgTiledRefreshInfo()
+        head = (self.h, None if n2o is None else _i(n2o), 0 if n2o is None else int(n2o.shape[0]))
+        if ptr is None:
+            self._chk(entry(*head, *([None] * 4), None, 0, *([None] * 6), C.byref(info)))
+            raise TrgError(1, "tiled refresh: the engine retains a tiled solve that this object did not make")
+        m = int(ptr.shape[0]) - 1
+        offset, V = self._tiled_ids()
+        at = value + "_at"
+        out = dict(offset=offset)
+        if full:
+            out.update({value: np.empty((m, V), np.float32), "hops": np.empty((m, V), np.int32),
+                        "parent": np.empty((m, V), np.int32) if parent else None})
+            if owners:
+                out["owner"] = np.empty((m, V), np.int32)
+        tg, n_t = None, 0
+        if targets is not None and owners:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+            n_t = int(tg.shape[0])
+            out.update({at: np.empty((m, n_t), np.float32), "hops_at": np.empty((m, n_t), np.int32),
+                        "owner_at": np.empty((m, n_t), np.int32)})
+        owned, split_owned = _owned_buffer(ptr)
+        gids = np.full(max(int(ptr[-1]), 1), -1, np.int32)
+        carried = np.zeros(m, np.int32)
+        arr = lambda name, conv: None if out.get(name) is None else conv(out[name])  # noqa: E731
+        self._chk(entry(
+            *head, arr(value, _f), arr("hops", _i), arr("parent", _i), arr("owner", _i),
+            None if tg is None or n_t == 0 else _i(tg), n_t, arr(at, _f), arr("hops_at", _i), arr("owner_at", _i),
+            _i(owned) if owners else None, _i(gids), _i(carried), C.byref(info)))
+        self._tiled_retained = (ptr, owners)
+        if owners:
+            out["owned"] = split_owned()
+        out["set_gids"] = [gids[ptr[k]:ptr[k + 1]].copy() for k in range(m)]
+        out["sets"] = out["set_gids"]
+        out["carried"] = carried
+        out["info"] = info
+        return out
+
+    def tiled_refresh_fields(self, new2old=None, targets=None, full=True, parent=True):
+        """Refresh across tiles (trg_engine_tiled_cost_field_refresh; DESIGN.md section 7, "Refresh across tiles"): the
+        retained tiled cost solve brought to the current stitch.  A collective call: every rank makes it after any
+        number of them changed their tile graph and ALL stitched again, with the ranks and tiles of the solve.
+        new2old: for every node of THIS tile's graph now its LOCAL id at the retained solve, -1 for a new node; None
+        takes the engine's own map through its update_graph calls.  targets / full / parent: tiled_cost_fields_from's
+        (targets, "owner" and "owned" only where the retained solve was a set solve).  -> that call's dict, bit for bit
+        what a fresh tiled solve from "set_gids" on the current stitch returns, plus "set_gids" (per set, the members'
+        NEW global ids, the same on every rank; also under "sets"), "carried" (m: this tile's nodes that kept a key
+        through carry and anchor) and "info" (TrgTiledRefreshInfo).  Bounded, modelled and start-cost solves are not
+        refreshed."""
+        return self._tiled_refresh("cost", self.L.trg_engine_tiled_cost_field_refresh, new2old, targets, full, parent)
+
+    def tiled_refresh_risk_fields(self, new2old=None, targets=None, full=True, parent=True):
+        """tiled_refresh_fields for a retained tiled RISK solve (trg_engine_tiled_risk_field_refresh): its dict with
+        "risk" / "risk_at" where that has "cost" / "cost_at"."""
+        return self._tiled_refresh("risk", self.L.trg_engine_tiled_risk_field_refresh, new2old, targets, full, parent)
 
     def tiled_field_reached(self, field=0, cap=None):
         """THIS tile's reached nodes of field `field` of the last tiled solve (trg_engine_tiled_field_reached), compacted
