@@ -566,6 +566,61 @@ TrgStatus trg_engine_cost_field_seeded(
     const int32_t *targets, int32_t n_targets,
     float *cost_at, int32_t *hops_at, int32_t *owner_at,
     int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info);
+/* Keep-out zones ("Keep-out zones"): trg_engine_cost_field_seeded with, per field, a list of discs
+ * that the field's walks avoid -- "avoid this" said per query, the graph left as it is.  A zone is a vertical
+ * cylinder (x, y, r); a zone set is a list of 0 .. TRG_ZONES_MAX zones; field k's is zones[zone_ptr[k] ..
+ * zone_ptr[k + 1]).  For the CSR edge in row u with column v let a = min(u, v), b = max(u, v) by node id (both
+ * directions of an edge get one verdict), P = pos[a].xy, Q = pos[b].xy.  Every operation below is one fp32 operation,
+ * rounded, with no contraction:
+ *   r2 = r*r
+ *   ax = x - Px;  ay = y - Py;  da = ax*ax + ay*ay
+ *   bx = x - Qx;  by = y - Qy;  db = bx*bx + by*by
+ *   dx = Qx - Px; dy = Qy - Py; L2 = dx*dx + dy*dy
+ *   t  = ax*dx + ay*dy
+ *   cr = ax*dy - ay*dx
+ *   closes = da <= r2 || db <= r2 || (t > 0 && t < L2 && cr*cr <= r2*L2)
+ * An edge is CLOSED by a zone set iff some zone of it closes it; a node v is INSIDE iff da <= r2 with P = pos[v] for
+ * some zone, so every edge at an inside node is closed by definition.  Comparisons are taken as written: a NaN position
+ * closes nothing.
+ * Field k under models[k] and zone set k is, bit for bit, the field trg_engine_cost_field_seeded computes under
+ * models[k] on the graph without the closed edges, CSR order otherwise kept: cost bits, hops, parents, owners, owned,
+ * the target reads, the bounds, reached_out, the saturation rule, the truncation and the start costs.  Set members
+ * are exempt as they are from the Invalid rule: a member inside a zone keeps its key and reaches nothing; a target
+ * inside a zone is unreached.  The bucket width's edge statistics are over admitted, unclosed edges; the bad-cost flag
+ * is over all edges.  zone_ptr == NULL, or an empty set for a field, is trg_engine_cost_field_seeded on every output
+ * bit; a single source is a set of one.
+ * The solve is retained with its zone sets: trg_engine_field_routes (a route edge is the admitted, unclosed, tight
+ * edge of least CSR index) and trg_engine_field_reached answer from it, and trg_engine_cost_field_refresh derives the
+ * closures again on the updated graph and its positions -- bit for bit the fresh zone solve there; bounded and
+ * start-cost solves stay refused by it.  Edge costs are cached per distinct (model, zone list as bytes) and graph.
+ * TRG_ERR_INVALID_ARG, naming field and zone, for a zone whose x or y is NaN or infinite or whose r is NaN, negative
+ * or infinite (r == 0 is a point and accepted), for more than TRG_ZONES_MAX zones in a field, and for a zone_ptr
+ * that does not start at 0 or descends; everything else as trg_engine_cost_field_seeded. */
+#define TRG_ZONES_MAX 256
+typedef struct TrgZone {
+  float x, y;  /* the centre, finite */
+  float r;     /* the radius: finite, >= 0 */
+} TrgZone;
+TrgStatus trg_engine_cost_field_zones(
+    TrgEngine *e, int32_t m,
+    const TrgFieldModel *models,
+    const int32_t *zone_ptr,     /* m + 1 offsets into zones, or NULL: no zones */
+    const TrgZone *zones,        /* zone_ptr[m] */
+    const int32_t *set_ptr, const int32_t *set_ids,
+    const float *set_cost0,
+    const float *budget, int32_t settle,
+    float *cost, int32_t *hops, int32_t *parent, int32_t *owner,
+    const int32_t *targets, int32_t n_targets,
+    float *cost_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info);
+/* What a zone set shuts on the current global graph, by the device function the solve uses: closed[e] = 1 iff the
+ * zone set closes CSR edge e (else 0; an edge whose column is no node is never closed), inside[v] = 1 iff node v is
+ * inside.  closed (num_edges bytes) and inside (num_nodes bytes) may each be NULL; *n_closed and *n_inside (may be
+ * NULL) always get the counts.  n_zones == 0 closes nothing.  The retained solve is left as it is.
+ * TRG_ERR_INVALID_ARG for n_zones outside 0 .. TRG_ZONES_MAX, a null zones with n_zones > 0 and a bad zone (as
+ * above, as field 0); TRG_ERR_NO_GRAPH without a graph; TRG_ERR_CAPACITY when device memory runs out. */
+TrgStatus trg_engine_zone_edges(TrgEngine *e, const TrgZone *zones, int32_t n_zones,
+    uint8_t *closed, uint8_t *inside, int32_t *n_closed, int32_t *n_inside);
 /* Risk fields ("Risk fields"): for every node, how risky is the worst edge that must be crossed
  * to get there -- trg_engine_cost_field_sets with max in the place of +, exact, for every node in one solve.
  * An edge of CSR index e is relaxable exactly as in a cost field (its col a node, and not Invalid); its risk is

@@ -42,6 +42,7 @@
 #include "map_order_sim.h"
 #include "node_map.h"
 #include "trg_kernels.h"
+#include "zone_sets.h"
 
 namespace {
 

@@ -39,6 +39,9 @@ struct FieldBufs {
     long long count;
     bool bad;                    // some edge cost is negative or not finite
     uint64_t used;               // ec_tick of the last solve that read it
+    // the keep-out zones of the slot ("Keep-out zones"), part of its identity, compared as bytes;
+    // empty: a slot of the model alone (slot 0 and the risk slot always are)
+    std::vector<TrgZone> zones;
   };
   std::vector<CostSlot> slots;
   size_t ec_stride = 0;      // entries from one slot to the next
@@ -66,10 +69,14 @@ struct FieldBufs {
     std::vector<TrgFieldModel> pairs;
     FieldModels models{};
     bool many = false;
+    ZoneSets zones;  // its keep-out zone lists ("Keep-out zones"); empty(): it had none
     // (F.V and F.m are the node count of its graph and its fields: what a refresh reads the old keys by)
   } last;
   DevArr set_ptr, set_ids, owner, owner_at, owned, own_changed;  // set solves; owner: m x V, only when asked for
   DevArr set_cost0;          // ... with start costs: one cost word per entry
+  // keep-out zones: the lists of the slots being computed (FIELD_ZONES_MAX zones a slot, in the order of `fresh`), and
+  // the verdicts and counts of trg_engine_zone_edges
+  DevArr zones, zone_closed, zone_inside, zone_counts;
   std::vector<int32_t> h_set_ptr, h_set_ids;  // the sets as uploaded, for a refresh to carry to the next graph
   DevArr key0, node_map, carried;  // refresh: the carried, then the anchored keys (m x V); new2old (V); counts (m)
   Pinned<int> h_carried;     // per field
@@ -93,6 +100,9 @@ void field_release(TrgEngine *e) {
 }
 
 static_assert(FIELD_MAX_SOURCES == TRG_FIELD_BATCH_MAX, "the kernels' and the header's batch limit differ");
+static_assert(FIELD_ZONES_MAX == TRG_ZONES_MAX && sizeof(FieldZone) == sizeof(TrgZone) &&
+                  offsetof(FieldZone, r) == offsetof(TrgZone, r),
+              "the kernels' and the header's zones differ");
 // the engine's own slot and one per field of the largest batch
 constexpr int FIELD_SLOTS_MAX = FIELD_MAX_SOURCES + 1;
 // The key of the slot that holds the edge risks ("Risk fields"): a NaN pattern in both words,
@@ -125,6 +135,10 @@ struct FieldRequest {
   int32_t *owned;     // set_ptr[m]
   // a cost model per field (trg_engine_cost_field_models), or nullptr: the engine's for every field
   const TrgFieldModel *models;  // m
+  // a keep-out zone list per field (trg_engine_cost_field_zones): field k's is zones[zone_ptr[k] .. zone_ptr[k + 1]),
+  // or nullptr: none
+  const int32_t *zone_ptr;  // m + 1
+  const TrgZone *zones;
   // a refresh (trg_engine_cost_field_refresh): m and the sources or sets are the retained solve's, filled in by
   // field_check_refresh, and its keys are carried through new2old instead of a cold start
   bool refresh;
@@ -165,6 +179,7 @@ struct FieldRun {
   FieldDev old{};
   std::vector<int32_t> identity, src, set_ptr, set_ids;
   std::vector<TrgFieldModel> pairs;  // ... and its models
+  ZoneSets zones;                    // ... and its keep-out zone lists
   std::vector<uint32_t> cost0;       // a seeded solve: the start costs as cost bits (-0 as +0), per entry
   // the edge costs of this solve (field_edge_costs): the slot table, whether the fields read more than one slot
   // (else F.ec is the one they share and no kernel takes the table), and the mean over its distinct slots
@@ -274,6 +289,11 @@ TrgStatus field_check_refresh(TrgEngine *e, FieldRun &run) {
   if (!old.pairs.empty()) {  // the retained models, whose costs field_edge_costs derives again on this graph
     run.pairs = old.pairs;
     rq.models = run.pairs.data();
+  }
+  if (!old.zones.empty()) {  // ... and the retained zone lists, whose closures it derives again from this graph's positions
+    run.zones = old.zones;
+    rq.zone_ptr = run.zones.ptr.data();
+    rq.zones = run.zones.zones.data();
   }
   return TRG_OK;
 }
@@ -409,9 +429,14 @@ TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
     uint32_t sfb = run.rq.models ? float_bits(run.rq.models[k].safety_factor) : sf0;
     uint32_t taub = run.rq.models ? float_bits(run.rq.models[k].max_weight) : FIELD_INF_BITS;
     if (run.rq.risk) sfb = taub = FIELD_RISK_SLOT;  // (every field of a risk solve reads the edge risks)
+    // (a risk solve has no zone lists: the zone entry is a cost entry)
+    const TrgZone *zk = run.rq.zone_ptr ? run.rq.zones + run.rq.zone_ptr[k] : nullptr;
+    const size_t nzk = run.rq.zone_ptr ? (size_t)(run.rq.zone_ptr[k + 1] - run.rq.zone_ptr[k]) : 0;
     int slot = -1;
     for (size_t i = 0; i < fb.slots.size() && slot < 0; ++i)
-      if (fb.slots[i].sf_bits == sfb && fb.slots[i].tau_bits == taub) slot = (int)i;
+      if (fb.slots[i].sf_bits == sfb && fb.slots[i].tau_bits == taub &&
+          zone_list_equal(fb.slots[i].zones.data(), fb.slots[i].zones.size(), zk, nzk))
+        slot = (int)i;
     if (slot < 0) {
       if ((int)fb.slots.size() < FIELD_SLOTS_MAX) {
         slot = (int)fb.slots.size();
@@ -423,6 +448,7 @@ TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
       if (slot < 0)
         return e->fail(TRG_ERR_CAPACITY, "cost field: no cache slot left for the model of field " + std::to_string(k));
       fb.slots[slot] = FieldBufs::CostSlot{sfb, taub, false, 0.0, 0, false, tick};
+      if (nzk) fb.slots[slot].zones.assign(zk, zk + nzk);
     }
     FieldBufs::CostSlot &cs = fb.slots[slot];
     if (!cs.valid && std::find(fresh.begin(), fresh.end(), slot) == fresh.end()) fresh.push_back(slot);
@@ -440,12 +466,22 @@ TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
   }
   if (!fresh.empty()) {
     FieldEdgeStats *d_stats = fb.stats.as<FieldEdgeStats>();
+    bool zoned = false;
+    for (const int i : fresh) zoned = zoned || !fb.slots[i].zones.empty();
+    if (zoned)  // (the lists stay in place until this phase's host wait)
+      if (const TrgStatus st = field_grow(e, fb.zones, fresh.size() * FIELD_ZONES_MAX * sizeof(FieldZone)); st != TRG_OK)
+        return st;
     for (size_t j = 0; j < fresh.size(); ++j) {
       const FieldBufs::CostSlot &cs = fb.slots[fresh[j]];
       float *slot = fb.ec.as<float>() + (size_t)fresh[j] * stride;
-      if (cs.sf_bits == FIELD_RISK_SLOT && cs.tau_bits == FIELD_RISK_SLOT)
+      if (cs.sf_bits == FIELD_RISK_SLOT && cs.tau_bits == FIELD_RISK_SLOT) {
         launch_field_edge_risk(G.col, G.w, G.state, run.F.V, G.E, slot, d_stats + j, s);
-      else
+      } else if (!cs.zones.empty()) {
+        FieldZone *d_zones = fb.zones.as<FieldZone>() + j * FIELD_ZONES_MAX;
+        HIPCHK(e, hipMemcpyAsync(d_zones, cs.zones.data(), cs.zones.size() * sizeof(FieldZone), hipMemcpyHostToDevice, s));
+        launch_field_edge_zones(G.rowptr, G.col, G.w, G.dist, G.state, G.xyz, run.F.V, G.E, bits_float(cs.sf_bits),
+                                bits_float(cs.tau_bits), d_zones, (int)cs.zones.size(), slot, d_stats + j, s);
+      } else
         launch_field_edge_cost(G.col, G.w, G.dist, G.state, run.F.V, G.E, bits_float(cs.sf_bits),
                                bits_float(cs.tau_bits), slot, d_stats + j, s);
     }
@@ -770,6 +806,7 @@ TrgStatus field_outputs(TrgEngine *e, FieldRun &run) {
   if (rq.models) fb.last.pairs.assign(rq.models, rq.models + m);
   fb.last.models = run.models;
   fb.last.many = run.many_models;
+  if (rq.zone_ptr) fb.last.zones.assign(m, rq.zone_ptr, rq.zones);
   e->field_map.state = NodeMap::IDENTITY;  // update_graph takes the node map on from here
   return field_timing(e, run.info, run.syncs, run.t_total);
 }
@@ -1053,17 +1090,25 @@ TrgStatus cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *source_ids,
   return field_solve(e, rq, out);
 }
 
-// ... and the one behind trg_engine_cost_field_seeded, without start costs trg_engine_cost_field_models and, without
-// models either, trg_engine_cost_field_sets
+// the zone-list checks of trg_engine_cost_field_zones (zone_sets.h); a null zone_ptr: no lists
+TrgStatus field_check_zones(TrgEngine *e, int32_t m, const int32_t *zone_ptr, const TrgZone *zones) {
+  std::string why;
+  if (zone_ptr && !zone_sets_check(m, zone_ptr, zones, why)) return e->fail(TRG_ERR_INVALID_ARG, "cost field zones: " + why);
+  return TRG_OK;
+}
+
+// ... and the one behind trg_engine_cost_field_zones, without zone lists trg_engine_cost_field_seeded, without start
+// costs either trg_engine_cost_field_models and, without models, trg_engine_cost_field_sets
 TrgStatus cost_field_models(TrgEngine *e, int32_t m, const TrgFieldModel *models, const int32_t *set_ptr,
                             const int32_t *set_ids, const float *set_cost0, const float *budget, int32_t settle, float *cost, int32_t *hops,
                             int32_t *parent, int32_t *owner, const int32_t *targets, int32_t n_targets, float *cost_at,
                             int32_t *hops_at, int32_t *owner_at, int32_t *owned, int32_t *reached_out, float *bound_out,
-                            TrgFieldInfo *out) {
+                            TrgFieldInfo *out, const int32_t *zone_ptr = nullptr, const TrgZone *zones = nullptr) {
   const char *no_sets = !set_ptr || !set_ids ? "null set_ptr or set_ids" : nullptr;
   if (const TrgStatus st = field_check_shape(e, "cost field sets", "sets", m, n_targets, no_sets); st != TRG_OK)
     return st;
   if (const TrgStatus st = field_check_models(e, m, models); st != TRG_OK) return st;
+  if (const TrgStatus st = field_check_zones(e, m, zone_ptr, zones); st != TRG_OK) return st;
   if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
   FieldRequest rq = field_request(m, cost, hops, parent, targets, n_targets, cost_at, hops_at, reached_out);
   rq.budget = budget;
@@ -1076,7 +1121,46 @@ TrgStatus cost_field_models(TrgEngine *e, int32_t m, const TrgFieldModel *models
   rq.owner_at = owner_at;
   rq.owned = owned;
   rq.models = models;
+  rq.zone_ptr = zone_ptr;
+  rq.zones = zones;
   return field_solve(e, rq, out);
+}
+
+// The verdicts of a zone set on the current global graph (trg_engine_zone_edges), by the kernels' own rule; the
+// retained solve and the edge-cost cache are left alone.
+TrgStatus zone_edges(TrgEngine *e, const TrgZone *zones, int32_t n_zones, uint8_t *closed, uint8_t *inside,
+                     int32_t *n_closed, int32_t *n_inside) {
+  if (n_zones < 0 || n_zones > TRG_ZONES_MAX)
+    return e->fail(TRG_ERR_INVALID_ARG, "zone edges: " + std::to_string(n_zones) + " zones (0.." +
+                                            std::to_string(TRG_ZONES_MAX) + ")");
+  const int32_t ptr[2] = {0, n_zones};
+  std::string why;
+  if (!zone_sets_check(1, ptr, zones, why)) return e->fail(TRG_ERR_INVALID_ARG, "zone edges: " + why);
+  TrgStatus st = plan_prepare(e);  // graph present, CSR rows current
+  if (st != TRG_OK) return st;
+  DevGraph G;
+  if ((st = ensure_dev_graph(e, DEV_NODES | DEV_EDGES, &G)) != TRG_OK) return st;
+  if (!e->field) e->field.reset(new FieldBufs());
+  FieldBufs &fb = *e->field;
+  hipStream_t s = e->s_main;
+  if ((st = field_grow(e, fb.zones, (size_t)FIELD_ZONES_MAX * sizeof(FieldZone))) != TRG_OK) return st;
+  if ((st = field_grow(e, fb.zone_counts, 2 * sizeof(int))) != TRG_OK) return st;
+  if (closed && (st = field_grow(e, fb.zone_closed, (size_t)G.E + 4)) != TRG_OK) return st;
+  if (inside && (st = field_grow(e, fb.zone_inside, (size_t)G.V + 4)) != TRG_OK) return st;
+  if (n_zones > 0)
+    HIPCHK(e, hipMemcpyAsync(fb.zones.p, zones, (size_t)n_zones * sizeof(FieldZone), hipMemcpyHostToDevice, s));
+  launch_field_zone_verdicts(G.rowptr, G.col, G.xyz, G.V, G.E, fb.zones.as<FieldZone>(), n_zones,
+                             closed ? fb.zone_closed.as<unsigned char>() : nullptr,
+                             inside ? fb.zone_inside.as<unsigned char>() : nullptr, fb.zone_counts.as<int>(), s);
+  HIPCHK(e, hipGetLastError());
+  int counts[2] = {0, 0};
+  HIPCHK(e, hipMemcpyAsync(counts, fb.zone_counts.p, sizeof counts, hipMemcpyDeviceToHost, s));
+  if (closed && G.E > 0) HIPCHK(e, hipMemcpyAsync(closed, fb.zone_closed.p, (size_t)G.E, hipMemcpyDeviceToHost, s));
+  if (inside && G.V > 0) HIPCHK(e, hipMemcpyAsync(inside, fb.zone_inside.p, (size_t)G.V, hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  if (n_closed) *n_closed = counts[0];
+  if (n_inside) *n_inside = counts[1];
+  return TRG_OK;
 }
 
 }  // namespace
@@ -1151,6 +1235,25 @@ TrgStatus trg_engine_cost_field_seeded(TrgEngine *e, int32_t m, const TrgFieldMo
     return cost_field_models(e, m, models, set_ptr, set_ids, set_cost0, budget, settle, cost, hops, parent, owner,
                              targets, n_targets, cost_at, hops_at, owner_at, owned, reached_out, bound_out, out);
   });
+}
+
+TrgStatus trg_engine_cost_field_zones(TrgEngine *e, int32_t m, const TrgFieldModel *models, const int32_t *zone_ptr,
+                                      const TrgZone *zones, const int32_t *set_ptr, const int32_t *set_ids,
+                                      const float *set_cost0, const float *budget, int32_t settle, float *cost,
+                                      int32_t *hops, int32_t *parent, int32_t *owner, const int32_t *targets,
+                                      int32_t n_targets, float *cost_at, int32_t *hops_at, int32_t *owner_at,
+                                      int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info) {
+  return field_entry(e, info, "cost field zones", [&](TrgFieldInfo *out) {
+    return cost_field_models(e, m, models, set_ptr, set_ids, set_cost0, budget, settle, cost, hops, parent, owner,
+                             targets, n_targets, cost_at, hops_at, owner_at, owned, reached_out, bound_out, out,
+                             zone_ptr, zones);
+  });
+}
+
+TrgStatus trg_engine_zone_edges(TrgEngine *e, const TrgZone *zones, int32_t n_zones, uint8_t *closed, uint8_t *inside,
+                                int32_t *n_closed, int32_t *n_inside) {
+  return entry(e, "zone edges", DEVICE,
+               [&] { return zone_edges(e, zones, n_zones, closed, inside, n_closed, n_inside); });
 }
 
 TrgStatus trg_engine_risk_field_sets(TrgEngine *e, int32_t m, const int32_t *set_ptr, const int32_t *set_ids,

@@ -64,6 +64,10 @@
 // have a MODELS instantiation that takes the slot from the item's field, one table read per queued item or route.
 // A solve whose fields share one model runs the plain instantiations on that slot.
 //
+// Keep-out zones ("Keep-out zones"): a field may also refuse edges by place -- every edge that a
+// disc of its zone set touches.  That is one more reason for the skip marker in a slot, decided by k_field_edge_zones
+// (near the end of this file) where k_field_edge_cost decides by weight; every kernel that reads a slot is unchanged.
+//
 // Risk fields ("Risk fields"): the least, over all walks, of the GREATEST edge weight on the walk.
 // The extension is (max(risk, r), hops + 1) with r = w + 0 -- monotone in the risk word and never below it, which is
 // all the argument above asks of fl(a + c), and it never rounds.  The hop word is no more monotone than under
@@ -992,6 +996,150 @@ void field_round(const FieldDev &F, int round, const FieldSettle *settle, const 
   hipLaunchKernelGGL(k_field_round_end<BOUNDED>, dim3(1), dim3(64), 0, s, F, par);
 }
 
+// ---- keep-out zones ("Keep-out zones") ------------------------------------------------------------
+// A zone set closes edges by geometry: k_field_edge_zones fills a slot of the edge-cost array with what
+// k_field_edge_cost writes, or the skip marker where the set closes the edge, so every kernel above runs unchanged on
+// such a slot.  The verdict needs the positions of BOTH ends, hence the row of an edge: one 16-lane group per row, as the
+// relaxation has it (no search in rowptr; the row's position is one load for the group, and consecutive groups read
+// consecutive stretches of col / w / dist / ec).  The zone set is staged in LDS once per workgroup as (x, y, r*r).
+
+// The rule, restated line for line from DESIGN.md: does the zone (x, y, r2 = r*r) close the edge between P and Q, P the
+// position of the end with the smaller node id.  Every operation is one fp32 operation (-ffp-contract=off); the
+// comparisons are taken as written, so a NaN position closes nothing.
+__device__ __forceinline__ bool zone_closes(float x, float y, float r2, float Px, float Py, float Qx, float Qy) {
+  const float ax = x - Px;
+  const float ay = y - Py;
+  const float da = ax * ax + ay * ay;
+  const float bx = x - Qx;
+  const float by = y - Qy;
+  const float db = bx * bx + by * by;
+  const float dx = Qx - Px;
+  const float dy = Qy - Py;
+  const float L2 = dx * dx + dy * dy;
+  const float t = ax * dx + ay * dy;
+  const float cr = ax * dy - ay * dx;
+  return da <= r2 || db <= r2 || (t > 0.0f && t < L2 && cr * cr <= r2 * L2);
+}
+
+// is the node at P inside the zone: the rule's da <= r2
+__device__ __forceinline__ bool zone_holds(float x, float y, float r2, float Px, float Py) {
+  const float ax = x - Px;
+  const float ay = y - Py;
+  const float da = ax * ax + ay * ay;
+  return da <= r2;
+}
+
+// the zone set into LDS, (x, y, r*r, unused) per zone; every thread of the workgroup calls it -> the zones staged
+__device__ __forceinline__ int zones_stage(float4 *zs, const FieldZone *__restrict__ zones, int nz) {
+  nz = min(max(nz, 0), FIELD_ZONES_MAX);
+  for (int i = threadIdx.x; i < nz; i += blockDim.x) {
+    const FieldZone z = zones[i];
+    zs[i] = make_float4(z.x, z.y, z.r * z.r, 0.0f);
+  }
+  __syncthreads();
+  return nz;
+}
+
+// does some staged zone close the edge between nodes u and v (both in [0, V)); P is the end of the smaller id
+__device__ __forceinline__ bool zones_close_edge(const float4 *zs, int nz, const float *__restrict__ xyz, int u, int v) {
+  const int a = min(u, v), b = max(u, v);
+  const float Px = xyz[3 * (size_t)a], Py = xyz[3 * (size_t)a + 1];
+  const float Qx = xyz[3 * (size_t)b], Qy = xyz[3 * (size_t)b + 1];
+  bool closed = false;
+  for (int i = 0; i < nz && !closed; ++i) {
+    const float4 z = zs[i];
+    closed = zone_closes(z.x, z.y, z.z, Px, Py, Qx, Qy);
+  }
+  return closed;
+}
+
+// the rows of the 16-lane group this thread belongs to: u = first, first + step, ... below V
+__device__ __forceinline__ void zone_group_rows(int &first, int &step, int &lane) {
+  first = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
+  step = gridDim.x * blockDim.x / GROUP;
+  lane = threadIdx.x & (GROUP - 1);
+}
+
+__global__ __launch_bounds__(THREADS) void k_field_edge_zones(
+    const int *__restrict__ rowptr, const int *__restrict__ col, const float *__restrict__ w,
+    const float *__restrict__ dist, const int *__restrict__ state, const float *__restrict__ xyz, int V, int E, float sf,
+    float tau, const FieldZone *__restrict__ zones, int nz, float *__restrict__ ec, FieldEdgeStats *st) {
+  __shared__ float4 zs[FIELD_ZONES_MAX];
+  nz = zones_stage(zs, zones, nz);
+  double sum = 0.0;
+  int cnt = 0, bad = 0;
+  int first, step, lane;
+  zone_group_rows(first, step, lane);
+  for (int u = first; u < V; u += step) {
+    const int beg = max(rowptr[u], 0), end = min(rowptr[u + 1], E);
+    for (int k = beg + lane; k < end; k += GROUP) {
+      const float c = (sf * w[k] + 1.0f) * dist[k];
+      if (!(c >= 0.0f) || c == __builtin_huge_valf()) bad = 1;
+      const int v = col[k];
+      bool skip = v < 0 || v >= V;
+      if (!skip) skip = state[v] == FIELD_NODE_INVALID;
+      skip = skip || w[k] > tau;  // (the ceiling; +inf: no weight is above it)
+      if (!skip) skip = zones_close_edge(zs, nz, xyz, u, v);
+      ec[k] = skip ? __uint_as_float(FIELD_EDGE_SKIP) : c;
+      if (!skip) {
+        sum += (double)c;
+        cnt++;
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    sum += __shfl_xor(sum, m);
+    cnt += __shfl_xor(cnt, m);
+    bad |= __shfl_xor(bad, m);
+  }
+  if (lane_id() == 0) {
+    if (cnt) {
+      atomicAdd(&st->sum, sum);
+      atomicAdd(&st->count, cnt);
+    }
+    if (bad) atomicOr(&st->bad, 1);
+  }
+}
+
+// The verdicts of a zone set by the device function of the solve: closed per CSR edge, inside per node (either may be
+// nullptr), and their counts.  An edge whose column is no node is not closed.
+__global__ __launch_bounds__(THREADS) void k_field_zone_verdicts(
+    const int *__restrict__ rowptr, const int *__restrict__ col, const float *__restrict__ xyz, int V, int E,
+    const FieldZone *__restrict__ zones, int nz, unsigned char *__restrict__ closed, unsigned char *__restrict__ inside,
+    int *counts) {
+  __shared__ float4 zs[FIELD_ZONES_MAX];
+  nz = zones_stage(zs, zones, nz);
+  int n_closed = 0, n_inside = 0;
+  int first, step, lane;
+  zone_group_rows(first, step, lane);
+  for (int u = first; u < V; u += step) {
+    if (lane == 0) {
+      const float Px = xyz[3 * (size_t)u], Py = xyz[3 * (size_t)u + 1];
+      bool in = false;
+      for (int i = 0; i < nz && !in; ++i) in = zone_holds(zs[i].x, zs[i].y, zs[i].z, Px, Py);
+      if (inside) inside[u] = in ? 1 : 0;
+      n_inside += in ? 1 : 0;
+    }
+    const int beg = max(rowptr[u], 0), end = min(rowptr[u + 1], E);
+    for (int k = beg + lane; k < end; k += GROUP) {
+      const int v = col[k];
+      const bool shut = v >= 0 && v < V && zones_close_edge(zs, nz, xyz, u, v);
+      if (closed) closed[k] = shut ? 1 : 0;
+      n_closed += shut ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    n_closed += __shfl_xor(n_closed, m);
+    n_inside += __shfl_xor(n_inside, m);
+  }
+  if (lane_id() == 0) {
+    if (n_closed) atomicAdd(&counts[0], n_closed);
+    if (n_inside) atomicAdd(&counts[1], n_inside);
+  }
+}
+
 }  // namespace
 
 void launch_field_edge_cost(const int *col, const float *w, const float *dist, const int *state, int V, int E,
@@ -1008,6 +1156,24 @@ void launch_field_edge_risk(const int *col, const float *w, const int *state, in
   if (E == 0) return;
   hipLaunchKernelGGL(k_field_edge_risk, dim3(field_blocks(E, THREADS * 8)), dim3(THREADS), 0, s, col, w, state, V, E,
                      er, st);
+}
+
+void launch_field_edge_zones(const int *rowptr, const int *col, const float *w, const float *dist, const int *state,
+                             const float *xyz, int V, int E, float safety_factor, float max_weight,
+                             const FieldZone *zones, int nz, float *ec, FieldEdgeStats *st, hipStream_t s) {
+  (void)hipMemsetAsync(st, 0, sizeof(FieldEdgeStats), s);
+  if (E == 0) return;
+  hipLaunchKernelGGL(k_field_edge_zones, dim3(field_blocks((long long)V * GROUP, THREADS)), dim3(THREADS), 0, s, rowptr,
+                     col, w, dist, state, xyz, V, E, safety_factor, max_weight, zones, nz, ec, st);
+}
+
+void launch_field_zone_verdicts(const int *rowptr, const int *col, const float *xyz, int V, int E,
+                                const FieldZone *zones, int nz, unsigned char *closed, unsigned char *inside,
+                                int *counts, hipStream_t s) {
+  (void)hipMemsetAsync(counts, 0, 2 * sizeof(int), s);
+  if (V == 0) return;
+  hipLaunchKernelGGL(k_field_zone_verdicts, dim3(field_blocks((long long)V * GROUP, THREADS)), dim3(THREADS), 0, s,
+                     rowptr, col, xyz, V, E, zones, nz, closed, inside, counts);
 }
 
 void launch_field_init(const FieldDev &F, const FieldSources &sources, const FieldSets *sets, const unsigned *cost0,

@@ -510,6 +510,24 @@ void launch_field_edge_cost(const int *col, const float *w, const float *dist, c
 // infinite).  `er` is a slot of the edge-cost array: a risk solve's F.ec points at it.
 void launch_field_edge_risk(const int *col, const float *w, const int *state, int V, int E, float *er,
                             FieldEdgeStats *st, hipStream_t s);
+// Keep-out zones ("Keep-out zones"): a disc that closes every edge it touches; the layout of the
+// header's TrgZone.  A zone set is at most FIELD_ZONES_MAX of them.
+struct FieldZone {
+  float x, y, r;
+};
+constexpr int FIELD_ZONES_MAX = 256;  // TRG_ZONES_MAX
+// launch_field_edge_cost for a slot with a zone set: ec[e] is what that launch writes, or FIELD_EDGE_SKIP where the set
+// (nz zones on the device, 1 .. FIELD_ZONES_MAX) closes edge e by the rule of DESIGN.md; *st (zeroed here) over the
+// edges that got a cost, its bad flag over all.  xyz: the node positions, 3 floats a node; one 16-lane group per row.
+void launch_field_edge_zones(const int *rowptr, const int *col, const float *w, const float *dist, const int *state,
+                             const float *xyz, int V, int E, float safety_factor, float max_weight,
+                             const FieldZone *zones, int nz, float *ec, FieldEdgeStats *st, hipStream_t s);
+// The verdicts themselves, by the same device function: closed[e] (E bytes, may be nullptr) 1 where the set closes edge
+// e, inside[v] (V bytes, may be nullptr) 1 where node v is inside a zone; counts[0] / counts[1] (zeroed here) the
+// closed edges and the inside nodes.  nz == 0: nothing is closed.
+void launch_field_zone_verdicts(const int *rowptr, const int *col, const float *xyz, int V, int E,
+                                const FieldZone *zones, int nz, unsigned char *closed, unsigned char *inside,
+                                int *counts, hipStream_t s);
 // Field k starts at node sources.id[k], k < F.m (duplicates give identical fields).  With `sets` (a set solve; else
 // nullptr) sources is not read: every item is left without a key, then a second launch seeds every distinct member
 // item and pushes it once to near queue 0; F.ctrl's queue size and work are the count of distinct member items.

@@ -99,6 +99,10 @@ class TrgFieldModel(C.Structure):
     _fields_ = [("safety_factor", C.c_float), ("max_weight", C.c_float)]
 
 
+class TrgZone(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("r", C.c_float)]
+
+
 class TrgPoseInfo(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_candidates", C.c_int32), ("n_links", C.c_int32), ("z", C.c_float)]
 
@@ -147,6 +151,7 @@ EXPORTS = [
     "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh", "trg_engine_cost_field_models",
     "trg_engine_risk_field_sets", "trg_engine_risk_field_refresh",
     "trg_engine_pose_links", "trg_engine_cost_field_seeded",
+    "trg_engine_cost_field_zones", "trg_engine_zone_edges",
     "trg_engine_tiled_cost_field", "trg_engine_stitch_ids", "trg_engine_tiled_cost_field_sets",
     "trg_engine_tiled_field_routes", "trg_engine_tiled_risk_field", "trg_engine_tiled_risk_field_sets",
     "trg_engine_tiled_cost_field_bounded", "trg_engine_tiled_risk_field_bounded", "trg_engine_tiled_field_reached",
@@ -154,6 +159,7 @@ EXPORTS = [
 ]
 
 TRG_FIELD_BATCH_MAX = 64  # include/trg_engine.h: fields of one trg_engine_cost_field_batch call
+TRG_ZONES_MAX = 256       # include/trg_engine.h: zones of one field of trg_engine_cost_field_zones
 # include/trg_engine.h: TRG_FIELD_SETTLE_*
 SETTLE_NONE, SETTLE_ANY, SETTLE_ALL = 0, 1, 2
 _SETTLE = {None: SETTLE_NONE, "any": SETTLE_ANY, "all": SETTLE_ALL}
@@ -252,6 +258,9 @@ def load_library():
     L.trg_engine_cost_field_seeded.argtypes = [vp, C.c_int32, C.POINTER(TrgFieldModel), ip, ip, fp, fp, C.c_int32, fp,
                                                ip, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, fp,
                                                C.POINTER(TrgFieldInfo)]
+    L.trg_engine_cost_field_zones.argtypes = [vp, C.c_int32, C.POINTER(TrgFieldModel), ip, C.POINTER(TrgZone)] + \
+        L.trg_engine_cost_field_seeded.argtypes[3:]
+    L.trg_engine_zone_edges.argtypes = [vp, C.POINTER(TrgZone), C.c_int32, u8p, u8p, ip, ip]
     L.trg_engine_pose_links.argtypes = [vp, fp, C.c_int32, C.c_float, C.c_int32, ip, fp, fp, C.POINTER(TrgPoseInfo)]
     L.trg_engine_risk_field_sets.argtypes = L.trg_engine_cost_field_sets.argtypes
     L.trg_engine_cost_field_refresh.argtypes = [vp, ip, C.c_int32, fp, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, ip, ip,
@@ -1275,7 +1284,95 @@ class Engine:
         "start_costs" (the m float32 arrays as solved) and, with `models`, "models"."""
         return self._cost_fields_from(sets, models, targets, full, budget, settle, start_costs=start_costs)
 
-    def _cost_fields_from(self, sets, models, targets, full, budget, settle, start_costs=None):
+    @staticmethod
+    def _zone_array(who, zones):
+        """One zone set -- None, or anything that reads as (Z, 3) float32 rows (x, y, r) -- as a contiguous (Z, 3)
+        float32 array."""
+        if zones is None:
+            return np.empty((0, 3), np.float32)
+        a = np.ascontiguousarray(zones, dtype=np.float32)
+        if a.size == 0:
+            return np.empty((0, 3), np.float32)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{who}: a zone set is a (Z, 3) array of (x, y, r), not of shape {a.shape}")
+        return a
+
+    def _zone_sets(self, who, zone_sets, m):
+        """`zone_sets` of cost_fields_avoiding -- one (Z, 3) array for all m fields, or a list with one per field (None
+        or (0, 3): no zones) -> (the m float32 (Z_k, 3) arrays, ptr int32 (m + 1), their concatenation (n, 3))."""
+        per_field = isinstance(zone_sets, (list, tuple)) and len(zone_sets) > 0 and \
+            any(z is None or np.ndim(z) == 2 for z in zone_sets)
+        if per_field:
+            if len(zone_sets) != m:
+                raise ValueError(f"{who}: {len(zone_sets)} zone sets for {m} fields")
+            each = [self._zone_array(who, z) for z in zone_sets]
+        else:
+            each = [self._zone_array(who, zone_sets)] * m
+        ptr = np.zeros(m + 1, np.int32)
+        np.cumsum([z.shape[0] for z in each], out=ptr[1:])
+        flat = np.ascontiguousarray(np.concatenate(each) if m else np.empty((0, 3), np.float32), dtype=np.float32)
+        return each, ptr, flat
+
+    def closed_edges(self, zones):
+        """What a keep-out zone set shuts on the current global graph (trg_engine_zone_edges; DESIGN.md section 2,
+        "Keep-out zones"), by the device function the solves use.  `zones`: (Z, 3) rows (x, y, r), Z <= 256; None or
+        (0, 3): no zones.  -> dict: "closed" (E,) uint8 per CSR edge, "inside" (V,) uint8 per node, "n_closed",
+        "n_inside"."""
+        z = self._zone_array("closed_edges", zones)
+        V, E = self.graph_sizes("global")
+        closed = np.zeros(max(E, 1), np.uint8)
+        inside = np.zeros(max(V, 1), np.uint8)
+        nc, ni = C.c_int32(0), C.c_int32(0)
+        u8 = C.POINTER(C.c_uint8)
+        self._chk(self.L.trg_engine_zone_edges(self.h, z.ctypes.data_as(C.POINTER(TrgZone)), z.shape[0],
+                                               closed.ctypes.data_as(u8), inside.ctypes.data_as(u8), C.byref(nc),
+                                               C.byref(ni)))
+        return {"closed": closed[:E], "inside": inside[:V], "n_closed": int(nc.value), "n_inside": int(ni.value)}
+
+    def cost_fields_avoiding(self, sets_or_sources, zone_sets, models=None, start_costs=None, targets=None, full=True,
+                             budget=None, settle=None):
+        """Cost fields that avoid keep-out zones (trg_engine_cost_field_zones; DESIGN.md section 2, "Keep-out zones"):
+        cost_fields_seeded on the graph without the edges that field k's zone set closes -- an edge is closed when a
+        disc (x, y, r) of the set touches it, so no walk enters or crosses a zone; the graph itself is left as it is.
+        `sets_or_sources`: m sets of node ids, or a flat list of node ids -- m sets of one.  `zone_sets`: one (Z, 3)
+        array of (x, y, r) rows for all fields, or a list with one per field; None or (0, 3) means no zones, Z <= 256.
+        `models` as cost_fields', `start_costs` as cost_fields_seeded's.  A member inside a zone keeps its key and
+        reaches nothing; a target inside a zone is unreached.  -> cost_fields_seeded's dict plus "zones" (the m
+        float32 (Z_k, 3) arrays as solved).  The solve is retained with its zones: routes, field_reached and
+        refresh_fields answer under them."""
+        sets = list(sets_or_sources)
+        if all(np.ndim(one) == 0 for one in sets):
+            sets = [[int(v)] for v in sets]
+        each, zptr, flat = self._zone_sets("cost_fields_avoiding", zone_sets, len(sets))
+        out = self._cost_fields_from(sets, models, targets, full, budget, settle, start_costs=start_costs,
+                                     zones=(zptr, flat))
+        out["zones"] = each
+        return out
+
+    def plan_avoiding(self, start_xy, goal_xy, zone_sets, model=None, early_exit=True):
+        """The same start-to-goal query under several keep-out zone sets -- the route if A is closed, if B is closed,
+        if both are: one field per zone set of `zone_sets` (a list of (Z, 3) arrays; None or (0, 3): no zones) from
+        the node planSafePath starts from for `start_xy`, in ONE solve under `model` (None, a safety factor or
+        (safety_factor, max_risk)), the goal resolved to a node as plan_many resolves it, the routes walked on the
+        device.  early_exit: every field stops once the goal is settled in it (settle "any"); the result is the same.
+        More than TRG_FIELD_BATCH_MAX zone sets run in chunks.  -> one dict per zone set: "zones" (Z, 3), "found"
+        (False where the zone set cuts the goal off or contains it), "ids" (int32 node ids start .. goal, empty when
+        not found), "xyz" (n, 3), "cost" (+inf when not found), "path_length", "avg_risk"."""
+        zone_sets = [self._zone_array("plan_avoiding", z) for z in zone_sets]
+        start, goal = (int(v) for v in self._resolve_nodes([np.asarray(start_xy, np.float32).reshape(2),
+                                                            np.asarray(goal_xy, np.float32).reshape(2)]))
+        out = []
+        for k0 in range(0, len(zone_sets), TRG_FIELD_BATCH_MAX):
+            part = zone_sets[k0:k0 + TRG_FIELD_BATCH_MAX]
+            r = self.cost_fields_avoiding([start] * len(part), part, models=None if model is None else [model] * len(part),
+                                          targets=[goal], full=False, settle="any" if early_exit else None)
+            routes = self.routes(np.arange(len(part)), [goal] * len(part), hops_at=r["hops_at"][:, 0])
+            for z, (ids, xyz, one) in zip(part, routes):
+                out.append({"zones": z, "found": one.num_nodes > 0, "ids": ids, "xyz": xyz, "cost": float(one.cost),
+                            "path_length": float(one.path_length), "avg_risk": float(one.avg_risk)})
+        return out
+
+    def _cost_fields_from(self, sets, models, targets, full, budget, settle, start_costs=None, zones=None):
         sets, ptr, ids, starts, c0 = pack_sets("cost_fields_from", sets, start_costs, who_starts="cost_fields_seeded")
         m = len(sets)
         marr, pairs = (None, None) if models is None else self._models("cost_fields_from_models", models, m)
@@ -1284,7 +1381,15 @@ class Engine:
         info = TrgFieldInfo()
         tail = [_i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
                 _i(owned), a["reached"], a["bound"], C.byref(info)]
-        if c0 is not None:
+        if zones is not None:  # (zptr int32 (m + 1), the (n, 3) float32 rows)
+            self._chk(self.L.trg_engine_cost_field_zones(
+                self.h, m, marr, _i(zones[0]), zones[1].ctypes.data_as(C.POINTER(TrgZone)), *tail[:2],
+                None if c0 is None else _f(c0), *tail[2:]))
+            if c0 is not None:
+                out["start_costs"] = starts
+            if marr is not None:
+                out["models"] = pairs
+        elif c0 is not None:
             self._chk(self.L.trg_engine_cost_field_seeded(self.h, m, marr, *tail[:2], _f(c0), *tail[2:]))
             out["start_costs"] = starts
             if marr is not None:
