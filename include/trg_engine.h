@@ -658,6 +658,35 @@ TrgStatus trg_engine_risk_field_sets(
     const int32_t *targets, int32_t n_targets,
     float *risk_at, int32_t *hops_at, int32_t *owner_at,           /* m x n_targets, any may be NULL */
     int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info);
+/* Keep-out zones on risk fields ("Keep-out zones on risk fields"): trg_engine_risk_field_sets
+ * with, per field, a list of discs that the field's walks avoid -- the safest way round a closure.  The zone lists
+ * and the rule that closes an edge are trg_engine_cost_field_zones' (above), unchanged: an edge is RELAXABLE FOR FIELD
+ * k iff it is relaxable in a risk field (its col a node, and not Invalid) and zone set k does not close it; its risk
+ * is r[e] = weight[e] + 0.0f as ever.
+ * Field k is, bit for bit, the field trg_engine_risk_field_sets computes on the graph without the edges that zone set
+ * k closes, CSR order otherwise kept: risk bits, hops, parents, owners, owned, the target reads, budgets and both
+ * settle modes, bound_out and reached_out.  Set members are exempt as they are from the Invalid rule: a member inside
+ * a zone keeps its key (+0, 0) and reaches nothing; a target inside a zone is unreached.  zone_ptr == NULL, or an
+ * empty list for a field, is trg_engine_risk_field_sets on every output bit.  The bad-weight flag stays over ALL
+ * edges: a closed edge with a NaN weight still refuses the solve.  The bucket width's edge statistics are over
+ * relaxable, unclosed edges.
+ * The solve is retained with its zone lists: trg_engine_field_routes (a route edge is the relaxable, unclosed, tight
+ * edge of least CSR index) and trg_engine_field_reached answer from it, and trg_engine_risk_field_refresh derives the
+ * closures again on the updated graph and its positions -- bit for bit the fresh zoned risk solve there, a node that
+ * the update moved into a zone shut; bounded solves stay refused by it.  Edge risks are cached per distinct zone list
+ * (as bytes) and graph, beside the edge costs.
+ * TRG_ERR_INVALID_ARG, the message starting "risk field zones:", for what trg_engine_cost_field_zones refuses in a
+ * zone or a zone_ptr; everything else as trg_engine_risk_field_sets. */
+TrgStatus trg_engine_risk_field_zones(
+    TrgEngine *e, int32_t m,
+    const int32_t *zone_ptr,     /* m + 1 offsets into zones, or NULL: no zones */
+    const TrgZone *zones,        /* zone_ptr[m] */
+    const int32_t *set_ptr, const int32_t *set_ids,
+    const float *budget, int32_t settle,
+    float *risk, int32_t *hops, int32_t *parent, int32_t *owner,
+    const int32_t *targets, int32_t n_targets,
+    float *risk_at, int32_t *hops_at, int32_t *owner_at,
+    int32_t *owned, int32_t *reached_out, float *bound_out, TrgFieldInfo *info);
 /* The nodes of field `field` (0 .. m-1) of the retained solve that have a key, compacted on the device: their
  * ids in ascending order with cost and hops, so that a bounded field that reaches few nodes is read without
  * copying anything of num_nodes entries.  *n_out is always the full count; node_ids, cost and hops (room for cap
@@ -741,7 +770,8 @@ TrgStatus trg_engine_cost_field_refresh(TrgEngine *e,
  * graph.  The differences: risk / risk_at are risks; a retained COST solve is refused (TRG_ERR_INVALID_ARG, the
  * message names trg_engine_cost_field_refresh) and left answering, as that call refuses a risk solve; and an edge
  * weight of the current graph that is NaN, negative or infinite is TRG_ERR_INVALID_ARG as in a fresh risk solve --
- * found after the retained solve is gone, so nothing is retained afterwards. */
+ * found after the retained solve is gone, so nothing is retained afterwards.  A solve of
+ * trg_engine_risk_field_zones is refreshed under its zone lists, which the retained solve carries. */
 TrgStatus trg_engine_risk_field_refresh(TrgEngine *e,
     const int32_t *new2old, int32_t n_map,
     float *risk, int32_t *hops, int32_t *parent,

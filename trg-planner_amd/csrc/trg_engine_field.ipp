@@ -40,7 +40,7 @@ struct FieldBufs {
     bool bad;                    // some edge cost is negative or not finite
     uint64_t used;               // ec_tick of the last solve that read it
     // the keep-out zones of the slot ("Keep-out zones"), part of its identity, compared as bytes;
-    // empty: a slot of the model alone (slot 0 and the risk slot always are)
+    // empty: a slot of the model, or of the edge risks, alone (slot 0 always is)
     std::vector<TrgZone> zones;
   };
   std::vector<CostSlot> slots;
@@ -135,8 +135,8 @@ struct FieldRequest {
   int32_t *owned;     // set_ptr[m]
   // a cost model per field (trg_engine_cost_field_models), or nullptr: the engine's for every field
   const TrgFieldModel *models;  // m
-  // a keep-out zone list per field (trg_engine_cost_field_zones): field k's is zones[zone_ptr[k] .. zone_ptr[k + 1]),
-  // or nullptr: none
+  // a keep-out zone list per field (trg_engine_cost_field_zones, trg_engine_risk_field_zones): field k's is
+  // zones[zone_ptr[k] .. zone_ptr[k + 1]), or nullptr: none
   const int32_t *zone_ptr;  // m + 1
   const TrgZone *zones;
   // a refresh (trg_engine_cost_field_refresh): m and the sources or sets are the retained solve's, filled in by
@@ -428,8 +428,8 @@ TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
   for (int k = 0; k < m; ++k) {
     uint32_t sfb = run.rq.models ? float_bits(run.rq.models[k].safety_factor) : sf0;
     uint32_t taub = run.rq.models ? float_bits(run.rq.models[k].max_weight) : FIELD_INF_BITS;
-    if (run.rq.risk) sfb = taub = FIELD_RISK_SLOT;  // (every field of a risk solve reads the edge risks)
-    // (a risk solve has no zone lists: the zone entry is a cost entry)
+    // (every field of a risk solve reads edge risks: those of its zone list, trg_engine_risk_field_zones)
+    if (run.rq.risk) sfb = taub = FIELD_RISK_SLOT;
     const TrgZone *zk = run.rq.zone_ptr ? run.rq.zones + run.rq.zone_ptr[k] : nullptr;
     const size_t nzk = run.rq.zone_ptr ? (size_t)(run.rq.zone_ptr[k + 1] - run.rq.zone_ptr[k]) : 0;
     int slot = -1;
@@ -474,11 +474,18 @@ TrgStatus field_edge_costs(TrgEngine *e, FieldRun &run) {
     for (size_t j = 0; j < fresh.size(); ++j) {
       const FieldBufs::CostSlot &cs = fb.slots[fresh[j]];
       float *slot = fb.ec.as<float>() + (size_t)fresh[j] * stride;
-      if (cs.sf_bits == FIELD_RISK_SLOT && cs.tau_bits == FIELD_RISK_SLOT) {
-        launch_field_edge_risk(G.col, G.w, G.state, run.F.V, G.E, slot, d_stats + j, s);
-      } else if (!cs.zones.empty()) {
-        FieldZone *d_zones = fb.zones.as<FieldZone>() + j * FIELD_ZONES_MAX;
+      const bool risk_slot = cs.sf_bits == FIELD_RISK_SLOT && cs.tau_bits == FIELD_RISK_SLOT;
+      FieldZone *d_zones = nullptr;
+      if (!cs.zones.empty()) {
+        d_zones = fb.zones.as<FieldZone>() + j * FIELD_ZONES_MAX;
         HIPCHK(e, hipMemcpyAsync(d_zones, cs.zones.data(), cs.zones.size() * sizeof(FieldZone), hipMemcpyHostToDevice, s));
+      }
+      if (risk_slot && d_zones) {
+        launch_field_edge_risk_zones(G.rowptr, G.col, G.w, G.state, G.xyz, run.F.V, G.E, d_zones, (int)cs.zones.size(),
+                                     slot, d_stats + j, s);
+      } else if (risk_slot) {
+        launch_field_edge_risk(G.col, G.w, G.state, run.F.V, G.E, slot, d_stats + j, s);
+      } else if (d_zones) {
         launch_field_edge_zones(G.rowptr, G.col, G.w, G.dist, G.state, G.xyz, run.F.V, G.E, bits_float(cs.sf_bits),
                                 bits_float(cs.tau_bits), d_zones, (int)cs.zones.size(), slot, d_stats + j, s);
       } else
@@ -1090,10 +1097,12 @@ TrgStatus cost_field_bounded(TrgEngine *e, int32_t m, const int32_t *source_ids,
   return field_solve(e, rq, out);
 }
 
-// the zone-list checks of trg_engine_cost_field_zones (zone_sets.h); a null zone_ptr: no lists
-TrgStatus field_check_zones(TrgEngine *e, int32_t m, const int32_t *zone_ptr, const TrgZone *zones) {
+// the zone-list checks of trg_engine_cost_field_zones and trg_engine_risk_field_zones (zone_sets.h), under the name
+// of the caller; a null zone_ptr: no lists
+TrgStatus field_check_zones(TrgEngine *e, const char *who, int32_t m, const int32_t *zone_ptr, const TrgZone *zones) {
   std::string why;
-  if (zone_ptr && !zone_sets_check(m, zone_ptr, zones, why)) return e->fail(TRG_ERR_INVALID_ARG, "cost field zones: " + why);
+  if (zone_ptr && !zone_sets_check(m, zone_ptr, zones, why))
+    return e->fail(TRG_ERR_INVALID_ARG, std::string(who) + ": " + why);
   return TRG_OK;
 }
 
@@ -1108,7 +1117,7 @@ TrgStatus cost_field_models(TrgEngine *e, int32_t m, const TrgFieldModel *models
   if (const TrgStatus st = field_check_shape(e, "cost field sets", "sets", m, n_targets, no_sets); st != TRG_OK)
     return st;
   if (const TrgStatus st = field_check_models(e, m, models); st != TRG_OK) return st;
-  if (const TrgStatus st = field_check_zones(e, m, zone_ptr, zones); st != TRG_OK) return st;
+  if (const TrgStatus st = field_check_zones(e, "cost field zones", m, zone_ptr, zones); st != TRG_OK) return st;
   if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
   FieldRequest rq = field_request(m, cost, hops, parent, targets, n_targets, cost_at, hops_at, reached_out);
   rq.budget = budget;
@@ -1123,6 +1132,32 @@ TrgStatus cost_field_models(TrgEngine *e, int32_t m, const TrgFieldModel *models
   rq.models = models;
   rq.zone_ptr = zone_ptr;
   rq.zones = zones;
+  return field_solve(e, rq, out);
+}
+
+// The solve behind trg_engine_risk_field_zones and, without zone lists, trg_engine_risk_field_sets.
+TrgStatus risk_field_sets(TrgEngine *e, int32_t m, const int32_t *zone_ptr, const TrgZone *zones,
+                          const int32_t *set_ptr, const int32_t *set_ids, const float *budget, int32_t settle,
+                          float *risk, int32_t *hops, int32_t *parent, int32_t *owner, const int32_t *targets,
+                          int32_t n_targets, float *risk_at, int32_t *hops_at, int32_t *owner_at, int32_t *owned,
+                          int32_t *reached_out, float *bound_out, TrgFieldInfo *out) {
+  const char *no_sets = !set_ptr || !set_ids ? "null set_ptr or set_ids" : nullptr;
+  if (const TrgStatus st = field_check_shape(e, "risk field sets", "sets", m, n_targets, no_sets); st != TRG_OK)
+    return st;
+  if (const TrgStatus st = field_check_zones(e, "risk field zones", m, zone_ptr, zones); st != TRG_OK) return st;
+  if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
+  FieldRequest rq = field_request(m, risk, hops, parent, targets, n_targets, risk_at, hops_at, reached_out);
+  rq.budget = budget;
+  rq.settle = settle;
+  rq.bound_out = bound_out;
+  rq.set_ptr = set_ptr;
+  rq.set_ids = set_ids;
+  rq.owner = owner;
+  rq.owner_at = owner_at;
+  rq.owned = owned;
+  rq.zone_ptr = zone_ptr;
+  rq.zones = zones;
+  rq.risk = true;
   return field_solve(e, rq, out);
 }
 
@@ -1262,21 +1297,20 @@ TrgStatus trg_engine_risk_field_sets(TrgEngine *e, int32_t m, const int32_t *set
                                      int32_t *hops_at, int32_t *owner_at, int32_t *owned, int32_t *reached_out,
                                      float *bound_out, TrgFieldInfo *info) {
   return field_entry(e, info, "risk field sets", [&](TrgFieldInfo *out) {
-    const char *no_sets = !set_ptr || !set_ids ? "null set_ptr or set_ids" : nullptr;
-    if (const TrgStatus st = field_check_shape(e, "risk field sets", "sets", m, n_targets, no_sets); st != TRG_OK)
-      return st;
-    if (const TrgStatus st = field_check_bounds(e, m, budget, settle, targets, n_targets); st != TRG_OK) return st;
-    FieldRequest rq = field_request(m, risk, hops, parent, targets, n_targets, risk_at, hops_at, reached_out);
-    rq.budget = budget;
-    rq.settle = settle;
-    rq.bound_out = bound_out;
-    rq.set_ptr = set_ptr;
-    rq.set_ids = set_ids;
-    rq.owner = owner;
-    rq.owner_at = owner_at;
-    rq.owned = owned;
-    rq.risk = true;
-    return field_solve(e, rq, out);
+    return risk_field_sets(e, m, nullptr, nullptr, set_ptr, set_ids, budget, settle, risk, hops, parent, owner, targets,
+                           n_targets, risk_at, hops_at, owner_at, owned, reached_out, bound_out, out);
+  });
+}
+
+TrgStatus trg_engine_risk_field_zones(TrgEngine *e, int32_t m, const int32_t *zone_ptr, const TrgZone *zones,
+                                      const int32_t *set_ptr, const int32_t *set_ids, const float *budget,
+                                      int32_t settle, float *risk, int32_t *hops, int32_t *parent, int32_t *owner,
+                                      const int32_t *targets, int32_t n_targets, float *risk_at, int32_t *hops_at,
+                                      int32_t *owner_at, int32_t *owned, int32_t *reached_out, float *bound_out,
+                                      TrgFieldInfo *info) {
+  return field_entry(e, info, "risk field zones", [&](TrgFieldInfo *out) {
+    return risk_field_sets(e, m, zone_ptr, zones, set_ptr, set_ids, budget, settle, risk, hops, parent, owner, targets,
+                           n_targets, risk_at, hops_at, owner_at, owned, reached_out, bound_out, out);
   });
 }
 

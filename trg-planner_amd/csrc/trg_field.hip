@@ -66,15 +66,18 @@
 //
 // Keep-out zones ("Keep-out zones"): a field may also refuse edges by place -- every edge that a
 // disc of its zone set touches.  That is one more reason for the skip marker in a slot, decided by k_field_edge_zones
-// (near the end of this file) where k_field_edge_cost decides by weight; every kernel that reads a slot is unchanged.
+// (near the end of this file) where k_field_edge_cost decides by weight, and by k_field_edge_risk_zones for a slot of
+// edge risks; every kernel that reads a slot is unchanged.
 //
 // Risk fields ("Risk fields"): the least, over all walks, of the GREATEST edge weight on the walk.
 // The extension is (max(risk, r), hops + 1) with r = w + 0 -- monotone in the risk word and never below it, which is
 // all the argument above asks of fl(a + c), and it never rounds.  The hop word is no more monotone than under
 // rounding (a < a' gives max(a, r) == max(a', r) for every r >= a'), so the two passes stay.  The kernels that read an
 // edge value (relax, parent sweep, route walk, warm seed) have a RISK instantiation whose only difference is that
-// extension; it never combines with MODELS (a risk solve has no cost model).  The edge risks lie in a slot of the
-// edge-cost array (k_field_edge_risk); every kernel that looks at cost bits only is used as it is.  A risk solve is
+// extension.  The edge risks lie in a slot of the edge-cost array (k_field_edge_risk); every kernel that looks at cost
+// bits only is used as it is.  RISK combines with MODELS where the fields of a risk solve read different slots: a risk
+// solve has no cost model, but its fields may avoid different keep-out zones ("Keep-out zones on
+// risk fields"; k_field_edge_risk_zones fills such a slot), and the slot table is the same.  A risk solve is
 // refreshed by the steps of the cost refresh ("Risk fields"): carry, anchors, warm init, rounds
 // and finish look at key bits only or have their RISK form, and the RISK warm seed queues by the maximum.  A bucket
 // width of 0 (all-zero weights) takes the warm control block, which starts at threshold 0, down the path of a cold one:
@@ -276,11 +279,11 @@ __global__ __launch_bounds__(THREADS) void k_field_init(FieldDev F, FieldSources
 // BOUNDED: pass 1 of a bounded solve -- an item above its field's bound is not expanded (it was queued before the
 // settle step lowered the bound), an extension above the bound is neither written nor pushed.
 // MODELS (with MULTI): the edge costs are those of the item's field.
-// RISK (never with MODELS): a risk field -- F.ec holds the edge risks, the extension is the maximum.
+// RISK: a risk field -- the slot holds edge risks, the extension is the maximum; with MODELS, fields under different
+// keep-out zone lists.
 template <bool MULTI, bool BOUNDED, bool MODELS, bool RISK = false>
 __global__ __launch_bounds__(THREADS) void k_field_relax(FieldDev F, int par, int stamp, FieldModelsArg<MODELS> M) {
   static_assert(MULTI || !MODELS, "one field has one model: the host points F.ec at its slot");
-  static_assert(!(RISK && MODELS), "a risk field has no cost model");
   const int N = MULTI ? F.N : F.V;
   const int n = min(F.ctrl->c.n[par], N);  // (past N only after an overflow, which the host then reports)
   if (n == 0) return;
@@ -556,7 +559,6 @@ __global__ __launch_bounds__(THREADS) void k_field_list_emit(FieldDev F, int fie
 // Parents: the smallest u with an edge u -> v whose extension of key[u] is key[v], in each field (grid.y).
 template <bool MODELS, bool RISK = false>
 __global__ __launch_bounds__(THREADS) void k_field_parent(FieldDev F, FieldModelsArg<MODELS> M) {
-  static_assert(!(RISK && MODELS), "a risk field has no cost model");
   const float *__restrict__ ec = field_costs<MODELS>(F, M, blockIdx.y);
   const int sub = threadIdx.x & (GROUP - 1);
   const int g0 = (blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
@@ -644,8 +646,9 @@ __global__ __launch_bounds__(THREADS) void k_field_route_len(FieldDev F, const i
 // host turns into an error, instead of a route that looks right.
 // Where it must end is all that SETS changes: at the field's source S.id[field], or, for a set solve (S its sets,
 // the owner pass has run), at the member that owns the target, ids[ptr[field] + owner[target]].  The single-source
-// instantiation has no owner array to read.  MODELS: the edge costs are those of the route's field.  RISK (never with
-// MODELS): the retained solve is a risk solve -- the matching extension is the maximum, `cost` the risk word.
+// instantiation has no owner array to read.  MODELS: the edge costs are those of the route's field.  RISK (with
+// MODELS: under a zone list per field): the retained solve is a risk solve -- the matching extension is the maximum,
+// `cost` the risk word.
 template <bool SETS, bool MODELS, bool RISK = false>
 __global__ __launch_bounds__(THREADS) void k_field_route_walk(FieldDev F, const float *__restrict__ w,
                                                               const float *__restrict__ dist,
@@ -908,7 +911,6 @@ __global__ __launch_bounds__(THREADS) void k_field_warm_init(FieldDev F, float d
 template <bool MULTI, bool TIGHT, bool MODELS, bool RISK = false>
 __global__ __launch_bounds__(THREADS) void k_field_warm_seed(FieldDev F, FieldModelsArg<MODELS> M) {
   static_assert(MULTI || !MODELS, "one field has one model: the host points F.ec at its slot");
-  static_assert(!(RISK && MODELS), "a risk field has no cost model");
   const int N = MULTI ? F.N : F.V;
   const int sub = threadIdx.x & (GROUP - 1);
   const int gw = lane_id() / GROUP;
@@ -976,6 +978,9 @@ void field_round(const FieldDev &F, int round, const FieldSettle *settle, const 
   if (risk && F.m == 1)
     hipLaunchKernelGGL((k_field_relax<false, BOUNDED, false, true>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1,
                        FieldNoModels{});
+  else if (risk && models)
+    hipLaunchKernelGGL((k_field_relax<true, BOUNDED, true, true>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1,
+                       *models);
   else if (risk)
     hipLaunchKernelGGL((k_field_relax<true, BOUNDED, false, true>), relax_grid, dim3(THREADS), 0, s, F, par, round + 1,
                        FieldNoModels{});
@@ -1102,6 +1107,50 @@ __global__ __launch_bounds__(THREADS) void k_field_edge_zones(
   }
 }
 
+// k_field_edge_risk for a slot with a zone set ("Keep-out zones on risk fields"): er[k] is what
+// that kernel writes, or the skip marker where the set closes the edge; the sum and count over relaxable, unclosed
+// edges, `bad` over ALL edges.  The row walk of k_field_edge_zones.
+__global__ __launch_bounds__(THREADS) void k_field_edge_risk_zones(
+    const int *__restrict__ rowptr, const int *__restrict__ col, const float *__restrict__ w,
+    const int *__restrict__ state, const float *__restrict__ xyz, int V, int E, const FieldZone *__restrict__ zones,
+    int nz, float *__restrict__ er, FieldEdgeStats *st) {
+  __shared__ float4 zs[FIELD_ZONES_MAX];
+  nz = zones_stage(zs, zones, nz);
+  double sum = 0.0;
+  int cnt = 0, bad = 0;
+  int first, step, lane;
+  zone_group_rows(first, step, lane);
+  for (int u = first; u < V; u += step) {
+    const int beg = max(rowptr[u], 0), end = min(rowptr[u + 1], E);
+    for (int k = beg + lane; k < end; k += GROUP) {
+      const float r = w[k] + 0.0f;
+      if (!(r >= 0.0f) || r == __builtin_huge_valf()) bad = 1;
+      const int v = col[k];
+      bool skip = v < 0 || v >= V;
+      if (!skip) skip = state[v] == FIELD_NODE_INVALID;
+      if (!skip) skip = zones_close_edge(zs, nz, xyz, u, v);
+      er[k] = skip ? __uint_as_float(FIELD_EDGE_SKIP) : r;
+      if (!skip) {
+        sum += (double)r;
+        cnt++;
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    sum += __shfl_xor(sum, m);
+    cnt += __shfl_xor(cnt, m);
+    bad |= __shfl_xor(bad, m);
+  }
+  if (lane_id() == 0) {
+    if (cnt) {
+      atomicAdd(&st->sum, sum);
+      atomicAdd(&st->count, cnt);
+    }
+    if (bad) atomicOr(&st->bad, 1);
+  }
+}
+
 // The verdicts of a zone set by the device function of the solve: closed per CSR edge, inside per node (either may be
 // nullptr), and their counts.  An edge whose column is no node is not closed.
 __global__ __launch_bounds__(THREADS) void k_field_zone_verdicts(
@@ -1165,6 +1214,15 @@ void launch_field_edge_zones(const int *rowptr, const int *col, const float *w, 
   if (E == 0) return;
   hipLaunchKernelGGL(k_field_edge_zones, dim3(field_blocks((long long)V * GROUP, THREADS)), dim3(THREADS), 0, s, rowptr,
                      col, w, dist, state, xyz, V, E, safety_factor, max_weight, zones, nz, ec, st);
+}
+
+void launch_field_edge_risk_zones(const int *rowptr, const int *col, const float *w, const int *state,
+                                  const float *xyz, int V, int E, const FieldZone *zones, int nz, float *er,
+                                  FieldEdgeStats *st, hipStream_t s) {
+  (void)hipMemsetAsync(st, 0, sizeof(FieldEdgeStats), s);
+  if (E == 0) return;
+  hipLaunchKernelGGL(k_field_edge_risk_zones, dim3(field_blocks((long long)V * GROUP, THREADS)), dim3(THREADS), 0, s,
+                     rowptr, col, w, state, xyz, V, E, zones, nz, er, st);
 }
 
 void launch_field_zone_verdicts(const int *rowptr, const int *col, const float *xyz, int V, int E,
@@ -1249,7 +1307,13 @@ void launch_field_route_walk(const FieldDev &F, const float *w, const float *dis
                              hipStream_t s, const FieldModels *models, bool risk) {
   if (n_routes <= 0) return;
   const dim3 grid(field_blocks((long long)n_routes * GROUP, THREADS));
-  if (risk && sets)
+  if (risk && sets && models)
+    hipLaunchKernelGGL((k_field_route_walk<true, true, true>), grid, dim3(THREADS), 0, s, F, w, dist, route_field,
+                       route_target, n_routes, offsets, node_ids, infos, *sets, *models);
+  else if (risk && models)
+    hipLaunchKernelGGL((k_field_route_walk<false, true, true>), grid, dim3(THREADS), 0, s, F, w, dist, route_field,
+                       route_target, n_routes, offsets, node_ids, infos, sources, *models);
+  else if (risk && sets)
     hipLaunchKernelGGL((k_field_route_walk<true, false, true>), grid, dim3(THREADS), 0, s, F, w, dist, route_field,
                        route_target, n_routes, offsets, node_ids, infos, *sets, FieldNoModels{});
   else if (risk)
@@ -1287,7 +1351,8 @@ void launch_field_carry(const unsigned long long *old_key, int V_old, const int 
 
 void launch_field_supporters(const FieldDev &F, hipStream_t s, const FieldModels *models, bool risk) {
   const dim3 grid(field_blocks((long long)F.V * GROUP, THREADS), F.m);
-  if (risk) hipLaunchKernelGGL((k_field_parent<false, true>), grid, dim3(THREADS), 0, s, F, FieldNoModels{});
+  if (risk && models) hipLaunchKernelGGL((k_field_parent<true, true>), grid, dim3(THREADS), 0, s, F, *models);
+  else if (risk) hipLaunchKernelGGL((k_field_parent<false, true>), grid, dim3(THREADS), 0, s, F, FieldNoModels{});
   else if (models) hipLaunchKernelGGL(k_field_parent<true>, grid, dim3(THREADS), 0, s, F, *models);
   else hipLaunchKernelGGL(k_field_parent<false>, grid, dim3(THREADS), 0, s, F, FieldNoModels{});
 }
@@ -1314,6 +1379,9 @@ void launch_field_warm_start(const FieldDev &F, float delta, bool reset_parents,
   if (risk && F.m == 1) {
     if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<false, true, false, true>), grid, dim3(THREADS), 0, s, F, none);
     else hipLaunchKernelGGL((k_field_warm_seed<false, false, false, true>), grid, dim3(THREADS), 0, s, F, none);
+  } else if (risk && models) {
+    if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<true, true, true, true>), grid, dim3(THREADS), 0, s, F, *models);
+    else hipLaunchKernelGGL((k_field_warm_seed<true, false, true, true>), grid, dim3(THREADS), 0, s, F, *models);
   } else if (risk) {
     if (F.tight) hipLaunchKernelGGL((k_field_warm_seed<true, true, false, true>), grid, dim3(THREADS), 0, s, F, none);
     else hipLaunchKernelGGL((k_field_warm_seed<true, false, false, true>), grid, dim3(THREADS), 0, s, F, none);

@@ -522,6 +522,12 @@ constexpr int FIELD_ZONES_MAX = 256;  // TRG_ZONES_MAX
 void launch_field_edge_zones(const int *rowptr, const int *col, const float *w, const float *dist, const int *state,
                              const float *xyz, int V, int E, float safety_factor, float max_weight,
                              const FieldZone *zones, int nz, float *ec, FieldEdgeStats *st, hipStream_t s);
+// launch_field_edge_risk for a slot with a zone set ("Keep-out zones on risk fields"): er[e] is
+// what that launch writes, or FIELD_EDGE_SKIP where the set (nz zones on the device, 1 .. FIELD_ZONES_MAX) closes edge
+// e; *st (zeroed here) over the relaxable, unclosed edges, its bad flag over all.  The row walk of the launch above.
+void launch_field_edge_risk_zones(const int *rowptr, const int *col, const float *w, const int *state,
+                                  const float *xyz, int V, int E, const FieldZone *zones, int nz, float *er,
+                                  FieldEdgeStats *st, hipStream_t s);
 // The verdicts themselves, by the same device function: closed[e] (E bytes, may be nullptr) 1 where the set closes edge
 // e, inside[v] (V bytes, may be nullptr) 1 where node v is inside a zone; counts[0] / counts[1] (zeroed here) the
 // closed edges and the inside nodes.  nz == 0: nothing is closed.

@@ -151,7 +151,7 @@ EXPORTS = [
     "trg_engine_cost_field_sets", "trg_engine_cost_field_refresh", "trg_engine_cost_field_models",
     "trg_engine_risk_field_sets", "trg_engine_risk_field_refresh",
     "trg_engine_pose_links", "trg_engine_cost_field_seeded",
-    "trg_engine_cost_field_zones", "trg_engine_zone_edges",
+    "trg_engine_cost_field_zones", "trg_engine_zone_edges", "trg_engine_risk_field_zones",
     "trg_engine_tiled_cost_field", "trg_engine_stitch_ids", "trg_engine_tiled_cost_field_sets",
     "trg_engine_tiled_field_routes", "trg_engine_tiled_risk_field", "trg_engine_tiled_risk_field_sets",
     "trg_engine_tiled_cost_field_bounded", "trg_engine_tiled_risk_field_bounded", "trg_engine_tiled_field_reached",
@@ -263,6 +263,8 @@ def load_library():
     L.trg_engine_zone_edges.argtypes = [vp, C.POINTER(TrgZone), C.c_int32, u8p, u8p, ip, ip]
     L.trg_engine_pose_links.argtypes = [vp, fp, C.c_int32, C.c_float, C.c_int32, ip, fp, fp, C.POINTER(TrgPoseInfo)]
     L.trg_engine_risk_field_sets.argtypes = L.trg_engine_cost_field_sets.argtypes
+    L.trg_engine_risk_field_zones.argtypes = [vp, C.c_int32, ip, C.POINTER(TrgZone)] + \
+        L.trg_engine_risk_field_sets.argtypes[2:]
     L.trg_engine_cost_field_refresh.argtypes = [vp, ip, C.c_int32, fp, ip, ip, ip, C.c_int32, fp, ip, ip, ip, ip, ip, ip,
                                                 C.POINTER(TrgFieldInfo)]
     L.trg_engine_risk_field_refresh.argtypes = L.trg_engine_cost_field_refresh.argtypes
@@ -1625,16 +1627,22 @@ class Engine:
         "owned" and "sets" as there, over the (risk, hops) keys."""
         return self._risk_fields_from("risk_fields_from", sets, targets, full, budget, settle, owners=True)
 
-    def _risk_fields_from(self, who, sets, targets, full, budget, settle, owners):
+    def _risk_fields_from(self, who, sets, targets, full, budget, settle, owners, zones=None):
         sets, ptr, ids, _, _ = pack_sets(who, sets)
         m = len(sets)
         out, a = self._field_outputs(who, m, targets, full, budget, settle, owners=owners)
         owned, split_owned = _owned_buffer(ptr)
         info = TrgFieldInfo()
-        self._chk(self.L.trg_engine_risk_field_sets(
-            self.h, m, _i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
-            _i(owned) if owners else None, a["reached"], a["bound"], C.byref(info)))
-        self._retain(risk=True, fields=m, sets=True, owners=owners, single=m == 1 and sets[0].shape[0] == 1)
+        tail = [_i(ptr), _i(ids), a["budget"], _SETTLE[settle], *a["full"], a["owner"], *a["at"], a["owner_at"],
+                _i(owned) if owners else None, a["reached"], a["bound"], C.byref(info)]
+        if zones is not None:  # (zptr int32 (m + 1) or None: a null zone_ptr, the (n, 3) float32 rows)
+            self._chk(self.L.trg_engine_risk_field_zones(self.h, m, None if zones[0] is None else _i(zones[0]),
+                                                         zones[1].ctypes.data_as(C.POINTER(TrgZone)), *tail))
+        else:
+            self._chk(self.L.trg_engine_risk_field_sets(self.h, m, *tail))
+        # (`single` is what frontier_ceilings' reuse asks for: a zoned solve, whose refresh stays zoned, is not that)
+        self._retain(risk=True, fields=m, sets=True, owners=owners,
+                     single=m == 1 and sets[0].shape[0] == 1 and (zones is None or zones[1].shape[0] == 0))
         _as_risk(out)
         if owners:
             out["owned"] = split_owned()
@@ -1664,6 +1672,81 @@ class Engine:
         route = self.routes([0], [goal], hops_at=r["hops_at"][:, 0])[0]
         return tau, self._route_record(r["models"][0], *route)
 
+    def risk_fields_avoiding(self, sets_or_sources, zone_sets, targets=None, full=True, budget=None, settle=None):
+        """Risk fields that avoid keep-out zones (trg_engine_risk_field_zones; DESIGN.md section 2, "Keep-out zones on
+        risk fields"): risk_fields_from on the graph without the edges that field k's zone set closes -- the least
+        worst-edge risk of the walks that stay out of the zones; the graph itself is left as it is.  `sets_or_sources`
+        and `zone_sets` as cost_fields_avoiding's: m sets of node ids or a flat list of ids; one (Z, 3) array of
+        (x, y, r) rows for all fields (they then share one slot of edge risks, the cheap case) or a list with one per
+        field; None or (0, 3) means no zones, Z <= 256.  A member inside a zone keeps risk 0 and reaches nothing; a
+        target inside a zone is unreached.  -> risk_fields_from's dict plus "zones" (the m float32 (Z_k, 3) arrays as
+        solved).  The solve is retained with its zones: routes, field_reached and refresh_risk_fields answer under
+        them."""
+        return self._risk_fields_avoiding("risk_fields_avoiding", sets_or_sources, zone_sets, targets, full, budget,
+                                          settle, owners=True)
+
+    def _risk_fields_avoiding(self, who, sets_or_sources, zone_sets, targets, full, budget, settle, owners):
+        """risk_fields_avoiding for `who`; owners=False (sets of one, which own all they reach): no owner pass and no
+        owner keys in the dict, as risk_fields has it."""
+        sets = list(sets_or_sources)
+        if all(np.ndim(one) == 0 for one in sets):
+            sets = [[int(v)] for v in sets]
+        each, zptr, flat = self._zone_sets(who, zone_sets, len(sets))
+        out = self._risk_fields_from(who, sets, targets, full, budget, settle, owners=owners,
+                                     zones=(None if zone_sets is None else zptr, flat))
+        out["zones"] = each
+        return out
+
+    def safest_route_avoiding(self, start_xy, goal_xy, zone_sets):
+        """safest_route under several keep-out zone sets -- the safest route if A is closed, if B is closed, if both
+        are (`zone_sets`: a list of (Z, 3) arrays; None or (0, 3): no zones): ONE zoned risk solve of one field per zone
+        set from the start node, settled at the goal (field k's risk there is its least ceiling), then ONE
+        cost_fields_avoiding solve under (the engine's safety factor, that ceiling) and the same zone sets, and one
+        routes call.  More than TRG_FIELD_BATCH_MAX zone sets run in chunks.  -> one entry per zone set: (max_risk,
+        route dict as plan_tradeoff's), or None where the zone set cuts the goal off or contains it.  With one empty
+        zone set the entry equals safest_route's result."""
+        zone_sets = [self._zone_array("safest_route_avoiding", z) for z in zone_sets]
+        start, goal = (int(v) for v in self._resolve_nodes([np.asarray(start_xy, np.float32).reshape(2),
+                                                            np.asarray(goal_xy, np.float32).reshape(2)]))
+        out = []
+        for k0 in range(0, len(zone_sets), TRG_FIELD_BATCH_MAX):
+            part = zone_sets[k0:k0 + TRG_FIELD_BATCH_MAX]
+            r = self._risk_fields_avoiding("safest_route_avoiding", [start] * len(part), part, [goal], False, None,
+                                           "any", owners=False)
+            found = r["hops_at"][:, 0] >= 0
+            if not found.any():
+                out += [None] * len(part)
+                continue
+            # (a field that does not reach the goal gets no ceiling: it does not reach it under any)
+            taus = [float(t) if ok else np.inf for t, ok in zip(r["risk_at"][:, 0], found)]
+            r = self.cost_fields_avoiding([start] * len(part), part, targets=[goal], full=False, settle="any",
+                                          models=[(self.params.safety_factor, tau) for tau in taus])
+            routes = self.routes(np.arange(len(part)), [goal] * len(part), hops_at=r["hops_at"][:, 0])
+            out += [(taus[k], self._route_record(r["models"][k], *routes[k])) if found[k] else None
+                    for k in range(len(part))]
+        return out
+
+    def frontier_ceilings_avoiding(self, pose_xy, zones):
+        """frontier_ceilings under one keep-out zone set (`zones`: (Z, 3) rows (x, y, r); None or (0, 3): no zones): one
+        zoned risk field from `pose_xy`, read at the Frontier nodes on the device -> (frontier ids int32 ascending,
+        risk float32 (+inf: unreachable or inside a zone), hops int32 (-1 there))."""
+        frontier = self._frontier_ids()
+        node = int(self._resolve_nodes(np.asarray(pose_xy, np.float32).reshape(1, 2))[0])
+        r = self._risk_fields_avoiding("frontier_ceilings_avoiding", [node],
+                                       self._zone_array("frontier_ceilings_avoiding", zones), frontier, False, None,
+                                       None, owners=False)
+        return frontier, r["risk_at"][0], r["hops_at"][0]
+
+    def safest_frontier_avoiding(self, pose_xy, zones):
+        """safest_frontier under one keep-out zone set: the least (risk, hops, id) among the Frontier nodes reachable
+        without entering a zone, with its route -> (node, risk, path ids), or None without a reachable one."""
+        frontier, risk, hops = self.frontier_ceilings_avoiding(pose_xy, zones)
+        pick = choose_frontier(frontier, risk, hops)
+        if pick is None:
+            return None
+        ids, _, _ = self.routes([0], [pick[0]], xyz=False, hops_at=[hops[pick[1]]])[0]
+        return pick[0], float(risk[pick[1]]), ids.tolist()
+
     def refresh_risk_fields(self, new2old=None, targets=None, full=True):
         """refresh_fields for a retained RISK solve (risk_fields or risk_fields_from before the last update_graph
         calls): trg_engine_risk_field_refresh, DESIGN.md section 2, "Risk fields".  The result is that of a fresh risk
@@ -1673,7 +1756,9 @@ class Engine:
         the retained solve came from risk_fields_from.  A retained cost solve is refused (refresh_fields is its call),
         as are a bounded risk solve and one that is already current; a refused call leaves the retained solve answering.
         A NaN, negative or infinite weight on the current graph raises as in risk_fields, and nothing is retained
-        afterwards.  Afterwards routes and field_reached answer from the refreshed solve."""
+        afterwards.  Afterwards routes and field_reached answer from the refreshed solve.  A solve of
+        risk_fields_avoiding carries its zone sets: the result is the fresh zoned solve's on the current graph, a node
+        that the update moved into a zone shut."""
         return _as_risk(self._refresh(self.L.trg_engine_risk_field_refresh, "refresh_risk_fields", new2old, targets,
                                       full))
 
